@@ -29,6 +29,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "qwen3-tts-rust_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import synth_models  # noqa: E402  (seeded synthetic weights, cached per user outside the checkout)
 
 FRAME_SEC = 1920.0 / 24000.0  # 12.5 Hz codec frames [EXT]
 HBM_PEAK_GBS = 8000.0         # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
@@ -49,7 +51,7 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c5"], help="timed workload (BASELINE.json configs[1] / [2] / [4])")
     ap.add_argument("--quant", default=None, help="weights: q8_0 (default), q5_k_m, bf16 (default for c5)")
-    ap.add_argument("--model-dir", default=os.environ.get("Q3_BENCH_MODEL", "/tmp/q3tts_synth_full"))
+    ap.add_argument("--model-dir", default=os.environ.get("Q3_BENCH_MODEL"), help="default: the seeded full-size model in this user's cache")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-codec", action="store_true")
     ap.add_argument("--no-c2-leg", action="store_true", help="skip the single-utterance latency leg that rides along with c3 / c5")
@@ -58,14 +60,25 @@ def parse_args(argv=None):
                                                             "admitted by the continuous-batching scheduler as slots retire")
     ap.add_argument("--clone", action="store_true", help="voice-clone prompt layout (implied by --config c5)")
     ap.add_argument("--ragged", action="store_true", help="utterance lengths 50..100 %% of 4*steps frames (slots retire at different times)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what it computed (codec tokens, PCM) "
+                                                                           "as DIR/<name>.npy, float32 / float64, at most 64 MB in all (over all ranks)")
     ap.add_argument("--stub-engine", action="store_true", help=argparse.SUPPRESS)  # CPU rehearsal of the rank logic (tests/test_dist_cpu.py)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "c5":
         args.clone = True
     if args.quant is None:
         args.quant = "bf16" if args.config == "c5" else "q8_0"
     if args.batch <= 0:
         args.batch = {"c2": 1, "c3": 64, "c5": 32}[args.config]
+    if args.dump_outputs:   # the codec tokens are always written whole: refuse before any work when they alone break the budget
+        n_req, n_fr = max(args.requests, args.batch), 4 * args.steps
+        if dump_fixed_bytes(n_req, n_fr) > DUMP_BYTES // args.gpus:
+            ap.error("--dump-outputs: the codec tokens of %d requests x %d frames on each of %d rank(s) exceed the %d MB budget"
+                     % (n_req, n_fr, args.gpus, DUMP_BYTES >> 20))
+    if args.model_dir is None:
+        args.model_dir = synth_models.model_dir("full")
     return args
 
 
@@ -110,14 +123,47 @@ def describe_ranks(dist, torch, dev, audio_s, elapsed, device_name):
 
 
 def ensure_model(model_dir, quant):
-    marker = os.path.join(model_dir, ".complete_" + quant)
-    if os.path.exists(marker):
-        return
-    tool = os.path.join(ROOT, "tools", "q3synth")
-    if not os.path.exists(tool):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    subprocess.check_call([tool, "--out", model_dir, "--preset", "full", "--quant", quant, "--seed", "1234"])
-    open(marker, "w").write("ok")
+    synth_models.full(quant, model_dir)
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs, all ranks together
+DUMP_HEADERS = 4096        # room left for the .npy headers
+
+
+def dump_fixed_bytes(n_req, max_frames):
+    """bytes of the arrays dump_outputs never samples: codes, frames, pcm_samples"""
+    return n_req * max_frames * 16 * 4 + 2 * n_req * 8 + DUMP_HEADERS
+
+
+def dump_outputs(out_dir, results, prefix="", budget=DUMP_BYTES):
+    """What the timed generate_batch call handed back to its caller, for output-for-output comparison of two builds:
+    codes.npy   [requests, max frames, 16] codec tokens (float32, exact below 2^24; -1 past a request's last frame)
+    frames.npy  [requests] frames per request (float64)
+    pcm.npy     the requests' PCM concatenated in request order (float32); when that exceeds what the budget leaves, a fixed
+                seeded sample of it, sorted, with pcm_index.npy (float64) = the sample's positions in the concatenation
+    pcm_samples.npy  [requests] PCM samples per request (float64)
+    Everything stays within `budget` bytes; the caller refuses shapes whose codes alone would not fit (dump_fixed_bytes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    frames = np.array([r["codes"].shape[0] for r in results], np.float64)
+    codes = np.full((len(results), int(frames.max()), 16), -1.0, np.float32)
+    for i, r in enumerate(results):
+        codes[i, : r["codes"].shape[0]] = r["codes"]
+    arrays = {"codes": codes, "frames": frames}
+    if dump_fixed_bytes(len(results), codes.shape[1]) > budget:
+        raise ValueError("dump_outputs: %d requests x %d frames of codes exceed the %d-byte budget" % (len(results), codes.shape[1], budget))
+    if all(r["pcm"] is not None for r in results):
+        pcm = np.concatenate([r["pcm"] for r in results]).astype(np.float32)
+        arrays["pcm_samples"] = np.array([r["pcm"].size for r in results], np.float64)
+        room = budget - sum(a.nbytes for a in arrays.values()) - DUMP_HEADERS
+        if pcm.nbytes > room:
+            n = room // (4 + 8)                                             # float32 value + float64 position per sampled sample
+            idx = np.sort(np.random.default_rng(0).choice(pcm.size, size=n, replace=False))
+            arrays["pcm_index"] = idx.astype(np.float64)
+            pcm = pcm[idx]
+        arrays["pcm"] = pcm
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    return sorted(arrays)
 
 
 def build_prompt(assets, spk_emb, n_text=32, seed=42):
@@ -372,6 +418,7 @@ def main(argv=None):
         if args.ragged and len(plist) > 1:
             ms = [max(1, int(4 * steps * (0.5 + 0.5 * ((i * 7) % 11) / 10.0))) for i in range(len(plist))]
         res = engine.generate_batch(plist, max_steps=ms, temperature=0.0, seed=42, mask_eos=True, want_pcm=pcm)
+        last_run["results"] = res
         last_run["frames"] = sum(r["codes"].shape[0] for r in res)
         last_run["first_chunk"] = [r["first_chunk_ms"] for r in res]
         assert all(r["codes"].shape[0] == m for r, m in zip(res, ms)), "EOS-masked runs must emit exactly max_steps frames"
@@ -398,6 +445,10 @@ def main(argv=None):
     log("timed region done: %.3f s (this rank %.3f s, %.1f audio-s)" % (elapsed, elapsed_local, audio_local))
     n_frames = res["codes"].shape[0]
     timed_first_chunk = list(last_run["first_chunk"])
+    if args.dump_outputs:
+        # every rank writes its own results under its own prefix, in an equal share of the budget
+        names = dump_outputs(args.dump_outputs, last_run["results"], "" if world == 1 else "rank%d_" % rank, DUMP_BYTES // world)
+        log("timed outputs written to %s: %s" % (args.dump_outputs, ", ".join(names)))
 
     if rank == 0:
         frame_ms = st["frame_loop_ms"] / max(st["graph_frames"], 1)   # one graph replay advances every active slot by a frame

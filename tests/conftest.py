@@ -15,10 +15,6 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
-def _run(cmd):
-    subprocess.check_call(cmd)
-
-
 @pytest.fixture(scope="session")
 def oracle():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
@@ -36,12 +32,11 @@ def synth_tool():
 @pytest.fixture(scope="session")
 def tiny_model(synth_tool):
     """Seeded tiny 'Q3TTS-synth' model (talker d=2048 L=2, predictor d=256 L=2, small codec), Q8_0 + Q5_K_M + f32."""
-    out = os.environ.get("Q3_TINY_MODEL", "/tmp/q3tts_pytest_tiny")
-    if not os.path.exists(os.path.join(out, ".complete3")):
-        _run([synth_tool, "--out", out, "--preset", "tiny", "--quant", "q8_0"])
-        _run([synth_tool, "--out", out, "--preset", "tiny", "--quant", "q5_k_m", "--what", "3"])
-        _run([synth_tool, "--out", out, "--preset", "tiny", "--quant", "bf16", "--what", "3"])
-        open(os.path.join(out, ".complete3"), "w").write("ok")
+    import synth_models
+    out = os.environ.get("Q3_TINY_MODEL", synth_models.model_dir("pytest_tiny"))
+    synth_models.ensure(out, [["--preset", "tiny", "--quant", "q8_0"],
+                              ["--preset", "tiny", "--quant", "q5_k_m", "--what", "3"],
+                              ["--preset", "tiny", "--quant", "bf16", "--what", "3"]])
     for sub in ("gguf_q5_k_m", "gguf_bf16"):   # the assets file is F32 in every quantisation directory (assets_manager.rs:163-167)
         dst = os.path.join(out, sub, "qwen3_assets.gguf")
         if not os.path.exists(dst):

@@ -4,19 +4,17 @@ so these vectors pin the ORACLE (against silent drift) and give the GPU tests an
 Run:  python tests/golden/make_golden.py   (needs oracle/libq3oracle.so and tools/q3synth)"""
 import json
 import os
-import subprocess
 import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import q3oracle as O
+import synth_models
 
 
 def main():
-    out = "/tmp/q3tts_pytest_tiny"
-    if not os.path.exists(os.path.join(out, "gguf_q8_0", "qwen3_tts_talker.gguf")):
-        subprocess.check_call([os.path.join(ROOT, "tools", "q3synth"), "--out", out, "--preset", "tiny", "--quant", "q8_0"])
+    out = synth_models.ensure(synth_models.model_dir("smoke_tiny"), [["--preset", "tiny", "--quant", "q8_0"]])
     spk = np.array(json.load(open(os.path.join(ROOT, "tests", "golden", "speakers", "vivian.json")))["spk_emb"], np.float32)
     eng = O.Engine(os.path.join(out, "gguf_q8_0"), os.path.join(out, "onnx", "q3tts_codec.gguf"), 4)
     text = np.arange(100, 108, dtype=np.int32)

@@ -5,18 +5,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import synth_models
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def full_model(synth_tool):
-    out = os.environ.get("Q3_BENCH_MODEL", "/tmp/q3tts_synth_full")
-    marker = os.path.join(out, ".complete_q8_0")
-    if not os.path.exists(marker):
-        subprocess.check_call([synth_tool, "--out", out, "--preset", "full", "--quant", "q8_0", "--seed", "1234"])
-        open(marker, "w").write("ok")
-    return out
+    return synth_models.full("q8_0")
 
 
 def test_fullsize_parity_and_properties(gpu, oracle, full_model, vivian):
@@ -101,11 +98,7 @@ def test_fullsize_batched_c3_shapes_vs_oracle_singles(gpu, oracle, full_model, v
 
 @pytest.fixture(scope="module")
 def full_model_bf16(synth_tool, full_model):
-    marker = os.path.join(full_model, ".complete_bf16")
-    if not os.path.exists(marker):
-        subprocess.check_call([synth_tool, "--out", full_model, "--preset", "full", "--quant", "bf16", "--seed", "1234"])
-        open(marker, "w").write("ok")
-    return full_model
+    return synth_models.full("bf16", full_model)
 
 
 def test_fullsize_c5_bf16_clone_batch32_vs_oracle(gpu, oracle, full_model_bf16, vivian):
@@ -197,11 +190,7 @@ def test_fullsize_codec_fallback_epilogues_match_the_16_byte_ones(gpu, full_mode
 
 @pytest.fixture(scope="module")
 def full_model_q5(synth_tool, full_model):
-    marker = os.path.join(full_model, ".complete_q5_k_m")
-    if not os.path.exists(marker):
-        subprocess.check_call([synth_tool, "--out", full_model, "--preset", "full", "--quant", "q5_k_m", "--seed", "1234"])
-        open(marker, "w").write("ok")
-    return full_model
+    return synth_models.full("q5_k_m", full_model)
 
 
 def test_fullsize_q5_k_m_packed_planes_vs_oracle(gpu, oracle, full_model_q5, vivian):

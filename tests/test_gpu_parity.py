@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import synth_models
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "oracle_tiny_v1.npz")
@@ -817,10 +819,8 @@ def test_llama_abi_replay_matches_oracle(gpu, oracle, tiny_model, vivian, tmp_pa
 def test_two_engines_keep_their_own_assets(gpu, synth_tool, tiny_model):
     """q3tts_engine_assets returns a handle that lives inside its engine (a thread-local view made the first engine read the
     second engine's tables): two engines over different assets files, interleaved calls, one destroyed before the other is used again."""
-    other = os.environ.get("Q3_TINY_MODEL2", "/tmp/q3tts_pytest_tiny_seed99")
-    if not os.path.exists(os.path.join(other, ".complete")):
-        subprocess.check_call([synth_tool, "--out", other, "--preset", "tiny", "--quant", "q8_0", "--seed", "99"])
-        open(os.path.join(other, ".complete"), "w").write("ok")
+    other = synth_models.ensure(os.environ.get("Q3_TINY_MODEL2", synth_models.model_dir("pytest_tiny_seed99")),
+                                [["--preset", "tiny", "--quant", "q8_0", "--seed", "99"]])
     e1 = gpu.Engine(tiny_model, "q8_0", max_batch=1, max_steps=8, load_codec=False)
     a1 = e1.assets.text_embedding(1234).copy()
     e2 = gpu.Engine(other, "q8_0", max_batch=1, max_steps=8, load_codec=False)
