@@ -41,6 +41,17 @@ typedef struct q3tts_sampler_config {
 } q3tts_sampler_config;
 void q3tts_sampler_config_default(q3tts_sampler_config* c);
 
+/* ---- generation controls beyond the reference [EXT] (q3tts_spec.h: definitions) ----
+ * Upstream (transformers' Qwen3-Omni talker) decodes with repetition_penalty 1.05 and samples the 15 residual codes with top_k 50 /
+ * top_p 0.8 whenever the talker samples.  The defaults below reproduce the reference: no penalty, greedy code predictor. */
+typedef struct q3tts_gen_options {
+    float repetition_penalty;      /* talker code_0; 1.0 = off (reference); must be finite and > 0 */
+    float predictor_temperature;   /* <= 0: greedy predictor (reference) */
+    int32_t predictor_top_k;       /* 0 = disabled; >= 0 */
+    float predictor_top_p;         /* 1.0 = disabled; in (0, 1] */
+} q3tts_gen_options;
+void q3tts_gen_options_default(q3tts_gen_options* o);
+
 /* ---- engine ---- */
 typedef struct q3tts_engine q3tts_engine;
 typedef struct q3tts_engine_params {
@@ -73,6 +84,9 @@ typedef struct q3tts_request {
 } q3tts_request;
 /* runs all requests to completion in lock step (request-level batching) */
 int q3tts_generate_batch(q3tts_engine* e, q3tts_request* reqs, int32_t n_reqs, int32_t want_pcm);
+/* the same with q3tts_gen_options: opts is NULL (defaults for every request) or an array parallel to reqs; invalid options fail the call
+ * before anything is queued */
+int q3tts_generate_batch_ex(q3tts_engine* e, q3tts_request* reqs, int32_t n_reqs, int32_t want_pcm, const q3tts_gen_options* opts);
 
 typedef struct q3tts_stats {
     double frame_loop_ms; int64_t frames; double prefill_ms;
@@ -104,6 +118,8 @@ typedef struct q3tts_req_status {
 } q3tts_req_status;
 /* r->prompt/n_prompt/sampler/max_steps/mask_eos are read (the prompt is copied); output fields of r are ignored */
 int q3tts_submit(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, int64_t* req_id);
+int q3tts_submit_ex(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts /* NULL = defaults */,
+                    int64_t* req_id);
 int q3tts_poll(q3tts_engine* e, int64_t req_id, q3tts_req_status* out);
 /* streaming read: frames [frame_off, frame_off+max_frames) and PCM [pcm_off, pcm_off+pcm_cap) available right now */
 int q3tts_fetch(q3tts_engine* e, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out,
@@ -121,6 +137,9 @@ int q3tts_voice_register(q3tts_engine* e, const float* spk_emb2048, const int32_
 int q3tts_submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                       const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                       int32_t mask_eos, int32_t want_pcm, int64_t* req_id);
+int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                         const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                         int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
 
 /* ---- multi-GPU: request sharding, weights replicated per device, no collective on the data path ----
  * q3tts_group_*: ONE process, N devices.  One engine (+ scheduler thread + decoder thread) per entry of device_ids; requests go round-robin
@@ -149,6 +168,10 @@ int q3tts_group_submit(q3tts_group* g, const q3tts_request* r, int32_t want_pcm,
 int q3tts_group_submit_text(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                             const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                             int32_t mask_eos, int32_t want_pcm, int64_t* req_id);
+int q3tts_group_submit_ex(q3tts_group* g, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
+int q3tts_group_submit_text_ex(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                               const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                               int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
 int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id); /* HIP device a request was sharded to */
 int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out);
 int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out,
@@ -323,6 +346,13 @@ int q3tts_op_argmax(const float* logits, int32_t n, int32_t start, int32_t end, 
 /* device sampler (llama/mod.rs:666-776): n_draws consecutive draws of one seeded sequence over logits[0,n), n <= 4096 */
 int q3tts_op_sample(const float* logits, int32_t n, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t mask_idx,
                     int32_t n_draws, int32_t* out);
+/* [EXT] the frame graph's sampler launches over B rows of logits [B][n] (host buffers), n_draws consecutive draws per row:
+ * kernel 0 = k_sample (talker; n <= 4096; penalty NULL = none, else per row with history hist[b*hist_cap + 0 .. hist_len[b]) of code_0 values,
+ * packed into the engine's device layout: the last entry becomes the current frame's key), kernel 1 = k_sample_pred (code predictor;
+ * n <= 2048; penalty must be NULL).  Row b's stream is seed_from_u64(seed[b]).  out [n_draws][B]. */
+int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t n, const float* temperature, const int32_t* top_k,
+                         const float* top_p, const float* penalty, const uint64_t* seed, const int32_t* hist, const int32_t* hist_len,
+                         int32_t hist_cap, int32_t n_draws, int32_t* out);
 int q3tts_op_project(const float* x, const float* w /* [n_out][n_in] */, const float* b, int32_t n_in, int32_t n_out, float* y);
 
 #ifdef __cplusplus

@@ -251,6 +251,18 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
     return (i & 0x007fffff) - 0x00400000;
 }
 
+/* ---------------- generation controls beyond the reference [EXT] (q3tts_gen_options; defaults reproduce the reference) ----------------
+ * Repetition penalty p (> 0, 1.0 = off) -- transformers' RepetitionPenaltyLogitsProcessor, upstream's talker default 1.05:
+ *   applied to the talker's code_0 logits before the sampler step (EOS mask, sort, top-k, ...).  History = the set of DISTINCT code_0 values
+ *   the sequence has emitted so far: for the logits of frame f+1, frames 0..f (the prompt is not part of it; the first code_0, drawn at
+ *   prefill, sees an empty history).  Each history token is changed once: l < 0 ? l * p : l / p, f32, correctly rounded division.
+ *   The penalty also applies when T <= 0 (greedy on the penalised logits).
+ * Sampled code predictor (predictor_temperature > 0; <= 0 = greedy, the reference's LlamaSampler::greedy at engine.rs:470):
+ *   each of the 15 passes draws with LlamaSampler::sample (llama/mod.rs:703-775) over that pass's 2048 logits with predictor_top_k /
+ *   predictor_top_p, from a second per-sequence ChaCha12 stream seed_from_u64(seed ^ Q3_PRED_SEED_XOR), seed = the request's resolved seed.
+ *   Draw order: passes 1..15 of frame 0, then of frame 1, ...  The talker's own stream is untouched. */
+#define Q3_PRED_SEED_XOR 0x9E3779B97F4A7C15ull
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

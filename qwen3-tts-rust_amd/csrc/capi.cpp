@@ -28,6 +28,7 @@ int q3tts_version(void) { return 100; }
 int q3tts_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 
 void q3tts_sampler_config_default(q3tts_sampler_config* c) { c->temperature = 0.7f; c->top_k = 40; c->top_p = 0.9f; c->has_seed = 0; c->seed = 0; }
+void q3tts_gen_options_default(q3tts_gen_options* o) { o->repetition_penalty = 1.0f; o->predictor_temperature = 0.0f; o->predictor_top_k = 0; o->predictor_top_p = 1.0f; }
 void q3tts_engine_params_default(q3tts_engine_params* p) {
     p->model_dir = nullptr; p->quant = "q8_0"; p->device = 0; p->max_batch = 1; p->max_prompt = 1024;
     p->max_steps = Q3_DEFAULT_MAX_STEPS; p->load_codec = 1; p->use_graph = 1;
@@ -52,11 +53,17 @@ void q3tts_engine_destroy(q3tts_engine* e) { delete e; }
 int32_t q3tts_engine_device(q3tts_engine* e) { return e ? e->e->device() : -1; }
 
 static GenRequest to_gen(const q3tts_request& q);
-int q3tts_generate_batch(q3tts_engine* e, q3tts_request* reqs, int32_t n, int32_t want_pcm) {
+static GenOptions to_opts(const q3tts_gen_options* o) {
+    GenOptions g;
+    if (o) { g.repetition_penalty = o->repetition_penalty; g.predictor_temperature = o->predictor_temperature; g.predictor_top_k = o->predictor_top_k; g.predictor_top_p = o->predictor_top_p; }
+    return g;
+}
+int q3tts_generate_batch(q3tts_engine* e, q3tts_request* reqs, int32_t n, int32_t want_pcm) { return q3tts_generate_batch_ex(e, reqs, n, want_pcm, nullptr); }
+int q3tts_generate_batch_ex(q3tts_engine* e, q3tts_request* reqs, int32_t n, int32_t want_pcm, const q3tts_gen_options* opts) {
     Q3_API_BEGIN
     Q3_CHECK(e && reqs && n >= 1, "bad arguments");
     std::vector<GenRequest> rq(n);
-    for (int i = 0; i < n; i++) rq[i] = to_gen(reqs[i]);
+    for (int i = 0; i < n; i++) { rq[i] = to_gen(reqs[i]); rq[i].opts = to_opts(opts ? &opts[i] : nullptr); }
     std::vector<GenResult> res;
     e->e->generate_batch(rq, res, want_pcm != 0);
     for (int i = 0; i < n; i++) {
@@ -78,10 +85,13 @@ static GenRequest to_gen(const q3tts_request& q) {
     g.sampler.has_seed = q.sampler.has_seed != 0; g.sampler.seed = q.sampler.seed;
     return g;
 }
-int q3tts_submit(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, int64_t* req_id) {
+int q3tts_submit(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, int64_t* req_id) { return q3tts_submit_ex(e, r, want_pcm, nullptr, req_id); }
+int q3tts_submit_ex(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
     Q3_API_BEGIN
     Q3_CHECK(e && r && req_id, "null argument");
-    *req_id = e->e->submit(to_gen(*r), want_pcm != 0, true);
+    GenRequest g = to_gen(*r);
+    g.opts = to_opts(opts);
+    *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -138,6 +148,11 @@ int q3tts_voice_register(q3tts_engine* e, const float* spk, const int32_t* ref_c
 int q3tts_submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                       int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
                       int64_t* req_id) {
+    return q3tts_submit_text_ex(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, nullptr, req_id);
+}
+int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
+                         int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
+                         const q3tts_gen_options* opts, int64_t* req_id) {
     Q3_API_BEGIN
     Q3_CHECK(e && text_ids && n_text >= 0 && req_id, "bad arguments");
     const Voice& v = e->e->voice(voice_id);
@@ -154,6 +169,7 @@ int q3tts_submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids
         g.sampler.temperature = sampler->temperature; g.sampler.top_k = sampler->top_k; g.sampler.top_p = sampler->top_p;
         g.sampler.has_seed = sampler->has_seed != 0; g.sampler.seed = sampler->seed;
     }
+    g.opts = to_opts(opts);
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)

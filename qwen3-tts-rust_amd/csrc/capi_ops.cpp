@@ -2,6 +2,7 @@
 #include "../../include/q3tts.h"
 #include "transformer.h"
 #include "host_logic.h"
+#include "kdev.h"
 
 using namespace q3;
 #define Q3_API_BEGIN try {
@@ -182,6 +183,55 @@ int q3tts_op_sample(const float* logits, int32_t n, float temperature, int32_t t
     std::vector<q3_u64> keys(n_draws);
     dout.download(keys.data(), n_draws);
     for (int i = 0; i < n_draws; i++) out[i] = (int32_t)(~(uint32_t)(keys[i] & 0xFFFFFFFFull));
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t n, const float* temperature, const int32_t* top_k,
+                         const float* top_p, const float* penalty, const uint64_t* seed, const int32_t* hist, const int32_t* hist_len,
+                         int32_t hist_cap, int32_t n_draws, int32_t* out) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(logits && temperature && top_k && top_p && seed && out && B >= 1 && n >= 1 && n_draws >= 1, "bad arguments");
+    Q3_CHECK(kernel == 0 || kernel == 1, "kernel must be 0 (k_sample) or 1 (k_sample_pred)");
+    Q3_CHECK(kernel == 0 || !penalty, "the predictor sampler takes no penalty");
+    Q3_CHECK(!penalty || (hist && hist_len && hist_cap >= 1), "a penalty needs a history");
+    DevBuf<float> dl((size_t)B * n), dt(B), dp(B), dpen(B); DevBuf<int32_t> dk(B); DevBuf<uint32_t> dkey((size_t)8 * B), ddraw(B);
+    DevBuf<q3_u64> dout((size_t)n_draws * B);
+    dl.upload(logits, dl.n); dt.upload(temperature, B); dp.upload(top_p, B); dk.upload(top_k, B);
+    std::vector<uint32_t> keys((size_t)8 * B), zero(B, 0u);
+    for (int b = 0; b < B; b++) { StdRng rng(seed[b]); std::copy(rng.key(), rng.key() + 8, keys.begin() + (size_t)b * 8); }
+    dkey.upload(keys.data(), keys.size()); ddraw.upload(zero.data(), B);
+    // history in the frame graph's layout: code_0 of frame f at hist[b*stride + f*16], the current frame's code_0 as an argmax key
+    DevBuf<int32_t> dh, dlen; DevBuf<q3_u64> dcur;
+    if (penalty) {
+        const int stride = hist_cap * 16;
+        std::vector<int32_t> hh((size_t)B * stride, -1), len(B);
+        std::vector<q3_u64> cur(B, 0ull); // key 0 = code -1: ignored
+        for (int b = 0; b < B; b++) {
+            Q3_CHECK(hist_len[b] >= 0 && hist_len[b] <= hist_cap, "hist_len out of range");
+            const int nh = hist_len[b];
+            for (int f = 0; f + 1 < nh; f++) hh[(size_t)b * stride + (size_t)f * 16] = hist[(size_t)b * hist_cap + f];
+            len[b] = nh > 0 ? nh - 1 : 0;
+            if (nh > 0) cur[b] = pack_key(0.0f, hist[(size_t)b * hist_cap + nh - 1]);
+        }
+        dh.alloc(hh.size()); dh.upload(hh.data(), hh.size()); dlen.alloc(B); dlen.upload(len.data(), B); dcur.alloc((size_t)16 * B);
+        std::vector<q3_u64> cur16((size_t)16 * B, 0ull);
+        for (int b = 0; b < B; b++) cur16[(size_t)b * 16] = cur[b];
+        dcur.upload(cur16.data(), cur16.size());
+        dpen.upload(penalty, B);
+    }
+    for (int i = 0; i < n_draws; i++) {
+        SampleArgs a{dl.p, n, n, dt.p, dk.p, dp.p, nullptr, dkey.p, ddraw.p, dout.p + (size_t)i * B, 1};
+        if (penalty) { a.penalty = dpen.p; a.hist = dh.p; a.hist_stride = hist_cap * 16; a.hist_len = dlen.p; a.cur_key = dcur.p; a.cur_stride = 16; }
+        if (kernel == 0) launch_sample(0, a, B);
+        else launch_sample_pred(0, a, B);
+        Q3_LAUNCH_CHECK();
+    }
+    Q3_HIP(hipDeviceSynchronize());
+    std::vector<q3_u64> res(dout.n);
+    dout.download(res.data(), res.size());
+    for (size_t i = 0; i < res.size(); i++) out[i] = key_code(res[i]);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

@@ -1,6 +1,7 @@
 // engine.cpp -- see engine.h.  Loop structure cites /root/reference/src/tts/engine.rs line numbers.
 #include "engine.h"
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -103,6 +104,9 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_maxframes_.alloc(B); d_maskeos_.alloc(B); d_hist_.alloc((size_t)B * hist_stride_);
     d_temp_.alloc(B); d_topp_.alloc(B); d_topk_.alloc(B); d_rngkey_.alloc((size_t)8 * B); d_draws_.alloc(B);
     d_temp_.zero(); d_topp_.zero(); d_topk_.zero(); d_rngkey_.zero(); d_draws_.zero();
+    d_pen_.alloc(B); d_ptemp_.alloc(B); d_ptopp_.alloc(B); d_ptopk_.alloc(B); d_prngkey_.alloc((size_t)8 * B); d_pdraws_.alloc(B);
+    d_plogits_.alloc((size_t)B * Q3_CODEBOOK_SIZE);
+    d_ptemp_.zero(); d_ptopk_.zero(); d_prngkey_.zero(); d_pdraws_.zero();
     d_tlogits_.alloc((size_t)B * tl_stride_); d_thidden_.alloc((size_t)B * Q3_EMBD); d_pin_.alloc((size_t)2 * B * dP_);
     d_fb_.alloc((size_t)B * Q3_EMBD);
     d_prompt_.alloc((size_t)talker_->max_tok() * Q3_EMBD);
@@ -119,6 +123,8 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_ppos_.alloc(pos.size()); d_ppos_.upload(pos.data(), pos.size());
     h_maxf_.assign(B, 0); h_fin_.assign(B, 1); h_nfr_.assign(B, 0); h_mask_.assign(B, -1); h_nprompt_.assign(B, 0); h_topk_.assign(B, 0);
     h_temp_.assign(B, 0.0f); h_topp_.assign(B, 1.0f);
+    h_pen_.assign(B, 1.0f); h_ptemp_.assign(B, 0.0f); h_ptopp_.assign(B, 1.0f); h_ptopk_.assign(B, 0);
+    d_pen_.upload(h_pen_.data(), B); d_ptopp_.upload(h_ptopp_.data(), B);
     slot_req_.assign(B, nullptr); slot_live_.assign(B, 0);
     if (async_pf_) { d_pf_logits_.alloc((size_t)B * tl_stride_); d_pf_hidden_.alloc((size_t)B * Q3_EMBD); }
     {
@@ -220,7 +226,10 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
 
 // One frame for fg.width slots (engine.rs:545-641).  code_0 of the frame is already in keys[b][0]: it was produced at the end
 // of the previous frame (or of the prefill) by the talker head's argmax epilogue or by the device sampler.
-void Engine::record_frame(FrameGraph& fg, bool sampled) {
+// [EXT] pen: the talker head writes logits and k_sample applies the penalty with the history the device already has (code_0 of frames
+// [0, n_frames) in d_hist_ + the current frame's key, which k_advance_keys appends only after the head); pred: every predictor head writes
+// its 2048 logits and k_sample_pred draws the code (greedy slots take its first-max branch).  Neither set: today's launch sequence.
+void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred) {
     const int B = fg.width;
     const KvCache kvt = kv_t_->view(), kvp = kv_p_->view();
     // :565-573 predictor input = [project(m_hidden) ; project(E_0[code_0])]
@@ -231,8 +240,14 @@ void Engine::record_frame(FrameGraph& fg, bool sampled) {
         Transformer::Input in; in.x = d_pin_.p; in.x_stride = dP_;
         predictor_->set_same_seq_tokens(true);
         predictor_->forward(st_, in, 2 * B, tm, kvp, nullptr);
-        ArgmaxEpi am{d_keys_.p + 1, 16, nullptr, 0};
-        predictor_->head(st_, B, B, 0, Q3_CODEBOOK_SIZE, nullptr, 0, &am);
+        if (pred) {
+            predictor_->head(st_, B, B, 0, Q3_CODEBOOK_SIZE, d_plogits_.p, Q3_CODEBOOK_SIZE);
+            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_ptemp_.p, d_ptopk_.p, d_ptopp_.p, nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + 1, 16};
+            launch_sample_pred(st_, sa, B);
+        } else {
+            ArgmaxEpi am{d_keys_.p + 1, 16, nullptr, 0};
+            predictor_->head(st_, B, B, 0, Q3_CODEBOOK_SIZE, nullptr, 0, &am);
+        }
     }
     predictor_->set_same_seq_tokens(false);
     for (int q = 1; q < 15; q++) { // :602-610 decode project(E_q[code_q]) at pos q+1
@@ -241,8 +256,14 @@ void Engine::record_frame(FrameGraph& fg, bool sampled) {
         if (pred_identity_pages_) { tm.uniform_pos = q + 1; kvq.page_table = nullptr; } // token t = sequence t = page t, position q+1 everywhere
         Transformer::Input in; in.x = d_proj_tab_[q].p; in.x_stride = dP_; in.idx_keys = d_keys_.p + q; in.idx_stride = 16;
         predictor_->forward(st_, in, B, tm, kvq, nullptr);
-        ArgmaxEpi am{d_keys_.p + q + 1, 16, nullptr, 0};
-        predictor_->head(st_, 0, B, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, nullptr, 0, &am);
+        if (pred) {
+            predictor_->head(st_, 0, B, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_plogits_.p, Q3_CODEBOOK_SIZE);
+            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_ptemp_.p, d_ptopk_.p, d_ptopp_.p, nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + q + 1, 16};
+            launch_sample_pred(st_, sa, B);
+        } else {
+            ArgmaxEpi am{d_keys_.p + q + 1, 16, nullptr, 0};
+            predictor_->head(st_, 0, B, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, nullptr, 0, &am);
+        }
     }
     // :622-631 feedback ; :633-639 talker step at pos = cur_pos ; :550-555 next frame's code_0
     launch_feedback_keys(st_, d_tab_ptrs_.p, d_tab_rows_.p, d_keys_.p, 16, d_tts_pad_.p, d_fb_.p, B);
@@ -251,9 +272,10 @@ void Engine::record_frame(FrameGraph& fg, bool sampled) {
         Transformer::Input in; in.x = d_fb_.p; in.x_stride = Q3_EMBD;
         talker_->set_same_seq_tokens(false);
         talker_->forward(st_, in, B, tm, kvt, nullptr);
-        if (sampled) { // llama/mod.rs:666-776 on device; greedy slots of a mixed batch take the kernel's T<=0 branch
+        if (sampled || pen) { // llama/mod.rs:666-776 on device; greedy slots of a mixed batch take the kernel's T<=0 branch
             talker_->head(st_, 0, B, 0, tl_stride_, d_tlogits_.p, tl_stride_, nullptr, -1, d_thidden_.p);
             SampleArgs sa{d_tlogits_.p, tl_stride_, Q3_SAMPLE_END, d_temp_.p, d_topk_.p, d_topp_.p, d_maskeos_.p, d_rngkey_.p, d_draws_.p, d_next_key0_.p, 1};
+            if (pen) { sa.penalty = d_pen_.p; sa.hist = d_hist_.p; sa.hist_stride = hist_stride_; sa.hist_len = d_nframes_.p; sa.cur_key = d_keys_.p; sa.cur_stride = 16; }
             launch_sample(st_, sa, B);
         } else {
             ArgmaxEpi am{d_next_key0_.p, 1, d_maskeos_.p, 0};
@@ -267,8 +289,8 @@ void Engine::record_frame(FrameGraph& fg, bool sampled) {
 
 std::mutex& capture_mutex() { static std::mutex mu; return mu; }
 
-Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool capture) {
-    std::unique_ptr<FrameGraph>& slot = graphs_[width * 2 + (sampled ? 1 : 0)];
+Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool pred, bool capture) {
+    std::unique_ptr<FrameGraph>& slot = graphs_[width * 8 + (pred ? 4 : 0) + (pen ? 2 : 0) + (sampled ? 1 : 0)];
     // one graph construction at a time per process: engines of a multi-device group (or several engines on one device) build their frame
     // graphs from different threads; the synchronous allocations / uploads below and concurrent thread-local captures were seen to
     // invalidate another thread's capture on ROCm 7.2 ("operation failed due to a previous error during capture")
@@ -292,7 +314,7 @@ Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool capture) {
     if (capture && !fg.exec) {
         (void)hipGetLastError();
         Q3_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
-        try { record_frame(fg, sampled); }
+        try { record_frame(fg, sampled, pen, pred); }
         catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(st_, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
         Q3_HIP(hipStreamEndCapture(st_, &fg.graph));
         Q3_HIP(hipGraphInstantiate(&fg.exec, fg.graph, nullptr, nullptr, 0));
@@ -310,6 +332,10 @@ void Engine::upload_slot_state() {
     h2d(d_maxframes_.p, h_maxf_.data(), (size_t)W * 4); h2d(d_finished_.p, h_fin_.data(), (size_t)W * 4); h2d(d_nframes_.p, h_nfr_.data(), (size_t)W * 4);
     h2d(d_tslot_.p, tslot.data(), (size_t)W * 4); h2d(d_tpos_.p, tpos.data(), (size_t)16 * W); h2d(d_maskeos_.p, h_mask_.data(), (size_t)W * 4);
     h2d(d_temp_.p, h_temp_.data(), (size_t)W * 4); h2d(d_topk_.p, h_topk_.data(), (size_t)W * 4); h2d(d_topp_.p, h_topp_.data(), (size_t)W * 4);
+    if (ext_used_) {
+        h2d(d_pen_.p, h_pen_.data(), (size_t)W * 4); h2d(d_ptemp_.p, h_ptemp_.data(), (size_t)W * 4);
+        h2d(d_ptopk_.p, h_ptopk_.data(), (size_t)W * 4); h2d(d_ptopp_.p, h_ptopp_.data(), (size_t)W * 4);
+    }
     slot_dirty_ = false;
 }
 
@@ -476,9 +502,19 @@ void Engine::harvest(bool block) {
     }
 }
 
+void Engine::check_options(const GenRequest& g) const {
+    const GenOptions& o = g.opts;
+    Q3_CHECK(std::isfinite(o.repetition_penalty) && o.repetition_penalty > 0.0f, "repetition_penalty must be finite and > 0");
+    Q3_CHECK(o.predictor_top_k >= 0, "predictor_top_k must be >= 0");
+    Q3_CHECK(o.predictor_top_p > 0.0f && o.predictor_top_p <= 1.0f, "predictor_top_p must be in (0, 1]");
+    Q3_CHECK(!(talker_->ggml_mode() && (o.penalised() || o.pred_sampled())),
+             "repetition_penalty / predictor sampling are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
+}
+
 int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
     Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
     Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
+    check_options(g);
     std::unique_ptr<Req> r(new Req());
     r->r = g;
     if (copy_prompt) { r->prompt_own.assign(g.prompt, g.prompt + (size_t)g.n_prompt * Q3_EMBD); r->r.prompt = r->prompt_own.data(); }
@@ -631,6 +667,14 @@ void Engine::activate() {
         StdRng rng(r->seed); // llama/mod.rs:648: the device regenerates this ChaCha12 stream from the key and a draw counter
         h2d(d_rngkey_.p + (size_t)b * 8, rng.key(), 32);
         h2d(d_draws_.p + b, &zero, 4);
+        const GenOptions& o = r->r.opts;
+        h_pen_[b] = o.repetition_penalty; h_ptemp_[b] = o.predictor_temperature; h_ptopk_[b] = o.predictor_top_k; h_ptopp_[b] = o.predictor_top_p;
+        if (o.penalised() || o.pred_sampled()) ext_used_ = true;
+        if (o.pred_sampled()) { // [EXT] the predictor's own stream: seed_from_u64(seed ^ Q3_PRED_SEED_XOR)
+            StdRng prng(r->seed ^ (uint64_t)Q3_PRED_SEED_XOR);
+            h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
+            h2d(d_pdraws_.p + b, &zero, 4);
+        }
         h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);
         h2d(d_next_key0_.p + b, armed, 8);
         slot_live_[b] = 1;
@@ -674,6 +718,7 @@ void Engine::finish_ar(Req* r) { // engine.rs:644-649: final flush of the chunke
         dcv_.notify_all();
     }
     h_fin_[b] = 1; h_maxf_[b] = 0; h_nfr_[b] = 0; h_nprompt_[b] = 0; h_temp_[b] = 0.0f; h_mask_[b] = -1;
+    h_pen_[b] = 1.0f; h_ptemp_[b] = 0.0f;
     kv_t_->release(b); // from the next group on the slot steps on the scratch sequence (upload_slot_state)
     slot_dirty_ = true;
 }
@@ -687,26 +732,28 @@ static int pick_width(int hi, int W) { // graph widths: powers of two (and the f
 // one streaming step (4 frames, engine.rs:505-512) for every active slot
 void Engine::run_group() {
     int hi = 0, remaining = 0;
-    bool sampled = false;
+    bool sampled = false, pen = false, pred = false;
     for (int b = 0; b < B_; b++)
         if (slot_live_[b]) {
             Req* r = slot_req_[b];
             hi = b + 1;
             remaining = std::max(remaining, r->r.max_steps - h_nfr_[b]);
             if (r->r.sampler.temperature > 0.0f) sampled = true;
+            if (r->r.opts.penalised()) pen = true;
+            if (r->r.opts.pred_sampled()) pred = true;
         }
     arena_used_ = 0; // st_ is idle between scheduler operations: everything staged earlier has been consumed
     if (slot_dirty_) upload_slot_state();
     const int width = pick_width(hi, B_);
     const int group = std::max(1, std::min(4, remaining));
     const bool eager = instrument_ || !p_.use_graph;
-    FrameGraph& fg = frame_graph(width, sampled, !eager);
+    FrameGraph& fg = frame_graph(width, sampled, pen, pred, !eager);
     if (instrument_) { talker_->timer = &timer_; predictor_->timer = &timer_; talker_->timer_gu = &timer_gu_; }
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
     Q3_HIP(hipEventRecord(e0, st_));
     for (int g = 0; g < group; g++) {
-        if (eager) record_frame(fg, sampled);
+        if (eager) record_frame(fg, sampled, pen, pred);
         else Q3_HIP(hipGraphLaunch(fg.exec, st_));
     }
     Q3_HIP(hipEventRecord(e1, st_));
@@ -885,6 +932,7 @@ void Engine::generate_batch(const std::vector<GenRequest>& reqs, std::vector<Gen
     for (const GenRequest& g : reqs) { // validate everything before anything is queued
         Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
         Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
+        check_options(g);
     }
     std::vector<int64_t> ids(n);
     for (int i = 0; i < n; i++) ids[i] = submit(reqs[i], want_pcm, false);

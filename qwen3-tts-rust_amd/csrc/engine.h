@@ -24,6 +24,16 @@ struct SamplerConfig { // engine.rs:13-45
     float temperature = 0.7f; int top_k = 40; float top_p = 0.9f; bool has_seed = false; uint64_t seed = 0;
 };
 
+// [EXT] generation controls beyond the reference (q3tts_spec.h "Repetition penalty" / "Sampled code predictor"); defaults = reference
+struct GenOptions {
+    float repetition_penalty = 1.0f;    // talker code_0; 1 = off
+    float predictor_temperature = 0.0f; // <= 0: greedy predictor
+    int predictor_top_k = 0;            // 0 = disabled
+    float predictor_top_p = 1.0f;       // 1 = disabled
+    bool penalised() const { return repetition_penalty != 1.0f; }
+    bool pred_sampled() const { return predictor_temperature > 0.0f; }
+};
+
 struct EngineParams {
     std::string model_dir;      // contains <quant dir>/ and onnx/
     std::string quant = "q8_0"; // engine.rs:91-95
@@ -39,6 +49,7 @@ struct GenRequest {
     SamplerConfig sampler;
     int max_steps = Q3_DEFAULT_MAX_STEPS;
     bool mask_eos = false;      // bench/test knob: exclude EOS so runs have a fixed length
+    GenOptions opts;
 };
 struct GenResult {
     std::vector<int32_t> codes; int n_frames = 0;
@@ -106,8 +117,10 @@ private:
         int width = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         DevBuf<int32_t> seqA, slotA, posA;
     };
-    void record_frame(FrameGraph& fg, bool sampled);  // enqueue one frame step for fg.width slots on st_
-    FrameGraph& frame_graph(int width, bool sampled, bool capture);
+    // enqueue one frame step for fg.width slots on st_; pen / pred: some live slot has a repetition penalty / samples the predictor
+    void record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred);
+    FrameGraph& frame_graph(int width, bool sampled, bool pen, bool pred, bool capture);
+    void check_options(const GenRequest& g) const;
     void prefill(const std::vector<Req*>& batch, bool sampled);
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
     // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
@@ -149,15 +162,19 @@ private:
     DevBuf<int32_t> d_tseq_, d_tslot_, d_tpos_, d_nframes_, d_finished_, d_maxframes_, d_hist_, d_maskeos_;
     DevBuf<q3_u64> d_keys_, d_next_key0_; // argmax keys: [B][16] codes of the current frame, [B] code_0 of the next frame
     DevBuf<float> d_temp_, d_topp_; DevBuf<int32_t> d_topk_; DevBuf<uint32_t> d_rngkey_, d_draws_; // device sampler state
+    // [EXT] GenOptions state: talker penalty, predictor sampler parameters, its ChaCha12 key and draw counter, the predictor logits rows
+    DevBuf<float> d_pen_, d_ptemp_, d_ptopp_, d_plogits_; DevBuf<int32_t> d_ptopk_; DevBuf<uint32_t> d_prngkey_, d_pdraws_;
     DevBuf<int32_t> d_pseq_, d_pslot_, d_ppos_;
     DevBuf<float> d_tlogits_, d_thidden_, d_pin_, d_fb_, d_prompt_;
     DevBuf<int32_t> d_pf_seq_, d_pf_slot_, d_pf_pos_;
     int hist_stride_ = 0, tl_stride_ = 0;
-    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*2 + sampled
+    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*8 + pred*4 + pen*2 + sampled
     bool instrument_ = false; bool pred_identity_pages_ = false;
     // host mirrors of the slot state (refreshed from the device after every frame group)
     std::vector<int32_t> h_maxf_, h_fin_, h_nfr_, h_mask_, h_nprompt_, h_topk_;
     std::vector<float> h_temp_, h_topp_;
+    std::vector<float> h_pen_, h_ptemp_, h_ptopp_; std::vector<int32_t> h_ptopk_;
+    bool ext_used_ = false; // some request carried GenOptions: upload_slot_state keeps their device arrays current from then on
     bool slot_dirty_ = false;
     // scheduler state
     std::mutex mu_; std::condition_variable cv_;

@@ -265,23 +265,29 @@ int q3tts_group_voice_register(q3tts_group* g, const float* spk, const int32_t* 
 
 static int pick_engine(q3tts_group* g) { return (int)(g->rr.fetch_add(1) % g->eng.size()); } // request i -> device i % n
 
-int q3tts_group_submit(q3tts_group* g, const q3tts_request* r, int32_t want_pcm, int64_t* req_id) {
+int q3tts_group_submit(q3tts_group* g, const q3tts_request* r, int32_t want_pcm, int64_t* req_id) { return q3tts_group_submit_ex(g, r, want_pcm, nullptr, req_id); }
+int q3tts_group_submit_ex(q3tts_group* g, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
     Q3_API_BEGIN
     Q3_CHECK(g && r && req_id, "null argument");
     const int i = pick_engine(g);
     int64_t id = 0;
-    if (q3tts_submit(g->eng[i], r, want_pcm, &id) != Q3TTS_OK) return Q3TTS_ERR;
+    if (q3tts_submit_ex(g->eng[i], r, want_pcm, opts, &id) != Q3TTS_OK) return Q3TTS_ERR;
     *req_id = (id << kEngineBits) | i;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
 int q3tts_group_submit_text(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                             int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm, int64_t* req_id) {
+    return q3tts_group_submit_text_ex(g, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, nullptr, req_id);
+}
+int q3tts_group_submit_text_ex(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
+                               int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
+                               const q3tts_gen_options* opts, int64_t* req_id) {
     Q3_API_BEGIN
     Q3_CHECK(g && req_id, "null argument");
     const int i = pick_engine(g);
     int64_t id = 0;
-    if (q3tts_submit_text(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, &id) != Q3TTS_OK) return Q3TTS_ERR;
+    if (q3tts_submit_text_ex(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, &id) != Q3TTS_OK) return Q3TTS_ERR;
     *req_id = (id << kEngineBits) | i;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)

@@ -169,7 +169,15 @@ struct SampleArgs {
     const int32_t* mask_idx;                                            // optional per sequence: index forced to -inf
     const uint32_t* rng_key; uint32_t* draws;                           // [B][8] ChaCha12 key, [B] u32 words consumed so far
     q3_u64* out_key; int out_stride;                                    // receives pack_key(0, token)
+    // [EXT] repetition penalty (k_sample only; null = off, spec "Repetition penalty"): the history of sequence b is code_0 of frames
+    // [0, hist_len[b]) at hist[b*hist_stride + f*16] plus key_code(cur_key[b*cur_stride]) (the current frame; a code outside [0, n) is ignored)
+    const float* penalty = nullptr;
+    const int32_t* hist = nullptr; int hist_stride = 0; const int32_t* hist_len = nullptr;
+    const q3_u64* cur_key = nullptr; int cur_stride = 0;
 };
 void launch_sample(hipStream_t st, const SampleArgs& a, int B);
+// the code predictor's sampler: the same draw as k_sample (bit for bit, every T / top_k / top_p) for n <= 2048, without the 4096-key sort;
+// the penalty / mask fields must be null
+void launch_sample_pred(hipStream_t st, const SampleArgs& a, int B);
 
 } // namespace q3

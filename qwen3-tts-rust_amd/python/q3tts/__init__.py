@@ -22,6 +22,14 @@ class SamplerConfig(C.Structure):  # engine.rs:13-45
                 ("seed", C.c_uint64)]
 
 
+class GenOptions(C.Structure):  # q3tts_gen_options [EXT]: upstream's generation controls; the defaults reproduce the reference
+    _fields_ = [("repetition_penalty", C.c_float), ("predictor_temperature", C.c_float), ("predictor_top_k", C.c_int32),
+                ("predictor_top_p", C.c_float)]
+
+
+GEN_DEFAULTS = {"repetition_penalty": 1.0, "predictor_temperature": 0.0, "predictor_top_k": 0, "predictor_top_p": 1.0}
+
+
 class EngineParams(C.Structure):
     _fields_ = [("model_dir", C.c_char_p), ("quant", C.c_char_p), ("device", C.c_int32), ("max_batch", C.c_int32),
                 ("max_prompt", C.c_int32), ("max_steps", C.c_int32), ("load_codec", C.c_int32), ("use_graph", C.c_int32)]
@@ -75,6 +83,8 @@ SYMBOLS = [
     "q3tts_text_nfc", "q3tts_op_gemv_kq", "q3tts_op_gateup_kq", "q3tts_onnx_decoder_open", "q3tts_onnx_decoder_close", "q3tts_onnx_decoder_reset", "q3tts_onnx_decoder_fetch", "q3tts_group_info", "q3tts_onnx_decoder_decode",
     "q3tts_decoder_state_floats", "q3tts_decoder_state_export", "q3tts_decoder_state_import", "q3tts_decoder_state_entry",
     "q3tts_tokenizer_open", "q3tts_tokenizer_close", "q3tts_tokenizer_encode", "q3tts_tokenizer_decode", "q3tts_tokenizer_vocab_size",
+    "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
+    "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
 ]
 
 
@@ -147,6 +157,18 @@ def lib():
         L.q3tts_op_argmax.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.q3tts_op_sample.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p]
         L.q3tts_op_project.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.q3tts_gen_options_default.argtypes = [C.POINTER(GenOptions)]
+        L.q3tts_submit_ex.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.POINTER(GenOptions), C.POINTER(C.c_int64)]
+        L.q3tts_submit_text_ex.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.POINTER(SamplerConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(GenOptions),
+                                           C.POINTER(C.c_int64)]
+        L.q3tts_generate_batch_ex.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.c_int32, C.POINTER(GenOptions)]
+        L.q3tts_group_submit_ex.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.POINTER(GenOptions), C.POINTER(C.c_int64)]
+        L.q3tts_group_submit_text_ex.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.POINTER(SamplerConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(GenOptions),
+                                                 C.POINTER(C.c_int64)]
+        L.q3tts_op_sample_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -283,6 +305,13 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
     def _per(v, i):
         return v[i] if isinstance(v, (list, tuple, np.ndarray)) else v
 
+    @classmethod
+    def _opts(cls, i, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p):
+        """q3tts_gen_options of request i; None when every value is the default (the plain entry points' path)"""
+        o = GenOptions(cls._per(repetition_penalty, i), cls._per(predictor_temperature, i), cls._per(predictor_top_k, i),
+                       cls._per(predictor_top_p, i))
+        return None if all(getattr(o, k) == v for k, v in GEN_DEFAULTS.items()) else o
+
     def _fill(self, r, pr, i, max_steps, temperature, top_k, top_p, seed, mask_eos):
         r.prompt = pr.ctypes.data
         r.n_prompt = pr.shape[0]
@@ -295,12 +324,17 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         r.mask_eos = 1 if self._per(mask_eos, i) else 0
 
     # ---- continuous-batching scheduler (q3tts_submit / poll / fetch / wait) ----
-    def submit(self, prompt, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False):
+    def submit(self, prompt, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
+               repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0):
         pr = np.ascontiguousarray(prompt, np.float32)
         r = Request()
         self._fill(r, pr, 0, max_steps, temperature, top_k, top_p, seed, mask_eos)
+        o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        _chk(lib().q3tts_submit(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(rid)))
+        if o is None:
+            _chk(lib().q3tts_submit(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(rid)))
+        else:
+            _chk(lib().q3tts_submit_ex(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o), C.byref(rid)))
         return rid.value
 
     def register_voice(self, spk_emb, ref_codes=None, ref_text_ids=None):
@@ -313,13 +347,15 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         return vid.value
 
     def submit_text(self, voice_id, text_ids, lang_id=2055, instr_ids=None, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42,
-                    mask_eos=True, want_pcm=False):
+                    mask_eos=True, want_pcm=False, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0):
         t = np.ascontiguousarray(text_ids, np.int32)
         ins = np.ascontiguousarray(instr_ids, np.int32) if instr_ids is not None else None
         sc = SamplerConfig(temperature, top_k, top_p, 1, seed)
+        o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        _chk(lib().q3tts_submit_text(self.h, voice_id, _p(t), t.size, lang_id, _p(ins), ins.size if ins is not None else 0, C.byref(sc),
-                                     max_steps, 1 if mask_eos else 0, 1 if want_pcm else 0, C.byref(rid)))
+        _chk(lib().q3tts_submit_text_ex(self.h, voice_id, _p(t), t.size, lang_id, _p(ins), ins.size if ins is not None else 0, C.byref(sc),
+                                        max_steps, 1 if mask_eos else 0, 1 if want_pcm else 0, C.byref(o) if o is not None else None,
+                                        C.byref(rid)))
         return rid.value
 
     def poll(self, rid):
@@ -363,10 +399,11 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         return {"codes": codes, "pcm": pcm if want_pcm else None, **st}
 
     def generate_batch(self, prompts, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
-                       pcm_per_frame=1920):
-        """per-request values may be given as lists (max_steps, temperature, top_k, top_p, seed, mask_eos)"""
+                       pcm_per_frame=1920, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0):
+        """per-request values may be given as lists (max_steps, temperature, top_k, top_p, seed, mask_eos and the GenOptions fields)"""
         n = len(prompts)
         reqs = (Request * n)()
+        opts = [self._opts(i, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p) for i in range(n)]
         keep = []
         for i, pr in enumerate(prompts):
             pr = np.ascontiguousarray(pr, np.float32)
@@ -379,7 +416,11 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
             r.codes_out = codes.ctypes.data
             r.pcm_out = pcm.ctypes.data if pcm is not None else None
             r.pcm_capacity = pcm.size if pcm is not None else 0
-        _chk(lib().q3tts_generate_batch(self.h, reqs, n, 1 if want_pcm else 0))
+        if all(o is None for o in opts):
+            _chk(lib().q3tts_generate_batch(self.h, reqs, n, 1 if want_pcm else 0))
+        else:
+            arr = (GenOptions * n)(*[o if o is not None else GenOptions(**GEN_DEFAULTS) for o in opts])
+            _chk(lib().q3tts_generate_batch_ex(self.h, reqs, n, 1 if want_pcm else 0, arr))
         out = []
         for i in range(n):
             nf = reqs[i].n_frames
@@ -551,6 +592,30 @@ def op_sample(logits, temperature, top_k, top_p, seed, n_draws=1, mask_idx=-1):
     logits = np.ascontiguousarray(logits, dtype=np.float32)
     out = np.zeros(n_draws, dtype=np.int32)
     _chk(lib().q3tts_op_sample(_p(logits), logits.size, temperature, top_k, top_p, seed, mask_idx, n_draws, _p(out)))
+    return out
+
+
+def op_sample_rows(logits, temperature, top_k, top_p, seed, n_draws=1, kernel=0, penalty=None, history=None):
+    """[EXT] the frame graph's sampler kernels over B rows: kernel 0 = k_sample (talker, optional penalty + per-row history lists of code_0),
+    kernel 1 = k_sample_pred (code predictor).  Per-row parameters are arrays of length B.  Returns [n_draws][B] codes."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    B, n = lg.shape
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (B,)))
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, np.int32), (B,)))
+    p = np.ascontiguousarray(np.broadcast_to(np.asarray(top_p, np.float32), (B,)))
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (B,)))
+    pen = hist = hlen = None
+    cap = 1
+    if penalty is not None:
+        pen = np.ascontiguousarray(np.broadcast_to(np.asarray(penalty, np.float32), (B,)))
+        history = history if history is not None else [[] for _ in range(B)]
+        cap = max(1, max(len(h) for h in history))
+        hist = np.full((B, cap), -1, np.int32)
+        hlen = np.array([len(h) for h in history], np.int32)
+        for b, h in enumerate(history):
+            hist[b, : len(h)] = h
+    out = np.zeros((n_draws, B), np.int32)
+    _chk(lib().q3tts_op_sample_rows(kernel, _p(lg), B, n, _p(t), _p(k), _p(p), _p(pen), _p(s), _p(hist), _p(hlen), cap, n_draws, _p(out)))
     return out
 
 
