@@ -87,6 +87,10 @@ int q3tts_generate_batch(q3tts_engine* e, q3tts_request* reqs, int32_t n_reqs, i
 /* the same with q3tts_gen_options: opts is NULL (defaults for every request) or an array parallel to reqs; invalid options fail the call
  * before anything is queued */
 int q3tts_generate_batch_ex(q3tts_engine* e, q3tts_request* reqs, int32_t n_reqs, int32_t want_pcm, const q3tts_gen_options* opts);
+/* [EXT] streaming-text talker input (q3tts_spec.h): trail_ids[i] / n_trail[i] are request i's trailing text ids (each n_trail[i] in
+ * [0, max_prompt], ids non-NULL when n_trail[i] > 0); n_trail NULL = none for every request; opts as in _ex */
+int q3tts_generate_batch_trailing(q3tts_engine* e, q3tts_request* reqs, int32_t n_reqs, int32_t want_pcm, const q3tts_gen_options* opts,
+                                  const int32_t* const* trail_ids, const int32_t* n_trail);
 
 typedef struct q3tts_stats {
     double frame_loop_ms; int64_t frames; double prefill_ms;
@@ -120,6 +124,10 @@ typedef struct q3tts_req_status {
 int q3tts_submit(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, int64_t* req_id);
 int q3tts_submit_ex(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts /* NULL = defaults */,
                     int64_t* req_id);
+/* [EXT] a raw prompt plus trailing text ids, one added to the feedback per frame (q3tts_spec.h); the ids are copied.  The first request
+ * with n_trail > 0 uploads the text table to the device (~1.24 GB f32 for the real model) */
+int q3tts_submit_trailing(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts /* NULL = defaults */,
+                          const int32_t* trail_ids, int32_t n_trail, int64_t* req_id);
 int q3tts_poll(q3tts_engine* e, int64_t req_id, q3tts_req_status* out);
 /* streaming read: frames [frame_off, frame_off+max_frames) and PCM [pcm_off, pcm_off+pcm_cap) available right now */
 int q3tts_fetch(q3tts_engine* e, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out,
@@ -140,6 +148,10 @@ int q3tts_submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids
 int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                          const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                          int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
+/* [EXT] q3tts_submit_text_ex in the streaming-text layout (q3tts_prompt_build_streaming); n_text >= 1 */
+int q3tts_submit_text_streaming(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                                int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
 
 /* ---- multi-GPU: request sharding, weights replicated per device, no collective on the data path ----
  * q3tts_group_*: ONE process, N devices.  One engine (+ scheduler thread + decoder thread) per entry of device_ids; requests go round-robin
@@ -172,6 +184,9 @@ int q3tts_group_submit_ex(q3tts_group* g, const q3tts_request* r, int32_t want_p
 int q3tts_group_submit_text_ex(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                                const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                                int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
+int q3tts_group_submit_text_streaming(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                      const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                                      int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
 int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id); /* HIP device a request was sharded to */
 int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out);
 int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out,
@@ -208,6 +223,13 @@ int q3tts_prompt_build_core(const q3tts_assets* a, const int32_t* text_ids, int3
 int q3tts_prompt_build_clone(const q3tts_assets* a, const int32_t* text_ids, int32_t n_text, const int32_t* ref_codes,
                              int32_t n_ref_codes, const int32_t* ref_text_ids, int32_t n_ref_text, const float* spk_emb2048,
                              int32_t lang_id, const int32_t* instr_ids, int32_t n_instr, float* out, int32_t max_rows);
+/* [EXT] streaming-text layout (q3tts_spec.h): the prompt of build_core (ref_codes NULL / n_ref_codes 0) or of build_clone (ref_codes given:
+ * clone voice, spk_emb2048 and lang_id required, spk_id ignored) cut after [text(BOS) + E0(PAD)] and ended by [text(t_0) + E0(BOS)];
+ * trail_ids (capacity trail_cap) receives t_1 .. t_{n-1}, TEXT_EOS and *n_trail = n_text.  n_text >= 1.  Returns rows written or < 0 */
+int q3tts_prompt_build_streaming(const q3tts_assets* a, const int32_t* text_ids, int32_t n_text, int32_t lang_id, int32_t spk_id,
+                                 const float* spk_emb2048, const int32_t* instr_ids, int32_t n_instr, const int32_t* ref_codes,
+                                 int32_t n_ref_codes, const int32_t* ref_text_ids, int32_t n_ref_text, float* out, int32_t max_rows,
+                                 int32_t* trail_ids, int32_t trail_cap, int32_t* n_trail);
 
 /* ---- sampler (host) ---- */
 typedef struct q3tts_sampler q3tts_sampler;

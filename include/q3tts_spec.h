@@ -263,6 +263,22 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  *   Draw order: passes 1..15 of frame 0, then of frame 1, ...  The talker's own stream is untouched. */
 #define Q3_PRED_SEED_XOR 0x9E3779B97F4A7C15ull
 
+/* ---------------- streaming-text ("dual-track") talker input [EXT] (q3tts_prompt_build_streaming, q3tts_submit_trailing) ----------------
+ * Upstream's second talker layout, transformers 5.15 models/qwen3_omni_moe/modeling_qwen3_omni_moe.py:
+ *   Qwen3OmniMoeForConditionalGeneration._get_talker_assistant_parts (prompt ends [tts_bos + codec_pad], [text_0 + codec_bos];
+ *   trailing_text_hidden = [text_1 .. text_{n-1}, tts_eos]) and Qwen3OmniMoeTalkerForConditionalGeneration.prepare_inputs_for_generation
+ *   (step input = sum of the codec rows + trailing_text_hidden[generation_step], or + tts_pad once the trailing rows are used up;
+ *   prefill sets generation_step = -1 and every step adds 1).
+ * In this engine's terms, for text ids t_0 .. t_{n-1} (n >= 1):
+ *   prompt   = the reference prompt (build_core / build_clone_prompt) up to and including [text(Q3_TEXT_BOS) + E_0(Q3_CODEC_PAD)],
+ *              then one row [text(t_0) + E_0(Q3_CODEC_BOS)]: n + 1 rows shorter than the reference prompt of the same text
+ *   trailing = t_1 .. t_{n-1}, Q3_TEXT_EOS (n_trail = n ids)
+ *   feedback of frame f (0-based; frame 0's code_0 comes from the prefill) =
+ *              (sum_q E_q[code_q], q = 0..15 in order) + (f < n_trail ? text(trail[f]) : tts_pad), f32 left to right
+ *   text(id) = HostAssets::text_embedding(id) exactly, the out-of-range fallback row fmod((float)((u64)id * 17 + i), 2) - 1 included
+ *   (the synthetic models have 4096 text rows: Q3_TEXT_EOS takes the fallback there).  tts_pad = the reference's marker row 151671.
+ * With n_trail = 0 the feedback is the reference's; a raw prompt with trailing ids may be submitted with any n_trail in [0, max_prompt]. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

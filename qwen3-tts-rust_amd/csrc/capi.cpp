@@ -60,10 +60,17 @@ static GenOptions to_opts(const q3tts_gen_options* o) {
 }
 int q3tts_generate_batch(q3tts_engine* e, q3tts_request* reqs, int32_t n, int32_t want_pcm) { return q3tts_generate_batch_ex(e, reqs, n, want_pcm, nullptr); }
 int q3tts_generate_batch_ex(q3tts_engine* e, q3tts_request* reqs, int32_t n, int32_t want_pcm, const q3tts_gen_options* opts) {
+    return q3tts_generate_batch_trailing(e, reqs, n, want_pcm, opts, nullptr, nullptr);
+}
+int q3tts_generate_batch_trailing(q3tts_engine* e, q3tts_request* reqs, int32_t n, int32_t want_pcm, const q3tts_gen_options* opts,
+                                  const int32_t* const* trail_ids, const int32_t* n_trail) {
     Q3_API_BEGIN
     Q3_CHECK(e && reqs && n >= 1, "bad arguments");
     std::vector<GenRequest> rq(n);
-    for (int i = 0; i < n; i++) { rq[i] = to_gen(reqs[i]); rq[i].opts = to_opts(opts ? &opts[i] : nullptr); }
+    for (int i = 0; i < n; i++) {
+        rq[i] = to_gen(reqs[i]); rq[i].opts = to_opts(opts ? &opts[i] : nullptr);
+        if (n_trail) { rq[i].n_trail = n_trail[i]; rq[i].trail = trail_ids ? trail_ids[i] : nullptr; } // validated with the rest, before queueing
+    }
     std::vector<GenResult> res;
     e->e->generate_batch(rq, res, want_pcm != 0);
     for (int i = 0; i < n; i++) {
@@ -91,6 +98,17 @@ int q3tts_submit_ex(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, c
     Q3_CHECK(e && r && req_id, "null argument");
     GenRequest g = to_gen(*r);
     g.opts = to_opts(opts);
+    *req_id = e->e->submit(g, want_pcm != 0, true);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_submit_trailing(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, const int32_t* trail_ids,
+                          int32_t n_trail, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && r && req_id, "null argument");
+    GenRequest g = to_gen(*r);
+    g.opts = to_opts(opts);
+    g.trail = trail_ids; g.n_trail = n_trail;
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
@@ -150,19 +168,35 @@ int q3tts_submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids
                       int64_t* req_id) {
     return q3tts_submit_text_ex(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, nullptr, req_id);
 }
+static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
+                       int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
+                       const q3tts_gen_options* opts, bool streaming, int64_t* req_id);
 int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                          int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
                          const q3tts_gen_options* opts, int64_t* req_id) {
+    return submit_text(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, false, req_id);
+}
+int q3tts_submit_text_streaming(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                                int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
+    return submit_text(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, true, req_id);
+}
+static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
+                       int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
+                       const q3tts_gen_options* opts, bool streaming, int64_t* req_id) {
     Q3_API_BEGIN
     Q3_CHECK(e && text_ids && n_text >= 0 && req_id, "bad arguments");
+    Q3_CHECK(!streaming || n_text >= 1, "the streaming-text layout needs n_text >= 1");
     const Voice& v = e->e->voice(voice_id);
     std::vector<int32_t> t(text_ids, text_ids + n_text), ins;
     if (instr_ids) ins.assign(instr_ids, instr_ids + n_instr);
     int lang = lang_id;
     // engine.rs:398-428: clone voices (codes + ref text) take build_clone_prompt, presets build_core with marker + spk_emb
+    std::vector<int32_t> trail;
+    std::vector<int32_t>* tr = streaming ? &trail : nullptr;
     PromptData pd = !v.ref_codes.empty()
-        ? PromptBuilder::build_clone_prompt(e->e->assets(), t, v.ref_codes, v.ref_text_ids, v.spk_emb.data(), lang_id, instr_ids ? &ins : nullptr)
-        : PromptBuilder::build_core(e->e->assets(), t, lang_id >= 0 ? &lang : nullptr, nullptr, v.spk_emb.data(), instr_ids ? &ins : nullptr, nullptr);
+        ? PromptBuilder::build_clone_prompt(e->e->assets(), t, v.ref_codes, v.ref_text_ids, v.spk_emb.data(), lang_id, instr_ids ? &ins : nullptr, tr)
+        : PromptBuilder::build_core(e->e->assets(), t, lang_id >= 0 ? &lang : nullptr, nullptr, v.spk_emb.data(), instr_ids ? &ins : nullptr, nullptr, tr);
     GenRequest g;
     g.prompt = pd.embd.data(); g.n_prompt = pd.n_rows; g.max_steps = max_steps; g.mask_eos = mask_eos != 0;
     if (sampler) {
@@ -170,6 +204,7 @@ int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_
         g.sampler.has_seed = sampler->has_seed != 0; g.sampler.seed = sampler->seed;
     }
     g.opts = to_opts(opts);
+    g.trail = trail.data(); g.n_trail = (int)trail.size();
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
@@ -246,6 +281,33 @@ int q3tts_prompt_build_clone(const q3tts_assets* a, const int32_t* text_ids, int
     std::vector<int32_t> t(text_ids, text_ids + n_text), rc(ref_codes, ref_codes + n_ref_codes), rt(ref_text_ids, ref_text_ids + n_ref_text), ins;
     if (instr_ids) ins.assign(instr_ids, instr_ids + n_instr);
     return emit_rows(PromptBuilder::build_clone_prompt(*a->a, t, rc, rt, spk_emb, lang_id, instr_ids ? &ins : nullptr), out, max_rows);
+    Q3_API_END(-1)
+}
+int q3tts_prompt_build_streaming(const q3tts_assets* a, const int32_t* text_ids, int32_t n_text, int32_t lang_id, int32_t spk_id,
+                                 const float* spk_emb, const int32_t* instr_ids, int32_t n_instr, const int32_t* ref_codes,
+                                 int32_t n_ref_codes, const int32_t* ref_text_ids, int32_t n_ref_text, float* out, int32_t max_rows,
+                                 int32_t* trail_ids, int32_t trail_cap, int32_t* n_trail) {
+    Q3_API_BEGIN
+    Q3_CHECK(a && text_ids && n_text >= 1 && trail_ids && n_trail, "bad arguments (the streaming-text layout needs n_text >= 1)");
+    Q3_CHECK(trail_cap >= n_text, "trail_cap < n_text");
+    std::vector<int32_t> t(text_ids, text_ids + n_text), ins, trail;
+    if (instr_ids) ins.assign(instr_ids, instr_ids + n_instr);
+    PromptData d;
+    if (ref_codes && n_ref_codes > 0) {
+        Q3_CHECK(spk_emb && lang_id >= 0, "a clone prompt needs spk_emb and lang_id");
+        std::vector<int32_t> rc(ref_codes, ref_codes + n_ref_codes), rt;
+        if (ref_text_ids) rt.assign(ref_text_ids, ref_text_ids + n_ref_text);
+        d = PromptBuilder::build_clone_prompt(*a->a, t, rc, rt, spk_emb, lang_id, instr_ids ? &ins : nullptr, &trail);
+    } else {
+        int lang = lang_id, spk = spk_id;
+        d = PromptBuilder::build_core(*a->a, t, lang_id >= 0 ? &lang : nullptr, spk_id >= 0 ? &spk : nullptr, spk_emb, instr_ids ? &ins : nullptr,
+                                      nullptr, &trail);
+    }
+    const int rows = emit_rows(d, out, max_rows);
+    if (rows < 0) return rows;
+    std::copy(trail.begin(), trail.end(), trail_ids);
+    *n_trail = (int32_t)trail.size();
+    return rows;
     Q3_API_END(-1)
 }
 

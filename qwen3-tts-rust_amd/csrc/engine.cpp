@@ -123,7 +123,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_ppos_.alloc(pos.size()); d_ppos_.upload(pos.data(), pos.size());
     h_maxf_.assign(B, 0); h_fin_.assign(B, 1); h_nfr_.assign(B, 0); h_mask_.assign(B, -1); h_nprompt_.assign(B, 0); h_topk_.assign(B, 0);
     h_temp_.assign(B, 0.0f); h_topp_.assign(B, 1.0f);
-    h_pen_.assign(B, 1.0f); h_ptemp_.assign(B, 0.0f); h_ptopp_.assign(B, 1.0f); h_ptopk_.assign(B, 0);
+    h_pen_.assign(B, 1.0f); h_ptemp_.assign(B, 0.0f); h_ptopp_.assign(B, 1.0f); h_ptopk_.assign(B, 0); h_ntrail_.assign(B, 0);
     d_pen_.upload(h_pen_.data(), B); d_ptopp_.upload(h_ptopp_.data(), B);
     slot_req_.assign(B, nullptr); slot_live_.assign(B, 0);
     if (async_pf_) { d_pf_logits_.alloc((size_t)B * tl_stride_); d_pf_hidden_.alloc((size_t)B * Q3_EMBD); }
@@ -178,7 +178,7 @@ void* Engine::d2h_begin(const void* src, size_t bytes) {
 // ---------------------------------------------------------------------------------------------------------------
 struct Engine::Req {
     int64_t id = 0;
-    GenRequest r; std::vector<float> prompt_own; bool want_pcm = false;
+    GenRequest r; std::vector<float> prompt_own; std::vector<int32_t> trail_own; bool want_pcm = false;
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
@@ -229,7 +229,8 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
 // [EXT] pen: the talker head writes logits and k_sample applies the penalty with the history the device already has (code_0 of frames
 // [0, n_frames) in d_hist_ + the current frame's key, which k_advance_keys appends only after the head); pred: every predictor head writes
 // its 2048 logits and k_sample_pred draws the code (greedy slots take its first-max branch).  Neither set: today's launch sequence.
-void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred) {
+// trail: the feedback kernel's streaming-text variant (same launch, reads d_nframes_ / d_ntrail_ / d_trail_ and the text table).
+void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail) {
     const int B = fg.width;
     const KvCache kvt = kv_t_->view(), kvp = kv_p_->view();
     // :565-573 predictor input = [project(m_hidden) ; project(E_0[code_0])]
@@ -266,7 +267,13 @@ void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred) {
         }
     }
     // :622-631 feedback ; :633-639 talker step at pos = cur_pos ; :550-555 next frame's code_0
-    launch_feedback_keys(st_, d_tab_ptrs_.p, d_tab_rows_.p, d_keys_.p, 16, d_tts_pad_.p, d_fb_.p, B);
+    if (trail) {
+        TextTrail tt; tt.n_frames = d_nframes_.p; tt.n_trail = d_ntrail_.p; tt.ids = d_trail_.p; tt.ids_stride = p_.max_prompt;
+        tt.table = d_text_.p; tt.rows = text_rows_;
+        launch_feedback_keys(st_, d_tab_ptrs_.p, d_tab_rows_.p, d_keys_.p, 16, d_tts_pad_.p, d_fb_.p, B, &tt);
+    } else {
+        launch_feedback_keys(st_, d_tab_ptrs_.p, d_tab_rows_.p, d_keys_.p, 16, d_tts_pad_.p, d_fb_.p, B);
+    }
     {
         TokMeta tm{d_tseq_.p, d_tslot_.p, d_tpos_.p};
         Transformer::Input in; in.x = d_fb_.p; in.x_stride = Q3_EMBD;
@@ -289,8 +296,8 @@ void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred) {
 
 std::mutex& capture_mutex() { static std::mutex mu; return mu; }
 
-Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool pred, bool capture) {
-    std::unique_ptr<FrameGraph>& slot = graphs_[width * 8 + (pred ? 4 : 0) + (pen ? 2 : 0) + (sampled ? 1 : 0)];
+Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool capture) {
+    std::unique_ptr<FrameGraph>& slot = graphs_[width * 16 + (trail ? 8 : 0) + (pred ? 4 : 0) + (pen ? 2 : 0) + (sampled ? 1 : 0)];
     // one graph construction at a time per process: engines of a multi-device group (or several engines on one device) build their frame
     // graphs from different threads; the synchronous allocations / uploads below and concurrent thread-local captures were seen to
     // invalidate another thread's capture on ROCm 7.2 ("operation failed due to a previous error during capture")
@@ -314,7 +321,7 @@ Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool 
     if (capture && !fg.exec) {
         (void)hipGetLastError();
         Q3_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
-        try { record_frame(fg, sampled, pen, pred); }
+        try { record_frame(fg, sampled, pen, pred, trail); }
         catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(st_, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
         Q3_HIP(hipStreamEndCapture(st_, &fg.graph));
         Q3_HIP(hipGraphInstantiate(&fg.exec, fg.graph, nullptr, nullptr, 0));
@@ -336,6 +343,7 @@ void Engine::upload_slot_state() {
         h2d(d_pen_.p, h_pen_.data(), (size_t)W * 4); h2d(d_ptemp_.p, h_ptemp_.data(), (size_t)W * 4);
         h2d(d_ptopk_.p, h_ptopk_.data(), (size_t)W * 4); h2d(d_ptopp_.p, h_ptopp_.data(), (size_t)W * 4);
     }
+    if (trail_used_) h2d(d_ntrail_.p, h_ntrail_.data(), (size_t)W * 4); // a reused slot never keeps its predecessor's count
     slot_dirty_ = false;
 }
 
@@ -509,15 +517,44 @@ void Engine::check_options(const GenRequest& g) const {
     Q3_CHECK(o.predictor_top_p > 0.0f && o.predictor_top_p <= 1.0f, "predictor_top_p must be in (0, 1]");
     Q3_CHECK(!(talker_->ggml_mode() && (o.penalised() || o.pred_sampled())),
              "repetition_penalty / predictor sampling are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
+    Q3_CHECK(g.n_trail >= 0 && g.n_trail <= p_.max_prompt, "n_trail must be in [0, max_prompt]");
+    Q3_CHECK(g.n_trail == 0 || g.trail, "trailing ids missing");
+    Q3_CHECK(!(talker_->ggml_mode() && g.n_trail > 0),
+             "trailing text ids are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
+}
+
+// The streaming-text state goes to the device on first use only: the real text table is 151936 x 2048 f32 (~1.24 GB).  Called from
+// submitting threads; the synchronous allocations and uploads hold capture_mutex() so they never land inside another thread's capture.
+void Engine::ensure_text_stream() {
+    std::lock_guard<std::mutex> lk(text_mu_);
+    if (text_ready_) return;
+    std::lock_guard<std::mutex> cap(capture_mutex());
+    int prev = 0;
+    Q3_HIP(hipGetDevice(&prev));
+    Q3_HIP(hipSetDevice(dev_));
+    try {
+        const HostAssets& a = *assets_;
+        text_rows_ = a.text_table ? a.text_rows : 0;
+        d_text_.alloc((size_t)std::max<int64_t>(text_rows_, 1) * Q3_EMBD);
+        if (text_rows_ > 0) d_text_.upload(a.text_table, (size_t)text_rows_ * Q3_EMBD);
+        d_trail_.alloc((size_t)B_ * p_.max_prompt); d_trail_.zero();
+        d_ntrail_.alloc(B_); d_ntrail_.zero();
+        Q3_HIP(hipStreamSynchronize(nullptr)); // the memsets ran on the null stream; the engine's streams do not wait for it
+    } catch (...) { (void)hipSetDevice(prev); throw; }
+    Q3_HIP(hipSetDevice(prev));
+    text_ready_ = true;
 }
 
 int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
     Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
     Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
     check_options(g);
+    if (g.n_trail > 0) ensure_text_stream();
     std::unique_ptr<Req> r(new Req());
     r->r = g;
     if (copy_prompt) { r->prompt_own.assign(g.prompt, g.prompt + (size_t)g.n_prompt * Q3_EMBD); r->r.prompt = r->prompt_own.data(); }
+    r->trail_own.assign(g.trail, g.trail + g.n_trail);
+    r->r.trail = r->trail_own.data();
     r->want_pcm = want_pcm && codec_;
     r->t_submit = now_ms();
     r->seed = g.sampler.has_seed ? g.sampler.seed
@@ -675,6 +712,11 @@ void Engine::activate() {
             h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
             h2d(d_pdraws_.p + b, &zero, 4);
         }
+        h_ntrail_[b] = r->r.n_trail;
+        if (r->r.n_trail > 0) { // [EXT] streaming text: the slot's trailing ids; upload_slot_state below sends the count
+            trail_used_ = true;
+            h2d(d_trail_.p + (size_t)b * p_.max_prompt, r->r.trail, (size_t)r->r.n_trail * 4);
+        }
         h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);
         h2d(d_next_key0_.p + b, armed, 8);
         slot_live_[b] = 1;
@@ -718,7 +760,7 @@ void Engine::finish_ar(Req* r) { // engine.rs:644-649: final flush of the chunke
         dcv_.notify_all();
     }
     h_fin_[b] = 1; h_maxf_[b] = 0; h_nfr_[b] = 0; h_nprompt_[b] = 0; h_temp_[b] = 0.0f; h_mask_[b] = -1;
-    h_pen_[b] = 1.0f; h_ptemp_[b] = 0.0f;
+    h_pen_[b] = 1.0f; h_ptemp_[b] = 0.0f; h_ntrail_[b] = 0;
     kv_t_->release(b); // from the next group on the slot steps on the scratch sequence (upload_slot_state)
     slot_dirty_ = true;
 }
@@ -732,7 +774,7 @@ static int pick_width(int hi, int W) { // graph widths: powers of two (and the f
 // one streaming step (4 frames, engine.rs:505-512) for every active slot
 void Engine::run_group() {
     int hi = 0, remaining = 0;
-    bool sampled = false, pen = false, pred = false;
+    bool sampled = false, pen = false, pred = false, trail = false;
     for (int b = 0; b < B_; b++)
         if (slot_live_[b]) {
             Req* r = slot_req_[b];
@@ -741,19 +783,20 @@ void Engine::run_group() {
             if (r->r.sampler.temperature > 0.0f) sampled = true;
             if (r->r.opts.penalised()) pen = true;
             if (r->r.opts.pred_sampled()) pred = true;
+            if (r->r.n_trail > 0) trail = true;
         }
     arena_used_ = 0; // st_ is idle between scheduler operations: everything staged earlier has been consumed
     if (slot_dirty_) upload_slot_state();
     const int width = pick_width(hi, B_);
     const int group = std::max(1, std::min(4, remaining));
     const bool eager = instrument_ || !p_.use_graph;
-    FrameGraph& fg = frame_graph(width, sampled, pen, pred, !eager);
+    FrameGraph& fg = frame_graph(width, sampled, pen, pred, trail, !eager);
     if (instrument_) { talker_->timer = &timer_; predictor_->timer = &timer_; talker_->timer_gu = &timer_gu_; }
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
     Q3_HIP(hipEventRecord(e0, st_));
     for (int g = 0; g < group; g++) {
-        if (eager) record_frame(fg, sampled, pen, pred);
+        if (eager) record_frame(fg, sampled, pen, pred, trail);
         else Q3_HIP(hipGraphLaunch(fg.exec, st_));
     }
     Q3_HIP(hipEventRecord(e1, st_));
@@ -934,6 +977,7 @@ void Engine::generate_batch(const std::vector<GenRequest>& reqs, std::vector<Gen
         Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
         check_options(g);
     }
+    for (const GenRequest& g : reqs) if (g.n_trail > 0) ensure_text_stream(); // the one step that can fail after validation: before queueing
     std::vector<int64_t> ids(n);
     for (int i = 0; i < n; i++) ids[i] = submit(reqs[i], want_pcm, false);
     double t_ar_end = 0;

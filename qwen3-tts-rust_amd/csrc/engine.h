@@ -50,6 +50,8 @@ struct GenRequest {
     int max_steps = Q3_DEFAULT_MAX_STEPS;
     bool mask_eos = false;      // bench/test knob: exclude EOS so runs have a fixed length
     GenOptions opts;
+    // [EXT] streaming-text talker input (q3tts_spec.h): trailing text ids, one per frame in the feedback; copied at submit
+    const int32_t* trail = nullptr; int n_trail = 0;
 };
 struct GenResult {
     std::vector<int32_t> codes; int n_frames = 0;
@@ -118,9 +120,11 @@ private:
         DevBuf<int32_t> seqA, slotA, posA;
     };
     // enqueue one frame step for fg.width slots on st_; pen / pred: some live slot has a repetition penalty / samples the predictor
-    void record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred);
-    FrameGraph& frame_graph(int width, bool sampled, bool pen, bool pred, bool capture);
+    // trail: some live slot has trailing text ids (the feedback kernel's streaming-text variant replaces the plain one)
+    void record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail);
+    FrameGraph& frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool capture);
     void check_options(const GenRequest& g) const;
+    void ensure_text_stream(); // first request with trailing ids: text table + per-slot id rows go to the device
     void prefill(const std::vector<Req*>& batch, bool sampled);
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
     // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
@@ -168,12 +172,17 @@ private:
     DevBuf<float> d_tlogits_, d_thidden_, d_pin_, d_fb_, d_prompt_;
     DevBuf<int32_t> d_pf_seq_, d_pf_slot_, d_pf_pos_;
     int hist_stride_ = 0, tl_stride_ = 0;
-    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*8 + pred*4 + pen*2 + sampled
+    // [EXT] streaming-text state, allocated by the first request with n_trail > 0: the text table, [B][max_prompt] trailing ids, [B] counts
+    DevBuf<float> d_text_; DevBuf<int32_t> d_trail_, d_ntrail_; int64_t text_rows_ = 0;
+    std::mutex text_mu_; bool text_ready_ = false; // text_ready_ is written under text_mu_ and capture_mutex()
+    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*16 + trail*8 + pred*4 + pen*2 + sampled
     bool instrument_ = false; bool pred_identity_pages_ = false;
     // host mirrors of the slot state (refreshed from the device after every frame group)
     std::vector<int32_t> h_maxf_, h_fin_, h_nfr_, h_mask_, h_nprompt_, h_topk_;
     std::vector<float> h_temp_, h_topp_;
     std::vector<float> h_pen_, h_ptemp_, h_ptopp_; std::vector<int32_t> h_ptopk_;
+    std::vector<int32_t> h_ntrail_;
+    bool trail_used_ = false; // some activated request had trailing ids: upload_slot_state keeps d_ntrail_ current from then on
     bool ext_used_ = false; // some request carried GenOptions: upload_slot_state keeps their device arrays current from then on
     bool slot_dirty_ = false;
     // scheduler state

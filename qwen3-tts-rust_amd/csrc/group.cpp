@@ -293,6 +293,19 @@ int q3tts_group_submit_text_ex(q3tts_group* g, int32_t voice_id, const int32_t* 
     Q3_API_END(Q3TTS_ERR)
 }
 #define Q3_GROUP_ENGINE(g, id) ((g) && eng_of(id) < (int)(g)->eng.size() ? (g)->eng[eng_of(id)] : nullptr)
+int q3tts_group_submit_text_streaming(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                      const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                                      int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && req_id, "null argument");
+    const int i = pick_engine(g);
+    int64_t id = 0;
+    if (q3tts_submit_text_streaming(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts,
+                                    &id) != Q3TTS_OK) return Q3TTS_ERR;
+    *req_id = (id << kEngineBits) | i;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id) { return (g && eng_of(req_id) < (int)g->slot.size()) ? g->slot[eng_of(req_id)].dev : -1; }
 int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out) {
     q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);

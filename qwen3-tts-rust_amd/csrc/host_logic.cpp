@@ -109,7 +109,8 @@ void sum2(const float* a, const float* b, float* o) { for (int i = 0; i < 2048; 
 }
 PromptData PromptBuilder::build_core(const HostAssets& a, const std::vector<int32_t>& text_ids, const int* lang_id,
                                      const int* spk_id, const float* spk_emb, const std::vector<int32_t>* instr_ids,
-                                     const std::vector<float>* mid_rows) {
+                                     const std::vector<float>* mid_rows, std::vector<int32_t>* trail) {
+    Q3_CHECK(!trail || !text_ids.empty(), "the streaming-text layout needs at least one text token");
     Rows R;
     std::vector<float> e(2048), marker(2048), pad0(2048), t(2048);
     auto text = [&](int64_t id) { a.text_embedding(id, R.add()); };
@@ -128,6 +129,13 @@ PromptData PromptBuilder::build_core(const HostAssets& a, const std::vector<int3
     if (mid_rows) { R.d.embd.insert(R.d.embd.end(), mid_rows->begin(), mid_rows->end()); R.d.n_rows += (int)(mid_rows->size() / 2048); } // :225-227
     a.codec_embedding(0, Q3_CODEC_PAD, pad0.data());                  // :232
     a.text_embedding(Q3_TEXT_BOS, t.data()); sum2(t.data(), pad0.data(), R.add());                    // :233-239
+    if (trail) { // [EXT] streaming text: [text(t_0) + E0(BOS)], the rest of the text arrives one id per frame
+        a.codec_embedding(0, Q3_CODEC_BOS, e.data());
+        a.text_embedding(text_ids[0], t.data()); sum2(t.data(), e.data(), R.add());
+        trail->assign(text_ids.begin() + 1, text_ids.end());
+        trail->push_back(Q3_TEXT_EOS);
+        return std::move(R.d);
+    }
     for (int32_t id : text_ids) { a.text_embedding(id, t.data()); sum2(t.data(), pad0.data(), R.add()); } // :241-245
     a.text_embedding(Q3_TEXT_EOS, t.data()); sum2(t.data(), pad0.data(), R.add());                    // :248-254
     mark_codec(Q3_CODEC_BOS);                                         // :258-264
@@ -135,7 +143,8 @@ PromptData PromptBuilder::build_core(const HostAssets& a, const std::vector<int3
 }
 PromptData PromptBuilder::build_clone_prompt(const HostAssets& a, const std::vector<int32_t>& text_ids,
                                              const std::vector<int32_t>& ref_codes, const std::vector<int32_t>& ref_text_ids,
-                                             const float* spk_emb, int lang_id, const std::vector<int32_t>* instr_ids) {
+                                             const float* spk_emb, int lang_id, const std::vector<int32_t>* instr_ids,
+                                             std::vector<int32_t>* trail) {
     std::vector<float> mid;
     auto add = [&]() { mid.resize(mid.size() + 2048); return mid.data() + mid.size() - 2048; };
     std::vector<float> pad(2048), t(2048), marker(2048), e(2048), sum(2048);
@@ -154,7 +163,7 @@ PromptData PromptBuilder::build_clone_prompt(const HostAssets& a, const std::vec
         sum2(marker.data(), sum.data(), add());
     }
     sum2(marker.data(), pad.data(), add());                                                      // :100-106
-    return build_core(a, text_ids, &lang_id, nullptr, spk_emb, instr_ids, &mid);
+    return build_core(a, text_ids, &lang_id, nullptr, spk_emb, instr_ids, &mid, trail);
 }
 
 // ---------------- Chunker ----------------

@@ -53,12 +53,15 @@ struct PromptData { std::vector<float> embd; int n_rows = 0; }; // rows of 2048 
 
 class PromptBuilder { // prompt.rs:26-277 ; token ids are supplied by the caller (tokenizer is row f-3, out of scope)
 public:
+    // trail != null: [EXT] streaming-text layout (q3tts_spec.h "streaming-text talker input"): the prompt stops after
+    // [text(BOS) + E0(PAD)], adds [text(t_0) + E0(BOS)], and *trail receives t_1 .. t_{n-1}, TEXT_EOS; needs text_ids.size() >= 1
     static PromptData build_core(const HostAssets& a, const std::vector<int32_t>& text_ids, const int* lang_id,
                                  const int* spk_id, const float* spk_emb, const std::vector<int32_t>* instr_ids,
-                                 const std::vector<float>* mid_rows);
+                                 const std::vector<float>* mid_rows, std::vector<int32_t>* trail = nullptr);
     static PromptData build_clone_prompt(const HostAssets& a, const std::vector<int32_t>& text_ids,
                                          const std::vector<int32_t>& ref_codes, const std::vector<int32_t>& ref_text_ids,
-                                         const float* spk_emb, int lang_id, const std::vector<int32_t>* instr_ids);
+                                         const float* spk_emb, int lang_id, const std::vector<int32_t>* instr_ids,
+                                         std::vector<int32_t>* trail = nullptr);
 };
 
 class Chunker { // engine.rs:505-541

@@ -152,8 +152,15 @@ void launch_attention_short(hipStream_t st, const float* qkv, int qkv_stride, in
                             float* att = nullptr /*optional f32 rows [ntok][n_head*128]*/);
 void launch_project_blk(hipStream_t st, const float* x, int x_stride, const float* Wblk /*[n_out/16][n_in][16]*/, const float* b,
                         int n_in, int n_out, float* out, int out_stride, int ntok);
+// [EXT] streaming-text feedback (q3tts_spec.h): slot b's last addend is text(ids[b*ids_stride + f]) while f = n_frames[b] < n_trail[b],
+// tts_pad after; text() reads table rows [0, rows) and computes the fallback row in-kernel for any other id
+struct TextTrail {
+    const int32_t* n_frames = nullptr; const int32_t* n_trail = nullptr; const int32_t* ids = nullptr; int ids_stride = 0;
+    const float* table = nullptr; int64_t rows = 0;
+};
+// trail == null: the reference's feedback (every slot adds tts_pad)
 void launch_feedback_keys(hipStream_t st, const float* const* tables, const int64_t* table_rows, const q3_u64* keys, int key_stride,
-                          const float* tts_pad, float* out, int ntok);
+                          const float* tts_pad, float* out, int ntok, const TextTrail* trail = nullptr);
 void launch_gather_rows_keys(hipStream_t st, const float* table, int64_t rows, const q3_u64* keys, int key_stride, int row_len,
                              float* dst, int ntok);
 struct AdvanceKeysArgs {

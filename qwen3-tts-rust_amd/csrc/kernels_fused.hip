@@ -807,9 +807,10 @@ void launch_project_blk(hipStream_t st, const float* x, int x_stride, const floa
 // ===================================================================================================
 // code consumers working on argmax keys
 // ===================================================================================================
+template <bool TRAIL>
 __global__ void __launch_bounds__(256) k_feedback_keys(const float* const* __restrict__ tables, const int64_t* __restrict__ table_rows,
                                                        const u64* __restrict__ keys, int key_stride,
-                                                       const float* __restrict__ tts_pad, float* __restrict__ out) {
+                                                       const float* __restrict__ tts_pad, float* __restrict__ out, TextTrail tt) {
     const int tok = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     float acc = 0.0f;
 #pragma unroll
@@ -819,12 +820,30 @@ __global__ void __launch_bounds__(256) k_feedback_keys(const float* const* __res
         const float v = ((int64_t)c < table_rows[q]) ? tables[q][(size_t)c * 2048 + i] : 0.0f;
         acc = acc + v;
     }
-    acc = acc + tts_pad[i];
+    float last;
+    if constexpr (TRAIL) {
+        const int f = tt.n_frames[tok];
+        if (f < tt.n_trail[tok]) {   // n_trail <= ids_stride: the read stays inside the slot's row
+            const int32_t id = tt.ids[(size_t)tok * tt.ids_stride + f];
+            if (id >= 0 && (int64_t)id < tt.rows) last = tt.table[(size_t)id * 2048 + i];
+            else { // HostAssets::text_embedding fallback, fmod((float)((u64)id * 17 + i), 2) - 1: below 2^24 the float is the exact
+                   // integer and fmod is its low bit; from 2^24 on every float is even
+                const float x = (float)((unsigned long long)(long long)id * 17ull + (unsigned long long)i);
+                last = (x < 16777216.0f ? (float)((uint32_t)x & 1u) : 0.0f) - 1.0f;
+            }
+        } else {
+            last = tts_pad[i];
+        }
+    } else {
+        last = tts_pad[i];
+    }
+    acc = acc + last;
     out[(size_t)tok * 2048 + i] = acc;
 }
 void launch_feedback_keys(hipStream_t st, const float* const* tables, const int64_t* table_rows, const u64* keys, int key_stride,
-                          const float* tts_pad, float* out, int ntok) {
-    hipLaunchKernelGGL(k_feedback_keys, dim3(8, ntok), dim3(256), 0, st, tables, table_rows, keys, key_stride, tts_pad, out);
+                          const float* tts_pad, float* out, int ntok, const TextTrail* trail) {
+    if (trail) hipLaunchKernelGGL(k_feedback_keys<true>, dim3(8, ntok), dim3(256), 0, st, tables, table_rows, keys, key_stride, tts_pad, out, *trail);
+    else hipLaunchKernelGGL(k_feedback_keys<false>, dim3(8, ntok), dim3(256), 0, st, tables, table_rows, keys, key_stride, tts_pad, out, TextTrail());
 }
 
 // project(m_hidden) and the pre-projected E_0[code_0] row side by side: predictor pass-A input rows [0,B) and [B,2B)

@@ -85,6 +85,8 @@ SYMBOLS = [
     "q3tts_tokenizer_open", "q3tts_tokenizer_close", "q3tts_tokenizer_encode", "q3tts_tokenizer_decode", "q3tts_tokenizer_vocab_size",
     "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
+    "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
+    "q3tts_group_submit_text_streaming",
 ]
 
 
@@ -169,6 +171,15 @@ def lib():
                                                  C.POINTER(C.c_int64)]
         L.q3tts_op_sample_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.q3tts_prompt_build_streaming.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                   C.POINTER(C.c_int32)]
+        L.q3tts_submit_trailing.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.POINTER(GenOptions), C.c_void_p, C.c_int32,
+                                            C.POINTER(C.c_int64)]
+        L.q3tts_submit_text_streaming.argtypes = L.q3tts_submit_text_ex.argtypes
+        L.q3tts_generate_batch_trailing.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.c_int32, C.POINTER(GenOptions),
+                                                    C.POINTER(C.c_void_p), C.c_void_p]
+        L.q3tts_group_submit_text_streaming.argtypes = L.q3tts_group_submit_text_ex.argtypes
         _lib = L
     return _lib
 
@@ -240,6 +251,25 @@ class Assets:
         if n < 0:
             raise Q3Error(lib().q3tts_last_error().decode())
         return out[:n].copy()
+
+
+    def prompt_build_streaming(self, text_ids, lang_id=2055, spk_id=None, spk_emb=None, instr_ids=None, ref_codes=None, ref_text_ids=None,
+                               max_rows=4096):
+        """[EXT] streaming-text layout: (prompt rows, trailing ids t_1 .. t_{n-1}, TEXT_EOS); ref_codes given = clone voice"""
+        t = np.ascontiguousarray(text_ids, np.int32)
+        ins = np.ascontiguousarray(instr_ids, np.int32) if instr_ids is not None else None
+        se = np.ascontiguousarray(spk_emb, np.float32) if spk_emb is not None else None
+        rc = np.ascontiguousarray(ref_codes, np.int32).reshape(-1) if ref_codes is not None else None
+        rt = np.ascontiguousarray(ref_text_ids, np.int32) if ref_text_ids is not None else None
+        out = np.zeros((max_rows, 2048), np.float32)
+        trail = np.zeros(max(t.size, 1), np.int32)
+        nt = C.c_int32()
+        n = lib().q3tts_prompt_build_streaming(self.h, _p(t), t.size, -1 if lang_id is None else lang_id, -1 if spk_id is None else spk_id,
+                                               _p(se), _p(ins), ins.size if ins is not None else 0, _p(rc), rc.size if rc is not None else 0,
+                                               _p(rt), rt.size if rt is not None else 0, _p(out), max_rows, _p(trail), trail.size, C.byref(nt))
+        if n < 0:
+            raise Q3Error(lib().q3tts_last_error().decode())
+        return out[:n].copy(), trail[: nt.value].copy()
 
 
 class Sampler:  # LlamaSampler (llama/mod.rs:627-776)
@@ -325,13 +355,18 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
 
     # ---- continuous-batching scheduler (q3tts_submit / poll / fetch / wait) ----
     def submit(self, prompt, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
-               repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0):
+               repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None):
+        """trailing_ids: [EXT] streaming-text input, one text id added to the feedback per frame (None = the reference's feedback)"""
         pr = np.ascontiguousarray(prompt, np.float32)
         r = Request()
         self._fill(r, pr, 0, max_steps, temperature, top_k, top_p, seed, mask_eos)
         o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        if o is None:
+        if trailing_ids is not None:
+            tr = np.ascontiguousarray(trailing_ids, np.int32)
+            _chk(lib().q3tts_submit_trailing(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o) if o is not None else None, _p(tr), tr.size,
+                                             C.byref(rid)))
+        elif o is None:
             _chk(lib().q3tts_submit(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(rid)))
         else:
             _chk(lib().q3tts_submit_ex(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o), C.byref(rid)))
@@ -347,13 +382,16 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         return vid.value
 
     def submit_text(self, voice_id, text_ids, lang_id=2055, instr_ids=None, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42,
-                    mask_eos=True, want_pcm=False, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0):
+                    mask_eos=True, want_pcm=False, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0,
+                    streaming_text=False):
+        """streaming_text: [EXT] upstream's streaming-text layout (q3tts_submit_text_streaming)"""
         t = np.ascontiguousarray(text_ids, np.int32)
         ins = np.ascontiguousarray(instr_ids, np.int32) if instr_ids is not None else None
         sc = SamplerConfig(temperature, top_k, top_p, 1, seed)
         o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        _chk(lib().q3tts_submit_text_ex(self.h, voice_id, _p(t), t.size, lang_id, _p(ins), ins.size if ins is not None else 0, C.byref(sc),
+        fn = lib().q3tts_submit_text_streaming if streaming_text else lib().q3tts_submit_text_ex
+        _chk(fn(self.h, voice_id, _p(t), t.size, lang_id, _p(ins), ins.size if ins is not None else 0, C.byref(sc),
                                         max_steps, 1 if mask_eos else 0, 1 if want_pcm else 0, C.byref(o) if o is not None else None,
                                         C.byref(rid)))
         return rid.value
@@ -399,8 +437,10 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         return {"codes": codes, "pcm": pcm if want_pcm else None, **st}
 
     def generate_batch(self, prompts, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
-                       pcm_per_frame=1920, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0):
-        """per-request values may be given as lists (max_steps, temperature, top_k, top_p, seed, mask_eos and the GenOptions fields)"""
+                       pcm_per_frame=1920, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0,
+                       trailing_ids=None):
+        """per-request values may be given as lists (max_steps, temperature, top_k, top_p, seed, mask_eos and the GenOptions fields);
+        trailing_ids: None, or a list with one entry per request (None or a sequence of text ids, [EXT] streaming-text input)"""
         n = len(prompts)
         reqs = (Request * n)()
         opts = [self._opts(i, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p) for i in range(n)]
@@ -416,7 +456,15 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
             r.codes_out = codes.ctypes.data
             r.pcm_out = pcm.ctypes.data if pcm is not None else None
             r.pcm_capacity = pcm.size if pcm is not None else 0
-        if all(o is None for o in opts):
+        if trailing_ids is not None:
+            if len(trailing_ids) != n:
+                raise Q3Error("trailing_ids needs one entry per request")
+            trs = [np.ascontiguousarray(t if t is not None else [], np.int32) for t in trailing_ids]
+            ptrs = (C.c_void_p * n)(*[t.ctypes.data if t.size else None for t in trs])
+            cnt = np.array([t.size for t in trs], np.int32)
+            arr = (GenOptions * n)(*[o if o is not None else GenOptions(**GEN_DEFAULTS) for o in opts])
+            _chk(lib().q3tts_generate_batch_trailing(self.h, reqs, n, 1 if want_pcm else 0, arr, ptrs, _p(cnt)))
+        elif all(o is None for o in opts):
             _chk(lib().q3tts_generate_batch(self.h, reqs, n, 1 if want_pcm else 0))
         else:
             arr = (GenOptions * n)(*[o if o is not None else GenOptions(**GEN_DEFAULTS) for o in opts])
