@@ -376,6 +376,33 @@ int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t
                          const float* top_p, const float* penalty, const uint64_t* seed, const int32_t* hist, const int32_t* hist_len,
                          int32_t hist_cap, int32_t n_draws, int32_t* out);
 int q3tts_op_project(const float* x, const float* w /* [n_out][n_in] */, const float* b, int32_t n_in, int32_t n_out, float* y);
+/* One codec-decoder GEMM (csrc/codec.hip), as the decoder runs it or with a named kernel form forced.  out[m][n] = epilogue(sum_k A'[m][k] W[n][k]
+ * + bias[n]) with K = taps * cin, k = j * cin + ci -> A' row m + (m / a_segT) * a_skip + j * dil, channel ci (a_segT = 0: unsegmented).  Output row m
+ * starts at out_off + m * ldo + (m / o_segT) * o_skip floats of the out buffer, residual row m at m * ldr + (m / r_segT) * r_skip floats of res.
+ * W is split into hi / lo f16 planes exactly as the decoder does at load.  `out` is read (uploaded) and written back whole, padding included. */
+enum { Q3TTS_GEMM_AUTO = 0, Q3TTS_GEMM_SKINNY4 = 1, Q3TTS_GEMM_SKINNY8 = 2, Q3TTS_GEMM_SKINNY16 = 3, /* k_skinny_gemm<4|8|16>, exact f32 */
+       Q3TTS_GEMM_F32_1 = 4, Q3TTS_GEMM_F32_2 = 5,                                                  /* k_conv_gemm<1|2>, f32 MFMA */
+       Q3TTS_GEMM_H1 = 6, Q3TTS_GEMM_H1_EPL = 7, Q3TTS_GEMM_H2 = 8, Q3TTS_GEMM_H2_EPL = 9,           /* k_conv_gemm_h<MR, EPL>, split f16 */
+       Q3TTS_GEMM_H3 = 10, Q3TTS_GEMM_H3_EPL = 11 };                                                /* k_conv_gemm_h3<..., EPL>, split f16 */
+enum { Q3TTS_EPI_NONE = 0, Q3TTS_EPI_GELU = 1, Q3TTS_EPI_RES_SCALE = 2 /* res + scale[n] * v */, Q3TTS_EPI_RES = 3 /* res + v */,
+       Q3TTS_EPI_SNAKE = 4 /* v + ib[n] * sin^2(ea[n] * v) */ };
+typedef struct q3tts_codec_gemm_desc {
+    int32_t M, N, cin, taps, dil;
+    const float* A; int64_t a_rows; int32_t lda, a_segT, a_skip;      /* A: a_rows x lda floats, history rows included */
+    int32_t a_split, o_split;                                          /* rows stored as [C x f16 hi][C x f16 lo] (input / output) */
+    const float* W; const float* bias;                                 /* W [N][K] f32; bias [N] or NULL */
+    int32_t epi; const float* res; int64_t res_floats; int32_t ldr, r_segT; int64_t r_skip;
+    const float* scale; const float* snake_ea; const float* snake_ib;  /* [N] each, where the epilogue uses them */
+    float* out; int64_t out_floats, out_off; int32_t ldo, o_segT; int64_t o_skip;
+    int64_t ws_floats;                                                 /* split-K workspace */
+    int32_t form, ksplit, reducer;  /* Q3TTS_GEMM_*; forced forms: ksplit >= 1 and reducer 0 = k_splitk_reduce, 1 = k_splitk_reduce4, -1 = none (ksplit 1) */
+    int32_t form_ran, ksplit_ran, reducer_ran;                         /* out: what ran (AUTO: what the decoder's dispatcher chose) */
+} q3tts_codec_gemm_desc;
+/* test entry: runs the GEMM (a forced form whose preconditions fail returns an error and launches nothing) */
+int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d);
+/* host only (no device needed): the decoder's dispatch for d's shape -> form_ran / ksplit_ran / reducer_ran.  Pointers are not dereferenced:
+ * NULL stands for a 16-byte aligned buffer (out_off still applies) */
+int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d);
 
 #ifdef __cplusplus
 }

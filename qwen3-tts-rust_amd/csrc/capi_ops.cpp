@@ -3,6 +3,7 @@
 #include "transformer.h"
 #include "host_logic.h"
 #include "kdev.h"
+#include "codec.h"
 
 using namespace q3;
 #define Q3_API_BEGIN try {
@@ -232,6 +233,21 @@ int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t
     std::vector<q3_u64> res(dout.n);
     dout.download(res.data(), res.size());
     for (size_t i = 0; i < res.size(); i++) out[i] = key_code(res[i]);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d) {
+    Q3_API_BEGIN
+    require_gpu();
+    codec_gemm_run(d);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d) {
+    Q3_API_BEGIN
+    codec_gemm_plan_only(d);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

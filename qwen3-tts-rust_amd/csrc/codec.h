@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+struct q3tts_codec_gemm_desc;
+
 namespace q3 {
 
 struct CodecStateEntry { std::string name; int64_t offset; int rows, cols; }; // one named tensor of a stream's state blob ([rows][cols] f32 at `offset` floats)
@@ -37,5 +39,9 @@ private:
     struct Impl;
     std::unique_ptr<Impl> impl_;
 };
+
+// test entry points (include/q3tts.h: q3tts_op_codec_gemm, q3tts_codec_gemm_plan): one codec GEMM, dispatched as the decoder does or forced
+void codec_gemm_run(q3tts_codec_gemm_desc* d);
+void codec_gemm_plan_only(q3tts_codec_gemm_desc* d); // host only
 
 } // namespace q3

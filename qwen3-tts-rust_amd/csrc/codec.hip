@@ -1,11 +1,13 @@
 // codec.hip -- streaming codec decoder on MI355X: codes -> 24 kHz PCM, "Q3TTS-codec-synth" (see codec.h).
 //
-// Every convolution / linear is one implicit-GEMM kernel on exact-f32 MFMA (v_mfma_f32_32x32x2_f32; bf16 would
-// not hold the 1e-4 RMS PCM bar).  Activations are time-major [T][C]; a causal conv with k taps and dilation d
+// Every convolution / linear is one implicit-GEMM kernel: exact-f32 operands (v_mfma_f32_32x32x2_f32, or the skinny
+// kernel's FMAs) for few rows, a split-f16 form with ~22-bit operands for many rows (see k_conv_gemm_h; bf16 would not
+// hold the 1e-4 RMS PCM bar).  Activations are time-major [T][C]; a causal conv with k taps and dilation d
 // reads its A operand straight from an "extended" buffer whose first (k-1)*d rows are the stream's history, so
 // streaming state lives on the device and chunked decoding equals a full-sequence pass exactly.
 // Transposed convs (k = 2*stride) are the same GEMM with two taps and N = stride*cout columns (r, co).
 #include "codec.h"
+#include "../../include/q3tts.h"
 #include "gguf.h"
 #include <cmath>
 #include <cstdlib>
@@ -21,6 +23,7 @@ struct GemmArgs {
     const float* A; int lda;        // A rows: time-major activations (extended buffer), row stride lda floats
     int cin, dil;                   // K index kk -> tap j = kk / cin, channel ci = kk % cin ; A row = m + j*dil
     const float* W;                 // [N][K] row-major (rearranged at load)
+    const float* wscale;            // [N] 2^-s_n: the split-f16 weights Wh/Wl hold row n scaled by 2^s_n (split_weights); the f32 W is unscaled
     const float* bias;              // [N] or null
     float* out; int ldo;            // out[m][n]
     int M, N, K;
@@ -204,10 +207,13 @@ __global__ void __launch_bounds__(256) k_conv_gemm(GemmArgs g) {
         }
     }
 }
-// Split-f16 form of the same GEMM for large M: every f32 operand x is carried as hi = f16(x), lo = f16(x - hi) (22 significant bits),
-// and a*b is accumulated in f32 as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_32x32x16_f16 -- three passes at the 16x f16 MFMA
-// rate instead of one at the f32 rate.  Weights are split once at load (Wh/Wl, [N][K] f16); activations are split while the tile
-// is staged into LDS.  Relative error per product ~2^-22 (f32: 2^-24); PCM stays within 1e-5 RMS of the double-precision oracle.
+// Split-f16 form of the same GEMM for large M: every f32 operand x is carried as hi = f16(x), lo = f16(x - hi), and a*b is accumulated
+// in f32 as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_32x32x16_f16 -- three passes at the 16x f16 MFMA rate instead of one at the
+// f32 rate.  hi + lo carries ~22 significant bits only while lo is a normal f16, i.e. for |x| >= 2^-3; below that lo has the fixed
+// subnormal step 2^-24 and the representation error is an absolute 2^-25.  Hence weights are split once at load with an exact per-row
+// power-of-two prescale (row n times 2^s_n, max |W[n]| * 2^s_n in [2^13, 2^14): ~22 bits per weight whatever its scale) and every
+// accumulator is multiplied by g.wscale[n] = 2^-s_n before it leaves registers (exact).  Activations are split unscaled while the tile
+// is staged into LDS: 22 bits for |a| >= 2^-3, an absolute 2^-25 below, and |a| <= 65504 (the f16 range) is required.
 // Same tiling, implicit-GEMM addressing, split-K and epilogues as k_conv_gemm<2>; BK = 32 (divides every cin of the decoder).
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef _Float16 h4v __attribute__((ext_vector_type(4)));
@@ -237,6 +243,8 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h(GemmArgs g, const _Float16*
 #pragma unroll
     for (int i = 0; i < NA; i++) { int mm = m0 + (tid + i * 256) / 8; mm = mm < g.M ? mm : g.M - 1; arow[i] = mm + seg_of(mm, g.a_segT) * g.a_skip; }
     const int wrow = (n0 + tid / 4 < g.N) ? n0 + tid / 4 : g.N - 1, wk = 8 * (tid & 3); // columns beyond N re-read row N - 1 (their outputs are never stored)
+    const int scol = n0 + wn * 32 + (lane & 31);
+    const float wsc = g.wscale[scol < g.N ? scol : g.N - 1]; // this lane's column's weight prescale, loaded before the K loop (its latency hides there)
     auto fetch = [&](int k0) {
         const int j = k0 / g.cin, ci0 = k0 % g.cin; // BK divides cin, so a K tile never straddles taps
 #pragma unroll
@@ -298,6 +306,11 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h(GemmArgs g, const _Float16*
     stash();
     lds_barrier();
     multiply();
+    // undo the weight rows' prescale (a power of two: exact) before a split-K slab write as well as before the epilogue
+#pragma unroll
+    for (int t = 0; t < MR; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[t][r] *= wsc;
     __syncthreads(); // the epilogue reuses the operand tiles
     if constexpr (EPL != 0) {
         auto& Ct = sh.Ct; // (the K loop ended on a barrier: the operand tiles are dead)
@@ -455,6 +468,9 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h3(GemmArgs g, const _Float16
     };
     // workgroup barriers of the K loop wait for LDS traffic only: __syncthreads() would also drain the prefetch (s_waitcnt vmcnt(0))
     auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    float wsc[NT]; // the weight prescale of this lane's columns (N % 96 == 0: every column exists), loaded before the K loop
+#pragma unroll
+    for (int u = 0; u < NT; u++) wsc[u] = g.wscale[n0 + u * 32 + (lane & 31)];
     Regs st[PF];
 #pragma unroll
     for (int j = 0; j < PF; j++)
@@ -484,6 +500,12 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h3(GemmArgs g, const _Float16
             }
         }
     }
+#pragma unroll
+    for (int u = 0; u < NT; u++) // undo the weight rows' prescale (a power of two: exact)
+#pragma unroll
+        for (int t = 0; t < MR; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[t][u][r] *= wsc[u];
     __syncthreads(); // the epilogue reuses the operand tiles
     // rows outermost: one row's addresses live at a time (columns outermost made the compiler keep every row's 64-bit addresses in
     // registers: 256 VGPRs, one wave per SIMD).  One call per row tile: a `for t` loop is "too large to unroll" and turns acc[t] into a
@@ -599,22 +621,18 @@ __global__ void __launch_bounds__(512) k_skinny_gemm(GemmArgs g) {
     if (lane < MT && lane < g.M && n < g.N) gemm_store(g, lane, n, gemm_epilogue(g, mine, lane, n));
 }
 static const bool g_codec_f32 = [] { const char* e = std::getenv("Q3_CODEC_F32"); return e && e[0] == '1'; }(); // A/B switch
-static void gemm(hipStream_t st, GemmArgs g, float* ws, size_t ws_floats, const _Float16* wh = nullptr, const _Float16* wl = nullptr) {
-    if (g.M <= 16) {
-        dim3 grid((g.N + 7) / 8);
-        if (g.M <= 4) hipLaunchKernelGGL((k_skinny_gemm<4>), grid, dim3(512), 0, st, g);
-        else if (g.M <= 8) hipLaunchKernelGGL((k_skinny_gemm<8>), grid, dim3(512), 0, st, g);
-        else hipLaunchKernelGGL((k_skinny_gemm<16>), grid, dim3(512), 0, st, g);
-        return;
-    }
+// Which instantiation runs one GEMM: form (Q3TTS_GEMM_*; the SPLIT template argument follows g.a_split), split-K factor, and for ks > 1
+// the reducer (0 = k_splitk_reduce, 1 = k_splitk_reduce4; -1 = none).  Host only: plan_gemm touches no device memory.
+struct GemmPlan { int form, ks, red; };
+// the production choice: shape, pointer alignment, workspace size and the Q3_CODEC_* switches (read once per process)
+static GemmPlan plan_gemm(const GemmArgs& g, size_t ws_floats, bool has_split_w) {
+    if (g.M <= 16) return GemmPlan{g.M <= 4 ? Q3TTS_GEMM_SKINNY4 : g.M <= 8 ? Q3TTS_GEMM_SKINNY8 : Q3TTS_GEMM_SKINNY16, 1, -1};
     const bool small = g.M <= 32;
     const int tiles = small ? ((g.N + 127) / 128) * ((g.M + 31) / 32) : ((g.N + 63) / 64) * ((g.M + 63) / 64);
     int ksplit = 1;
     while (tiles * ksplit < 256 && ksplit < 16 && (g.K / (ksplit * 2)) % 16 == 0 && g.K / (ksplit * 2) >= 128 &&
            (size_t)(ksplit * 2) * g.M * g.N <= ws_floats) ksplit *= 2;
-    g.ws = ws;
-    static const int xcd_on = [] { const char* e = std::getenv("Q3_CODEC_XCD"); return e ? atoi(e) : 1; }();
-    g.xcd_swizzle = xcd_on;
+    const bool ws_a16 = (reinterpret_cast<uintptr_t>(g.ws) & 15) == 0;
     static const int h3_min_wgs = [] { const char* e = std::getenv("Q3_CODEC_H3_MIN_WGS"); return e ? atoi(e) : 128; }(); // workgroups from which the 128 x 96 tile serves (0 = never)
     static const int h3_max_n = [] { const char* e = std::getenv("Q3_CODEC_H3_MAXN"); return e ? atoi(e) : 1 << 30; }();
     static const int epl_on = [] { const char* e = std::getenv("Q3_CODEC_H3_EPL"); return e ? atoi(e) : 1; }();
@@ -623,9 +641,9 @@ static void gemm(hipStream_t st, GemmArgs g, float* ws, size_t ws_floats, const 
     // (3.68 -> 3.40 ms per 16-stream pass), but next to the frame loop the extra workgroups cost more than they save (C3 664 -> 650-657 audio-s/s)
     static const int h3_wgs = [] { const char* e = std::getenv("Q3_CODEC_H3_WGS"); return e ? atoi(e) : 0; }();
     static const int h3_min_tiles = [] { const char* e = std::getenv("Q3_CODEC_H3_MIN_TILES"); return e ? atoi(e) : 96; }();
-    if (!small && wh && !g_codec_f32 && g.cin % 32 == 0 && h3_min_wgs > 0 && g.N % 96 == 0 && g.N <= h3_max_n) {
+    if (!small && has_split_w && !g_codec_f32 && g.cin % 32 == 0 && h3_min_wgs > 0 && g.N % 96 == 0 && g.N <= h3_max_n) {
         const int tiles3 = (g.N / 96) * ((g.M + 127) / 128);
-        const bool vec_ok = epl_on && epilogue4_ok(g) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0;
+        const bool vec_ok = epl_on && epilogue4_ok(g) && ws_a16;
         int ks = 1;
         if (vec_ok && h3_wgs > 0 && tiles3 >= h3_min_tiles && tiles3 < h3_wgs) {
             static const int cand[] = {2, 3, 4, 6, 7, 8, 12, 14, 16};
@@ -635,21 +653,10 @@ static void gemm(hipStream_t st, GemmArgs g, float* ws, size_t ws_floats, const 
                 if (tiles3 * c >= h3_wgs) break;
             }
         }
-        if (tiles3 * ks >= h3_min_wgs) {
-            g.ws = ws;
-            const dim3 grid3(g.N / 96, (g.M + 127) / 128, vec_ok ? ks : 1);
-#define Q3_H3(EPLV, PFV) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, true>), grid3, dim3(256), 0, st, g, wh, wl); \
-                              else hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, false>), grid3, dim3(256), 0, st, g, wh, wl); } while (0)
-            if (!vec_ok) Q3_H3(0, 1); else Q3_H3(1, 1); // PF = 2 / 3 measured equal at 64 slots and slower at 256 (profiles/r02_codec_ab_sweeps.txt)
-#undef Q3_H3
-            if (ks > 1) {
-                const size_t n = (size_t)g.M * g.N;
-                hipLaunchKernelGGL(k_splitk_reduce4, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, g, ks);
-            }
-            return;
-        }
+        // PF = 2 / 3 measured equal at 64 slots and slower at 256 (profiles/r02_codec_ab_sweeps.txt): PF = 1 throughout
+        if (tiles3 * ks >= h3_min_wgs) return GemmPlan{vec_ok ? Q3TTS_GEMM_H3_EPL : Q3TTS_GEMM_H3, ks, ks > 1 ? 1 : -1};
     }
-    if (!small && wh && !g_codec_f32 && g.cin % 32 == 0) { // large M: split-f16 matrix cores (K tile 32)
+    if (!small && has_split_w && !g_codec_f32 && g.cin % 32 == 0) { // large M: split-f16 matrix cores (K tile 32)
         static const int big_m = [] { const char* e = std::getenv("Q3_CODEC_BM128"); return e ? atoi(e) : 1024; }(); // rows from which the 128-row tile is used
         // measured inside the 64-stream pipeline: N = 768 (K = 5376) 96 -> 64 us with the tall tile, N <= 384 no gain
         const bool tall = g.M >= big_m && g.N >= 512 && ((g.N + 63) / 64) * ((g.M + 127) / 128) >= 160;
@@ -658,26 +665,78 @@ static void gemm(hipStream_t st, GemmArgs g, float* ws, size_t ws_floats, const 
         int ks = 1;
         while (t2 * ks < wg_target && ks < 16 && (g.K / (ks * 2)) % 32 == 0 && g.K / (ks * 2) >= 128 && (size_t)(ks * 2) * g.M * g.N <= ws_floats) ks *= 2;
         static const int epl4 = [] { const char* e = std::getenv("Q3_CODEC_EPL4"); return e ? atoi(e) : 1; }();
-        const bool vec_ok = epl4 && epilogue4_ok(g) && (reinterpret_cast<uintptr_t>(g.ws) & 15) == 0;
-#define Q3_H(MRV, EPLV, GRID) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h<MRV, EPLV, true>), GRID, dim3(256), 0, st, g, wh, wl); \
-                                   else hipLaunchKernelGGL((k_conv_gemm_h<MRV, EPLV, false>), GRID, dim3(256), 0, st, g, wh, wl); } while (0)
-        const dim3 grid_t((g.N + 63) / 64, (g.M + 127) / 128, ks), grid_s((g.N + 63) / 64, (g.M + 63) / 64, ks);
-        if (vec_ok) { if (tall) Q3_H(2, 1, grid_t); else Q3_H(1, 1, grid_s); }
-        else { if (tall) Q3_H(2, 0, grid_t); else Q3_H(1, 0, grid_s); }
+        const bool vec_ok = epl4 && epilogue4_ok(g) && ws_a16;
+        const int form = tall ? (vec_ok ? Q3TTS_GEMM_H2_EPL : Q3TTS_GEMM_H2) : (vec_ok ? Q3TTS_GEMM_H1_EPL : Q3TTS_GEMM_H1);
+        return GemmPlan{form, ks, ks > 1 ? (vec_ok ? 1 : 0) : -1};
+    }
+    return GemmPlan{small ? Q3TTS_GEMM_F32_1 : Q3TTS_GEMM_F32_2, ksplit, ksplit > 1 ? 0 : -1};
+}
+// why a plan cannot run on these arguments (nullptr: it can) -- the preconditions every kernel relies on, checked before anything is launched
+static const char* gemm_plan_error(const GemmArgs& g, const GemmPlan& p, size_t ws_floats, bool has_split_w) {
+    const int f = p.form;
+    if (f < Q3TTS_GEMM_SKINNY4 || f > Q3TTS_GEMM_H3_EPL) return "unknown GEMM form";
+    if (g.M < 1 || g.N < 1 || g.cin < 4 || g.K % g.cin != 0 || g.dil < 1) return "bad GEMM shape";
+    if (g.cin % 4 != 0 || g.lda % 4 != 0 || g.lda < g.cin) return "A rows need cin % 4 == 0 and lda % 4 == 0, lda >= cin";
+    if (p.ks < 1 || g.K % p.ks != 0) return "ksplit must divide K";
+    const bool skinny = f <= Q3TTS_GEMM_SKINNY16, f32 = f == Q3TTS_GEMM_F32_1 || f == Q3TTS_GEMM_F32_2, h3 = f >= Q3TTS_GEMM_H3;
+    const bool epl = f == Q3TTS_GEMM_H1_EPL || f == Q3TTS_GEMM_H2_EPL || f == Q3TTS_GEMM_H3_EPL;
+    const bool ws_a16 = (reinterpret_cast<uintptr_t>(g.ws) & 15) == 0;
+    if (skinny) {
+        if (g.M > (f == Q3TTS_GEMM_SKINNY4 ? 4 : f == Q3TTS_GEMM_SKINNY8 ? 8 : 16)) return "skinny form: M exceeds its row count";
+        if (p.ks != 1) return "skinny form: no split-K";
+        return nullptr;
+    }
+    if (f32 && (g.cin % 16 != 0 || (g.K / p.ks) % 16 != 0)) return "f32 form: cin and K / ksplit must be multiples of 16";
+    if (!f32) {
+        if (!has_split_w || !g.wscale) return "split-f16 form without split weights";
+        if (g.cin % 32 != 0 || (g.K / p.ks) % 32 != 0) return "split-f16 form: cin and K / ksplit must be multiples of 32";
+        if (h3 && g.N % 96 != 0) return "h3 form: N must be a multiple of 96";
+        if (epl && !(epilogue4_ok(g) && ws_a16)) return "16-byte epilogue form: pointers / strides not 16-byte aligned or N % 4 != 0";
+    }
+    if (p.ks > 1) {
+        if (p.ks > 64) return "ksplit too large";
+        if ((size_t)p.ks * g.M * g.N > ws_floats) return "split-K workspace too small";
+        if (p.red != 0 && p.red != 1) return "split-K needs a reducer (0 or 1)";
+        if (p.red == 1 && !(epilogue4_ok(g) && ws_a16)) return "k_splitk_reduce4: pointers / strides not 16-byte aligned or N % 4 != 0";
+    } else if (p.red != -1) return "a reducer without split-K";
+    return nullptr;
+}
+static void launch_gemm(hipStream_t st, const GemmArgs& g, const GemmPlan& p, const _Float16* wh, const _Float16* wl) {
+    const dim3 b256(256);
+    const unsigned ks = (unsigned)p.ks;
+#define Q3_H(MRV, EPLV, GRID) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h<MRV, EPLV, true>), GRID, b256, 0, st, g, wh, wl); \
+                                   else hipLaunchKernelGGL((k_conv_gemm_h<MRV, EPLV, false>), GRID, b256, 0, st, g, wh, wl); } while (0)
+#define Q3_H3(EPLV, PFV) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, true>), grid3, b256, 0, st, g, wh, wl); \
+                              else hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, false>), grid3, b256, 0, st, g, wh, wl); } while (0)
+    const dim3 grid_sk((g.N + 7) / 8), grid_t((g.N + 63) / 64, (g.M + 127) / 128, ks), grid_s((g.N + 63) / 64, (g.M + 63) / 64, ks);
+    const dim3 grid3(g.N / 96, (g.M + 127) / 128, ks);
+    switch (p.form) {
+    case Q3TTS_GEMM_SKINNY4: hipLaunchKernelGGL((k_skinny_gemm<4>), grid_sk, dim3(512), 0, st, g); break;
+    case Q3TTS_GEMM_SKINNY8: hipLaunchKernelGGL((k_skinny_gemm<8>), grid_sk, dim3(512), 0, st, g); break;
+    case Q3TTS_GEMM_SKINNY16: hipLaunchKernelGGL((k_skinny_gemm<16>), grid_sk, dim3(512), 0, st, g); break;
+    case Q3TTS_GEMM_F32_1: hipLaunchKernelGGL((k_conv_gemm<1>), dim3((g.N + 127) / 128, (g.M + 31) / 32, ks), b256, 0, st, g); break;
+    case Q3TTS_GEMM_F32_2: hipLaunchKernelGGL((k_conv_gemm<2>), dim3((g.N + 63) / 64, (g.M + 63) / 64, ks), b256, 0, st, g); break;
+    case Q3TTS_GEMM_H1: Q3_H(1, 0, grid_s); break;
+    case Q3TTS_GEMM_H1_EPL: Q3_H(1, 1, grid_s); break;
+    case Q3TTS_GEMM_H2: Q3_H(2, 0, grid_t); break;
+    case Q3TTS_GEMM_H2_EPL: Q3_H(2, 1, grid_t); break;
+    case Q3TTS_GEMM_H3: Q3_H3(0, 1); break;
+    case Q3TTS_GEMM_H3_EPL: Q3_H3(1, 1); break;
+    default: throw Error("unknown GEMM form");
+    }
 #undef Q3_H
-        if (ks > 1) {
-            const size_t n = (size_t)g.M * g.N;
-            if (vec_ok) hipLaunchKernelGGL(k_splitk_reduce4, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, g, ks);
-            else hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, ks);
-        }
-        return;
-    }
-    if (small) hipLaunchKernelGGL((k_conv_gemm<1>), dim3((g.N + 127) / 128, (g.M + 31) / 32, ksplit), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_conv_gemm<2>), dim3((g.N + 63) / 64, (g.M + 63) / 64, ksplit), dim3(256), 0, st, g);
-    if (ksplit > 1) {
+#undef Q3_H3
+    if (p.ks > 1) {
         const size_t n = (size_t)g.M * g.N;
-        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, ksplit);
+        if (p.red == 1) hipLaunchKernelGGL(k_splitk_reduce4, dim3((unsigned)((n / 4 + 255) / 256)), b256, 0, st, g, p.ks);
+        else hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), b256, 0, st, g, p.ks);
     }
+}
+static int xcd_swizzle_on() { static const int on = [] { const char* e = std::getenv("Q3_CODEC_XCD"); return e ? atoi(e) : 1; }(); return on; }
+static void gemm(hipStream_t st, GemmArgs g, float* ws, size_t ws_floats, const _Float16* wh = nullptr, const _Float16* wl = nullptr) {
+    g.ws = ws;
+    g.xcd_swizzle = xcd_swizzle_on();
+    launch_gemm(st, g, plan_gemm(g, ws_floats, wh != nullptr), wh, wl);
 }
 
 // ---------------- small elementwise / reduction kernels ----------------
@@ -908,7 +967,27 @@ __global__ void __launch_bounds__(256) k_conv_out_win(const float* __restrict__ 
     }
 }
 // ---------------- host side ----------------
-struct ConvW { DevBuf<float> w, b; DevBuf<_Float16> wh, wl; int N = 0, K = 0, cin = 0, taps = 1, dil = 1; };
+// hi / lo f16 split of a rearranged weight matrix [N][K] for the split-f16 kernels, with the exact per-row prescale they undo (k_conv_gemm_h):
+// row n is multiplied by 2^s_n, max |W[n]| * 2^s_n in [2^13, 2^14), so hi keeps 11 bits and lo (a normal f16 for elements down to ~2^-16 of
+// the row maximum) 11 more whatever the row's scale; wscale[n] = 2^-s_n.  Unscaled, rows of ~1e-2 (1/sqrt(fan_in)) already lost bits to lo's
+// subnormal step.
+static void split_weights(const float* w, int N, int K, _Float16* wh, _Float16* wl, float* wscale) {
+    for (int n = 0; n < N; n++) {
+        const float* r = w + (size_t)n * K;
+        float mx = 0.0f;
+        for (int k = 0; k < K; k++) mx = std::max(mx, std::fabs(r[k]));
+        int e = 0, s = 0;
+        if (mx > 0.0f && std::isfinite(mx)) { std::frexp(mx, &e); s = std::min(14 - e, 126); } // mx in [2^(e-1), 2^e); 2^-126 stays a normal f32
+        wscale[n] = std::ldexp(1.0f, -s);
+        const float up = std::ldexp(1.0f, s);
+        for (int k = 0; k < K; k++) {
+            const float x = r[k] * up; // exact (a result below the f32 normal range is below the f16 one too)
+            const _Float16 h = (_Float16)x;
+            wh[(size_t)n * K + k] = h; wl[(size_t)n * K + k] = (_Float16)(x - (float)h);
+        }
+    }
+}
+struct ConvW { DevBuf<float> w, b, wsc; DevBuf<_Float16> wh, wl; int N = 0, K = 0, cin = 0, taps = 1, dil = 1; };
 struct Snake { DevBuf<float> ea, inv_eb; int C = 0; };
 // A causal conv's streaming state.  `hist` is the persistent store [n_streams][H][C]; the rows a call works on live in a
 // per-lane batched extended buffer [G][(H + T)][C] (Scratch::work[id]): history first, then the call's T new rows.
@@ -952,12 +1031,15 @@ struct CodecDecoder::Impl {
         return std::vector<float>(p, p + t.nbytes / 4);
     }
     static void up_f(DevBuf<float>& d, const std::vector<float>& v) { d.alloc(v.size()); d.upload(v.data(), v.size()); }
-    // hi/lo f16 split of a rearranged weight matrix for k_conv_gemm_h (only matrices that can see >= 64 rows per call need it)
-    static void split_w(ConvW& c, const std::vector<float>& r) {
+    // split weights (+ row scales) of a rearranged weight matrix [N][K] for the split-f16 GEMMs
+    static void split_w(ConvW& c, const std::vector<float>& r, int N) {
+        const int K = (int)(r.size() / N);
         std::vector<_Float16> h(r.size()), l(r.size());
-        for (size_t i = 0; i < r.size(); i++) { h[i] = (_Float16)r[i]; l[i] = (_Float16)(r[i] - (float)h[i]); }
+        std::vector<float> sc(N);
+        split_weights(r.data(), N, K, h.data(), l.data(), sc.data());
         c.wh.alloc(h.size()); c.wh.upload(h.data(), h.size());
         c.wl.alloc(l.size()); c.wl.upload(l.data(), l.size());
+        up_f(c.wsc, sc);
     }
     // causal conv weight [cout][cin][k] -> Wr[co][j*cin + ci]
     void make_conv(ConvW& c, const Gguf& g, const std::string& wn, const std::string& bn, int cout, int cin, int k, int dil) {
@@ -966,11 +1048,11 @@ struct CodecDecoder::Impl {
         std::vector<float> r((size_t)cout * cin * k);
         for (int co = 0; co < cout; co++) for (int ci = 0; ci < cin; ci++) for (int j = 0; j < k; j++)
             r[((size_t)co * k + j) * cin + ci] = w[((size_t)co * cin + ci) * k + j];
-        up_f(c.w, r); split_w(c, r);
+        up_f(c.w, r); split_w(c, r, cout);
         if (!bn.empty()) up_f(c.b, tensor(g, bn));
         c.N = cout; c.K = cin * k; c.cin = cin; c.taps = k; c.dil = dil;
     }
-    void make_linear(ConvW& c, const std::vector<float>& w, int N, int K) { up_f(c.w, w); split_w(c, w); c.N = N; c.K = K; c.cin = K; c.taps = 1; c.dil = 1; }
+    void make_linear(ConvW& c, const std::vector<float>& w, int N, int K) { up_f(c.w, w); split_w(c, w, N); c.N = N; c.K = K; c.cin = K; c.taps = 1; c.dil = 1; }
     // transposed conv weight [cin][cout][k], stride s (k == 2s or k == s) -> Wr[(r,co)][j*cin+ci], tap 0 = previous frame
     void make_convt(ConvW& c, const Gguf& g, const std::string& wn, const std::string& bn, int cin, int cout, int k, int s) {
         auto w = tensor(g, wn);
@@ -987,7 +1069,7 @@ struct CodecDecoder::Impl {
                 } else r[(size_t)(rr * cout + co) * cin + ci] = w[((size_t)ci * cout + co) * k + rr];
             }
         }
-        up_f(c.w, r); split_w(c, r); up_f(c.b, br);
+        up_f(c.w, r); split_w(c, r, s * cout); up_f(c.b, br);
         c.N = s * cout; c.K = taps * cin; c.cin = cin; c.taps = taps; c.dil = 1;
     }
     void make_snake(Snake& s, const Gguf& g, const std::string& an, const std::string& bn, int C) {
@@ -1015,7 +1097,7 @@ struct CodecDecoder::Impl {
                   bool o_split = false) {
         GemmArgs g{};
         g.a_split = a_split ? 1 : 0; g.o_split = o_split ? 1 : 0;
-        g.A = A.p; g.lda = lda; g.cin = c.cin; g.dil = c.dil; g.W = c.w.p; g.bias = c.b.n ? c.b.p : nullptr; g.out = out.p; g.ldo = ldo;
+        g.A = A.p; g.lda = lda; g.cin = c.cin; g.dil = c.dil; g.W = c.w.p; g.wscale = c.wsc.p; g.bias = c.b.n ? c.b.p : nullptr; g.out = out.p; g.ldo = ldo;
         g.M = M; g.N = c.N; g.K = c.K; g.epi = epi; g.res = res.p; g.ldr = ldr; g.scale = scale;
         g.a_segT = A.segT; g.a_skip = (int)A.skip_rows;
         g.o_segT = out.segT; g.o_skip = out.skip_rows * out_C;
@@ -1417,6 +1499,72 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     Q3_LAUNCH_CHECK();
     for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
     return T;
+}
+
+// ---------------- test entry points: one GEMM as the decoder dispatches it, or with a named form forced ----------------
+static GemmArgs desc_args(const q3tts_codec_gemm_desc& d) {
+    GemmArgs g{};
+    g.lda = d.lda; g.cin = d.cin; g.dil = d.dil; g.M = d.M; g.N = d.N; g.K = d.cin * d.taps; g.ldo = d.ldo; g.epi = d.epi; g.ldr = d.ldr;
+    g.a_segT = d.a_segT > 0 ? d.a_segT : SEG_NONE; g.a_skip = d.a_segT > 0 ? d.a_skip : 0;
+    g.o_segT = d.o_segT > 0 ? d.o_segT : SEG_NONE; g.o_skip = d.o_segT > 0 ? d.o_skip : 0;
+    g.r_segT = d.r_segT > 0 ? d.r_segT : SEG_NONE; g.r_skip = d.r_segT > 0 ? d.r_skip : 0;
+    g.a_split = d.a_split ? 1 : 0; g.o_split = d.o_split ? 1 : 0;
+    g.xcd_swizzle = xcd_swizzle_on();
+    return g;
+}
+// every access the kernels make stays inside the caller's buffers
+static void check_desc(const q3tts_codec_gemm_desc& d) {
+    Q3_CHECK(d.M >= 1 && d.N >= 1 && d.cin >= 1 && d.taps >= 1 && d.dil >= 1 && d.epi >= EPI_NONE && d.epi <= EPI_SNAKE, "bad codec GEMM descriptor");
+    Q3_CHECK(d.a_segT >= 0 && d.o_segT >= 0 && d.r_segT >= 0 && d.a_skip >= 0 && d.o_skip >= 0 && d.r_skip >= 0 && d.out_off >= 0 && d.ws_floats >= 0,
+             "negative segment / offset fields");
+    Q3_CHECK(d.A && d.W && d.out && d.lda >= d.cin && d.ldo >= d.N, "codec GEMM: A, W and out are required; lda >= cin, ldo >= N");
+    const long long m = d.M - 1;
+    const long long arow = m + (d.a_segT > 0 ? m / d.a_segT * d.a_skip : 0) + (long long)(d.taps - 1) * d.dil;
+    Q3_CHECK(arow < d.a_rows, "A rows read beyond a_rows");
+    Q3_CHECK(d.out_off + m * d.ldo + (d.o_segT > 0 ? m / d.o_segT * d.o_skip : 0) + d.N <= d.out_floats, "output rows beyond out_floats");
+    if (d.epi == EPI_RES || d.epi == EPI_RES_SCALE)
+        Q3_CHECK(d.res && d.ldr >= d.N && m * d.ldr + (d.r_segT > 0 ? m / d.r_segT * d.r_skip : 0) + d.N <= d.res_floats, "residual rows beyond res_floats");
+    Q3_CHECK(d.epi != EPI_RES_SCALE || d.scale, "EPI_RES_SCALE needs scale");
+    Q3_CHECK(d.epi != EPI_SNAKE || (d.snake_ea && d.snake_ib), "EPI_SNAKE needs ea / ib");
+}
+void codec_gemm_plan_only(q3tts_codec_gemm_desc* d) {
+    Q3_CHECK(d && d->M >= 1 && d->N >= 1 && d->cin >= 1 && d->taps >= 1 && d->out_off >= 0, "bad codec GEMM descriptor");
+    GemmArgs g = desc_args(*d);
+    // pointers only matter for alignment here: NULL = an aligned buffer (256, like hipMalloc); nothing is dereferenced
+    auto at = [](const float* p, long long off) { return reinterpret_cast<float*>((p ? reinterpret_cast<uintptr_t>(p) : (uintptr_t)256) + 4 * (uintptr_t)off); };
+    g.A = at(d->A, 0); g.W = at(d->W, 0); g.bias = d->bias; g.res = at(d->res, 0); g.scale = at(d->scale, 0);
+    g.snake_ea = at(d->snake_ea, 0); g.snake_ib = at(d->snake_ib, 0); g.out = at(d->out, d->out_off); g.ws = at(nullptr, 0);
+    const GemmPlan p = plan_gemm(g, (size_t)d->ws_floats, true);
+    d->form_ran = p.form; d->ksplit_ran = p.ks; d->reducer_ran = p.red;
+}
+void codec_gemm_run(q3tts_codec_gemm_desc* d) {
+    Q3_CHECK(d, "null codec GEMM descriptor");
+    check_desc(*d);
+    GemmArgs g = desc_args(*d);
+    const int N = g.N, K = g.K;
+    const bool res_used = g.epi == EPI_RES || g.epi == EPI_RES_SCALE;
+    DevBuf<float> dA((size_t)d->a_rows * d->lda), dW((size_t)N * K), dsc(N), dbias(d->bias ? N : 0), dres(res_used ? d->res_floats : 0);
+    DevBuf<float> dscale(d->scale ? N : 0), dea(d->snake_ea ? N : 0), dib(d->snake_ib ? N : 0), dout(d->out_floats), dws(std::max<int64_t>(d->ws_floats, 4));
+    DevBuf<_Float16> dwh((size_t)N * K), dwl((size_t)N * K);
+    g.A = dA.p; g.W = dW.p; g.wscale = dsc.p; g.bias = dbias.p; g.res = dres.p; g.scale = dscale.p; g.snake_ea = dea.p; g.snake_ib = dib.p;
+    g.out = dout.p + d->out_off; g.ws = dws.p;
+    const GemmPlan p = d->form == Q3TTS_GEMM_AUTO ? plan_gemm(g, (size_t)d->ws_floats, true) : GemmPlan{d->form, d->ksplit, d->reducer};
+    if (const char* why = gemm_plan_error(g, p, (size_t)d->ws_floats, true)) throw Error(std::string("codec GEMM form not applicable: ") + why);
+    std::vector<_Float16> h((size_t)N * K), l((size_t)N * K);
+    std::vector<float> sc(N);
+    split_weights(d->W, N, K, h.data(), l.data(), sc.data()); // exactly as the decoder does at load
+    dA.upload(d->A, dA.n); dW.upload(d->W, dW.n); dwh.upload(h.data(), h.size()); dwl.upload(l.data(), l.size()); dsc.upload(sc.data(), N);
+    if (d->bias) dbias.upload(d->bias, N);
+    if (res_used) dres.upload(d->res, dres.n);
+    if (d->scale) dscale.upload(d->scale, N);
+    if (d->snake_ea) dea.upload(d->snake_ea, N);
+    if (d->snake_ib) dib.upload(d->snake_ib, N);
+    dout.upload(d->out, dout.n);
+    launch_gemm(0, g, p, dwh.p, dwl.p);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    dout.download(d->out, dout.n);
+    d->form_ran = p.form; d->ksplit_ran = p.ks; d->reducer_ran = p.red;
 }
 
 } // namespace q3

@@ -86,7 +86,7 @@ SYMBOLS = [
     "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
-    "q3tts_group_submit_text_streaming",
+    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan",
 ]
 
 
@@ -674,6 +674,77 @@ def op_project(x, w, b):
     y = np.zeros(b.size, np.float32)
     _chk(lib().q3tts_op_project(_p(x), _p(w), _p(b), x.size, b.size, _p(y)))
     return y
+
+
+# codec GEMM forms (include/q3tts.h Q3TTS_GEMM_*) and epilogues (Q3TTS_EPI_*)
+GEMM_FORMS = {"AUTO": 0, "SKINNY4": 1, "SKINNY8": 2, "SKINNY16": 3, "F32_1": 4, "F32_2": 5, "H1": 6, "H1_EPL": 7, "H2": 8, "H2_EPL": 9,
+              "H3": 10, "H3_EPL": 11}
+GEMM_FORM_NAMES = {v: k for k, v in GEMM_FORMS.items()}
+EPI_NONE, EPI_GELU, EPI_RES_SCALE, EPI_RES, EPI_SNAKE = range(5)
+
+
+class CodecGemmDesc(C.Structure):  # q3tts_codec_gemm_desc
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("cin", C.c_int32), ("taps", C.c_int32), ("dil", C.c_int32),
+                ("A", C.c_void_p), ("a_rows", C.c_int64), ("lda", C.c_int32), ("a_segT", C.c_int32), ("a_skip", C.c_int32),
+                ("a_split", C.c_int32), ("o_split", C.c_int32),
+                ("W", C.c_void_p), ("bias", C.c_void_p),
+                ("epi", C.c_int32), ("res", C.c_void_p), ("res_floats", C.c_int64), ("ldr", C.c_int32), ("r_segT", C.c_int32), ("r_skip", C.c_int64),
+                ("scale", C.c_void_p), ("snake_ea", C.c_void_p), ("snake_ib", C.c_void_p),
+                ("out", C.c_void_p), ("out_floats", C.c_int64), ("out_off", C.c_int64), ("ldo", C.c_int32), ("o_segT", C.c_int32), ("o_skip", C.c_int64),
+                ("ws_floats", C.c_int64),
+                ("form", C.c_int32), ("ksplit", C.c_int32), ("reducer", C.c_int32),
+                ("form_ran", C.c_int32), ("ksplit_ran", C.c_int32), ("reducer_ran", C.c_int32)]
+
+
+def _codec_gemm_desc(M, N, cin, taps, dil, lda, a_rows, a_segT, a_skip, epi, ldr, res_floats, r_segT, r_skip, ldo, out_floats, out_off,
+                     o_segT, o_skip, a_split, o_split, ws_floats, form, ksplit, reducer):
+    d = CodecGemmDesc()
+    d.M, d.N, d.cin, d.taps, d.dil = M, N, cin, taps, dil
+    d.lda, d.a_rows, d.a_segT, d.a_skip = lda, a_rows, a_segT, a_skip
+    d.epi, d.ldr, d.res_floats, d.r_segT, d.r_skip = epi, ldr, res_floats, r_segT, r_skip
+    d.ldo, d.out_floats, d.out_off, d.o_segT, d.o_skip = ldo, out_floats, out_off, o_segT, o_skip
+    d.a_split, d.o_split, d.ws_floats = int(bool(a_split)), int(bool(o_split)), ws_floats
+    d.form = GEMM_FORMS[form] if isinstance(form, str) else form
+    d.ksplit, d.reducer = ksplit, reducer
+    return d
+
+
+def op_codec_gemm(A, W, M, cin, taps=1, dil=1, out=None, ldo=None, out_off=0, o_segT=0, o_skip=0, a_segT=0, a_skip=0, bias=None,
+                  epi=EPI_NONE, res=None, ldr=0, r_segT=0, r_skip=0, scale=None, ea=None, ib=None, a_split=False, o_split=False,
+                  ws_floats=1 << 22, form="AUTO", ksplit=1, reducer=-1):
+    """one codec-decoder GEMM on the device (q3tts_op_codec_gemm).  A: [a_rows][lda] (float32, or the bit pattern of split rows);
+    W: [N][cin*taps] float32; out: the whole output buffer (1-D float32 / uint32; uploaded, then returned written back whole).
+    Returns (out buffer, (form name, ksplit, reducer)) of what ran."""
+    A = np.ascontiguousarray(A)
+    assert A.ndim == 2 and A.dtype.itemsize == 4
+    W = np.ascontiguousarray(W, np.float32)
+    N = W.shape[0]
+    ldo = N if ldo is None else ldo
+    if out is None:
+        out = np.zeros(out_off + M * ldo, np.float32)
+    out = np.array(out, copy=True).reshape(-1)
+    assert out.dtype.itemsize == 4
+    vecs = [None if v is None else np.ascontiguousarray(v, np.float32) for v in (bias, scale, ea, ib)]
+    for v in vecs:
+        assert v is None or v.size == N
+    res = None if res is None else np.ascontiguousarray(res, np.float32).reshape(-1)
+    d = _codec_gemm_desc(M, N, cin, taps, dil, A.shape[1], A.shape[0], a_segT, a_skip, epi, ldr, 0 if res is None else res.size, r_segT, r_skip,
+                         ldo, out.size, out_off, o_segT, o_skip, a_split, o_split, ws_floats, form, ksplit, reducer)
+    d.A, d.W, d.out, d.res = _p(A), _p(W), _p(out), _p(res)
+    d.bias, d.scale, d.snake_ea, d.snake_ib = (_p(v) for v in vecs)
+    lib().q3tts_op_codec_gemm.argtypes = [C.POINTER(CodecGemmDesc)]
+    _chk(lib().q3tts_op_codec_gemm(C.byref(d)))
+    return out, (GEMM_FORM_NAMES[d.form_ran], d.ksplit_ran, d.reducer_ran)
+
+
+def codec_gemm_plan(M, N, cin, taps=1, dil=1, lda=None, ldo=None, out_off=0, o_segT=0, o_skip=0, a_segT=0, a_skip=0, epi=EPI_NONE, ldr=0,
+                    r_segT=0, r_skip=0, a_split=False, o_split=False, ws_floats=1 << 22):
+    """the decoder's dispatch for one GEMM shape (host only; every buffer taken as 16-byte aligned, out shifted by out_off floats)"""
+    d = _codec_gemm_desc(M, N, cin, taps, dil, cin if lda is None else lda, 0, a_segT, a_skip, epi, ldr, 0, r_segT, r_skip,
+                         N if ldo is None else ldo, 0, out_off, o_segT, o_skip, a_split, o_split, ws_floats, 0, 1, -1)
+    lib().q3tts_codec_gemm_plan.argtypes = [C.POINTER(CodecGemmDesc)]
+    _chk(lib().q3tts_codec_gemm_plan(C.byref(d)))
+    return GEMM_FORM_NAMES[d.form_ran], d.ksplit_ran, d.reducer_ran
 
 
 def mel(audio):
