@@ -404,6 +404,36 @@ int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d);
  * NULL stands for a 16-byte aligned buffer (out_off still applies) */
 int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d);
 
+/* One transformer attention step (spec S4' per-head RMSNorm, S5 M-RoPE, S6 f16 KV append, S7 causal GQA attention, S2 quantisation of the
+ * output) for one layer, as Transformer::forward dispatches it or with a named kernel form forced.  Every buffer is a host buffer.
+ *   qkv      [ntok] rows of qkv_stride floats: n_head q heads, n_kv k heads, n_kv v heads of 128 each
+ *   tokens   uniform_pos >= 0: token t is sequence t at slot uniform_pos, all four position streams = uniform_pos (seq / slot / pos unused);
+ *            otherwise seq[t], slot[t] (the cache position written, = #cached before it) and pos[t][4]
+ *   paging   page_table [n_seq][max_pages] of physical pages, or NULL = identity (sequence s owns page s; slots < 64)
+ *   caches   K [n_pages][n_layer][n_kv][16][64][8] and V [n_pages][n_layer][n_kv][64][128] f16, uploaded and written back whole
+ *   RoPE     tables built as the Transformer builds them from rope_base for n_ctx positions; positions are clamped to [0, n_ctx-1]
+ *   outputs  att [ntok][n_head*128] f32 (UNFUSED, SHORT1/2, GGML; may be NULL), aq [ntok][n_head*128] / ad [ntok][n_head*4] (every form but GGML)
+ * AUTO runs what plan_attention picks for the flags below (hpw1_max <= 0: the engine's threshold); form_ran reports the form.  A form whose
+ * preconditions fail returns an error and launches nothing. */
+enum { Q3TTS_ATTN_AUTO = 0, Q3TTS_ATTN_UNFUSED = 1 /* k_qk_rope_append + k_attention */, Q3TTS_ATTN_FUSED = 2 /* k_attention_fused */,
+       Q3TTS_ATTN_SHORT1 = 3, Q3TTS_ATTN_SHORT2 = 4 /* k_attention_short<1|2> */, Q3TTS_ATTN_GGML = 5 /* k_gg_qk_rope_append + k_gg_attention */ };
+typedef struct q3tts_attention_desc {
+    int32_t n_head, n_kv, n_layer, layer, ntok;
+    const float* qkv; int32_t qkv_stride;
+    const float* q_norm; const float* k_norm;                          /* [128] each */
+    float eps, rope_base; int32_t n_ctx; int32_t mrope_sec[4];
+    const int32_t* seq; const int32_t* slot; const int32_t* pos; int32_t uniform_pos;
+    const int32_t* page_table; int32_t n_seq, max_pages;
+    uint16_t* k_cache; uint16_t* v_cache; int32_t n_pages;
+    int32_t fused, fused_max_tok, same_seq, short_attn_min, hpw1_max, float_mode, ggml_mode; /* AUTO's Transformer flags */
+    int32_t form;
+    float* att; int8_t* aq; uint16_t* ad;
+    int32_t form_ran;
+} q3tts_attention_desc;
+int q3tts_op_attention(q3tts_attention_desc* d);
+/* host only (no device needed): the form AUTO picks for d's ntok / n_head / n_kv / flags -> form_ran; no buffer is read */
+int q3tts_attention_plan(q3tts_attention_desc* d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,13 @@ void q3o_attn_head_ggml(const float* q, const uint16_t* K, const uint16_t* V, si
 float q3o_sumsq_vec(const float* x, int64_t d);
 void q3o_rmsnorm(const float* x, const float* g, int64_t d, float eps, float* y);
 void q3o_headnorm128(const float* x, const float* g, float eps, float* y);
+/* spec S5 RoPE tables [n_ctx][64] (cos / sin of p * base^(-i/64) in double, rounded to f32) */
+void q3o_rope_tables(float rope_base, int n_ctx, float* rope_cos, float* rope_sin);
+/* spec S4' + S5 for one head vector: RMSNorm (ggml != 0: the ggml-mode norm), then M-RoPE at pos[4] with sections sec; out may alias x */
+void q3o_head_rope(const float* x, const float* g, float eps, const int32_t pos[4], const int32_t sec[4], const float* rope_cos,
+                   const float* rope_sin, int n_ctx, int ggml, float* out);
+/* spec S7: one query head against n cached f16 positions, element (pos, d) of K / V at base[pos * stride + d] */
+void q3o_attn_head(const float* q, const uint16_t* K, const uint16_t* V, size_t stride, int n, float* out);
 
 /* ---------------- transformer (talker / predictor) ---------------- */
 typedef struct q3o_layer {

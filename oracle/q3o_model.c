@@ -93,13 +93,7 @@ q3o_model* q3o_model_load(const char* path, int n_ctx, char* err, size_t errlen)
     m->vcache = (uint16_t*)calloc(kvn, 2);
     m->rope_cos = (float*)malloc((size_t)n_ctx * 64 * 4);
     m->rope_sin = (float*)malloc((size_t)n_ctx * 64 * 4);
-    for (int p = 0; p < n_ctx; p++)
-        for (int i = 0; i < 64; i++) {
-            double inv = pow((double)m->rope_base, -(double)i / 64.0);
-            double ang = (double)p * inv;
-            m->rope_cos[p * 64 + i] = (float)cos(ang);
-            m->rope_sin[p * 64 + i] = (float)sin(ang);
-        }
+    q3o_rope_tables(m->rope_base, n_ctx, m->rope_cos, m->rope_sin);
     m->n_threads = 0;
     return m;
 }
@@ -120,8 +114,34 @@ static void mv(const q3o_gguf_tensor* w, const int8_t* xq, const uint16_t* xd, c
 static void rmsn(const float* x, const float* g, int64_t d, float eps, float* y) { if (q3o_arith_mode()) q3o_rmsnorm_ggml(x, g, d, eps, y); else q3o_rmsnorm(x, g, d, eps, y); }
 static int is_float_type(int t) { return t == Q3_T_F32 || t == Q3_T_F16 || t == Q3_T_BF16; }
 
+/* spec S5 tables [n_ctx][64] */
+void q3o_rope_tables(float rope_base, int n_ctx, float* rope_cos, float* rope_sin) {
+    for (int p = 0; p < n_ctx; p++)
+        for (int i = 0; i < 64; i++) {
+            double inv = pow((double)rope_base, -(double)i / 64.0);
+            double ang = (double)p * inv;
+            rope_cos[p * 64 + i] = (float)cos(ang);
+            rope_sin[p * 64 + i] = (float)sin(ang);
+        }
+}
+
+/* spec S4' + S5: per-head RMSNorm of one 128-vector, then NeoX M-RoPE pair i with position stream q3_mrope_stream(i, sec),
+ * positions clamped to [0, n_ctx-1].  out may alias x. */
+void q3o_head_rope(const float* x, const float* g, float eps, const int32_t pos[4], const int32_t sec[4], const float* rope_cos,
+                   const float* rope_sin, int n_ctx, int ggml, float* out) {
+    float tmp[128];
+    if (ggml) q3o_headnorm128_ggml(x, g, eps, tmp);
+    else q3o_headnorm128(x, g, eps, tmp);
+    for (int i = 0; i < 64; i++) {
+        int32_t pp = pos[q3_mrope_stream(i, sec)];
+        if (pp < 0) pp = 0;
+        if (pp >= n_ctx) pp = n_ctx - 1;
+        q3_rope_pair(tmp[i], tmp[i + 64], rope_cos[pp * 64 + i], rope_sin[pp * 64 + i], &out[i], &out[i + 64]);
+    }
+}
+
 /* spec S7: one query head against n cached positions. K/V: f16, element (pos,d) at base[pos*stride+d] */
-static void attn_head(const float* q, const uint16_t* K, const uint16_t* V, size_t stride, int n, float* out) {
+void q3o_attn_head(const float* q, const uint16_t* K, const uint16_t* V, size_t stride, int n, float* out) {
     const float scale = 0.08838834764831845f; /* 1/sqrt(128) */
     float M = 0, L = 0, O[128];
     float s[Q3_ATT_CHUNK], p[Q3_ATT_CHUNK];
@@ -203,17 +223,10 @@ int q3o_model_eval(q3o_model* m, const float* x, const int32_t pos[4], float* hi
         mv(L->wq, xq, xd, xn, q); mv(L->wk, xq, xd, xn, k); mv(L->wv, xq, xd, xn, v);
         uint16_t* Kl = m->kcache + (size_t)l * m->n_ctx * stride;
         uint16_t* Vl = m->vcache + (size_t)l * m->n_ctx * stride;
-        float tmp[128];
         for (int hh = 0; hh < nh + nkv; hh++) {
             float* vec = hh < nh ? q + 128 * hh : k + 128 * (hh - nh);
-            if (q3o_arith_mode()) q3o_headnorm128_ggml(vec, (const float*)(hh < nh ? L->q_norm->data : L->k_norm->data), m->eps, tmp);
-            else q3o_headnorm128(vec, (const float*)(hh < nh ? L->q_norm->data : L->k_norm->data), m->eps, tmp);
-            for (int i = 0; i < 64; i++) {
-                int32_t pp = pos[q3_mrope_stream(i, m->mrope_sec)];
-                if (pp < 0) pp = 0;
-                if (pp >= m->n_ctx) pp = m->n_ctx - 1;
-                q3_rope_pair(tmp[i], tmp[i + 64], m->rope_cos[pp * 64 + i], m->rope_sin[pp * 64 + i], &vec[i], &vec[i + 64]);
-            }
+            q3o_head_rope(vec, (const float*)(hh < nh ? L->q_norm->data : L->k_norm->data), m->eps, pos, m->mrope_sec, m->rope_cos, m->rope_sin,
+                          m->n_ctx, q3o_arith_mode(), vec);
         }
         for (int i = 0; i < dkv; i++) {
             Kl[(size_t)slot * stride + i] = q3_f32_to_f16(k[i]);
@@ -224,7 +237,7 @@ int q3o_model_eval(q3o_model* m, const float* x, const int32_t pos[4], float* hi
         for (int hh = 0; hh < nh; hh++) {
             int kvh = hh / grp;
             if (q3o_arith_mode()) q3o_attn_head_ggml(q + 128 * hh, Kl + 128 * kvh, Vl + 128 * kvh, stride, slot + 1, att + 128 * hh);
-            else attn_head(q + 128 * hh, Kl + 128 * kvh, Vl + 128 * kvh, stride, slot + 1, att + 128 * hh);
+            else q3o_attn_head(q + 128 * hh, Kl + 128 * kvh, Vl + 128 * kvh, stride, slot + 1, att + 128 * hh);
         }
         q3o_quant_act(att, dq, xq, xd);
         mv(L->wo, xq, xd, att, o);

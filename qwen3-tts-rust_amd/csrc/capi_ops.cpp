@@ -13,7 +13,117 @@ static void require_gpu() {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error("no HIP device available: the HIP path is the only compute path (no CPU fallback)");
 }
 
+// ---- q3tts_op_attention: one layer's attention step through the Transformer's launchers ----
+static int attention_op_plan(const q3tts_attention_desc& d) {
+    AttnPlanIn a;
+    a.ntok = d.ntok; a.fused = d.fused != 0; a.fused_max_tok = d.fused_max_tok; a.same_seq = d.same_seq != 0; a.short_attn_min = d.short_attn_min;
+    a.n_head = d.n_head; a.n_kv = d.n_kv; a.hpw1_max = d.hpw1_max > 0 ? d.hpw1_max : short_attn_hpw1_max();
+    a.float_mode = d.float_mode != 0; a.ggml_mode = d.ggml_mode != 0;
+    return plan_attention(a);
+}
+
+// every precondition of the form, checked on the host before anything is allocated or launched
+static void attention_op_check(const q3tts_attention_desc& d, int form) {
+    Q3_CHECK(form >= ATTN_UNFUSED && form <= ATTN_GGML, "unknown attention form");
+    Q3_CHECK(d.n_head >= 1 && d.n_kv >= 1 && d.n_head % d.n_kv == 0, "n_head must be a multiple of n_kv");
+    Q3_CHECK(d.n_layer >= 1 && d.layer >= 0 && d.layer < d.n_layer && d.ntok >= 1 && d.ntok <= 65535, "bad layer / token count");
+    Q3_CHECK(d.qkv && d.q_norm && d.k_norm && d.k_cache && d.v_cache && d.qkv_stride >= (d.n_head + 2 * d.n_kv) * 128, "bad qkv / norm / cache buffers");
+    Q3_CHECK(d.n_ctx >= 1 && d.n_pages >= 1, "bad n_ctx / n_pages");
+    if (form != ATTN_GGML) Q3_CHECK(d.aq && d.ad, "aq / ad are required");
+    else Q3_CHECK(d.att, "the ggml form produces att only");
+    if (d.uniform_pos < 0) Q3_CHECK(d.seq && d.slot && d.pos, "per-token seq / slot / pos are required without uniform_pos");
+    if (d.page_table) {
+        Q3_CHECK(d.n_seq >= 1 && d.max_pages >= 1, "bad page table shape");
+        for (int64_t i = 0; i < (int64_t)d.n_seq * d.max_pages; i++)
+            Q3_CHECK(d.page_table[i] >= 0 && d.page_table[i] < d.n_pages, "page table entry out of range");
+    }
+    const bool short_form = form == ATTN_SHORT1 || form == ATTN_SHORT2;
+    if (short_form) Q3_CHECK(d.n_head == 2 * d.n_kv, "the short forms need n_head == 2 * n_kv");
+    std::map<std::pair<int, int>, int> seen;   // (seq, slot) -> tokens
+    std::map<int, int> per_seq;
+    for (int t = 0; t < d.ntok; t++) {
+        const int seq = d.uniform_pos >= 0 ? t : d.seq[t], slot = d.uniform_pos >= 0 ? d.uniform_pos : d.slot[t];
+        Q3_CHECK(slot >= 0 && slot < d.n_ctx, "slot out of [0, n_ctx)");
+        if (d.page_table) Q3_CHECK(seq >= 0 && seq < d.n_seq && slot < d.max_pages * 64, "sequence or slot beyond the page table");
+        else Q3_CHECK(seq >= 0 && seq < d.n_pages && slot < 64, "identity paging: sequence beyond the cache or slot beyond its one page");
+        if (short_form) Q3_CHECK(slot < 64, "the short forms read page 0 only: slot must be < 64");
+        Q3_CHECK(seen[std::make_pair(seq, slot)]++ == 0, "two tokens write the same (sequence, slot)");
+        if (++per_seq[seq] > 1) Q3_CHECK(form == ATTN_UNFUSED || form == ATTN_GGML, "the fused and short forms need one token per sequence");
+    }
+}
+
+static void attention_op_run(q3tts_attention_desc* dp) {
+    Q3_CHECK(dp, "null attention descriptor");
+    q3tts_attention_desc& d = *dp;
+    Q3_CHECK(d.ntok >= 1 && d.n_head >= 1 && d.n_kv >= 1, "bad attention shape");
+    const int form = d.form == Q3TTS_ATTN_AUTO ? attention_op_plan(d) : d.form;
+    attention_op_check(d, form);
+    const int nt = d.ntok, dq = d.n_head * 128, qs = d.qkv_stride;
+    DevBuf<float> qkv((size_t)nt * qs); qkv.upload(d.qkv, qkv.n);
+    DevBuf<float> qn(128), kn(128); qn.upload(d.q_norm, 128); kn.upload(d.k_norm, 128);
+    std::vector<float> hc, hs;
+    build_rope_tables(d.rope_base, d.n_ctx, hc, hs);
+    DevBuf<float> rc(hc.size()), rs(hs.size()); rc.upload(hc.data(), hc.size()); rs.upload(hs.data(), hs.size());
+    DevBuf<int32_t> sec(4); sec.upload(d.mrope_sec, 4);
+    DevBuf<int32_t> dseq, dslot, dpos, dtab;
+    TokMeta tm{nullptr, nullptr, nullptr};
+    if (d.uniform_pos >= 0) tm.uniform_pos = d.uniform_pos;
+    else {
+        dseq.alloc(nt); dseq.upload(d.seq, nt); dslot.alloc(nt); dslot.upload(d.slot, nt); dpos.alloc((size_t)nt * 4); dpos.upload(d.pos, (size_t)nt * 4);
+        tm.seq = dseq.p; tm.slot = dslot.p; tm.pos = dpos.p;
+    }
+    const size_t cache_halfs = (size_t)d.n_pages * d.n_layer * d.n_kv * 8192;
+    DevBuf<uint16_t> kc(cache_halfs), vc(cache_halfs);
+    kc.upload(d.k_cache, cache_halfs); vc.upload(d.v_cache, cache_halfs);
+    KvCache kv;
+    kv.k = kc.p; kv.v = vc.p; kv.page_table = nullptr; kv.max_pages = d.page_table ? d.max_pages : 1; kv.n_layer = d.n_layer; kv.n_kv = d.n_kv;
+    if (d.page_table) { dtab.alloc((size_t)d.n_seq * d.max_pages); dtab.upload(d.page_table, dtab.n); kv.page_table = dtab.p; }
+    DevBuf<float> att((size_t)nt * dq), qrot, scores;
+    DevBuf<int8_t> aq((size_t)nt * dq); DevBuf<uint16_t> ad((size_t)nt * (dq / 32));
+    switch (form) {
+    case ATTN_UNFUSED:
+        qrot.alloc((size_t)nt * dq);
+        launch_qk_rope_append(0, qkv.p, qs, nullptr, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, qrot.p, nt);
+        launch_attention(0, qrot.p, d.n_head, d.n_kv, tm, kv, d.layer, att.p, aq.p, ad.p, nt);
+        break;
+    case ATTN_FUSED:
+        launch_attention_fused(0, qkv.p, qs, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, aq.p, ad.p, nt);
+        break;
+    case ATTN_SHORT1: case ATTN_SHORT2:
+        launch_attention_short(0, form == ATTN_SHORT1 ? 1 : 2, qkv.p, qs, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv,
+                               d.layer, aq.p, ad.p, nt, att.p);
+        break;
+    default: // ATTN_GGML: q is rotated in place in the qkv copy
+        scores.alloc((size_t)nt * d.n_head * d.n_ctx);
+        gg_qk_rope_append(0, qkv.p, qs, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, nt);
+        gg_attention(0, qkv.p, qs, d.n_head, d.n_kv, tm, kv, d.layer, att.p, scores.p, d.n_ctx, nt);
+        break;
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    kc.download(d.k_cache, cache_halfs); vc.download(d.v_cache, cache_halfs);
+    if (d.att && form != ATTN_FUSED) att.download(d.att, att.n);
+    if (form != ATTN_GGML) { aq.download(d.aq, aq.n); ad.download(d.ad, ad.n); }
+    d.form_ran = form;
+}
+
 extern "C" {
+
+int q3tts_op_attention(q3tts_attention_desc* d) {
+    Q3_API_BEGIN
+    require_gpu();
+    attention_op_run(d);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_attention_plan(q3tts_attention_desc* d) {
+    Q3_API_BEGIN
+    Q3_CHECK(d && d->ntok >= 1 && d->n_kv >= 1 && d->n_head >= 1, "bad attention shape");
+    d->form_ran = attention_op_plan(*d);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 
 int q3tts_op_gemv_q8(const void* w, int32_t n, int32_t k, const int8_t* xq, const uint16_t* xd, int32_t ntok, float* y, int32_t lpr) {
     Q3_API_BEGIN

@@ -41,7 +41,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         int min_tok = 8;
         if (const char* e = std::getenv("Q3_SHORT_ATTN_MIN")) min_tok = atoi(e); // 0 = never
         // (the engine drives the predictor through positions 0..16 only -- 2 prompt rows + 15 code passes -- i.e. one KV page)
-        predictor_->set_short_attention(min_tok);
+        predictor_->set_short_attention(min_tok, 17);
     }
     Q3_CHECK(talker_->hp().n_embd == Q3_EMBD, "talker n_embd must be 2048 (reference hard-codes 2048-wide rows)");
     dP_ = predictor_->hp().n_embd;

@@ -146,10 +146,13 @@ void launch_attention_fused(hipStream_t st, const float* qkv, int qkv_stride, in
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad,
                             int ntok);
-void launch_attention_short(hipStream_t st, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
+// k_attention_short<hpw>: hpw = q heads per wave (1 or 2); needs n_head == 2*n_kv and every slot < 64 (page 0 of the sequence only)
+void launch_attention_short(hipStream_t st, int hpw, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad, int ntok,
                             float* att = nullptr /*optional f32 rows [ntok][n_head*128]*/);
+// largest token count for which the engine runs k_attention_short<1> (Q3_SHORT_ATTN_HPW1_MAX, default 128); above it <2>
+int short_attn_hpw1_max();
 void launch_project_blk(hipStream_t st, const float* x, int x_stride, const float* Wblk /*[n_out/16][n_in][16]*/, const float* b,
                         int n_in, int n_out, float* out, int out_stride, int ntok);
 // [EXT] streaming-text feedback (q3tts_spec.h): slot b's last addend is text(ids[b*ids_stride + f]) while f = n_frames[b] < n_trail[b],

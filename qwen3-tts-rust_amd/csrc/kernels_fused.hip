@@ -727,12 +727,15 @@ __global__ void __launch_bounds__(64) k_attention_short(const float* __restrict_
     Q3_STAMP(6);
     Q3_STAMP_FLUSH();
 }
-void launch_attention_short(hipStream_t st, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
+int short_attn_hpw1_max() {
+    // one q head per wave while that still leaves the chip under-filled (measured crossover: see DESIGN section 4)
+    static const int v = [] { const char* e = std::getenv("Q3_SHORT_ATTN_HPW1_MAX"); return e ? atoi(e) : 128; }();
+    return v;
+}
+void launch_attention_short(hipStream_t st, int hpw, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad, int ntok, float* att) {
-    // one q head per wave while that still leaves the chip under-filled (measured crossover: see DESIGN section 4)
-    static const int hpw1_max = [] { const char* e = std::getenv("Q3_SHORT_ATTN_HPW1_MAX"); return e ? atoi(e) : 128; }();
-    if (ntok <= hpw1_max)
+    if (hpw == 1)
         hipLaunchKernelGGL(k_attention_short<1>, dim3(n_head, ntok), dim3(64), 0, st, qkv, qkv_stride, n_head, n_kv, q_norm_w, k_norm_w, eps, rope_cos,
                            rope_sin, n_ctx, mrope_sec, tm, kv, layer, aq, ad, att);
     else

@@ -348,19 +348,41 @@ Transformer::Transformer(const std::string& path, int n_ctx, int max_tok) : n_ct
     if (float_mode_) { foutput_ = make_fmat(g, {"output.weight"}, d); fused = false; }
     else output_ = make_mat(g, {{"output.weight", 0}}, hp_.n_vocab, d);
     if (ggml_mode_) gg_output_ = gg_load(g, "output.weight", hp_.n_vocab, d);
-    // RoPE tables: same double-precision expressions as the oracle (spec S5)
-    std::vector<float> c((size_t)n_ctx * 64), s((size_t)n_ctx * 64);
-    for (int p = 0; p < n_ctx; p++)
-        for (int i = 0; i < 64; i++) {
-            const double inv = std::pow((double)hp_.rope_base, -(double)i / 64.0);
-            const double ang = (double)p * inv;
-            c[(size_t)p * 64 + i] = (float)std::cos(ang);
-            s[(size_t)p * 64 + i] = (float)std::sin(ang);
-        }
+    std::vector<float> c, s;
+    build_rope_tables(hp_.rope_base, n_ctx, c, s);
     rope_cos_.alloc(c.size()); rope_cos_.upload(c.data(), c.size());
     rope_sin_.alloc(s.size()); rope_sin_.upload(s.data(), s.size());
     d_mrope_.alloc(4); d_mrope_.upload(hp_.mrope_sec, 4);
     alloc_workspace();
+}
+
+// RoPE tables: same double-precision expressions as the oracle (spec S5)
+void build_rope_tables(float rope_base, int n_ctx, std::vector<float>& c, std::vector<float>& s) {
+    c.assign((size_t)n_ctx * 64, 0.0f); s.assign((size_t)n_ctx * 64, 0.0f);
+    for (int p = 0; p < n_ctx; p++)
+        for (int i = 0; i < 64; i++) {
+            const double inv = std::pow((double)rope_base, -(double)i / 64.0);
+            const double ang = (double)p * inv;
+            c[(size_t)p * 64 + i] = (float)std::cos(ang);
+            s[(size_t)p * 64 + i] = (float)std::sin(ang);
+        }
+}
+
+int plan_attention(const AttnPlanIn& a) {
+    if (a.ggml_mode) return ATTN_GGML;
+    // the single-wave form: wide steps of one token per sequence, two q heads per kv head
+    if (a.short_attn_min > 0 && a.ntok >= a.short_attn_min && !a.same_seq && a.n_head == 2 * a.n_kv)
+        return a.ntok <= a.hpw1_max ? ATTN_SHORT1 : ATTN_SHORT2;
+    // k_attention_fused belongs to the 5-launch layer path (quantised weights, at most fused_max_tok tokens, one token per sequence)
+    if (!a.float_mode && a.fused && a.ntok <= a.fused_max_tok && !a.same_seq) return ATTN_FUSED;
+    return ATTN_UNFUSED;
+}
+
+int Transformer::attention_form(int ntok) const {
+    AttnPlanIn a;
+    a.ntok = ntok; a.fused = fused; a.fused_max_tok = fused_max_tok_; a.same_seq = same_seq_; a.short_attn_min = short_attn_min_;
+    a.n_head = hp_.n_head; a.n_kv = hp_.n_kv; a.hpw1_max = short_attn_hpw1_max(); a.float_mode = float_mode_; a.ggml_mode = ggml_mode_;
+    return plan_attention(a);
 }
 
 // second context over the same weights: see transformer.h
@@ -444,10 +466,24 @@ void Transformer::gemv(hipStream_t st, const Q8Mat& w, int row0, int nrows, cons
 void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMeta& tm, const KvCache& kv, float* hidden_out) {
     Q3_CHECK(ntok >= 1 && ntok <= max_tok_, "ntok out of range");
     const int d = hp_.n_embd, dq = hp_.n_head * 128, dkv = hp_.n_kv * 128, ff = hp_.n_ff;
-    if (ggml_mode_) { last_fused_ = false; last_ntok_ = ntok; forward_ggml(st, in, ntok, tm, kv, hidden_out); return; }
+    const int af = attention_form(ntok);
+    if (af == ATTN_GGML) { last_fused_ = false; last_ntok_ = ntok; forward_ggml(st, in, ntok, tm, kv, hidden_out); return; }
     if (float_mode_) { last_fused_ = false; last_ntok_ = ntok; forward_float(st, in, ntok, tm, kv, hidden_out); return; }
     const bool use_fused = fused && ntok <= fused_max_tok_; // batched steps (ntok > 8) take the weight-stationary token-sweep GEMM path
     last_fused_ = use_fused; last_ntok_ = ntok;
+    auto attention = [&](const Layer& L, int l, float* att) {
+        if (af == ATTN_SHORT1 || af == ATTN_SHORT2)
+            launch_attention_short(st, af == ATTN_SHORT1 ? 1 : 2, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
+                                   rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok, att);
+        else if (af == ATTN_FUSED)
+            launch_attention_fused(st, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
+                                   rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok);
+        else {
+            launch_qk_rope_append(st, qkv_.p, dq + 2 * dkv, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
+                                  rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, qrot_.p, ntok);
+            launch_attention(st, qrot_.p, hp_.n_head, hp_.n_kv, tm, kv, l, att, aq_.p, ad_.p, ntok);
+        }
+    };
     if (use_fused) {
         // residual stream ping-pongs h_ <-> h2_: a fused prologue may not overwrite what other workgroups still read
         for (int l = 0; l < hp_.n_layer; l++) {
@@ -459,18 +495,7 @@ void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMe
             if (timer) timer->begin(st);
             launch_gemv_q8_norm(st, L.wqkv, 0, dq + 2 * dkv, a, qkv_.p, dq + 2 * dkv, ntok, nullptr);
             if (timer) timer->end(st, (double)L.wqkv.bytes());
-            if (same_seq_) {
-                launch_qk_rope_append(st, qkv_.p, dq + 2 * dkv, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                      rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, qrot_.p, ntok);
-                launch_attention(st, qrot_.p, hp_.n_head, hp_.n_kv, tm, kv, l, nullptr, aq_.p, ad_.p, ntok);
-            } else {
-                if (short_attn_min_ > 0 && ntok >= short_attn_min_ && hp_.n_head == 2 * hp_.n_kv)
-                    launch_attention_short(st, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                           rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok);
-                else
-                launch_attention_fused(st, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                       rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok);
-            }
+            attention(L, l, nullptr);
             gemv(st, L.wo, 0, d, aq_.p, ad_.p, parts_o_.p, d, ntok);
             NormPro b{};
             b.h_in = h_.p; b.h_stride = d; b.parts = parts_o_.p; b.nparts = 1; b.parts_stride = d; b.parts_slab = (size_t)ntok * d; b.h_out = h2_.p;
@@ -504,14 +529,7 @@ void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMe
         a.h_out = h_.p; a.g = L.attn_norm; a.eps = hp_.eps; a.d = d; a.xq = xq_.p; a.xd = xd_.p;
         norm(a);
         gemv(st, L.wqkv, 0, dq + 2 * dkv, xq_.p, xd_.p, qkv_.p, dq + 2 * dkv, ntok);
-        if (short_attn_min_ > 0 && ntok >= short_attn_min_ && !same_seq_ && hp_.n_head == 2 * hp_.n_kv)
-            launch_attention_short(st, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
-                                   n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok);
-        else {
-            launch_qk_rope_append(st, qkv_.p, dq + 2 * dkv, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                  rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, qrot_.p, ntok);
-            launch_attention(st, qrot_.p, hp_.n_head, hp_.n_kv, tm, kv, l, nullptr, aq_.p, ad_.p, ntok);
-        }
+        attention(L, l, nullptr);
         NormArgs b{};
         b.h_in = h_.p; b.h_stride = d; b.parts = parts_o_.p; b.nparts = 1; b.parts_stride = d; b.h_out = h_.p;
         b.g = L.ffn_norm; b.eps = hp_.eps; b.d = d; b.xq = xq_.p; b.xd = xd_.p;
@@ -558,14 +576,16 @@ void Transformer::forward_float(hipStream_t st, const Input& in, int ntok, const
         launch_gemv_float(st, w, 0, w.N, x, xs, out, os, ntok);
         if (timer) timer->end(st, (double)w.bytes());
     };
+    const int af = attention_form(ntok);
+    Q3_CHECK(af != ATTN_FUSED, "float mode has no fused attention form");
     for (int l = 0; l < hp_.n_layer; l++) {
         const Layer& L = layers_[l];
         if (l == 0) norm(in.x, in.x_stride, in.idx_keys, in.idx_stride, nullptr, L.attn_norm, xnf_.p);
         else norm(h_.p, d, nullptr, 0, parts_d_.p, L.attn_norm, xnf_.p);
         fgemv(L.fqkv, xnf_.p, d, qkv_.p, dq + 2 * dkv);
-        if (short_attn_min_ > 0 && ntok >= short_attn_min_ && !same_seq_ && hp_.n_head == 2 * hp_.n_kv)
-            launch_attention_short(st, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
-                                   n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok, attf_.p);
+        if (af == ATTN_SHORT1 || af == ATTN_SHORT2)
+            launch_attention_short(st, af == ATTN_SHORT1 ? 1 : 2, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
+                                   rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok, attf_.p);
         else {
             launch_qk_rope_append(st, qkv_.p, dq + 2 * dkv, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
                                   n_ctx_, d_mrope_.p, tm, kv, l, qrot_.p, ntok);

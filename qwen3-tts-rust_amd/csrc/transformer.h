@@ -17,6 +17,24 @@ struct TfHparams {
     int32_t mrope_sec[4] = {0, 0, 0, 0};
 };
 
+// The attention forms of spec S7 (S4' per-head RMSNorm, S5 M-RoPE, S6 f16 KV append, causal GQA softmax.V), numbered as q3tts.h's
+// Q3TTS_ATTN_*: UNFUSED = k_qk_rope_append + k_attention, FUSED = k_attention_fused, SHORT1 / SHORT2 = k_attention_short<1|2>,
+// GGML = k_gg_qk_rope_append + k_gg_attention (the Q3_SPEC=ggml arithmetic).
+enum AttnForm { ATTN_UNFUSED = 1, ATTN_FUSED = 2, ATTN_SHORT1 = 3, ATTN_SHORT2 = 4, ATTN_GGML = 5 };
+struct AttnPlanIn {
+    int ntok = 1;
+    bool fused = true; int fused_max_tok = 8;   // Transformer::fused and the 5-launch layer path's token limit
+    bool same_seq = false;                      // several tokens of one sequence in the step
+    int short_attn_min = 0;                     // 0 = the short form is off
+    int n_head = 1, n_kv = 1;
+    int hpw1_max = 128;                         // short_attn_hpw1_max()
+    bool float_mode = false, ggml_mode = false;
+};
+// host only: the form Transformer::forward runs for one step (its launches depend on nothing else)
+int plan_attention(const AttnPlanIn& in);
+// spec S5 RoPE tables [n_ctx][64]: cos / sin of p * base^(-i/64), in double, rounded once to f32
+void build_rope_tables(float rope_base, int n_ctx, std::vector<float>& cos_out, std::vector<float>& sin_out);
+
 class Transformer {
 public:
     Transformer(const std::string& gguf_path, int n_ctx, int max_tok);
@@ -45,9 +63,12 @@ public:
     void head(hipStream_t st, int tok0, int tok_count, int row0, int nrows, float* logits, int logits_stride,
               const ArgmaxEpi* am = nullptr, int nrows_valid = -1, float* hidden_out = nullptr);
     void set_same_seq_tokens(bool v) { same_seq_ = v; }
-    // every cached context of this model stays <= 64 positions (the code predictor): fold attention into the o-proj launch
-    // sequences never exceed 64 positions (one KV page): steps of at least `min_tok` tokens use the single-wave attention kernel
-    void set_short_attention(int min_tok) { short_attn_min_ = min_tok; }
+    // steps of at least `min_tok` tokens (0 = never) use the single-wave attention kernel, which reads page 0 of a sequence only: the
+    // caller states that no sequence ever holds more than `max_positions` positions, and that must fit one KV page (64)
+    void set_short_attention(int min_tok, int max_positions) {
+        Q3_CHECK(min_tok <= 0 || (max_positions >= 1 && max_positions <= 64), "the short attention form serves at most 64 positions per sequence");
+        short_attn_min_ = min_tok;
+    }
     // largest token count that still takes the 5-launch fused layer path (its GEMVs re-read the weights once per 4-8 token tile,
     // which is fine for a model whose weights stay cache-resident, i.e. the code predictor)
     void set_fused_max_tokens(int n) { fused_max_tok_ = n; }
@@ -55,6 +76,8 @@ public:
     // Q3_SPEC=ggml at construction: the opt-in "ggml-CPU" arithmetic mode (ggml_mode.hip) -- every forward() / head() then runs llama.cpp's portable
     // arithmetic (as the test suite's CPU restatement of the mode has it), on raw copies of the GGUF matrices; slow by design, bit-exact with that restatement
     bool ggml_mode() const { return ggml_mode_; }
+    // the attention form forward() runs for an ntok-token step under the current flags
+    int attention_form(int ntok) const;
 
     LaunchTimer* timer = nullptr;    // optional per-GEMV-launch event timing (instrumented bench leg): whole GEMV family
     LaunchTimer* timer_gu = nullptr; // ... and the gate/up kernel alone (the dominant launch by bytes)

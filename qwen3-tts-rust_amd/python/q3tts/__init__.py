@@ -86,7 +86,7 @@ SYMBOLS = [
     "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
-    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan",
+    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_op_attention", "q3tts_attention_plan",
 ]
 
 
@@ -839,6 +839,84 @@ class OnnxDecoder:
             rc = lib().q3tts_onnx_decoder_fetch(self.h, out.ctypes.data, out.size, C.byref(n))
         _chk(rc)
         return out[: n.value].copy()
+
+
+ATTN_FORMS = {"AUTO": 0, "UNFUSED": 1, "FUSED": 2, "SHORT1": 3, "SHORT2": 4, "GGML": 5}
+ATTN_FORM_NAMES = {v: k for k, v in ATTN_FORMS.items()}
+
+
+class AttentionDesc(C.Structure):  # q3tts_attention_desc
+    _fields_ = [("n_head", C.c_int32), ("n_kv", C.c_int32), ("n_layer", C.c_int32), ("layer", C.c_int32), ("ntok", C.c_int32),
+                ("qkv", C.c_void_p), ("qkv_stride", C.c_int32), ("q_norm", C.c_void_p), ("k_norm", C.c_void_p),
+                ("eps", C.c_float), ("rope_base", C.c_float), ("n_ctx", C.c_int32), ("mrope_sec", C.c_int32 * 4),
+                ("seq", C.c_void_p), ("slot", C.c_void_p), ("pos", C.c_void_p), ("uniform_pos", C.c_int32),
+                ("page_table", C.c_void_p), ("n_seq", C.c_int32), ("max_pages", C.c_int32),
+                ("k_cache", C.c_void_p), ("v_cache", C.c_void_p), ("n_pages", C.c_int32),
+                ("fused", C.c_int32), ("fused_max_tok", C.c_int32), ("same_seq", C.c_int32), ("short_attn_min", C.c_int32),
+                ("hpw1_max", C.c_int32), ("float_mode", C.c_int32), ("ggml_mode", C.c_int32),
+                ("form", C.c_int32), ("att", C.c_void_p), ("aq", C.c_void_p), ("ad", C.c_void_p), ("form_ran", C.c_int32)]
+
+
+def _attn_flags(d, fused, fused_max_tok, same_seq, short_attn_min, hpw1_max, float_mode, ggml_mode):
+    d.fused, d.fused_max_tok, d.same_seq, d.short_attn_min = int(fused), fused_max_tok, int(same_seq), short_attn_min
+    d.hpw1_max, d.float_mode, d.ggml_mode = hpw1_max, int(float_mode), int(ggml_mode)
+
+
+def attention_plan(ntok, n_head=16, n_kv=8, fused=True, fused_max_tok=8, same_seq=False, short_attn_min=0, hpw1_max=0, float_mode=False,
+                   ggml_mode=False):
+    """the attention form Transformer::forward runs for one step with these flags (host only; hpw1_max 0 = the engine's threshold)"""
+    d = AttentionDesc()
+    d.ntok, d.n_head, d.n_kv = ntok, n_head, n_kv
+    _attn_flags(d, fused, fused_max_tok, same_seq, short_attn_min, hpw1_max, float_mode, ggml_mode)
+    lib().q3tts_attention_plan.argtypes = [C.POINTER(AttentionDesc)]
+    _chk(lib().q3tts_attention_plan(C.byref(d)))
+    return ATTN_FORM_NAMES[d.form_ran]
+
+
+def op_attention(qkv, q_norm, k_norm, k_cache, v_cache, n_head, n_kv, n_layer, layer, eps=1e-6, rope_base=1e6, n_ctx=4096,
+                 mrope_sec=(0, 0, 0, 0), seq=None, slot=None, pos=None, uniform_pos=-1, page_table=None, form="AUTO", fused=True,
+                 fused_max_tok=8, same_seq=False, short_attn_min=0, hpw1_max=0, float_mode=False, ggml_mode=False):
+    """one layer's attention step on the device (q3tts_op_attention).  qkv [ntok][>= (n_head + 2 n_kv) * 128] f32; k_cache / v_cache: the
+    paged f16 caches as uint16 [n_pages][n_layer][n_kv][8192] (copied; the written-back caches are returned); seq / slot [ntok] and
+    pos [ntok][4], or uniform_pos >= 0; page_table [n_seq][max_pages] or None (identity).
+    Returns dict(att=[ntok][n_head*128] f32 or None, aq, ad (None for GGML), k_cache, v_cache, form=name of what ran)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    ntok = qkv.shape[0]
+    q_norm = np.ascontiguousarray(q_norm, np.float32)
+    k_norm = np.ascontiguousarray(k_norm, np.float32)
+    kc = np.array(k_cache, np.uint16, copy=True, order="C")
+    vc = np.array(v_cache, np.uint16, copy=True, order="C")
+    assert kc.shape == vc.shape and kc.size % (n_layer * n_kv * 8192) == 0
+    d = AttentionDesc()
+    d.n_head, d.n_kv, d.n_layer, d.layer, d.ntok = n_head, n_kv, n_layer, layer, ntok
+    d.qkv, d.qkv_stride, d.q_norm, d.k_norm = _p(qkv), qkv.shape[1], _p(q_norm), _p(k_norm)
+    d.eps, d.rope_base, d.n_ctx = eps, rope_base, n_ctx
+    for i in range(4):
+        d.mrope_sec[i] = int(mrope_sec[i])
+    keep = []
+    if uniform_pos < 0:
+        seq = np.ascontiguousarray(seq, np.int32)
+        slot = np.ascontiguousarray(slot, np.int32)
+        pos = np.ascontiguousarray(pos, np.int32).reshape(ntok, 4)
+        keep += [seq, slot, pos]
+        d.seq, d.slot, d.pos = _p(seq), _p(slot), _p(pos)
+    d.uniform_pos = uniform_pos
+    if page_table is not None:
+        page_table = np.ascontiguousarray(page_table, np.int32)
+        keep.append(page_table)
+        d.page_table, d.n_seq, d.max_pages = _p(page_table), page_table.shape[0], page_table.shape[1]
+    d.k_cache, d.v_cache, d.n_pages = _p(kc), _p(vc), kc.size // (n_layer * n_kv * 8192)
+    _attn_flags(d, fused, fused_max_tok, same_seq, short_attn_min, hpw1_max, float_mode, ggml_mode)
+    d.form = ATTN_FORMS[form]
+    att = np.full((ntok, n_head * 128), np.nan, np.float32)
+    aq = np.zeros((ntok, n_head * 128), np.int8)
+    ad = np.zeros((ntok, n_head * 4), np.uint16)
+    d.att, d.aq, d.ad = _p(att), _p(aq), _p(ad)
+    lib().q3tts_op_attention.argtypes = [C.POINTER(AttentionDesc)]
+    _chk(lib().q3tts_op_attention(C.byref(d)))
+    ran = ATTN_FORM_NAMES[d.form_ran]
+    return dict(att=None if ran == "FUSED" else att, aq=None if ran == "GGML" else aq, ad=None if ran == "GGML" else ad,
+                k_cache=kc, v_cache=vc, form=ran)
 
 
 def op_gemv_kq(parts, k, xq, xd, lpr=0):

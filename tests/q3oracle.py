@@ -71,6 +71,11 @@ def lib():
         L.q3o_matvec.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.q3o_rmsnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
         L.q3o_headnorm128.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        L.q3o_rope_tables.argtypes = [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        L.q3o_head_rope.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_void_p]
+        L.q3o_attn_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.q3o_attn_head_ggml.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.q3o_sumsq_vec.restype = C.c_float
         L.q3o_sumsq_vec.argtypes = [C.c_void_p, C.c_int64]
         L.q3o_gguf_open.restype = C.c_void_p
@@ -278,3 +283,44 @@ def sample(logits, start, end, temperature=0.0, top_k=0, top_p=1.0, seed=42, sta
         state = C.create_string_buffer(256)
         lib().q3o_sampler_init(state, temperature, top_k, top_p, seed)
     return lib().q3o_sample(state, _p(logits), logits.size, start, end), state
+
+
+# ---- spec S2 / S4' / S5 / S7 one head at a time (tests/test_gpu_attention.py) ----
+def rope_tables(rope_base, n_ctx):
+    """the spec S5 tables: (cos, sin) [n_ctx][64] f32"""
+    c = np.zeros((n_ctx, 64), np.float32)
+    s = np.zeros((n_ctx, 64), np.float32)
+    lib().q3o_rope_tables(rope_base, n_ctx, _p(c), _p(s))
+    return c, s
+
+
+def head_rope(x, g, eps, pos, sec, tables, ggml=False):
+    """S4' RMSNorm of one 128-vector (ggml: the ggml-mode norm) then S5 M-RoPE at positions pos[4] with sections sec[4]"""
+    x = np.ascontiguousarray(x, np.float32)
+    g = np.ascontiguousarray(g, np.float32)
+    pos = np.ascontiguousarray(pos, np.int32)
+    sec = np.ascontiguousarray(sec, np.int32)
+    c, s = tables
+    out = np.zeros(128, np.float32)
+    lib().q3o_head_rope(_p(x), _p(g), eps, _p(pos), _p(sec), _p(c), _p(s), c.shape[0], 1 if ggml else 0, _p(out))
+    return out
+
+
+def attn_head(q, K, V, ggml=False):
+    """S7 (ggml: the ggml-mode attention): one query head q[128] f32 against K, V [n][128] f16 bit patterns (uint16)"""
+    q = np.ascontiguousarray(q, np.float32)
+    K = np.ascontiguousarray(K, np.uint16)
+    V = np.ascontiguousarray(V, np.uint16)
+    out = np.zeros(128, np.float32)
+    fn = lib().q3o_attn_head_ggml if ggml else lib().q3o_attn_head
+    fn(_p(q), _p(K), _p(V), 128, K.shape[0], _p(out))
+    return out
+
+
+def quant_act(x):
+    """S2: int8 blocks of 32 and their f16 scales (uint16)"""
+    x = np.ascontiguousarray(x, np.float32)
+    q = np.zeros(x.size, np.int8)
+    d = np.zeros(x.size // 32, np.uint16)
+    lib().q3o_quant_act(_p(x), x.size, _p(q), _p(d))
+    return q, d
