@@ -245,6 +245,10 @@ void q3tts_chunker_free(q3tts_chunker* c);
 int q3tts_chunker_push(q3tts_chunker* c, const int64_t* codes, int32_t n, int32_t is_final);
 
 /* ---- streaming codec decoder (device) ---- */
+/* A stream carries at most this many frames between resets (12.5 frames/s: about 87 minutes): its RoPE positions 0 .. Q3TTS_CODEC_MAX_FRAMES-1
+ * match the oracle's unbounded n_seen + t.  A decode call that would take a stream past it returns an error before anything is uploaded or
+ * launched and leaves every stream's state unchanged; _state_import refuses a frame counter above it. */
+#define Q3TTS_CODEC_MAX_FRAMES 65536
 typedef struct q3tts_decoder q3tts_decoder;
 int q3tts_decoder_create(const char* codec_gguf, int32_t n_streams, q3tts_decoder** out);
 void q3tts_decoder_destroy(q3tts_decoder* d);
@@ -403,6 +407,41 @@ int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d);
 /* host only (no device needed): the decoder's dispatch for d's shape -> form_ran / ksplit_ran / reducer_ran.  Pointers are not dereferenced:
  * NULL stands for a 16-byte aligned buffer (out_off still applies) */
 int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d);
+
+/* One codec-decoder kernel other than the GEMMs (csrc/codec.hip), launched as decode_group_async launches it.  R = G * T logical rows: stream g's
+ * rows are g*T .. g*T+T-1.  An "extended" buffer is [G][H + T][C]: per stream H history rows (right-aligned), then the T new rows.
+ *   RVQ_SUM         codes [R][n_q] (clamped to [0, cb_size)), in[0] codebooks [n_q][cb_size][C] -> out[0] extended, new rows written
+ *   RMSNORM_ROWS    in[0] x [R][C] (NULL: in place on out[0]), p0 gain [C], eps -> out[0] [R][C]
+ *   LAYERNORM_ROWS  the same with p0 weight, p1 bias (two-pass mean / variance)
+ *   ROPE_APPEND     C = n_heads * head_dim; out[0] qkv [R][3C] rotated in place (NeoX, position meta[2G+g] + t, rope_base), out[1] K and out[2] V
+ *                   extended (H = window - 1), new rows written.  Every position must be below Q3TTS_CODEC_MAX_FRAMES.
+ *   WINDOW_ATTN     in[0] qkv [R][3C] (q read), in[1] K, in[2] V extended (H = window - 1, last meta[G+g] history rows valid) -> out[0] [R][C];
+ *                   row t attends to the window - 1 positions before it and itself; head_dim and window <= 128
+ *   SWIGLU_ROWS     in[0] gate|up [R][2C] -> out[0] [R][C]
+ *   DWCONV7         in[0] extended (H = 6), p0 w [C][7], p1 bias [C] -> out[0] [R][C] (causal depthwise, tap 6 = the current row)
+ *   SNAKE[_SPLIT]   in[0] [R][C], p0 exp(alpha) [C], p1 1/(exp(beta)+1e-9) [C] -> out[0] extended, new rows (SPLIT: [C f16 hi][C f16 lo]); C % 4 == 0
+ *   CONV_OUT_WAVE / CONV_OUT_WIN  in[0] extended (H = 6), p0 w [7][C] (tap-major), bias -> out[0] pcm [R] clamped to [-1, 1];
+ *                   C % 4 == 0; WIN (k_conv_out_win<96>): C == 96 and T % 128 == 0
+ *   HIST_LOAD       in[0] store [n_streams][H][C] -> out[0] extended: stream g's history rows from slot meta[g]
+ *   HIST_SAVE       in[0] extended -> out[0] store: the last H rows of (history + new rows) of stream g into slot meta[g]
+ *   HIST_ZERO       out[0] store: slot `stream` zeroed
+ * meta [3G] = stream slot, cached K/V rows, frames seen, as the decoder uploads it per call.  Outputs are uploaded and written back whole, so
+ * anything a kernel writes outside its logical output shows.  A kernel whose preconditions fail returns an error and launches nothing. */
+enum { Q3TTS_CK_RVQ_SUM = 0, Q3TTS_CK_RMSNORM_ROWS = 1, Q3TTS_CK_LAYERNORM_ROWS = 2, Q3TTS_CK_ROPE_APPEND = 3, Q3TTS_CK_WINDOW_ATTN = 4,
+       Q3TTS_CK_SWIGLU_ROWS = 5, Q3TTS_CK_DWCONV7 = 6, Q3TTS_CK_SNAKE = 7, Q3TTS_CK_SNAKE_SPLIT = 8, Q3TTS_CK_CONV_OUT_WAVE = 9,
+       Q3TTS_CK_CONV_OUT_WIN = 10, Q3TTS_CK_HIST_LOAD = 11, Q3TTS_CK_HIST_SAVE = 12, Q3TTS_CK_HIST_ZERO = 13 };
+typedef struct q3tts_codec_kernel_desc {
+    int32_t kernel;
+    int32_t G, T, C, H;                                   /* streams, new rows per stream, channels, history rows per extended segment */
+    int32_t n_heads, head_dim, window; float rope_base, eps, bias;
+    const int64_t* meta;                                  /* [3G] */
+    const int64_t* codes; int32_t n_q, cb_size;           /* RVQ_SUM */
+    int32_t n_streams, stream;                            /* HIST_*: slots of the store; HIST_ZERO: the slot */
+    const float* in[3]; int64_t in_floats[3];
+    const float* p0; const float* p1; int64_t p0_floats, p1_floats;
+    float* out[3]; int64_t out_floats[3];
+} q3tts_codec_kernel_desc;
+int q3tts_op_codec_kernel(q3tts_codec_kernel_desc* d);
 
 /* One transformer attention step (spec S4' per-head RMSNorm, S5 M-RoPE, S6 f16 KV append, S7 causal GQA attention, S2 quantisation of the
  * output) for one layer, as Transformer::forward dispatches it or with a named kernel form forced.  Every buffer is a host buffer.

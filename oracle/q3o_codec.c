@@ -263,6 +263,7 @@ void q3o_set_threads(int n) {
     (void)n;
 #endif
 }
+void q3o_codec_set_frames_seen(q3o_codec* c, int64_t n_seen) { c->n_seen = n_seen; }
 int q3o_codec_samples_per_frame(const q3o_codec* c) {
     int s = 1;
     for (int i = 0; i < c->n_up; i++) s *= c->up_ratios[i];

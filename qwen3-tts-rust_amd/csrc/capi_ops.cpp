@@ -362,6 +362,14 @@ int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d) {
     Q3_API_END(Q3TTS_ERR)
 }
 
+int q3tts_op_codec_kernel(q3tts_codec_kernel_desc* d) {
+    Q3_API_BEGIN
+    require_gpu();
+    codec_kernel_run(d);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 int q3tts_op_project(const float* x, const float* w, const float* b, int32_t n_in, int32_t n_out, float* y) {
     Q3_API_BEGIN
     require_gpu();

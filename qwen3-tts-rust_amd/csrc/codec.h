@@ -7,6 +7,7 @@
 #include <vector>
 
 struct q3tts_codec_gemm_desc;
+struct q3tts_codec_kernel_desc;
 
 namespace q3 {
 
@@ -43,5 +44,6 @@ private:
 // test entry points (include/q3tts.h: q3tts_op_codec_gemm, q3tts_codec_gemm_plan): one codec GEMM, dispatched as the decoder does or forced
 void codec_gemm_run(q3tts_codec_gemm_desc* d);
 void codec_gemm_plan_only(q3tts_codec_gemm_desc* d); // host only
+void codec_kernel_run(q3tts_codec_kernel_desc* d); // q3tts_op_codec_kernel: one non-GEMM kernel as the decoder launches it
 
 } // namespace q3

@@ -794,13 +794,13 @@ __global__ void __launch_bounds__(256) k_layernorm_rows(const float* __restrict_
 // NeoX RoPE on q and k inside a packed [G*T0][3*H] qkv buffer (head_dim hd), absolute position seen[g] + t
 // RoPE of q and k plus the K / V window append in one launch: thread e < H/2 rotates pair e of q (in place) and of k (in place and into the K window);
 // every thread also copies two V elements into the V window
+// (the tables hold Q3TTS_CODEC_MAX_FRAMES positions; the host refuses a call whose positions reach past them: positions_error)
 __global__ void k_codec_rope_append(float* __restrict__ qkv, int ld, int H, int hd, const float* __restrict__ cs, const float* __restrict__ sn,
-                                    const int64_t* __restrict__ meta, int G, int T0, int max_pos, float* __restrict__ kext, float* __restrict__ vext, RowMap om) {
+                                    const int64_t* __restrict__ meta, int G, int T0, float* __restrict__ kext, float* __restrict__ vext, RowMap om) {
     const int r = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x, half = hd / 2;
     if (e >= H / 2) return;
     const int head = e / half, i = e % half;
-    long long p = meta[2 * G + r / T0] + (r % T0);
-    if (p >= max_pos) p = max_pos - 1;
+    const long long p = meta[2 * G + r / T0] + (r % T0);
     const float c = cs[(size_t)p * half + i], s = sn[(size_t)p * half + i];
     const size_t o = map_row(om, r) * H;
     float* row = qkv + (size_t)r * ld;
@@ -926,12 +926,10 @@ __global__ void __launch_bounds__(256) k_conv_out_wave(const float* __restrict__
     if (t >= n) return;
     const float* row = in_ext + map_row(im, t) * C; // 7 consecutive rows of C floats = one contiguous span of 7*C
     float a = 0.0f;
-    if ((C & 3) == 0) { // 16-byte loads (rows start on C-float boundaries; C % 4 == 0 for every decoder width)
-        for (int i = lane; i < 7 * C / 4; i += 64) {
-            const float4 x = *reinterpret_cast<const float4*>(row + 4 * i), ww = *reinterpret_cast<const float4*>(w + 4 * i);
-            a += ww.x * x.x + ww.y * x.y + ww.z * x.z + ww.w * x.w;
-        }
-    } else for (int i = lane; i < 7 * C; i += 64) a += w[i] * row[i];
+    for (int i = lane; i < 7 * C / 4; i += 64) { // 16-byte loads: rows start on C-float boundaries and C % 4 == 0 (checked at load and by the test entry)
+        const float4 x = *reinterpret_cast<const float4*>(row + 4 * i), ww = *reinterpret_cast<const float4*>(w + 4 * i);
+        a += ww.x * x.x + ww.y * x.y + ww.z * x.z + ww.w * x.w;
+    }
     for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o);
     a += bias;
     if (lane == 0) pcm[t] = a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
@@ -966,6 +964,63 @@ __global__ void __launch_bounds__(256) k_conv_out_win(const float* __restrict__ 
         if (lane == 0 && t0 + tl < n) pcm[t0 + tl] = a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
     }
 }
+// ---------------- launch helpers: decode_group_async and the test entry (codec_kernel_run) launch the same kernels with the same grids ----------------
+static void launch_rvq_sum(hipStream_t st, const int64_t* codes, const float* const* cb, int n_q, int cb_size, int cb_dim, int R, float* out, RowMap om) {
+    hipLaunchKernelGGL(k_rvq_sum, dim3((cb_dim + 255) / 256, R), dim3(256), 0, st, codes, cb, n_q, cb_size, cb_dim, out, cb_dim, om);
+}
+static void launch_rmsnorm(hipStream_t st, const float* x, const float* g, int C, float eps, float* y, int R) {
+    hipLaunchKernelGGL(k_rmsnorm_rows, dim3(R), dim3(256), 0, st, x, C, g, C, eps, y, C);
+}
+static void launch_layernorm(hipStream_t st, const float* x, const float* w, const float* b, int C, float eps, float* y, int R) {
+    hipLaunchKernelGGL(k_layernorm_rows, dim3(R), dim3(256), 0, st, x, C, w, b, C, eps, y, C);
+}
+// qkv [G*T0][3H] (H = n_heads * hd); kext / vext: extended buffers with the new rows at map om
+static void launch_rope_append(hipStream_t st, float* qkv, int H, int hd, const float* cs, const float* sn, const int64_t* meta, int G, int T0,
+                               float* kext, float* vext, RowMap om) {
+    hipLaunchKernelGGL(k_codec_rope_append, dim3((H / 2 + 255) / 256, G * T0), dim3(256), 0, st, qkv, 3 * H, H, hd, cs, sn, meta, G, T0, kext, vext, om);
+}
+static void launch_window_attn(hipStream_t st, const float* qkv, int n_heads, int H, int hd, const float* kext, const float* vext, const int64_t* meta,
+                               int G, int T0, int W, float* out) {
+    hipLaunchKernelGGL(k_codec_attn, dim3(n_heads, G * T0), dim3(64), 0, st, qkv, 3 * H, H, hd, kext, vext, meta, G, T0, W, out, H);
+}
+static void launch_swiglu(hipStream_t st, const float* gu, int ff, float* out, int R) {
+    hipLaunchKernelGGL(k_swiglu_rows, dim3((ff + 255) / 256, R), dim3(256), 0, st, gu, ff, out);
+}
+static void launch_dwconv7(hipStream_t st, const float* in_ext, int C, const float* w, const float* b, float* out, int R, RowMap im) {
+    hipLaunchKernelGGL(k_dwconv7, dim3((C + 255) / 256, R), dim3(256), 0, st, in_ext, C, w, b, out, im);
+}
+static void launch_snake(hipStream_t st, const float* src, float* dst, int C, const float* ea, const float* inv_eb, int rows, RowMap dm, bool split) {
+    const size_t n = (size_t)rows * (C / 4);
+    hipLaunchKernelGGL(k_snake, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, C, ea, inv_eb, n, dm, split ? 1 : 0);
+}
+// the window form of the output conv needs the full decoder width and whole 128-sample blocks per stream
+static bool conv_out_win_ok(int C, int T) { return C == 96 && T % 128 == 0; }
+static void launch_conv_out(hipStream_t st, const float* in_ext, int C, const float* w, float bias, float* pcm, int G, int T, RowMap im, bool win) {
+    if (win) hipLaunchKernelGGL((k_conv_out_win<96>), dim3(G * T / 128), dim3(256), 0, st, in_ext, w, bias, pcm, G * T, im);
+    else hipLaunchKernelGGL(k_conv_out_wave, dim3((G * T + 3) / 4), dim3(256), 0, st, in_ext, C, w, bias, pcm, G * T, im);
+}
+static void launch_hist_all(hipStream_t st, const HistTable& tab, int G, const int64_t* meta, bool save) {
+    size_t mx = 0;
+    for (int i = 0; i < tab.n; i++) mx = std::max(mx, (size_t)tab.d[i].H * tab.d[i].C);
+    hipLaunchKernelGGL(k_hist_all, dim3((unsigned)((mx / 4 + 255) / 256), G, tab.n), dim3(256), 0, st, tab, meta, save ? 1 : 0);
+}
+static void launch_hist_zero(hipStream_t st, const HistTable& tab, int stream) {
+    size_t mx = 0;
+    for (int i = 0; i < tab.n; i++) mx = std::max(mx, (size_t)tab.d[i].H * tab.d[i].C);
+    hipLaunchKernelGGL(k_hist_zero, dim3((unsigned)((mx + 255) / 256), 1, tab.n), dim3(256), 0, st, tab, stream);
+}
+// NeoX RoPE tables [n_pos][hd/2] for the absolute frame positions, rounded once from double (the oracle's angles)
+static void rope_tables(int hd, float base, int n_pos, std::vector<float>& c, std::vector<float>& s) {
+    const int half = hd / 2;
+    c.resize((size_t)n_pos * half); s.resize((size_t)n_pos * half);
+    for (int i = 0; i < half; i++) {
+        const double f = std::pow((double)base, -(double)i / half);
+        for (int p = 0; p < n_pos; p++) { const double ang = (double)p * f; c[(size_t)p * half + i] = (float)std::cos(ang); s[(size_t)p * half + i] = (float)std::sin(ang); }
+    }
+}
+// a stream that has seen `seen` frames may take T0 more only while every position stays inside the tables
+static bool positions_ok(long long seen, int T0) { return seen >= 0 && T0 >= 0 && seen + T0 <= (long long)Q3TTS_CODEC_MAX_FRAMES; }
+
 // ---------------- host side ----------------
 // hi / lo f16 split of a rearranged weight matrix [N][K] for the split-f16 kernels, with the exact per-row prescale they undo (k_conv_gemm_h):
 // row n is multiplied by 2^s_n, max |W[n]| * 2^s_n in [2^13, 2^14), so hi keeps 11 bits and lo (a normal f16 for elements down to ~2^-16 of
@@ -997,7 +1052,7 @@ struct CodecDecoder::Impl {
     int n_q, cb_size, cb_dim, hidden, n_layers, n_heads, head_dim, ffn, window, n_up, dec_dim, n_dec;
     int up_ratios[4], dec_rates[8];
     float rope_base, eps;
-    int n_streams, max_frames, max_pos = 8192;
+    int n_streams, max_frames;
     std::vector<DevBuf<float>> codebooks; DevBuf<const float*> d_cb_ptrs;
     ConvW pre_conv;
     struct TfL { DevBuf<float> attn_norm, ffn_norm, ls_attn, ls_ffn; ConvW wqkv, wo, wgu, wdown; };
@@ -1114,16 +1169,11 @@ struct CodecDecoder::Impl {
         Q3_CHECK(e.C % 4 == 0, "streaming state rows must be a multiple of 4 channels (k_hist_all moves float4s)");
         table.d[table.n++] = HistDesc{work(e), e.hist.p, e.H, e.C, T, 0};
     }
-    void move_hist(hipStream_t st, int G, const int64_t* meta, bool save) {
-        size_t mx = 0;
-        for (int i = 0; i < table.n; i++) mx = std::max(mx, (size_t)table.d[i].H * table.d[i].C);
-        hipLaunchKernelGGL(k_hist_all, dim3((unsigned)((mx / 4 + 255) / 256), G, table.n), dim3(256), 0, st, table, meta, save ? 1 : 0);
-    }
+    void move_hist(hipStream_t st, int G, const int64_t* meta, bool save) { launch_hist_all(st, table, G, meta, save); }
 
     void snake(hipStream_t st, const Snake& s, const float* src, float* dst, int rows, RowMap dm, bool split = false) {
         Q3_CHECK(s.C % 4 == 0, "SnakeBeta channel count must be a multiple of 4");
-        const size_t n = (size_t)rows * (s.C / 4);
-        hipLaunchKernelGGL(k_snake, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, s.C, s.ea.p, s.inv_eb.p, n, dm, split ? 1 : 0);
+        launch_snake(st, src, dst, s.C, s.ea.p, s.inv_eb.p, rows, dm, split);
     }
     void copy_rows(hipStream_t st, const float* src, float* dst, int rows, int C, RowMap dm) {
         const size_t n = (size_t)rows * C;
@@ -1173,13 +1223,9 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
         fl += 2.0 * (4.0 * H * H + 3.0 * H * m.ffn);
     }
     Impl::up_f(m.tf_norm, Impl::tensor(g, "codec.tf.norm"));
-    {
-        const int half = m.head_dim / 2;
-        std::vector<float> c((size_t)m.max_pos * half), s((size_t)m.max_pos * half);
-        for (int p = 0; p < m.max_pos; p++) for (int i = 0; i < half; i++) {
-            const double ang = (double)p * std::pow((double)m.rope_base, -(double)i / half);
-            c[(size_t)p * half + i] = (float)std::cos(ang); s[(size_t)p * half + i] = (float)std::sin(ang);
-        }
+    {   // every position a stream can reach (Q3TTS_CODEC_MAX_FRAMES; decode_group_async and state_import refuse more)
+        std::vector<float> c, s;
+        rope_tables(m.head_dim, m.rope_base, Q3TTS_CODEC_MAX_FRAMES, c, s);
         Impl::up_f(m.rope_c, c); Impl::up_f(m.rope_s, s);
     }
     int rate = 1;
@@ -1224,6 +1270,7 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
     }
     m.make_snake(m.snake_out, g, "codec.dec.snake_out.alpha", "codec.dec.snake_out.beta", ch);
     {   // conv_out weight [1][ch][7] -> [j][c]
+        Q3_CHECK(ch % 4 == 0, "conv_out width must be a multiple of 4 (k_conv_out_wave reads float4 rows)");
         auto w = Impl::tensor(g, "codec.dec.conv_out.weight");
         std::vector<float> r((size_t)7 * ch);
         for (int c = 0; c < ch; c++) for (int j = 0; j < 7; j++) r[(size_t)j * ch + c] = w[(size_t)c * 7 + j];
@@ -1338,7 +1385,8 @@ void CodecDecoder::state_import(int s, const float* in, size_t n_floats) {
     // the trailer drives device-side indexing of the KV / history buffers on the next decode: validate before anything is committed
     const float kvf = in[n_floats - 2], seenf = in[n_floats - 1];
     Q3_CHECK(kvf == kvf && seenf == seenf && kvf >= 0.0f && kvf <= (float)(m.window - 1) && kvf == (float)(int)kvf, "state_import: cached-position count in the blob is not an integer in [0, window)");
-    Q3_CHECK(seenf >= 0.0f && seenf < 9.0e15f && seenf == (float)(long long)seenf, "state_import: frame counter in the blob is negative or not finite");
+    Q3_CHECK(seenf >= 0.0f && seenf <= (float)Q3TTS_CODEC_MAX_FRAMES && seenf == (float)(long long)seenf,
+             "state_import: frame counter in the blob is not an integer in [0, Q3TTS_CODEC_MAX_FRAMES]");
     std::lock_guard<std::mutex> cap(capture_mutex());
     Q3_HIP(hipDeviceSynchronize());
     size_t off = 0;
@@ -1356,16 +1404,14 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     Impl& m = *impl_;
     Q3_CHECK(s >= 0 && s < m.n_streams, "stream out of range");
     HistTable tab{};
-    size_t mx = 0;
     auto flush = [&]() {
-        if (tab.n) hipLaunchKernelGGL(k_hist_zero, dim3((unsigned)((mx + 255) / 256), 1, tab.n), dim3(256), 0, st, tab, s);
-        tab.n = 0; mx = 0;
+        if (tab.n) launch_hist_zero(st, tab, s);
+        tab.n = 0;
     };
     for (Ext* e : m.all_ext) {
         if (!e->H) continue;
         HistDesc d{}; d.hist = e->hist.p; d.H = e->H; d.C = e->C;
         tab.d[tab.n++] = d;
-        mx = std::max(mx, (size_t)e->H * e->C);
         if (tab.n == 48) flush();
     }
     flush();
@@ -1394,6 +1440,7 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     for (int g = 0; g < G; g++) {
         Q3_CHECK(streams[g] >= 0 && streams[g] < m.n_streams, "stream out of range");
         for (int h = 0; h < g; h++) Q3_CHECK(streams[h] != streams[g], "a stream may appear once per group");
+        Q3_CHECK(positions_ok(m.n_seen[streams[g]], n_frames), "codec stream would pass Q3TTS_CODEC_MAX_FRAMES frames (RoPE positions)");
     }
     const int H = m.hidden, T0 = n_frames, R0 = G * T0, W = m.window;
     if (m.S->ring_idx == m.ring) { Q3_HIP(hipStreamSynchronize(st)); m.S->ring_idx = 0; } // all earlier uploads have been consumed
@@ -1420,23 +1467,20 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
         m.move_hist(st, G, meta, false);
     }
     // 1. RVQ sum -> z_ext current rows ; 2. pre_conv
-    hipLaunchKernelGGL(k_rvq_sum, dim3((m.cb_dim + 255) / 256, R0), dim3(256), 0, st, d_codes, m.d_cb_ptrs.p, m.n_q, m.cb_size, m.cb_dim,
-                       m.work(m.z_ext), m.cb_dim, m.cur_map(m.z_ext, T0));
+    launch_rvq_sum(st, d_codes, m.d_cb_ptrs.p, m.n_q, m.cb_size, m.cb_dim, R0, m.work(m.z_ext), m.cur_map(m.z_ext, T0));
     m.run_conv(st, m.pre_conv, m.ext_base(m.z_ext, T0), m.cb_dim, R0, m.plain(m.S->h.p), H, H);
     // 3. transformer
     for (int l = 0; l < m.n_layers; l++) {
         auto& L = m.tf[l];
         Ext &ke = m.k_ext[l], &ve = m.v_ext[l];
-        hipLaunchKernelGGL(k_rmsnorm_rows, dim3(R0), dim3(256), 0, st, m.S->h.p, H, L.attn_norm.p, H, m.eps, m.S->xn.p, H);
+        launch_rmsnorm(st, m.S->h.p, L.attn_norm.p, H, m.eps, m.S->xn.p, R0);
         m.run_conv(st, L.wqkv, m.plain(m.S->xn.p), H, R0, m.plain(m.S->qkv.p), 3 * H, 3 * H);
-        hipLaunchKernelGGL(k_codec_rope_append, dim3((H / 2 + 255) / 256, R0), dim3(256), 0, st, m.S->qkv.p, 3 * H, H, m.head_dim, m.rope_c.p, m.rope_s.p,
-                           meta, G, T0, m.max_pos, m.work(ke), m.work(ve), m.cur_map(ke, T0));
-        hipLaunchKernelGGL(k_codec_attn, dim3(m.n_heads, R0), dim3(64), 0, st, m.S->qkv.p, 3 * H, H, m.head_dim, m.work(ke), m.work(ve), meta, G, T0, W,
-                           m.S->att.p, H);
+        launch_rope_append(st, m.S->qkv.p, H, m.head_dim, m.rope_c.p, m.rope_s.p, meta, G, T0, m.work(ke), m.work(ve), m.cur_map(ke, T0));
+        launch_window_attn(st, m.S->qkv.p, m.n_heads, H, m.head_dim, m.work(ke), m.work(ve), meta, G, T0, W, m.S->att.p);
         m.run_conv(st, L.wo, m.plain(m.S->att.p), H, R0, m.plain(m.S->h.p), H, H, EPI_RES_SCALE, m.plain(m.S->h.p), H, L.ls_attn.p);
-        hipLaunchKernelGGL(k_rmsnorm_rows, dim3(R0), dim3(256), 0, st, m.S->h.p, H, L.ffn_norm.p, H, m.eps, m.S->xn.p, H);
+        launch_rmsnorm(st, m.S->h.p, L.ffn_norm.p, H, m.eps, m.S->xn.p, R0);
         m.run_conv(st, L.wgu, m.plain(m.S->xn.p), H, R0, m.plain(m.S->gu.p), 2 * m.ffn, 2 * m.ffn);
-        hipLaunchKernelGGL(k_swiglu_rows, dim3((m.ffn + 255) / 256, R0), dim3(256), 0, st, m.S->gu.p, m.ffn, m.S->act.p);
+        launch_swiglu(st, m.S->gu.p, m.ffn, m.S->act.p, R0);
         m.run_conv(st, L.wdown, m.plain(m.S->act.p), m.ffn, R0, m.plain(m.S->h.p), H, H, EPI_RES_SCALE, m.plain(m.S->h.p), H, L.ls_ffn.p);
     }
     for (int g = 0; g < G; g++) {
@@ -1445,7 +1489,7 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
         m.n_seen[s] += T0;
     }
     // 4. final norm -> t1 [R0][H]
-    hipLaunchKernelGGL(k_rmsnorm_rows, dim3(R0), dim3(256), 0, st, m.S->h.p, H, m.tf_norm.p, H, m.eps, m.S->t1.p, H);
+    launch_rmsnorm(st, m.S->h.p, m.tf_norm.p, H, m.eps, m.S->t1.p, R0);
     // 5. upsample stages: x in t1 (plain rows; T = rows per stream)
     int T = T0;
     float* x = m.S->t1.p;
@@ -1456,8 +1500,8 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
         // transposed conv: GEMM row (g,t) writes f consecutive H-wide rows of segment g: [T][f*H] == [T*f][H]
         m.run_conv(st, U.ct, m.plain(x), H, G * T, Impl::Loc{m.work(e) + (size_t)e.H * e.C, T, e.H}, f * H, H);
         T *= f;
-        hipLaunchKernelGGL(k_dwconv7, dim3((H + 255) / 256, G * T), dim3(256), 0, st, m.work(e), H, U.dw_w.p, U.dw_b.p, m.S->t2.p, m.base_map(e, T));
-        hipLaunchKernelGGL(k_layernorm_rows, dim3(G * T), dim3(256), 0, st, m.S->t2.p, H, U.ln_w.p, U.ln_b.p, H, 1e-6f, m.S->t2.p, H);
+        launch_dwconv7(st, m.work(e), H, U.dw_w.p, U.dw_b.p, m.S->t2.p, G * T, m.base_map(e, T));
+        launch_layernorm(st, m.S->t2.p, U.ln_w.p, U.ln_b.p, H, 1e-6f, m.S->t2.p, G * T);
         float* m1 = m.S->t1.p; // [G*T][4H]
         m.run_conv(st, U.pw1, m.plain(m.S->t2.p), H, G * T, m.plain(m1), 4 * H, 4 * H, EPI_GELU);
         // y_new = y + gamma * (pw2(m1) + b): write into t2 (y lives in the ext buffer)
@@ -1490,11 +1534,8 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     }
     // 8. output conv
     m.snake(st, m.snake_out, d, m.work(m.out_ext), G * T, m.cur_map(m.out_ext, T));
-    if (m.out_ext.C == 96 && T % 128 == 0) // (T = frames x 1920: every chunk length qualifies at the full decoder width)
-        hipLaunchKernelGGL((k_conv_out_win<96>), dim3(G * T / 128), dim3(256), 0, st, m.work(m.out_ext), m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G * T, m.base_map(m.out_ext, T));
-    else
-    hipLaunchKernelGGL(k_conv_out_wave, dim3((G * T + 3) / 4), dim3(256), 0, st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G * T,
-                       m.base_map(m.out_ext, T));
+    // (T = frames x 1920: every chunk length takes the window form at the full decoder width)
+    launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
     for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
@@ -1565,6 +1606,112 @@ void codec_gemm_run(q3tts_codec_gemm_desc* d) {
     Q3_HIP(hipDeviceSynchronize());
     dout.download(d->out, dout.n);
     d->form_ran = p.form; d->ksplit_ran = p.ks; d->reducer_ran = p.red;
+}
+
+// ---------------- test entry: one non-GEMM kernel on host buffers (include/q3tts.h q3tts_op_codec_kernel) ----------------
+void codec_kernel_run(q3tts_codec_kernel_desc* d) {
+    Q3_CHECK(d, "null codec kernel descriptor");
+    const int k = d->kernel, G = d->G, T = d->T, C = d->C, H = d->H;
+    Q3_CHECK(k >= Q3TTS_CK_RVQ_SUM && k <= Q3TTS_CK_HIST_ZERO, "unknown codec kernel");
+    Q3_CHECK(G >= 1 && T >= 1 && C >= 1 && H >= 0 && (long long)G * T <= (1 << 20), "codec kernel: G, T, C >= 1 and H >= 0");
+    const long long R = (long long)G * T, ext = (long long)G * (H + T) * C;
+    // every buffer a kernel touches, with the floats it needs; checked before anything is allocated or launched
+    auto need_in = [&](int i, long long n) { Q3_CHECK(d->in[i] && d->in_floats[i] >= n, "codec kernel: in[" + std::to_string(i) + "] missing or too small"); };
+    auto need_out = [&](int i, long long n) { Q3_CHECK(d->out[i] && d->out_floats[i] >= n, "codec kernel: out[" + std::to_string(i) + "] missing or too small"); };
+    auto need_p = [&](const float* p, int64_t have, long long n) { Q3_CHECK(p && have >= n, "codec kernel: parameter vector missing or too small"); };
+    auto need_meta = [&]() { Q3_CHECK(d->meta, "codec kernel: meta is required"); };
+    const bool win = k == Q3TTS_CK_CONV_OUT_WIN;
+    switch (k) {
+    case Q3TTS_CK_RVQ_SUM:
+        Q3_CHECK(d->codes && d->n_q >= 1 && d->cb_size >= 1, "RVQ_SUM: codes, n_q and cb_size are required");
+        need_in(0, (long long)d->n_q * d->cb_size * C); need_out(0, ext); break;
+    case Q3TTS_CK_RMSNORM_ROWS: case Q3TTS_CK_LAYERNORM_ROWS:
+        if (d->in[0]) need_in(0, R * C);
+        need_p(d->p0, d->p0_floats, C);
+        if (k == Q3TTS_CK_LAYERNORM_ROWS) need_p(d->p1, d->p1_floats, C);
+        need_out(0, R * C); break;
+    case Q3TTS_CK_ROPE_APPEND: case Q3TTS_CK_WINDOW_ATTN:
+        Q3_CHECK(d->n_heads >= 1 && d->head_dim >= 2 && d->head_dim % 2 == 0 && (long long)d->n_heads * d->head_dim == C, "C must equal n_heads * head_dim (even)");
+        Q3_CHECK(d->window >= 1 && H == d->window - 1, "the K / V extended buffers hold window - 1 history rows");
+        need_meta();
+        if (k == Q3TTS_CK_ROPE_APPEND) {
+            for (int g = 0; g < G; g++)
+                Q3_CHECK(positions_ok(d->meta[2 * G + g], T), "ROPE_APPEND: a position reaches Q3TTS_CODEC_MAX_FRAMES (or frames seen < 0)");
+            need_out(0, R * 3 * C); need_out(1, ext); need_out(2, ext);
+        } else {
+            Q3_CHECK(d->head_dim <= 128 && d->window <= 128, "WINDOW_ATTN: head_dim and window must be <= 128 (LDS rows)");
+            for (int g = 0; g < G; g++) Q3_CHECK(d->meta[G + g] >= 0 && d->meta[G + g] <= d->window - 1, "WINDOW_ATTN: kv_len outside [0, window)");
+            need_in(0, R * 3 * C); need_in(1, ext); need_in(2, ext); need_out(0, R * C);
+        }
+        break;
+    case Q3TTS_CK_SWIGLU_ROWS: need_in(0, R * 2 * C); need_out(0, R * C); break;
+    case Q3TTS_CK_DWCONV7:
+        Q3_CHECK(H == 6, "DWCONV7: 6 history rows"); need_in(0, ext); need_p(d->p0, d->p0_floats, 7LL * C); need_p(d->p1, d->p1_floats, C); need_out(0, R * C); break;
+    case Q3TTS_CK_SNAKE: case Q3TTS_CK_SNAKE_SPLIT:
+        Q3_CHECK(C % 4 == 0, "SNAKE: C % 4 == 0 (float4 rows)");
+        need_in(0, R * C); need_p(d->p0, d->p0_floats, C); need_p(d->p1, d->p1_floats, C); need_out(0, ext); break;
+    case Q3TTS_CK_CONV_OUT_WAVE: case Q3TTS_CK_CONV_OUT_WIN:
+        Q3_CHECK(H == 6 && C % 4 == 0, "CONV_OUT: 6 history rows and C % 4 == 0");
+        Q3_CHECK(!win || conv_out_win_ok(C, T), "CONV_OUT_WIN: needs C == 96 and T % 128 == 0");
+        need_in(0, ext); need_p(d->p0, d->p0_floats, 7LL * C); need_out(0, R); break;
+    case Q3TTS_CK_HIST_LOAD: case Q3TTS_CK_HIST_SAVE: case Q3TTS_CK_HIST_ZERO: {
+        Q3_CHECK(H >= 1 && C % 4 == 0 && d->n_streams >= 1, "HIST: H >= 1, C % 4 == 0, n_streams >= 1");
+        const long long store = (long long)d->n_streams * H * C;
+        if (k == Q3TTS_CK_HIST_ZERO) { Q3_CHECK(d->stream >= 0 && d->stream < d->n_streams, "HIST_ZERO: stream out of range"); need_out(0, store); break; }
+        need_meta();
+        for (int g = 0; g < G; g++) Q3_CHECK(d->meta[g] >= 0 && d->meta[g] < d->n_streams, "HIST: stream slot out of range");
+        if (k == Q3TTS_CK_HIST_LOAD) { need_in(0, store); need_out(0, ext); } else { need_in(0, ext); need_out(0, store); }
+        break;
+    }
+    }
+    // upload: inputs and outputs whole (outputs come back whole)
+    DevBuf<float> din[3], dout[3], dp0, dp1;
+    for (int i = 0; i < 3; i++) {
+        if (d->in[i] && d->in_floats[i] > 0) { din[i].alloc((size_t)d->in_floats[i]); din[i].upload(d->in[i], din[i].n); }
+        if (d->out[i] && d->out_floats[i] > 0) { dout[i].alloc((size_t)d->out_floats[i]); dout[i].upload(d->out[i], dout[i].n); }
+    }
+    if (d->p0 && d->p0_floats > 0) { dp0.alloc((size_t)d->p0_floats); dp0.upload(d->p0, dp0.n); }
+    if (d->p1 && d->p1_floats > 0) { dp1.alloc((size_t)d->p1_floats); dp1.upload(d->p1, dp1.n); }
+    DevBuf<int64_t> dmeta, dcodes;
+    if (d->meta) { dmeta.alloc(3 * (size_t)G); dmeta.upload(d->meta, dmeta.n); }
+    if (k == Q3TTS_CK_RVQ_SUM) { dcodes.alloc((size_t)R * d->n_q); dcodes.upload(d->codes, dcodes.n); }
+    const RowMap cur{T, H, H}, base{T, H, 0};
+    std::vector<float> rc, rs;
+    DevBuf<float> drc, drs;
+    DevBuf<const float*> dcb;
+    const hipStream_t st = 0;
+    switch (k) {
+    case Q3TTS_CK_RVQ_SUM: {
+        std::vector<const float*> cbp(d->n_q);
+        for (int q = 0; q < d->n_q; q++) cbp[q] = din[0].p + (size_t)q * d->cb_size * C;
+        dcb.alloc(d->n_q); dcb.upload(cbp.data(), d->n_q);
+        launch_rvq_sum(st, dcodes.p, dcb.p, d->n_q, d->cb_size, C, (int)R, dout[0].p, cur);
+        break;
+    }
+    case Q3TTS_CK_RMSNORM_ROWS: launch_rmsnorm(st, d->in[0] ? din[0].p : dout[0].p, dp0.p, C, d->eps, dout[0].p, (int)R); break;
+    case Q3TTS_CK_LAYERNORM_ROWS: launch_layernorm(st, d->in[0] ? din[0].p : dout[0].p, dp0.p, dp1.p, C, d->eps, dout[0].p, (int)R); break;
+    case Q3TTS_CK_ROPE_APPEND:
+        rope_tables(d->head_dim, d->rope_base, Q3TTS_CODEC_MAX_FRAMES, rc, rs); // as the decoder builds them at load
+        drc.alloc(rc.size()); drc.upload(rc.data(), rc.size()); drs.alloc(rs.size()); drs.upload(rs.data(), rs.size());
+        launch_rope_append(st, dout[0].p, C, d->head_dim, drc.p, drs.p, dmeta.p, G, T, dout[1].p, dout[2].p, cur);
+        break;
+    case Q3TTS_CK_WINDOW_ATTN: launch_window_attn(st, din[0].p, d->n_heads, C, d->head_dim, din[1].p, din[2].p, dmeta.p, G, T, d->window, dout[0].p); break;
+    case Q3TTS_CK_SWIGLU_ROWS: launch_swiglu(st, din[0].p, C, dout[0].p, (int)R); break;
+    case Q3TTS_CK_DWCONV7: launch_dwconv7(st, din[0].p, C, dp0.p, dp1.p, dout[0].p, (int)R, base); break;
+    case Q3TTS_CK_SNAKE: case Q3TTS_CK_SNAKE_SPLIT:
+        launch_snake(st, din[0].p, dout[0].p, C, dp0.p, dp1.p, (int)R, cur, k == Q3TTS_CK_SNAKE_SPLIT); break;
+    case Q3TTS_CK_CONV_OUT_WAVE: case Q3TTS_CK_CONV_OUT_WIN: launch_conv_out(st, din[0].p, C, dp0.p, d->bias, dout[0].p, G, T, base, win); break;
+    default: {
+        HistTable tab{};
+        tab.n = 1;
+        if (k == Q3TTS_CK_HIST_ZERO) { tab.d[0] = HistDesc{nullptr, dout[0].p, H, C, T, 0}; launch_hist_zero(st, tab, d->stream); }
+        else if (k == Q3TTS_CK_HIST_LOAD) { tab.d[0] = HistDesc{dout[0].p, din[0].p, H, C, T, 0}; launch_hist_all(st, tab, G, dmeta.p, false); }
+        else { tab.d[0] = HistDesc{din[0].p, dout[0].p, H, C, T, 0}; launch_hist_all(st, tab, G, dmeta.p, true); }
+    }
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    for (int i = 0; i < 3; i++) if (dout[i].n) dout[i].download(d->out[i], dout[i].n);
 }
 
 } // namespace q3

@@ -1,5 +1,6 @@
 // engine.cpp -- see engine.h.  Loop structure cites /root/reference/src/tts/engine.rs line numbers.
 #include "engine.h"
+#include "../../include/q3tts.h"
 #include <algorithm>
 #include <cmath>
 #include <chrono>
@@ -136,6 +137,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     Q3_HIP(hipDeviceSynchronize()); // memsets / table kernels above ran on other streams than st_
     upload_slot_state();
     if (p.load_codec) {
+        Q3_CHECK(p.max_steps <= Q3TTS_CODEC_MAX_FRAMES, "max_steps above Q3TTS_CODEC_MAX_FRAMES: a request's codec stream could not be decoded to its end");
         // codec streams outnumber the slots: a retired sequence's last chunks still drain while its slot is already reused
         // up to 16 streams share one decode pass; two lanes (HIP streams + scratch) let consecutive groups overlap
         // streams per decode pass, measured on MI355X: 64 slots 617 / 607 / 600 audio-s/s at 16 / 32 / 64, 256 slots 821 / 860 / 836

@@ -86,7 +86,7 @@ SYMBOLS = [
     "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
-    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_op_attention", "q3tts_attention_plan",
+    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan",
 ]
 
 
@@ -745,6 +745,60 @@ def codec_gemm_plan(M, N, cin, taps=1, dil=1, lda=None, ldo=None, out_off=0, o_s
     lib().q3tts_codec_gemm_plan.argtypes = [C.POINTER(CodecGemmDesc)]
     _chk(lib().q3tts_codec_gemm_plan(C.byref(d)))
     return GEMM_FORM_NAMES[d.form_ran], d.ksplit_ran, d.reducer_ran
+
+
+# codec non-GEMM kernels (include/q3tts.h Q3TTS_CK_*) and the per-stream frame limit
+CODEC_KERNELS = {"RVQ_SUM": 0, "RMSNORM_ROWS": 1, "LAYERNORM_ROWS": 2, "ROPE_APPEND": 3, "WINDOW_ATTN": 4, "SWIGLU_ROWS": 5, "DWCONV7": 6,
+                 "SNAKE": 7, "SNAKE_SPLIT": 8, "CONV_OUT_WAVE": 9, "CONV_OUT_WIN": 10, "HIST_LOAD": 11, "HIST_SAVE": 12, "HIST_ZERO": 13}
+CODEC_MAX_FRAMES = 65536
+
+
+class CodecKernelDesc(C.Structure):  # q3tts_codec_kernel_desc
+    _fields_ = [("kernel", C.c_int32), ("G", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
+                ("n_heads", C.c_int32), ("head_dim", C.c_int32), ("window", C.c_int32), ("rope_base", C.c_float), ("eps", C.c_float),
+                ("bias", C.c_float), ("meta", C.c_void_p), ("codes", C.c_void_p), ("n_q", C.c_int32), ("cb_size", C.c_int32),
+                ("n_streams", C.c_int32), ("stream", C.c_int32), ("inp", C.c_void_p * 3), ("in_floats", C.c_int64 * 3),
+                ("p0", C.c_void_p), ("p1", C.c_void_p), ("p0_floats", C.c_int64), ("p1_floats", C.c_int64),
+                ("out", C.c_void_p * 3), ("out_floats", C.c_int64 * 3)]
+
+
+def op_codec_kernel(kernel, G, T, C_, H=0, ins=(), outs=(), p0=None, p1=None, meta=None, codes=None, n_q=0, cb_size=0, n_heads=0,
+                    head_dim=0, window=0, rope_base=10000.0, eps=1e-5, bias=0.0, n_streams=0, stream=0):
+    """one codec-decoder kernel on the device (q3tts_op_codec_kernel).  ins / outs: up to 3 float32 (or 4-byte) arrays each, None allowed;
+    the outputs are uploaded and returned written back whole (copies).  meta: [3G] int64 (slot, kv_len, frames seen)."""
+    d = CodecKernelDesc()
+    d.kernel = CODEC_KERNELS[kernel] if isinstance(kernel, str) else kernel
+    d.G, d.T, d.C, d.H = G, T, C_, H
+    d.n_heads, d.head_dim, d.window, d.rope_base, d.eps, d.bias = n_heads, head_dim, window, rope_base, eps, bias
+    d.n_q, d.cb_size, d.n_streams, d.stream = n_q, cb_size, n_streams, stream
+    keep = []
+    if meta is not None:
+        meta = np.ascontiguousarray(meta, np.int64).reshape(-1)
+        assert meta.size == 3 * G
+        d.meta = meta.ctypes.data; keep.append(meta)
+    if codes is not None:
+        codes = np.ascontiguousarray(codes, np.int64).reshape(-1)
+        assert codes.size == G * T * n_q
+        d.codes = codes.ctypes.data; keep.append(codes)
+    for i, a in enumerate(ins):
+        if a is not None:
+            a = np.ascontiguousarray(a).reshape(-1)
+            assert a.dtype.itemsize == 4
+            d.inp[i], d.in_floats[i] = a.ctypes.data, a.size; keep.append(a)
+    res = []
+    for i, a in enumerate(outs):
+        a = None if a is None else np.array(a, copy=True).reshape(-1)
+        if a is not None:
+            assert a.dtype.itemsize == 4
+            d.out[i], d.out_floats[i] = a.ctypes.data, a.size
+        res.append(a)
+    for nm, a in (("p0", p0), ("p1", p1)):
+        if a is not None:
+            a = np.ascontiguousarray(a, np.float32).reshape(-1)
+            setattr(d, nm, a.ctypes.data); setattr(d, nm + "_floats", a.size); keep.append(a)
+    lib().q3tts_op_codec_kernel.argtypes = [C.POINTER(CodecKernelDesc)]
+    _chk(lib().q3tts_op_codec_kernel(C.byref(d)))
+    return res
 
 
 def mel(audio):

@@ -255,6 +255,11 @@ class Codec:
     def reset(self):
         lib().q3o_codec_reset(self.h)
 
+    def set_frames_seen(self, n):
+        """absolute position of the next frame (what a decoder state's frame counter holds); histories are left as they are"""
+        lib().q3o_codec_set_frames_seen.argtypes = [C.c_void_p, C.c_int64]
+        lib().q3o_codec_set_frames_seen(self.h, int(n))
+
     def decode(self, codes, is_last=False):
         codes = np.ascontiguousarray(codes, np.int64).reshape(-1, 16)
         pcm = np.zeros(codes.shape[0] * self.spf, np.float32)
