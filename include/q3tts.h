@@ -473,6 +473,67 @@ int q3tts_op_attention(q3tts_attention_desc* d);
 /* host only (no device needed): the form AUTO picks for d's ntok / n_head / n_kv / flags -> form_ran; no buffer is read */
 int q3tts_attention_plan(q3tts_attention_desc* d);
 
+/* One talker / predictor linear-layer operation (csrc/kernels.hip, kernels_fused.hip) with a form forced, or as the engine dispatches it (AUTO).
+ * Ops: GEMV int8 x -> f32 super-segment slabs out[out_off + (s*ntok + t)*out_stride + r], s < ceil(K/2048), NOT summed;
+ *      GATEUP int8 x -> SwiGLU -> aq [ntok][ff] / ad [ntok][ff/32] (weights: gate rows [0, ff) then up rows);
+ *      NORM  h = h_in (+ parts) -> xq_out / xd_out [ntok][K] (+ h_out, xn_out);  NORM_GEMV: the same prologue -> f32 rows out[out_off + t*out_stride + r];
+ *      NORM_ARGMAX: the prologue -> keys[t*key_stride] (atomic first-max over rows [0, nrows_valid));  NORM_GATEUP: the prologue -> aq / ad;
+ *      F_GEMV f32 x -> f32 rows (out_off / out_stride as NORM_GEMV);  F_GATEUP f32 x -> SwiGLU -> f32 act out[out_off + t*out_stride + j], j < ff.
+ * Forced-form preconditions (refused before any allocation or launch; all forms: K % 256 == 0, 0 <= row0, row0 + nrows <= rows of the matrix):
+ *   GEMV_Q8 (k_gemv_q8<LPR,MT>)        Q8_0 weights; lpr in {2,4,8}, mt in {1,2,4,8}
+ *   GEMM_Q8_TOK (k_gemm_q8_tok)        Q8_0 weights
+ *   GEMM_Q8_MFMA (k_gemm_q8_mfma)      Q8_0 weights; 1 <= ztiles <= ceil(ntok/32)
+ *   GEMM_Q8_TILE1 (k_gemm_q8_tile1)    Q8_0; K <= 1024; nrows % 4 == 0; out_stride % 4 == 0; out + out_off 16-byte aligned; ztiles == ceil(ntok/32)
+ *   GEMV_KQ (k_gemv_kq<LPR,MT,TS>)     K-quant-file weights (any mix of Q5_K / Q6_K / Q8_0 tensors); lpr in {2,4,8}, mt in {1,2,4,8}
+ *   GEMM_KQ_MFMA (k_gemm_kq_mfma)      K-quant-file weights; 1 <= ztiles <= ceil(ntok/32)
+ *   GU_Q8_TILE1 / GU_Q8_MFMA           Q8_0; K in {1024, 2048}; ff % 32 == 0; ceil(ntiles/4) <= ztiles <= ntiles (TILE1: ztiles == ntiles)
+ *   GU_KQ_MFMA                         K-quant-file weights of ONE tensor type; the same K / ff / ztiles rules
+ *   GU_UNFUSED                         the GEMV the engine would run (any weights) + k_swiglu_quant; ff % 32 == 0; K <= 2048 (one slab)
+ *   NORM (k_rmsnorm_quant)             K <= 2048; parts_slab == ntok * parts_stride; takes idx (int32 rows) or idx_keys
+ *   NORM_WG (k_rmsnorm_quant_wg)       K <= 2048; no int32 idx
+ *   GEMV_NORM (k_gemv_q8_norm<LPR,MT,0>), GEMV_NORM_ARGMAX (<2,MT,1>), GU_SWIGLU_NORM (k_gateup_swiglu<MT,NSEG,TS>)
+ *                                      K <= 2048; no int32 idx; GEMV_NORM lpr in {2,4,8}; ARGMAX lpr 2; mt in {1,2,4,8} (GU: {1,2,4});
+ *                                      GU_SWIGLU_NORM: gate and up rows of one tensor type, ff % 32 == 0
+ *   F_GEMV (k_gemv_float<T,MT,1>)      float weights; mt in {1,2,4,8}
+ *   F_MFMA16 / F_MFMA                  float weights; row0 % 64 == 0; x 16-byte aligned; x_stride % 4 == 0
+ *   F_GU_MFMA16                        the same, nrows == 2 * ff, ff % 16 == 0 (the engine's 2..95-token window is a dispatch choice only)
+ *   F_GU_UNFUSED                       the float GEMV the engine would run + k_swiglu_f32
+ * Every buffer is uploaded whole and written back whole, so bytes outside the logical outputs show any stray write. */
+enum { Q3TTS_LOP_GEMV = 0, Q3TTS_LOP_GATEUP = 1, Q3TTS_LOP_NORM = 2, Q3TTS_LOP_NORM_GEMV = 3, Q3TTS_LOP_NORM_ARGMAX = 4, Q3TTS_LOP_NORM_GATEUP = 5,
+       Q3TTS_LOP_F_GEMV = 6, Q3TTS_LOP_F_GATEUP = 7 };
+enum { Q3TTS_LIN_AUTO = 0, Q3TTS_LIN_GEMV_Q8 = 1, Q3TTS_LIN_GEMM_Q8_TOK = 2, Q3TTS_LIN_GEMM_Q8_MFMA = 3, Q3TTS_LIN_GEMM_Q8_TILE1 = 4,
+       Q3TTS_LIN_GEMV_KQ = 5, Q3TTS_LIN_GEMM_KQ_MFMA = 6, Q3TTS_LIN_GU_Q8_TILE1 = 7, Q3TTS_LIN_GU_Q8_MFMA = 8, Q3TTS_LIN_GU_KQ_MFMA = 9,
+       Q3TTS_LIN_GU_UNFUSED = 10, Q3TTS_LIN_NORM = 11, Q3TTS_LIN_NORM_WG = 12, Q3TTS_LIN_GEMV_NORM = 13, Q3TTS_LIN_GEMV_NORM_ARGMAX = 14,
+       Q3TTS_LIN_GU_SWIGLU_NORM = 15, Q3TTS_LIN_F_GEMV = 16, Q3TTS_LIN_F_MFMA16 = 17, Q3TTS_LIN_F_MFMA = 18, Q3TTS_LIN_F_GU_MFMA16 = 19,
+       Q3TTS_LIN_F_GU_UNFUSED = 20 };
+typedef struct q3tts_linear_desc {
+    int32_t op, form;
+    /* weights: quantised = up to 3 raw GGUF tensors [rows[i]][K] of type[i] (8 Q8_0, 13 Q5_K, 14 Q6_K; all-Q8_0 = the Q8_0 file layout unless
+     * kq_layout != 0); float = raw[0] [rows[0]][K] of type[0] (0 f32, 1 f16, 30 bf16) */
+    int32_t nw; const void* raw[3]; int32_t type[3]; int32_t rows[3]; int32_t kq_layout;
+    int32_t K, row0, nrows, nrows_valid, ntok, ff;
+    int32_t lpr, mt, ztiles;       /* forced parameters, 0 = the plan's */
+    int32_t fused;                 /* GATEUP AUTO: the Transformer's fused switch */
+    const int8_t* xq; const uint16_t* xd; int32_t a_rows;                 /* int8 inputs [a_rows][K], [a_rows][K/32], a_rows >= ntok */
+    const float* x; int64_t x_floats; int32_t x_off, x_stride;             /* float inputs: row t at x + x_off + t*x_stride */
+    const float* h_in; int64_t h_floats; int32_t h_stride;                 /* norm prologue (NormPro) */
+    const uint64_t* idx_keys; const int32_t* idx; int32_t idx_stride;      /* row select: argmax key (low word ~index) or int32 (NORM only) */
+    const float* parts; int64_t parts_floats; int32_t nparts, parts_stride; int64_t parts_slab;
+    const float* g; float eps;
+    float* h_out; float* xn_out;                                           /* [ntok][K] each, or NULL */
+    int8_t* xq_out; uint16_t* xd_out;                                      /* NORM / NORM_WG: [ntok][K], [ntok][K/32] */
+    uint64_t* keys; int64_t n_keys; int32_t key_stride; const int32_t* mask_per_tok; int32_t idx_add;  /* argmax epilogue */
+    float* out; int64_t out_floats, out_off; int32_t out_stride;
+    int8_t* aq; uint16_t* ad;                                              /* gate/up: [ntok][ff], [ntok][ff/32] */
+    int32_t form_ran, lpr_ran, mt_ran, z_ran;                              /* out: what ran */
+} q3tts_linear_desc;
+int q3tts_op_linear(q3tts_linear_desc* d);
+/* host only (no device needed): the engine's dispatch for d's op and shape -> form_ran / lpr_ran / mt_ran / z_ran.  Buffers are not read; their
+ * addresses count only for alignment (NULL = aligned; out_off and x_off still apply). */
+int q3tts_linear_plan(q3tts_linear_desc* d);
+/* host only: the argmax key the device packs for logit v at index idx (kdev.h pack_key: order-preserving value bits, ~idx, -0 as +0) */
+uint64_t q3tts_argmax_key(float v, int32_t idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,250 @@ static void attention_op_run(q3tts_attention_desc* dp) {
     d.form_ran = form;
 }
 
+// ---- q3tts_op_linear: one linear-layer operation through the same run_* launches as the engine ----
+static bool lin_quant(const q3tts_linear_desc& d) { return d.op <= LOP_NORM_GATEUP && d.op != LOP_NORM; }
+static bool lin_kq(const q3tts_linear_desc& d) {
+    if (d.kq_layout || d.nw > 1) return true;
+    return d.type[0] != Q3_T_Q8_0;
+}
+static int lin_rows(const q3tts_linear_desc& d) { int n = 0; for (int i = 0; i < d.nw; i++) n += d.rows[i]; return n; }
+static int lin_wts(const q3tts_linear_desc& d) { // wslice_ts of the matrix kqmat_from_host builds (tensors of one type in a row merge)
+    if (d.op >= LOP_F_GEMV) return d.type[0];
+    if (!lin_kq(d)) return 0;
+    int n = 0, last = -1;
+    for (int i = 0; i < d.nw; i++) if (d.type[i] != last) { n++; last = d.type[i]; }
+    return n == 1 ? d.type[0] : -1;
+}
+static LinearPlanIn lin_plan_in(const q3tts_linear_desc& d) {
+    LinearPlanIn in;
+    in.op = d.op; in.K = d.K; in.row0 = d.row0; in.nrows = d.nrows; in.ntok = d.ntok; in.ff = d.ff;
+    in.kq = lin_quant(d) && lin_kq(d); in.wts = lin_wts(d); in.has_wt = true;
+    if (in.kq) { int n = 0, last = -1; for (int i = 0; i < d.nw; i++) if (d.type[i] != last) { n++; last = d.type[i]; } in.kq_parts = n; }
+    in.out_stride = d.out_stride; in.out_addr = (uintptr_t)d.out_off * 4 + (d.out ? (uintptr_t)d.out : 0);
+    in.x_stride = d.x_stride; in.x_addr = (uintptr_t)d.x_off * 4 + (d.x ? (uintptr_t)d.x : 0);
+    in.aq_addr = 0; in.fused = d.fused != 0;
+    return in;
+}
+static LinearPlan lin_plan(const q3tts_linear_desc& d) {
+    Q3_CHECK(d.op >= LOP_GEMV && d.op <= LOP_F_GATEUP, "unknown linear op");
+    Q3_CHECK(d.K >= 256 && d.K % 256 == 0 && d.ntok >= 1 && d.ntok <= 65535 && d.nrows >= 1 && d.row0 >= 0, "bad linear shape");
+    return plan_linear(lin_plan_in(d));
+}
+static bool in_set(int v, std::initializer_list<int> s) { for (int x : s) if (v == x) return true; return false; }
+static int op_of_form(int f) {
+    if (f <= LIN_GEMM_KQ_MFMA) return LOP_GEMV;
+    if (f <= LIN_GU_UNFUSED) return LOP_GATEUP;
+    if (f <= LIN_NORM_WG) return LOP_NORM;
+    if (f == LIN_GEMV_NORM) return LOP_NORM_GEMV;
+    if (f == LIN_GEMV_NORM_ARGMAX) return LOP_NORM_ARGMAX;
+    if (f == LIN_GU_SWIGLU_NORM) return LOP_NORM_GATEUP;
+    if (f <= LIN_F_MFMA) return LOP_F_GEMV;
+    return LOP_F_GATEUP;
+}
+// every precondition of the form (include/q3tts.h), checked on the host before anything is allocated or launched
+static void lin_check(const q3tts_linear_desc& d, const LinearPlan& p) {
+    const int f = p.form, K = d.K, nt = d.ntok, ntiles = (nt + 31) / 32;
+    Q3_CHECK(f >= LIN_GEMV_Q8 && f <= LIN_F_GU_UNFUSED && op_of_form(f) == d.op, "the form does not compute this op");
+    const bool quant = lin_quant(d), kq = quant && lin_kq(d), norm = d.op >= LOP_NORM && d.op <= LOP_NORM_GATEUP;
+    if (d.op != LOP_NORM) {
+        Q3_CHECK(d.nw >= 1 && d.nw <= 3, "1 to 3 weight tensors");
+        for (int i = 0; i < d.nw; i++) Q3_CHECK(d.raw[i] && d.rows[i] >= 1, "missing weight tensor");
+        if (d.op >= LOP_F_GEMV) Q3_CHECK(d.nw == 1 && (d.type[0] == Q3_T_F32 || d.type[0] == Q3_T_F16 || d.type[0] == Q3_T_BF16), "float ops take one f32 / f16 / bf16 tensor");
+        else if (kq) for (int i = 0; i < d.nw; i++) Q3_CHECK(in_set(d.type[i], {Q3_T_Q8_0, Q3_T_Q5_K, Q3_T_Q6_K}) && d.rows[i] % 32 == 0, "K-quant layout: Q8_0 / Q5_K / Q6_K tensors of 32-row multiples");
+        Q3_CHECK(d.row0 + d.nrows <= lin_rows(d), "rows past the matrix");
+    }
+    if (d.op == LOP_GATEUP) Q3_CHECK(K <= 2048, "int8 gate/up: K <= 2048 (k_swiglu_quant reads one super-segment slab)");
+    if (d.op == LOP_GATEUP || d.op == LOP_NORM_GATEUP || d.op == LOP_F_GATEUP)
+        Q3_CHECK(d.row0 == 0 && d.nrows == 2 * d.ff && d.ff >= 1 && d.ff % (d.op == LOP_F_GATEUP ? 1 : 32) == 0, "gate/up: row0 0, nrows 2 * ff, ff % 32 == 0");
+    if (quant && !norm) Q3_CHECK(d.xq && d.xd && d.a_rows >= nt, "int8 activations [a_rows >= ntok][K]");
+    if (d.op >= LOP_F_GEMV) Q3_CHECK(d.x && d.x_off >= 0 && d.x_stride >= K && d.x_off + (int64_t)(nt - 1) * d.x_stride + K <= d.x_floats, "float activations out of their buffer");
+    if (norm) {
+        Q3_CHECK(K <= 2048 && d.h_in && d.g && d.h_stride >= K, "norm prologue: K <= 2048, h_in and g required");
+        Q3_CHECK(!(d.idx && d.idx_keys), "idx or idx_keys, not both");
+        if (d.idx) Q3_CHECK(f == LIN_NORM, "int32 row indices: NORM only");
+        for (int t = 0; t < nt; t++) {
+            int64_t row = t;
+            if (d.idx) row = d.idx[(size_t)t * d.idx_stride];
+            else if (d.idx_keys) row = key_code(d.idx_keys[(size_t)t * d.idx_stride]);
+            Q3_CHECK(row >= 0 && row * d.h_stride + K <= d.h_floats, "selected h_in row outside h_in");
+        }
+        Q3_CHECK(d.nparts >= 0 && (d.nparts == 0 || (d.parts && d.parts_stride >= K && d.parts_slab >= 0 &&
+                 (int64_t)(d.nparts - 1) * d.parts_slab + (int64_t)(nt - 1) * d.parts_stride + K <= d.parts_floats)), "residual slabs out of their buffer");
+        if (f == LIN_NORM && d.nparts > 1) Q3_CHECK(d.parts_slab == (int64_t)nt * d.parts_stride, "NORM: slabs are ntok * parts_stride apart");
+        if (d.op == LOP_NORM) Q3_CHECK(d.xq_out && d.xd_out, "NORM: xq_out / xd_out required");
+    }
+    if (in_set(d.op, {LOP_GEMV, LOP_NORM_GEMV, LOP_F_GEMV, LOP_F_GATEUP})) {
+        const int64_t cols = d.op == LOP_F_GATEUP ? d.ff : d.nrows;
+        const int64_t slabs = d.op == LOP_GEMV ? (K / 256 + 7) / 8 : 1;
+        Q3_CHECK(d.out && d.out_off >= 0 && d.out_stride >= cols && d.out_off + (slabs * nt - 1) * d.out_stride + cols <= d.out_floats, "output out of its buffer");
+    }
+    if (in_set(d.op, {LOP_GATEUP, LOP_NORM_GATEUP})) Q3_CHECK(d.aq && d.ad, "gate/up: aq / ad required");
+    if (f == LIN_GEMV_NORM_ARGMAX) {
+        Q3_CHECK(d.keys && d.key_stride >= 1 && (int64_t)(nt - 1) * d.key_stride < d.n_keys, "argmax keys out of their buffer");
+        Q3_CHECK(d.nrows_valid >= 1 && d.nrows_valid <= d.nrows, "1 <= nrows_valid <= nrows");
+    }
+    const bool q8 = quant && !kq;
+    switch (f) {
+    case LIN_GEMV_Q8: case LIN_GEMV_KQ:
+        Q3_CHECK(f == LIN_GEMV_Q8 ? q8 : kq, "GEMV_Q8 takes the Q8_0 layout, GEMV_KQ the K-quant layout");
+        Q3_CHECK(in_set(p.lpr, {2, 4, 8}) && in_set(p.mt, {1, 2, 4, 8}), "lpr in {2,4,8}, mt in {1,2,4,8}");
+        break;
+    case LIN_GEMM_Q8_TOK: Q3_CHECK(q8, "GEMM_Q8_TOK takes the Q8_0 layout"); break;
+    case LIN_GEMM_Q8_MFMA: case LIN_GEMM_KQ_MFMA:
+        Q3_CHECK(f == LIN_GEMM_Q8_MFMA ? q8 : kq, "GEMM_Q8_MFMA takes the Q8_0 layout, GEMM_KQ_MFMA the K-quant layout");
+        Q3_CHECK(p.z >= 1 && p.z <= ntiles, "1 <= ztiles <= token tiles");
+        break;
+    case LIN_GEMM_Q8_TILE1:
+        Q3_CHECK(q8 && K <= 1024 && d.nrows % 4 == 0 && d.out_stride % 4 == 0 && ((uintptr_t)(d.out + d.out_off) & 15) == 0 && p.z == ntiles,
+                 "GEMM_Q8_TILE1: Q8_0, K <= 1024, nrows % 4 == 0, out_stride % 4 == 0, 16-byte out, ztiles == token tiles");
+        break;
+    case LIN_GU_Q8_TILE1: case LIN_GU_Q8_MFMA: case LIN_GU_KQ_MFMA:
+        Q3_CHECK(f == LIN_GU_KQ_MFMA ? (kq && lin_wts(d) != -1) : q8, "GU_Q8_*: Q8_0 layout; GU_KQ_MFMA: K-quant layout of one tensor type");
+        Q3_CHECK((K == 1024 || K == 2048) && d.ff % 32 == 0, "fused gate/up: K in {1024, 2048}, ff % 32 == 0");
+        Q3_CHECK(p.z >= (ntiles + 3) / 4 && p.z <= ntiles && (f != LIN_GU_Q8_TILE1 || p.z == ntiles), "fused gate/up: ceil(tiles/4) <= ztiles <= tiles (TILE1: == tiles)");
+        break;
+    case LIN_GEMV_NORM: case LIN_GEMV_NORM_ARGMAX: case LIN_GU_SWIGLU_NORM:
+        Q3_CHECK(f == LIN_GU_SWIGLU_NORM ? (in_set(p.mt, {1, 2, 4}) && lin_wts(d) != -1) : in_set(p.mt, {1, 2, 4, 8}), "mt out of range / GU_SWIGLU_NORM needs one tensor type");
+        Q3_CHECK(f == LIN_GU_SWIGLU_NORM || (f == LIN_GEMV_NORM_ARGMAX ? p.lpr == 2 : in_set(p.lpr, {2, 4, 8})), "GEMV_NORM: lpr in {2,4,8}; ARGMAX: lpr 2");
+        break;
+    case LIN_F_GEMV: Q3_CHECK(in_set(p.mt, {1, 2, 4, 8}), "mt in {1,2,4,8}"); break;
+    case LIN_F_MFMA16: case LIN_F_MFMA: case LIN_F_GU_MFMA16:
+        Q3_CHECK(d.row0 % 64 == 0 && ((uintptr_t)(d.x + d.x_off) & 15) == 0 && d.x_stride % 4 == 0, "float matrix-core forms: row0 % 64 == 0, 16-byte x, x_stride % 4 == 0");
+        if (f == LIN_F_GU_MFMA16) Q3_CHECK(d.ff % 16 == 0, "F_GU_MFMA16: ff % 16 == 0");
+        break;
+    default: break;
+    }
+}
+static void lin_run(q3tts_linear_desc* dp) {
+    Q3_CHECK(dp, "null linear descriptor");
+    q3tts_linear_desc& d = *dp;
+    LinearPlan p = lin_plan(d);
+    if (d.form != LIN_AUTO) { // forced: the plan's parameters unless given
+        Q3_CHECK(d.form >= LIN_GEMV_Q8 && d.form <= LIN_F_GU_UNFUSED, "unknown linear form");
+        LinearPlan fp; fp.form = d.form; fp.nseg = d.K / 256;
+        const int f = d.form, ntiles = (d.ntok + 31) / 32;
+        const int mt_def = d.ntok == 1 ? 1 : d.ntok == 2 ? 2 : d.ntok <= 4 ? 4 : 8;
+        fp.mt = d.mt ? d.mt : (p.form == f && p.mt ? p.mt : (f == LIN_GU_SWIGLU_NORM ? (mt_def > 4 ? 4 : mt_def) : mt_def));
+        fp.lpr = d.lpr ? d.lpr : (p.form == f && p.lpr ? p.lpr : (f == LIN_GEMV_NORM_ARGMAX ? 2 : 8));
+        int zdef = p.form == f && p.z ? p.z : ntiles;
+        fp.z = d.ztiles ? d.ztiles : zdef;
+        p = fp;
+    }
+    lin_check(d, p);
+    const int K = d.K, nt = d.ntok, ff = d.ff;
+    // weights
+    DevBuf<uint8_t> storage, fw, fwt;
+    Q8Mat m; FMat fm;
+    if (d.op >= LOP_F_GEMV) {
+        const int n = d.rows[0];
+        const size_t esz = d.type[0] == Q3_T_F32 ? 4 : 2;
+        fw.alloc((size_t)n * K * esz); fw.upload((const uint8_t*)d.raw[0], fw.n);
+        fwt.alloc((size_t)((n + 63) / 64) * 64 * K * esz);
+        launch_tile_float(0, fw.p, fwt.p, d.type[0], n, K);
+        fm.w = fw.p; fm.wt = fwt.p; fm.type = d.type[0]; fm.N = n; fm.K = K;
+    } else if (d.op != LOP_NORM) {
+        if (!lin_kq(d)) m = q8mat_from_host(d.raw[0], d.rows[0], K, storage);
+        else {
+            KqPart parts[3];
+            for (int i = 0; i < d.nw; i++) parts[i] = KqPart{d.raw[i], d.type[i], d.rows[i]};
+            m = kqmat_from_host(parts, d.nw, K, storage);
+        }
+    }
+    // inputs
+    DevBuf<int8_t> dxq; DevBuf<uint16_t> dxd; DevBuf<float> dx, dh, dparts, dg, dhout, dxn, dout, dgu;
+    DevBuf<q3_u64> dkeys_in, dkeys; DevBuf<int32_t> didx, dmask; DevBuf<int8_t> daq, dxq_out; DevBuf<uint16_t> dad, dxd_out;
+    if (d.xq) { dxq.alloc((size_t)d.a_rows * K); dxq.upload(d.xq, dxq.n); dxd.alloc((size_t)d.a_rows * (K / 32)); dxd.upload(d.xd, dxd.n); }
+    if (d.op >= LOP_F_GEMV) { dx.alloc((size_t)d.x_floats); dx.upload(d.x, dx.n); }
+    NormPro a{};
+    const bool norm = d.op >= LOP_NORM && d.op <= LOP_NORM_GATEUP;
+    if (norm) {
+        dh.alloc((size_t)d.h_floats); dh.upload(d.h_in, dh.n);
+        dg.alloc(K); dg.upload(d.g, K);
+        a.h_in = dh.p; a.h_stride = d.h_stride; a.g = dg.p; a.eps = d.eps; a.idx_stride = d.idx_stride;
+        if (d.idx_keys) { dkeys_in.alloc((size_t)(nt - 1) * d.idx_stride + 1); dkeys_in.upload((const q3_u64*)d.idx_keys, dkeys_in.n); a.idx_keys = dkeys_in.p; }
+        if (d.idx) { didx.alloc((size_t)(nt - 1) * d.idx_stride + 1); didx.upload(d.idx, didx.n); }
+        if (d.nparts > 0) { dparts.alloc((size_t)d.parts_floats); dparts.upload(d.parts, dparts.n); }
+        a.parts = dparts.p; a.nparts = d.nparts; a.parts_stride = d.parts_stride; a.parts_slab = (size_t)d.parts_slab;
+        if (d.h_out) { dhout.alloc((size_t)nt * K); dhout.upload(d.h_out, dhout.n); a.h_out = dhout.p; }
+        if (d.xn_out) { dxn.alloc((size_t)nt * K); dxn.upload(d.xn_out, dxn.n); a.xn_out = dxn.p; }
+    }
+    if (d.out) { dout.alloc((size_t)d.out_floats); dout.upload(d.out, dout.n); }
+    if (d.aq) { daq.alloc((size_t)nt * ff); daq.upload(d.aq, daq.n); dad.alloc((size_t)nt * (ff / 32)); dad.upload(d.ad, dad.n); }
+    float* out = d.out ? dout.p + d.out_off : nullptr;
+    switch (p.form) {
+    case LIN_GEMV_Q8: case LIN_GEMM_Q8_TOK: case LIN_GEMM_Q8_MFMA: case LIN_GEMM_Q8_TILE1: case LIN_GEMV_KQ: case LIN_GEMM_KQ_MFMA:
+        run_gemv_q8(0, p, m, d.row0, d.nrows, dxq.p, dxd.p, out, d.out_stride, nt);
+        break;
+    case LIN_GU_Q8_TILE1: case LIN_GU_Q8_MFMA: case LIN_GU_KQ_MFMA:
+        run_gateup_q8(0, p, m, ff, dxq.p, dxd.p, daq.p, dad.p, nt);
+        break;
+    case LIN_GU_UNFUSED: { // what Transformer::forward runs when the fused gate/up form does not apply
+        dgu.alloc((size_t)((K / 256 + 7) / 8) * nt * 2 * ff);
+        LinearPlanIn gi = linear_plan_in(LOP_GEMV, m, 0, 2 * ff, nt);
+        gi.out_stride = 2 * ff; gi.out_addr = (uintptr_t)dgu.p;
+        const LinearPlan gp = plan_linear(gi);
+        run_gemv_q8(0, gp, m, 0, 2 * ff, dxq.p, dxd.p, dgu.p, 2 * ff, nt);
+        launch_swiglu_quant(0, dgu.p, ff, daq.p, dad.p, nt);
+        p.lpr = gp.lpr; p.mt = gp.mt; p.z = gp.z;
+        break;
+    }
+    case LIN_NORM: {
+        dxq_out.alloc((size_t)nt * K); dxq_out.upload(d.xq_out, dxq_out.n); dxd_out.alloc((size_t)nt * (K / 32)); dxd_out.upload(d.xd_out, dxd_out.n);
+        NormArgs na{};
+        na.h_in = a.h_in; na.h_stride = a.h_stride; na.idx = didx.p; na.idx_stride = d.idx_stride; na.idx_keys = a.idx_keys; na.parts = a.parts;
+        na.nparts = a.nparts; na.parts_stride = a.parts_stride; na.h_out = a.h_out; na.g = a.g; na.eps = a.eps; na.d = K; na.xq = dxq_out.p; na.xd = dxd_out.p;
+        na.xn_out = a.xn_out;
+        launch_rmsnorm_quant(0, na, nt);
+        break;
+    }
+    case LIN_NORM_WG:
+        dxq_out.alloc((size_t)nt * K); dxq_out.upload(d.xq_out, dxq_out.n); dxd_out.alloc((size_t)nt * (K / 32)); dxd_out.upload(d.xd_out, dxd_out.n);
+        launch_rmsnorm_quant_wg(0, a, K, dxq_out.p, dxd_out.p, nt);
+        break;
+    case LIN_GEMV_NORM: case LIN_GEMV_NORM_ARGMAX: {
+        ArgmaxEpi am{};
+        if (p.form == LIN_GEMV_NORM_ARGMAX) {
+            dkeys.alloc((size_t)d.n_keys); dkeys.upload((const q3_u64*)d.keys, dkeys.n);
+            if (d.mask_per_tok) { dmask.alloc(nt); dmask.upload(d.mask_per_tok, nt); }
+            am.keys = dkeys.p; am.key_stride = d.key_stride; am.mask_per_tok = dmask.p; am.idx_add = d.idx_add;
+            run_gemv_q8_norm(0, p, m, d.row0, d.nrows_valid, a, nullptr, 0, nt, &am);
+        } else run_gemv_q8_norm(0, p, m, d.row0, d.nrows, a, out, d.out_stride, nt, nullptr);
+        break;
+    }
+    case LIN_GU_SWIGLU_NORM: run_gateup_swiglu(0, p, m, ff, a, daq.p, dad.p, nt); break;
+    case LIN_F_GEMV: case LIN_F_MFMA16: case LIN_F_MFMA:
+        run_gemv_float(0, p, fm, d.row0, d.nrows, dx.p + d.x_off, d.x_stride, out, d.out_stride, nt);
+        break;
+    case LIN_F_GU_MFMA16:
+        dgu.alloc((size_t)nt * ff);
+        run_gateup_float(0, p, fm, ff, dx.p + d.x_off, d.x_stride, dgu.p, nt);
+        break;
+    case LIN_F_GU_UNFUSED: { // the float matmul the engine would run + k_swiglu_f32
+        dgu.alloc((size_t)nt * 2 * ff);
+        LinearPlanIn gi = lin_plan_in(d); gi.op = LOP_F_GEMV;
+        const LinearPlan gp = plan_linear(gi);
+        run_gemv_float(0, gp, fm, 0, 2 * ff, dx.p + d.x_off, d.x_stride, dgu.p, 2 * ff, nt);
+        DevBuf<float> act((size_t)nt * ff);
+        launch_swiglu_f32(0, dgu.p, ff, act.p, nt);
+        Q3_HIP(hipMemcpy2D(out, (size_t)d.out_stride * 4, act.p, (size_t)ff * 4, (size_t)ff * 4, nt, hipMemcpyDeviceToDevice));
+        Q3_HIP(hipDeviceSynchronize());
+        p.lpr = gp.lpr; p.mt = gp.mt; p.z = gp.z;
+        break;
+    }
+    default: throw Error("unhandled linear form");
+    }
+    Q3_LAUNCH_CHECK();
+    if (p.form == LIN_F_GU_MFMA16) Q3_HIP(hipMemcpy2D(out, (size_t)d.out_stride * 4, dgu.p, (size_t)ff * 4, (size_t)ff * 4, nt, hipMemcpyDeviceToDevice));
+    Q3_HIP(hipDeviceSynchronize());
+    if (d.out) dout.download(d.out, dout.n);
+    if (d.aq) { daq.download(d.aq, daq.n); dad.download(d.ad, dad.n); }
+    if (d.h_out) dhout.download(d.h_out, dhout.n);
+    if (d.xn_out) dxn.download(d.xn_out, dxn.n);
+    if (dxq_out.p) { dxq_out.download(d.xq_out, dxq_out.n); dxd_out.download(d.xd_out, dxd_out.n); }
+    if (dkeys.p) dkeys.download((q3_u64*)d.keys, dkeys.n);
+    d.form_ran = p.form; d.lpr_ran = p.lpr; d.mt_ran = p.mt; d.z_ran = p.z;
+}
+
 extern "C" {
 
 int q3tts_op_attention(q3tts_attention_desc* d) {
@@ -124,6 +368,25 @@ int q3tts_attention_plan(q3tts_attention_desc* d) {
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+
+int q3tts_op_linear(q3tts_linear_desc* d) {
+    Q3_API_BEGIN
+    require_gpu();
+    lin_run(d);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_linear_plan(q3tts_linear_desc* d) {
+    Q3_API_BEGIN
+    Q3_CHECK(d, "null linear descriptor");
+    const LinearPlan p = lin_plan(*d);
+    d->form_ran = p.form; d->lpr_ran = p.lpr; d->mt_ran = p.mt; d->z_ran = p.z;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+uint64_t q3tts_argmax_key(float v, int32_t idx) { return pack_key(v, idx); }
 
 int q3tts_op_gemv_q8(const void* w, int32_t n, int32_t k, const int8_t* xq, const uint16_t* xd, int32_t ntok, float* y, int32_t lpr) {
     Q3_API_BEGIN

@@ -134,7 +134,10 @@ struct NormPro {
 };
 // epilogue of the head GEMV: first-max argmax through one 64-bit atomicMax per workgroup and token
 struct ArgmaxEpi {
-    q3_u64* keys; int key_stride;               // keys[tok*key_stride], pre-armed with pack_key(-inf, 0)
+    // keys[tok*key_stride], pre-armed with pack_key(-inf, 0).  A row takes part when it is valid, not the masked index and its logit is > -inf
+    // (NaN never does); among those the first maximum wins, as the oracle's greedy pick.  A token with no such row keeps the armed key: code 0,
+    // whatever idx_add is.  The oracle returns `start` there; the engine passes idx_add = 0 with slice-relative codes, where the two agree.
+    q3_u64* keys; int key_stride;
     const int32_t* mask_per_tok;                // optional: index excluded from the argmax (EOS masking)
     int idx_add;                                // added to the row index (0: slice-relative codes)
 };
@@ -157,6 +160,41 @@ void launch_project_blk(hipStream_t st, const float* x, int x_stride, const floa
                         int n_in, int n_out, float* out, int out_stride, int ntok);
 // [EXT] streaming-text feedback (q3tts_spec.h): slot b's last addend is text(ids[b*ids_stride + f]) while f = n_frames[b] < n_trail[b],
 // tts_pad after; text() reads table rows [0, rows) and computes the fallback row in-kernel for any other id
+// ---- linear-layer dispatch: one host-only rule (plan_linear) that every launcher above and q3tts_op_linear follow ----
+// The ops and forms mirror include/q3tts.h's Q3TTS_LOP_* / Q3TTS_LIN_* (same numbers).
+enum LinearOp { LOP_GEMV = 0, LOP_GATEUP = 1, LOP_NORM = 2, LOP_NORM_GEMV = 3, LOP_NORM_ARGMAX = 4, LOP_NORM_GATEUP = 5, LOP_F_GEMV = 6,
+                LOP_F_GATEUP = 7 };
+enum LinearForm { LIN_AUTO = 0, LIN_GEMV_Q8 = 1, LIN_GEMM_Q8_TOK = 2, LIN_GEMM_Q8_MFMA = 3, LIN_GEMM_Q8_TILE1 = 4, LIN_GEMV_KQ = 5,
+                  LIN_GEMM_KQ_MFMA = 6, LIN_GU_Q8_TILE1 = 7, LIN_GU_Q8_MFMA = 8, LIN_GU_KQ_MFMA = 9, LIN_GU_UNFUSED = 10, LIN_NORM = 11,
+                  LIN_NORM_WG = 12, LIN_GEMV_NORM = 13, LIN_GEMV_NORM_ARGMAX = 14, LIN_GU_SWIGLU_NORM = 15, LIN_F_GEMV = 16, LIN_F_MFMA16 = 17,
+                  LIN_F_MFMA = 18, LIN_F_GU_MFMA16 = 19, LIN_F_GU_UNFUSED = 20 };
+struct LinearPlanIn {
+    int op = LOP_GEMV;
+    int K = 0, row0 = 0, nrows = 0, ntok = 0, ff = 0;
+    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 8 / 13 / 14 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
+    bool kq = false;      // quantised matrix built from K-quant-file tensors (Q8Mat::rg_type != null)
+    int kq_parts = 0;     // Q8Mat::nparts
+    bool has_wt = false;  // float: the tiled copy exists
+    int out_stride = 0; uintptr_t out_addr = 0;   // address bits only (alignment tests)
+    int x_stride = 0; uintptr_t x_addr = 0;
+    uintptr_t aq_addr = 0;
+    int lpr_hint = 0;     // launch_gemv_q8's lpr_hint (0 = none)
+    bool fused = true;    // LOP_GATEUP: the Transformer's `fused` switch (false: GEMV + k_swiglu_quant always)
+};
+struct LinearPlan { int form = LIN_AUTO, lpr = 0, mt = 0, z = 0, nseg = 0; };
+LinearPlan plan_linear(const LinearPlanIn& in);
+// the launch of one planned form (no dispatch left: the plan's form, LPR, MT and z tiles are used as given)
+void run_gemv_q8(hipStream_t st, const LinearPlan& p, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd, float* out,
+                 int out_stride, int ntok);
+void run_gateup_q8(hipStream_t st, const LinearPlan& p, const Q8Mat& wgu, int ff, const int8_t* xq, const uint16_t* xd, int8_t* aq, uint16_t* ad,
+                   int ntok);
+void run_gemv_q8_norm(hipStream_t st, const LinearPlan& p, const Q8Mat& w, int row0, int nrows, const NormPro& a, float* out, int out_stride,
+                      int ntok, const ArgmaxEpi* am);
+void run_gateup_swiglu(hipStream_t st, const LinearPlan& p, const Q8Mat& wgu, int ff, const NormPro& a, int8_t* aq, uint16_t* ad, int ntok);
+void run_gemv_float(hipStream_t st, const LinearPlan& p, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out,
+                    int out_stride, int ntok);
+void run_gateup_float(hipStream_t st, const LinearPlan& p, const FMat& wgu, int ff, const float* x, int x_stride, float* act, int ntok);
+LinearPlanIn linear_plan_in(int op, const Q8Mat& w, int row0, int nrows, int ntok);
 struct TextTrail {
     const int32_t* n_frames = nullptr; const int32_t* n_trail = nullptr; const int32_t* ids = nullptr; int ids_stride = 0;
     const float* table = nullptr; int64_t rows = 0;

@@ -189,11 +189,10 @@ __global__ void __launch_bounds__(512) k_gemv_kq(Q8Mat w, int row0, int nrows, c
     }
 }
 template <int LPR>
-static void gemv_kq_mt(hipStream_t st, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd, float* out,
+static void gemv_kq_mt(hipStream_t st, int mt, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd, float* out,
                        int out_stride, int ntok) {
     constexpr int R = 64 / LPR;
     const int nseg = w.K >> 8, nsseg = (nseg + 7) / 8, nw = nseg < 8 ? nseg : 8;
-    const int mt = ntok == 1 ? 1 : ntok == 2 ? 2 : ntok <= 4 ? 4 : 8;
     dim3 grid((nrows + R - 1) / R, nsseg, (ntok + mt - 1) / mt);
     if (mt == 1) Q3_TS_SWITCH(w, hipLaunchKernelGGL((k_gemv_kq<LPR, 1, TS>), grid, dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok));
     else if (mt == 2) Q3_TS_SWITCH(w, hipLaunchKernelGGL((k_gemv_kq<LPR, 2, TS>), grid, dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok));
@@ -211,82 +210,157 @@ static void gemv_launch(hipStream_t st, const Q8Mat& w, int row0, int nrows, con
     hipLaunchKernelGGL((k_gemv_q8<LPR, MT>), grid, dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok);
 }
 template <int LPR>
-static void gemv_launch_mt(hipStream_t st, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd,
+static void gemv_launch_mt(hipStream_t st, int mt, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd,
                            float* out, int out_stride, int ntok) {
-    if (ntok == 1) gemv_launch<LPR, 1>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-    else if (ntok == 2) gemv_launch<LPR, 2>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-    else if (ntok <= 4) gemv_launch<LPR, 4>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
+    if (mt == 1) gemv_launch<LPR, 1>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
+    else if (mt == 2) gemv_launch<LPR, 2>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
+    else if (mt == 4) gemv_launch<LPR, 4>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
     else gemv_launch<LPR, 8>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
 }
-void launch_gemv_q8(hipStream_t st, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd,
-                    float* out, int out_stride, int ntok, int lpr_hint) {
-    const int nsseg = ((w.K >> 8) + 7) / 8;
-    if (w.rg_type && ntok >= 16 && !lpr_hint && kq_mfma()) { // K-quant rows on the matrix cores (k_gemm_kq_mfma)
-        const int nseg = w.K >> 8, nw = nseg < 8 ? nseg : 8;
-        const int rgs = (nrows + 31) / 32;
-        Q3_TS_SWITCH(w, hipLaunchKernelGGL((k_gemm_kq_mfma<false, TS>), dim3(rgs, nsseg, mfma_ztiles(rgs, nsseg, ntok)), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr));
-        return;
+
+// -----------------------------------------------------------------------------------------------------
+// The dispatch rule of every linear-layer launcher (host only: no device, no memory access).  Reads the same environment knobs with the
+// same defaults as the launchers always did; launch_* = plan_linear + run_*.
+// -----------------------------------------------------------------------------------------------------
+static int mt_of(int ntok) { return ntok == 1 ? 1 : ntok == 2 ? 2 : ntok <= 4 ? 4 : 8; }
+static int gemv_lpr(long rows32, long rows16) { return rows32 >= 512 ? 2 : rows16 >= 256 ? 4 : 8; }
+LinearPlanIn linear_plan_in(int op, const Q8Mat& w, int row0, int nrows, int ntok) {
+    LinearPlanIn in;
+    in.op = op; in.K = w.K; in.row0 = row0; in.nrows = nrows; in.ntok = ntok;
+    in.kq = w.rg_type != nullptr; in.kq_parts = w.nparts; in.wts = wslice_ts(w);
+    return in;
+}
+LinearPlan plan_linear(const LinearPlanIn& in) {
+    LinearPlan p;
+    const int nseg = in.K >> 8, nsseg = (nseg + 7) / 8, nw = nseg < 8 ? nseg : 8, ntiles = (in.ntok + 31) / 32;
+    p.nseg = nseg;
+    switch (in.op) {
+    case LOP_GEMV: {
+        if (in.kq && in.ntok >= 16 && !in.lpr_hint && kq_mfma()) { // K-quant rows on the matrix cores (k_gemm_kq_mfma)
+            p.form = LIN_GEMM_KQ_MFMA; p.z = mfma_ztiles((in.nrows + 31) / 32, nsseg, in.ntok);
+            return p;
+        }
+        if (in.kq) { // mixed K-quant matrix: one kernel handles every type; tokens beyond 8 go to z tiles
+            int lpr = in.lpr_hint;
+            if (!lpr) lpr = gemv_lpr((long)(in.nrows / 32) * nsseg, (long)(in.nrows / 16) * nsseg);
+            // Q6_K rows with 8 lanes per row: measured 14.6-62 us per launch for the predictor's 1024 x 3072 down-projection (2.1 MB; the Q5_K
+            // layers of the same shape take 4.7 us) with the same instruction and fetch counts but 4 x the SQ busy cycles
+            // (gpurun_out/pmc_kq.txt, round 2); 4 lanes per row does not show it, so Q6_K matrices stop at 4.  Q3_KQ_Q6_LPR8=1 restores 8 for A/B.
+            static const bool q6_lpr8 = [] { const char* e = std::getenv("Q3_KQ_Q6_LPR8"); return e && e[0] == '1'; }();
+            if (lpr == 8 && !in.lpr_hint && !q6_lpr8 && in.wts != Q3_T_Q5_K && in.wts != Q3_T_Q8_0) lpr = 4;
+            p.form = LIN_GEMV_KQ; p.lpr = lpr; p.mt = mt_of(in.ntok);
+            return p;
+        }
+        if (in.ntok >= 16 && !in.lpr_hint) { // matrix-core path: exact int8 block dots for 32 tokens x 32 rows per MFMA
+            p.z = mfma_ztiles((in.nrows + 31) / 32, nsseg, in.ntok);
+            // one token tile per workgroup and K <= 1024 (4 waves): the latency-tuned form.  Measured in-graph at 64 tokens (profiles/r03_gemm_stamps.txt): predictor
+            // q,k,v 4.67 -> 4.46 us, head 4.50 -> 4.35; with 8 waves per workgroup (K >= 2048) its extra matrix instruction per block costs more than the
+            // combine saves (o-projection 5.3 -> 5.9 us), so those shapes stay on the resident-tile kernel
+            const bool tile1 = p.z == ntiles && nw <= 4 && !(in.nrows & 3) && !(in.out_stride & 3) && !(in.out_addr & 15);
+            p.form = tile1 ? LIN_GEMM_Q8_TILE1 : LIN_GEMM_Q8_MFMA;
+            return p;
+        }
+        if (in.ntok > 8 && !in.lpr_hint) { p.form = LIN_GEMM_Q8_TOK; return p; }
+        p.form = LIN_GEMV_Q8; p.mt = mt_of(in.ntok);
+        p.lpr = in.lpr_hint ? in.lpr_hint : gemv_lpr((long)(in.nrows / 32) * nsseg, (long)(in.nrows / 16) * nsseg); // enough workgroups to cover 256 CUs twice
+        return p;
     }
-    if (w.rg_type) { // mixed K-quant matrix: one kernel handles every type; tokens beyond 8 go to z tiles
-        int lpr = lpr_hint;
-        if (!lpr) lpr = ((long)(nrows / 32) * nsseg >= 512) ? 2 : ((long)(nrows / 16) * nsseg >= 256) ? 4 : 8;
-        // Q6_K rows with 8 lanes per row: measured 14.6-62 us per launch for the predictor's 1024 x 3072 down-projection (2.1 MB; the Q5_K
-        // layers of the same shape take 4.7 us) with the same instruction and fetch counts but 4 x the SQ busy cycles
-        // (gpurun_out/pmc_kq.txt, round 2); 4 lanes per row does not show it, so Q6_K matrices stop at 4.  Q3_KQ_Q6_LPR8=1 restores 8 for A/B.
-        static const bool q6_lpr8 = [] { const char* e = std::getenv("Q3_KQ_Q6_LPR8"); return e && e[0] == '1'; }();
-        if (lpr == 8 && !lpr_hint && !q6_lpr8 && wslice_ts(w) != Q3_T_Q5_K && wslice_ts(w) != Q3_T_Q8_0) lpr = 4;
-        if (lpr == 2) gemv_kq_mt<2>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-        else if (lpr == 4) gemv_kq_mt<4>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-        else gemv_kq_mt<8>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-        return;
+    case LOP_GATEUP: { // batched steps (ntok >= 16, K = 1024 or 2048): gate/up GEMM with the SwiGLU + quant epilogue; else GEMV + k_swiglu_quant
+        p.form = LIN_GU_UNFUSED;
+        if (!in.fused || in.ntok < 16 || (in.K != 1024 && in.K != 2048) || (in.ff & 31)) return p;
+        if (in.kq && (!kq_mfma() || in.kq_parts != 1)) return p;
+        int z = mfma_ztiles(in.ff / 32, 1, in.ntok);
+        if (z < (ntiles + 3) / 4) z = (ntiles + 3) / 4; // a workgroup parks at most 4 tiles of gate sums
+        p.z = z;
+        p.form = in.kq ? LIN_GU_KQ_MFMA : (z == ntiles && !(in.aq_addr & 3)) ? LIN_GU_Q8_TILE1 : LIN_GU_Q8_MFMA;
+        return p;
     }
-    if (ntok >= 16 && !lpr_hint) { // matrix-core path: exact int8 block dots for 32 tokens x 32 rows per MFMA
-        const int nseg = w.K >> 8, nw = nseg < 8 ? nseg : 8;
-        const int rgs = (nrows + 31) / 32;
-        const int z = mfma_ztiles(rgs, nsseg, ntok);
-        // one token tile per workgroup and K <= 1024 (4 waves): the latency-tuned form.  Measured in-graph at 64 tokens (profiles/r03_gemm_stamps.txt): predictor
-        // q,k,v 4.67 -> 4.46 us, head 4.50 -> 4.35; with 8 waves per workgroup (K >= 2048) its extra matrix instruction per block costs more than the
-        // combine saves (o-projection 5.3 -> 5.9 us), so those shapes stay on the resident-tile kernel
-        if (z == (ntok + 31) / 32 && nw <= 4 && !(nrows & 3) && !(out_stride & 3) && !((uintptr_t)out & 15))
-            hipLaunchKernelGGL((k_gemm_q8_tile1<false>), dim3(rgs, nsseg, z), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr);
-        else
-            hipLaunchKernelGGL((k_gemm_q8_mfma<false>), dim3(rgs, nsseg, z), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr);
-        return;
+    case LOP_NORM: p.form = in.ntok > 8 ? LIN_NORM_WG : LIN_NORM; return p; // batched steps: workgroup-per-token norm (same arithmetic, one global round trip)
+    case LOP_NORM_GEMV:
+        p.form = LIN_GEMV_NORM; p.mt = mt_of(in.ntok);
+        p.lpr = in.nrows / 32 >= 512 ? 2 : in.nrows / 16 >= 256 ? 4 : 8;
+        return p;
+    case LOP_NORM_ARGMAX: p.form = LIN_GEMV_NORM_ARGMAX; p.lpr = 2; p.mt = mt_of(in.ntok); return p;
+    case LOP_NORM_GATEUP: p.form = LIN_GU_SWIGLU_NORM; p.mt = in.ntok == 1 ? 1 : in.ntok == 2 ? 2 : 4; return p;
+    case LOP_F_GEMV: {
+        // measured on MI355X (bf16, AR step ms): 2 sequences 5.58 vs 6.15 (GEMV), 8 sequences 6.02 vs 11.87 -- the matrix-core form wins
+        // from two tokens up even though a 16-token tile is then mostly padding (the step is latency-, not throughput-bound)
+        static const int min_tok = [] { const char* e = std::getenv("Q3_FLOAT_MFMA_MIN"); return e ? atoi(e) : 2; }();
+        static const int wide_tok = [] { const char* e = std::getenv("Q3_FLOAT_MFMA_WIDE"); return e ? atoi(e) : 96; }();
+        if (!in.has_wt || min_tok <= 0 || in.ntok < min_tok || in.row0 % 64 != 0 || (in.K & 255) != 0 || (in.x_stride & 3) != 0 || (in.x_addr & 15) != 0) {
+            p.form = LIN_F_GEMV; p.mt = mt_of(in.ntok);
+            return p;
+        }
+        p.form = in.ntok < wide_tok ? LIN_F_MFMA16 : LIN_F_MFMA; // few tokens: 16 x 16 tiles, 16x more workgroups
+        return p;
     }
-    if (ntok > 8 && !lpr_hint) {
-        const int nseg = w.K >> 8, nw = nseg < 8 ? nseg : 8;
+    case LOP_F_GATEUP: { // fused gate/up + SwiGLU for batched steps; else the matmul and k_swiglu_f32
+        static const int max_tok = [] { const char* e = std::getenv("Q3_FLOAT_GU_FUSED_MAX"); return e ? atoi(e) : 95; }();
+        const bool ok = in.has_wt && in.ntok >= 2 && in.ntok <= max_tok && in.nrows == 2 * in.ff && (in.ff & 15) == 0 && (in.K & 255) == 0 &&
+                        (in.x_stride & 3) == 0 && (in.x_addr & 15) == 0;
+        p.form = ok ? LIN_F_GU_MFMA16 : LIN_F_GU_UNFUSED;
+        return p;
+    }
+    default: throw Error("plan_linear: unknown op");
+    }
+}
+
+void run_gemv_q8(hipStream_t st, const LinearPlan& p, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd, float* out,
+                 int out_stride, int ntok) {
+    const int nseg = w.K >> 8, nsseg = (nseg + 7) / 8, nw = nseg < 8 ? nseg : 8, rgs = (nrows + 31) / 32;
+    switch (p.form) {
+    case LIN_GEMM_KQ_MFMA:
+        Q3_TS_SWITCH(w, hipLaunchKernelGGL((k_gemm_kq_mfma<false, TS>), dim3(rgs, nsseg, p.z), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr));
+        return;
+    case LIN_GEMV_KQ:
+        if (p.lpr == 2) gemv_kq_mt<2>(st, p.mt, w, row0, nrows, xq, xd, out, out_stride, ntok);
+        else if (p.lpr == 4) gemv_kq_mt<4>(st, p.mt, w, row0, nrows, xq, xd, out, out_stride, ntok);
+        else gemv_kq_mt<8>(st, p.mt, w, row0, nrows, xq, xd, out, out_stride, ntok);
+        return;
+    case LIN_GEMM_Q8_TILE1:
+        hipLaunchKernelGGL((k_gemm_q8_tile1<false>), dim3(rgs, nsseg, p.z), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr);
+        return;
+    case LIN_GEMM_Q8_MFMA:
+        hipLaunchKernelGGL((k_gemm_q8_mfma<false>), dim3(rgs, nsseg, p.z), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr);
+        return;
+    case LIN_GEMM_Q8_TOK: {
         const size_t lds = 16 * 2048 + 16 * 128 + 8 * 16 * 64 * 4; // 66 KiB: activations of 16 tokens + segment sums
         init_kernel_attributes(); // (normally done at engine construction; a no-op then)
         hipLaunchKernelGGL(k_gemm_q8_tok, dim3((nrows + 63) / 64, nsseg, (ntok + 15) / 16), dim3(64 * nw), lds, st, w, row0, nrows, xq, xd, out,
                            out_stride, ntok);
         return;
     }
-    int lpr = lpr_hint;
-    if (!lpr) { // enough workgroups to cover 256 CUs twice, else narrower row groups
-        if ((long)(nrows / 32) * nsseg >= 512) lpr = 2;
-        else if ((long)(nrows / 16) * nsseg >= 256) lpr = 4;
-        else lpr = 8;
+    case LIN_GEMV_Q8:
+        if (p.lpr == 2) gemv_launch_mt<2>(st, p.mt, w, row0, nrows, xq, xd, out, out_stride, ntok);
+        else if (p.lpr == 4) gemv_launch_mt<4>(st, p.mt, w, row0, nrows, xq, xd, out, out_stride, ntok);
+        else gemv_launch_mt<8>(st, p.mt, w, row0, nrows, xq, xd, out, out_stride, ntok);
+        return;
+    default: throw Error("run_gemv_q8: not an int8 GEMV form");
     }
-    if (lpr == 2) gemv_launch_mt<2>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-    else if (lpr == 4) gemv_launch_mt<4>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-    else gemv_launch_mt<8>(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
+}
+void launch_gemv_q8(hipStream_t st, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd,
+                    float* out, int out_stride, int ntok, int lpr_hint) {
+    LinearPlanIn in = linear_plan_in(LOP_GEMV, w, row0, nrows, ntok);
+    in.out_stride = out_stride; in.out_addr = (uintptr_t)out; in.lpr_hint = lpr_hint;
+    run_gemv_q8(st, plan_linear(in), w, row0, nrows, xq, xd, out, out_stride, ntok);
 }
 
-// gate/up GEMM + SwiGLU + int8 quantisation for batched steps (ntok >= 16, pure Q8_0, K = 1024 or 2048)
+void run_gateup_q8(hipStream_t st, const LinearPlan& p, const Q8Mat& wgu, int ff, const int8_t* xq, const uint16_t* xd, int8_t* aq, uint16_t* ad,
+                   int ntok) {
+    const int rgs = ff / 32;
+    if (p.form == LIN_GU_KQ_MFMA) // K-quant gate / up rows (one type for both, see Transformer): the matrix-core form with the SwiGLU + quant epilogue
+        Q3_TS_SWITCH(wgu, hipLaunchKernelGGL((k_gemm_kq_mfma<true, TS>), dim3(rgs, 1, p.z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad));
+    else if (p.form == LIN_GU_Q8_TILE1) hipLaunchKernelGGL((k_gemm_q8_tile1<true>), dim3(rgs, 1, p.z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
+    else if (p.form == LIN_GU_Q8_MFMA) hipLaunchKernelGGL((k_gemm_q8_mfma<true>), dim3(rgs, 1, p.z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
+    else throw Error("run_gateup_q8: not a fused gate/up form");
+}
+// gate/up GEMM + SwiGLU + int8 quantisation for batched steps (ntok >= 16, K = 1024 or 2048); false = the plan says GEMV + k_swiglu_quant
 bool launch_gateup_mfma(hipStream_t st, const Q8Mat& wgu, int ff, const int8_t* xq, const uint16_t* xd, int8_t* aq, uint16_t* ad, int ntok) {
-    if (ntok < 16 || (wgu.K != 1024 && wgu.K != 2048) || (ff & 31)) return false;
-    const int rgs = ff / 32, ntiles = (ntok + 31) / 32;
-    if (wgu.rg_type) { // K-quant gate / up rows (one type for both, see Transformer): the matrix-core form with the SwiGLU + quant epilogue
-        if (!kq_mfma() || wgu.nparts != 1) return false;
-        int z = mfma_ztiles(rgs, 1, ntok);
-        if (z < (ntiles + 3) / 4) z = (ntiles + 3) / 4; // a workgroup parks at most 4 tiles of gate sums
-        Q3_TS_SWITCH(wgu, hipLaunchKernelGGL((k_gemm_kq_mfma<true, TS>), dim3(rgs, 1, z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad));
-        return true;
-    }
-    int z = mfma_ztiles(rgs, 1, ntok);
-    if (z < (ntiles + 3) / 4) z = (ntiles + 3) / 4; // a workgroup parks at most 4 tiles of gate sums
-    if (z == ntiles && !((uintptr_t)aq & 3)) hipLaunchKernelGGL((k_gemm_q8_tile1<true>), dim3(rgs, 1, z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
-    else hipLaunchKernelGGL((k_gemm_q8_mfma<true>), dim3(rgs, 1, z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
+    LinearPlanIn in = linear_plan_in(LOP_GATEUP, wgu, 0, 2 * ff, ntok);
+    in.ff = ff; in.aq_addr = (uintptr_t)aq;
+    const LinearPlan p = plan_linear(in);
+    if (p.form == LIN_GU_UNFUSED) return false;
+    run_gateup_q8(st, p, wgu, ff, xq, xd, aq, ad, ntok);
     return true;
 }
 
@@ -1285,8 +1359,7 @@ __global__ void __launch_bounds__(256) k_gemv_float(const void* __restrict__ w, 
     }
 }
 template <int TYPE>
-static void gemv_float_mt(hipStream_t st, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out, int out_stride, int ntok) {
-    const int mt = ntok == 1 ? 1 : ntok == 2 ? 2 : ntok <= 4 ? 4 : 8;
+static void gemv_float_mt(hipStream_t st, int mt, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out, int out_stride, int ntok) {
     // rows per wave (RW) > 1 shares activation loads between rows; measured at 32 sequences, bf16: RW 1 -> 68.8, 2 -> 68.3, 4 -> 60.2 audio-s/s,
     // so every token count uses one row per wave (the in-order block sums, not the loads, bound this kernel)
     dim3 grid((nrows + 3) / 4, (ntok + mt - 1) / mt);
@@ -1607,40 +1680,50 @@ void launch_tile_float(hipStream_t st, const void* w, void* wt, int type, int N,
     else hipLaunchKernelGGL((k_tile_rows<2>), dim3(grid), dim3(256), 0, st, (const char*)w, (char*)wt, N, K);
 }
 template <int TYPE>
-static bool gemm_float_mfma(hipStream_t st, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out, int out_stride, int ntok) {
-    // measured on MI355X (bf16, AR step ms): 2 sequences 5.58 vs 6.15 (GEMV), 8 sequences 6.02 vs 11.87 -- the matrix-core form wins
-    // from two tokens up even though a 16-token tile is then mostly padding (the step is latency-, not throughput-bound)
-    static const int min_tok = [] { const char* e = std::getenv("Q3_FLOAT_MFMA_MIN"); return e ? atoi(e) : 2; }();
-    if (!w.wt || min_tok <= 0 || ntok < min_tok || row0 % 64 != 0 || (w.K & 255) != 0 || (x_stride & 3) != 0 || ((uintptr_t)x & 15) != 0) return false;
-    constexpr size_t lds = (size_t)Q3_SSEG_SEGS * 64 * FM_PAD * sizeof(float);
-    init_kernel_attributes(); // (normally done at engine construction; a no-op then)
-    static const int wide_tok = [] { const char* e = std::getenv("Q3_FLOAT_MFMA_WIDE"); return e ? atoi(e) : 96; }();
-    if (ntok < wide_tok) { // few tokens: 16 x 16 tiles, 16x more workgroups
+static void run_gemv_float_t(hipStream_t st, const LinearPlan& p, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out,
+                             int out_stride, int ntok) {
+    if (p.form == LIN_F_GEMV) { gemv_float_mt<TYPE>(st, p.mt, w, row0, nrows, x, x_stride, out, out_stride, ntok); return; }
+    if (p.form == LIN_F_MFMA16) {
         dim3 grid16(xcd_grid((nrows + 15) / 16, (ntok + 15) / 16));
         hipLaunchKernelGGL((k_gemm_float_mfma16<TYPE>), grid16, dim3(512), 0, st, w.wt, w.K, row0 / 64, nrows, x, x_stride, out, out_stride, ntok);
-        return true;
+        return;
     }
+    if (p.form != LIN_F_MFMA) throw Error("run_gemv_float: not a float GEMV form");
+    constexpr size_t lds = (size_t)Q3_SSEG_SEGS * 64 * FM_PAD * sizeof(float);
+    init_kernel_attributes(); // (normally done at engine construction; a no-op then)
     dim3 grid(xcd_grid((nrows + 63) / 64, (ntok + FM_TOK - 1) / FM_TOK));
     hipLaunchKernelGGL((k_gemm_float_mfma<TYPE>), grid, dim3(512), lds, st, w.wt, w.K, row0 / 64, nrows, x, x_stride, out, out_stride, ntok);
-    return true;
 }
-// fused gate/up + SwiGLU for batched steps; false = not applicable (caller runs the matmul and k_swiglu_f32)
-bool launch_gateup_float(hipStream_t st, const FMat& wgu, int ff, const float* x, int x_stride, float* act, int ntok) {
-    static const int max_tok = [] { const char* e = std::getenv("Q3_FLOAT_GU_FUSED_MAX"); return e ? atoi(e) : 95; }();
-    if (!wgu.wt || ntok < 2 || ntok > max_tok || wgu.N != 2 * ff || (ff & 15) != 0 || (wgu.K & 255) != 0 || (x_stride & 3) != 0 || ((uintptr_t)x & 15) != 0) return false;
+void run_gemv_float(hipStream_t st, const LinearPlan& p, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out,
+                    int out_stride, int ntok) {
+    if (w.type == Q3_T_F32) run_gemv_float_t<Q3_T_F32>(st, p, w, row0, nrows, x, x_stride, out, out_stride, ntok);
+    else if (w.type == Q3_T_F16) run_gemv_float_t<Q3_T_F16>(st, p, w, row0, nrows, x, x_stride, out, out_stride, ntok);
+    else run_gemv_float_t<Q3_T_BF16>(st, p, w, row0, nrows, x, x_stride, out, out_stride, ntok);
+}
+static LinearPlanIn float_plan_in(int op, const FMat& w, int row0, int nrows, const float* x, int x_stride, int ntok) {
+    LinearPlanIn in;
+    in.op = op; in.K = w.K; in.row0 = row0; in.nrows = nrows; in.ntok = ntok; in.wts = w.type; in.has_wt = w.wt != nullptr;
+    in.x_stride = x_stride; in.x_addr = (uintptr_t)x;
+    return in;
+}
+void run_gateup_float(hipStream_t st, const LinearPlan& p, const FMat& wgu, int ff, const float* x, int x_stride, float* act, int ntok) {
+    if (p.form != LIN_F_GU_MFMA16) throw Error("run_gateup_float: not the fused float gate/up form");
     dim3 grid(xcd_grid(ff / 16, (ntok + 15) / 16));
     if (wgu.type == Q3_T_F32) hipLaunchKernelGGL((k_gateup_float_mfma16<Q3_T_F32>), grid, dim3(512), 0, st, wgu.wt, wgu.K, ff, x, x_stride, act, ntok);
     else if (wgu.type == Q3_T_F16) hipLaunchKernelGGL((k_gateup_float_mfma16<Q3_T_F16>), grid, dim3(512), 0, st, wgu.wt, wgu.K, ff, x, x_stride, act, ntok);
     else hipLaunchKernelGGL((k_gateup_float_mfma16<Q3_T_BF16>), grid, dim3(512), 0, st, wgu.wt, wgu.K, ff, x, x_stride, act, ntok);
+}
+// fused gate/up + SwiGLU for batched steps; false = not applicable (caller runs the matmul and k_swiglu_f32)
+bool launch_gateup_float(hipStream_t st, const FMat& wgu, int ff, const float* x, int x_stride, float* act, int ntok) {
+    LinearPlanIn in = float_plan_in(LOP_F_GATEUP, wgu, 0, wgu.N, x, x_stride, ntok);
+    in.ff = ff;
+    const LinearPlan p = plan_linear(in);
+    if (p.form != LIN_F_GU_MFMA16) return false;
+    run_gateup_float(st, p, wgu, ff, x, x_stride, act, ntok);
     return true;
 }
 void launch_gemv_float(hipStream_t st, const FMat& w, int row0, int nrows, const float* x, int x_stride, float* out, int out_stride, int ntok) {
-    if (w.type == Q3_T_F32 ? gemm_float_mfma<Q3_T_F32>(st, w, row0, nrows, x, x_stride, out, out_stride, ntok)
-        : w.type == Q3_T_F16 ? gemm_float_mfma<Q3_T_F16>(st, w, row0, nrows, x, x_stride, out, out_stride, ntok)
-                             : gemm_float_mfma<Q3_T_BF16>(st, w, row0, nrows, x, x_stride, out, out_stride, ntok)) return;
-    if (w.type == Q3_T_F32) gemv_float_mt<Q3_T_F32>(st, w, row0, nrows, x, x_stride, out, out_stride, ntok);
-    else if (w.type == Q3_T_F16) gemv_float_mt<Q3_T_F16>(st, w, row0, nrows, x, x_stride, out, out_stride, ntok);
-    else gemv_float_mt<Q3_T_BF16>(st, w, row0, nrows, x, x_stride, out, out_stride, ntok);
+    run_gemv_float(st, plan_linear(float_plan_in(LOP_F_GEMV, w, row0, nrows, x, x_stride, ntok)), w, row0, nrows, x, x_stride, out, out_stride, ntok);
 }
 __global__ void k_swiglu_f32(const float* __restrict__ gu, int ff, float* __restrict__ out) {
     const int tok = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;

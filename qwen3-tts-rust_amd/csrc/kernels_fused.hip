@@ -235,20 +235,30 @@ static void gemv_norm_launch(hipStream_t st, const Q8Mat& w, int row0, int nrows
     Q3_TS_SWITCH(w, hipLaunchKernelGGL((k_gemv_q8_norm<LPR, MT, EPI, TS>), grid, dim3(64 * nseg), 0, st, w, row0, nrows, a, out, out_stride, ntok, am));
 }
 template <int LPR, int EPI>
-static void gemv_norm_mt(hipStream_t st, const Q8Mat& w, int row0, int nrows, const NormPro& a, float* out, int out_stride, int ntok,
+static void gemv_norm_mt(hipStream_t st, int mt, const Q8Mat& w, int row0, int nrows, const NormPro& a, float* out, int out_stride, int ntok,
                          const ArgmaxEpi& am) {
-    if (ntok == 1) gemv_norm_launch<LPR, 1, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
-    else if (ntok == 2) gemv_norm_launch<LPR, 2, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
-    else if (ntok <= 4) gemv_norm_launch<LPR, 4, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
+    if (mt == 1) gemv_norm_launch<LPR, 1, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
+    else if (mt == 2) gemv_norm_launch<LPR, 2, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
+    else if (mt == 4) gemv_norm_launch<LPR, 4, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
     else gemv_norm_launch<LPR, 8, EPI>(st, w, row0, nrows, a, out, out_stride, ntok, am);
+}
+void run_gemv_q8_norm(hipStream_t st, const LinearPlan& p, const Q8Mat& w, int row0, int nrows, const NormPro& a, float* out, int out_stride,
+                      int ntok, const ArgmaxEpi* am) {
+    ArgmaxEpi none{};
+    if (p.form == LIN_GEMV_NORM_ARGMAX) {
+        if (!am || p.lpr != 2) throw Error("run_gemv_q8_norm: the argmax epilogue needs keys and LPR 2");
+        gemv_norm_mt<2, 1>(st, p.mt, w, row0, nrows, a, out, out_stride, ntok, *am);
+        return;
+    }
+    if (p.form != LIN_GEMV_NORM) throw Error("run_gemv_q8_norm: not a norm GEMV form");
+    if (p.lpr == 2) gemv_norm_mt<2, 0>(st, p.mt, w, row0, nrows, a, out, out_stride, ntok, none);
+    else if (p.lpr == 4) gemv_norm_mt<4, 0>(st, p.mt, w, row0, nrows, a, out, out_stride, ntok, none);
+    else gemv_norm_mt<8, 0>(st, p.mt, w, row0, nrows, a, out, out_stride, ntok, none);
 }
 void launch_gemv_q8_norm(hipStream_t st, const Q8Mat& w, int row0, int nrows, const NormPro& a, float* out, int out_stride, int ntok,
                          const ArgmaxEpi* am) {
-    ArgmaxEpi none{};
-    if (am) { gemv_norm_mt<2, 1>(st, w, row0, nrows, a, out, out_stride, ntok, *am); return; }
-    if (nrows / 32 >= 512) gemv_norm_mt<2, 0>(st, w, row0, nrows, a, out, out_stride, ntok, none);
-    else if (nrows / 16 >= 256) gemv_norm_mt<4, 0>(st, w, row0, nrows, a, out, out_stride, ntok, none);
-    else gemv_norm_mt<8, 0>(st, w, row0, nrows, a, out, out_stride, ntok, none);
+    run_gemv_q8_norm(st, plan_linear(linear_plan_in(am ? LOP_NORM_ARGMAX : LOP_NORM_GEMV, w, row0, nrows, ntok)), w, row0, nrows, a, out,
+                     out_stride, ntok, am);
 }
 
 // ===================================================================================================
@@ -337,9 +347,10 @@ __global__ void __launch_bounds__(64 * NSEG) k_gateup_swiglu(Q8Mat w, int ff, No
         }
     }
 }
-void launch_gateup_swiglu(hipStream_t st, const Q8Mat& w, int ff, const NormPro& a, int8_t* aq, uint16_t* ad, int ntok) {
+void run_gateup_swiglu(hipStream_t st, const LinearPlan& p, const Q8Mat& w, int ff, const NormPro& a, int8_t* aq, uint16_t* ad, int ntok) {
+    if (p.form != LIN_GU_SWIGLU_NORM) throw Error("run_gateup_swiglu: not the fused norm gate/up form");
     const int nseg = w.K >> 8;
-    const int mt = ntok == 1 ? 1 : ntok == 2 ? 2 : 4;
+    const int mt = p.mt;
     dim3 grid(ff / 32, 1, (ntok + mt - 1) / mt);
 #define Q3_GU(MTV, NS) Q3_TS_SWITCH(w, hipLaunchKernelGGL((k_gateup_swiglu<MTV, NS, TS>), grid, dim3(64 * NS), 0, st, w, ff, a, aq, ad, ntok))
 #define Q3_GU_NS(NS) do { if (mt == 1) Q3_GU(1, NS); else if (mt == 2) Q3_GU(2, NS); else Q3_GU(4, NS); } while (0)
@@ -350,6 +361,11 @@ void launch_gateup_swiglu(hipStream_t st, const Q8Mat& w, int ff, const NormPro&
     }
 #undef Q3_GU_NS
 #undef Q3_GU
+}
+void launch_gateup_swiglu(hipStream_t st, const Q8Mat& w, int ff, const NormPro& a, int8_t* aq, uint16_t* ad, int ntok) {
+    LinearPlanIn in = linear_plan_in(LOP_NORM_GATEUP, w, 0, 2 * ff, ntok);
+    in.ff = ff;
+    run_gateup_swiglu(st, plan_linear(in), w, ff, a, aq, ad, ntok);
 }
 
 // ===================================================================================================

@@ -511,7 +511,8 @@ void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMe
         Q3_LAUNCH_CHECK();
         return;
     }
-    const bool wgnorm = ntok > 8; // batched steps: workgroup-per-token norm kernel (same arithmetic, one global round trip)
+    LinearPlanIn npi; npi.op = LOP_NORM; npi.ntok = ntok;
+    const bool wgnorm = plan_linear(npi).form == LIN_NORM_WG; // batched steps: workgroup-per-token norm kernel (same arithmetic, one global round trip)
     auto norm = [&](const NormArgs& a) {
         if (!wgnorm) { launch_rmsnorm_quant(st, a, ntok); return; }
         NormPro p{};
@@ -565,7 +566,8 @@ void Transformer::forward_float(hipStream_t st, const Input& in, int ntok, const
         NormArgs a{};
         a.h_in = h_in; a.h_stride = h_stride; a.idx_keys = idx_keys; a.idx_stride = idx_stride; a.parts = parts; a.nparts = parts ? 1 : 0; a.parts_stride = d;
         a.h_out = h_.p; a.g = g; a.eps = hp_.eps; a.d = d; a.xq = xq_.p; a.xd = xd_.p; a.xn_out = xn; // int8 copy unused in float mode
-        if (ntok <= 8) { launch_rmsnorm_quant(st, a, ntok); return; }
+        LinearPlanIn npi; npi.op = LOP_NORM; npi.ntok = ntok;
+        if (plan_linear(npi).form == LIN_NORM) { launch_rmsnorm_quant(st, a, ntok); return; }
         NormPro p{}; // batched steps: workgroup-per-token norm kernel (same arithmetic)
         p.h_in = a.h_in; p.h_stride = a.h_stride; p.idx_keys = a.idx_keys; p.idx_stride = a.idx_stride; p.parts = a.parts; p.nparts = a.nparts;
         p.parts_stride = a.parts_stride; p.parts_slab = (size_t)ntok * a.parts_stride; p.h_out = a.h_out; p.g = a.g; p.eps = a.eps; p.xn_out = a.xn_out;

@@ -87,6 +87,7 @@ SYMBOLS = [
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
     "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan",
+    "q3tts_op_linear", "q3tts_linear_plan", "q3tts_argmax_key",
 ]
 
 
@@ -1128,3 +1129,77 @@ class Tokenizer:  # utils/tokenizer.rs:4-38
         buf = C.create_string_buffer(n + 1)
         lib().q3tts_tokenizer_decode(self.h, _p(a), a.size, buf, n + 1)
         return buf.raw[:n].decode("utf-8", errors="replace")
+
+
+# ---- one linear-layer operation (q3tts_op_linear / q3tts_linear_plan) ----
+LOP_GEMV, LOP_GATEUP, LOP_NORM, LOP_NORM_GEMV, LOP_NORM_ARGMAX, LOP_NORM_GATEUP, LOP_F_GEMV, LOP_F_GATEUP = range(8)
+LIN_FORMS = ["AUTO", "GEMV_Q8", "GEMM_Q8_TOK", "GEMM_Q8_MFMA", "GEMM_Q8_TILE1", "GEMV_KQ", "GEMM_KQ_MFMA", "GU_Q8_TILE1", "GU_Q8_MFMA", "GU_KQ_MFMA",
+             "GU_UNFUSED", "NORM", "NORM_WG", "GEMV_NORM", "GEMV_NORM_ARGMAX", "GU_SWIGLU_NORM", "F_GEMV", "F_MFMA16", "F_MFMA", "F_GU_MFMA16",
+             "F_GU_UNFUSED"]
+LIN = {n: i for i, n in enumerate(LIN_FORMS)}
+
+
+class LinearDesc(C.Structure):  # q3tts_linear_desc
+    _fields_ = [("op", C.c_int32), ("form", C.c_int32),
+                ("nw", C.c_int32), ("raw", C.c_void_p * 3), ("type", C.c_int32 * 3), ("rows", C.c_int32 * 3), ("kq_layout", C.c_int32),
+                ("K", C.c_int32), ("row0", C.c_int32), ("nrows", C.c_int32), ("nrows_valid", C.c_int32), ("ntok", C.c_int32), ("ff", C.c_int32),
+                ("lpr", C.c_int32), ("mt", C.c_int32), ("ztiles", C.c_int32), ("fused", C.c_int32),
+                ("xq", C.c_void_p), ("xd", C.c_void_p), ("a_rows", C.c_int32),
+                ("x", C.c_void_p), ("x_floats", C.c_int64), ("x_off", C.c_int32), ("x_stride", C.c_int32),
+                ("h_in", C.c_void_p), ("h_floats", C.c_int64), ("h_stride", C.c_int32),
+                ("idx_keys", C.c_void_p), ("idx", C.c_void_p), ("idx_stride", C.c_int32),
+                ("parts", C.c_void_p), ("parts_floats", C.c_int64), ("nparts", C.c_int32), ("parts_stride", C.c_int32), ("parts_slab", C.c_int64),
+                ("g", C.c_void_p), ("eps", C.c_float),
+                ("h_out", C.c_void_p), ("xn_out", C.c_void_p), ("xq_out", C.c_void_p), ("xd_out", C.c_void_p),
+                ("keys", C.c_void_p), ("n_keys", C.c_int64), ("key_stride", C.c_int32), ("mask_per_tok", C.c_void_p), ("idx_add", C.c_int32),
+                ("out", C.c_void_p), ("out_floats", C.c_int64), ("out_off", C.c_int64), ("out_stride", C.c_int32),
+                ("aq", C.c_void_p), ("ad", C.c_void_p),
+                ("form_ran", C.c_int32), ("lpr_ran", C.c_int32), ("mt_ran", C.c_int32), ("z_ran", C.c_int32)]
+
+
+_LIN_SIZES = {"x": "x_floats", "h_in": "h_floats", "parts": "parts_floats", "out": "out_floats", "keys": "n_keys"}
+
+
+def _linear_desc(op, form, weights, fields):
+    """weights: [(raw ndarray, type, rows)]; fields: LinearDesc fields, ndarrays for the buffers (passed by address: outputs are written in place)"""
+    d = LinearDesc()
+    d.op = op; d.form = LIN[form] if isinstance(form, str) else form; d.fused = 1
+    keep = []
+    d.nw = len(weights)
+    for i, (raw, t, rows) in enumerate(weights):
+        raw = np.ascontiguousarray(raw); keep.append(raw)
+        d.raw[i] = raw.ctypes.data if raw.size else None; d.type[i] = t; d.rows[i] = rows
+    for k, v in fields.items():
+        if isinstance(v, np.ndarray):
+            assert v.flags.c_contiguous, k
+            keep.append(v)
+            setattr(d, k, v.ctypes.data)
+            if k in _LIN_SIZES and k + "_n" not in fields:
+                setattr(d, _LIN_SIZES[k], v.size)
+        elif v is not None:
+            setattr(d, k, v)
+    return d, keep
+
+
+def op_linear(op, form="AUTO", weights=(), **fields):
+    """runs one linear-layer op on the device; output ndarrays in fields are overwritten whole.  Returns (form_ran name, lpr, mt, z)"""
+    d, keep = _linear_desc(op, form, list(weights), fields)
+    lib().q3tts_op_linear.argtypes = [C.POINTER(LinearDesc)]
+    _chk(lib().q3tts_op_linear(C.byref(d)))
+    return LIN_FORMS[d.form_ran], d.lpr_ran, d.mt_ran, d.z_ran
+
+
+def linear_plan(op, weights=(), **fields):
+    """host only: the engine's dispatch for the op / shape -> (form name, lpr, mt, z)"""
+    d, keep = _linear_desc(op, 0, list(weights), fields)
+    lib().q3tts_linear_plan.argtypes = [C.POINTER(LinearDesc)]
+    _chk(lib().q3tts_linear_plan(C.byref(d)))
+    return LIN_FORMS[d.form_ran], d.lpr_ran, d.mt_ran, d.z_ran
+
+
+def argmax_key(v, idx):
+    """host only: kdev.h's pack_key(v, idx) as the library computes it"""
+    L = lib()
+    L.q3tts_argmax_key.restype = C.c_uint64
+    L.q3tts_argmax_key.argtypes = [C.c_float, C.c_int32]
+    return int(L.q3tts_argmax_key(v, idx))
