@@ -128,6 +128,17 @@ int q3tts_submit_ex(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, c
  * with n_trail > 0 uploads the text table to the device (~1.24 GB f32 for the real model) */
 int q3tts_submit_trailing(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts /* NULL = defaults */,
                           const int32_t* trail_ids, int32_t n_trail, int64_t* req_id);
+/* [EXT] live text append (q3tts_spec.h): like q3tts_submit_trailing, but the trail stays open: n_trail may be 0; frames past the appended
+ * ids wait (they change nothing the request owns) until q3tts_trail_append brings more.  Appends may come from any thread while the
+ * request is queued, being prefilled or running */
+int q3tts_submit_trailing_open(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                               const int32_t* trail_ids, int32_t n_trail, int64_t* req_id);
+/* appends raw trailing ids (copied); close = 1 closes the trail (n may be 0).
+ * 0: appended; 1: the request no longer takes text (finished by EOS / max_steps, done or failed) -- nothing appended;
+ * < 0: unknown id, request not open, already closed, n < 0, ids NULL with n > 0, or the total would exceed max_prompt (nothing appended) */
+int q3tts_trail_append(q3tts_engine* e, int64_t req_id, const int32_t* ids, int32_t n, int32_t close);
+/* appended ids, ids consumed by the feedback so far (min(n_frames, appended)), closed flag (1 for a request not submitted open) */
+int q3tts_trail_progress(q3tts_engine* e, int64_t req_id, int32_t* n_appended, int32_t* n_consumed, int32_t* closed);
 int q3tts_poll(q3tts_engine* e, int64_t req_id, q3tts_req_status* out);
 /* streaming read: frames [frame_off, frame_off+max_frames) and PCM [pcm_off, pcm_off+pcm_cap) available right now */
 int q3tts_fetch(q3tts_engine* e, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out,
@@ -152,6 +163,13 @@ int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_
 int q3tts_submit_text_streaming(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                                 const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                                 int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
+/* [EXT] text level: the streaming layout from the text known so far (n_text >= 1, only t_0 enters the prompt; t_1 .. become the open
+ * trail).  open(t[:k]) + q3tts_text_append(t[k:], is_last = 1) gives what q3tts_submit_text_streaming(t) gives */
+int q3tts_submit_text_streaming_open(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                     const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                                     int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
+/* appends text ids; is_last = 1 also appends Q3_TEXT_EOS and closes.  Return codes as q3tts_trail_append */
+int q3tts_text_append(q3tts_engine* e, int64_t req_id, const int32_t* text_ids, int32_t n, int32_t is_last);
 
 /* ---- multi-GPU: request sharding, weights replicated per device, no collective on the data path ----
  * q3tts_group_*: ONE process, N devices.  One engine (+ scheduler thread + decoder thread) per entry of device_ids; requests go round-robin
@@ -187,6 +205,14 @@ int q3tts_group_submit_text_ex(q3tts_group* g, int32_t voice_id, const int32_t* 
 int q3tts_group_submit_text_streaming(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                                       const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                                       int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id);
+/* [EXT] live text append through a group: append / progress are routed by the engine index the group request id carries */
+int q3tts_group_submit_text_streaming_open(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                           const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler,
+                                           int32_t max_steps, int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts,
+                                           int64_t* req_id);
+int q3tts_group_text_append(q3tts_group* g, int64_t req_id, const int32_t* text_ids, int32_t n, int32_t is_last);
+int q3tts_group_trail_append(q3tts_group* g, int64_t req_id, const int32_t* ids, int32_t n, int32_t close);
+int q3tts_group_trail_progress(q3tts_group* g, int64_t req_id, int32_t* n_appended, int32_t* n_consumed, int32_t* closed);
 int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id); /* HIP device a request was sharded to */
 int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out);
 int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out,

@@ -279,6 +279,21 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  *   (the synthetic models have 4096 text rows: Q3_TEXT_EOS takes the fallback there).  tts_pad = the reference's marker row 151671.
  * With n_trail = 0 the feedback is the reference's; a raw prompt with trailing ids may be submitted with any n_trail in [0, max_prompt]. */
 
+/* ---------------- live text append [EXT] (q3tts_submit_trailing_open, q3tts_trail_append, q3tts_text_append) ----------------
+ * A streaming-text request may be submitted with an OPEN trail.  Let n_avail = the number of trailing ids appended so far.
+ *   while the trail is open:  frame f runs only when f < n_avail; otherwise the slot WAITS: that frame has no effect on anything the slot
+ *                             owns (codes, history, positions, finished flag, the talker hidden row, the talker and predictor RNG draw
+ *                             counters; the talker KV row at the frame's position is rewritten by the frame that runs there later)
+ *   once it is closed:        frames behave as in the streaming-text definition above: trail[f] while f < n_trail, then tts_pad
+ * Device predicate, slot b, read at the start and at the end of every gated frame (nothing inside a frame changes its inputs):
+ *   waits = !finished[b] && n_frames[b] < max_frames[b] && open[b] && n_frames[b] >= n_trail[b]
+ * Consequence: an open request that ends with the id list T, appended in any pieces, at any moments, with any number of waited frames,
+ * gives the codes and PCM of the same request submitted closed with T (q3tts_submit_trailing).  Waiting never consumes an RNG draw, writes
+ * history or advances a position, and the other slots of the batch step as they would without it.
+ * Text level: q3tts_submit_text_streaming_open(t[:k]) opens the trail t_1 .. t_{k-1} (the prompt depends on t_0 only);
+ * q3tts_text_append(t[k:], is_last = 1) appends t_k .. t_{n-1}, Q3_TEXT_EOS and closes: together the trail of q3tts_submit_text_streaming(t).
+ * The total number of trailing ids stays within max_prompt. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -113,6 +113,41 @@ int q3tts_submit_trailing(q3tts_engine* e, const q3tts_request* r, int32_t want_
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+int q3tts_submit_trailing_open(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                               const int32_t* trail_ids, int32_t n_trail, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && r && req_id, "null argument");
+    GenRequest g = to_gen(*r);
+    g.opts = to_opts(opts);
+    g.trail = trail_ids; g.n_trail = n_trail; g.open = true;
+    *req_id = e->e->submit(g, want_pcm != 0, true);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_trail_append(q3tts_engine* e, int64_t req_id, const int32_t* ids, int32_t n, int32_t close) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    return e->e->append_trail(req_id, ids, n, close != 0);
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_trail_progress(q3tts_engine* e, int64_t req_id, int32_t* n_appended, int32_t* n_consumed, int32_t* closed) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && n_appended && n_consumed && closed, "null argument");
+    int na = 0, nc = 0; bool cl = false;
+    e->e->trail_progress(req_id, &na, &nc, &cl);
+    *n_appended = na; *n_consumed = nc; *closed = cl ? 1 : 0;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_text_append(q3tts_engine* e, int64_t req_id, const int32_t* text_ids, int32_t n, int32_t is_last) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    Q3_CHECK(n >= 0 && (n == 0 || text_ids), "bad arguments");
+    std::vector<int32_t> ids(text_ids, text_ids + n);
+    if (is_last) ids.push_back(Q3_TEXT_EOS); // the streaming layout's trail ends with TEXT_EOS (q3tts_spec.h)
+    return e->e->append_trail(req_id, ids.data(), (int)ids.size(), is_last != 0);
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_poll(q3tts_engine* e, int64_t id, q3tts_req_status* o) {
     Q3_API_BEGIN
     Q3_CHECK(e && o, "null argument");
@@ -170,7 +205,7 @@ int q3tts_submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids
 }
 static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                        int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
-                       const q3tts_gen_options* opts, bool streaming, int64_t* req_id);
+                       const q3tts_gen_options* opts, bool streaming, int64_t* req_id, bool open = false);
 int q3tts_submit_text_ex(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                          int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
                          const q3tts_gen_options* opts, int64_t* req_id) {
@@ -181,9 +216,15 @@ int q3tts_submit_text_streaming(q3tts_engine* e, int32_t voice_id, const int32_t
                                 int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
     return submit_text(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, true, req_id);
 }
+int q3tts_submit_text_streaming_open(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                     const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
+                                     int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
+    return submit_text(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, true, req_id,
+                       true);
+}
 static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                        int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
-                       const q3tts_gen_options* opts, bool streaming, int64_t* req_id) {
+                       const q3tts_gen_options* opts, bool streaming, int64_t* req_id, bool open) {
     Q3_API_BEGIN
     Q3_CHECK(e && text_ids && n_text >= 0 && req_id, "bad arguments");
     Q3_CHECK(!streaming || n_text >= 1, "the streaming-text layout needs n_text >= 1");
@@ -204,7 +245,8 @@ static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_id
         g.sampler.has_seed = sampler->has_seed != 0; g.sampler.seed = sampler->seed;
     }
     g.opts = to_opts(opts);
-    g.trail = trail.data(); g.n_trail = (int)trail.size();
+    if (open) trail.pop_back(); // the TEXT_EOS that ends the trail comes with q3tts_text_append(is_last = 1)
+    g.trail = trail.data(); g.n_trail = (int)trail.size(); g.open = open;
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)

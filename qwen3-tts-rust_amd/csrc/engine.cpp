@@ -125,6 +125,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     h_maxf_.assign(B, 0); h_fin_.assign(B, 1); h_nfr_.assign(B, 0); h_mask_.assign(B, -1); h_nprompt_.assign(B, 0); h_topk_.assign(B, 0);
     h_temp_.assign(B, 0.0f); h_topp_.assign(B, 1.0f);
     h_pen_.assign(B, 1.0f); h_ptemp_.assign(B, 0.0f); h_ptopp_.assign(B, 1.0f); h_ptopk_.assign(B, 0); h_ntrail_.assign(B, 0);
+    h_open_.assign(B, 0); h_pend_.assign(B, std::vector<int32_t>()); h_pend_off_.assign(B, 0);
     d_pen_.upload(h_pen_.data(), B); d_ptopp_.upload(h_ptopp_.data(), B);
     slot_req_.assign(B, nullptr); slot_live_.assign(B, 0);
     if (async_pf_) { d_pf_logits_.alloc((size_t)B * tl_stride_); d_pf_hidden_.alloc((size_t)B * Q3_EMBD); }
@@ -181,6 +182,7 @@ void* Engine::d2h_begin(const void* src, size_t bytes) {
 struct Engine::Req {
     int64_t id = 0;
     GenRequest r; std::vector<float> prompt_own; std::vector<int32_t> trail_own; bool want_pcm = false;
+    bool closed = false;  // [EXT] open trail (r.open): closed by append_trail; trail_own and closed change under mu_ only
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
@@ -232,9 +234,18 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
 // [0, n_frames) in d_hist_ + the current frame's key, which k_advance_keys appends only after the head); pred: every predictor head writes
 // its 2048 logits and k_sample_pred draws the code (greedy slots take its first-max branch).  Neither set: today's launch sequence.
 // trail: the feedback kernel's streaming-text variant (same launch, reads d_nframes_ / d_ntrail_ / d_trail_ and the text table).
-void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail) {
+// gate: [EXT] live text append -- k_stall_save before everything and the gated k_advance_keys in place of the plain one; a slot that
+// waits runs through every launch in between and its work is discarded (q3tts_spec.h "live text append").  Clear: today's launches.
+void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail, bool gate) {
     const int B = fg.width;
     const KvCache kvt = kv_t_->view(), kvp = kv_p_->view();
+    AdvanceKeysArgs a{B, d_finished_.p, d_nframes_.p, d_maxframes_.p, d_keys_.p, d_next_key0_.p, d_hist_.p, hist_stride_, d_tslot_.p, d_tpos_.p};
+    StallArgs sg;
+    if (gate) {
+        sg.open = d_open_.p; sg.n_trail = d_ntrail_.p; sg.hidden = d_thidden_.p; sg.draws = d_draws_.p; sg.pdraws = d_pdraws_.p;
+        sg.save_hidden = d_stall_hidden_.p; sg.save_draws = d_stall_draws_.p;
+        launch_stall_save(st_, a, sg);
+    }
     // :565-573 predictor input = [project(m_hidden) ; project(E_0[code_0])]
     launch_project_blk(st_, d_thidden_.p, Q3_EMBD, d_proj_wblk_.p, d_proj_b_.p, Q3_EMBD, dP_, d_pin_.p, dP_, B);
     launch_gather_rows_keys(st_, d_proj_tab_[0].p, assets_->codec_rows[0], d_keys_.p, 16, dP_, d_pin_.p + (size_t)B * dP_, B);
@@ -291,15 +302,15 @@ void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, boo
             talker_->head(st_, 0, B, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, d_thidden_.p);
         }
     }
-    AdvanceKeysArgs a{B, d_finished_.p, d_nframes_.p, d_maxframes_.p, d_keys_.p, d_next_key0_.p, d_hist_.p, hist_stride_, d_tslot_.p, d_tpos_.p};
-    launch_advance_keys(st_, a);
+    if (gate) launch_advance_keys_gated(st_, a, sg);
+    else launch_advance_keys(st_, a);
     Q3_LAUNCH_CHECK();
 }
 
 std::mutex& capture_mutex() { static std::mutex mu; return mu; }
 
-Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool capture) {
-    std::unique_ptr<FrameGraph>& slot = graphs_[width * 16 + (trail ? 8 : 0) + (pred ? 4 : 0) + (pen ? 2 : 0) + (sampled ? 1 : 0)];
+Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool gate, bool capture) {
+    std::unique_ptr<FrameGraph>& slot = graphs_[width * 32 + (gate ? 16 : 0) + (trail ? 8 : 0) + (pred ? 4 : 0) + (pen ? 2 : 0) + (sampled ? 1 : 0)];
     // one graph construction at a time per process: engines of a multi-device group (or several engines on one device) build their frame
     // graphs from different threads; the synchronous allocations / uploads below and concurrent thread-local captures were seen to
     // invalidate another thread's capture on ROCm 7.2 ("operation failed due to a previous error during capture")
@@ -323,7 +334,7 @@ Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool 
     if (capture && !fg.exec) {
         (void)hipGetLastError();
         Q3_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
-        try { record_frame(fg, sampled, pen, pred, trail); }
+        try { record_frame(fg, sampled, pen, pred, trail, gate); }
         catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(st_, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
         Q3_HIP(hipStreamEndCapture(st_, &fg.graph));
         Q3_HIP(hipGraphInstantiate(&fg.exec, fg.graph, nullptr, nullptr, 0));
@@ -345,7 +356,9 @@ void Engine::upload_slot_state() {
         h2d(d_pen_.p, h_pen_.data(), (size_t)W * 4); h2d(d_ptemp_.p, h_ptemp_.data(), (size_t)W * 4);
         h2d(d_ptopk_.p, h_ptopk_.data(), (size_t)W * 4); h2d(d_ptopp_.p, h_ptopp_.data(), (size_t)W * 4);
     }
-    if (trail_used_) h2d(d_ntrail_.p, h_ntrail_.data(), (size_t)W * 4); // a reused slot never keeps its predecessor's count
+    if (trail_used_) { // a reused slot never keeps its predecessor's count or open flag
+        h2d(d_ntrail_.p, h_ntrail_.data(), (size_t)W * 4); h2d(d_open_.p, h_open_.data(), (size_t)W * 4);
+    }
     slot_dirty_ = false;
 }
 
@@ -488,6 +501,7 @@ void Engine::harvest(bool block) {
             c = comp_.front();
             if (!block && hipEventQuery(c.ev) != hipSuccess) return; // completions of a lane finish in order; keep it simple: FIFO
             comp_.pop_front();
+            dec_pending_--;
         }
         Q3_HIP(hipEventSynchronize(c.ev));
         Req* r = c.r;
@@ -521,7 +535,7 @@ void Engine::check_options(const GenRequest& g) const {
              "repetition_penalty / predictor sampling are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
     Q3_CHECK(g.n_trail >= 0 && g.n_trail <= p_.max_prompt, "n_trail must be in [0, max_prompt]");
     Q3_CHECK(g.n_trail == 0 || g.trail, "trailing ids missing");
-    Q3_CHECK(!(talker_->ggml_mode() && g.n_trail > 0),
+    Q3_CHECK(!(talker_->ggml_mode() && (g.n_trail > 0 || g.open)),
              "trailing text ids are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
 }
 
@@ -541,6 +555,8 @@ void Engine::ensure_text_stream() {
         if (text_rows_ > 0) d_text_.upload(a.text_table, (size_t)text_rows_ * Q3_EMBD);
         d_trail_.alloc((size_t)B_ * p_.max_prompt); d_trail_.zero();
         d_ntrail_.alloc(B_); d_ntrail_.zero();
+        d_open_.alloc(B_); d_open_.zero();
+        d_stall_hidden_.alloc((size_t)B_ * Q3_EMBD); d_stall_draws_.alloc((size_t)2 * B_);
         Q3_HIP(hipStreamSynchronize(nullptr)); // the memsets ran on the null stream; the engine's streams do not wait for it
     } catch (...) { (void)hipSetDevice(prev); throw; }
     Q3_HIP(hipSetDevice(prev));
@@ -551,10 +567,11 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
     Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
     Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
     check_options(g);
-    if (g.n_trail > 0) ensure_text_stream();
+    if (g.n_trail > 0 || g.open) ensure_text_stream();
     std::unique_ptr<Req> r(new Req());
     r->r = g;
     if (copy_prompt) { r->prompt_own.assign(g.prompt, g.prompt + (size_t)g.n_prompt * Q3_EMBD); r->r.prompt = r->prompt_own.data(); }
+    if (g.open) r->trail_own.reserve((size_t)p_.max_prompt);
     r->trail_own.assign(g.trail, g.trail + g.n_trail);
     r->r.trail = r->trail_own.data();
     r->want_pcm = want_pcm && codec_;
@@ -566,12 +583,74 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
     Req* raw = r.get();
     reqs_[raw->id] = std::move(r);
     pending_.push_back(raw);
+    wake_++;
     cv_.notify_all();
     return raw->id;
 }
 
+// [EXT] live text append.  The caller's thread only copies under mu_; the scheduler thread moves the ids to the device between frame
+// groups (collect_appends + run_group), so an append never issues a HIP call that could land inside another thread's graph capture.
+int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
+    Q3_CHECK(n >= 0, "n must be >= 0");
+    Q3_CHECK(n == 0 || ids, "ids missing");
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    Req& r = *it->second;
+    Q3_CHECK(r.r.open, "the request was not submitted with an open trail");
+    Q3_CHECK(!r.closed, "the request's trail is already closed");
+    if (r.state != REQ_QUEUED && r.state != REQ_RUNNING) return 1; // finished (EOS / max_steps), done or failed: nothing appended
+    Q3_CHECK(r.trail_own.size() + (size_t)n <= (size_t)p_.max_prompt, "the trail would exceed max_prompt ids");
+    r.trail_own.insert(r.trail_own.end(), ids, ids + n);
+    if (close) r.closed = true;
+    trail_dirty_ = true;
+    wake_++;
+    cv_.notify_all();
+    return 0;
+}
+
+void Engine::trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* closed) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    const Req& r = *it->second;
+    const int n = (int)r.trail_own.size();
+    *n_appended = n; *n_consumed = std::min(r.fed, n); *closed = !r.r.open || r.closed;
+}
+
+// scheduler thread: appended ids and close flags of live open slots go into the host mirrors; the ids are uploaded by run_group
+void Engine::collect_appends() {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!trail_dirty_) return;
+    trail_dirty_ = false;
+    for (int b = 0; b < B_; b++) {
+        if (!slot_live_[b] || !slot_req_[b]->r.open) continue;
+        const Req& r = *slot_req_[b];
+        const int n = (int)r.trail_own.size();
+        if (n > h_ntrail_[b]) {
+            if (h_pend_[b].empty()) h_pend_off_[b] = h_ntrail_[b];
+            h_pend_[b].insert(h_pend_[b].end(), r.trail_own.begin() + h_ntrail_[b], r.trail_own.begin() + n);
+            h_ntrail_[b] = n;
+            slot_dirty_ = true;
+        }
+        const int op = r.closed ? 0 : 1;
+        if (op != h_open_[b]) { h_open_[b] = op; slot_dirty_ = true; }
+    }
+}
+
+// the host side of the device's stall predicate (the mirrors are exact between frame groups)
+bool Engine::all_live_stalled() const {
+    bool any = false;
+    for (int b = 0; b < B_; b++) {
+        if (!slot_live_[b]) continue;
+        any = true;
+        if (!(h_open_[b] && !h_fin_[b] && h_nfr_[b] < h_maxf_[b] && h_nfr_[b] >= h_ntrail_[b])) return false;
+    }
+    return any;
+}
+
 // moves queued requests into free slots (lowest slot first, so the live slots stay packed and a narrow graph suffices)
-void Engine::admit() {
+void Engine::admit(bool stalled) {
     if (async_pf_ && !pf_batch_.empty()) return; // one admission wave in flight at a time
     std::vector<Req*> batch;
     {
@@ -582,7 +661,7 @@ void Engine::admit() {
         for (int b = 0; b < B_; b++) if (slot_req_[b]) reserved++;
         static const int quantum_div = [] { const char* e = std::getenv("Q3_ADMIT_DIV"); return e ? std::max(1, atoi(e)) : 8; }();
         const int free_slots = B_ - reserved, quantum = std::max(1, B_ / quantum_div);
-        if (free_slots < quantum && n_active_ > 0 && free_slots < (int)pending_.size()) return;
+        if (free_slots < quantum && n_active_ > 0 && free_slots < (int)pending_.size() && !stalled) return; // waiting slots free nothing
         size_t rows = 0;
         while (!pending_.empty() && reserved < B_) {
             Req* r = pending_.front();
@@ -608,7 +687,7 @@ void Engine::admit() {
         }
         r->chunker.reset(new Chunker([this, r](const int64_t* codes, int n_codes, bool is_final) {
             if (!r->want_pcm) return;
-            { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false}); }
+            { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false}); dec_pending_++; }
             dcv_.notify_all();
         }));
         Q3_HIP(hipEventCreate(&r->ev_admit));
@@ -714,8 +793,15 @@ void Engine::activate() {
             h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
             h2d(d_pdraws_.p + b, &zero, 4);
         }
-        h_ntrail_[b] = r->r.n_trail;
-        if (r->r.n_trail > 0) { // [EXT] streaming text: the slot's trailing ids; upload_slot_state below sends the count
+        h_ntrail_[b] = r->r.n_trail; h_open_[b] = 0;
+        h_pend_[b].clear();
+        if (r->r.open) { // [EXT] live text append: whatever has been appended so far (later ids: collect_appends)
+            trail_used_ = true;
+            std::vector<int32_t> ids;
+            { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_own; h_open_[b] = r->closed ? 0 : 1; }
+            h_ntrail_[b] = (int)ids.size();
+            if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
+        } else if (r->r.n_trail > 0) { // [EXT] streaming text: the slot's trailing ids; upload_slot_state below sends the count
             trail_used_ = true;
             h2d(d_trail_.p + (size_t)b * p_.max_prompt, r->r.trail, (size_t)r->r.n_trail * 4);
         }
@@ -758,11 +844,11 @@ void Engine::finish_ar(Req* r) { // engine.rs:644-649: final flush of the chunke
         else { r->state = REQ_DONE; r->t_done = now_ms(); cv_.notify_all(); }
     }
     if (r->want_pcm) {
-        { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, {}, false, true, false}); }
+        { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, {}, false, true, false}); dec_pending_++; }
         dcv_.notify_all();
     }
     h_fin_[b] = 1; h_maxf_[b] = 0; h_nfr_[b] = 0; h_nprompt_[b] = 0; h_temp_[b] = 0.0f; h_mask_[b] = -1;
-    h_pen_[b] = 1.0f; h_ptemp_[b] = 0.0f; h_ntrail_[b] = 0;
+    h_pen_[b] = 1.0f; h_ptemp_[b] = 0.0f; h_ntrail_[b] = 0; h_open_[b] = 0; h_pend_[b].clear();
     kv_t_->release(b); // from the next group on the slot steps on the scratch sequence (upload_slot_state)
     slot_dirty_ = true;
 }
@@ -776,7 +862,7 @@ static int pick_width(int hi, int W) { // graph widths: powers of two (and the f
 // one streaming step (4 frames, engine.rs:505-512) for every active slot
 void Engine::run_group() {
     int hi = 0, remaining = 0;
-    bool sampled = false, pen = false, pred = false, trail = false;
+    bool sampled = false, pen = false, pred = false, trail = false, gate = false;
     for (int b = 0; b < B_; b++)
         if (slot_live_[b]) {
             Req* r = slot_req_[b];
@@ -785,20 +871,26 @@ void Engine::run_group() {
             if (r->r.sampler.temperature > 0.0f) sampled = true;
             if (r->r.opts.penalised()) pen = true;
             if (r->r.opts.pred_sampled()) pred = true;
-            if (r->r.n_trail > 0) trail = true;
+            if (r->r.n_trail > 0 || r->r.open) trail = true;
+            if (h_open_[b]) gate = trail = true;
         }
     arena_used_ = 0; // st_ is idle between scheduler operations: everything staged earlier has been consumed
+    for (int b = 0; b < B_; b++) // [EXT] appended ids collected since the last group: the new tail of the slot's id row
+        if (!h_pend_[b].empty()) {
+            h2d(d_trail_.p + (size_t)b * p_.max_prompt + h_pend_off_[b], h_pend_[b].data(), h_pend_[b].size() * 4);
+            h_pend_[b].clear();
+        }
     if (slot_dirty_) upload_slot_state();
     const int width = pick_width(hi, B_);
     const int group = std::max(1, std::min(4, remaining));
     const bool eager = instrument_ || !p_.use_graph;
-    FrameGraph& fg = frame_graph(width, sampled, pen, pred, trail, !eager);
+    FrameGraph& fg = frame_graph(width, sampled, pen, pred, trail, gate, !eager);
     if (instrument_) { talker_->timer = &timer_; predictor_->timer = &timer_; talker_->timer_gu = &timer_gu_; }
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
     Q3_HIP(hipEventRecord(e0, st_));
     for (int g = 0; g < group; g++) {
-        if (eager) record_frame(fg, sampled, pen, pred, trail);
+        if (eager) record_frame(fg, sampled, pen, pred, trail, gate);
         else Q3_HIP(hipGraphLaunch(fg.exec, st_));
     }
     Q3_HIP(hipEventRecord(e1, st_));
@@ -853,11 +945,17 @@ bool Engine::step() {
         if (n_active_ == 0) Q3_HIP(hipEventSynchronize(pf_done_));
         if (hipEventQuery(pf_done_) == hipSuccess) activate();
     }
-    admit();
+    collect_appends();
+    admit(n_active_ > 0 && all_live_stalled());
     const double t2 = now_ms();
-    if (n_active_ > 0) run_group();
+    // [EXT] live text append: when every live slot waits for text, no frame group runs (graph_frames stays put); prefill and codec
+    // work still proceed, and with none left the driver sleeps until a submit or an append
+    const bool stalled = n_active_ > 0 && all_live_stalled();
+    int dec_pending = 0;
+    if (stalled) { std::lock_guard<std::mutex> lk(dmu_); dec_pending = dec_pending_; }
+    if (n_active_ > 0 && !stalled) run_group();
     else if (n_prefilling_ > 0) { Q3_HIP(hipEventSynchronize(pf_done_)); activate(); }
-    else if (n_draining_ > 0) harvest(true);
+    else if (n_draining_ > 0 || dec_pending > 0) harvest(true);
     const double t3 = now_ms();
     if (g_trace) {
         g_t_harvest += t1 - t0; g_t_admit += t2 - t1; (n_active_ > 0 ? g_t_group : g_t_idle) += t3 - t2;
@@ -865,6 +963,7 @@ bool Engine::step() {
                 stats.frame_loop_ms, stats.prefill_ms);
     }
     std::lock_guard<std::mutex> lk(mu_);
+    stalled_idle_ = stalled && n_prefilling_ == 0 && dec_pending == 0;
     return n_active_ > 0 || n_prefilling_ > 0 || n_draining_ > 0 || !pending_.empty();
 }
 
@@ -904,6 +1003,7 @@ void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, fl
 
 bool Engine::wait(int64_t id, double timeout_ms) {
     const double t0 = now_ms();
+    uint64_t seen = 0;
     for (;;) {
         {
             std::unique_lock<std::mutex> lk(mu_);
@@ -912,6 +1012,9 @@ bool Engine::wait(int64_t id, double timeout_ms) {
             if (it->second->state == REQ_DONE || it->second->state == REQ_FAILED) return true;
             if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
             if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
+            // every live slot waits for text: no busy loop until another thread submits or appends
+            if (stalled_idle_ && wake_ == seen) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
+            seen = wake_;
         }
         step();
     }
@@ -934,10 +1037,13 @@ void Engine::start_driver() {
         try {
             Q3_HIP(hipSetDevice(dev_));
             for (;;) {
+                uint64_t seen;
+                { std::lock_guard<std::mutex> lk(mu_); seen = wake_; }
                 const bool busy = step();
                 std::unique_lock<std::mutex> lk(mu_);
                 if (driver_stop_) return;
                 if (!busy) cv_.wait_for(lk, std::chrono::milliseconds(1), [this] { return driver_stop_ || !pending_.empty(); });
+                else if (stalled_idle_) cv_.wait(lk, [&] { return driver_stop_ || wake_ != seen; }); // every live slot waits for text
             }
         } catch (const std::exception& ex) {
             std::lock_guard<std::mutex> lk(mu_);
@@ -978,6 +1084,7 @@ void Engine::generate_batch(const std::vector<GenRequest>& reqs, std::vector<Gen
         Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
         Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
         check_options(g);
+        Q3_CHECK(!g.open, "open trails need the submit / append interface");
     }
     for (const GenRequest& g : reqs) if (g.n_trail > 0) ensure_text_stream(); // the one step that can fail after validation: before queueing
     std::vector<int64_t> ids(n);

@@ -52,6 +52,8 @@ struct GenRequest {
     GenOptions opts;
     // [EXT] streaming-text talker input (q3tts_spec.h): trailing text ids, one per frame in the feedback; copied at submit
     const int32_t* trail = nullptr; int n_trail = 0;
+    // [EXT] live text append (q3tts_spec.h): the trail stays open; frames past the appended ids wait until append_trail() brings more
+    bool open = false;
 };
 struct GenResult {
     std::vector<int32_t> codes; int n_frames = 0;
@@ -90,6 +92,10 @@ public:
 
     // ---- continuous-batching scheduler ----
     int64_t submit(const GenRequest& r, bool want_pcm, bool copy_prompt = true); // thread-safe
+    // [EXT] live text append, thread-safe and free of HIP calls (the scheduler uploads): 0 appended, 1 the request no longer takes text
+    // (finished, done or failed); throws for an unknown id, a request not submitted open, a closed trail or a total beyond max_prompt
+    int append_trail(int64_t id, const int32_t* ids, int n, bool close);
+    void trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* closed);
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -121,8 +127,9 @@ private:
     };
     // enqueue one frame step for fg.width slots on st_; pen / pred: some live slot has a repetition penalty / samples the predictor
     // trail: some live slot has trailing text ids (the feedback kernel's streaming-text variant replaces the plain one)
-    void record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail);
-    FrameGraph& frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool capture);
+    // gate: some live slot has an open trail (implies trail): k_stall_save first, the gated k_advance_keys last
+    void record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail, bool gate);
+    FrameGraph& frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool gate, bool capture);
     void check_options(const GenRequest& g) const;
     void ensure_text_stream(); // first request with trailing ids: text table + per-slot id rows go to the device
     void prefill(const std::vector<Req*>& batch, bool sampled);
@@ -131,8 +138,10 @@ private:
     // join the batch ("activate") between two frame groups once the prefill event has completed.
     void prefill_async(const std::vector<Req*>& batch);
     void activate();
-    void admit();
+    void admit(bool stalled); // stalled: every live slot waits for text (the admission quantum is not waited for)
     void run_group();
+    void collect_appends();   // scheduler: new ids / close flags of live open slots into the host mirrors (upload in run_group)
+    bool all_live_stalled() const;
     void harvest(bool block);
     void finish_ar(Req* r);
     void decoder_main();
@@ -175,13 +184,16 @@ private:
     // [EXT] streaming-text state, allocated by the first request with n_trail > 0: the text table, [B][max_prompt] trailing ids, [B] counts
     DevBuf<float> d_text_; DevBuf<int32_t> d_trail_, d_ntrail_; int64_t text_rows_ = 0;
     std::mutex text_mu_; bool text_ready_ = false; // text_ready_ is written under text_mu_ and capture_mutex()
-    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*16 + trail*8 + pred*4 + pen*2 + sampled
+    // [EXT] live text append: [B] open flags and the stall save area ([B][2048] hidden rows, [B][2] draw counters), allocated with the above
+    DevBuf<int32_t> d_open_; DevBuf<float> d_stall_hidden_; DevBuf<uint32_t> d_stall_draws_;
+    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*32 + gate*16 + trail*8 + pred*4 + pen*2 + sampled
     bool instrument_ = false; bool pred_identity_pages_ = false;
     // host mirrors of the slot state (refreshed from the device after every frame group)
     std::vector<int32_t> h_maxf_, h_fin_, h_nfr_, h_mask_, h_nprompt_, h_topk_;
     std::vector<float> h_temp_, h_topp_;
     std::vector<float> h_pen_, h_ptemp_, h_ptopp_; std::vector<int32_t> h_ptopk_;
-    std::vector<int32_t> h_ntrail_;
+    std::vector<int32_t> h_ntrail_, h_open_;
+    std::vector<std::vector<int32_t>> h_pend_; std::vector<int> h_pend_off_; // appended ids not yet on the device: ids [off, off+size)
     bool trail_used_ = false; // some activated request had trailing ids: upload_slot_state keeps d_ntrail_ current from then on
     bool ext_used_ = false; // some request carried GenOptions: upload_slot_state keeps their device arrays current from then on
     bool slot_dirty_ = false;
@@ -194,6 +206,9 @@ private:
     std::vector<int> cs_free_;          // free codec streams
     int64_t next_id_ = 1;
     int n_active_ = 0, n_draining_ = 0;
+    bool trail_dirty_ = false;          // an append arrived since the scheduler last looked (mu_)
+    uint64_t wake_ = 0;                 // bumped by every submit / append: a driver idling on stalled slots sleeps until it changes (mu_)
+    bool stalled_idle_ = false;         // the last step() ran nothing: every live slot waits for text and nothing else is in flight
     std::vector<Voice> voices_;
     std::thread driver_; bool driver_on_ = false, driver_stop_ = false;
     // decoder thread
@@ -202,6 +217,7 @@ private:
     std::thread dec_thread_; bool dec_started_ = false, dec_stop_ = false;
     std::mutex dmu_; std::condition_variable dcv_;
     std::deque<DecTask> dq_; std::deque<Completion> comp_;
+    int dec_pending_ = 0;               // chunk / fence tasks whose completion has not been harvested yet (dmu_)
     std::string derr_;
     LaunchTimer timer_, timer_gu_;
 };

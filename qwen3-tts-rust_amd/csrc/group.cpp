@@ -306,6 +306,35 @@ int q3tts_group_submit_text_streaming(q3tts_group* g, int32_t voice_id, const in
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+int q3tts_group_submit_text_streaming_open(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
+                                           const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler,
+                                           int32_t max_steps, int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts,
+                                           int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && req_id, "null argument");
+    const int i = pick_engine(g);
+    int64_t id = 0;
+    if (q3tts_submit_text_streaming_open(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos,
+                                         want_pcm, opts, &id) != Q3TTS_OK) return Q3TTS_ERR;
+    *req_id = (id << kEngineBits) | i;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_group_text_append(q3tts_group* g, int64_t req_id, const int32_t* text_ids, int32_t n, int32_t is_last) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_text_append(e, rid_of(req_id), text_ids, n, is_last);
+}
+int q3tts_group_trail_append(q3tts_group* g, int64_t req_id, const int32_t* ids, int32_t n, int32_t close) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_trail_append(e, rid_of(req_id), ids, n, close);
+}
+int q3tts_group_trail_progress(q3tts_group* g, int64_t req_id, int32_t* n_appended, int32_t* n_consumed, int32_t* closed) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_trail_progress(e, rid_of(req_id), n_appended, n_consumed, closed);
+}
 int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id) { return (g && eng_of(req_id) < (int)g->slot.size()) ? g->slot[eng_of(req_id)].dev : -1; }
 int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out) {
     q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);

@@ -209,6 +209,18 @@ struct AdvanceKeysArgs {
     int32_t *t_slot, *t_pos;
 };
 void launch_advance_keys(hipStream_t st, const AdvanceKeysArgs& a);
+// [EXT] live text append (q3tts_spec.h): slot b waits this frame when
+//   !finished[b] && n_frames[b] < max_frames[b] && open[b] && n_frames[b] >= n_trail[b]
+// k_stall_save (the gated frame's first launch) copies a waiting slot's hidden row and talker / predictor draw counters to the save area;
+// the gated k_advance_keys (the frame's last launch) copies them back, keeps keys[b][0], re-arms keys 1..15 and next_key0, and leaves
+// n_frames / finished / history / positions alone.  Active slots take the plain advance.
+struct StallArgs {
+    const int32_t* open = nullptr; const int32_t* n_trail = nullptr;
+    float* hidden = nullptr; uint32_t* draws = nullptr; uint32_t* pdraws = nullptr; // live state ([B][2048], [B], [B])
+    float* save_hidden = nullptr; uint32_t* save_draws = nullptr;                   // save area ([B][2048], [B][2])
+};
+void launch_stall_save(hipStream_t st, const AdvanceKeysArgs& a, const StallArgs& s);
+void launch_advance_keys_gated(hipStream_t st, const AdvanceKeysArgs& a, const StallArgs& s);
 
 // on-device LlamaSampler::sample (sampler.hip): one workgroup per sequence over logits[b*stride + [0,n)), n <= 4096
 struct SampleArgs {

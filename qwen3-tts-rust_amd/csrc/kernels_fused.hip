@@ -879,9 +879,7 @@ void launch_gather_rows_keys(hipStream_t st, const float* table, int64_t rows, c
     hipLaunchKernelGGL(k_gather_rows_keys, dim3((row_len + 255) / 256, ntok), dim3(256), 0, st, table, rows, keys, key_stride, row_len, dst);
 }
 
-__global__ void k_advance_keys(AdvanceKeysArgs a) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= a.B) return;
+__device__ __forceinline__ void advance_slot(const AdvanceKeysArgs& a, int b) {
     u64* k = a.keys + (size_t)b * 16;
     const bool live = !a.finished[b] && a.n_frames[b] < a.max_frames[b];
     if (live) {
@@ -900,8 +898,59 @@ __global__ void k_advance_keys(AdvanceKeysArgs a) {
     a.next_key0[b] = pack_key(-INFINITY, 0);
     for (int q = 1; q < 16; q++) k[q] = pack_key(-INFINITY, 0);
 }
+__global__ void k_advance_keys(AdvanceKeysArgs a) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    advance_slot(a, b);
+}
 void launch_advance_keys(hipStream_t st, const AdvanceKeysArgs& a) {
     hipLaunchKernelGGL(k_advance_keys, dim3((a.B + 63) / 64), dim3(64), 0, st, a);
+}
+
+// [EXT] live text append: the stall gate.  Its inputs (finished, n_frames, max_frames, open, n_trail) are written by nothing inside a
+// frame before the gated advance reads them, so k_stall_save at the frame's start and the advance at its end see the same answer.
+__device__ __forceinline__ bool slot_waits(const AdvanceKeysArgs& a, const StallArgs& s, int b) {
+    const int f = a.n_frames[b];
+    return !a.finished[b] && f < a.max_frames[b] && s.open[b] && f >= s.n_trail[b];
+}
+// one workgroup per slot: 256 lanes x 2 float4 = the 2048-float hidden row
+__global__ void __launch_bounds__(256) k_stall_save(AdvanceKeysArgs a, StallArgs s) {
+    const int b = blockIdx.x;
+    if (!slot_waits(a, s, b)) return;
+    const float4* src = reinterpret_cast<const float4*>(s.hidden + (size_t)b * 2048);
+    float4* dst = reinterpret_cast<float4*>(s.save_hidden + (size_t)b * 2048);
+    const float4 v0 = src[threadIdx.x], v1 = src[threadIdx.x + 256];
+    dst[threadIdx.x] = v0;
+    dst[threadIdx.x + 256] = v1;
+    if (threadIdx.x == 0) { s.save_draws[2 * b] = s.draws[b]; s.save_draws[2 * b + 1] = s.pdraws[b]; }
+}
+void launch_stall_save(hipStream_t st, const AdvanceKeysArgs& a, const StallArgs& s) {
+    hipLaunchKernelGGL(k_stall_save, dim3(a.B), dim3(256), 0, st, a, s);
+}
+// the gate is read by every lane before lane 0 changes n_frames / finished (barrier), so the restore and the skip agree
+__global__ void __launch_bounds__(256) k_advance_keys_gated(AdvanceKeysArgs a, StallArgs s) {
+    const int b = blockIdx.x;
+    const bool waits = slot_waits(a, s, b);
+    __syncthreads();
+    if (!waits) {
+        if (threadIdx.x == 0) advance_slot(a, b);
+        return;
+    }
+    const float4* src = reinterpret_cast<const float4*>(s.save_hidden + (size_t)b * 2048);
+    float4* dst = reinterpret_cast<float4*>(s.hidden + (size_t)b * 2048);
+    const float4 v0 = src[threadIdx.x], v1 = src[threadIdx.x + 256];
+    dst[threadIdx.x] = v0;
+    dst[threadIdx.x + 256] = v1;
+    if (threadIdx.x == 0) {
+        s.draws[b] = s.save_draws[2 * b];
+        s.pdraws[b] = s.save_draws[2 * b + 1];
+        u64* k = a.keys + (size_t)b * 16; // k[0] is this frame's code_0 again next frame
+        a.next_key0[b] = pack_key(-INFINITY, 0);
+        for (int q = 1; q < 16; q++) k[q] = pack_key(-INFINITY, 0);
+    }
+}
+void launch_advance_keys_gated(hipStream_t st, const AdvanceKeysArgs& a, const StallArgs& s) {
+    hipLaunchKernelGGL(k_advance_keys_gated, dim3(a.B), dim3(256), 0, st, a, s);
 }
 
 } // namespace q3

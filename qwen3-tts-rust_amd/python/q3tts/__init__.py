@@ -88,6 +88,8 @@ SYMBOLS = [
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
     "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan",
     "q3tts_op_linear", "q3tts_linear_plan", "q3tts_argmax_key",
+    "q3tts_submit_trailing_open", "q3tts_trail_append", "q3tts_trail_progress", "q3tts_submit_text_streaming_open", "q3tts_text_append",
+    "q3tts_group_submit_text_streaming_open", "q3tts_group_text_append", "q3tts_group_trail_append", "q3tts_group_trail_progress",
 ]
 
 
@@ -181,6 +183,15 @@ def lib():
         L.q3tts_generate_batch_trailing.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.c_int32, C.POINTER(GenOptions),
                                                     C.POINTER(C.c_void_p), C.c_void_p]
         L.q3tts_group_submit_text_streaming.argtypes = L.q3tts_group_submit_text_ex.argtypes
+        L.q3tts_submit_trailing_open.argtypes = L.q3tts_submit_trailing.argtypes
+        L.q3tts_trail_append.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32]
+        L.q3tts_trail_progress.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.q3tts_submit_text_streaming_open.argtypes = L.q3tts_submit_text_ex.argtypes
+        L.q3tts_text_append.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32]
+        L.q3tts_group_submit_text_streaming_open.argtypes = L.q3tts_group_submit_text_ex.argtypes
+        L.q3tts_group_text_append.argtypes = L.q3tts_text_append.argtypes
+        L.q3tts_group_trail_append.argtypes = L.q3tts_trail_append.argtypes
+        L.q3tts_group_trail_progress.argtypes = L.q3tts_trail_progress.argtypes
         _lib = L
     return _lib
 
@@ -356,16 +367,19 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
 
     # ---- continuous-batching scheduler (q3tts_submit / poll / fetch / wait) ----
     def submit(self, prompt, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
-               repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None):
-        """trailing_ids: [EXT] streaming-text input, one text id added to the feedback per frame (None = the reference's feedback)"""
+               repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None,
+               open_trail=False):
+        """trailing_ids: [EXT] streaming-text input, one text id added to the feedback per frame (None = the reference's feedback);
+        open_trail: [EXT] live text append -- the trail stays open (trailing_ids may be None / empty), frames past it wait for trail_append"""
         pr = np.ascontiguousarray(prompt, np.float32)
         r = Request()
         self._fill(r, pr, 0, max_steps, temperature, top_k, top_p, seed, mask_eos)
         o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        if trailing_ids is not None:
-            tr = np.ascontiguousarray(trailing_ids, np.int32)
-            _chk(lib().q3tts_submit_trailing(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o) if o is not None else None, _p(tr), tr.size,
+        if trailing_ids is not None or open_trail:
+            tr = np.ascontiguousarray(trailing_ids if trailing_ids is not None else [], np.int32)
+            fn = lib().q3tts_submit_trailing_open if open_trail else lib().q3tts_submit_trailing
+            _chk(fn(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o) if o is not None else None, _p(tr), tr.size,
                                              C.byref(rid)))
         elif o is None:
             _chk(lib().q3tts_submit(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(rid)))
@@ -384,18 +398,44 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
 
     def submit_text(self, voice_id, text_ids, lang_id=2055, instr_ids=None, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42,
                     mask_eos=True, want_pcm=False, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0,
-                    streaming_text=False):
-        """streaming_text: [EXT] upstream's streaming-text layout (q3tts_submit_text_streaming)"""
+                    streaming_text=False, open_text=False):
+        """streaming_text: [EXT] upstream's streaming-text layout (q3tts_submit_text_streaming); open_text (with streaming_text): the text
+        known so far, the rest follows through text_append (q3tts_submit_text_streaming_open)"""
+        if open_text and not streaming_text:
+            raise Q3Error("open_text needs streaming_text=True")
         t = np.ascontiguousarray(text_ids, np.int32)
         ins = np.ascontiguousarray(instr_ids, np.int32) if instr_ids is not None else None
         sc = SamplerConfig(temperature, top_k, top_p, 1, seed)
         o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        fn = lib().q3tts_submit_text_streaming if streaming_text else lib().q3tts_submit_text_ex
+        fn = (lib().q3tts_submit_text_streaming_open if open_text else lib().q3tts_submit_text_streaming) if streaming_text \
+            else lib().q3tts_submit_text_ex
         _chk(fn(self.h, voice_id, _p(t), t.size, lang_id, _p(ins), ins.size if ins is not None else 0, C.byref(sc),
                                         max_steps, 1 if mask_eos else 0, 1 if want_pcm else 0, C.byref(o) if o is not None else None,
                                         C.byref(rid)))
         return rid.value
+
+    def trail_append(self, rid, ids, close=False):
+        """[EXT] appends raw trailing ids to an open request: 0 appended, 1 the request no longer takes text (raises on errors)"""
+        a = np.ascontiguousarray(ids if ids is not None else [], np.int32)
+        rc = lib().q3tts_trail_append(self.h, rid, _p(a) if a.size else None, a.size, 1 if close else 0)
+        if rc < 0:
+            _chk(rc)
+        return rc
+
+    def text_append(self, rid, ids, is_last=False):
+        """[EXT] appends text ids to an open text-level request; is_last also appends TEXT_EOS and closes.  Returns as trail_append"""
+        a = np.ascontiguousarray(ids if ids is not None else [], np.int32)
+        rc = lib().q3tts_text_append(self.h, rid, _p(a) if a.size else None, a.size, 1 if is_last else 0)
+        if rc < 0:
+            _chk(rc)
+        return rc
+
+    def trail_progress(self, rid):
+        """[EXT] (ids appended, ids consumed by the feedback so far, closed)"""
+        na, nc, cl = C.c_int32(), C.c_int32(), C.c_int32()
+        _chk(lib().q3tts_trail_progress(self.h, rid, C.byref(na), C.byref(nc), C.byref(cl)))
+        return na.value, nc.value, bool(cl.value)
 
     def poll(self, rid):
         s = ReqStatus()
