@@ -4,10 +4,6 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <thread>
 #include "kdev.h"
 #include <functional>
 
@@ -101,13 +97,10 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     // ---- per-slot state ----
     hist_stride_ = p.max_steps * 16;
     tl_stride_ = (Q3_SAMPLE_END + 31) & ~31;
-    d_tseq_.alloc(B); d_tslot_.alloc(B); d_tpos_.alloc(4 * B); d_keys_.alloc(16 * B); d_next_key0_.alloc(B); d_nframes_.alloc(B); d_finished_.alloc(B);
-    d_maxframes_.alloc(B); d_maskeos_.alloc(B); d_hist_.alloc((size_t)B * hist_stride_);
-    d_temp_.alloc(B); d_topp_.alloc(B); d_topk_.alloc(B); d_rngkey_.alloc((size_t)8 * B); d_draws_.alloc(B);
-    d_temp_.zero(); d_topp_.zero(); d_topk_.zero(); d_rngkey_.zero(); d_draws_.zero();
-    d_pen_.alloc(B); d_ptemp_.alloc(B); d_ptopp_.alloc(B); d_ptopk_.alloc(B); d_prngkey_.alloc((size_t)8 * B); d_pdraws_.alloc(B);
-    d_plogits_.alloc((size_t)B * Q3_CODEBOOK_SIZE);
-    d_ptemp_.zero(); d_ptopk_.zero(); d_prngkey_.zero(); d_pdraws_.zero();
+    slots_ = SlotTable(B); d_slots_.alloc(slots_.host.size()); slots_.dev = d_slots_.p; // every slot idle; sent by upload_slot_state below
+    d_keys_.alloc(16 * B); d_next_key0_.alloc(B); d_hist_.alloc((size_t)B * hist_stride_);
+    d_rngkey_.alloc((size_t)8 * B); d_draws_.alloc(B); d_prngkey_.alloc((size_t)8 * B); d_pdraws_.alloc(B);
+    d_rngkey_.zero(); d_draws_.zero(); d_prngkey_.zero(); d_pdraws_.zero(); d_plogits_.alloc((size_t)B * Q3_CODEBOOK_SIZE);
     d_tlogits_.alloc((size_t)B * tl_stride_); d_thidden_.alloc((size_t)B * Q3_EMBD); d_pin_.alloc((size_t)2 * B * dP_);
     d_fb_.alloc((size_t)B * Q3_EMBD);
     d_prompt_.alloc((size_t)talker_->max_tok() * Q3_EMBD);
@@ -122,12 +115,8 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_pseq_.alloc(B); d_pseq_.upload(seq.data(), B);
     d_pslot_.alloc(slot.size()); d_pslot_.upload(slot.data(), slot.size());
     d_ppos_.alloc(pos.size()); d_ppos_.upload(pos.data(), pos.size());
-    h_maxf_.assign(B, 0); h_fin_.assign(B, 1); h_nfr_.assign(B, 0); h_mask_.assign(B, -1); h_nprompt_.assign(B, 0); h_topk_.assign(B, 0);
-    h_temp_.assign(B, 0.0f); h_topp_.assign(B, 1.0f);
-    h_pen_.assign(B, 1.0f); h_ptemp_.assign(B, 0.0f); h_ptopp_.assign(B, 1.0f); h_ptopk_.assign(B, 0); h_ntrail_.assign(B, 0);
-    h_open_.assign(B, 0); h_pend_.assign(B, std::vector<int32_t>()); h_pend_off_.assign(B, 0);
-    d_pen_.upload(h_pen_.data(), B); d_ptopp_.upload(h_ptopp_.data(), B);
-    slot_req_.assign(B, nullptr); slot_live_.assign(B, 0);
+    h_pend_.assign(B, std::vector<int32_t>()); h_pend_off_.assign(B, 0);
+    slot_req_.assign(B, nullptr);
     if (async_pf_) { d_pf_logits_.alloc((size_t)B * tl_stride_); d_pf_hidden_.alloc((size_t)B * Q3_EMBD); }
     {
         std::vector<q3_u64> k0((size_t)16 * B, pack_key(-INFINITY, 0)), n0(B, pack_key(-INFINITY, 0));
@@ -230,19 +219,18 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
 
 // One frame for fg.width slots (engine.rs:545-641).  code_0 of the frame is already in keys[b][0]: it was produced at the end
 // of the previous frame (or of the prefill) by the talker head's argmax epilogue or by the device sampler.
-// [EXT] pen: the talker head writes logits and k_sample applies the penalty with the history the device already has (code_0 of frames
-// [0, n_frames) in d_hist_ + the current frame's key, which k_advance_keys appends only after the head); pred: every predictor head writes
-// its 2048 logits and k_sample_pred draws the code (greedy slots take its first-max branch).  Neither set: today's launch sequence.
-// trail: the feedback kernel's streaming-text variant (same launch, reads d_nframes_ / d_ntrail_ / d_trail_ and the text table).
-// gate: [EXT] live text append -- k_stall_save before everything and the gated k_advance_keys in place of the plain one; a slot that
-// waits runs through every launch in between and its work is discarded (q3tts_spec.h "live text append").  Clear: today's launches.
-void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail, bool gate) {
+// [EXT] v.pen: the talker head writes logits and k_sample applies the penalty with the history the device already has (code_0 of frames
+// [0, n_frames) in d_hist_ + the current frame's key, which k_advance_keys appends only after the head); v.pred: every predictor head writes
+// its 2048 logits and k_sample_pred draws the code (greedy slots take its first-max branch); v.trail: the feedback kernel reads the slot
+// table's n_frames / n_trail rows, d_trail_ and the text table; v.gate: a slot that waits runs through every launch between k_stall_save and
+// the gated advance and its work is discarded (q3tts_spec.h "live text append").  A clear flag leaves the launches as they are without it.
+void Engine::record_frame(FrameGraph& fg, FrameVariant v) {
     const int B = fg.width;
     const KvCache kvt = kv_t_->view(), kvp = kv_p_->view();
-    AdvanceKeysArgs a{B, d_finished_.p, d_nframes_.p, d_maxframes_.p, d_keys_.p, d_next_key0_.p, d_hist_.p, hist_stride_, d_tslot_.p, d_tpos_.p};
+    AdvanceKeysArgs a{B, di(SF_FINISHED), di(SF_NFRAMES), di(SF_MAXFRAMES), d_keys_.p, d_next_key0_.p, d_hist_.p, hist_stride_, di(SF_TSLOT), di(SF_TPOS)};
     StallArgs sg;
-    if (gate) {
-        sg.open = d_open_.p; sg.n_trail = d_ntrail_.p; sg.hidden = d_thidden_.p; sg.draws = d_draws_.p; sg.pdraws = d_pdraws_.p;
+    if (v.gate) {
+        sg.open = di(SF_OPEN); sg.n_trail = di(SF_NTRAIL); sg.hidden = d_thidden_.p; sg.draws = d_draws_.p; sg.pdraws = d_pdraws_.p;
         sg.save_hidden = d_stall_hidden_.p; sg.save_draws = d_stall_draws_.p;
         launch_stall_save(st_, a, sg);
     }
@@ -254,9 +242,9 @@ void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, boo
         Transformer::Input in; in.x = d_pin_.p; in.x_stride = dP_;
         predictor_->set_same_seq_tokens(true);
         predictor_->forward(st_, in, 2 * B, tm, kvp, nullptr);
-        if (pred) {
+        if (v.pred) {
             predictor_->head(st_, B, B, 0, Q3_CODEBOOK_SIZE, d_plogits_.p, Q3_CODEBOOK_SIZE);
-            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_ptemp_.p, d_ptopk_.p, d_ptopp_.p, nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + 1, 16};
+            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, df(SF_PTEMP), di(SF_PTOPK), df(SF_PTOPP), nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + 1, 16};
             launch_sample_pred(st_, sa, B);
         } else {
             ArgmaxEpi am{d_keys_.p + 1, 16, nullptr, 0};
@@ -270,9 +258,9 @@ void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, boo
         if (pred_identity_pages_) { tm.uniform_pos = q + 1; kvq.page_table = nullptr; } // token t = sequence t = page t, position q+1 everywhere
         Transformer::Input in; in.x = d_proj_tab_[q].p; in.x_stride = dP_; in.idx_keys = d_keys_.p + q; in.idx_stride = 16;
         predictor_->forward(st_, in, B, tm, kvq, nullptr);
-        if (pred) {
+        if (v.pred) {
             predictor_->head(st_, 0, B, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_plogits_.p, Q3_CODEBOOK_SIZE);
-            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_ptemp_.p, d_ptopk_.p, d_ptopp_.p, nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + q + 1, 16};
+            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, df(SF_PTEMP), di(SF_PTOPK), df(SF_PTOPP), nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + q + 1, 16};
             launch_sample_pred(st_, sa, B);
         } else {
             ArgmaxEpi am{d_keys_.p + q + 1, 16, nullptr, 0};
@@ -280,37 +268,37 @@ void Engine::record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, boo
         }
     }
     // :622-631 feedback ; :633-639 talker step at pos = cur_pos ; :550-555 next frame's code_0
-    if (trail) {
-        TextTrail tt; tt.n_frames = d_nframes_.p; tt.n_trail = d_ntrail_.p; tt.ids = d_trail_.p; tt.ids_stride = p_.max_prompt;
+    if (v.trail) {
+        TextTrail tt; tt.n_frames = di(SF_NFRAMES); tt.n_trail = di(SF_NTRAIL); tt.ids = d_trail_.p; tt.ids_stride = p_.max_prompt;
         tt.table = d_text_.p; tt.rows = text_rows_;
         launch_feedback_keys(st_, d_tab_ptrs_.p, d_tab_rows_.p, d_keys_.p, 16, d_tts_pad_.p, d_fb_.p, B, &tt);
     } else {
         launch_feedback_keys(st_, d_tab_ptrs_.p, d_tab_rows_.p, d_keys_.p, 16, d_tts_pad_.p, d_fb_.p, B);
     }
     {
-        TokMeta tm{d_tseq_.p, d_tslot_.p, d_tpos_.p};
+        TokMeta tm{di(SF_TSEQ), di(SF_TSLOT), di(SF_TPOS)};
         Transformer::Input in; in.x = d_fb_.p; in.x_stride = Q3_EMBD;
         talker_->set_same_seq_tokens(false);
         talker_->forward(st_, in, B, tm, kvt, nullptr);
-        if (sampled || pen) { // llama/mod.rs:666-776 on device; greedy slots of a mixed batch take the kernel's T<=0 branch
+        if (v.sampled || v.pen) { // llama/mod.rs:666-776 on device; greedy slots of a mixed batch take the kernel's T<=0 branch
             talker_->head(st_, 0, B, 0, tl_stride_, d_tlogits_.p, tl_stride_, nullptr, -1, d_thidden_.p);
-            SampleArgs sa{d_tlogits_.p, tl_stride_, Q3_SAMPLE_END, d_temp_.p, d_topk_.p, d_topp_.p, d_maskeos_.p, d_rngkey_.p, d_draws_.p, d_next_key0_.p, 1};
-            if (pen) { sa.penalty = d_pen_.p; sa.hist = d_hist_.p; sa.hist_stride = hist_stride_; sa.hist_len = d_nframes_.p; sa.cur_key = d_keys_.p; sa.cur_stride = 16; }
+            SampleArgs sa{d_tlogits_.p, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP), di(SF_TOPK), df(SF_TOPP), di(SF_MASKEOS), d_rngkey_.p, d_draws_.p, d_next_key0_.p, 1};
+            if (v.pen) { sa.penalty = df(SF_PEN); sa.hist = d_hist_.p; sa.hist_stride = hist_stride_; sa.hist_len = di(SF_NFRAMES); sa.cur_key = d_keys_.p; sa.cur_stride = 16; }
             launch_sample(st_, sa, B);
         } else {
-            ArgmaxEpi am{d_next_key0_.p, 1, d_maskeos_.p, 0};
+            ArgmaxEpi am{d_next_key0_.p, 1, di(SF_MASKEOS), 0};
             talker_->head(st_, 0, B, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, d_thidden_.p);
         }
     }
-    if (gate) launch_advance_keys_gated(st_, a, sg);
+    if (v.gate) launch_advance_keys_gated(st_, a, sg);
     else launch_advance_keys(st_, a);
     Q3_LAUNCH_CHECK();
 }
 
 std::mutex& capture_mutex() { static std::mutex mu; return mu; }
 
-Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool gate, bool capture) {
-    std::unique_ptr<FrameGraph>& slot = graphs_[width * 32 + (gate ? 16 : 0) + (trail ? 8 : 0) + (pred ? 4 : 0) + (pen ? 2 : 0) + (sampled ? 1 : 0)];
+Engine::FrameGraph& Engine::frame_graph(int width, FrameVariant v, bool capture) {
+    std::unique_ptr<FrameGraph>& slot = graphs_[v.key(width)];
     // one graph construction at a time per process: engines of a multi-device group (or several engines on one device) build their frame
     // graphs from different threads; the synchronous allocations / uploads below and concurrent thread-local captures were seen to
     // invalidate another thread's capture on ROCm 7.2 ("operation failed due to a previous error during capture")
@@ -334,7 +322,7 @@ Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool 
     if (capture && !fg.exec) {
         (void)hipGetLastError();
         Q3_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
-        try { record_frame(fg, sampled, pen, pred, trail, gate); }
+        try { record_frame(fg, v); }
         catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(st_, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
         Q3_HIP(hipStreamEndCapture(st_, &fg.graph));
         Q3_HIP(hipGraphInstantiate(&fg.exec, fg.graph, nullptr, nullptr, 0));
@@ -343,22 +331,8 @@ Engine::FrameGraph& Engine::frame_graph(int width, bool sampled, bool pen, bool 
 }
 
 void Engine::upload_slot_state() {
-    const int W = B_;
-    std::vector<int32_t> tslot(W, 0), tpos((size_t)4 * W, 0), tseq(W, W); // idle slots step on the scratch sequence (row W)
-    for (int b = 0; b < W; b++) {
-        if (!slot_live_.empty() && slot_live_[b]) { const int t = h_nprompt_[b] + h_nfr_[b]; tslot[b] = t; tpos[4 * b] = tpos[4 * b + 1] = tpos[4 * b + 2] = t; tseq[b] = b; }
-    }
-    h2d(d_tseq_.p, tseq.data(), (size_t)W * 4);
-    h2d(d_maxframes_.p, h_maxf_.data(), (size_t)W * 4); h2d(d_finished_.p, h_fin_.data(), (size_t)W * 4); h2d(d_nframes_.p, h_nfr_.data(), (size_t)W * 4);
-    h2d(d_tslot_.p, tslot.data(), (size_t)W * 4); h2d(d_tpos_.p, tpos.data(), (size_t)16 * W); h2d(d_maskeos_.p, h_mask_.data(), (size_t)W * 4);
-    h2d(d_temp_.p, h_temp_.data(), (size_t)W * 4); h2d(d_topk_.p, h_topk_.data(), (size_t)W * 4); h2d(d_topp_.p, h_topp_.data(), (size_t)W * 4);
-    if (ext_used_) {
-        h2d(d_pen_.p, h_pen_.data(), (size_t)W * 4); h2d(d_ptemp_.p, h_ptemp_.data(), (size_t)W * 4);
-        h2d(d_ptopk_.p, h_ptopk_.data(), (size_t)W * 4); h2d(d_ptopp_.p, h_ptopp_.data(), (size_t)W * 4);
-    }
-    if (trail_used_) { // a reused slot never keeps its predecessor's count or open flag
-        h2d(d_ntrail_.p, h_ntrail_.data(), (size_t)W * 4); h2d(d_open_.p, h_open_.data(), (size_t)W * 4);
-    }
+    slots_.route();
+    h2d(slots_.dev, slots_.host.data(), slots_.host.size() * 4);
     slot_dirty_ = false;
 }
 
@@ -367,38 +341,29 @@ void Engine::upload_slot_state() {
 // head: code_0 of its first frame (:550-555) + the hidden row the predictor starts from (:565-566).
 void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
     size_t total = 0;
-    for (Req* r : batch) total += (size_t)r->r.n_prompt;
+    std::vector<PromptRef> refs;
+    for (Req* r : batch) { total += (size_t)r->r.n_prompt; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot}); }
     const int chunk = talker_->max_tok();
     std::vector<int32_t> seq(chunk), slot(chunk), pos((size_t)4 * chunk);
-    size_t bi = 0; int t = 0; // cursor over (request, token)
-    size_t done = 0;
+    PrefillCursor cur; std::vector<std::pair<int, int>> lasts;
     talker_->set_same_seq_tokens(true);
-    while (done < total) {
-        int n = 0;
-        std::vector<std::pair<Req*, int>> lasts; // (request, index inside this chunk) of final prompt tokens
-        const size_t left = total - done;
-        float* stage = (float*)stage_alloc(std::min<size_t>(left, (size_t)chunk) * Q3_EMBD * 4);
-        while (n < chunk && bi < batch.size()) {
-            Req* r = batch[bi];
-            std::copy(r->r.prompt + (size_t)t * Q3_EMBD, r->r.prompt + (size_t)(t + 1) * Q3_EMBD, stage + (size_t)n * Q3_EMBD);
-            seq[n] = r->slot; slot[n] = t; pos[4 * n] = pos[4 * n + 1] = pos[4 * n + 2] = t; pos[4 * n + 3] = 0; // :306-314
-            if (t == r->r.n_prompt - 1) { lasts.emplace_back(r, n); bi++; t = 0; } else t++;
-            n++;
-        }
+    for (size_t done = 0; done < total;) {
+        float* stage = (float*)stage_alloc(std::min<size_t>(total - done, (size_t)chunk) * Q3_EMBD * 4);
+        const int n = pack_prefill_chunk(refs, cur, chunk, stage, seq.data(), slot.data(), pos.data(), lasts);
         Q3_HIP(hipMemcpyAsync(d_prompt_.p, stage, (size_t)n * Q3_EMBD * 4, hipMemcpyHostToDevice, st_));
         h2d(d_pf_seq_.p, seq.data(), (size_t)n * 4); h2d(d_pf_slot_.p, slot.data(), (size_t)n * 4); h2d(d_pf_pos_.p, pos.data(), (size_t)n * 16);
         TokMeta tm{d_pf_seq_.p, d_pf_slot_.p, d_pf_pos_.p};
         Transformer::Input in; in.x = d_prompt_.p; in.x_stride = Q3_EMBD;
         talker_->forward(st_, in, n, tm, kv_t_->view(), nullptr);
         for (auto& lb : lasts) {
-            const int sb = lb.first->slot, ti = lb.second;
+            const int sb = refs[lb.first].slot, ti = lb.second;
             if (sampled) {
                 talker_->head(st_, ti, 1, 0, tl_stride_, d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_thidden_.p + (size_t)sb * Q3_EMBD);
-                SampleArgs sa{d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, Q3_SAMPLE_END, d_temp_.p + sb, d_topk_.p + sb, d_topp_.p + sb,
-                              d_maskeos_.p + sb, d_rngkey_.p + (size_t)sb * 8, d_draws_.p + sb, d_keys_.p + (size_t)sb * 16, 16};
+                SampleArgs sa{d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + sb, di(SF_TOPK) + sb, df(SF_TOPP) + sb,
+                              di(SF_MASKEOS) + sb, d_rngkey_.p + (size_t)sb * 8, d_draws_.p + sb, d_keys_.p + (size_t)sb * 16, 16};
                 launch_sample(st_, sa, 1);
             } else {
-                ArgmaxEpi am{d_keys_.p + (size_t)sb * 16, 16, d_maskeos_.p + sb, 0};
+                ArgmaxEpi am{d_keys_.p + (size_t)sb * 16, 16, di(SF_MASKEOS) + sb, 0};
                 talker_->head(st_, ti, 1, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, d_thidden_.p + (size_t)sb * Q3_EMBD);
             }
         }
@@ -526,7 +491,9 @@ void Engine::harvest(bool block) {
     }
 }
 
-void Engine::check_options(const GenRequest& g) const {
+void Engine::validate(const GenRequest& g) const {
+    Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
+    Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
     const GenOptions& o = g.opts;
     Q3_CHECK(std::isfinite(o.repetition_penalty) && o.repetition_penalty > 0.0f, "repetition_penalty must be finite and > 0");
     Q3_CHECK(o.predictor_top_k >= 0, "predictor_top_k must be >= 0");
@@ -554,8 +521,6 @@ void Engine::ensure_text_stream() {
         d_text_.alloc((size_t)std::max<int64_t>(text_rows_, 1) * Q3_EMBD);
         if (text_rows_ > 0) d_text_.upload(a.text_table, (size_t)text_rows_ * Q3_EMBD);
         d_trail_.alloc((size_t)B_ * p_.max_prompt); d_trail_.zero();
-        d_ntrail_.alloc(B_); d_ntrail_.zero();
-        d_open_.alloc(B_); d_open_.zero();
         d_stall_hidden_.alloc((size_t)B_ * Q3_EMBD); d_stall_draws_.alloc((size_t)2 * B_);
         Q3_HIP(hipStreamSynchronize(nullptr)); // the memsets ran on the null stream; the engine's streams do not wait for it
     } catch (...) { (void)hipSetDevice(prev); throw; }
@@ -564,9 +529,7 @@ void Engine::ensure_text_stream() {
 }
 
 int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
-    Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
-    Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
-    check_options(g);
+    validate(g);
     if (g.n_trail > 0 || g.open) ensure_text_stream();
     std::unique_ptr<Req> r(new Req());
     r->r = g;
@@ -618,35 +581,25 @@ void Engine::trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* 
     *n_appended = n; *n_consumed = std::min(r.fed, n); *closed = !r.r.open || r.closed;
 }
 
-// scheduler thread: appended ids and close flags of live open slots go into the host mirrors; the ids are uploaded by run_group
+// scheduler thread: appended ids and close flags of live open slots go into the slot table; the ids are uploaded by run_group
 void Engine::collect_appends() {
     std::lock_guard<std::mutex> lk(mu_);
     if (!trail_dirty_) return;
     trail_dirty_ = false;
     for (int b = 0; b < B_; b++) {
-        if (!slot_live_[b] || !slot_req_[b]->r.open) continue;
+        if (!slots_.live[b] || !slot_req_[b]->r.open) continue;
         const Req& r = *slot_req_[b];
+        int32_t& have = slots_.hi(SF_NTRAIL)[b]; int32_t& open = slots_.hi(SF_OPEN)[b];
         const int n = (int)r.trail_own.size();
-        if (n > h_ntrail_[b]) {
-            if (h_pend_[b].empty()) h_pend_off_[b] = h_ntrail_[b];
-            h_pend_[b].insert(h_pend_[b].end(), r.trail_own.begin() + h_ntrail_[b], r.trail_own.begin() + n);
-            h_ntrail_[b] = n;
+        if (n > have) {
+            if (h_pend_[b].empty()) h_pend_off_[b] = have;
+            h_pend_[b].insert(h_pend_[b].end(), r.trail_own.begin() + have, r.trail_own.begin() + n);
+            have = n;
             slot_dirty_ = true;
         }
         const int op = r.closed ? 0 : 1;
-        if (op != h_open_[b]) { h_open_[b] = op; slot_dirty_ = true; }
+        if (op != open) { open = op; slot_dirty_ = true; }
     }
-}
-
-// the host side of the device's stall predicate (the mirrors are exact between frame groups)
-bool Engine::all_live_stalled() const {
-    bool any = false;
-    for (int b = 0; b < B_; b++) {
-        if (!slot_live_[b]) continue;
-        any = true;
-        if (!(h_open_[b] && !h_fin_[b] && h_nfr_[b] < h_maxf_[b] && h_nfr_[b] >= h_ntrail_[b])) return false;
-    }
-    return any;
 }
 
 // moves queued requests into free slots (lowest slot first, so the live slots stay packed and a narrow graph suffices)
@@ -697,9 +650,8 @@ void Engine::admit(bool stalled) {
     arena_used_ = 0; // st_ is idle between scheduler operations
     for (Req* r : batch) kv_t_->release(r->slot), kv_t_->ensure(r->slot, r->r.n_prompt + r->r.max_steps + 1, st_);
     pf_batch_ = batch;
-    bool sampled = false;
+    bool sampled = live_variant(slots_).sampled; // of the prefill heads: the wave joins whatever is live
     for (Req* r : batch) if (r->r.sampler.temperature > 0.0f) sampled = true;
-    for (int b = 0; b < B_; b++) if (slot_live_[b] && slot_req_[b]->r.sampler.temperature > 0.0f) sampled = true;
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
     activate(); // slot state first: the prefill heads write code_0 / hidden straight into the live arrays
@@ -719,33 +671,26 @@ void Engine::admit(bool stalled) {
 // the wave sit in their own pinned arena); each sequence's last token leaves its logits row and hidden row in staging buffers.
 void Engine::prefill_async(const std::vector<Req*>& batch) {
     size_t total = 0;
+    std::vector<PromptRef> refs;
     for (Req* r : batch) {
-        total += (size_t)r->r.n_prompt;
+        total += (size_t)r->r.n_prompt; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot});
         kv_t_->release(r->slot);
         kv_t_->ensure(r->slot, r->r.n_prompt + r->r.max_steps + 1, st_pf_);
     }
     const int chunk = talker_pf_->max_tok();
     unsigned char* cur = arena_pf_;
-    size_t bi = 0; int t = 0, done_tok = 0;
+    PrefillCursor pc; std::vector<std::pair<int, int>> lasts; size_t done_tok = 0;
     Q3_HIP(hipEventRecord(pf_e0_, st_pf_));
     for (Req* r : batch) Q3_HIP(hipEventRecord(r->ev_admit, st_pf_));
     talker_pf_->set_same_seq_tokens(true);
-    while ((size_t)done_tok < total) {
+    while (done_tok < total) {
         const int n_max = (int)std::min<size_t>(total - done_tok, (size_t)chunk);
         float* stage = (float*)cur; cur += (size_t)n_max * Q3_EMBD * 4;
         int32_t* seq = (int32_t*)cur; cur += (size_t)n_max * 4;
         int32_t* slot = (int32_t*)cur; cur += (size_t)n_max * 4;
         int32_t* pos = (int32_t*)cur; cur += (size_t)n_max * 16;
         Q3_CHECK((size_t)(cur - arena_pf_) <= arena_pf_cap_, "prefill staging arena overflow");
-        int n = 0;
-        std::vector<std::pair<Req*, int>> lasts;
-        while (n < n_max && bi < batch.size()) {
-            Req* r = batch[bi];
-            std::copy(r->r.prompt + (size_t)t * Q3_EMBD, r->r.prompt + (size_t)(t + 1) * Q3_EMBD, stage + (size_t)n * Q3_EMBD);
-            seq[n] = r->slot; slot[n] = t; pos[4 * n] = pos[4 * n + 1] = pos[4 * n + 2] = t; pos[4 * n + 3] = 0; // engine.rs:306-314
-            if (t == r->r.n_prompt - 1) { lasts.emplace_back(r, n); bi++; t = 0; } else t++;
-            n++;
-        }
+        const int n = pack_prefill_chunk(refs, pc, n_max, stage, seq, slot, pos, lasts);
         Q3_HIP(hipMemcpyAsync(d_prompt_pf_.p, stage, (size_t)n * Q3_EMBD * 4, hipMemcpyHostToDevice, st_pf_));
         Q3_HIP(hipMemcpyAsync(d_pfa_seq_.p, seq, (size_t)n * 4, hipMemcpyHostToDevice, st_pf_));
         Q3_HIP(hipMemcpyAsync(d_pfa_slot_.p, slot, (size_t)n * 4, hipMemcpyHostToDevice, st_pf_));
@@ -754,7 +699,7 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
         Transformer::Input in; in.x = d_prompt_pf_.p; in.x_stride = Q3_EMBD;
         talker_pf_->forward(st_pf_, in, n, tm, kv_t_->view(), nullptr);
         for (auto& lb : lasts) { // logits + hidden of the LAST prompt token (engine.rs:550-554,565-566); code_0 is drawn at activation
-            const int sb = lb.first->slot;
+            const int sb = refs[lb.first].slot;
             talker_pf_->head(st_pf_, lb.second, 1, 0, tl_stride_, d_pf_logits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_pf_hidden_.p + (size_t)sb * Q3_EMBD);
         }
         done_tok += n;
@@ -772,42 +717,27 @@ void Engine::activate() {
     std::vector<Req*> batch;
     batch.swap(pf_batch_);
     arena_used_ = 0; // st_ is idle between scheduler operations
-    const q3_u64 armed[17] = {pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0),
-                              pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0),
-                              pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0), pack_key(-INFINITY, 0),
-                              pack_key(-INFINITY, 0), pack_key(-INFINITY, 0)};
+    q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
     const uint32_t zero = 0;
     for (Req* r : batch) {
         const int b = r->slot;
-        h_maxf_[b] = r->r.max_steps; h_fin_[b] = 0; h_nfr_[b] = 0; h_nprompt_[b] = r->r.n_prompt;
-        h_mask_[b] = r->r.mask_eos ? Q3_CODEC_EOS : -1;
-        h_temp_[b] = r->r.sampler.temperature; h_topk_[b] = r->r.sampler.top_k; h_topp_[b] = r->r.sampler.top_p;
+        slots_.load(b, r->r);
         StdRng rng(r->seed); // llama/mod.rs:648: the device regenerates this ChaCha12 stream from the key and a draw counter
         h2d(d_rngkey_.p + (size_t)b * 8, rng.key(), 32);
         h2d(d_draws_.p + b, &zero, 4);
-        const GenOptions& o = r->r.opts;
-        h_pen_[b] = o.repetition_penalty; h_ptemp_[b] = o.predictor_temperature; h_ptopk_[b] = o.predictor_top_k; h_ptopp_[b] = o.predictor_top_p;
-        if (o.penalised() || o.pred_sampled()) ext_used_ = true;
-        if (o.pred_sampled()) { // [EXT] the predictor's own stream: seed_from_u64(seed ^ Q3_PRED_SEED_XOR)
+        if (r->r.opts.pred_sampled()) { // [EXT] the predictor's own stream: seed_from_u64(seed ^ Q3_PRED_SEED_XOR)
             StdRng prng(r->seed ^ (uint64_t)Q3_PRED_SEED_XOR);
             h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
             h2d(d_pdraws_.p + b, &zero, 4);
         }
-        h_ntrail_[b] = r->r.n_trail; h_open_[b] = 0;
         h_pend_[b].clear();
-        if (r->r.open) { // [EXT] live text append: whatever has been appended so far (later ids: collect_appends)
-            trail_used_ = true;
-            std::vector<int32_t> ids;
-            { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_own; h_open_[b] = r->closed ? 0 : 1; }
-            h_ntrail_[b] = (int)ids.size();
-            if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
-        } else if (r->r.n_trail > 0) { // [EXT] streaming text: the slot's trailing ids; upload_slot_state below sends the count
-            trail_used_ = true;
-            h2d(d_trail_.p + (size_t)b * p_.max_prompt, r->r.trail, (size_t)r->r.n_trail * 4);
-        }
+        std::vector<int32_t> ids; // [EXT] streaming text: the slot's trailing ids -- of an open trail those appended so far (later: collect_appends)
+        { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_own; slots_.hi(SF_OPEN)[b] = r->r.open && !r->closed; }
+        slots_.hi(SF_NTRAIL)[b] = (int)ids.size(); // upload_slot_state below sends the count and the flag
+        if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
         h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);
         h2d(d_next_key0_.p + b, armed, 8);
-        slot_live_[b] = 1;
+        slots_.live[b] = 1;
     }
     upload_slot_state();
     if (n_prefilling_ > 0) { // the wave was prefilled on the second talker instance
@@ -817,8 +747,8 @@ void Engine::activate() {
         for (Req* r : batch) {
             const int b = r->slot;
             Q3_HIP(hipMemcpyAsync(d_thidden_.p + (size_t)b * Q3_EMBD, d_pf_hidden_.p + (size_t)b * Q3_EMBD, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_));
-            SampleArgs sa{d_pf_logits_.p + (size_t)b * tl_stride_, tl_stride_, Q3_SAMPLE_END, d_temp_.p + b, d_topk_.p + b, d_topp_.p + b,
-                          d_maskeos_.p + b, d_rngkey_.p + (size_t)b * 8, d_draws_.p + b, d_keys_.p + (size_t)b * 16, 16};
+            SampleArgs sa{d_pf_logits_.p + (size_t)b * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + b, di(SF_TOPK) + b, df(SF_TOPP) + b,
+                          di(SF_MASKEOS) + b, d_rngkey_.p + (size_t)b * 8, d_draws_.p + b, d_keys_.p + (size_t)b * 16, 16};
             launch_sample(st_, sa, 1);
         }
         Q3_HIP(hipStreamSynchronize(st_));
@@ -838,7 +768,7 @@ void Engine::finish_ar(Req* r) { // engine.rs:644-649: final flush of the chunke
     const int b = r->slot;
     {
         std::lock_guard<std::mutex> lk(mu_);
-        slot_req_[b] = nullptr; slot_live_[b] = 0; n_active_--;
+        slot_req_[b] = nullptr; slots_.live[b] = 0; n_active_--;
         r->slot = -1;
         if (r->want_pcm) { r->state = REQ_DRAINING; n_draining_++; }
         else { r->state = REQ_DONE; r->t_done = now_ms(); cv_.notify_all(); }
@@ -847,8 +777,7 @@ void Engine::finish_ar(Req* r) { // engine.rs:644-649: final flush of the chunke
         { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, {}, false, true, false}); dec_pending_++; }
         dcv_.notify_all();
     }
-    h_fin_[b] = 1; h_maxf_[b] = 0; h_nfr_[b] = 0; h_nprompt_[b] = 0; h_temp_[b] = 0.0f; h_mask_[b] = -1;
-    h_pen_[b] = 1.0f; h_ptemp_[b] = 0.0f; h_ntrail_[b] = 0; h_open_[b] = 0; h_pend_[b].clear();
+    slots_.reset(b); h_pend_[b].clear();
     kv_t_->release(b); // from the next group on the slot steps on the scratch sequence (upload_slot_state)
     slot_dirty_ = true;
 }
@@ -862,18 +791,10 @@ static int pick_width(int hi, int W) { // graph widths: powers of two (and the f
 // one streaming step (4 frames, engine.rs:505-512) for every active slot
 void Engine::run_group() {
     int hi = 0, remaining = 0;
-    bool sampled = false, pen = false, pred = false, trail = false, gate = false;
+    int32_t* h_nfr = slots_.hi(SF_NFRAMES); int32_t* h_fin = slots_.hi(SF_FINISHED);
     for (int b = 0; b < B_; b++)
-        if (slot_live_[b]) {
-            Req* r = slot_req_[b];
-            hi = b + 1;
-            remaining = std::max(remaining, r->r.max_steps - h_nfr_[b]);
-            if (r->r.sampler.temperature > 0.0f) sampled = true;
-            if (r->r.opts.penalised()) pen = true;
-            if (r->r.opts.pred_sampled()) pred = true;
-            if (r->r.n_trail > 0 || r->r.open) trail = true;
-            if (h_open_[b]) gate = trail = true;
-        }
+        if (slots_.live[b]) { hi = b + 1; remaining = std::max(remaining, slot_req_[b]->r.max_steps - h_nfr[b]); }
+    const FrameVariant v = live_variant(slots_);
     arena_used_ = 0; // st_ is idle between scheduler operations: everything staged earlier has been consumed
     for (int b = 0; b < B_; b++) // [EXT] appended ids collected since the last group: the new tail of the slot's id row
         if (!h_pend_[b].empty()) {
@@ -884,22 +805,22 @@ void Engine::run_group() {
     const int width = pick_width(hi, B_);
     const int group = std::max(1, std::min(4, remaining));
     const bool eager = instrument_ || !p_.use_graph;
-    FrameGraph& fg = frame_graph(width, sampled, pen, pred, trail, gate, !eager);
+    FrameGraph& fg = frame_graph(width, v, !eager);
     if (instrument_) { talker_->timer = &timer_; predictor_->timer = &timer_; talker_->timer_gu = &timer_gu_; }
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
     Q3_HIP(hipEventRecord(e0, st_));
     for (int g = 0; g < group; g++) {
-        if (eager) record_frame(fg, sampled, pen, pred, trail, gate);
+        if (eager) record_frame(fg, v);
         else Q3_HIP(hipGraphLaunch(fg.exec, st_));
     }
     Q3_HIP(hipEventRecord(e1, st_));
     // results of the group: frame counters, finished flags and the (at most `group`) new code rows of every active slot
-    const int32_t* p_nfr = (const int32_t*)d2h_begin(d_nframes_.p, (size_t)width * 4);
-    const int32_t* p_fin = (const int32_t*)d2h_begin(d_finished_.p, (size_t)width * 4);
+    const int32_t* p_nfr = (const int32_t*)d2h_begin(di(SF_NFRAMES), (size_t)width * 4);
+    const int32_t* p_fin = (const int32_t*)d2h_begin(di(SF_FINISHED), (size_t)width * 4);
     std::vector<const int32_t*> p_hist(width, nullptr);
     for (int b = 0; b < width; b++)
-        if (slot_live_[b]) {
+        if (slots_.live[b]) {
             Req* r = slot_req_[b];
             const int rows = std::min(group, r->r.max_steps - r->fed);
             if (rows > 0) p_hist[b] = (const int32_t*)d2h_begin(d_hist_.p + (size_t)b * hist_stride_ + (size_t)r->fed * 16, (size_t)rows * 64);
@@ -913,14 +834,14 @@ void Engine::run_group() {
         stats.gemv_ms += timer_.collect_ms(); stats.gemv_bytes += timer_.bytes; stats.gemv_launches += timer_.launches; timer_.bytes = 0; timer_.launches = 0;
         stats.gu_ms += timer_gu_.collect_ms(); stats.gu_bytes += timer_gu_.bytes; stats.gu_launches += timer_gu_.launches; timer_gu_.bytes = 0; timer_gu_.launches = 0;
     }
-    std::memcpy(h_nfr_.data(), p_nfr, (size_t)width * 4); std::memcpy(h_fin_.data(), p_fin, (size_t)width * 4);
+    std::memcpy(h_nfr, p_nfr, (size_t)width * 4); std::memcpy(h_fin, p_fin, (size_t)width * 4);
     for (int b = 0; b < width; b++) {
-        if (!slot_live_[b]) continue;
+        if (!slots_.live[b]) continue;
         Req* r = slot_req_[b];
-        if (h_nfr_[b] > r->fed) { // hand new frames to the chunker (engine.rs:613-620)
-            const int nnew = h_nfr_[b] - r->fed;
+        if (h_nfr[b] > r->fed) { // hand new frames to the chunker (engine.rs:613-620)
+            const int nnew = h_nfr[b] - r->fed;
             const int32_t* hbuf = p_hist[b];
-            { std::lock_guard<std::mutex> lk(mu_); r->codes.insert(r->codes.end(), hbuf, hbuf + (size_t)nnew * 16); r->fed = h_nfr_[b]; }
+            { std::lock_guard<std::mutex> lk(mu_); r->codes.insert(r->codes.end(), hbuf, hbuf + (size_t)nnew * 16); r->fed = h_nfr[b]; }
             for (int f = 0; f < nnew; f++) {
                 int64_t fc[16];
                 for (int q = 0; q < 16; q++) fc[q] = hbuf[(size_t)f * 16 + q];
@@ -928,7 +849,7 @@ void Engine::run_group() {
             }
             stats.frames += nnew;
         }
-        if (h_fin_[b] || h_nfr_[b] >= r->r.max_steps) finish_ar(r);
+        if (h_fin[b] || h_nfr[b] >= r->r.max_steps) finish_ar(r);
     }
 }
 
@@ -946,11 +867,11 @@ bool Engine::step() {
         if (hipEventQuery(pf_done_) == hipSuccess) activate();
     }
     collect_appends();
-    admit(n_active_ > 0 && all_live_stalled());
+    admit(n_active_ > 0 && slots_.all_live_stalled());
     const double t2 = now_ms();
     // [EXT] live text append: when every live slot waits for text, no frame group runs (graph_frames stays put); prefill and codec
     // work still proceed, and with none left the driver sleeps until a submit or an append
-    const bool stalled = n_active_ > 0 && all_live_stalled();
+    const bool stalled = n_active_ > 0 && slots_.all_live_stalled();
     int dec_pending = 0;
     if (stalled) { std::lock_guard<std::mutex> lk(dmu_); dec_pending = dec_pending_; }
     if (n_active_ > 0 && !stalled) run_group();
@@ -1080,12 +1001,7 @@ void Engine::generate_batch(const std::vector<GenRequest>& reqs, std::vector<Gen
     Q3_CHECK(n >= 1, "no requests");
     Q3_CHECK(!driver_on_, "generate_batch cannot be mixed with a running scheduler thread");
     out.assign(n, GenResult());
-    for (const GenRequest& g : reqs) { // validate everything before anything is queued
-        Q3_CHECK(g.prompt && g.n_prompt >= 1 && g.n_prompt <= p_.max_prompt, "prompt length out of range");
-        Q3_CHECK(g.max_steps >= 0 && g.max_steps <= p_.max_steps, "max_steps out of range");
-        check_options(g);
-        Q3_CHECK(!g.open, "open trails need the submit / append interface");
-    }
+    for (const GenRequest& g : reqs) { validate(g); Q3_CHECK(!g.open, "open trails need the submit / append interface"); } // before anything is queued
     for (const GenRequest& g : reqs) if (g.n_trail > 0) ensure_text_stream(); // the one step that can fail after validation: before queueing
     std::vector<int64_t> ids(n);
     for (int i = 0; i < n; i++) ids[i] = submit(reqs[i], want_pcm, false);

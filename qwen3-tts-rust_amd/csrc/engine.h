@@ -10,6 +10,7 @@
 #pragma once
 #include "transformer.h"
 #include "host_logic.h"
+#include "sched_logic.h"
 #include "codec.h"
 #include <condition_variable>
 #include <deque>
@@ -19,20 +20,6 @@
 #include <thread>
 
 namespace q3 {
-
-struct SamplerConfig { // engine.rs:13-45
-    float temperature = 0.7f; int top_k = 40; float top_p = 0.9f; bool has_seed = false; uint64_t seed = 0;
-};
-
-// [EXT] generation controls beyond the reference (q3tts_spec.h "Repetition penalty" / "Sampled code predictor"); defaults = reference
-struct GenOptions {
-    float repetition_penalty = 1.0f;    // talker code_0; 1 = off
-    float predictor_temperature = 0.0f; // <= 0: greedy predictor
-    int predictor_top_k = 0;            // 0 = disabled
-    float predictor_top_p = 1.0f;       // 1 = disabled
-    bool penalised() const { return repetition_penalty != 1.0f; }
-    bool pred_sampled() const { return predictor_temperature > 0.0f; }
-};
 
 struct EngineParams {
     std::string model_dir;      // contains <quant dir>/ and onnx/
@@ -44,17 +31,6 @@ struct EngineParams {
     bool use_graph = true;
 };
 
-struct GenRequest {
-    const float* prompt = nullptr; int n_prompt = 0; // [n_prompt][2048] host
-    SamplerConfig sampler;
-    int max_steps = Q3_DEFAULT_MAX_STEPS;
-    bool mask_eos = false;      // bench/test knob: exclude EOS so runs have a fixed length
-    GenOptions opts;
-    // [EXT] streaming-text talker input (q3tts_spec.h): trailing text ids, one per frame in the feedback; copied at submit
-    const int32_t* trail = nullptr; int n_trail = 0;
-    // [EXT] live text append (q3tts_spec.h): the trail stays open; frames past the appended ids wait until append_trail() brings more
-    bool open = false;
-};
 struct GenResult {
     std::vector<int32_t> codes; int n_frames = 0;
     std::vector<float> pcm;
@@ -125,12 +101,9 @@ private:
         int width = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         DevBuf<int32_t> seqA, slotA, posA;
     };
-    // enqueue one frame step for fg.width slots on st_; pen / pred: some live slot has a repetition penalty / samples the predictor
-    // trail: some live slot has trailing text ids (the feedback kernel's streaming-text variant replaces the plain one)
-    // gate: some live slot has an open trail (implies trail): k_stall_save first, the gated k_advance_keys last
-    void record_frame(FrameGraph& fg, bool sampled, bool pen, bool pred, bool trail, bool gate);
-    FrameGraph& frame_graph(int width, bool sampled, bool pen, bool pred, bool trail, bool gate, bool capture);
-    void check_options(const GenRequest& g) const;
+    void record_frame(FrameGraph& fg, FrameVariant v); // enqueue one frame step for fg.width slots on st_
+    FrameGraph& frame_graph(int width, FrameVariant v, bool capture);
+    void validate(const GenRequest& g) const; // prompt and max_steps ranges, then the options
     void ensure_text_stream(); // first request with trailing ids: text table + per-slot id rows go to the device
     void prefill(const std::vector<Req*>& batch, bool sampled);
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
@@ -140,12 +113,11 @@ private:
     void activate();
     void admit(bool stalled); // stalled: every live slot waits for text (the admission quantum is not waited for)
     void run_group();
-    void collect_appends();   // scheduler: new ids / close flags of live open slots into the host mirrors (upload in run_group)
-    bool all_live_stalled() const;
+    void collect_appends();   // scheduler: new ids / close flags of live open slots into the slot table (upload in run_group)
     void harvest(bool block);
     void finish_ar(Req* r);
     void decoder_main();
-    void upload_slot_state();
+    void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).
     void* stage_alloc(size_t bytes);
@@ -162,7 +134,6 @@ private:
     hipStream_t st_pf_ = nullptr; unsigned char* arena_pf_ = nullptr; size_t arena_pf_cap_ = 0;
     DevBuf<float> d_prompt_pf_, d_pf_logits_, d_pf_hidden_; DevBuf<int32_t> d_pfa_seq_, d_pfa_slot_, d_pfa_pos_;
     std::vector<Req*> pf_batch_; hipEvent_t pf_done_ = nullptr, pf_e0_ = nullptr; bool async_pf_ = false; int n_prefilling_ = 0;
-    std::vector<char> slot_live_;      // slot_req_[b] set = reserved; live = stepping inside the frame graph
     std::unique_ptr<KvPool> kv_t_, kv_p_;
     std::unique_ptr<CodecDecoder> codec_;
     // device assets
@@ -170,33 +141,25 @@ private:
     DevBuf<float> d_proj_wt_, d_proj_wblk_, d_proj_b_, d_tts_pad_;
     DevBuf<const float*> d_tab_ptrs_; DevBuf<int64_t> d_tab_rows_;
     int dP_ = 0;
-    // per-slot device state
-    int B_ = 0;
-    DevBuf<int32_t> d_tseq_, d_tslot_, d_tpos_, d_nframes_, d_finished_, d_maxframes_, d_hist_, d_maskeos_;
-    DevBuf<q3_u64> d_keys_, d_next_key0_; // argmax keys: [B][16] codes of the current frame, [B] code_0 of the next frame
-    DevBuf<float> d_temp_, d_topp_; DevBuf<int32_t> d_topk_; DevBuf<uint32_t> d_rngkey_, d_draws_; // device sampler state
-    // [EXT] GenOptions state: talker penalty, predictor sampler parameters, its ChaCha12 key and draw counter, the predictor logits rows
-    DevBuf<float> d_pen_, d_ptemp_, d_ptopp_, d_plogits_; DevBuf<int32_t> d_ptopk_; DevBuf<uint32_t> d_prngkey_, d_pdraws_;
+    // per-slot state: the mirrored scalars (slot_req_[b] set = reserved; slots_.live[b] = stepping inside the frame graph) ...
+    int B_ = 0; SlotTable slots_; DevBuf<uint32_t> d_slots_; bool slot_dirty_ = false; // dirty: the host block changed since upload_slot_state
+    int32_t* di(SlotField f) const { return slots_.di(f); } float* df(SlotField f) const { return slots_.df(f); }
+    // ... and what only the device keeps: code history, argmax keys ([B][16] codes of this frame, [B] code_0 of the next), the ChaCha12
+    // keys and draw counters of the talker sampler and of the [EXT] predictor sampler, the predictor logits rows
+    DevBuf<int32_t> d_hist_; DevBuf<q3_u64> d_keys_, d_next_key0_;
+    DevBuf<uint32_t> d_rngkey_, d_draws_, d_prngkey_, d_pdraws_; DevBuf<float> d_plogits_;
     DevBuf<int32_t> d_pseq_, d_pslot_, d_ppos_;
     DevBuf<float> d_tlogits_, d_thidden_, d_pin_, d_fb_, d_prompt_;
     DevBuf<int32_t> d_pf_seq_, d_pf_slot_, d_pf_pos_;
     int hist_stride_ = 0, tl_stride_ = 0;
-    // [EXT] streaming-text state, allocated by the first request with n_trail > 0: the text table, [B][max_prompt] trailing ids, [B] counts
-    DevBuf<float> d_text_; DevBuf<int32_t> d_trail_, d_ntrail_; int64_t text_rows_ = 0;
+    // [EXT] streaming-text state, allocated by the first request with n_trail > 0: the text table, [B][max_prompt] trailing ids
+    DevBuf<float> d_text_; DevBuf<int32_t> d_trail_; int64_t text_rows_ = 0;
     std::mutex text_mu_; bool text_ready_ = false; // text_ready_ is written under text_mu_ and capture_mutex()
-    // [EXT] live text append: [B] open flags and the stall save area ([B][2048] hidden rows, [B][2] draw counters), allocated with the above
-    DevBuf<int32_t> d_open_; DevBuf<float> d_stall_hidden_; DevBuf<uint32_t> d_stall_draws_;
-    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = width*32 + gate*16 + trail*8 + pred*4 + pen*2 + sampled
+    // [EXT] live text append: the stall save area ([B][2048] hidden rows, [B][2] draw counters), allocated with the above
+    DevBuf<float> d_stall_hidden_; DevBuf<uint32_t> d_stall_draws_;
+    std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = FrameVariant::key(width)
     bool instrument_ = false; bool pred_identity_pages_ = false;
-    // host mirrors of the slot state (refreshed from the device after every frame group)
-    std::vector<int32_t> h_maxf_, h_fin_, h_nfr_, h_mask_, h_nprompt_, h_topk_;
-    std::vector<float> h_temp_, h_topp_;
-    std::vector<float> h_pen_, h_ptemp_, h_ptopp_; std::vector<int32_t> h_ptopk_;
-    std::vector<int32_t> h_ntrail_, h_open_;
     std::vector<std::vector<int32_t>> h_pend_; std::vector<int> h_pend_off_; // appended ids not yet on the device: ids [off, off+size)
-    bool trail_used_ = false; // some activated request had trailing ids: upload_slot_state keeps d_ntrail_ current from then on
-    bool ext_used_ = false; // some request carried GenOptions: upload_slot_state keeps their device arrays current from then on
-    bool slot_dirty_ = false;
     // scheduler state
     std::mutex mu_; std::condition_variable cv_;
     std::mutex step_mu_;               // step() is driven by one thread at a time (driver thread, wait() callers, generate_batch)

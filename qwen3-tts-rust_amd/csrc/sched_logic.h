@@ -1,0 +1,120 @@
+// sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
+// the frame variant, the per-slot state table and the prefill chunk packer.  tests/test_sched_logic_cpu.py builds it with plain g++.
+#pragma once
+#include "../../include/q3tts_spec.h"
+#include <algorithm>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+namespace q3 {
+
+struct SamplerConfig { // engine.rs:13-45
+    float temperature = 0.7f; int top_k = 40; float top_p = 0.9f; bool has_seed = false; uint64_t seed = 0;
+};
+
+// [EXT] generation controls beyond the reference (q3tts_spec.h "Repetition penalty" / "Sampled code predictor"); defaults = reference
+struct GenOptions {
+    float repetition_penalty = 1.0f;    // talker code_0; 1 = off
+    float predictor_temperature = 0.0f; // <= 0: greedy predictor
+    int predictor_top_k = 0;            // 0 = disabled
+    float predictor_top_p = 1.0f;       // 1 = disabled
+    bool penalised() const { return repetition_penalty != 1.0f; }
+    bool pred_sampled() const { return predictor_temperature > 0.0f; }
+};
+
+struct GenRequest {
+    const float* prompt = nullptr; int n_prompt = 0; // [n_prompt][2048] host
+    SamplerConfig sampler;
+    int max_steps = Q3_DEFAULT_MAX_STEPS;
+    bool mask_eos = false;      // bench/test knob: exclude EOS so runs have a fixed length
+    GenOptions opts;
+    // [EXT] streaming-text talker input (q3tts_spec.h): trailing text ids, one per frame in the feedback; copied at submit
+    const int32_t* trail = nullptr; int n_trail = 0;
+    // [EXT] live text append (q3tts_spec.h): the trail stays open; frames past the appended ids wait until append_trail() brings more
+    bool open = false;
+};
+
+// Which launches one frame step issues: some live slot samples the talker / has a repetition penalty / samples the predictor / has trailing text
+// ids (trail: the feedback kernel's streaming-text variant) / has an open trail (gate, implies trail: k_stall_save first, the gated k_advance_keys last)
+struct FrameVariant {
+    bool sampled = false, pen = false, pred = false, trail = false, gate = false;
+    int key(int width) const { return width * 32 + gate * 16 + trail * 8 + pred * 4 + pen * 2 + sampled; } // of the frame-graph cache
+};
+
+// Every per-slot scalar the host mirrors, as one host block and one device block laid out [field][B] in 4-byte words (int32 or float), each
+// row padded to 64 bytes.  The talker routing rows (t_seq, t_slot, t_pos[B][4]) are derived by route(); the device advances them itself.
+enum SlotField { SF_TSEQ, SF_TSLOT, SF_TPOS, SF_FINISHED, SF_MAXFRAMES, SF_NFRAMES, SF_NPROMPT, SF_MASKEOS, SF_TEMP, SF_TOPK, SF_TOPP,
+                 SF_PEN, SF_PTEMP, SF_PTOPK, SF_PTOPP, SF_NTRAIL, SF_OPEN, SF_COUNT };
+struct SlotTable {
+    int B = 0, off[SF_COUNT + 1] = {0}; // off: first word of each row
+    std::vector<uint32_t> host; uint32_t* dev = nullptr; // dev: host.size() words the owner allocates once (captured graphs hold its addresses)
+    std::vector<char> live; std::vector<const GenRequest*> req; // live: the slot steps inside the frame graph, for the request load() saw
+    explicit SlotTable(int n = 0) : B(n), live(n, 0), req(n, nullptr) {
+        for (int f = 0; f < SF_COUNT; f++) off[f + 1] = off[f] + (((f == SF_TPOS ? 4 : 1) * B + 15) & ~15);
+        host.assign(off[SF_COUNT], 0); // padding stays zero
+        for (int b = 0; b < B; b++) reset(b);
+        route();
+    }
+    int32_t* hi(SlotField f) { return (int32_t*)(host.data() + off[f]); }
+    float* hf(SlotField f) { return (float*)(host.data() + off[f]); }
+    const int32_t* hi(SlotField f) const { return (const int32_t*)(host.data() + off[f]); }
+    int32_t* di(SlotField f) const { return (int32_t*)(dev + off[f]); }
+    float* df(SlotField f) const { return (float*)(dev + off[f]); }
+    void reset(int b) { // the idle slot: finished, nothing to step, neutral sampler parameters, no text
+        req[b] = nullptr;
+        hi(SF_FINISHED)[b] = 1; hi(SF_MAXFRAMES)[b] = hi(SF_NFRAMES)[b] = hi(SF_NPROMPT)[b] = 0; hi(SF_MASKEOS)[b] = -1;
+        hf(SF_TEMP)[b] = 0.0f; hi(SF_TOPK)[b] = 0; hf(SF_TOPP)[b] = 1.0f; hi(SF_NTRAIL)[b] = hi(SF_OPEN)[b] = 0;
+        hf(SF_PEN)[b] = 1.0f; hf(SF_PTEMP)[b] = 0.0f; hi(SF_PTOPK)[b] = 0; hf(SF_PTOPP)[b] = 1.0f;
+    }
+    void load(int b, const GenRequest& r) { // a slot about to go live (an open trail's count and flag: Engine::activate, under its lock)
+        req[b] = &r;
+        hi(SF_FINISHED)[b] = 0; hi(SF_MAXFRAMES)[b] = r.max_steps; hi(SF_NFRAMES)[b] = 0; hi(SF_NPROMPT)[b] = r.n_prompt;
+        hi(SF_MASKEOS)[b] = r.mask_eos ? Q3_CODEC_EOS : -1; hi(SF_NTRAIL)[b] = r.n_trail; hi(SF_OPEN)[b] = 0;
+        hf(SF_TEMP)[b] = r.sampler.temperature; hi(SF_TOPK)[b] = r.sampler.top_k; hf(SF_TOPP)[b] = r.sampler.top_p;
+        const GenOptions& o = r.opts;
+        hf(SF_PEN)[b] = o.repetition_penalty; hf(SF_PTEMP)[b] = o.predictor_temperature; hi(SF_PTOPK)[b] = o.predictor_top_k; hf(SF_PTOPP)[b] = o.predictor_top_p;
+    }
+    void route() { // a live slot steps at position n_prompt + n_frames of its own sequence, an idle one on the scratch sequence (row B)
+        for (int b = 0; b < B; b++) {
+            const int t = live[b] ? hi(SF_NPROMPT)[b] + hi(SF_NFRAMES)[b] : 0;
+            int32_t* pos = hi(SF_TPOS) + 4 * b;
+            hi(SF_TSEQ)[b] = live[b] ? b : B; hi(SF_TSLOT)[b] = pos[0] = pos[1] = pos[2] = t; pos[3] = 0;
+        }
+    }
+    // the host side of the device's stall predicate (the mirrors are exact between frame groups)
+    bool stalled(int b) const { const int f = hi(SF_NFRAMES)[b]; return hi(SF_OPEN)[b] && !hi(SF_FINISHED)[b] && f < hi(SF_MAXFRAMES)[b] && f >= hi(SF_NTRAIL)[b]; }
+    bool all_live_stalled() const {
+        bool any = false;
+        for (int b = 0; b < B; b++) if (live[b]) { if (!stalled(b)) return false; any = true; }
+        return any;
+    }
+};
+
+inline FrameVariant live_variant(const SlotTable& t) { // of the live batch
+    FrameVariant v;
+    for (int b = 0; b < t.B; b++) if (t.live[b]) {
+        const GenRequest& r = *t.req[b];
+        const bool open = t.hi(SF_OPEN)[b] != 0; // a closed trail leaves the gate, not the trail variant
+        v.sampled |= r.sampler.temperature > 0.0f; v.pen |= r.opts.penalised(); v.pred |= r.opts.pred_sampled();
+        v.trail |= r.n_trail > 0 || r.open || open; v.gate |= open;
+    }
+    return v;
+}
+
+// Prefill: the prompts of one admission wave form one token stream.  Fills one chunk of at most n_max tokens from the cursor on -- prompt rows,
+// per-token seq / slot / pos routing (engine.rs:306-314) -- and returns its token count; lasts = (request, index inside the chunk) of final prompt tokens.
+struct PromptRef { const float* rows; int n, slot; }; struct PrefillCursor { size_t req = 0; int tok = 0; };
+inline int pack_prefill_chunk(const std::vector<PromptRef>& batch, PrefillCursor& c, int n_max, float* stage, int32_t* seq, int32_t* slot,
+                              int32_t* pos, std::vector<std::pair<int, int>>& lasts) {
+    int n = 0;
+    for (lasts.clear(); n < n_max && c.req < batch.size(); n++) {
+        const PromptRef& r = batch[c.req];
+        std::copy(r.rows + (size_t)c.tok * Q3_EMBD, r.rows + (size_t)(c.tok + 1) * Q3_EMBD, stage + (size_t)n * Q3_EMBD);
+        seq[n] = r.slot; slot[n] = c.tok; pos[4 * n] = pos[4 * n + 1] = pos[4 * n + 2] = c.tok; pos[4 * n + 3] = 0;
+        if (c.tok == r.n - 1) { lasts.emplace_back((int)c.req, n); c.req++; c.tok = 0; } else c.tok++;
+    }
+    return n;
+}
+
+} // namespace q3
