@@ -249,12 +249,7 @@ static void lin_run(q3tts_linear_desc* dp) {
         launch_tile_float(0, fw.p, fwt.p, d.type[0], n, K);
         fm.w = fw.p; fm.wt = fwt.p; fm.type = d.type[0]; fm.N = n; fm.K = K;
     } else if (d.op != LOP_NORM) {
-        if (!lin_kq(d)) m = q8mat_from_host(d.raw[0], d.rows[0], K, storage);
-        else {
-            KqPart parts[3];
-            for (int i = 0; i < d.nw; i++) parts[i] = KqPart{d.raw[i], d.type[i], d.rows[i]};
-            m = kqmat_from_host(parts, d.nw, K, storage);
-        }
+        m = lin_kq(d) ? kqmat_from_host(d.raw, d.type, d.rows, d.nw, K, storage) : q8mat_from_host(d.raw[0], d.rows[0], K, storage);
     }
     // inputs
     DevBuf<int8_t> dxq; DevBuf<uint16_t> dxd; DevBuf<float> dx, dh, dparts, dg, dhout, dxn, dout, dgu;
@@ -296,11 +291,7 @@ static void lin_run(q3tts_linear_desc* dp) {
     }
     case LIN_NORM: {
         dxq_out.alloc((size_t)nt * K); dxq_out.upload(d.xq_out, dxq_out.n); dxd_out.alloc((size_t)nt * (K / 32)); dxd_out.upload(d.xd_out, dxd_out.n);
-        NormArgs na{};
-        na.h_in = a.h_in; na.h_stride = a.h_stride; na.idx = didx.p; na.idx_stride = d.idx_stride; na.idx_keys = a.idx_keys; na.parts = a.parts;
-        na.nparts = a.nparts; na.parts_stride = a.parts_stride; na.h_out = a.h_out; na.g = a.g; na.eps = a.eps; na.d = K; na.xq = dxq_out.p; na.xd = dxd_out.p;
-        na.xn_out = a.xn_out;
-        launch_rmsnorm_quant(0, na, nt);
+        launch_rmsnorm_quant(0, norm_args(a, K, dxq_out.p, dxd_out.p, didx.p), nt);
         break;
     }
     case LIN_NORM_WG:
@@ -434,11 +425,9 @@ int q3tts_op_gemv_kq(const void* const* raws, const int32_t* types, const int32_
     Q3_API_BEGIN
     require_gpu();
     Q3_CHECK(raws && types && rows && nparts >= 1 && nparts <= 3 && xq && xd && y && ntok >= 1 && k % 256 == 0, "bad K-quant gemv arguments");
-    KqPart parts[3];
-    int n = 0;
-    for (int i = 0; i < nparts; i++) { parts[i] = KqPart{raws[i], types[i], rows[i]}; n += rows[i]; }
     DevBuf<uint8_t> storage;
-    Q8Mat m = kqmat_from_host(parts, nparts, k, storage);
+    Q8Mat m = kqmat_from_host(raws, types, rows, nparts, k, storage);
+    const int n = m.N;
     DevBuf<int8_t> dxq((size_t)ntok * k); dxq.upload(xq, dxq.n);
     DevBuf<uint16_t> dxd((size_t)ntok * (k / 32)); dxd.upload(xd, dxd.n);
     const int nsseg = ((k >> 8) + 7) / 8;
@@ -462,9 +451,9 @@ int q3tts_op_gateup_kq(const void* gate_raw, const void* up_raw, int32_t type, i
     Q3_API_BEGIN
     require_gpu();
     Q3_CHECK(gate_raw && up_raw && xq && xd && aq && ad && ff > 0 && ff % 32 == 0 && k % 256 == 0 && ntok >= 1, "bad gate/up shape");
-    KqPart parts[2] = {KqPart{gate_raw, type, ff}, KqPart{up_raw, type, ff}};
+    const void* raws[2] = {gate_raw, up_raw}; const int32_t types[2] = {type, type}, rows[2] = {ff, ff};
     DevBuf<uint8_t> storage;
-    Q8Mat m = kqmat_from_host(parts, 2, k, storage);
+    Q8Mat m = kqmat_from_host(raws, types, rows, 2, k, storage);
     DevBuf<int8_t> dxq((size_t)ntok * k); dxq.upload(xq, dxq.n);
     DevBuf<uint16_t> dxd((size_t)ntok * (k / 32)); dxd.upload(xd, dxd.n);
     DevBuf<int8_t> daq((size_t)ntok * ff); DevBuf<uint16_t> dad((size_t)ntok * (ff / 32));

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "wlayout.h"
 
 namespace q3 {
 
@@ -33,8 +34,7 @@ struct Q8Mat {
     int nparts = 0; int p1_rg0 = 0x7fffffff, p2_rg0 = 0x7fffffff; int p0_type = 0, p1_type = 0, p2_type = 0; uint32_t p0_off = 0, p1_off = 0, p2_off = 0;
     size_t bytes() const { return (qbytes ? qbytes : (size_t)Npad * K) + (size_t)Npad * (K / 32) * 2 + (meta ? (size_t)Npad * (K / 256) * 16 : 0); }
 };
-// bytes of one 32-row group of K columns in HBM, by ggml type (8 = Q8_0, 13 = Q5_K, 14 = Q6_K)
-inline size_t q3_rowgroup_bytes(int type, int K) { return type == 13 ? (size_t)(K / 256) * 5120 : type == 14 ? (size_t)(K / 256) * 6144 : (size_t)(K / 32) * 1024; }
+// (row-group sizes, section order and the tensor map: wlayout.h)
 
 // Per-token routing for batched steps (one entry per token row of the activation matrix)
 struct TokMeta {
@@ -144,6 +144,10 @@ struct ArgmaxEpi {
 void launch_gemv_q8_norm(hipStream_t st, const Q8Mat& w, int row0, int nrows, const NormPro& a, float* out, int out_stride,
                          int ntok, const ArgmaxEpi* am);
 void launch_rmsnorm_quant_wg(hipStream_t st, const NormPro& a, int d, int8_t* xq, uint16_t* xd, int ntok);
+// the same norm as k_rmsnorm_quant's arguments: slabs are ntok * parts_stride apart there, and the row index may be a plain int32 (idx)
+inline NormArgs norm_args(const NormPro& p, int d, int8_t* xq, uint16_t* xd, const int32_t* idx = nullptr) {
+    return NormArgs{p.h_in, p.h_stride, idx, p.idx_stride, p.idx_keys, p.parts, p.nparts, p.parts_stride, p.h_out, p.g, p.eps, d, xq, xd, p.xn_out};
+}
 void launch_gateup_swiglu(hipStream_t st, const Q8Mat& wgu, int ff, const NormPro& a, int8_t* aq, uint16_t* ad, int ntok);
 void launch_attention_fused(hipStream_t st, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,

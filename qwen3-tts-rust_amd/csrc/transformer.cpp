@@ -96,151 +96,59 @@ __global__ void k_repack_q6k(const uint8_t* __restrict__ raw, int n, int K, int 
     }
 }
 
-Q8Mat q8mat_from_host(const void* raw_q8_0, int n, int k, DevBuf<uint8_t>& storage) {
-    Q3_CHECK(k % 256 == 0 && n > 0, "bad Q8_0 matrix shape");
+// The one device builder: allocates and zeroes the blob wlayout.h planned, uploads the row-group map of a mapped matrix and repacks every tensor
+// (raw[i] = host GGUF rows of L.tensors[i]) into its row groups.
+Q8Mat build_q8mat(const WLayout& L, const void* const* raw, DevBuf<uint8_t>& blob) {
+    blob.alloc(L.total());
+    blob.zero();
+    uint8_t* base = blob.p;
+    uint16_t* sc = reinterpret_cast<uint16_t*>(base + L.sc_at());
+    uint8_t* meta = base + L.meta_at();
+    uint32_t* off = reinterpret_cast<uint32_t*>(base + L.off_at());
     Q8Mat m;
-    m.N = n; m.Npad = (n + 31) & ~31; m.K = k;
-    const size_t qs_bytes = (size_t)m.Npad * k, sc_bytes = (size_t)m.Npad * (k / 32) * 2;
-    storage.alloc(qs_bytes + sc_bytes);
-    storage.zero();
-    m.qs = storage.p;
-    m.sc = reinterpret_cast<const uint16_t*>(storage.p + qs_bytes);
-    const size_t raw_bytes = (size_t)n * (k / 32) * 34;
-    DevBuf<uint8_t> raw(raw_bytes);
-    raw.upload((const uint8_t*)raw_q8_0, raw_bytes);
-    const size_t nblk = (size_t)n * (k / 32);
-    hipLaunchKernelGGL(k_repack_q8, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, 0, raw.p, n, k, 0, storage.p,
-                       reinterpret_cast<uint16_t*>(storage.p + qs_bytes), 0);
-    Q3_HIP(hipDeviceSynchronize());
-    return m;
-}
-
-Q8Mat kqmat_from_host(const KqPart* parts, int nparts, int k, DevBuf<uint8_t>& storage) {
-    Q3_CHECK(parts && nparts >= 1 && nparts <= 3 && k % 256 == 0, "bad K-quant matrix description");
-    Q8Mat m;
-    int n = 0;
-    for (int i = 0; i < nparts; i++) { Q3_CHECK(parts[i].rows > 0 && parts[i].rows % 32 == 0, "tensor rows must be a multiple of 32"); n += parts[i].rows; }
-    m.N = n; m.Npad = n; m.K = k;
-    const int nrg = n / 32;
-    std::vector<uint8_t> types((size_t)nrg);
-    std::vector<uint32_t> off((size_t)nrg);
-    size_t qs_bytes = 0;
-    { int rg = 0; for (int i = 0; i < nparts; i++) for (int j = 0; j < parts[i].rows / 32; j++, rg++) { types[(size_t)rg] = (uint8_t)parts[i].type; off[(size_t)rg] = (uint32_t)(qs_bytes / 16); qs_bytes += q3_rowgroup_bytes(parts[i].type, k); } }
-    const size_t sc_bytes = (size_t)n * (k / 32) * 2, meta_bytes = (size_t)n * (k / 256) * 16, ty_bytes = (size_t)((nrg + 15) & ~15), off_bytes = (size_t)((nrg * 4 + 15) & ~15);
-    storage.alloc(qs_bytes + sc_bytes + meta_bytes + ty_bytes + off_bytes);
-    storage.zero();
-    uint8_t* base = storage.p;
-    uint16_t* sc = reinterpret_cast<uint16_t*>(base + qs_bytes);
-    uint8_t* meta = base + qs_bytes + sc_bytes;
-    uint8_t* ty = meta + meta_bytes;
-    uint32_t* offd = reinterpret_cast<uint32_t*>(ty + ty_bytes);
-    Q3_HIP(hipMemcpy(ty, types.data(), types.size(), hipMemcpyHostToDevice));
-    Q3_HIP(hipMemcpy(offd, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    m.qs = base; m.sc = sc; m.meta = meta; m.rg_type = ty; m.rg_off = offd; m.qbytes = qs_bytes;
-    int last = -1, row_off = 0;
-    for (int i = 0; i < nparts; i++) {
-        const int t = parts[i].type, rows = parts[i].rows;
-        Q3_CHECK(t == Q3_T_Q8_0 || t == Q3_T_Q5_K || t == Q3_T_Q6_K, "unsupported weight type");
-        if (t != last) {
-            const int rg0 = row_off / 32;
-            if (m.nparts == 0) { m.p0_type = t; m.p0_off = off[(size_t)rg0]; }
-            else if (m.nparts == 1) { m.p1_rg0 = rg0; m.p1_type = t; m.p1_off = off[(size_t)rg0]; }
-            else { m.p2_rg0 = rg0; m.p2_type = t; m.p2_off = off[(size_t)rg0]; }
-            m.nparts++; last = t;
-        }
-        const size_t raw_bytes = t == Q3_T_Q8_0 ? (size_t)rows * (k / 32) * 34 : (size_t)rows * (k / 256) * (t == Q3_T_Q5_K ? 176 : 210);
-        DevBuf<uint8_t> raw(raw_bytes);
-        raw.upload((const uint8_t*)parts[i].raw, raw_bytes);
-        if (t == Q3_T_Q8_0) {
-            const size_t nblk = (size_t)rows * (k / 32);
-            hipLaunchKernelGGL(k_repack_q8, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, 0, raw.p, rows, k, 0, base + (size_t)off[(size_t)(row_off / 32)] * 16, sc, row_off);
-        } else {
-            const size_t nsb = (size_t)rows * (k / 256);
-            if (t == Q3_T_Q5_K) hipLaunchKernelGGL(k_repack_q5k, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, 0, raw.p, rows, k, row_off, base, offd, sc, meta);
-            else hipLaunchKernelGGL(k_repack_q6k, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, 0, raw.p, rows, k, row_off, base, offd, sc, meta);
-        }
+    m.N = L.N; m.Npad = L.Npad; m.K = L.K; m.qs = base; m.sc = sc;
+    if (L.mapped) {
+        Q3_HIP(hipMemcpy(base + L.ty_at(), L.rg_type.data(), L.rg_type.size(), hipMemcpyHostToDevice));
+        Q3_HIP(hipMemcpy(off, L.rg_off.data(), L.rg_off.size() * 4, hipMemcpyHostToDevice));
+        m.meta = meta; m.rg_type = base + L.ty_at(); m.rg_off = off; m.qbytes = L.qbytes;
+        m.nparts = L.nparts; m.p1_rg0 = L.p1_rg0; m.p2_rg0 = L.p2_rg0; m.p0_type = L.p0_type; m.p1_type = L.p1_type; m.p2_type = L.p2_type;
+        m.p0_off = L.p0_off; m.p1_off = L.p1_off; m.p2_off = L.p2_off;
+    }
+    for (size_t i = 0; i < L.tensors.size(); i++) {
+        const WTensor& t = L.tensors[i];
+        const size_t raw_bytes = (size_t)t.rows * q3_gguf_row_bytes(t.type, L.K);
+        DevBuf<uint8_t> d(raw_bytes);
+        d.upload((const uint8_t*)raw[i], raw_bytes);
+        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 ? 32 : 256));
+        const dim3 grid((unsigned)((nblk + 255) / 256));
+        // Q8_0 tiles are laid out the same in both layouts: the kernel is based on the tensor's first row group and counts rows from there
+        if (t.type == Q3_T_Q8_0) hipLaunchKernelGGL(k_repack_q8, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0 & 31, base + (size_t)L.rg_off[(size_t)(t.row0 / 32)] * 16, sc, t.row0 & ~31);
+        else if (t.type == Q3_T_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
+        else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         Q3_HIP(hipDeviceSynchronize());
-        row_off += rows;
     }
     return m;
 }
+Q8Mat q8mat_from_host(const void* raw_q8_0, int n, int k, DevBuf<uint8_t>& storage) { return build_q8mat(plan_wlayout({{Q3_T_Q8_0, 0, n}}, n, k, false), &raw_q8_0, storage); }
+Q8Mat kqmat_from_host(const void* const* raw, const int32_t* types, const int32_t* rows, int nw, int k, DevBuf<uint8_t>& storage) {
+    std::vector<WTensor> t;
+    int n = 0;
+    for (int i = 0; i < nw; i++) { t.push_back({types[i], n, rows[i]}); n += rows[i]; }
+    return build_q8mat(plan_wlayout(t, n, k, true), raw, storage);
+}
 
 Q8Mat Transformer::make_mat(const Gguf& g, const std::vector<std::pair<std::string, int>>& rows, int N, int K) {
-    Q3_CHECK(K % 256 == 0, "K must be a multiple of 256");
-    Q8Mat m;
-    m.N = N; m.Npad = (N + 31) & ~31; m.K = K;
-    const int nrg = m.Npad / 32;
-    // the tensors of the fused matrix decide the storage of every 32-row group (Q8_0 tiles or packed K-quant planes)
-    std::vector<uint8_t> types((size_t)nrg, (uint8_t)Q3_T_Q8_0);
-    bool kq = false;
+    std::vector<WTensor> tensors; std::vector<const void*> raw;
     for (auto& r : rows) {
         const GgufTensor& t = g.need(r.first);
         if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K)
             throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q5_K, Q6_K)");
-        Q3_CHECK(r.second % 32 == 0 && t.ne[1] % 32 == 0 && r.second + t.ne[1] <= m.Npad, "bad row range for " + r.first);
-        for (int64_t i = 0; i < t.ne[1] / 32; i++) types[(size_t)(r.second / 32 + i)] = (uint8_t)t.type;
-        kq = kq || t.type != Q3_T_Q8_0;
+        Q3_CHECK(t.ne[0] == K, "unexpected K for " + r.first);
+        tensors.push_back({t.type, r.second, (int)t.ne[1]}); raw.push_back(t.data);
     }
-    std::vector<uint32_t> off((size_t)nrg);
-    size_t qs_bytes = 0;
-    for (int i = 0; i < nrg; i++) { off[(size_t)i] = (uint32_t)(qs_bytes / 16); qs_bytes += q3_rowgroup_bytes(kq ? types[(size_t)i] : Q3_T_Q8_0, K); }
-    Q3_CHECK(qs_bytes / 16 < (1ull << 32), "matrix too large for 32-bit row-group offsets");
-    const size_t sc_bytes = (size_t)m.Npad * (K / 32) * 2;
-    const size_t meta_bytes = kq ? (size_t)m.Npad * (K / 256) * 16 : 0, ty_bytes = (size_t)((nrg + 15) & ~15), off_bytes = kq ? (size_t)((nrg * 4 + 15) & ~15) : 0;
-    blobs_.emplace_back(qs_bytes + sc_bytes + meta_bytes + ty_bytes + off_bytes);
-    blobs_.back().zero();
-    uint8_t* base = blobs_.back().p;
-    m.qs = base;
-    m.sc = reinterpret_cast<const uint16_t*>(base + qs_bytes);
-    mat_meta_[m.qs] = base + qs_bytes + sc_bytes;
-    mat_types_[m.qs] = base + qs_bytes + sc_bytes + meta_bytes;
-    mat_off_[m.qs] = reinterpret_cast<uint32_t*>(base + qs_bytes + sc_bytes + meta_bytes + ty_bytes);
-    if (kq) {
-        Q3_HIP(hipMemcpy(mat_types_[m.qs], types.data(), types.size(), hipMemcpyHostToDevice));
-        Q3_HIP(hipMemcpy(mat_off_[m.qs], off.data(), off.size() * 4, hipMemcpyHostToDevice));
-        m.meta = mat_meta_[m.qs]; m.rg_type = mat_types_[m.qs]; m.rg_off = mat_off_[m.qs]; m.qbytes = qs_bytes;
-        all_q8_ = false;
-        // tensor map for the kernel arguments: runs of equal type (rows not covered by a tensor stay Q8_0-typed zero tiles)
-        int last = -1;
-        for (int i = 0; i < nrg; i++) {
-            if (last == types[(size_t)i]) continue;
-            last = types[(size_t)i];
-            Q3_CHECK(m.nparts < 3, "more than 3 runs of weight types in one fused matrix");
-            if (m.nparts == 0) { m.p0_type = last; m.p0_off = off[(size_t)i]; }
-            else if (m.nparts == 1) { m.p1_rg0 = i; m.p1_type = last; m.p1_off = off[(size_t)i]; }
-            else { m.p2_rg0 = i; m.p2_type = last; m.p2_off = off[(size_t)i]; }
-            m.nparts++;
-        }
-    }
-    for (auto& r : rows) load_into(g, r.first, m, r.second, K);
-    return m;
-}
-
-void Transformer::load_into(const Gguf& g, const std::string& name, Q8Mat& dst, int row_off, int K_expect) {
-    const GgufTensor& t = g.need(name);
-    Q3_CHECK(t.ne[0] == K_expect, "unexpected K for " + name);
-    DevBuf<uint8_t> raw(t.nbytes);
-    raw.upload(t.data, t.nbytes);
-    uint8_t* qs = const_cast<uint8_t*>(dst.qs);
-    uint16_t* sc = const_cast<uint16_t*>(dst.sc);
-    if (t.type == Q3_T_Q8_0) {
-        const size_t nblk = (size_t)t.ne[1] * (t.ne[0] / 32);
-        // in a K-quant matrix the Q8_0 row groups start at their own offsets; the tile layout inside a row group is the same
-        uint8_t* q0 = qs;
-        int ro = row_off;
-        if (dst.rg_off) { // row groups of one tensor are contiguous: rebase on the first one
-            uint32_t o = 0;
-            Q3_HIP(hipMemcpy(&o, dst.rg_off + row_off / 32, 4, hipMemcpyDeviceToHost));
-            q0 = qs + (size_t)o * 16; ro = 0;
-        }
-        hipLaunchKernelGGL(k_repack_q8, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, 0, raw.p, (int)t.ne[1], (int)t.ne[0], ro, q0, sc, row_off - ro);
-    } else {
-        const size_t nsb = (size_t)t.ne[1] * (t.ne[0] / 256);
-        uint8_t* meta = mat_meta_.at(dst.qs);
-        if (t.type == Q3_T_Q5_K) hipLaunchKernelGGL(k_repack_q5k, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, 0, raw.p, (int)t.ne[1], (int)t.ne[0], row_off, qs, dst.rg_off, sc, meta);
-        else hipLaunchKernelGGL(k_repack_q6k, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, 0, raw.p, (int)t.ne[1], (int)t.ne[0], row_off, qs, dst.rg_off, sc, meta);
-    }
-    Q3_HIP(hipDeviceSynchronize());
+    const WLayout L = plan_wlayout(tensors, N, K, false);
+    blobs_.emplace_back();
+    return build_q8mat(L, raw.data(), blobs_.back());
 }
 
 FMat Transformer::make_fmat(const Gguf& g, const std::vector<std::string>& names, int K_expect) {
@@ -388,7 +296,7 @@ int Transformer::attention_form(int ntok) const {
 // second context over the same weights: see transformer.h
 Transformer::Transformer(const Transformer& o, int max_tok)
     : fused(o.fused), float_mode_(o.float_mode_), foutput_(o.foutput_), hp_(o.hp_), n_ctx_(o.n_ctx_), max_tok_(max_tok), layers_(o.layers_), output_(o.output_),
-      output_norm_(o.output_norm_), ws_(o.ws_), weight_bytes_(o.weight_bytes_), layer_weight_bytes_(o.layer_weight_bytes_), all_q8_(o.all_q8_),
+      output_norm_(o.output_norm_), ws_(o.ws_), weight_bytes_(o.weight_bytes_), layer_weight_bytes_(o.layer_weight_bytes_),
       ggml_mode_(o.ggml_mode_), gg_layers_(o.gg_layers_), gg_output_(o.gg_output_) {
     alloc_workspace();
 }
@@ -417,7 +325,7 @@ GgMat Transformer::gg_load(const Gguf& g, const std::string& name, int n_expect,
     Q3_CHECK((int)t.ne[0] == k_expect && (int)t.ne[1] == n_expect, "ggml mode: shape of " + name);
     Q3_CHECK(t.type == Q3_T_Q8_0 || t.type == Q3_T_Q5_K || t.type == Q3_T_Q6_K, "ggml mode: type of " + name);
     GgMat m; m.type = t.type; m.n = n_expect; m.k = k_expect;
-    m.row_bytes = t.type == Q3_T_Q8_0 ? (size_t)(k_expect / 32) * 34 : t.type == Q3_T_Q5_K ? (size_t)(k_expect / 256) * 176 : (size_t)(k_expect / 256) * 210;
+    m.row_bytes = q3_gguf_row_bytes(t.type, k_expect);
     blobs_.emplace_back(m.row_bytes * (size_t)n_expect);
     blobs_.back().upload(reinterpret_cast<const uint8_t*>(t.data), m.row_bytes * (size_t)n_expect);
     m.p = blobs_.back().p;
@@ -429,7 +337,7 @@ void Transformer::gg_linear(hipStream_t st, const GgMat& w, int row0, int nrows,
 }
 void Transformer::forward_ggml(hipStream_t st, const Input& in, int ntok, const TokMeta& tm, const KvCache& kv, float* hidden_out) {
     const int d = hp_.n_embd, dq = hp_.n_head * 128, dkv = hp_.n_kv * 128, ff = hp_.n_ff, qs = dq + 2 * dkv;
-    gg_load_rows(st, in.x, in.x_stride, in.idx, in.idx_stride, in.idx_keys, d, h_.p, ntok);
+    gg_load_rows(st, in.x, in.x_stride, nullptr, in.idx_stride, in.idx_keys, d, h_.p, ntok);
     for (int l = 0; l < hp_.n_layer; l++) {
         const Layer& L = layers_[l];
         const GgLayer& G = gg_layers_[l];
@@ -456,159 +364,113 @@ void Transformer::forward_ggml(hipStream_t st, const Input& in, int ntok, const 
 }
 
 
+// one launch (or none) bracketed by the optional event timer, accounted as `bytes` of weight traffic
+template <class F> static void timed(LaunchTimer* t, hipStream_t st, double bytes, F&& launch) {
+    if (t) t->begin(st);
+    launch();
+    if (t) t->end(st, bytes);
+}
+
 void Transformer::gemv(hipStream_t st, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd, float* out,
                        int out_stride, int ntok) {
-    if (timer) timer->begin(st);
-    launch_gemv_q8(st, w, row0, nrows, xq, xd, out, out_stride, ntok);
-    if (timer) timer->end(st, (double)nrows * ((double)w.K + (double)(w.K / 32) * 2.0));
+    timed(timer, st, (double)nrows * ((double)w.K + (double)(w.K / 32) * 2.0), [&] { launch_gemv_q8(st, w, row0, nrows, xq, xd, out, out_stride, ntok); });
+}
+
+// ---- the layer walk: forward() runs every non-ggml path through these steps; each picks its launch from the Pass ----
+void Transformer::norm(const Pass& s, const NormPro& a) {
+    if (s.wgnorm) launch_rmsnorm_quant_wg(s.st, a, hp_.n_embd, xq_.p, xd_.p, s.ntok); // batched steps: workgroup-per-token kernel (same arithmetic, one global round trip)
+    else launch_rmsnorm_quant(s.st, norm_args(a, hp_.n_embd, xq_.p, xd_.p), s.ntok);  // (the int8 copy is unused in float mode)
+}
+
+// out[ntok][N] (super-segment slabs when quantised) = the whole matrix times the step's activations: int8 blocks, or f32 rows in float mode
+void Transformer::linear(const Pass& s, const Q8Mat& w, const FMat& fw, const float* xf, const int8_t* xq, const uint16_t* xd, float* out) {
+    if (float_mode_) timed(timer, s.st, (double)fw.bytes(), [&] { launch_gemv_float(s.st, fw, 0, fw.N, xf, fw.K, out, fw.N, s.ntok); });
+    else gemv(s.st, w, 0, w.N, xq, xd, out, w.N, s.ntok);
+}
+
+void Transformer::qkv(const Pass& s, const Layer& L, const NormPro& a) {
+    if (!s.fused) { norm(s, a); linear(s, L.wqkv, L.fqkv, xnf_.p, xq_.p, xd_.p, qkv_.p); return; }
+    timed(timer, s.st, (double)L.wqkv.bytes(), [&] { launch_gemv_q8_norm(s.st, L.wqkv, 0, L.wqkv.N, a, qkv_.p, L.wqkv.N, s.ntok, nullptr); });
+}
+
+void Transformer::attention(const Pass& s, const Layer& L, int l) {
+    const int qs = (hp_.n_head + 2 * hp_.n_kv) * 128;
+    float* att = float_mode_ ? attf_.p : nullptr; // f32 rows for the float o-projection; the int8 copy (aq_, ad_) is always written
+    if (s.af == ATTN_SHORT1 || s.af == ATTN_SHORT2)
+        launch_attention_short(s.st, s.af == ATTN_SHORT1 ? 1 : 2, qkv_.p, qs, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
+                               n_ctx_, d_mrope_.p, s.tm, s.kv, l, aq_.p, ad_.p, s.ntok, att);
+    else if (s.af == ATTN_FUSED)
+        launch_attention_fused(s.st, qkv_.p, qs, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p, s.tm,
+                               s.kv, l, aq_.p, ad_.p, s.ntok);
+    else {
+        launch_qk_rope_append(s.st, qkv_.p, qs, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p,
+                              s.tm, s.kv, l, qrot_.p, s.ntok);
+        launch_attention(s.st, qrot_.p, hp_.n_head, hp_.n_kv, s.tm, s.kv, l, att, aq_.p, ad_.p, s.ntok);
+    }
+}
+
+// ffn norm + gate/up + SwiGLU -> the down-projection's activations (fq_ / fd_, or actf_ in float mode)
+void Transformer::gate_up(const Pass& s, const Layer& L, const NormPro& b) {
+    const int d = hp_.n_embd, ff = hp_.n_ff;
+    LaunchTimer* tg = timer_gu ? timer_gu : timer; // the talker's gate/up launch is timed on its own (bench roofline kernel)
+    const double bytes = float_mode_ ? (double)L.fgu.bytes() : (double)L.wgu.bytes();
+    if (s.fused) { timed(tg, s.st, bytes, [&] { launch_gateup_swiglu(s.st, L.wgu, ff, b, fq_.p, fd_.p, s.ntok); }); return; }
+    norm(s, b);
+    LinearPlanIn in; // plan first, then run: a fused gate/up form, or the matmul (the timed launch) and k_swiglu_*
+    if (float_mode_) {
+        in.op = LOP_F_GATEUP; in.K = d; in.nrows = 2 * ff; in.ntok = s.ntok; in.wts = L.fgu.type; in.has_wt = L.fgu.wt != nullptr;
+        in.x_stride = d; in.x_addr = (uintptr_t)xnf_.p;
+    } else { in = linear_plan_in(LOP_GATEUP, L.wgu, 0, 2 * ff, s.ntok); in.aq_addr = (uintptr_t)fq_.p; in.fused = fused; }
+    in.ff = ff;
+    const LinearPlan p = plan_linear(in);
+    timed(tg, s.st, bytes, [&] {
+        if (p.form == LIN_F_GU_MFMA16) run_gateup_float(s.st, p, L.fgu, ff, xnf_.p, d, actf_.p, s.ntok);
+        else if (p.form == LIN_F_GU_UNFUSED) launch_gemv_float(s.st, L.fgu, 0, 2 * ff, xnf_.p, d, gu_.p, 2 * ff, s.ntok);
+        else if (p.form == LIN_GU_UNFUSED) launch_gemv_q8(s.st, L.wgu, 0, 2 * ff, xq_.p, xd_.p, gu_.p, 2 * ff, s.ntok);
+        else run_gateup_q8(s.st, p, L.wgu, ff, xq_.p, xd_.p, fq_.p, fd_.p, s.ntok);
+    });
+    if (p.form == LIN_F_GU_UNFUSED) launch_swiglu_f32(s.st, gu_.p, ff, actf_.p, s.ntok);
+    else if (p.form == LIN_GU_UNFUSED) launch_swiglu_quant(s.st, gu_.p, ff, fq_.p, fd_.p, s.ntok);
 }
 
 void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMeta& tm, const KvCache& kv, float* hidden_out) {
     Q3_CHECK(ntok >= 1 && ntok <= max_tok_, "ntok out of range");
-    const int d = hp_.n_embd, dq = hp_.n_head * 128, dkv = hp_.n_kv * 128, ff = hp_.n_ff;
-    const int af = attention_form(ntok);
-    if (af == ATTN_GGML) { last_fused_ = false; last_ntok_ = ntok; forward_ggml(st, in, ntok, tm, kv, hidden_out); return; }
-    if (float_mode_) { last_fused_ = false; last_ntok_ = ntok; forward_float(st, in, ntok, tm, kv, hidden_out); return; }
-    const bool use_fused = fused && ntok <= fused_max_tok_; // batched steps (ntok > 8) take the weight-stationary token-sweep GEMM path
-    last_fused_ = use_fused; last_ntok_ = ntok;
-    auto attention = [&](const Layer& L, int l, float* att) {
-        if (af == ATTN_SHORT1 || af == ATTN_SHORT2)
-            launch_attention_short(st, af == ATTN_SHORT1 ? 1 : 2, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                   rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok, att);
-        else if (af == ATTN_FUSED)
-            launch_attention_fused(st, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                   rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok);
-        else {
-            launch_qk_rope_append(st, qkv_.p, dq + 2 * dkv, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                  rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, qrot_.p, ntok);
-            launch_attention(st, qrot_.p, hp_.n_head, hp_.n_kv, tm, kv, l, att, aq_.p, ad_.p, ntok);
-        }
-    };
-    if (use_fused) {
-        // residual stream ping-pongs h_ <-> h2_: a fused prologue may not overwrite what other workgroups still read
-        for (int l = 0; l < hp_.n_layer; l++) {
-            const Layer& L = layers_[l];
-            NormPro a{};
-            if (l == 0) { a.h_in = in.x; a.h_stride = in.x_stride; a.idx_keys = in.idx_keys; a.idx_stride = in.idx_stride; a.nparts = 0; }
-            else { a.h_in = h2_.p; a.h_stride = d; a.parts = parts_d_.p; a.nparts = nparts_d_; a.parts_stride = d; a.parts_slab = (size_t)ntok * d; }
-            a.h_out = h_.p; a.g = L.attn_norm; a.eps = hp_.eps;
-            if (timer) timer->begin(st);
-            launch_gemv_q8_norm(st, L.wqkv, 0, dq + 2 * dkv, a, qkv_.p, dq + 2 * dkv, ntok, nullptr);
-            if (timer) timer->end(st, (double)L.wqkv.bytes());
-            attention(L, l, nullptr);
-            gemv(st, L.wo, 0, d, aq_.p, ad_.p, parts_o_.p, d, ntok);
-            NormPro b{};
-            b.h_in = h_.p; b.h_stride = d; b.parts = parts_o_.p; b.nparts = 1; b.parts_stride = d; b.parts_slab = (size_t)ntok * d; b.h_out = h2_.p;
-            b.g = L.ffn_norm; b.eps = hp_.eps;
-            LaunchTimer* tg = timer_gu ? timer_gu : timer;
-            if (tg) tg->begin(st);
-            launch_gateup_swiglu(st, L.wgu, ff, b, fq_.p, fd_.p, ntok);
-            if (tg) tg->end(st, (double)L.wgu.bytes());
-            gemv(st, L.wdown, 0, d, fq_.p, fd_.p, parts_d_.p, d, ntok);
-        }
-        // final norm is the prologue of head(); hidden_out is produced there too
-        if (hidden_out) head(st, 0, ntok, 0, 0, nullptr, 0, nullptr, -1, hidden_out);
-        Q3_LAUNCH_CHECK();
-        return;
-    }
+    const int d = hp_.n_embd;
+    Pass s{st, ntok, tm, kv, attention_form(ntok), false, false};
+    last_fused_ = false; last_ntok_ = ntok;
+    if (s.af == ATTN_GGML) { forward_ggml(st, in, ntok, tm, kv, hidden_out); return; }
+    Q3_CHECK(!float_mode_ || s.af != ATTN_FUSED, "float mode has no fused attention form");
+    // 5 launches per layer (norms as GEMV prologues) for quantised decode steps; batched steps (ntok > fused_max_tok_) and float weights take the
+    // unfused sequence, whose GEMMs are weight-stationary over the tokens
+    last_fused_ = s.fused = !float_mode_ && fused && ntok <= fused_max_tok_;
     LinearPlanIn npi; npi.op = LOP_NORM; npi.ntok = ntok;
-    const bool wgnorm = plan_linear(npi).form == LIN_NORM_WG; // batched steps: workgroup-per-token norm kernel (same arithmetic, one global round trip)
-    auto norm = [&](const NormArgs& a) {
-        if (!wgnorm) { launch_rmsnorm_quant(st, a, ntok); return; }
-        NormPro p{};
-        p.h_in = a.h_in; p.h_stride = a.h_stride; p.idx_keys = a.idx_keys; p.idx_stride = a.idx_stride; p.parts = a.parts; p.nparts = a.nparts;
-        p.parts_stride = a.parts_stride; p.parts_slab = (size_t)ntok * a.parts_stride; p.h_out = a.h_out; p.g = a.g; p.eps = a.eps; p.xn_out = a.xn_out;
-        Q3_CHECK(a.idx == nullptr, "int32 row indices are not supported on the batched path");
-        launch_rmsnorm_quant_wg(st, p, a.d, a.xq, a.xd, ntok);
+    s.wgnorm = plan_linear(npi).form == LIN_NORM_WG;
+    // Residual stream.  Fused: it ping-pongs h_ <-> h2_, because a fused prologue may not overwrite what other workgroups still read.  Unfused and
+    // float: the norm kernels run in place on h_ (the wg kernel forbids h_out aliasing h_in only across workgroups; there each token is one workgroup).
+    float* hb = s.fused ? h2_.p : h_.p;
+    const int npd = float_mode_ ? 1 : nparts_d_; // slabs of the down-projection: the float matmul writes whole sums
+    float* xn = float_mode_ ? xnf_.p : nullptr;  // float mode: the next matmul reads the f32 norm output
+    auto pro = [&](const float* h_in, const float* parts, int nparts, float* h_out, const float* g, float* xn_out) {
+        NormPro a{};
+        a.h_in = h_in; a.h_stride = d; a.parts = parts; a.nparts = nparts; a.parts_stride = d; a.parts_slab = (size_t)ntok * d;
+        a.h_out = h_out; a.g = g; a.eps = hp_.eps; a.xn_out = xn_out;
+        return a;
     };
-    // NB the wg kernel forbids h_out aliasing h_in only across workgroups; here each token is one workgroup, so in-place is safe
     for (int l = 0; l < hp_.n_layer; l++) {
         const Layer& L = layers_[l];
-        NormArgs a{};
-        if (l == 0) { a.h_in = in.x; a.h_stride = in.x_stride; a.idx = in.idx; a.idx_keys = in.idx_keys; a.idx_stride = in.idx_stride; a.nparts = 0; }
-        else { a.h_in = h_.p; a.h_stride = d; a.parts = parts_d_.p; a.nparts = nparts_d_; a.parts_stride = d; }
-        a.h_out = h_.p; a.g = L.attn_norm; a.eps = hp_.eps; a.d = d; a.xq = xq_.p; a.xd = xd_.p;
-        norm(a);
-        gemv(st, L.wqkv, 0, dq + 2 * dkv, xq_.p, xd_.p, qkv_.p, dq + 2 * dkv, ntok);
-        attention(L, l, nullptr);
-        NormArgs b{};
-        b.h_in = h_.p; b.h_stride = d; b.parts = parts_o_.p; b.nparts = 1; b.parts_stride = d; b.h_out = h_.p;
-        b.g = L.ffn_norm; b.eps = hp_.eps; b.d = d; b.xq = xq_.p; b.xd = xd_.p;
-        gemv(st, L.wo, 0, d, aq_.p, ad_.p, parts_o_.p, d, ntok);
-        norm(b);
-        bool gu_done = false;
-        LaunchTimer* tg = timer_gu ? timer_gu : timer; // the talker's gate/up launch is timed on its own (bench roofline kernel)
-        if (fused) {
-            if (tg) tg->begin(st);
-            gu_done = launch_gateup_mfma(st, L.wgu, ff, xq_.p, xd_.p, fq_.p, fd_.p, ntok);
-            if (tg && gu_done) tg->end(st, (double)L.wgu.bytes()); // an unmatched begin() is simply re-recorded by the next one
-        }
-        if (!gu_done) {
-            if (tg) { tg->begin(st); launch_gemv_q8(st, L.wgu, 0, 2 * ff, xq_.p, xd_.p, gu_.p, 2 * ff, ntok); tg->end(st, (double)L.wgu.bytes()); }
-            else
-            gemv(st, L.wgu, 0, 2 * ff, xq_.p, xd_.p, gu_.p, 2 * ff, ntok);
-            launch_swiglu_quant(st, gu_.p, ff, fq_.p, fd_.p, ntok);
-        }
-        gemv(st, L.wdown, 0, d, fq_.p, fd_.p, parts_d_.p, d, ntok);
-        if (l + 1 == hp_.n_layer) { // the final norm (the next layer's attention norm consumes the down-projection otherwise)
-            NormArgs nx{};
-            nx.h_in = h_.p; nx.h_stride = d; nx.parts = parts_d_.p; nx.nparts = nparts_d_; nx.parts_stride = d; nx.eps = hp_.eps; nx.d = d; nx.xq = xq_.p; nx.xd = xd_.p;
-            nx.h_out = nullptr; nx.g = output_norm_; nx.xn_out = hidden_out ? hidden_out : hid_.p;
-            norm(nx);
-        }
+        NormPro a = pro(hb, parts_d_.p, npd, h_.p, L.attn_norm, xn); // the previous layer's down-projection is consumed here
+        if (l == 0) { a.h_in = in.x; a.h_stride = in.x_stride; a.idx_keys = in.idx_keys; a.idx_stride = in.idx_stride; a.parts = nullptr; a.nparts = 0; }
+        qkv(s, L, a);
+        attention(s, L, l);
+        linear(s, L.wo, L.fo, attf_.p, aq_.p, ad_.p, parts_o_.p);
+        gate_up(s, L, pro(h_.p, parts_o_.p, 1, hb, L.ffn_norm, xn));
+        linear(s, L.wdown, L.fdown, actf_.p, fq_.p, fd_.p, parts_d_.p);
     }
-    Q3_LAUNCH_CHECK();
-}
-
-void Transformer::forward_float(hipStream_t st, const Input& in, int ntok, const TokMeta& tm, const KvCache& kv, float* hidden_out) {
-    const int d = hp_.n_embd, dq = hp_.n_head * 128, dkv = hp_.n_kv * 128, ff = hp_.n_ff;
-    auto norm = [&](const float* h_in, int h_stride, const unsigned long long* idx_keys, int idx_stride, const float* parts, const float* g, float* xn) {
-        NormArgs a{};
-        a.h_in = h_in; a.h_stride = h_stride; a.idx_keys = idx_keys; a.idx_stride = idx_stride; a.parts = parts; a.nparts = parts ? 1 : 0; a.parts_stride = d;
-        a.h_out = h_.p; a.g = g; a.eps = hp_.eps; a.d = d; a.xq = xq_.p; a.xd = xd_.p; a.xn_out = xn; // int8 copy unused in float mode
-        LinearPlanIn npi; npi.op = LOP_NORM; npi.ntok = ntok;
-        if (plan_linear(npi).form == LIN_NORM) { launch_rmsnorm_quant(st, a, ntok); return; }
-        NormPro p{}; // batched steps: workgroup-per-token norm kernel (same arithmetic)
-        p.h_in = a.h_in; p.h_stride = a.h_stride; p.idx_keys = a.idx_keys; p.idx_stride = a.idx_stride; p.parts = a.parts; p.nparts = a.nparts;
-        p.parts_stride = a.parts_stride; p.parts_slab = (size_t)ntok * a.parts_stride; p.h_out = a.h_out; p.g = a.g; p.eps = a.eps; p.xn_out = a.xn_out;
-        launch_rmsnorm_quant_wg(st, p, a.d, a.xq, a.xd, ntok);
-    };
-    auto fgemv = [&](const FMat& w, const float* x, int xs, float* out, int os) {
-        if (timer) timer->begin(st);
-        launch_gemv_float(st, w, 0, w.N, x, xs, out, os, ntok);
-        if (timer) timer->end(st, (double)w.bytes());
-    };
-    const int af = attention_form(ntok);
-    Q3_CHECK(af != ATTN_FUSED, "float mode has no fused attention form");
-    for (int l = 0; l < hp_.n_layer; l++) {
-        const Layer& L = layers_[l];
-        if (l == 0) norm(in.x, in.x_stride, in.idx_keys, in.idx_stride, nullptr, L.attn_norm, xnf_.p);
-        else norm(h_.p, d, nullptr, 0, parts_d_.p, L.attn_norm, xnf_.p);
-        fgemv(L.fqkv, xnf_.p, d, qkv_.p, dq + 2 * dkv);
-        if (af == ATTN_SHORT1 || af == ATTN_SHORT2)
-            launch_attention_short(st, af == ATTN_SHORT1 ? 1 : 2, qkv_.p, dq + 2 * dkv, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p,
-                                   rope_sin_.p, n_ctx_, d_mrope_.p, tm, kv, l, aq_.p, ad_.p, ntok, attf_.p);
-        else {
-            launch_qk_rope_append(st, qkv_.p, dq + 2 * dkv, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
-                                  n_ctx_, d_mrope_.p, tm, kv, l, qrot_.p, ntok);
-            launch_attention(st, qrot_.p, hp_.n_head, hp_.n_kv, tm, kv, l, attf_.p, aq_.p, ad_.p, ntok);
-        }
-        fgemv(L.fo, attf_.p, dq, parts_o_.p, d);
-        norm(h_.p, d, nullptr, 0, parts_o_.p, L.ffn_norm, xnf_.p);
-        LaunchTimer* tg = timer_gu ? timer_gu : timer;
-        if (tg) tg->begin(st);
-        const bool gu_fused = launch_gateup_float(st, L.fgu, ff, xnf_.p, d, actf_.p, ntok);
-        if (tg && gu_fused) tg->end(st, (double)L.fgu.bytes()); // an unmatched begin() is simply re-recorded by the next one
-        if (!gu_fused) {
-            if (tg) { tg->begin(st); launch_gemv_float(st, L.fgu, 0, L.fgu.N, xnf_.p, d, gu_.p, 2 * ff, ntok); tg->end(st, (double)L.fgu.bytes()); }
-            else
-            fgemv(L.fgu, xnf_.p, d, gu_.p, 2 * ff);
-            launch_swiglu_f32(st, gu_.p, ff, actf_.p, ntok);
-        }
-        fgemv(L.fdown, actf_.p, ff, parts_d_.p, d);
+    if (s.fused) { if (hidden_out) head(st, 0, ntok, 0, 0, nullptr, 0, nullptr, -1, hidden_out); } // the final norm is the prologue of head()
+    else {
+        norm(s, pro(h_.p, parts_d_.p, npd, nullptr, output_norm_, hidden_out ? hidden_out : hid_.p));
+        if (float_mode_ && hidden_out) launch_copy_f32(st, hidden_out, hid_.p, (size_t)ntok * d); // head() reads hid_
     }
-    norm(h_.p, d, nullptr, 0, parts_d_.p, output_norm_, hidden_out ? hidden_out : hid_.p);
-    if (hidden_out) launch_copy_f32(st, hidden_out, hid_.p, (size_t)ntok * d);
     Q3_LAUNCH_CHECK();
 }
 
@@ -619,20 +481,8 @@ void Transformer::head(hipStream_t st, int tok0, int tok_count, int row0, int nr
 }
 void Transformer::head_impl(hipStream_t st, int tok0, int tok_count, int row0, int nrows, float* logits, int logits_stride,
                             const ArgmaxEpi* am, int nrows_valid, float* hidden_out) {
-    const int d = hp_.n_embd;
+    const int d = hp_.n_embd, nv = nrows_valid > 0 ? nrows_valid : nrows;
     Q3_CHECK(row0 % 32 == 0 && (float_mode_ || row0 + nrows <= output_.Npad), "head row range");
-    if (ggml_mode_) { // final-norm hidden states are in hid_ (f32): quantise them for the output matrix's type, plain dots, optional argmax keys
-        if (hidden_out) launch_copy_f32(st, hid_.p + (size_t)tok0 * d, hidden_out, (size_t)tok_count * d);
-        if (nrows <= 0) return;
-        int nr = nrows;
-        if (row0 + nr > gg_output_.n) nr = gg_output_.n - row0;   // (callers pass row counts padded to 32)
-        float* dst = am ? big_logits_.p : logits;
-        const int ls = am ? nrows : logits_stride;
-        if (am && big_logits_.n < (size_t)tok_count * nrows) throw Error("head scratch too small");
-        gg_linear(st, gg_output_, row0, nr, hid_.p + (size_t)tok0 * d, dst, ls, tok_count);
-        if (am) launch_argmax_keys(st, big_logits_.p, nrows, std::min(nrows_valid > 0 ? nrows_valid : nrows, nr), am->mask_per_tok, am->keys, am->key_stride, tok_count);
-        return;
-    }
     if (last_fused_) {
         // final RMSNorm (+ last down-proj partials + residual) as the prologue of the output-matrix GEMV
         NormPro f{};
@@ -640,37 +490,28 @@ void Transformer::head_impl(hipStream_t st, int tok0, int tok_count, int row0, i
         f.parts = parts_d_.p + (size_t)tok0 * d; f.nparts = nparts_d_; f.parts_stride = d;
         f.parts_slab = (size_t)last_ntok_ * d; // slabs are [p][ntok of the forward that wrote them][d]
         f.g = output_norm_; f.eps = hp_.eps; f.xn_out = hidden_out;
-        if (nrows <= 0) { // hidden only: run the prologue through a 32-row GEMV whose output is discarded
-            if (timer) timer->begin(st);
-            launch_gemv_q8_norm(st, output_, 0, 32, f, scratch_logits(tok_count), 32, tok_count, nullptr);
-            if (timer) timer->end(st, 32.0 * ((double)d * 1.0625));
-            return;
-        }
-        if (timer) timer->begin(st);
-        if (am) launch_gemv_q8_norm(st, output_, row0, nrows_valid > 0 ? nrows_valid : nrows, f, nullptr, 0, tok_count, am);
-        else launch_gemv_q8_norm(st, output_, row0, nrows, f, logits, logits_stride, tok_count, nullptr);
-        if (timer) timer->end(st, (double)nrows * ((double)d * 1.0625));
+        if (nrows <= 0) // hidden only: run the prologue through a 32-row GEMV whose output is discarded
+            timed(timer, st, 32.0 * ((double)d * 1.0625), [&] { launch_gemv_q8_norm(st, output_, 0, 32, f, scratch_logits(tok_count), 32, tok_count, nullptr); });
+        else
+            timed(timer, st, (double)nrows * ((double)d * 1.0625),
+                  [&] { launch_gemv_q8_norm(st, output_, row0, am ? nv : nrows, f, am ? nullptr : logits, am ? 0 : logits_stride, tok_count, am); });
         return;
     }
+    // the final-norm hidden states are in hid_ (f32) and xq_ / xd_ (int8): one matmul by mode; with an argmax epilogue, logits to scratch, then the keys
     if (hidden_out) launch_copy_f32(st, hid_.p + (size_t)tok0 * d, hidden_out, (size_t)tok_count * d);
     if (nrows <= 0) return;
-    if (float_mode_) {
-        float* dst = am ? big_logits_.p : logits;
-        const int ls = am ? nrows : logits_stride;
-        if (timer) timer->begin(st);
-        launch_gemv_float(st, foutput_, row0, nrows, hid_.p + (size_t)tok0 * d, d, dst, ls, tok_count);
-        if (timer) timer->end(st, (double)nrows * d * (foutput_.type == Q3_T_F32 ? 4 : 2));
-        if (am) launch_argmax_keys(st, big_logits_.p, nrows, nrows_valid > 0 ? nrows_valid : nrows, am->mask_per_tok, am->keys, am->key_stride, tok_count);
-        return;
-    }
-    if (am) { // batched-step path: logits to scratch, then argmax keys
-        const int nv = nrows_valid > 0 ? nrows_valid : nrows;
-        if (big_logits_.n < (size_t)tok_count * nrows) throw Error("head scratch too small");
-        gemv(st, output_, row0, nrows, xq_.p + (size_t)tok0 * d, xd_.p + (size_t)tok0 * (d / 32), big_logits_.p, nrows, tok_count);
-        launch_argmax_keys(st, big_logits_.p, nrows, nv, am->mask_per_tok, am->keys, am->key_stride, tok_count);
-        return;
-    }
-    gemv(st, output_, row0, nrows, xq_.p + (size_t)tok0 * d, xd_.p + (size_t)tok0 * (d / 32), logits, logits_stride, tok_count);
+    float* dst = am ? big_logits_.p : logits;
+    const int ls = am ? nrows : logits_stride;
+    if (am && big_logits_.n < (size_t)tok_count * nrows) throw Error("head scratch too small");
+    int nr = nrows;
+    if (ggml_mode_) { // quantise hid_ for the output matrix's type, plain dots
+        nr = std::min(nrows, gg_output_.n - row0); // (callers pass row counts padded to 32)
+        gg_linear(st, gg_output_, row0, nr, hid_.p + (size_t)tok0 * d, dst, ls, tok_count);
+    } else if (float_mode_)
+        timed(timer, st, (double)nrows * d * (foutput_.type == Q3_T_F32 ? 4 : 2),
+              [&] { launch_gemv_float(st, foutput_, row0, nrows, hid_.p + (size_t)tok0 * d, d, dst, ls, tok_count); });
+    else gemv(st, output_, row0, nrows, xq_.p + (size_t)tok0 * d, xd_.p + (size_t)tok0 * (d / 32), dst, ls, tok_count);
+    if (am) launch_argmax_keys(st, big_logits_.p, nrows, std::min(nv, nr), am->mask_per_tok, am->keys, am->key_stride, tok_count);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -698,20 +539,23 @@ void KvPool::assign(int seq, int lp, int pp) {
     table_[(size_t)seq * max_pages_ + lp] = pp;
     Q3_HIP(hipMemcpy(d_table_.p + (size_t)seq * max_pages_ + lp, &pp, 4, hipMemcpyHostToDevice));
 }
-void KvPool::ensure(int seq, int n_positions) {
-    const int need = (n_positions + 63) / 64;
-    Q3_CHECK(seq >= 0 && seq < n_seq_, "KV sequence index out of range");
-    Q3_CHECK(need <= max_pages_ && need <= n_pages_, "sequence exceeds max pages");
-    while (used_pages_[seq] < need) { assign(seq, used_pages_[seq], alloc_page()); used_pages_[seq]++; }
-}
-void KvPool::ensure(int seq, int n_positions, hipStream_t st) {
+int KvPool::grow(int seq, int n_positions) {
     const int need = (n_positions + 63) / 64;
     Q3_CHECK(seq >= 0 && seq < n_seq_, "KV sequence index out of range");
     Q3_CHECK(need <= max_pages_ && need <= n_pages_, "sequence exceeds max pages");
     const int first = used_pages_[seq];
+    Q3_CHECK(need - first <= (int)free_.size(), "KV pool exhausted"); // all or nothing: a failed call leaves the tables as they were
     while (used_pages_[seq] < need) { table_[(size_t)seq * max_pages_ + used_pages_[seq]] = alloc_page(); used_pages_[seq]++; }
-    if (need > first) // rows of other sequences are untouched, and this row is not rewritten before `st` is synchronised by the caller
-        Q3_HIP(hipMemcpyAsync(d_table_.p + (size_t)seq * max_pages_ + first, table_ + (size_t)seq * max_pages_ + first, (size_t)(need - first) * 4,
+    return first;
+}
+void KvPool::ensure(int seq, int n_positions) {
+    const int first = grow(seq, n_positions);
+    for (int lp = first; lp < used_pages_[seq]; lp++) assign(seq, lp, page(seq, lp));
+}
+void KvPool::ensure(int seq, int n_positions, hipStream_t st) {
+    const int first = grow(seq, n_positions), n_new = used_pages_[seq] - first;
+    if (n_new > 0) // rows of other sequences are untouched, and this row is not rewritten before `st` is synchronised by the caller
+        Q3_HIP(hipMemcpyAsync(d_table_.p + (size_t)seq * max_pages_ + first, table_ + (size_t)seq * max_pages_ + first, (size_t)n_new * 4,
                               hipMemcpyHostToDevice, st));
 }
 KvPool::~KvPool() { if (table_) (void)hipHostFree(table_); }

@@ -5,7 +5,6 @@
 #include "gguf.h"
 #include "kernels.h"
 #include "ggml_mode.h"
-#include <map>
 #include <memory>
 
 namespace q3 {
@@ -50,8 +49,7 @@ public:
 
     struct Input {
         const float* x = nullptr; int x_stride = 0;   // [ntok][x_stride] embeddings ...
-        const int32_t* idx = nullptr; int idx_stride = 0; // ... or table rows: x + idx[tok*idx_stride]*x_stride (unfused path)
-        const q3_u64* idx_keys = nullptr;             // ... or table rows selected by argmax keys (fused path)
+        const q3_u64* idx_keys = nullptr; int idx_stride = 0; // ... or table rows selected by argmax keys: x + code(idx_keys[tok*idx_stride])*x_stride
     };
     // fused = 5 launches/layer (decode steps: every token from a different sequence, or a single sequence's
     // tokens when `same_seq_tokens` is set, in which case attention stays unfused)
@@ -90,14 +88,20 @@ private:
                    int nrows_valid, float* hidden_out);
     struct Layer { Q8Mat wqkv, wo, wgu, wdown; FMat fqkv, fo, fgu, fdown; float *attn_norm, *q_norm, *k_norm, *ffn_norm; };
     FMat make_fmat(const Gguf& g, const std::vector<std::string>& names, int K_expect);
-    void forward_float(hipStream_t st, const Input& in, int ntok, const TokMeta& tm, const KvCache& kv, float* hidden_out);
+    // The layer walk.  One forward() = one Pass: what the launch choice of every step depends on, computed once.
+    struct Pass { hipStream_t st; int ntok; const TokMeta& tm; const KvCache& kv; int af /* AttnForm */; bool fused /* 5 launches per layer */, wgnorm /* LIN_NORM_WG */; };
+    void norm(const Pass& s, const NormPro& a);                         // residual add + RMSNorm + quantise, as its own launch
+    void linear(const Pass& s, const Q8Mat& w, const FMat& fw, const float* xf, const int8_t* xq, const uint16_t* xd, float* out);
+    void qkv(const Pass& s, const Layer& L, const NormPro& a);          // attention norm + q/k/v projection -> qkv_
+    void attention(const Pass& s, const Layer& L, int l);               // -> aq_ / ad_ (+ attf_ in float mode)
+    void gate_up(const Pass& s, const Layer& L, const NormPro& b);      // ffn norm + gate/up + SwiGLU -> fq_ / fd_ (actf_ in float mode)
     bool float_mode_ = false; FMat foutput_; DevBuf<float> xnf_, attf_, actf_;
     float* scratch_logits(int) { return scratch_.p; }
     DevBuf<float> scratch_, hid_, big_logits_;
     void gemv(hipStream_t st, const Q8Mat& w, int row0, int nrows, const int8_t* xq, const uint16_t* xd, float* out,
               int out_stride, int ntok);
+    // looks the tensors up in the GGUF, plans the layout (wlayout.h) and builds it into a new blob
     Q8Mat make_mat(const Gguf& g, const std::vector<std::pair<std::string, int>>& rows /* tensor, first row */, int N, int K);
-    void load_into(const Gguf& g, const std::string& name, Q8Mat& dst, int row_off, int K_expect);
     float* load_f32(const Gguf& g, const std::string& name, int64_t n_expect);
     TfHparams hp_;
     int n_ctx_ = 0, max_tok_ = 0;
@@ -106,7 +110,6 @@ private:
     float* output_norm_ = nullptr;
     struct WeightStore { // device memory shared by every context of one model
         std::vector<DevBuf<uint8_t>> blobs; DevBuf<float> rope_cos, rope_sin; DevBuf<int32_t> d_mrope;
-        std::map<const uint8_t*, uint8_t*> mat_meta, mat_types; std::map<const uint8_t*, uint32_t*> mat_off;
     };
     std::shared_ptr<WeightStore> ws_;
     std::vector<DevBuf<uint8_t>>& blobs_ = ws_init()->blobs;
@@ -117,8 +120,7 @@ private:
     void alloc_workspace();
     // activations
     DevBuf<float> h_, h2_, parts_o_, parts_d_, qkv_, qrot_, gu_;
-    bool same_seq_ = false; int short_attn_min_ = 0; int fused_max_tok_ = 8; bool last_fused_ = false; int last_ntok_ = 0; bool all_q8_ = true;
-    std::map<const uint8_t*, uint8_t*>& mat_meta_ = ws_->mat_meta; std::map<const uint8_t*, uint8_t*>& mat_types_ = ws_->mat_types; std::map<const uint8_t*, uint32_t*>& mat_off_ = ws_->mat_off;
+    bool same_seq_ = false; int short_attn_min_ = 0; int fused_max_tok_ = 8; bool last_fused_ = false; int last_ntok_ = 0;
     DevBuf<int8_t> xq_, aq_, fq_;
     DevBuf<uint16_t> xd_, ad_, fd_;
     int nparts_d_ = 1;
@@ -134,12 +136,12 @@ private:
     DevBuf<int8_t> gg_q8_, gg_qk_; DevBuf<uint16_t> gg_d8_; DevBuf<float> gg_dk_, gg_xn_, gg_att_, gg_scores_, gg_act_f_; DevBuf<int16_t> gg_bs_;
 };
 
-// standalone repack of host GGUF Q8_0 rows into a device Q8Mat (storage owns the memory); used by parity ops
+// The one builder of a device Q8Mat: the blob wlayout.h planned, filled from the host GGUF rows raw[i] of L.tensors[i]; `blob` owns the memory.
+// Transformer::make_mat and the parity ops all come through here.
+Q8Mat build_q8mat(const WLayout& L, const void* const* raw, DevBuf<uint8_t>& blob);
+// for the parity ops: one Q8_0 tensor in the uniform layout (any n), and nw stacked tensors in the row-group layout (forced, also when all are Q8_0)
 Q8Mat q8mat_from_host(const void* raw_q8_0, int n, int k, DevBuf<uint8_t>& storage);
-// the same for a K-quant matrix built from up to 3 tensors (GGUF rows of type Q8_0 / Q5_K / Q6_K, row counts multiples of 32): packed planes + tensor map,
-// exactly what Transformer::make_mat produces (op-level parity tests)
-struct KqPart { const void* raw; int type; int rows; };
-Q8Mat kqmat_from_host(const KqPart* parts, int nparts, int k, DevBuf<uint8_t>& storage);
+Q8Mat kqmat_from_host(const void* const* raw, const int32_t* types, const int32_t* rows, int nw, int k, DevBuf<uint8_t>& storage);
 
 // simple paged KV pool (pages of 64 positions) -- "paged KV cache sized for 288 GB HBM3E"
 class KvPool {
@@ -153,12 +155,13 @@ public:
     void free_page(int p);
     void assign(int seq, int logical_page, int physical_page); // updates host + device table
     void ensure(int seq, int n_positions);                      // make sure pages for [0,n_positions) exist
-    void ensure(int seq, int n_positions, hipStream_t st);      // same; the table row is uploaded asynchronously on `st`
+    void ensure(int seq, int n_positions, hipStream_t st);      // same; the new part of the table row is uploaded asynchronously on `st`
     void release(int seq);
     int pages_free() const { return (int)free_.size(); }
     int page(int seq, int logical_page) const { return table_[(size_t)seq * max_pages_ + logical_page]; }
     size_t bytes() const { return (k_.n + v_.n) * 2; }
 private:
+    int grow(int seq, int n_positions); // host table only: takes the missing pages, returns the first new logical page
     int n_layer_, n_kv_, n_pages_, n_seq_, max_pages_;
     DevBuf<uint16_t> k_, v_;
     DevBuf<int32_t> d_table_;

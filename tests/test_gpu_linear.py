@@ -61,6 +61,7 @@ GEMV_CASES = [  # (types, rows per tensor, K, ntok, row0, nrows, kq_layout)
     ([8], [32], 512, 256, 0, 32, 0), ([8], [32], 256, 300, 0, 32, 0), ([13, 14], [32, 32], 1024, 300, 0, 64, 1),
     ([13], [64], 1024, 4, 0, 64, 1), ([14], [64], 3072, 32, 0, 64, 1), ([13, 14, 8], [32, 32, 64], 2048, 8, 0, 128, 1),
     ([13, 14, 8], [32, 32, 32], 6144, 40, 32, 64, 1), ([8], [64], 512, 2, 0, 64, 1),
+    ([13, 8, 14], [32, 32, 32], 256, 2, 0, 96, 1), ([13, 14, 13], [32, 32, 32], 256, 17, 0, 96, 1),  # a Q8_0 tensor between two others; a type that returns
 ]
 
 
