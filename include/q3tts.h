@@ -115,6 +115,7 @@ double q3tts_engine_bytes_per_step(q3tts_engine* e, int32_t batch, double mean_c
 #define Q3TTS_REQ_RUNNING 1
 #define Q3TTS_REQ_DRAINING 2 /* all frames generated, codec still decoding the tail */
 #define Q3TTS_REQ_DONE 3
+#define Q3TTS_REQ_CANCELLED 4 /* [EXT] stopped by q3tts_cancel; terminal like DONE and FAILED, partial results stay fetchable until release */
 #define Q3TTS_REQ_FAILED (-1)
 typedef struct q3tts_req_status {
     int32_t state; int32_t n_frames; int64_t n_pcm; /* frames emitted / PCM samples decoded so far (streamable) */
@@ -135,6 +136,7 @@ int q3tts_submit_trailing_open(q3tts_engine* e, const q3tts_request* r, int32_t 
                                const int32_t* trail_ids, int32_t n_trail, int64_t* req_id);
 /* appends raw trailing ids (copied); close = 1 closes the trail (n may be 0).
  * 0: appended; 1: the request no longer takes text (finished by EOS / max_steps, done or failed) -- nothing appended;
+ * (the same from the moment q3tts_cancel returned 0);
  * < 0: unknown id, request not open, already closed, n < 0, ids NULL with n > 0, or the total would exceed max_prompt (nothing appended) */
 int q3tts_trail_append(q3tts_engine* e, int64_t req_id, const int32_t* ids, int32_t n, int32_t close);
 /* appended ids, ids consumed by the feedback so far (min(n_frames, appended)), closed flag (1 for a request not submitted open) */
@@ -145,6 +147,15 @@ int q3tts_fetch(q3tts_engine* e, int64_t req_id, int32_t* codes_out, int32_t fra
                 int64_t pcm_off, int64_t pcm_cap, int32_t* got_frames, int64_t* got_pcm);
 int q3tts_wait(q3tts_engine* e, int64_t req_id, double timeout_ms /* <0: forever */); /* 0 done, 1 timeout, <0 error */
 int q3tts_release(q3tts_engine* e, int64_t req_id);
+/* [EXT] stops a request wherever it is.  Thread-safe, issues no HIP call (the scheduler does the device work between two frame groups).
+ * 0: cancellation requested (the request reaches Q3TTS_REQ_CANCELLED within the scheduler's next steps; a second call while that is
+ *    pending returns 0 again);  1: the request had already ended (done, failed or cancelled) -- nothing changes;  < 0: unknown id.
+ * A queued request is CANCELLED at once.  A running one keeps the frames harvested before the scheduler honoured the cancel (bit-identical
+ * to the same prefix of the uncancelled run) and the PCM of the whole 4-frame chunks whose decode had been enqueued by then; the tail is
+ * not flushed and chunks the decoder thread had not taken are dropped.  The state turns CANCELLED only when nothing of the request is in
+ * flight any more: its codec work has completed, its PCM has left the staging region, its codec stream, slot and KV pages are free.
+ * q3tts_wait returns 0 on it, q3tts_release accepts it.  Other requests in the batch are untouched.  q3tts_generate_batch* cannot be cancelled */
+int q3tts_cancel(q3tts_engine* e, int64_t req_id);
 int q3tts_sched_start(q3tts_engine* e);
 int q3tts_sched_stop(q3tts_engine* e);
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy);
@@ -219,6 +230,7 @@ int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_
                       int64_t pcm_off, int64_t pcm_cap, int32_t* got_frames, int64_t* got_pcm);
 int q3tts_group_wait(q3tts_group* g, int64_t req_id, double timeout_ms);
 int q3tts_group_release(q3tts_group* g, int64_t req_id);
+int q3tts_group_cancel(q3tts_group* g, int64_t req_id);       /* [EXT] q3tts_cancel, routed by the engine index the id carries */
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
 int q3tts_group_stop(q3tts_group* g);
 /* q3tts_comm_*: ONE process per GPU (what `bench.py --gpus N` / torchrun-style launchers use).  Rank 0 makes the 128-byte id and ships it to

@@ -176,6 +176,7 @@ int q3tts_wait(q3tts_engine* e, int64_t id, double timeout_ms) {
     Q3_API_END(Q3TTS_ERR)
 }
 int q3tts_release(q3tts_engine* e, int64_t id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->release(id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_cancel(q3tts_engine* e, int64_t id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); return e->e->cancel(id); Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

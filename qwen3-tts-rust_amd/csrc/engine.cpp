@@ -172,6 +172,7 @@ struct Engine::Req {
     int64_t id = 0;
     GenRequest r; std::vector<float> prompt_own; std::vector<int32_t> trail_own; bool want_pcm = false;
     bool closed = false;  // [EXT] open trail (r.open): closed by append_trail; trail_own and closed change under mu_ only
+    bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
@@ -483,7 +484,7 @@ void Engine::harvest(bool block) {
             r->pcm.assign(pcm_pinned_ + (size_t)r->cs * slot_cap_, pcm_pinned_ + (size_t)r->cs * slot_cap_ + c.pcm_after);
             cs_free_.push_back(r->cs);
             r->cs = -1;
-            r->state = REQ_DONE; r->t_done = now_ms();
+            r->state = fenced_state(r->cancel); r->t_done = now_ms();
             n_draining_--;
             cv_.notify_all();
         }
@@ -562,7 +563,7 @@ int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
     Req& r = *it->second;
     Q3_CHECK(r.r.open, "the request was not submitted with an open trail");
     Q3_CHECK(!r.closed, "the request's trail is already closed");
-    if (r.state != REQ_QUEUED && r.state != REQ_RUNNING) return 1; // finished (EOS / max_steps), done or failed: nothing appended
+    if (r.cancel || (r.state != REQ_QUEUED && r.state != REQ_RUNNING)) return 1; // cancelled, finished (EOS / max_steps), done or failed: nothing appended
     Q3_CHECK(r.trail_own.size() + (size_t)n <= (size_t)p_.max_prompt, "the trail would exceed max_prompt ids");
     r.trail_own.insert(r.trail_own.end(), ids, ids + n);
     if (close) r.closed = true;
@@ -600,6 +601,58 @@ void Engine::collect_appends() {
         const int op = r.closed ? 0 : 1;
         if (op != open) { open = op; slot_dirty_ = true; }
     }
+}
+
+// [EXT] request cancellation.  Like an append, the caller's thread only marks the request under mu_ and wakes the scheduler, which does
+// the device-side work between two frame groups; a request still in the queue owns nothing and ends right here.
+int Engine::cancel(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    Req& r = *it->second;
+    if (req_ended(r.state)) return 1;
+    if (r.cancel) return 0; // the first cancel is still pending
+    r.cancel = true;
+    if (cancel_action(r.state, false, false, r.want_pcm) == CANCEL_AT_ONCE) {
+        pending_.erase(std::find(pending_.begin(), pending_.end(), &r));
+        r.state = REQ_CANCELLED; r.t_done = now_ms();
+    } else cancel_ids_.push_back(id);
+    wake_++;
+    cv_.notify_all();
+    return 0;
+}
+
+// drops the chunk tasks of r the decoder thread has not taken yet (dmu_ held); what it has taken runs to its end
+void Engine::purge_chunks(Req* r) {
+    for (auto it = dq_.begin(); it != dq_.end();) {
+        if (it->r == r && !it->fence && !it->reset) { it = dq_.erase(it); dec_pending_--; }
+        else ++it;
+    }
+}
+
+// scheduler thread, between two frame groups: live slots of cancelled requests are retired, draining ones lose their unstarted chunks;
+// a request inside an asynchronous prefill wave stays on the list until activate() has kept it out of the batch
+void Engine::collect_cancels() {
+    std::vector<Req*> live;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (cancel_ids_.empty()) return;
+        std::vector<int64_t> ids;
+        ids.swap(cancel_ids_);
+        for (int64_t id : ids) {
+            auto it = reqs_.find(id);
+            if (it == reqs_.end()) continue; // ended and released meanwhile
+            Req* r = it->second.get();
+            const bool is_live = r->slot >= 0 && slots_.live[r->slot];
+            switch (cancel_action(r->state, r->slot >= 0 && !is_live, is_live, r->want_pcm)) {
+            case CANCEL_AT_ACTIVATE: cancel_ids_.push_back(id); break;
+            case CANCEL_RETIRE: case CANCEL_RETIRE_FENCE: live.push_back(r); break;
+            case CANCEL_PURGE: { std::lock_guard<std::mutex> dlk(dmu_); purge_chunks(r); } break;
+            default: break;
+            }
+        }
+    }
+    for (Req* r : live) retire(r, false);
 }
 
 // moves queued requests into free slots (lowest slot first, so the live slots stay packed and a narrow graph suffices)
@@ -714,8 +767,15 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
 // slot's own sampler state (greedy slots take the sampler kernel's first-max branch).  Runs on st_ between two frame groups.
 void Engine::activate() {
     if (pf_batch_.empty()) return;
-    std::vector<Req*> batch;
+    std::vector<Req*> batch, dropped;
     batch.swap(pf_batch_);
+    if (n_prefilling_ > 0) { // [EXT] requests cancelled while the asynchronous wave ran do not go live; their wave-mates are not disturbed
+        std::lock_guard<std::mutex> lk(mu_);
+        const double t = now_ms();
+        for (Req* r : batch) if (r->cancel) { r->prefill_ms = t - r->t_submit; dropped.push_back(r); }
+        batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->cancel; }), batch.end());
+    }
+    for (Req* r : dropped) retire(r, false); // slot, KV pages and -- through the fence, behind the reset task already queued -- codec stream
     arena_used_ = 0; // st_ is idle between scheduler operations
     q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
     const uint32_t zero = 0;
@@ -763,18 +823,27 @@ void Engine::activate() {
     }
 }
 
-void Engine::finish_ar(Req* r) { // engine.rs:644-649: final flush of the chunker, then the decoder drains
-    r->chunker->push(nullptr, 0, true);
+// A request gives its slot back.  flush_tail (EOS / max_steps; engine.rs:644-649): final flush of the chunker, then the decoder drains.
+// [EXT] Without it (a cancel): the tail is not decoded and the chunks the decoder thread has not taken yet are dropped.  Either way a request
+// with PCM ends behind a fence, once nothing of it is in flight; a slot that never went live (cancelled inside a prefill wave) is only unreserved.
+void Engine::retire(Req* r, bool flush_tail) {
+    if (flush_tail) r->chunker->push(nullptr, 0, true);
     const int b = r->slot;
     {
         std::lock_guard<std::mutex> lk(mu_);
-        slot_req_[b] = nullptr; slots_.live[b] = 0; n_active_--;
+        slot_req_[b] = nullptr;
+        if (slots_.live[b]) { slots_.live[b] = 0; n_active_--; }
         r->slot = -1;
-        if (r->want_pcm) { r->state = REQ_DRAINING; n_draining_++; }
-        else { r->state = REQ_DONE; r->t_done = now_ms(); cv_.notify_all(); }
+        r->state = retired_state(r->want_pcm, r->cancel);
+        if (r->want_pcm) n_draining_++;
+        else { r->t_done = now_ms(); cv_.notify_all(); }
     }
     if (r->want_pcm) {
-        { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, {}, false, true, false}); dec_pending_++; }
+        {
+            std::lock_guard<std::mutex> lk(dmu_);
+            if (!flush_tail) purge_chunks(r);
+            dq_.push_back(DecTask{r, {}, false, true, false}); dec_pending_++;
+        }
         dcv_.notify_all();
     }
     slots_.reset(b); h_pend_[b].clear();
@@ -849,7 +918,7 @@ void Engine::run_group() {
             }
             stats.frames += nnew;
         }
-        if (h_fin[b] || h_nfr[b] >= r->r.max_steps) finish_ar(r);
+        if (h_fin[b] || h_nfr[b] >= r->r.max_steps) retire(r, true);
     }
 }
 
@@ -867,6 +936,7 @@ bool Engine::step() {
         if (hipEventQuery(pf_done_) == hipSuccess) activate();
     }
     collect_appends();
+    collect_cancels(); // before admit: a slot a cancel frees can be refilled in this step
     admit(n_active_ > 0 && slots_.all_live_stalled());
     const double t2 = now_ms();
     // [EXT] live text append: when every live slot waits for text, no frame group runs (graph_frames stays put); prefill and codec
@@ -894,10 +964,11 @@ ReqStatus Engine::poll(int64_t id) {
     Q3_CHECK(it != reqs_.end(), "unknown request id");
     const Req& r = *it->second;
     ReqStatus s;
-    s.state = r.state; s.n_frames = r.fed; s.n_pcm = (int64_t)(r.state == REQ_DONE ? r.pcm.size() : r.pcm_ready);
-    s.queue_ms = r.t_admit > 0 ? r.t_admit - r.t_submit : now_ms() - r.t_submit;
+    const bool ended = r.state == REQ_DONE || r.state == REQ_CANCELLED; // t_done is set, the PCM sits in r.pcm
+    s.state = r.state; s.n_frames = r.fed; s.n_pcm = (int64_t)(ended ? r.pcm.size() : r.pcm_ready);
+    s.queue_ms = (r.t_admit > 0 ? r.t_admit : ended ? r.t_done : now_ms()) - r.t_submit; // cancelled in the queue: until then
     s.prefill_ms = r.prefill_ms; s.first_chunk_ms = r.first_chunk_ms;
-    s.total_ms = (r.state == REQ_DONE ? r.t_done : now_ms()) - r.t_submit;
+    s.total_ms = (ended ? r.t_done : now_ms()) - r.t_submit;
     s.error = r.error;
     return s;
 }
@@ -913,7 +984,7 @@ void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, fl
         std::copy(r.codes.begin() + (size_t)frame_off * 16, r.codes.begin() + (size_t)(frame_off + nf) * 16, codes);
     }
     if (pcm && pcm_off >= 0) {
-        const bool done = r.state == REQ_DONE;
+        const bool done = r.state == REQ_DONE || r.state == REQ_CANCELLED;
         const int64_t avail = (int64_t)(done ? r.pcm.size() : r.pcm_ready);
         const float* src = done ? r.pcm.data() : (r.cs >= 0 ? pcm_pinned_ + (size_t)r.cs * slot_cap_ : nullptr);
         if (src && pcm_off < avail) { np = std::min(pcm_cap, avail - pcm_off); std::copy(src + pcm_off, src + pcm_off + np, pcm); }
@@ -930,7 +1001,7 @@ bool Engine::wait(int64_t id, double timeout_ms) {
             std::unique_lock<std::mutex> lk(mu_);
             auto it = reqs_.find(id);
             Q3_CHECK(it != reqs_.end(), "unknown request id");
-            if (it->second->state == REQ_DONE || it->second->state == REQ_FAILED) return true;
+            if (req_ended(it->second->state)) return true;
             if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
             if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
             // every live slot waits for text: no busy loop until another thread submits or appends
@@ -945,7 +1016,7 @@ void Engine::release(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
     auto it = reqs_.find(id);
     Q3_CHECK(it != reqs_.end(), "unknown request id");
-    Q3_CHECK(it->second->state == REQ_DONE || it->second->state == REQ_FAILED, "request still in flight");
+    Q3_CHECK(req_ended(it->second->state), "request still in flight");
     if (it->second->ev_admit) (void)hipEventDestroy(it->second->ev_admit);
     reqs_.erase(it);
 }
@@ -968,7 +1039,7 @@ void Engine::start_driver() {
             }
         } catch (const std::exception& ex) {
             std::lock_guard<std::mutex> lk(mu_);
-            for (auto& kv : reqs_) if (kv.second->state != REQ_DONE) { kv.second->state = REQ_FAILED; kv.second->error = ex.what(); }
+            for (auto& kv : reqs_) if (kv.second->state != REQ_DONE && kv.second->state != REQ_CANCELLED) { kv.second->state = REQ_FAILED; kv.second->error = ex.what(); }
             cv_.notify_all();
         }
     });

@@ -47,7 +47,6 @@ struct EngineStats { // accumulated since reset
     long graph_frames = 0;                       // frame-graph replays
 };
 
-enum ReqState { REQ_QUEUED = 0, REQ_RUNNING = 1, REQ_DRAINING = 2, REQ_DONE = 3, REQ_FAILED = -1 };
 struct ReqStatus {
     int state = REQ_QUEUED; int n_frames = 0; int64_t n_pcm = 0; // frames emitted / PCM samples decoded so far
     double queue_ms = 0, prefill_ms = 0, first_chunk_ms = 0, total_ms = 0;
@@ -72,6 +71,9 @@ public:
     // (finished, done or failed); throws for an unknown id, a request not submitted open, a closed trail or a total beyond max_prompt
     int append_trail(int64_t id, const int32_t* ids, int n, bool close);
     void trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* closed);
+    // [EXT] stops a request wherever it is; thread-safe and free of HIP calls (the scheduler retires the slot between two frame groups):
+    // 0 cancellation requested, 1 the request had already ended; throws for an unknown id
+    int cancel(int64_t id);
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -114,8 +116,10 @@ private:
     void admit(bool stalled); // stalled: every live slot waits for text (the admission quantum is not waited for)
     void run_group();
     void collect_appends();   // scheduler: new ids / close flags of live open slots into the slot table (upload in run_group)
+    void collect_cancels();   // scheduler: retires the slots of cancelled requests, drops the unstarted chunks of draining ones
     void harvest(bool block);
-    void finish_ar(Req* r);
+    void purge_chunks(Req* r);
+    void retire(Req* r, bool flush_tail); // the slot leaves the batch: EOS / max_steps (tail flushed) or a cancel (tail and unstarted chunks dropped)
     void decoder_main();
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
@@ -170,7 +174,8 @@ private:
     int64_t next_id_ = 1;
     int n_active_ = 0, n_draining_ = 0;
     bool trail_dirty_ = false;          // an append arrived since the scheduler last looked (mu_)
-    uint64_t wake_ = 0;                 // bumped by every submit / append: a driver idling on stalled slots sleeps until it changes (mu_)
+    std::vector<int64_t> cancel_ids_;   // cancelled requests the scheduler has not dealt with yet (mu_)
+    uint64_t wake_ = 0;                 // bumped by every submit / append / cancel: a driver idling on stalled slots sleeps until it changes (mu_)
     bool stalled_idle_ = false;         // the last step() ran nothing: every live slot waits for text and nothing else is in flight
     std::vector<Voice> voices_;
     std::thread driver_; bool driver_on_ = false, driver_stop_ = false;

@@ -357,6 +357,11 @@ int q3tts_group_release(q3tts_group* g, int64_t req_id) {
     if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
     return q3tts_release(e, rid_of(req_id));
 }
+int q3tts_group_cancel(q3tts_group* g, int64_t req_id) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_cancel(e, rid_of(req_id));
+}
 int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
     if (!g) return Q3TTS_ERR;
     for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;

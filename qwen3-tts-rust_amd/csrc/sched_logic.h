@@ -1,5 +1,6 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table and the prefill chunk packer.  tests/test_sched_logic_cpu.py builds it with plain g++.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, and the prefill chunk packer.
+// tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
 #include <algorithm>
@@ -101,6 +102,30 @@ inline FrameVariant live_variant(const SlotTable& t) { // of the live batch
     }
     return v;
 }
+
+enum ReqState { REQ_QUEUED = 0, REQ_RUNNING = 1, REQ_DRAINING = 2, REQ_DONE = 3, REQ_CANCELLED = 4, REQ_FAILED = -1 };
+inline bool req_ended(int state) { return state == REQ_DONE || state == REQ_CANCELLED || state == REQ_FAILED; }
+
+// [EXT] request cancellation: what a cancel does to a request in `state`.  in_wave: RUNNING with a slot reserved but still inside an
+// asynchronous prefill wave; live: RUNNING and stepping inside the frame graph; want_pcm: the request holds a codec stream.
+enum CancelAction {
+    CANCEL_NOTHING,     // already ended: the call returns 1
+    CANCEL_AT_ONCE,     // QUEUED: leaves the queue and is CANCELLED in the caller's thread
+    CANCEL_AT_ACTIVATE, // in a prefill wave: the wave is not disturbed, the request does not go live (then as RETIRE / RETIRE_FENCE)
+    CANCEL_RETIRE,      // live, codes only: the slot is retired between two frame groups, CANCELLED right there
+    CANCEL_RETIRE_FENCE,// live with PCM: retired without the tail flush, unstarted chunks dropped, a fence ends it once the codec is quiet
+    CANCEL_PURGE        // DRAINING: unstarted chunks dropped, the fence already queued ends it
+};
+inline CancelAction cancel_action(int state, bool in_wave, bool live, bool want_pcm) {
+    if (state == REQ_QUEUED) return CANCEL_AT_ONCE;
+    if (state == REQ_DRAINING) return CANCEL_PURGE;
+    if (state != REQ_RUNNING) return CANCEL_NOTHING;
+    if (!live) return in_wave ? CANCEL_AT_ACTIVATE : CANCEL_NOTHING; // RUNNING without a slot does not exist
+    return want_pcm ? CANCEL_RETIRE_FENCE : CANCEL_RETIRE;
+}
+// the state a request takes when its slot is retired (EOS, max_steps or a cancel) and when its fence completes
+inline int retired_state(bool want_pcm, bool cancelled) { return want_pcm ? REQ_DRAINING : cancelled ? REQ_CANCELLED : REQ_DONE; }
+inline int fenced_state(bool cancelled) { return cancelled ? REQ_CANCELLED : REQ_DONE; }
 
 // Prefill: the prompts of one admission wave form one token stream.  Fills one chunk of at most n_max tokens from the cursor on -- prompt rows,
 // per-token seq / slot / pos routing (engine.rs:306-314) -- and returns its token count; lasts = (request, index inside the chunk) of final prompt tokens.

@@ -55,7 +55,7 @@ class ReqStatus(C.Structure):
                 ("prefill_ms", C.c_double), ("first_chunk_ms", C.c_double), ("total_ms", C.c_double)]
 
 
-REQ_QUEUED, REQ_RUNNING, REQ_DRAINING, REQ_DONE, REQ_FAILED = 0, 1, 2, 3, -1
+REQ_QUEUED, REQ_RUNNING, REQ_DRAINING, REQ_DONE, REQ_CANCELLED, REQ_FAILED = 0, 1, 2, 3, 4, -1
 
 
 DECODE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32)
@@ -90,6 +90,7 @@ SYMBOLS = [
     "q3tts_op_linear", "q3tts_linear_plan", "q3tts_argmax_key",
     "q3tts_submit_trailing_open", "q3tts_trail_append", "q3tts_trail_progress", "q3tts_submit_text_streaming_open", "q3tts_text_append",
     "q3tts_group_submit_text_streaming_open", "q3tts_group_text_append", "q3tts_group_trail_append", "q3tts_group_trail_progress",
+    "q3tts_cancel", "q3tts_group_cancel",
 ]
 
 
@@ -192,6 +193,8 @@ def lib():
         L.q3tts_group_text_append.argtypes = L.q3tts_text_append.argtypes
         L.q3tts_group_trail_append.argtypes = L.q3tts_trail_append.argtypes
         L.q3tts_group_trail_progress.argtypes = L.q3tts_trail_progress.argtypes
+        L.q3tts_cancel.argtypes = [C.c_void_p, C.c_int64]
+        L.q3tts_group_cancel.argtypes = [C.c_void_p, C.c_int64]
         _lib = L
     return _lib
 
@@ -458,6 +461,14 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
 
     def release(self, rid):
         _chk(lib().q3tts_release(self.h, rid))
+
+    def cancel(self, rid):
+        """[EXT] stops a request wherever it is (any thread): True when the cancellation was requested -- the request reaches REQ_CANCELLED
+        within the scheduler's next steps and keeps what it produced until release --, False when it had already ended (raises on errors)"""
+        rc = lib().q3tts_cancel(self.h, rid)
+        if rc < 0:
+            _chk(rc)
+        return rc == 0
 
     def sched_start(self):
         _chk(lib().q3tts_sched_start(self.h))
