@@ -156,6 +156,24 @@ int q3tts_release(q3tts_engine* e, int64_t req_id);
  * flight any more: its codec work has completed, its PCM has left the staging region, its codec stream, slot and KV pages are free.
  * q3tts_wait returns 0 on it, q3tts_release accepts it.  Other requests in the batch are untouched.  q3tts_generate_batch* cannot be cancelled */
 int q3tts_cancel(q3tts_engine* e, int64_t req_id);
+/* [EXT] resume (q3tts_spec.h): r, opts, trail as q3tts_submit_trailing / _open (open != 0: the trail stays open);
+ * prefix_codes [n_prefix][16] copied.  n_prefix = 0 is the plain submission.
+ * The request continues from frames it is handed instead of generating them: frames 0 .. n_prefix-1 are prefix_codes, frame n_prefix on is
+ * generated, and every frame equals the frame the uninterrupted request emits (codes bit-identical, PCM within 1e-4 RMS with the same
+ * sample count).  The prefix comes from q3tts_fetch of a cancelled, failed or still running request, on this engine or another one with
+ * the same model.  n_frames starts at n_prefix and the prefix is fetchable at once; its PCM is decoded again once the request is admitted.
+ * The prompt, sampler, options and trailing ids must be those of the original request.  Exact continuation of a sampled request needs the
+ * ORIGINAL seed: has_seed = 0 draws a fresh one as always (the new frames are then a fresh draw behind the kept prefix; so with another seed).
+ * Refused (< 0, q3tts_last_error says why, nothing is queued): n_prefix < 0; n_prefix >= max_steps; prefix_codes NULL with n_prefix > 0;
+ * a prefix code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS; a residual code outside [0, 2048); an open trail with
+ * n_trail < n_prefix (those frames ran, so their ids were known); n_prompt + n_prefix beyond the slot's KV capacity; n_prefix > 0 under
+ * Q3_SPEC=ggml (as trailing ids there) */
+int q3tts_submit_resume(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                        const int32_t* trail_ids, int32_t n_trail, int32_t open,
+                        const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id);
+/* rows of one talker prefill launch: a longer admission wave (prompts + resumed prefixes) is prefilled in chunks of this many rows
+ * (an asynchronous wave, admitted beside running requests, in chunks of at most 256) */
+int32_t q3tts_engine_prefill_width(q3tts_engine* e);
 int q3tts_sched_start(q3tts_engine* e);
 int q3tts_sched_stop(q3tts_engine* e);
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy);
@@ -231,6 +249,10 @@ int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_
 int q3tts_group_wait(q3tts_group* g, int64_t req_id, double timeout_ms);
 int q3tts_group_release(q3tts_group* g, int64_t req_id);
 int q3tts_group_cancel(q3tts_group* g, int64_t req_id);       /* [EXT] q3tts_cancel, routed by the engine index the id carries */
+/* [EXT] q3tts_submit_resume on engine engine_index (-1 = round robin): a request cancelled or failed on one engine goes on on another */
+int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                              const int32_t* trail_ids, int32_t n_trail, int32_t open,
+                              const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
 int q3tts_group_stop(q3tts_group* g);
 /* q3tts_comm_*: ONE process per GPU (what `bench.py --gpus N` / torchrun-style launchers use).  Rank 0 makes the 128-byte id and ships it to
@@ -418,6 +440,9 @@ int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t
                          const float* top_p, const float* penalty, const uint64_t* seed, const int32_t* hist, const int32_t* hist_len,
                          int32_t hist_cap, int32_t n_draws, int32_t* out);
 int q3tts_op_project(const float* x, const float* w /* [n_out][n_in] */, const float* b, int32_t n_in, int32_t n_out, float* y);
+/* [EXT] resume test surface, host buffers: rows [n][2048] = the feedback rows of codes [n][16] (+ trail ids [n_trail], row f takes id f
+ * while f < n_trail; NULL / 0 = every row adds tts_pad) against the given tables (k_feedback_codes) */
+int q3tts_op_feedback_rows(const q3tts_assets* a, const int32_t* codes, int32_t n, const int32_t* trail_ids, int32_t n_trail, float* rows);
 /* One codec-decoder GEMM (csrc/codec.hip), as the decoder runs it or with a named kernel form forced.  out[m][n] = epilogue(sum_k A'[m][k] W[n][k]
  * + bias[n]) with K = taps * cin, k = j * cin + ci -> A' row m + (m / a_segT) * a_skip + j * dil, channel ci (a_segT = 0: unsegmented).  Output row m
  * starts at out_off + m * ldo + (m / o_segT) * o_skip floats of the out buffer, residual row m at m * ldr + (m / r_segT) * r_skip floats of res.

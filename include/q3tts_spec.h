@@ -294,6 +294,28 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  * q3tts_text_append(t[k:], is_last = 1) appends t_k .. t_{n-1}, Q3_TEXT_EOS and closes: together the trail of q3tts_submit_text_streaming(t).
  * The total number of trailing ids stays within max_prompt. */
 
+/* ---------------- resume [EXT] (q3tts_submit_resume, q3tts_group_submit_resume) ----------------
+ * Let R be a request: prompt, sampler config with a given seed, q3tts_gen_options, and a trailing-id list that is closed or open.
+ * Let c[0..k) be the first k frames R emits, 1 <= k < max_steps, none of them EOS.
+ * resume(R, c[0..k)) is a request whose frame f equals R's frame f for every f: frames 0..k-1 are taken from the caller, frames k.. are
+ * generated.  Nothing of R but its prompt, options, seed and emitted codes is needed:
+ *   prefill    the talker prefill runs over n_prompt + k rows.  Row n_prompt + f is the feedback row of frame f exactly as defined above,
+ *              (sum_q E_q[c[f][q]], q = 0..15 in order) + (f < n_trail ? text(trail[f]) : tts_pad), f32 left to right; a negative code
+ *              reads row 0 and a code past its table the zero row, as the frame's own feedback does.  It sits at position n_prompt + f in
+ *              the three running position streams (the fourth stays 0), as the decode step of that frame placed it.  The arithmetic is
+ *              independent of launch geometry, batch size and chunking, so the K/V rows are the rows the decode steps wrote
+ *   head       runs on the last row: the hidden row the predictor starts from, and the logits of frame k's code_0
+ *   penalty    the history is the distinct code_0 values of frames 0..k-1, so the penalty applies to that first head, greedy requests
+ *              included (a plain prefill's first head sees an empty history)
+ *   RNG        frame k's code_0 consumes talker draw k; the predictor stream stands at draw 15 k; greedy streams stay at 0
+ *   counters   the frame counter, the trailing cursor, the positions and the history length all start at k
+ *   codec      the stream is reset, then fed frames 0..k-1 in the chunks the scheduler would have cut (4 frames each), then the new frames:
+ *              codes and PCM are those of the whole utterance; n_frames starts at k and the prefix is fetchable at once
+ *   k = 0      is q3tts_submit_trailing / q3tts_submit_trailing_open itself
+ * An open trail must hold at least k ids when it is resumed: frames 0..k-1 ran, so their ids were known.
+ * Consequence: for any split point k the codes of resume(R, c[0..k)) are bit-identical to R's, the PCM within 1e-4 RMS with the same
+ * sample count.  With another seed (has_seed = 0 draws a fresh one) the prefix is kept and the rest is a fresh draw. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

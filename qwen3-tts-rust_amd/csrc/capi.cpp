@@ -51,6 +51,7 @@ int q3tts_engine_create(const q3tts_engine_params* p, q3tts_engine** out) {
 }
 void q3tts_engine_destroy(q3tts_engine* e) { delete e; }
 int32_t q3tts_engine_device(q3tts_engine* e) { return e ? e->e->device() : -1; }
+int32_t q3tts_engine_prefill_width(q3tts_engine* e) { return e ? e->e->talker().max_tok() : -1; }
 
 static GenRequest to_gen(const q3tts_request& q);
 static GenOptions to_opts(const q3tts_gen_options* o) {
@@ -120,6 +121,18 @@ int q3tts_submit_trailing_open(q3tts_engine* e, const q3tts_request* r, int32_t 
     GenRequest g = to_gen(*r);
     g.opts = to_opts(opts);
     g.trail = trail_ids; g.n_trail = n_trail; g.open = true;
+    *req_id = e->e->submit(g, want_pcm != 0, true);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_submit_resume(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, const int32_t* trail_ids,
+                        int32_t n_trail, int32_t open, const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && r && req_id, "null argument");
+    GenRequest g = to_gen(*r);
+    g.opts = to_opts(opts);
+    g.trail = trail_ids; g.n_trail = n_trail; g.open = open != 0;
+    g.prefix = prefix_codes; g.n_prefix = n_prefix;
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
@@ -286,6 +299,46 @@ const q3tts_assets* q3tts_engine_assets(q3tts_engine* e) { return e ? &e->assets
 int q3tts_assets_codec_embedding(const q3tts_assets* a, int32_t q, int32_t code, float* out) { Q3_API_BEGIN a->a->codec_embedding(q, code, out); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_assets_text_embedding(const q3tts_assets* a, int64_t tok, float* out) { Q3_API_BEGIN a->a->text_embedding(tok, out); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_assets_tts_pad(const q3tts_assets* a, float* out) { Q3_API_BEGIN std::copy(a->a->tts_pad(), a->a->tts_pad() + 2048, out); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+
+// [EXT] resume: k_feedback_codes against an assets file's tables, host buffers in and out
+int q3tts_op_feedback_rows(const q3tts_assets* a, const int32_t* codes, int32_t n, const int32_t* trail_ids, int32_t n_trail, float* rows) {
+    Q3_API_BEGIN
+    Q3_CHECK(a && a->a && codes && rows && n >= 1, "bad arguments");
+    Q3_CHECK(n_trail >= 0 && (n_trail == 0 || trail_ids), "trailing ids missing");
+    require_gpu();
+    const HostAssets& h = *a->a;
+    Q3_CHECK(h.n_codec == 16, "need 16 codec embedding tables");
+    std::vector<DevBuf<float>> tab(16);
+    std::vector<const float*> ptrs(16); std::vector<int64_t> nrows(16);
+    for (int q = 0; q < 16; q++) {
+        const size_t sz = (size_t)h.codec_rows[q] * Q3_EMBD;
+        tab[q].alloc(sz); tab[q].upload(h.codec[q], sz);
+        ptrs[q] = tab[q].p; nrows[q] = h.codec_rows[q];
+    }
+    DevBuf<const float*> d_ptrs(16); DevBuf<int64_t> d_nrows(16); DevBuf<float> d_pad(Q3_EMBD), d_text, d_rows((size_t)(n + 2) * Q3_EMBD);
+    DevBuf<int32_t> d_codes((size_t)n * 16), d_ids;
+    d_ptrs.upload(ptrs.data(), 16); d_nrows.upload(nrows.data(), 16); d_pad.upload(h.tts_pad(), Q3_EMBD); d_codes.upload(codes, (size_t)n * 16);
+    FeedbackIds fi;
+    const int nt = std::min(n_trail, n);
+    if (nt > 0) {
+        const int64_t tr = h.text_table ? h.text_rows : 0;
+        d_text.alloc((size_t)std::max<int64_t>(tr, 1) * Q3_EMBD);
+        if (tr > 0) d_text.upload(h.text_table, (size_t)tr * Q3_EMBD);
+        d_ids.alloc(nt); d_ids.upload(trail_ids, nt);
+        fi.ids = d_ids.p; fi.n_ids = nt; fi.table = d_text.p; fi.rows = tr;
+    }
+    // one guard row on either side of the device rows: a write outside [0, n) rows is an error here, not silent damage
+    std::vector<float> all((size_t)(n + 2) * Q3_EMBD, -12345.0f);
+    d_rows.upload(all.data(), all.size());
+    launch_feedback_codes(0, d_ptrs.p, d_nrows.p, d_codes.p, d_pad.p, d_rows.p + Q3_EMBD, n, &fi);
+    Q3_HIP(hipDeviceSynchronize());
+    d_rows.download(all.data(), all.size());
+    for (int i = 0; i < Q3_EMBD; i++)
+        Q3_CHECK(all[i] == -12345.0f && all[(size_t)(n + 1) * Q3_EMBD + i] == -12345.0f, "k_feedback_codes wrote outside its rows");
+    std::copy(all.begin() + Q3_EMBD, all.begin() + (size_t)(n + 1) * Q3_EMBD, rows);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 
 // host-side projection with the reference's exact loop (assets_manager.rs:383-399); used by the Boundary-A replay harness
 extern "C" int q3tts_assets_proj_out(const q3tts_assets* a) { return (int)a->a->proj_out; }

@@ -73,6 +73,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_tab_rows_.alloc(16); d_tab_rows_.upload(rows.data(), 16);
     // ---- KV pools ----
     const int pages_per_seq = (p.max_prompt + p.max_steps + 1 + 63) / 64;
+    kv_rows_ = (int64_t)pages_per_seq * 64;
     // talker page-table row B is the scratch sequence: idle slots of the frame graph read and write its single page, so the pages of a
     // slot that is being prefilled (or was just recycled) are never touched by the graph
     kv_t_.reset(new KvPool(talker_->hp().n_layer, talker_->hp().n_kv, B * pages_per_seq + 1, B + 1, pages_per_seq));
@@ -90,9 +91,11 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         talker_pf_.reset(new Transformer(*talker_, 256)); // shares the talker's device weights; own activation workspace
         Q3_HIP(hipStreamCreateWithFlags(&st_pf_, hipStreamNonBlocking));
         Q3_HIP(hipEventCreate(&pf_done_)); Q3_HIP(hipEventCreate(&pf_e0_));
-        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24) + ((size_t)1 << 16); // prompts of one admission: at most 4096 rows + routing tables
+        // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row)
+        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24 + 68) + ((size_t)1 << 16);
         Q3_HIP(hipHostMalloc((void**)&arena_pf_, arena_pf_cap_));
         d_prompt_pf_.alloc((size_t)256 * Q3_EMBD); d_pfa_seq_.alloc(256); d_pfa_slot_.alloc(256); d_pfa_pos_.alloc(4 * 256);
+        d_pfa_codes_.alloc((size_t)256 * 16); d_pfa_ids_.alloc(256);
     }
     // ---- per-slot state ----
     hist_stride_ = p.max_steps * 16;
@@ -105,6 +108,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_fb_.alloc((size_t)B * Q3_EMBD);
     d_prompt_.alloc((size_t)talker_->max_tok() * Q3_EMBD);
     d_pf_seq_.alloc(talker_->max_tok()); d_pf_slot_.alloc(talker_->max_tok()); d_pf_pos_.alloc(4 * (size_t)talker_->max_tok());
+    d_pf_codes_.alloc((size_t)talker_->max_tok() * 16); d_pf_ids_.alloc(talker_->max_tok());
     d_hist_.zero(); d_tlogits_.zero(); d_thidden_.zero();
     // predictor routing: pass i (i = 2..15) handles position i of every slot; tables are [16][B] so any graph width can use them
     std::vector<int32_t> seq(B), slot((size_t)16 * B), pos((size_t)16 * B * 4);
@@ -171,6 +175,7 @@ void* Engine::d2h_begin(const void* src, size_t bytes) {
 struct Engine::Req {
     int64_t id = 0;
     GenRequest r; std::vector<float> prompt_own; std::vector<int32_t> trail_own; bool want_pcm = false;
+    std::vector<int32_t> prefix_own; // [EXT] resume: the caller's frames [n_prefix][16]; codes starts as a copy of it and fed at n_prefix
     bool closed = false;  // [EXT] open trail (r.open): closed by append_trail; trail_own and closed change under mu_ only
     bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
@@ -343,25 +348,31 @@ void Engine::upload_slot_state() {
 void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
     size_t total = 0;
     std::vector<PromptRef> refs;
-    for (Req* r : batch) { total += (size_t)r->r.n_prompt; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot}); }
+    for (Req* r : batch) { total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix}); }
     const int chunk = talker_->max_tok();
     std::vector<int32_t> seq(chunk), slot(chunk), pos((size_t)4 * chunk);
-    PrefillCursor cur; std::vector<std::pair<int, int>> lasts;
+    PrefillCursor cur; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb;
     talker_->set_same_seq_tokens(true);
     for (size_t done = 0; done < total;) {
-        float* stage = (float*)stage_alloc(std::min<size_t>(total - done, (size_t)chunk) * Q3_EMBD * 4);
-        const int n = pack_prefill_chunk(refs, cur, chunk, stage, seq.data(), slot.data(), pos.data(), lasts);
-        Q3_HIP(hipMemcpyAsync(d_prompt_.p, stage, (size_t)n * Q3_EMBD * 4, hipMemcpyHostToDevice, st_));
+        const size_t n_max = std::min<size_t>(total - done, (size_t)chunk);
+        float* stage = (float*)stage_alloc(n_max * Q3_EMBD * 4);
+        int32_t* hc = (int32_t*)stage_alloc(n_max * 68); // [EXT] resume: codes [rows][16] and ids [rows] of the chunk's feedback rows
+        const int n = pack_prefill_chunk(refs, cur, chunk, stage, seq.data(), slot.data(), pos.data(), lasts, &fb);
+        for (auto& run : staged_runs(n, fb))
+            Q3_HIP(hipMemcpyAsync(d_prompt_.p + (size_t)run.first * Q3_EMBD, stage + (size_t)run.first * Q3_EMBD, (size_t)run.second * Q3_EMBD * 4, hipMemcpyHostToDevice, st_));
+        feedback_rows(st_, batch, fb, hc, d_pf_codes_.p, d_pf_ids_.p, d_prompt_.p);
         h2d(d_pf_seq_.p, seq.data(), (size_t)n * 4); h2d(d_pf_slot_.p, slot.data(), (size_t)n * 4); h2d(d_pf_pos_.p, pos.data(), (size_t)n * 16);
         TokMeta tm{d_pf_seq_.p, d_pf_slot_.p, d_pf_pos_.p};
         Transformer::Input in; in.x = d_prompt_.p; in.x_stride = Q3_EMBD;
         talker_->forward(st_, in, n, tm, kv_t_->view(), nullptr);
         for (auto& lb : lasts) {
             const int sb = refs[lb.first].slot, ti = lb.second;
-            if (sampled) {
+            const bool hist = resumed_penalised(batch[lb.first]->r); // [EXT] resume: the first head already sees a history, greedy slots included
+            if (sampled || hist) {
                 talker_->head(st_, ti, 1, 0, tl_stride_, d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_thidden_.p + (size_t)sb * Q3_EMBD);
                 SampleArgs sa{d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + sb, di(SF_TOPK) + sb, df(SF_TOPP) + sb,
                               di(SF_MASKEOS) + sb, d_rngkey_.p + (size_t)sb * 8, d_draws_.p + sb, d_keys_.p + (size_t)sb * 16, 16};
+                if (hist) head_history(sa, sb);
                 launch_sample(st_, sa, 1);
             } else {
                 ArgmaxEpi am{d_keys_.p + (size_t)sb * 16, 16, di(SF_MASKEOS) + sb, 0};
@@ -370,6 +381,40 @@ void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
         }
         done += (size_t)n;
     }
+}
+
+// [EXT] resume: the feedback rows of one prefill chunk.  The codes (64 B a frame) and trailing ids of every run go up through hc (pinned, not
+// reused before the stream has consumed it) and k_feedback_codes writes the rows into the chunk's input buffer, behind the staged rows' copies.
+void Engine::feedback_rows(hipStream_t st, const std::vector<Req*>& batch, const std::vector<FbRun>& fb, int32_t* hc, int32_t* d_codes, int32_t* d_ids,
+                           float* d_rows) {
+    if (fb.empty()) return;
+    int rows = 0;
+    for (const FbRun& f : fb) rows += f.n;
+    int32_t* hi = hc + (size_t)rows * 16;
+    std::vector<int> n_ids(fb.size());
+    int at = 0;
+    for (size_t i = 0; i < fb.size(); i++) {
+        const FbRun& f = fb[i]; Req* r = batch[f.req];
+        std::copy(r->prefix_own.begin() + (size_t)f.frame * 16, r->prefix_own.begin() + (size_t)(f.frame + f.n) * 16, hc + (size_t)at * 16);
+        std::lock_guard<std::mutex> lk(mu_); // an open trail grows under mu_; the ids of the prefix frames were there at submit
+        n_ids[i] = std::max(0, std::min(f.n, (int)r->trail_own.size() - f.frame));
+        std::copy(r->trail_own.begin() + std::min<size_t>(f.frame, r->trail_own.size()), r->trail_own.begin() + std::min<size_t>(f.frame, r->trail_own.size()) + n_ids[i], hi + at);
+        at += f.n;
+    }
+    Q3_HIP(hipMemcpyAsync(d_codes, hc, (size_t)rows * 64, hipMemcpyHostToDevice, st));
+    Q3_HIP(hipMemcpyAsync(d_ids, hi, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+    at = 0;
+    for (size_t i = 0; i < fb.size(); i++) {
+        const FbRun& f = fb[i];
+        FeedbackIds fi; fi.ids = d_ids + at; fi.n_ids = n_ids[i]; fi.table = d_text_.p; fi.rows = text_rows_;
+        launch_feedback_codes(st, d_tab_ptrs_.p, d_tab_rows_.p, d_codes + (size_t)at * 16, d_tts_pad_.p, d_rows + (size_t)f.row * Q3_EMBD, f.n, &fi);
+        at += f.n;
+    }
+}
+// the sampler arguments of a resumed slot's first head: the penalty with the history the prefix seeded (activate), no current frame
+void Engine::head_history(SampleArgs& sa, int b) const {
+    sa.penalty = df(SF_PEN) + b; sa.hist = d_hist_.p + (size_t)b * hist_stride_; sa.hist_stride = hist_stride_; sa.hist_len = di(SF_NFRAMES) + b;
+    sa.cur_key = nullptr; sa.cur_stride = 0;
 }
 
 // ---------------- decoder thread (the reference decodes on a second thread too, engine.rs:495-543): it owns every codec
@@ -505,6 +550,10 @@ void Engine::validate(const GenRequest& g) const {
     Q3_CHECK(g.n_trail == 0 || g.trail, "trailing ids missing");
     Q3_CHECK(!(talker_->ggml_mode() && (g.n_trail > 0 || g.open)),
              "trailing text ids are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
+    // [EXT] resume: the pure rule of sched_logic.h, before anything is queued
+    if (const char* why = resume_refusal(g.n_prompt, g.max_steps, g.prefix, g.n_prefix, g.open, g.n_trail, kv_rows_)) throw Error(why);
+    Q3_CHECK(!(talker_->ggml_mode() && g.n_prefix > 0),
+             "resuming from a prefix is not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
 }
 
 // The streaming-text state goes to the device on first use only: the real text table is 151936 x 2048 f32 (~1.24 GB).  Called from
@@ -538,6 +587,11 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
     if (g.open) r->trail_own.reserve((size_t)p_.max_prompt);
     r->trail_own.assign(g.trail, g.trail + g.n_trail);
     r->r.trail = r->trail_own.data();
+    if (g.n_prefix > 0) { // [EXT] resume: the request starts with the caller's frames
+        r->prefix_own.assign(g.prefix, g.prefix + (size_t)g.n_prefix * 16);
+        r->codes = r->prefix_own; r->fed = g.n_prefix;
+    }
+    r->r.prefix = r->prefix_own.data();
     r->want_pcm = want_pcm && codec_;
     r->t_submit = now_ms();
     r->seed = g.sampler.has_seed ? g.sampler.seed
@@ -672,7 +726,7 @@ void Engine::admit(bool stalled) {
         while (!pending_.empty() && reserved < B_) {
             Req* r = pending_.front();
             if (r->want_pcm && cs_free_.empty()) break; // every codec stream still drains: admit after the next harvest
-            if (async_pf_ && n_active_ > 0 && !batch.empty() && rows + (size_t)r->r.n_prompt > 4096) break; // staging arena of one asynchronous wave
+            if (async_pf_ && n_active_ > 0 && !batch.empty() && rows + (size_t)r->r.n_prompt + r->r.n_prefix > 4096) break; // staging arena of one asynchronous wave
             int slot = -1;
             for (int b = 0; b < B_; b++) if (!slot_req_[b]) { slot = b; break; }
             if (slot < 0) break;
@@ -681,7 +735,7 @@ void Engine::admit(bool stalled) {
             if (r->want_pcm) { r->cs = cs_free_.back(); cs_free_.pop_back(); }
             r->state = REQ_RUNNING; r->t_admit = now_ms();
             slot_req_[slot] = r; reserved++;
-            rows += (size_t)r->r.n_prompt;
+            rows += (size_t)r->r.n_prompt + r->r.n_prefix;
             batch.push_back(r);
         }
     }
@@ -726,13 +780,13 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
     size_t total = 0;
     std::vector<PromptRef> refs;
     for (Req* r : batch) {
-        total += (size_t)r->r.n_prompt; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot});
+        total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix});
         kv_t_->release(r->slot);
         kv_t_->ensure(r->slot, r->r.n_prompt + r->r.max_steps + 1, st_pf_);
     }
     const int chunk = talker_pf_->max_tok();
     unsigned char* cur = arena_pf_;
-    PrefillCursor pc; std::vector<std::pair<int, int>> lasts; size_t done_tok = 0;
+    PrefillCursor pc; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb; size_t done_tok = 0;
     Q3_HIP(hipEventRecord(pf_e0_, st_pf_));
     for (Req* r : batch) Q3_HIP(hipEventRecord(r->ev_admit, st_pf_));
     talker_pf_->set_same_seq_tokens(true);
@@ -742,9 +796,12 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
         int32_t* seq = (int32_t*)cur; cur += (size_t)n_max * 4;
         int32_t* slot = (int32_t*)cur; cur += (size_t)n_max * 4;
         int32_t* pos = (int32_t*)cur; cur += (size_t)n_max * 16;
+        int32_t* hc = (int32_t*)cur; cur += (size_t)n_max * 68; // [EXT] resume: codes and ids of the chunk's feedback rows
         Q3_CHECK((size_t)(cur - arena_pf_) <= arena_pf_cap_, "prefill staging arena overflow");
-        const int n = pack_prefill_chunk(refs, pc, n_max, stage, seq, slot, pos, lasts);
-        Q3_HIP(hipMemcpyAsync(d_prompt_pf_.p, stage, (size_t)n * Q3_EMBD * 4, hipMemcpyHostToDevice, st_pf_));
+        const int n = pack_prefill_chunk(refs, pc, n_max, stage, seq, slot, pos, lasts, &fb);
+        for (auto& run : staged_runs(n, fb))
+            Q3_HIP(hipMemcpyAsync(d_prompt_pf_.p + (size_t)run.first * Q3_EMBD, stage + (size_t)run.first * Q3_EMBD, (size_t)run.second * Q3_EMBD * 4, hipMemcpyHostToDevice, st_pf_));
+        feedback_rows(st_pf_, batch, fb, hc, d_pfa_codes_.p, d_pfa_ids_.p, d_prompt_pf_.p);
         Q3_HIP(hipMemcpyAsync(d_pfa_seq_.p, seq, (size_t)n * 4, hipMemcpyHostToDevice, st_pf_));
         Q3_HIP(hipMemcpyAsync(d_pfa_slot_.p, slot, (size_t)n * 4, hipMemcpyHostToDevice, st_pf_));
         Q3_HIP(hipMemcpyAsync(d_pfa_pos_.p, pos, (size_t)n * 16, hipMemcpyHostToDevice, st_pf_));
@@ -778,17 +835,28 @@ void Engine::activate() {
     for (Req* r : dropped) retire(r, false); // slot, KV pages and -- through the fence, behind the reset task already queued -- codec stream
     arena_used_ = 0; // st_ is idle between scheduler operations
     q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
-    const uint32_t zero = 0;
     for (Req* r : batch) {
         const int b = r->slot;
         slots_.load(b, r->r);
+        // [EXT] resume: frame k's code_0 is talker draw k and the predictor stream stands at 15 k; greedy streams stay at 0.  The history row
+        // takes the prefix frames as k_advance_keys would have written them, and the chunker the chunks the scheduler would have cut.
+        const int k = r->r.n_prefix;
+        const uint32_t draws = r->r.sampler.temperature > 0.0f ? (uint32_t)k : 0u, pdraws = 15u * (uint32_t)k;
+        if (k > 0) {
+            h2d(d_hist_.p + (size_t)b * hist_stride_, r->prefix_own.data(), (size_t)k * 64);
+            for (int f = 0; f < k; f++) {
+                int64_t fc[16];
+                for (int q = 0; q < 16; q++) fc[q] = r->prefix_own[(size_t)f * 16 + q];
+                r->chunker->push(fc, 16, false);
+            }
+        }
         StdRng rng(r->seed); // llama/mod.rs:648: the device regenerates this ChaCha12 stream from the key and a draw counter
         h2d(d_rngkey_.p + (size_t)b * 8, rng.key(), 32);
-        h2d(d_draws_.p + b, &zero, 4);
+        h2d(d_draws_.p + b, &draws, 4);
         if (r->r.opts.pred_sampled()) { // [EXT] the predictor's own stream: seed_from_u64(seed ^ Q3_PRED_SEED_XOR)
             StdRng prng(r->seed ^ (uint64_t)Q3_PRED_SEED_XOR);
             h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
-            h2d(d_pdraws_.p + b, &zero, 4);
+            h2d(d_pdraws_.p + b, &pdraws, 4);
         }
         h_pend_[b].clear();
         std::vector<int32_t> ids; // [EXT] streaming text: the slot's trailing ids -- of an open trail those appended so far (later: collect_appends)
@@ -809,6 +877,7 @@ void Engine::activate() {
             Q3_HIP(hipMemcpyAsync(d_thidden_.p + (size_t)b * Q3_EMBD, d_pf_hidden_.p + (size_t)b * Q3_EMBD, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_));
             SampleArgs sa{d_pf_logits_.p + (size_t)b * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + b, di(SF_TOPK) + b, df(SF_TOPP) + b,
                           di(SF_MASKEOS) + b, d_rngkey_.p + (size_t)b * 8, d_draws_.p + b, d_keys_.p + (size_t)b * 16, 16};
+            if (resumed_penalised(r->r)) head_history(sa, b);
             launch_sample(st_, sa, 1);
         }
         Q3_HIP(hipStreamSynchronize(st_));

@@ -108,6 +108,10 @@ private:
     void validate(const GenRequest& g) const; // prompt and max_steps ranges, then the options
     void ensure_text_stream(); // first request with trailing ids: text table + per-slot id rows go to the device
     void prefill(const std::vector<Req*>& batch, bool sampled);
+    // [EXT] resume (q3tts_spec.h): the prefix frames' feedback rows of a prefill chunk, made on the device; the first head's history
+    void feedback_rows(hipStream_t st, const std::vector<Req*>& batch, const std::vector<FbRun>& fb, int32_t* hc, int32_t* d_codes, int32_t* d_ids, float* d_rows);
+    void head_history(SampleArgs& sa, int b) const;
+    static bool resumed_penalised(const GenRequest& g) { return g.n_prefix > 0 && g.opts.penalised(); }
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
     // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
     // join the batch ("activate") between two frame groups once the prefill event has completed.
@@ -155,6 +159,8 @@ private:
     DevBuf<int32_t> d_pseq_, d_pslot_, d_ppos_;
     DevBuf<float> d_tlogits_, d_thidden_, d_pin_, d_fb_, d_prompt_;
     DevBuf<int32_t> d_pf_seq_, d_pf_slot_, d_pf_pos_;
+    DevBuf<int32_t> d_pf_codes_, d_pf_ids_, d_pfa_codes_, d_pfa_ids_; // [EXT] resume: codes / trailing ids of a prefill chunk's feedback rows (in-line, asynchronous)
+    int64_t kv_rows_ = 0; // positions a slot's KV pages hold
     int hist_stride_ = 0, tl_stride_ = 0;
     // [EXT] streaming-text state, allocated by the first request with n_trail > 0: the text table, [B][max_prompt] trailing ids
     DevBuf<float> d_text_; DevBuf<int32_t> d_trail_; int64_t text_rows_ = 0;

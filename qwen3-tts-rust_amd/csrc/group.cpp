@@ -362,6 +362,18 @@ int q3tts_group_cancel(q3tts_group* g, int64_t req_id) {
     if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
     return q3tts_cancel(e, rid_of(req_id));
 }
+int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                              const int32_t* trail_ids, int32_t n_trail, int32_t open, const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && r && req_id, "null argument");
+    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
+    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
+    int64_t id = 0;
+    if (q3tts_submit_resume(g->eng[i], r, want_pcm, opts, trail_ids, n_trail, open, prefix_codes, n_prefix, &id) != Q3TTS_OK) return Q3TTS_ERR;
+    *req_id = (id << kEngineBits) | i;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
     if (!g) return Q3TTS_ERR;
     for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;

@@ -206,6 +206,11 @@ struct TextTrail {
 // trail == null: the reference's feedback (every slot adds tts_pad)
 void launch_feedback_keys(hipStream_t st, const float* const* tables, const int64_t* table_rows, const q3_u64* keys, int key_stride,
                           const float* tts_pad, float* out, int ntok, const TextTrail* trail = nullptr);
+// [EXT] resume (q3tts_spec.h): rows [n][2048] = the feedback rows of codes [n][16] (device, int32).  ids (device) holds the trailing id of
+// rows [0, n_ids); the rows after it, and every row when ids is null, add tts_pad
+struct FeedbackIds { const int32_t* ids = nullptr; int n_ids = 0; const float* table = nullptr; int64_t rows = 0; };
+void launch_feedback_codes(hipStream_t st, const float* const* tables, const int64_t* table_rows, const int32_t* codes, const float* tts_pad,
+                           float* out, int n, const FeedbackIds* ids = nullptr);
 void launch_gather_rows_keys(hipStream_t st, const float* table, int64_t rows, const q3_u64* keys, int key_stride, int row_len,
                              float* dst, int ntok);
 struct AdvanceKeysArgs {
@@ -234,7 +239,8 @@ struct SampleArgs {
     const uint32_t* rng_key; uint32_t* draws;                           // [B][8] ChaCha12 key, [B] u32 words consumed so far
     q3_u64* out_key; int out_stride;                                    // receives pack_key(0, token)
     // [EXT] repetition penalty (k_sample only; null = off, spec "Repetition penalty"): the history of sequence b is code_0 of frames
-    // [0, hist_len[b]) at hist[b*hist_stride + f*16] plus key_code(cur_key[b*cur_stride]) (the current frame; a code outside [0, n) is ignored)
+    // [0, hist_len[b]) at hist[b*hist_stride + f*16] plus key_code(cur_key[b*cur_stride]) (the current frame; a code outside [0, n) is ignored;
+    // cur_key null = no current frame)
     const float* penalty = nullptr;
     const int32_t* hist = nullptr; int hist_stride = 0; const int32_t* hist_len = nullptr;
     const q3_u64* cur_key = nullptr; int cur_stride = 0;

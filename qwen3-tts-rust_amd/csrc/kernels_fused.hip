@@ -865,6 +865,47 @@ void launch_feedback_keys(hipStream_t st, const float* const* tables, const int6
     else hipLaunchKernelGGL(k_feedback_keys<false>, dim3(8, ntok), dim3(256), 0, st, tables, table_rows, keys, key_stride, tts_pad, out, TextTrail());
 }
 
+// [EXT] resume (q3tts_spec.h): the feedback rows of n frames a caller already holds, written straight into a prefill input buffer.  Row j is
+// k_feedback_keys' sum for codes[j][0..16) -- same order, same 0 / zero-row handling of codes outside a table -- and, with TRAIL, its last
+// addend is text(ids[j]) while j < n_ids (the fallback row for ids outside the table), tts_pad otherwise.
+template <bool TRAIL>
+__global__ void __launch_bounds__(256) k_feedback_codes(const float* const* __restrict__ tables, const int64_t* __restrict__ table_rows,
+                                                        const int32_t* __restrict__ codes, const float* __restrict__ tts_pad,
+                                                        float* __restrict__ out, FeedbackIds fi) {
+    const int tok = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    float acc = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        int c = codes[(size_t)tok * 16 + q];
+        if (c < 0) c = 0;
+        const float v = ((int64_t)c < table_rows[q]) ? tables[q][(size_t)c * 2048 + i] : 0.0f;
+        acc = acc + v;
+    }
+    float last;
+    if constexpr (TRAIL) {
+        if (tok < fi.n_ids) {
+            const int32_t id = fi.ids[tok];
+            if (id >= 0 && (int64_t)id < fi.rows) last = fi.table[(size_t)id * 2048 + i];
+            else { // as k_feedback_keys: fmod((float)((u64)id * 17 + i), 2) - 1
+                const float x = (float)((unsigned long long)(long long)id * 17ull + (unsigned long long)i);
+                last = (x < 16777216.0f ? (float)((uint32_t)x & 1u) : 0.0f) - 1.0f;
+            }
+        } else {
+            last = tts_pad[i];
+        }
+    } else {
+        last = tts_pad[i];
+    }
+    acc = acc + last;
+    out[(size_t)tok * 2048 + i] = acc;
+}
+void launch_feedback_codes(hipStream_t st, const float* const* tables, const int64_t* table_rows, const int32_t* codes, const float* tts_pad,
+                           float* out, int n, const FeedbackIds* ids) {
+    if (n <= 0) return;
+    if (ids && ids->n_ids > 0) hipLaunchKernelGGL(k_feedback_codes<true>, dim3(8, n), dim3(256), 0, st, tables, table_rows, codes, tts_pad, out, *ids);
+    else hipLaunchKernelGGL(k_feedback_codes<false>, dim3(8, n), dim3(256), 0, st, tables, table_rows, codes, tts_pad, out, FeedbackIds());
+}
+
 // project(m_hidden) and the pre-projected E_0[code_0] row side by side: predictor pass-A input rows [0,B) and [B,2B)
 __global__ void __launch_bounds__(256) k_gather_rows_keys(const float* __restrict__ table, int64_t rows, const u64* __restrict__ keys,
                                                           int key_stride, int row_len, float* __restrict__ dst) {

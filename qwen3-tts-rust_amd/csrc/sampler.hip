@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) k_sample(SampleArgs a) {
             const int c = h[(size_t)f * 16];
             if (c >= 0 && c < n) atomicOr(&seen[c >> 5], 1u << (c & 31));
         }
-        if (tid == 0) {
+        if (tid == 0 && a.cur_key) { // null: hist_len covers the whole history (the head of a resumed prefill)
             const int c = key_code(a.cur_key[(size_t)b * a.cur_stride]);
             if (c >= 0 && c < n) atomicOr(&seen[c >> 5], 1u << (c & 31));
         }

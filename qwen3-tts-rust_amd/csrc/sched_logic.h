@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, and the prefill chunk packer.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer and the checks of a resumed prefix.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -34,6 +34,8 @@ struct GenRequest {
     const int32_t* trail = nullptr; int n_trail = 0;
     // [EXT] live text append (q3tts_spec.h): the trail stays open; frames past the appended ids wait until append_trail() brings more
     bool open = false;
+    // [EXT] resume (q3tts_spec.h): frames 0 .. n_prefix-1 of the request, [n_prefix][16] codes; copied at submit
+    const int32_t* prefix = nullptr; int n_prefix = 0;
 };
 
 // Which launches one frame step issues: some live slot samples the talker / has a repetition penalty / samples the predictor / has trailing text
@@ -70,7 +72,7 @@ struct SlotTable {
     }
     void load(int b, const GenRequest& r) { // a slot about to go live (an open trail's count and flag: Engine::activate, under its lock)
         req[b] = &r;
-        hi(SF_FINISHED)[b] = 0; hi(SF_MAXFRAMES)[b] = r.max_steps; hi(SF_NFRAMES)[b] = 0; hi(SF_NPROMPT)[b] = r.n_prompt;
+        hi(SF_FINISHED)[b] = 0; hi(SF_MAXFRAMES)[b] = r.max_steps; hi(SF_NFRAMES)[b] = r.n_prefix; hi(SF_NPROMPT)[b] = r.n_prompt;
         hi(SF_MASKEOS)[b] = r.mask_eos ? Q3_CODEC_EOS : -1; hi(SF_NTRAIL)[b] = r.n_trail; hi(SF_OPEN)[b] = 0;
         hf(SF_TEMP)[b] = r.sampler.temperature; hi(SF_TOPK)[b] = r.sampler.top_k; hf(SF_TOPP)[b] = r.sampler.top_p;
         const GenOptions& o = r.opts;
@@ -129,17 +131,51 @@ inline int fenced_state(bool cancelled) { return cancelled ? REQ_CANCELLED : REQ
 
 // Prefill: the prompts of one admission wave form one token stream.  Fills one chunk of at most n_max tokens from the cursor on -- prompt rows,
 // per-token seq / slot / pos routing (engine.rs:306-314) -- and returns its token count; lasts = (request, index inside the chunk) of final prompt tokens.
-struct PromptRef { const float* rows; int n, slot; }; struct PrefillCursor { size_t req = 0; int tok = 0; };
+// [EXT] resume: a request's n_fb feedback rows follow its prompt at positions n .. n + n_fb - 1.  They are not staged: the device writes them
+// (k_feedback_codes), and fb lists each run of them inside the chunk.
+struct PromptRef { const float* rows; int n, slot; int n_fb = 0; }; struct PrefillCursor { size_t req = 0; int tok = 0; };
+struct FbRun { int req, row, frame, n; }; // request index, first row inside the chunk, first frame, number of rows
 inline int pack_prefill_chunk(const std::vector<PromptRef>& batch, PrefillCursor& c, int n_max, float* stage, int32_t* seq, int32_t* slot,
-                              int32_t* pos, std::vector<std::pair<int, int>>& lasts) {
+                              int32_t* pos, std::vector<std::pair<int, int>>& lasts, std::vector<FbRun>* fb = nullptr) {
     int n = 0;
+    if (fb) fb->clear();
     for (lasts.clear(); n < n_max && c.req < batch.size(); n++) {
         const PromptRef& r = batch[c.req];
-        std::copy(r.rows + (size_t)c.tok * Q3_EMBD, r.rows + (size_t)(c.tok + 1) * Q3_EMBD, stage + (size_t)n * Q3_EMBD);
+        if (c.tok < r.n) std::copy(r.rows + (size_t)c.tok * Q3_EMBD, r.rows + (size_t)(c.tok + 1) * Q3_EMBD, stage + (size_t)n * Q3_EMBD);
+        else if (fb) {
+            if (!fb->empty() && fb->back().req == (int)c.req && fb->back().row + fb->back().n == n) fb->back().n++;
+            else fb->push_back({(int)c.req, n, c.tok - r.n, 1});
+        }
         seq[n] = r.slot; slot[n] = c.tok; pos[4 * n] = pos[4 * n + 1] = pos[4 * n + 2] = c.tok; pos[4 * n + 3] = 0;
-        if (c.tok == r.n - 1) { lasts.emplace_back((int)c.req, n); c.req++; c.tok = 0; } else c.tok++;
+        if (c.tok == r.n + r.n_fb - 1) { lasts.emplace_back((int)c.req, n); c.req++; c.tok = 0; } else c.tok++;
     }
     return n;
+}
+// the runs of staged (host) rows of a chunk of n rows: what fb leaves out, as (first row, count)
+inline std::vector<std::pair<int, int>> staged_runs(int n, const std::vector<FbRun>& fb) {
+    std::vector<std::pair<int, int>> out;
+    int at = 0;
+    for (const FbRun& f : fb) { if (f.row > at) out.emplace_back(at, f.row - at); at = f.row + f.n; }
+    if (n > at) out.emplace_back(at, n - at);
+    return out;
+}
+
+// [EXT] resume (q3tts_spec.h): why a prefix cannot be resumed, or null.  Pure: the submitting thread runs it before anything is queued.
+// kv_rows = positions the slot's KV pages hold; codes [n_prefix][16].
+inline const char* resume_refusal(int n_prompt, int max_steps, const int32_t* codes, int n_prefix, bool open, int n_trail, int64_t kv_rows) {
+    if (n_prefix < 0) return "n_prefix must be >= 0";
+    if (n_prefix == 0) return nullptr;
+    if (n_prefix >= max_steps) return "n_prefix must be below max_steps: a resumed request generates at least one frame";
+    if (!codes) return "prefix codes missing";
+    for (int f = 0; f < n_prefix; f++) {
+        const int32_t* c = codes + (size_t)f * 16;
+        if (c[0] < 0 || c[0] >= Q3_SAMPLE_END) return "a prefix code_0 lies outside [0, Q3_SAMPLE_END)";
+        if (c[0] == Q3_CODEC_EOS) return "a prefix frame is EOS: the request had ended there";
+        for (int q = 1; q < 16; q++) if (c[q] < 0 || c[q] >= Q3_CODEBOOK_SIZE) return "a prefix residual code lies outside [0, 2048)";
+    }
+    if (open && n_trail < n_prefix) return "an open trail must hold at least n_prefix ids: the prefix frames ran, so their ids were known";
+    if ((int64_t)n_prompt + n_prefix + 1 > kv_rows) return "n_prompt + n_prefix exceeds the slot's KV capacity";
+    return nullptr;
 }
 
 } // namespace q3

@@ -91,6 +91,7 @@ SYMBOLS = [
     "q3tts_submit_trailing_open", "q3tts_trail_append", "q3tts_trail_progress", "q3tts_submit_text_streaming_open", "q3tts_text_append",
     "q3tts_group_submit_text_streaming_open", "q3tts_group_text_append", "q3tts_group_trail_append", "q3tts_group_trail_progress",
     "q3tts_cancel", "q3tts_group_cancel",
+    "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
 ]
 
 
@@ -195,6 +196,11 @@ def lib():
         L.q3tts_group_trail_progress.argtypes = L.q3tts_trail_progress.argtypes
         L.q3tts_cancel.argtypes = [C.c_void_p, C.c_int64]
         L.q3tts_group_cancel.argtypes = [C.c_void_p, C.c_int64]
+        L.q3tts_submit_resume.argtypes = [C.c_void_p, C.POINTER(Request), C.c_int32, C.POINTER(GenOptions), C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+        L.q3tts_group_submit_resume.argtypes = [C.c_void_p, C.c_int32] + L.q3tts_submit_resume.argtypes[1:]
+        L.q3tts_op_feedback_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.q3tts_engine_prefill_width.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -287,6 +293,17 @@ class Assets:
         return out[:n].copy(), trail[: nt.value].copy()
 
 
+def op_feedback_rows(assets, codes, trailing_ids=None):
+    """[EXT] resume: the feedback rows [n][2048] of codes [n][16] as k_feedback_codes writes them (row f adds text(trailing_ids[f]) while
+    f < len(trailing_ids), tts_pad after)"""
+    c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+    t = np.ascontiguousarray(trailing_ids, np.int32) if trailing_ids is not None else None
+    rows = np.zeros((c.shape[0], 2048), np.float32)
+    _chk(lib().q3tts_op_feedback_rows(assets.h, _p(c), c.shape[0], _p(t) if t is not None and t.size else None,
+                                      t.size if t is not None else 0, _p(rows)))
+    return rows
+
+
 class Sampler:  # LlamaSampler (llama/mod.rs:627-776)
     def __init__(self, temperature=0.0, top_k=0, top_p=1.0, seed=42):
         self.h = lib().q3tts_sampler_new(temperature, top_k, top_p, seed)
@@ -371,15 +388,23 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
     # ---- continuous-batching scheduler (q3tts_submit / poll / fetch / wait) ----
     def submit(self, prompt, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
                repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None,
-               open_trail=False):
+               open_trail=False, prefix_codes=None):
         """trailing_ids: [EXT] streaming-text input, one text id added to the feedback per frame (None = the reference's feedback);
-        open_trail: [EXT] live text append -- the trail stays open (trailing_ids may be None / empty), frames past it wait for trail_append"""
+        open_trail: [EXT] live text append -- the trail stays open (trailing_ids may be None / empty), frames past it wait for trail_append;
+        prefix_codes: [EXT] resume (q3tts_submit_resume) -- [k][16] frames the request already emitted: it goes on behind them, with every
+        other argument (the seed too) as the original submission had it"""
         pr = np.ascontiguousarray(prompt, np.float32)
         r = Request()
         self._fill(r, pr, 0, max_steps, temperature, top_k, top_p, seed, mask_eos)
         o = self._opts(0, repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p)
         rid = C.c_int64()
-        if trailing_ids is not None or open_trail:
+        if prefix_codes is not None:
+            pc = np.ascontiguousarray(prefix_codes, np.int32).reshape(-1, 16)
+            tr = np.ascontiguousarray(trailing_ids if trailing_ids is not None else [], np.int32)
+            _chk(lib().q3tts_submit_resume(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o) if o is not None else None,
+                                           _p(tr) if tr.size else None, tr.size, 1 if open_trail else 0, _p(pc) if pc.size else None,
+                                           pc.shape[0], C.byref(rid)))
+        elif trailing_ids is not None or open_trail:
             tr = np.ascontiguousarray(trailing_ids if trailing_ids is not None else [], np.int32)
             fn = lib().q3tts_submit_trailing_open if open_trail else lib().q3tts_submit_trailing
             _chk(fn(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o) if o is not None else None, _p(tr), tr.size,
@@ -469,6 +494,10 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         if rc < 0:
             _chk(rc)
         return rc == 0
+
+    def prefill_width(self):
+        """rows of one talker prefill launch (q3tts_engine_prefill_width)"""
+        return lib().q3tts_engine_prefill_width(self.h)
 
     def sched_start(self):
         _chk(lib().q3tts_sched_start(self.h))
