@@ -171,6 +171,20 @@ int q3tts_cancel(q3tts_engine* e, int64_t req_id);
 int q3tts_submit_resume(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                         const int32_t* trail_ids, int32_t n_trail, int32_t open,
                         const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id);
+/* [EXT] token log-probabilities (q3tts_spec.h): per frame 17 floats -- log softmax of the RAW head logits (before the repetition penalty,
+ * temperature / top-k / top-p and the mask_eos knob) at code_0 (column 0), at the 15 predictor codes (columns 1..15) and at Q3_CODEC_EOS in
+ * code_0's talker row (column 16: how close the model was to stopping).  Values are <= 0, within 1e-5 * max(1, |lp|) of the float64
+ * log-softmax of the same f32 logits; Q3TTS_LOGPROB_NONE marks a value nothing computed (the prefix rows of a resumed request).
+ * Recording is opt-in and changes neither codes nor PCM; with it off the frame graphs are exactly those of an engine that never heard of it.
+ * The first enable allocates [max_batch][max_steps + 1][17] + [15][max_batch][2048] floats on the device. */
+#define Q3TTS_LOGPROB_COLS 17
+#define Q3TTS_LOGPROB_NONE 1.0f
+/* requests submitted from now on (any q3tts_submit* form) record log-probabilities; thread-safe; the flag is read once per request at submit.
+ * q3tts_generate_batch* never records.  < 0: Q3_SPEC=ggml (as the other [EXT] features there) */
+int q3tts_engine_set_logprobs(q3tts_engine* e, int32_t on);
+/* rows [frame_off, frame_off+max_frames) available now, [got][17]; got_frames is what q3tts_fetch reports for the same arguments: the two grow
+ * together.  A cancelled request keeps the rows of the frames it keeps.  < 0: unknown id, or the request was not recording */
+int q3tts_fetch_logprobs(q3tts_engine* e, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
 /* rows of one talker prefill launch: a longer admission wave (prompts + resumed prefixes) is prefilled in chunks of this many rows
  * (an asynchronous wave, admitted beside running requests, in chunks of at most 256) */
 int32_t q3tts_engine_prefill_width(q3tts_engine* e);
@@ -253,6 +267,8 @@ int q3tts_group_cancel(q3tts_group* g, int64_t req_id);       /* [EXT] q3tts_can
 int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                               const int32_t* trail_ids, int32_t n_trail, int32_t open,
                               const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id);
+int q3tts_group_set_logprobs(q3tts_group* g, int32_t on);      /* [EXT] q3tts_engine_set_logprobs on every engine */
+int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
 int q3tts_group_stop(q3tts_group* g);
 /* q3tts_comm_*: ONE process per GPU (what `bench.py --gpus N` / torchrun-style launchers use).  Rank 0 makes the 128-byte id and ships it to
@@ -440,6 +456,10 @@ int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t
                          const float* top_p, const float* penalty, const uint64_t* seed, const int32_t* hist, const int32_t* hist_len,
                          int32_t hist_cap, int32_t n_draws, int32_t* out);
 int q3tts_op_project(const float* x, const float* w /* [n_out][n_in] */, const float* b, int32_t n_in, int32_t n_out, float* y);
+/* [EXT] test surface of k_logprob_rows, host buffers: logits [B][stride] (n <= stride, n <= 4096), chosen [B], extra_idx < 0 = none;
+ * out_chosen [B] = log softmax(row)[chosen], out_extra [B] (or NULL) = log softmax(row)[extra_idx] */
+int q3tts_op_logprob_rows(const float* logits, int32_t B, int32_t n, int32_t stride, const int32_t* chosen, int32_t extra_idx,
+                          float* out_chosen, float* out_extra);
 /* [EXT] resume test surface, host buffers: rows [n][2048] = the feedback rows of codes [n][16] (+ trail ids [n_trail], row f takes id f
  * while f < n_trail; NULL / 0 = every row adds tts_pad) against the given tables (k_feedback_codes) */
 int q3tts_op_feedback_rows(const q3tts_assets* a, const int32_t* codes, int32_t n, const int32_t* trail_ids, int32_t n_trail, float* rows);

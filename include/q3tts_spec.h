@@ -316,6 +316,25 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  * Consequence: for any split point k the codes of resume(R, c[0..k)) are bit-identical to R's, the PCM within 1e-4 RMS with the same
  * sample count.  With another seed (has_seed = 0 draws a fresh one) the prefix is kept and the rest is a fresh draw. */
 
+/* ---------------- token log-probabilities [EXT] (q3tts_engine_set_logprobs, q3tts_fetch_logprobs, q3tts_op_logprob_rows) ----------------
+ * A recording request carries Q3_LOGPROB_COLS = 17 floats per frame f:
+ *   column 0      log softmax(L_T)[code_0]: L_T = the talker head's raw f32 logits over the sampling range [0, Q3_SAMPLE_END), of the head
+ *                 that produced frame f's code_0 (the prefill head for the first generated frame, frame f-1's head otherwise)
+ *   column q      q = 1..15: log softmax(L_q)[code_q] over the 2048 predictor logits of step q
+ *   column 16     log softmax(L_T)[Q3_CODEC_EOS], same talker row as column 0: how close the model was to stopping at this frame
+ * Raw = before the repetition penalty, before temperature / top-k / top-p and without the mask_eos knob: the model's own distribution,
+ * whatever the sampler then did with it (column 16 is finite for a request that masks EOS).
+ * Arithmetic, f32:  m = max_i x_i (over finite and -inf entries);  s = sum_i q3_expf(x_i - m), per-lane strided partial sums, then a tree;
+ *   lp = (x_c - m) - logf(s).  An -inf logit at the chosen index gives -inf; results are <= 0, a positive rounding residue is clamped to 0.
+ * NOT a bit-exact spec item (the summation order is the kernel's, logf is the device library's): pinned to the float64 log-softmax of the same
+ * f32 logits within |lp - lp64| <= 1e-5 * max(1, |lp64|)  (a strided-plus-tree f32 sum of <= 4096 positive terms: < ~1e-6 relative; q3_expf
+ * and logf a few ulp each; two subtractions, one rounding each: together < ~2e-6 * max(1, |lp|), the tolerance is 5 x that).
+ * Q3_LOGPROB_NONE marks a value that was not computed -- rows 0 .. n_prefix-1 of a resumed request, requests that retire before a row is
+ * complete.  A real value is never positive.
+ * Recording changes nothing else: codes and PCM of a recording request are those of the same request without it. */
+#define Q3_LOGPROB_COLS 17
+#define Q3_LOGPROB_NONE 1.0f
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

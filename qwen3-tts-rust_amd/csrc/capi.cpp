@@ -190,6 +190,16 @@ int q3tts_wait(q3tts_engine* e, int64_t id, double timeout_ms) {
 }
 int q3tts_release(q3tts_engine* e, int64_t id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->release(id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_cancel(q3tts_engine* e, int64_t id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); return e->e->cancel(id); Q3_API_END(Q3TTS_ERR) }
+int q3tts_engine_set_logprobs(q3tts_engine* e, int32_t on) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_logprobs(on != 0); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_fetch_logprobs(q3tts_engine* e, int64_t id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int gf = 0;
+    e->e->fetch_logprobs(id, out, frame_off, max_frames, &gf);
+    if (got_frames) *got_frames = gf;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

@@ -599,6 +599,33 @@ int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t
     Q3_API_END(Q3TTS_ERR)
 }
 
+/* [EXT] token log-probabilities: k_logprob_rows in its plain form over host rows.  The device outputs carry one guard element on either side. */
+int q3tts_op_logprob_rows(const float* logits, int32_t B, int32_t n, int32_t stride, const int32_t* chosen, int32_t extra_idx, float* out_chosen,
+                          float* out_extra) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(logits && chosen && out_chosen && B >= 1 && n >= 1 && n <= 4096 && stride >= n, "bad arguments");
+    Q3_CHECK(extra_idx < n && (extra_idx < 0 || out_extra), "extra_idx must lie below n and needs out_extra");
+    DevBuf<float> dl((size_t)B * stride), dout((size_t)2 * (B + 2)); DevBuf<int32_t> dc(B);
+    dl.upload(logits, dl.n); dc.upload(chosen, B);
+    const float guard = -777.0f;
+    std::vector<float> h(dout.n, guard);
+    dout.upload(h.data(), h.size());
+    LogprobArgs a; // two columns per row: the chosen code's value and the extra index's, each in its own guarded array
+    a.p.logits = dl.p; a.p.stride = stride; a.p.n = n; a.p.chosen = dc.p; a.p.extra_idx = extra_idx; a.p.col = 0; a.p.col_extra = B + 2; a.n_first = 1;
+    a.out = dout.p + 1; a.out_stride = 1;
+    launch_logprob_rows(0, a, B);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    dout.download(h.data(), h.size());
+    Q3_CHECK(h[0] == guard && h[B + 1] == guard && h[B + 2] == guard && h[2 * B + 3] == guard, "k_logprob_rows wrote outside its rows");
+    for (int b = 0; b < B; b++) Q3_CHECK(extra_idx >= 0 || h[B + 3 + b] == guard, "k_logprob_rows wrote an extra value nobody asked for");
+    std::copy(h.begin() + 1, h.begin() + 1 + B, out_chosen);
+    if (extra_idx >= 0) std::copy(h.begin() + B + 3, h.begin() + B + 3 + B, out_extra);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d) {
     Q3_API_BEGIN
     require_gpu();

@@ -180,6 +180,7 @@ struct Engine::Req {
     bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
+    std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
     size_t pcm_ready = 0; // samples whose decode has completed (harvested events)
     std::unique_ptr<Chunker> chunker;
@@ -229,7 +230,9 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
 // [0, n_frames) in d_hist_ + the current frame's key, which k_advance_keys appends only after the head); v.pred: every predictor head writes
 // its 2048 logits and k_sample_pred draws the code (greedy slots take its first-max branch); v.trail: the feedback kernel reads the slot
 // table's n_frames / n_trail rows, d_trail_ and the text table; v.gate: a slot that waits runs through every launch between k_stall_save and
-// the gated advance and its work is discarded (q3tts_spec.h "live text append").  A clear flag leaves the launches as they are without it.
+// the gated advance and its work is discarded (q3tts_spec.h "live text append").  [EXT] v.lp: every head writes its logits -- the predictor's
+// into per-step slices of d_plp_ -- every slot draws through the samplers with its own parameters, and one k_logprob_rows launch between the
+// talker's sampler and the advance covers all 16 heads.  A clear flag leaves the launches as they are without it.
 void Engine::record_frame(FrameGraph& fg, FrameVariant v) {
     const int B = fg.width;
     const KvCache kvt = kv_t_->view(), kvp = kv_p_->view();
@@ -248,9 +251,10 @@ void Engine::record_frame(FrameGraph& fg, FrameVariant v) {
         Transformer::Input in; in.x = d_pin_.p; in.x_stride = dP_;
         predictor_->set_same_seq_tokens(true);
         predictor_->forward(st_, in, 2 * B, tm, kvp, nullptr);
-        if (v.pred) {
-            predictor_->head(st_, B, B, 0, Q3_CODEBOOK_SIZE, d_plogits_.p, Q3_CODEBOOK_SIZE);
-            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, df(SF_PTEMP), di(SF_PTOPK), df(SF_PTOPP), nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + 1, 16};
+        if (v.pred || v.lp) {
+            float* pl = v.lp ? d_plp_.p : d_plogits_.p;
+            predictor_->head(st_, B, B, 0, Q3_CODEBOOK_SIZE, pl, Q3_CODEBOOK_SIZE);
+            SampleArgs sa{pl, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, df(SF_PTEMP), di(SF_PTOPK), df(SF_PTOPP), nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + 1, 16};
             launch_sample_pred(st_, sa, B);
         } else {
             ArgmaxEpi am{d_keys_.p + 1, 16, nullptr, 0};
@@ -264,9 +268,10 @@ void Engine::record_frame(FrameGraph& fg, FrameVariant v) {
         if (pred_identity_pages_) { tm.uniform_pos = q + 1; kvq.page_table = nullptr; } // token t = sequence t = page t, position q+1 everywhere
         Transformer::Input in; in.x = d_proj_tab_[q].p; in.x_stride = dP_; in.idx_keys = d_keys_.p + q; in.idx_stride = 16;
         predictor_->forward(st_, in, B, tm, kvq, nullptr);
-        if (v.pred) {
-            predictor_->head(st_, 0, B, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_plogits_.p, Q3_CODEBOOK_SIZE);
-            SampleArgs sa{d_plogits_.p, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, df(SF_PTEMP), di(SF_PTOPK), df(SF_PTOPP), nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + q + 1, 16};
+        if (v.pred || v.lp) {
+            float* pl = v.lp ? d_plp_.p + (size_t)q * B_ * Q3_CODEBOOK_SIZE : d_plogits_.p;
+            predictor_->head(st_, 0, B, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, pl, Q3_CODEBOOK_SIZE);
+            SampleArgs sa{pl, Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, df(SF_PTEMP), di(SF_PTOPK), df(SF_PTOPP), nullptr, d_prngkey_.p, d_pdraws_.p, d_keys_.p + q + 1, 16};
             launch_sample_pred(st_, sa, B);
         } else {
             ArgmaxEpi am{d_keys_.p + q + 1, 16, nullptr, 0};
@@ -286,11 +291,22 @@ void Engine::record_frame(FrameGraph& fg, FrameVariant v) {
         Transformer::Input in; in.x = d_fb_.p; in.x_stride = Q3_EMBD;
         talker_->set_same_seq_tokens(false);
         talker_->forward(st_, in, B, tm, kvt, nullptr);
-        if (v.sampled || v.pen) { // llama/mod.rs:666-776 on device; greedy slots of a mixed batch take the kernel's T<=0 branch
+        if (v.sampled || v.pen || v.lp) { // llama/mod.rs:666-776 on device; greedy slots of a mixed batch take the kernel's T<=0 branch
             talker_->head(st_, 0, B, 0, tl_stride_, d_tlogits_.p, tl_stride_, nullptr, -1, d_thidden_.p);
             SampleArgs sa{d_tlogits_.p, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP), di(SF_TOPK), df(SF_TOPP), di(SF_MASKEOS), d_rngkey_.p, d_draws_.p, d_next_key0_.p, 1};
             if (v.pen) { sa.penalty = df(SF_PEN); sa.hist = d_hist_.p; sa.hist_stride = hist_stride_; sa.hist_len = di(SF_NFRAMES); sa.cur_key = d_keys_.p; sa.cur_stride = 16; }
             launch_sample(st_, sa, B);
+            if (v.lp) { // columns 1..15 of this frame's row, columns 0 and 16 of the next frame's: before k_advance_keys moves n_frames
+                LogprobArgs la;
+                la.p.logits = d_plp_.p; la.p.stride = Q3_CODEBOOK_SIZE; la.p.head_stride = (size_t)B_ * Q3_CODEBOOK_SIZE; la.p.n = Q3_CODEBOOK_SIZE;
+                la.p.key = d_keys_.p + 1; la.p.key_stride = 16; la.p.col = 1; la.n_first = 15;
+                la.t.logits = d_tlogits_.p; la.t.stride = tl_stride_; la.t.n = Q3_SAMPLE_END; la.t.key = d_next_key0_.p; la.t.key_stride = 1;
+                la.t.extra_idx = Q3_CODEC_EOS; la.t.col = 0; la.t.col_extra = Q3_LOGPROB_COLS - 1; la.t.row_ahead = 1;
+                la.out = d_lp_.p; la.out_stride = Q3_LOGPROB_COLS; la.out_rows = lp_rows_;
+                la.n_frames = di(SF_NFRAMES); la.finished = di(SF_FINISHED); la.max_frames = di(SF_MAXFRAMES); la.open = di(SF_OPEN);
+                la.n_trail = di(SF_NTRAIL); la.record = d_lp_rec_.p;
+                launch_logprob_rows(st_, la, B);
+            }
         } else {
             ArgmaxEpi am{d_next_key0_.p, 1, di(SF_MASKEOS), 0};
             talker_->head(st_, 0, B, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, d_thidden_.p);
@@ -368,12 +384,14 @@ void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
         for (auto& lb : lasts) {
             const int sb = refs[lb.first].slot, ti = lb.second;
             const bool hist = resumed_penalised(batch[lb.first]->r); // [EXT] resume: the first head already sees a history, greedy slots included
-            if (sampled || hist) {
+            const bool rec = batch[lb.first]->r.logprobs;       // [EXT] log-probabilities: the first frame's talker columns need the logits
+            if (sampled || hist || rec) {
                 talker_->head(st_, ti, 1, 0, tl_stride_, d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_thidden_.p + (size_t)sb * Q3_EMBD);
                 SampleArgs sa{d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + sb, di(SF_TOPK) + sb, df(SF_TOPP) + sb,
                               di(SF_MASKEOS) + sb, d_rngkey_.p + (size_t)sb * 8, d_draws_.p + sb, d_keys_.p + (size_t)sb * 16, 16};
                 if (hist) head_history(sa, sb);
                 launch_sample(st_, sa, 1);
+                if (rec) first_head_logprobs(st_, d_tlogits_.p + (size_t)sb * tl_stride_, sb, batch[lb.first]->r.n_prefix);
             } else {
                 ArgmaxEpi am{d_keys_.p + (size_t)sb * 16, 16, di(SF_MASKEOS) + sb, 0};
                 talker_->head(st_, ti, 1, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, d_thidden_.p + (size_t)sb * Q3_EMBD);
@@ -415,6 +433,13 @@ void Engine::feedback_rows(hipStream_t st, const std::vector<Req*>& batch, const
 void Engine::head_history(SampleArgs& sa, int b) const {
     sa.penalty = df(SF_PEN) + b; sa.hist = d_hist_.p + (size_t)b * hist_stride_; sa.hist_stride = hist_stride_; sa.hist_len = di(SF_NFRAMES) + b;
     sa.cur_key = nullptr; sa.cur_stride = 0;
+}
+void Engine::first_head_logprobs(hipStream_t st, const float* logits_row, int b, int row) {
+    LogprobArgs la;
+    la.t.logits = logits_row; la.t.stride = tl_stride_; la.t.n = Q3_SAMPLE_END; la.t.key = d_keys_.p + (size_t)b * 16; la.t.key_stride = 16;
+    la.t.extra_idx = Q3_CODEC_EOS; la.t.col = 0; la.t.col_extra = Q3_LOGPROB_COLS - 1;
+    la.out = d_lp_.p + ((size_t)b * lp_rows_ + row) * Q3_LOGPROB_COLS; la.out_stride = Q3_LOGPROB_COLS;
+    launch_logprob_rows(st, la, 1);
 }
 
 // ---------------- decoder thread (the reference decodes on a second thread too, engine.rs:495-543): it owns every codec
@@ -552,6 +577,7 @@ void Engine::validate(const GenRequest& g) const {
              "trailing text ids are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
     // [EXT] resume: the pure rule of sched_logic.h, before anything is queued
     if (const char* why = resume_refusal(g.n_prompt, g.max_steps, g.prefix, g.n_prefix, g.open, g.n_trail, kv_rows_)) throw Error(why);
+    Q3_CHECK(!g.logprobs || lp_ready_.load(), "the request records log-probabilities but recording was never enabled on this engine");
     Q3_CHECK(!(talker_->ggml_mode() && g.n_prefix > 0),
              "resuming from a prefix is not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
 }
@@ -578,11 +604,38 @@ void Engine::ensure_text_stream() {
     text_ready_ = true;
 }
 
-int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
+// [EXT] token log-probabilities: like the streaming-text state, the buffers go to the device on first use only (the predictor logits
+// slices are 15 x B x 8 KB); same locking, so the synchronous allocations never land inside another thread's capture.
+void Engine::set_logprobs(bool on) {
+    if (on) {
+        Q3_CHECK(!talker_->ggml_mode(),
+                 "token log-probabilities are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)");
+        std::lock_guard<std::mutex> lk(lp_mu_);
+        if (!lp_ready_.load()) {
+            std::lock_guard<std::mutex> cap(capture_mutex());
+            int prev = 0;
+            Q3_HIP(hipGetDevice(&prev));
+            Q3_HIP(hipSetDevice(dev_));
+            try {
+                lp_rows_ = p_.max_steps + 1;
+                d_lp_.alloc((size_t)B_ * lp_rows_ * Q3_LOGPROB_COLS);
+                d_plp_.alloc((size_t)15 * B_ * Q3_CODEBOOK_SIZE);
+                d_lp_rec_.alloc(B_); d_lp_rec_.zero();
+                Q3_HIP(hipStreamSynchronize(nullptr)); // the memset ran on the null stream; the engine's streams do not wait for it
+            } catch (...) { (void)hipSetDevice(prev); throw; }
+            Q3_HIP(hipSetDevice(prev));
+            lp_ready_ = true;
+        }
+    }
+    lp_on_ = on;
+}
+
+int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, bool may_record) {
     validate(g);
     if (g.n_trail > 0 || g.open) ensure_text_stream();
     std::unique_ptr<Req> r(new Req());
     r->r = g;
+    r->r.logprobs = may_record && (g.logprobs || lp_on_.load()); // [EXT] the engine's flag, read once per request
     if (copy_prompt) { r->prompt_own.assign(g.prompt, g.prompt + (size_t)g.n_prompt * Q3_EMBD); r->r.prompt = r->prompt_own.data(); }
     if (g.open) r->trail_own.reserve((size_t)p_.max_prompt);
     r->trail_own.assign(g.trail, g.trail + g.n_trail);
@@ -590,6 +643,7 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt) {
     if (g.n_prefix > 0) { // [EXT] resume: the request starts with the caller's frames
         r->prefix_own.assign(g.prefix, g.prefix + (size_t)g.n_prefix * 16);
         r->codes = r->prefix_own; r->fed = g.n_prefix;
+        if (r->r.logprobs) r->lp.assign((size_t)g.n_prefix * Q3_LOGPROB_COLS, Q3_LOGPROB_NONE); // nothing computed them
     }
     r->r.prefix = r->prefix_own.data();
     r->want_pcm = want_pcm && codec_;
@@ -865,6 +919,12 @@ void Engine::activate() {
         if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
         h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);
         h2d(d_next_key0_.p + b, armed, 8);
+        if (lp_ready_.load()) { // [EXT] log-probabilities: the slot's record flag; a recording slot's rows start as "not computed"
+            const int32_t rec = r->r.logprobs ? 1 : 0;
+            h2d(d_lp_rec_.p + b, &rec, 4);
+            if (rec) Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_lp_.p + (size_t)b * lp_rows_ * Q3_LOGPROB_COLS), (int)q3_f32_bits(Q3_LOGPROB_NONE),
+                                              (size_t)lp_rows_ * Q3_LOGPROB_COLS, st_));
+        }
         slots_.live[b] = 1;
     }
     upload_slot_state();
@@ -879,6 +939,7 @@ void Engine::activate() {
                           di(SF_MASKEOS) + b, d_rngkey_.p + (size_t)b * 8, d_draws_.p + b, d_keys_.p + (size_t)b * 16, 16};
             if (resumed_penalised(r->r)) head_history(sa, b);
             launch_sample(st_, sa, 1);
+            if (r->r.logprobs) first_head_logprobs(st_, d_pf_logits_.p + (size_t)b * tl_stride_, b, r->r.n_prefix);
         }
         Q3_HIP(hipStreamSynchronize(st_));
         n_prefilling_ = 0;
@@ -957,11 +1018,14 @@ void Engine::run_group() {
     const int32_t* p_nfr = (const int32_t*)d2h_begin(di(SF_NFRAMES), (size_t)width * 4);
     const int32_t* p_fin = (const int32_t*)d2h_begin(di(SF_FINISHED), (size_t)width * 4);
     std::vector<const int32_t*> p_hist(width, nullptr);
+    std::vector<const float*> p_lp(width, nullptr); // [EXT] the same rows of d_lp_, for the slots that record
     for (int b = 0; b < width; b++)
         if (slots_.live[b]) {
             Req* r = slot_req_[b];
             const int rows = std::min(group, r->r.max_steps - r->fed);
             if (rows > 0) p_hist[b] = (const int32_t*)d2h_begin(d_hist_.p + (size_t)b * hist_stride_ + (size_t)r->fed * 16, (size_t)rows * 64);
+            if (rows > 0 && r->r.logprobs)
+                p_lp[b] = (const float*)d2h_begin(d_lp_.p + ((size_t)b * lp_rows_ + r->fed) * Q3_LOGPROB_COLS, (size_t)rows * Q3_LOGPROB_COLS * 4);
         }
     Q3_HIP(hipStreamSynchronize(st_));
     { float ms = 0; Q3_HIP(hipEventElapsedTime(&ms, e0, e1)); stats.frame_loop_ms += ms; }
@@ -979,7 +1043,12 @@ void Engine::run_group() {
         if (h_nfr[b] > r->fed) { // hand new frames to the chunker (engine.rs:613-620)
             const int nnew = h_nfr[b] - r->fed;
             const int32_t* hbuf = p_hist[b];
-            { std::lock_guard<std::mutex> lk(mu_); r->codes.insert(r->codes.end(), hbuf, hbuf + (size_t)nnew * 16); r->fed = h_nfr[b]; }
+            {   // codes and log-probabilities grow in one critical section: fetch() and fetch_logprobs() never disagree on n_frames
+                std::lock_guard<std::mutex> lk(mu_);
+                r->codes.insert(r->codes.end(), hbuf, hbuf + (size_t)nnew * 16);
+                if (p_lp[b]) r->lp.insert(r->lp.end(), p_lp[b], p_lp[b] + (size_t)nnew * Q3_LOGPROB_COLS);
+                r->fed = h_nfr[b];
+            }
             for (int f = 0; f < nnew; f++) {
                 int64_t fc[16];
                 for (int q = 0; q < 16; q++) fc[q] = hbuf[(size_t)f * 16 + q];
@@ -1060,6 +1129,20 @@ void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, fl
     }
     if (got_frames) *got_frames = nf;
     if (got_pcm) *got_pcm = np;
+}
+
+void Engine::fetch_logprobs(int64_t id, float* out, int frame_off, int max_frames, int* got_frames) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    const Req& r = *it->second;
+    Q3_CHECK(r.r.logprobs, "the request does not record log-probabilities (q3tts_engine_set_logprobs was off when it was submitted)");
+    int nf = 0;
+    if (out && frame_off >= 0 && frame_off < r.fed && max_frames > 0) {
+        nf = std::min(max_frames, r.fed - frame_off);
+        std::copy(r.lp.begin() + (size_t)frame_off * Q3_LOGPROB_COLS, r.lp.begin() + (size_t)(frame_off + nf) * Q3_LOGPROB_COLS, out);
+    }
+    if (got_frames) *got_frames = nf;
 }
 
 bool Engine::wait(int64_t id, double timeout_ms) {
@@ -1144,7 +1227,7 @@ void Engine::generate_batch(const std::vector<GenRequest>& reqs, std::vector<Gen
     for (const GenRequest& g : reqs) { validate(g); Q3_CHECK(!g.open, "open trails need the submit / append interface"); } // before anything is queued
     for (const GenRequest& g : reqs) if (g.n_trail > 0) ensure_text_stream(); // the one step that can fail after validation: before queueing
     std::vector<int64_t> ids(n);
-    for (int i = 0; i < n; i++) ids[i] = submit(reqs[i], want_pcm, false);
+    for (int i = 0; i < n; i++) ids[i] = submit(reqs[i], want_pcm, false, false); // [EXT] a blocking batch never records log-probabilities
     double t_ar_end = 0;
     while (step()) {
         if (t_ar_end == 0 && n_active_ == 0) { std::lock_guard<std::mutex> lk(mu_); if (pending_.empty()) t_ar_end = now_ms(); }

@@ -12,6 +12,7 @@
 #include "host_logic.h"
 #include "sched_logic.h"
 #include "codec.h"
+#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <map>
@@ -66,7 +67,13 @@ public:
     void generate_batch(const std::vector<GenRequest>& reqs, std::vector<GenResult>& out, bool want_pcm);
 
     // ---- continuous-batching scheduler ----
-    int64_t submit(const GenRequest& r, bool want_pcm, bool copy_prompt = true); // thread-safe
+    // may_record = false: the request never records log-probabilities, whatever the engine's flag says (generate_batch)
+    int64_t submit(const GenRequest& r, bool want_pcm, bool copy_prompt = true, bool may_record = true); // thread-safe
+    // [EXT] token log-probabilities (q3tts_spec.h): requests submitted from now on record 17 floats per frame.  Thread-safe; the first
+    // enable allocates the device buffers ([B][max_steps + 1][17] rows, [15][B][2048] predictor logits); refused under Q3_SPEC=ggml
+    void set_logprobs(bool on);
+    // rows [frame_off, frame_off + max_frames) available now, [got][17]; the row count is fetch()'s; throws for a request that does not record
+    void fetch_logprobs(int64_t id, float* out, int frame_off, int max_frames, int* got_frames);
     // [EXT] live text append, thread-safe and free of HIP calls (the scheduler uploads): 0 appended, 1 the request no longer takes text
     // (finished, done or failed); throws for an unknown id, a request not submitted open, a closed trail or a total beyond max_prompt
     int append_trail(int64_t id, const int32_t* ids, int n, bool close);
@@ -112,6 +119,8 @@ private:
     void feedback_rows(hipStream_t st, const std::vector<Req*>& batch, const std::vector<FbRun>& fb, int32_t* hc, int32_t* d_codes, int32_t* d_ids, float* d_rows);
     void head_history(SampleArgs& sa, int b) const;
     static bool resumed_penalised(const GenRequest& g) { return g.n_prefix > 0 && g.opts.penalised(); }
+    // [EXT] log-probabilities: columns 0 and 16 of slot b's row `row` from the talker logits row a prefill head wrote and the key its sampler drew
+    void first_head_logprobs(hipStream_t st, const float* logits_row, int b, int row);
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
     // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
     // join the batch ("activate") between two frame groups once the prefill event has completed.
@@ -167,6 +176,11 @@ private:
     std::mutex text_mu_; bool text_ready_ = false; // text_ready_ is written under text_mu_ and capture_mutex()
     // [EXT] live text append: the stall save area ([B][2048] hidden rows, [B][2] draw counters), allocated with the above
     DevBuf<float> d_stall_hidden_; DevBuf<uint32_t> d_stall_draws_;
+    // [EXT] token log-probabilities, allocated when recording is first enabled: d_lp_ [B][lp_rows_][17] (row f = frame f; one row past
+    // max_steps takes the last frame's talker columns), d_plp_ [15][B][2048] the predictor heads' logits of one frame, d_lp_rec_ [B] the
+    // slot records.  lp_on_: what submit() reads; lp_ready_ is written under lp_mu_ and capture_mutex()
+    DevBuf<float> d_lp_, d_plp_; DevBuf<int32_t> d_lp_rec_; int lp_rows_ = 0;
+    std::mutex lp_mu_; std::atomic<bool> lp_on_{false}, lp_ready_{false};
     std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = FrameVariant::key(width)
     bool instrument_ = false; bool pred_identity_pages_ = false;
     std::vector<std::vector<int32_t>> h_pend_; std::vector<int> h_pend_off_; // appended ids not yet on the device: ids [off, off+size)

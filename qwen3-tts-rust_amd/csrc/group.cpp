@@ -374,6 +374,16 @@ int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+int q3tts_group_set_logprobs(q3tts_group* g, int32_t on) { // [EXT] q3tts_engine_set_logprobs on every engine
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    for (auto* e : g->eng) if (q3tts_engine_set_logprobs(e, on) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_fetch_logprobs(e, rid_of(req_id), out, frame_off, max_frames, got_frames);
+}
 int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
     if (!g) return Q3TTS_ERR;
     for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;

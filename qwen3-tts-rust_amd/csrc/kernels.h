@@ -250,4 +250,25 @@ void launch_sample(hipStream_t st, const SampleArgs& a, int B);
 // the penalty / mask fields must be null
 void launch_sample_pred(hipStream_t st, const SampleArgs& a, int B);
 
+// [EXT] token log-probabilities (logprob.hip, q3tts_spec.h): out[col] = log softmax(row)[code] per row, f32, raw logits.
+// One head group: row b of head h is logits[h*head_stride + b*stride + [0, n)), n <= 4096; its code is chosen[b] (plain int32, when set) or
+// key_code(key[b*key_stride + h]) (the packed keys the samplers write); the value goes to column col + h, and -- extra_idx >= 0 --
+// log softmax(row)[extra_idx] to column col_extra.  row_ahead: engine form only, rows past n_frames[b] the head's values belong to.
+struct LogprobHead {
+    const float* logits = nullptr; int stride = 0; size_t head_stride = 0; int n = 0;
+    const q3_u64* key = nullptr; int key_stride = 0; const int32_t* chosen = nullptr;
+    int extra_idx = -1; int col = 0, col_extra = -1; int row_ahead = 0;
+};
+// A launch covers n_first heads of shape p and, when t.logits is set, one more head of shape t (grid = B x heads).
+// Plain form (n_frames null): row b writes out[b*out_stride + column].  Engine form: slot b writes row n_frames[b] + row_ahead of its
+// out_rows rows, out[(b*out_rows + row)*out_stride + column], and only when it is live (!finished, n_frames < max_frames), does not
+// wait for text (open && n_frames >= n_trail), records (record[b] != 0) and the row exists.
+struct LogprobArgs {
+    LogprobHead p; int n_first = 0; LogprobHead t;
+    float* out = nullptr; int out_stride = 0, out_rows = 0;
+    const int32_t* n_frames = nullptr; const int32_t* finished = nullptr; const int32_t* max_frames = nullptr;
+    const int32_t* open = nullptr; const int32_t* n_trail = nullptr; const int32_t* record = nullptr;
+};
+void launch_logprob_rows(hipStream_t st, const LogprobArgs& a, int B);
+
 } // namespace q3

@@ -36,13 +36,17 @@ struct GenRequest {
     bool open = false;
     // [EXT] resume (q3tts_spec.h): frames 0 .. n_prefix-1 of the request, [n_prefix][16] codes; copied at submit
     const int32_t* prefix = nullptr; int n_prefix = 0;
+    // [EXT] token log-probabilities (q3tts_spec.h): the request records 17 floats per frame; set by Engine::submit from the engine's flag
+    bool logprobs = false;
 };
 
 // Which launches one frame step issues: some live slot samples the talker / has a repetition penalty / samples the predictor / has trailing text
 // ids (trail: the feedback kernel's streaming-text variant) / has an open trail (gate, implies trail: k_stall_save first, the gated k_advance_keys last)
+// / records log-probabilities (lp: every head writes its logits, as sampled / pen / pred make it, and k_logprob_rows follows the talker's sampler)
 struct FrameVariant {
-    bool sampled = false, pen = false, pred = false, trail = false, gate = false;
-    int key(int width) const { return width * 32 + gate * 16 + trail * 8 + pred * 4 + pen * 2 + sampled; } // of the frame-graph cache
+    bool sampled = false, pen = false, pred = false, trail = false, gate = false, lp = false;
+    // of the frame-graph cache; widths stay below 2^15, so the lp bit sits above every key without it and those keep their values
+    int key(int width) const { return lp * (1 << 20) + width * 32 + gate * 16 + trail * 8 + pred * 4 + pen * 2 + sampled; }
 };
 
 // Every per-slot scalar the host mirrors, as one host block and one device block laid out [field][B] in 4-byte words (int32 or float), each
@@ -100,7 +104,7 @@ inline FrameVariant live_variant(const SlotTable& t) { // of the live batch
         const GenRequest& r = *t.req[b];
         const bool open = t.hi(SF_OPEN)[b] != 0; // a closed trail leaves the gate, not the trail variant
         v.sampled |= r.sampler.temperature > 0.0f; v.pen |= r.opts.penalised(); v.pred |= r.opts.pred_sampled();
-        v.trail |= r.n_trail > 0 || r.open || open; v.gate |= open;
+        v.trail |= r.n_trail > 0 || r.open || open; v.gate |= open; v.lp |= r.logprobs;
     }
     return v;
 }

@@ -92,7 +92,11 @@ SYMBOLS = [
     "q3tts_group_submit_text_streaming_open", "q3tts_group_text_append", "q3tts_group_trail_append", "q3tts_group_trail_progress",
     "q3tts_cancel", "q3tts_group_cancel",
     "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
+    "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
 ]
+
+LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
+LOGPROB_NONE = 1.0    # Q3TTS_LOGPROB_NONE: not computed (a real value is never positive)
 
 
 def lib():
@@ -201,6 +205,11 @@ def lib():
         L.q3tts_group_submit_resume.argtypes = [C.c_void_p, C.c_int32] + L.q3tts_submit_resume.argtypes[1:]
         L.q3tts_op_feedback_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_engine_prefill_width.argtypes = [C.c_void_p]
+        L.q3tts_engine_set_logprobs.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_fetch_logprobs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        L.q3tts_group_set_logprobs.argtypes = L.q3tts_engine_set_logprobs.argtypes
+        L.q3tts_group_fetch_logprobs.argtypes = L.q3tts_fetch_logprobs.argtypes
+        L.q3tts_op_logprob_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -302,6 +311,35 @@ def op_feedback_rows(assets, codes, trailing_ids=None):
     _chk(lib().q3tts_op_feedback_rows(assets.h, _p(c), c.shape[0], _p(t) if t is not None and t.size else None,
                                       t.size if t is not None else 0, _p(rows)))
     return rows
+
+
+def op_logprob_rows(logits, chosen, n=None, extra_idx=-1):
+    """[EXT] k_logprob_rows over host rows: logits [B][stride] f32 (the first n columns of a row count, default all), chosen [B] ->
+    log softmax(row)[chosen] [B]; with extra_idx >= 0 also log softmax(row)[extra_idx] [B]"""
+    lg = np.ascontiguousarray(logits, np.float32)
+    lg = lg.reshape(-1, lg.shape[-1])
+    c = np.ascontiguousarray(chosen, np.int32).reshape(-1)
+    B, stride = lg.shape
+    out, extra = np.zeros(B, np.float32), np.zeros(B, np.float32)
+    _chk(lib().q3tts_op_logprob_rows(_p(lg), B, stride if n is None else n, stride, _p(c), extra_idx, _p(out), _p(extra) if extra_idx >= 0 else None))
+    return (out, extra) if extra_idx >= 0 else out
+
+
+def _fetch_logprobs(fn, h, rid, frame_off, max_frames):
+    out = np.zeros((max(max_frames, 1), LOGPROB_COLS), np.float32)
+    gf = C.c_int32()
+    _chk(fn(h, rid, _p(out), frame_off, max_frames, C.byref(gf)))
+    return out[: gf.value].copy()
+
+
+def group_set_logprobs(group, on):
+    """[EXT] q3tts_group_set_logprobs on a q3tts_group handle: every engine of the group records from now on (or stops)"""
+    _chk(lib().q3tts_group_set_logprobs(group, 1 if on else 0))
+
+
+def group_fetch_logprobs(group, rid, frame_off=0, max_frames=4096):
+    """[EXT] q3tts_group_fetch_logprobs: float32 [n][17] of a group request id"""
+    return _fetch_logprobs(lib().q3tts_group_fetch_logprobs, group, rid, frame_off, max_frames)
 
 
 class Sampler:  # LlamaSampler (llama/mod.rs:627-776)
@@ -495,6 +533,19 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
             _chk(rc)
         return rc == 0
 
+    def set_logprobs(self, on):
+        """[EXT] token log-probabilities (q3tts_engine_set_logprobs): requests submitted from now on record 17 floats per frame"""
+        _chk(lib().q3tts_engine_set_logprobs(self.h, 1 if on else 0))
+
+    def fetch_logprobs(self, rid, frame_off=0, max_frames=4096):
+        """[EXT] float32 [n][17] available now -- log softmax of the raw logits at code_0, the 15 predictor codes and (column 16) EOS;
+        LOGPROB_NONE where nothing was computed.  Raises for a request that does not record"""
+        return _fetch_logprobs(lib().q3tts_fetch_logprobs, self.h, rid, frame_off, max_frames)
+
+    def records(self, rid):
+        """whether the request records log-probabilities"""
+        return lib().q3tts_fetch_logprobs(self.h, rid, None, 0, 0, None) == 0
+
     def prefill_width(self):
         """rows of one talker prefill launch (q3tts_engine_prefill_width)"""
         return lib().q3tts_engine_prefill_width(self.h)
@@ -514,8 +565,11 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         """collects a finished request (codes [n][16], pcm) and releases it"""
         st = self.poll(rid)
         codes, pcm = self.fetch(rid, 0, max(st["n_frames"], 1), 0, st["n_pcm"] if want_pcm else 0)
+        out = {"codes": codes, "pcm": pcm if want_pcm else None, **st}
+        if self.records(rid):
+            out["logprobs"] = self.fetch_logprobs(rid, 0, max(st["n_frames"], 1))
         self.release(rid)
-        return {"codes": codes, "pcm": pcm if want_pcm else None, **st}
+        return out
 
     def generate_batch(self, prompts, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42, mask_eos=True, want_pcm=False,
                        pcm_per_frame=1920, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0,
