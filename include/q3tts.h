@@ -105,6 +105,10 @@ int q3tts_engine_stats(q3tts_engine* e, q3tts_stats* out);
 void q3tts_engine_reset_stats(q3tts_engine* e);
 void q3tts_engine_set_instrument(q3tts_engine* e, int32_t on);
 double q3tts_engine_bytes_per_step(q3tts_engine* e, int32_t batch, double mean_ctx);
+/* device bytes of the code predictor's layer-0 q/k/v table: for predictor passes 1..14 the engine builds, once at creation, the layer-0
+ * attention norm + q/k/v projection of every projected codec row (f32, 14 x rows x (n_head + 2 n_kv) * 128 floats; about 470 MB at full size)
+ * and the frame reads rows of it instead of recomputing them.  Same tokens either way.  0 = off: Q3_PRED_L0_TABLE=0 at creation, or Q3_SPEC=ggml */
+int64_t q3tts_pred_table_bytes(q3tts_engine* e);
 
 /* ---- continuous-batching scheduler (SURVEY 8b "q3tts_submit / q3tts_poll"; BASELINE config 3) ----
  * Requests queue up and are admitted into the engine's max_batch sequence slots as slots free up; every slot advances
@@ -553,6 +557,10 @@ typedef struct q3tts_attention_desc {
     int32_t form_ran;
 } q3tts_attention_desc;
 int q3tts_op_attention(q3tts_attention_desc* d);
+/* the same step with d->qkv holding a table of qkv_rows rows (qkv_stride floats each): token t reads the row the low word of
+ * keys[t * key_stride] selects (an argmax key, q3tts_argmax_key), as the code predictor's layer 0 reads its q/k/v table.  Every form but GGML.
+ * The table is uploaded whole and written back whole into d->qkv. */
+int q3tts_op_attention_keyed(q3tts_attention_desc* d, const uint64_t* keys, int32_t key_stride, int32_t qkv_rows);
 /* host only (no device needed): the form AUTO picks for d's ntok / n_head / n_kv / flags -> form_ran; no buffer is read */
 int q3tts_attention_plan(q3tts_attention_desc* d);
 

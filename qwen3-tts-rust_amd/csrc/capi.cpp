@@ -292,6 +292,7 @@ int q3tts_engine_stats(q3tts_engine* e, q3tts_stats* o) {
 void q3tts_engine_reset_stats(q3tts_engine* e) { if (e) e->e->reset_stats(); }
 void q3tts_engine_set_instrument(q3tts_engine* e, int32_t on) { if (e) e->e->set_instrument(on != 0); }
 double q3tts_engine_bytes_per_step(q3tts_engine* e, int32_t batch, double mean_ctx) { return e ? (double)e->e->bytes_per_frame_step(batch, mean_ctx) : 0.0; }
+int64_t q3tts_pred_table_bytes(q3tts_engine* e) { return e ? (int64_t)e->e->pred_table_bytes() : 0; }
 
 // ---------------- assets / prompt ----------------
 int q3tts_assets_open(const char* path, q3tts_assets** out) {

@@ -52,14 +52,27 @@ static void attention_op_check(const q3tts_attention_desc& d, int form) {
     }
 }
 
-static void attention_op_run(q3tts_attention_desc* dp) {
+// keys set (q3tts_op_attention_keyed): d.qkv is a table of qkv_rows rows and token t reads row key_code(keys[t * key_stride]); the table is
+// written back whole
+static void attention_op_run(q3tts_attention_desc* dp, const uint64_t* keys = nullptr, int key_stride = 0, int qkv_rows = 0) {
     Q3_CHECK(dp, "null attention descriptor");
     q3tts_attention_desc& d = *dp;
     Q3_CHECK(d.ntok >= 1 && d.n_head >= 1 && d.n_kv >= 1, "bad attention shape");
     const int form = d.form == Q3TTS_ATTN_AUTO ? attention_op_plan(d) : d.form;
     attention_op_check(d, form);
     const int nt = d.ntok, dq = d.n_head * 128, qs = d.qkv_stride;
-    DevBuf<float> qkv((size_t)nt * qs); qkv.upload(d.qkv, qkv.n);
+    DevBuf<q3_u64> dkeys;
+    if (keys) {
+        Q3_CHECK(form != ATTN_GGML, "the ggml form reads no keyed rows");
+        Q3_CHECK(key_stride >= 1 && qkv_rows >= 1, "bad key stride / table rows");
+        for (int t = 0; t < nt; t++) {
+            const int c = key_code(keys[(size_t)t * key_stride]);
+            Q3_CHECK(c >= 0 && c < qkv_rows, "a key selects a row outside the table");
+        }
+        dkeys.alloc((size_t)(nt - 1) * key_stride + 1); dkeys.upload((const q3_u64*)keys, dkeys.n);
+    }
+    DevBuf<float> qkv((size_t)(keys ? qkv_rows : nt) * qs); qkv.upload(d.qkv, qkv.n);
+    const QkvRows rows(qkv.p, qs, dkeys.p, key_stride);
     DevBuf<float> qn(128), kn(128); qn.upload(d.q_norm, 128); kn.upload(d.k_norm, 128);
     std::vector<float> hc, hs;
     build_rope_tables(d.rope_base, d.n_ctx, hc, hs);
@@ -83,14 +96,14 @@ static void attention_op_run(q3tts_attention_desc* dp) {
     switch (form) {
     case ATTN_UNFUSED:
         qrot.alloc((size_t)nt * dq);
-        launch_qk_rope_append(0, qkv.p, qs, nullptr, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, qrot.p, nt);
+        launch_qk_rope_append(0, rows, nullptr, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, qrot.p, nt);
         launch_attention(0, qrot.p, d.n_head, d.n_kv, tm, kv, d.layer, att.p, aq.p, ad.p, nt);
         break;
     case ATTN_FUSED:
-        launch_attention_fused(0, qkv.p, qs, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, aq.p, ad.p, nt);
+        launch_attention_fused(0, rows, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, aq.p, ad.p, nt);
         break;
     case ATTN_SHORT1: case ATTN_SHORT2:
-        launch_attention_short(0, form == ATTN_SHORT1 ? 1 : 2, qkv.p, qs, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv,
+        launch_attention_short(0, form == ATTN_SHORT1 ? 1 : 2, rows, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv,
                                d.layer, aq.p, ad.p, nt, att.p);
         break;
     default: // ATTN_GGML: q is rotated in place in the qkv copy
@@ -104,6 +117,7 @@ static void attention_op_run(q3tts_attention_desc* dp) {
     kc.download(d.k_cache, cache_halfs); vc.download(d.v_cache, cache_halfs);
     if (d.att && form != ATTN_FUSED) att.download(d.att, att.n);
     if (form != ATTN_GGML) { aq.download(d.aq, aq.n); ad.download(d.ad, ad.n); }
+    if (keys) qkv.download(const_cast<float*>(d.qkv), qkv.n);
     d.form_ran = form;
 }
 
@@ -348,6 +362,15 @@ int q3tts_op_attention(q3tts_attention_desc* d) {
     Q3_API_BEGIN
     require_gpu();
     attention_op_run(d);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_op_attention_keyed(q3tts_attention_desc* d, const uint64_t* keys, int32_t key_stride, int32_t qkv_rows) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(keys, "null keys");
+    attention_op_run(d, keys, key_stride, qkv_rows);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

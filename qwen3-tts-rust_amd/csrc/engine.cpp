@@ -71,6 +71,21 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     }
     d_tab_ptrs_.alloc(16); d_tab_ptrs_.upload(ptrs.data(), 16);
     d_tab_rows_.alloc(16); d_tab_rows_.upload(rows.data(), 16);
+    // Predictor passes 1..14 start from P_q[code]: layer 0's attention norm and q/k/v projection of that row depend on (q, code) alone, so
+    // Q_q[c] = qkv_0(P_q[c]) is built once here, by the predictor's own norm and matmul launches, and the frame reads rows of it instead
+    // of recomputing them for every slot in every pass (f32, bit for bit the in-frame result).  Q3_PRED_L0_TABLE=0 turns it off.
+    pred_l0_table_ = !predictor_->ggml_mode();
+    if (const char* e = std::getenv("Q3_PRED_L0_TABLE")) if (e[0] == '0') pred_l0_table_ = false;
+    if (pred_l0_table_) {
+        const int qs = (predictor_->hp().n_head + 2 * predictor_->hp().n_kv) * 128;
+        Transformer wide(*predictor_, 256); // the predictor's weights with a workspace of 256 rows per chunk (its own may be 2)
+        for (int q = 1; q < 15; q++) {
+            d_qkv0_tab_[q].alloc((size_t)assets_->codec_rows[q] * qs);
+            wide.build_layer0_qkv(st_, d_proj_tab_[q].p, dP_, assets_->codec_rows[q], d_qkv0_tab_[q].p);
+            pred_table_bytes_ += d_qkv0_tab_[q].n * sizeof(float);
+        }
+        Q3_HIP(hipStreamSynchronize(st_)); // `wide` frees its workspace here
+    }
     // ---- KV pools ----
     const int pages_per_seq = (p.max_prompt + p.max_steps + 1 + 63) / 64;
     kv_rows_ = (int64_t)pages_per_seq * 64;
@@ -220,8 +235,11 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
     const size_t head_t = (size_t)tl_stride_ * talker_->head_bytes_per_row();
     const size_t head_p = (size_t)15 * Q3_CODEBOOK_SIZE * predictor_->head_bytes_per_row();
     const size_t kv_per_tok = (size_t)t.n_layer * 2 * t.n_kv * 128 * 2;
+    // the predictor's weights count once per frame (they stay in cache across its 15 passes, and pass A still reads layer 0's q/k/v rows), so
+    // the layer-0 table takes nothing off them; it adds one f32 q/k/v row per slot in each of passes 1..14
+    const size_t tab_rows = pred_l0_table_ ? (size_t)batch * 14 * (size_t)(predictor_->hp().n_head + 2 * predictor_->hp().n_kv) * 128 * 4 : 0;
     return talker_->weight_bytes() + head_t + predictor_->weight_bytes() + head_p +
-           (size_t)((double)batch * mean_ctx * (double)kv_per_tok) + (size_t)batch * 17 * 8192;
+           (size_t)((double)batch * mean_ctx * (double)kv_per_tok) + (size_t)batch * 17 * 8192 + tab_rows;
 }
 
 // One frame for fg.width slots (engine.rs:545-641).  code_0 of the frame is already in keys[b][0]: it was produced at the end
@@ -267,6 +285,7 @@ void Engine::record_frame(FrameGraph& fg, FrameVariant v) {
         KvCache kvq = kvp;
         if (pred_identity_pages_) { tm.uniform_pos = q + 1; kvq.page_table = nullptr; } // token t = sequence t = page t, position q+1 everywhere
         Transformer::Input in; in.x = d_proj_tab_[q].p; in.x_stride = dP_; in.idx_keys = d_keys_.p + q; in.idx_stride = 16;
+        if (pred_l0_table_) { in.qkv0 = d_qkv0_tab_[q].p; in.qkv0_stride = (predictor_->hp().n_head + 2 * predictor_->hp().n_kv) * 128; }
         predictor_->forward(st_, in, B, tm, kvq, nullptr);
         if (v.pred || v.lp) {
             float* pl = v.lp ? d_plp_.p + (size_t)q * B_ * Q3_CODEBOOK_SIZE : d_plogits_.p;

@@ -100,6 +100,7 @@ public:
     EngineStats stats; void reset_stats() { stats = EngineStats(); }
     void set_instrument(bool on) { instrument_ = on; }
     size_t bytes_per_frame_step(int batch, double mean_ctx) const; // algorithmic HBM bytes of one batched frame step
+    size_t pred_table_bytes() const { return pred_table_bytes_; }  // the predictor's layer-0 q/k/v table (0 = off: Q3_PRED_L0_TABLE=0 or Q3_SPEC=ggml)
     hipStream_t stream() const { return st_; }
     int max_batch() const { return B_; }
     int device() const { return dev_; }
@@ -155,6 +156,7 @@ private:
     std::unique_ptr<CodecDecoder> codec_;
     // device assets
     DevBuf<float> d_codec_tab_[16]; DevBuf<float> d_proj_tab_[16];
+    DevBuf<float> d_qkv0_tab_[16]; bool pred_l0_table_ = false; size_t pred_table_bytes_ = 0; // Q_q[c]: the predictor's layer-0 q/k/v of P_q[c], q = 1..14
     DevBuf<float> d_proj_wt_, d_proj_wblk_, d_proj_b_, d_tts_pad_;
     DevBuf<const float*> d_tab_ptrs_; DevBuf<int64_t> d_tab_rows_;
     int dP_ = 0;

@@ -80,8 +80,21 @@ struct NormArgs {
 };
 void launch_rmsnorm_quant(hipStream_t st, const NormArgs& a, int ntok);
 
+// The q/k/v rows an attention front end reads: token t's row is base + t*stride, or -- keys set -- row code(keys[t*key_stride]) of a table
+// (the code predictor's layer-0 rows, which depend on the code alone and are built once at load).  Null keys is the plain addressing.
+struct QkvRows {
+    const float* base = nullptr;
+    const unsigned long long* keys = nullptr;   // argmax keys (low word = ~index)
+    int stride = 0, key_stride = 0;             // (pointers first: 24 bytes, so the kernels' next arguments stay among the preloaded ones)
+    QkvRows() = default;
+    QkvRows(const float* b, int s, const unsigned long long* k = nullptr, int ks = 0) : base(b), keys(k), stride(s), key_stride(ks) {}
+    __device__ __forceinline__ const float* row(int tok) const {
+        return base + (size_t)(keys ? (int)(~(uint32_t)keys[(size_t)tok * key_stride]) : tok) * stride;
+    }
+};
+
 // per-head q/k RMSNorm + NeoX M-RoPE; q -> qrot f32; k,v -> f16 paged cache (spec S4',S5,S6)
-void launch_qk_rope_append(hipStream_t st, const float* qkv, int qkv_stride, const float* parts_unused, int n_head, int n_kv,
+void launch_qk_rope_append(hipStream_t st, const QkvRows& qkv, const float* parts_unused, int n_head, int n_kv,
                            const float* q_norm_w, const float* k_norm_w, float eps, const float* rope_cos,
                            const float* rope_sin, int n_ctx, const int32_t* mrope_sec /*device [4]*/, const TokMeta& tm,
                            const KvCache& kv, int layer, float* qrot, int ntok);
@@ -149,12 +162,12 @@ inline NormArgs norm_args(const NormPro& p, int d, int8_t* xq, uint16_t* xd, con
     return NormArgs{p.h_in, p.h_stride, idx, p.idx_stride, p.idx_keys, p.parts, p.nparts, p.parts_stride, p.h_out, p.g, p.eps, d, xq, xd, p.xn_out};
 }
 void launch_gateup_swiglu(hipStream_t st, const Q8Mat& wgu, int ff, const NormPro& a, int8_t* aq, uint16_t* ad, int ntok);
-void launch_attention_fused(hipStream_t st, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
+void launch_attention_fused(hipStream_t st, const QkvRows& qkv, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad,
                             int ntok);
 // k_attention_short<hpw>: hpw = q heads per wave (1 or 2); needs n_head == 2*n_kv and every slot < 64 (page 0 of the sequence only)
-void launch_attention_short(hipStream_t st, int hpw, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
+void launch_attention_short(hipStream_t st, int hpw, const QkvRows& qkv, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad, int ntok,
                             float* att = nullptr /*optional f32 rows [ntok][n_head*128]*/);

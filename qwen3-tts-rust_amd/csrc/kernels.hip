@@ -952,14 +952,14 @@ void launch_rmsnorm_quant(hipStream_t st, const NormArgs& a, int ntok) {
 // per-head RMSNorm + NeoX (M-)RoPE + KV append (spec S4', S5, S6).  One wave per (token, head vector);
 // lane l owns the rotation pair (x[l], x[l+64]).
 // =====================================================================================================
-__global__ void __launch_bounds__(64) k_qk_rope_append(const float* __restrict__ qkv, int qkv_stride, int n_head, int n_kv,
+__global__ void __launch_bounds__(64) k_qk_rope_append(QkvRows qkv, int n_head, int n_kv,
                                                        const float* __restrict__ q_norm_w, const float* __restrict__ k_norm_w,
                                                        float eps, const float* __restrict__ rope_cos,
                                                        const float* __restrict__ rope_sin, int n_ctx,
                                                        const int32_t* __restrict__ mrope_sec, TokMeta tm, KvCache kv,
                                                        int layer, float* __restrict__ qrot) {
     const int hv = blockIdx.x, tok = blockIdx.y, lane = threadIdx.x;
-    const float* vec = qkv + (size_t)tok * qkv_stride + (size_t)hv * 128;
+    const float* vec = qkv.row(tok) + (size_t)hv * 128;
     float x1 = vec[lane], x2 = vec[lane + 64];
     const int seq = tm.seq_of(tok), slot = tm.slot_of(tok);
     const int page = kv.page_of(seq, slot >> 6);
@@ -995,11 +995,11 @@ __global__ void __launch_bounds__(64) k_qk_rope_append(const float* __restrict__
         Vb[ps * 128 + lane + 64] = f2h(x2);
     }
 }
-void launch_qk_rope_append(hipStream_t st, const float* qkv, int qkv_stride, const float*, int n_head, int n_kv,
+void launch_qk_rope_append(hipStream_t st, const QkvRows& qkv, const float*, int n_head, int n_kv,
                            const float* q_norm_w, const float* k_norm_w, float eps, const float* rope_cos,
                            const float* rope_sin, int n_ctx, const int32_t* mrope_sec, const TokMeta& tm,
                            const KvCache& kv, int layer, float* qrot, int ntok) {
-    hipLaunchKernelGGL(k_qk_rope_append, dim3(n_head + 2 * n_kv, ntok), dim3(64), 0, st, qkv, qkv_stride, n_head, n_kv,
+    hipLaunchKernelGGL(k_qk_rope_append, dim3(n_head + 2 * n_kv, ntok), dim3(64), 0, st, qkv, n_head, n_kv,
                        q_norm_w, k_norm_w, eps, rope_cos, rope_sin, n_ctx, mrope_sec, tm, kv, layer, qrot);
 }
 

@@ -373,7 +373,7 @@ void launch_gateup_swiglu(hipStream_t st, const Q8Mat& w, int ff, const NormPro&
 // to a different sequence, so no token needs another token's K/V from the same launch).  The current
 // position's K/V are taken from LDS (not re-read from global) so no intra-launch global visibility is needed.
 // ===================================================================================================
-__global__ void __launch_bounds__(256) k_attention_fused(const float* __restrict__ qkv, int qkv_stride, int n_head, int n_kv,
+__global__ void __launch_bounds__(256) k_attention_fused(QkvRows qkv, int n_head, int n_kv,
                                                          const float* __restrict__ q_norm_w, const float* __restrict__ k_norm_w,
                                                          float eps, const float* __restrict__ rope_cos,
                                                          const float* __restrict__ rope_sin, int n_ctx,
@@ -413,7 +413,7 @@ __global__ void __launch_bounds__(256) k_attention_fused(const float* __restrict
     }
     // ---- prologue: wave 0 = q head, wave 1 = k head, wave 2 = v head ----
     if (wave < 3) {
-        const float* vec = qkv + (size_t)tok * qkv_stride + (wave == 0 ? (size_t)h * 128 : wave == 1 ? (size_t)(n_head + kvh) * 128 : (size_t)(n_head + n_kv + kvh) * 128);
+        const float* vec = qkv.row(tok) + (wave == 0 ? (size_t)h * 128 : wave == 1 ? (size_t)(n_head + kvh) * 128 : (size_t)(n_head + n_kv + kvh) * 128);
         const float x1 = vec[lane], x2 = vec[lane + 64];
         const int page = kv.page_of(seq, slot >> 6), ps = slot & 63;
         if (wave < 2) {
@@ -571,11 +571,11 @@ __global__ void __launch_bounds__(256) k_attention_fused(const float* __restrict
         }
     }
 }
-void launch_attention_fused(hipStream_t st, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
+void launch_attention_fused(hipStream_t st, const QkvRows& qkv, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad,
                             int ntok) {
-    hipLaunchKernelGGL(k_attention_fused, dim3(n_head, ntok), dim3(256), 0, st, qkv, qkv_stride, n_head, n_kv, q_norm_w, k_norm_w,
+    hipLaunchKernelGGL(k_attention_fused, dim3(n_head, ntok), dim3(256), 0, st, qkv, n_head, n_kv, q_norm_w, k_norm_w,
                        eps, rope_cos, rope_sin, n_ctx, mrope_sec, tm, kv, layer, aq, ad);
 }
 
@@ -586,7 +586,7 @@ void launch_attention_fused(hipStream_t st, const float* qkv, int qkv_stride, in
 // waves of the pair and written by the even one (half the serial work per wave: narrow steps).  Same arithmetic as k_attention_fused (S7).
 // ===================================================================================================
 template <int HPW>
-__global__ void __launch_bounds__(64) k_attention_short(const float* __restrict__ qkv, int qkv_stride, int n_head, int n_kv,
+__global__ void __launch_bounds__(64) k_attention_short(QkvRows qkv, int n_head, int n_kv,
                                                         const float* __restrict__ q_norm_w, const float* __restrict__ k_norm_w, float eps,
                                                         const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, int n_ctx,
                                                         const int32_t* __restrict__ mrope_sec, TokMeta tm, KvCache kv, int layer,
@@ -600,6 +600,7 @@ __global__ void __launch_bounds__(64) k_attention_short(const float* __restrict_
     Q3_STAMP(0);
     const bool writer = HPW == 2 || (blockIdx.x & 1) == 0;
     const int tok = blockIdx.y, lane = threadIdx.x;
+    const float* tv = qkv.row(tok); // (a keyed row's address hangs on a scalar load of the key: issued in front of the K/V loads)
     const float scale = 0.08838834764831845f;
     const int jj = lane >> 4, dc = lane & 15;
     const int seq = tm.seq_of(tok), slot = tm.slot_of(tok), n = slot + 1;
@@ -622,7 +623,6 @@ __global__ void __launch_bounds__(64) k_attention_short(const float* __restrict_
     if (pp < 0) pp = 0;
     if (pp > n_ctx - 1) pp = n_ctx - 1;
     const float cs = rope_cos[(size_t)pp * 64 + lane], sn = rope_sin[(size_t)pp * 64 + lane];
-    const float* tv = qkv + (size_t)tok * qkv_stride;
 #pragma unroll
     for (int which = 0; which < HPW + 1; which++) { // q heads, then k
         const float* vec = tv + (which < HPW ? (size_t)(h0 + which) * 128 : (size_t)(n_head + kvh) * 128);
@@ -748,14 +748,14 @@ int short_attn_hpw1_max() {
     static const int v = [] { const char* e = std::getenv("Q3_SHORT_ATTN_HPW1_MAX"); return e ? atoi(e) : 128; }();
     return v;
 }
-void launch_attention_short(hipStream_t st, int hpw, const float* qkv, int qkv_stride, int n_head, int n_kv, const float* q_norm_w,
+void launch_attention_short(hipStream_t st, int hpw, const QkvRows& qkv, int n_head, int n_kv, const float* q_norm_w,
                             const float* k_norm_w, float eps, const float* rope_cos, const float* rope_sin, int n_ctx,
                             const int32_t* mrope_sec, const TokMeta& tm, const KvCache& kv, int layer, int8_t* aq, uint16_t* ad, int ntok, float* att) {
     if (hpw == 1)
-        hipLaunchKernelGGL(k_attention_short<1>, dim3(n_head, ntok), dim3(64), 0, st, qkv, qkv_stride, n_head, n_kv, q_norm_w, k_norm_w, eps, rope_cos,
+        hipLaunchKernelGGL(k_attention_short<1>, dim3(n_head, ntok), dim3(64), 0, st, qkv, n_head, n_kv, q_norm_w, k_norm_w, eps, rope_cos,
                            rope_sin, n_ctx, mrope_sec, tm, kv, layer, aq, ad, att);
     else
-        hipLaunchKernelGGL(k_attention_short<2>, dim3(n_kv, ntok), dim3(64), 0, st, qkv, qkv_stride, n_head, n_kv, q_norm_w, k_norm_w, eps, rope_cos,
+        hipLaunchKernelGGL(k_attention_short<2>, dim3(n_kv, ntok), dim3(64), 0, st, qkv, n_head, n_kv, q_norm_w, k_norm_w, eps, rope_cos,
                            rope_sin, n_ctx, mrope_sec, tm, kv, layer, aq, ad, att);
 }
 

@@ -2,6 +2,7 @@
 #include "transformer.h"
 #include <cstdlib>
 #include <cmath>
+#include <algorithm>
 
 namespace q3 {
 
@@ -393,17 +394,16 @@ void Transformer::qkv(const Pass& s, const Layer& L, const NormPro& a) {
     timed(timer, s.st, (double)L.wqkv.bytes(), [&] { launch_gemv_q8_norm(s.st, L.wqkv, 0, L.wqkv.N, a, qkv_.p, L.wqkv.N, s.ntok, nullptr); });
 }
 
-void Transformer::attention(const Pass& s, const Layer& L, int l) {
-    const int qs = (hp_.n_head + 2 * hp_.n_kv) * 128;
+void Transformer::attention(const Pass& s, const Layer& L, int l, const QkvRows& rows) {
     float* att = float_mode_ ? attf_.p : nullptr; // f32 rows for the float o-projection; the int8 copy (aq_, ad_) is always written
     if (s.af == ATTN_SHORT1 || s.af == ATTN_SHORT2)
-        launch_attention_short(s.st, s.af == ATTN_SHORT1 ? 1 : 2, qkv_.p, qs, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
+        launch_attention_short(s.st, s.af == ATTN_SHORT1 ? 1 : 2, rows, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
                                n_ctx_, d_mrope_.p, s.tm, s.kv, l, aq_.p, ad_.p, s.ntok, att);
     else if (s.af == ATTN_FUSED)
-        launch_attention_fused(s.st, qkv_.p, qs, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p, s.tm,
+        launch_attention_fused(s.st, rows, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p, s.tm,
                                s.kv, l, aq_.p, ad_.p, s.ntok);
     else {
-        launch_qk_rope_append(s.st, qkv_.p, qs, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p,
+        launch_qk_rope_append(s.st, rows, nullptr, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p,
                               s.tm, s.kv, l, qrot_.p, s.ntok);
         launch_attention(s.st, qrot_.p, hp_.n_head, hp_.n_kv, s.tm, s.kv, l, att, aq_.p, ad_.p, s.ntok);
     }
@@ -435,7 +435,8 @@ void Transformer::gate_up(const Pass& s, const Layer& L, const NormPro& b) {
 
 void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMeta& tm, const KvCache& kv, float* hidden_out) {
     Q3_CHECK(ntok >= 1 && ntok <= max_tok_, "ntok out of range");
-    const int d = hp_.n_embd;
+    Q3_CHECK(!in.qkv0 || (in.idx_keys && !ggml_mode_), "layer-0 q/k/v rows need the argmax keys that select them (and are not for the ggml mode)");
+    const int d = hp_.n_embd, qs = (hp_.n_head + 2 * hp_.n_kv) * 128;
     Pass s{st, ntok, tm, kv, attention_form(ntok), false, false};
     last_fused_ = false; last_ntok_ = ntok;
     if (s.af == ATTN_GGML) { forward_ggml(st, in, ntok, tm, kv, hidden_out); return; }
@@ -460,16 +461,41 @@ void Transformer::forward(hipStream_t st, const Input& in, int ntok, const TokMe
         const Layer& L = layers_[l];
         NormPro a = pro(hb, parts_d_.p, npd, h_.p, L.attn_norm, xn); // the previous layer's down-projection is consumed here
         if (l == 0) { a.h_in = in.x; a.h_stride = in.x_stride; a.idx_keys = in.idx_keys; a.idx_stride = in.idx_stride; a.parts = nullptr; a.nparts = 0; }
-        qkv(s, L, a);
-        attention(s, L, l);
+        NormPro b = pro(h_.p, parts_o_.p, 1, hb, L.ffn_norm, xn);
+        const bool tab0 = l == 0 && in.qkv0; // layer 0's q/k/v come from the caller's table: no norm, no projection, and h_ is not written
+        if (tab0) { b.h_in = in.x; b.h_stride = in.x_stride; b.idx_keys = in.idx_keys; b.idx_stride = in.idx_stride; }
+        else qkv(s, L, a);
+        attention(s, L, l, tab0 ? QkvRows(in.qkv0, in.qkv0_stride, in.idx_keys, in.idx_stride) : QkvRows(qkv_.p, qs));
         linear(s, L.wo, L.fo, attf_.p, aq_.p, ad_.p, parts_o_.p);
-        gate_up(s, L, pro(h_.p, parts_o_.p, 1, hb, L.ffn_norm, xn));
+        gate_up(s, L, b);
         linear(s, L.wdown, L.fdown, actf_.p, fq_.p, fd_.p, parts_d_.p);
     }
     if (s.fused) { if (hidden_out) head(st, 0, ntok, 0, 0, nullptr, 0, nullptr, -1, hidden_out); } // the final norm is the prologue of head()
     else {
         norm(s, pro(h_.p, parts_d_.p, npd, nullptr, output_norm_, hidden_out ? hidden_out : hid_.p));
         if (float_mode_ && hidden_out) launch_copy_f32(st, hidden_out, hid_.p, (size_t)ntok * d); // head() reads hid_
+    }
+    Q3_LAUNCH_CHECK();
+}
+
+// out[r] = layer 0's attention norm + q/k/v projection of row r of x, through the unfused steps of the layer walk (norm, linear) in chunks of
+// max_tok rows.  The norm works per token and every linear form gives the same bits, so a row equals what forward() computes for that input
+// in any step; a caller with a table of possible inputs builds the rows once and passes them as Input::qkv0.
+void Transformer::build_layer0_qkv(hipStream_t st, const float* x, int x_stride, int64_t rows, float* out) {
+    Q3_CHECK(!ggml_mode_, "the ggml mode takes no layer-0 q/k/v rows");
+    const int d = hp_.n_embd, qs = (hp_.n_head + 2 * hp_.n_kv) * 128;
+    const Layer& L = layers_[0];
+    const TokMeta tm{nullptr, nullptr, nullptr}; const KvCache kv{}; // (the two steps touch neither)
+    for (int64_t r0 = 0; r0 < rows; r0 += max_tok_) {
+        const int n = (int)std::min<int64_t>(max_tok_, rows - r0);
+        Pass s{st, n, tm, kv, ATTN_UNFUSED, false, false};
+        LinearPlanIn npi; npi.op = LOP_NORM; npi.ntok = n;
+        s.wgnorm = plan_linear(npi).form == LIN_NORM_WG;
+        NormPro a{};
+        a.h_in = x + (size_t)r0 * x_stride; a.h_stride = x_stride; a.parts_stride = d; a.g = L.attn_norm; a.eps = hp_.eps;
+        a.xn_out = float_mode_ ? xnf_.p : nullptr;
+        norm(s, a);
+        linear(s, L.wqkv, L.fqkv, xnf_.p, xq_.p, xd_.p, out + (size_t)r0 * qs);
     }
     Q3_LAUNCH_CHECK();
 }

@@ -50,6 +50,9 @@ public:
     struct Input {
         const float* x = nullptr; int x_stride = 0;   // [ntok][x_stride] embeddings ...
         const q3_u64* idx_keys = nullptr; int idx_stride = 0; // ... or table rows selected by argmax keys: x + code(idx_keys[tok*idx_stride])*x_stride
+        // optional, with idx_keys: layer 0's q/k/v rows of the same table (build_layer0_qkv), row code(idx_keys[...]) at qkv0 + code*qkv0_stride.
+        // Layer 0 then runs no attention norm and no q/k/v projection; its attention and its ffn norm read the two tables through the keys.
+        const float* qkv0 = nullptr; int qkv0_stride = 0;
     };
     // fused = 5 launches/layer (decode steps: every token from a different sequence, or a single sequence's
     // tokens when `same_seq_tokens` is set, in which case attention stays unfused)
@@ -60,6 +63,9 @@ public:
     // logits[tok_count][nrows] = output rows [row0,row0+nrows) . final hidden of tokens [tok0, tok0+tok_count)
     void head(hipStream_t st, int tok0, int tok_count, int row0, int nrows, float* logits, int logits_stride,
               const ArgmaxEpi* am = nullptr, int nrows_valid = -1, float* hidden_out = nullptr);
+    // out[rows][(n_head + 2 n_kv) * 128] = layer 0's attention norm + q/k/v projection of x's rows, bit for bit what forward() computes for that
+    // input: the rows Input::qkv0 takes.  Runs in chunks of max_tok rows on this context's workspace.
+    void build_layer0_qkv(hipStream_t st, const float* x, int x_stride, int64_t rows, float* out);
     void set_same_seq_tokens(bool v) { same_seq_ = v; }
     // steps of at least `min_tok` tokens (0 = never) use the single-wave attention kernel, which reads page 0 of a sequence only: the
     // caller states that no sequence ever holds more than `max_positions` positions, and that must fit one KV page (64)
@@ -93,7 +99,7 @@ private:
     void norm(const Pass& s, const NormPro& a);                         // residual add + RMSNorm + quantise, as its own launch
     void linear(const Pass& s, const Q8Mat& w, const FMat& fw, const float* xf, const int8_t* xq, const uint16_t* xd, float* out);
     void qkv(const Pass& s, const Layer& L, const NormPro& a);          // attention norm + q/k/v projection -> qkv_
-    void attention(const Pass& s, const Layer& L, int l);               // -> aq_ / ad_ (+ attf_ in float mode)
+    void attention(const Pass& s, const Layer& L, int l, const QkvRows& rows); // -> aq_ / ad_ (+ attf_ in float mode)
     void gate_up(const Pass& s, const Layer& L, const NormPro& b);      // ffn norm + gate/up + SwiGLU -> fq_ / fd_ (actf_ in float mode)
     bool float_mode_ = false; FMat foutput_; DevBuf<float> xnf_, attf_, actf_;
     float* scratch_logits(int) { return scratch_.p; }

@@ -93,6 +93,7 @@ SYMBOLS = [
     "q3tts_cancel", "q3tts_group_cancel",
     "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
     "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
+    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed",
 ]
 
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
@@ -626,6 +627,13 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
     def bytes_per_step(self, batch, mean_ctx):
         return lib().q3tts_engine_bytes_per_step(self.h, batch, mean_ctx)
 
+    def pred_table_bytes(self):
+        """device bytes of the predictor's layer-0 q/k/v table (q3tts_pred_table_bytes; 0 = off)"""
+        L = lib()
+        L.q3tts_pred_table_bytes.restype = C.c_int64
+        L.q3tts_pred_table_bytes.argtypes = [C.c_void_p]
+        return int(L.q3tts_pred_table_bytes(self.h))
+
 
 class TfContext:  # LlamaModel + LlamaContext at the embedding level (llama/mod.rs:326-513)
     def __init__(self, path, n_ctx=4096, max_tok=64):
@@ -1064,13 +1072,21 @@ def attention_plan(ntok, n_head=16, n_kv=8, fused=True, fused_max_tok=8, same_se
 
 def op_attention(qkv, q_norm, k_norm, k_cache, v_cache, n_head, n_kv, n_layer, layer, eps=1e-6, rope_base=1e6, n_ctx=4096,
                  mrope_sec=(0, 0, 0, 0), seq=None, slot=None, pos=None, uniform_pos=-1, page_table=None, form="AUTO", fused=True,
-                 fused_max_tok=8, same_seq=False, short_attn_min=0, hpw1_max=0, float_mode=False, ggml_mode=False):
+                 fused_max_tok=8, same_seq=False, short_attn_min=0, hpw1_max=0, float_mode=False, ggml_mode=False, keys=None):
     """one layer's attention step on the device (q3tts_op_attention).  qkv [ntok][>= (n_head + 2 n_kv) * 128] f32; k_cache / v_cache: the
     paged f16 caches as uint16 [n_pages][n_layer][n_kv][8192] (copied; the written-back caches are returned); seq / slot [ntok] and
     pos [ntok][4], or uniform_pos >= 0; page_table [n_seq][max_pages] or None (identity).
-    Returns dict(att=[ntok][n_head*128] f32 or None, aq, ad (None for GGML), k_cache, v_cache, form=name of what ran)."""
-    qkv = np.ascontiguousarray(qkv, np.float32)
-    ntok = qkv.shape[0]
+    keys (q3tts_op_attention_keyed): uint64 [ntok][key_stride] argmax keys; qkv is then a table and token t reads the row keys[t][0] selects.
+    Returns dict(att=[ntok][n_head*128] f32 or None, aq, ad (None for GGML), k_cache, v_cache, form=name of what ran; keyed: qkv = the
+    table as written back)."""
+    if keys is not None:
+        keys = np.ascontiguousarray(keys, np.uint64)
+        keys = keys.reshape(keys.shape[0], -1)
+        qkv = np.array(qkv, np.float32, copy=True, order="C")
+        ntok = keys.shape[0]
+    else:
+        qkv = np.ascontiguousarray(qkv, np.float32)
+        ntok = qkv.shape[0]
     q_norm = np.ascontiguousarray(q_norm, np.float32)
     k_norm = np.ascontiguousarray(k_norm, np.float32)
     kc = np.array(k_cache, np.uint16, copy=True, order="C")
@@ -1101,11 +1117,18 @@ def op_attention(qkv, q_norm, k_norm, k_cache, v_cache, n_head, n_kv, n_layer, l
     aq = np.zeros((ntok, n_head * 128), np.int8)
     ad = np.zeros((ntok, n_head * 4), np.uint16)
     d.att, d.aq, d.ad = _p(att), _p(aq), _p(ad)
-    lib().q3tts_op_attention.argtypes = [C.POINTER(AttentionDesc)]
-    _chk(lib().q3tts_op_attention(C.byref(d)))
+    if keys is not None:
+        lib().q3tts_op_attention_keyed.argtypes = [C.POINTER(AttentionDesc), C.c_void_p, C.c_int32, C.c_int32]
+        _chk(lib().q3tts_op_attention_keyed(C.byref(d), _p(keys), keys.shape[1], qkv.shape[0]))
+    else:
+        lib().q3tts_op_attention.argtypes = [C.POINTER(AttentionDesc)]
+        _chk(lib().q3tts_op_attention(C.byref(d)))
     ran = ATTN_FORM_NAMES[d.form_ran]
-    return dict(att=None if ran == "FUSED" else att, aq=None if ran == "GGML" else aq, ad=None if ran == "GGML" else ad,
-                k_cache=kc, v_cache=vc, form=ran)
+    r = dict(att=None if ran == "FUSED" else att, aq=None if ran == "GGML" else aq, ad=None if ran == "GGML" else ad,
+             k_cache=kc, v_cache=vc, form=ran)
+    if keys is not None:
+        r["qkv"] = qkv
+    return r
 
 
 def op_gemv_kq(parts, k, xq, xd, lpr=0):
