@@ -1007,81 +1007,148 @@ void launch_qk_rope_append(hipStream_t st, const QkvRows& qkv, const float*, int
 // causal GQA decode attention over the paged f16 cache (spec S7).  Workgroup = 4 waves per (head, token):
 // wave w scores positions c0+64w+lane of each 256-chunk (K stored [d/8][pos][8] so a wave load is 1 KiB
 // contiguous), then accumulates PV chains r = 4w + lane/16 over positions j = r (mod 16).
+// Loads first: the q row, the wave's 16 K rows and the first V batch of a chunk are requested before the first barrier (they depend on
+// the page table alone); the other V batches go out right behind the score chain, into the registers K has just left, in front of the
+// softmax barriers.  A V batch = the 64 positions of one page = row groups 4b .. 4b+3 of the chunk.  No load sits behind an exec-mask
+// branch (its join costs an s_waitcnt vmcnt(0)): inside a batch every lane loads, a row past the token's last position is clamped to
+// that position -- the address, so nothing the token may not see is read -- and zeroed by a select after the load; batches the token
+// does not reach are not loaded at all (one straight-line instance of the chunk per batch count).  The arithmetic keeps its
+// wave-uniform skips.  No barrier waits for a global load (wg_barrier_lds).  128 VGPRs (four waves per SIMD: the 1024 workgroups of
+// a 64-token step are resident in one round), no scratch: tests/test_attention_budget_cpu.py.  blockIdx.x -> head: the q heads of one
+// kv head get workgroup ids congruent mod 8 (one XCD, one L2 copy of the head's K/V rows) when n_kv is a multiple of 8.
 // =====================================================================================================
-__global__ void __launch_bounds__(256) k_attention(const float* __restrict__ qrot, int n_head, int n_kv, TokMeta tm,
-                                                   KvCache kv, int layer, float* __restrict__ att,
-                                                   int8_t* __restrict__ aq, uint16_t* __restrict__ ad) {
-    __shared__ float q_s[128];
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_attention(const float* __restrict__ qrot, int n_head, int n_kv, TokMeta tm, KvCache kv, int layer, float* __restrict__ att,
+            int8_t* __restrict__ aq, uint16_t* __restrict__ ad) {
+    __shared__ __attribute__((aligned(16))) float q_s[128];
     __shared__ float p_s[256];
     __shared__ float red_s[4][128];
     __shared__ float wmax_s[4];
-    const int h = blockIdx.x, tok = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tok = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = n_head / n_kv, bx = blockIdx.x;
+    const int h = (n_kv & 7) == 0 ? (bx % n_kv) * grp + bx / n_kv : bx;   // a bijection on [0, n_head): n_head = n_kv * grp
     const int seq = tm.seq_of(tok), n = tm.slot_of(tok) + 1;
-    const int kvh = h / (n_head / n_kv);
+    const int kvh = h / grp;
     const size_t head_off = (size_t)layer * kv.layer_stride() + (size_t)kvh * 8192;
-    if (tid < 128) q_s[tid] = qrot[((size_t)tok * n_head + h) * 128 + tid];
-    __syncthreads();
-    const float scale = 0.08838834764831845f;
     const int jj = lane >> 4, dc = lane & 15;
+    // page ids through the constant address space: the table does not change during the launch, and only so does the compiler keep the
+    // lookups of the later batches scalar (behind the barriers' memory clobber a global load is a vector load + s_waitcnt vmcnt(0))
+    typedef const int32_t __attribute__((address_space(4))) * const_i32_ptr;
+    const const_i32_ptr ptab = (const_i32_ptr)(uintptr_t)kv.page_table;
+    auto page_of = [&](int logical) { return kv.page_table ? ptab[(size_t)seq * kv.max_pages + logical] : seq; };
+    const float qv = qrot[((size_t)tok * n_head + h) * 128 + (tid & 127)];
+    const float scale = 0.08838834764831845f;
     float M = 0.0f, L = 0.0f, O[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) O[i] = 0.0f;
     for (int c0 = 0; c0 < n; c0 += 256) {
-        const int jbase = c0 + wave * 64;
-        const bool valid = (jbase + lane) < n;
-        float s = -INFINITY;
-        if (jbase < n) {
-            const int page = kv.page_of(seq, jbase >> 6);
-            const uint16_t* Kb = kv.k + (size_t)page * kv.page_stride() + head_off;
-            float acc = 0.0f;
-#pragma unroll
-            for (int d8 = 0; d8 < 16; d8++) {
-                const uint4 kk = *reinterpret_cast<const uint4*>(Kb + (d8 * 64 + lane) * 8);
-                const float4 qa = *reinterpret_cast<const float4*>(&q_s[8 * d8]);
-                const float4 qb = *reinterpret_cast<const float4*>(&q_s[8 * d8 + 4]);
-                acc = q3_fmaf(qa.x, h2f(kk.x & 0xFFFFu), acc); acc = q3_fmaf(qa.y, h2f(kk.x >> 16), acc);
-                acc = q3_fmaf(qa.z, h2f(kk.y & 0xFFFFu), acc); acc = q3_fmaf(qa.w, h2f(kk.y >> 16), acc);
-                acc = q3_fmaf(qb.x, h2f(kk.z & 0xFFFFu), acc); acc = q3_fmaf(qb.y, h2f(kk.z >> 16), acc);
-                acc = q3_fmaf(qb.z, h2f(kk.w & 0xFFFFu), acc); acc = q3_fmaf(qb.w, h2f(kk.w >> 16), acc);
-            }
-            if (valid) s = acc * scale;
-        }
-        const float wm = wave_max_bfly(s);
-        if (lane == 0) wmax_s[wave] = wm;
-        __syncthreads();
-        const float mc = fmaxf(fmaxf(wmax_s[0], wmax_s[1]), fmaxf(wmax_s[2], wmax_s[3]));
-        const float p = valid ? q3_expf(s - mc) : 0.0f;
-        p_s[wave * 64 + lane] = p;
-        __syncthreads();
-        // PV: 16 chains; this wave owns chains 4*wave+jj
-        float S[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) S[i] = 0.0f;
         const int cn = (n - c0) < 256 ? (n - c0) : 256;
-#pragma unroll 4
-        for (int u = 0; u < 16; u++) {
-            if (16 * u < cn) {
-                const int jl = 16 * u + 4 * wave + jj;
-                const int jg = c0 + jl;
-                const float pj = p_s[jl];
-                uint4 vv = make_uint4(0, 0, 0, 0);
-                if (jg < n) {
-                    const int page = kv.page_of(seq, jg >> 6);
-                    vv = *reinterpret_cast<const uint4*>(kv.v + (size_t)page * kv.page_stride() + head_off + (jg & 63) * 128 + dc * 8);
+        const int jbase = c0 + wave * 64;
+        float S[8], mc;
+        // The chunk up to its PV chains, for a token that reaches NB of the chunk's four 64-position batches (NB is the same for the whole
+        // workgroup): one straight-line instance per NB, so a batch nobody needs costs no load instruction and no register of the loaded
+        // rows is defined on one path only (a phi(undef, load) is live round the whole loop and spills)
+        auto chunk = [&](auto nb_const) {
+            constexpr int NB = decltype(nb_const)::value;
+            uint4 vreg[4 * NB];
+            int pg[NB];   // the pages of the NB batches, looked up together (scalar loads)
+#pragma unroll
+            for (int b = 0; b < NB; b++) pg[b] = page_of((c0 >> 6) + b);
+            // V batch b: every lane loads; a row past the token's last position (last batch only) is clamped to that position -- same page.
+            // `after`: a value the loads must stay behind -- their address is laundered through it, otherwise the compiler hoists them
+            // above the chain whose registers they are meant to reuse
+            auto load_v = [&](int b, const float* after) {
+                const uint16_t* Vb = kv.v + (size_t)pg[b] * kv.page_stride() + head_off;
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const int jg = c0 + 64 * b + 16 * g + 4 * wave + jj;
+                    uint32_t off = (uint32_t)(((jg < n ? jg : n - 1) & 63) * 128 + dc * 8);
+                    if (after) asm volatile("" : "+v"(off) : "v"(*after));
+                    vreg[4 * b + g] = *reinterpret_cast<const uint4*>(Vb + off);
                 }
-                S[0] = q3_fmaf(pj, h2f(vv.x & 0xFFFFu), S[0]); S[1] = q3_fmaf(pj, h2f(vv.x >> 16), S[1]);
-                S[2] = q3_fmaf(pj, h2f(vv.y & 0xFFFFu), S[2]); S[3] = q3_fmaf(pj, h2f(vv.y >> 16), S[3]);
-                S[4] = q3_fmaf(pj, h2f(vv.z & 0xFFFFu), S[4]); S[5] = q3_fmaf(pj, h2f(vv.z >> 16), S[5]);
-                S[6] = q3_fmaf(pj, h2f(vv.w & 0xFFFFu), S[6]); S[7] = q3_fmaf(pj, h2f(vv.w >> 16), S[7]);
+            };
+            auto q_handoff = [&]() {   // first chunk: the q row arrives while the chunk's K and V rows are already on their way
+                if (c0 == 0) {
+                    q_s[tid & 127] = qv;   // (waves 2 and 3 store what waves 0 and 1 store)
+                    wg_barrier_lds();
+                }
+            };
+            const bool valid = (jbase + lane) < n;
+            float s = -INFINITY;
+            if (jbase < n) {   // (wave < NB) the wave's 64 positions are one page
+                int pgk = pg[0];
+#pragma unroll
+                for (int b = 1; b < NB; b++) pgk = wave == b ? pg[b] : pgk;   // (jbase >> 6 = (c0 >> 6) + wave)
+                const uint16_t* Kb = kv.k + (size_t)pgk * kv.page_stride() + head_off;
+                uint4 kreg[16];
+#pragma unroll
+                for (int d8 = 0; d8 < 16; d8++) kreg[d8] = *reinterpret_cast<const uint4*>(Kb + (d8 * 64 + lane) * 8);
+                load_v(0, nullptr);
+                q_handoff();
+                float acc = 0.0f;
+                // q comes from LDS one row ahead of the chain and no further: the index of row d8 + 1 is laundered through the sum over rows
+                // < d8 (read further ahead -- the compiler reads all 128 floats up front -- q alone takes the registers the V rows need)
+                float4 qa = *reinterpret_cast<const float4*>(&q_s[0]), qb = *reinterpret_cast<const float4*>(&q_s[4]);
+#pragma unroll
+                for (int d8 = 0; d8 < 16; d8++) {
+                    const uint4 kk = kreg[d8];
+                    float4 na = qa, nb = qb;
+                    if (d8 < 15) {
+                        int qi = 8 * (d8 + 1);
+                        asm volatile("" : "+v"(qi) : "v"(acc));
+                        na = *reinterpret_cast<const float4*>(&q_s[qi]);
+                        nb = *reinterpret_cast<const float4*>(&q_s[qi + 4]);
+                    }
+                    acc = q3_fmaf(qa.x, h2f(kk.x & 0xFFFFu), acc); acc = q3_fmaf(qa.y, h2f(kk.x >> 16), acc);
+                    acc = q3_fmaf(qa.z, h2f(kk.y & 0xFFFFu), acc); acc = q3_fmaf(qa.w, h2f(kk.y >> 16), acc);
+                    acc = q3_fmaf(qb.x, h2f(kk.z & 0xFFFFu), acc); acc = q3_fmaf(qb.y, h2f(kk.z >> 16), acc);
+                    acc = q3_fmaf(qb.z, h2f(kk.w & 0xFFFFu), acc); acc = q3_fmaf(qb.w, h2f(kk.w >> 16), acc);
+                    qa = na; qb = nb;
+                }
+                if (valid) s = acc * scale;
+            } else {   // nothing to score: the wave's own barrier instruction (s_barrier counts arrivals, whichever instruction a wave arrives at)
+                load_v(0, nullptr);
+                q_handoff();
             }
-        }
+            // the K registers are dead: the chunk's other V batches go out here, and fly under the two softmax barriers
+#pragma unroll
+            for (int b = 1; b < NB; b++) load_v(b, &s);
+            const float wm = wave_max_bfly(s);
+            if (lane == 0) wmax_s[wave] = wm;
+            wg_barrier_lds();
+            mc = fmaxf(fmaxf(wmax_s[0], wmax_s[1]), fmaxf(wmax_s[2], wmax_s[3]));
+            const float p = valid ? q3_expf(s - mc) : 0.0f;
+            p_s[wave * 64 + lane] = p;
+            wg_barrier_lds();
+            // PV: 16 chains; this wave owns chains 4*wave+jj
+#pragma unroll
+            for (int i = 0; i < 8; i++) S[i] = 0.0f;
+#pragma unroll
+            for (int u = 0; u < 4 * NB; u++) {
+                if (16 * u < cn) {
+                    const int jl = 16 * u + 4 * wave + jj;
+                    const int jg = c0 + jl;
+                    const float pj = p_s[jl];
+                    uint4 vv = vreg[u];
+                    if (!(jg < n)) vv = make_uint4(0, 0, 0, 0);   // (a select: the load above was of a clamped row)
+                    S[0] = q3_fmaf(pj, h2f(vv.x & 0xFFFFu), S[0]); S[1] = q3_fmaf(pj, h2f(vv.x >> 16), S[1]);
+                    S[2] = q3_fmaf(pj, h2f(vv.y & 0xFFFFu), S[2]); S[3] = q3_fmaf(pj, h2f(vv.y >> 16), S[3]);
+                    S[4] = q3_fmaf(pj, h2f(vv.z & 0xFFFFu), S[4]); S[5] = q3_fmaf(pj, h2f(vv.z >> 16), S[5]);
+                    S[6] = q3_fmaf(pj, h2f(vv.w & 0xFFFFu), S[6]); S[7] = q3_fmaf(pj, h2f(vv.w >> 16), S[7]);
+                }
+            }
+        };
+        if (cn <= 64) chunk(std::integral_constant<int, 1>());
+        else if (cn <= 128) chunk(std::integral_constant<int, 2>());
+        else if (cn <= 192) chunk(std::integral_constant<int, 3>());
+        else chunk(std::integral_constant<int, 4>());
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const float a = S[i] + xor_lane<16>(S[i]);   // (S0+S1) | (S2+S3)
             const float T = a + xor_lane<32>(a);          // (S0+S1)+(S2+S3)
             if (jj == 0) red_s[wave][dc * 8 + i] = T;
         }
-        __syncthreads();
+        wg_barrier_lds();
         if (wave == 0) {
             float a = p_s[lane];                            // spec: a = 0 + p0 (== p0), then + p1, p2, p3
             a = a + p_s[lane + 64]; a = a + p_s[lane + 128]; a = a + p_s[lane + 192];
@@ -1103,7 +1170,7 @@ __global__ void __launch_bounds__(256) k_attention(const float* __restrict__ qro
                 M = mn;
             }
         }
-        __syncthreads();
+        wg_barrier_lds();
     }
     if (wave == 0) {
         float y[8];
