@@ -625,6 +625,35 @@ int q3tts_linear_plan(q3tts_linear_desc* d);
 /* host only: the argmax key the device packs for logit v at index idx (kdev.h pack_key: order-preserving value bits, ~idx, -0 as +0) */
 uint64_t q3tts_argmax_key(float v, int32_t idx);
 
+/* [EXT] test surface of the four token-selection kernels, host buffers: k_sample, k_sample_pred, k_argmax, k_argmax_keys over B rows
+ * logits [B][n], with everything SampleArgs / launch_argmax / launch_argmax_keys take.  On the device row b starts row_off + b*stride floats
+ * into its buffer; the floats before row 0 and columns [n, stride) of every row hold 3e38f (a kernel that reads one changes its pick).
+ * Launch i of n_draws (the argmax kernels run once) writes slot b*out_stride of its own B*out_stride output slots; every slot is pre-set to
+ * Q3TTS_SELECT_SENTINEL (k_argmax: its low 32 bits, the slots are int32 there) and the whole array comes back in out_raw.
+ * Shapes a launcher refuses (SAMPLE: n > 4096; SAMPLE_PRED: n > 2048, a penalty or a mask) fail through that launcher's own check and leave
+ * tokens / out_raw / draws_out unwritten. */
+enum { Q3TTS_SEL_SAMPLE = 0, Q3TTS_SEL_SAMPLE_PRED = 1, Q3TTS_SEL_ARGMAX = 2, Q3TTS_SEL_ARGMAX_KEYS = 3 };
+#define Q3TTS_SELECT_SENTINEL 0xA5C3F00D5A3C0FF1ull
+typedef struct q3tts_select_desc {
+    int32_t kernel;                  /* Q3TTS_SEL_* */
+    int32_t B, n, stride, row_off;   /* stride >= n, row_off >= 0 */
+    const float* logits;             /* [B][n] */
+    const float* temperature; const int32_t* top_k; const float* top_p;   /* [B] each (samplers) */
+    const int32_t* mask_idx;         /* optional [B]; < 0 = none */
+    const uint64_t* seed;            /* [B] (samplers): row b's stream is seed_from_u64(seed[b]) ... */
+    const uint32_t* draw0;           /* optional [B]: ... read from word draw0[b] on (NULL = 0) */
+    int32_t n_draws;                 /* samplers: consecutive launches over the same rows */
+    /* penalty block (NULL penalty = none): hist [B][hist_cap] holds row b's codes as given, out-of-range values included, hist_len [B]
+     * <= hist_cap; cur_code NULL = the launch's cur_key is null, else [B] codes packed into keys (cur_stride 16) */
+    const float* penalty; const int32_t* hist; const int32_t* hist_len; int32_t hist_cap; const int32_t* cur_code;
+    int32_t out_stride;              /* 1 or 16 */
+    int32_t start, end, add;         /* ARGMAX: 0 <= start <= end <= n */
+    int32_t* tokens;                 /* out [n_draws][B] */
+    uint64_t* out_raw;               /* out [n_draws][B*out_stride] (ARGMAX: the int32 slots zero-extended) */
+    uint32_t* draws_out;             /* out [B]: the draw counters after the last launch (samplers) */
+} q3tts_select_desc;
+int q3tts_op_select_rows(q3tts_select_desc* d);
+
 #ifdef __cplusplus
 }
 #endif

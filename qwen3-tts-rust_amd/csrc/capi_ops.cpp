@@ -649,6 +649,90 @@ int q3tts_op_logprob_rows(const float* logits, int32_t B, int32_t n, int32_t str
     Q3_API_END(Q3TTS_ERR)
 }
 
+/* [EXT] the four token-selection kernels over guarded device buffers (include/q3tts.h).  Only what keeps the launch inside its buffers is
+ * checked here; what a launcher refuses is left to that launcher, and nothing is written to the host outputs before the last launch ran. */
+int q3tts_op_select_rows(q3tts_select_desc* dp) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(dp, "null select descriptor");
+    const q3tts_select_desc& d = *dp;
+    const bool sampler = d.kernel == Q3TTS_SEL_SAMPLE || d.kernel == Q3TTS_SEL_SAMPLE_PRED;
+    Q3_CHECK(sampler || d.kernel == Q3TTS_SEL_ARGMAX || d.kernel == Q3TTS_SEL_ARGMAX_KEYS, "unknown selection kernel");
+    Q3_CHECK(d.logits && d.tokens && d.out_raw && d.B >= 1 && d.B <= 65535 && d.n >= 1 && d.stride >= d.n && d.row_off >= 0, "bad row shape");
+    Q3_CHECK(d.out_stride == 1 || d.out_stride == 16, "out_stride must be 1 or 16");
+    const int B = d.B, n = d.n, nl = sampler ? d.n_draws : 1;
+    if (sampler) Q3_CHECK(d.temperature && d.top_k && d.top_p && d.seed && d.draws_out && d.n_draws >= 1, "the samplers need temperature / top_k / top_p / seed / draws_out");
+    if (d.kernel == Q3TTS_SEL_ARGMAX) Q3_CHECK(d.start >= 0 && d.start <= d.end && d.end <= n, "argmax window outside [0, n]");
+    if (d.penalty) {
+        Q3_CHECK(d.hist && d.hist_len && d.hist_cap >= 1, "a penalty needs a history");
+        for (int b = 0; b < B; b++) Q3_CHECK(d.hist_len[b] >= 0 && d.hist_len[b] <= d.hist_cap, "hist_len out of range");
+    }
+    // logits: guard value everywhere, then the rows
+    const float guard = 3e38f;
+    std::vector<float> hl((size_t)d.row_off + (size_t)B * d.stride, guard);
+    for (int b = 0; b < B; b++) std::copy(d.logits + (size_t)b * n, d.logits + (size_t)(b + 1) * n, hl.begin() + d.row_off + (size_t)b * d.stride);
+    DevBuf<float> dl(hl.size()); dl.upload(hl.data(), hl.size());
+    const float* rows = dl.p + d.row_off;
+    DevBuf<int32_t> dm;
+    if (d.mask_idx) { dm.alloc(B); dm.upload(d.mask_idx, B); }
+    const size_t slots = (size_t)B * d.out_stride;
+    std::vector<q3_u64> raw((size_t)nl * slots);
+    if (d.kernel == Q3TTS_SEL_ARGMAX) {
+        const int32_t s32 = (int32_t)(uint32_t)(Q3TTS_SELECT_SENTINEL & 0xFFFFFFFFull);
+        std::vector<int32_t> ho(slots, s32);
+        DevBuf<int32_t> dout(slots); dout.upload(ho.data(), slots);
+        launch_argmax(0, rows, d.stride, d.start, d.end, dm.p, dout.p, d.out_stride, d.add, B);
+        Q3_LAUNCH_CHECK();
+        Q3_HIP(hipDeviceSynchronize());
+        dout.download(ho.data(), slots);
+        for (size_t i = 0; i < slots; i++) raw[i] = (q3_u64)(uint32_t)ho[i];
+        std::copy(raw.begin(), raw.end(), (q3_u64*)d.out_raw);
+        for (int b = 0; b < B; b++) d.tokens[b] = ho[(size_t)b * d.out_stride];
+        return Q3TTS_OK;
+    }
+    std::fill(raw.begin(), raw.end(), (q3_u64)Q3TTS_SELECT_SENTINEL);
+    DevBuf<q3_u64> dout(raw.size()); dout.upload(raw.data(), raw.size());
+    if (d.kernel == Q3TTS_SEL_ARGMAX_KEYS) {
+        launch_argmax_keys(0, rows, d.stride, n, dm.p, dout.p, d.out_stride, B);
+        Q3_LAUNCH_CHECK();
+        Q3_HIP(hipDeviceSynchronize());
+        dout.download((q3_u64*)d.out_raw, raw.size());
+        for (int b = 0; b < B; b++) d.tokens[b] = key_code(d.out_raw[(size_t)b * d.out_stride]);
+        return Q3TTS_OK;
+    }
+    DevBuf<float> dt(B), dp_(B), dpen; DevBuf<int32_t> dk(B), dh, dlen; DevBuf<uint32_t> dkey((size_t)8 * B), ddraw(B); DevBuf<q3_u64> dcur;
+    dt.upload(d.temperature, B); dp_.upload(d.top_p, B); dk.upload(d.top_k, B);
+    std::vector<uint32_t> keys((size_t)8 * B), draw(B, 0u);
+    for (int b = 0; b < B; b++) { StdRng rng(d.seed[b]); std::copy(rng.key(), rng.key() + 8, keys.begin() + (size_t)b * 8); if (d.draw0) draw[b] = d.draw0[b]; }
+    dkey.upload(keys.data(), keys.size()); ddraw.upload(draw.data(), B);
+    SampleArgs a{rows, d.stride, n, dt.p, dk.p, dp_.p, dm.p, dkey.p, ddraw.p, dout.p, d.out_stride};
+    if (d.penalty) { // the frame graph's layout: code f of row b at hist[b*hist_stride + f*16]; the 15 ints between two codes hold a value in [0, n)
+        const size_t hs = (size_t)d.hist_cap * 16;
+        std::vector<int32_t> hh((size_t)B * hs, 0);
+        for (int b = 0; b < B; b++) for (int f = 0; f < d.hist_cap; f++) hh[(size_t)b * hs + (size_t)f * 16] = d.hist[(size_t)b * d.hist_cap + f];
+        dh.alloc(hh.size()); dh.upload(hh.data(), hh.size()); dlen.alloc(B); dlen.upload(d.hist_len, B); dpen.alloc(B); dpen.upload(d.penalty, B);
+        a.penalty = dpen.p; a.hist = dh.p; a.hist_stride = (int)hs; a.hist_len = dlen.p;
+        if (d.cur_code) {
+            std::vector<q3_u64> cur((size_t)16 * B, pack_key(0.0f, 0));
+            for (int b = 0; b < B; b++) cur[(size_t)b * 16] = pack_key(0.0f, d.cur_code[b]);
+            dcur.alloc(cur.size()); dcur.upload(cur.data(), cur.size());
+            a.cur_key = dcur.p; a.cur_stride = 16;
+        }
+    }
+    for (int i = 0; i < nl; i++) {
+        a.out_key = dout.p + (size_t)i * slots;
+        if (d.kernel == Q3TTS_SEL_SAMPLE) launch_sample(0, a, B);
+        else launch_sample_pred(0, a, B);
+        Q3_LAUNCH_CHECK();
+    }
+    Q3_HIP(hipDeviceSynchronize());
+    dout.download((q3_u64*)d.out_raw, raw.size());
+    ddraw.download(d.draws_out, B);
+    for (int i = 0; i < nl; i++) for (int b = 0; b < B; b++) d.tokens[(size_t)i * B + b] = key_code(d.out_raw[(size_t)i * slots + (size_t)b * d.out_stride]);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d) {
     Q3_API_BEGIN
     require_gpu();

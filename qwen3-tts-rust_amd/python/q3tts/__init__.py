@@ -93,7 +93,7 @@ SYMBOLS = [
     "q3tts_cancel", "q3tts_group_cancel",
     "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
     "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
-    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed",
+    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows",
 ]
 
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
@@ -1360,3 +1360,56 @@ def argmax_key(v, idx):
     L.q3tts_argmax_key.restype = C.c_uint64
     L.q3tts_argmax_key.argtypes = [C.c_float, C.c_int32]
     return int(L.q3tts_argmax_key(v, idx))
+
+
+# ---- the four token-selection kernels (q3tts_op_select_rows) ----
+SEL_SAMPLE, SEL_SAMPLE_PRED, SEL_ARGMAX, SEL_ARGMAX_KEYS = range(4)
+SELECT_SENTINEL = 0xA5C3F00D5A3C0FF1   # Q3TTS_SELECT_SENTINEL
+
+
+class SelectDesc(C.Structure):  # q3tts_select_desc
+    _fields_ = [("kernel", C.c_int32), ("B", C.c_int32), ("n", C.c_int32), ("stride", C.c_int32), ("row_off", C.c_int32),
+                ("logits", C.c_void_p), ("temperature", C.c_void_p), ("top_k", C.c_void_p), ("top_p", C.c_void_p), ("mask_idx", C.c_void_p),
+                ("seed", C.c_void_p), ("draw0", C.c_void_p), ("n_draws", C.c_int32),
+                ("penalty", C.c_void_p), ("hist", C.c_void_p), ("hist_len", C.c_void_p), ("hist_cap", C.c_int32), ("cur_code", C.c_void_p),
+                ("out_stride", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("add", C.c_int32),
+                ("tokens", C.c_void_p), ("out_raw", C.c_void_p), ("draws_out", C.c_void_p)]
+
+
+def select_outputs(B, n_draws=1, out_stride=1):
+    """the output arrays of op_select_rows, every element a sentinel: (tokens [n_draws][B] = -1, raw [n_draws][B*out_stride], draws [B])"""
+    return (np.full((n_draws, B), -1, np.int32), np.full((n_draws, B * out_stride), SELECT_SENTINEL, np.uint64),
+            np.full(B, 0xFFFFFFFF, np.uint32))
+
+
+def op_select_rows(kernel, logits, stride=None, row_off=0, temperature=0.0, top_k=0, top_p=1.0, mask_idx=None, seed=0, draw0=None, n_draws=1,
+                   penalty=None, history=None, cur_code=None, out_stride=1, start=0, end=None, add=0, outputs=None):
+    """one of k_sample / k_sample_pred / k_argmax / k_argmax_keys over the rows logits [B][n] (q3tts_op_select_rows).  Per-row parameters are
+    scalars or arrays of length B; history = per-row lists of codes, passed on as they are.  Returns (tokens, raw, draws); `outputs` (from
+    select_outputs) is written in place, so that a caller still holds it when the call raises."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    B, n = lg.shape
+    row = lambda v, t: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, t), (B,)))
+    sampler = kernel in (SEL_SAMPLE, SEL_SAMPLE_PRED)
+    nl = n_draws if sampler else 1
+    keep = [lg, row(temperature, np.float32), row(top_k, np.int32), row(top_p, np.float32), row(mask_idx, np.int32), row(seed, np.uint64),
+            row(draw0, np.uint32), row(penalty, np.float32), row(cur_code, np.int32)]
+    d = SelectDesc()
+    d.kernel, d.B, d.n, d.stride, d.row_off, d.n_draws = kernel, B, n, n if stride is None else stride, row_off, n_draws
+    d.logits, d.temperature, d.top_k, d.top_p, d.mask_idx, d.seed, d.draw0, d.penalty, d.cur_code = [_p(a) for a in keep]
+    if penalty is not None:
+        history = history if history is not None else [[] for _ in range(B)]
+        d.hist_cap = max(1, max(len(h) for h in history))
+        hist = np.full((B, d.hist_cap), -1, np.int32)
+        hlen = np.array([len(h) for h in history], np.int32)
+        for b, h in enumerate(history):
+            hist[b, : len(h)] = h
+        keep += [hist, hlen]
+        d.hist, d.hist_len = _p(hist), _p(hlen)
+    d.out_stride, d.start, d.end, d.add = out_stride, start, n if end is None else end, add
+    tokens, raw, draws = outputs if outputs is not None else select_outputs(B, nl, out_stride)
+    assert tokens.shape == (nl, B) and raw.shape == (nl, B * out_stride) and draws.shape == (B,)
+    d.tokens, d.out_raw, d.draws_out = _p(tokens), _p(raw), _p(draws)
+    lib().q3tts_op_select_rows.argtypes = [C.POINTER(SelectDesc)]
+    _chk(lib().q3tts_op_select_rows(C.byref(d)))
+    return tokens, raw, draws
