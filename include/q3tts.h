@@ -189,6 +189,22 @@ int q3tts_engine_set_logprobs(q3tts_engine* e, int32_t on);
 /* rows [frame_off, frame_off+max_frames) available now, [got][17]; got_frames is what q3tts_fetch reports for the same arguments: the two grow
  * together.  A cancelled request keeps the rows of the frames it keeps.  < 0: unknown id, or the request was not recording */
 int q3tts_fetch_logprobs(q3tts_engine* e, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
+/* [EXT] score (q3tts_spec.h "scoring"): the teacher-forced log-probabilities of frames the caller already holds -- codes [n][16] behind
+ * prompt [n_prompt][2048] and optional CLOSED trailing ids [n_trail] (NULL / 0: none).  Queued like any request; ends Q3TTS_REQ_DONE with
+ * n_frames = n and no PCM.  prompt, ids and codes are copied.  Row f of q3tts_fetch_logprobs is the row a recording request that emitted
+ * exactly these codes shows for frame f (raw logits: no penalty, temperature, top-k / top-p or EOS mask; within 1e-5 * max(1, |lp|) of the
+ * float64 log-softmax of the same f32 logits); q3tts_fetch returns the given codes.  Both report 0 frames until the request is DONE and n
+ * afterwards.  q3tts_poll / q3tts_wait / q3tts_release as for any request; q3tts_cancel gives CANCELLED with 0 frames; q3tts_trail_append
+ * returns < 0 (the trail is not open).  Scoring neither needs q3tts_engine_set_logprobs nor changes it, and no running request is disturbed.
+ * The request is prefilled in the ordinary admission waves, holds one slot and its KV pages until its rows are computed and never joins the
+ * frame graph.  The first call allocates the scoring state (a second predictor context of 16 * score_width tokens and
+ * [max_batch][max_steps][17] floats of rows).
+ * Refused (< 0, q3tts_last_error says why, nothing is queued): n <= 0; n > the engine's max_steps; codes or prompt NULL; n_prompt < 1 or
+ * > max_prompt; a code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS; a residual code outside [0, 2048); n_trail < 0 or
+ * > max_prompt, or trail_ids NULL with n_trail > 0; n_prompt + n beyond the slot's KV capacity; Q3_SPEC=ggml */
+int q3tts_submit_score(q3tts_engine* e, const float* prompt, int32_t n_prompt, const int32_t* trail_ids, int32_t n_trail,
+                       const int32_t* codes, int32_t n, int64_t* req_id);
+int32_t q3tts_engine_score_width(q3tts_engine* e);   /* frames per predictor scoring pass */
 /* rows of one talker prefill launch: a longer admission wave (prompts + resumed prefixes) is prefilled in chunks of this many rows
  * (an asynchronous wave, admitted beside running requests, in chunks of at most 256) */
 int32_t q3tts_engine_prefill_width(q3tts_engine* e);
@@ -271,6 +287,9 @@ int q3tts_group_cancel(q3tts_group* g, int64_t req_id);       /* [EXT] q3tts_can
 int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                               const int32_t* trail_ids, int32_t n_trail, int32_t open,
                               const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id);
+/* [EXT] q3tts_submit_score on engine engine_index (-1 = round robin) */
+int q3tts_group_submit_score(q3tts_group* g, int32_t engine_index, const float* prompt, int32_t n_prompt, const int32_t* trail_ids,
+                             int32_t n_trail, const int32_t* codes, int32_t n, int64_t* req_id);
 int q3tts_group_set_logprobs(q3tts_group* g, int32_t on);      /* [EXT] q3tts_engine_set_logprobs on every engine */
 int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
@@ -464,6 +483,13 @@ int q3tts_op_project(const float* x, const float* w /* [n_out][n_in] */, const f
  * out_chosen [B] = log softmax(row)[chosen], out_extra [B] (or NULL) = log softmax(row)[extra_idx] */
 int q3tts_op_logprob_rows(const float* logits, int32_t B, int32_t n, int32_t stride, const int32_t* chosen, int32_t extra_idx,
                           float* out_chosen, float* out_extra);
+/* [EXT] scoring test surfaces, host buffers.  k_score_rows: tlogits [F][t_stride] (the first Q3_SAMPLE_END columns of a row count; a
+ * t_stride that is no multiple of 4 makes odd rows unaligned), plogits [15][F][2048], codes [F][16] -> out [F][17].  k_score_inputs:
+ * hidden_proj [F][dP], tabs[q] = table q of tab_rows[q] rows of dP floats (q = 0..14), codes [F][16] -> out [16 F][dP], row p * F + f =
+ * position p of frame f.  Both run with guard values around the device output and fail if the kernel wrote outside it */
+int q3tts_op_score_rows(const float* tlogits, int32_t t_stride, const float* plogits, const int32_t* codes, int32_t F, float* out);
+int q3tts_op_score_inputs(const float* hidden_proj, const float* const* tabs, const int64_t* tab_rows, int32_t dP, const int32_t* codes,
+                          int32_t F, float* out);
 /* [EXT] resume test surface, host buffers: rows [n][2048] = the feedback rows of codes [n][16] (+ trail ids [n_trail], row f takes id f
  * while f < n_trail; NULL / 0 = every row adds tts_pad) against the given tables (k_feedback_codes) */
 int q3tts_op_feedback_rows(const q3tts_assets* a, const int32_t* codes, int32_t n, const int32_t* trail_ids, int32_t n_trail, float* rows);

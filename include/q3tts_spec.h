@@ -335,6 +335,24 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
 #define Q3_LOGPROB_COLS 17
 #define Q3_LOGPROB_NONE 1.0f
 
+/* ---------------- scoring given frames [EXT] (q3tts_submit_score, q3tts_group_submit_score, q3tts_op_score_rows / _inputs) ----------------
+ * Given a prompt of n_prompt rows, optional closed trailing ids and codes c[0..n)[16], row f of the result is the row q3tts_fetch_logprobs
+ * shows for frame f of a request that emitted exactly these codes.  Nothing is sampled; the pass is teacher-forced on the given codes:
+ *   talker     columns 0 and 16 come from the raw talker logits [0, Q3_SAMPLE_END) of prefill row n_prompt - 1 + f: the last prompt row for
+ *              f = 0, the feedback row of frame f - 1 for f >= 1, built and placed as "resume" builds the rows of a prefix (with
+ *              text(trail[f - 1]) as its last addend while f - 1 < n_trail).  Column 0 is the log-softmax at c[f][0], column 16 at
+ *              Q3_CODEC_EOS.  The feedback row of frame n - 1 would only serve a frame n; it is not needed
+ *   predictor  columns 1..15 come from a 16-token sequence of the code predictor: position 0 is project(hidden of that talker row), position 1
+ *              is project(E_0[c[f][0]]), position q + 1 is project(E_q[c[f][q]]) for q = 1..14 (a negative code reads row 0 and a code past
+ *              its table the zero row); the logits for c[f][q + 1] are head slice q at position q + 1, q = 0..14
+ *   raw        as for recording: no penalty, no temperature / top-k / top-p, no EOS mask
+ * Arithmetic and tolerance are those of "token log-probabilities": q3_expf, |lp - lp64| <= 1e-5 * max(1, |lp64|) against the float64
+ * log-softmax of the same f32 logits.  The logits are those of the generating request bit for bit (the arithmetic is independent of launch
+ * geometry, batch size and chunking), so a scored row and the row recorded while the same engine generated the same codes differ by at most
+ * 2e-5 * max(1, |lp|): both lie within the tolerance of one float64 value.
+ * Refused: n < 1 or n > max_steps; a code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS (no request emits a frame with it); a residual
+ * code outside [0, 2048); n_prompt + n beyond the KV capacity of a slot; the ggml-arithmetic mode. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -137,6 +137,15 @@ int q3tts_submit_resume(q3tts_engine* e, const q3tts_request* r, int32_t want_pc
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+int q3tts_submit_score(q3tts_engine* e, const float* prompt, int32_t n_prompt, const int32_t* trail_ids, int32_t n_trail, const int32_t* codes,
+                       int32_t n, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && req_id, "null argument");
+    *req_id = e->e->submit_score(prompt, n_prompt, trail_ids, n_trail, codes, n);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int32_t q3tts_engine_score_width(q3tts_engine* e) { return e ? e->e->score_width() : -1; }
 int q3tts_trail_append(q3tts_engine* e, int64_t req_id, const int32_t* ids, int32_t n, int32_t close) {
     Q3_API_BEGIN
     Q3_CHECK(e, "null argument");

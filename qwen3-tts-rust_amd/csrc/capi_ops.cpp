@@ -649,6 +649,56 @@ int q3tts_op_logprob_rows(const float* logits, int32_t B, int32_t n, int32_t str
     Q3_API_END(Q3TTS_ERR)
 }
 
+/* [EXT] scoring: k_score_rows and k_score_inputs over host buffers, one guard row on either side of the device output */
+int q3tts_op_score_rows(const float* tlogits, int32_t t_stride, const float* plogits, const int32_t* codes, int32_t F, float* out) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(tlogits && plogits && codes && out && F >= 1 && F <= 4096 && t_stride >= Q3_SAMPLE_END, "bad arguments");
+    DevBuf<float> dt((size_t)F * t_stride), dp((size_t)15 * F * Q3_CODEBOOK_SIZE), dout((size_t)(F + 2) * Q3_LOGPROB_COLS); DevBuf<int32_t> dc((size_t)F * 16);
+    dt.upload(tlogits, dt.n); dp.upload(plogits, dp.n); dc.upload(codes, dc.n);
+    const float guard = -777.0f;
+    std::vector<float> h(dout.n, guard);
+    dout.upload(h.data(), h.size());
+    ScoreRowsArgs a;
+    a.tlogits = dt.p; a.t_stride = t_stride; a.plogits = dp.p; a.p_head_stride = (size_t)F * Q3_CODEBOOK_SIZE; a.codes = dc.p;
+    a.out = dout.p + Q3_LOGPROB_COLS;
+    launch_score_rows(0, a, F);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    dout.download(h.data(), h.size());
+    for (int i = 0; i < Q3_LOGPROB_COLS; i++)
+        Q3_CHECK(h[i] == guard && h[(size_t)(F + 1) * Q3_LOGPROB_COLS + i] == guard, "k_score_rows wrote outside its rows");
+    std::copy(h.begin() + Q3_LOGPROB_COLS, h.begin() + (size_t)(F + 1) * Q3_LOGPROB_COLS, out);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_op_score_inputs(const float* hidden_proj, const float* const* tabs, const int64_t* tab_rows, int32_t dP, const int32_t* codes, int32_t F,
+                          float* out) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(hidden_proj && tabs && tab_rows && codes && out && F >= 1 && F <= 4096 && dP >= 4 && dP % 4 == 0, "bad arguments");
+    std::vector<DevBuf<float>> tab(15);
+    std::vector<const float*> ptrs(15);
+    for (int q = 0; q < 15; q++) {
+        Q3_CHECK(tabs[q] && tab_rows[q] >= 1, "table missing");
+        tab[q].alloc((size_t)tab_rows[q] * dP); tab[q].upload(tabs[q], tab[q].n);
+        ptrs[q] = tab[q].p;
+    }
+    DevBuf<const float*> d_ptrs(15); DevBuf<int64_t> d_rows(15); DevBuf<float> dh((size_t)F * dP), dout((size_t)(16 * F + 2) * dP); DevBuf<int32_t> dc((size_t)F * 16);
+    d_ptrs.upload(ptrs.data(), 15); d_rows.upload(tab_rows, 15); dh.upload(hidden_proj, dh.n); dc.upload(codes, dc.n);
+    const float guard = -12345.0f;
+    std::vector<float> h(dout.n, guard);
+    dout.upload(h.data(), h.size());
+    launch_score_inputs(0, dh.p, d_ptrs.p, d_rows.p, dP, dc.p, F, dout.p + dP);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    dout.download(h.data(), h.size());
+    for (int i = 0; i < dP; i++) Q3_CHECK(h[i] == guard && h[(size_t)(16 * F + 1) * dP + i] == guard, "k_score_inputs wrote outside its rows");
+    std::copy(h.begin() + dP, h.begin() + (size_t)(16 * F + 1) * dP, out);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 /* [EXT] the four token-selection kernels over guarded device buffers (include/q3tts.h).  Only what keeps the launch inside its buffers is
  * checked here; what a launcher refuses is left to that launcher, and nothing is written to the host outputs before the last launch ran. */
 int q3tts_op_select_rows(q3tts_select_desc* dp) {

@@ -106,8 +106,9 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         talker_pf_.reset(new Transformer(*talker_, 256)); // shares the talker's device weights; own activation workspace
         Q3_HIP(hipStreamCreateWithFlags(&st_pf_, hipStreamNonBlocking));
         Q3_HIP(hipEventCreate(&pf_done_)); Q3_HIP(hipEventCreate(&pf_e0_));
-        // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row)
-        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24 + 68) + ((size_t)1 << 16);
+        // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row) and the
+        // codes of score rows (64 B a row)
+        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16);
         Q3_HIP(hipHostMalloc((void**)&arena_pf_, arena_pf_cap_));
         d_prompt_pf_.alloc((size_t)256 * Q3_EMBD); d_pfa_seq_.alloc(256); d_pfa_slot_.alloc(256); d_pfa_pos_.alloc(4 * 256);
         d_pfa_codes_.alloc((size_t)256 * 16); d_pfa_ids_.alloc(256);
@@ -136,6 +137,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_ppos_.alloc(pos.size()); d_ppos_.upload(pos.data(), pos.size());
     h_pend_.assign(B, std::vector<int32_t>()); h_pend_off_.assign(B, 0);
     slot_req_.assign(B, nullptr);
+    if (const char* e = std::getenv("Q3_SCORE_WIDTH")) score_w_ = std::max(16, std::min(64, atoi(e))); // experiment knob (DESIGN.md "Scoring given frames")
     if (async_pf_) { d_pf_logits_.alloc((size_t)B * tl_stride_); d_pf_hidden_.alloc((size_t)B * Q3_EMBD); }
     {
         std::vector<q3_u64> k0((size_t)16 * B, pack_key(-INFINITY, 0)), n0(B, pack_key(-INFINITY, 0));
@@ -195,6 +197,7 @@ struct Engine::Req {
     bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
+    bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
     size_t pcm_ready = 0; // samples whose decode has completed (harvested events)
@@ -387,11 +390,15 @@ void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
     const int chunk = talker_->max_tok();
     std::vector<int32_t> seq(chunk), slot(chunk), pos((size_t)4 * chunk);
     PrefillCursor cur; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb;
+    std::vector<char> is_score; // [EXT] scoring: which requests of the wave only want their rows scored
+    for (Req* r : batch) is_score.push_back(r->score);
     talker_->set_same_seq_tokens(true);
     for (size_t done = 0; done < total;) {
         const size_t n_max = std::min<size_t>(total - done, (size_t)chunk);
         float* stage = (float*)stage_alloc(n_max * Q3_EMBD * 4);
         int32_t* hc = (int32_t*)stage_alloc(n_max * 68); // [EXT] resume: codes [rows][16] and ids [rows] of the chunk's feedback rows
+        int32_t* hs = (int32_t*)stage_alloc(n_max * 64); // [EXT] scoring: codes [rows][16] of the chunk's score rows
+        const PrefillCursor before = cur;
         const int n = pack_prefill_chunk(refs, cur, chunk, stage, seq.data(), slot.data(), pos.data(), lasts, &fb);
         for (auto& run : staged_runs(n, fb))
             Q3_HIP(hipMemcpyAsync(d_prompt_.p + (size_t)run.first * Q3_EMBD, stage + (size_t)run.first * Q3_EMBD, (size_t)run.second * Q3_EMBD * 4, hipMemcpyHostToDevice, st_));
@@ -400,7 +407,9 @@ void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
         TokMeta tm{d_pf_seq_.p, d_pf_slot_.p, d_pf_pos_.p};
         Transformer::Input in; in.x = d_prompt_.p; in.x_stride = Q3_EMBD;
         talker_->forward(st_, in, n, tm, kv_t_->view(), nullptr);
+        score_chunk(st_, *talker_, batch, score_head_runs(refs, is_score, before, n), hs);
         for (auto& lb : lasts) {
+            if (is_score[lb.first]) continue; // no first frame to draw
             const int sb = refs[lb.first].slot, ti = lb.second;
             const bool hist = resumed_penalised(batch[lb.first]->r); // [EXT] resume: the first head already sees a history, greedy slots included
             const bool rec = batch[lb.first]->r.logprobs;       // [EXT] log-probabilities: the first frame's talker columns need the logits
@@ -828,7 +837,7 @@ void Engine::admit(bool stalled) {
     if (async_pf_ && n_active_ > 0) { prefill_async(batch); return; } // sequences are running: do not stall them
     // ---- in-line form (nothing is running, or a single-slot engine): one batched prefill of the whole wave on the AR stream ----
     arena_used_ = 0; // st_ is idle between scheduler operations
-    for (Req* r : batch) kv_t_->release(r->slot), kv_t_->ensure(r->slot, r->r.n_prompt + r->r.max_steps + 1, st_);
+    for (Req* r : batch) kv_t_->release(r->slot), kv_t_->ensure(r->slot, kv_positions(r->r, r->score), st_);
     pf_batch_ = batch;
     bool sampled = live_variant(slots_).sampled; // of the prefill heads: the wave joins whatever is live
     for (Req* r : batch) if (r->r.sampler.temperature > 0.0f) sampled = true;
@@ -842,9 +851,14 @@ void Engine::admit(bool stalled) {
     Q3_HIP(hipStreamSynchronize(st_));
     { float ms = 0; Q3_HIP(hipEventElapsedTime(&ms, e0, e1)); stats.prefill_ms += ms; }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    const double t = now_ms();
-    std::lock_guard<std::mutex> lk(mu_);
-    for (Req* r : batch) r->prefill_ms = t - r->t_submit;
+    {
+        const double t = now_ms();
+        std::lock_guard<std::mutex> lk(mu_);
+        for (Req* r : batch) r->prefill_ms = t - r->t_submit;
+    }
+    std::vector<Req*> scores; // [EXT] scoring: their rows are computed; they were never live
+    for (Req* r : batch) if (r->score) scores.push_back(r);
+    finish_scores(scores);
 }
 
 // Prefill of one admission wave on the second talker instance / stream: every chunk is enqueued without host waits (the prompts of
@@ -855,8 +869,10 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
     for (Req* r : batch) {
         total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix});
         kv_t_->release(r->slot);
-        kv_t_->ensure(r->slot, r->r.n_prompt + r->r.max_steps + 1, st_pf_);
+        kv_t_->ensure(r->slot, kv_positions(r->r, r->score), st_pf_);
     }
+    std::vector<char> is_score;
+    for (Req* r : batch) is_score.push_back(r->score);
     const int chunk = talker_pf_->max_tok();
     unsigned char* cur = arena_pf_;
     PrefillCursor pc; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb; size_t done_tok = 0;
@@ -870,6 +886,8 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
         int32_t* slot = (int32_t*)cur; cur += (size_t)n_max * 4;
         int32_t* pos = (int32_t*)cur; cur += (size_t)n_max * 16;
         int32_t* hc = (int32_t*)cur; cur += (size_t)n_max * 68; // [EXT] resume: codes and ids of the chunk's feedback rows
+        int32_t* hs = (int32_t*)cur; cur += (size_t)n_max * 64; // [EXT] scoring: codes of the chunk's score rows
+        const PrefillCursor before = pc;
         Q3_CHECK((size_t)(cur - arena_pf_) <= arena_pf_cap_, "prefill staging arena overflow");
         const int n = pack_prefill_chunk(refs, pc, n_max, stage, seq, slot, pos, lasts, &fb);
         for (auto& run : staged_runs(n, fb))
@@ -881,7 +899,9 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
         TokMeta tm{d_pfa_seq_.p, d_pfa_slot_.p, d_pfa_pos_.p};
         Transformer::Input in; in.x = d_prompt_pf_.p; in.x_stride = Q3_EMBD;
         talker_pf_->forward(st_pf_, in, n, tm, kv_t_->view(), nullptr);
+        score_chunk(st_pf_, *talker_pf_, batch, score_head_runs(refs, is_score, before, n), hs);
         for (auto& lb : lasts) { // logits + hidden of the LAST prompt token (engine.rs:550-554,565-566); code_0 is drawn at activation
+            if (is_score[lb.first]) continue;
             const int sb = refs[lb.first].slot;
             talker_pf_->head(st_pf_, lb.second, 1, 0, tl_stride_, d_pf_logits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_pf_hidden_.p + (size_t)sb * Q3_EMBD);
         }
@@ -906,6 +926,9 @@ void Engine::activate() {
         batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->cancel; }), batch.end());
     }
     for (Req* r : dropped) retire(r, false); // slot, KV pages and -- through the fence, behind the reset task already queued -- codec stream
+    std::vector<Req*> scores; // [EXT] scoring: a score request never goes live; an asynchronous wave's end here (the in-line form's: admit)
+    for (Req* r : batch) if (r->score) scores.push_back(r);
+    batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->score; }), batch.end());
     arena_used_ = 0; // st_ is idle between scheduler operations
     q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
     for (Req* r : batch) {
@@ -947,6 +970,7 @@ void Engine::activate() {
         slots_.live[b] = 1;
     }
     upload_slot_state();
+    bool async_wave = false;
     if (n_prefilling_ > 0) { // the wave was prefilled on the second talker instance
         float ms = 0;
         Q3_HIP(hipEventElapsedTime(&ms, pf_e0_, pf_done_));
@@ -965,10 +989,136 @@ void Engine::activate() {
         const double t = now_ms();
         std::lock_guard<std::mutex> lk(mu_);
         for (Req* r : batch) r->prefill_ms = t - r->t_submit;
+        for (Req* r : scores) r->prefill_ms = t - r->t_submit;
         n_active_ += (int)batch.size();
+        async_wave = true;
     } else {
         std::lock_guard<std::mutex> lk(mu_);
         n_active_ += (int)batch.size();
+    }
+    if (async_wave) finish_scores(scores);
+}
+
+// [EXT] scoring given frames.  Like the log-probability buffers, the state goes to the device on first use, under the same locks.
+void Engine::ensure_score() {
+    std::lock_guard<std::mutex> lk(sc_mu_);
+    if (sc_ready_.load()) return;
+    std::lock_guard<std::mutex> cap(capture_mutex());
+    int prev = 0;
+    Q3_HIP(hipGetDevice(&prev));
+    Q3_HIP(hipSetDevice(dev_));
+    try {
+        const int W = score_w_, rows = std::max(talker_->max_tok(), 256); // rows: the widest prefill chunk of either lane
+        pred_sc_.reset(new Transformer(*predictor_, 16 * W));
+        kv_sc_.reset(new KvPool(predictor_->hp().n_layer, predictor_->hp().n_kv, W, W, 1));
+        for (int w = 0; w < W; w++) kv_sc_->ensure(w, 16);
+        std::vector<int32_t> seq, slot, pos;
+        for (int F = 1; F <= W; F++)
+            for (int p = 0; p < 16; p++)
+                for (int f = 0; f < F; f++) { seq.push_back(f); slot.push_back(p); for (int s4 = 0; s4 < 4; s4++) pos.push_back(p); } // engine.rs:316-318
+        d_sc_seq_.alloc(seq.size()); d_sc_seq_.upload(seq.data(), seq.size());
+        d_sc_slot_.alloc(slot.size()); d_sc_slot_.upload(slot.data(), slot.size());
+        d_sc_pos_.alloc(pos.size()); d_sc_pos_.upload(pos.data(), pos.size());
+        std::vector<const float*> tabs(15); std::vector<int64_t> tab_rows(15);
+        for (int q = 0; q < 15; q++) { tabs[q] = d_proj_tab_[q].p; tab_rows[q] = assets_->codec_rows[q]; }
+        d_sc_tabs_.alloc(15); d_sc_tabs_.upload(tabs.data(), 15);
+        d_sc_tab_rows_.alloc(15); d_sc_tab_rows_.upload(tab_rows.data(), 15);
+        d_sc_codes_.alloc((size_t)rows * 16); d_sc_tlogits_.alloc((size_t)rows * tl_stride_); d_sc_hidden_.alloc((size_t)rows * Q3_EMBD);
+        d_sc_hproj_.alloc((size_t)W * dP_); d_sc_in_.alloc((size_t)16 * W * dP_); d_sc_plogits_.alloc((size_t)15 * W * Q3_CODEBOOK_SIZE);
+        d_sc_out_.alloc((size_t)B_ * p_.max_steps * Q3_LOGPROB_COLS);
+        Q3_HIP(hipStreamSynchronize(nullptr)); // the pool's memsets ran on the null stream; the engine's streams do not wait for it
+    } catch (...) { (void)hipSetDevice(prev); throw; }
+    Q3_HIP(hipSetDevice(prev));
+    sc_ready_ = true;
+}
+
+int64_t Engine::submit_score(const float* prompt, int n_prompt, const int32_t* trail, int n_trail, const int32_t* codes, int n) {
+    if (const char* why = score_refusal(prompt, n_prompt, p_.max_prompt, trail, n_trail, codes, n, p_.max_steps, kv_rows_, talker_->ggml_mode()))
+        throw Error(why);
+    ensure_score();
+    if (n_trail > 0) ensure_text_stream();
+    std::unique_ptr<Req> r(new Req());
+    r->score = true;
+    GenRequest& g = r->r;
+    g.n_prompt = n_prompt; g.max_steps = n; g.sampler.temperature = 0.0f; g.n_trail = n_trail;
+    g.n_prefix = n - 1; // feedback rows behind the prompt: the last frame's row would only serve a frame n
+    r->prompt_own.assign(prompt, prompt + (size_t)n_prompt * Q3_EMBD); g.prompt = r->prompt_own.data();
+    r->trail_own.assign(trail, trail + n_trail); g.trail = r->trail_own.data();
+    r->prefix_own.assign(codes, codes + (size_t)n * 16); g.prefix = r->prefix_own.data();
+    r->t_submit = now_ms();
+    std::lock_guard<std::mutex> lk(mu_);
+    r->id = next_id_++;
+    Req* raw = r.get();
+    reqs_[raw->id] = std::move(r);
+    pending_.push_back(raw);
+    wake_++;
+    cv_.notify_all();
+    return raw->id;
+}
+
+// The score rows of one prefill chunk, behind the chunk's forward on its stream: per run the talker head over the rows (logits and hidden rows
+// into chunk-wide buffers), then passes of at most W frames on the second predictor context -- projection of the hidden rows (k_project_mt, as
+// the frame graph's), k_score_inputs, one forward of 16 F position-major tokens, 15 heads over contiguous token ranges, k_score_rows.
+void Engine::score_chunk(hipStream_t st, Transformer& talker, const std::vector<Req*>& batch, const std::vector<ScoreRun>& runs, int32_t* h_codes) {
+    if (runs.empty()) return;
+    const int W = score_w_;
+    int at = 0;
+    for (const ScoreRun& run : runs) {
+        Req* r = batch[run.req];
+        Q3_CHECK((size_t)(at + run.n) * 16 <= d_sc_codes_.n && run.frame + run.n <= r->r.max_steps, "score rows outside the chunk buffers");
+        std::copy(r->prefix_own.begin() + (size_t)run.frame * 16, r->prefix_own.begin() + (size_t)(run.frame + run.n) * 16, h_codes + (size_t)at * 16);
+        Q3_HIP(hipMemcpyAsync(d_sc_codes_.p + (size_t)at * 16, h_codes + (size_t)at * 16, (size_t)run.n * 64, hipMemcpyHostToDevice, st));
+        talker.head(st, run.row, run.n, 0, tl_stride_, d_sc_tlogits_.p + (size_t)at * tl_stride_, tl_stride_, nullptr, -1, d_sc_hidden_.p + (size_t)at * Q3_EMBD);
+        for (int f0 = 0; f0 < run.n; f0 += W) {
+            const int F = std::min(W, run.n - f0);
+            const int32_t* codes = d_sc_codes_.p + (size_t)(at + f0) * 16;
+            launch_project_blk(st, d_sc_hidden_.p + (size_t)(at + f0) * Q3_EMBD, Q3_EMBD, d_proj_wblk_.p, d_proj_b_.p, Q3_EMBD, dP_, d_sc_hproj_.p, dP_, F);
+            launch_score_inputs(st, d_sc_hproj_.p, d_sc_tabs_.p, d_sc_tab_rows_.p, dP_, codes, F, d_sc_in_.p);
+            const size_t m0 = (size_t)16 * F * (F - 1) / 2; // the routing tables of width F
+            TokMeta tm{d_sc_seq_.p + m0, d_sc_slot_.p + m0, d_sc_pos_.p + m0 * 4};
+            Transformer::Input in; in.x = d_sc_in_.p; in.x_stride = dP_;
+            pred_sc_->set_same_seq_tokens(true);
+            pred_sc_->forward(st, in, 16 * F, tm, kv_sc_->view(), nullptr);
+            for (int q = 0; q < 15; q++) // the logits for codes[f][q + 1]: head slice q at position q + 1
+                pred_sc_->head(st, (q + 1) * F, F, q * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE, d_sc_plogits_.p + (size_t)q * W * Q3_CODEBOOK_SIZE, Q3_CODEBOOK_SIZE);
+            ScoreRowsArgs sa;
+            sa.tlogits = d_sc_tlogits_.p + (size_t)(at + f0) * tl_stride_; sa.t_stride = tl_stride_;
+            sa.plogits = d_sc_plogits_.p; sa.p_head_stride = (size_t)W * Q3_CODEBOOK_SIZE; sa.codes = codes;
+            sa.out = d_sc_out_.p + ((size_t)r->slot * p_.max_steps + run.frame + f0) * Q3_LOGPROB_COLS;
+            launch_score_rows(st, sa, F);
+        }
+        at += run.n;
+    }
+    Q3_LAUNCH_CHECK();
+}
+
+// Scheduler thread, st_ idle and the wave's prefill complete: a score request's rows come to the host, rows and codes appear in one critical
+// section, and the slot and its KV pages are free again.  A request cancelled meanwhile ends CANCELLED with no frames.
+void Engine::finish_scores(const std::vector<Req*>& scores) {
+    for (Req* r : scores) {
+        const int b = r->slot, n = r->r.max_steps;
+        bool cancelled;
+        { std::lock_guard<std::mutex> lk(mu_); cancelled = r->cancel; }
+        const float* rows = nullptr;
+        if (!cancelled) {
+            arena_used_ = 0;
+            rows = (const float*)d2h_begin(d_sc_out_.p + (size_t)b * p_.max_steps * Q3_LOGPROB_COLS, (size_t)n * Q3_LOGPROB_COLS * 4);
+            Q3_HIP(hipStreamSynchronize(st_));
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (r->cancel) r->state = REQ_CANCELLED;
+            else {
+                r->codes = r->prefix_own;
+                r->lp.assign(rows, rows + (size_t)n * Q3_LOGPROB_COLS);
+                r->fed = n;
+                r->state = REQ_DONE;
+            }
+            slot_req_[b] = nullptr; r->slot = -1;
+            r->t_done = now_ms();
+            cv_.notify_all();
+        }
+        kv_t_->release(b);
     }
 }
 
@@ -1155,7 +1305,7 @@ void Engine::fetch_logprobs(int64_t id, float* out, int frame_off, int max_frame
     auto it = reqs_.find(id);
     Q3_CHECK(it != reqs_.end(), "unknown request id");
     const Req& r = *it->second;
-    Q3_CHECK(r.r.logprobs, "the request does not record log-probabilities (q3tts_engine_set_logprobs was off when it was submitted)");
+    Q3_CHECK(r.r.logprobs || r.score, "the request does not record log-probabilities (q3tts_engine_set_logprobs was off when it was submitted)");
     int nf = 0;
     if (out && frame_off >= 0 && frame_off < r.fed && max_frames > 0) {
         nf = std::min(max_frames, r.fed - frame_off);

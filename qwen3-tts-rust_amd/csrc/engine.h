@@ -81,6 +81,11 @@ public:
     // [EXT] stops a request wherever it is; thread-safe and free of HIP calls (the scheduler retires the slot between two frame groups):
     // 0 cancellation requested, 1 the request had already ended; throws for an unknown id
     int cancel(int64_t id);
+    // [EXT] scoring given frames (q3tts_spec.h "scoring"): teacher-forced log-probabilities of codes [n][16] behind prompt [n_prompt][2048] and
+    // optional closed trailing ids.  Queued like any request; ends REQ_DONE with n frames (the given codes) and their [n][17] rows, no PCM.
+    // Thread-safe; the first call allocates the scoring state; throws score_refusal's reason before anything is queued
+    int64_t submit_score(const float* prompt, int n_prompt, const int32_t* trail, int n_trail, const int32_t* codes, int n);
+    int score_width() const { return score_w_; } // frames per predictor scoring pass
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -122,6 +127,12 @@ private:
     static bool resumed_penalised(const GenRequest& g) { return g.n_prefix > 0 && g.opts.penalised(); }
     // [EXT] log-probabilities: columns 0 and 16 of slot b's row `row` from the talker logits row a prefill head wrote and the key its sampler drew
     void first_head_logprobs(hipStream_t st, const float* logits_row, int b, int row);
+    // [EXT] scoring: the state's one-time allocation; the talker heads and predictor passes of a prefill chunk's score rows, on the chunk's
+    // stream (h_codes: pinned, 64 B per row of the chunk); the rows' way to the host and the end of the requests (st_ idle)
+    void ensure_score();
+    void score_chunk(hipStream_t st, Transformer& talker, const std::vector<Req*>& batch, const std::vector<ScoreRun>& runs, int32_t* h_codes);
+    void finish_scores(const std::vector<Req*>& scores);
+    static int kv_positions(const GenRequest& g, bool score) { return score ? g.n_prompt + g.n_prefix + 1 : g.n_prompt + g.max_steps + 1; }
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
     // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
     // join the batch ("activate") between two frame groups once the prefill event has completed.
@@ -183,6 +194,14 @@ private:
     // slot records.  lp_on_: what submit() reads; lp_ready_ is written under lp_mu_ and capture_mutex()
     DevBuf<float> d_lp_, d_plp_; DevBuf<int32_t> d_lp_rec_; int lp_rows_ = 0;
     std::mutex lp_mu_; std::atomic<bool> lp_on_{false}, lp_ready_{false};
+    // [EXT] scoring given frames, allocated by the first submit_score: a second predictor context over the shared weights (16 W tokens a pass)
+    // with W one-page sequences of its own, routing tables for every pass width F <= W (token p*F + f: sequence f, position p; the tables of
+    // width F start at 16 * F(F-1)/2), the 15 pre-projected table pointers, and per prefill chunk the talker logits / hidden rows / codes of
+    // its score rows.  d_sc_out_ [B][max_steps][17]: slot b's rows until finish_scores takes them.  Written under sc_mu_ and capture_mutex()
+    std::unique_ptr<Transformer> pred_sc_; std::unique_ptr<KvPool> kv_sc_; int score_w_ = 32;
+    DevBuf<int32_t> d_sc_seq_, d_sc_slot_, d_sc_pos_, d_sc_codes_; DevBuf<const float*> d_sc_tabs_; DevBuf<int64_t> d_sc_tab_rows_;
+    DevBuf<float> d_sc_tlogits_, d_sc_hidden_, d_sc_hproj_, d_sc_in_, d_sc_plogits_, d_sc_out_;
+    std::mutex sc_mu_; std::atomic<bool> sc_ready_{false};
     std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = FrameVariant::key(width)
     bool instrument_ = false; bool pred_identity_pages_ = false;
     std::vector<std::vector<int32_t>> h_pend_; std::vector<int> h_pend_off_; // appended ids not yet on the device: ids [off, off+size)

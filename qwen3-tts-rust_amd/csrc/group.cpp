@@ -374,6 +374,18 @@ int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+int q3tts_group_submit_score(q3tts_group* g, int32_t engine_index, const float* prompt, int32_t n_prompt, const int32_t* trail_ids, int32_t n_trail,
+                             const int32_t* codes, int32_t n, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && req_id, "null argument");
+    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
+    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
+    int64_t id = 0;
+    if (q3tts_submit_score(g->eng[i], prompt, n_prompt, trail_ids, n_trail, codes, n, &id) != Q3TTS_OK) return Q3TTS_ERR;
+    *req_id = (id << kEngineBits) | i;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_group_set_logprobs(q3tts_group* g, int32_t on) { // [EXT] q3tts_engine_set_logprobs on every engine
     if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
     for (auto* e : g->eng) if (q3tts_engine_set_logprobs(e, on) != Q3TTS_OK) return Q3TTS_ERR;

@@ -284,4 +284,18 @@ struct LogprobArgs {
 };
 void launch_logprob_rows(hipStream_t st, const LogprobArgs& a, int B);
 
+// [EXT] scoring given frames (score.hip, q3tts_spec.h "scoring"): one teacher-forced predictor pass over F frames.
+// Input rows out[(p*F + f)*dP + ..], p = 0..15: p = 0 copies hidden_proj[f] (the projected hidden row), p >= 1 row codes[f][p-1] of tabs[p-1]
+// (tab_rows[p-1] rows of dP floats; a negative code reads row 0, a code past the table gives a zero row).  tabs / tab_rows / codes: device.
+void launch_score_inputs(hipStream_t st, const float* hidden_proj, const float* const* tabs, const int64_t* tab_rows, int dP, const int32_t* codes,
+                         int F, float* out);
+// out[f][17] of frames f = 0..F-1 in k_logprob_rows' arithmetic: columns 0 / 16 from tlogits[f*t_stride + [0, Q3_SAMPLE_END)) at codes[f][0] /
+// Q3_CODEC_EOS, column q + 1 from plogits[q*p_head_stride + f*2048 + [0, 2048)) at codes[f][q + 1]
+struct ScoreRowsArgs {
+    const float* tlogits = nullptr; int t_stride = 0;
+    const float* plogits = nullptr; size_t p_head_stride = 0;
+    const int32_t* codes = nullptr; float* out = nullptr;
+};
+void launch_score_rows(hipStream_t st, const ScoreRowsArgs& a, int F);
+
 } // namespace q3

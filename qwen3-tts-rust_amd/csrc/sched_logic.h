@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer and the checks of a resumed prefix.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix and of a score request, and the chunk rows a score request needs the head for.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -180,6 +180,42 @@ inline const char* resume_refusal(int n_prompt, int max_steps, const int32_t* co
     if (open && n_trail < n_prefix) return "an open trail must hold at least n_prefix ids: the prefix frames ran, so their ids were known";
     if ((int64_t)n_prompt + n_prefix + 1 > kv_rows) return "n_prompt + n_prefix exceeds the slot's KV capacity";
     return nullptr;
+}
+
+// [EXT] scoring given frames (q3tts_spec.h "scoring"): why a score request is refused, or null.  Pure, like resume_refusal, whose code range
+// checks it reuses (a score request has no frame to generate, so n = max_steps of the engine is allowed).  ggml: the engine runs Q3_SPEC=ggml.
+inline const char* score_refusal(const float* prompt, int n_prompt, int max_prompt, const int32_t* trail, int n_trail, const int32_t* codes, int n,
+                                 int max_steps, int64_t kv_rows, bool ggml) {
+    if (ggml) return "scoring is not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)";
+    if (n <= 0) return "n must be >= 1: there is no frame to score";
+    if (n > max_steps) return "n exceeds the engine's max_steps";
+    if (!codes) return "codes missing";
+    if (!prompt) return "prompt missing";
+    if (n_prompt < 1 || n_prompt > max_prompt) return "prompt length out of range";
+    if (n_trail < 0 || n_trail > max_prompt) return "n_trail must be in [0, max_prompt]";
+    if (n_trail > 0 && !trail) return "trailing ids missing";
+    if ((int64_t)n_prompt + n > kv_rows) return "n_prompt + n exceeds the slot's KV capacity";
+    // the code ranges: resume_refusal's, with its own limits out of the way (n + 1 steps, a closed trail, the capacity checked above)
+    return resume_refusal(n_prompt, n + 1, codes, n, false, n_trail, (int64_t)n_prompt + n + 1);
+}
+
+// The rows of one prefill chunk that a score request needs the talker head for.  Frame f of a request with n prompt rows is scored from row
+// n - 1 + f of its stream: the last prompt row and every feedback row (the packer is given n_fb = frames - 1 feedback rows, so the stream ends
+// with the row of the last frame).  `before` is the cursor pack_prefill_chunk started the chunk from, n_chunk the token count it returned;
+// a run is (request, first row inside the chunk, first frame, number of rows), in chunk order.  score[i] != 0: request i is a score request.
+struct ScoreRun { int req, row, frame, n; };
+inline std::vector<ScoreRun> score_head_runs(const std::vector<PromptRef>& batch, const std::vector<char>& score, PrefillCursor before, int n_chunk) {
+    std::vector<ScoreRun> out;
+    PrefillCursor c = before;
+    for (int i = 0; i < n_chunk && c.req < batch.size(); i++) {
+        const PromptRef& r = batch[c.req];
+        if (score[c.req] && c.tok >= r.n - 1) {
+            if (!out.empty() && out.back().req == (int)c.req && out.back().row + out.back().n == i) out.back().n++;
+            else out.push_back({(int)c.req, i, c.tok - (r.n - 1), 1});
+        }
+        if (c.tok == r.n + r.n_fb - 1) { c.req++; c.tok = 0; } else c.tok++;
+    }
+    return out;
 }
 
 } // namespace q3

@@ -93,6 +93,7 @@ SYMBOLS = [
     "q3tts_cancel", "q3tts_group_cancel",
     "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
     "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
+    "q3tts_submit_score", "q3tts_group_submit_score", "q3tts_engine_score_width", "q3tts_op_score_rows", "q3tts_op_score_inputs",
     "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows",
 ]
 
@@ -210,6 +211,12 @@ def lib():
         L.q3tts_fetch_logprobs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.q3tts_group_set_logprobs.argtypes = L.q3tts_engine_set_logprobs.argtypes
         L.q3tts_group_fetch_logprobs.argtypes = L.q3tts_fetch_logprobs.argtypes
+        L.q3tts_submit_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+        L.q3tts_group_submit_score.argtypes = [C.c_void_p, C.c_int32] + L.q3tts_submit_score.argtypes[1:]
+        L.q3tts_engine_score_width.argtypes = [C.c_void_p]
+        L.q3tts_engine_score_width.restype = C.c_int32
+        L.q3tts_op_score_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.q3tts_op_score_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_logprob_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
@@ -324,6 +331,46 @@ def op_logprob_rows(logits, chosen, n=None, extra_idx=-1):
     out, extra = np.zeros(B, np.float32), np.zeros(B, np.float32)
     _chk(lib().q3tts_op_logprob_rows(_p(lg), B, stride if n is None else n, stride, _p(c), extra_idx, _p(out), _p(extra) if extra_idx >= 0 else None))
     return (out, extra) if extra_idx >= 0 else out
+
+
+def op_score_rows(tlogits, plogits, codes):
+    """[EXT] k_score_rows over host buffers: tlogits [F][t_stride >= 2160] f32, plogits [15][F][2048], codes [F][16] -> float32 [F][17]"""
+    tl = np.ascontiguousarray(tlogits, np.float32)
+    pl = np.ascontiguousarray(plogits, np.float32)
+    c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+    F = c.shape[0]
+    if tl.ndim != 2 or tl.shape[0] != F or pl.shape != (15, F, 2048):
+        raise Q3Error("op_score_rows: tlogits [F][stride], plogits [15][F][2048], codes [F][16]")
+    out = np.zeros((F, LOGPROB_COLS), np.float32)
+    _chk(lib().q3tts_op_score_rows(_p(tl), tl.shape[1], _p(pl), _p(c), F, _p(out)))
+    return out
+
+
+def op_score_inputs(hidden_proj, tabs, codes):
+    """[EXT] k_score_inputs over host buffers: hidden_proj [F][dP], tabs = 15 tables [rows_q][dP], codes [F][16] -> float32 [16 F][dP],
+    row p * F + f = position p of frame f"""
+    hp = np.ascontiguousarray(hidden_proj, np.float32)
+    c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+    F, dP = hp.shape
+    tb = [np.ascontiguousarray(t, np.float32) for t in tabs]
+    if len(tb) != 15 or c.shape[0] != F or any(t.ndim != 2 or t.shape[1] != dP for t in tb):
+        raise Q3Error("op_score_inputs: hidden_proj [F][dP], 15 tables [rows][dP], codes [F][16]")
+    ptrs = (C.c_void_p * 15)(*[t.ctypes.data for t in tb])
+    rows = np.array([t.shape[0] for t in tb], np.int64)
+    out = np.zeros((16 * F, dP), np.float32)
+    _chk(lib().q3tts_op_score_inputs(_p(hp), ptrs, _p(rows), dP, _p(c), F, _p(out)))
+    return out
+
+
+def group_submit_score(group, engine_index, prompt, codes, trailing_ids=None):
+    """[EXT] q3tts_group_submit_score on a q3tts_group handle (engine_index -1 = round robin): the group request id"""
+    pr = np.ascontiguousarray(prompt, np.float32)
+    c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+    tr = np.ascontiguousarray(trailing_ids if trailing_ids is not None else [], np.int32)
+    rid = C.c_int64()
+    _chk(lib().q3tts_group_submit_score(group, engine_index, _p(pr), pr.shape[0], _p(tr) if tr.size else None, tr.size,
+                                        _p(c) if c.size else None, c.shape[0], C.byref(rid)))
+    return rid.value
 
 
 def _fetch_logprobs(fn, h, rid, frame_off, max_frames):
@@ -453,6 +500,21 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         else:
             _chk(lib().q3tts_submit_ex(self.h, C.byref(r), 1 if want_pcm else 0, C.byref(o), C.byref(rid)))
         return rid.value
+
+    def submit_score(self, prompt, codes, trailing_ids=None):
+        """[EXT] scoring given frames (q3tts_submit_score): queues the teacher-forced scoring of codes [n][16] behind prompt [rows][2048]
+        (and closed trailing ids); when the request is DONE, fetch_logprobs gives float32 [n][17] and fetch the given codes"""
+        pr = np.ascontiguousarray(prompt, np.float32)
+        c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+        tr = np.ascontiguousarray(trailing_ids if trailing_ids is not None else [], np.int32)
+        rid = C.c_int64()
+        _chk(lib().q3tts_submit_score(self.h, _p(pr), pr.shape[0], _p(tr) if tr.size else None, tr.size, _p(c) if c.size else None,
+                                      c.shape[0], C.byref(rid)))
+        return rid.value
+
+    def score_width(self):
+        """[EXT] frames per predictor scoring pass (q3tts_engine_score_width)"""
+        return lib().q3tts_engine_score_width(self.h)
 
     def register_voice(self, spk_emb, ref_codes=None, ref_text_ids=None):
         spk = np.ascontiguousarray(spk_emb, np.float32)
