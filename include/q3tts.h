@@ -205,6 +205,25 @@ int q3tts_fetch_logprobs(q3tts_engine* e, int64_t req_id, float* out, int32_t fr
 int q3tts_submit_score(q3tts_engine* e, const float* prompt, int32_t n_prompt, const int32_t* trail_ids, int32_t n_trail,
                        const int32_t* codes, int32_t n, int64_t* req_id);
 int32_t q3tts_engine_score_width(q3tts_engine* e);   /* frames per predictor scoring pass */
+/* [EXT] candidate sets (q3tts_spec.h "candidate sets"): n sampled takes of ONE prompt behind ONE prefill, for best-of-n ranking with
+ * q3tts_fetch_logprobs / q3tts_submit_score and q3tts_cancel.  Candidate i is exactly what q3tts_submit_trailing(e, r, want_pcm, opts,
+ * trail_ids, n_trail) queues with r->sampler.has_seed = 1 and seed = seeds[i] -- its codes, PCM and log-probability rows are those of that
+ * request run alone, bit for bit -- with its own talker and predictor streams (seed ^ Q3_PRED_SEED_XOR); r->sampler.seed / has_seed are
+ * ignored.  Options and the closed trail are shared, the recording flag is read once for the set, and prompt and ids are copied once.
+ * The n requests are queued together and admitted whole into one wave: the set waits at the head of the queue until n slots (and, with
+ * want_pcm, n codec streams) are free, and nothing behind it overtakes.  The first member not cancelled in the queue is prefilled; its
+ * ceil(n_prompt / 64) KV pages are copied whole into the other members' pages by one kernel launch, and every member draws its first
+ * code_0 from the last prompt row's logits.  From then on the members are ordinary requests: req_ids[0 .. n-1] take q3tts_poll / _fetch /
+ * _wait / _cancel / _release / _fetch_logprobs one by one, and a cancelled member -- the prefilled one included -- leaves the others as
+ * they are.  n = 1 is q3tts_submit_trailing.  Greedy sampling is allowed: every candidate is then the plain greedy run.
+ * No resumed prefix and no open trail: a set is made of fresh requests with a closed trail (use q3tts_submit_resume / _trailing_open singly).
+ * Refused (< 0, q3tts_last_error says why, nothing is queued, req_ids untouched): n < 1; n > max_batch; seeds or req_ids NULL; n_trail < 0 or
+ * > max_prompt, or trail_ids NULL with n_trail > 0; a prompt, max_steps or options q3tts_submit_ex refuses; Q3_SPEC=ggml */
+int q3tts_submit_candidates(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                            const int32_t* trail_ids, int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids);
+/* sets of n >= 2 accepted; prompt rows whose prefill a copy replaced ((members prefilled together - 1) * n_prompt per set); KV pages copied,
+ * counted per destination.  Any pointer may be NULL */
+int q3tts_engine_candidate_stats(q3tts_engine* e, int64_t* sets, int64_t* prefill_rows_saved, int64_t* pages_copied);
 /* rows of one talker prefill launch: a longer admission wave (prompts + resumed prefixes) is prefilled in chunks of this many rows
  * (an asynchronous wave, admitted beside running requests, in chunks of at most 256) */
 int32_t q3tts_engine_prefill_width(q3tts_engine* e);
@@ -290,6 +309,9 @@ int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_
 /* [EXT] q3tts_submit_score on engine engine_index (-1 = round robin) */
 int q3tts_group_submit_score(q3tts_group* g, int32_t engine_index, const float* prompt, int32_t n_prompt, const int32_t* trail_ids,
                              int32_t n_trail, const int32_t* codes, int32_t n, int64_t* req_id);
+/* [EXT] q3tts_submit_candidates on engine engine_index (-1 = round robin): the whole set goes to ONE engine, every id carries its index */
+int q3tts_group_submit_candidates(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
+                                  const int32_t* trail_ids, int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids);
 int q3tts_group_set_logprobs(q3tts_group* g, int32_t on);      /* [EXT] q3tts_engine_set_logprobs on every engine */
 int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
@@ -490,6 +512,13 @@ int q3tts_op_logprob_rows(const float* logits, int32_t B, int32_t n, int32_t str
 int q3tts_op_score_rows(const float* tlogits, int32_t t_stride, const float* plogits, const int32_t* codes, int32_t F, float* out);
 int q3tts_op_score_inputs(const float* hidden_proj, const float* const* tabs, const int64_t* tab_rows, int32_t dP, const int32_t* codes,
                           int32_t F, float* out);
+/* [EXT] candidate sets test surface of k_kv_fork, host buffers: k_cache / v_cache [n_pages][n_layer][n_kv][8192] f16 bits, uploaded whole and
+ * written back whole (a stray write shows); page_table [n_seq][max_pages].  Logical pages [0, ceil(n_positions / 64)) of src_seq are copied
+ * into those of dst_seqs[0 .. n_dst-1].  Refused before anything is uploaded or launched: n_dst < 1; a sequence out of range; a destination
+ * equal to the source or listed twice; n_positions < 1 or > max_pages * 64; a page-table entry of the copied range outside [0, n_pages);
+ * two of the physical pages involved coincide */
+int q3tts_op_kv_fork(uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, int32_t n_layer, int32_t n_kv, const int32_t* page_table,
+                     int32_t n_seq, int32_t max_pages, int32_t src_seq, const int32_t* dst_seqs, int32_t n_dst, int32_t n_positions);
 /* [EXT] resume test surface, host buffers: rows [n][2048] = the feedback rows of codes [n][16] (+ trail ids [n_trail], row f takes id f
  * while f < n_trail; NULL / 0 = every row adds tts_pad) against the given tables (k_feedback_codes) */
 int q3tts_op_feedback_rows(const q3tts_assets* a, const int32_t* codes, int32_t n, const int32_t* trail_ids, int32_t n_trail, float* rows);

@@ -353,6 +353,22 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  * Refused: n < 1 or n > max_steps; a code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS (no request emits a frame with it); a residual
  * code outside [0, 2048); n_prompt + n beyond the KV capacity of a slot; the ggml-arithmetic mode. */
 
+/* ---------------- candidate sets [EXT] (q3tts_submit_candidates, q3tts_group_submit_candidates, q3tts_op_kv_fork) ----------------
+ * n sampled takes of one prompt behind one prefill.  Candidate i of a set over (prompt, options, closed trail, seeds[0..n)) is, bit for bit in
+ * its codes, PCM and log-probability rows, the request q3tts_submit_trailing queues for the same prompt, options and trail with seed seeds[i]:
+ *   streams    talker draws from StdRng(seeds[i]), predictor draws (sampled predictor) from StdRng(seeds[i] ^ Q3_PRED_SEED_XOR), both from draw 0
+ *   prefill    the talker's K/V of prompt position p depends on rows [0, p] of the prompt alone and the arithmetic is independent of launch
+ *              geometry, batch size and chunking, so the K/V one member's prefill wrote is the K/V every member's own prefill would write.
+ *              It is copied in whole pages: logical pages [0, ceil(n_prompt / 64)) of the prefilled member's sequence go, K plane and V
+ *              plane, into the same logical pages of every other member.  Positions n_prompt .. of the last copied page carry whatever the
+ *              source page held; no member reads a position before its own decode step has written it
+ *   frame 0    every member's code_0 is drawn by its own sampler state from the raw logits of prompt row n_prompt - 1, and its predictor starts
+ *              from that row's hidden state: one head pass per member in an in-line wave, one staged row copied per member in an asynchronous one
+ *   afterwards a member is an ordinary request: nothing in the frame graph knows about sets
+ * A set is admitted whole (one slot per member, one codec stream per member with PCM) and its rows count once against the 4096 rows of an
+ * asynchronous wave.  A member cancelled in the queue leaves the set; the first member left is the one prefilled.
+ * Refused: n < 1 or n > max_batch; a resumed prefix or an open trail (not expressible); the ggml-arithmetic mode. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

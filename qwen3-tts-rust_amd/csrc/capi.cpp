@@ -146,6 +146,30 @@ int q3tts_submit_score(q3tts_engine* e, const float* prompt, int32_t n_prompt, c
     Q3_API_END(Q3TTS_ERR)
 }
 int32_t q3tts_engine_score_width(q3tts_engine* e) { return e ? e->e->score_width() : -1; }
+int q3tts_submit_candidates(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, const int32_t* trail_ids,
+                            int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && r, "null argument");
+    GenRequest g = to_gen(*r);
+    g.opts = to_opts(opts);
+    g.trail = trail_ids; g.n_trail = n_trail;
+    std::vector<int64_t> ids((size_t)std::max(n, 1)); // the caller's array is written only when the whole set is queued
+    e->e->submit_candidates(g, want_pcm != 0, seeds, n, req_ids ? ids.data() : nullptr);
+    std::copy(ids.begin(), ids.begin() + n, req_ids);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_candidate_stats(q3tts_engine* e, int64_t* sets, int64_t* prefill_rows_saved, int64_t* pages_copied) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int64_t s = 0, r = 0, p = 0;
+    e->e->candidate_stats(&s, &r, &p);
+    if (sets) *sets = s;
+    if (prefill_rows_saved) *prefill_rows_saved = r;
+    if (pages_copied) *pages_copied = p;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_trail_append(q3tts_engine* e, int64_t req_id, const int32_t* ids, int32_t n, int32_t close) {
     Q3_API_BEGIN
     Q3_CHECK(e, "null argument");

@@ -402,6 +402,50 @@ int q3tts_linear_plan(q3tts_linear_desc* d) {
 
 uint64_t q3tts_argmax_key(float v, int32_t idx) { return pack_key(v, idx); }
 
+/* [EXT] candidate sets: k_kv_fork over host images of both cache planes; every precondition is checked before anything is uploaded or launched */
+int q3tts_op_kv_fork(uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, int32_t n_layer, int32_t n_kv, const int32_t* page_table,
+                     int32_t n_seq, int32_t max_pages, int32_t src_seq, const int32_t* dst_seqs, int32_t n_dst, int32_t n_positions) {
+    Q3_API_BEGIN
+    Q3_CHECK(k_cache && v_cache && page_table && dst_seqs, "null argument");
+    Q3_CHECK(n_pages >= 1 && n_layer >= 1 && n_kv >= 1 && n_seq >= 1 && max_pages >= 1, "bad cache / page table shape");
+    Q3_CHECK((int64_t)n_layer * n_kv <= 65536 && (int64_t)n_pages * n_layer * n_kv <= ((int64_t)1 << 24), "cache too large for the test surface");
+    Q3_CHECK(n_dst >= 1, "n_dst must be >= 1");
+    Q3_CHECK(n_positions >= 1 && (int64_t)n_positions <= (int64_t)max_pages * 64, "n_positions must be in [1, max_pages * 64]");
+    Q3_CHECK(src_seq >= 0 && src_seq < n_seq, "source sequence out of range");
+    const int np = (n_positions + 63) / 64;
+    std::vector<int> owner((size_t)n_pages, -1); // physical page -> the sequence that brought it in
+    std::vector<char> listed((size_t)n_seq, 0);
+    listed[src_seq] = 1;
+    for (int d = -1; d < n_dst; d++) {
+        const int seq = d < 0 ? src_seq : dst_seqs[d];
+        if (d >= 0) {
+            Q3_CHECK(seq >= 0 && seq < n_seq, "destination sequence out of range");
+            Q3_CHECK(seq != src_seq, "a destination equals the source");
+            Q3_CHECK(!listed[seq], "a destination is listed twice");
+            listed[seq] = 1;
+        }
+        for (int l = 0; l < np; l++) {
+            const int pg = page_table[(size_t)seq * max_pages + l];
+            Q3_CHECK(pg >= 0 && pg < n_pages, "page table entry out of range");
+            Q3_CHECK(owner[pg] < 0, "two of the physical pages involved coincide");
+            owner[pg] = seq;
+        }
+    }
+    require_gpu();
+    const size_t halfs = (size_t)n_pages * n_layer * n_kv * 8192;
+    DevBuf<uint16_t> dk(halfs), dv(halfs);
+    dk.upload(k_cache, halfs); dv.upload(v_cache, halfs);
+    DevBuf<int32_t> dpt((size_t)n_seq * max_pages), dd((size_t)n_dst);
+    dpt.upload(page_table, dpt.n); dd.upload(dst_seqs, dd.n);
+    KvCache kv; kv.k = dk.p; kv.v = dv.p; kv.page_table = dpt.p; kv.max_pages = max_pages; kv.n_layer = n_layer; kv.n_kv = n_kv;
+    launch_kv_fork(0, kv, src_seq, dd.p, n_dst, np);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    dk.download(k_cache, halfs); dv.download(v_cache, halfs);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 int q3tts_op_gemv_q8(const void* w, int32_t n, int32_t k, const int8_t* xq, const uint16_t* xd, int32_t ntok, float* y, int32_t lpr) {
     Q3_API_BEGIN
     require_gpu();

@@ -108,10 +108,10 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         Q3_HIP(hipEventCreate(&pf_done_)); Q3_HIP(hipEventCreate(&pf_e0_));
         // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row) and the
         // codes of score rows (64 B a row)
-        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16);
+        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4; // + [EXT] the fork destinations of a wave
         Q3_HIP(hipHostMalloc((void**)&arena_pf_, arena_pf_cap_));
         d_prompt_pf_.alloc((size_t)256 * Q3_EMBD); d_pfa_seq_.alloc(256); d_pfa_slot_.alloc(256); d_pfa_pos_.alloc(4 * 256);
-        d_pfa_codes_.alloc((size_t)256 * 16); d_pfa_ids_.alloc(256);
+        d_pfa_codes_.alloc((size_t)256 * 16); d_pfa_ids_.alloc(256); d_fork_dst_pf_.alloc(B);
     }
     // ---- per-slot state ----
     hist_stride_ = p.max_steps * 16;
@@ -124,7 +124,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_fb_.alloc((size_t)B * Q3_EMBD);
     d_prompt_.alloc((size_t)talker_->max_tok() * Q3_EMBD);
     d_pf_seq_.alloc(talker_->max_tok()); d_pf_slot_.alloc(talker_->max_tok()); d_pf_pos_.alloc(4 * (size_t)talker_->max_tok());
-    d_pf_codes_.alloc((size_t)talker_->max_tok() * 16); d_pf_ids_.alloc(talker_->max_tok());
+    d_pf_codes_.alloc((size_t)talker_->max_tok() * 16); d_pf_ids_.alloc(talker_->max_tok()); d_fork_dst_.alloc(B);
     d_hist_.zero(); d_tlogits_.zero(); d_thidden_.zero();
     // predictor routing: pass i (i = 2..15) handles position i of every slot; tables are [16][B] so any graph width can use them
     std::vector<int32_t> seq(B), slot((size_t)16 * B), pos((size_t)16 * B * 4);
@@ -189,8 +189,11 @@ void* Engine::d2h_begin(const void* src, size_t bytes) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+struct CandSet { std::vector<float> prompt; std::vector<int32_t> trail; }; // [EXT] candidate sets: what the members of a set share
 struct Engine::Req {
     int64_t id = 0;
+    int64_t set = 0; std::shared_ptr<const CandSet> shared; // [EXT] candidate sets: the set's id (0 = a plain request) and its one prompt / trail copy
+    const std::vector<int32_t>& trail_ids() const { return shared ? shared->trail : trail_own; }
     GenRequest r; std::vector<float> prompt_own; std::vector<int32_t> trail_own; bool want_pcm = false;
     std::vector<int32_t> prefix_own; // [EXT] resume: the caller's frames [n_prefix][16]; codes starts as a copy of it and fed at n_prefix
     bool closed = false;  // [EXT] open trail (r.open): closed by append_trail; trail_own and closed change under mu_ only
@@ -383,9 +386,11 @@ void Engine::upload_slot_state() {
 // Prefill (engine.rs:455-462) of newly admitted sequences: all prompts as ONE token stream, chunked by the talker's launch
 // width; tokens of different sequences share a launch (per-token seq/slot/pos routing); each sequence's last token gets the
 // head: code_0 of its first frame (:550-555) + the hidden row the predictor starts from (:565-566).
-void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
+void Engine::prefill(const std::vector<Req*>& wave, bool sampled) {
     size_t total = 0;
     std::vector<PromptRef> refs;
+    std::vector<Req*> batch; std::vector<std::vector<Req*>> rest; // [EXT] candidate sets: a set's later members add no rows
+    split_sets(wave, batch, rest);
     for (Req* r : batch) { total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix}); }
     const int chunk = talker_->max_tok();
     std::vector<int32_t> seq(chunk), slot(chunk), pos((size_t)4 * chunk);
@@ -408,9 +413,10 @@ void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
         Transformer::Input in; in.x = d_prompt_.p; in.x_stride = Q3_EMBD;
         talker_->forward(st_, in, n, tm, kv_t_->view(), nullptr);
         score_chunk(st_, *talker_, batch, score_head_runs(refs, is_score, before, n), hs);
-        for (auto& lb : lasts) {
+        for (auto& lb : lasts)
+          for (size_t m = 0; m <= rest[lb.first].size(); m++) { // [EXT] candidate sets: every member's slot draws from the set's last prompt token
             if (is_score[lb.first]) continue; // no first frame to draw
-            const int sb = refs[lb.first].slot, ti = lb.second;
+            const int sb = m == 0 ? refs[lb.first].slot : rest[lb.first][m - 1]->slot, ti = lb.second;
             const bool hist = resumed_penalised(batch[lb.first]->r); // [EXT] resume: the first head already sees a history, greedy slots included
             const bool rec = batch[lb.first]->r.logprobs;       // [EXT] log-probabilities: the first frame's talker columns need the logits
             if (sampled || hist || rec) {
@@ -427,6 +433,31 @@ void Engine::prefill(const std::vector<Req*>& batch, bool sampled) {
         }
         done += (size_t)n;
     }
+    if (batch.size() < wave.size()) fork_sets(st_, batch, rest, (int32_t*)stage_alloc((size_t)B_ * 4), d_fork_dst_.p); // a wave without a set stages nothing more
+}
+
+// [EXT] candidate sets.  The members of a set stand together in a wave (they were queued together and admitted whole); the first is prefilled.
+void Engine::split_sets(const std::vector<Req*>& batch, std::vector<Req*>& lead, std::vector<std::vector<Req*>>& rest) {
+    for (Req* r : batch) {
+        if (r->set != 0 && !lead.empty() && lead.back()->set == r->set) rest.back().push_back(r);
+        else { lead.push_back(r); rest.emplace_back(); }
+    }
+}
+// One k_kv_fork launch per set behind the wave's last chunk, on the chunks' stream: the pages that hold the prompt go from the prefilled
+// member's slot into the others'.  The page-table rows of all of them were uploaded on this stream before the first chunk.
+void Engine::fork_sets(hipStream_t st, const std::vector<Req*>& lead, const std::vector<std::vector<Req*>>& rest, int32_t* h_dst, int32_t* d_dst) {
+    int at = 0;
+    for (size_t i = 0; i < lead.size(); i++) {
+        const int n_dst = (int)rest[i].size(), n_pages = (lead[i]->r.n_prompt + 63) / 64;
+        if (n_dst == 0) continue;
+        Q3_CHECK(at + n_dst <= B_, "fork destinations beyond the slots");
+        for (int d = 0; d < n_dst; d++) h_dst[at + d] = rest[i][d]->slot;
+        Q3_HIP(hipMemcpyAsync(d_dst + at, h_dst + at, (size_t)n_dst * 4, hipMemcpyHostToDevice, st));
+        launch_kv_fork(st, kv_t_->view(), lead[i]->slot, d_dst + at, n_dst, n_pages);
+        cand_rows_saved_ += (int64_t)n_dst * lead[i]->r.n_prompt; cand_pages_ += (int64_t)n_dst * n_pages;
+        at += n_dst;
+    }
+    if (at > 0) Q3_LAUNCH_CHECK();
 }
 
 // [EXT] resume: the feedback rows of one prefill chunk.  The codes (64 B a frame) and trailing ids of every run go up through hc (pinned, not
@@ -688,6 +719,45 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     return raw->id;
 }
 
+// [EXT] candidate sets: n consecutive queue entries that share one copy of the prompt and trail; each is what submit() would queue with its seed.
+void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64_t* seeds, int n, int64_t* req_ids) {
+    if (const char* why = candidates_refusal(n, B_, seeds, req_ids, g0.trail, g0.n_trail, p_.max_prompt, talker_->ggml_mode())) throw Error(why);
+    GenRequest g = g0;
+    g.open = false; g.prefix = nullptr; g.n_prefix = 0; // not in a set
+    g.sampler.has_seed = true; g.sampler.seed = seeds[0];
+    if (n == 1) { req_ids[0] = submit(g, want_pcm, true); return; }
+    validate(g);
+    if (g.n_trail > 0) ensure_text_stream();
+    std::shared_ptr<CandSet> sh(new CandSet());
+    sh->prompt.assign(g.prompt, g.prompt + (size_t)g.n_prompt * Q3_EMBD);
+    sh->trail.assign(g.trail, g.trail + g.n_trail);
+    g.prompt = sh->prompt.data(); g.trail = sh->trail.data();
+    g.logprobs = g.logprobs || lp_on_.load(); // the engine's flag, read once per set
+    std::vector<std::unique_ptr<Req>> rs;
+    const double t = now_ms();
+    for (int i = 0; i < n; i++) {
+        std::unique_ptr<Req> r(new Req());
+        r->r = g; r->r.sampler.seed = seeds[i]; r->seed = seeds[i];
+        r->r.prefix = r->prefix_own.data();
+        r->shared = sh;
+        r->want_pcm = want_pcm && codec_;
+        r->t_submit = t;
+        rs.push_back(std::move(r));
+    }
+    std::lock_guard<std::mutex> lk(mu_);
+    const int64_t set = next_set_++;
+    for (int i = 0; i < n; i++) {
+        Req* raw = rs[i].get();
+        raw->set = set; raw->id = next_id_++;
+        req_ids[i] = raw->id;
+        reqs_[raw->id] = std::move(rs[i]);
+        pending_.push_back(raw);
+    }
+    cand_sets_++;
+    wake_++;
+    cv_.notify_all();
+}
+
 // [EXT] live text append.  The caller's thread only copies under mu_; the scheduler thread moves the ids to the device between frame
 // groups (collect_appends + run_group), so an append never issues a HIP call that could land inside another thread's graph capture.
 int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
@@ -714,7 +784,7 @@ void Engine::trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* 
     auto it = reqs_.find(id);
     Q3_CHECK(it != reqs_.end(), "unknown request id");
     const Req& r = *it->second;
-    const int n = (int)r.trail_own.size();
+    const int n = (int)r.trail_ids().size();
     *n_appended = n; *n_consumed = std::min(r.fed, n); *closed = !r.r.open || r.closed;
 }
 
@@ -804,20 +874,22 @@ void Engine::admit(bool stalled) {
         static const int quantum_div = [] { const char* e = std::getenv("Q3_ADMIT_DIV"); return e ? std::max(1, atoi(e)) : 8; }();
         const int free_slots = B_ - reserved, quantum = std::max(1, B_ / quantum_div);
         if (free_slots < quantum && n_active_ > 0 && free_slots < (int)pending_.size() && !stalled) return; // waiting slots free nothing
-        size_t rows = 0;
-        while (!pending_.empty() && reserved < B_) {
+        // what the wave takes (sched_logic.h): a slot each, a codec stream each with PCM, the 4096 rows of an asynchronous wave's staging arena,
+        // [EXT] a candidate set whole or not at all.  The rule sees the entries the free slots could take and the rest of the last one's set
+        std::vector<QueueEntry> q;
+        for (Req* r : pending_) {
+            if ((int)q.size() >= free_slots && (q.empty() || r->set == 0 || r->set != q.back().set)) break;
+            q.push_back({r->r.n_prompt + r->r.n_prefix, r->want_pcm, r->set});
+        }
+        for (int take = admission_take(q, free_slots, (int)cs_free_.size(), async_pf_ && n_active_ > 0); take > 0; take--) {
             Req* r = pending_.front();
-            if (r->want_pcm && cs_free_.empty()) break; // every codec stream still drains: admit after the next harvest
-            if (async_pf_ && n_active_ > 0 && !batch.empty() && rows + (size_t)r->r.n_prompt + r->r.n_prefix > 4096) break; // staging arena of one asynchronous wave
             int slot = -1;
             for (int b = 0; b < B_; b++) if (!slot_req_[b]) { slot = b; break; }
-            if (slot < 0) break;
             pending_.pop_front();
             r->slot = slot;
             if (r->want_pcm) { r->cs = cs_free_.back(); cs_free_.pop_back(); }
             r->state = REQ_RUNNING; r->t_admit = now_ms();
-            slot_req_[slot] = r; reserved++;
-            rows += (size_t)r->r.n_prompt + r->r.n_prefix;
+            slot_req_[slot] = r;
             batch.push_back(r);
         }
     }
@@ -863,11 +935,13 @@ void Engine::admit(bool stalled) {
 
 // Prefill of one admission wave on the second talker instance / stream: every chunk is enqueued without host waits (the prompts of
 // the wave sit in their own pinned arena); each sequence's last token leaves its logits row and hidden row in staging buffers.
-void Engine::prefill_async(const std::vector<Req*>& batch) {
+void Engine::prefill_async(const std::vector<Req*>& wave) {
     size_t total = 0;
     std::vector<PromptRef> refs;
-    for (Req* r : batch) {
-        total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix});
+    std::vector<Req*> batch; std::vector<std::vector<Req*>> rest; // [EXT] candidate sets: a set's later members add no rows
+    split_sets(wave, batch, rest);
+    for (Req* r : batch) { total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix}); }
+    for (Req* r : wave) {
         kv_t_->release(r->slot);
         kv_t_->ensure(r->slot, kv_positions(r->r, r->score), st_pf_);
     }
@@ -877,7 +951,7 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
     unsigned char* cur = arena_pf_;
     PrefillCursor pc; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb; size_t done_tok = 0;
     Q3_HIP(hipEventRecord(pf_e0_, st_pf_));
-    for (Req* r : batch) Q3_HIP(hipEventRecord(r->ev_admit, st_pf_));
+    for (Req* r : wave) Q3_HIP(hipEventRecord(r->ev_admit, st_pf_));
     talker_pf_->set_same_seq_tokens(true);
     while (done_tok < total) {
         const int n_max = (int)std::min<size_t>(total - done_tok, (size_t)chunk);
@@ -904,12 +978,18 @@ void Engine::prefill_async(const std::vector<Req*>& batch) {
             if (is_score[lb.first]) continue;
             const int sb = refs[lb.first].slot;
             talker_pf_->head(st_pf_, lb.second, 1, 0, tl_stride_, d_pf_logits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_pf_hidden_.p + (size_t)sb * Q3_EMBD);
+            for (Req* m : rest[lb.first]) { // [EXT] candidate sets: the staged rows reach every member; activate() stays per slot
+                Q3_HIP(hipMemcpyAsync(d_pf_logits_.p + (size_t)m->slot * tl_stride_, d_pf_logits_.p + (size_t)sb * tl_stride_, (size_t)tl_stride_ * 4, hipMemcpyDeviceToDevice, st_pf_));
+                Q3_HIP(hipMemcpyAsync(d_pf_hidden_.p + (size_t)m->slot * Q3_EMBD, d_pf_hidden_.p + (size_t)sb * Q3_EMBD, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_pf_));
+            }
         }
         done_tok += n;
     }
+    Q3_CHECK((size_t)(cur - arena_pf_) + (size_t)B_ * 4 <= arena_pf_cap_, "prefill staging arena overflow");
+    if (batch.size() < wave.size()) fork_sets(st_pf_, batch, rest, (int32_t*)cur, d_fork_dst_pf_.p);
     Q3_HIP(hipEventRecord(pf_done_, st_pf_));
-    pf_batch_ = batch;
-    n_prefilling_ = (int)batch.size();
+    pf_batch_ = wave;
+    n_prefilling_ = (int)wave.size();
 }
 
 // The admission wave joins the frame graph: slot state (positions, sampler parameters, RNG stream, frame counters) goes live, and --
@@ -956,7 +1036,7 @@ void Engine::activate() {
         }
         h_pend_[b].clear();
         std::vector<int32_t> ids; // [EXT] streaming text: the slot's trailing ids -- of an open trail those appended so far (later: collect_appends)
-        { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_own; slots_.hi(SF_OPEN)[b] = r->r.open && !r->closed; }
+        { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_ids(); slots_.hi(SF_OPEN)[b] = r->r.open && !r->closed; }
         slots_.hi(SF_NTRAIL)[b] = (int)ids.size(); // upload_slot_state below sends the count and the flag
         if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
         h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);

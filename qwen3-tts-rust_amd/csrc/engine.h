@@ -86,6 +86,15 @@ public:
     // Thread-safe; the first call allocates the scoring state; throws score_refusal's reason before anything is queued
     int64_t submit_score(const float* prompt, int n_prompt, const int32_t* trail, int n_trail, const int32_t* codes, int n);
     int score_width() const { return score_w_; } // frames per predictor scoring pass
+    // [EXT] candidate sets (q3tts_spec.h "candidate sets"): n requests of one prompt, candidate i exactly submit() of g with seed seeds[i] (g's own
+    // seed is ignored; no prefix, no open trail).  The prompt and trail are copied once; the members are queued consecutively, admitted in one
+    // wave, prefilled once and forked (k_kv_fork).  n = 1 is submit().  Thread-safe; throws candidates_refusal's reason or validate()'s before
+    // anything is queued
+    void submit_candidates(const GenRequest& g, bool want_pcm, const uint64_t* seeds, int n, int64_t* req_ids);
+    // sets of two or more candidates accepted, prompt rows whose prefill the forks replaced, KV pages k_kv_fork copied (per destination)
+    void candidate_stats(int64_t* sets, int64_t* rows_saved, int64_t* pages_copied) const {
+        *sets = cand_sets_.load(); *rows_saved = cand_rows_saved_.load(); *pages_copied = cand_pages_.load();
+    }
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -132,6 +141,10 @@ private:
     void ensure_score();
     void score_chunk(hipStream_t st, Transformer& talker, const std::vector<Req*>& batch, const std::vector<ScoreRun>& runs, int32_t* h_codes);
     void finish_scores(const std::vector<Req*>& scores);
+    // [EXT] candidate sets: the members of a wave that are prefilled (`lead`: everything but the later members of a set, in wave order) and per
+    // lead its set's other members; the forks of a wave, enqueued on `st` behind its last chunk (h_dst: pinned, d_dst: device, B ints each)
+    static void split_sets(const std::vector<Req*>& batch, std::vector<Req*>& lead, std::vector<std::vector<Req*>>& rest);
+    void fork_sets(hipStream_t st, const std::vector<Req*>& lead, const std::vector<std::vector<Req*>>& rest, int32_t* h_dst, int32_t* d_dst);
     static int kv_positions(const GenRequest& g, bool score) { return score ? g.n_prompt + g.n_prefix + 1 : g.n_prompt + g.max_steps + 1; }
     // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
     // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
@@ -202,6 +215,9 @@ private:
     DevBuf<int32_t> d_sc_seq_, d_sc_slot_, d_sc_pos_, d_sc_codes_; DevBuf<const float*> d_sc_tabs_; DevBuf<int64_t> d_sc_tab_rows_;
     DevBuf<float> d_sc_tlogits_, d_sc_hidden_, d_sc_hproj_, d_sc_in_, d_sc_plogits_, d_sc_out_;
     std::mutex sc_mu_; std::atomic<bool> sc_ready_{false};
+    // [EXT] candidate sets: the destination sequences of a wave's forks (in-line wave, asynchronous wave), the set ids (mu_), the counters
+    DevBuf<int32_t> d_fork_dst_, d_fork_dst_pf_; int64_t next_set_ = 1;
+    std::atomic<int64_t> cand_sets_{0}, cand_rows_saved_{0}, cand_pages_{0};
     std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = FrameVariant::key(width)
     bool instrument_ = false; bool pred_identity_pages_ = false;
     std::vector<std::vector<int32_t>> h_pend_; std::vector<int> h_pend_off_; // appended ids not yet on the device: ids [off, off+size)

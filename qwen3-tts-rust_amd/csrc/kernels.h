@@ -298,4 +298,9 @@ struct ScoreRowsArgs {
 };
 void launch_score_rows(hipStream_t st, const ScoreRowsArgs& a, int F);
 
+// [EXT] candidate sets (kvfork.hip, q3tts_spec.h "candidate sets"): logical pages [0, n_pages) of sequence src_seq are copied, whole and in
+// both planes, into the same logical pages of the n_dst sequences dst_seqs[] (device array).  Physical page ids come from kv.page_table on
+// the device (it must be set); every sequence involved must own those pages, and no two of the physical pages may coincide.
+void launch_kv_fork(hipStream_t st, const KvCache& kv, int src_seq, const int32_t* dst_seqs, int n_dst, int n_pages);
+
 } // namespace q3

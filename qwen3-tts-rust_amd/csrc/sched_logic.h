@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix and of a score request, and the chunk rows a score request needs the head for.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request and of a candidate set, what an admission wave takes from the queue, and the chunk rows a score request needs the head for.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -197,6 +197,42 @@ inline const char* score_refusal(const float* prompt, int n_prompt, int max_prom
     if ((int64_t)n_prompt + n > kv_rows) return "n_prompt + n exceeds the slot's KV capacity";
     // the code ranges: resume_refusal's, with its own limits out of the way (n + 1 steps, a closed trail, the capacity checked above)
     return resume_refusal(n_prompt, n + 1, codes, n, false, n_trail, (int64_t)n_prompt + n + 1);
+}
+
+// [EXT] candidate sets (q3tts_spec.h "candidate sets"): why a set of n seeded candidates of one prompt is refused, or null.  Pure, like the two
+// above; the prompt, max_steps and the options are checked by the rule every submission goes through.  A set takes no resumed prefix and no
+// open trail, so neither appears here.
+inline const char* candidates_refusal(int n, int max_batch, const uint64_t* seeds, const int64_t* req_ids, const int32_t* trail, int n_trail,
+                                      int max_prompt, bool ggml) {
+    if (ggml) return "candidate sets are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)";
+    if (n < 1) return "n must be >= 1: a set has at least one candidate";
+    if (n > max_batch) return "n exceeds max_batch: a set is admitted whole, one slot per candidate";
+    if (!seeds) return "seeds missing";
+    if (!req_ids) return "req_ids missing";
+    if (n_trail < 0 || n_trail > max_prompt) return "n_trail must be in [0, max_prompt]";
+    if (n_trail > 0 && !trail) return "trailing ids missing";
+    return nullptr;
+}
+
+// How many entries from the head of the queue the next admission wave takes.  A plain request (set = 0) needs a slot, a codec stream when it
+// wants PCM, and -- limit_rows: an asynchronous wave, whose prompts sit in one staging arena -- room for its rows below max_rows unless it
+// is the wave's first.  The members of a candidate set are the consecutive entries with its id (those cancelled in the queue have left it):
+// they are taken all or none, need a slot and a codec stream each, and their rows count once, since one member alone is prefilled.
+// Whatever does not fit ends the wave, so nothing overtakes it.  With no set in the queue this is the loop admit() always ran.
+struct QueueEntry { int rows; bool want_pcm; int64_t set; }; // rows: n_prompt + n_prefix
+inline int admission_take(const std::vector<QueueEntry>& q, int free_slots, int free_codec, bool limit_rows, size_t max_rows = 4096) {
+    size_t take = 0, rows = 0;
+    while (take < q.size() && free_slots > 0) {
+        const QueueEntry& e = q[take];
+        size_t k = 1;
+        if (e.set != 0) while (take + k < q.size() && q[take + k].set == e.set) k++;
+        if ((size_t)free_slots < k) break;
+        if (e.want_pcm && (size_t)free_codec < k) break; // every codec stream still drains: after the next harvest
+        if (limit_rows && take > 0 && rows + (size_t)e.rows > max_rows) break;
+        take += k; free_slots -= (int)k; rows += (size_t)e.rows;
+        if (e.want_pcm) free_codec -= (int)k;
+    }
+    return (int)take;
 }
 
 // The rows of one prefill chunk that a score request needs the talker head for.  Frame f of a request with n prompt rows is scored from row

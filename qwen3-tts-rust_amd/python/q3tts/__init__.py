@@ -95,6 +95,7 @@ SYMBOLS = [
     "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
     "q3tts_submit_score", "q3tts_group_submit_score", "q3tts_engine_score_width", "q3tts_op_score_rows", "q3tts_op_score_inputs",
     "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows",
+    "q3tts_submit_candidates", "q3tts_group_submit_candidates", "q3tts_engine_candidate_stats", "q3tts_op_kv_fork",
 ]
 
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
@@ -214,6 +215,11 @@ def lib():
         L.q3tts_submit_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
         L.q3tts_group_submit_score.argtypes = [C.c_void_p, C.c_int32] + L.q3tts_submit_score.argtypes[1:]
         L.q3tts_engine_score_width.argtypes = [C.c_void_p]
+        L.q3tts_submit_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.q3tts_group_submit_candidates.argtypes = [C.c_void_p, C.c_int32] + L.q3tts_submit_candidates.argtypes[1:]
+        L.q3tts_engine_candidate_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.q3tts_op_kv_fork.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_int32, C.c_int32]
         L.q3tts_engine_score_width.restype = C.c_int32
         L.q3tts_op_score_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_score_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
@@ -360,6 +366,44 @@ def op_score_inputs(hidden_proj, tabs, codes):
     out = np.zeros((16 * F, dP), np.float32)
     _chk(lib().q3tts_op_score_inputs(_p(hp), ptrs, _p(rows), dP, _p(c), F, _p(out)))
     return out
+
+
+def op_kv_fork(k_cache, v_cache, page_table, src_seq, dst_seqs, n_positions):
+    """[EXT] k_kv_fork over host buffers (q3tts_op_kv_fork): k_cache / v_cache uint16 [n_pages][n_layer][n_kv][8192], page_table int32
+    [n_seq][max_pages]; returns the two caches after the copy (the arguments are not changed)"""
+    k = np.array(k_cache, np.uint16, order="C")
+    v = np.array(v_cache, np.uint16, order="C")
+    pt = np.ascontiguousarray(page_table, np.int32)
+    ds = np.ascontiguousarray(dst_seqs, np.int32).reshape(-1)
+    if k.ndim != 4 or k.shape != v.shape or k.shape[3] != 8192 or pt.ndim != 2:
+        raise Q3Error("op_kv_fork: caches [n_pages][n_layer][n_kv][8192] of one shape, page_table [n_seq][max_pages]")
+    _chk(lib().q3tts_op_kv_fork(_p(k), _p(v), k.shape[0], k.shape[1], k.shape[2], _p(pt), pt.shape[0], pt.shape[1], src_seq,
+                                _p(ds) if ds.size else None, ds.size, n_positions))
+    return k, v
+
+
+def group_submit_candidates(group, engine_index, prompt, seeds, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, mask_eos=True, want_pcm=False,
+                            repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None):
+    """[EXT] q3tts_group_submit_candidates on a q3tts_group handle (engine_index -1 = round robin): the group request ids, all on one engine"""
+    return _submit_candidates(lib().q3tts_group_submit_candidates, (group, engine_index), prompt, seeds, max_steps, temperature, top_k, top_p,
+                              mask_eos, want_pcm, GenOptions(repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p), trailing_ids)
+
+
+def _submit_candidates(fn, head, prompt, seeds, max_steps, temperature, top_k, top_p, mask_eos, want_pcm, opts, trailing_ids):
+    pr = np.ascontiguousarray(prompt, np.float32)
+    sd = np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+    tr = np.ascontiguousarray(trailing_ids if trailing_ids is not None else [], np.int32)
+    r = Request()
+    r.prompt = pr.ctypes.data
+    r.n_prompt = pr.shape[0]
+    r.sampler.temperature, r.sampler.top_k, r.sampler.top_p = temperature, top_k, top_p
+    r.max_steps = max_steps
+    r.mask_eos = 1 if mask_eos else 0
+    o = None if all(getattr(opts, k) == v for k, v in GEN_DEFAULTS.items()) else opts
+    ids = np.zeros(max(sd.size, 1), np.int64)
+    _chk(fn(*head, C.byref(r), 1 if want_pcm else 0, C.byref(o) if o is not None else None, _p(tr) if tr.size else None, tr.size,
+            _p(sd) if sd.size else None, sd.size, _p(ids)))
+    return [int(i) for i in ids[: sd.size]]
 
 
 def group_submit_score(group, engine_index, prompt, codes, trailing_ids=None):
@@ -511,6 +555,19 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         _chk(lib().q3tts_submit_score(self.h, _p(pr), pr.shape[0], _p(tr) if tr.size else None, tr.size, _p(c) if c.size else None,
                                       c.shape[0], C.byref(rid)))
         return rid.value
+
+    def submit_candidates(self, prompt, seeds, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, mask_eos=True, want_pcm=False,
+                          repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None):
+        """[EXT] candidate sets (q3tts_submit_candidates): len(seeds) takes of one prompt behind one prefill; candidate i is exactly
+        submit(prompt, seed=seeds[i], ...) with the same arguments (a closed trail only).  Returns the request ids, in seed order"""
+        return _submit_candidates(lib().q3tts_submit_candidates, (self.h,), prompt, seeds, max_steps, temperature, top_k, top_p, mask_eos, want_pcm,
+                                  GenOptions(repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p), trailing_ids)
+
+    def candidate_stats(self):
+        """[EXT] q3tts_engine_candidate_stats: dict(sets, prefill_rows_saved, pages_copied)"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_candidate_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(sets=a.value, prefill_rows_saved=b.value, pages_copied=c.value)
 
     def score_width(self):
         """[EXT] frames per predictor scoring pass (q3tts_engine_score_width)"""
