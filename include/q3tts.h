@@ -224,6 +224,31 @@ int q3tts_submit_candidates(q3tts_engine* e, const q3tts_request* r, int32_t wan
 /* sets of n >= 2 accepted; prompt rows whose prefill a copy replaced ((members prefilled together - 1) * n_prompt per set); KV pages copied,
  * counted per destination.  Any pointer may be NULL */
 int q3tts_engine_candidate_stats(q3tts_engine* e, int64_t* sets, int64_t* prefill_rows_saved, int64_t* pages_copied);
+/* [EXT] decode given frames (q3tts_spec.h "decoding given frames"): the PCM of frames the caller already holds -- codes [n][16] as q3tts_fetch
+ * returns them, copied -- through the engine's own codec: no second copy of the codec weights, and the chunks share decode passes with those
+ * of the running requests.  For the winner of a codes-only candidate set, for utterances cached as codes, for a request that ran with
+ * want_pcm = 0, for frames another engine generated.  The PCM is that of a request that emitted exactly these frames and ended after frame
+ * n - 1: same sample count, within 1e-4 RMS (the stream is reset, the frames are clamped and cut into 4-frame chunks and the n % 4 left are
+ * flushed, as for a generating request).  The request takes no talker slot and no KV pages, is never prefilled and never part of the frame
+ * graph; it holds one codec stream and its PCM staging region from admission to its fence.  It waits in a queue of its own -- requests
+ * waiting for a slot do not hold it up -- and is admitted, after the step's generating wave has taken its streams, while a stream is free
+ * and fewer than q3tts_engine_decode_width such requests hold one.  Its chunks reach the decoder thread together with the chunks of that
+ * step's frame group (at once on an engine that steps nothing) and take the seats the running requests' chunks leave in a decode
+ * pass, and lead every fifth pass when they would otherwise wait.  No other request's codes change; its PCM stays within the same tolerance.
+ * Q3TTS_REQ_QUEUED until it holds a stream, then Q3TTS_REQ_DRAINING, Q3TTS_REQ_DONE behind its fence.  q3tts_poll reports n_frames = n from
+ * submission on, prefill_ms = 0, and n_pcm growing chunk by chunk; q3tts_fetch returns the given codes at once and the PCM decoded so far;
+ * q3tts_wait / q3tts_release as for any request.  q3tts_cancel: a queued request is CANCELLED at once with no PCM; one that holds a stream
+ * keeps the PCM of the chunks already enqueued and turns CANCELLED behind its fence, as a draining request does.  q3tts_fetch_logprobs,
+ * q3tts_trail_append and q3tts_trail_progress return < 0 (nothing is recorded, there is no trail).  Works under Q3_SPEC=ggml: nothing of the
+ * talker runs.  Thread-safe, and free of HIP calls in the caller's thread.
+ * Refused (< 0, q3tts_last_error says why, nothing is queued, *req_id untouched): e, codes or req_id NULL; n < 1; n > the engine's max_steps
+ * (a stream's staging region holds max_steps frames); an engine created with load_codec = 0; a code_0 outside [0, Q3_SAMPLE_END) or equal
+ * to Q3_CODEC_EOS; a residual code outside [0, 2048) */
+int q3tts_submit_decode(q3tts_engine* e, const int32_t* codes, int32_t n, int64_t* req_id);
+int32_t q3tts_engine_decode_width(q3tts_engine* e);  /* decode-only requests that may hold a codec stream at once: max(1, (streams - max_batch) / 2); 0 without a codec */
+/* decode-only requests accepted; their chunks decoded; of those, chunks that shared a pass with at least one chunk of a generating request.
+ * Any pointer may be NULL */
+int q3tts_engine_decode_stats(q3tts_engine* e, int64_t* requests, int64_t* chunks, int64_t* chunks_shared);
 /* rows of one talker prefill launch: a longer admission wave (prompts + resumed prefixes) is prefilled in chunks of this many rows
  * (an asynchronous wave, admitted beside running requests, in chunks of at most 256) */
 int32_t q3tts_engine_prefill_width(q3tts_engine* e);
@@ -310,6 +335,9 @@ int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_
 int q3tts_group_submit_score(q3tts_group* g, int32_t engine_index, const float* prompt, int32_t n_prompt, const int32_t* trail_ids,
                              int32_t n_trail, const int32_t* codes, int32_t n, int64_t* req_id);
 /* [EXT] q3tts_submit_candidates on engine engine_index (-1 = round robin): the whole set goes to ONE engine, every id carries its index */
+/* [EXT] q3tts_submit_decode on engine engine_index (-1 = round robin); the id carries the engine, so q3tts_group_poll / _fetch / _wait / _cancel /
+ * _release serve it */
+int q3tts_group_submit_decode(q3tts_group* g, int32_t engine_index, const int32_t* codes, int32_t n, int64_t* req_id);
 int q3tts_group_submit_candidates(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                                   const int32_t* trail_ids, int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids);
 int q3tts_group_set_logprobs(q3tts_group* g, int32_t on);      /* [EXT] q3tts_engine_set_logprobs on every engine */

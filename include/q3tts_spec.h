@@ -369,6 +369,31 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  * asynchronous wave.  A member cancelled in the queue leaves the set; the first member left is the one prefilled.
  * Refused: n < 1 or n > max_batch; a resumed prefix or an open trail (not expressible); the ggml-arithmetic mode. */
 
+/* ---------------- decoding given frames [EXT] (q3tts_submit_decode, q3tts_group_submit_decode) ----------------
+ * Let c[0..n) be frames [16] as q3tts_fetch returns them.
+ *   D1  PCM        decode(c) delivers the PCM of a request that emitted exactly c and ended after frame n - 1: the same sample count, within the
+ *                  standing PCM tolerance of 1e-4 RMS.  By construction: the codec stream is reset (AudioDecoder::create_state), and the frames
+ *                  go through a Chunker as a generating request's do -- every code clamped to [0, 2047], chunks of Q3_CHUNK_CODES codes
+ *                  (4 frames), then the is_final flush of the n % 4 frames left
+ *   D2  others     the codes of every other request are bit-identical to those without the decode-only request (it touches nothing of the
+ *                  talker or predictor); their PCM has the same count and stays within the same tolerance (a chunk's result does not depend
+ *                  on which other streams share its pass beyond that)
+ *   D3  resources  no talker slot, no KV pages, no prefill wave, no frame graph: on an otherwise idle engine q3tts_stats.graph_frames, frames,
+ *                  sched_steps and prefill_ms stay where they were.  One codec stream and its PCM staging region, from admission to the fence
+ * Admission: decode-only requests wait in a FIFO of their own.  In a scheduler step the generating wave takes its codec streams first; then
+ * decode-only requests are admitted in order while a stream is free and fewer than decode_width = max(1, (n_cs - max_batch) / 2) of them
+ * hold one (n_cs: the engine's codec streams; the surplus n_cs - max_batch serves requests whose slot is reused while they drain).
+ * Seats: the decoder thread keeps the tasks of decode-only requests in a second queue.  A pass is led by the oldest pending chunk of a
+ * generating request, seats the first pending chunks of the other generating requests with the lead's frame count, then those of decode-only
+ * requests, one chunk per request, at most gmax; with no generating chunk the oldest decode-only chunk leads.  After 4 consecutive passes
+ * that seated no decode-only chunk while one waited, the oldest decode-only chunk leads the next pass.  A decode-only request's reset and
+ * fence run alone as soon as they head its tasks.  With no decode-only request the passes are those formed without this feature.
+ * Hand-over: a request's tasks (reset, chunks, fence) reach the decoder thread in the scheduler step that admitted it -- at once when that step
+ * runs no frame group, else together with the chunks the step's frame group produced, so that the two kinds meet in the queues.
+ * States: Q3TTS_REQ_QUEUED until a stream is taken, Q3TTS_REQ_DRAINING until the fence, Q3TTS_REQ_DONE; n_frames = n from submission on.
+ * Refused: n < 1 or n > max_steps; no codec; a code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS; a residual code outside [0, 2048)
+ * (no request emits such a frame). */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -146,6 +146,25 @@ int q3tts_submit_score(q3tts_engine* e, const float* prompt, int32_t n_prompt, c
     Q3_API_END(Q3TTS_ERR)
 }
 int32_t q3tts_engine_score_width(q3tts_engine* e) { return e ? e->e->score_width() : -1; }
+int q3tts_submit_decode(q3tts_engine* e, const int32_t* codes, int32_t n, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && codes && req_id, "null argument");
+    *req_id = e->e->submit_decode(codes, n);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int32_t q3tts_engine_decode_width(q3tts_engine* e) { return e ? e->e->decode_width() : -1; }
+int q3tts_engine_decode_stats(q3tts_engine* e, int64_t* requests, int64_t* chunks, int64_t* chunks_shared) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int64_t r = 0, c = 0, s = 0;
+    e->e->decode_stats(&r, &c, &s);
+    if (requests) *requests = r;
+    if (chunks) *chunks = c;
+    if (chunks_shared) *chunks_shared = s;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_submit_candidates(q3tts_engine* e, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, const int32_t* trail_ids,
                             int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids) {
     Q3_API_BEGIN

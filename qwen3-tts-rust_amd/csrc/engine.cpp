@@ -163,6 +163,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         slot_cap_ = (size_t)p.max_steps * codec_->samples_per_frame();
         Q3_HIP(hipHostMalloc((void**)&pcm_pinned_, (size_t)n_cs * slot_cap_ * sizeof(float)));
         for (int c = n_cs - 1; c >= 0; c--) cs_free_.push_back(c);
+        decode_w_ = q3::decode_width(n_cs, B); // [EXT] decoding given frames: half of the surplus streams
     }
     Q3_HIP(hipStreamSynchronize(st_));
     Q3_HIP(hipDeviceSynchronize());
@@ -200,6 +201,7 @@ struct Engine::Req {
     bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
+    bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
@@ -508,29 +510,39 @@ void Engine::decoder_main() {
         Q3_HIP(hipSetDevice(dev_)); // HIP's current device is per thread
         const int spf = codec_->samples_per_frame(), gmax = codec_->max_group(), n_lanes = (int)st2_.size();
         std::map<Req*, std::pair<int, hipEvent_t>> last;            // request -> (lane, event after its latest chunk)
-        int next_lane = 0;
+        int next_lane = 0, dry = 0;                                 // dry: seat_chunks' count of passes that left a decode-only chunk waiting
         for (;;) {
             // take the oldest task; if it is a chunk, add the first pending chunk of other requests with the same frame count:
-            // one decode pass then serves the whole group (weights streamed once, one set of launches)
+            // one decode pass then serves the whole group (weights streamed once, one set of launches).  [EXT] The chunks of decode-only
+            // requests wait in a queue of their own and take the seats that are left; the rule is seat_chunks (sched_logic.h)
             std::vector<DecTask> grp;
             {
                 std::unique_lock<std::mutex> lk(dmu_);
-                dcv_.wait(lk, [&] { return dec_stop_ || !dq_.empty(); });
-                if (dq_.empty()) return;
-                grp.push_back(std::move(dq_.front()));
-                dq_.pop_front();
-                if (!grp[0].fence && !grp[0].reset && gmax > 1) {
-                    const size_t nc = grp[0].codes.size();
-                    std::vector<Req*> seen{grp[0].r};
-                    for (auto it = dq_.begin(); it != dq_.end() && (int)grp.size() < gmax;) {
-                        const bool dup = std::find(seen.begin(), seen.end(), it->r) != seen.end();
-                        if (!dup) seen.push_back(it->r);
-                        if (!dup && !it->fence && !it->reset && it->codes.size() == nc) { grp.push_back(std::move(*it)); it = dq_.erase(it); }
-                        else ++it;
-                    }
+                dcv_.wait(lk, [&] { return dec_stop_ || (!dec_hold_ && (!dq_.empty() || !dq_lo_.empty())); });
+                if (dq_.empty() && dq_lo_.empty()) return;
+                auto heads = [](const std::deque<DecTask>& q) {
+                    std::vector<TaskHead> h;
+                    for (const DecTask& t : q) h.push_back({t.r->id, (int)t.codes.size() / 16, t.reset ? TASK_RESET : t.fence ? TASK_FENCE : TASK_CHUNK});
+                    return h;
+                };
+                const Seating s = seat_chunks(heads(dq_), heads(dq_lo_), gmax, dry);
+                dry = s.dry;
+                for (const Seat& c : s.seats) grp.push_back(std::move((c.low ? dq_lo_ : dq_)[c.index]));
+                for (int low = 0; low < 2; low++) { // the seated tasks leave their queue, last first
+                    std::deque<DecTask>& q = low ? dq_lo_ : dq_;
+                    std::vector<int> idx;
+                    for (const Seat& c : s.seats) if ((int)c.low == low) idx.push_back(c.index);
+                    std::sort(idx.rbegin(), idx.rend());
+                    for (int i : idx) q.erase(q.begin() + i);
                 }
             }
             const int G = (int)grp.size();
+            if (!grp[0].fence && !grp[0].reset) {
+                int n_low = 0;
+                for (const DecTask& t : grp) n_low += t.r->decode;
+                dec_chunks_ += n_low;
+                if (n_low < G) dec_shared_ += n_low;
+            }
             int lane = next_lane;
             { auto it = last.find(grp[0].r); if (G == 1 && it != last.end()) lane = it->second.first; else next_lane = (next_lane + 1) % n_lanes; }
             for (auto& t : grp) { // a request's chunks must run in order even when consecutive groups use different lanes
@@ -615,6 +627,7 @@ void Engine::harvest(bool block) {
             r->cs = -1;
             r->state = fenced_state(r->cancel); r->t_done = now_ms();
             n_draining_--;
+            if (r->decode) n_decoding_--;
             cv_.notify_all();
         }
         block = false; // after one blocking wait, drain whatever else is ready
@@ -784,6 +797,7 @@ void Engine::trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* 
     auto it = reqs_.find(id);
     Q3_CHECK(it != reqs_.end(), "unknown request id");
     const Req& r = *it->second;
+    Q3_CHECK(!r.decode, "a decode-only request has no trail");
     const int n = (int)r.trail_ids().size();
     *n_appended = n; *n_consumed = std::min(r.fed, n); *closed = !r.r.open || r.closed;
 }
@@ -820,7 +834,8 @@ int Engine::cancel(int64_t id) {
     if (r.cancel) return 0; // the first cancel is still pending
     r.cancel = true;
     if (cancel_action(r.state, false, false, r.want_pcm) == CANCEL_AT_ONCE) {
-        pending_.erase(std::find(pending_.begin(), pending_.end(), &r));
+        std::deque<Req*>& q = r.decode ? decode_q_ : pending_;
+        q.erase(std::find(q.begin(), q.end(), &r));
         r.state = REQ_CANCELLED; r.t_done = now_ms();
     } else cancel_ids_.push_back(id);
     wake_++;
@@ -830,8 +845,9 @@ int Engine::cancel(int64_t id) {
 
 // drops the chunk tasks of r the decoder thread has not taken yet (dmu_ held); what it has taken runs to its end
 void Engine::purge_chunks(Req* r) {
-    for (auto it = dq_.begin(); it != dq_.end();) {
-        if (it->r == r && !it->fence && !it->reset) { it = dq_.erase(it); dec_pending_--; }
+    std::deque<DecTask>& q = r->decode ? dq_lo_ : dq_;
+    for (auto it = q.begin(); it != q.end();) {
+        if (it->r == r && !it->fence && !it->reset) { it = q.erase(it); dec_pending_--; }
         else ++it;
     }
 }
@@ -931,6 +947,65 @@ void Engine::admit(bool stalled) {
     std::vector<Req*> scores; // [EXT] scoring: their rows are computed; they were never live
     for (Req* r : batch) if (r->score) scores.push_back(r);
     finish_scores(scores);
+}
+
+// [EXT] decoding given frames.  The request is the codec half of a request alone: a copy of the caller's frames that waits for a codec stream.
+int64_t Engine::submit_decode(const int32_t* codes, int n) {
+    if (const char* why = decode_refusal(codes, n, p_.max_steps, codec_ != nullptr)) throw Error(why);
+    std::unique_ptr<Req> r(new Req());
+    r->decode = true; r->want_pcm = true;
+    r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
+    r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
+    r->t_submit = now_ms();
+    std::lock_guard<std::mutex> lk(mu_);
+    r->id = next_id_++;
+    Req* raw = r.get();
+    reqs_[raw->id] = std::move(r);
+    decode_q_.push_back(raw);
+    dec_reqs_++;
+    wake_++;
+    cv_.notify_all();
+    return raw->id;
+}
+
+// scheduler thread, after admit(): the generating wave has taken its streams; decode-only requests take free ones in order, up to decode_w_
+// holders.
+void Engine::admit_decodes() {
+    std::lock_guard<std::mutex> lk(mu_);
+    for (int take = decode_admit((int)decode_q_.size(), (int)cs_free_.size(), n_decoding_, decode_w_); take > 0; take--) {
+        Req* r = decode_q_.front();
+        decode_q_.pop_front();
+        r->cs = cs_free_.back(); cs_free_.pop_back();
+        r->state = REQ_DRAINING; r->t_admit = now_ms();
+        n_draining_++; n_decoding_++;
+        dec_admitted_.push_back(r);
+    }
+}
+
+// A request's whole task list -- reset, the chunks a Chunker cuts from its frames, fence -- goes to the low queue in one piece.
+void Engine::enqueue_decodes() {
+    std::vector<Req*> batch;
+    batch.swap(dec_admitted_);
+    for (Req* r : batch) {
+        Q3_HIP(hipEventCreate(&r->ev_admit));
+        Q3_HIP(hipEventRecord(r->ev_admit, st_)); // the AR stream is idle here: marks "admitted"
+        std::vector<DecTask> tasks;
+        tasks.push_back(DecTask{r, {}, false, false, true});
+        Chunker cut([&](const int64_t* codes, int n_codes, bool is_final) { tasks.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false}); });
+        for (int f = 0; f < r->fed; f++) {
+            int64_t fc[16];
+            for (int q = 0; q < 16; q++) fc[q] = r->codes[(size_t)f * 16 + q];
+            cut.push(fc, 16, false);
+        }
+        cut.push(nullptr, 0, true);
+        tasks.push_back(DecTask{r, {}, false, true, false});
+        {
+            std::lock_guard<std::mutex> lk(dmu_);
+            dec_pending_ += (int)tasks.size() - 1; // the chunks and the fence
+            for (DecTask& t : tasks) dq_lo_.push_back(std::move(t));
+        }
+        dcv_.notify_all();
+    }
 }
 
 // Prefill of one admission wave on the second talker instance / stream: every chunk is enqueued without host waits (the prompts of
@@ -1286,6 +1361,13 @@ void Engine::run_group() {
         stats.gu_ms += timer_gu_.collect_ms(); stats.gu_bytes += timer_gu_.bytes; stats.gu_launches += timer_gu_.launches; timer_gu_.bytes = 0; timer_gu_.launches = 0;
     }
     std::memcpy(h_nfr, p_nfr, (size_t)width * 4); std::memcpy(h_fin, p_fin, (size_t)width * 4);
+    // [EXT] decode-only requests admitted in this step: their tasks reach the decoder thread together with this group's chunks.  The thread
+    // forms no pass while both are handed over (microseconds); with nothing admitted, nothing is held
+    struct Hold {
+        Engine* e; bool on;
+        Hold(Engine* e_, bool on_) : e(e_), on(on_) { if (on) { std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = true; } }
+        ~Hold() { if (on) { { std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = false; } e->dcv_.notify_all(); } }
+    } hold(this, !dec_admitted_.empty());
     for (int b = 0; b < width; b++) {
         if (!slots_.live[b]) continue;
         Req* r = slot_req_[b];
@@ -1307,6 +1389,7 @@ void Engine::run_group() {
         }
         if (h_fin[b] || h_nfr[b] >= r->r.max_steps) retire(r, true);
     }
+    enqueue_decodes();
 }
 
 static double g_t_harvest = 0, g_t_admit = 0, g_t_group = 0, g_t_idle = 0;
@@ -1325,6 +1408,8 @@ bool Engine::step() {
     collect_appends();
     collect_cancels(); // before admit: a slot a cancel frees can be refilled in this step
     admit(n_active_ > 0 && slots_.all_live_stalled());
+    if (codec_) admit_decodes();
+    if (!(n_active_ > 0 && !slots_.all_live_stalled())) enqueue_decodes(); // no frame group in this step: nothing to meet, the tasks go at once
     const double t2 = now_ms();
     // [EXT] live text append: when every live slot waits for text, no frame group runs (graph_frames stays put); prefill and codec
     // work still proceed, and with none left the driver sleeps until a submit or an append
@@ -1342,7 +1427,7 @@ bool Engine::step() {
     }
     std::lock_guard<std::mutex> lk(mu_);
     stalled_idle_ = stalled && n_prefilling_ == 0 && dec_pending == 0;
-    return n_active_ > 0 || n_prefilling_ > 0 || n_draining_ > 0 || !pending_.empty();
+    return n_active_ > 0 || n_prefilling_ > 0 || n_draining_ > 0 || !pending_.empty() || !decode_q_.empty();
 }
 
 ReqStatus Engine::poll(int64_t id) {
@@ -1435,7 +1520,7 @@ void Engine::start_driver() {
                 const bool busy = step();
                 std::unique_lock<std::mutex> lk(mu_);
                 if (driver_stop_) return;
-                if (!busy) cv_.wait_for(lk, std::chrono::milliseconds(1), [this] { return driver_stop_ || !pending_.empty(); });
+                if (!busy) cv_.wait_for(lk, std::chrono::milliseconds(1), [this] { return driver_stop_ || !pending_.empty() || !decode_q_.empty(); });
                 else if (stalled_idle_) cv_.wait(lk, [&] { return driver_stop_ || wake_ != seen; }); // every live slot waits for text
             }
         } catch (const std::exception& ex) {

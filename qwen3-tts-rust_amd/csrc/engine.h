@@ -95,6 +95,16 @@ public:
     void candidate_stats(int64_t* sets, int64_t* rows_saved, int64_t* pages_copied) const {
         *sets = cand_sets_.load(); *rows_saved = cand_rows_saved_.load(); *pages_copied = cand_pages_.load();
     }
+    // [EXT] decoding given frames (q3tts_spec.h "decoding given frames"): the PCM of codes [n][16], through the engine's codec.  The request
+    // waits in a queue of its own, takes a codec stream (at most decode_width() such requests hold one) and nothing of the talker: no slot, no
+    // KV pages, no prefill, no frame.  QUEUED until it holds a stream, then DRAINING, DONE behind its fence; its frames are the given codes
+    // from submission on.  Thread-safe and free of HIP calls; throws decode_refusal's reason before anything is queued
+    int64_t submit_decode(const int32_t* codes, int n);
+    int decode_width() const { return decode_w_; }
+    // decode-only requests accepted, their chunks decoded, and of those the chunks that shared a pass with a generating request's chunk
+    void decode_stats(int64_t* requests, int64_t* chunks, int64_t* chunks_shared) const {
+        *requests = dec_reqs_.load(); *chunks = dec_chunks_.load(); *chunks_shared = dec_shared_.load();
+    }
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -151,6 +161,10 @@ private:
     // join the batch ("activate") between two frame groups once the prefill event has completed.
     void prefill_async(const std::vector<Req*>& batch);
     void activate();
+    void admit_decodes();     // [EXT] decode-only requests take free codec streams, after admit()
+    // their reset, chunks and fence go to the low queue: at once when the step runs no frame group, else together with the chunks the group
+    // produced (run_group), so that both kinds meet in the decoder thread's queues and share passes
+    void enqueue_decodes();
     void admit(bool stalled); // stalled: every live slot waits for text (the admission quantum is not waited for)
     void run_group();
     void collect_appends();   // scheduler: new ids / close flags of live open slots into the slot table (upload in run_group)
@@ -230,6 +244,11 @@ private:
     std::vector<int> cs_free_;          // free codec streams
     int64_t next_id_ = 1;
     int n_active_ = 0, n_draining_ = 0;
+    // [EXT] decoding given frames: the queue decode-only requests wait in for a codec stream, how many hold one (they count in n_draining_
+    // too), the limit, and the counters
+    std::deque<Req*> decode_q_; int n_decoding_ = 0, decode_w_ = 0;
+    std::vector<Req*> dec_admitted_;    // admitted in this step, tasks not yet enqueued (scheduler thread only)
+    std::atomic<int64_t> dec_reqs_{0}, dec_chunks_{0}, dec_shared_{0};
     bool trail_dirty_ = false;          // an append arrived since the scheduler last looked (mu_)
     std::vector<int64_t> cancel_ids_;   // cancelled requests the scheduler has not dealt with yet (mu_)
     uint64_t wake_ = 0;                 // bumped by every submit / append / cancel: a driver idling on stalled slots sleeps until it changes (mu_)
@@ -241,7 +260,8 @@ private:
     struct Completion { Req* r; hipEvent_t ev; size_t pcm_after; bool fence; };
     std::thread dec_thread_; bool dec_started_ = false, dec_stop_ = false;
     std::mutex dmu_; std::condition_variable dcv_;
-    std::deque<DecTask> dq_; std::deque<Completion> comp_;
+    std::deque<DecTask> dq_, dq_lo_; std::deque<Completion> comp_; // dq_lo_: [EXT] the tasks of decode-only requests (seat_chunks)
+    bool dec_hold_ = false;             // [EXT] the scheduler is handing over a frame group's chunks and decode-only tasks: no pass is formed meanwhile (dmu_)
     int dec_pending_ = 0;               // chunk / fence tasks whose completion has not been harvested yet (dmu_)
     std::string derr_;
     LaunchTimer timer_, timer_gu_;

@@ -386,6 +386,17 @@ int q3tts_group_submit_score(q3tts_group* g, int32_t engine_index, const float* 
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+int q3tts_group_submit_decode(q3tts_group* g, int32_t engine_index, const int32_t* codes, int32_t n, int64_t* req_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && codes && req_id, "null argument");
+    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
+    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
+    int64_t id = 0;
+    if (q3tts_submit_decode(g->eng[i], codes, n, &id) != Q3TTS_OK) return Q3TTS_ERR;
+    *req_id = (id << kEngineBits) | i;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_group_submit_candidates(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                                   const int32_t* trail_ids, int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids) {
     Q3_API_BEGIN

@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request and of a candidate set, what an admission wave takes from the queue, and the chunk rows a score request needs the head for.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set and of a decode-only request, what an admission wave takes from the queue, the chunk rows a score request needs the head for, and how the decoder thread seats chunks in a codec pass.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -212,6 +212,66 @@ inline const char* candidates_refusal(int n, int max_batch, const uint64_t* seed
     if (n_trail < 0 || n_trail > max_prompt) return "n_trail must be in [0, max_prompt]";
     if (n_trail > 0 && !trail) return "trailing ids missing";
     return nullptr;
+}
+
+// [EXT] decoding given frames (q3tts_spec.h "decoding given frames"): why a decode-only request is refused, or null.  Pure, like the three above.
+// The code ranges are resume_refusal's: no request emits a frame outside them, so there is no PCM "of a request that emitted it" to deliver.
+inline const char* decode_refusal(const int32_t* codes, int n, int max_steps, bool have_codec) {
+    if (!have_codec) return "the engine was created with load_codec = 0: there is no codec to decode with";
+    if (n < 1) return "n must be >= 1: there is no frame to decode";
+    if (n > max_steps) return "n exceeds the engine's max_steps (a codec stream's staging region holds max_steps frames)";
+    if (!codes) return "codes missing";
+    return resume_refusal(1, n + 1, codes, n, false, 0, (int64_t)n + 2); // the ranges alone: its own limits are out of the way
+}
+// Decode-only requests that may hold a codec stream at once: half of the streams the engine keeps beyond one per slot (those serve
+// requests whose slot is already reused while their last chunks drain), and how many of the queued ones a scheduler step admits after
+// the generating wave has taken its streams.
+inline int decode_width(int n_cs, int max_batch) { return std::max(1, (n_cs - max_batch) / 2); }
+inline int decode_admit(int queued, int free_cs, int holding, int width) { return std::max(0, std::min(queued, std::min(free_cs, width - holding))); }
+
+// The decoder thread's next step.  It has two queues: `live` (tasks of generating requests) and `low` (tasks of decode-only requests), each in
+// arrival order; a request's tasks are reset, chunks, fence, in that order, and all sit in one queue.  A step is one task alone (a reset or a
+// fence) or one codec pass: chunks of equal frame count, one per request, at most gmax.  Only a request's first pending task can be chosen.
+//   control  a reset or fence that heads a decode-only request's tasks runs at once, alone (no codec work; it keeps a stream's turnover short)
+//   lead     the head of the live queue -- a reset or fence runs alone, a chunk leads the pass; with the live queue empty, the oldest
+//            decode-only chunk leads
+//   seats    the first pending chunks of the other generating requests with the lead's frame count, in queue order, then those of
+//            decode-only requests, in queue order
+//   turn     after SEAT_DRY_MAX consecutive passes that seated no decode-only chunk while one was waiting, the oldest decode-only chunk
+//            leads the next pass; generating chunks of its frame count still take the other seats first
+// With the low queue empty this is the grouping the thread always did.  dry = the count of such passes so far; the result carries the next.
+enum TaskKind { TASK_CHUNK = 0, TASK_RESET = 1, TASK_FENCE = 2 };
+enum { SEAT_DRY_MAX = 4 };
+struct TaskHead { int64_t req; int frames; int kind; }; // frames: of a chunk, else 0
+struct Seat { bool low; int index; };                   // index into its queue
+struct Seating { std::vector<Seat> seats; int dry = 0; };
+inline Seating seat_chunks(const std::vector<TaskHead>& live, const std::vector<TaskHead>& low, int gmax, int dry) {
+    Seating out;
+    out.dry = dry;
+    // the first pending task of every decode-only request, in queue order
+    std::vector<int> heads; std::vector<int64_t> seen;
+    for (int i = 0; i < (int)low.size(); i++)
+        if (std::find(seen.begin(), seen.end(), low[i].req) == seen.end()) { seen.push_back(low[i].req); heads.push_back(i); }
+    for (int i : heads) if (low[i].kind != TASK_CHUNK) { out.seats.push_back({true, i}); return out; }
+    if (live.empty() && heads.empty()) return out;
+    const bool turn = !heads.empty() && (live.empty() || dry >= SEAT_DRY_MAX);
+    if (!turn && live[0].kind != TASK_CHUNK) { out.seats.push_back({false, 0}); return out; }
+    const TaskHead& lead = turn ? low[heads[0]] : live[0];
+    out.seats.push_back({turn, turn ? heads[0] : 0});
+    seen.assign(1, lead.req); // request ids are the engine's: no two requests share one, whichever queue they wait in
+    for (int i = 0; i < (int)live.size() && (int)out.seats.size() < gmax; i++) {
+        const bool dup = std::find(seen.begin(), seen.end(), live[i].req) != seen.end();
+        if (!dup) seen.push_back(live[i].req);
+        if (!dup && live[i].kind == TASK_CHUNK && live[i].frames == lead.frames) out.seats.push_back({false, i});
+    }
+    bool seated_low = turn;
+    for (int i : heads) {
+        if ((int)out.seats.size() >= gmax) break;
+        if (turn && i == heads[0]) continue;
+        if (low[i].frames == lead.frames) { out.seats.push_back({true, i}); seated_low = true; }
+    }
+    out.dry = seated_low ? 0 : heads.empty() ? 0 : dry + 1;
+    return out;
 }
 
 // How many entries from the head of the queue the next admission wave takes.  A plain request (set = 0) needs a slot, a codec stream when it

@@ -402,6 +402,29 @@ AudioSample TtsEngine::generate_with_voice_ids_stream(const std::vector<int32_t>
     return out;
 }
 
+AudioSample TtsEngine::vocode(const std::vector<int32_t>& codes) {
+    if (codes.size() % 16 != 0) throw std::runtime_error("codes must hold whole frames of 16");
+    int64_t id = 0;
+    if (q3tts_submit_decode(e_, codes.data(), (int32_t)(codes.size() / 16), &id) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
+    const int rc = q3tts_wait(e_, id, -1.0);
+    q3tts_req_status st{};
+    if (rc < 0 || q3tts_poll(e_, id, &st) != Q3TTS_OK || st.state != Q3TTS_REQ_DONE) {
+        const std::string why = q3tts_last_error();
+        q3tts_release(e_, id);
+        throw std::runtime_error(why.empty() ? "decoding failed" : why);
+    }
+    AudioSample out;
+    out.samples.assign((size_t)st.n_pcm, 0.0f);
+    int64_t got = 0;
+    if (st.n_pcm > 0 && q3tts_fetch(e_, id, nullptr, 0, 0, out.samples.data(), 0, st.n_pcm, nullptr, &got) != Q3TTS_OK) {
+        q3tts_release(e_, id);
+        throw std::runtime_error(q3tts_last_error());
+    }
+    out.samples.resize((size_t)got);
+    q3tts_release(e_, id);
+    return out; // AudioSample{samples, 24000, 1}
+}
+
 std::vector<int64_t> TtsEngine::encode_audio(const std::vector<float>& audio) const { // onnx.rs:97-121
     if (!enc_) throw std::runtime_error("AudioEncoder not loaded. Please ensure models/onnx/qwen3_tts_codec_encoder.onnx exists.");
     const int64_t shape[2] = {1, (int64_t)audio.size()};

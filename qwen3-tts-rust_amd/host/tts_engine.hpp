@@ -77,6 +77,9 @@ public:
     AudioSample generate_with_voice_ids_stream(const std::vector<int32_t>& text_ids, const VoiceFile& voice, const ChunkFn& on_chunk,
                                                const std::vector<int32_t>* instruct_ids = nullptr, const std::vector<int32_t>* ref_text_ids = nullptr,
                                                std::vector<int32_t>* codes_out = nullptr);
+    // [EXT] decoding given frames (q3tts_submit_decode): the audio of codes [n][16] the caller holds -- a cached utterance, the winner of a
+    // codes-only candidate set -- on the engine's own codec.  Throws with the engine's reason when the frames are refused.
+    AudioSample vocode(const std::vector<int32_t>& codes);
     // create_voice_file -- :324-387.  The two encoders are ONNX graphs run by the engine's own graph executor (q3tts_onnx_session_*, rows a17 /
     // f-2): <model_dir>/onnx/qwen3_tts_codec_encoder.onnx ("input_values" [1, T] -> "audio_codes") and qwen3_tts_speaker_encoder.onnx ("mels"
     // [1, n, 128] from q3tts_mel -> "spk_emb"), loaded when the files exist (engine.rs:106-127); without them the reference's errors are returned.

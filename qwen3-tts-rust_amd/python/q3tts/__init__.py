@@ -96,6 +96,7 @@ SYMBOLS = [
     "q3tts_submit_score", "q3tts_group_submit_score", "q3tts_engine_score_width", "q3tts_op_score_rows", "q3tts_op_score_inputs",
     "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows",
     "q3tts_submit_candidates", "q3tts_group_submit_candidates", "q3tts_engine_candidate_stats", "q3tts_op_kv_fork",
+    "q3tts_submit_decode", "q3tts_group_submit_decode", "q3tts_engine_decode_width", "q3tts_engine_decode_stats",
 ]
 
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
@@ -221,6 +222,11 @@ def lib():
         L.q3tts_op_kv_fork.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_int32, C.c_int32]
         L.q3tts_engine_score_width.restype = C.c_int32
+        L.q3tts_submit_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+        L.q3tts_group_submit_decode.argtypes = [C.c_void_p, C.c_int32] + L.q3tts_submit_decode.argtypes[1:]
+        L.q3tts_engine_decode_width.argtypes = [C.c_void_p]
+        L.q3tts_engine_decode_width.restype = C.c_int32
+        L.q3tts_engine_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.q3tts_op_score_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_score_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_logprob_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -417,6 +423,14 @@ def group_submit_score(group, engine_index, prompt, codes, trailing_ids=None):
     return rid.value
 
 
+def group_submit_decode(group, engine_index, codes):
+    """[EXT] q3tts_group_submit_decode on a q3tts_group handle (engine_index -1 = round robin): the group request id"""
+    c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+    rid = C.c_int64()
+    _chk(lib().q3tts_group_submit_decode(group, engine_index, _p(c) if c.size else None, c.shape[0], C.byref(rid)))
+    return rid.value
+
+
 def _fetch_logprobs(fn, h, rid, frame_off, max_frames):
     out = np.zeros((max(max_frames, 1), LOGPROB_COLS), np.float32)
     gf = C.c_int32()
@@ -562,6 +576,24 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         submit(prompt, seed=seeds[i], ...) with the same arguments (a closed trail only).  Returns the request ids, in seed order"""
         return _submit_candidates(lib().q3tts_submit_candidates, (self.h,), prompt, seeds, max_steps, temperature, top_k, top_p, mask_eos, want_pcm,
                                   GenOptions(repetition_penalty, predictor_temperature, predictor_top_k, predictor_top_p), trailing_ids)
+
+    def submit_decode(self, codes):
+        """[EXT] decoding given frames (q3tts_submit_decode): queues the decoding of codes [n][16] to PCM on the engine's codec.  The request
+        takes no talker slot; poll / fetch / wait / cancel / result(rid, want_pcm=True) serve it like any other"""
+        c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+        rid = C.c_int64()
+        _chk(lib().q3tts_submit_decode(self.h, _p(c) if c.size else None, c.shape[0], C.byref(rid)))
+        return rid.value
+
+    def decode_width(self):
+        """[EXT] decode-only requests that may hold a codec stream at once (q3tts_engine_decode_width)"""
+        return lib().q3tts_engine_decode_width(self.h)
+
+    def decode_stats(self):
+        """[EXT] q3tts_engine_decode_stats: dict(requests, chunks, chunks_shared)"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_decode_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(requests=a.value, chunks=b.value, chunks_shared=c.value)
 
     def candidate_stats(self):
         """[EXT] q3tts_engine_candidate_stats: dict(sets, prefill_rows_saved, pages_copied)"""
