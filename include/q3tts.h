@@ -528,6 +528,8 @@ int q3tts_op_sample(const float* logits, int32_t n, float temperature, int32_t t
 int q3tts_op_sample_rows(int32_t kernel, const float* logits, int32_t B, int32_t n, const float* temperature, const int32_t* top_k,
                          const float* top_p, const float* penalty, const uint64_t* seed, const int32_t* hist, const int32_t* hist_len,
                          int32_t hist_cap, int32_t n_draws, int32_t* out);
+/* one row through k_project_mt, the per-frame projection: n_in % 512 == 0 and n_out % 16 == 0; any other shape is refused by the kernel's
+ * launcher and leaves y unwritten */
 int q3tts_op_project(const float* x, const float* w /* [n_out][n_in] */, const float* b, int32_t n_in, int32_t n_out, float* y);
 /* [EXT] test surface of k_logprob_rows, host buffers: logits [B][stride] (n <= stride, n <= 4096), chosen [B], extra_idx < 0 = none;
  * out_chosen [B] = log softmax(row)[chosen], out_extra [B] (or NULL) = log softmax(row)[extra_idx] */
@@ -736,6 +738,50 @@ typedef struct q3tts_select_desc {
     uint32_t* draws_out;             /* out [B]: the draw counters after the last launch (samplers) */
 } q3tts_select_desc;
 int q3tts_op_select_rows(q3tts_select_desc* d);
+
+/* [EXT] test surface of the glue kernels between the GEMMs of a decode frame, host buffers: one call uploads what the caller gives, makes
+ * exactly one launch through the launcher the engine calls, and downloads everything.  Inputs are synthetic: tables of any row count, a
+ * row-major weight [n_out][n_in] (Wt / Wblk are built by the engine's own layout helpers), keys as raw 64-bit words.
+ * A q3tts_guarded buffer is in/out and arrives WHOLE: Q3TTS_GLUE_GUARD guard elements, the core, Q3TTS_GLUE_GUARD guard elements.  The
+ * device works at element Q3TTS_GLUE_GUARD; the caller pre-sets guards, stride padding and the state of one slot past ntok to a sentinel of
+ * its choice and finds every stray write in what comes back.  `n` counts the whole buffer; the core may be larger than the minimum below.
+ * Only what keeps the launch inside its buffers is checked here; what a launcher refuses (PROJECT_MT: n_in % 512, n_out % 16, x_stride % 4,
+ * a row address off 16 bytes) fails through that launcher and leaves every buffer unwritten.
+ *   PROJECT_MT         out[t*out_stride + o] = project(x row t), t < ntok; x holds the rows as the device sees them (row t at t*x_stride,
+ *                      gaps included) and lands x_off floats past a 256-byte aligned address, 16 rows of 3e38 behind it.  out core >= ntok*out_stride
+ *   PROJECT_TABLE      x = table [ntok][n_in], out core >= ntok*n_out (dense rows)
+ *   (every table of the two kernels below sits between two rows of 3e38 on the device)
+ *   FEEDBACK_KEYS      16 tables [table_rows[q]][2048], keys core >= ntok*key_stride (key_stride >= 16), tts_pad [2048], out core >= ntok*2048.
+ *                      trail != 0: the TextTrail form over n_frames (guarded, core >= ntok), n_trail [ntok] <= ids_stride,
+ *                      trail_ids [ntok][ids_stride], text_table [text_rows][2048]
+ *   GATHER_ROWS_KEYS   tables[0] = [table_rows[0]][row_len], keys core >= ntok*key_stride, out core >= ntok*row_len
+ *   ADVANCE_KEYS       AdvanceKeysArgs over ntok slots: keys core >= ntok*16, next_key0 / finished / n_frames / t_slot >= ntok, t_pos >= 4*ntok,
+ *                      hist >= ntok*hist_stride, max_frames [ntok] with max_frames*16 <= hist_stride
+ *   STALL_SAVE, ADVANCE_KEYS_GATED   the same plus StallArgs: open / n_trail [ntok], hidden / save_hidden >= ntok*2048, draws / pdraws >= ntok,
+ *                      save_draws >= 2*ntok */
+enum { Q3TTS_GLUE_PROJECT_MT = 0, Q3TTS_GLUE_PROJECT_TABLE = 1, Q3TTS_GLUE_FEEDBACK_KEYS = 2, Q3TTS_GLUE_GATHER_ROWS_KEYS = 3,
+       Q3TTS_GLUE_ADVANCE_KEYS = 4, Q3TTS_GLUE_STALL_SAVE = 5, Q3TTS_GLUE_ADVANCE_KEYS_GATED = 6 };
+#define Q3TTS_GLUE_GUARD 64
+typedef struct q3tts_guarded { void* p; int64_t n; } q3tts_guarded;
+typedef struct q3tts_frame_glue_desc {
+    int32_t kernel;                  /* Q3TTS_GLUE_* */
+    int32_t ntok;                    /* token rows, table rows (PROJECT_TABLE) or slots B */
+    int32_t n_in, n_out, x_stride, x_off, out_stride;
+    const float* x; int64_t x_floats;
+    const float* w; const float* b;  /* [n_out][n_in], [n_out] */
+    const float* const* tables; const int64_t* table_rows;
+    int32_t row_len, key_stride;
+    const float* tts_pad;
+    int32_t trail; const int32_t* trail_ids; int32_t ids_stride; const float* text_table; int64_t text_rows;
+    const int32_t* n_trail; const int32_t* open; const int32_t* max_frames;
+    int32_t hist_stride;
+    q3tts_guarded out;               /* float */
+    q3tts_guarded keys, next_key0;   /* uint64 */
+    q3tts_guarded finished, n_frames, t_slot, t_pos, hist;   /* int32 */
+    q3tts_guarded hidden, save_hidden;                       /* float */
+    q3tts_guarded draws, pdraws, save_draws;                 /* uint32 */
+} q3tts_frame_glue_desc;
+int q3tts_op_frame_glue(q3tts_frame_glue_desc* d);
 
 #ifdef __cplusplus
 }

@@ -356,6 +356,20 @@ static void lin_run(q3tts_linear_desc* dp) {
     d.form_ran = p.form; d.lpr_ran = p.lpr; d.mt_ran = p.mt; d.z_ran = p.z;
 }
 
+// q3tts_op_frame_glue: one guarded in/out buffer.  It goes up whole, the kernel works Q3TTS_GLUE_GUARD elements in, and it comes back whole
+// after the launch ran.
+template <class T> struct GlueBuf {
+    DevBuf<T> d; T* host = nullptr; size_t n = 0;
+    // core = the elements the kernel may touch at the least; 0 = the kernel does not use this buffer
+    void up(const q3tts_guarded& g, size_t core, const char* what) {
+        Q3_CHECK(g.p && g.n >= (int64_t)(core + 2 * Q3TTS_GLUE_GUARD), std::string("guarded buffer too small or missing: ") + what);
+        host = (T*)g.p; n = (size_t)g.n;
+        d.alloc(n); d.upload(host, n);
+    }
+    T* p() const { return d.p + Q3TTS_GLUE_GUARD; }
+    void down() { if (host) d.download(host, n); }
+};
+
 extern "C" {
 
 int q3tts_op_attention(q3tts_attention_desc* d) {
@@ -853,13 +867,128 @@ int q3tts_op_codec_kernel(q3tts_codec_kernel_desc* d) {
 int q3tts_op_project(const float* x, const float* w, const float* b, int32_t n_in, int32_t n_out, float* y) {
     Q3_API_BEGIN
     require_gpu();
-    std::vector<float> wt((size_t)n_in * n_out);
-    for (int o = 0; o < n_out; o++) for (int i = 0; i < n_in; i++) wt[(size_t)i * n_out + o] = w[(size_t)o * n_in + i];
-    DevBuf<float> dx(n_in), dw(wt.size()), db(n_out), dy(n_out);
-    dx.upload(x, n_in); dw.upload(wt.data(), wt.size()); db.upload(b, n_out);
-    launch_project(0, dx.p, n_in, dw.p, db.p, n_in, n_out, dy.p, n_out, 1);
+    Q3_CHECK(x && w && b && y && n_in >= 1 && n_out >= 1, "bad arguments");
+    const std::vector<float> wb = project_wblk(w, n_in, n_out);   // padded to whole blocks of 16; the launcher refuses what k_project_mt cannot run
+    DevBuf<float> dx(n_in), dw(wb.size()), db(n_out), dy(n_out);
+    dx.upload(x, n_in); dw.upload(wb.data(), wb.size()); db.upload(b, n_out);
+    launch_project_blk(0, dx.p, n_in, dw.p, db.p, n_in, n_out, dy.p, n_out, 1);
+    Q3_LAUNCH_CHECK();
     Q3_HIP(hipDeviceSynchronize());
     dy.download(y, n_out);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] the frame-loop glue kernels over guarded device buffers (include/q3tts.h): one launch through the engine's launcher, no dispatch
+ * here.  A guarded buffer goes up whole, the kernel works Q3TTS_GLUE_GUARD elements in, and it comes back whole after the launch ran. */
+int q3tts_op_frame_glue(q3tts_frame_glue_desc* dp) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(dp, "null frame-glue descriptor");
+    const q3tts_frame_glue_desc& d = *dp;
+    Q3_CHECK(d.kernel >= Q3TTS_GLUE_PROJECT_MT && d.kernel <= Q3TTS_GLUE_ADVANCE_KEYS_GATED, "unknown frame-glue kernel");
+    Q3_CHECK(d.ntok >= 1 && d.ntok <= 65535, "ntok out of [1, 65535]");
+    const size_t n = (size_t)d.ntok;
+    GlueBuf<float> out, hidden, save_hidden;
+    GlueBuf<q3_u64> keys, next_key0;
+    GlueBuf<int32_t> finished, n_frames, t_slot, t_pos, hist;
+    GlueBuf<uint32_t> draws, pdraws, save_draws;
+    if (d.kernel == Q3TTS_GLUE_PROJECT_MT || d.kernel == Q3TTS_GLUE_PROJECT_TABLE) {
+        const bool mt = d.kernel == Q3TTS_GLUE_PROJECT_MT;
+        Q3_CHECK(d.x && d.w && d.b && d.n_in >= 1 && d.n_out >= 1, "bad projection shape");
+        DevBuf<float> dw, db(d.n_out), dx;
+        db.upload(d.b, d.n_out);
+        if (mt) {
+            Q3_CHECK(d.x_off >= 0 && d.x_stride >= d.n_in && d.out_stride >= d.n_out, "bad projection strides");
+            Q3_CHECK(d.x_floats >= (int64_t)(n - 1) * d.x_stride + d.n_in, "x does not hold ntok rows");
+            out.up(d.out, n * d.out_stride, "out");
+            const std::vector<float> wb = project_wblk(d.w, d.n_in, d.n_out);   // whole blocks of 16; the launcher refuses a partial one
+            dw.alloc(wb.size()); dw.upload(wb.data(), wb.size());
+            // 16 more rows of 3e38 behind the caller's: a fetch that runs past row ntok inside its tile of 16 stays inside the allocation
+            std::vector<float> hx((size_t)d.x_off + d.x_floats + (size_t)16 * d.x_stride, 3e38f);
+            std::copy(d.x, d.x + d.x_floats, hx.begin() + d.x_off);
+            dx.alloc(hx.size()); dx.upload(hx.data(), hx.size());
+            launch_project_blk(0, dx.p + d.x_off, d.x_stride, dw.p, db.p, d.n_in, d.n_out, out.p(), d.out_stride, d.ntok);
+        } else {
+            Q3_CHECK(d.x_floats >= (int64_t)n * d.n_in && d.n_in <= 4096, "the table does not hold ntok rows of n_in <= 4096 floats");
+            out.up(d.out, n * d.n_out, "out");
+            const std::vector<float> wt = project_wt(d.w, d.n_in, d.n_out);
+            dw.alloc(wt.size()); dw.upload(wt.data(), wt.size());
+            dx.alloc((size_t)d.x_floats); dx.upload(d.x, (size_t)d.x_floats);
+            launch_project_table(0, dx.p, d.ntok, dw.p, db.p, d.n_in, d.n_out, out.p());
+        }
+        Q3_LAUNCH_CHECK();
+        Q3_HIP(hipDeviceSynchronize());
+        out.down();
+        return Q3TTS_OK;
+    }
+    if (d.kernel == Q3TTS_GLUE_FEEDBACK_KEYS || d.kernel == Q3TTS_GLUE_GATHER_ROWS_KEYS) {
+        const bool fb = d.kernel == Q3TTS_GLUE_FEEDBACK_KEYS;
+        const int nt = fb ? 16 : 1, len = fb ? Q3_EMBD : d.row_len;
+        Q3_CHECK(d.tables && d.table_rows && len >= 1 && d.key_stride >= nt, "bad tables / row length / key stride");
+        std::vector<DevBuf<float>> tab(nt);
+        std::vector<const float*> ptrs(nt);
+        for (int q = 0; q < nt; q++) {   // a negative code reads row 0: every table has one
+            Q3_CHECK(d.tables[q] && d.table_rows[q] >= 1, "table missing");
+            std::vector<float> ht((size_t)(d.table_rows[q] + 2) * len, 3e38f);   // one row of 3e38 before and after the table
+            std::copy(d.tables[q], d.tables[q] + (size_t)d.table_rows[q] * len, ht.begin() + len);
+            tab[q].alloc(ht.size()); tab[q].upload(ht.data(), ht.size());
+            ptrs[q] = tab[q].p + len;
+        }
+        keys.up(d.keys, n * d.key_stride, "keys");
+        out.up(d.out, n * len, "out");
+        if (!fb) {
+            launch_gather_rows_keys(0, ptrs[0], d.table_rows[0], keys.p(), d.key_stride, len, out.p(), d.ntok);
+        } else {
+            Q3_CHECK(d.tts_pad, "tts_pad missing");
+            DevBuf<const float*> d_ptrs(16); DevBuf<int64_t> d_rows(16); DevBuf<float> d_pad(Q3_EMBD), d_text; DevBuf<int32_t> d_ntrail, d_ids;
+            d_ptrs.upload(ptrs.data(), 16); d_rows.upload(d.table_rows, 16); d_pad.upload(d.tts_pad, Q3_EMBD);
+            if (d.trail) {
+                Q3_CHECK(d.n_trail && d.trail_ids && d.ids_stride >= 1 && d.text_table && d.text_rows >= 1, "the trail form needs n_trail / trail_ids / text_table");
+                n_frames.up(d.n_frames, n, "n_frames");
+                for (size_t t = 0; t < n; t++)   // the kernel reads trail_ids[t][n_frames[t]] while n_frames[t] < n_trail[t]
+                    Q3_CHECK(n_frames.host[Q3TTS_GLUE_GUARD + t] >= 0 && d.n_trail[t] <= d.ids_stride, "n_frames < 0 or n_trail > ids_stride");
+                d_ntrail.alloc(n); d_ntrail.upload(d.n_trail, n);
+                d_ids.alloc(n * d.ids_stride); d_ids.upload(d.trail_ids, d_ids.n);
+                d_text.alloc((size_t)d.text_rows * Q3_EMBD); d_text.upload(d.text_table, d_text.n);
+                TextTrail tt; tt.n_frames = n_frames.p(); tt.n_trail = d_ntrail.p; tt.ids = d_ids.p; tt.ids_stride = d.ids_stride; tt.table = d_text.p; tt.rows = d.text_rows;
+                launch_feedback_keys(0, d_ptrs.p, d_rows.p, keys.p(), d.key_stride, d_pad.p, out.p(), d.ntok, &tt);
+            } else {
+                launch_feedback_keys(0, d_ptrs.p, d_rows.p, keys.p(), d.key_stride, d_pad.p, out.p(), d.ntok);
+            }
+        }
+        Q3_LAUNCH_CHECK();
+        Q3_HIP(hipDeviceSynchronize());
+        out.down(); keys.down(); n_frames.down();
+        return Q3TTS_OK;
+    }
+    // the slot state machine
+    const bool gate = d.kernel != Q3TTS_GLUE_ADVANCE_KEYS;
+    Q3_CHECK(d.max_frames && d.hist_stride >= 16, "max_frames / hist_stride missing");
+    keys.up(d.keys, n * 16, "keys"); next_key0.up(d.next_key0, n, "next_key0");
+    finished.up(d.finished, n, "finished"); n_frames.up(d.n_frames, n, "n_frames"); t_slot.up(d.t_slot, n, "t_slot");
+    t_pos.up(d.t_pos, 4 * n, "t_pos"); hist.up(d.hist, n * d.hist_stride, "hist");
+    for (size_t b = 0; b < n; b++)   // a live slot appends 16 codes at n_frames*16 < max_frames*16
+        Q3_CHECK(n_frames.host[Q3TTS_GLUE_GUARD + b] >= 0 && d.max_frames[b] >= 0 && (int64_t)d.max_frames[b] * 16 <= d.hist_stride, "history row outside hist_stride");
+    DevBuf<int32_t> d_max(n + 1), d_open, d_ntrail;   // read-only per-slot inputs: one zero entry past the last slot
+    d_max.zero(); d_max.upload(d.max_frames, n);
+    AdvanceKeysArgs a{d.ntok, finished.p(), n_frames.p(), d_max.p, keys.p(), next_key0.p(), hist.p(), d.hist_stride, t_slot.p(), t_pos.p()};
+    if (!gate) {
+        launch_advance_keys(0, a);
+    } else {
+        Q3_CHECK(d.open && d.n_trail, "the gated kernels need open / n_trail");
+        hidden.up(d.hidden, n * Q3_EMBD, "hidden"); save_hidden.up(d.save_hidden, n * Q3_EMBD, "save_hidden");
+        draws.up(d.draws, n, "draws"); pdraws.up(d.pdraws, n, "pdraws"); save_draws.up(d.save_draws, 2 * n, "save_draws");
+        d_open.alloc(n + 1); d_open.zero(); d_open.upload(d.open, n); d_ntrail.alloc(n + 1); d_ntrail.zero(); d_ntrail.upload(d.n_trail, n);
+        StallArgs s; s.open = d_open.p; s.n_trail = d_ntrail.p; s.hidden = hidden.p(); s.draws = draws.p(); s.pdraws = pdraws.p();
+        s.save_hidden = save_hidden.p(); s.save_draws = save_draws.p();
+        if (d.kernel == Q3TTS_GLUE_STALL_SAVE) launch_stall_save(0, a, s);
+        else launch_advance_keys_gated(0, a, s);
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    keys.down(); next_key0.down(); finished.down(); n_frames.down(); t_slot.down(); t_pos.down(); hist.down();
+    hidden.down(); save_hidden.down(); draws.down(); pdraws.down(); save_draws.down();
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

@@ -46,15 +46,10 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     Q3_CHECK(assets_->n_codec == 16, "need 16 codec embedding tables");
     Q3_CHECK(predictor_->hp().n_vocab >= 15 * Q3_CODEBOOK_SIZE, "predictor vocab < 15*2048");
     // ---- device assets ----
-    std::vector<float> wt((size_t)Q3_EMBD * dP_);
-    for (int o = 0; o < dP_; o++)
-        for (int i = 0; i < Q3_EMBD; i++) wt[(size_t)i * dP_ + o] = assets_->proj_w[(size_t)o * Q3_EMBD + i];
-    d_proj_wt_.alloc(wt.size()); d_proj_wt_.upload(wt.data(), wt.size());
     Q3_CHECK(dP_ % 16 == 0, "projection width must be a multiple of 16");
-    {   // blocked copy [dP/16][2048][16] for the per-frame projection of m_hidden
-        std::vector<float> wb((size_t)Q3_EMBD * dP_);
-        for (int o = 0; o < dP_; o++)
-            for (int i = 0; i < Q3_EMBD; i++) wb[((size_t)(o / 16) * Q3_EMBD + i) * 16 + (o % 16)] = assets_->proj_w[(size_t)o * Q3_EMBD + i];
+    {   // Wt for the load-time table projection, the blocked copy [dP/16][2048][16] for the per-frame projection of m_hidden
+        const std::vector<float> wt = project_wt(assets_->proj_w, Q3_EMBD, dP_), wb = project_wblk(assets_->proj_w, Q3_EMBD, dP_);
+        d_proj_wt_.alloc(wt.size()); d_proj_wt_.upload(wt.data(), wt.size());
         d_proj_wblk_.alloc(wb.size()); d_proj_wblk_.upload(wb.data(), wb.size());
     }
     d_proj_b_.alloc(dP_); d_proj_b_.upload(assets_->proj_b, dP_);

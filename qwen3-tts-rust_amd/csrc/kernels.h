@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <vector>
 #include "wlayout.h"
 
 namespace q3 {
@@ -110,10 +111,22 @@ void launch_swiglu_quant(hipStream_t st, const float* gu, int ff, int8_t* aq, ui
 void launch_argmax(hipStream_t st, const float* logits, int stride, int start, int end, const int32_t* mask_per_tok,
                    int32_t* out, int out_stride, int add, int ntok);
 
-// assets_manager.rs:383-399 : out[o] = b[o] + sum_i x[i]*Wt[i][o]  (mul then add, ascending i). Wt is [n_in][n_out].
-void launch_project(hipStream_t st, const float* x, int x_stride, const float* Wt, const float* b, int n_in, int n_out,
-                    float* out, int out_stride, int ntok);
-// batched form over table rows, used once at load to pre-project the codec tables (same arithmetic)
+// assets_manager.rs:383-399 : out[o] = b[o] + sum_i x[i]*W[o][i]  (mul then add, ascending i).  The two device layouts of the row-major
+// weight W [n_out][n_in], built on the host: Wt [n_in][n_out] (k_project_table) and Wblk [ceil(n_out/16)][n_in][16] (k_project_mt; the columns
+// of a partial last block are zero, and launch_project_blk refuses such a width)
+inline std::vector<float> project_wt(const float* w, int n_in, int n_out) {
+    std::vector<float> wt((size_t)n_in * n_out);
+    for (int o = 0; o < n_out; o++)
+        for (int i = 0; i < n_in; i++) wt[(size_t)i * n_out + o] = w[(size_t)o * n_in + i];
+    return wt;
+}
+inline std::vector<float> project_wblk(const float* w, int n_in, int n_out) {
+    std::vector<float> wb((size_t)((n_out + 15) / 16) * 16 * n_in, 0.0f);
+    for (int o = 0; o < n_out; o++)
+        for (int i = 0; i < n_in; i++) wb[((size_t)(o / 16) * n_in + i) * 16 + (o % 16)] = w[(size_t)o * n_in + i];
+    return wb;
+}
+// batched form over table rows, used once at load to pre-project the codec tables (the same chain, over Wt)
 void launch_project_table(hipStream_t st, const float* table, int64_t rows, const float* Wt, const float* b, int n_in,
                           int n_out, float* out);
 

@@ -1262,28 +1262,10 @@ void launch_argmax(hipStream_t st, const float* logits, int stride, int start, i
 }
 
 // =====================================================================================================
-// 2048 -> 1024 projection with the reference's exact order (assets_manager.rs:383-399): one thread per
-// output, bias first, ascending i, separate mul and add.  Wt is the transposed weight [n_in][n_out] so
-// that a wave reads 256 contiguous bytes per step.
+// 2048 -> 1024 projection with the reference's exact order (assets_manager.rs:383-399) over table rows:
+// one thread per output, bias first, ascending i, separate mul and add.  Wt is the transposed weight
+// [n_in][n_out] so that a wave reads 256 contiguous bytes per step.  (The per-frame form is k_project_mt.)
 // =====================================================================================================
-__global__ void __launch_bounds__(256) k_project(const float* __restrict__ x, int x_stride, const float* __restrict__ Wt,
-                                                 const float* __restrict__ b, int n_in, int n_out,
-                                                 float* __restrict__ out, int out_stride) {
-    extern __shared__ float xs[];
-    const int tok = blockIdx.y, o = blockIdx.x * 256 + threadIdx.x;
-    for (int i = threadIdx.x; i < n_in; i += 256) xs[i] = x[(size_t)tok * x_stride + i];
-    __syncthreads();
-    if (o >= n_out) return;
-    float sum = b[o];
-#pragma unroll 8
-    for (int i = 0; i < n_in; i++) { const float t = xs[i] * Wt[(size_t)i * n_out + o]; sum = sum + t; }
-    out[(size_t)tok * out_stride + o] = sum;
-}
-void launch_project(hipStream_t st, const float* x, int x_stride, const float* Wt, const float* b, int n_in, int n_out,
-                    float* out, int out_stride, int ntok) {
-    hipLaunchKernelGGL(k_project, dim3((n_out + 255) / 256, ntok), dim3(256), n_in * sizeof(float), st, x, x_stride, Wt, b,
-                       n_in, n_out, out, out_stride);
-}
 template <int CT>
 __global__ void __launch_bounds__(256) k_project_table(const float* __restrict__ table, int64_t rows,
                                                        const float* __restrict__ Wt, const float* __restrict__ b,

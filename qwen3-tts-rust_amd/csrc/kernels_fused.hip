@@ -820,6 +820,7 @@ void init_fused_kernel_attributes() {} // nothing needs a per-device opt-in any 
 void launch_project_blk(hipStream_t st, const float* x, int x_stride, const float* Wblk, const float* b, int n_in, int n_out,
                         float* out, int out_stride, int ntok) {
     if (n_in % 512 != 0 || x_stride % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) throw Error("k_project_mt: n_in must be a multiple of 512 and the rows 16-byte aligned");
+    if (n_out % 16 != 0) throw Error("k_project_mt: n_out must be a multiple of 16");
     hipLaunchKernelGGL(k_project_mt, dim3(n_out / 16, (ntok + 15) / 16), dim3(256), 0, st, x, x_stride, Wblk, b, n_in, n_out, out, out_stride, ntok);
 }
 

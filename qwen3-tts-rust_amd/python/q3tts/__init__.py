@@ -94,7 +94,7 @@ SYMBOLS = [
     "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
     "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
     "q3tts_submit_score", "q3tts_group_submit_score", "q3tts_engine_score_width", "q3tts_op_score_rows", "q3tts_op_score_inputs",
-    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows",
+    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows", "q3tts_op_frame_glue",
     "q3tts_submit_candidates", "q3tts_group_submit_candidates", "q3tts_engine_candidate_stats", "q3tts_op_kv_fork",
     "q3tts_submit_decode", "q3tts_group_submit_decode", "q3tts_engine_decode_width", "q3tts_engine_decode_stats",
 ]
@@ -230,6 +230,7 @@ def lib():
         L.q3tts_op_score_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_score_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_logprob_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.q3tts_op_frame_glue.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -1564,3 +1565,80 @@ def op_select_rows(kernel, logits, stride=None, row_off=0, temperature=0.0, top_
     lib().q3tts_op_select_rows.argtypes = [C.POINTER(SelectDesc)]
     _chk(lib().q3tts_op_select_rows(C.byref(d)))
     return tokens, raw, draws
+
+
+# ---- the frame-loop glue kernels (q3tts_op_frame_glue) ----
+(GLUE_PROJECT_MT, GLUE_PROJECT_TABLE, GLUE_FEEDBACK_KEYS, GLUE_GATHER_ROWS_KEYS, GLUE_ADVANCE_KEYS, GLUE_STALL_SAVE,
+ GLUE_ADVANCE_KEYS_GATED) = range(7)
+GLUE_GUARD = 64   # Q3TTS_GLUE_GUARD
+
+
+class Guarded(C.Structure):  # q3tts_guarded
+    _fields_ = [("p", C.c_void_p), ("n", C.c_int64)]
+
+
+_GLUE_GUARDED = {"out": np.float32, "keys": np.uint64, "next_key0": np.uint64, "finished": np.int32, "n_frames": np.int32, "t_slot": np.int32,
+                 "t_pos": np.int32, "hist": np.int32, "hidden": np.float32, "save_hidden": np.float32, "draws": np.uint32, "pdraws": np.uint32,
+                 "save_draws": np.uint32}
+_GLUE_ARRAYS = {"x": np.float32, "w": np.float32, "b": np.float32, "tts_pad": np.float32, "trail_ids": np.int32, "text_table": np.float32,
+                "n_trail": np.int32, "open": np.int32, "max_frames": np.int32}
+
+
+_GLUE_INTS = ("ntok", "n_in", "n_out", "x_stride", "x_off", "out_stride", "row_len", "key_stride", "trail", "ids_stride", "hist_stride")
+
+
+class FrameGlueDesc(C.Structure):  # q3tts_frame_glue_desc
+    _fields_ = [("kernel", C.c_int32), ("ntok", C.c_int32),
+                ("n_in", C.c_int32), ("n_out", C.c_int32), ("x_stride", C.c_int32), ("x_off", C.c_int32), ("out_stride", C.c_int32),
+                ("x", C.c_void_p), ("x_floats", C.c_int64), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("tables", C.c_void_p), ("table_rows", C.c_void_p), ("row_len", C.c_int32), ("key_stride", C.c_int32), ("tts_pad", C.c_void_p),
+                ("trail", C.c_int32), ("trail_ids", C.c_void_p), ("ids_stride", C.c_int32), ("text_table", C.c_void_p), ("text_rows", C.c_int64),
+                ("n_trail", C.c_void_p), ("open", C.c_void_p), ("max_frames", C.c_void_p), ("hist_stride", C.c_int32)] + \
+               [(k, Guarded) for k in ("out", "keys", "next_key0", "finished", "n_frames", "t_slot", "t_pos", "hist", "hidden", "save_hidden",
+                                       "draws", "pdraws", "save_draws")]
+
+
+def glue_guarded(core, sentinel, dtype=None):
+    """a whole q3tts_guarded buffer: GLUE_GUARD sentinels, the core (any shape, flattened), GLUE_GUARD sentinels"""
+    core = np.ascontiguousarray(core, dtype).reshape(-1)
+    whole = np.full(core.size + 2 * GLUE_GUARD, sentinel, core.dtype)
+    whole[GLUE_GUARD: GLUE_GUARD + core.size] = core
+    return whole
+
+
+def glue_core(whole, shape=None):
+    """the core of a whole guarded buffer (a view)"""
+    c = whole[GLUE_GUARD: whole.size - GLUE_GUARD]
+    return c if shape is None else c.reshape(shape)
+
+
+def op_frame_glue(kernel, tables=None, **fields):
+    """one launch of one frame-loop glue kernel (q3tts_op_frame_glue).  Guarded buffers (out, keys, next_key0, finished, n_frames, t_slot, t_pos,
+    hist, hidden, save_hidden, draws, pdraws, save_draws) are whole arrays from glue_guarded and are rewritten in place after the launch ran; a
+    refused call leaves them as they were.  tables = a list of float32 arrays [rows][row length]; every other field is an int or an array."""
+    d = FrameGlueDesc()
+    d.kernel = kernel
+    keep = []
+    for k, v in fields.items():
+        if k in _GLUE_GUARDED:
+            assert isinstance(v, np.ndarray) and v.dtype == _GLUE_GUARDED[k] and v.ndim == 1 and v.flags["C_CONTIGUOUS"], k
+            setattr(d, k, Guarded(v.ctypes.data, v.size))
+        elif k in _GLUE_ARRAYS:
+            a = np.ascontiguousarray(v, _GLUE_ARRAYS[k])
+            keep.append(a)
+            setattr(d, k, a.ctypes.data)
+            if k == "x":
+                d.x_floats = a.size
+            if k == "text_table":
+                d.text_rows = a.shape[0]
+        elif k in _GLUE_INTS:
+            setattr(d, k, int(v))
+        else:
+            raise TypeError("op_frame_glue: q3tts_frame_glue_desc has no field %r for the caller to set" % k)
+    if tables is not None:
+        tabs = [np.ascontiguousarray(t, np.float32) for t in tables]
+        ptrs = (C.c_void_p * len(tabs))(*[t.ctypes.data for t in tabs])
+        rows = np.array([t.shape[0] for t in tabs], np.int64)
+        keep += [tabs, ptrs, rows]
+        d.tables, d.table_rows = C.cast(ptrs, C.c_void_p), rows.ctypes.data
+    _chk(lib().q3tts_op_frame_glue(C.byref(d)))
