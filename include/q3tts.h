@@ -20,6 +20,7 @@
 #define Q3TTS_H
 #include <stdint.h>
 #include <stddef.h>
+#include "q3tts_spec.h"   /* q3tts_pcm_format ("output formats") */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -189,6 +190,24 @@ int q3tts_engine_set_logprobs(q3tts_engine* e, int32_t on);
 /* rows [frame_off, frame_off+max_frames) available now, [got][17]; got_frames is what q3tts_fetch reports for the same arguments: the two grow
  * together.  A cancelled request keeps the rows of the frames it keeps.  < 0: unknown id, or the request was not recording */
 int q3tts_fetch_logprobs(q3tts_engine* e, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
+/* [EXT] output formats (q3tts_spec.h "output formats"): the PCM of a request resampled to one of eight rates and / or quantised to int16 on
+ * the device, behind the codec, before it crosses to the host.  Opt-in per request; the native path -- its launches, its bytes -- is
+ * untouched, and the codes of a request do not depend on its format.
+ * q3tts_engine_set_output_format: requests submitted from now on, through any q3tts_submit* form with want_pcm (text, trailing, resume,
+ * candidates, decode), deliver *f.  The format is read once per request at submit and once per candidate set, as q3tts_engine_set_logprobs
+ * is.  NULL = native, {24000, f32}.  Thread-safe; works under Q3_SPEC=ggml.  < 0: an unknown rate or encoding, f32 above 24000 Hz, or an
+ * engine without a codec.  q3tts_generate_batch* always delivers native.
+ * The converted stream is the native one DELAYED by Z F / L native samples (48 at 8000 Hz = 2 ms, 24 at 16000, 16 at 32000 / 44100 / 48000)
+ * and nothing is flushed: the last Z F / L native samples of an utterance do not come out.  n frames give exactly n * 1920 * L / M samples.
+ * q3tts_poll's n_pcm and every offset, capacity and count of the fetch calls are in samples of the request's format.
+ * q3tts_request_format: the format a request delivers ({24000, f32} when none was set).
+ * q3tts_fetch serves an f32 request at any rate; with pcm_out != NULL on an s16 request it returns < 0 (pcm_out == NULL works as ever).
+ * q3tts_fetch_pcm16 is its PCM half for s16 requests and returns < 0 on an f32 request.
+ * q3tts_engine_pcm_out_stats: stream chunks the converter has taken and output samples it has made (0, 0 while no request converted). */
+int q3tts_engine_set_output_format(q3tts_engine* e, const q3tts_pcm_format* f);
+int q3tts_request_format(q3tts_engine* e, int64_t req_id, q3tts_pcm_format* out);
+int q3tts_fetch_pcm16(q3tts_engine* e, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
+int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64_t* samples_out);
 /* [EXT] score (q3tts_spec.h "scoring"): the teacher-forced log-probabilities of frames the caller already holds -- codes [n][16] behind
  * prompt [n_prompt][2048] and optional CLOSED trailing ids [n_trail] (NULL / 0: none).  Queued like any request; ends Q3TTS_REQ_DONE with
  * n_frames = n and no PCM.  prompt, ids and codes are copied.  Row f of q3tts_fetch_logprobs is the row a recording request that emitted
@@ -342,6 +361,9 @@ int q3tts_group_submit_candidates(q3tts_group* g, int32_t engine_index, const q3
                                   const int32_t* trail_ids, int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids);
 int q3tts_group_set_logprobs(q3tts_group* g, int32_t on);      /* [EXT] q3tts_engine_set_logprobs on every engine */
 int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames);
+int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f);   /* [EXT] q3tts_engine_set_output_format on every engine */
+int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
+int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
 int q3tts_group_stop(q3tts_group* g);
 /* q3tts_comm_*: ONE process per GPU (what `bench.py --gpus N` / torchrun-style launchers use).  Rank 0 makes the 128-byte id and ships it to
@@ -782,6 +804,33 @@ typedef struct q3tts_frame_glue_desc {
     q3tts_guarded draws, pdraws, save_draws;                 /* uint32 */
 } q3tts_frame_glue_desc;
 int q3tts_op_frame_glue(q3tts_frame_glue_desc* d);
+
+/* [EXT] output formats (q3tts_spec.h "output formats"): sample-rate conversion and int16 PCM on the device, behind the codec.
+ * Host only, no device needed:
+ *   q3tts_pcm_out_plan     L, M, the prototype's tap count N and the most taps one output sample sums (24000: 1, 1, 0, 0); < 0 for a
+ *                          rate that is not one of the eight.  Any out pointer may be NULL
+ *   q3tts_pcm_out_filter   the f32 prototype h32[0..N) the converter uploads, into h32[cap]; returns N, < 0 for an unknown rate or cap < N
+ *   q3tts_pcm_out_samples  output samples of n_native native samples from a stream's reset, floor(n_native L / M); < 0 for an unknown rate
+ *   q3tts_pcm_format_check 0 for a format the converter delivers, < 0 (and q3tts_last_error) for an unknown rate or encoding or f32 above 24000
+ * q3tts_op_pcm_convert is the test surface of the convert kernel, host buffers in the style of q3tts_op_frame_glue: G streams run through
+ * n_chunks launches of the engine's own launcher, one per chunk, on a fresh converter (every history entry is read from half 0 of the
+ * store first; a slot's live half flips with each chunk it converts).
+ *   in            the chunks one after the other, chunk c = [G][chunk_samples[c]] native f32 samples (position g of every chunk is stream g)
+ *   chunk_samples native samples per stream of each chunk; the launcher refuses what is no positive multiple of 1920
+ *   streams       [n_chunks][G]: the history slot of position g in chunk c, out of n_streams
+ *   fmt           [G]; a native stream's samples are copied through as the engine's copy does
+ *   reset_before  [n_chunks][G] or NULL: nonzero = that position's slot is reset ahead of the chunk
+ *   out           [G] WHOLE buffers of out_bytes[g] bytes: Q3TTS_GLUE_GUARD guard elements of the stream's encoding, the core, as many guard
+ *                 elements.  Stream g's output is appended from the core's first element on, chunk after chunk; n_out[g] = its sample count
+ *   hist_store    in/out, WHOLE: Q3TTS_GLUE_GUARD floats, [n_streams][2][96], Q3TTS_GLUE_GUARD floats
+ * Everything is checked before anything is launched; a refused call leaves every buffer unwritten. */
+int q3tts_pcm_out_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_phase);
+int64_t q3tts_pcm_out_filter(int32_t rate, float* h32, int64_t cap);
+int64_t q3tts_pcm_out_samples(int32_t rate, int64_t n_native);
+int q3tts_pcm_format_check(const q3tts_pcm_format* f);
+int q3tts_op_pcm_convert(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                         const q3tts_pcm_format* fmt, const int32_t* reset_before, void* const* out, const int64_t* out_bytes, int64_t* n_out,
+                         float* hist_store);
 
 #ifdef __cplusplus
 }

@@ -394,6 +394,36 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  * Refused: n < 1 or n > max_steps; no codec; a code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS; a residual code outside [0, 2048)
  * (no request emits such a frame). */
 
+/* ---------------- output formats [EXT] (q3tts_pcm_out_plan / _filter / _samples, q3tts_op_pcm_convert) ----------------
+ * The codec delivers f32 samples at 24000 Hz.  A converter strictly behind it turns a stream's samples into one of these formats:
+ *   rates      8000, 12000, 16000, 22050, 24000 (native), 32000, 44100, 48000.  g = gcd(rate, 24000), L = rate / g, M = 24000 / g
+ *              (22050 is 147/160, 44100 is 147/80)
+ *   encodings  f32 for rates <= 24000 only, s16 for every rate: no format needs more bytes per native sample than the native one
+ *              (48000 s16 needs exactly as many).  {24000, f32} is "native" and means no conversion at all
+ *   filter     F = max(L, M), Z = 16, N = 2 Z F + 1 taps, fc = 0.9 / (2F);
+ *              h[i] = L * 2fc * sinc(2fc * (i - Z F)) * kaiser_{beta = 9}(i), i = 0 .. N-1, in double, then rounded to f32 (h32).
+ *              sinc(x) = sin(pi x) / (pi x); kaiser(i) = I0(beta * sqrt(1 - ((i - Z F) / (Z F))^2)) / I0(beta)
+ *   sample     output sample n of a stream, counted from the stream's reset: t = n M, p = t mod L, j = t div L,
+ *              y[n] = sum over k = 0, 1, ... with p + k L < N of h32[p + k L] * x[j - k], where x[< 0] = 0 (samples before the reset).
+ *              One f32 accumulator starting at 0, k ascending, one fmaf per term; the result is clamped to [-1, 1] as the codec's output is.
+ *              s16 is (int16) rintf(y * 32767.0f), ties to even, from that same clamped f32 value (the product rounded to f32 first), so
+ *              the two encodings never disagree
+ *   24000      no filter and no delay; s16 at 24000 is the clamp and the rounding alone
+ *   counts     T native samples give exactly T L / M output samples.  A frame is 1920 samples and 1920 L / M is an integer for all eight
+ *              rates, so no phase is carried between chunks and the converted stream does not depend on how the frames were cut into chunks
+ *   delay      the converted stream is the native one delayed by Z F / L native samples: 48 at 8000 Hz (2 ms), 32 at 12000, 24 at 16000,
+ *              16 at 32000, 44100 and 48000, 17.4 at 22050.  Nothing is held back and nothing is flushed: THE LAST Z F / L NATIVE SAMPLES
+ *              OF AN UTTERANCE DO NOT COME OUT
+ * One output sample sums 33 to 97 terms and reaches at most 96 native samples back: the converter keeps the last 96 samples per stream. */
+typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts_pcm_format;   /* encoding: 0 = f32, 1 = s16 */
+#define Q3_PCM_F32 0
+#define Q3_PCM_S16 1
+#define Q3_PCM_NATIVE_RATE 24000
+#define Q3_PCM_FRAME 1920        /* native samples per frame */
+#define Q3_PCM_FILTER_Z 16
+#define Q3_PCM_FILTER_BETA 9.0
+#define Q3_PCM_HIST 96           /* native samples of history per stream */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -252,6 +252,31 @@ int q3tts_fetch_logprobs(q3tts_engine* e, int64_t id, float* out, int32_t frame_
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] output formats */
+int q3tts_engine_set_output_format(q3tts_engine* e, const q3tts_pcm_format* f) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_output_format(f); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_format(q3tts_engine* e, int64_t id, q3tts_pcm_format* out) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && out, "null argument");
+    *out = e->e->request_format(id);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_fetch_pcm16(q3tts_engine* e, int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int64_t n = 0;
+    e->e->fetch_pcm16(id, out, off, cap, &n);
+    if (got) *got = n;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64_t* samples_out) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && chunks_converted && samples_out, "null argument");
+    e->e->pcm_out_stats(chunks_converted, samples_out);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

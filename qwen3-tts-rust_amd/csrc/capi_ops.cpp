@@ -4,6 +4,8 @@
 #include "host_logic.h"
 #include "kdev.h"
 #include "codec.h"
+#include "kernels.h"
+#include "pcm_out.h"
 
 using namespace q3;
 #define Q3_API_BEGIN try {
@@ -989,6 +991,94 @@ int q3tts_op_frame_glue(q3tts_frame_glue_desc* dp) {
     Q3_HIP(hipDeviceSynchronize());
     keys.down(); next_key0.down(); finished.down(); n_frames.down(); t_slot.down(); t_pos.down(); hist.down();
     hidden.down(); save_hidden.down(); draws.down(); pdraws.down(); save_draws.down();
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] output formats: the host-only half (pcm_out.h) */
+int q3tts_pcm_out_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_phase) {
+    Q3_API_BEGIN
+    PcmPlan p;
+    Q3_CHECK(pcm_plan(rate, &p), "unknown sample rate");
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (n_taps) *n_taps = p.n_taps;
+    if (taps_per_phase) *taps_per_phase = p.taps_per_phase;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int64_t q3tts_pcm_out_filter(int32_t rate, float* h32, int64_t cap) {
+    Q3_API_BEGIN
+    Q3_CHECK(pcm_rate_index(rate) >= 0, "unknown sample rate");
+    const std::vector<float> h = pcm_filter(rate);
+    Q3_CHECK((h32 || h.empty()) && cap >= (int64_t)h.size(), "h32 is too small for the rate's taps");
+    std::copy(h.begin(), h.end(), h32);
+    return (int64_t)h.size();
+    Q3_API_END(Q3TTS_ERR)
+}
+int64_t q3tts_pcm_out_samples(int32_t rate, int64_t n_native) { return pcm_samples_of_native(rate, n_native); }
+int q3tts_pcm_format_check(const q3tts_pcm_format* f) {
+    Q3_API_BEGIN
+    Q3_CHECK(f, "null format");
+    if (const char* why = pcm_format_why_not(f->sample_rate, f->encoding)) throw Error(why);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] the convert kernel over guarded host buffers (include/q3tts.h): one launch_pcm_convert per chunk, each stream's output appended
+ * behind its earlier chunks' inside its guarded buffer on the device, everything downloaded whole. */
+int q3tts_op_pcm_convert(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                         const q3tts_pcm_format* fmt, const int32_t* reset_before, void* const* out, const int64_t* out_bytes, int64_t* n_out,
+                         float* hist_store) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(in && chunk_samples && streams && fmt && out && out_bytes && n_out && hist_store, "null argument");
+    Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
+    // every chunk is checked as its launch will be, before anything is allocated
+    int64_t in_floats = 0;
+    for (int c = 0; c < n_chunks; c++) {
+        if (const char* why = pcm_convert_refusal(G, G, chunk_samples[c], streams + (size_t)c * G, n_streams, fmt)) throw Error(std::string("pcm convert: ") + why);
+        in_floats += (int64_t)G * chunk_samples[c];
+    }
+    std::vector<int64_t> reg(G), esz(G), need(G, 0);   // each stream's region of the one device buffer, its element size, its output bytes
+    int64_t total = 0;
+    for (int g = 0; g < G; g++) {
+        esz[g] = fmt[g].encoding == Q3_PCM_S16 ? 2 : 4;
+        for (int c = 0; c < n_chunks; c++) need[g] += pcm_samples_of_native(fmt[g].sample_rate, chunk_samples[c]) * esz[g];
+        Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
+        reg[g] = total;
+        total += (out_bytes[g] + 255) / 256 * 256;
+    }
+    DevBuf<uint8_t> d_out((size_t)total);
+    for (int g = 0; g < G; g++) Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
+    DevBuf<float> d_in((size_t)in_floats); d_in.upload(in, (size_t)in_floats);
+    const size_t hist_n = (size_t)n_streams * 2 * Q3_PCM_HIST + 2 * Q3TTS_GLUE_GUARD;
+    DevBuf<float> d_hist(hist_n); d_hist.upload(hist_store, hist_n);
+    PcmConverter conv(n_streams, G);
+    conv.hist = d_hist.p + Q3TTS_GLUE_GUARD;
+    std::vector<int64_t> off(G), done(G, 0), cnt(G);
+    const float* x = d_in.p;
+    for (int c = 0; c < n_chunks; c++) {
+        const int T = chunk_samples[c];
+        const int32_t* sl = streams + (size_t)c * G;
+        for (int g = 0; g < G; g++) {
+            if (reset_before && reset_before[(size_t)c * G + g]) conv.reset_async(0, sl[g]);
+            off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + done[g];
+        }
+        launch_pcm_convert(0, conv, x, G, T, sl, fmt, d_out.p, off.data(), cnt.data());
+        for (int g = 0; g < G; g++) {
+            if (pcm_format_native(fmt[g])) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
+            done[g] += cnt[g] * esz[g];
+        }
+        x += (size_t)G * T;
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    for (int g = 0; g < G; g++) {
+        Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
+        n_out[g] = done[g] / esz[g];
+    }
+    d_hist.download(hist_store, hist_n);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

@@ -34,7 +34,13 @@ public:
     // same, but returns right after enqueueing: pcm_pinned must be hipHostMalloc'd and stay valid until `st` is synchronised
     int decode_async(hipStream_t st, int stream, const int64_t* codes, int n_frames, bool is_last, float* pcm_pinned, int lane = 0);
     // G distinct streams, each with n_frames new frames: codes [G][n_frames][16], pcm[g] pinned destinations
-    int decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm_pinned, int lane = 0);
+    // [EXT] output formats (q3tts_spec.h): fmt[g] = the format stream g is delivered in.  NULL, or every entry {24000, f32}, is the plain call:
+    // the same launches, the same copies.  Otherwise one convert launch (pcmout.hip) follows the output conv on `st` and a converting
+    // stream's copy takes its T*L/M samples of 4 or 2 bytes from the converted buffer; pcm_pinned[g] then receives those bytes.  n_out[g]
+    // (optional) = the samples stream g was given.  The converter's tables, history store and per-lane buffers are allocated on first use
+    int decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm_pinned, int lane = 0,
+                           const q3tts_pcm_format* fmt = nullptr, int64_t* n_out = nullptr);
+    void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks the converter took, output samples it made
     double flops_per_frame() const;
 private:
     struct Impl;

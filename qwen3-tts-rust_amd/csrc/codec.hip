@@ -9,6 +9,9 @@
 #include "codec.h"
 #include "../../include/q3tts.h"
 #include "gguf.h"
+#include "kernels.h"
+#include "pcm_out.h"
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -1076,6 +1079,10 @@ struct CodecDecoder::Impl {
         int64_t* h_in = nullptr; int ring_idx = 0;    // pinned staging ring for the (tiny) code + metadata uploads of async calls
     };
     std::vector<Scratch> lanes; Scratch* S = nullptr; int ring = 256;
+    // [EXT] output formats: made by the first call that converts (decode_group_async), under capture_mutex(); pcm_out[lane] = the converted
+    // chunk of each stream of a pass, region g at g * T * 4 bytes.  The counters are read by other threads
+    std::unique_ptr<PcmConverter> conv; std::vector<DevBuf<float>> pcm_out; size_t pcm_lane_floats = 0;
+    std::atomic<int64_t> conv_chunks{0}, conv_samples{0};
     size_t in_slot() const { return (size_t)gmax * max_frames * n_q + 3 * (size_t)gmax; }
     double flops_frame = 0;
 
@@ -1310,6 +1317,7 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
         L.h.alloc(R0 * H); L.xn.alloc(R0 * H); L.qkv.alloc(R0 * 3 * H); L.att.alloc(R0 * H);
         L.gu.alloc(R0 * 2 * m.ffn); L.act.alloc(R0 * m.ffn);
         L.t1.alloc(max_act); L.t2.alloc(max_act); L.pcm.alloc((size_t)GM * T);
+        m.pcm_lane_floats = (size_t)GM * T;
         L.work.resize(m.all_ext.size());
         for (Ext* e : m.all_ext) L.work[e->id].alloc((size_t)GM * (e->H + e->Tmax) * e->C);
         L.d_in.alloc(m.in_slot());
@@ -1335,7 +1343,11 @@ void CodecDecoder::reset(int s) {
     Q3_CHECK(s >= 0 && s < m.n_streams, "stream out of range");
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
+    if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
     m.kv_len[s] = 0; m.n_seen[s] = 0;
+}
+void CodecDecoder::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const {
+    *chunks_converted = impl_->conv_chunks.load(); *samples_out = impl_->conv_samples.load();
 }
 
 // ---- DecoderState export / import (onnx.rs:461-496: the reference carries the streaming state as named tensors between decode calls;
@@ -1415,6 +1427,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
         if (tab.n == 48) flush();
     }
     flush();
+    if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1430,7 +1443,8 @@ int CodecDecoder::decode_async(hipStream_t st, int s, const int64_t* codes, int 
 
 // One pass for G streams that each contribute n_frames new frames: every GEMM runs over G*T rows, so the 733 MB of
 // codec weights are streamed once per group instead of once per stream, and one set of launches serves the group.
-int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane) {
+int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane,
+                                     const q3tts_pcm_format* fmt, int64_t* n_out) {
     Impl& m = *impl_;
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     Q3_CHECK(G >= 1 && G <= m.gmax, "group size out of range");
@@ -1538,7 +1552,30 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
-    for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+    bool converts = false;
+    for (int g = 0; fmt && g < G; g++) converts = converts || !pcm_format_native(fmt[g]);
+    if (!converts) {
+        for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+        for (int g = 0; n_out && g < G; g++) n_out[g] = T;
+        return T;
+    }
+    // [EXT] output formats: one convert launch behind the output conv, then every stream's bytes from where its format left them
+    if (!m.conv) {
+        std::lock_guard<std::mutex> cap(capture_mutex());
+        m.pcm_out.resize(m.lanes.size());
+        for (auto& b : m.pcm_out) b.alloc(m.pcm_lane_floats);
+        m.conv.reset(new PcmConverter(m.n_streams, m.gmax));
+    }
+    std::vector<int64_t> cnt((size_t)G);
+    const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
+    launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, fmt, m.pcm_out[lane].p, nullptr, cnt.data());
+    Q3_LAUNCH_CHECK();
+    m.conv_chunks += m.conv->chunks_converted - c0; m.conv_samples += m.conv->samples_out - s0;
+    for (int g = 0; g < G; g++) {
+        if (pcm_format_native(fmt[g])) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+        else Q3_HIP(hipMemcpyAsync(pcm[g], m.pcm_out[lane].p + (size_t)g * T, (size_t)cnt[g] * (fmt[g].encoding == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+        if (n_out) n_out[g] = cnt[g];
+    }
     return T;
 }
 

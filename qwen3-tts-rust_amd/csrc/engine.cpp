@@ -196,6 +196,10 @@ struct Engine::Req {
     bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
+    // [EXT] output formats: what the request's PCM is delivered in, read at submit.  pcm_enq / pcm_ready count samples of that format; pcm
+    // holds their bytes as the converter left them (pcm_n samples of 4 or 2 bytes, rounded up to whole floats)
+    q3tts_pcm_format fmt{Q3_PCM_NATIVE_RATE, Q3_PCM_F32}; int64_t pcm_n = 0;
+    size_t sample_bytes() const { return fmt.encoding == Q3_PCM_S16 ? 2 : 4; }
     bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
@@ -550,15 +554,21 @@ void Engine::decoder_main() {
                 std::vector<int> streams(G);
                 std::vector<float*> dst(G);
                 std::vector<int64_t> codes((size_t)G * nf * 16);
+                std::vector<q3tts_pcm_format> fmt(G); std::vector<int64_t> n_out(G); bool converts = false; // [EXT] output formats
                 for (int g = 0; g < G; g++) {
                     Req* r = grp[g].r;
-                    Q3_CHECK(r->pcm_enq + (size_t)nf * spf <= slot_cap_, "pcm staging overflow");
-                    streams[g] = r->cs; dst[g] = pcm_pinned_ + (size_t)r->cs * slot_cap_ + r->pcm_enq;
+                    fmt[g] = r->fmt; converts = converts || !pcm_format_native(r->fmt);
+                    // in bytes: a stream's region holds slot_cap_ native floats, and no format needs more bytes per frame than the native one
+                    const size_t at = r->pcm_enq * r->sample_bytes();
+                    const size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
+                    Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
+                    streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r->cs * slot_cap_) + at);
                     std::copy(grp[g].codes.begin(), grp[g].codes.end(), codes.begin() + (size_t)g * nf * 16);
                 }
                 // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
-                const int got = codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane);
-                for (int g = 0; g < G; g++) grp[g].r->pcm_enq += (size_t)std::max(got, 0);
+                const int got = codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane,
+                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr);
+                for (int g = 0; g < G; g++) grp[g].r->pcm_enq += converts ? (size_t)n_out[g] : (size_t)std::max(got, 0);
             }
             for (auto& t : grp) {
                 hipEvent_t ev = nullptr;
@@ -617,7 +627,8 @@ void Engine::harvest(bool block) {
         }
         (void)hipEventDestroy(c.ev);
         if (c.fence) {
-            r->pcm.assign(pcm_pinned_ + (size_t)r->cs * slot_cap_, pcm_pinned_ + (size_t)r->cs * slot_cap_ + c.pcm_after);
+            r->pcm_n = (int64_t)c.pcm_after; // the bytes as they are: whole floats for f32, (n + 1) / 2 of them for s16
+            r->pcm.assign(pcm_pinned_ + (size_t)r->cs * slot_cap_, pcm_pinned_ + (size_t)r->cs * slot_cap_ + (c.pcm_after * r->sample_bytes() + 3) / 4);
             cs_free_.push_back(r->cs);
             r->cs = -1;
             r->state = fenced_state(r->cancel); r->t_done = now_ms();
@@ -714,6 +725,7 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     }
     r->r.prefix = r->prefix_own.data();
     r->want_pcm = want_pcm && codec_;
+    if (r->want_pcm && may_record) r->fmt = unpack_fmt(out_fmt_.load()); // [EXT] the engine's output format, read once per request; a blocking batch is native
     r->t_submit = now_ms();
     r->seed = g.sampler.has_seed ? g.sampler.seed
                                  : (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count(); // :473-478
@@ -741,6 +753,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
     sh->trail.assign(g.trail, g.trail + g.n_trail);
     g.prompt = sh->prompt.data(); g.trail = sh->trail.data();
     g.logprobs = g.logprobs || lp_on_.load(); // the engine's flag, read once per set
+    const q3tts_pcm_format set_fmt = unpack_fmt(out_fmt_.load()); // and its output format
     std::vector<std::unique_ptr<Req>> rs;
     const double t = now_ms();
     for (int i = 0; i < n; i++) {
@@ -749,6 +762,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->r.prefix = r->prefix_own.data();
         r->shared = sh;
         r->want_pcm = want_pcm && codec_;
+        if (r->want_pcm) r->fmt = set_fmt;
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
@@ -949,6 +963,7 @@ int64_t Engine::submit_decode(const int32_t* codes, int n) {
     if (const char* why = decode_refusal(codes, n, p_.max_steps, codec_ != nullptr)) throw Error(why);
     std::unique_ptr<Req> r(new Req());
     r->decode = true; r->want_pcm = true;
+    r->fmt = unpack_fmt(out_fmt_.load());
     r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
     r->t_submit = now_ms();
@@ -1432,7 +1447,7 @@ ReqStatus Engine::poll(int64_t id) {
     const Req& r = *it->second;
     ReqStatus s;
     const bool ended = r.state == REQ_DONE || r.state == REQ_CANCELLED; // t_done is set, the PCM sits in r.pcm
-    s.state = r.state; s.n_frames = r.fed; s.n_pcm = (int64_t)(ended ? r.pcm.size() : r.pcm_ready);
+    s.state = r.state; s.n_frames = r.fed; s.n_pcm = ended ? r.pcm_n : (int64_t)r.pcm_ready;
     s.queue_ms = (r.t_admit > 0 ? r.t_admit : ended ? r.t_done : now_ms()) - r.t_submit; // cancelled in the queue: until then
     s.prefill_ms = r.prefill_ms; s.first_chunk_ms = r.first_chunk_ms;
     s.total_ms = (ended ? r.t_done : now_ms()) - r.t_submit;
@@ -1445,19 +1460,54 @@ void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, fl
     auto it = reqs_.find(id);
     Q3_CHECK(it != reqs_.end(), "unknown request id");
     const Req& r = *it->second;
+    if (pcm) Q3_CHECK(r.fmt.encoding == Q3_PCM_F32, "the request delivers int16 PCM: fetch it with fetch_pcm16"); // [EXT] output formats; nothing is copied
     int nf = 0; int64_t np = 0;
     if (codes && frame_off >= 0 && frame_off < r.fed) {
         nf = std::min(max_frames, r.fed - frame_off);
         std::copy(r.codes.begin() + (size_t)frame_off * 16, r.codes.begin() + (size_t)(frame_off + nf) * 16, codes);
     }
-    if (pcm && pcm_off >= 0) {
-        const bool done = r.state == REQ_DONE || r.state == REQ_CANCELLED;
-        const int64_t avail = (int64_t)(done ? r.pcm.size() : r.pcm_ready);
-        const float* src = done ? r.pcm.data() : (r.cs >= 0 ? pcm_pinned_ + (size_t)r.cs * slot_cap_ : nullptr);
-        if (src && pcm_off < avail) { np = std::min(pcm_cap, avail - pcm_off); std::copy(src + pcm_off, src + pcm_off + np, pcm); }
-    }
+    if (pcm && pcm_off >= 0) np = copy_pcm(r, pcm, pcm_off, pcm_cap);
     if (got_frames) *got_frames = nf;
     if (got_pcm) *got_pcm = np;
+}
+
+// samples [off, off + cap) of the request's format that are available now, as bytes (mu_ held)
+int64_t Engine::copy_pcm(const Req& r, void* out, int64_t off, int64_t cap) const {
+    const bool done = r.state == REQ_DONE || r.state == REQ_CANCELLED;
+    const int64_t avail = done ? r.pcm_n : (int64_t)r.pcm_ready;
+    const unsigned char* src = done ? reinterpret_cast<const unsigned char*>(r.pcm.data())
+                                    : (r.cs >= 0 ? reinterpret_cast<const unsigned char*>(pcm_pinned_ + (size_t)r.cs * slot_cap_) : nullptr);
+    if (!src || off >= avail || cap <= 0) return 0;
+    const int64_t n = std::min(cap, avail - off);
+    const size_t b = r.sample_bytes();
+    std::memcpy(out, src + (size_t)off * b, (size_t)n * b);
+    return n;
+}
+
+// [EXT] output formats (q3tts_spec.h "output formats")
+void Engine::set_output_format(const q3tts_pcm_format* f) {
+    if (const char* why = pcm_format_refusal(f, codec_ != nullptr)) throw Error(why);
+    out_fmt_ = f ? pack_fmt(*f) : pack_fmt(q3tts_pcm_format{Q3_PCM_NATIVE_RATE, Q3_PCM_F32});
+}
+q3tts_pcm_format Engine::request_format(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    return it->second->fmt;
+}
+void Engine::fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    const Req& r = *it->second;
+    Q3_CHECK(r.fmt.encoding == Q3_PCM_S16, "the request delivers f32 PCM: fetch it with fetch");
+    Q3_CHECK(out && off >= 0, "null buffer or negative offset");
+    const int64_t n = copy_pcm(r, out, off, cap);
+    if (got) *got = n;
+}
+void Engine::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const {
+    *chunks_converted = *samples_out = 0;
+    if (codec_) codec_->pcm_out_stats(chunks_converted, samples_out);
 }
 
 void Engine::fetch_logprobs(int64_t id, float* out, int frame_off, int max_frames, int* got_frames) {

@@ -105,6 +105,14 @@ public:
     void decode_stats(int64_t* requests, int64_t* chunks, int64_t* chunks_shared) const {
         *requests = dec_reqs_.load(); *chunks = dec_chunks_.load(); *chunks_shared = dec_shared_.load();
     }
+    // [EXT] output formats (q3tts_spec.h "output formats"): requests submitted from now on with want_pcm deliver this format (NULL: native);
+    // read once per request at submit and once per candidate set; generate_batch always delivers native.  Thread-safe, no HIP calls; throws
+    // pcm_format_refusal's reason.  fetch() serves f32 requests at their rate and refuses a PCM pointer on an s16 request; fetch_pcm16 is
+    // its PCM half for s16 requests and refuses an f32 one.  poll()'s n_pcm counts samples of the request's format
+    void set_output_format(const q3tts_pcm_format* f);
+    q3tts_pcm_format request_format(int64_t id);
+    void fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
+    void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks converted, output samples made
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -173,6 +181,10 @@ private:
     void purge_chunks(Req* r);
     void retire(Req* r, bool flush_tail); // the slot leaves the batch: EOS / max_steps (tail flushed) or a cancel (tail and unstarted chunks dropped)
     void decoder_main();
+    int64_t copy_pcm(const Req& r, void* out, int64_t off, int64_t cap) const;
+    static int64_t pack_fmt(const q3tts_pcm_format& f) { return (int64_t)f.sample_rate * 4 + f.encoding; }
+    static q3tts_pcm_format unpack_fmt(int64_t v) { return q3tts_pcm_format{(int32_t)(v / 4), (int32_t)(v % 4)}; }
+    std::atomic<int64_t> out_fmt_{(int64_t)Q3_PCM_NATIVE_RATE * 4 + Q3_PCM_F32}; // what submit() reads
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).

@@ -418,6 +418,22 @@ int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32
     if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
     return q3tts_fetch_logprobs(e, rid_of(req_id), out, frame_off, max_frames, got_frames);
 }
+int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f) { // [EXT] q3tts_engine_set_output_format on every engine
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    if (f && q3tts_pcm_format_check(f) != Q3TTS_OK) return Q3TTS_ERR; // all engines or none
+    for (auto* e : g->eng) if (q3tts_engine_set_output_format(e, f) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_fetch_pcm16(e, rid_of(req_id), out, off, cap, got);
+}
+int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_request_format(e, rid_of(req_id), out);
+}
 int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
     if (!g) return Q3TTS_ERR;
     for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;

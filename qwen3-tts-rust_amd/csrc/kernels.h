@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 #include "wlayout.h"
+#include "q3_common.h"
 
 namespace q3 {
 
@@ -315,5 +316,38 @@ void launch_score_rows(hipStream_t st, const ScoreRowsArgs& a, int F);
 // both planes, into the same logical pages of the n_dst sequences dst_seqs[] (device array).  Physical page ids come from kv.page_table on
 // the device (it must be set); every sequence involved must own those pages, and no two of the physical pages may coincide.
 void launch_kv_fork(hipStream_t st, const KvCache& kv, int src_seq, const int32_t* dst_seqs, int n_dst, int n_pages);
+
+// [EXT] output formats (pcmout.hip, q3tts_spec.h "output formats"): sample-rate conversion and int16 PCM behind the codec.
+// One entry per stream of a launch, written by launch_pcm_convert into the converter's upload ring.
+struct PcmStreamMeta {
+    int32_t enc;              // Q3_PCM_F32 / Q3_PCM_S16; -1: the native format, the stream's blocks exit at once
+    int32_t slot, parity;     // history store entry; which of its two halves this launch reads (it leaves the new tail in the other)
+    int32_t L, M, stride;     // the rate's ratio; floats per phase row of its table (0: 24000 Hz, no filter)
+    int32_t tab_off, n_out;   // first float of the rate's table in PcmConverter::tabs; output samples of this chunk
+    int64_t out_off, pad;     // first output byte, from the launch's `out`
+};
+// The converter's device state: the eight filter tables (phase-major, pcm_out.h), the history store [n_streams][2][Q3_PCM_HIST], and a ring
+// of upload slots (pinned host + device) of max_group entries each, every slot with the event of the launch that last read it.  One owner
+// thread; its launches may go to different HIP streams, and the caller orders a stream slot's chunks across them as it does for the codec.
+struct PcmConverter {
+    PcmConverter(int n_streams, int max_group);
+    ~PcmConverter();
+    PcmConverter(const PcmConverter&) = delete; PcmConverter& operator=(const PcmConverter&) = delete;
+    void reset_async(hipStream_t st, int slot);   // zeroes the slot's history: its next sample is sample 0 of a stream
+    int n_streams, max_group;
+    float* hist;                                   // = hist_own.p, or a caller's store of the same shape (the test entry point's guarded one)
+    DevBuf<float> tabs, hist_own; DevBuf<PcmStreamMeta> d_ring;
+    PcmStreamMeta* h_ring = nullptr; int ring_idx = 0; std::vector<hipEvent_t> ring_ev; std::vector<char> ring_used;
+    int tab_off[8], tab_stride[8], tab_L[8], tab_M[8];
+    std::vector<uint8_t> parity;                   // per slot: the half the next launch reads
+    int64_t chunks_converted = 0, samples_out = 0;
+};
+// in [G][T] native samples (T = frames * 1920), stream g of history slot streams[g] in format fmt[g].  Stream g's T*L/M output samples go to
+// out + out_off[g] bytes (out_off NULL: g * T * 4, which every format fits into); n_out[g] receives their count.  A native stream is not
+// touched: n_out[g] = T and its bytes stay where they are, in `in`.  16-byte stores where the destination is 16-byte aligned.
+// Refused (pcm_convert_refusal, pcm_out.h) before anything is uploaded or launched: T % 1920 != 0, G outside [1, max_group], an unknown
+// format, a stream out of range or listed twice.
+void launch_pcm_convert(hipStream_t st, PcmConverter& c, const float* in, int G, int T, const int32_t* streams, const q3tts_pcm_format* fmt,
+                        void* out, const int64_t* out_off, int64_t* n_out);
 
 } // namespace q3

@@ -1,0 +1,68 @@
+// pcm_out.h -- [EXT] output formats (q3tts_spec.h "output formats"): what the converter needs beyond the rules in sched_logic.h (the eight
+// rates, their ratios, which formats exist, how many samples and bytes come out) and still without a device: the normative prototype filter
+// built in double and rounded to f32, its phase-major image as the kernel reads it, and what a convert launch refuses.  No HIP, no threads:
+// tests/host/pcm_out_logic_main.cpp builds it with plain g++ under the host sanitizers.
+#pragma once
+#include "sched_logic.h"
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+namespace q3 {
+
+constexpr int PCM_TAPS_ALIGN = 4;
+// one phase's row in the kernel's table: its taps, rounded up to whole 16-byte vectors
+inline int pcm_phase_stride(const PcmPlan& p) { return (p.taps_per_phase + PCM_TAPS_ALIGN - 1) / PCM_TAPS_ALIGN * PCM_TAPS_ALIGN; }
+
+inline double pcm_bessel_i0(double x) { // power series; every term is positive, so it stops when a term no longer changes the sum
+    const double q = x * x / 4.0;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; k++) {
+        term *= q / ((double)k * (double)k);
+        const double next = sum + term;
+        if (next == sum) break;
+        sum = next;
+    }
+    return sum;
+}
+
+// h[i] = L * 2fc * sinc(2fc * (i - Z*F)) * kaiser_9(i), i = 0 .. N-1, fc = 0.9 / (2F), in double, then rounded to f32
+inline std::vector<float> pcm_filter(int rate) {
+    PcmPlan p;
+    std::vector<float> h;
+    if (!pcm_plan(rate, &p) || p.n_taps == 0) return h;
+    const int F = p.L > p.M ? p.L : p.M, c = Q3_PCM_FILTER_Z * F;
+    const double pi = 3.14159265358979323846, fc2 = 0.9 / (double)F, i0b = pcm_bessel_i0(Q3_PCM_FILTER_BETA);
+    h.resize((size_t)p.n_taps);
+    for (int i = 0; i < p.n_taps; i++) {
+        const double x = fc2 * (double)(i - c), r = (double)(i - c) / (double)c;
+        const double sinc = (i == c) ? 1.0 : std::sin(pi * x) / (pi * x);
+        const double w = pcm_bessel_i0(Q3_PCM_FILTER_BETA * std::sqrt(1.0 - r * r)) / i0b;
+        h[(size_t)i] = (float)((double)p.L * fc2 * sinc * w);
+    }
+    return h;
+}
+// [L][stride]: row p holds h[p], h[p + L], h[p + 2L], ... and zeros behind the last tap below N
+inline std::vector<float> pcm_filter_phase_major(const PcmPlan& p, const std::vector<float>& h) {
+    const int stride = pcm_phase_stride(p);
+    std::vector<float> t((size_t)p.L * stride, 0.0f);
+    for (int ph = 0; ph < p.L; ph++)
+        for (int k = 0; ph + k * p.L < p.n_taps; k++) t[(size_t)ph * stride + k] = h[(size_t)(ph + k * p.L)];
+    return t;
+}
+
+// what a convert launch refuses (nullptr = it may run): G streams of T native samples each, streams[] slots of an n_streams history store
+inline const char* pcm_convert_refusal(int G, int max_group, int64_t T, const int32_t* streams, int n_streams, const q3tts_pcm_format* fmt) {
+    if (G < 1 || G > max_group) return "group size out of range";
+    if (T < Q3_PCM_FRAME || T % Q3_PCM_FRAME != 0) return "chunk length is no whole number of frames";
+    if (T > (int64_t)0x7fffffff / 147) return "chunk too long";   // n * M and T * L stay below 2^31 for every rate
+    if (!streams || !fmt) return "null streams / formats";
+    for (int g = 0; g < G; g++) {
+        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
+        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
+        if (const char* why = pcm_format_why_not(fmt[g].sample_rate, fmt[g].encoding)) return why;
+    }
+    return nullptr;
+}
+
+} // namespace q3

@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set and of a decode-only request, what an admission wave takes from the queue, the chunk rows a score request needs the head for, and how the decoder thread seats chunks in a codec pass.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set and of a decode-only request, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, and the rules of the output formats.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -312,6 +312,59 @@ inline std::vector<ScoreRun> score_head_runs(const std::vector<PromptRef>& batch
         if (c.tok == r.n + r.n_fb - 1) { c.req++; c.tok = 0; } else c.tok++;
     }
     return out;
+}
+
+// [EXT] output formats (q3tts_spec.h "output formats"): the eight rates and their ratios, which formats exist, what comes out of n frames.
+constexpr int PCM_N_RATES = 8;
+inline const int* pcm_rates() { static const int r[PCM_N_RATES] = {8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000}; return r; }
+inline int pcm_rate_index(int rate) { // -1: not one of the eight
+    for (int i = 0; i < PCM_N_RATES; i++) if (pcm_rates()[i] == rate) return i;
+    return -1;
+}
+
+// rate = 24000 * L / M in lowest terms; n_taps = N of the prototype, taps_per_phase = the most terms one output sample sums.
+// 24000 itself has no filter: L = M = 1 and no taps.
+struct PcmPlan { int L = 1, M = 1, n_taps = 0, taps_per_phase = 0; };
+inline bool pcm_plan(int rate, PcmPlan* out) {
+    if (pcm_rate_index(rate) < 0) return false;
+    int a = rate, b = Q3_PCM_NATIVE_RATE;
+    while (b) { const int t = a % b; a = b; b = t; }
+    PcmPlan p;
+    p.L = rate / a; p.M = Q3_PCM_NATIVE_RATE / a;
+    if (rate != Q3_PCM_NATIVE_RATE) {
+        const int F = p.L > p.M ? p.L : p.M;
+        p.n_taps = 2 * Q3_PCM_FILTER_Z * F + 1;
+        p.taps_per_phase = (p.n_taps + p.L - 1) / p.L;
+    }
+    *out = p;
+    return true;
+}
+// output samples of n_native native samples from a stream's reset: floor(n_native * L / M); -1 for an unknown rate or a negative count
+inline int64_t pcm_samples_of_native(int rate, int64_t n_native) {
+    PcmPlan p;
+    if (n_native < 0 || !pcm_plan(rate, &p)) return -1;
+    return n_native * p.L / p.M;
+}
+
+// which formats exist: nullptr = allowed, else the reason.  f32 only up to the native rate, so that no format needs more bytes per native
+// sample than the native one.
+inline const char* pcm_format_why_not(int rate, int encoding) {
+    if (pcm_rate_index(rate) < 0) return "unknown sample rate";
+    if (encoding != Q3_PCM_F32 && encoding != Q3_PCM_S16) return "unknown encoding";
+    if (encoding == Q3_PCM_F32 && rate > Q3_PCM_NATIVE_RATE) return "f32 is delivered up to 24000 Hz only";
+    return nullptr;
+}
+inline bool pcm_format_native(const q3tts_pcm_format& f) { return f.sample_rate == Q3_PCM_NATIVE_RATE && f.encoding == Q3_PCM_F32; }
+
+// what a request may ask for and what n frames of it come to.  f == NULL is the native format.  No format needs more bytes than the native one, so a staging region sized for native floats serves every format.
+inline const char* pcm_format_refusal(const q3tts_pcm_format* f, bool have_codec) {
+    if (!have_codec) return "the engine has no codec";
+    return f ? pcm_format_why_not(f->sample_rate, f->encoding) : nullptr;
+}
+inline int64_t pcm_out_samples(const q3tts_pcm_format& f, int64_t n_frames) { return pcm_samples_of_native(f.sample_rate, n_frames * Q3_PCM_FRAME); }
+inline int64_t pcm_out_bytes(const q3tts_pcm_format& f, int64_t n_frames) {
+    const int64_t n = pcm_out_samples(f, n_frames);
+    return n < 0 ? -1 : n * (f.encoding == Q3_PCM_S16 ? 2 : 4);
 }
 
 } // namespace q3

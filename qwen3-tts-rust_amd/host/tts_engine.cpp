@@ -133,11 +133,13 @@ void VoiceFile::save(const std::string& path) const {
 void AudioSample::save_wav(const std::string& path) const { // audio.rs:26-41
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) throw std::runtime_error("cannot create " + path);
-    const uint32_t data_bytes = (uint32_t)samples.size() * 2, riff = 36 + data_bytes, fmt_len = 16, byte_rate = sample_rate * channels * 2;
+    const bool s16 = encoding == 1;
+    const uint32_t data_bytes = (uint32_t)(s16 ? samples16.size() : samples.size()) * 2, riff = 36 + data_bytes, fmt_len = 16, byte_rate = sample_rate * channels * 2;
     const uint16_t pcm = 1, block = (uint16_t)(channels * 2), bits = 16;
     fwrite("RIFF", 1, 4, f); fwrite(&riff, 4, 1, f); fwrite("WAVEfmt ", 1, 8, f); fwrite(&fmt_len, 4, 1, f); fwrite(&pcm, 2, 1, f);
     fwrite(&channels, 2, 1, f); fwrite(&sample_rate, 4, 1, f); fwrite(&byte_rate, 4, 1, f); fwrite(&block, 2, 1, f); fwrite(&bits, 2, 1, f);
     fwrite("data", 1, 4, f); fwrite(&data_bytes, 4, 1, f);
+    if (s16) { if (!samples16.empty()) fwrite(samples16.data(), 2, samples16.size(), f); fclose(f); return; } // [EXT] the engine's own int16
     for (float s : samples) { float a = s * 32767.0f; a = a < -32768.0f ? -32768.0f : (a > 32767.0f ? 32767.0f : a); const int16_t v = (int16_t)a; fwrite(&v, 2, 1, f); }
     fclose(f);
 }
@@ -364,6 +366,28 @@ AudioSample TtsEngine::generate(const std::string& text, const std::string& ref_
     return generate_ids(tok_(text), ref_audio_path, tok_(ref_text), instruct ? &ins : nullptr);
 }
 
+void TtsEngine::set_output_format(uint32_t sample_rate, int32_t encoding) {
+    const q3tts_pcm_format f{(int32_t)sample_rate, encoding};
+    if (q3tts_engine_set_output_format(e_, sample_rate ? &f : nullptr) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
+}
+// PCM samples [at, ...) of a request in its own format, appended to `out`; returns how many came (floats are made of int16 as v / 32767)
+static int64_t fetch_more(q3tts_engine* e, int64_t id, AudioSample& out, std::vector<float>& buf, std::vector<int16_t>& buf16) {
+    int64_t got = 0;
+    if (out.encoding == 1) {
+        if (q3tts_fetch_pcm16(e, id, buf16.data(), (int64_t)out.samples16.size(), (int64_t)buf16.size(), &got) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
+        out.samples16.insert(out.samples16.end(), buf16.begin(), buf16.begin() + got);
+        for (int64_t i = 0; i < got; i++) buf[(size_t)i] = (float)buf16[(size_t)i] / 32767.0f;
+    } else if (q3tts_fetch(e, id, nullptr, 0, 0, buf.data(), (int64_t)out.samples.size(), (int64_t)buf.size(), nullptr, &got) != Q3TTS_OK)
+        throw std::runtime_error(q3tts_last_error());
+    out.samples.insert(out.samples.end(), buf.begin(), buf.begin() + got);
+    return got;
+}
+static void take_format(q3tts_engine* e, int64_t id, AudioSample& out) {
+    q3tts_pcm_format f{24000, 0};
+    if (q3tts_request_format(e, id, &f) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
+    out.sample_rate = (uint32_t)f.sample_rate; out.encoding = f.encoding;
+}
+
 AudioSample TtsEngine::generate_with_voice_ids_stream(const std::vector<int32_t>& text_ids, const VoiceFile& voice, const ChunkFn& on_chunk,
                                                       const std::vector<int32_t>* ins, const std::vector<int32_t>* ref_text_ids,
                                                       std::vector<int32_t>* codes_out) {
@@ -374,19 +398,17 @@ AudioSample TtsEngine::generate_with_voice_ids_stream(const std::vector<int32_t>
     int64_t id = 0;
     if (q3tts_submit(e_, &r, 1, &id) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
     AudioSample out;
-    std::vector<float> buf(4 * 1920 * 4);
+    take_format(e_, id, out);
+    std::vector<float> buf(4 * 1920 * 4); std::vector<int16_t> buf16(buf.size());
     for (;;) {
         int32_t busy = 0;
         if (q3tts_sched_step(e_, &busy) != Q3TTS_OK) { q3tts_release(e_, id); throw std::runtime_error(q3tts_last_error()); }
         q3tts_req_status st{};
         if (q3tts_poll(e_, id, &st) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
         while ((int64_t)out.samples.size() < st.n_pcm) { // hand over whatever the codec finished since the last look
-            int64_t got = 0;
-            if (q3tts_fetch(e_, id, nullptr, 0, 0, buf.data(), (int64_t)out.samples.size(), (int64_t)buf.size(), nullptr, &got) != Q3TTS_OK)
-                throw std::runtime_error(q3tts_last_error());
+            const int64_t got = fetch_more(e_, id, out, buf, buf16);
             if (got <= 0) break;
             if (on_chunk) on_chunk(buf.data(), (size_t)got);
-            out.samples.insert(out.samples.end(), buf.begin(), buf.begin() + got);
         }
         if (st.state == Q3TTS_REQ_DONE && (int64_t)out.samples.size() >= st.n_pcm) {
             if (codes_out) {
@@ -414,15 +436,13 @@ AudioSample TtsEngine::vocode(const std::vector<int32_t>& codes) {
         throw std::runtime_error(why.empty() ? "decoding failed" : why);
     }
     AudioSample out;
-    out.samples.assign((size_t)st.n_pcm, 0.0f);
-    int64_t got = 0;
-    if (st.n_pcm > 0 && q3tts_fetch(e_, id, nullptr, 0, 0, out.samples.data(), 0, st.n_pcm, nullptr, &got) != Q3TTS_OK) {
-        q3tts_release(e_, id);
-        throw std::runtime_error(q3tts_last_error());
-    }
-    out.samples.resize((size_t)got);
+    try {
+        take_format(e_, id, out);
+        std::vector<float> buf((size_t)std::max<int64_t>(st.n_pcm, 1)); std::vector<int16_t> buf16(buf.size());
+        if (st.n_pcm > 0) fetch_more(e_, id, out, buf, buf16);
+    } catch (...) { q3tts_release(e_, id); throw; }
     q3tts_release(e_, id);
-    return out; // AudioSample{samples, 24000, 1}
+    return out; // AudioSample{samples, 24000, 1} unless an output format is set
 }
 
 std::vector<int64_t> TtsEngine::encode_audio(const std::vector<float>& audio) const { // onnx.rs:97-121

@@ -39,8 +39,11 @@ void load_cache(const std::string& path, std::vector<int64_t>& codes, std::vecto
 
 struct AudioSample { // audio.rs:4-46
     std::vector<float> samples; uint32_t sample_rate = 24000; uint16_t channels = 1;
+    // [EXT] output formats (q3tts_spec.h): encoding 1 = the engine delivered int16 at sample_rate; they are in samples16, as delivered, and
+    // samples holds the same values / 32767 for callers that want floats
+    int32_t encoding = 0; std::vector<int16_t> samples16;
     static AudioSample load_wav(const std::string& path); // audio.rs:11-23: samples read as i16 / 32768, channel count kept but not de-interleaved
-    void save_wav(const std::string& path) const;
+    void save_wav(const std::string& path) const;         // PCM16 at sample_rate; an int16 sample is written as it is
     float duration() const { return (float)samples.size() / (float)sample_rate; }
 };
 
@@ -54,6 +57,9 @@ public:
     TtsEngine(const TtsEngine&) = delete;
     ~TtsEngine();
     void set_max_steps(size_t steps) { max_steps_ = steps; }                       // :172-174
+    // [EXT] output formats: what generate_with_voice_ids_stream and vocode deliver from now on (q3tts_engine_set_output_format; rate 0 =
+    // native).  The blocking generate* calls stay native.  The converted audio lags by 16 F / L native samples and loses that much at its end
+    void set_output_format(uint32_t sample_rate, int32_t encoding);
     void set_sampler_config(const SamplerConfig& c) { sampler_ = c; }              // :177-179
     const SamplerConfig& get_sampler_config() const { return sampler_; }           // :182-184
     void load_speakers(const std::string& dir);                                    // :187-208

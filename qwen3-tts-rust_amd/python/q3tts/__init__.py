@@ -97,8 +97,18 @@ SYMBOLS = [
     "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows", "q3tts_op_frame_glue",
     "q3tts_submit_candidates", "q3tts_group_submit_candidates", "q3tts_engine_candidate_stats", "q3tts_op_kv_fork",
     "q3tts_submit_decode", "q3tts_group_submit_decode", "q3tts_engine_decode_width", "q3tts_engine_decode_stats",
+    "q3tts_engine_set_output_format", "q3tts_request_format", "q3tts_fetch_pcm16", "q3tts_engine_pcm_out_stats",
+    "q3tts_group_set_output_format", "q3tts_group_fetch_pcm16", "q3tts_group_request_format",
+    "q3tts_pcm_out_plan", "q3tts_pcm_out_filter", "q3tts_pcm_out_samples", "q3tts_pcm_format_check", "q3tts_op_pcm_convert",
 ]
 
+class PcmFormat(C.Structure):  # q3tts_pcm_format
+    _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32)]
+
+
+PCM_F32, PCM_S16 = 0, 1                                                  # q3tts_pcm_format.encoding
+PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)      # q3tts_spec.h "output formats"
+PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
 LOGPROB_NONE = 1.0    # Q3TTS_LOGPROB_NONE: not computed (a real value is never positive)
 
@@ -231,6 +241,21 @@ def lib():
         L.q3tts_op_score_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.q3tts_op_logprob_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.q3tts_op_frame_glue.argtypes = [C.c_void_p]
+        L.q3tts_engine_set_output_format.argtypes = [C.c_void_p, C.POINTER(PcmFormat)]
+        L.q3tts_request_format.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PcmFormat)]
+        L.q3tts_fetch_pcm16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.q3tts_engine_pcm_out_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.q3tts_group_set_output_format.argtypes = L.q3tts_engine_set_output_format.argtypes
+        L.q3tts_group_fetch_pcm16.argtypes = L.q3tts_fetch_pcm16.argtypes
+        L.q3tts_group_request_format.argtypes = L.q3tts_request_format.argtypes
+        L.q3tts_pcm_out_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
+        L.q3tts_pcm_out_filter.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
+        L.q3tts_pcm_out_filter.restype = C.c_int64
+        L.q3tts_pcm_out_samples.argtypes = [C.c_int32, C.c_int64]
+        L.q3tts_pcm_out_samples.restype = C.c_int64
+        L.q3tts_pcm_format_check.argtypes = [C.POINTER(PcmFormat)]
+        L.q3tts_op_pcm_convert.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -447,6 +472,38 @@ def group_set_logprobs(group, on):
 def group_fetch_logprobs(group, rid, frame_off=0, max_frames=4096):
     """[EXT] q3tts_group_fetch_logprobs: float32 [n][17] of a group request id"""
     return _fetch_logprobs(lib().q3tts_group_fetch_logprobs, group, rid, frame_off, max_frames)
+
+
+def _set_output_format(fn, h, rate, encoding):
+    _chk(fn(h, None if rate is None else C.byref(PcmFormat(int(rate), int(encoding)))))
+
+
+def _request_format(fn, h, rid):
+    f = PcmFormat()
+    _chk(fn(h, rid, C.byref(f)))
+    return f.sample_rate, f.encoding
+
+
+def _fetch_pcm16(fn, h, rid, off, cap):
+    out = np.zeros(max(cap, 1), np.int16)
+    got = C.c_int64()
+    _chk(fn(h, rid, _p(out), off, cap, C.byref(got)))
+    return out[: got.value].copy()
+
+
+def group_set_output_format(group, rate=None, encoding=PCM_F32):
+    """[EXT] q3tts_group_set_output_format on a q3tts_group handle: every engine of the group (rate None = native)"""
+    _set_output_format(lib().q3tts_group_set_output_format, group, rate, encoding)
+
+
+def group_request_format(group, rid):
+    """[EXT] q3tts_group_request_format: (sample_rate, encoding) of a group request id"""
+    return _request_format(lib().q3tts_group_request_format, group, rid)
+
+
+def group_fetch_pcm16(group, rid, off=0, cap=0):
+    """[EXT] q3tts_group_fetch_pcm16: int16 samples [off, off + cap) available now of a group request id"""
+    return _fetch_pcm16(lib().q3tts_group_fetch_pcm16, group, rid, off, cap)
 
 
 class Sampler:  # LlamaSampler (llama/mod.rs:627-776)
@@ -669,6 +726,26 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
                                C.byref(gf), C.byref(gp)))
         return codes[: gf.value * 16].reshape(gf.value, 16).copy(), pcm[: gp.value].copy()
 
+    def set_output_format(self, rate=None, encoding=PCM_F32):
+        """[EXT] output formats (q3tts_engine_set_output_format): requests submitted from now on with want_pcm deliver `rate` Hz (one of
+        PCM_RATES) as PCM_F32 (up to 24000) or PCM_S16; rate None = native.  The converted stream lags the native one by 16 F / L native
+        samples (2 ms at 8000 Hz) and its last such samples do not come out"""
+        _set_output_format(lib().q3tts_engine_set_output_format, self.h, rate, encoding)
+
+    def request_format(self, rid):
+        """[EXT] (sample_rate, encoding) the request delivers"""
+        return _request_format(lib().q3tts_request_format, self.h, rid)
+
+    def fetch_pcm16(self, rid, off=0, cap=0):
+        """[EXT] int16 samples [off, off + cap) available now of an s16 request (raises on an f32 one)"""
+        return _fetch_pcm16(lib().q3tts_fetch_pcm16, self.h, rid, off, cap)
+
+    def pcm_out_stats(self):
+        """[EXT] q3tts_engine_pcm_out_stats: dict(chunks_converted, samples_out)"""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_pcm_out_stats(self.h, C.byref(a), C.byref(b)))
+        return dict(chunks_converted=a.value, samples_out=b.value)
+
     def wait(self, rid, timeout_ms=-1.0):
         rc = lib().q3tts_wait(self.h, rid, timeout_ms)
         if rc < 0:
@@ -715,10 +792,15 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         return bool(b.value)
 
     def result(self, rid, want_pcm=False):
-        """collects a finished request (codes [n][16], pcm) and releases it"""
+        """collects a finished request (codes [n][16], pcm) and releases it.  pcm is float32 or, for an s16 request ([EXT] output formats),
+        int16, at sample_rate Hz"""
         st = self.poll(rid)
-        codes, pcm = self.fetch(rid, 0, max(st["n_frames"], 1), 0, st["n_pcm"] if want_pcm else 0)
-        out = {"codes": codes, "pcm": pcm if want_pcm else None, **st}
+        rate, enc = self.request_format(rid)
+        s16 = want_pcm and enc == PCM_S16
+        codes, pcm = self.fetch(rid, 0, max(st["n_frames"], 1), 0, st["n_pcm"] if want_pcm and not s16 else 0)
+        if s16:
+            pcm = self.fetch_pcm16(rid, 0, st["n_pcm"])
+        out = {"codes": codes, "pcm": pcm if want_pcm else None, "sample_rate": rate, **st}
         if self.records(rid):
             out["logprobs"] = self.fetch_logprobs(rid, 0, max(st["n_frames"], 1))
         self.release(rid)
@@ -1642,3 +1724,74 @@ def op_frame_glue(kernel, tables=None, **fields):
         keep += [tabs, ptrs, rows]
         d.tables, d.table_rows = C.cast(ptrs, C.c_void_p), rows.ctypes.data
     _chk(lib().q3tts_op_frame_glue(C.byref(d)))
+
+
+# ---- output formats: the host-only half and the convert kernel (q3tts_op_pcm_convert) ----
+def pcm_out_plan(rate):
+    """(L, M, n_taps, taps_per_phase) of one of PCM_RATES"""
+    v = [C.c_int32() for _ in range(4)]
+    _chk(lib().q3tts_pcm_out_plan(rate, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def pcm_out_filter(rate):
+    """the f32 prototype filter the converter uploads for this rate (empty at 24000)"""
+    h = np.zeros(pcm_out_plan(rate)[2], np.float32)
+    n = lib().q3tts_pcm_out_filter(rate, _p(h), h.size)
+    if n != h.size:
+        raise Q3Error(lib().q3tts_last_error().decode())
+    return h
+
+
+def pcm_out_samples(rate, n_native):
+    return int(lib().q3tts_pcm_out_samples(rate, n_native))
+
+
+def pcm_format_ok(rate, encoding):
+    return lib().q3tts_pcm_format_check(C.byref(PcmFormat(rate, encoding))) == 0
+
+
+def pcm_dtype(encoding):
+    return np.int16 if encoding == PCM_S16 else np.float32
+
+
+def op_pcm_convert(x, chunk_samples, streams, n_streams, fmts, reset_before=None, hist=None, slack=0, fill=0x5A):
+    """the convert kernel over host buffers, one launch of the engine's launcher per chunk.  x [G][sum(chunk_samples)] f32: the native signal of
+    each position; streams [n_chunks][G] history slots; fmts [G] (rate, encoding).  hist: a whole guarded store (GLUE_GUARD floats,
+    [n_streams][2][96], GLUE_GUARD floats) or None for a zero store between guards of -3e38.  Every output buffer is made exactly as large as
+    the result plus `slack` elements, every byte `fill`.  Returns (outs, wholes, n_out, hist): the converted samples per position, the whole
+    buffers as they came back, the counts the call reported, the whole store.  A refused call raises Q3Error carrying wholes / n_out / hist as they are then."""
+    x = np.ascontiguousarray(x, np.float32)
+    G = x.shape[0] if x.ndim == 2 else 0
+    cs = np.ascontiguousarray(chunk_samples, np.int32)
+    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
+    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    parts, at = [], 0
+    for t in cs:                       # [n_chunks concatenated][G][T_c]
+        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
+        at += max(int(t), 0)
+    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G else np.zeros(1, np.float32)
+    fm = (PcmFormat * max(len(fmts), 1))(*[PcmFormat(int(r), int(e)) for r, e in fmts])
+    wholes, want = [], []
+    for r, e in fmts:
+        n = sum(max(pcm_out_samples(r, int(t)), 0) for t in cs)
+        want.append(n)
+        wholes.append(np.full((n + slack + 2 * GLUE_GUARD) * np.dtype(pcm_dtype(e)).itemsize, fill, np.uint8))
+    if hist is None:
+        hist = np.zeros(n_streams * 2 * PCM_HIST + 2 * GLUE_GUARD, np.float32)
+        hist[:GLUE_GUARD] = hist[-GLUE_GUARD:] = -3e38
+    assert hist.dtype == np.float32 and hist.size == n_streams * 2 * PCM_HIST + 2 * GLUE_GUARD and hist.flags["C_CONTIGUOUS"]
+    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
+    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
+    n_out = np.full(max(len(wholes), 1), -1, np.int64)
+    try:
+        _chk(lib().q3tts_op_pcm_convert(_p(flat), G, _p(cs), cs.size, _p(sl), n_streams, C.cast(fm, C.c_void_p), _p(rb), ptrs, _p(nbytes),
+                                        _p(n_out), _p(hist)))
+    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
+        ex.wholes, ex.n_out, ex.hist = wholes, n_out[: len(wholes)].copy(), hist
+        raise
+    outs = []
+    for w, (r, e), n in zip(wholes, fmts, want):
+        v = w.view(pcm_dtype(e))
+        outs.append(v[GLUE_GUARD: GLUE_GUARD + n].copy())
+    return outs, wholes, n_out[: len(wholes)].copy(), hist
