@@ -208,6 +208,33 @@ int q3tts_engine_set_output_format(q3tts_engine* e, const q3tts_pcm_format* f);
 int q3tts_request_format(q3tts_engine* e, int64_t req_id, q3tts_pcm_format* out);
 int q3tts_fetch_pcm16(q3tts_engine* e, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
 int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64_t* samples_out);
+/* [EXT] codec preambles (q3tts_spec.h "codec preambles"): a request's codec stream starts from the state behind given frames -- a clone
+ * voice's reference codes -- instead of zeros, so its first sample is already "in the voice".  The state is built once per preamble and
+ * kept on the device; a primed request restores it with one device-to-device launch where the zeroing launch ran.  Opt-in; codes,
+ * log-probability rows and every unprimed request are unchanged, only the PCM of a primed request differs: it is decode(preamble ++ frames)
+ * without the preamble's samples, at the sample count of the unprimed request.
+ * q3tts_preamble_create: codes [n][16] as q3tts_submit_decode takes them; built like a decode-only request (it waits for a codec stream and
+ * passes through the decoder thread).  Thread-safe, no HIP call in the caller's thread.  < 0 and nothing queued: q3tts_submit_decode's
+ * refusals, Q3TTS_MAX_PREAMBLES live preambles, or n + max_steps above Q3TTS_CODEC_MAX_FRAMES.
+ * q3tts_preamble_poll / _wait: state and frame count; _wait returns 0 once the preamble is READY or FAILED, 1 on timeout, and drives the
+ * scheduler itself when no driver thread runs, as q3tts_wait does.
+ * q3tts_preamble_release: the creator's reference goes.  Voices, the engine-level setting and submitted requests hold their own; the
+ * snapshot's slot is recycled when the last one is gone and every restore enqueued from it has completed.  The id is never reused.
+ * q3tts_voice_set_preamble: requests submitted through any q3tts_submit_text* form with that voice and want_pcm are primed (-1: none); the
+ * engine-level setting does not apply to text forms.  q3tts_engine_set_preamble: read once per request at submit and once per candidate
+ * set by the raw-prompt forms (q3tts_submit, _ex, _trailing, _trailing_open, _resume, _candidates, _decode) with want_pcm (-1: none).
+ * Both refuse a preamble that is not READY.  want_pcm = 0 and q3tts_generate_batch* are never primed.
+ * q3tts_request_preamble: the preamble a request was primed with, -1 when none.
+ * q3tts_engine_preamble_stats: preambles built, restores enqueued, device bytes of one snapshot (NULL pointers are skipped). */
+/* Q3TTS_MAX_PREAMBLES and the Q3TTS_PREAMBLE_* states: q3tts_spec.h */
+int q3tts_preamble_create(q3tts_engine* e, const int32_t* codes, int32_t n, int32_t* preamble_id);
+int q3tts_preamble_poll(q3tts_engine* e, int32_t preamble_id, int32_t* state, int32_t* n_frames);
+int q3tts_preamble_wait(q3tts_engine* e, int32_t preamble_id, double timeout_ms);
+int q3tts_preamble_release(q3tts_engine* e, int32_t preamble_id);
+int q3tts_voice_set_preamble(q3tts_engine* e, int32_t voice_id, int32_t preamble_id);
+int q3tts_engine_set_preamble(q3tts_engine* e, int32_t preamble_id);
+int q3tts_request_preamble(q3tts_engine* e, int64_t req_id, int32_t* preamble_id);
+int q3tts_engine_preamble_stats(q3tts_engine* e, int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot);
 /* [EXT] score (q3tts_spec.h "scoring"): the teacher-forced log-probabilities of frames the caller already holds -- codes [n][16] behind
  * prompt [n_prompt][2048] and optional CLOSED trailing ids [n_trail] (NULL / 0: none).  Queued like any request; ends Q3TTS_REQ_DONE with
  * n_frames = n and no PCM.  prompt, ids and codes are copied.  Row f of q3tts_fetch_logprobs is the row a recording request that emitted
@@ -364,6 +391,13 @@ int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32
 int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f);   /* [EXT] q3tts_engine_set_output_format on every engine */
 int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
 int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out);
+/* [EXT] codec preambles on every engine under one id, as voices are (create preambles through the group only); _wait waits for all of them */
+int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id);
+int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms);
+int q3tts_group_preamble_release(q3tts_group* g, int32_t preamble_id);
+int q3tts_group_voice_set_preamble(q3tts_group* g, int32_t voice_id, int32_t preamble_id);
+int q3tts_group_set_preamble(q3tts_group* g, int32_t preamble_id);
+int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamble_id);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
 int q3tts_group_stop(q3tts_group* g);
 /* q3tts_comm_*: ONE process per GPU (what `bench.py --gpus N` / torchrun-style launchers use).  Rank 0 makes the 128-byte id and ships it to
@@ -443,6 +477,16 @@ int64_t q3tts_decoder_state_floats(q3tts_decoder* d);
 int q3tts_decoder_state_export(q3tts_decoder* d, int32_t stream, float* out, int64_t n_floats);
 int q3tts_decoder_state_import(q3tts_decoder* d, int32_t stream, const float* in, int64_t n_floats);
 int32_t q3tts_decoder_state_entry(q3tts_decoder* d, int32_t i, const char** name, int64_t* offset, int32_t* rows, int32_t* cols);
+/* [EXT] codec preambles (q3tts_spec.h "codec preambles"): a device-side copy of one stream's whole state -- the history slots of every state
+ * tensor and the two counters -- made and put back by one launch each on the decoder's own HIP stream, in order with its decodes and without
+ * any synchronisation.  _create snapshots `stream` as it stands behind the decodes issued so far; _restore writes a snapshot into any stream
+ * (the stream's next decode continues the snapshotted one bit for bit, other streams are not touched); _free gives the slot back.  A
+ * snapshot outlives resets and decodes of its source stream.  < 0 before anything is launched: a stream or snapshot out of range, a freed
+ * snapshot.  q3tts_decoder_snapshot_bytes: device bytes of one snapshot (the blob without its two counters). */
+int q3tts_decoder_snapshot_create(q3tts_decoder* d, int32_t stream, int32_t* snapshot);
+int q3tts_decoder_snapshot_restore(q3tts_decoder* d, int32_t snapshot, int32_t stream);
+int q3tts_decoder_snapshot_free(q3tts_decoder* d, int32_t snapshot);
+int64_t q3tts_decoder_snapshot_bytes(q3tts_decoder* d);
 
 /* ---- mel front end (device) ---- */
 int q3tts_mel_frames(int32_t n_samples);

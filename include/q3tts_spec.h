@@ -424,6 +424,33 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3_PCM_FILTER_BETA 9.0
 #define Q3_PCM_HIST 96           /* native samples of history per stream */
 
+/* ---------------- codec preambles [EXT] (q3tts_preamble_*, q3tts_decoder_snapshot_*) ----------------
+ * Every request's codec stream starts from a reset.  A preamble is a stream state to start from instead: the state behind frames p[0..m),
+ * [16] codes each -- typically a clone voice's reference codes -- built once, kept on the device and restored per request.
+ * Let c[0..n) be the frames a request emits or is given.
+ *   P1 PCM     the request's native PCM is decode(p ++ c) with the first m * 1920 samples dropped.  decode is one stream from a reset; every
+ *              code is clamped to [0, 2047]; p is cut into 4-frame chunks plus an m % 4 tail, then c as a Chunker cuts it (4-frame chunks,
+ *              then the final flush).  The sample count is that of the unprimed request; tolerance 1e-4 RMS (D1, resume).  RoPE positions
+ *              continue: frame f of the request sits at position m + f, so m + max_steps stays within Q3TTS_CODEC_MAX_FRAMES
+ *   P2 codes   codes, log-probability rows and every other request's codes are bit-identical to the run without a preamble: nothing of
+ *              the talker or the predictor knows about it
+ *   P3 formats a converting request delivers the conversion of preamble_pcm ++ request_pcm with the first m * 1920 * L / M output samples
+ *              dropped: at the restore the stream's converter history holds the preamble's last Q3_PCM_HIST native samples instead of
+ *              zeros.  Counts and tolerances of "output formats" are unchanged
+ *   P4 restore a restore writes the stream's history slots of every state tensor and its two counters (cached positions, frames seen) from
+ *              the snapshot, and nothing else; a state blob exported after a restore equals the blob exported at the snapshot, bit for bit
+ *   resume     the restore comes first, then the prefix frames, then the new ones
+ *   decode     the PCM of a decode-only request is P1 with c = the given frames
+ *   sets       every member of a candidate set restores the same snapshot into its own stream
+ *   cancel     unchanged: the prefix kept is the primed run's prefix
+ *   never      want_pcm = 0 and q3tts_generate_batch* are never primed
+ * A setter takes a READY preamble only, so whether a request is primed never depends on timing and admission waits for nothing new.
+ * At most Q3TTS_MAX_PREAMBLES preambles are live per engine; an id is never reused. */
+#define Q3TTS_MAX_PREAMBLES 64
+#define Q3TTS_PREAMBLE_BUILDING 0
+#define Q3TTS_PREAMBLE_READY 1
+#define Q3TTS_PREAMBLE_FAILED -1
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -277,6 +277,51 @@ int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] codec preambles */
+int q3tts_preamble_create(q3tts_engine* e, const int32_t* codes, int32_t n, int32_t* preamble_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && preamble_id, "null argument");
+    *preamble_id = e->e->preamble_create(codes, n);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_preamble_poll(q3tts_engine* e, int32_t preamble_id, int32_t* state, int32_t* n_frames) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int st = 0, n = 0;
+    e->e->preamble_poll(preamble_id, &st, &n);
+    if (state) *state = st;
+    if (n_frames) *n_frames = n;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_preamble_wait(q3tts_engine* e, int32_t preamble_id, double timeout_ms) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    return e->e->preamble_wait(preamble_id, timeout_ms) ? 0 : 1;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_preamble_release(q3tts_engine* e, int32_t preamble_id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->preamble_release(preamble_id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_voice_set_preamble(q3tts_engine* e, int32_t voice_id, int32_t preamble_id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_voice_preamble(voice_id, preamble_id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_engine_set_preamble(q3tts_engine* e, int32_t preamble_id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_preamble(preamble_id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_preamble(q3tts_engine* e, int64_t req_id, int32_t* preamble_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && preamble_id, "null argument");
+    *preamble_id = e->e->request_preamble(req_id);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_preamble_stats(q3tts_engine* e, int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int64_t b = 0, r = 0, n = 0;
+    e->e->preamble_stats(&b, &r, &n);
+    if (built) *built = b;
+    if (restores) *restores = r;
+    if (bytes_per_snapshot) *bytes_per_snapshot = n;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {
@@ -348,6 +393,7 @@ static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_id
     g.opts = to_opts(opts);
     if (open) trail.pop_back(); // the TEXT_EOS that ends the trail comes with q3tts_text_append(is_last = 1)
     g.trail = trail.data(); g.n_trail = (int)trail.size(); g.open = open;
+    g.preamble = e->e->voice_preamble(voice_id); // [EXT] codec preambles: a text form takes its voice's, never the engine-level setting
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
@@ -562,6 +608,17 @@ int q3tts_decoder_decode(q3tts_decoder* d, int32_t stream, const int64_t* codes,
 int64_t q3tts_decoder_state_floats(q3tts_decoder* d) { return d ? (int64_t)d->d->state_floats() : -1; }
 int q3tts_decoder_state_export(q3tts_decoder* d, int32_t stream, float* out, int64_t n_floats) { Q3_API_BEGIN Q3_CHECK(d && out && n_floats >= 0, "null argument"); d->d->state_export(stream, out, (size_t)n_floats); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_decoder_state_import(q3tts_decoder* d, int32_t stream, const float* in, int64_t n_floats) { Q3_API_BEGIN Q3_CHECK(d && in && n_floats >= 0, "null argument"); d->d->state_import(stream, in, (size_t)n_floats); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+// [EXT] codec preambles: device-side snapshots on the decoder's own HIP stream (ordered with its decodes, no synchronisation)
+int q3tts_decoder_snapshot_create(q3tts_decoder* d, int32_t stream, int32_t* snapshot) {
+    Q3_API_BEGIN
+    Q3_CHECK(d && snapshot, "null argument");
+    *snapshot = d->d->snapshot_async(d->st, stream);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_decoder_snapshot_restore(q3tts_decoder* d, int32_t snapshot, int32_t stream) { Q3_API_BEGIN Q3_CHECK(d, "null argument"); d->d->restore_async(d->st, snapshot, stream); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_decoder_snapshot_free(q3tts_decoder* d, int32_t snapshot) { Q3_API_BEGIN Q3_CHECK(d, "null argument"); d->d->snapshot_free(snapshot); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int64_t q3tts_decoder_snapshot_bytes(q3tts_decoder* d) { return d ? (int64_t)d->d->snapshot_bytes() : -1; }
 /* entry i of the layout: name (valid until the decoder is destroyed), offset in floats, rows x cols; returns the number of entries */
 int32_t q3tts_decoder_state_entry(q3tts_decoder* d, int32_t i, const char** name, int64_t* offset, int32_t* rows, int32_t* cols) {
     if (!d) return -1;

@@ -29,6 +29,18 @@ public:
     int samples_per_frame() const;
     void reset(int stream); // AudioDecoder::create_state (onnx.rs:338-340, 474-495)
     void reset_async(hipStream_t st, int stream); // same, ordered on `st` (call from the thread that issues the decodes)
+    // [EXT] codec preambles (q3tts_spec.h): a device-side copy of one stream's whole state.  snapshot_async copies the stream's history slots
+    // of every state tensor into a free slot of the snapshot store (one k_hist_copy launch per 48 tensors) and notes its two counters;
+    // restore_async copies a snapshot into a stream the same way and sets the stream's counters from it, where reset_async zeroes both.
+    // Both are ordered on `st` and synchronise nothing; a slot's buffer is allocated by the first snapshot that takes it.  pcm_tail (optional,
+    // Q3_PCM_HIST floats of pinned host memory that stay valid until `st` has passed): the stream will be delivered converted and its converter
+    // history starts as these samples.  The caller sees to it that a freed slot's restores have completed before the slot is taken again
+    // on another HIP stream.  All three refuse a stream or snapshot out of range and a freed snapshot before anything is launched
+    int snapshot_async(hipStream_t st, int stream);
+    void restore_async(hipStream_t st, int snapshot, int stream, const float* pcm_tail = nullptr);
+    void snapshot_free(int snapshot);
+    size_t snapshot_bytes() const; // device bytes of one snapshot
+    int snapshots_live() const;
     // codes: host [n_frames][16] (already clamped to [0,2047], engine.rs:515-519); pcm: host, n_frames*spf floats
     int decode(hipStream_t st, int stream, const int64_t* codes, int n_frames, bool is_last, float* pcm);
     // same, but returns right after enqueueing: pcm_pinned must be hipHostMalloc'd and stay valid until `st` is synchronised

@@ -922,6 +922,17 @@ __global__ void k_hist_zero(HistTable tab, int stream) {
     const size_t n = (size_t)e.H * e.C, i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) e.hist[(size_t)stream * n + i] = 0.0f;
 }
+// [EXT] codec preambles: a stream's histories to a snapshot (to_snap) or back, one launch for every convolution as above.  HistDesc::work is
+// the snapshot's copy of the tensor, HistDesc::hist the store; 4 floats per thread (every C is a multiple of 4, so every tensor of every
+// stream and of every snapshot starts on a 16-byte boundary and holds whole float4s)
+__global__ void k_hist_copy(HistTable tab, int stream, int to_snap) {
+    const HistDesc e = tab.d[blockIdx.z];
+    const size_t n = (size_t)e.H * e.C, i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    float* h = e.hist + (size_t)stream * n;
+    if (to_snap) *reinterpret_cast<float4*>(e.work + i) = *reinterpret_cast<const float4*>(h + i);
+    else *reinterpret_cast<float4*>(h + i) = *reinterpret_cast<const float4*>(e.work + i);
+}
 // final conv (cout = 1): one wave per output sample, lanes split the 7*C products (coalesced rows), butterfly sum, clamp
 __global__ void __launch_bounds__(256) k_conv_out_wave(const float* __restrict__ in_ext, int C, const float* __restrict__ w, float bias,
                                                        float* __restrict__ pcm, int n, RowMap im) {
@@ -1012,6 +1023,11 @@ static void launch_hist_zero(hipStream_t st, const HistTable& tab, int stream) {
     for (int i = 0; i < tab.n; i++) mx = std::max(mx, (size_t)tab.d[i].H * tab.d[i].C);
     hipLaunchKernelGGL(k_hist_zero, dim3((unsigned)((mx + 255) / 256), 1, tab.n), dim3(256), 0, st, tab, stream);
 }
+static void launch_hist_copy(hipStream_t st, const HistTable& tab, int stream, bool to_snap) {
+    size_t mx = 0;
+    for (int i = 0; i < tab.n; i++) mx = std::max(mx, (size_t)tab.d[i].H * tab.d[i].C);
+    hipLaunchKernelGGL(k_hist_copy, dim3((unsigned)((mx / 4 + 255) / 256), 1, tab.n), dim3(256), 0, st, tab, stream, to_snap ? 1 : 0);
+}
 // NeoX RoPE tables [n_pos][hd/2] for the absolute frame positions, rounded once from double (the oracle's angles)
 static void rope_tables(int hd, float base, int n_pos, std::vector<float>& c, std::vector<float>& s) {
     const int half = hd / 2;
@@ -1083,6 +1099,36 @@ struct CodecDecoder::Impl {
     // chunk of each stream of a pass, region g at g * T * 4 bytes.  The counters are read by other threads
     std::unique_ptr<PcmConverter> conv; std::vector<DevBuf<float>> pcm_out; size_t pcm_lane_floats = 0;
     std::atomic<int64_t> conv_chunks{0}, conv_samples{0};
+    // [EXT] codec preambles: the snapshot store.  A slot holds one stream's histories back to back in all_ext order (the shape of one stream's
+    // share of the history stores) and the two host counters as they stood when the snapshot was enqueued.  A slot's buffer is allocated by the
+    // first snapshot that takes it, under capture_mutex(), and kept for the next one; snap_mu guards the table (a slot may be freed by
+    // another thread than the one that enqueues)
+    struct Snap { DevBuf<float> buf; int kv_len = 0; long long n_seen = 0; bool live = false; };
+    std::vector<std::unique_ptr<Snap>> snaps; std::mutex snap_mu;
+    size_t hist_floats() const { size_t n = 0; for (const Ext* e : all_ext) n += (size_t)e->H * e->C; return n; }
+    void copy_hist(hipStream_t st, float* snap, int s, bool to_snap) { // at most 48 tensors a launch, flushed as reset_async flushes
+        HistTable tab{};
+        size_t off = 0;
+        auto flush = [&]() {
+            if (tab.n) launch_hist_copy(st, tab, s, to_snap);
+            tab.n = 0;
+        };
+        for (Ext* e : all_ext) {
+            if (!e->H) continue;
+            HistDesc d{}; d.work = snap + off; d.hist = e->hist.p; d.H = e->H; d.C = e->C;
+            off += (size_t)e->H * e->C;
+            tab.d[tab.n++] = d;
+            if (tab.n == 48) flush();
+        }
+        flush();
+    }
+    void ensure_conv() { // the converter's one-time allocation, by the first call that needs it
+        if (conv) return;
+        std::lock_guard<std::mutex> cap(capture_mutex());
+        pcm_out.resize(lanes.size());
+        for (auto& b : pcm_out) b.alloc(pcm_lane_floats);
+        conv.reset(new PcmConverter(n_streams, gmax));
+    }
     size_t in_slot() const { return (size_t)gmax * max_frames * n_q + 3 * (size_t)gmax; }
     double flops_frame = 0;
 
@@ -1431,6 +1477,63 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
+// ---- [EXT] codec preambles (q3tts_spec.h "codec preambles"): device-side snapshots of one stream's state ----
+size_t CodecDecoder::snapshot_bytes() const { return impl_->hist_floats() * sizeof(float); }
+int CodecDecoder::snapshots_live() const {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.snap_mu);
+    int n = 0;
+    for (const auto& s : m.snaps) n += s->live;
+    return n;
+}
+int CodecDecoder::snapshot_async(hipStream_t st, int s) {
+    Impl& m = *impl_;
+    Q3_CHECK(s >= 0 && s < m.n_streams, "stream out of range");
+    for (const Ext* e : m.all_ext) Q3_CHECK(e->C % 4 == 0, "streaming state rows must be a multiple of 4 channels (k_hist_copy moves float4s)");
+    int id = -1;
+    Impl::Snap* sn = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(m.snap_mu);
+        for (size_t i = 0; i < m.snaps.size() && id < 0; i++) if (!m.snaps[i]->live) id = (int)i;
+        if (id < 0) { m.snaps.emplace_back(new Impl::Snap()); id = (int)m.snaps.size() - 1; }
+        sn = m.snaps[(size_t)id].get();
+        sn->live = true; // taken: no other caller picks it while its buffer is being made
+    }
+    if (!sn->buf.n) {
+        try {
+            std::lock_guard<std::mutex> cap(capture_mutex()); // an allocation must not land inside another thread's stream capture
+            sn->buf.alloc(m.hist_floats());
+        } catch (...) { std::lock_guard<std::mutex> lk(m.snap_mu); sn->live = false; throw; }
+    }
+    m.copy_hist(st, sn->buf.p, s, true);
+    sn->kv_len = m.kv_len[s]; sn->n_seen = m.n_seen[s];
+    return id;
+}
+void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* pcm_tail) {
+    Impl& m = *impl_;
+    Q3_CHECK(s >= 0 && s < m.n_streams, "stream out of range");
+    Impl::Snap* sn = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(m.snap_mu);
+        Q3_CHECK(snap >= 0 && snap < (int)m.snaps.size(), "snapshot out of range");
+        sn = m.snaps[(size_t)snap].get();
+        Q3_CHECK(sn->live, "the snapshot has been freed");
+    }
+    m.copy_hist(st, sn->buf.p, s, false);
+    if (pcm_tail) { // the stream is delivered converted: its converter history is the preamble's last Q3_PCM_HIST native samples, not zeros
+        m.ensure_conv();
+        Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
+    }
+    m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
+}
+void CodecDecoder::snapshot_free(int snap) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.snap_mu);
+    Q3_CHECK(snap >= 0 && snap < (int)m.snaps.size(), "snapshot out of range");
+    Q3_CHECK(m.snaps[(size_t)snap]->live, "the snapshot has been freed");
+    m.snaps[(size_t)snap]->live = false; // the buffer stays for the next snapshot that takes the slot
+}
+
 int CodecDecoder::decode(hipStream_t st, int s, const int64_t* codes, int n_frames, bool is_last, float* pcm) {
     const int T = decode_async(st, s, codes, n_frames, is_last, pcm, 0);
     Q3_HIP(hipStreamSynchronize(st));
@@ -1560,12 +1663,7 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
         return T;
     }
     // [EXT] output formats: one convert launch behind the output conv, then every stream's bytes from where its format left them
-    if (!m.conv) {
-        std::lock_guard<std::mutex> cap(capture_mutex());
-        m.pcm_out.resize(m.lanes.size());
-        for (auto& b : m.pcm_out) b.alloc(m.pcm_lane_floats);
-        m.conv.reset(new PcmConverter(m.n_streams, m.gmax));
-    }
+    m.ensure_conv();
     std::vector<int64_t> cnt((size_t)G);
     const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
     launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, fmt, m.pcm_out[lane].p, nullptr, cnt.data());

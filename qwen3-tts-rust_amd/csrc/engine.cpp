@@ -157,6 +157,8 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         for (auto& s2 : st2_) Q3_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
         slot_cap_ = (size_t)p.max_steps * codec_->samples_per_frame();
         Q3_HIP(hipHostMalloc((void**)&pcm_pinned_, (size_t)n_cs * slot_cap_ * sizeof(float)));
+        Q3_HIP(hipHostMalloc((void**)&pre_tails_, (size_t)Q3TTS_MAX_PREAMBLES * Q3_PCM_HIST * sizeof(float))); // [EXT] codec preambles: 24 KB
+        for (int i = Q3TTS_MAX_PREAMBLES - 1; i >= 0; i--) pre_tail_free_.push_back(i);
         for (int c = n_cs - 1; c >= 0; c--) cs_free_.push_back(c);
         decode_w_ = q3::decode_width(n_cs, B); // [EXT] decoding given frames: half of the surplus streams
     }
@@ -202,6 +204,10 @@ struct Engine::Req {
     size_t sample_bytes() const { return fmt.encoding == Q3_PCM_S16 ? 2 : 4; }
     bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
+    // [EXT] codec preambles: the preamble the request is primed with (-1: none; kept for request_preamble after the end), whether it still
+    // holds it, the snapshot and pinned tail its `reset` task restores (fixed at submit: the preamble was READY); build_pre: this is the hidden
+    // decode-only request that builds that preamble, and build_snap the snapshot the decoder thread enqueued at its fence
+    int pre = -1; bool pre_held = false; int pre_snap = -1; const float* pre_tail = nullptr; int build_pre = -1, build_snap = -1;
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
     size_t pcm_ready = 0; // samples whose decode has completed (harvested events)
@@ -227,6 +233,7 @@ Engine::~Engine() {
         if (g.second->graph) (void)hipGraphDestroy(g.second->graph);
     }
     if (pcm_pinned_) (void)hipHostFree(pcm_pinned_);
+    if (pre_tails_) (void)hipHostFree(pre_tails_);
     if (arena_) (void)hipHostFree(arena_);
     if (arena_pf_) (void)hipHostFree(arena_pf_);
     if (pf_done_) (void)hipEventDestroy(pf_done_);
@@ -548,7 +555,12 @@ void Engine::decoder_main() {
                 auto it = last.find(t.r);
                 if (it != last.end() && it->second.first != lane) Q3_HIP(hipStreamWaitEvent(st2_[lane], it->second.second, 0));
             }
-            if (grp[0].reset) codec_->reset_async(st2_[lane], grp[0].r->cs); // AudioDecoder::create_state for a new request
+            if (grp[0].reset && grp[0].r->pre_snap >= 0) { // [EXT] codec preambles: the stream starts from the snapshot; a converting one also from the preamble's tail
+                Req* r = grp[0].r;
+                codec_->restore_async(st2_[lane], r->pre_snap, r->cs, pcm_format_native(r->fmt) ? nullptr : r->pre_tail);
+                pre_restores_++;
+            }
+            else if (grp[0].reset) codec_->reset_async(st2_[lane], grp[0].r->cs); // AudioDecoder::create_state for a new request
             else if (!grp[0].fence) {
                 const int nf = (int)grp[0].codes.size() / 16;
                 std::vector<int> streams(G);
@@ -570,6 +582,8 @@ void Engine::decoder_main() {
                                                            converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr);
                 for (int g = 0; g < G; g++) grp[g].r->pcm_enq += converts ? (size_t)n_out[g] : (size_t)std::max(got, 0);
             }
+            // [EXT] codec preambles: a build's fence enqueues the snapshot behind its last chunk (this lane has waited for it above)
+            if (grp[0].fence && grp[0].r->build_pre >= 0 && !grp[0].r->cancel) grp[0].r->build_snap = codec_->snapshot_async(st2_[lane], grp[0].r->cs);
             for (auto& t : grp) {
                 hipEvent_t ev = nullptr;
                 if (!t.reset) {
@@ -634,6 +648,22 @@ void Engine::harvest(bool block) {
             r->state = fenced_state(r->cancel); r->t_done = now_ms();
             n_draining_--;
             if (r->decode) n_decoding_--;
+            pre_drop(r); // [EXT] codec preambles: the restore this request enqueued has completed
+            if (r->build_pre >= 0) { // the preamble is built: its snapshot is on the device, its last native samples become its tail
+                auto it = pres_.find(r->build_pre);
+                if (it != pres_.end()) {
+                    Preamble& p = it->second;
+                    p.snap = r->build_snap;
+                    if (p.snap >= 0 && r->pcm.size() >= (size_t)Q3_PCM_HIST) {
+                        std::copy(r->pcm.end() - Q3_PCM_HIST, r->pcm.end(), pre_tails_ + (size_t)p.tail * Q3_PCM_HIST);
+                        p.refs.state = Q3TTS_PREAMBLE_READY; pre_built_++;
+                    } else p.refs.state = Q3TTS_PREAMBLE_FAILED;
+                    const int pid = it->first;
+                    p.refs.holders++; pre_unhold(pid); // recycles at once when it was released while it built
+                }
+                if (r->ev_admit) (void)hipEventDestroy(r->ev_admit);
+                reqs_.erase(r->id); // the build request is nobody's to release
+            }
             cv_.notify_all();
         }
         block = false; // after one blocking wait, drain whatever else is ready
@@ -730,6 +760,9 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     r->seed = g.sampler.has_seed ? g.sampler.seed
                                  : (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count(); // :473-478
     std::lock_guard<std::mutex> lk(mu_);
+    // [EXT] codec preambles: the engine-level setting or the caller's (a voice's), read once per request; a blocking batch is never primed
+    const int pid = preamble_of_request(r->want_pcm && may_record, g.preamble, eng_pre_);
+    if (pid >= 0) pre_attach(r.get(), pid); // throws before anything is queued
     r->id = next_id_++;
     Req* raw = r.get();
     reqs_[raw->id] = std::move(r);
@@ -767,6 +800,10 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         rs.push_back(std::move(r));
     }
     std::lock_guard<std::mutex> lk(mu_);
+    {   // [EXT] codec preambles: the engine-level setting, read once per set; every member restores the same snapshot into its own stream
+        const int pid = preamble_of_request(want_pcm && codec_, g.preamble, eng_pre_);
+        for (int i = 0; pid >= 0 && i < n; i++) pre_attach(rs[i].get(), pid);
+    }
     const int64_t set = next_set_++;
     for (int i = 0; i < n; i++) {
         Req* raw = rs[i].get();
@@ -846,6 +883,7 @@ int Engine::cancel(int64_t id) {
         std::deque<Req*>& q = r.decode ? decode_q_ : pending_;
         q.erase(std::find(q.begin(), q.end(), &r));
         r.state = REQ_CANCELLED; r.t_done = now_ms();
+        pre_drop(&r); // [EXT] codec preambles: it never enqueued a restore
     } else cancel_ids_.push_back(id);
     wake_++;
     cv_.notify_all();
@@ -968,6 +1006,7 @@ int64_t Engine::submit_decode(const int32_t* codes, int n) {
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
     r->t_submit = now_ms();
     std::lock_guard<std::mutex> lk(mu_);
+    if (eng_pre_ >= 0) pre_attach(r.get(), eng_pre_); // [EXT] codec preambles: the engine-level setting, read once per request
     r->id = next_id_++;
     Req* raw = r.get();
     reqs_[raw->id] = std::move(r);
@@ -1510,6 +1549,119 @@ void Engine::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) cons
     if (codec_) codec_->pcm_out_stats(chunks_converted, samples_out);
 }
 
+// [EXT] codec preambles (q3tts_spec.h "codec preambles")
+void Engine::pre_attach(Req* r, int pid) {
+    auto it = pres_.find(pid);
+    Q3_CHECK(it != pres_.end() && it->second.refs.state == Q3TTS_PREAMBLE_READY, "the request's preamble is not ready");
+    Preamble& p = it->second;
+    p.refs.holders++;
+    r->pre = pid; r->pre_held = true; r->pre_snap = p.snap; r->pre_tail = pre_tails_ + (size_t)p.tail * Q3_PCM_HIST;
+}
+void Engine::pre_drop(Req* r) {
+    if (!r->pre_held) return;
+    r->pre_held = false;
+    pre_unhold(r->pre);
+}
+void Engine::pre_unhold(int pid) {
+    auto it = pres_.find(pid);
+    if (it == pres_.end()) return;
+    Preamble& p = it->second;
+    p.refs.holders--;
+    if (!preamble_recyclable(p.refs)) return;
+    if (p.snap >= 0) codec_->snapshot_free(p.snap); // host bookkeeping only: every restore enqueued from it has completed
+    pre_tail_free_.push_back(p.tail);
+    pres_.erase(it);
+}
+int Engine::preamble_create(const int32_t* codes, int n) {
+    std::unique_ptr<Req> r(new Req());
+    int live = 0;
+    { std::lock_guard<std::mutex> lk(mu_); live = (int)pres_.size(); }
+    if (const char* why = preamble_refusal(codes, n, p_.max_steps, codec_ != nullptr, live, Q3TTS_CODEC_MAX_FRAMES)) throw Error(why);
+    r->decode = true; r->want_pcm = true; // native format: the tail is taken from the staging region's floats
+    r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
+    r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
+    r->t_submit = now_ms();
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK((int)pres_.size() < Q3TTS_MAX_PREAMBLES && !pre_tail_free_.empty(), "Q3TTS_MAX_PREAMBLES preambles are live: release one first");
+    const int pid = next_pre_++;
+    Preamble& p = pres_[pid];
+    p.n = n; p.tail = pre_tail_free_.back(); pre_tail_free_.pop_back();
+    r->build_pre = pid;
+    r->id = next_id_++;
+    Req* raw = r.get();
+    reqs_[raw->id] = std::move(r);
+    decode_q_.push_back(raw);
+    wake_++;
+    cv_.notify_all();
+    return pid;
+}
+void Engine::preamble_poll(int id, int* state, int* n_frames) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = pres_.find(id);
+    Q3_CHECK(it != pres_.end(), "unknown preamble id");
+    *state = it->second.refs.state; *n_frames = it->second.n;
+}
+bool Engine::preamble_wait(int id, double timeout_ms) {
+    const double t0 = now_ms();
+    for (;;) {
+        {
+            std::unique_lock<std::mutex> lk(mu_);
+            auto it = pres_.find(id);
+            Q3_CHECK(it != pres_.end(), "unknown preamble id");
+            if (it->second.refs.state != Q3TTS_PREAMBLE_BUILDING) return true;
+            if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
+            if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
+        }
+        step();
+    }
+}
+void Engine::preamble_release(int id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = pres_.find(id);
+    Q3_CHECK(it != pres_.end(), "unknown preamble id");
+    Q3_CHECK(it->second.refs.creator, "the preamble has already been released");
+    it->second.refs.creator = false;
+    it->second.refs.holders++; pre_unhold(id); // recycles when nobody else holds it
+}
+void Engine::set_voice_preamble(int voice_id, int preamble_id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
+    if (preamble_id >= 0) {
+        auto it = pres_.find(preamble_id);
+        if (const char* why = preamble_set_refusal(it != pres_.end(), it != pres_.end() ? it->second.refs.state : 0)) throw Error(why);
+        it->second.refs.holders++;
+    } else Q3_CHECK(preamble_id == -1, "preamble id must be -1 (none) or a preamble's id");
+    const int old = voices_[(size_t)voice_id].preamble;
+    voices_[(size_t)voice_id].preamble = preamble_id;
+    if (old >= 0) pre_unhold(old);
+}
+int Engine::voice_preamble(int voice_id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
+    return voices_[(size_t)voice_id].preamble;
+}
+void Engine::set_preamble(int preamble_id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (preamble_id >= 0) {
+        auto it = pres_.find(preamble_id);
+        if (const char* why = preamble_set_refusal(it != pres_.end(), it != pres_.end() ? it->second.refs.state : 0)) throw Error(why);
+        it->second.refs.holders++;
+    } else Q3_CHECK(preamble_id == -1, "preamble id must be -1 (none) or a preamble's id");
+    const int old = eng_pre_;
+    eng_pre_ = preamble_id;
+    if (old >= 0) pre_unhold(old);
+}
+int Engine::request_preamble(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    return it->second->pre;
+}
+void Engine::preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot) const {
+    *built = pre_built_.load(); *restores = pre_restores_.load();
+    *bytes_per_snapshot = codec_ ? (int64_t)codec_->snapshot_bytes() : 0;
+}
+
 void Engine::fetch_logprobs(int64_t id, float* out, int frame_off, int max_frames, int* got_frames) {
     std::lock_guard<std::mutex> lk(mu_);
     auto it = reqs_.find(id);
@@ -1571,6 +1723,7 @@ void Engine::start_driver() {
         } catch (const std::exception& ex) {
             std::lock_guard<std::mutex> lk(mu_);
             for (auto& kv : reqs_) if (kv.second->state != REQ_DONE && kv.second->state != REQ_CANCELLED) { kv.second->state = REQ_FAILED; kv.second->error = ex.what(); }
+            for (auto& kv : pres_) if (kv.second.refs.state == Q3TTS_PREAMBLE_BUILDING) kv.second.refs.state = Q3TTS_PREAMBLE_FAILED; // [EXT] nothing builds them any more
             cv_.notify_all();
         }
     });

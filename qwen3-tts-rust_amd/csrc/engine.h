@@ -56,6 +56,7 @@ struct ReqStatus {
 
 struct Voice { // a registered voice: preset embedding or clone material (engine.rs:390-435, voice_file.rs:5-22)
     std::vector<float> spk_emb; std::vector<int32_t> ref_codes, ref_text_ids;
+    int preamble = -1; // [EXT] codec preambles: what requests of the text forms with this voice are primed with (mu_)
 };
 
 
@@ -113,6 +114,21 @@ public:
     q3tts_pcm_format request_format(int64_t id);
     void fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
     void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks converted, output samples made
+    // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
+    // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
+    // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The
+    // setters take a READY preamble only (preamble_set_refusal).  submit() / submit_candidates() / submit_decode() read the engine-level
+    // setting once per request / set; a request with PCM holds a reference from submit to its end, and the `reset` task of a primed request
+    // restores the snapshot (and, when it converts, uploads the preamble's last Q3_PCM_HIST samples) where it zeroed the stream
+    int preamble_create(const int32_t* codes, int n);
+    void preamble_poll(int id, int* state, int* n_frames);
+    bool preamble_wait(int id, double timeout_ms); // true once READY or FAILED; drives step() itself when no driver thread is running
+    void preamble_release(int id);                 // the creator's reference
+    void set_voice_preamble(int voice_id, int preamble_id); // -1: none
+    int voice_preamble(int voice_id);
+    void set_preamble(int preamble_id);                     // -1: none
+    int request_preamble(int64_t id);
+    void preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot) const;
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -261,6 +277,15 @@ private:
     std::deque<Req*> decode_q_; int n_decoding_ = 0, decode_w_ = 0;
     std::vector<Req*> dec_admitted_;    // admitted in this step, tasks not yet enqueued (scheduler thread only)
     std::atomic<int64_t> dec_reqs_{0}, dec_chunks_{0}, dec_shared_{0};
+    // [EXT] codec preambles (all under mu_): the live preambles by id, the next id (never reused), the engine-level setting, the pinned
+    // tails ([Q3TTS_MAX_PREAMBLES][Q3_PCM_HIST] floats, allocated with the codec's staging) and their free entries, the counters
+    struct Preamble { PreambleRefs refs; int n = 0, snap = -1, tail = -1; };
+    std::map<int, Preamble> pres_; int next_pre_ = 0, eng_pre_ = -1;
+    float* pre_tails_ = nullptr; std::vector<int> pre_tail_free_;
+    std::atomic<int64_t> pre_built_{0}, pre_restores_{0};
+    void pre_attach(Req* r, int pid);   // r is primed with READY preamble pid and holds it (mu_ held)
+    void pre_drop(Req* r);              // r has ended (mu_ held)
+    void pre_unhold(int pid);           // one holder less; recycles the snapshot's slot when nobody is left (mu_ held)
     bool trail_dirty_ = false;          // an append arrived since the scheduler last looked (mu_)
     std::vector<int64_t> cancel_ids_;   // cancelled requests the scheduler has not dealt with yet (mu_)
     uint64_t wake_ = 0;                 // bumped by every submit / append / cancel: a driver idling on stalled slots sleeps until it changes (mu_)

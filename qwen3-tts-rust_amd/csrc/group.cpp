@@ -434,6 +434,68 @@ int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format*
     if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
     return q3tts_request_format(e, rid_of(req_id), out);
 }
+// [EXT] codec preambles: built on every engine under one id, as voices are.  The engines of a group are alike and hand out ids in order, so
+// what the first engine accepts the others accept under the same id; a preamble created on one engine behind the group's back breaks that
+int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && preamble_id, "null argument");
+    int32_t pid = -1;
+    for (size_t i = 0; i < g->eng.size(); i++) {
+        int32_t id = -1;
+        if (q3tts_preamble_create(g->eng[i], codes, n, &id) != Q3TTS_OK) {
+            const std::string why = last_error();
+            for (size_t k = 0; k < i; k++) (void)q3tts_preamble_release(g->eng[k], pid); // all engines or none
+            throw Error(why);
+        }
+        if (i == 0) pid = id;
+        Q3_CHECK(id == pid, "engines of a group must hand out the same preamble ids (create preambles through the group only)");
+    }
+    *preamble_id = pid;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms) { // 0 once every engine's copy is READY or FAILED, 1 on timeout
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    int worst = 0;
+    for (auto* e : g->eng) {
+        const int rc = q3tts_preamble_wait(e, preamble_id, timeout_ms);
+        if (rc < 0) return rc;
+        worst = std::max(worst, rc);
+    }
+    return worst;
+}
+int q3tts_group_preamble_release(q3tts_group* g, int32_t preamble_id) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    int rc = Q3TTS_OK;
+    for (auto* e : g->eng) if (q3tts_preamble_release(e, preamble_id) != Q3TTS_OK) rc = Q3TTS_ERR;
+    return rc;
+}
+static int group_preamble_ready(q3tts_group* g, int32_t preamble_id) { // a setter takes a preamble that is READY on every engine: all engines or none
+    if (preamble_id < 0) return Q3TTS_OK;
+    for (auto* e : g->eng) {
+        int32_t st = 0;
+        if (q3tts_preamble_poll(e, preamble_id, &st, nullptr) != Q3TTS_OK) return Q3TTS_ERR;
+        if (const char* why = preamble_set_refusal(true, st)) { set_last_error(why); return Q3TTS_ERR; }
+    }
+    return Q3TTS_OK;
+}
+int q3tts_group_voice_set_preamble(q3tts_group* g, int32_t voice_id, int32_t preamble_id) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    if (group_preamble_ready(g, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
+    for (auto* e : g->eng) if (q3tts_voice_set_preamble(e, voice_id, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_set_preamble(q3tts_group* g, int32_t preamble_id) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    if (group_preamble_ready(g, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
+    for (auto* e : g->eng) if (q3tts_engine_set_preamble(e, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamble_id) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_request_preamble(e, rid_of(req_id), preamble_id);
+}
 int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
     if (!g) return Q3TTS_ERR;
     for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;

@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set and of a decode-only request, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, and the rules of the output formats.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request and of a codec preamble (with who holds one), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, and the rules of the output formats.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -38,6 +38,9 @@ struct GenRequest {
     const int32_t* prefix = nullptr; int n_prefix = 0;
     // [EXT] token log-probabilities (q3tts_spec.h): the request records 17 floats per frame; set by Engine::submit from the engine's flag
     bool logprobs = false;
+    // [EXT] codec preambles (q3tts_spec.h): -2 the engine-level setting (the raw-prompt forms), -1 none, else that preamble (a text form
+    // passes its voice's); resolved by Engine::submit, which never primes a request without PCM
+    int preamble = -2;
 };
 
 // Which launches one frame step issues: some live slot samples the talker / has a repetition penalty / samples the predictor / has trailing text
@@ -223,6 +226,34 @@ inline const char* decode_refusal(const int32_t* codes, int n, int max_steps, bo
     if (!codes) return "codes missing";
     return resume_refusal(1, n + 1, codes, n, false, 0, (int64_t)n + 2); // the ranges alone: its own limits are out of the way
 }
+// [EXT] codec preambles (q3tts_spec.h "codec preambles"): why a preamble of n frames is refused, or null.  Pure, like the four above.  A preamble
+// is built like a decode-only request, so decode_refusal's reasons come first; live = preambles the engine holds now (building ones included).
+// Frame f of a primed request sits at RoPE position n + f, so n + max_steps must stay within the codec's positions.
+inline const char* preamble_refusal(const int32_t* codes, int n, int max_steps, bool have_codec, int live, int64_t max_positions) {
+    if (const char* why = decode_refusal(codes, n, max_steps, have_codec)) return why;
+    if (live >= Q3TTS_MAX_PREAMBLES) return "Q3TTS_MAX_PREAMBLES preambles are live: release one first";
+    if ((int64_t)n + max_steps > max_positions) return "n + max_steps exceeds the codec's frame positions";
+    return nullptr;
+}
+// Who holds a preamble: its creator until q3tts_preamble_release, and `holders` = the voices it is set on, the engine-level setting, and the
+// requests submitted with it that have not ended (a request with PCM ends behind its fence, so every restore it enqueued has completed).
+struct PreambleRefs { bool creator = true; int holders = 0; int state = Q3TTS_PREAMBLE_BUILDING; };
+// the snapshot's slot goes back only when nobody holds the preamble and its build has ended (a building preamble's stream is still decoding)
+inline bool preamble_recyclable(const PreambleRefs& p) { return !p.creator && p.holders == 0 && p.state != Q3TTS_PREAMBLE_BUILDING; }
+// what a setter (voice or engine level) refuses, or null: it takes a READY preamble only, so "primed or not" never depends on timing
+inline const char* preamble_set_refusal(bool known, int state) {
+    if (!known) return "unknown preamble id";
+    if (state == Q3TTS_PREAMBLE_BUILDING) return "the preamble is still building: wait for it (q3tts_preamble_wait)";
+    if (state != Q3TTS_PREAMBLE_READY) return "the preamble failed to build";
+    return nullptr;
+}
+// the preamble a request is primed with: never without PCM; a text form takes its voice's, a raw-prompt form the engine-level setting
+enum { PREAMBLE_NONE = -1, PREAMBLE_ENGINE = -2 };
+inline int preamble_of_request(bool want_pcm, int asked, int engine_level) {
+    if (!want_pcm) return PREAMBLE_NONE;
+    return asked == PREAMBLE_ENGINE ? engine_level : asked;
+}
+
 // Decode-only requests that may hold a codec stream at once: half of the streams the engine keeps beyond one per slot (those serve
 // requests whose slot is already reused while their last chunks drain), and how many of the queued ones a scheduler step admits after
 // the generating wave has taken its streams.

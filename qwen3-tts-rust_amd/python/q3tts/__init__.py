@@ -100,6 +100,11 @@ SYMBOLS = [
     "q3tts_engine_set_output_format", "q3tts_request_format", "q3tts_fetch_pcm16", "q3tts_engine_pcm_out_stats",
     "q3tts_group_set_output_format", "q3tts_group_fetch_pcm16", "q3tts_group_request_format",
     "q3tts_pcm_out_plan", "q3tts_pcm_out_filter", "q3tts_pcm_out_samples", "q3tts_pcm_format_check", "q3tts_op_pcm_convert",
+    "q3tts_decoder_snapshot_create", "q3tts_decoder_snapshot_restore", "q3tts_decoder_snapshot_free", "q3tts_decoder_snapshot_bytes",
+    "q3tts_preamble_create", "q3tts_preamble_poll", "q3tts_preamble_wait", "q3tts_preamble_release", "q3tts_voice_set_preamble",
+    "q3tts_engine_set_preamble", "q3tts_request_preamble", "q3tts_engine_preamble_stats",
+    "q3tts_group_preamble_create", "q3tts_group_preamble_wait", "q3tts_group_preamble_release", "q3tts_group_voice_set_preamble",
+    "q3tts_group_set_preamble", "q3tts_group_request_preamble",
 ]
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
@@ -109,6 +114,8 @@ class PcmFormat(C.Structure):  # q3tts_pcm_format
 PCM_F32, PCM_S16 = 0, 1                                                  # q3tts_pcm_format.encoding
 PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)      # q3tts_spec.h "output formats"
 PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
+MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
+PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
 LOGPROB_NONE = 1.0    # Q3TTS_LOGPROB_NONE: not computed (a real value is never positive)
 
@@ -248,6 +255,25 @@ def lib():
         L.q3tts_group_set_output_format.argtypes = L.q3tts_engine_set_output_format.argtypes
         L.q3tts_group_fetch_pcm16.argtypes = L.q3tts_fetch_pcm16.argtypes
         L.q3tts_group_request_format.argtypes = L.q3tts_request_format.argtypes
+        L.q3tts_decoder_snapshot_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.q3tts_decoder_snapshot_restore.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.q3tts_decoder_snapshot_free.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_decoder_snapshot_bytes.argtypes = [C.c_void_p]
+        L.q3tts_decoder_snapshot_bytes.restype = C.c_int64
+        L.q3tts_preamble_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.q3tts_preamble_poll.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.q3tts_preamble_wait.argtypes = [C.c_void_p, C.c_int32, C.c_double]
+        L.q3tts_preamble_release.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_voice_set_preamble.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.q3tts_engine_set_preamble.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_request_preamble.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.q3tts_engine_preamble_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.q3tts_group_preamble_create.argtypes = L.q3tts_preamble_create.argtypes
+        L.q3tts_group_preamble_wait.argtypes = L.q3tts_preamble_wait.argtypes
+        L.q3tts_group_preamble_release.argtypes = L.q3tts_preamble_release.argtypes
+        L.q3tts_group_voice_set_preamble.argtypes = L.q3tts_voice_set_preamble.argtypes
+        L.q3tts_group_set_preamble.argtypes = L.q3tts_engine_set_preamble.argtypes
+        L.q3tts_group_request_preamble.argtypes = L.q3tts_request_preamble.argtypes
         L.q3tts_pcm_out_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
         L.q3tts_pcm_out_filter.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
         L.q3tts_pcm_out_filter.restype = C.c_int64
@@ -506,6 +532,55 @@ def group_fetch_pcm16(group, rid, off=0, cap=0):
     return _fetch_pcm16(lib().q3tts_group_fetch_pcm16, group, rid, off, cap)
 
 
+def _preamble_create(fn, h, codes):
+    c = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
+    pid = C.c_int32()
+    _chk(fn(h, _p(c) if c.size else None, c.shape[0], C.byref(pid)))
+    return pid.value
+
+
+def _preamble_wait(fn, h, pid, timeout_ms):
+    rc = fn(h, pid, timeout_ms)
+    if rc < 0:
+        _chk(rc)
+    return rc == 0
+
+
+def _request_preamble(fn, h, rid):
+    pid = C.c_int32()
+    _chk(fn(h, rid, C.byref(pid)))
+    return pid.value
+
+
+def group_preamble_create(group, codes):
+    """[EXT] q3tts_group_preamble_create on a q3tts_group handle: the preamble of codes [n][16] on every engine, under one id"""
+    return _preamble_create(lib().q3tts_group_preamble_create, group, codes)
+
+
+def group_preamble_wait(group, pid, timeout_ms=-1.0):
+    """[EXT] q3tts_group_preamble_wait: True once every engine's copy is READY or FAILED"""
+    return _preamble_wait(lib().q3tts_group_preamble_wait, group, pid, timeout_ms)
+
+
+def group_preamble_release(group, pid):
+    _chk(lib().q3tts_group_preamble_release(group, pid))
+
+
+def group_voice_set_preamble(group, voice_id, pid):
+    """[EXT] q3tts_group_voice_set_preamble (pid None or -1: none)"""
+    _chk(lib().q3tts_group_voice_set_preamble(group, voice_id, -1 if pid is None else pid))
+
+
+def group_set_preamble(group, pid):
+    """[EXT] q3tts_group_set_preamble on every engine (pid None or -1: none)"""
+    _chk(lib().q3tts_group_set_preamble(group, -1 if pid is None else pid))
+
+
+def group_request_preamble(group, rid):
+    """[EXT] q3tts_group_request_preamble: the preamble a group request was primed with, -1 when none"""
+    return _request_preamble(lib().q3tts_group_request_preamble, group, rid)
+
+
 class Sampler:  # LlamaSampler (llama/mod.rs:627-776)
     def __init__(self, temperature=0.0, top_k=0, top_p=1.0, seed=42):
         self.h = lib().q3tts_sampler_new(temperature, top_k, top_p, seed)
@@ -558,6 +633,7 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         _chk(lib().q3tts_engine_create(C.byref(p), C.byref(h)))
         self.h = h.value
         self.max_steps = max_steps
+        self._voice_ref = {}   # voice id -> its reference codes [n][16] (prime_voice)
         self.assets = Assets(handle=lib().q3tts_engine_assets(self.h))
 
     def close(self):
@@ -670,7 +746,60 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         vid = C.c_int32()
         _chk(lib().q3tts_voice_register(self.h, _p(spk), _p(rc), rc.size if rc is not None else 0, _p(rt), rt.size if rt is not None else 0,
                                         C.byref(vid)))
+        if rc is not None and rc.size:
+            self._voice_ref[vid.value] = rc.reshape(-1, 16).copy()
         return vid.value
+
+    # ---- [EXT] codec preambles (q3tts_spec.h "codec preambles") ----
+    def preamble_create(self, codes):
+        """q3tts_preamble_create: queues the build of the codec state behind codes [n][16]; returns the preamble id (BUILDING)"""
+        return _preamble_create(lib().q3tts_preamble_create, self.h, codes)
+
+    def preamble_poll(self, pid):
+        """(state, n_frames): PREAMBLE_BUILDING / _READY / _FAILED"""
+        st, n = C.c_int32(), C.c_int32()
+        _chk(lib().q3tts_preamble_poll(self.h, pid, C.byref(st), C.byref(n)))
+        return st.value, n.value
+
+    def preamble_wait(self, pid, timeout_ms=-1.0):
+        """True once the preamble is READY or FAILED; drives the scheduler itself when no driver thread runs"""
+        return _preamble_wait(lib().q3tts_preamble_wait, self.h, pid, timeout_ms)
+
+    def preamble_release(self, pid):
+        """the creator's reference goes; voices, the engine-level setting and submitted requests hold their own"""
+        _chk(lib().q3tts_preamble_release(self.h, pid))
+
+    def voice_set_preamble(self, voice_id, pid):
+        """requests of the text forms with this voice and want_pcm are primed with READY preamble pid (None or -1: none)"""
+        _chk(lib().q3tts_voice_set_preamble(self.h, voice_id, -1 if pid is None else pid))
+
+    def set_preamble(self, pid):
+        """requests of the raw-prompt forms (submit, candidates, decode) submitted from now on with want_pcm are primed (None or -1: none)"""
+        _chk(lib().q3tts_engine_set_preamble(self.h, -1 if pid is None else pid))
+
+    def request_preamble(self, rid):
+        """the preamble the request was primed with, -1 when none"""
+        return _request_preamble(lib().q3tts_request_preamble, self.h, rid)
+
+    def preamble_stats(self):
+        """q3tts_engine_preamble_stats: dict(built, restores, bytes_per_snapshot)"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_preamble_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(built=a.value, restores=b.value, bytes_per_snapshot=c.value)
+
+    def prime_voice(self, voice_id, timeout_ms=-1.0):
+        """create -> wait -> set from the clone voice's own reference codes; the voice then holds the preamble (the creator's reference is
+        released).  Returns the preamble id"""
+        if voice_id not in self._voice_ref:
+            raise Q3Error("voice %d has no reference codes to prime from (a preset voice)" % voice_id)
+        pid = self.preamble_create(self._voice_ref[voice_id])
+        try:
+            if not self.preamble_wait(pid, timeout_ms) or self.preamble_poll(pid)[0] != PREAMBLE_READY:
+                raise Q3Error("the preamble of voice %d did not become ready" % voice_id)
+            self.voice_set_preamble(voice_id, pid)
+        finally:
+            self.preamble_release(pid)
+        return pid
 
     def submit_text(self, voice_id, text_ids, lang_id=2055, instr_ids=None, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, seed=42,
                     mask_eos=True, want_pcm=False, repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0,
@@ -921,6 +1050,21 @@ class Decoder:  # AudioDecoder (onnx.rs:324-496)
         _chk(lib().q3tts_decoder_decode(self.h, stream, _p(codes), codes.shape[0], 1 if is_last else 0, _p(wav), C.byref(valid)))
         return wav[: valid.value]
 
+
+    # ---- [EXT] codec preambles: device-side snapshots of a stream's state (q3tts_decoder_snapshot_*) ----
+    def snapshot_create(self, stream=0):
+        s = C.c_int32()
+        _chk(lib().q3tts_decoder_snapshot_create(self.h, stream, C.byref(s)))
+        return s.value
+
+    def snapshot_restore(self, snapshot, stream=0):
+        _chk(lib().q3tts_decoder_snapshot_restore(self.h, snapshot, stream))
+
+    def snapshot_free(self, snapshot):
+        _chk(lib().q3tts_decoder_snapshot_free(self.h, snapshot))
+
+    def snapshot_bytes(self):
+        return int(lib().q3tts_decoder_snapshot_bytes(self.h))
 
     def state_export(self, stream=0):
         L = lib()
