@@ -208,6 +208,25 @@ int q3tts_engine_set_output_format(q3tts_engine* e, const q3tts_pcm_format* f);
 int q3tts_request_format(q3tts_engine* e, int64_t req_id, q3tts_pcm_format* out);
 int q3tts_fetch_pcm16(q3tts_engine* e, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
 int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64_t* samples_out);
+/* [EXT] speaking rate (q3tts_spec.h "speaking rate"): a pitch-preserving time-scale change (WSOLA) of a request's PCM on the device, behind
+ * the codec, before it crosses to the host.  Opt-in per request; an ordinary request keeps its launches and its bytes, and the codes and
+ * log-probability rows of a request do not depend on its rate.
+ * q3tts_engine_set_speech_rate: requests submitted from now on, through any q3tts_submit* form with want_pcm (text, trailing, open, resume,
+ * candidates, decode), are spoken at rate_pct percent of the native tempo, an integer in [50, 200]; 100 = off.  Read once per request at submit
+ * and once per candidate set.  Thread-safe; works under Q3_SPEC=ggml.  < 0: out of range, or an engine without a codec.
+ * A request with a rate other than 100 delivers 24000 Hz, f32 or s16 (q3tts_engine_set_output_format), and
+ * q3tts_tsm_samples(rate, max_steps * 1920, 1) samples of its encoding must fit the engine's staging for one request, max_steps(engine) * 1920
+ * * 4 bytes: slowing down makes more samples than native.  Otherwise the submit fails and nothing is queued.
+ * While it runs, N native samples have delivered q3tts_tsm_samples(rate, N, 0) samples; at its end the stretcher is flushed and a request of n
+ * frames delivers q3tts_tsm_samples(rate, n * 1920, 1).  A cancelled request keeps the whole hops it has and is not flushed.
+ * q3tts_poll's n_pcm and every offset, capacity and count of the fetch calls are in delivered samples.
+ * Not stretched: want_pcm = 0, q3tts_generate_batch*, scoring, preamble builds.  A primed request's stretcher starts from a reset.
+ * q3tts_request_speech_rate: the rate a request was submitted with (100 when none was set).
+ * q3tts_engine_tsm_stats: stream chunks the stretcher has taken, synthesis frames (480 samples each) it has made, and flushes (all 0 while no
+ * request had a rate). */
+int q3tts_engine_set_speech_rate(q3tts_engine* e, int32_t rate_pct);
+int q3tts_request_speech_rate(q3tts_engine* e, int64_t req_id, int32_t* rate_pct);
+int q3tts_engine_tsm_stats(q3tts_engine* e, int64_t* chunks, int64_t* frames_out, int64_t* flushes);
 /* [EXT] codec preambles (q3tts_spec.h "codec preambles"): a request's codec stream starts from the state behind given frames -- a clone
  * voice's reference codes -- instead of zeros, so its first sample is already "in the voice".  The state is built once per preamble and
  * kept on the device; a primed request restores it with one device-to-device launch where the zeroing launch ran.  Opt-in; codes,
@@ -391,6 +410,8 @@ int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32
 int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f);   /* [EXT] q3tts_engine_set_output_format on every engine */
 int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
 int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out);
+int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct);   /* [EXT] q3tts_engine_set_speech_rate on every engine */
+int q3tts_group_request_speech_rate(q3tts_group* g, int64_t req_id, int32_t* rate_pct);
 /* [EXT] codec preambles on every engine under one id, as voices are (create preambles through the group only); _wait waits for all of them */
 int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id);
 int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms);
@@ -875,6 +896,30 @@ int q3tts_pcm_format_check(const q3tts_pcm_format* f);
 int q3tts_op_pcm_convert(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
                          const q3tts_pcm_format* fmt, const int32_t* reset_before, void* const* out, const int64_t* out_bytes, int64_t* n_out,
                          float* hist_store);
+
+/* [EXT] speaking rate (q3tts_spec.h "speaking rate"): the WSOLA stretcher on the device, behind the codec.
+ * Host only, no device needed:
+ *   q3tts_tsm_samples  samples delivered for n_native native samples from a stream's reset: 480 * #{k : a_k + 1200 <= n_native} while
+ *                      streaming (final = 0), 480 * ceil(100 n_native / (480 rate_pct)) once flushed (final != 0); < 0 for a rate outside [50, 200]
+ *   q3tts_tsm_windows  the two normative 480-entry f32 tables w and w2
+ * q3tts_op_tsm is the test surface of the stretch kernel, host buffers in the style of q3tts_op_pcm_convert: G streams run through n_chunks
+ * launches of the engine's own launcher, one per chunk, and one more (no input, flush) when `flush` is nonzero, on a fresh stretcher.
+ *   in            the chunks one after the other, chunk c = [G][chunk_samples[c]] native f32 samples (position g of every chunk is stream g)
+ *   chunk_samples native samples per stream of each chunk; the launcher refuses what is no positive multiple of 1920
+ *   streams       [n_chunks][G]: the state slot of position g in chunk c, out of n_streams; the flush takes the last chunk's
+ *   rate_pct      [G]; a stream at 100 is copied through as native f32, as the engine's copy does
+ *   encoding      [G]: 0 = f32, 1 = s16
+ *   reset_before  [n_chunks][G] or NULL: nonzero = that position's slot is reset ahead of the chunk
+ *   out           [G] WHOLE buffers of out_bytes[g] bytes: Q3TTS_GLUE_GUARD guard elements of the stream's encoding, the core, as many guard
+ *                 elements.  Stream g's hops are appended from the core's first element on; n_out[g] = its sample count
+ *   delta_trace   [G] WHOLE int32 buffers of trace_len[g] entries: Q3TTS_GLUE_GUARD guards, one d_k per synthesis frame, as many guards
+ *   hist_store    in/out, WHOLE: Q3TTS_GLUE_GUARD floats, [n_streams][1920], Q3TTS_GLUE_GUARD floats
+ * Everything is checked before anything is launched; a refused call leaves every buffer unwritten. */
+int64_t q3tts_tsm_samples(int32_t rate_pct, int64_t n_native, int32_t final);
+int q3tts_tsm_windows(float* w, float* w2);
+int q3tts_op_tsm(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                 const int32_t* rate_pct, const int32_t* encoding, const int32_t* reset_before, int32_t flush, void* const* out,
+                 const int64_t* out_bytes, int64_t* n_out, int32_t* const* delta_trace, const int64_t* trace_len, float* hist_store);
 
 #ifdef __cplusplus
 }

@@ -451,6 +451,43 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3TTS_PREAMBLE_READY 1
 #define Q3TTS_PREAMBLE_FAILED -1
 
+/* ---------------- speaking rate [EXT] (q3tts_engine_set_speech_rate, q3tts_tsm_samples / _windows, q3tts_op_tsm) ----------------
+ * A pitch-preserving time-scale change (WSOLA) of the native 24000 Hz stream, strictly behind the codec.  x[n] is the native stream, y[m] the
+ * delivered one; every position is a sample index counted from the stream's reset.
+ *   rate       pct, an integer percent in [Q3_TSM_MIN, Q3_TSM_MAX]; input consumed per second of output is pct / 100.  100 means off: the
+ *              request is an ordinary one and nothing of this section runs
+ *   analysis   synthesis frame k >= 0 covers y[480 k .. 480 k + 480).  Its analysis position is a_k = floor(k * 480 * pct / 100) in 64-bit
+ *              integers
+ *   windows    for i in [0, 480): w[i] = f32(0.5 - 0.5 cos(2 pi i / 960)), w2[i] = f32(0.5 + 0.5 cos(2 pi i / 960)), evaluated in double and
+ *              then rounded to f32.  The two tables are normative, as the converter's h32 is
+ *   template   p_{-1} = -480.  The natural continuation of frame k is t_k = p_{k-1} + 480
+ *   candidates c = a_k + d for d in [-240, 240] with c >= 0
+ *   cost       SSD_k(d) = sum over i = 0 .. 479 of (x[c + i] - x[t_k + i])^2, evaluated with one f32 accumulator starting at +0, i ascending,
+ *              diff = x[c + i] - x[t_k + i] as one f32 subtraction, acc = fmaf(diff, diff, acc)
+ *   selection  visit order o(0) = 0, o(-j) = 2 j - 1, o(+j) = 2 j.  The chosen d_k minimises (SSD, o) lexicographically; a non-negative f32's
+ *              bit pattern orders as the value does, so the minimum of (bits << 32 | o) decides it.  p_k = a_k + d_k
+ *   output     y[480 k + i] = fmaf(w[i], x[p_k + i], w2[i] * x[t_k + i]) with the product rounded to f32 first, clamped to [-1, 1].
+ *              s16 is the converter's rule, (int16) rintf(y * 32767.0f) of the clamped value.  Every output sample depends on the input
+ *              alone: no output state is carried
+ *   available  frame k is computed once N, the native samples seen, satisfies a_k + 1200 <= N.  That suffices for every pct in range:
+ *              p_k + 960 <= a_k + 1200 and t_k + 480 <= a_k + 1200.  While streaming, N samples have produced exactly
+ *              480 * #{k : a_k + 1200 <= N} output samples, and the result does not depend on how the input was cut into chunks
+ *   flush      at the end of an utterance x[n >= N] = 0 and every frame with a_k < N is produced: 480 * ceil(100 N / (480 pct)) samples in
+ *              all.  A cancelled request is not flushed
+ *   history    the next frame reaches back to a_k - 720 at most and forward to N, which is below a_k + 1200: the last Q3_TSM_HIST native
+ *              samples per stream, d of the last frame and the two counters (N, frames made) are the whole state
+ * What follows from it: at pct = 100, d_k = 0 for all k and |y - x| <= 2^-23 |x| (the engine never runs it: 100 is off).  For an exactly
+ * periodic input x[n] = tab[n mod P] every chosen candidate has SSD exactly 0 and y[m] = tab[m mod P] within the same bound: the waveform
+ * continues in phase at any rate.  All-zero input gives d = 0 everywhere.
+ * A stretching request delivers 24000 Hz, f32 or s16; rates combined with resampled formats are not defined. */
+#define Q3_TSM_HOP 480           /* synthesis hop: 20 ms */
+#define Q3_TSM_WIN 960
+#define Q3_TSM_SEARCH 240        /* +-10 ms */
+#define Q3_TSM_LOOK 1200         /* native samples a frame needs past its analysis position */
+#define Q3_TSM_HIST 1920         /* native samples of history per stream */
+#define Q3_TSM_MIN 50
+#define Q3_TSM_MAX 200
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -322,6 +322,22 @@ int q3tts_engine_preamble_stats(q3tts_engine* e, int64_t* built, int64_t* restor
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] speaking rate */
+int q3tts_engine_set_speech_rate(q3tts_engine* e, int32_t rate_pct) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_speech_rate(rate_pct); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_speech_rate(q3tts_engine* e, int64_t id, int32_t* rate_pct) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && rate_pct, "null argument");
+    *rate_pct = e->e->request_speech_rate(id);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_tsm_stats(q3tts_engine* e, int64_t* chunks, int64_t* frames_out, int64_t* flushes) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && chunks && frames_out && flushes, "null argument");
+    e->e->tsm_stats(chunks, frames_out, flushes);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

@@ -6,6 +6,7 @@
 #include "codec.h"
 #include "kernels.h"
 #include "pcm_out.h"
+#include "tsm.h"
 
 using namespace q3;
 #define Q3_API_BEGIN try {
@@ -1077,6 +1078,95 @@ int q3tts_op_pcm_convert(const float* in, int32_t G, const int32_t* chunk_sample
     for (int g = 0; g < G; g++) {
         Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
         n_out[g] = done[g] / esz[g];
+    }
+    d_hist.download(hist_store, hist_n);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] speaking rate: the host-only half (sched_logic.h, tsm.h) */
+int64_t q3tts_tsm_samples(int32_t rate_pct, int64_t n_native, int32_t final) { return tsm_out_samples(rate_pct, n_native, final != 0); }
+int q3tts_tsm_windows(float* w, float* w2) {
+    Q3_API_BEGIN
+    Q3_CHECK(w && w2, "null argument");
+    tsm_windows(w, w2);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] the stretch kernel over guarded host buffers (include/q3tts.h): one launch_tsm_stretch per chunk and one more for the flush, each
+ * stream's hops appended behind its earlier ones inside its guarded buffer on the device, everything downloaded whole. */
+int q3tts_op_tsm(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                 const int32_t* rate_pct, const int32_t* encoding, const int32_t* reset_before, int32_t flush, void* const* out,
+                 const int64_t* out_bytes, int64_t* n_out, int32_t* const* delta_trace, const int64_t* trace_len, float* hist_store) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(in && chunk_samples && streams && rate_pct && encoding && out && out_bytes && n_out && delta_trace && trace_len && hist_store, "null argument");
+    Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
+    // every chunk is checked as its launch will be, and every count is worked out as the launcher will, before anything is allocated
+    int64_t in_floats = 0;
+    for (int c = 0; c < n_chunks; c++) {
+        if (const char* why = tsm_launch_refusal(G, G, chunk_samples[c], false, streams + (size_t)c * G, n_streams, rate_pct, encoding)) throw Error(std::string("tsm stretch: ") + why);
+        in_floats += (int64_t)G * chunk_samples[c];
+    }
+    std::vector<int64_t> seen((size_t)n_streams, 0), done((size_t)n_streams, 0), frames(G, 0), need(G, 0), esz(G), reg(G), treg(G);
+    for (int c = 0; c <= n_chunks; c++) {
+        if (c == n_chunks && !flush) break;
+        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;   // the flush follows the last chunk's slots
+        const int64_t T = c < n_chunks ? chunk_samples[c] : 0;
+        for (int g = 0; g < G; g++) {
+            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) seen[(size_t)sl[g]] = done[(size_t)sl[g]] = 0;
+            if (rate_pct[g] == 100) { need[g] += T * 4; continue; }
+            const int64_t total = tsm_frames(rate_pct[g], seen[(size_t)sl[g]] + T, c == n_chunks), nf = std::max<int64_t>(total - done[(size_t)sl[g]], 0);
+            seen[(size_t)sl[g]] += T; done[(size_t)sl[g]] += nf; frames[g] += nf;
+        }
+    }
+    int64_t total = 0, ttotal = 0;
+    for (int g = 0; g < G; g++) {
+        esz[g] = rate_pct[g] != 100 && encoding[g] == Q3_PCM_S16 ? 2 : 4;   // a stream at 100 is copied through as native f32
+        if (rate_pct[g] != 100) need[g] = frames[g] * Q3_TSM_HOP * esz[g];
+        Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
+        Q3_CHECK(delta_trace[g] && trace_len[g] >= frames[g] + 2 * Q3TTS_GLUE_GUARD, "guarded trace buffer too small or missing");
+        reg[g] = total; total += (out_bytes[g] + 255) / 256 * 256;
+        treg[g] = ttotal; ttotal += (trace_len[g] + 63) / 64 * 64;
+    }
+    DevBuf<uint8_t> d_out((size_t)total);
+    DevBuf<int32_t> d_trace((size_t)ttotal);
+    for (int g = 0; g < G; g++) {
+        Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
+        Q3_HIP(hipMemcpy(d_trace.p + treg[g], delta_trace[g], (size_t)trace_len[g] * 4, hipMemcpyHostToDevice));
+    }
+    DevBuf<float> d_in((size_t)std::max<int64_t>(in_floats, 1)); d_in.upload(in, (size_t)in_floats);
+    const size_t hist_n = (size_t)n_streams * Q3_TSM_HIST + 2 * Q3TTS_GLUE_GUARD;
+    DevBuf<float> d_hist(hist_n); d_hist.upload(hist_store, hist_n);
+    TsmStretcher ts(n_streams, G);
+    ts.hist = d_hist.p + Q3TTS_GLUE_GUARD;
+    std::vector<int64_t> off(G), toff(G), bytes(G, 0), fr(G, 0), cnt(G);
+    const float* x = d_in.p;
+    for (int c = 0; c <= n_chunks; c++) {
+        if (c == n_chunks && !flush) break;
+        const int T = c < n_chunks ? chunk_samples[c] : 0;
+        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;
+        for (int g = 0; g < G; g++) {
+            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) ts.reset_async(0, sl[g]);
+            off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + bytes[g];
+            toff[g] = treg[g] + Q3TTS_GLUE_GUARD + fr[g];
+        }
+        launch_tsm_stretch(0, ts, x, G, T, c == n_chunks, sl, rate_pct, encoding, d_out.p, off.data(), cnt.data(), d_trace.p, toff.data());
+        for (int g = 0; g < G; g++) {
+            if (rate_pct[g] == 100 && T > 0) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
+            bytes[g] += cnt[g] * esz[g];
+            if (rate_pct[g] != 100) fr[g] += cnt[g] / Q3_TSM_HOP;
+        }
+        x += (size_t)G * T;
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    for (int g = 0; g < G; g++) {
+        Q3_CHECK(bytes[g] == need[g], "the launcher's counts differ from the plan");
+        Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
+        Q3_HIP(hipMemcpy(delta_trace[g], d_trace.p + treg[g], (size_t)trace_len[g] * 4, hipMemcpyDeviceToHost));
+        n_out[g] = bytes[g] / esz[g];
     }
     d_hist.download(hist_store, hist_n);
     return Q3TTS_OK;

@@ -11,6 +11,7 @@
 #include "gguf.h"
 #include "kernels.h"
 #include "pcm_out.h"
+#include "tsm.h"
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -1099,6 +1100,22 @@ struct CodecDecoder::Impl {
     // chunk of each stream of a pass, region g at g * T * 4 bytes.  The counters are read by other threads
     std::unique_ptr<PcmConverter> conv; std::vector<DevBuf<float>> pcm_out; size_t pcm_lane_floats = 0;
     std::atomic<int64_t> conv_chunks{0}, conv_samples{0};
+    // [EXT] speaking rate: made by the first call that stretches, under capture_mutex(); tsm_out[lane] = the hops of each stream of a pass,
+    // region g of tsm_region floats (a chunk at rate 50 makes twice its samples plus a hop; a flush at most six hops).  tsm_pct / tsm_enc =
+    // what a stream was last stretched with since its reset (0: it was not), which is what its flush runs with
+    std::unique_ptr<TsmStretcher> tsm; std::vector<DevBuf<float>> tsm_out; std::vector<int32_t> tsm_pct, tsm_enc;
+    size_t tsm_region() const { return 2 * (pcm_lane_floats / (size_t)gmax) + 8 * Q3_TSM_HOP; }
+    std::atomic<int64_t> tsm_chunks{0}, tsm_frames{0}, tsm_flushes{0};
+    void ensure_tsm() {
+        if (tsm) return;
+        std::lock_guard<std::mutex> cap(capture_mutex());
+        tsm_out.resize(lanes.size());
+        for (auto& b : tsm_out) b.alloc((size_t)gmax * tsm_region());
+        tsm_pct.assign((size_t)n_streams, 0); tsm_enc.assign((size_t)n_streams, 0);
+        tsm.reset(new TsmStretcher(n_streams, gmax));
+    }
+    void tsm_reset(hipStream_t st, int s) { if (tsm) { tsm->reset_async(st, s); tsm_pct[(size_t)s] = 0; } }
+    void tsm_count(int64_t c0, int64_t f0, int64_t l0) { tsm_chunks += tsm->chunks - c0; tsm_frames += tsm->frames_out - f0; tsm_flushes += tsm->flushes - l0; }
     // [EXT] codec preambles: the snapshot store.  A slot holds one stream's histories back to back in all_ext order (the shape of one stream's
     // share of the history stores) and the two host counters as they stood when the snapshot was enqueued.  A slot's buffer is allocated by the
     // first snapshot that takes it, under capture_mutex(), and kept for the next one; snap_mu guards the table (a slot may be freed by
@@ -1390,7 +1407,11 @@ void CodecDecoder::reset(int s) {
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
     if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
+    if (m.tsm) { m.tsm_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
     m.kv_len[s] = 0; m.n_seen[s] = 0;
+}
+void CodecDecoder::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
+    *chunks = impl_->tsm_chunks.load(); *frames_out = impl_->tsm_frames.load(); *flushes = impl_->tsm_flushes.load();
 }
 void CodecDecoder::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const {
     *chunks_converted = impl_->conv_chunks.load(); *samples_out = impl_->conv_samples.load();
@@ -1474,6 +1495,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     }
     flush();
     if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
+    m.tsm_reset(st, s);                     // and so is the stretcher's state
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1524,6 +1546,7 @@ void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* p
         m.ensure_conv();
         Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
     }
+    m.tsm_reset(st, s); // [EXT] speaking rate: a primed stream's stretcher starts from a reset
     m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
 }
 void CodecDecoder::snapshot_free(int snap) {
@@ -1547,7 +1570,7 @@ int CodecDecoder::decode_async(hipStream_t st, int s, const int64_t* codes, int 
 // One pass for G streams that each contribute n_frames new frames: every GEMM runs over G*T rows, so the 733 MB of
 // codec weights are streamed once per group instead of once per stream, and one set of launches serves the group.
 int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane,
-                                     const q3tts_pcm_format* fmt, int64_t* n_out) {
+                                     const q3tts_pcm_format* fmt, int64_t* n_out, const int32_t* rate) {
     Impl& m = *impl_;
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     Q3_CHECK(G >= 1 && G <= m.gmax, "group size out of range");
@@ -1655,26 +1678,71 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
-    bool converts = false;
-    for (int g = 0; fmt && g < G; g++) converts = converts || !pcm_format_native(fmt[g]);
-    if (!converts) {
+    bool converts = false, stretches = false;
+    for (int g = 0; rate && g < G; g++) stretches = stretches || rate[g] != 100;
+    for (int g = 0; fmt && g < G; g++) converts = converts || (!pcm_format_native(fmt[g]) && !(rate && rate[g] != 100));
+    if (!converts && !stretches) {
         for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
         for (int g = 0; n_out && g < G; g++) n_out[g] = T;
         return T;
     }
-    // [EXT] output formats: one convert launch behind the output conv, then every stream's bytes from where its format left them
-    m.ensure_conv();
-    std::vector<int64_t> cnt((size_t)G);
-    const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
-    launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, fmt, m.pcm_out[lane].p, nullptr, cnt.data());
-    Q3_LAUNCH_CHECK();
-    m.conv_chunks += m.conv->chunks_converted - c0; m.conv_samples += m.conv->samples_out - s0;
+    // [EXT] output formats / speaking rate: one convert launch and / or one stretch launch behind the output conv, then every stream's bytes
+    // from where its stage left them.  A stretching stream delivers 24000 Hz and is the stretcher's alone: the converter sees it as native
+    const q3tts_pcm_format native{Q3_PCM_NATIVE_RATE, Q3_PCM_F32};
+    std::vector<q3tts_pcm_format> cf((size_t)G, native);
+    std::vector<int32_t> pct((size_t)G, 100), enc((size_t)G, Q3_PCM_F32);
     for (int g = 0; g < G; g++) {
-        if (pcm_format_native(fmt[g])) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-        else Q3_HIP(hipMemcpyAsync(pcm[g], m.pcm_out[lane].p + (size_t)g * T, (size_t)cnt[g] * (fmt[g].encoding == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
-        if (n_out) n_out[g] = cnt[g];
+        if (rate && rate[g] != 100) {
+            Q3_CHECK(!fmt || fmt[g].sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate needs the 24000 Hz output format");
+            pct[(size_t)g] = rate[g]; enc[(size_t)g] = fmt ? fmt[g].encoding : Q3_PCM_F32;
+        } else if (fmt) cf[(size_t)g] = fmt[g];
+    }
+    std::vector<int64_t> cnt((size_t)G, T), tcnt((size_t)G, T), toff((size_t)G);
+    if (converts) {
+        m.ensure_conv();
+        const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
+        launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, cf.data(), m.pcm_out[lane].p, nullptr, cnt.data());
+        Q3_LAUNCH_CHECK();
+        m.conv_chunks += m.conv->chunks_converted - c0; m.conv_samples += m.conv->samples_out - s0;
+    }
+    if (stretches) {
+        m.ensure_tsm();
+        Q3_CHECK(2 * (size_t)T + Q3_TSM_HOP <= m.tsm_region(), "chunk too long for the stretcher's buffers");
+        for (int g = 0; g < G; g++) toff[(size_t)g] = (int64_t)((size_t)g * m.tsm_region() * sizeof(float));
+        const int64_t c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;
+        launch_tsm_stretch(st, *m.tsm, m.S->pcm.p, G, T, false, streams, pct.data(), enc.data(), m.tsm_out[lane].p, toff.data(), tcnt.data());
+        Q3_LAUNCH_CHECK();
+        m.tsm_count(c0, f0, l0);
+    }
+    for (int g = 0; g < G; g++) {
+        if (pct[(size_t)g] != 100) {
+            m.tsm_pct[(size_t)streams[g]] = pct[(size_t)g]; m.tsm_enc[(size_t)streams[g]] = enc[(size_t)g];
+            cnt[(size_t)g] = tcnt[(size_t)g];
+            if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], m.tsm_out[lane].p + (size_t)g * m.tsm_region(), (size_t)cnt[(size_t)g] * (enc[(size_t)g] == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+        }
+        else if (pcm_format_native(cf[(size_t)g])) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+        else Q3_HIP(hipMemcpyAsync(pcm[g], m.pcm_out[lane].p + (size_t)g * T, (size_t)cnt[(size_t)g] * (cf[(size_t)g].encoding == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+        if (n_out) n_out[g] = cnt[(size_t)g];
     }
     return T;
+}
+
+// [EXT] speaking rate: the end of a stretched utterance.  The stream's input ends in zeros and every frame with a_k < N comes out: one launch
+// without input, then the copy of its hops to dst (pinned).  A stream that was not stretched since its reset gives nothing
+void CodecDecoder::tsm_flush_async(hipStream_t st, int s, void* dst, int64_t* n_out, int lane) {
+    Impl& m = *impl_;
+    Q3_CHECK(s >= 0 && s < m.n_streams && n_out, "stream out of range");
+    Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
+    *n_out = 0;
+    if (!m.tsm || m.tsm_pct[(size_t)s] == 0) return;
+    const int32_t sl = s, pct = m.tsm_pct[(size_t)s], enc = m.tsm_enc[(size_t)s];
+    const int64_t off = 0, c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;
+    launch_tsm_stretch(st, *m.tsm, nullptr, 1, 0, true, &sl, &pct, &enc, m.tsm_out[lane].p, &off, n_out);
+    Q3_LAUNCH_CHECK();
+    m.tsm_count(c0, f0, l0);
+    Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the stretcher's buffer");
+    if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, m.tsm_out[lane].p, (size_t)*n_out * (enc == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+    m.tsm_pct[(size_t)s] = 0; // flushed: the stream is reset before it is used again
 }
 
 // ---------------- test entry points: one GEMM as the decoder dispatches it, or with a named form forced ----------------

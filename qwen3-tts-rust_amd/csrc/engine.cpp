@@ -202,6 +202,9 @@ struct Engine::Req {
     // holds their bytes as the converter left them (pcm_n samples of 4 or 2 bytes, rounded up to whole floats)
     q3tts_pcm_format fmt{Q3_PCM_NATIVE_RATE, Q3_PCM_F32}; int64_t pcm_n = 0;
     size_t sample_bytes() const { return fmt.encoding == Q3_PCM_S16 ? 2 : 4; }
+    // [EXT] speaking rate: the percent the request is spoken at, read at submit (100: off).  pcm_enq / pcm_ready / pcm_n count the samples
+    // delivered; tsm_native = the native samples its stream has been given (decoder thread)
+    int rate_pct = 100; int64_t tsm_native = 0;
     bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
     // [EXT] codec preambles: the preamble the request is primed with (-1: none; kept for request_preamble after the end), whether it still
@@ -567,20 +570,39 @@ void Engine::decoder_main() {
                 std::vector<float*> dst(G);
                 std::vector<int64_t> codes((size_t)G * nf * 16);
                 std::vector<q3tts_pcm_format> fmt(G); std::vector<int64_t> n_out(G); bool converts = false; // [EXT] output formats
+                std::vector<int32_t> rate(G); bool stretches = false;                                       // [EXT] speaking rate
                 for (int g = 0; g < G; g++) {
                     Req* r = grp[g].r;
                     fmt[g] = r->fmt; converts = converts || !pcm_format_native(r->fmt);
                     // in bytes: a stream's region holds slot_cap_ native floats, and no format needs more bytes per frame than the native one
                     const size_t at = r->pcm_enq * r->sample_bytes();
-                    const size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
+                    size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
+                    rate[g] = r->rate_pct;
+                    if (r->rate_pct != 100) { // the hops that become available with these frames: possibly none, at a slow rate more than native
+                        stretches = converts = true;
+                        add = (size_t)(tsm_out_samples(r->rate_pct, r->tsm_native + (int64_t)nf * spf, false) - tsm_out_samples(r->rate_pct, r->tsm_native, false)) * r->sample_bytes();
+                        r->tsm_native += (int64_t)nf * spf;
+                    }
                     Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
                     streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r->cs * slot_cap_) + at);
                     std::copy(grp[g].codes.begin(), grp[g].codes.end(), codes.begin() + (size_t)g * nf * 16);
                 }
                 // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
                 const int got = codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane,
-                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr);
+                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr, stretches ? rate.data() : nullptr);
                 for (int g = 0; g < G; g++) grp[g].r->pcm_enq += converts ? (size_t)n_out[g] : (size_t)std::max(got, 0);
+            }
+            // [EXT] speaking rate: the fence of a stretching request that was not cancelled flushes its stretcher -- the hops its last samples
+            // still owe -- behind its last chunk (this lane has waited for it above), before the fence's completion is recorded
+            for (auto& t : grp) {
+                Req* r = t.r;
+                if (!t.fence || r->rate_pct == 100 || r->cancel || r->cs < 0) continue;
+                const size_t at = r->pcm_enq * r->sample_bytes();
+                const size_t add = (size_t)(tsm_out_samples(r->rate_pct, r->tsm_native, true) - tsm_out_samples(r->rate_pct, r->tsm_native, false)) * r->sample_bytes();
+                Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
+                int64_t n = 0;
+                codec_->tsm_flush_async(st2_[lane], r->cs, reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r->cs * slot_cap_) + at, &n, lane);
+                r->pcm_enq += (size_t)n;
             }
             // [EXT] codec preambles: a build's fence enqueues the snapshot behind its last chunk (this lane has waited for it above)
             if (grp[0].fence && grp[0].r->build_pre >= 0 && !grp[0].r->cancel) grp[0].r->build_snap = codec_->snapshot_async(st2_[lane], grp[0].r->cs);
@@ -756,6 +778,7 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     r->r.prefix = r->prefix_own.data();
     r->want_pcm = want_pcm && codec_;
     if (r->want_pcm && may_record) r->fmt = unpack_fmt(out_fmt_.load()); // [EXT] the engine's output format, read once per request; a blocking batch is native
+    if (r->want_pcm && may_record) take_rate(r.get(), g.max_steps);       // [EXT] and its speech rate; throws before anything is queued
     r->t_submit = now_ms();
     r->seed = g.sampler.has_seed ? g.sampler.seed
                                  : (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count(); // :473-478
@@ -796,6 +819,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->shared = sh;
         r->want_pcm = want_pcm && codec_;
         if (r->want_pcm) r->fmt = set_fmt;
+        if (r->want_pcm) take_rate(r.get(), g.max_steps, i == 0 ? -1 : rs[0]->rate_pct); // [EXT] the speech rate, read once per set
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
@@ -1002,6 +1026,7 @@ int64_t Engine::submit_decode(const int32_t* codes, int n) {
     std::unique_ptr<Req> r(new Req());
     r->decode = true; r->want_pcm = true;
     r->fmt = unpack_fmt(out_fmt_.load());
+    take_rate(r.get(), n); // [EXT] speaking rate
     r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
     r->t_submit = now_ms();
@@ -1547,6 +1572,30 @@ void Engine::fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int
 void Engine::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const {
     *chunks_converted = *samples_out = 0;
     if (codec_) codec_->pcm_out_stats(chunks_converted, samples_out);
+}
+
+// [EXT] speaking rate (q3tts_spec.h "speaking rate")
+void Engine::set_speech_rate(int pct) {
+    Q3_CHECK(codec_, "the engine has no codec");
+    if (const char* why = tsm_rate_why_not(pct)) throw Error(why);
+    rate_pct_ = pct;
+}
+// the engine's rate (or `given`, the one a candidate set's first member read) becomes the request's, if the request's format and length allow it
+void Engine::take_rate(Req* r, int max_steps, int given) const {
+    const int pct = given >= 0 ? given : rate_pct_.load();
+    if (pct == 100) return;
+    if (const char* why = tsm_submit_refusal(pct, r->fmt, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
+    r->rate_pct = pct;
+}
+int Engine::request_speech_rate(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    return it->second->rate_pct;
+}
+void Engine::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
+    *chunks = *frames_out = *flushes = 0;
+    if (codec_) codec_->tsm_stats(chunks, frames_out, flushes);
 }
 
 // [EXT] codec preambles (q3tts_spec.h "codec preambles")

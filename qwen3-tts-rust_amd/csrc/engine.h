@@ -114,6 +114,13 @@ public:
     q3tts_pcm_format request_format(int64_t id);
     void fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
     void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks converted, output samples made
+    // [EXT] speaking rate (q3tts_spec.h "speaking rate"): requests submitted from now on with want_pcm are spoken at pct percent of the native
+    // tempo (100: off); read once per request at submit and once per candidate set; generate_batch, scoring and preamble builds are never
+    // stretched.  Thread-safe, no HIP calls; throws for a rate outside [50, 200] or an engine without a codec.  A submit with a rate throws
+    // tsm_submit_refusal's reason.  poll()'s n_pcm and the fetch offsets count delivered samples
+    void set_speech_rate(int pct);
+    int request_speech_rate(int64_t id);
+    void tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const; // stream chunks stretched, synthesis frames made, flushes
     // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
     // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
     // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The
@@ -201,6 +208,8 @@ private:
     static int64_t pack_fmt(const q3tts_pcm_format& f) { return (int64_t)f.sample_rate * 4 + f.encoding; }
     static q3tts_pcm_format unpack_fmt(int64_t v) { return q3tts_pcm_format{(int32_t)(v / 4), (int32_t)(v % 4)}; }
     std::atomic<int64_t> out_fmt_{(int64_t)Q3_PCM_NATIVE_RATE * 4 + Q3_PCM_F32}; // what submit() reads
+    std::atomic<int> rate_pct_{100};                                             // [EXT] speaking rate: what submit() reads
+    void take_rate(Req* r, int max_steps, int given = -1) const;
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).

@@ -496,6 +496,17 @@ int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamb
     if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
     return q3tts_request_preamble(e, rid_of(req_id), preamble_id);
 }
+int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) { // [EXT] q3tts_engine_set_speech_rate on every engine
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    if (q3tts_tsm_samples(rate_pct, 0, 0) < 0) { set_last_error("speech rate out of range [50, 200]"); return Q3TTS_ERR; } // all engines or none
+    for (auto* e : g->eng) if (q3tts_engine_set_speech_rate(e, rate_pct) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_request_speech_rate(q3tts_group* g, int64_t req_id, int32_t* rate_pct) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_request_speech_rate(e, rid_of(req_id), rate_pct);
+}
 int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
     if (!g) return Q3TTS_ERR;
     for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;

@@ -350,4 +350,40 @@ struct PcmConverter {
 void launch_pcm_convert(hipStream_t st, PcmConverter& c, const float* in, int G, int T, const int32_t* streams, const q3tts_pcm_format* fmt,
                         void* out, const int64_t* out_off, int64_t* n_out);
 
+// [EXT] speaking rate (tsm.hip, q3tts_spec.h "speaking rate"): WSOLA time-scale change behind the codec.
+// One entry per stream of a launch, written by launch_tsm_stretch into the stretcher's upload ring.  The counts are data-independent, so the
+// host keeps the two counters of every stream and hands the kernel what it derived from them.
+struct TsmStreamMeta {
+    int32_t enc;              // Q3_PCM_F32 / Q3_PCM_S16; -1: the stream is not stretched, its workgroup exits at once
+    int32_t slot, pct;        // state store entry; the rate
+    int32_t n_frames;         // synthesis frames this launch makes: k0 .. k0 + n_frames - 1
+    int64_t n_prev, k0;       // native samples seen before this chunk; first frame to make
+    int64_t out_off;          // first output byte, from the launch's `out`
+    int64_t trace_off;        // first entry of the launch's `trace` (unused when that is NULL)
+};
+// The stretcher's device state: the two window tables, the history store [n_streams][Q3_TSM_HIST] (a stream's last 1920 native samples), the
+// offset of every stream's last frame, and an upload ring as the converter's.  n_seen / k_done are the host's counters per stream.  One owner
+// thread; its launches may go to different HIP streams, and the caller orders a stream slot's chunks across them as it does for the codec.
+struct TsmStretcher {
+    TsmStretcher(int n_streams, int max_group);
+    ~TsmStretcher();
+    TsmStretcher(const TsmStretcher&) = delete; TsmStretcher& operator=(const TsmStretcher&) = delete;
+    void reset_async(hipStream_t st, int slot);    // zeroes the slot's history, offset and counters: its next sample is sample 0 of a stream
+    int n_streams, max_group;
+    float* hist;                                   // = hist_own.p, or a caller's store of the same shape (the test entry point's guarded one)
+    DevBuf<float> tabs, hist_own; DevBuf<int32_t> d_prev; DevBuf<TsmStreamMeta> d_ring;
+    TsmStreamMeta* h_ring = nullptr; int ring_idx = 0; std::vector<hipEvent_t> ring_ev; std::vector<char> ring_used;
+    std::vector<int64_t> n_seen, k_done;
+    int64_t chunks = 0, frames_out = 0, flushes = 0;
+};
+// in [G][T] native samples (T a multiple of 1920; 0 with flush alone), stream g of state slot streams[g] at pct[g] percent in encoding
+// enc[g].  The frames that became available (with flush: every frame with a_k < N, the input ending in zeros) go to out + out_off[g] bytes,
+// 480 samples each; n_out[g] receives their sample count.  A stream at 100 is not touched: n_out[g] = T and its bytes stay where they are, in
+// `in`.  trace (optional, device) receives d_k of every frame made, stream g's from entry trace_off[g] on.  The hops leave as 16-byte
+// stores: out + out_off[g] must be 16-byte aligned.  A flushed stream must be reset before it is used again.
+// Refused (tsm_launch_refusal, tsm.h) before anything is uploaded or launched.
+void launch_tsm_stretch(hipStream_t st, TsmStretcher& s, const float* in, int G, int T, bool flush, const int32_t* streams, const int32_t* pct,
+                        const int32_t* enc, void* out, const int64_t* out_off, int64_t* n_out, int32_t* trace = nullptr,
+                        const int64_t* trace_off = nullptr);
+
 } // namespace q3

@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request and of a codec preamble (with who holds one), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, and the rules of the output formats.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request and of a codec preamble (with who holds one), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -396,6 +396,35 @@ inline int64_t pcm_out_samples(const q3tts_pcm_format& f, int64_t n_frames) { re
 inline int64_t pcm_out_bytes(const q3tts_pcm_format& f, int64_t n_frames) {
     const int64_t n = pcm_out_samples(f, n_frames);
     return n < 0 ? -1 : n * (f.encoding == Q3_PCM_S16 ? 2 : 4);
+}
+
+// [EXT] speaking rate (q3tts_spec.h "speaking rate"): which rates exist, how many frames and samples n_native samples come to, and what a
+// request with a rate may ask for.  The counts depend on pct and n_native alone, never on the samples: the host computes every size and offset.
+inline const char* tsm_rate_why_not(int pct) { return (pct < Q3_TSM_MIN || pct > Q3_TSM_MAX) ? "speech rate out of range [50, 200]" : nullptr; }
+inline int64_t tsm_analysis_pos(int pct, int64_t k) { return k * Q3_TSM_HOP * pct / 100; }
+// synthesis frames of a stream that has seen n_native samples: #{k : a_k + 1200 <= N} while streaming, #{k : a_k < N} once it is final
+inline int64_t tsm_frames(int pct, int64_t n_native, bool final) {
+    if (tsm_rate_why_not(pct) || n_native < 0) return -1;
+    const int64_t step = (int64_t)Q3_TSM_HOP * pct;   // a_k = floor(k * step / 100)
+    if (final) return (100 * n_native + step - 1) / step;
+    if (n_native < Q3_TSM_LOOK) return 0;
+    return (100 * (n_native - Q3_TSM_LOOK + 1) - 1) / step + 1;   // a_k <= N - 1200  <=>  k * step < 100 (N - 1199)
+}
+inline int64_t tsm_out_samples(int pct, int64_t n_native, bool final) {
+    const int64_t f = tsm_frames(pct, n_native, final);
+    return f < 0 ? -1 : f * Q3_TSM_HOP;
+}
+// the submit rule.  A request with pct != 100 delivers 24000 Hz, f32 or s16, and its flushed utterance of max_steps frames must fit the
+// stream's staging region of cap_bytes bytes (slowing down makes more samples than native).  nullptr = it may be queued
+inline const char* tsm_submit_refusal(int pct, const q3tts_pcm_format& f, int max_steps, int64_t cap_bytes, bool have_codec) {
+    if (!have_codec) return "the engine has no codec";
+    if (const char* why = tsm_rate_why_not(pct)) return why;
+    if (pct == 100) return nullptr;
+    if (f.sample_rate != Q3_PCM_NATIVE_RATE) return "a speech rate needs the 24000 Hz output format";
+    if (f.encoding != Q3_PCM_F32 && f.encoding != Q3_PCM_S16) return "unknown encoding";
+    if (tsm_out_samples(pct, (int64_t)max_steps * Q3_PCM_FRAME, true) * (f.encoding == Q3_PCM_S16 ? 2 : 4) > cap_bytes)
+        return "max_steps at this speech rate makes more PCM than a request's staging holds";
+    return nullptr;
 }
 
 } // namespace q3

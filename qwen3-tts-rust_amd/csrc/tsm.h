@@ -1,0 +1,42 @@
+// tsm.h -- [EXT] speaking rate (q3tts_spec.h "speaking rate"): what the stretcher needs beyond the counts and the submit rule in sched_logic.h
+// and still without a device: the two normative window tables, built in double and rounded to f32, the visit order of the candidates, and
+// what a stretch launch refuses.  No HIP, no threads: tests/host/tsm_logic_main.cpp builds it with plain g++ under the host sanitizers.
+#pragma once
+#include "sched_logic.h"
+#include <cmath>
+#include <cstdint>
+
+namespace q3 {
+
+// w[i] = f32(0.5 - 0.5 cos(2 pi i / 960)), w2[i] = f32(0.5 + 0.5 cos(2 pi i / 960)), i in [0, 480)
+inline void tsm_windows(float* w, float* w2) {
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < Q3_TSM_HOP; i++) {
+        const double c = std::cos(2.0 * pi * (double)i / (double)Q3_TSM_WIN);
+        w[i] = (float)(0.5 - 0.5 * c);
+        w2[i] = (float)(0.5 + 0.5 * c);
+    }
+}
+
+// the visit order of offset d in [-240, 240] and back: o(0) = 0, o(-j) = 2j - 1, o(+j) = 2j
+constexpr int tsm_visit_order(int d) { return d == 0 ? 0 : (d < 0 ? -2 * d - 1 : 2 * d); }
+constexpr int tsm_offset_of_order(int o) { return (o & 1) ? -((o + 1) >> 1) : (o >> 1); }
+
+// what a stretch launch refuses (nullptr = it may run): G streams of T native samples each, streams[] slots of an n_streams state store,
+// stream g at pct[g] percent (100: the stream is not touched) in encoding enc[g].  T = 0 is a flush alone
+inline const char* tsm_launch_refusal(int G, int max_group, int64_t T, bool flush, const int32_t* streams, int n_streams, const int32_t* pct,
+                                      const int32_t* enc) {
+    if (G < 1 || G > max_group) return "group size out of range";
+    if (T < 0 || T % Q3_TSM_HIST != 0 || (T == 0 && !flush)) return "chunk length is no positive multiple of 1920 samples";
+    if (T > (int64_t)1 << 24) return "chunk too long";
+    if (!streams || !pct || !enc) return "null streams / rates / encodings";
+    for (int g = 0; g < G; g++) {
+        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
+        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
+        if (const char* why = tsm_rate_why_not(pct[g])) return why;
+        if (enc[g] != Q3_PCM_F32 && enc[g] != Q3_PCM_S16) return "unknown encoding";
+    }
+    return nullptr;
+}
+
+} // namespace q3

@@ -105,6 +105,8 @@ SYMBOLS = [
     "q3tts_engine_set_preamble", "q3tts_request_preamble", "q3tts_engine_preamble_stats",
     "q3tts_group_preamble_create", "q3tts_group_preamble_wait", "q3tts_group_preamble_release", "q3tts_group_voice_set_preamble",
     "q3tts_group_set_preamble", "q3tts_group_request_preamble",
+    "q3tts_engine_set_speech_rate", "q3tts_request_speech_rate", "q3tts_engine_tsm_stats", "q3tts_group_set_speech_rate",
+    "q3tts_group_request_speech_rate", "q3tts_tsm_samples", "q3tts_tsm_windows", "q3tts_op_tsm",
 ]
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
@@ -114,6 +116,7 @@ class PcmFormat(C.Structure):  # q3tts_pcm_format
 PCM_F32, PCM_S16 = 0, 1                                                  # q3tts_pcm_format.encoding
 PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)      # q3tts_spec.h "output formats"
 PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
+TSM_HOP, TSM_WIN, TSM_SEARCH, TSM_LOOK, TSM_HIST, TSM_MIN, TSM_MAX = 480, 960, 240, 1200, 1920, 50, 200   # q3tts_spec.h "speaking rate"
 MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
 PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
@@ -282,6 +285,16 @@ def lib():
         L.q3tts_pcm_format_check.argtypes = [C.POINTER(PcmFormat)]
         L.q3tts_op_pcm_convert.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.q3tts_engine_set_speech_rate.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_request_speech_rate.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.q3tts_engine_tsm_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+        L.q3tts_group_set_speech_rate.argtypes = L.q3tts_engine_set_speech_rate.argtypes
+        L.q3tts_group_request_speech_rate.argtypes = L.q3tts_request_speech_rate.argtypes
+        L.q3tts_tsm_samples.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+        L.q3tts_tsm_samples.restype = C.c_int64
+        L.q3tts_tsm_windows.argtypes = [C.c_void_p, C.c_void_p]
+        L.q3tts_op_tsm.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -530,6 +543,22 @@ def group_request_format(group, rid):
 def group_fetch_pcm16(group, rid, off=0, cap=0):
     """[EXT] q3tts_group_fetch_pcm16: int16 samples [off, off + cap) available now of a group request id"""
     return _fetch_pcm16(lib().q3tts_group_fetch_pcm16, group, rid, off, cap)
+
+
+def _request_speech_rate(fn, h, rid):
+    v = C.c_int32()
+    _chk(fn(h, rid, C.byref(v)))
+    return v.value
+
+
+def group_set_speech_rate(group, rate_pct=100):
+    """[EXT] q3tts_group_set_speech_rate on a q3tts_group handle: every engine of the group (100 = off)"""
+    _chk(lib().q3tts_group_set_speech_rate(group, int(rate_pct)))
+
+
+def group_request_speech_rate(group, rid):
+    """[EXT] q3tts_group_request_speech_rate: the percent a group request id is spoken at"""
+    return _request_speech_rate(lib().q3tts_group_request_speech_rate, group, rid)
 
 
 def _preamble_create(fn, h, codes):
@@ -874,6 +903,22 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         a, b = C.c_int64(), C.c_int64()
         _chk(lib().q3tts_engine_pcm_out_stats(self.h, C.byref(a), C.byref(b)))
         return dict(chunks_converted=a.value, samples_out=b.value)
+
+    def set_speech_rate(self, rate_pct=100):
+        """[EXT] speaking rate (q3tts_engine_set_speech_rate): requests submitted from now on with want_pcm are spoken at rate_pct percent of
+        the native tempo, TSM_MIN .. TSM_MAX, pitch preserved; 100 = off.  Such a request delivers 24000 Hz (f32 or s16) and
+        tsm_samples(rate_pct, n * 1920, True) samples for n frames"""
+        _chk(lib().q3tts_engine_set_speech_rate(self.h, int(rate_pct)))
+
+    def request_speech_rate(self, rid):
+        """[EXT] the percent the request is spoken at (100: not stretched)"""
+        return _request_speech_rate(lib().q3tts_request_speech_rate, self.h, rid)
+
+    def tsm_stats(self):
+        """[EXT] q3tts_engine_tsm_stats: dict(chunks, frames_out, flushes)"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_tsm_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(chunks=a.value, frames_out=b.value, flushes=c.value)
 
     def wait(self, rid, timeout_ms=-1.0):
         rc = lib().q3tts_wait(self.h, rid, timeout_ms)
@@ -1939,3 +1984,79 @@ def op_pcm_convert(x, chunk_samples, streams, n_streams, fmts, reset_before=None
         v = w.view(pcm_dtype(e))
         outs.append(v[GLUE_GUARD: GLUE_GUARD + n].copy())
     return outs, wholes, n_out[: len(wholes)].copy(), hist
+
+
+# ---- speaking rate: the host-only half and the stretch kernel (q3tts_op_tsm) ----
+def tsm_samples(rate_pct, n_native, final=False):
+    """samples delivered for n_native native samples at rate_pct: while streaming, or (final) once flushed; < 0 for a rate out of range"""
+    return int(lib().q3tts_tsm_samples(int(rate_pct), int(n_native), 1 if final else 0))
+
+
+def tsm_windows():
+    """the two normative 480-entry f32 tables (w, w2)"""
+    w, w2 = np.zeros(TSM_HOP, np.float32), np.zeros(TSM_HOP, np.float32)
+    _chk(lib().q3tts_tsm_windows(_p(w), _p(w2)))
+    return w, w2
+
+
+def op_tsm(x, chunk_samples, streams, n_streams, rates, encodings, reset_before=None, flush=False, hist=None, slack=0, fill=0x5A):
+    """the stretch kernel over host buffers, one launch of the engine's launcher per chunk and one more for the flush.  x [G][sum(chunk_samples)]
+    f32: the native signal of each position; streams [n_chunks][G] state slots; rates [G] percent; encodings [G].  hist: a whole guarded store
+    (GLUE_GUARD floats, [n_streams][1920], GLUE_GUARD floats) or None for a zero store between guards of -3e38.  Every output and trace buffer
+    is made exactly as large as the result plus `slack` elements, every byte `fill`.  A position whose slot is reset starts a new utterance: its
+    counts start over.  Returns (outs, traces, wholes, twholes, n_out, hist).  A refused call raises Q3Error carrying wholes / twholes / n_out /
+    hist as they are then."""
+    x = np.ascontiguousarray(x, np.float32)
+    G = x.shape[0] if x.ndim == 2 else 0
+    cs = np.ascontiguousarray(chunk_samples, np.int32)
+    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
+    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    rt = np.ascontiguousarray(rates, np.int32)
+    en = np.ascontiguousarray(encodings, np.int32)
+    parts, at = [], 0
+    for t in cs:                       # [n_chunks concatenated][G][T_c]
+        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
+        at += max(int(t), 0)
+    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G and sum(p.size for p in parts) else np.zeros(1, np.float32)
+    wholes, twholes, want, dts = [], [], [], []
+    seen, done, ns, frs = {}, {}, [0] * len(rt), [0] * len(rt)   # the plan, as the call works it out: counters per slot, starting over at a reset
+    for c in range(cs.size + (1 if flush else 0)):
+        T = max(int(cs[c]), 0) if c < cs.size else 0
+        for g in range(len(rt)):
+            s = int(sl[min(c, cs.size - 1), g]) if sl.size else 0
+            if c < cs.size and rb is not None and rb[c, g]:
+                seen[s] = done[s] = 0
+            if rt[g] == 100:
+                ns[g] += T
+                continue
+            tot = max(tsm_samples(rt[g], seen.get(s, 0) + T, c == cs.size), 0) // TSM_HOP
+            nf = max(tot - done.get(s, 0), 0)
+            seen[s] = seen.get(s, 0) + T
+            done[s] = done.get(s, 0) + nf
+            ns[g] += nf * TSM_HOP
+            frs[g] += nf
+    for g in range(len(rt)):
+        dt = np.int16 if (en[g] == PCM_S16 and rt[g] != 100) else np.float32
+        want.append((ns[g], frs[g])); dts.append(dt)
+        wholes.append(np.full((ns[g] + slack + 2 * GLUE_GUARD) * np.dtype(dt).itemsize, fill, np.uint8))
+        twholes.append(np.full(frs[g] + slack + 2 * GLUE_GUARD, 0x5A5A5A5A, np.int32))
+    if hist is None:
+        hist = np.zeros(n_streams * TSM_HIST + 2 * GLUE_GUARD, np.float32)
+        hist[:GLUE_GUARD] = hist[-GLUE_GUARD:] = -3e38
+    assert hist.dtype == np.float32 and hist.size == n_streams * TSM_HIST + 2 * GLUE_GUARD and hist.flags["C_CONTIGUOUS"]
+    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
+    tptrs = (C.c_void_p * max(len(twholes), 1))(*[w.ctypes.data for w in twholes])
+    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
+    tlen = np.array([w.size for w in twholes] or [0], np.int64)
+    n_out = np.full(max(len(wholes), 1), -1, np.int64)
+    try:
+        pad = np.zeros(1, np.int32)    # an empty list still hands the call a pointer
+        _chk(lib().q3tts_op_tsm(_p(flat), G, _p(cs), cs.size, _p(sl if sl.size else pad), n_streams, _p(rt if rt.size else pad),
+                                _p(en if en.size else pad), _p(rb), 1 if flush else 0, ptrs, _p(nbytes),
+                                _p(n_out), tptrs, _p(tlen), _p(hist)))
+    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
+        ex.wholes, ex.twholes, ex.n_out, ex.hist = wholes, twholes, n_out[: len(wholes)].copy(), hist
+        raise
+    outs = [w.view(dt)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, dt, (n, fr) in zip(wholes, dts, want)]
+    traces = [t[GLUE_GUARD: GLUE_GUARD + fr].copy() for t, (n, fr) in zip(twholes, want)]
+    return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist
