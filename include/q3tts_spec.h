@@ -390,6 +390,11 @@ Q3_HD int q3_nearest_int_ggml(float fval) {
  * fence run alone as soon as they head its tasks.  With no decode-only request the passes are those formed without this feature.
  * Hand-over: a request's tasks (reset, chunks, fence) reach the decoder thread in the scheduler step that admitted it -- at once when that step
  * runs no frame group, else together with the chunks the step's frame group produced, so that the two kinds meet in the queues.
+ * Every frame group's chunks (with the tails and fences of the slots it retires) are one hand-over: the thread forms no pass while they
+ * arrive, and the generating chunks of one pass come from one hand-over.  Which generating streams share a pass is therefore a function of
+ * the schedule -- which step hands over which chunks --, not of the two threads' timing: two runs with the same schedule give the same PCM
+ * bit for bit, and a request keeps its bits when only another request's codes change (a pass's row count picks the GEMM forms, so the bits
+ * do depend on who shares the pass; D2's tolerance covers that).
  * States: Q3TTS_REQ_QUEUED until a stream is taken, Q3TTS_REQ_DRAINING until the fence, Q3TTS_REQ_DONE; n_frames = n from submission on.
  * Refused: n < 1 or n > max_steps; no codec; a code_0 outside [0, Q3_SAMPLE_END) or equal to Q3_CODEC_EOS; a residual code outside [0, 2048)
  * (no request emits such a frame). */

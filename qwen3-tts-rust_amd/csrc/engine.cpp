@@ -6,6 +6,7 @@
 #include <chrono>
 #include "kdev.h"
 #include <functional>
+#include <optional>
 
 namespace q3 {
 
@@ -531,7 +532,7 @@ void Engine::decoder_main() {
                 if (dq_.empty() && dq_lo_.empty()) return;
                 auto heads = [](const std::deque<DecTask>& q) {
                     std::vector<TaskHead> h;
-                    for (const DecTask& t : q) h.push_back({t.r->id, (int)t.codes.size() / 16, t.reset ? TASK_RESET : t.fence ? TASK_FENCE : TASK_CHUNK});
+                    for (const DecTask& t : q) h.push_back({t.r->id, (int)t.codes.size() / 16, t.reset ? TASK_RESET : t.fence ? TASK_FENCE : TASK_CHUNK, t.epoch});
                     return h;
                 };
                 const Seating s = seat_chunks(heads(dq_), heads(dq_lo_), gmax, dry);
@@ -988,7 +989,7 @@ void Engine::admit(bool stalled) {
         }
         r->chunker.reset(new Chunker([this, r](const int64_t* codes, int n_codes, bool is_final) {
             if (!r->want_pcm) return;
-            { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false}); dec_pending_++; }
+            { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false, dec_epoch_}); dec_pending_++; }
             dcv_.notify_all();
         }));
         Q3_HIP(hipEventCreate(&r->ev_admit));
@@ -1160,6 +1161,10 @@ void Engine::activate() {
     batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->score; }), batch.end());
     arena_used_ = 0; // st_ is idle between scheduler operations
     q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
+    bool prefix_pcm = false; // [EXT] resume: the chunks the wave's prefixes make up are one hand-over to the decoder thread
+    for (Req* r : batch) prefix_pcm = prefix_pcm || (r->want_pcm && r->r.n_prefix >= 4);
+    std::optional<DecHold> hold;
+    hold.emplace(this, codec_ != nullptr && prefix_pcm);
     for (Req* r : batch) {
         const int b = r->slot;
         slots_.load(b, r->r);
@@ -1198,6 +1203,7 @@ void Engine::activate() {
         }
         slots_.live[b] = 1;
     }
+    hold.reset();
     upload_slot_state();
     bool async_wave = false;
     if (n_prefilling_ > 0) { // the wave was prefilled on the second talker instance
@@ -1435,13 +1441,11 @@ void Engine::run_group() {
         stats.gu_ms += timer_gu_.collect_ms(); stats.gu_bytes += timer_gu_.bytes; stats.gu_launches += timer_gu_.launches; timer_gu_.bytes = 0; timer_gu_.launches = 0;
     }
     std::memcpy(h_nfr, p_nfr, (size_t)width * 4); std::memcpy(h_fin, p_fin, (size_t)width * 4);
-    // [EXT] decode-only requests admitted in this step: their tasks reach the decoder thread together with this group's chunks.  The thread
-    // forms no pass while both are handed over (microseconds); with nothing admitted, nothing is held
-    struct Hold {
-        Engine* e; bool on;
-        Hold(Engine* e_, bool on_) : e(e_), on(on_) { if (on) { std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = true; } }
-        ~Hold() { if (on) { { std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = false; } e->dcv_.notify_all(); } }
-    } hold(this, !dec_admitted_.empty());
+    // The group's chunks, the tails and fences of the slots it retires and the tasks of the decode-only requests admitted in this step reach
+    // the decoder thread as one hand-over: it forms no pass meanwhile (microseconds), and seat_chunks keeps the chunks of one hand-over
+    // together.  Handed over one by one, the thread would start a pass with the chunks that happened to have arrived: which streams share a
+    // pass, and with it the GEMM forms a request's samples go through, would depend on the two threads' timing
+    DecHold hold(this, codec_ != nullptr);
     for (int b = 0; b < width; b++) {
         if (!slots_.live[b]) continue;
         Req* r = slot_req_[b];

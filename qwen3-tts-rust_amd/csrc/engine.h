@@ -302,12 +302,18 @@ private:
     std::vector<Voice> voices_;
     std::thread driver_; bool driver_on_ = false, driver_stop_ = false;
     // decoder thread
-    struct DecTask { Req* r; std::vector<int64_t> codes; bool is_final; bool fence; bool reset; };
+    struct DecTask { Req* r; std::vector<int64_t> codes; bool is_final; bool fence; bool reset; int64_t epoch = 0; }; // epoch: the hand-over it came with (seat_chunks)
     struct Completion { Req* r; hipEvent_t ev; size_t pcm_after; bool fence; };
     std::thread dec_thread_; bool dec_started_ = false, dec_stop_ = false;
     std::mutex dmu_; std::condition_variable dcv_;
     std::deque<DecTask> dq_, dq_lo_; std::deque<Completion> comp_; // dq_lo_: [EXT] the tasks of decode-only requests (seat_chunks)
-    bool dec_hold_ = false;             // [EXT] the scheduler is handing over a frame group's chunks and decode-only tasks: no pass is formed meanwhile (dmu_)
+    bool dec_hold_ = false;             // the scheduler is handing over a frame group's chunks and decode-only tasks: no pass is formed meanwhile (dmu_)
+    int64_t dec_epoch_ = 0;             // hand-overs so far (scheduler thread): the tasks of one carry its number and arrive in one piece
+    struct DecHold {                    // one hand-over: a new epoch, and the decoder thread forms no pass until every task of it is queued
+        Engine* e; bool on;
+        DecHold(Engine* e_, bool on_) : e(e_), on(on_) { if (on) { e->dec_epoch_++; std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = true; } }
+        ~DecHold() { if (on) { { std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = false; } e->dcv_.notify_all(); } }
+    };
     int dec_pending_ = 0;               // chunk / fence tasks whose completion has not been harvested yet (dmu_)
     std::string derr_;
     LaunchTimer timer_, timer_gu_;

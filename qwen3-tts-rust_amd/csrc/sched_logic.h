@@ -268,12 +268,16 @@ inline int decode_admit(int queued, int free_cs, int holding, int width) { retur
 //            decode-only chunk leads
 //   seats    the first pending chunks of the other generating requests with the lead's frame count, in queue order, then those of
 //            decode-only requests, in queue order
+//   epoch    the generating chunks of one pass come from one hand-over (TaskHead::epoch: the scheduler numbers its hand-overs and gives a
+//            hand-over's tasks to the thread in one piece).  A pass then holds the same chunks whether the thread forms it before or after
+//            the next hand-over arrives, so what a request's samples are computed with -- the rows of its pass pick the GEMM forms --
+//            depends on the schedule and not on how fast the thread runs.  Decode-only chunks carry no epoch: they take the seats left
 //   turn     after SEAT_DRY_MAX consecutive passes that seated no decode-only chunk while one was waiting, the oldest decode-only chunk
 //            leads the next pass; generating chunks of its frame count still take the other seats first
 // With the low queue empty this is the grouping the thread always did.  dry = the count of such passes so far; the result carries the next.
 enum TaskKind { TASK_CHUNK = 0, TASK_RESET = 1, TASK_FENCE = 2 };
 enum { SEAT_DRY_MAX = 4 };
-struct TaskHead { int64_t req; int frames; int kind; }; // frames: of a chunk, else 0
+struct TaskHead { int64_t req; int frames; int kind; int64_t epoch = 0; }; // frames: of a chunk, else 0; epoch: of a generating request's task
 struct Seat { bool low; int index; };                   // index into its queue
 struct Seating { std::vector<Seat> seats; int dry = 0; };
 inline Seating seat_chunks(const std::vector<TaskHead>& live, const std::vector<TaskHead>& low, int gmax, int dry) {
@@ -290,10 +294,13 @@ inline Seating seat_chunks(const std::vector<TaskHead>& live, const std::vector<
     const TaskHead& lead = turn ? low[heads[0]] : live[0];
     out.seats.push_back({turn, turn ? heads[0] : 0});
     seen.assign(1, lead.req); // request ids are the engine's: no two requests share one, whichever queue they wait in
+    bool bound = !turn; int64_t epoch = lead.epoch; // a decode-only lead binds the pass to the epoch of the first generating chunk it seats
     for (int i = 0; i < (int)live.size() && (int)out.seats.size() < gmax; i++) {
         const bool dup = std::find(seen.begin(), seen.end(), live[i].req) != seen.end();
         if (!dup) seen.push_back(live[i].req);
-        if (!dup && live[i].kind == TASK_CHUNK && live[i].frames == lead.frames) out.seats.push_back({false, i});
+        if (dup || live[i].kind != TASK_CHUNK || live[i].frames != lead.frames || (bound && live[i].epoch != epoch)) continue;
+        out.seats.push_back({false, i});
+        bound = true; epoch = live[i].epoch;
     }
     bool seated_low = turn;
     for (int i : heads) {

@@ -7,12 +7,14 @@
 
 using namespace q3;
 
-static std::vector<TaskHead> read_queue(int n) { // per task: request id, frame count, kind (C chunk, R reset, F fence)
+static bool g_epochs = false; // "epochs 1": every task line carries a fourth field, the hand-over it came with
+static std::vector<TaskHead> read_queue(int n) { // per task: request id, frame count, kind (C chunk, R reset, F fence)[, epoch]
     std::vector<TaskHead> q;
     for (int i = 0; i < n; i++) {
-        long long req; int frames; char kind;
+        long long req, epoch = 0; int frames; char kind;
         std::cin >> req >> frames >> kind;
-        q.push_back({(int64_t)req, frames, kind == 'R' ? TASK_RESET : kind == 'F' ? TASK_FENCE : TASK_CHUNK});
+        if (g_epochs) std::cin >> epoch;
+        q.push_back({(int64_t)req, frames, kind == 'R' ? TASK_RESET : kind == 'F' ? TASK_FENCE : TASK_CHUNK, (int64_t)epoch});
     }
     return q;
 }
@@ -37,6 +39,10 @@ int main() {
             if (at >= 0) { codes[(size_t)at * 16] = c0; codes[(size_t)at * 16 + 15] = res; }
             const char* why = decode_refusal(null_codes ? nullptr : codes.data(), n, max_steps, have_codec != 0);
             printf("%s\n", why ? why : "ok");
+        } else if (cmd == "epochs") { // epochs 0|1: how the task lines that follow are read
+            int on;
+            std::cin >> on;
+            g_epochs = on != 0;
         } else if (cmd == "width") { // width n_cs max_batch
             int n_cs, b;
             std::cin >> n_cs >> b;

@@ -4,72 +4,9 @@ Mel front end: oracle vs a numpy restatement of /root/reference/src/models/onnx.
 import os
 import numpy as np
 import pytest
-import ggml_ref as G
 
 torch = pytest.importorskip("torch")
-F = torch.nn.functional
-
-
-def _w(t, name):
-    ty, ne, raw = t[name]
-    return torch.from_numpy(np.array(raw).view(np.float32).reshape(list(reversed(ne))).copy())
-
-
-def torch_codec(path, codes):
-    kv, t = G.read_gguf(path)
-    H, nh, hd, W = kv["codec.hidden"], kv["codec.n_heads"], kv["codec.head_dim"], kv["codec.window"]
-    T = codes.shape[0]
-    z = sum(_w(t, "codec.codebook.%d" % q)[codes[:, q]] for q in range(16)).T.unsqueeze(0)   # [1,512,T]
-    causal = lambda x, w, b, dil=1, groups=1: F.conv1d(F.pad(x, ((w.shape[-1] - 1) * dil, 0)), w, b, dilation=dil, groups=groups)
-    h = causal(z, _w(t, "codec.pre_conv.weight"), _w(t, "codec.pre_conv.bias"))[0].T                  # [T,H]
-    rms = lambda x, g: x * torch.rsqrt((x * x).mean(-1, keepdim=True) + kv["codec.eps"]) * g
-    pos = torch.arange(T, dtype=torch.float64)
-    inv = torch.tensor(kv["codec.rope_base"], dtype=torch.float64) ** (-torch.arange(hd // 2, dtype=torch.float64) / (hd // 2))
-    ang = pos[:, None] * inv[None]
-    cs, sn = torch.cos(ang).float(), torch.sin(ang).float()
-
-    def rope(x):  # [T, nh, hd]
-        a, b = x[..., : hd // 2], x[..., hd // 2:]
-        return torch.cat([a * cs[:, None] - b * sn[:, None], b * cs[:, None] + a * sn[:, None]], -1)
-    idx = torch.arange(T)
-    mask = (idx[None] <= idx[:, None]) & (idx[:, None] - idx[None] < W)
-    for l in range(kv["codec.n_layers"]):
-        p = "codec.tf.%d." % l
-        xn = rms(h, _w(t, p + "attn_norm"))
-        q = rope((xn @ _w(t, p + "wq").T).view(T, nh, hd)); k = rope((xn @ _w(t, p + "wk").T).view(T, nh, hd))
-        v = (xn @ _w(t, p + "wv").T).view(T, nh, hd)
-        s = torch.einsum("thd,shd->hts", q, k) / hd ** 0.5
-        s = s.masked_fill(~mask[None], float("-inf"))
-        a = torch.einsum("hts,shd->thd", torch.softmax(s, -1), v).reshape(T, nh * hd)
-        h = h + _w(t, p + "ls_attn") * (a @ _w(t, p + "wo").T)
-        xn = rms(h, _w(t, p + "ffn_norm"))
-        h = h + _w(t, p + "ls_ffn") * ((F.silu(xn @ _w(t, p + "w_gate").T) * (xn @ _w(t, p + "w_up").T)) @ _w(t, p + "w_down").T)
-    x = rms(h, _w(t, "codec.tf.norm")).T.unsqueeze(0)                                              # [1,H,T]
-
-    def convt(x, w, b, s):  # keep the first T*s outputs (right trim k-s): the streamable causal form
-        y = F.conv_transpose1d(x, w, b, stride=s)
-        return y[..., : x.shape[-1] * s]
-    for i in range(kv["codec.n_up"]):
-        p = "codec.up.%d." % i
-        x = convt(x, _w(t, p + "convt.weight"), _w(t, p + "convt.bias"), kv["codec.up_ratio.%d" % i])
-        d = causal(x, _w(t, p + "dw.weight").unsqueeze(1), _w(t, p + "dw.bias"), groups=H)
-        d = F.layer_norm(d.transpose(1, 2), (H,), _w(t, p + "ln.weight"), _w(t, p + "ln.bias"), 1e-6)
-        d = F.gelu(d @ _w(t, p + "pw1.weight").T + _w(t, p + "pw1.bias")) @ _w(t, p + "pw2.weight").T + _w(t, p + "pw2.bias")
-        x = x + (_w(t, p + "gamma") * d).transpose(1, 2)
-    snake = lambda x, a, b: x + (1.0 / (torch.exp(b) + 1e-9))[None, :, None] * torch.sin(x * torch.exp(a)[None, :, None]) ** 2
-    x = causal(x, _w(t, "codec.dec.conv_in.weight"), _w(t, "codec.dec.conv_in.bias"))
-    for b in range(kv["codec.n_dec"]):
-        p = "codec.dec.%d." % b
-        r = kv["codec.dec_rate.%d" % b]
-        x = convt(snake(x, _w(t, p + "snake.alpha"), _w(t, p + "snake.beta")), _w(t, p + "convt.weight"), _w(t, p + "convt.bias"), r)
-        for u, dil in enumerate((1, 3, 9)):
-            q = p + "ru.%d." % u
-            y = causal(snake(x, _w(t, q + "snake1.alpha"), _w(t, q + "snake1.beta")), _w(t, q + "conv1.weight"), _w(t, q + "conv1.bias"), dil)
-            y = causal(snake(y, _w(t, q + "snake2.alpha"), _w(t, q + "snake2.beta")), _w(t, q + "conv2.weight"), _w(t, q + "conv2.bias"))
-            x = x + y
-    x = causal(snake(x, _w(t, "codec.dec.snake_out.alpha"), _w(t, "codec.dec.snake_out.beta")), _w(t, "codec.dec.conv_out.weight").reshape(1, -1, 7),
-               _w(t, "codec.dec.conv_out.bias").reshape(1))
-    return x.clamp(-1, 1)[0, 0].numpy()
+from codec_f64_ref import torch_codec   # the restatement lives in tests/codec_f64_ref.py; float32 here, as always
 
 
 def test_codec_streaming_equals_full_and_matches_torch(tiny_model, oracle):

@@ -250,3 +250,28 @@ def test_gmax_one(driver):
     assert passes[:5] == [["L1/4C"], ["L2/4C"], ["L1/4C"], ["L2/4C"], ["D10/4C"]]   # its turn after four passes without a seat
     assert passes[5] == ["D10/0F"]                                        # the fence heads the request's tasks now
     assert passes[6:] == [["L1/4C"], ["L2/4C"]]
+
+
+def _drain_e(driver, gmax, live, low):
+    q = lambda tasks: "\n".join(" ".join(str(x) for x in t) for t in tasks)
+    out = driver("epochs 1\ndrain %d %d %d\n%s\n%s\n" % (gmax, len(live), len(low), q(live), q(low)))
+    assert out[-1] == "end"
+    return [ln.split("|")[0].split() for ln in out[:-1]]
+
+
+def test_a_pass_holds_the_generating_chunks_of_one_hand_over(driver):
+    """the thread's passes are the same whether it forms them before or after the next hand-over has arrived: three requests hand over a
+    chunk each in epochs 1 and 2, gmax 2.  Seen one hand-over at a time the passes are {1, 2}, {3}, {1', 2'}, {3'}; with both in the queue
+    at once request 1's second chunk does not take the seat beside request 3's first"""
+    e1, e2 = [(r, 4, "C", 1) for r in (1, 2, 3)], [(r, 4, "C", 2) for r in (1, 2, 3)]
+    apart = _drain_e(driver, 2, e1, []) + _drain_e(driver, 2, e2, [])
+    assert apart == [["L1/4C", "L2/4C"], ["L3/4C"]] * 2
+    assert _drain_e(driver, 2, e1 + e2, []) == apart
+    assert _drain(driver, 2, [t[:3] for t in e1 + e2], []) == [["L1/4C", "L2/4C"], ["L3/4C", "L1/4C"], ["L2/4C", "L3/4C"]]   # one epoch: seats by age alone
+    # tails of another frame count and fences keep their places; the 1-frame tails of one hand-over share a pass
+    live = [(1, 4, "C", 1), (2, 1, "C", 1), (2, 0, "F", 1), (3, 1, "C", 1), (3, 0, "F", 1), (1, 4, "C", 2), (4, 1, "C", 2)]
+    assert _drain_e(driver, 4, live, []) == [["L1/4C"], ["L2/1C", "L3/1C"], ["L2/0F"], ["L3/0F"], ["L1/4C"], ["L4/1C"]]
+    # decode-only chunks carry no epoch: they take the seats left; a decode-only lead binds the pass to the first generating chunk's epoch
+    assert _drain_e(driver, 4, e1[:1] + e2[1:2], [(10, 4, "C", 0), (11, 4, "C", 0)]) == [["L1/4C", "D10/4C", "D11/4C"], ["L2/4C"]]
+    out = driver("epochs 1\nseat 4 4 3 1\n1 4 C 1\n2 4 C 2\n3 4 C 1\n10 4 C 0\n")[0]
+    assert out.split("|")[0].split() == ["D10/4C", "L1/4C", "L3/4C"]

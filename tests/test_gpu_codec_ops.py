@@ -364,7 +364,8 @@ def test_decoder_positions_across_8192_and_the_limit(gpu, oracle, tiny_model):
 
 
 def _staggered(gpu, oracle, path, n_streams, max_group, joins, n_chunks, check, seed):
-    """streams join the group at the chunks in `joins` and decode 4-frame chunks until n_chunks; each stream's PCM vs the oracle's"""
+    """streams join the group at the chunks in `joins` and decode 4-frame chunks until n_chunks; each stream's PCM vs the oracle's.
+    Returns every stream's codes and PCM (test_gpu_codec_pcm_f64.py holds them to float64 per frame)"""
     gd = gpu.Decoder(path, n_streams=n_streams, max_frames=4, max_group=max_group)
     rng = np.random.default_rng(seed)
     G = len(joins)
@@ -386,6 +387,7 @@ def _staggered(gpu, oracle, path, n_streams, max_group, joins, n_chunks, check, 
         oc.reset()
         _pcm_close(np.concatenate(pcm[i]), oc.decode(codes[i]).copy(), "stream %d (joined at chunk %d)" % (i, joins[i]))
     oc.close(); gd.close()
+    return codes, [np.concatenate(p) for p in pcm]
 
 
 def test_decoder_staggered_group_joins(gpu, oracle, tiny_model):
