@@ -6,7 +6,6 @@
 #include <chrono>
 #include "kdev.h"
 #include <functional>
-#include <optional>
 
 namespace q3 {
 
@@ -103,11 +102,9 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         Q3_HIP(hipStreamCreateWithFlags(&st_pf_, hipStreamNonBlocking));
         Q3_HIP(hipEventCreate(&pf_done_)); Q3_HIP(hipEventCreate(&pf_e0_));
         // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row) and the
-        // codes of score rows (64 B a row)
-        arena_pf_cap_ = (size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4; // + [EXT] the fork destinations of a wave
-        Q3_HIP(hipHostMalloc((void**)&arena_pf_, arena_pf_cap_));
-        d_prompt_pf_.alloc((size_t)256 * Q3_EMBD); d_pfa_seq_.alloc(256); d_pfa_slot_.alloc(256); d_pfa_pos_.alloc(4 * 256);
-        d_pfa_codes_.alloc((size_t)256 * 16); d_pfa_ids_.alloc(256); d_fork_dst_pf_.alloc(B);
+        // codes of score rows (64 B a row) + [EXT] the fork destinations of a wave.  Every piece starts on a 64-byte boundary: six pieces a
+        // chunk lose at most 6 x 63 B, over the at most 17 chunks of a 4096-row wave 6426 B, the destinations 63 B more -- inside the 64 KiB slack
+        lane_alloc(pf_, talker_pf_.get(), st_pf_, 256, true, (size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4);
     }
     // ---- per-slot state ----
     hist_stride_ = p.max_steps * 16;
@@ -118,9 +115,6 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     d_rngkey_.zero(); d_draws_.zero(); d_prngkey_.zero(); d_pdraws_.zero(); d_plogits_.alloc((size_t)B * Q3_CODEBOOK_SIZE);
     d_tlogits_.alloc((size_t)B * tl_stride_); d_thidden_.alloc((size_t)B * Q3_EMBD); d_pin_.alloc((size_t)2 * B * dP_);
     d_fb_.alloc((size_t)B * Q3_EMBD);
-    d_prompt_.alloc((size_t)talker_->max_tok() * Q3_EMBD);
-    d_pf_seq_.alloc(talker_->max_tok()); d_pf_slot_.alloc(talker_->max_tok()); d_pf_pos_.alloc(4 * (size_t)talker_->max_tok());
-    d_pf_codes_.alloc((size_t)talker_->max_tok() * 16); d_pf_ids_.alloc(talker_->max_tok()); d_fork_dst_.alloc(B);
     d_hist_.zero(); d_tlogits_.zero(); d_thidden_.zero();
     // predictor routing: pass i (i = 2..15) handles position i of every slot; tables are [16][B] so any graph width can use them
     std::vector<int32_t> seq(B), slot((size_t)16 * B), pos((size_t)16 * B * 4);
@@ -139,8 +133,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         std::vector<q3_u64> k0((size_t)16 * B, pack_key(-INFINITY, 0)), n0(B, pack_key(-INFINITY, 0));
         d_keys_.upload(k0.data(), k0.size()); d_next_key0_.upload(n0.data(), n0.size());
     }
-    arena_cap_ = (size_t)talker_->max_tok() * Q3_EMBD * 4 + (size_t)B * 4096 + ((size_t)1 << 20);
-    Q3_HIP(hipHostMalloc((void**)&arena_, arena_cap_));
+    lane_alloc(ar_, talker_.get(), st_, talker_->max_tok(), false, (size_t)talker_->max_tok() * Q3_EMBD * 4 + (size_t)B * 4096 + ((size_t)1 << 20));
     Q3_HIP(hipDeviceSynchronize()); // memsets / table kernels above ran on other streams than st_
     upload_slot_state();
     if (p.load_codec) {
@@ -165,16 +158,28 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     }
     Q3_HIP(hipStreamSynchronize(st_));
     Q3_HIP(hipDeviceSynchronize());
-    arena_used_ = 0;
+    ar_.cur.reset();
 }
 
-void* Engine::stage_alloc(size_t bytes) {
-    bytes = (bytes + 63) & ~(size_t)63;
-    Q3_CHECK(bytes <= arena_cap_, "staging request larger than the arena");
-    if (arena_used_ + bytes > arena_cap_) { Q3_HIP(hipStreamSynchronize(st_)); arena_used_ = 0; } // everything staged so far has been consumed
-    void* p = arena_ + arena_used_;
-    arena_used_ += bytes;
-    return p;
+void Engine::lane_alloc(PrefillLane& L, Transformer* talker, hipStream_t st, int chunk, bool async, size_t arena_bytes) {
+    L.talker = talker; L.st = st; L.chunk = chunk; L.async = async;
+    L.d_rows.alloc((size_t)chunk * Q3_EMBD); L.d_seq.alloc(chunk); L.d_slot.alloc(chunk); L.d_pos.alloc(4 * (size_t)chunk);
+    L.d_codes.alloc((size_t)chunk * 16); L.d_ids.alloc(chunk); L.d_fork_dst.alloc(B_);
+    L.cur.cap = arena_bytes;
+    Q3_HIP(hipHostMalloc((void**)&L.arena, arena_bytes));
+}
+// The next piece of a lane's staging.  A full AR arena waits for its stream -- everything staged so far has then been consumed -- and starts
+// over; the asynchronous lane's holds a whole wave and never waits.
+void* Engine::stage_take(PrefillLane& L, size_t bytes) {
+    size_t at = L.cur.take(bytes);
+    if (at == StageCursor::NONE) {
+        Q3_CHECK(!L.async, "prefill staging arena overflow");
+        Q3_HIP(hipStreamSynchronize(L.st));
+        L.cur.reset();
+        at = L.cur.take(bytes);
+        Q3_CHECK(at != StageCursor::NONE, "staging request larger than the arena");
+    }
+    return L.arena + at;
 }
 void Engine::h2d(void* dst, const void* src, size_t bytes) {
     void* p = stage_alloc(bytes);
@@ -222,6 +227,20 @@ struct Engine::Req {
     std::string error;
 };
 
+static void push_frames(Chunker& c, const int32_t* codes, int n) { // n frames [n][16] of int32 codes, as the chunker takes them
+    for (int f = 0; f < n; f++) {
+        int64_t fc[16];
+        for (int q = 0; q < 16; q++) fc[q] = codes[(size_t)f * 16 + q];
+        c.push(fc, 16, false);
+    }
+}
+// in bytes: a stream's region holds slot_cap_ native floats, and no format needs more bytes per frame than the native one
+unsigned char* Engine::pcm_stage(const Req& r, size_t add) const {
+    const size_t at = r.pcm_enq * r.sample_bytes();
+    Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
+    return reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r.cs * slot_cap_) + at;
+}
+
 Engine::~Engine() {
     (void)hipSetDevice(dev_);
     try { stop_driver(); } catch (...) {}
@@ -238,8 +257,8 @@ Engine::~Engine() {
     }
     if (pcm_pinned_) (void)hipHostFree(pcm_pinned_);
     if (pre_tails_) (void)hipHostFree(pre_tails_);
-    if (arena_) (void)hipHostFree(arena_);
-    if (arena_pf_) (void)hipHostFree(arena_pf_);
+    if (ar_.arena) (void)hipHostFree(ar_.arena);
+    if (pf_.arena) (void)hipHostFree(pf_.arena);
     if (pf_done_) (void)hipEventDestroy(pf_done_);
     if (pf_e0_) (void)hipEventDestroy(pf_e0_);
     if (st_pf_) (void)hipStreamDestroy(st_pf_);
@@ -395,57 +414,80 @@ void Engine::upload_slot_state() {
     slot_dirty_ = false;
 }
 
-// Prefill (engine.rs:455-462) of newly admitted sequences: all prompts as ONE token stream, chunked by the talker's launch
-// width; tokens of different sequences share a launch (per-token seq/slot/pos routing); each sequence's last token gets the
-// head: code_0 of its first frame (:550-555) + the hidden row the predictor starts from (:565-566).
-void Engine::prefill(const std::vector<Req*>& wave, bool sampled) {
+// Prefill (engine.rs:455-462) of one admission wave on lane L: all prompts as ONE token stream, chunked by the lane's width; tokens of
+// different sequences share a launch (per-token seq/slot/pos routing); each sequence's last token gets the head -- code_0 of its first
+// frame (:550-555) + the hidden row the predictor starts from (:565-566) -- as the lane takes it: head_live or head_staged.  Every chunk
+// is enqueued on L.st; only the AR lane's staging can make the host wait (stage_take).
+void Engine::prefill_wave(PrefillLane& L, const std::vector<Req*>& wave, bool sampled) {
     size_t total = 0;
     std::vector<PromptRef> refs;
     std::vector<Req*> batch; std::vector<std::vector<Req*>> rest; // [EXT] candidate sets: a set's later members add no rows
     split_sets(wave, batch, rest);
     for (Req* r : batch) { total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix}); }
-    const int chunk = talker_->max_tok();
-    std::vector<int32_t> seq(chunk), slot(chunk), pos((size_t)4 * chunk);
     PrefillCursor cur; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb;
     std::vector<char> is_score; // [EXT] scoring: which requests of the wave only want their rows scored
     for (Req* r : batch) is_score.push_back(r->score);
-    talker_->set_same_seq_tokens(true);
+    L.talker->set_same_seq_tokens(true);
     for (size_t done = 0; done < total;) {
-        const size_t n_max = std::min<size_t>(total - done, (size_t)chunk);
-        float* stage = (float*)stage_alloc(n_max * Q3_EMBD * 4);
-        int32_t* hc = (int32_t*)stage_alloc(n_max * 68); // [EXT] resume: codes [rows][16] and ids [rows] of the chunk's feedback rows
-        int32_t* hs = (int32_t*)stage_alloc(n_max * 64); // [EXT] scoring: codes [rows][16] of the chunk's score rows
+        const size_t n_max = std::min<size_t>(total - done, (size_t)L.chunk);
+        float* stage = (float*)stage_take(L, n_max * Q3_EMBD * 4);
+        int32_t* hc = (int32_t*)stage_take(L, n_max * 68); // [EXT] resume: codes [rows][16] and ids [rows] of the chunk's feedback rows
+        int32_t* hs = (int32_t*)stage_take(L, n_max * 64); // [EXT] scoring: codes [rows][16] of the chunk's score rows
+        int32_t* seq = (int32_t*)stage_take(L, n_max * 4); int32_t* slot = (int32_t*)stage_take(L, n_max * 4); int32_t* pos = (int32_t*)stage_take(L, n_max * 16);
         const PrefillCursor before = cur;
-        const int n = pack_prefill_chunk(refs, cur, chunk, stage, seq.data(), slot.data(), pos.data(), lasts, &fb);
+        const int n = pack_prefill_chunk(refs, cur, (int)n_max, stage, seq, slot, pos, lasts, &fb);
         for (auto& run : staged_runs(n, fb))
-            Q3_HIP(hipMemcpyAsync(d_prompt_.p + (size_t)run.first * Q3_EMBD, stage + (size_t)run.first * Q3_EMBD, (size_t)run.second * Q3_EMBD * 4, hipMemcpyHostToDevice, st_));
-        feedback_rows(st_, batch, fb, hc, d_pf_codes_.p, d_pf_ids_.p, d_prompt_.p);
-        h2d(d_pf_seq_.p, seq.data(), (size_t)n * 4); h2d(d_pf_slot_.p, slot.data(), (size_t)n * 4); h2d(d_pf_pos_.p, pos.data(), (size_t)n * 16);
-        TokMeta tm{d_pf_seq_.p, d_pf_slot_.p, d_pf_pos_.p};
-        Transformer::Input in; in.x = d_prompt_.p; in.x_stride = Q3_EMBD;
-        talker_->forward(st_, in, n, tm, kv_t_->view(), nullptr);
-        score_chunk(st_, *talker_, batch, score_head_runs(refs, is_score, before, n), hs);
-        for (auto& lb : lasts)
-          for (size_t m = 0; m <= rest[lb.first].size(); m++) { // [EXT] candidate sets: every member's slot draws from the set's last prompt token
+            Q3_HIP(hipMemcpyAsync(L.d_rows.p + (size_t)run.first * Q3_EMBD, stage + (size_t)run.first * Q3_EMBD, (size_t)run.second * Q3_EMBD * 4, hipMemcpyHostToDevice, L.st));
+        feedback_rows(L.st, batch, fb, hc, L.d_codes.p, L.d_ids.p, L.d_rows.p);
+        Q3_HIP(hipMemcpyAsync(L.d_seq.p, seq, (size_t)n * 4, hipMemcpyHostToDevice, L.st));
+        Q3_HIP(hipMemcpyAsync(L.d_slot.p, slot, (size_t)n * 4, hipMemcpyHostToDevice, L.st));
+        Q3_HIP(hipMemcpyAsync(L.d_pos.p, pos, (size_t)n * 16, hipMemcpyHostToDevice, L.st));
+        TokMeta tm{L.d_seq.p, L.d_slot.p, L.d_pos.p};
+        Transformer::Input in; in.x = L.d_rows.p; in.x_stride = Q3_EMBD;
+        L.talker->forward(L.st, in, n, tm, kv_t_->view(), nullptr);
+        score_chunk(L.st, *L.talker, batch, score_head_runs(refs, is_score, before, n), hs);
+        for (auto& lb : lasts) {
             if (is_score[lb.first]) continue; // no first frame to draw
-            const int sb = m == 0 ? refs[lb.first].slot : rest[lb.first][m - 1]->slot, ti = lb.second;
-            const bool hist = resumed_penalised(batch[lb.first]->r); // [EXT] resume: the first head already sees a history, greedy slots included
-            const bool rec = batch[lb.first]->r.logprobs;       // [EXT] log-probabilities: the first frame's talker columns need the logits
-            if (sampled || hist || rec) {
-                talker_->head(st_, ti, 1, 0, tl_stride_, d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_thidden_.p + (size_t)sb * Q3_EMBD);
-                SampleArgs sa{d_tlogits_.p + (size_t)sb * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + sb, di(SF_TOPK) + sb, df(SF_TOPP) + sb,
-                              di(SF_MASKEOS) + sb, d_rngkey_.p + (size_t)sb * 8, d_draws_.p + sb, d_keys_.p + (size_t)sb * 16, 16};
-                if (hist) head_history(sa, sb);
-                launch_sample(st_, sa, 1);
-                if (rec) first_head_logprobs(st_, d_tlogits_.p + (size_t)sb * tl_stride_, sb, batch[lb.first]->r.n_prefix);
-            } else {
-                ArgmaxEpi am{d_keys_.p + (size_t)sb * 16, 16, di(SF_MASKEOS) + sb, 0};
-                talker_->head(st_, ti, 1, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, d_thidden_.p + (size_t)sb * Q3_EMBD);
-            }
+            if (L.async) head_staged(batch[lb.first], rest[lb.first], lb.second);
+            else head_live(batch[lb.first], rest[lb.first], lb.second, sampled);
         }
         done += (size_t)n;
     }
-    if (batch.size() < wave.size()) fork_sets(st_, batch, rest, (int32_t*)stage_alloc((size_t)B_ * 4), d_fork_dst_.p); // a wave without a set stages nothing more
+    if (batch.size() < wave.size()) fork_sets(L.st, batch, rest, (int32_t*)stage_take(L, (size_t)B_ * 4), L.d_fork_dst.p); // a wave without a set stages nothing more
+}
+SampleArgs Engine::first_head_args(const float* logits_row, int b) const {
+    return SampleArgs{logits_row, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + b, di(SF_TOPK) + b, df(SF_TOPP) + b,
+                      di(SF_MASKEOS) + b, d_rngkey_.p + (size_t)b * 8, d_draws_.p + b, d_keys_.p + (size_t)b * 16, 16};
+}
+// In line: the head of a request's last prompt token `tok` draws code_0 straight into the live arrays, once per member of its set ([EXT]
+// candidate sets: every member's slot draws from the set's last prompt token).  The argmax epilogue, unless something needs the logits.
+void Engine::head_live(Req* lead, const std::vector<Req*>& rest, int tok, bool sampled) {
+    const bool hist = resumed_penalised(lead->r); // [EXT] resume: the first head already sees a history, greedy slots included
+    const bool rec = lead->r.logprobs;            // [EXT] log-probabilities: the first frame's talker columns need the logits
+    for (size_t m = 0; m <= rest.size(); m++) {
+        const int sb = m == 0 ? lead->slot : rest[m - 1]->slot;
+        float* logits = d_tlogits_.p + (size_t)sb * tl_stride_; float* hidden = d_thidden_.p + (size_t)sb * Q3_EMBD;
+        if (sampled || hist || rec) {
+            talker_->head(st_, tok, 1, 0, tl_stride_, logits, tl_stride_, nullptr, -1, hidden);
+            SampleArgs sa = first_head_args(logits, sb);
+            if (hist) head_history(sa, sb);
+            launch_sample(st_, sa, 1);
+            if (rec) first_head_logprobs(st_, logits, sb, lead->r.n_prefix);
+        } else {
+            ArgmaxEpi am{d_keys_.p + (size_t)sb * 16, 16, di(SF_MASKEOS) + sb, 0};
+            talker_->head(st_, tok, 1, 0, tl_stride_, nullptr, 0, &am, Q3_SAMPLE_END, hidden);
+        }
+    }
+}
+// Asynchronously: logits + hidden of the LAST prompt token (engine.rs:550-554,565-566) wait in the staging rows of the request's slot;
+// code_0 is drawn at activation.  [EXT] candidate sets: the staged rows reach every member; activate() stays per slot.
+void Engine::head_staged(Req* lead, const std::vector<Req*>& rest, int tok) {
+    float* logits = d_pf_logits_.p + (size_t)lead->slot * tl_stride_; float* hidden = d_pf_hidden_.p + (size_t)lead->slot * Q3_EMBD;
+    talker_pf_->head(st_pf_, tok, 1, 0, tl_stride_, logits, tl_stride_, nullptr, -1, hidden);
+    for (Req* m : rest) {
+        Q3_HIP(hipMemcpyAsync(d_pf_logits_.p + (size_t)m->slot * tl_stride_, logits, (size_t)tl_stride_ * 4, hipMemcpyDeviceToDevice, st_pf_));
+        Q3_HIP(hipMemcpyAsync(d_pf_hidden_.p + (size_t)m->slot * Q3_EMBD, hidden, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_pf_));
+    }
 }
 
 // [EXT] candidate sets.  The members of a set stand together in a wave (they were queued together and admitted whole); the first is prefilled.
@@ -500,7 +542,7 @@ void Engine::feedback_rows(hipStream_t st, const std::vector<Req*>& batch, const
         at += f.n;
     }
 }
-// the sampler arguments of a resumed slot's first head: the penalty with the history the prefix seeded (activate), no current frame
+// the sampler arguments of a resumed slot's first head: the penalty with the history the prefix seeded (go_live), no current frame
 void Engine::head_history(SampleArgs& sa, int b) const {
     sa.penalty = df(SF_PEN) + b; sa.hist = d_hist_.p + (size_t)b * hist_stride_; sa.hist_stride = hist_stride_; sa.hist_len = di(SF_NFRAMES) + b;
     sa.cur_key = nullptr; sa.cur_stride = 0;
@@ -575,8 +617,6 @@ void Engine::decoder_main() {
                 for (int g = 0; g < G; g++) {
                     Req* r = grp[g].r;
                     fmt[g] = r->fmt; converts = converts || !pcm_format_native(r->fmt);
-                    // in bytes: a stream's region holds slot_cap_ native floats, and no format needs more bytes per frame than the native one
-                    const size_t at = r->pcm_enq * r->sample_bytes();
                     size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
                     rate[g] = r->rate_pct;
                     if (r->rate_pct != 100) { // the hops that become available with these frames: possibly none, at a slow rate more than native
@@ -584,8 +624,7 @@ void Engine::decoder_main() {
                         add = (size_t)(tsm_out_samples(r->rate_pct, r->tsm_native + (int64_t)nf * spf, false) - tsm_out_samples(r->rate_pct, r->tsm_native, false)) * r->sample_bytes();
                         r->tsm_native += (int64_t)nf * spf;
                     }
-                    Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
-                    streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r->cs * slot_cap_) + at);
+                    streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(pcm_stage(*r, add));
                     std::copy(grp[g].codes.begin(), grp[g].codes.end(), codes.begin() + (size_t)g * nf * 16);
                 }
                 // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
@@ -598,11 +637,9 @@ void Engine::decoder_main() {
             for (auto& t : grp) {
                 Req* r = t.r;
                 if (!t.fence || r->rate_pct == 100 || r->cancel || r->cs < 0) continue;
-                const size_t at = r->pcm_enq * r->sample_bytes();
                 const size_t add = (size_t)(tsm_out_samples(r->rate_pct, r->tsm_native, true) - tsm_out_samples(r->rate_pct, r->tsm_native, false)) * r->sample_bytes();
-                Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
                 int64_t n = 0;
-                codec_->tsm_flush_async(st2_[lane], r->cs, reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r->cs * slot_cap_) + at, &n, lane);
+                codec_->tsm_flush_async(st2_[lane], r->cs, pcm_stage(*r, add), &n, lane);
                 r->pcm_enq += (size_t)n;
             }
             // [EXT] codec preambles: a build's fence enqueues the snapshot behind its last chunk (this lane has waited for it above)
@@ -761,6 +798,20 @@ void Engine::set_logprobs(bool on) {
     lp_on_ = on;
 }
 
+Engine::Req& Engine::req(int64_t id) {
+    auto it = reqs_.find(id);
+    Q3_CHECK(it != reqs_.end(), "unknown request id");
+    return *it->second;
+}
+int64_t Engine::enqueue(std::unique_ptr<Req> r, std::deque<Req*>& queue) {
+    const int64_t id = r->id = next_id_++;
+    queue.push_back(r.get());
+    reqs_[id] = std::move(r);
+    wake_++;
+    cv_.notify_all();
+    return id;
+}
+
 int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, bool may_record) {
     validate(g);
     if (g.n_trail > 0 || g.open) ensure_text_stream();
@@ -787,13 +838,7 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     // [EXT] codec preambles: the engine-level setting or the caller's (a voice's), read once per request; a blocking batch is never primed
     const int pid = preamble_of_request(r->want_pcm && may_record, g.preamble, eng_pre_);
     if (pid >= 0) pre_attach(r.get(), pid); // throws before anything is queued
-    r->id = next_id_++;
-    Req* raw = r.get();
-    reqs_[raw->id] = std::move(r);
-    pending_.push_back(raw);
-    wake_++;
-    cv_.notify_all();
-    return raw->id;
+    return enqueue(std::move(r), pending_);
 }
 
 // [EXT] candidate sets: n consecutive queue entries that share one copy of the prompt and trail; each is what submit() would queue with its seed.
@@ -830,16 +875,8 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         for (int i = 0; pid >= 0 && i < n; i++) pre_attach(rs[i].get(), pid);
     }
     const int64_t set = next_set_++;
-    for (int i = 0; i < n; i++) {
-        Req* raw = rs[i].get();
-        raw->set = set; raw->id = next_id_++;
-        req_ids[i] = raw->id;
-        reqs_[raw->id] = std::move(rs[i]);
-        pending_.push_back(raw);
-    }
+    for (int i = 0; i < n; i++) { rs[i]->set = set; req_ids[i] = enqueue(std::move(rs[i]), pending_); }
     cand_sets_++;
-    wake_++;
-    cv_.notify_all();
 }
 
 // [EXT] live text append.  The caller's thread only copies under mu_; the scheduler thread moves the ids to the device between frame
@@ -848,9 +885,7 @@ int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
     Q3_CHECK(n >= 0, "n must be >= 0");
     Q3_CHECK(n == 0 || ids, "ids missing");
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    Req& r = *it->second;
+    Req& r = req(id);
     Q3_CHECK(r.r.open, "the request was not submitted with an open trail");
     Q3_CHECK(!r.closed, "the request's trail is already closed");
     if (r.cancel || (r.state != REQ_QUEUED && r.state != REQ_RUNNING)) return 1; // cancelled, finished (EOS / max_steps), done or failed: nothing appended
@@ -865,9 +900,7 @@ int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
 
 void Engine::trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* closed) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    const Req& r = *it->second;
+    const Req& r = req(id);
     Q3_CHECK(!r.decode, "a decode-only request has no trail");
     const int n = (int)r.trail_ids().size();
     *n_appended = n; *n_consumed = std::min(r.fed, n); *closed = !r.r.open || r.closed;
@@ -898,9 +931,7 @@ void Engine::collect_appends() {
 // the device-side work between two frame groups; a request still in the queue owns nothing and ends right here.
 int Engine::cancel(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    Req& r = *it->second;
+    Req& r = req(id);
     if (req_ended(r.state)) return 1;
     if (r.cancel) return 0; // the first cancel is still pending
     r.cancel = true;
@@ -996,17 +1027,20 @@ void Engine::admit(bool stalled) {
     }
     if (async_pf_ && n_active_ > 0) { prefill_async(batch); return; } // sequences are running: do not stall them
     // ---- in-line form (nothing is running, or a single-slot engine): one batched prefill of the whole wave on the AR stream ----
-    arena_used_ = 0; // st_ is idle between scheduler operations
     for (Req* r : batch) kv_t_->release(r->slot), kv_t_->ensure(r->slot, kv_positions(r->r, r->score), st_);
-    pf_batch_ = batch;
     bool sampled = live_variant(slots_).sampled; // of the prefill heads: the wave joins whatever is live
-    for (Req* r : batch) if (r->r.sampler.temperature > 0.0f) sampled = true;
+    std::vector<Req*> live, scores; // [EXT] scoring: a score request never goes live; its rows are computed by the walk
+    for (Req* r : batch) {
+        if (r->r.sampler.temperature > 0.0f) sampled = true;
+        (r->score ? scores : live).push_back(r);
+    }
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
-    activate(); // slot state first: the prefill heads write code_0 / hidden straight into the live arrays
+    go_live(live); // slot state first: the prefill heads write code_0 / hidden straight into the live arrays
+    { std::lock_guard<std::mutex> lk(mu_); n_active_ += (int)live.size(); }
     Q3_HIP(hipEventRecord(e0, st_));
     for (Req* r : batch) Q3_HIP(hipEventRecord(r->ev_admit, st_)); // the AR stream is idle here: marks "admitted"
-    prefill(batch, sampled);
+    prefill_wave(ar_, batch, sampled);
     Q3_HIP(hipEventRecord(e1, st_));
     Q3_HIP(hipStreamSynchronize(st_));
     { float ms = 0; Q3_HIP(hipEventElapsedTime(&ms, e0, e1)); stats.prefill_ms += ms; }
@@ -1016,8 +1050,6 @@ void Engine::admit(bool stalled) {
         std::lock_guard<std::mutex> lk(mu_);
         for (Req* r : batch) r->prefill_ms = t - r->t_submit;
     }
-    std::vector<Req*> scores; // [EXT] scoring: their rows are computed; they were never live
-    for (Req* r : batch) if (r->score) scores.push_back(r);
     finish_scores(scores);
 }
 
@@ -1033,14 +1065,8 @@ int64_t Engine::submit_decode(const int32_t* codes, int n) {
     r->t_submit = now_ms();
     std::lock_guard<std::mutex> lk(mu_);
     if (eng_pre_ >= 0) pre_attach(r.get(), eng_pre_); // [EXT] codec preambles: the engine-level setting, read once per request
-    r->id = next_id_++;
-    Req* raw = r.get();
-    reqs_[raw->id] = std::move(r);
-    decode_q_.push_back(raw);
     dec_reqs_++;
-    wake_++;
-    cv_.notify_all();
-    return raw->id;
+    return enqueue(std::move(r), decode_q_);
 }
 
 // scheduler thread, after admit(): the generating wave has taken its streams; decode-only requests take free ones in order, up to decode_w_
@@ -1067,11 +1093,7 @@ void Engine::enqueue_decodes() {
         std::vector<DecTask> tasks;
         tasks.push_back(DecTask{r, {}, false, false, true});
         Chunker cut([&](const int64_t* codes, int n_codes, bool is_final) { tasks.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false}); });
-        for (int f = 0; f < r->fed; f++) {
-            int64_t fc[16];
-            for (int q = 0; q < 16; q++) fc[q] = r->codes[(size_t)f * 16 + q];
-            cut.push(fc, 16, false);
-        }
+        push_frames(cut, r->codes.data(), r->fed);
         cut.push(nullptr, 0, true);
         tasks.push_back(DecTask{r, {}, false, true, false});
         {
@@ -1083,155 +1105,104 @@ void Engine::enqueue_decodes() {
     }
 }
 
-// Prefill of one admission wave on the second talker instance / stream: every chunk is enqueued without host waits (the prompts of
-// the wave sit in their own pinned arena); each sequence's last token leaves its logits row and hidden row in staging buffers.
+// The asynchronous form's start: the wave is prefilled on the second talker context and its stream while the frame graph keeps stepping
+// the running sequences.  Nothing here waits: every chunk is enqueued, and pf_done_ behind the last tells step() when to activate().
 void Engine::prefill_async(const std::vector<Req*>& wave) {
-    size_t total = 0;
-    std::vector<PromptRef> refs;
-    std::vector<Req*> batch; std::vector<std::vector<Req*>> rest; // [EXT] candidate sets: a set's later members add no rows
-    split_sets(wave, batch, rest);
-    for (Req* r : batch) { total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix}); }
     for (Req* r : wave) {
         kv_t_->release(r->slot);
         kv_t_->ensure(r->slot, kv_positions(r->r, r->score), st_pf_);
     }
-    std::vector<char> is_score;
-    for (Req* r : batch) is_score.push_back(r->score);
-    const int chunk = talker_pf_->max_tok();
-    unsigned char* cur = arena_pf_;
-    PrefillCursor pc; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb; size_t done_tok = 0;
+    pf_.cur.reset(); // the previous wave has been activated: its staging has been consumed
     Q3_HIP(hipEventRecord(pf_e0_, st_pf_));
     for (Req* r : wave) Q3_HIP(hipEventRecord(r->ev_admit, st_pf_));
-    talker_pf_->set_same_seq_tokens(true);
-    while (done_tok < total) {
-        const int n_max = (int)std::min<size_t>(total - done_tok, (size_t)chunk);
-        float* stage = (float*)cur; cur += (size_t)n_max * Q3_EMBD * 4;
-        int32_t* seq = (int32_t*)cur; cur += (size_t)n_max * 4;
-        int32_t* slot = (int32_t*)cur; cur += (size_t)n_max * 4;
-        int32_t* pos = (int32_t*)cur; cur += (size_t)n_max * 16;
-        int32_t* hc = (int32_t*)cur; cur += (size_t)n_max * 68; // [EXT] resume: codes and ids of the chunk's feedback rows
-        int32_t* hs = (int32_t*)cur; cur += (size_t)n_max * 64; // [EXT] scoring: codes of the chunk's score rows
-        const PrefillCursor before = pc;
-        Q3_CHECK((size_t)(cur - arena_pf_) <= arena_pf_cap_, "prefill staging arena overflow");
-        const int n = pack_prefill_chunk(refs, pc, n_max, stage, seq, slot, pos, lasts, &fb);
-        for (auto& run : staged_runs(n, fb))
-            Q3_HIP(hipMemcpyAsync(d_prompt_pf_.p + (size_t)run.first * Q3_EMBD, stage + (size_t)run.first * Q3_EMBD, (size_t)run.second * Q3_EMBD * 4, hipMemcpyHostToDevice, st_pf_));
-        feedback_rows(st_pf_, batch, fb, hc, d_pfa_codes_.p, d_pfa_ids_.p, d_prompt_pf_.p);
-        Q3_HIP(hipMemcpyAsync(d_pfa_seq_.p, seq, (size_t)n * 4, hipMemcpyHostToDevice, st_pf_));
-        Q3_HIP(hipMemcpyAsync(d_pfa_slot_.p, slot, (size_t)n * 4, hipMemcpyHostToDevice, st_pf_));
-        Q3_HIP(hipMemcpyAsync(d_pfa_pos_.p, pos, (size_t)n * 16, hipMemcpyHostToDevice, st_pf_));
-        TokMeta tm{d_pfa_seq_.p, d_pfa_slot_.p, d_pfa_pos_.p};
-        Transformer::Input in; in.x = d_prompt_pf_.p; in.x_stride = Q3_EMBD;
-        talker_pf_->forward(st_pf_, in, n, tm, kv_t_->view(), nullptr);
-        score_chunk(st_pf_, *talker_pf_, batch, score_head_runs(refs, is_score, before, n), hs);
-        for (auto& lb : lasts) { // logits + hidden of the LAST prompt token (engine.rs:550-554,565-566); code_0 is drawn at activation
-            if (is_score[lb.first]) continue;
-            const int sb = refs[lb.first].slot;
-            talker_pf_->head(st_pf_, lb.second, 1, 0, tl_stride_, d_pf_logits_.p + (size_t)sb * tl_stride_, tl_stride_, nullptr, -1, d_pf_hidden_.p + (size_t)sb * Q3_EMBD);
-            for (Req* m : rest[lb.first]) { // [EXT] candidate sets: the staged rows reach every member; activate() stays per slot
-                Q3_HIP(hipMemcpyAsync(d_pf_logits_.p + (size_t)m->slot * tl_stride_, d_pf_logits_.p + (size_t)sb * tl_stride_, (size_t)tl_stride_ * 4, hipMemcpyDeviceToDevice, st_pf_));
-                Q3_HIP(hipMemcpyAsync(d_pf_hidden_.p + (size_t)m->slot * Q3_EMBD, d_pf_hidden_.p + (size_t)sb * Q3_EMBD, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_pf_));
-            }
-        }
-        done_tok += n;
-    }
-    Q3_CHECK((size_t)(cur - arena_pf_) + (size_t)B_ * 4 <= arena_pf_cap_, "prefill staging arena overflow");
-    if (batch.size() < wave.size()) fork_sets(st_pf_, batch, rest, (int32_t*)cur, d_fork_dst_pf_.p);
+    prefill_wave(pf_, wave, false);
     Q3_HIP(hipEventRecord(pf_done_, st_pf_));
     pf_batch_ = wave;
     n_prefilling_ = (int)wave.size();
 }
 
-// The admission wave joins the frame graph: slot state (positions, sampler parameters, RNG stream, frame counters) goes live, and --
-// asynchronous form -- the staged hidden row is copied in and code_0 of the first frame is drawn from the staged logits with the
-// slot's own sampler state (greedy slots take the sampler kernel's first-max branch).  Runs on st_ between two frame groups.
+// The slots of a wave's requests join the frame graph: slot state (positions, sampler parameters, RNG stream, frame counters) goes live.
+// Runs on st_ between two scheduler operations; in line before the walk, asynchronously behind it (activate).
+void Engine::go_live(const std::vector<Req*>& batch) {
+    ar_.cur.reset(); // st_ is idle between scheduler operations
+    q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
+    bool prefix_pcm = false; // [EXT] resume: the chunks the wave's prefixes make up are one hand-over to the decoder thread
+    for (Req* r : batch) prefix_pcm = prefix_pcm || (r->want_pcm && r->r.n_prefix >= 4);
+    {
+        DecHold hold(this, codec_ != nullptr && prefix_pcm);
+        for (Req* r : batch) {
+            const int b = r->slot;
+            slots_.load(b, r->r);
+            // [EXT] resume: frame k's code_0 is talker draw k and the predictor stream stands at 15 k; greedy streams stay at 0.  The history row
+            // takes the prefix frames as k_advance_keys would have written them, and the chunker the chunks the scheduler would have cut.
+            const int k = r->r.n_prefix;
+            const uint32_t draws = r->r.sampler.temperature > 0.0f ? (uint32_t)k : 0u, pdraws = 15u * (uint32_t)k;
+            if (k > 0) {
+                h2d(d_hist_.p + (size_t)b * hist_stride_, r->prefix_own.data(), (size_t)k * 64);
+                push_frames(*r->chunker, r->prefix_own.data(), k);
+            }
+            StdRng rng(r->seed); // llama/mod.rs:648: the device regenerates this ChaCha12 stream from the key and a draw counter
+            h2d(d_rngkey_.p + (size_t)b * 8, rng.key(), 32);
+            h2d(d_draws_.p + b, &draws, 4);
+            if (r->r.opts.pred_sampled()) { // [EXT] the predictor's own stream: seed_from_u64(seed ^ Q3_PRED_SEED_XOR)
+                StdRng prng(r->seed ^ (uint64_t)Q3_PRED_SEED_XOR);
+                h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
+                h2d(d_pdraws_.p + b, &pdraws, 4);
+            }
+            h_pend_[b].clear();
+            std::vector<int32_t> ids; // [EXT] streaming text: the slot's trailing ids -- of an open trail those appended so far (later: collect_appends)
+            { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_ids(); slots_.hi(SF_OPEN)[b] = r->r.open && !r->closed; }
+            slots_.hi(SF_NTRAIL)[b] = (int)ids.size(); // upload_slot_state below sends the count and the flag
+            if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
+            h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);
+            h2d(d_next_key0_.p + b, armed, 8);
+            if (lp_ready_.load()) { // [EXT] log-probabilities: the slot's record flag; a recording slot's rows start as "not computed"
+                const int32_t rec = r->r.logprobs ? 1 : 0;
+                h2d(d_lp_rec_.p + b, &rec, 4);
+                if (rec) Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_lp_.p + (size_t)b * lp_rows_ * Q3_LOGPROB_COLS), (int)q3_f32_bits(Q3_LOGPROB_NONE),
+                                                  (size_t)lp_rows_ * Q3_LOGPROB_COLS, st_));
+            }
+            slots_.live[b] = 1;
+        }
+    }
+    upload_slot_state();
+}
+
+// The asynchronous wave's completion, on st_ between two frame groups once pf_done_ has completed: its requests go live, the staged hidden
+// row of each is copied in and code_0 of its first frame is drawn from the staged logits with the slot's own sampler state (greedy slots
+// take the sampler kernel's first-max branch).
 void Engine::activate() {
-    if (pf_batch_.empty()) return;
-    std::vector<Req*> batch, dropped;
+    std::vector<Req*> batch, dropped, scores;
     batch.swap(pf_batch_);
-    if (n_prefilling_ > 0) { // [EXT] requests cancelled while the asynchronous wave ran do not go live; their wave-mates are not disturbed
+    {   // [EXT] requests cancelled while the wave ran do not go live; their wave-mates are not disturbed
         std::lock_guard<std::mutex> lk(mu_);
         const double t = now_ms();
         for (Req* r : batch) if (r->cancel) { r->prefill_ms = t - r->t_submit; dropped.push_back(r); }
         batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->cancel; }), batch.end());
     }
     for (Req* r : dropped) retire(r, false); // slot, KV pages and -- through the fence, behind the reset task already queued -- codec stream
-    std::vector<Req*> scores; // [EXT] scoring: a score request never goes live; an asynchronous wave's end here (the in-line form's: admit)
-    for (Req* r : batch) if (r->score) scores.push_back(r);
+    for (Req* r : batch) if (r->score) scores.push_back(r); // [EXT] scoring: a score request never goes live
     batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->score; }), batch.end());
-    arena_used_ = 0; // st_ is idle between scheduler operations
-    q3_u64 armed[17]; std::fill_n(armed, 17, pack_key(-INFINITY, 0));
-    bool prefix_pcm = false; // [EXT] resume: the chunks the wave's prefixes make up are one hand-over to the decoder thread
-    for (Req* r : batch) prefix_pcm = prefix_pcm || (r->want_pcm && r->r.n_prefix >= 4);
-    std::optional<DecHold> hold;
-    hold.emplace(this, codec_ != nullptr && prefix_pcm);
+    go_live(batch);
     for (Req* r : batch) {
         const int b = r->slot;
-        slots_.load(b, r->r);
-        // [EXT] resume: frame k's code_0 is talker draw k and the predictor stream stands at 15 k; greedy streams stay at 0.  The history row
-        // takes the prefix frames as k_advance_keys would have written them, and the chunker the chunks the scheduler would have cut.
-        const int k = r->r.n_prefix;
-        const uint32_t draws = r->r.sampler.temperature > 0.0f ? (uint32_t)k : 0u, pdraws = 15u * (uint32_t)k;
-        if (k > 0) {
-            h2d(d_hist_.p + (size_t)b * hist_stride_, r->prefix_own.data(), (size_t)k * 64);
-            for (int f = 0; f < k; f++) {
-                int64_t fc[16];
-                for (int q = 0; q < 16; q++) fc[q] = r->prefix_own[(size_t)f * 16 + q];
-                r->chunker->push(fc, 16, false);
-            }
-        }
-        StdRng rng(r->seed); // llama/mod.rs:648: the device regenerates this ChaCha12 stream from the key and a draw counter
-        h2d(d_rngkey_.p + (size_t)b * 8, rng.key(), 32);
-        h2d(d_draws_.p + b, &draws, 4);
-        if (r->r.opts.pred_sampled()) { // [EXT] the predictor's own stream: seed_from_u64(seed ^ Q3_PRED_SEED_XOR)
-            StdRng prng(r->seed ^ (uint64_t)Q3_PRED_SEED_XOR);
-            h2d(d_prngkey_.p + (size_t)b * 8, prng.key(), 32);
-            h2d(d_pdraws_.p + b, &pdraws, 4);
-        }
-        h_pend_[b].clear();
-        std::vector<int32_t> ids; // [EXT] streaming text: the slot's trailing ids -- of an open trail those appended so far (later: collect_appends)
-        { std::lock_guard<std::mutex> lk(mu_); ids = r->trail_ids(); slots_.hi(SF_OPEN)[b] = r->r.open && !r->closed; }
-        slots_.hi(SF_NTRAIL)[b] = (int)ids.size(); // upload_slot_state below sends the count and the flag
-        if (!ids.empty()) h2d(d_trail_.p + (size_t)b * p_.max_prompt, ids.data(), ids.size() * 4);
-        h2d(d_keys_.p + (size_t)b * 16, armed, 16 * 8);
-        h2d(d_next_key0_.p + b, armed, 8);
-        if (lp_ready_.load()) { // [EXT] log-probabilities: the slot's record flag; a recording slot's rows start as "not computed"
-            const int32_t rec = r->r.logprobs ? 1 : 0;
-            h2d(d_lp_rec_.p + b, &rec, 4);
-            if (rec) Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_lp_.p + (size_t)b * lp_rows_ * Q3_LOGPROB_COLS), (int)q3_f32_bits(Q3_LOGPROB_NONE),
-                                              (size_t)lp_rows_ * Q3_LOGPROB_COLS, st_));
-        }
-        slots_.live[b] = 1;
+        Q3_HIP(hipMemcpyAsync(d_thidden_.p + (size_t)b * Q3_EMBD, d_pf_hidden_.p + (size_t)b * Q3_EMBD, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_));
+        SampleArgs sa = first_head_args(d_pf_logits_.p + (size_t)b * tl_stride_, b);
+        if (resumed_penalised(r->r)) head_history(sa, b);
+        launch_sample(st_, sa, 1);
+        if (r->r.logprobs) first_head_logprobs(st_, d_pf_logits_.p + (size_t)b * tl_stride_, b, r->r.n_prefix);
     }
-    hold.reset();
-    upload_slot_state();
-    bool async_wave = false;
-    if (n_prefilling_ > 0) { // the wave was prefilled on the second talker instance
-        float ms = 0;
-        Q3_HIP(hipEventElapsedTime(&ms, pf_e0_, pf_done_));
-        stats.prefill_ms += ms;
-        for (Req* r : batch) {
-            const int b = r->slot;
-            Q3_HIP(hipMemcpyAsync(d_thidden_.p + (size_t)b * Q3_EMBD, d_pf_hidden_.p + (size_t)b * Q3_EMBD, (size_t)Q3_EMBD * 4, hipMemcpyDeviceToDevice, st_));
-            SampleArgs sa{d_pf_logits_.p + (size_t)b * tl_stride_, tl_stride_, Q3_SAMPLE_END, df(SF_TEMP) + b, di(SF_TOPK) + b, df(SF_TOPP) + b,
-                          di(SF_MASKEOS) + b, d_rngkey_.p + (size_t)b * 8, d_draws_.p + b, d_keys_.p + (size_t)b * 16, 16};
-            if (resumed_penalised(r->r)) head_history(sa, b);
-            launch_sample(st_, sa, 1);
-            if (r->r.logprobs) first_head_logprobs(st_, d_pf_logits_.p + (size_t)b * tl_stride_, b, r->r.n_prefix);
-        }
-        Q3_HIP(hipStreamSynchronize(st_));
-        n_prefilling_ = 0;
+    Q3_HIP(hipStreamSynchronize(st_));
+    { float ms = 0; Q3_HIP(hipEventElapsedTime(&ms, pf_e0_, pf_done_)); stats.prefill_ms += ms; }
+    n_prefilling_ = 0;
+    {
         const double t = now_ms();
         std::lock_guard<std::mutex> lk(mu_);
         for (Req* r : batch) r->prefill_ms = t - r->t_submit;
         for (Req* r : scores) r->prefill_ms = t - r->t_submit;
         n_active_ += (int)batch.size();
-        async_wave = true;
-    } else {
-        std::lock_guard<std::mutex> lk(mu_);
-        n_active_ += (int)batch.size();
     }
-    if (async_wave) finish_scores(scores);
+    finish_scores(scores);
 }
 
 // [EXT] scoring given frames.  Like the log-probability buffers, the state goes to the device on first use, under the same locks.
@@ -1282,13 +1253,7 @@ int64_t Engine::submit_score(const float* prompt, int n_prompt, const int32_t* t
     r->prefix_own.assign(codes, codes + (size_t)n * 16); g.prefix = r->prefix_own.data();
     r->t_submit = now_ms();
     std::lock_guard<std::mutex> lk(mu_);
-    r->id = next_id_++;
-    Req* raw = r.get();
-    reqs_[raw->id] = std::move(r);
-    pending_.push_back(raw);
-    wake_++;
-    cv_.notify_all();
-    return raw->id;
+    return enqueue(std::move(r), pending_);
 }
 
 // The score rows of one prefill chunk, behind the chunk's forward on its stream: per run the talker head over the rows (logits and hidden rows
@@ -1336,7 +1301,7 @@ void Engine::finish_scores(const std::vector<Req*>& scores) {
         { std::lock_guard<std::mutex> lk(mu_); cancelled = r->cancel; }
         const float* rows = nullptr;
         if (!cancelled) {
-            arena_used_ = 0;
+            ar_.cur.reset();
             rows = (const float*)d2h_begin(d_sc_out_.p + (size_t)b * p_.max_steps * Q3_LOGPROB_COLS, (size_t)n * Q3_LOGPROB_COLS * 4);
             Q3_HIP(hipStreamSynchronize(st_));
         }
@@ -1398,7 +1363,7 @@ void Engine::run_group() {
     for (int b = 0; b < B_; b++)
         if (slots_.live[b]) { hi = b + 1; remaining = std::max(remaining, slot_req_[b]->r.max_steps - h_nfr[b]); }
     const FrameVariant v = live_variant(slots_);
-    arena_used_ = 0; // st_ is idle between scheduler operations: everything staged earlier has been consumed
+    ar_.cur.reset(); // st_ is idle between scheduler operations: everything staged earlier has been consumed
     for (int b = 0; b < B_; b++) // [EXT] appended ids collected since the last group: the new tail of the slot's id row
         if (!h_pend_[b].empty()) {
             h2d(d_trail_.p + (size_t)b * p_.max_prompt + h_pend_off_[b], h_pend_[b].data(), h_pend_[b].size() * 4);
@@ -1458,11 +1423,7 @@ void Engine::run_group() {
                 if (p_lp[b]) r->lp.insert(r->lp.end(), p_lp[b], p_lp[b] + (size_t)nnew * Q3_LOGPROB_COLS);
                 r->fed = h_nfr[b];
             }
-            for (int f = 0; f < nnew; f++) {
-                int64_t fc[16];
-                for (int q = 0; q < 16; q++) fc[q] = hbuf[(size_t)f * 16 + q];
-                r->chunker->push(fc, 16, false);
-            }
+            push_frames(*r->chunker, hbuf, nnew);
             stats.frames += nnew;
         }
         if (h_fin[b] || h_nfr[b] >= r->r.max_steps) retire(r, true);
@@ -1510,9 +1471,7 @@ bool Engine::step() {
 
 ReqStatus Engine::poll(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    const Req& r = *it->second;
+    const Req& r = req(id);
     ReqStatus s;
     const bool ended = r.state == REQ_DONE || r.state == REQ_CANCELLED; // t_done is set, the PCM sits in r.pcm
     s.state = r.state; s.n_frames = r.fed; s.n_pcm = ended ? r.pcm_n : (int64_t)r.pcm_ready;
@@ -1525,9 +1484,7 @@ ReqStatus Engine::poll(int64_t id) {
 
 void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, float* pcm, int64_t pcm_off, int64_t pcm_cap, int* got_frames, int64_t* got_pcm) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    const Req& r = *it->second;
+    const Req& r = req(id);
     if (pcm) Q3_CHECK(r.fmt.encoding == Q3_PCM_F32, "the request delivers int16 PCM: fetch it with fetch_pcm16"); // [EXT] output formats; nothing is copied
     int nf = 0; int64_t np = 0;
     if (codes && frame_off >= 0 && frame_off < r.fed) {
@@ -1559,15 +1516,11 @@ void Engine::set_output_format(const q3tts_pcm_format* f) {
 }
 q3tts_pcm_format Engine::request_format(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    return it->second->fmt;
+    return req(id).fmt;
 }
 void Engine::fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    const Req& r = *it->second;
+    const Req& r = req(id);
     Q3_CHECK(r.fmt.encoding == Q3_PCM_S16, "the request delivers f32 PCM: fetch it with fetch");
     Q3_CHECK(out && off >= 0, "null buffer or negative offset");
     const int64_t n = copy_pcm(r, out, off, cap);
@@ -1593,9 +1546,7 @@ void Engine::take_rate(Req* r, int max_steps, int given) const {
 }
 int Engine::request_speech_rate(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    return it->second->rate_pct;
+    return req(id).rate_pct;
 }
 void Engine::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
     *chunks = *frames_out = *flushes = 0;
@@ -1640,12 +1591,7 @@ int Engine::preamble_create(const int32_t* codes, int n) {
     Preamble& p = pres_[pid];
     p.n = n; p.tail = pre_tail_free_.back(); pre_tail_free_.pop_back();
     r->build_pre = pid;
-    r->id = next_id_++;
-    Req* raw = r.get();
-    reqs_[raw->id] = std::move(r);
-    decode_q_.push_back(raw);
-    wake_++;
-    cv_.notify_all();
+    enqueue(std::move(r), decode_q_);
     return pid;
 }
 void Engine::preamble_poll(int id, int* state, int* n_frames) {
@@ -1706,9 +1652,7 @@ void Engine::set_preamble(int preamble_id) {
 }
 int Engine::request_preamble(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    return it->second->pre;
+    return req(id).pre;
 }
 void Engine::preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot) const {
     *built = pre_built_.load(); *restores = pre_restores_.load();
@@ -1717,9 +1661,7 @@ void Engine::preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_pe
 
 void Engine::fetch_logprobs(int64_t id, float* out, int frame_off, int max_frames, int* got_frames) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    const Req& r = *it->second;
+    const Req& r = req(id);
     Q3_CHECK(r.r.logprobs || r.score, "the request does not record log-probabilities (q3tts_engine_set_logprobs was off when it was submitted)");
     int nf = 0;
     if (out && frame_off >= 0 && frame_off < r.fed && max_frames > 0) {
@@ -1735,9 +1677,7 @@ bool Engine::wait(int64_t id, double timeout_ms) {
     for (;;) {
         {
             std::unique_lock<std::mutex> lk(mu_);
-            auto it = reqs_.find(id);
-            Q3_CHECK(it != reqs_.end(), "unknown request id");
-            if (req_ended(it->second->state)) return true;
+            if (req_ended(req(id).state)) return true;
             if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
             if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
             // every live slot waits for text: no busy loop until another thread submits or appends
@@ -1750,11 +1690,10 @@ bool Engine::wait(int64_t id, double timeout_ms) {
 
 void Engine::release(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = reqs_.find(id);
-    Q3_CHECK(it != reqs_.end(), "unknown request id");
-    Q3_CHECK(req_ended(it->second->state), "request still in flight");
-    if (it->second->ev_admit) (void)hipEventDestroy(it->second->ev_admit);
-    reqs_.erase(it);
+    Req& r = req(id);
+    Q3_CHECK(req_ended(r.state), "request still in flight");
+    if (r.ev_admit) (void)hipEventDestroy(r.ev_admit);
+    reqs_.erase(id);
 }
 
 void Engine::start_driver() {

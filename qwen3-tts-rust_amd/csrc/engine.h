@@ -170,7 +170,28 @@ private:
     FrameGraph& frame_graph(int width, FrameVariant v, bool capture);
     void validate(const GenRequest& g) const; // prompt and max_steps ranges, then the options
     void ensure_text_stream(); // first request with trailing ids: text table + per-slot id rows go to the device
-    void prefill(const std::vector<Req*>& batch, bool sampled);
+    Req& req(int64_t id);                                             // throws for an unknown id (mu_ held)
+    int64_t enqueue(std::unique_ptr<Req> r, std::deque<Req*>& queue); // a submission's tail: id, reqs_, the queue, the wake-up (mu_ held)
+    // Admission.  A wave is prefilled by one walk, prefill_wave, on one of two lanes.  A PrefillLane holds what the two forms differ in: the
+    // talker context, the stream, the chunk width, the device buffers of one chunk and the pinned staging its rows and tables go up through.
+    //   ar_  in line, on the AR stream (an idle engine, a one-slot engine, Q3_ASYNC_PREFILL=0): the talker itself, chunks of its launch width,
+    //        the scheduler's staging arena, which waits for the stream and starts over when it is full.  The heads of the last prompt tokens
+    //        draw code_0 straight into the live arrays (head_live), so go_live() runs before the walk
+    //   pf_  asynchronously, beside running slots (async_pf_ only): a second talker context over the same weights on a stream of its own,
+    //        chunks of 256, an arena that holds a whole wave and never waits.  The heads leave logits and hidden rows in d_pf_logits_ /
+    //        d_pf_hidden_ (head_staged); activate() brings the wave in between two frame groups once pf_done_ has completed
+    struct PrefillLane {
+        Transformer* talker = nullptr; hipStream_t st = nullptr; int chunk = 0; bool async = false;
+        DevBuf<float> d_rows; DevBuf<int32_t> d_seq, d_slot, d_pos; // one chunk: its input rows, seq / slot / pos [4] per token
+        DevBuf<int32_t> d_codes, d_ids, d_fork_dst;                 // [EXT] resume: codes / trailing ids of its feedback rows; candidate sets: a wave's fork destinations
+        unsigned char* arena = nullptr; StageCursor cur;            // pinned staging
+    };
+    void lane_alloc(PrefillLane& L, Transformer* talker, hipStream_t st, int chunk, bool async, size_t arena_bytes);
+    void* stage_take(PrefillLane& L, size_t bytes);
+    void prefill_wave(PrefillLane& L, const std::vector<Req*>& wave, bool sampled); // sampled: of head_live, some slot draws with a temperature
+    void head_live(Req* lead, const std::vector<Req*>& rest, int tok, bool sampled);
+    void head_staged(Req* lead, const std::vector<Req*>& rest, int tok);
+    SampleArgs first_head_args(const float* logits_row, int b) const; // slot b's first draw from a prefill head's logits row
     // [EXT] resume (q3tts_spec.h): the prefix frames' feedback rows of a prefill chunk, made on the device; the first head's history
     void feedback_rows(hipStream_t st, const std::vector<Req*>& batch, const std::vector<FbRun>& fb, int32_t* hc, int32_t* d_codes, int32_t* d_ids, float* d_rows);
     void head_history(SampleArgs& sa, int b) const;
@@ -187,11 +208,9 @@ private:
     static void split_sets(const std::vector<Req*>& batch, std::vector<Req*>& lead, std::vector<std::vector<Req*>>& rest);
     void fork_sets(hipStream_t st, const std::vector<Req*>& lead, const std::vector<std::vector<Req*>>& rest, int32_t* h_dst, int32_t* d_dst);
     static int kv_positions(const GenRequest& g, bool score) { return score ? g.n_prompt + g.n_prefix + 1 : g.n_prompt + g.max_steps + 1; }
-    // Asynchronous admission (engines with more than one slot): the prompt of newly admitted requests is prefilled by a second talker
-    // instance (own weights copy, own scratch, own stream) while the frame graph keeps stepping the running sequences; the slots
-    // join the batch ("activate") between two frame groups once the prefill event has completed.
-    void prefill_async(const std::vector<Req*>& batch);
-    void activate();
+    void prefill_async(const std::vector<Req*>& wave); // the asynchronous wave's start: KV pages, events, the walk on pf_, pf_batch_
+    void go_live(const std::vector<Req*>& batch);      // slot state of a wave's requests (no score request among them) goes live, on st_
+    void activate();                                   // the asynchronous wave's completion
     void admit_decodes();     // [EXT] decode-only requests take free codec streams, after admit()
     // their reset, chunks and fence go to the low queue: at once when the step runs no frame group, else together with the chunks the group
     // produced (run_group), so that both kinds meet in the decoder thread's queues and share passes
@@ -213,19 +232,19 @@ private:
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).
-    void* stage_alloc(size_t bytes);
+    void* stage_alloc(size_t bytes) { return stage_take(ar_, bytes); }
     void h2d(void* dst, const void* src, size_t bytes);            // async on st_, source copied into the arena first
     void* d2h_begin(const void* src, size_t bytes);                // async on st_ into the arena; valid after the next sync of st_
-    unsigned char* arena_ = nullptr; size_t arena_cap_ = 0, arena_used_ = 0;
 
     EngineParams p_;
     hipStream_t st_ = nullptr; int dev_ = 0;
     std::vector<hipStream_t> st2_; // codec decoder lanes: overlapped with the next AR frames and with each other
     float* pcm_pinned_ = nullptr; size_t slot_cap_ = 0;
+    unsigned char* pcm_stage(const Req& r, size_t add) const; // where the decoder thread's next `add` bytes of r land in its stream's region
     std::unique_ptr<HostAssets> assets_;
     std::unique_ptr<Transformer> talker_, predictor_, talker_pf_;
-    hipStream_t st_pf_ = nullptr; unsigned char* arena_pf_ = nullptr; size_t arena_pf_cap_ = 0;
-    DevBuf<float> d_prompt_pf_, d_pf_logits_, d_pf_hidden_; DevBuf<int32_t> d_pfa_seq_, d_pfa_slot_, d_pfa_pos_;
+    hipStream_t st_pf_ = nullptr; PrefillLane ar_, pf_;
+    DevBuf<float> d_pf_logits_, d_pf_hidden_; // [B] rows: what head_staged leaves for activate()
     std::vector<Req*> pf_batch_; hipEvent_t pf_done_ = nullptr, pf_e0_ = nullptr; bool async_pf_ = false; int n_prefilling_ = 0;
     std::unique_ptr<KvPool> kv_t_, kv_p_;
     std::unique_ptr<CodecDecoder> codec_;
@@ -243,9 +262,7 @@ private:
     DevBuf<int32_t> d_hist_; DevBuf<q3_u64> d_keys_, d_next_key0_;
     DevBuf<uint32_t> d_rngkey_, d_draws_, d_prngkey_, d_pdraws_; DevBuf<float> d_plogits_;
     DevBuf<int32_t> d_pseq_, d_pslot_, d_ppos_;
-    DevBuf<float> d_tlogits_, d_thidden_, d_pin_, d_fb_, d_prompt_;
-    DevBuf<int32_t> d_pf_seq_, d_pf_slot_, d_pf_pos_;
-    DevBuf<int32_t> d_pf_codes_, d_pf_ids_, d_pfa_codes_, d_pfa_ids_; // [EXT] resume: codes / trailing ids of a prefill chunk's feedback rows (in-line, asynchronous)
+    DevBuf<float> d_tlogits_, d_thidden_, d_pin_, d_fb_;
     int64_t kv_rows_ = 0; // positions a slot's KV pages hold
     int hist_stride_ = 0, tl_stride_ = 0;
     // [EXT] streaming-text state, allocated by the first request with n_trail > 0: the text table, [B][max_prompt] trailing ids
@@ -266,8 +283,8 @@ private:
     DevBuf<int32_t> d_sc_seq_, d_sc_slot_, d_sc_pos_, d_sc_codes_; DevBuf<const float*> d_sc_tabs_; DevBuf<int64_t> d_sc_tab_rows_;
     DevBuf<float> d_sc_tlogits_, d_sc_hidden_, d_sc_hproj_, d_sc_in_, d_sc_plogits_, d_sc_out_;
     std::mutex sc_mu_; std::atomic<bool> sc_ready_{false};
-    // [EXT] candidate sets: the destination sequences of a wave's forks (in-line wave, asynchronous wave), the set ids (mu_), the counters
-    DevBuf<int32_t> d_fork_dst_, d_fork_dst_pf_; int64_t next_set_ = 1;
+    // [EXT] candidate sets: the set ids (mu_), the counters
+    int64_t next_set_ = 1;
     std::atomic<int64_t> cand_sets_{0}, cand_rows_saved_{0}, cand_pages_{0};
     std::map<int, std::unique_ptr<FrameGraph>> graphs_; // key = FrameVariant::key(width)
     bool instrument_ = false; bool pred_identity_pages_ = false;

@@ -1,9 +1,10 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request and of a codec preamble (with who holds one), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request and of a codec preamble (with who holds one), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <utility>
 #include <vector>
@@ -77,7 +78,7 @@ struct SlotTable {
         hf(SF_TEMP)[b] = 0.0f; hi(SF_TOPK)[b] = 0; hf(SF_TOPP)[b] = 1.0f; hi(SF_NTRAIL)[b] = hi(SF_OPEN)[b] = 0;
         hf(SF_PEN)[b] = 1.0f; hf(SF_PTEMP)[b] = 0.0f; hi(SF_PTOPK)[b] = 0; hf(SF_PTOPP)[b] = 1.0f;
     }
-    void load(int b, const GenRequest& r) { // a slot about to go live (an open trail's count and flag: Engine::activate, under its lock)
+    void load(int b, const GenRequest& r) { // a slot about to go live (an open trail's count and flag: Engine::go_live, under its lock)
         req[b] = &r;
         hi(SF_FINISHED)[b] = 0; hi(SF_MAXFRAMES)[b] = r.max_steps; hi(SF_NFRAMES)[b] = r.n_prefix; hi(SF_NPROMPT)[b] = r.n_prompt;
         hi(SF_MASKEOS)[b] = r.mask_eos ? Q3_CODEC_EOS : -1; hi(SF_NTRAIL)[b] = r.n_trail; hi(SF_OPEN)[b] = 0;
@@ -135,6 +136,23 @@ inline CancelAction cancel_action(int state, bool in_wave, bool live, bool want_
 // the state a request takes when its slot is retired (EOS, max_steps or a cancel) and when its fence completes
 inline int retired_state(bool want_pcm, bool cancelled) { return want_pcm ? REQ_DRAINING : cancelled ? REQ_CANCELLED : REQ_DONE; }
 inline int fenced_state(bool cancelled) { return cancelled ? REQ_CANCELLED : REQ_DONE; }
+
+// The bump cursor of a pinned staging arena of `cap` bytes.  take() hands out the offset of the next 64-byte-aligned piece, or NONE when the
+// piece does not fit behind what is in use; the cursor then stays as it is, and the owner decides: the AR arena waits for its stream and
+// starts over (reset), the asynchronous prefill arena must never wait and treats NONE as an error.
+struct StageCursor {
+    static constexpr size_t NONE = ~(size_t)0;
+    size_t cap = 0, used = 0;
+    size_t take(size_t bytes) {
+        if (bytes > cap) return NONE; // not even an empty arena serves it (and rounding up cannot wrap below)
+        bytes = (bytes + 63) & ~(size_t)63;
+        if (bytes > cap - used) return NONE;
+        const size_t at = used;
+        used += bytes;
+        return at;
+    }
+    void reset() { used = 0; }
+};
 
 // Prefill: the prompts of one admission wave form one token stream.  Fills one chunk of at most n_max tokens from the cursor on -- prompt rows,
 // per-token seq / slot / pos routing (engine.rs:306-314) -- and returns its token count; lasts = (request, index inside the chunk) of final prompt tokens.

@@ -91,6 +91,15 @@ int main() {
                 printf("\n");
             }
             printf("cursor %zu %d\n", c.req, c.tok);
+        } else if (cmd == "stage") { // stage cap n, then n sizes (-1: reset): per size "offset used", offset -1 = does not fit
+            size_t cap; int n; std::cin >> cap >> n;
+            StageCursor c; c.cap = cap;
+            for (int i = 0; i < n; i++) {
+                long long b; std::cin >> b;
+                if (b < 0) { c.reset(); printf("reset %zu\n", c.used); continue; }
+                const size_t at = c.take((size_t)b);
+                printf("%lld %zu\n", at == StageCursor::NONE ? -1LL : (long long)at, c.used);
+            }
         } else { fprintf(stderr, "unknown command %s\n", cmd.c_str()); return 2; }
     }
     return 0;

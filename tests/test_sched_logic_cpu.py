@@ -1,4 +1,4 @@
-"""The scheduler's pure bookkeeping (qwen3-tts-rust_amd/csrc/sched_logic.h: frame variant, slot table, stall predicate, prefill chunk packer),
+"""The scheduler's pure bookkeeping (qwen3-tts-rust_amd/csrc/sched_logic.h: frame variant, slot table, stall predicate, prefill chunk packer, staging cursor),
 built with plain g++ -- no HIP header, no GPU -- and compared with the few lines of Python that restate each rule here."""
 import itertools
 import os
@@ -183,3 +183,59 @@ def test_prefill_packer(driver):
         assert stage == ["stage"] + ["%g" % (100 * i + t) for i, t in toks] + ["-1"] * (n_max - len(toks))  # rows past n stay untouched
     # what this batch is for: a one-token prompt, prompts that straddle a chunk edge, the last one ending exactly on one
     assert chunks[0][0] == (0, 0) and chunks[1][0] == (1, 3) and chunks[1][-1][0] == 3 and chunks[2][0][0] == 3
+
+
+def stage_ref(cap, sizes):
+    """The staging cursor restated: 64-byte pieces handed out in order, nothing moves when a piece does not fit."""
+    used, out = 0, []
+    for b in sizes:
+        if b < 0:
+            used = 0
+            out.append(("reset", 0))
+            continue
+        need = (b + 63) // 64 * 64
+        if b > cap or used + need > cap:
+            out.append((-1, used))
+        else:
+            out.append((used, used + need))
+            used += need
+    return out
+
+
+def stage_run(driver, cap, sizes):
+    out = driver("stage %d %d\n%s\n" % (cap, len(sizes), " ".join(str(b) for b in sizes)))
+    assert len(out) == len(sizes)
+    return [("reset", int(l.split()[1])) if l.startswith("reset") else tuple(int(x) for x in l.split()) for l in out]
+
+
+def test_stage_cursor_offsets_are_aligned(driver):
+    cap = 4096
+    sizes = [1, 63, 64, 65, 0, 100, 128, 1000, 7, 640, 1, 1, 2000, 5, -1, 4000, 96, 1, -1, 33, 4033, 31]
+    got = stage_run(driver, cap, sizes)
+    assert got == stage_ref(cap, sizes)
+    offsets = [at for at, _ in got if at not in ("reset", -1)]
+    assert len(offsets) >= 15 and all(at % 64 == 0 for at in offsets)
+    assert any(at == -1 for at, _ in got)                       # the sequence fills the arena at least once
+    assert all(used % 64 == 0 and used <= cap for _, used in got)
+
+
+def test_stage_cursor_exact_fit_and_one_byte_more(driver):
+    # 256 bytes: 192 in use, then exactly the 64 that are left / one byte more than what is left
+    assert stage_run(driver, 256, [192, 64]) == [(0, 192), (192, 256)]
+    assert stage_run(driver, 256, [192, 65]) == [(0, 192), (-1, 192)]          # does not fit: the cursor stays
+    assert stage_run(driver, 256, [192, 65, 64]) == [(0, 192), (-1, 192), (192, 256)]  # and still serves what does
+    assert stage_run(driver, 256, [256, 1, 0]) == [(0, 256), (-1, 256), (256, 256)]    # a full arena: the whole of it, then nothing but nothing
+    # a capacity that is no multiple of 64: the piece is rounded up, so the last 36 bytes serve nobody
+    assert stage_run(driver, 100, [64, 1]) == [(0, 64), (-1, 64)]
+
+
+def test_stage_cursor_refuses_what_no_arena_holds(driver):
+    for before in ([], [64], [64, 64, 64, 64]):                 # whatever is in use: empty, partly, full
+        got = stage_run(driver, 256, before + [257, 1 << 40])
+        used = 64 * len(before)
+        assert got[len(before):] == [(-1, used), (-1, used)]
+
+
+def test_stage_cursor_reset(driver):
+    got = stage_run(driver, 256, [100, 100, 100, -1, 10, -1, 256])
+    assert got == [(0, 128), (128, 256), (-1, 256), ("reset", 0), (0, 64), ("reset", 0), (0, 256)]
