@@ -761,6 +761,9 @@ int q3tts_attention_plan(q3tts_attention_desc* d);
  *   F_MFMA16 / F_MFMA                  float weights; row0 % 64 == 0; x 16-byte aligned; x_stride % 4 == 0
  *   F_GU_MFMA16                        the same, nrows == 2 * ff, ff % 16 == 0 (the engine's 2..95-token window is a dispatch choice only)
  *   F_GU_UNFUSED                       the float GEMV the engine would run + k_swiglu_f32
+ *   GEMM_Q8_WIDE (k_gemm_q8_wide<0>)   Q8_0 weights; ztiles == ceil(ntok/32).  AUTO above 256 tokens.  It stores single floats: any out / out_stride
+ *                                      the op accepts is accepted
+ *   GU_Q8_WIDE (k_gemm_q8_wide<1>)     Q8_0; K in {1024, 2048}; ff % 32 == 0; ztiles == ceil(ntok/32).  AUTO above 256 tokens
  * Every buffer is uploaded whole and written back whole, so bytes outside the logical outputs show any stray write. */
 enum { Q3TTS_LOP_GEMV = 0, Q3TTS_LOP_GATEUP = 1, Q3TTS_LOP_NORM = 2, Q3TTS_LOP_NORM_GEMV = 3, Q3TTS_LOP_NORM_ARGMAX = 4, Q3TTS_LOP_NORM_GATEUP = 5,
        Q3TTS_LOP_F_GEMV = 6, Q3TTS_LOP_F_GATEUP = 7 };
@@ -768,7 +771,7 @@ enum { Q3TTS_LIN_AUTO = 0, Q3TTS_LIN_GEMV_Q8 = 1, Q3TTS_LIN_GEMM_Q8_TOK = 2, Q3T
        Q3TTS_LIN_GEMV_KQ = 5, Q3TTS_LIN_GEMM_KQ_MFMA = 6, Q3TTS_LIN_GU_Q8_TILE1 = 7, Q3TTS_LIN_GU_Q8_MFMA = 8, Q3TTS_LIN_GU_KQ_MFMA = 9,
        Q3TTS_LIN_GU_UNFUSED = 10, Q3TTS_LIN_NORM = 11, Q3TTS_LIN_NORM_WG = 12, Q3TTS_LIN_GEMV_NORM = 13, Q3TTS_LIN_GEMV_NORM_ARGMAX = 14,
        Q3TTS_LIN_GU_SWIGLU_NORM = 15, Q3TTS_LIN_F_GEMV = 16, Q3TTS_LIN_F_MFMA16 = 17, Q3TTS_LIN_F_MFMA = 18, Q3TTS_LIN_F_GU_MFMA16 = 19,
-       Q3TTS_LIN_F_GU_UNFUSED = 20 };
+       Q3TTS_LIN_F_GU_UNFUSED = 20, Q3TTS_LIN_GEMM_Q8_WIDE = 21, Q3TTS_LIN_GU_Q8_WIDE = 22 };
 typedef struct q3tts_linear_desc {
     int32_t op, form;
     /* weights: quantised = up to 3 raw GGUF tensors [rows[i]][K] of type[i] (8 Q8_0, 13 Q5_K, 14 Q6_K; all-Q8_0 = the Q8_0 file layout unless

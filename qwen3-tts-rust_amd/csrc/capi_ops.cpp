@@ -155,6 +155,8 @@ static LinearPlan lin_plan(const q3tts_linear_desc& d) {
 }
 static bool in_set(int v, std::initializer_list<int> s) { for (int x : s) if (v == x) return true; return false; }
 static int op_of_form(int f) {
+    if (f == LIN_GEMM_Q8_WIDE) return LOP_GEMV;
+    if (f == LIN_GU_Q8_WIDE) return LOP_GATEUP;
     if (f <= LIN_GEMM_KQ_MFMA) return LOP_GEMV;
     if (f <= LIN_GU_UNFUSED) return LOP_GATEUP;
     if (f <= LIN_NORM_WG) return LOP_NORM;
@@ -167,7 +169,7 @@ static int op_of_form(int f) {
 // every precondition of the form (include/q3tts.h), checked on the host before anything is allocated or launched
 static void lin_check(const q3tts_linear_desc& d, const LinearPlan& p) {
     const int f = p.form, K = d.K, nt = d.ntok, ntiles = (nt + 31) / 32;
-    Q3_CHECK(f >= LIN_GEMV_Q8 && f <= LIN_F_GU_UNFUSED && op_of_form(f) == d.op, "the form does not compute this op");
+    Q3_CHECK(f >= LIN_GEMV_Q8 && f <= LIN_GU_Q8_WIDE && op_of_form(f) == d.op, "the form does not compute this op");
     const bool quant = lin_quant(d), kq = quant && lin_kq(d), norm = d.op >= LOP_NORM && d.op <= LOP_NORM_GATEUP;
     if (d.op != LOP_NORM) {
         Q3_CHECK(d.nw >= 1 && d.nw <= 3, "1 to 3 weight tensors");
@@ -226,6 +228,11 @@ static void lin_check(const q3tts_linear_desc& d, const LinearPlan& p) {
         Q3_CHECK((K == 1024 || K == 2048) && d.ff % 32 == 0, "fused gate/up: K in {1024, 2048}, ff % 32 == 0");
         Q3_CHECK(p.z >= (ntiles + 3) / 4 && p.z <= ntiles && (f != LIN_GU_Q8_TILE1 || p.z == ntiles), "fused gate/up: ceil(tiles/4) <= ztiles <= tiles (TILE1: == tiles)");
         break;
+    case LIN_GEMM_Q8_WIDE: case LIN_GU_Q8_WIDE:
+        Q3_CHECK(q8, "GEMM_Q8_WIDE / GU_Q8_WIDE take the Q8_0 layout");
+        if (f == LIN_GU_Q8_WIDE) Q3_CHECK((K == 1024 || K == 2048) && d.ff % 32 == 0, "fused gate/up: K in {1024, 2048}, ff % 32 == 0");
+        Q3_CHECK(p.z == ntiles, "wide forms: ztiles == token tiles");
+        break;
     case LIN_GEMV_NORM: case LIN_GEMV_NORM_ARGMAX: case LIN_GU_SWIGLU_NORM:
         Q3_CHECK(f == LIN_GU_SWIGLU_NORM ? (in_set(p.mt, {1, 2, 4}) && lin_wts(d) != -1) : in_set(p.mt, {1, 2, 4, 8}), "mt out of range / GU_SWIGLU_NORM needs one tensor type");
         Q3_CHECK(f == LIN_GU_SWIGLU_NORM || (f == LIN_GEMV_NORM_ARGMAX ? p.lpr == 2 : in_set(p.lpr, {2, 4, 8})), "GEMV_NORM: lpr in {2,4,8}; ARGMAX: lpr 2");
@@ -243,7 +250,7 @@ static void lin_run(q3tts_linear_desc* dp) {
     q3tts_linear_desc& d = *dp;
     LinearPlan p = lin_plan(d);
     if (d.form != LIN_AUTO) { // forced: the plan's parameters unless given
-        Q3_CHECK(d.form >= LIN_GEMV_Q8 && d.form <= LIN_F_GU_UNFUSED, "unknown linear form");
+        Q3_CHECK(d.form >= LIN_GEMV_Q8 && d.form <= LIN_GU_Q8_WIDE, "unknown linear form");
         LinearPlan fp; fp.form = d.form; fp.nseg = d.K / 256;
         const int f = d.form, ntiles = (d.ntok + 31) / 32;
         const int mt_def = d.ntok == 1 ? 1 : d.ntok == 2 ? 2 : d.ntok <= 4 ? 4 : 8;
@@ -251,6 +258,7 @@ static void lin_run(q3tts_linear_desc* dp) {
         fp.lpr = d.lpr ? d.lpr : (p.form == f && p.lpr ? p.lpr : (f == LIN_GEMV_NORM_ARGMAX ? 2 : 8));
         int zdef = p.form == f && p.z ? p.z : ntiles;
         fp.z = d.ztiles ? d.ztiles : zdef;
+        if (f == LIN_GEMM_Q8_WIDE || f == LIN_GU_Q8_WIDE) { fp.mt = 0; fp.lpr = 0; } // (one parameter: ztiles == token tiles)
         p = fp;
     }
     lin_check(d, p);
@@ -287,14 +295,22 @@ static void lin_run(q3tts_linear_desc* dp) {
         if (d.xn_out) { dxn.alloc((size_t)nt * K); dxn.upload(d.xn_out, dxn.n); a.xn_out = dxn.p; }
     }
     if (d.out) { dout.alloc((size_t)d.out_floats); dout.upload(d.out, dout.n); }
-    if (d.aq) { daq.alloc((size_t)nt * ff); daq.upload(d.aq, daq.n); dad.alloc((size_t)nt * (ff / 32)); dad.upload(d.ad, dad.n); }
+    // gate/up outputs: LIN_GUARD elements of 0x5A bytes in front of and behind [ntok][ff] / [ntok][ff/32] on the device; a form that writes one is refused below
+    constexpr size_t LIN_GUARD = 64;
+    const size_t n_aq = d.aq ? (size_t)nt * ff : 0, n_ad = d.aq ? (size_t)nt * (ff / 32) : 0;
+    if (d.aq) {
+        daq.alloc(n_aq + 2 * LIN_GUARD); dad.alloc(n_ad + 2 * LIN_GUARD);
+        Q3_HIP(hipMemset(daq.p, 0x5A, daq.n)); Q3_HIP(hipMemset(dad.p, 0x5A, dad.n * 2));
+        Q3_HIP(hipMemcpy(daq.p + LIN_GUARD, d.aq, n_aq, hipMemcpyHostToDevice)); Q3_HIP(hipMemcpy(dad.p + LIN_GUARD, d.ad, n_ad * 2, hipMemcpyHostToDevice));
+    }
+    int8_t* const aqp = d.aq ? daq.p + LIN_GUARD : nullptr; uint16_t* const adp = d.aq ? dad.p + LIN_GUARD : nullptr;
     float* out = d.out ? dout.p + d.out_off : nullptr;
     switch (p.form) {
-    case LIN_GEMV_Q8: case LIN_GEMM_Q8_TOK: case LIN_GEMM_Q8_MFMA: case LIN_GEMM_Q8_TILE1: case LIN_GEMV_KQ: case LIN_GEMM_KQ_MFMA:
+    case LIN_GEMV_Q8: case LIN_GEMM_Q8_TOK: case LIN_GEMM_Q8_MFMA: case LIN_GEMM_Q8_TILE1: case LIN_GEMV_KQ: case LIN_GEMM_KQ_MFMA: case LIN_GEMM_Q8_WIDE:
         run_gemv_q8(0, p, m, d.row0, d.nrows, dxq.p, dxd.p, out, d.out_stride, nt);
         break;
-    case LIN_GU_Q8_TILE1: case LIN_GU_Q8_MFMA: case LIN_GU_KQ_MFMA:
-        run_gateup_q8(0, p, m, ff, dxq.p, dxd.p, daq.p, dad.p, nt);
+    case LIN_GU_Q8_TILE1: case LIN_GU_Q8_MFMA: case LIN_GU_KQ_MFMA: case LIN_GU_Q8_WIDE:
+        run_gateup_q8(0, p, m, ff, dxq.p, dxd.p, aqp, adp, nt);
         break;
     case LIN_GU_UNFUSED: { // what Transformer::forward runs when the fused gate/up form does not apply
         dgu.alloc((size_t)((K / 256 + 7) / 8) * nt * 2 * ff);
@@ -302,7 +318,7 @@ static void lin_run(q3tts_linear_desc* dp) {
         gi.out_stride = 2 * ff; gi.out_addr = (uintptr_t)dgu.p;
         const LinearPlan gp = plan_linear(gi);
         run_gemv_q8(0, gp, m, 0, 2 * ff, dxq.p, dxd.p, dgu.p, 2 * ff, nt);
-        launch_swiglu_quant(0, dgu.p, ff, daq.p, dad.p, nt);
+        launch_swiglu_quant(0, dgu.p, ff, aqp, adp, nt);
         p.lpr = gp.lpr; p.mt = gp.mt; p.z = gp.z;
         break;
     }
@@ -325,7 +341,7 @@ static void lin_run(q3tts_linear_desc* dp) {
         } else run_gemv_q8_norm(0, p, m, d.row0, d.nrows, a, out, d.out_stride, nt, nullptr);
         break;
     }
-    case LIN_GU_SWIGLU_NORM: run_gateup_swiglu(0, p, m, ff, a, daq.p, dad.p, nt); break;
+    case LIN_GU_SWIGLU_NORM: run_gateup_swiglu(0, p, m, ff, a, aqp, adp, nt); break;
     case LIN_F_GEMV: case LIN_F_MFMA16: case LIN_F_MFMA:
         run_gemv_float(0, p, fm, d.row0, d.nrows, dx.p + d.x_off, d.x_stride, out, d.out_stride, nt);
         break;
@@ -351,7 +367,13 @@ static void lin_run(q3tts_linear_desc* dp) {
     if (p.form == LIN_F_GU_MFMA16) Q3_HIP(hipMemcpy2D(out, (size_t)d.out_stride * 4, dgu.p, (size_t)ff * 4, (size_t)ff * 4, nt, hipMemcpyDeviceToDevice));
     Q3_HIP(hipDeviceSynchronize());
     if (d.out) dout.download(d.out, dout.n);
-    if (d.aq) { daq.download(d.aq, daq.n); dad.download(d.ad, dad.n); }
+    if (d.aq) {
+        std::vector<int8_t> hq(daq.n); std::vector<uint16_t> hd(dad.n);
+        daq.download(hq.data(), hq.size()); dad.download(hd.data(), hd.size());
+        for (size_t i = 0; i < LIN_GUARD; i++)
+            Q3_CHECK(hq[i] == 0x5A && hq[LIN_GUARD + n_aq + i] == 0x5A && hd[i] == 0x5A5A && hd[LIN_GUARD + n_ad + i] == 0x5A5A, "gate/up form wrote outside aq / ad");
+        std::memcpy(d.aq, hq.data() + LIN_GUARD, n_aq); std::memcpy(d.ad, hd.data() + LIN_GUARD, n_ad * 2);
+    }
     if (d.h_out) dhout.download(d.h_out, dhout.n);
     if (d.xn_out) dxn.download(d.xn_out, dxn.n);
     if (dxq_out.p) { dxq_out.download(d.xq_out, dxq_out.n); dxd_out.download(d.xd_out, dxd_out.n); }

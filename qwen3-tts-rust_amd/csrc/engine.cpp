@@ -29,6 +29,10 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     const int B = p.max_batch;
     B_ = B;
     talker_.reset(new Transformer(dir + "/qwen3_tts_talker.gguf", Q3_TALKER_NCTX, std::max(256, B)));
+    // Prompt chunks: 512 rows for a Q8_0 talker, whose four GEMMs take the wide forms above 256 tokens (k_gemm_q8_wide: 118.8 us per
+    // layer against 176.0 us for two 256-token rounds, profiles/prefill_wide_gemm_kernel_counts.md); 256 for K-quant and float files, and under Q3_PREFILL_WIDE=0.
+    // A row's result does not depend on the chunk it travels in: every kernel of the walk computes each token on its own, with the same bits.
+    if (talker_->q8_uniform() && prefill_wide()) { pf_chunk_ = 512; if (talker_->max_tok() < pf_chunk_) talker_->set_max_tok(pf_chunk_); }
     predictor_.reset(new Transformer(dir + "/qwen3_tts_predictor.gguf", Q3_PRED_NCTX, 2 * B));
     if (const char* e = std::getenv("Q3_PRED_FUSED_MAX")) predictor_->set_fused_max_tokens(atoi(e)); // experiment knob
     // The predictor never holds more than 17 positions per sequence: wide steps use the single-wave attention kernel (one wave per
@@ -98,13 +102,13 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         async_pf_ = B > 1 && !(e && e[0] == '0');
     }
     if (async_pf_) {
-        talker_pf_.reset(new Transformer(*talker_, 256)); // shares the talker's device weights; own activation workspace
+        talker_pf_.reset(new Transformer(*talker_, pf_chunk_)); // shares the talker's device weights; own activation workspace
         Q3_HIP(hipStreamCreateWithFlags(&st_pf_, hipStreamNonBlocking));
         Q3_HIP(hipEventCreate(&pf_done_)); Q3_HIP(hipEventCreate(&pf_e0_));
         // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row) and the
         // codes of score rows (64 B a row) + [EXT] the fork destinations of a wave.  Every piece starts on a 64-byte boundary: six pieces a
         // chunk lose at most 6 x 63 B, over the at most 17 chunks of a 4096-row wave 6426 B, the destinations 63 B more -- inside the 64 KiB slack
-        lane_alloc(pf_, talker_pf_.get(), st_pf_, 256, true, (size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4);
+        lane_alloc(pf_, talker_pf_.get(), st_pf_, pf_chunk_, true,(size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4);
     }
     // ---- per-slot state ----
     hist_stride_ = p.max_steps * 16;
@@ -1214,7 +1218,7 @@ void Engine::ensure_score() {
     Q3_HIP(hipGetDevice(&prev));
     Q3_HIP(hipSetDevice(dev_));
     try {
-        const int W = score_w_, rows = std::max(talker_->max_tok(), 256); // rows: the widest prefill chunk of either lane
+        const int W = score_w_, rows = std::max(talker_->max_tok(), pf_chunk_); // rows: the widest prefill chunk of either lane
         pred_sc_.reset(new Transformer(*predictor_, 16 * W));
         kv_sc_.reset(new KvPool(predictor_->hp().n_layer, predictor_->hp().n_kv, W, W, 1));
         for (int w = 0; w < W; w++) kv_sc_->ensure(w, 16);

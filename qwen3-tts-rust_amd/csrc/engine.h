@@ -178,7 +178,7 @@ private:
     //        the scheduler's staging arena, which waits for the stream and starts over when it is full.  The heads of the last prompt tokens
     //        draw code_0 straight into the live arrays (head_live), so go_live() runs before the walk
     //   pf_  asynchronously, beside running slots (async_pf_ only): a second talker context over the same weights on a stream of its own,
-    //        chunks of 256, an arena that holds a whole wave and never waits.  The heads leave logits and hidden rows in d_pf_logits_ /
+    //        chunks of pf_chunk_ rows, an arena that holds a whole wave and never waits.  The heads leave logits and hidden rows in d_pf_logits_ /
     //        d_pf_hidden_ (head_staged); activate() brings the wave in between two frame groups once pf_done_ has completed
     struct PrefillLane {
         Transformer* talker = nullptr; hipStream_t st = nullptr; int chunk = 0; bool async = false;
@@ -246,6 +246,7 @@ private:
     hipStream_t st_pf_ = nullptr; PrefillLane ar_, pf_;
     DevBuf<float> d_pf_logits_, d_pf_hidden_; // [B] rows: what head_staged leaves for activate()
     std::vector<Req*> pf_batch_; hipEvent_t pf_done_ = nullptr, pf_e0_ = nullptr; bool async_pf_ = false; int n_prefilling_ = 0;
+    int pf_chunk_ = 256; // rows of one prompt chunk of the asynchronous lane, and the least the in-line lane takes (512: Q8_0 talker, wide GEMM forms)
     std::unique_ptr<KvPool> kv_t_, kv_p_;
     std::unique_ptr<CodecDecoder> codec_;
     // device assets

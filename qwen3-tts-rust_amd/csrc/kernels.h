@@ -198,7 +198,8 @@ enum LinearOp { LOP_GEMV = 0, LOP_GATEUP = 1, LOP_NORM = 2, LOP_NORM_GEMV = 3, L
 enum LinearForm { LIN_AUTO = 0, LIN_GEMV_Q8 = 1, LIN_GEMM_Q8_TOK = 2, LIN_GEMM_Q8_MFMA = 3, LIN_GEMM_Q8_TILE1 = 4, LIN_GEMV_KQ = 5,
                   LIN_GEMM_KQ_MFMA = 6, LIN_GU_Q8_TILE1 = 7, LIN_GU_Q8_MFMA = 8, LIN_GU_KQ_MFMA = 9, LIN_GU_UNFUSED = 10, LIN_NORM = 11,
                   LIN_NORM_WG = 12, LIN_GEMV_NORM = 13, LIN_GEMV_NORM_ARGMAX = 14, LIN_GU_SWIGLU_NORM = 15, LIN_F_GEMV = 16, LIN_F_MFMA16 = 17,
-                  LIN_F_MFMA = 18, LIN_F_GU_MFMA16 = 19, LIN_F_GU_UNFUSED = 20 };
+                  LIN_F_MFMA = 18, LIN_F_GU_MFMA16 = 19, LIN_F_GU_UNFUSED = 20, LIN_GEMM_Q8_WIDE = 21, LIN_GU_Q8_WIDE = 22 };
+bool prefill_wide(); // Q3_PREFILL_WIDE != 0 (the default): prompt chunks of 512 tokens on the wide int8 GEMM forms
 struct LinearPlanIn {
     int op = LOP_GEMV;
     int K = 0, row0 = 0, nrows = 0, ntok = 0, ff = 0;

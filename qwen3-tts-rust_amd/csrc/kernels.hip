@@ -101,6 +101,11 @@ __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_mfma(Q8Mat w, int row0, int nrows, c
 template <bool GU>
 __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_tile1(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, const uint16_t* __restrict__ xd,
                                float* __restrict__ out, int out_stride, int ntok, int ff, int8_t* __restrict__ aq, uint16_t* __restrict__ ad);
+// wide form (prompt chunks above 256 tokens): 2 waves per SIMD = 256 VGPRs, two 4-wave workgroups per CU
+#define Q3_GEMM_Q8_WIDE_BUDGET __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+template <bool GU>
+__global__ void Q3_GEMM_Q8_WIDE_BUDGET k_gemm_q8_wide(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, const uint16_t* __restrict__ xd,
+                               float* __restrict__ out, int out_stride, int ntok, int ff, int8_t* __restrict__ aq, uint16_t* __restrict__ ad);
 template <int TYPE> // register budget cut for 2 waves per SIMD = 256 VGPRs (no spill, 1 workgroup per CU; the 128-VGPR build spilled 200 B per lane in its K loop)
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_gemm_float_mfma(const void* __restrict__ wt, int K, int tile0, int nrows, const float* __restrict__ x, int x_stride, float* __restrict__ out, int out_stride, int ntok);
@@ -127,10 +132,13 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
 // token tiles per launch dimension z: as few as keep >= 256 workgroups in flight (z = 1 streams the weights exactly once)
 static int mfma_ztiles(int rowgroups, int nsseg, int ntok) {
     const int ntiles = (ntok + 31) / 32;
-    static const int target = [] { const char* e = std::getenv("Q3_MFMA_WGS"); return e ? atoi(e) : 1024; }(); // measured on MI355X at 64 tokens: 128 -> 6.74, 256 -> 6.16, 512..2048 -> 6.14 ms/step (prefill 50.6 -> 48.1 ms at 1024)
+    static const int target = [] { const char* e = std::getenv("Q3_MFMA_WGS"); return e ? atoi(e) : 1024; }(); // measured on MI355X at 64 tokens: 128 -> 6.74, 256 -> 6.16, 512..2048 -> 6.14 ms/step (prefill 50.6 -> 48.1 ms at 1024, when prompt chunks of 256 tokens ran on this kernel; above 256 tokens a Q8_0 matrix now takes k_gemm_q8_wide: prefill 42.8 -> 30.5 ms)
     int z = (target + rowgroups * nsseg - 1) / (rowgroups * nsseg);
     return z < 1 ? 1 : (z > ntiles ? ntiles : z);
 }
+// Q3_PREFILL_WIDE=0: prompt chunks stay at 256 tokens and no launch takes the wide forms (the A/B switch).  Read at every call: it is asked only
+// above 256 tokens and by the engine's constructor, never on a decode step.
+bool prefill_wide() { const char* e = std::getenv("Q3_PREFILL_WIDE"); return !(e && e[0] == '0'); }
 
 // =====================================================================================================
 // Mixed-type form (Q5_K_M files: Q5_K + Q6_K + Q8_0 rows in one fused matrix).  Same wave mapping and the same
@@ -251,6 +259,10 @@ LinearPlan plan_linear(const LinearPlanIn& in) {
             p.form = LIN_GEMV_KQ; p.lpr = lpr; p.mt = mt_of(in.ntok);
             return p;
         }
+        if (in.ntok > 256 && !in.lpr_hint && prefill_wide()) { // prompt chunks: a wave walks its rows' whole super-segment for one token tile
+            p.form = LIN_GEMM_Q8_WIDE; p.z = ntiles;
+            return p;
+        }
         if (in.ntok >= 16 && !in.lpr_hint) { // matrix-core path: exact int8 block dots for 32 tokens x 32 rows per MFMA
             p.z = mfma_ztiles((in.nrows + 31) / 32, nsseg, in.ntok);
             // one token tile per workgroup and K <= 1024 (4 waves): the latency-tuned form.  Measured in-graph at 64 tokens (profiles/r03_gemm_stamps.txt): predictor
@@ -269,6 +281,10 @@ LinearPlan plan_linear(const LinearPlanIn& in) {
         p.form = LIN_GU_UNFUSED;
         if (!in.fused || in.ntok < 16 || (in.K != 1024 && in.K != 2048) || (in.ff & 31)) return p;
         if (in.kq && (!kq_mfma() || in.kq_parts != 1)) return p;
+        if (!in.kq && in.ntok > 256 && prefill_wide()) {
+            p.form = LIN_GU_Q8_WIDE; p.z = ntiles;
+            return p;
+        }
         int z = mfma_ztiles(in.ff / 32, 1, in.ntok);
         if (z < (ntiles + 3) / 4) z = (ntiles + 3) / 4; // a workgroup parks at most 4 tiles of gate sums
         p.z = z;
@@ -323,6 +339,10 @@ void run_gemv_q8(hipStream_t st, const LinearPlan& p, const Q8Mat& w, int row0, 
     case LIN_GEMM_Q8_MFMA:
         hipLaunchKernelGGL((k_gemm_q8_mfma<false>), dim3(rgs, nsseg, p.z), dim3(64 * nw), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr);
         return;
+    case LIN_GEMM_Q8_WIDE:
+        if ((uint64_t)w.Npad * w.K >= (1ull << 32) || (uint64_t)ntok * w.K >= (1ull << 32)) throw Error("GEMM_Q8_WIDE: 32-bit lane offsets (matrix and activations below 4 GiB)");
+        hipLaunchKernelGGL((k_gemm_q8_wide<false>), dim3((rgs + 3) / 4, nsseg, (ntok + 31) / 32), dim3(256), 0, st, w, row0, nrows, xq, xd, out, out_stride, ntok, 0, (int8_t*)nullptr, (uint16_t*)nullptr);
+        return;
     case LIN_GEMM_Q8_TOK: {
         const size_t lds = 16 * 2048 + 16 * 128 + 8 * 16 * 64 * 4; // 66 KiB: activations of 16 tokens + segment sums
         init_kernel_attributes(); // (normally done at engine construction; a no-op then)
@@ -352,7 +372,10 @@ void run_gateup_q8(hipStream_t st, const LinearPlan& p, const Q8Mat& wgu, int ff
         Q3_TS_SWITCH(wgu, hipLaunchKernelGGL((k_gemm_kq_mfma<true, TS>), dim3(rgs, 1, p.z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad));
     else if (p.form == LIN_GU_Q8_TILE1) hipLaunchKernelGGL((k_gemm_q8_tile1<true>), dim3(rgs, 1, p.z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
     else if (p.form == LIN_GU_Q8_MFMA) hipLaunchKernelGGL((k_gemm_q8_mfma<true>), dim3(rgs, 1, p.z), dim3(wgu.K / 4), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
-    else throw Error("run_gateup_q8: not a fused gate/up form");
+    else if (p.form == LIN_GU_Q8_WIDE) {
+        if ((uint64_t)wgu.Npad * wgu.K >= (1ull << 32) || (uint64_t)ntok * wgu.K >= (1ull << 32)) throw Error("GU_Q8_WIDE: 32-bit lane offsets (matrix and activations below 4 GiB)");
+        hipLaunchKernelGGL((k_gemm_q8_wide<true>), dim3((rgs + 3) / 4, 1, (ntok + 31) / 32), dim3(256), 0, st, wgu, 0, ff, xq, xd, (float*)nullptr, 0, ntok, ff, aq, ad);
+    } else throw Error("run_gateup_q8: not a fused gate/up form");
 }
 // gate/up GEMM + SwiGLU + int8 quantisation for batched steps (ntok >= 16, K = 1024 or 2048); false = the plan says GEMV + k_swiglu_quant
 bool launch_gateup_mfma(hipStream_t st, const Q8Mat& wgu, int ff, const int8_t* xq, const uint16_t* xd, int8_t* aq, uint16_t* ad, int ntok) {
@@ -586,6 +609,211 @@ __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_mfma(Q8Mat w, int row0, int nrows, c
     }
     Q3_STAMP(6);
     Q3_STAMP_FLUSH();
+}
+
+// -----------------------------------------------------------------------------------------------------
+// Wide form of the batched int8 GEMM: prompt chunks above 256 tokens, where a launch is throughput-bound.  Same arithmetic as k_gemm_q8_mfma per
+// (row, token): same block dots, same fma chain per segment, segment sums added in order -> same bits.  What differs is who owns what:
+//   * a wave owns one 32-row group and walks the whole super-segment (up to 8 segments = 64 blocks) itself.  The chain of the running segment and
+//     the sum of the finished ones stay in its registers: no cross-wave combine, and no barrier that the arithmetic needs.
+//   * the wave carries one token tile of 32 (the gate/up form: that tile for the gate rows and for the matching up rows, which share the A operand).
+//     Its 1 KiB weight blocks -- stored as the B operand -- are fetched PF blocks ahead of their use.  (Two token tiles per wave, each weight block
+//     feeding two matrix instructions, was built and measured on MI355X at 512 tokens: gate/up 61.7 vs 51.2 us, q/k/v 22.0 vs 20.0, down 29.9 vs
+//     30.6 -- the kernel is bound by the latency of its matrix-result -> fma chains, not by the weight stream, and half as many waves hide less.)
+//   * the 4 waves of a workgroup take 4 neighbouring row groups and share the 32 tokens' activations: one segment (256 int8 + 8 f16 scales per
+//     token) at a time goes through LDS, fetched with coalesced 16-byte loads while the segment before it is being multiplied, double-buffered:
+//     one LDS-only barrier per segment.  Token rows are 272 bytes apart in LDS, so the 16-byte A-operand reads of 16 tokens cover all 64 banks.
+// The scale tiles d_x d_w come from the f32 matrix pipe as in k_gemm_q8_mfma.  K > 2048 keeps one output slab per super-segment (blockIdx.y).
+// Launch: grid (ceil(row groups / 4), super-segments, token tiles), 256 threads.
+// -----------------------------------------------------------------------------------------------------
+template <bool GU>
+__global__ void Q3_GEMM_Q8_WIDE_BUDGET k_gemm_q8_wide(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, const uint16_t* __restrict__ xd,
+                                                      float* __restrict__ out, int out_stride, int ntok, int ff, int8_t* __restrict__ aq,
+                                                      uint16_t* __restrict__ ad) {
+    constexpr int T = 1, TT = 32 * T, NQ = GU ? 2 : 1, NA = NQ * T; // token tiles per wave; tokens per workgroup; weight row sets (gate, up); accumulator tiles per wave
+    constexpr int XROW = 272;                                 // LDS bytes per token and segment: 256 + 16 of padding
+    constexpr int PF = 8 / NQ;                                // weight blocks in flight per row set
+    constexpr int NP = 2 * T, PSTEP = 4 / NP;                 // 16-byte activation pieces per thread and segment (TT x 16 / 256 threads): one every PSTEP block pairs
+    __shared__ __attribute__((aligned(16))) unsigned char xs[2][TT * XROW];
+    __shared__ __attribute__((aligned(16))) uint4 ds[2][TT];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, half = lane >> 5;
+    const int nseg = w.K >> 8, nb = w.K >> 5;
+    const int sseg = blockIdx.y;
+    int nsg = nseg - sseg * 8;
+    if (nsg > 8) nsg = 8;
+    const int nblk = nsg * 8;
+    const int tok0 = blockIdx.z * TT;
+    const int rgi = blockIdx.x * 4 + wave;       // this wave's row group within [row0, row0 + nrows)
+    const bool active = rgi * 32 < nrows;        // wave-uniform.  An idle wave (rows past the end) walks its clamped rows like the others and stores nothing
+    // ---- staging: thread t moves piece (t & 15) of tokens (t >> 4) + 16 k, k < NP; threads < TT the 8 block scales of one token ----
+    const int pc = threadIdx.x & 15, pm = threadIdx.x >> 4;
+    // (addresses = a wave-uniform 64-bit base that moves with the segment + a 32-bit lane offset fixed for the launch: the loads take the base from
+    // scalar registers and the chain's VALU stays free of address arithmetic; the launcher checks that the offsets fit 32 bits)
+    uint32_t xoff[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        int tok = tok0 + pm + 16 * k;
+        if (tok > ntok - 1) tok = ntok - 1;      // tokens past the end repeat the last one; their results are not stored
+        xoff[k] = (uint32_t)tok * (uint32_t)w.K + pc * 16;
+    }
+    const int8_t* const xseg0 = xq + (size_t)sseg * 2048;
+    auto xaddr = [&](int k, int s) { return reinterpret_cast<const uint4*>(xseg0 + (size_t)s * 256 + xoff[k]); };
+    const int dm = threadIdx.x % TT;            // (every thread moves a token's scales: the 256 / TT copies of a token store the same 16 bytes -- no branch)
+    int dtok = tok0 + dm;
+    if (dtok > ntok - 1) dtok = ntok - 1;
+    const uint32_t doff = (uint32_t)dtok * (uint32_t)nb;
+    const uint16_t* const dseg0 = xd + sseg * 64;
+    auto daddr = [&](int s) { return reinterpret_cast<const uint4*>(dseg0 + (size_t)s * 8 + doff); };
+    // ---- weights: blocks [0, nblk) of the wave's rows are one contiguous stream of 1 KiB pieces ----
+    uint32_t woff[NQ], scoff[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        int row = row0 + rgi * 32 + r + q * ff;
+        if (row > w.Npad - 1) row = w.Npad - 1;
+        const int rg = row >> 5, r32 = row & 31;
+        woff[q] = ((uint32_t)rg * (uint32_t)nb) * 1024u + half * 512 + r32 * 16;
+        scoff[q] = (((uint32_t)rg * (uint32_t)nseg) * 32 + r32) * 8 + half; // lanes 0..31 feed a pair's first block scale, 32..63 its second
+    }
+    const uint8_t* const wseg0 = w.qs + (size_t)sseg * 64 * 1024;
+    const uint16_t* const scseg0 = w.sc + (size_t)sseg * 8 * 256;
+    auto waddr = [&](int q, int blk) { return reinterpret_cast<const i32x4v*>(wseg0 + (size_t)blk * 1024 + woff[q]); };
+    auto scaddr = [&](int q, int pair) { return scseg0 + (size_t)((pair >> 2) * 256 + (pair & 3) * 2) + scoff[q]; };
+    i32x4v wv[NQ][PF];
+    uint32_t ew[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+#pragma unroll
+        for (int i = 0; i < PF; i++) wv[q][i] = *waddr(q, i);
+        ew[q] = *scaddr(q, 0);
+    }
+#pragma unroll
+    for (int k = 0; k < NP; k++) *reinterpret_cast<uint4*>(&xs[0][(pm + 16 * k) * XROW + pc * 16]) = *xaddr(k, 0);
+    ds[0][dm] = *daddr(0);
+    wg_barrier_lds();
+    // C layout: column = lane & 31 (weight row), C row = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5) (token)
+    f32x2v acc2[NA][8], S2[NA][8];
+    // The chain is VALU-bound (16 conversions + 8 packed fmas per block and tile).  The int8 matrix instruction starts from the bit pattern of
+    // 1.5 * 2^23 instead of 0: |dot| <= 32 * 127 * 127 < 2^22, so pattern + dot is the float 1.5 * 2^23 + dot exactly, and subtracting 1.5 * 2^23 --
+    // exact as well -- gives (float)dot in one packed add per pair instead of two conversions.  The constant tile lives in 16 registers.
+    i32x16 cmagic;
+#pragma unroll
+    for (int g = 0; g < 16; g++) cmagic[g] = 0x4B400000;
+    asm volatile("" : "+v"(cmagic)); // (opaque: kept in registers, not rebuilt in front of every matrix instruction)
+    const f32x2v fmagic = f32x2v{12582912.0f, 12582912.0f};
+#pragma unroll 1
+    for (int s = 0; s < nsg; s++) {
+        const int p = s & 1;
+        const bool more = s + 1 < nsg;
+#pragma unroll
+        for (int a = 0; a < NA; a++)
+#pragma unroll
+            for (int g = 0; g < 8; g++) acc2[a][g] = f32x2v{0.0f, 0.0f};
+#pragma unroll
+        for (int ip = 0; ip < 4; ip++) { // block pairs: one f32 matrix instruction lays out the scale tiles of two blocks
+            // in flight under this pair's arithmetic: one piece of the next segment's activations, and the next pair's weight scales.  The segment's
+            // arithmetic is ONE basic block (behind the last segment the last one is staged again, unused): with a branch in it the compiler sinks
+            // the fma chains below the branch, every matrix result stays live, and the kernel spills
+            const bool stage = ip % PSTEP == 0; // (constants once the pair loop is unrolled)
+            const int k = ip / PSTEP;
+            const int sn = more ? s + 1 : s;
+            uint4 px = make_uint4(0, 0, 0, 0), pd = px;
+            if (stage) px = *xaddr(k, sn);
+            if (stage && k == 0) pd = *daddr(sn);
+            uint32_t ewn[NQ];
+            {
+                int lp = s * 4 + ip + 1; // (past the end: the last pair again, unused)
+                if (lp > nsg * 4 - 1) lp = nsg * 4 - 1;
+#pragma unroll
+                for (int q = 0; q < NQ; q++) ewn[q] = *scaddr(q, lp);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < T; j++) {
+                const unsigned char* xp = &xs[p][(j * 32 + r) * XROW + half * 16 + ip * 64];
+                const i32x4v av0 = *reinterpret_cast<const i32x4v*>(xp), av1 = *reinterpret_cast<const i32x4v*>(xp + 32);
+                const uint32_t ex = reinterpret_cast<const uint16_t*>(&ds[p][j * 32 + r])[2 * ip + half];
+#pragma unroll
+                for (int q = 0; q < NQ; q++) {
+                    const int a = q * T + j;
+                    f32x32q D;
+#pragma unroll
+                    for (int g = 0; g < 32; g++) D[g] = 0.0f;
+                    D = __builtin_amdgcn_mfma_f32_32x32x1f32(h2f(ex), h2f(ew[q]), D, 0, 0, 0);
+#pragma unroll
+                    for (int i2 = 0; i2 < 2; i2++) {
+                        const i32x16 c = __builtin_amdgcn_mfma_i32_32x32x32_i8(i2 ? av1 : av0, wv[q][(2 * ip + i2) % PF], cmagic, 0, 0, 0);
+#pragma unroll
+                        for (int g4 = 0; g4 < 4; g4++) {
+                            const int o = 16 * i2 + 4 * g4;
+                            const f32x2v sc_a = f32x2v{D[o], D[o + 1]}, sc_b = f32x2v{D[o + 2], D[o + 3]};
+                            const f32x2v ca = f32x2v{__int_as_float(c[4 * g4]), __int_as_float(c[4 * g4 + 1])} - fmagic;
+                            const f32x2v cb = f32x2v{__int_as_float(c[4 * g4 + 2]), __int_as_float(c[4 * g4 + 3])} - fmagic;
+                            acc2[a][2 * g4] = __builtin_elementwise_fma(ca, sc_a, acc2[a][2 * g4]);
+                            acc2[a][2 * g4 + 1] = __builtin_elementwise_fma(cb, sc_b, acc2[a][2 * g4 + 1]);
+                        }
+                        // (the chain is pure arithmetic, which instruction selection may emit on either side of a scheduling barrier: an empty volatile asm
+                        // over the accumulators is ordered with the barriers and holds the block's chain in front of it)
+                        asm volatile("" : "+v"(acc2[a][0]), "+v"(acc2[a][1]), "+v"(acc2[a][2]), "+v"(acc2[a][3]), "+v"(acc2[a][4]), "+v"(acc2[a][5]),
+                                          "+v"(acc2[a][6]), "+v"(acc2[a][7]));
+                    }
+                    // one (tile, row set, block pair) at a time: left alone, the scheduler issues every matrix instruction of the segment first, and
+                    // their 48 result registers each do not fit (the kernel then spills); the SIMD's other wave fills the gaps instead
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (stage) *reinterpret_cast<uint4*>(&xs[p ^ 1][(pm + 16 * k) * XROW + pc * 16]) = px;
+            if (stage && k == 0) ds[p ^ 1][dm] = pd;
+            // the pair's weight registers are free: fetch the blocks PF further down the stream into them
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+#pragma unroll
+                for (int i2 = 0; i2 < 2; i2++) {
+                    int nxt = s * 8 + 2 * ip + i2 + PF; // (past the end: the last block again, unused -- no branch in the chain)
+                    if (nxt > nblk - 1) nxt = nblk - 1;
+                    wv[q][(2 * ip + i2) % PF] = *waddr(q, nxt);
+                }
+                ew[q] = ewn[q];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // segment sums in spec order: S = acc_0; S = S + acc_s
+        if (s == 0) {
+#pragma unroll
+            for (int a = 0; a < NA; a++)
+#pragma unroll
+                for (int g = 0; g < 8; g++) S2[a][g] = acc2[a][g];
+        } else {
+#pragma unroll
+            for (int a = 0; a < NA; a++)
+#pragma unroll
+                for (int g = 0; g < 8; g++) S2[a][g] = S2[a][g] + acc2[a][g];
+        }
+        if (more) wg_barrier_lds(); // the next segment's activations are in place, and nobody still reads the buffer the segment after it overwrites
+    }
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+#pragma unroll
+        for (int g = 0; g < 16; g++) {
+            const int tok = tok0 + j * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
+            if (!GU) {
+                const int orow = rgi * 32 + r;
+                if (orow < nrows && tok < ntok) out[((size_t)sseg * ntok + tok) * out_stride + orow] = S2[j][g >> 1][g & 1];
+            } else {
+                const float y = q3_swiglu(S2[j][g >> 1][g & 1], S2[T + j][g >> 1][g & 1]);
+                float amax = q3_fabsf(y); // over the 32 rows of the block = the 32 lanes of this half
+                amax = fmaxf(amax, xor_lane<16>(amax)); amax = fmaxf(amax, xor_lane<8>(amax)); amax = fmaxf(amax, xor_lane<4>(amax));
+                amax = fmaxf(amax, xor_lane<2>(amax)); amax = fmaxf(amax, xor_lane<1>(amax));
+                const float dd = amax / 127.0f;
+                const float id = (dd != 0.0f) ? (1.0f / dd) : 0.0f;
+                if (tok < ntok) {
+                    aq[(size_t)tok * ff + rgi * 32 + r] = (int8_t)(int)q3_rintf(y * id);
+                    if (r == 0) ad[(size_t)tok * (ff >> 5) + rgi] = f2h(dd);
+                }
+            }
+        }
+    }
 }
 
 

@@ -43,6 +43,14 @@ public:
     const TfHparams& hp() const { return hp_; }
     int n_ctx() const { return n_ctx_; }
     int max_tok() const { return max_tok_; }
+    // a new activation workspace for launches of up to max_tok tokens (before the context's first launch)
+    void set_max_tok(int max_tok) { max_tok_ = max_tok; alloc_workspace(); }
+    // every layer matrix is a uniform Q8_0 one: the shapes the wide prompt-chunk GEMM forms take (plan_linear above 256 tokens)
+    bool q8_uniform() const {
+        if (float_mode_ || ggml_mode_) return false;
+        for (const Layer& L : layers_) if (L.wqkv.rg_type || L.wo.rg_type || L.wgu.rg_type || L.wdown.rg_type) return false;
+        return true;
+    }
     size_t weight_bytes() const { return weight_bytes_; }       // repacked matmul weights (algorithmic bytes/step)
     size_t layer_weight_bytes() const { return layer_weight_bytes_; }
     size_t head_bytes_per_row() const { return (size_t)hp_.n_embd + (size_t)(hp_.n_embd / 32) * 2; }

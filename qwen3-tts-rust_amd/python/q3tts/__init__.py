@@ -1715,7 +1715,7 @@ class Tokenizer:  # utils/tokenizer.rs:4-38
 LOP_GEMV, LOP_GATEUP, LOP_NORM, LOP_NORM_GEMV, LOP_NORM_ARGMAX, LOP_NORM_GATEUP, LOP_F_GEMV, LOP_F_GATEUP = range(8)
 LIN_FORMS = ["AUTO", "GEMV_Q8", "GEMM_Q8_TOK", "GEMM_Q8_MFMA", "GEMM_Q8_TILE1", "GEMV_KQ", "GEMM_KQ_MFMA", "GU_Q8_TILE1", "GU_Q8_MFMA", "GU_KQ_MFMA",
              "GU_UNFUSED", "NORM", "NORM_WG", "GEMV_NORM", "GEMV_NORM_ARGMAX", "GU_SWIGLU_NORM", "F_GEMV", "F_MFMA16", "F_MFMA", "F_GU_MFMA16",
-             "F_GU_UNFUSED"]
+             "F_GU_UNFUSED", "GEMM_Q8_WIDE", "GU_Q8_WIDE"]
 LIN = {n: i for i, n in enumerate(LIN_FORMS)}
 
 
