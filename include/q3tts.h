@@ -873,6 +873,40 @@ typedef struct q3tts_frame_glue_desc {
 } q3tts_frame_glue_desc;
 int q3tts_op_frame_glue(q3tts_frame_glue_desc* d);
 
+/* [EXT] test surface of the ggml-mode kernels (csrc/ggml_mode.hip; Q3_SPEC=ggml), host buffers, no model: one call uploads what the caller
+ * gives, runs ONE launcher of ggml_mode.h on it (LINEAR: gg_quant then gg_matvec, as Transformer::gg_linear chains them) and downloads every
+ * guarded buffer whole.  Guarded buffers follow q3tts_op_frame_glue: Q3TTS_GLUE_GUARD guard elements, the core, as many guard elements; the
+ * device works at element Q3TTS_GLUE_GUARD, the core may be larger than the minimum, and whatever the caller pre-set outside the logical
+ * output shows a stray write.
+ *   LOAD_ROWS  out[t*k + i] = x[row(t)*x_stride + i], i < k: row(t) = t, idx[t*idx_stride] or the code of idx_keys[t*idx_stride] (an argmax
+ *              key); x holds x_rows rows (x_floats >= (x_rows-1)*x_stride + k, x_stride >= k), every selected row is checked against x_rows,
+ *              idx / idx_keys hold idx_n >= (ntok-1)*idx_stride + 1 entries.  out core >= ntok*k
+ *   ADD        out[i] = out[i] + x[i], i < n.  x_floats >= n, out core >= n
+ *   RMSNORM    out [ntok][k] = ggml's RMSNorm of x [ntok][k] with weight u [k] and eps
+ *   QUANT      x [ntok][k] f32 (k % 256 == 0) -> q8 [ntok][k], d8 [ntok][k/32] (f16 bits), qk [ntok][k], dk [ntok][k/256], bs [ntok][k/16]
+ *   MATVEC     out[t*out_stride + r] = W[row0 + r] . activation row t, r < nrows, from the five quantised arrays as given (all five are
+ *              required; the kernel reads q8 / d8 for type 8 and qk / dk / bs for types 13 / 14).  W = `rows` raw GGUF rows of k weights of
+ *              `type`.  out_stride >= nrows, out core >= (ntok-1)*out_stride + nrows
+ *   LINEAR     QUANT of x, then MATVEC: the five arrays come back as QUANT left them
+ *   SWIGLU     out[i] = silu(x[i]) * u[i], i < n
+ * Refusals happen before anything is uploaded and leave every buffer unwritten: what gg_matvec refuses (a type other than 8 / 13 / 14, a row
+ * range outside [0, rows]), a buffer too small for its shape, ntok > 65535.  MATVEC / LINEAR with nrows == 0 or ntok == 0 (after those
+ * checks), and every other op with ntok == 0 (ADD / SWIGLU: n == 0), are no-ops that write nothing. */
+enum { Q3TTS_GG_LOAD_ROWS = 0, Q3TTS_GG_ADD = 1, Q3TTS_GG_RMSNORM = 2, Q3TTS_GG_QUANT = 3, Q3TTS_GG_MATVEC = 4, Q3TTS_GG_LINEAR = 5,
+       Q3TTS_GG_SWIGLU = 6 };
+typedef struct q3tts_ggml_desc {
+    int32_t op;                      /* Q3TTS_GG_* */
+    int32_t ntok, k;                 /* token rows and their width (LOAD_ROWS / RMSNORM: the row length d) */
+    int64_t n;                       /* ADD / SWIGLU: elements */
+    const float* x; int64_t x_floats; int32_t x_stride; int32_t x_rows;   /* x_stride / x_rows: LOAD_ROWS only */
+    const float* u; float eps;       /* RMSNORM: weight [k]; SWIGLU: up [n] */
+    const int32_t* idx; const uint64_t* idx_keys; int32_t idx_stride; int64_t idx_n;
+    const void* w; int32_t type, rows, row0, nrows, out_stride;
+    q3tts_guarded out;               /* float */
+    q3tts_guarded q8, d8, qk, dk, bs;   /* int8, uint16, int8, float, int16 */
+} q3tts_ggml_desc;
+int q3tts_op_ggml(q3tts_ggml_desc* d);
+
 /* [EXT] output formats (q3tts_spec.h "output formats"): sample-rate conversion and int16 PCM on the device, behind the codec.
  * Host only, no device needed:
  *   q3tts_pcm_out_plan     L, M, the prototype's tap count N and the most taps one output sample sums (24000: 1, 1, 0, 0); < 0 for a

@@ -75,6 +75,8 @@ void q3o_matvec(int type, const void* w, int64_t n, int64_t k, const int8_t* xq,
 int q3o_arith_mode(void);
 void q3o_set_arith_mode(int mode);
 void q3o_matvec_ggml(int type, const void* w, int64_t n, int64_t k, const float* xf, float* y);
+void q3o_quant_q8_0_ggml(const float* x, int64_t k, int8_t* q, uint16_t* d16);                  /* quantize_row_q8_0_ref: [k], [k/32] f16 bits */
+void q3o_quant_q8_K_ggml(const float* x, int64_t k, int8_t* qs, float* d, int16_t* bsums);      /* quantize_row_q8_K_ref: [k], [k/256], [k/16] */
 void q3o_rmsnorm_ggml(const float* x, const float* g, int64_t d, float eps, float* y);
 void q3o_headnorm128_ggml(const float* x, const float* g, float eps, float* y);
 float q3o_swiglu_ggml(float gt, float up);

@@ -165,6 +165,15 @@ static float dot_q6_K(const uint8_t* row, int64_t k, const blk_q8_K* y) {
     return sumf;
 }
 
+/* the two activation quantisers on their own (tests hold a numpy restatement against them): Q8_K blocks come back as three plain arrays */
+void q3o_quant_q8_0_ggml(const float* x, int64_t k, int8_t* q, uint16_t* d16) { quant_q8_0_ggml(x, k, q, d16); }
+void q3o_quant_q8_K_ggml(const float* x, int64_t k, int8_t* qs, float* d, int16_t* bsums) {
+    blk_q8_K* y = (blk_q8_K*)malloc(sizeof(blk_q8_K) * (size_t)(k / 256));
+    quant_q8_K_ggml(x, k, y);
+    for (int64_t i = 0; i < k / 256; i++) { d[i] = y[i].d; memcpy(qs + 256 * i, y[i].qs, 256); memcpy(bsums + 16 * i, y[i].bsums, sizeof(y[i].bsums)); }
+    free(y);
+}
+
 /* y[n] = W[n][k] . x  the way ggml's CPU backend would: activations converted once per call to the weight type's vec_dot_type */
 void q3o_matvec_ggml(int type, const void* w, int64_t n, int64_t k, const float* xf, float* y) {
     const size_t rb = q3o_type_row_bytes(type, k);

@@ -1018,6 +1018,95 @@ int q3tts_op_frame_glue(q3tts_frame_glue_desc* dp) {
     Q3_API_END(Q3TTS_ERR)
 }
 
+/* [EXT] the ggml-mode kernels over host buffers (include/q3tts.h): every check first, then the uploads, one launcher of ggml_mode.h (LINEAR:
+ * the two gg_linear chains), and every guarded buffer downloaded whole. */
+int q3tts_op_ggml(q3tts_ggml_desc* dp) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(dp, "null ggml-mode descriptor");
+    const q3tts_ggml_desc& d = *dp;
+    Q3_CHECK(d.op >= Q3TTS_GG_LOAD_ROWS && d.op <= Q3TTS_GG_SWIGLU, "unknown ggml-mode op");
+    const bool flat = d.op == Q3TTS_GG_ADD || d.op == Q3TTS_GG_SWIGLU;
+    const bool mat = d.op == Q3TTS_GG_MATVEC || d.op == Q3TTS_GG_LINEAR, quant = d.op == Q3TTS_GG_QUANT || mat;
+    const auto holds = [](const q3tts_guarded& g, size_t core) { return g.p && g.n >= (int64_t)(core + 2 * Q3TTS_GLUE_GUARD); };
+    GlueBuf<float> out, dk;
+    GlueBuf<int8_t> q8, qk;
+    GlueBuf<uint16_t> d8;
+    GlueBuf<int16_t> bs;
+    DevBuf<float> dx, du;
+    if (flat) {
+        Q3_CHECK(d.n >= 0 && d.n <= ((int64_t)1 << 31), "n out of [0, 2^31]");
+        if (d.n == 0) return Q3TTS_OK;
+        const size_t n = (size_t)d.n;
+        Q3_CHECK(d.x && d.x_floats >= d.n && holds(d.out, n), "x / out do not hold n elements");
+        Q3_CHECK(d.op == Q3TTS_GG_ADD || d.u, "u missing");
+        out.up(d.out, n, "out");
+        dx.alloc(n); dx.upload(d.x, n);
+        if (d.op == Q3TTS_GG_ADD) gg_add(0, out.p(), dx.p, n);
+        else { du.alloc(n); du.upload(d.u, n); gg_swiglu(0, dx.p, du.p, out.p(), n); }
+        Q3_LAUNCH_CHECK();
+        Q3_HIP(hipDeviceSynchronize());
+        out.down();
+        return Q3TTS_OK;
+    }
+    Q3_CHECK(d.ntok >= 0 && d.ntok <= 65535 && d.k >= 1, "ntok out of [0, 65535] or k < 1");
+    const size_t nt = (size_t)d.ntok, k = (size_t)d.k;
+    GgMat w;
+    if (mat) { // what gg_matvec refuses, refused here before anything moves
+        w.type = d.type; w.n = d.rows; w.k = d.k;
+        Q3_CHECK(w.type == Q3_T_Q8_0 || w.type == Q3_T_Q5_K || w.type == Q3_T_Q6_K, "ggml mode serves Q8_0 / Q5_K / Q6_K matrices");
+        Q3_CHECK(d.rows >= 0 && d.row0 >= 0 && d.nrows >= 0 && (int64_t)d.row0 + d.nrows <= d.rows, "ggml-mode matvec row range");
+        if (d.nrows == 0) return Q3TTS_OK;
+    }
+    if (nt == 0) return Q3TTS_OK;
+    if (quant) {
+        Q3_CHECK(d.k % 256 == 0, "k % 256 != 0");
+        Q3_CHECK(holds(d.q8, nt * k) && holds(d.d8, nt * k / 32) && holds(d.qk, nt * k) && holds(d.dk, nt * k / 256) && holds(d.bs, nt * k / 16),
+                 "a quantised array does not hold ntok rows");
+    }
+    if (d.op == Q3TTS_GG_LOAD_ROWS) {
+        Q3_CHECK(d.x && d.x_rows >= 1 && d.x_stride >= d.k && d.x_floats >= (int64_t)(d.x_rows - 1) * d.x_stride + d.k, "x does not hold x_rows rows");
+        Q3_CHECK(!(d.idx && d.idx_keys) && holds(d.out, nt * k), "both index forms given, or out too small");
+        if (d.idx || d.idx_keys) {
+            Q3_CHECK(d.idx_stride >= 1 && d.idx_n >= (int64_t)(nt - 1) * d.idx_stride + 1, "idx / idx_keys do not hold ntok entries");
+            for (size_t t = 0; t < nt; t++) {
+                const int64_t row = d.idx_keys ? (int64_t)key_code(d.idx_keys[t * d.idx_stride]) : (int64_t)d.idx[t * d.idx_stride];
+                Q3_CHECK(row >= 0 && row < d.x_rows, "a selected row lies outside x");
+            }
+        } else Q3_CHECK(d.ntok <= d.x_rows, "x holds fewer than ntok rows");
+    } else if (d.op != Q3TTS_GG_MATVEC) {
+        Q3_CHECK(d.x && d.x_floats >= (int64_t)(nt * k), "x does not hold [ntok][k]");
+    }
+    if (d.op == Q3TTS_GG_RMSNORM) Q3_CHECK(d.u && holds(d.out, nt * k), "weight missing or out too small");
+    if (mat) {
+        Q3_CHECK(d.w && d.out_stride >= d.nrows && holds(d.out, (nt - 1) * d.out_stride + d.nrows), "weights missing, out_stride < nrows or out too small");
+        w.row_bytes = q3_gguf_row_bytes(w.type, w.k);
+    }
+    // ---- uploads, the launch, downloads ----
+    DevBuf<uint8_t> dw; DevBuf<int32_t> didx; DevBuf<unsigned long long> dkeys;
+    if (d.op != Q3TTS_GG_QUANT) out.up(d.out, 0, "out");
+    if (quant) { q8.up(d.q8, 0, "q8"); d8.up(d.d8, 0, "d8"); qk.up(d.qk, 0, "qk"); dk.up(d.dk, 0, "dk"); bs.up(d.bs, 0, "bs"); }
+    if (d.op != Q3TTS_GG_MATVEC) { dx.alloc((size_t)d.x_floats); dx.upload(d.x, dx.n); }
+    if (d.op == Q3TTS_GG_LOAD_ROWS) {
+        if (d.idx) { didx.alloc((size_t)d.idx_n); didx.upload(d.idx, didx.n); }
+        if (d.idx_keys) { dkeys.alloc((size_t)d.idx_n); dkeys.upload((const unsigned long long*)d.idx_keys, dkeys.n); }
+        gg_load_rows(0, dx.p, d.x_stride, didx.p, d.idx_stride, dkeys.p, d.k, out.p(), d.ntok);
+    } else if (d.op == Q3TTS_GG_RMSNORM) {
+        du.alloc(k); du.upload(d.u, k);
+        gg_rmsnorm(0, dx.p, du.p, d.k, d.eps, out.p(), d.ntok);
+    } else {
+        const GgAct act{q8.p(), d8.p(), qk.p(), dk.p(), bs.p()};
+        if (mat) { dw.alloc(w.row_bytes * (size_t)d.rows); dw.upload((const uint8_t*)d.w, dw.n); w.p = dw.p; }
+        if (d.op != Q3TTS_GG_MATVEC) gg_quant(0, dx.p, d.k, act, d.ntok);
+        if (mat) gg_matvec(0, w, d.row0, d.nrows, act, out.p(), d.out_stride, d.ntok);
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    out.down(); q8.down(); d8.down(); qk.down(); dk.down(); bs.down();
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 /* [EXT] output formats: the host-only half (pcm_out.h) */
 int q3tts_pcm_out_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_phase) {
     Q3_API_BEGIN

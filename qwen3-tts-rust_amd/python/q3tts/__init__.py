@@ -94,7 +94,7 @@ SYMBOLS = [
     "q3tts_submit_resume", "q3tts_group_submit_resume", "q3tts_op_feedback_rows", "q3tts_engine_prefill_width",
     "q3tts_engine_set_logprobs", "q3tts_fetch_logprobs", "q3tts_group_set_logprobs", "q3tts_group_fetch_logprobs", "q3tts_op_logprob_rows",
     "q3tts_submit_score", "q3tts_group_submit_score", "q3tts_engine_score_width", "q3tts_op_score_rows", "q3tts_op_score_inputs",
-    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows", "q3tts_op_frame_glue",
+    "q3tts_pred_table_bytes", "q3tts_op_attention_keyed", "q3tts_op_select_rows", "q3tts_op_frame_glue", "q3tts_op_ggml",
     "q3tts_submit_candidates", "q3tts_group_submit_candidates", "q3tts_engine_candidate_stats", "q3tts_op_kv_fork",
     "q3tts_submit_decode", "q3tts_group_submit_decode", "q3tts_engine_decode_width", "q3tts_engine_decode_stats",
     "q3tts_engine_set_output_format", "q3tts_request_format", "q3tts_fetch_pcm16", "q3tts_engine_pcm_out_stats",
@@ -1913,6 +1913,50 @@ def op_frame_glue(kernel, tables=None, **fields):
         keep += [tabs, ptrs, rows]
         d.tables, d.table_rows = C.cast(ptrs, C.c_void_p), rows.ctypes.data
     _chk(lib().q3tts_op_frame_glue(C.byref(d)))
+
+
+# ---- the ggml-mode kernels (q3tts_op_ggml) ----
+GG_LOAD_ROWS, GG_ADD, GG_RMSNORM, GG_QUANT, GG_MATVEC, GG_LINEAR, GG_SWIGLU = range(7)
+_GG_GUARDED = {"out": np.float32, "q8": np.int8, "d8": np.uint16, "qk": np.int8, "dk": np.float32, "bs": np.int16}
+_GG_ARRAYS = {"x": np.float32, "u": np.float32, "idx": np.int32, "idx_keys": np.uint64, "w": np.uint8}
+_GG_INTS = ("ntok", "k", "n", "x_stride", "x_rows", "idx_stride", "type", "rows", "row0", "nrows", "out_stride")
+
+
+class GgmlDesc(C.Structure):  # q3tts_ggml_desc
+    _fields_ = [("op", C.c_int32), ("ntok", C.c_int32), ("k", C.c_int32), ("n", C.c_int64),
+                ("x", C.c_void_p), ("x_floats", C.c_int64), ("x_stride", C.c_int32), ("x_rows", C.c_int32),
+                ("u", C.c_void_p), ("eps", C.c_float),
+                ("idx", C.c_void_p), ("idx_keys", C.c_void_p), ("idx_stride", C.c_int32), ("idx_n", C.c_int64),
+                ("w", C.c_void_p), ("type", C.c_int32), ("rows", C.c_int32), ("row0", C.c_int32), ("nrows", C.c_int32), ("out_stride", C.c_int32)] + \
+               [(k, Guarded) for k in ("out", "q8", "d8", "qk", "dk", "bs")]
+
+
+def op_ggml(op, **fields):
+    """one launcher of csrc/ggml_mode.h on caller buffers (q3tts_op_ggml; GG_LINEAR = gg_quant then gg_matvec).  out, q8, d8, qk, dk, bs are
+    whole arrays from glue_guarded and are rewritten in place after the launch ran; a refused call and a no-op leave them as they were."""
+    d = GgmlDesc()
+    d.op = op
+    keep = []
+    for k, v in fields.items():
+        if k in _GG_GUARDED:
+            assert isinstance(v, np.ndarray) and v.dtype == _GG_GUARDED[k] and v.ndim == 1 and v.flags["C_CONTIGUOUS"], k
+            setattr(d, k, Guarded(v.ctypes.data, v.size))
+        elif k in _GG_ARRAYS:
+            a = np.ascontiguousarray(v, _GG_ARRAYS[k]).reshape(-1)
+            keep.append(a)
+            setattr(d, k, a.ctypes.data if a.size else None)
+            if k == "x":
+                d.x_floats = a.size
+            if k in ("idx", "idx_keys"):
+                d.idx_n = a.size
+        elif k in _GG_INTS:
+            setattr(d, k, int(v))
+        elif k == "eps":
+            d.eps = float(v)
+        else:
+            raise TypeError("op_ggml: q3tts_ggml_desc has no field %r for the caller to set" % k)
+    lib().q3tts_op_ggml.argtypes = [C.POINTER(GgmlDesc)]
+    _chk(lib().q3tts_op_ggml(C.byref(d)))
 
 
 # ---- output formats: the host-only half and the convert kernel (q3tts_op_pcm_convert) ----

@@ -25,6 +25,7 @@ def test_all_declared_symbols_are_exported(q3):
     missing = [n for n in decl if not hasattr(L, n)]
     assert not missing, missing
     assert set(q3.SYMBOLS) <= set(decl)
+    assert "q3tts_op_ggml" in decl and "q3tts_op_ggml" in q3.SYMBOLS   # the ggml-mode kernels' test surface (tests/test_gpu_ggml_mode.py)
     llama = [n for n in _declared("q3tts_llama.h") if n.startswith("llama_")]
     assert len(llama) == 28   # llama/mod.rs:241-292: all .expect()-resolved
 
