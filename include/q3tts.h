@@ -254,6 +254,38 @@ int q3tts_voice_set_preamble(q3tts_engine* e, int32_t voice_id, int32_t preamble
 int q3tts_engine_set_preamble(q3tts_engine* e, int32_t preamble_id);
 int q3tts_request_preamble(q3tts_engine* e, int64_t req_id, int32_t* preamble_id);
 int q3tts_engine_preamble_stats(q3tts_engine* e, int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot);
+/* [EXT] prompt stems (q3tts_spec.h "prompt stems"): the head a voice's prompts share -- role, control and speaker rows, the reference text and
+ * codes of a clone voice -- is prefilled once and its talker K/V kept on the device; a request whose prompt starts with exactly those rows
+ * copies the K/V into its pages with one launch per admission wave and prefills only its own rows.  Opt-in; the codes, log-probability rows
+ * and PCM of a request that takes a stem are bit-identical to the same request without one, and a request that does not match runs the
+ * plain path (counted as a mismatch, never an error).
+ * q3tts_stem_create: rows [n_rows][2048] f32, copied.  Thread-safe, no HIP call in the caller's thread: the build is an internal member of
+ * the next admission wave (a slot for one wave, no head, no frame).  < 0 and nothing queued: NULL rows, n_rows outside [1, max_prompt),
+ * Q3TTS_MAX_STEMS live stems, a Q3_SPEC=ggml engine.
+ * q3tts_voice_stem_create: the rows the q3tts_submit_text* forms build in front of the task text for that voice, lang_id and instruction
+ * (NULL / 0: none), through the text BOS row; taken from the prompt builder's own output.
+ * q3tts_stem_poll / _wait: state (Q3TTS_STEM_*) and row count; _wait returns 0 once the stem is READY or FAILED, 1 on timeout, and drives the
+ * scheduler itself when no driver thread runs, as q3tts_wait does.
+ * q3tts_stem_release: the creator's reference goes.  Voices, the engine-level setting and the requests that took the stem hold their own; the
+ * device store is freed (by the scheduler thread) when the last one is gone.  The id is never reused.
+ * q3tts_voice_set_stem: applies the stem to requests of any q3tts_submit_text* form with that voice (-1: none); a changed lang_id or
+ * instruction makes other rows, so such a request runs plain.  q3tts_engine_set_stem: applies it to the raw-prompt forms (q3tts_submit, _ex,
+ * _trailing, _trailing_open, _resume, _candidates), read once per request at submit and once per candidate set (-1: none).  Both refuse a
+ * stem that is not READY.  q3tts_submit_score, q3tts_submit_decode and q3tts_generate_batch* never take a stem.
+ * q3tts_request_stem: the stem a request took and the prompt rows it did not prefill; -1 / 0 when none.
+ * q3tts_engine_stem_stats: stems built, restores (requests restored), prompt rows not prefilled, pages copied (per destination), requests a
+ * stem applied to that ran plain, device bytes the stores hold now. */
+/* Q3TTS_MAX_STEMS and the Q3TTS_STEM_* states: q3tts_spec.h */
+typedef struct q3tts_stem_stats { int64_t built, restores, rows_not_prefilled, pages_copied, mismatches, device_bytes; } q3tts_stem_stats;
+int q3tts_stem_create(q3tts_engine* e, const float* rows, int32_t n_rows, int32_t* stem_id);
+int q3tts_voice_stem_create(q3tts_engine* e, int32_t voice_id, int32_t lang_id, const int32_t* instr_ids, int32_t n_instr, int32_t* stem_id);
+int q3tts_stem_poll(q3tts_engine* e, int32_t stem_id, int32_t* state, int32_t* n_rows);
+int q3tts_stem_wait(q3tts_engine* e, int32_t stem_id, double timeout_ms);
+int q3tts_stem_release(q3tts_engine* e, int32_t stem_id);
+int q3tts_voice_set_stem(q3tts_engine* e, int32_t voice_id, int32_t stem_id);
+int q3tts_engine_set_stem(q3tts_engine* e, int32_t stem_id);
+int q3tts_request_stem(q3tts_engine* e, int64_t req_id, int32_t* stem_id, int32_t* rows_reused);
+int q3tts_engine_stem_stats(q3tts_engine* e, q3tts_stem_stats* out);
 /* [EXT] score (q3tts_spec.h "scoring"): the teacher-forced log-probabilities of frames the caller already holds -- codes [n][16] behind
  * prompt [n_prompt][2048] and optional CLOSED trailing ids [n_trail] (NULL / 0: none).  Queued like any request; ends Q3TTS_REQ_DONE with
  * n_frames = n and no PCM.  prompt, ids and codes are copied.  Row f of q3tts_fetch_logprobs is the row a recording request that emitted
@@ -419,6 +451,16 @@ int q3tts_group_preamble_release(q3tts_group* g, int32_t preamble_id);
 int q3tts_group_voice_set_preamble(q3tts_group* g, int32_t voice_id, int32_t preamble_id);
 int q3tts_group_set_preamble(q3tts_group* g, int32_t preamble_id);
 int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamble_id);
+/* [EXT] prompt stems on every engine under one id, as preambles are (create stems through the group only); _wait waits for all of them, the
+ * setters take a stem that is READY on every engine, _stem_stats adds the engines' counters up */
+int q3tts_group_stem_create(q3tts_group* g, const float* rows, int32_t n_rows, int32_t* stem_id);
+int q3tts_group_voice_stem_create(q3tts_group* g, int32_t voice_id, int32_t lang_id, const int32_t* instr_ids, int32_t n_instr, int32_t* stem_id);
+int q3tts_group_stem_wait(q3tts_group* g, int32_t stem_id, double timeout_ms);
+int q3tts_group_stem_release(q3tts_group* g, int32_t stem_id);
+int q3tts_group_voice_set_stem(q3tts_group* g, int32_t voice_id, int32_t stem_id);
+int q3tts_group_set_stem(q3tts_group* g, int32_t stem_id);
+int q3tts_group_request_stem(q3tts_group* g, int64_t req_id, int32_t* stem_id, int32_t* rows_reused);
+int q3tts_group_stem_stats(q3tts_group* g, q3tts_stem_stats* out);
 int q3tts_group_start(q3tts_group* g);                         /* q3tts_sched_start on every engine */
 int q3tts_group_stop(q3tts_group* g);
 /* q3tts_comm_*: ONE process per GPU (what `bench.py --gpus N` / torchrun-style launchers use).  Rank 0 makes the 128-byte id and ships it to
@@ -636,6 +678,17 @@ int q3tts_op_score_inputs(const float* hidden_proj, const float* const* tabs, co
  * two of the physical pages involved coincide */
 int q3tts_op_kv_fork(uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, int32_t n_layer, int32_t n_kv, const int32_t* page_table,
                      int32_t n_seq, int32_t max_pages, int32_t src_seq, const int32_t* dst_seqs, int32_t n_dst, int32_t n_positions);
+/* [EXT] prompt stems test surface of k_kv_stem, host buffers: k_cache / v_cache as q3tts_op_kv_fork takes them; store_k / store_v
+ * [n_store_pages][n_layer][n_kv][8192] f16 bits, one arena the jobs' stores lie in; all four are uploaded whole and written back whole (a
+ * stray write shows).  Job j: store pages [job_page0[j], job_page0[j] + job_n_pages[j]), slots[job_first[j] .. job_first[j] + job_n_dst[j]).
+ * save = 0 restores store page l into logical page l of every listed slot, save = 1 saves logical page l of the job's one slot into store
+ * page l; one launch for all jobs.  Refused before anything is uploaded or launched: n_jobs < 1; a job with n_pages outside [1, max_pages], a
+ * store range outside the arena, a slot range outside slots, n_dst < 1 (save: != 1); a slot outside [0, n_seq); a page-table entry of a
+ * copied range outside [0, n_pages); restore: two destination pages coincide; save: two jobs' store ranges overlap */
+int q3tts_op_kv_stem(uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, int32_t n_layer, int32_t n_kv, const int32_t* page_table,
+                     int32_t n_seq, int32_t max_pages, uint16_t* store_k, uint16_t* store_v, int32_t n_store_pages, int32_t n_jobs,
+                     const int32_t* job_page0, const int32_t* job_n_pages, const int32_t* job_first, const int32_t* job_n_dst,
+                     const int32_t* slots, int32_t n_slots, int32_t save);
 /* [EXT] resume test surface, host buffers: rows [n][2048] = the feedback rows of codes [n][16] (+ trail ids [n_trail], row f takes id f
  * while f < n_trail; NULL / 0 = every row adds tts_pad) against the given tables (k_feedback_codes) */
 int q3tts_op_feedback_rows(const q3tts_assets* a, const int32_t* codes, int32_t n, const int32_t* trail_ids, int32_t n_trail, float* rows);

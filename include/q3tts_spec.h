@@ -493,6 +493,30 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3_TSM_MIN 50
 #define Q3_TSM_MAX 200
 
+/* ---------------- prompt stems [EXT] (q3tts_stem_*, q3tts_op_kv_stem) ----------------
+ * A stem is n rows [n][2048] f32, 1 <= n < max_prompt, together with the talker K/V of those rows at positions 0 .. n-1: the head a voice's
+ * prompts share, prefilled once, kept on the device in a store of its own (ceil(n / 64) whole pages per plane, the pool's page layout) and
+ * copied into a request's pages where the request's prefill would have written the same bits.
+ *   applies    a text form takes its voice's stem (q3tts_voice_set_stem), a raw-prompt form (q3tts_submit, _ex, _trailing, _trailing_open,
+ *              _resume, _candidates) the engine-level one (q3tts_engine_set_stem); read once per request at submit, once per candidate set
+ *   takes      a request takes stem S when S applies to it, S is READY, n_prompt > n, and the first n * 2048 floats of its prompt are
+ *              bytewise equal (memcmp) to S's rows.  The comparison runs once, at submit
+ *   S1 result  a request that takes S produces exactly the codes, log-probability rows and PCM of the same request without a stem: its
+ *              prefill starts at row n, rows [n, n_prompt) and the feedback rows of a resumed prefix land at the positions they always
+ *              did, and positions [0, n) of its pages hold the store's bytes, which are the bytes its own prefill would have written
+ *              (the talker's arithmetic is batch-invariant and chunk-invariant).  The stale positions of the store's last page, n .. , are
+ *              written by the request's own rows before anything reads them
+ *   S2 else    anything else runs the plain path and is counted as a mismatch, never an error: a wrong or stale stem costs time and
+ *              cannot change a result
+ *   sets       the first member of a candidate set restores, the others are forked from it
+ *   never      score requests, decode-only requests, q3tts_generate_batch*, Q3_SPEC=ggml engines (q3tts_stem_create is refused there)
+ * A setter takes a READY stem only.  At most Q3TTS_MAX_STEMS stems are live per engine; an id is never reused.  The states are the
+ * preamble's, and so is the holder rule: the creator, the voices and the engine-level setting it is set on, and the requests that took it. */
+#define Q3TTS_MAX_STEMS 64
+#define Q3TTS_STEM_BUILDING 0
+#define Q3TTS_STEM_READY 1
+#define Q3TTS_STEM_FAILED -1
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -322,6 +322,68 @@ int q3tts_engine_preamble_stats(q3tts_engine* e, int64_t* built, int64_t* restor
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] prompt stems */
+int q3tts_stem_create(q3tts_engine* e, const float* rows, int32_t n_rows, int32_t* stem_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && stem_id, "null argument");
+    *stem_id = e->e->stem_create(rows, n_rows);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+// The rows the text forms build in front of the task text for this voice, language and instruction: the builder's output for an empty text is
+// head ++ [text EOS row] ++ [codec BOS row], and its last two rows are cut.  The head ends with the text BOS row, which both layouts share.
+int q3tts_voice_stem_create(q3tts_engine* e, int32_t voice_id, int32_t lang_id, const int32_t* instr_ids, int32_t n_instr, int32_t* stem_id) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && stem_id, "null argument");
+    Q3_CHECK(n_instr >= 0 && (n_instr == 0 || instr_ids), "bad arguments");
+    const Voice& v = e->e->voice(voice_id);
+    std::vector<int32_t> none, ins;
+    if (instr_ids) ins.assign(instr_ids, instr_ids + n_instr);
+    int lang = lang_id;
+    const PromptData pd = !v.ref_codes.empty()
+        ? PromptBuilder::build_clone_prompt(e->e->assets(), none, v.ref_codes, v.ref_text_ids, v.spk_emb.data(), lang_id, instr_ids ? &ins : nullptr, nullptr)
+        : PromptBuilder::build_core(e->e->assets(), none, lang_id >= 0 ? &lang : nullptr, nullptr, v.spk_emb.data(), instr_ids ? &ins : nullptr, nullptr, nullptr);
+    *stem_id = e->e->stem_create(pd.embd.data(), pd.n_rows - 2);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_stem_poll(q3tts_engine* e, int32_t stem_id, int32_t* state, int32_t* n_rows) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    int st = 0, n = 0;
+    e->e->stem_poll(stem_id, &st, &n);
+    if (state) *state = st;
+    if (n_rows) *n_rows = n;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_stem_wait(q3tts_engine* e, int32_t stem_id, double timeout_ms) {
+    Q3_API_BEGIN
+    Q3_CHECK(e, "null argument");
+    return e->e->stem_wait(stem_id, timeout_ms) ? 0 : 1;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_stem_release(q3tts_engine* e, int32_t stem_id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stem_release(stem_id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_voice_set_stem(q3tts_engine* e, int32_t voice_id, int32_t stem_id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_voice_stem(voice_id, stem_id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_engine_set_stem(q3tts_engine* e, int32_t stem_id) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_stem(stem_id); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_stem(q3tts_engine* e, int64_t req_id, int32_t* stem_id, int32_t* rows_reused) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && stem_id && rows_reused, "null argument");
+    int sid = -1, n = 0;
+    e->e->request_stem(req_id, &sid, &n);
+    *stem_id = sid; *rows_reused = n;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_stem_stats(q3tts_engine* e, q3tts_stem_stats* out) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && out, "null argument");
+    const Engine::StemStats s = e->e->stem_stats();
+    out->built = s.built; out->restores = s.restores; out->rows_not_prefilled = s.rows_skipped; out->pages_copied = s.pages_copied;
+    out->mismatches = s.mismatches; out->device_bytes = s.bytes_held;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 /* [EXT] speaking rate */
 int q3tts_engine_set_speech_rate(q3tts_engine* e, int32_t rate_pct) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_speech_rate(rate_pct); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_request_speech_rate(q3tts_engine* e, int64_t id, int32_t* rate_pct) {
@@ -410,6 +472,7 @@ static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_id
     if (open) trail.pop_back(); // the TEXT_EOS that ends the trail comes with q3tts_text_append(is_last = 1)
     g.trail = trail.data(); g.n_trail = (int)trail.size(); g.open = open;
     g.preamble = e->e->voice_preamble(voice_id); // [EXT] codec preambles: a text form takes its voice's, never the engine-level setting
+    g.stem = e->e->voice_stem(voice_id);         // [EXT] prompt stems: likewise
     *req_id = e->e->submit(g, want_pcm != 0, true);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)

@@ -485,6 +485,55 @@ int q3tts_op_kv_fork(uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, int3
     Q3_API_END(Q3TTS_ERR)
 }
 
+/* [EXT] prompt stems: k_kv_stem over host images of both cache planes and of a store arena; every precondition is checked before anything is uploaded or launched */
+int q3tts_op_kv_stem(uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, int32_t n_layer, int32_t n_kv, const int32_t* page_table,
+                     int32_t n_seq, int32_t max_pages, uint16_t* store_k, uint16_t* store_v, int32_t n_store_pages, int32_t n_jobs,
+                     const int32_t* job_page0, const int32_t* job_n_pages, const int32_t* job_first, const int32_t* job_n_dst,
+                     const int32_t* slots, int32_t n_slots, int32_t save) {
+    Q3_API_BEGIN
+    Q3_CHECK(n_jobs >= 1 && n_jobs <= 4096, "n_jobs must be in [1, 4096]");
+    Q3_CHECK(k_cache && v_cache && page_table && store_k && store_v && job_page0 && job_n_pages && job_first && job_n_dst && slots, "null argument");
+    Q3_CHECK(n_pages >= 1 && n_layer >= 1 && n_kv >= 1 && n_seq >= 1 && max_pages >= 1 && n_store_pages >= 1 && n_slots >= 1, "bad cache / page table / store shape");
+    Q3_CHECK((int64_t)n_layer * n_kv <= 65536 && (int64_t)(n_pages + n_store_pages) * n_layer * n_kv <= ((int64_t)1 << 24), "cache too large for the test surface");
+    std::vector<char> pool_hit((size_t)n_pages, 0), store_hit((size_t)n_store_pages, 0);
+    int most = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const int np = job_n_pages[j];
+        Q3_CHECK(np >= 1 && np <= max_pages, "a job's n_pages must be in [1, max_pages]");
+        Q3_CHECK(job_page0[j] >= 0 && (int64_t)job_page0[j] + np <= n_store_pages, "a job's store range lies outside the arena");
+        Q3_CHECK(job_n_dst[j] >= 1 && (!save || job_n_dst[j] == 1), "a job's n_dst must be >= 1 (save: exactly 1)");
+        Q3_CHECK(job_first[j] >= 0 && (int64_t)job_first[j] + job_n_dst[j] <= n_slots, "a job's slot range lies outside slots");
+        most = std::max(most, np);
+        for (int l = 0; l < np; l++) {
+            if (save) { Q3_CHECK(!store_hit[job_page0[j] + l], "two jobs' store ranges overlap"); store_hit[job_page0[j] + l] = 1; }
+            for (int d = 0; d < job_n_dst[j]; d++) {
+                const int seq = slots[job_first[j] + d];
+                Q3_CHECK(seq >= 0 && seq < n_seq, "slot out of range");
+                const int pg = page_table[(size_t)seq * max_pages + l];
+                Q3_CHECK(pg >= 0 && pg < n_pages, "page table entry out of range");
+                if (!save) { Q3_CHECK(!pool_hit[pg], "two destination pages coincide"); pool_hit[pg] = 1; }
+            }
+        }
+    }
+    require_gpu();
+    const size_t per = (size_t)n_layer * n_kv * 8192, halfs = (size_t)n_pages * per, shalfs = (size_t)n_store_pages * per;
+    DevBuf<uint16_t> dk(halfs), dv(halfs), sk(shalfs), sv(shalfs);
+    dk.upload(k_cache, halfs); dv.upload(v_cache, halfs); sk.upload(store_k, shalfs); sv.upload(store_v, shalfs);
+    DevBuf<int32_t> dpt((size_t)n_seq * max_pages), ds((size_t)n_slots);
+    dpt.upload(page_table, dpt.n); ds.upload(slots, ds.n);
+    std::vector<StemJob> jobs((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; j++) jobs[j] = StemJob{sk.p + (size_t)job_page0[j] * per, sv.p + (size_t)job_page0[j] * per, job_n_pages[j], job_first[j], job_n_dst[j], 0};
+    DevBuf<StemJob> dj((size_t)n_jobs);
+    dj.upload(jobs.data(), jobs.size());
+    KvCache kv; kv.k = dk.p; kv.v = dv.p; kv.page_table = dpt.p; kv.max_pages = max_pages; kv.n_layer = n_layer; kv.n_kv = n_kv;
+    launch_kv_stem(0, kv, dj.p, n_jobs, most, ds.p, save != 0);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    dk.download(k_cache, halfs); dv.download(v_cache, halfs); sk.download(store_k, shalfs); sv.download(store_v, shalfs);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
 int q3tts_op_gemv_q8(const void* w, int32_t n, int32_t k, const int8_t* xq, const uint16_t* xd, int32_t ntok, float* y, int32_t lpr) {
     Q3_API_BEGIN
     require_gpu();

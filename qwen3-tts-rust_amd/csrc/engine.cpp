@@ -108,7 +108,8 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         // prompts of one admission: at most 4096 rows + routing tables + [EXT] the codes and ids of resumed prefixes (68 B a row) and the
         // codes of score rows (64 B a row) + [EXT] the fork destinations of a wave.  Every piece starts on a 64-byte boundary: six pieces a
         // chunk lose at most 6 x 63 B, over the at most 17 chunks of a 4096-row wave 6426 B, the destinations 63 B more -- inside the 64 KiB slack
-        lane_alloc(pf_, talker_pf_.get(), st_pf_, pf_chunk_, true,(size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4);
+        lane_alloc(pf_, talker_pf_.get(), st_pf_, pf_chunk_, true,(size_t)4096 * (Q3_EMBD * 4 + 24 + 68 + 64) + ((size_t)1 << 16) + (size_t)B * 4 +
+                   (size_t)B * 2 * (sizeof(StemJob) + 4) + 256); // [EXT] prompt stems: the job tables and slot lists of a wave, four pieces
     }
     // ---- per-slot state ----
     hist_stride_ = p.max_steps * 16;
@@ -169,6 +170,7 @@ void Engine::lane_alloc(PrefillLane& L, Transformer* talker, hipStream_t st, int
     L.talker = talker; L.st = st; L.chunk = chunk; L.async = async;
     L.d_rows.alloc((size_t)chunk * Q3_EMBD); L.d_seq.alloc(chunk); L.d_slot.alloc(chunk); L.d_pos.alloc(4 * (size_t)chunk);
     L.d_codes.alloc((size_t)chunk * 16); L.d_ids.alloc(chunk); L.d_fork_dst.alloc(B_);
+    L.d_stem_jobs.alloc((size_t)2 * B_); L.d_stem_slots.alloc((size_t)2 * B_); // [EXT] prompt stems: 40 B a slot for each of restore and save
     L.cur.cap = arena_bytes;
     Q3_HIP(hipHostMalloc((void**)&L.arena, arena_bytes));
 }
@@ -221,6 +223,12 @@ struct Engine::Req {
     // holds it, the snapshot and pinned tail its `reset` task restores (fixed at submit: the preamble was READY); build_pre: this is the hidden
     // decode-only request that builds that preamble, and build_snap the snapshot the decoder thread enqueued at its fence
     int pre = -1; bool pre_held = false; int pre_snap = -1; const float* pre_tail = nullptr; int build_pre = -1, build_snap = -1;
+    // [EXT] prompt stems: the stem the request took (-1: none; kept for request_stem after the end), whether it still holds it, the rows its
+    // prefill skips and the store its wave restores them from (fixed at submit: the stem was READY); build_stem: this is the hidden wave
+    // member that builds that stem -- stem_rows keeps its rows alive, build_store is what the scheduler allocated for it
+    int stem = -1; bool stem_held = false; int n_skip = 0; uint16_t* stem_store = nullptr;
+    int build_stem = -1; std::shared_ptr<const std::vector<float>> stem_rows; uint16_t* build_store = nullptr;
+    bool offline() const { return score || build_stem >= 0; } // takes a slot for one wave and never goes live
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
     size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
     size_t pcm_ready = 0; // samples whose decode has completed (harvested events)
@@ -259,6 +267,8 @@ Engine::~Engine() {
         if (g.second->exec) (void)hipGraphExecDestroy(g.second->exec);
         if (g.second->graph) (void)hipGraphDestroy(g.second->graph);
     }
+    for (auto& s : stems_) if (s.second.store) (void)hipFree(s.second.store); // [EXT] prompt stems
+    for (auto& d : stem_garbage_) (void)hipFree(d.first);
     if (pcm_pinned_) (void)hipHostFree(pcm_pinned_);
     if (pre_tails_) (void)hipHostFree(pre_tails_);
     if (ar_.arena) (void)hipHostFree(ar_.arena);
@@ -427,10 +437,14 @@ void Engine::prefill_wave(PrefillLane& L, const std::vector<Req*>& wave, bool sa
     std::vector<PromptRef> refs;
     std::vector<Req*> batch; std::vector<std::vector<Req*>> rest; // [EXT] candidate sets: a set's later members add no rows
     split_sets(wave, batch, rest);
-    for (Req* r : batch) { total += (size_t)r->r.n_prompt + r->r.n_prefix; refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix}); }
+    for (Req* r : batch) { // [EXT] prompt stems: the rows a stem covers are restored below and neither staged nor prefilled
+        total += (size_t)admission_rows(r->r.n_prompt, r->n_skip, r->r.n_prefix);
+        refs.push_back({r->r.prompt, r->r.n_prompt, r->slot, r->r.n_prefix, r->n_skip});
+    }
     PrefillCursor cur; std::vector<std::pair<int, int>> lasts; std::vector<FbRun> fb;
     std::vector<char> is_score; // [EXT] scoring: which requests of the wave only want their rows scored
     for (Req* r : batch) is_score.push_back(r->score);
+    restore_stems(L, batch); // behind the page-table rows KvPool::ensure put on this stream, in front of the first chunk
     L.talker->set_same_seq_tokens(true);
     for (size_t done = 0; done < total;) {
         const size_t n_max = std::min<size_t>(total - done, (size_t)L.chunk);
@@ -451,12 +465,13 @@ void Engine::prefill_wave(PrefillLane& L, const std::vector<Req*>& wave, bool sa
         L.talker->forward(L.st, in, n, tm, kv_t_->view(), nullptr);
         score_chunk(L.st, *L.talker, batch, score_head_runs(refs, is_score, before, n), hs);
         for (auto& lb : lasts) {
-            if (is_score[lb.first]) continue; // no first frame to draw
+            if (batch[lb.first]->offline()) continue; // no first frame to draw
             if (L.async) head_staged(batch[lb.first], rest[lb.first], lb.second);
             else head_live(batch[lb.first], rest[lb.first], lb.second, sampled);
         }
         done += (size_t)n;
     }
+    save_stems(L, batch); // [EXT] prompt stems: the pages of the wave's builds go into their stores, behind the last chunk
     if (batch.size() < wave.size()) fork_sets(L.st, batch, rest, (int32_t*)stage_take(L, (size_t)B_ * 4), L.d_fork_dst.p); // a wave without a set stages nothing more
 }
 SampleArgs Engine::first_head_args(const float* logits_row, int b) const {
@@ -516,6 +531,103 @@ void Engine::fork_sets(hipStream_t st, const std::vector<Req*>& lead, const std:
         at += n_dst;
     }
     if (at > 0) Q3_LAUNCH_CHECK();
+}
+
+// [EXT] prompt stems.  One k_kv_stem launch restores every stem the wave's prefilled members took: a job per stem, its slots listed together
+// (a candidate set's first member is restored; fork_sets copies its pages to the others behind the last chunk).  The job table and the slot
+// list go up through the lane's staging.  A wave without a stem stages and launches nothing.
+void Engine::restore_stems(PrefillLane& L, const std::vector<Req*>& lead) {
+    std::vector<Req*> takers;
+    for (Req* r : lead) if (r->n_skip > 0) takers.push_back(r);
+    if (takers.empty()) return;
+    std::stable_sort(takers.begin(), takers.end(), [](const Req* a, const Req* b) { return a->stem < b->stem; });
+    Q3_CHECK((int)takers.size() <= B_, "stem restores beyond the slots");
+    StemJob* jobs = (StemJob*)stage_take(L, takers.size() * sizeof(StemJob));
+    int32_t* slots = (int32_t*)stage_take(L, takers.size() * 4);
+    const size_t plane = kv_t_->view().page_stride();
+    int n_jobs = 0, max_pages = 0;
+    for (size_t i = 0; i < takers.size(); i++) {
+        Req* r = takers[i];
+        const int np = stem_pages(r->n_skip);
+        slots[i] = r->slot;
+        if (i == 0 || takers[i - 1]->stem != r->stem) {
+            jobs[n_jobs++] = StemJob{r->stem_store, r->stem_store + (size_t)np * plane, np, (int32_t)i, 0, 0};
+            max_pages = std::max(max_pages, np);
+        }
+        jobs[n_jobs - 1].n_dst++;
+        stem_restores_++; stem_rows_ += r->n_skip; stem_pages_ += np;
+    }
+    Q3_HIP(hipMemcpyAsync(L.d_stem_jobs.p, jobs, (size_t)n_jobs * sizeof(StemJob), hipMemcpyHostToDevice, L.st));
+    Q3_HIP(hipMemcpyAsync(L.d_stem_slots.p, slots, takers.size() * 4, hipMemcpyHostToDevice, L.st));
+    launch_kv_stem(L.st, kv_t_->view(), L.d_stem_jobs.p, n_jobs, max_pages, L.d_stem_slots.p, false);
+    Q3_LAUNCH_CHECK();
+}
+// One k_kv_stem launch saves the pages of every build of the wave into its store: a job per build, one slot each.  The save half of the
+// lane's tables starts at entry B.
+void Engine::save_stems(PrefillLane& L, const std::vector<Req*>& lead) {
+    std::vector<Req*> builds;
+    for (Req* r : lead) if (r->build_stem >= 0) builds.push_back(r);
+    if (builds.empty()) return;
+    StemJob* jobs = (StemJob*)stage_take(L, builds.size() * sizeof(StemJob));
+    int32_t* slots = (int32_t*)stage_take(L, builds.size() * 4);
+    const size_t plane = kv_t_->view().page_stride();
+    int max_pages = 0;
+    for (size_t i = 0; i < builds.size(); i++) {
+        Req* r = builds[i];
+        const int np = stem_pages(r->r.n_prompt);
+        Q3_CHECK(r->build_store, "a stem build without a store");
+        slots[i] = r->slot;
+        jobs[i] = StemJob{r->build_store, r->build_store + (size_t)np * plane, np, (int32_t)i, 1, 0};
+        max_pages = std::max(max_pages, np);
+    }
+    Q3_HIP(hipMemcpyAsync(L.d_stem_jobs.p + B_, jobs, builds.size() * sizeof(StemJob), hipMemcpyHostToDevice, L.st));
+    Q3_HIP(hipMemcpyAsync(L.d_stem_slots.p + B_, slots, builds.size() * 4, hipMemcpyHostToDevice, L.st));
+    launch_kv_stem(L.st, kv_t_->view(), L.d_stem_jobs.p + B_, (int)builds.size(), max_pages, L.d_stem_slots.p + B_, true);
+    Q3_LAUNCH_CHECK();
+}
+// The stores of a wave's builds: one allocation per stem, K plane pages then V plane pages, made by the scheduler thread under
+// capture_mutex() like every allocation after construction.  A failed allocation fails the wave as any scheduler error does.
+void Engine::alloc_stem_stores(const std::vector<Req*>& wave) {
+    bool any = false;
+    for (Req* r : wave) any = any || r->build_stem >= 0;
+    if (!any) return;
+    std::lock_guard<std::mutex> cap(capture_mutex());
+    for (Req* r : wave) {
+        if (r->build_stem < 0) continue;
+        const int64_t bytes = stem_store_bytes(r->r.n_prompt, talker_->hp().n_layer, talker_->hp().n_kv);
+        Q3_HIP(hipMalloc((void**)&r->build_store, (size_t)bytes));
+        stem_bytes_ += bytes;
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = stems_.find(r->build_stem);
+        if (it != stems_.end()) { it->second.store = r->build_store; it->second.bytes = bytes; }
+        else stem_garbage_.emplace_back(r->build_store, bytes); // cannot happen: a building stem is never recycled
+    }
+}
+// Scheduler thread, the wave's prefill and saves complete: the stems are READY, the slots and their KV pages free again, the hidden requests gone.
+void Engine::finish_builds(const std::vector<Req*>& builds) {
+    for (Req* r : builds) {
+        const int b = r->slot;
+        kv_t_->release(b);
+        std::lock_guard<std::mutex> lk(mu_);
+        slot_req_[b] = nullptr; r->slot = -1;
+        const int sid = r->build_stem;
+        auto it = stems_.find(sid);
+        if (it != stems_.end()) {
+            it->second.refs.state = Q3TTS_STEM_READY; stem_built_++;
+            it->second.refs.holders++; stem_unhold(sid); // recycles at once when it was released while it built
+        }
+        if (r->ev_admit) (void)hipEventDestroy(r->ev_admit);
+        reqs_.erase(r->id); // the build request is nobody's to release
+        cv_.notify_all();
+    }
+}
+// Scheduler thread: the stores of stems nobody holds any more.  hipFree waits for the device, so every restore has long completed.
+void Engine::free_stem_stores() {
+    std::vector<std::pair<uint16_t*, int64_t>> dead;
+    { std::lock_guard<std::mutex> lk(mu_); dead.swap(stem_garbage_); }
+    if (dead.empty()) return;
+    std::lock_guard<std::mutex> cap(capture_mutex());
+    for (auto& d : dead) { (void)hipFree(d.first); stem_bytes_ -= d.second; }
 }
 
 // [EXT] resume: the feedback rows of one prefill chunk.  The codes (64 B a frame) and trailing ids of every run go up through hc (pinned, not
@@ -713,6 +825,7 @@ void Engine::harvest(bool block) {
             n_draining_--;
             if (r->decode) n_decoding_--;
             pre_drop(r); // [EXT] codec preambles: the restore this request enqueued has completed
+            stem_drop(r); // [EXT] prompt stems: so has its wave's
             if (r->build_pre >= 0) { // the preamble is built: its snapshot is on the device, its last native samples become its tail
                 auto it = pres_.find(r->build_pre);
                 if (it != pres_.end()) {
@@ -838,10 +951,11 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     r->t_submit = now_ms();
     r->seed = g.sampler.has_seed ? g.sampler.seed
                                  : (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count(); // :473-478
+    if (may_record) { Req* one = r.get(); stem_match(&one, 1, g.stem); } // [EXT] prompt stems: the take rule, once per request; never a blocking batch
     std::lock_guard<std::mutex> lk(mu_);
     // [EXT] codec preambles: the engine-level setting or the caller's (a voice's), read once per request; a blocking batch is never primed
     const int pid = preamble_of_request(r->want_pcm && may_record, g.preamble, eng_pre_);
-    if (pid >= 0) pre_attach(r.get(), pid); // throws before anything is queued
+    if (pid >= 0) { try { pre_attach(r.get(), pid); } catch (...) { stem_drop(r.get()); throw; } } // throws before anything is queued
     return enqueue(std::move(r), pending_);
 }
 
@@ -873,10 +987,16 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
+    {   // [EXT] prompt stems: the take rule, once per set; every member holds the stem, since whichever stands first in the wave is restored
+        std::vector<Req*> members;
+        for (auto& r : rs) members.push_back(r.get());
+        stem_match(members.data(), n, g.stem);
+    }
     std::lock_guard<std::mutex> lk(mu_);
     {   // [EXT] codec preambles: the engine-level setting, read once per set; every member restores the same snapshot into its own stream
         const int pid = preamble_of_request(want_pcm && codec_, g.preamble, eng_pre_);
-        for (int i = 0; pid >= 0 && i < n; i++) pre_attach(rs[i].get(), pid);
+        try { for (int i = 0; pid >= 0 && i < n; i++) pre_attach(rs[i].get(), pid); }
+        catch (...) { for (auto& r : rs) { pre_drop(r.get()); stem_drop(r.get()); } throw; }
     }
     const int64_t set = next_set_++;
     for (int i = 0; i < n; i++) { rs[i]->set = set; req_ids[i] = enqueue(std::move(rs[i]), pending_); }
@@ -936,6 +1056,7 @@ void Engine::collect_appends() {
 int Engine::cancel(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
     Req& r = req(id);
+    Q3_CHECK(r.build_stem < 0, "unknown request id"); // [EXT] prompt stems: a build is internal; q3tts_stem_release is how a stem goes
     if (req_ended(r.state)) return 1;
     if (r.cancel) return 0; // the first cancel is still pending
     r.cancel = true;
@@ -944,6 +1065,7 @@ int Engine::cancel(int64_t id) {
         q.erase(std::find(q.begin(), q.end(), &r));
         r.state = REQ_CANCELLED; r.t_done = now_ms();
         pre_drop(&r); // [EXT] codec preambles: it never enqueued a restore
+        stem_drop(&r); // [EXT] prompt stems: nor one of these
     } else cancel_ids_.push_back(id);
     wake_++;
     cv_.notify_all();
@@ -1002,7 +1124,7 @@ void Engine::admit(bool stalled) {
         std::vector<QueueEntry> q;
         for (Req* r : pending_) {
             if ((int)q.size() >= free_slots && (q.empty() || r->set == 0 || r->set != q.back().set)) break;
-            q.push_back({r->r.n_prompt + r->r.n_prefix, r->want_pcm, r->set});
+            q.push_back({admission_rows(r->r.n_prompt, r->n_skip, r->r.n_prefix), r->want_pcm, r->set});
         }
         for (int take = admission_take(q, free_slots, (int)cs_free_.size(), async_pf_ && n_active_ > 0); take > 0; take--) {
             Req* r = pending_.front();
@@ -1017,6 +1139,7 @@ void Engine::admit(bool stalled) {
         }
     }
     if (batch.empty()) return;
+    alloc_stem_stores(batch); // [EXT] prompt stems: the stores of the wave's builds
     for (Req* r : batch) {
         if (r->want_pcm) { // the decoder thread clears the codec stream's state right before the request's first chunk
             { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, {}, false, false, true}); }
@@ -1033,10 +1156,10 @@ void Engine::admit(bool stalled) {
     // ---- in-line form (nothing is running, or a single-slot engine): one batched prefill of the whole wave on the AR stream ----
     for (Req* r : batch) kv_t_->release(r->slot), kv_t_->ensure(r->slot, kv_positions(r->r, r->score), st_);
     bool sampled = live_variant(slots_).sampled; // of the prefill heads: the wave joins whatever is live
-    std::vector<Req*> live, scores; // [EXT] scoring: a score request never goes live; its rows are computed by the walk
+    std::vector<Req*> live, scores, builds; // [EXT] scoring: a score request never goes live; its rows are computed by the walk.  Nor does a stem build
     for (Req* r : batch) {
         if (r->r.sampler.temperature > 0.0f) sampled = true;
-        (r->score ? scores : live).push_back(r);
+        (r->build_stem >= 0 ? builds : r->score ? scores : live).push_back(r);
     }
     hipEvent_t e0, e1;
     Q3_HIP(hipEventCreate(&e0)); Q3_HIP(hipEventCreate(&e1));
@@ -1055,6 +1178,7 @@ void Engine::admit(bool stalled) {
         for (Req* r : batch) r->prefill_ms = t - r->t_submit;
     }
     finish_scores(scores);
+    finish_builds(builds);
 }
 
 // [EXT] decoding given frames.  The request is the codec half of a request alone: a copy of the caller's frames that waits for a codec stream.
@@ -1176,8 +1300,10 @@ void Engine::go_live(const std::vector<Req*>& batch) {
 // row of each is copied in and code_0 of its first frame is drawn from the staged logits with the slot's own sampler state (greedy slots
 // take the sampler kernel's first-max branch).
 void Engine::activate() {
-    std::vector<Req*> batch, dropped, scores;
+    std::vector<Req*> batch, dropped, scores, builds;
     batch.swap(pf_batch_);
+    for (Req* r : batch) if (r->build_stem >= 0) builds.push_back(r); // [EXT] prompt stems: a build never goes live and cannot be cancelled
+    batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->build_stem >= 0; }), batch.end());
     {   // [EXT] requests cancelled while the wave ran do not go live; their wave-mates are not disturbed
         std::lock_guard<std::mutex> lk(mu_);
         const double t = now_ms();
@@ -1207,6 +1333,7 @@ void Engine::activate() {
         n_active_ += (int)batch.size();
     }
     finish_scores(scores);
+    finish_builds(builds);
 }
 
 // [EXT] scoring given frames.  Like the log-probability buffers, the state goes to the device on first use, under the same locks.
@@ -1339,7 +1466,7 @@ void Engine::retire(Req* r, bool flush_tail) {
         r->slot = -1;
         r->state = retired_state(r->want_pcm, r->cancel);
         if (r->want_pcm) n_draining_++;
-        else { r->t_done = now_ms(); cv_.notify_all(); }
+        else { r->t_done = now_ms(); stem_drop(r); cv_.notify_all(); } // [EXT] prompt stems: its wave completed before it went live or was dropped
     }
     if (r->want_pcm) {
         {
@@ -1448,6 +1575,7 @@ bool Engine::step() {
         if (n_active_ == 0) Q3_HIP(hipEventSynchronize(pf_done_));
         if (hipEventQuery(pf_done_) == hipSuccess) activate();
     }
+    free_stem_stores(); // [EXT] prompt stems: the stores of stems recycled since the last step
     collect_appends();
     collect_cancels(); // before admit: a slot a cancel frees can be refilled in this step
     admit(n_active_ > 0 && slots_.all_live_stalled());
@@ -1663,6 +1791,132 @@ void Engine::preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_pe
     *bytes_per_snapshot = codec_ ? (int64_t)codec_->snapshot_bytes() : 0;
 }
 
+// [EXT] prompt stems (q3tts_spec.h "prompt stems")
+// The take rule at submit, for one request or the members of one candidate set (they share a prompt).  The stem that applies is read under
+// mu_, the rows are compared outside it (a 300-row stem is 2.4 MB), and the holds are taken under mu_ again -- if the stem is still there.
+void Engine::stem_match(Req* const* rs, int n_reqs, int asked) {
+    int sid, n = 0, state = Q3TTS_STEM_FAILED; std::shared_ptr<const std::vector<float>> rows;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        sid = stem_of_request(asked, eng_stem_);
+        if (sid < 0) return;
+        auto it = stems_.find(sid);
+        if (it != stems_.end()) { n = it->second.n; state = it->second.refs.state; rows = it->second.rows; }
+    }
+    const GenRequest& g = rs[0]->r;
+    bool take = stem_takes(state, n, rows ? rows->data() : nullptr, g.prompt, g.n_prompt, rs[0]->score);
+    if (take) {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = stems_.find(sid);
+        take = it != stems_.end() && it->second.refs.state == Q3TTS_STEM_READY && it->second.store;
+        for (int i = 0; take && i < n_reqs; i++) {
+            it->second.refs.holders++;
+            rs[i]->stem = sid; rs[i]->stem_held = true; rs[i]->n_skip = n; rs[i]->stem_store = it->second.store;
+        }
+    }
+    if (!take) stem_miss_ += n_reqs;
+}
+void Engine::stem_drop(Req* r) {
+    if (!r->stem_held) return;
+    r->stem_held = false;
+    stem_unhold(r->stem);
+}
+void Engine::stem_unhold(int sid) {
+    auto it = stems_.find(sid);
+    if (it == stems_.end()) return;
+    Stem& s = it->second;
+    s.refs.holders--;
+    if (!preamble_recyclable(s.refs)) return;
+    if (s.store) stem_garbage_.emplace_back(s.store, s.bytes); // the scheduler thread frees it: no HIP call in a caller's thread
+    stems_.erase(it);
+    wake_++; cv_.notify_all();
+}
+int Engine::stem_create(const float* rows, int n) {
+    int live = 0;
+    { std::lock_guard<std::mutex> lk(mu_); live = (int)stems_.size(); }
+    if (const char* why = stem_refusal(rows, n, p_.max_prompt, live, talker_->ggml_mode())) throw Error(why);
+    std::unique_ptr<Req> r(new Req());
+    r->stem_rows.reset(new std::vector<float>(rows, rows + (size_t)n * Q3_EMBD));
+    r->r.prompt = r->stem_rows->data(); r->r.n_prompt = n; r->r.max_steps = 0; r->r.sampler.temperature = 0.0f;
+    r->r.trail = r->trail_own.data(); r->r.prefix = r->prefix_own.data();
+    r->t_submit = now_ms();
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK((int)stems_.size() < Q3TTS_MAX_STEMS, "Q3TTS_MAX_STEMS stems are live: release one first");
+    const int sid = next_stem_++;
+    Stem& st = stems_[sid];
+    st.n = n; st.rows = r->stem_rows;
+    r->build_stem = sid;
+    enqueue(std::move(r), pending_);
+    return sid;
+}
+void Engine::stem_poll(int id, int* state, int* n_rows) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = stems_.find(id);
+    Q3_CHECK(it != stems_.end(), "unknown stem id");
+    *state = it->second.refs.state; *n_rows = it->second.n;
+}
+bool Engine::stem_wait(int id, double timeout_ms) {
+    const double t0 = now_ms();
+    for (;;) {
+        {
+            std::unique_lock<std::mutex> lk(mu_);
+            auto it = stems_.find(id);
+            Q3_CHECK(it != stems_.end(), "unknown stem id");
+            if (it->second.refs.state != Q3TTS_STEM_BUILDING) return true;
+            if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
+            if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
+        }
+        step();
+    }
+}
+void Engine::stem_release(int id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = stems_.find(id);
+    Q3_CHECK(it != stems_.end(), "unknown stem id");
+    Q3_CHECK(it->second.refs.creator, "the stem has already been released");
+    it->second.refs.creator = false;
+    it->second.refs.holders++; stem_unhold(id); // recycles when nobody else holds it
+}
+void Engine::set_voice_stem(int voice_id, int stem_id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
+    if (stem_id >= 0) {
+        auto it = stems_.find(stem_id);
+        if (const char* why = stem_set_refusal(it != stems_.end(), it != stems_.end() ? it->second.refs.state : 0)) throw Error(why);
+        it->second.refs.holders++;
+    } else Q3_CHECK(stem_id == -1, "stem id must be -1 (none) or a stem's id");
+    const int old = voices_[(size_t)voice_id].stem;
+    voices_[(size_t)voice_id].stem = stem_id;
+    if (old >= 0) stem_unhold(old);
+}
+int Engine::voice_stem(int voice_id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
+    return voices_[(size_t)voice_id].stem;
+}
+void Engine::set_stem(int stem_id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (stem_id >= 0) {
+        auto it = stems_.find(stem_id);
+        if (const char* why = stem_set_refusal(it != stems_.end(), it != stems_.end() ? it->second.refs.state : 0)) throw Error(why);
+        it->second.refs.holders++;
+    } else Q3_CHECK(stem_id == -1, "stem id must be -1 (none) or a stem's id");
+    const int old = eng_stem_;
+    eng_stem_ = stem_id;
+    if (old >= 0) stem_unhold(old);
+}
+void Engine::request_stem(int64_t id, int* stem_id, int* rows_reused) {
+    std::lock_guard<std::mutex> lk(mu_);
+    const Req& r = req(id);
+    *stem_id = r.stem; *rows_reused = r.n_skip;
+}
+Engine::StemStats Engine::stem_stats() const {
+    StemStats s;
+    s.built = stem_built_.load(); s.restores = stem_restores_.load(); s.rows_skipped = stem_rows_.load(); s.pages_copied = stem_pages_.load();
+    s.mismatches = stem_miss_.load(); s.bytes_held = stem_bytes_.load();
+    return s;
+}
+
 void Engine::fetch_logprobs(int64_t id, float* out, int frame_off, int max_frames, int* got_frames) {
     std::lock_guard<std::mutex> lk(mu_);
     const Req& r = req(id);
@@ -1720,6 +1974,7 @@ void Engine::start_driver() {
             std::lock_guard<std::mutex> lk(mu_);
             for (auto& kv : reqs_) if (kv.second->state != REQ_DONE && kv.second->state != REQ_CANCELLED) { kv.second->state = REQ_FAILED; kv.second->error = ex.what(); }
             for (auto& kv : pres_) if (kv.second.refs.state == Q3TTS_PREAMBLE_BUILDING) kv.second.refs.state = Q3TTS_PREAMBLE_FAILED; // [EXT] nothing builds them any more
+            for (auto& kv : stems_) if (kv.second.refs.state == Q3TTS_STEM_BUILDING) kv.second.refs.state = Q3TTS_STEM_FAILED;
             cv_.notify_all();
         }
     });

@@ -57,6 +57,7 @@ struct ReqStatus {
 struct Voice { // a registered voice: preset embedding or clone material (engine.rs:390-435, voice_file.rs:5-22)
     std::vector<float> spk_emb; std::vector<int32_t> ref_codes, ref_text_ids;
     int preamble = -1; // [EXT] codec preambles: what requests of the text forms with this voice are primed with (mu_)
+    int stem = -1;     // [EXT] prompt stems: what applies to requests of the text forms with this voice (mu_)
 };
 
 
@@ -136,6 +137,21 @@ public:
     void set_preamble(int preamble_id);                     // -1: none
     int request_preamble(int64_t id);
     void preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot) const;
+    // [EXT] prompt stems (q3tts_spec.h "prompt stems"): n prompt rows and their talker K/V at positions 0 .. n-1, built once by an internal wave
+    // member (a slot for one wave, no head) whose pages the save launch copies into the stem's own device store, and restored by one launch
+    // per wave in front of the first chunk.  create: thread-safe, no HIP calls (the scheduler allocates the store); throws stem_refusal's
+    // reason before anything is queued.  The setters take a READY stem only.  submit() / submit_candidates() read the engine-level setting
+    // once per request / set and apply the take rule; a request that took a stem holds a reference from submit to its end
+    int stem_create(const float* rows, int n);
+    void stem_poll(int id, int* state, int* n_rows);
+    bool stem_wait(int id, double timeout_ms); // true once READY or FAILED; drives step() itself when no driver thread is running
+    void stem_release(int id);                 // the creator's reference
+    void set_voice_stem(int voice_id, int stem_id); // -1: none
+    int voice_stem(int voice_id);
+    void set_stem(int stem_id);                     // -1: none
+    void request_stem(int64_t id, int* stem_id, int* rows_reused); // -1 / 0: the request took none
+    struct StemStats { int64_t built = 0, restores = 0, rows_skipped = 0, pages_copied = 0, mismatches = 0, bytes_held = 0; };
+    StemStats stem_stats() const;
     bool step();                                  // one scheduling iteration on the calling thread; false when idle
     ReqStatus poll(int64_t id);                   // thread-safe snapshot
     // copies frames [frame_off, ...) and PCM samples [pcm_off, ...) that are available now; returns counts
@@ -184,6 +200,7 @@ private:
         Transformer* talker = nullptr; hipStream_t st = nullptr; int chunk = 0; bool async = false;
         DevBuf<float> d_rows; DevBuf<int32_t> d_seq, d_slot, d_pos; // one chunk: its input rows, seq / slot / pos [4] per token
         DevBuf<int32_t> d_codes, d_ids, d_fork_dst;                 // [EXT] resume: codes / trailing ids of its feedback rows; candidate sets: a wave's fork destinations
+        DevBuf<StemJob> d_stem_jobs; DevBuf<int32_t> d_stem_slots;  // [EXT] prompt stems: a wave's restore jobs [B] then its save jobs [B], and their slot lists
         unsigned char* arena = nullptr; StageCursor cur;            // pinned staging
     };
     void lane_alloc(PrefillLane& L, Transformer* talker, hipStream_t st, int chunk, bool async, size_t arena_bytes);
@@ -208,6 +225,14 @@ private:
     static void split_sets(const std::vector<Req*>& batch, std::vector<Req*>& lead, std::vector<std::vector<Req*>>& rest);
     void fork_sets(hipStream_t st, const std::vector<Req*>& lead, const std::vector<std::vector<Req*>>& rest, int32_t* h_dst, int32_t* d_dst);
     static int kv_positions(const GenRequest& g, bool score) { return score ? g.n_prompt + g.n_prefix + 1 : g.n_prompt + g.max_steps + 1; }
+    // [EXT] prompt stems: the restores of a wave, one launch on the lane's stream behind the page-table rows and in front of the first chunk;
+    // the saves of its builds, one launch behind the last chunk; the stores of the wave's builds (scheduler thread, capture_mutex()); the end
+    // of the builds (the wave's prefill complete); the stores nobody holds any more (scheduler thread)
+    void restore_stems(PrefillLane& L, const std::vector<Req*>& lead);
+    void save_stems(PrefillLane& L, const std::vector<Req*>& lead);
+    void alloc_stem_stores(const std::vector<Req*>& wave);
+    void finish_builds(const std::vector<Req*>& builds);
+    void free_stem_stores();
     void prefill_async(const std::vector<Req*>& wave); // the asynchronous wave's start: KV pages, events, the walk on pf_, pf_batch_
     void go_live(const std::vector<Req*>& batch);      // slot state of a wave's requests (no score request among them) goes live, on st_
     void activate();                                   // the asynchronous wave's completion
@@ -313,6 +338,15 @@ private:
     void pre_attach(Req* r, int pid);   // r is primed with READY preamble pid and holds it (mu_ held)
     void pre_drop(Req* r);              // r has ended (mu_ held)
     void pre_unhold(int pid);           // one holder less; recycles the snapshot's slot when nobody is left (mu_ held)
+    // [EXT] prompt stems (all under mu_): the live stems by id, the next id (never reused), the engine-level setting, the stores of recycled
+    // stems the scheduler thread has yet to free, the counters
+    struct Stem { PreambleRefs refs; int n = 0; std::shared_ptr<const std::vector<float>> rows; uint16_t* store = nullptr; int64_t bytes = 0; };
+    std::map<int, Stem> stems_; int next_stem_ = 0, eng_stem_ = -1;
+    std::vector<std::pair<uint16_t*, int64_t>> stem_garbage_;
+    std::atomic<int64_t> stem_built_{0}, stem_restores_{0}, stem_rows_{0}, stem_pages_{0}, stem_miss_{0}, stem_bytes_{0};
+    void stem_match(Req* const* rs, int n_reqs, int asked); // the take rule at submit: the requests take the stem and hold it, or run plain (takes mu_ itself)
+    void stem_drop(Req* r);                         // r has ended (mu_ held)
+    void stem_unhold(int sid);                      // one holder less; the store goes to stem_garbage_ when nobody is left (mu_ held)
     bool trail_dirty_ = false;          // an append arrived since the scheduler last looked (mu_)
     std::vector<int64_t> cancel_ids_;   // cancelled requests the scheduler has not dealt with yet (mu_)
     uint64_t wake_ = 0;                 // bumped by every submit / append / cancel: a driver idling on stalled slots sleeps until it changes (mu_)

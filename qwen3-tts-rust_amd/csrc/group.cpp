@@ -15,6 +15,7 @@
 #include "engine.h"
 #include <dlfcn.h>
 #include <atomic>
+#include <functional>
 
 using namespace q3;
 
@@ -495,6 +496,85 @@ int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamb
     q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
     if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
     return q3tts_request_preamble(e, rid_of(req_id), preamble_id);
+}
+// [EXT] prompt stems: built on every engine under one id, as preambles are (create stems through the group only)
+static int group_stem_create(q3tts_group* g, int32_t* stem_id, const std::function<int(q3tts_engine*, int32_t*)>& create) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && stem_id, "null argument");
+    int32_t sid = -1;
+    for (size_t i = 0; i < g->eng.size(); i++) {
+        int32_t id = -1;
+        if (create(g->eng[i], &id) != Q3TTS_OK) {
+            const std::string why = last_error();
+            for (size_t k = 0; k < i; k++) (void)q3tts_stem_release(g->eng[k], sid); // all engines or none
+            throw Error(why);
+        }
+        if (i == 0) sid = id;
+        Q3_CHECK(id == sid, "engines of a group must hand out the same stem ids (create stems through the group only)");
+    }
+    *stem_id = sid;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_group_stem_create(q3tts_group* g, const float* rows, int32_t n_rows, int32_t* stem_id) {
+    return group_stem_create(g, stem_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_stem_create(e, rows, n_rows, id); });
+}
+int q3tts_group_voice_stem_create(q3tts_group* g, int32_t voice_id, int32_t lang_id, const int32_t* instr_ids, int32_t n_instr, int32_t* stem_id) {
+    return group_stem_create(g, stem_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_voice_stem_create(e, voice_id, lang_id, instr_ids, n_instr, id); });
+}
+int q3tts_group_stem_wait(q3tts_group* g, int32_t stem_id, double timeout_ms) { // 0 once every engine's copy is READY or FAILED, 1 on timeout
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    int worst = 0;
+    for (auto* e : g->eng) {
+        const int rc = q3tts_stem_wait(e, stem_id, timeout_ms);
+        if (rc < 0) return rc;
+        worst = std::max(worst, rc);
+    }
+    return worst;
+}
+int q3tts_group_stem_release(q3tts_group* g, int32_t stem_id) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    int rc = Q3TTS_OK;
+    for (auto* e : g->eng) if (q3tts_stem_release(e, stem_id) != Q3TTS_OK) rc = Q3TTS_ERR;
+    return rc;
+}
+static int group_stem_ready(q3tts_group* g, int32_t stem_id) { // a setter takes a stem that is READY on every engine: all engines or none
+    if (stem_id < 0) return Q3TTS_OK;
+    for (auto* e : g->eng) {
+        int32_t st = 0;
+        if (q3tts_stem_poll(e, stem_id, &st, nullptr) != Q3TTS_OK) return Q3TTS_ERR;
+        if (const char* why = stem_set_refusal(true, st)) { set_last_error(why); return Q3TTS_ERR; }
+    }
+    return Q3TTS_OK;
+}
+int q3tts_group_voice_set_stem(q3tts_group* g, int32_t voice_id, int32_t stem_id) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    if (group_stem_ready(g, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
+    for (auto* e : g->eng) if (q3tts_voice_set_stem(e, voice_id, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_set_stem(q3tts_group* g, int32_t stem_id) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    if (group_stem_ready(g, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
+    for (auto* e : g->eng) if (q3tts_engine_set_stem(e, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
+    return Q3TTS_OK;
+}
+int q3tts_group_request_stem(q3tts_group* g, int64_t req_id, int32_t* stem_id, int32_t* rows_reused) {
+    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
+    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return q3tts_request_stem(e, rid_of(req_id), stem_id, rows_reused);
+}
+int q3tts_group_stem_stats(q3tts_group* g, q3tts_stem_stats* out) { // the engines' counters added up
+    if (!g || !out) { set_last_error("null argument"); return Q3TTS_ERR; }
+    q3tts_stem_stats sum = {0, 0, 0, 0, 0, 0};
+    for (auto* e : g->eng) {
+        q3tts_stem_stats s;
+        if (q3tts_engine_stem_stats(e, &s) != Q3TTS_OK) return Q3TTS_ERR;
+        sum.built += s.built; sum.restores += s.restores; sum.rows_not_prefilled += s.rows_not_prefilled; sum.pages_copied += s.pages_copied;
+        sum.mismatches += s.mismatches; sum.device_bytes += s.device_bytes;
+    }
+    *out = sum;
+    return Q3TTS_OK;
 }
 int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) { // [EXT] q3tts_engine_set_speech_rate on every engine
     if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }

@@ -318,6 +318,13 @@ void launch_score_rows(hipStream_t st, const ScoreRowsArgs& a, int F);
 // the device (it must be set); every sequence involved must own those pages, and no two of the physical pages may coincide.
 void launch_kv_fork(hipStream_t st, const KvCache& kv, int src_seq, const int32_t* dst_seqs, int n_dst, int n_pages);
 
+// [EXT] prompt stems (kvstem.hip, q3tts_spec.h "prompt stems"): one launch for a device table of n_jobs jobs.  A job's store holds n_pages
+// contiguous plane pages at k and as many at v.  Restore: store page l goes into logical page l of the sequences slots[first .. first + n_dst).
+// Save: logical page l of sequence slots[first] goes into store page l.  max_pages = the largest n_pages among the jobs.  Physical page ids
+// come from kv.page_table on the device (it must be set); every sequence involved must own logical pages [0, n_pages) of its job.
+struct StemJob { uint16_t* k; uint16_t* v; int32_t n_pages, first, n_dst, pad; };
+void launch_kv_stem(hipStream_t st, const KvCache& kv, const StemJob* jobs, int n_jobs, int max_pages, const int32_t* slots, bool save);
+
 // [EXT] output formats (pcmout.hip, q3tts_spec.h "output formats"): sample-rate conversion and int16 PCM behind the codec.
 // One entry per stream of a launch, written by launch_pcm_convert into the converter's upload ring.
 struct PcmStreamMeta {

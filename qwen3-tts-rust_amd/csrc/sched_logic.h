@@ -1,11 +1,12 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request and of a codec preamble (with who holds one), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble (with who holds one) and of a prompt stem (with its take rule), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -42,6 +43,9 @@ struct GenRequest {
     // [EXT] codec preambles (q3tts_spec.h): -2 the engine-level setting (the raw-prompt forms), -1 none, else that preamble (a text form
     // passes its voice's); resolved by Engine::submit, which never primes a request without PCM
     int preamble = -2;
+    // [EXT] prompt stems (q3tts_spec.h): -2 the engine-level setting (the raw-prompt forms), -1 none, else that stem (a text form passes its
+    // voice's); Engine::submit applies the take rule
+    int stem = -2;
 };
 
 // Which launches one frame step issues: some live slot samples the talker / has a repetition penalty / samples the predictor / has trailing text
@@ -158,7 +162,9 @@ struct StageCursor {
 // per-token seq / slot / pos routing (engine.rs:306-314) -- and returns its token count; lasts = (request, index inside the chunk) of final prompt tokens.
 // [EXT] resume: a request's n_fb feedback rows follow its prompt at positions n .. n + n_fb - 1.  They are not staged: the device writes them
 // (k_feedback_codes), and fb lists each run of them inside the chunk.
-struct PromptRef { const float* rows; int n, slot; int n_fb = 0; }; struct PrefillCursor { size_t req = 0; int tok = 0; };
+// [EXT] prompt stems: a request's first n_skip rows are not prefilled (their K/V is restored from the stem's store); its cursor starts there, and
+// positions and slots stay the row index, so every other row lands where it always did.
+struct PromptRef { const float* rows; int n, slot; int n_fb = 0; int n_skip = 0; }; struct PrefillCursor { size_t req = 0; int tok = 0; };
 struct FbRun { int req, row, frame, n; }; // request index, first row inside the chunk, first frame, number of rows
 inline int pack_prefill_chunk(const std::vector<PromptRef>& batch, PrefillCursor& c, int n_max, float* stage, int32_t* seq, int32_t* slot,
                               int32_t* pos, std::vector<std::pair<int, int>>& lasts, std::vector<FbRun>* fb = nullptr) {
@@ -166,6 +172,7 @@ inline int pack_prefill_chunk(const std::vector<PromptRef>& batch, PrefillCursor
     if (fb) fb->clear();
     for (lasts.clear(); n < n_max && c.req < batch.size(); n++) {
         const PromptRef& r = batch[c.req];
+        if (c.tok < r.n_skip) c.tok = r.n_skip;
         if (c.tok < r.n) std::copy(r.rows + (size_t)c.tok * Q3_EMBD, r.rows + (size_t)(c.tok + 1) * Q3_EMBD, stage + (size_t)n * Q3_EMBD);
         else if (fb) {
             if (!fb->empty() && fb->back().req == (int)c.req && fb->back().row + fb->back().n == n) fb->back().n++;
@@ -272,6 +279,40 @@ inline int preamble_of_request(bool want_pcm, int asked, int engine_level) {
     return asked == PREAMBLE_ENGINE ? engine_level : asked;
 }
 
+// [EXT] prompt stems (q3tts_spec.h "prompt stems").  The states and the holder rule are the preamble's (PreambleRefs / preamble_recyclable): the
+// store goes back when nobody holds the stem and its build has ended; a request that took it holds it from submit to its end, so every
+// restore enqueued from it has completed by then.
+static_assert(Q3TTS_STEM_BUILDING == Q3TTS_PREAMBLE_BUILDING && Q3TTS_STEM_READY == Q3TTS_PREAMBLE_READY && Q3TTS_STEM_FAILED == Q3TTS_PREAMBLE_FAILED,
+              "stems share PreambleRefs: the states must agree");
+// why a stem of n rows is refused, or null.  Pure; live = stems the engine holds now (building ones included)
+inline const char* stem_refusal(const float* rows, int n, int max_prompt, int live, bool ggml) {
+    if (ggml) return "prompt stems are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)";
+    if (!rows) return "stem rows missing";
+    if (n < 1) return "n_rows must be >= 1";
+    if (n >= max_prompt) return "n_rows must be below max_prompt: a request that takes a stem has at least one row of its own";
+    if (live >= Q3TTS_MAX_STEMS) return "Q3TTS_MAX_STEMS stems are live: release one first";
+    return nullptr;
+}
+inline const char* stem_set_refusal(bool known, int state) {
+    if (!known) return "unknown stem id";
+    if (state == Q3TTS_STEM_BUILDING) return "the stem is still building: wait for it (q3tts_stem_wait)";
+    if (state != Q3TTS_STEM_READY) return "the stem failed to build";
+    return nullptr;
+}
+// the stem that applies to a request: a text form passes its voice's, a raw-prompt form takes the engine-level setting
+enum { STEM_NONE = -1, STEM_ENGINE = -2 };
+inline int stem_of_request(int asked, int engine_level) { return asked == STEM_ENGINE ? engine_level : asked; }
+// the take rule, given that a stem of n rows in `state` applies: READY, n_prompt > n, the first n rows bytewise equal; never a score request
+inline bool stem_takes(int state, int n, const float* stem_rows, const float* prompt, int n_prompt, bool score) {
+    if (score || state != Q3TTS_STEM_READY || n < 1 || n_prompt <= n || !stem_rows || !prompt) return false;
+    return std::memcmp(stem_rows, prompt, (size_t)n * Q3_EMBD * sizeof(float)) == 0; // bytes: -0 differs from +0 and a NaN equals itself
+}
+inline int stem_pages(int n) { return (n + 63) / 64; }
+// device bytes of a stem's store: K and V planes of whole pages, f16
+inline int64_t stem_store_bytes(int n, int n_layer, int n_kv) { return (int64_t)2 * stem_pages(n) * n_layer * n_kv * 8192 * 2; }
+// the rows of a request that an admission wave stages and prefills
+inline int admission_rows(int n_prompt, int n_skip, int n_prefix) { return n_prompt - n_skip + n_prefix; }
+
 // Decode-only requests that may hold a codec stream at once: half of the streams the engine keeps beyond one per slot (those serve
 // requests whose slot is already reused while their last chunks drain), and how many of the queued ones a scheduler step admits after
 // the generating wave has taken its streams.
@@ -335,7 +376,7 @@ inline Seating seat_chunks(const std::vector<TaskHead>& live, const std::vector<
 // is the wave's first.  The members of a candidate set are the consecutive entries with its id (those cancelled in the queue have left it):
 // they are taken all or none, need a slot and a codec stream each, and their rows count once, since one member alone is prefilled.
 // Whatever does not fit ends the wave, so nothing overtakes it.  With no set in the queue this is the loop admit() always ran.
-struct QueueEntry { int rows; bool want_pcm; int64_t set; }; // rows: n_prompt + n_prefix
+struct QueueEntry { int rows; bool want_pcm; int64_t set; }; // rows: n_prompt - n_skip + n_prefix ([EXT] prompt stems: admission_rows)
 inline int admission_take(const std::vector<QueueEntry>& q, int free_slots, int free_codec, bool limit_rows, size_t max_rows = 4096) {
     size_t take = 0, rows = 0;
     while (take < q.size() && free_slots > 0) {
@@ -361,6 +402,7 @@ inline std::vector<ScoreRun> score_head_runs(const std::vector<PromptRef>& batch
     PrefillCursor c = before;
     for (int i = 0; i < n_chunk && c.req < batch.size(); i++) {
         const PromptRef& r = batch[c.req];
+        if (c.tok < r.n_skip) c.tok = r.n_skip; // as the packer
         if (score[c.req] && c.tok >= r.n - 1) {
             if (!out.empty() && out.back().req == (int)c.req && out.back().row + out.back().n == i) out.back().n++;
             else out.push_back({(int)c.req, i, c.tok - (r.n - 1), 1});

@@ -105,6 +105,10 @@ SYMBOLS = [
     "q3tts_engine_set_preamble", "q3tts_request_preamble", "q3tts_engine_preamble_stats",
     "q3tts_group_preamble_create", "q3tts_group_preamble_wait", "q3tts_group_preamble_release", "q3tts_group_voice_set_preamble",
     "q3tts_group_set_preamble", "q3tts_group_request_preamble",
+    "q3tts_stem_create", "q3tts_voice_stem_create", "q3tts_stem_poll", "q3tts_stem_wait", "q3tts_stem_release", "q3tts_voice_set_stem",
+    "q3tts_engine_set_stem", "q3tts_request_stem", "q3tts_engine_stem_stats", "q3tts_op_kv_stem",
+    "q3tts_group_stem_create", "q3tts_group_voice_stem_create", "q3tts_group_stem_wait", "q3tts_group_stem_release",
+    "q3tts_group_voice_set_stem", "q3tts_group_set_stem", "q3tts_group_request_stem", "q3tts_group_stem_stats",
     "q3tts_engine_set_speech_rate", "q3tts_request_speech_rate", "q3tts_engine_tsm_stats", "q3tts_group_set_speech_rate",
     "q3tts_group_request_speech_rate", "q3tts_tsm_samples", "q3tts_tsm_windows", "q3tts_op_tsm",
 ]
@@ -113,12 +117,19 @@ class PcmFormat(C.Structure):  # q3tts_pcm_format
     _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32)]
 
 
+class StemStats(C.Structure):  # q3tts_stem_stats
+    _fields_ = [("built", C.c_int64), ("restores", C.c_int64), ("rows_not_prefilled", C.c_int64), ("pages_copied", C.c_int64),
+                ("mismatches", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 PCM_F32, PCM_S16 = 0, 1                                                  # q3tts_pcm_format.encoding
 PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)      # q3tts_spec.h "output formats"
 PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
 TSM_HOP, TSM_WIN, TSM_SEARCH, TSM_LOOK, TSM_HIST, TSM_MIN, TSM_MAX = 480, 960, 240, 1200, 1920, 50, 200   # q3tts_spec.h "speaking rate"
 MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
 PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
+MAX_STEMS = 64                                                           # Q3TTS_MAX_STEMS (q3tts_spec.h "prompt stems")
+STEM_BUILDING, STEM_READY, STEM_FAILED = 0, 1, -1                        # Q3TTS_STEM_*
 LOGPROB_COLS = 17     # Q3TTS_LOGPROB_COLS: code_0, the 15 predictor codes, EOS in code_0's talker row
 LOGPROB_NONE = 1.0    # Q3TTS_LOGPROB_NONE: not computed (a real value is never positive)
 
@@ -277,6 +288,25 @@ def lib():
         L.q3tts_group_voice_set_preamble.argtypes = L.q3tts_voice_set_preamble.argtypes
         L.q3tts_group_set_preamble.argtypes = L.q3tts_engine_set_preamble.argtypes
         L.q3tts_group_request_preamble.argtypes = L.q3tts_request_preamble.argtypes
+        L.q3tts_stem_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.q3tts_voice_stem_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.q3tts_stem_poll.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.q3tts_stem_wait.argtypes = [C.c_void_p, C.c_int32, C.c_double]
+        L.q3tts_stem_release.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_voice_set_stem.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.q3tts_engine_set_stem.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_request_stem.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.q3tts_engine_stem_stats.argtypes = [C.c_void_p, C.POINTER(StemStats)]
+        L.q3tts_group_stem_create.argtypes = L.q3tts_stem_create.argtypes
+        L.q3tts_group_voice_stem_create.argtypes = L.q3tts_voice_stem_create.argtypes
+        L.q3tts_group_stem_wait.argtypes = L.q3tts_stem_wait.argtypes
+        L.q3tts_group_stem_release.argtypes = L.q3tts_stem_release.argtypes
+        L.q3tts_group_voice_set_stem.argtypes = L.q3tts_voice_set_stem.argtypes
+        L.q3tts_group_set_stem.argtypes = L.q3tts_engine_set_stem.argtypes
+        L.q3tts_group_request_stem.argtypes = L.q3tts_request_stem.argtypes
+        L.q3tts_group_stem_stats.argtypes = L.q3tts_engine_stem_stats.argtypes
+        L.q3tts_op_kv_stem.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
         L.q3tts_pcm_out_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
         L.q3tts_pcm_out_filter.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
         L.q3tts_pcm_out_filter.restype = C.c_int64
@@ -453,6 +483,31 @@ def op_kv_fork(k_cache, v_cache, page_table, src_seq, dst_seqs, n_positions):
     return k, v
 
 
+def op_kv_stem(k_cache, v_cache, page_table, store_k, store_v, jobs, save):
+    """[EXT] k_kv_stem over host buffers (q3tts_op_kv_stem): k_cache / v_cache uint16 [n_pages][n_layer][n_kv][8192], page_table int32
+    [n_seq][max_pages], store_k / store_v uint16 [n_store_pages][n_layer][n_kv][8192]; jobs = [(first store page, n_pages, [slots])], all in
+    one launch; save False restores store pages into the slots' pages, True saves the one slot's pages into the store.  Returns
+    (k_cache, v_cache, store_k, store_v) after the launch (the arguments are not changed)"""
+    k = np.array(k_cache, np.uint16, order="C")
+    v = np.array(v_cache, np.uint16, order="C")
+    sk = np.array(store_k, np.uint16, order="C")
+    sv = np.array(store_v, np.uint16, order="C")
+    pt = np.ascontiguousarray(page_table, np.int32)
+    if k.ndim != 4 or k.shape != v.shape or k.shape[3] != 8192 or pt.ndim != 2 or sk.ndim != 4 or sk.shape != sv.shape or sk.shape[1:] != k.shape[1:]:
+        raise Q3Error("op_kv_stem: caches and stores [pages][n_layer][n_kv][8192], page_table [n_seq][max_pages]")
+    page0 = np.array([j[0] for j in jobs], np.int32)
+    npg = np.array([j[1] for j in jobs], np.int32)
+    ndst = np.array([len(j[2]) for j in jobs], np.int32)
+    first = np.array([sum(len(j[2]) for j in jobs[:i]) for i in range(len(jobs))], np.int32)
+    slots = np.array([b for j in jobs for b in j[2]], np.int32)
+    if slots.size == 0:
+        slots = np.zeros(1, np.int32)   # a job without slots is refused for its n_dst, not for the empty list
+    _chk(lib().q3tts_op_kv_stem(_p(k), _p(v), k.shape[0], k.shape[1], k.shape[2], _p(pt), pt.shape[0], pt.shape[1], _p(sk), _p(sv), sk.shape[0],
+                                len(jobs), _p(page0) if len(jobs) else None, _p(npg) if len(jobs) else None, _p(first) if len(jobs) else None,
+                                _p(ndst) if len(jobs) else None, _p(slots), slots.size, 1 if save else 0))
+    return k, v, sk, sv
+
+
 def group_submit_candidates(group, engine_index, prompt, seeds, max_steps=8, temperature=0.0, top_k=40, top_p=0.9, mask_eos=True, want_pcm=False,
                             repetition_penalty=1.0, predictor_temperature=0.0, predictor_top_k=0, predictor_top_p=1.0, trailing_ids=None):
     """[EXT] q3tts_group_submit_candidates on a q3tts_group handle (engine_index -1 = round robin): the group request ids, all on one engine"""
@@ -608,6 +663,71 @@ def group_set_preamble(group, pid):
 def group_request_preamble(group, rid):
     """[EXT] q3tts_group_request_preamble: the preamble a group request was primed with, -1 when none"""
     return _request_preamble(lib().q3tts_group_request_preamble, group, rid)
+
+
+def _stem_create(fn, h, rows):
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, 2048) if rows is not None else None
+    sid = C.c_int32()
+    _chk(fn(h, _p(r) if r is not None and r.size else None, r.shape[0] if r is not None else 0, C.byref(sid)))
+    return sid.value
+
+
+def _voice_stem_create(fn, h, voice_id, lang_id, instr_ids):
+    ins = np.ascontiguousarray(instr_ids, np.int32) if instr_ids is not None else None
+    sid = C.c_int32()
+    _chk(fn(h, voice_id, lang_id, _p(ins), ins.size if ins is not None else 0, C.byref(sid)))
+    return sid.value
+
+
+def _request_stem(fn, h, rid):
+    sid, n = C.c_int32(), C.c_int32()
+    _chk(fn(h, rid, C.byref(sid), C.byref(n)))
+    return sid.value, n.value
+
+
+def _stem_stats(fn, h):
+    s = StemStats()
+    _chk(fn(h, C.byref(s)))
+    return {k: getattr(s, k) for k, _ in StemStats._fields_}
+
+
+def group_stem_create(group, rows):
+    """[EXT] q3tts_group_stem_create on a q3tts_group handle: the stem of rows [n][2048] on every engine, under one id"""
+    return _stem_create(lib().q3tts_group_stem_create, group, rows)
+
+
+def group_voice_stem_create(group, voice_id, lang_id=2055, instr_ids=None):
+    """[EXT] q3tts_group_voice_stem_create: the head the text forms build for this voice, language and instruction, on every engine"""
+    return _voice_stem_create(lib().q3tts_group_voice_stem_create, group, voice_id, lang_id, instr_ids)
+
+
+def group_stem_wait(group, sid, timeout_ms=-1.0):
+    """[EXT] q3tts_group_stem_wait: True once every engine's copy is READY or FAILED"""
+    return _preamble_wait(lib().q3tts_group_stem_wait, group, sid, timeout_ms)
+
+
+def group_stem_release(group, sid):
+    _chk(lib().q3tts_group_stem_release(group, sid))
+
+
+def group_voice_set_stem(group, voice_id, sid):
+    """[EXT] q3tts_group_voice_set_stem (sid None or -1: none)"""
+    _chk(lib().q3tts_group_voice_set_stem(group, voice_id, -1 if sid is None else sid))
+
+
+def group_set_stem(group, sid):
+    """[EXT] q3tts_group_set_stem on every engine (sid None or -1: none)"""
+    _chk(lib().q3tts_group_set_stem(group, -1 if sid is None else sid))
+
+
+def group_request_stem(group, rid):
+    """[EXT] q3tts_group_request_stem: (stem id, rows not prefilled) of a group request; (-1, 0) when it took none"""
+    return _request_stem(lib().q3tts_group_request_stem, group, rid)
+
+
+def group_stem_stats(group):
+    """[EXT] q3tts_group_stem_stats: the engines' counters added up"""
+    return _stem_stats(lib().q3tts_group_stem_stats, group)
 
 
 class Sampler:  # LlamaSampler (llama/mod.rs:627-776)
@@ -815,6 +935,58 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _chk(lib().q3tts_engine_preamble_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(built=a.value, restores=b.value, bytes_per_snapshot=c.value)
+
+    # ---- [EXT] prompt stems (q3tts_spec.h "prompt stems") ----
+    def stem_create(self, rows):
+        """q3tts_stem_create: queues the build of the talker K/V behind rows [n][2048]; returns the stem id (BUILDING)"""
+        return _stem_create(lib().q3tts_stem_create, self.h, rows)
+
+    def voice_stem_create(self, voice_id, lang_id=2055, instr_ids=None):
+        """q3tts_voice_stem_create: the stem of the rows the text forms build in front of the task text for this voice, language and
+        instruction"""
+        return _voice_stem_create(lib().q3tts_voice_stem_create, self.h, voice_id, lang_id, instr_ids)
+
+    def stem_poll(self, sid):
+        """(state, n_rows): STEM_BUILDING / _READY / _FAILED"""
+        st, n = C.c_int32(), C.c_int32()
+        _chk(lib().q3tts_stem_poll(self.h, sid, C.byref(st), C.byref(n)))
+        return st.value, n.value
+
+    def stem_wait(self, sid, timeout_ms=-1.0):
+        """True once the stem is READY or FAILED; drives the scheduler itself when no driver thread runs"""
+        return _preamble_wait(lib().q3tts_stem_wait, self.h, sid, timeout_ms)
+
+    def stem_release(self, sid):
+        """the creator's reference goes; voices, the engine-level setting and the requests that took the stem hold their own"""
+        _chk(lib().q3tts_stem_release(self.h, sid))
+
+    def voice_set_stem(self, voice_id, sid):
+        """the READY stem sid applies to requests of the text forms with this voice (None or -1: none)"""
+        _chk(lib().q3tts_voice_set_stem(self.h, voice_id, -1 if sid is None else sid))
+
+    def set_stem(self, sid):
+        """the READY stem sid applies to requests of the raw-prompt forms (submit, candidates) submitted from now on (None or -1: none)"""
+        _chk(lib().q3tts_engine_set_stem(self.h, -1 if sid is None else sid))
+
+    def request_stem(self, rid):
+        """(stem id, prompt rows not prefilled) of a request; (-1, 0) when it took none"""
+        return _request_stem(lib().q3tts_request_stem, self.h, rid)
+
+    def stem_stats(self):
+        """q3tts_engine_stem_stats: dict(built, restores, rows_not_prefilled, pages_copied, mismatches, device_bytes)"""
+        return _stem_stats(lib().q3tts_engine_stem_stats, self.h)
+
+    def stem_voice(self, voice_id, lang_id=2055, instr_ids=None, timeout_ms=-1.0):
+        """create -> wait -> set for the head of this voice's prompts; the voice then holds the stem (the creator's reference is released).
+        Returns the stem id"""
+        sid = self.voice_stem_create(voice_id, lang_id, instr_ids)
+        try:
+            if not self.stem_wait(sid, timeout_ms) or self.stem_poll(sid)[0] != STEM_READY:
+                raise Q3Error("the stem of voice %d did not become ready" % voice_id)
+            self.voice_set_stem(voice_id, sid)
+        finally:
+            self.stem_release(sid)
+        return sid
 
     def prime_voice(self, voice_id, timeout_ms=-1.0):
         """create -> wait -> set from the clone voice's own reference codes; the voice then holds the preamble (the creator's reference is
