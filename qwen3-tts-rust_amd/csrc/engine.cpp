@@ -267,7 +267,7 @@ Engine::~Engine() {
         if (g.second->exec) (void)hipGraphExecDestroy(g.second->exec);
         if (g.second->graph) (void)hipGraphDestroy(g.second->graph);
     }
-    for (auto& s : stems_) if (s.second.store) (void)hipFree(s.second.store); // [EXT] prompt stems
+    for (auto& s : stems_.entries()) if (s.second.payload.store) (void)hipFree(s.second.payload.store); // [EXT] prompt stems
     for (auto& d : stem_garbage_) (void)hipFree(d.first);
     if (pcm_pinned_) (void)hipHostFree(pcm_pinned_);
     if (pre_tails_) (void)hipHostFree(pre_tails_);
@@ -598,8 +598,7 @@ void Engine::alloc_stem_stores(const std::vector<Req*>& wave) {
         Q3_HIP(hipMalloc((void**)&r->build_store, (size_t)bytes));
         stem_bytes_ += bytes;
         std::lock_guard<std::mutex> lk(mu_);
-        auto it = stems_.find(r->build_stem);
-        if (it != stems_.end()) { it->second.store = r->build_store; it->second.bytes = bytes; }
+        if (auto* s = stems_.find(r->build_stem)) { s->payload.store = r->build_store; s->payload.bytes = bytes; }
         else stem_garbage_.emplace_back(r->build_store, bytes); // cannot happen: a building stem is never recycled
     }
 }
@@ -610,15 +609,9 @@ void Engine::finish_builds(const std::vector<Req*>& builds) {
         kv_t_->release(b);
         std::lock_guard<std::mutex> lk(mu_);
         slot_req_[b] = nullptr; r->slot = -1;
-        const int sid = r->build_stem;
-        auto it = stems_.find(sid);
-        if (it != stems_.end()) {
-            it->second.refs.state = Q3TTS_STEM_READY; stem_built_++;
-            it->second.refs.holders++; stem_unhold(sid); // recycles at once when it was released while it built
-        }
-        if (r->ev_admit) (void)hipEventDestroy(r->ev_admit);
-        reqs_.erase(r->id); // the build request is nobody's to release
-        cv_.notify_all();
+        if (stems_.find(r->build_stem)) stem_built_++;
+        recycled(stems_.finish(r->build_stem, true)); // recycles at once when it was released while it built
+        end_build(r);
     }
 }
 // Scheduler thread: the stores of stems nobody holds any more.  hipFree waits for the device, so every restore has long completed.
@@ -824,24 +817,18 @@ void Engine::harvest(bool block) {
             r->state = fenced_state(r->cancel); r->t_done = now_ms();
             n_draining_--;
             if (r->decode) n_decoding_--;
-            pre_drop(r); // [EXT] codec preambles: the restore this request enqueued has completed
-            stem_drop(r); // [EXT] prompt stems: so has its wave's
+            drop_held(r); // [EXT] codec preambles, prompt stems: the restores this request and its wave enqueued have completed
             if (r->build_pre >= 0) { // the preamble is built: its snapshot is on the device, its last native samples become its tail
-                auto it = pres_.find(r->build_pre);
-                if (it != pres_.end()) {
-                    Preamble& p = it->second;
+                bool ok = false;
+                if (auto* e = pres_.find(r->build_pre)) {
+                    PreHeld& p = e->payload;
                     p.snap = r->build_snap;
-                    if (p.snap >= 0 && r->pcm.size() >= (size_t)Q3_PCM_HIST) {
-                        std::copy(r->pcm.end() - Q3_PCM_HIST, r->pcm.end(), pre_tails_ + (size_t)p.tail * Q3_PCM_HIST);
-                        p.refs.state = Q3TTS_PREAMBLE_READY; pre_built_++;
-                    } else p.refs.state = Q3TTS_PREAMBLE_FAILED;
-                    const int pid = it->first;
-                    p.refs.holders++; pre_unhold(pid); // recycles at once when it was released while it built
+                    ok = p.snap >= 0 && r->pcm.size() >= (size_t)Q3_PCM_HIST;
+                    if (ok) { std::copy(r->pcm.end() - Q3_PCM_HIST, r->pcm.end(), pre_tails_ + (size_t)p.tail * Q3_PCM_HIST); pre_built_++; }
                 }
-                if (r->ev_admit) (void)hipEventDestroy(r->ev_admit);
-                reqs_.erase(r->id); // the build request is nobody's to release
-            }
-            cv_.notify_all();
+                recycled(pres_.finish(r->build_pre, ok)); // recycles at once when it was released while it built
+                end_build(r);
+            } else cv_.notify_all();
         }
         block = false; // after one blocking wait, drain whatever else is ready
     }
@@ -954,8 +941,8 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     if (may_record) { Req* one = r.get(); stem_match(&one, 1, g.stem); } // [EXT] prompt stems: the take rule, once per request; never a blocking batch
     std::lock_guard<std::mutex> lk(mu_);
     // [EXT] codec preambles: the engine-level setting or the caller's (a voice's), read once per request; a blocking batch is never primed
-    const int pid = preamble_of_request(r->want_pcm && may_record, g.preamble, eng_pre_);
-    if (pid >= 0) { try { pre_attach(r.get(), pid); } catch (...) { stem_drop(r.get()); throw; } } // throws before anything is queued
+    const int pid = preamble_of_request(r->want_pcm && may_record, g.preamble, pres_.setting);
+    if (pid >= 0) { try { pre_attach(r.get(), pid); } catch (...) { drop_held(r.get()); throw; } } // throws before anything is queued
     return enqueue(std::move(r), pending_);
 }
 
@@ -994,9 +981,9 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
     }
     std::lock_guard<std::mutex> lk(mu_);
     {   // [EXT] codec preambles: the engine-level setting, read once per set; every member restores the same snapshot into its own stream
-        const int pid = preamble_of_request(want_pcm && codec_, g.preamble, eng_pre_);
+        const int pid = preamble_of_request(want_pcm && codec_, g.preamble, pres_.setting);
         try { for (int i = 0; pid >= 0 && i < n; i++) pre_attach(rs[i].get(), pid); }
-        catch (...) { for (auto& r : rs) { pre_drop(r.get()); stem_drop(r.get()); } throw; }
+        catch (...) { for (auto& r : rs) drop_held(r.get()); throw; }
     }
     const int64_t set = next_set_++;
     for (int i = 0; i < n; i++) { rs[i]->set = set; req_ids[i] = enqueue(std::move(rs[i]), pending_); }
@@ -1064,8 +1051,7 @@ int Engine::cancel(int64_t id) {
         std::deque<Req*>& q = r.decode ? decode_q_ : pending_;
         q.erase(std::find(q.begin(), q.end(), &r));
         r.state = REQ_CANCELLED; r.t_done = now_ms();
-        pre_drop(&r); // [EXT] codec preambles: it never enqueued a restore
-        stem_drop(&r); // [EXT] prompt stems: nor one of these
+        drop_held(&r); // [EXT] codec preambles, prompt stems: it never enqueued a restore
     } else cancel_ids_.push_back(id);
     wake_++;
     cv_.notify_all();
@@ -1192,7 +1178,7 @@ int64_t Engine::submit_decode(const int32_t* codes, int n) {
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
     r->t_submit = now_ms();
     std::lock_guard<std::mutex> lk(mu_);
-    if (eng_pre_ >= 0) pre_attach(r.get(), eng_pre_); // [EXT] codec preambles: the engine-level setting, read once per request
+    if (pres_.setting >= 0) pre_attach(r.get(), pres_.setting); // [EXT] codec preambles: the engine-level setting, read once per request
     dec_reqs_++;
     return enqueue(std::move(r), decode_q_);
 }
@@ -1466,7 +1452,7 @@ void Engine::retire(Req* r, bool flush_tail) {
         r->slot = -1;
         r->state = retired_state(r->want_pcm, r->cancel);
         if (r->want_pcm) n_draining_++;
-        else { r->t_done = now_ms(); stem_drop(r); cv_.notify_all(); } // [EXT] prompt stems: its wave completed before it went live or was dropped
+        else { r->t_done = now_ms(); drop_held(r); cv_.notify_all(); } // [EXT] prompt stems: its wave completed before it went live or was dropped (without PCM it holds no preamble)
     }
     if (r->want_pcm) {
         {
@@ -1685,102 +1671,93 @@ void Engine::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) c
     if (codec_) codec_->tsm_stats(chunks, frames_out, flushes);
 }
 
-// [EXT] codec preambles (q3tts_spec.h "codec preambles")
-void Engine::pre_attach(Req* r, int pid) {
-    auto it = pres_.find(pid);
-    Q3_CHECK(it != pres_.end() && it->second.refs.state == Q3TTS_PREAMBLE_READY, "the request's preamble is not ready");
-    Preamble& p = it->second;
-    p.refs.holders++;
-    r->pre = pid; r->pre_held = true; r->pre_snap = p.snap; r->pre_tail = pre_tails_ + (size_t)p.tail * Q3_PCM_HIST;
+// [EXT] codec preambles and prompt stems (q3tts_spec.h "codec preambles" / "prompt stems"): the held objects.  Who holds what is counted by
+// pres_ / stems_ (HeldTable, sched_logic.h); here is what the two kinds differ in, and the calls they share, once.
+void Engine::recycled(const std::optional<PreHeld>& p) { // host bookkeeping only: every restore enqueued from the snapshot has completed
+    if (!p) return;
+    if (p->snap >= 0) codec_->snapshot_free(p->snap);
+    pre_tail_free_.push_back(p->tail);
 }
-void Engine::pre_drop(Req* r) {
-    if (!r->pre_held) return;
-    r->pre_held = false;
-    pre_unhold(r->pre);
+void Engine::recycled(const std::optional<StemHeld>& s) { // the scheduler thread frees the store: no HIP call in a caller's thread
+    if (!s) return;
+    if (s->store) stem_garbage_.emplace_back(s->store, s->bytes);
+    wake_++; cv_.notify_all();
 }
-void Engine::pre_unhold(int pid) {
-    auto it = pres_.find(pid);
-    if (it == pres_.end()) return;
-    Preamble& p = it->second;
-    p.refs.holders--;
-    if (!preamble_recyclable(p.refs)) return;
-    if (p.snap >= 0) codec_->snapshot_free(p.snap); // host bookkeeping only: every restore enqueued from it has completed
-    pre_tail_free_.push_back(p.tail);
-    pres_.erase(it);
+void Engine::drop_held(Req* r) {
+    if (r->pre_held) { r->pre_held = false; recycled(pres_.unhold(r->pre)); }
+    if (r->stem_held) { r->stem_held = false; recycled(stems_.unhold(r->stem)); }
 }
-int Engine::preamble_create(const int32_t* codes, int n) {
-    std::unique_ptr<Req> r(new Req());
-    int live = 0;
-    { std::lock_guard<std::mutex> lk(mu_); live = (int)pres_.size(); }
-    if (const char* why = preamble_refusal(codes, n, p_.max_steps, codec_ != nullptr, live, Q3TTS_CODEC_MAX_FRAMES)) throw Error(why);
-    r->decode = true; r->want_pcm = true; // native format: the tail is taken from the staging region's floats
-    r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
-    r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
-    r->t_submit = now_ms();
+void Engine::end_build(Req* r) {
+    if (r->ev_admit) (void)hipEventDestroy(r->ev_admit);
+    reqs_.erase(r->id);
+    cv_.notify_all();
+}
+template <class T> void Engine::held_poll(T& tab, int id, int* state, int* n) {
     std::lock_guard<std::mutex> lk(mu_);
-    Q3_CHECK((int)pres_.size() < Q3TTS_MAX_PREAMBLES && !pre_tail_free_.empty(), "Q3TTS_MAX_PREAMBLES preambles are live: release one first");
-    const int pid = next_pre_++;
-    Preamble& p = pres_[pid];
-    p.n = n; p.tail = pre_tail_free_.back(); pre_tail_free_.pop_back();
-    r->build_pre = pid;
-    enqueue(std::move(r), decode_q_);
-    return pid;
+    const auto& e = tab.at(id);
+    *state = e.refs.state; *n = e.n;
 }
-void Engine::preamble_poll(int id, int* state, int* n_frames) {
-    std::lock_guard<std::mutex> lk(mu_);
-    auto it = pres_.find(id);
-    Q3_CHECK(it != pres_.end(), "unknown preamble id");
-    *state = it->second.refs.state; *n_frames = it->second.n;
-}
-bool Engine::preamble_wait(int id, double timeout_ms) {
+template <class T> bool Engine::held_wait(T& tab, int id, double timeout_ms) {
     const double t0 = now_ms();
     for (;;) {
         {
             std::unique_lock<std::mutex> lk(mu_);
-            auto it = pres_.find(id);
-            Q3_CHECK(it != pres_.end(), "unknown preamble id");
-            if (it->second.refs.state != Q3TTS_PREAMBLE_BUILDING) return true;
+            if (tab.at(id).refs.state != HELD_BUILDING) return true;
             if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
             if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
         }
         step();
     }
 }
-void Engine::preamble_release(int id) {
+template <class T> void Engine::held_release(T& tab, int id) {
     std::lock_guard<std::mutex> lk(mu_);
-    auto it = pres_.find(id);
-    Q3_CHECK(it != pres_.end(), "unknown preamble id");
-    Q3_CHECK(it->second.refs.creator, "the preamble has already been released");
-    it->second.refs.creator = false;
-    it->second.refs.holders++; pre_unhold(id); // recycles when nobody else holds it
+    recycled(tab.release_creator(id));
 }
-void Engine::set_voice_preamble(int voice_id, int preamble_id) {
+template <class T> void Engine::held_set(T& tab, int Voice::*field, int voice_id, int id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Q3_CHECK(!field || (voice_id >= 0 && voice_id < (int)voices_.size()), "unknown voice id");
+    recycled(tab.swap_setting(field ? voices_[(size_t)voice_id].*field : tab.setting, id));
+}
+int Engine::voice_setting(int Voice::*field, int voice_id) {
     std::lock_guard<std::mutex> lk(mu_);
     Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
-    if (preamble_id >= 0) {
-        auto it = pres_.find(preamble_id);
-        if (const char* why = preamble_set_refusal(it != pres_.end(), it != pres_.end() ? it->second.refs.state : 0)) throw Error(why);
-        it->second.refs.holders++;
-    } else Q3_CHECK(preamble_id == -1, "preamble id must be -1 (none) or a preamble's id");
-    const int old = voices_[(size_t)voice_id].preamble;
-    voices_[(size_t)voice_id].preamble = preamble_id;
-    if (old >= 0) pre_unhold(old);
+    return voices_[(size_t)voice_id].*field;
 }
-int Engine::voice_preamble(int voice_id) {
-    std::lock_guard<std::mutex> lk(mu_);
-    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
-    return voices_[(size_t)voice_id].preamble;
+void Engine::preamble_poll(int id, int* state, int* n_frames) { held_poll(pres_, id, state, n_frames); }
+void Engine::stem_poll(int id, int* state, int* n_rows) { held_poll(stems_, id, state, n_rows); }
+bool Engine::preamble_wait(int id, double timeout_ms) { return held_wait(pres_, id, timeout_ms); }
+bool Engine::stem_wait(int id, double timeout_ms) { return held_wait(stems_, id, timeout_ms); }
+void Engine::preamble_release(int id) { held_release(pres_, id); }
+void Engine::stem_release(int id) { held_release(stems_, id); }
+void Engine::set_voice_preamble(int voice_id, int preamble_id) { held_set(pres_, &Voice::preamble, voice_id, preamble_id); }
+void Engine::set_voice_stem(int voice_id, int stem_id) { held_set(stems_, &Voice::stem, voice_id, stem_id); }
+void Engine::set_preamble(int preamble_id) { held_set(pres_, nullptr, 0, preamble_id); }
+void Engine::set_stem(int stem_id) { held_set(stems_, nullptr, 0, stem_id); }
+int Engine::voice_preamble(int voice_id) { return voice_setting(&Voice::preamble, voice_id); }
+int Engine::voice_stem(int voice_id) { return voice_setting(&Voice::stem, voice_id); }
+
+void Engine::pre_attach(Req* r, int pid) {
+    auto* p = pres_.find(pid);
+    Q3_CHECK(p && p->refs.state == Q3TTS_PREAMBLE_READY, "the request's preamble is not ready");
+    pres_.hold(pid);
+    r->pre = pid; r->pre_held = true; r->pre_snap = p->payload.snap; r->pre_tail = pre_tails_ + (size_t)p->payload.tail * Q3_PCM_HIST;
 }
-void Engine::set_preamble(int preamble_id) {
+int Engine::preamble_create(const int32_t* codes, int n) {
+    std::unique_ptr<Req> r(new Req());
+    int live = 0;
+    { std::lock_guard<std::mutex> lk(mu_); live = pres_.live(); }
+    if (const char* why = preamble_refusal(codes, n, p_.max_steps, codec_ != nullptr, live, Q3TTS_CODEC_MAX_FRAMES)) throw Error(why);
+    r->decode = true; r->want_pcm = true; // native format: the tail is taken from the staging region's floats
+    r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
+    r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
+    r->t_submit = now_ms();
     std::lock_guard<std::mutex> lk(mu_);
-    if (preamble_id >= 0) {
-        auto it = pres_.find(preamble_id);
-        if (const char* why = preamble_set_refusal(it != pres_.end(), it != pres_.end() ? it->second.refs.state : 0)) throw Error(why);
-        it->second.refs.holders++;
-    } else Q3_CHECK(preamble_id == -1, "preamble id must be -1 (none) or a preamble's id");
-    const int old = eng_pre_;
-    eng_pre_ = preamble_id;
-    if (old >= 0) pre_unhold(old);
+    Q3_CHECK(pres_.live() < Q3TTS_MAX_PREAMBLES && !pre_tail_free_.empty(), "Q3TTS_MAX_PREAMBLES preambles are live: release one first");
+    const int pid = pres_.add(n);
+    pres_.at(pid).payload.tail = pre_tail_free_.back(); pre_tail_free_.pop_back();
+    r->build_pre = pid;
+    enqueue(std::move(r), decode_q_);
+    return pid;
 }
 int Engine::request_preamble(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
@@ -1791,49 +1768,32 @@ void Engine::preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_pe
     *bytes_per_snapshot = codec_ ? (int64_t)codec_->snapshot_bytes() : 0;
 }
 
-// [EXT] prompt stems (q3tts_spec.h "prompt stems")
 // The take rule at submit, for one request or the members of one candidate set (they share a prompt).  The stem that applies is read under
 // mu_, the rows are compared outside it (a 300-row stem is 2.4 MB), and the holds are taken under mu_ again -- if the stem is still there.
 void Engine::stem_match(Req* const* rs, int n_reqs, int asked) {
     int sid, n = 0, state = Q3TTS_STEM_FAILED; std::shared_ptr<const std::vector<float>> rows;
     {
         std::lock_guard<std::mutex> lk(mu_);
-        sid = stem_of_request(asked, eng_stem_);
+        sid = stem_of_request(asked, stems_.setting);
         if (sid < 0) return;
-        auto it = stems_.find(sid);
-        if (it != stems_.end()) { n = it->second.n; state = it->second.refs.state; rows = it->second.rows; }
+        if (auto* s = stems_.find(sid)) { n = s->n; state = s->refs.state; rows = s->payload.rows; }
     }
     const GenRequest& g = rs[0]->r;
     bool take = stem_takes(state, n, rows ? rows->data() : nullptr, g.prompt, g.n_prompt, rs[0]->score);
     if (take) {
         std::lock_guard<std::mutex> lk(mu_);
-        auto it = stems_.find(sid);
-        take = it != stems_.end() && it->second.refs.state == Q3TTS_STEM_READY && it->second.store;
+        auto* s = stems_.find(sid);
+        take = s && s->refs.state == Q3TTS_STEM_READY && s->payload.store;
         for (int i = 0; take && i < n_reqs; i++) {
-            it->second.refs.holders++;
-            rs[i]->stem = sid; rs[i]->stem_held = true; rs[i]->n_skip = n; rs[i]->stem_store = it->second.store;
+            stems_.hold(sid);
+            rs[i]->stem = sid; rs[i]->stem_held = true; rs[i]->n_skip = n; rs[i]->stem_store = s->payload.store;
         }
     }
     if (!take) stem_miss_ += n_reqs;
 }
-void Engine::stem_drop(Req* r) {
-    if (!r->stem_held) return;
-    r->stem_held = false;
-    stem_unhold(r->stem);
-}
-void Engine::stem_unhold(int sid) {
-    auto it = stems_.find(sid);
-    if (it == stems_.end()) return;
-    Stem& s = it->second;
-    s.refs.holders--;
-    if (!preamble_recyclable(s.refs)) return;
-    if (s.store) stem_garbage_.emplace_back(s.store, s.bytes); // the scheduler thread frees it: no HIP call in a caller's thread
-    stems_.erase(it);
-    wake_++; cv_.notify_all();
-}
 int Engine::stem_create(const float* rows, int n) {
     int live = 0;
-    { std::lock_guard<std::mutex> lk(mu_); live = (int)stems_.size(); }
+    { std::lock_guard<std::mutex> lk(mu_); live = stems_.live(); }
     if (const char* why = stem_refusal(rows, n, p_.max_prompt, live, talker_->ggml_mode())) throw Error(why);
     std::unique_ptr<Req> r(new Req());
     r->stem_rows.reset(new std::vector<float>(rows, rows + (size_t)n * Q3_EMBD));
@@ -1841,69 +1801,12 @@ int Engine::stem_create(const float* rows, int n) {
     r->r.trail = r->trail_own.data(); r->r.prefix = r->prefix_own.data();
     r->t_submit = now_ms();
     std::lock_guard<std::mutex> lk(mu_);
-    Q3_CHECK((int)stems_.size() < Q3TTS_MAX_STEMS, "Q3TTS_MAX_STEMS stems are live: release one first");
-    const int sid = next_stem_++;
-    Stem& st = stems_[sid];
-    st.n = n; st.rows = r->stem_rows;
+    Q3_CHECK(stems_.live() < Q3TTS_MAX_STEMS, "Q3TTS_MAX_STEMS stems are live: release one first");
+    const int sid = stems_.add(n);
+    stems_.at(sid).payload.rows = r->stem_rows;
     r->build_stem = sid;
     enqueue(std::move(r), pending_);
     return sid;
-}
-void Engine::stem_poll(int id, int* state, int* n_rows) {
-    std::lock_guard<std::mutex> lk(mu_);
-    auto it = stems_.find(id);
-    Q3_CHECK(it != stems_.end(), "unknown stem id");
-    *state = it->second.refs.state; *n_rows = it->second.n;
-}
-bool Engine::stem_wait(int id, double timeout_ms) {
-    const double t0 = now_ms();
-    for (;;) {
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            auto it = stems_.find(id);
-            Q3_CHECK(it != stems_.end(), "unknown stem id");
-            if (it->second.refs.state != Q3TTS_STEM_BUILDING) return true;
-            if (timeout_ms >= 0 && now_ms() - t0 > timeout_ms) return false;
-            if (driver_on_) { cv_.wait_for(lk, std::chrono::milliseconds(5)); continue; }
-        }
-        step();
-    }
-}
-void Engine::stem_release(int id) {
-    std::lock_guard<std::mutex> lk(mu_);
-    auto it = stems_.find(id);
-    Q3_CHECK(it != stems_.end(), "unknown stem id");
-    Q3_CHECK(it->second.refs.creator, "the stem has already been released");
-    it->second.refs.creator = false;
-    it->second.refs.holders++; stem_unhold(id); // recycles when nobody else holds it
-}
-void Engine::set_voice_stem(int voice_id, int stem_id) {
-    std::lock_guard<std::mutex> lk(mu_);
-    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
-    if (stem_id >= 0) {
-        auto it = stems_.find(stem_id);
-        if (const char* why = stem_set_refusal(it != stems_.end(), it != stems_.end() ? it->second.refs.state : 0)) throw Error(why);
-        it->second.refs.holders++;
-    } else Q3_CHECK(stem_id == -1, "stem id must be -1 (none) or a stem's id");
-    const int old = voices_[(size_t)voice_id].stem;
-    voices_[(size_t)voice_id].stem = stem_id;
-    if (old >= 0) stem_unhold(old);
-}
-int Engine::voice_stem(int voice_id) {
-    std::lock_guard<std::mutex> lk(mu_);
-    Q3_CHECK(voice_id >= 0 && voice_id < (int)voices_.size(), "unknown voice id");
-    return voices_[(size_t)voice_id].stem;
-}
-void Engine::set_stem(int stem_id) {
-    std::lock_guard<std::mutex> lk(mu_);
-    if (stem_id >= 0) {
-        auto it = stems_.find(stem_id);
-        if (const char* why = stem_set_refusal(it != stems_.end(), it != stems_.end() ? it->second.refs.state : 0)) throw Error(why);
-        it->second.refs.holders++;
-    } else Q3_CHECK(stem_id == -1, "stem id must be -1 (none) or a stem's id");
-    const int old = eng_stem_;
-    eng_stem_ = stem_id;
-    if (old >= 0) stem_unhold(old);
 }
 void Engine::request_stem(int64_t id, int* stem_id, int* rows_reused) {
     std::lock_guard<std::mutex> lk(mu_);
@@ -1973,8 +1876,7 @@ void Engine::start_driver() {
         } catch (const std::exception& ex) {
             std::lock_guard<std::mutex> lk(mu_);
             for (auto& kv : reqs_) if (kv.second->state != REQ_DONE && kv.second->state != REQ_CANCELLED) { kv.second->state = REQ_FAILED; kv.second->error = ex.what(); }
-            for (auto& kv : pres_) if (kv.second.refs.state == Q3TTS_PREAMBLE_BUILDING) kv.second.refs.state = Q3TTS_PREAMBLE_FAILED; // [EXT] nothing builds them any more
-            for (auto& kv : stems_) if (kv.second.refs.state == Q3TTS_STEM_BUILDING) kv.second.refs.state = Q3TTS_STEM_FAILED;
+            pres_.fail_building(); stems_.fail_building(); // [EXT] nothing builds them any more
             cv_.notify_all();
         }
     });

@@ -125,7 +125,7 @@ public:
     // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
     // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
     // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The
-    // setters take a READY preamble only (preamble_set_refusal).  submit() / submit_candidates() / submit_decode() read the engine-level
+    // setters take a READY preamble only (HeldTable::set_refusal).  submit() / submit_candidates() / submit_decode() read the engine-level
     // setting once per request / set; a request with PCM holds a reference from submit to its end, and the `reset` task of a primed request
     // restores the snapshot (and, when it converts, uploads the preamble's last Q3_PCM_HIST samples) where it zeroed the stream
     int preamble_create(const int32_t* codes, int n);
@@ -329,24 +329,32 @@ private:
     std::deque<Req*> decode_q_; int n_decoding_ = 0, decode_w_ = 0;
     std::vector<Req*> dec_admitted_;    // admitted in this step, tasks not yet enqueued (scheduler thread only)
     std::atomic<int64_t> dec_reqs_{0}, dec_chunks_{0}, dec_shared_{0};
-    // [EXT] codec preambles (all under mu_): the live preambles by id, the next id (never reused), the engine-level setting, the pinned
-    // tails ([Q3TTS_MAX_PREAMBLES][Q3_PCM_HIST] floats, allocated with the codec's staging) and their free entries, the counters
-    struct Preamble { PreambleRefs refs; int n = 0, snap = -1, tail = -1; };
-    std::map<int, Preamble> pres_; int next_pre_ = 0, eng_pre_ = -1;
+    // [EXT] codec preambles and prompt stems (all under mu_) live in one HeldTable each (sched_logic.h): the live objects by id, the next id,
+    // the engine-level setting and every count of who holds what are the table's.  The engine keeps what the two kinds differ in: what an
+    // object owns (its payload) and how a recycled payload is disposed of (recycled()).
+    //   preamble  its snapshot and its pinned tail ([Q3TTS_MAX_PREAMBLES][Q3_PCM_HIST] floats, allocated with the codec's staging; free entries
+    //             in pre_tail_free_); both go back in place, which is host bookkeeping only
+    //   stem      its rows, its device store and the store's bytes; the store goes to stem_garbage_ for the scheduler thread to free (no HIP
+    //             call in a caller's thread), which is woken
+    struct PreHeld { int snap = -1, tail = -1; };
+    struct StemHeld { std::shared_ptr<const std::vector<float>> rows; uint16_t* store = nullptr; int64_t bytes = 0; };
+    HeldTable<PreHeld> pres_{"preamble"}; HeldTable<StemHeld> stems_{"stem"};
     float* pre_tails_ = nullptr; std::vector<int> pre_tail_free_;
-    std::atomic<int64_t> pre_built_{0}, pre_restores_{0};
-    void pre_attach(Req* r, int pid);   // r is primed with READY preamble pid and holds it (mu_ held)
-    void pre_drop(Req* r);              // r has ended (mu_ held)
-    void pre_unhold(int pid);           // one holder less; recycles the snapshot's slot when nobody is left (mu_ held)
-    // [EXT] prompt stems (all under mu_): the live stems by id, the next id (never reused), the engine-level setting, the stores of recycled
-    // stems the scheduler thread has yet to free, the counters
-    struct Stem { PreambleRefs refs; int n = 0; std::shared_ptr<const std::vector<float>> rows; uint16_t* store = nullptr; int64_t bytes = 0; };
-    std::map<int, Stem> stems_; int next_stem_ = 0, eng_stem_ = -1;
     std::vector<std::pair<uint16_t*, int64_t>> stem_garbage_;
+    std::atomic<int64_t> pre_built_{0}, pre_restores_{0};
     std::atomic<int64_t> stem_built_{0}, stem_restores_{0}, stem_rows_{0}, stem_pages_{0}, stem_miss_{0}, stem_bytes_{0};
+    void recycled(const std::optional<PreHeld>& p);  // nothing when the table handed nothing back (mu_ held, as everything below)
+    void recycled(const std::optional<StemHeld>& s);
+    void pre_attach(Req* r, int pid);   // r is primed with READY preamble pid and holds it
     void stem_match(Req* const* rs, int n_reqs, int asked); // the take rule at submit: the requests take the stem and hold it, or run plain (takes mu_ itself)
-    void stem_drop(Req* r);                         // r has ended (mu_ held)
-    void stem_unhold(int sid);                      // one holder less; the store goes to stem_garbage_ when nobody is left (mu_ held)
+    void drop_held(Req* r);             // r has ended, or never ran: the preamble and the stem it holds
+    void end_build(Req* r);             // the hidden request of a finished build is nobody's to release
+    // what the public twins above are one call of each (they take mu_ themselves); field: &Voice::preamble / &Voice::stem, null = the engine level
+    template <class T> void held_poll(T& tab, int id, int* state, int* n);
+    template <class T> bool held_wait(T& tab, int id, double timeout_ms);
+    template <class T> void held_release(T& tab, int id);
+    template <class T> void held_set(T& tab, int Voice::*field, int voice_id, int id);
+    int voice_setting(int Voice::*field, int voice_id);
     bool trail_dirty_ = false;          // an append arrived since the scheduler last looked (mu_)
     std::vector<int64_t> cancel_ids_;   // cancelled requests the scheduler has not dealt with yet (mu_)
     uint64_t wake_ = 0;                 // bumped by every submit / append / cancel: a driver idling on stalled slots sleeps until it changes (mu_)

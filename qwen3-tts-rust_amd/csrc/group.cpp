@@ -15,7 +15,6 @@
 #include "engine.h"
 #include <dlfcn.h>
 #include <atomic>
-#include <functional>
 
 using namespace q3;
 
@@ -264,18 +263,91 @@ int q3tts_group_voice_register(q3tts_group* g, const float* spk, const int32_t* 
     Q3_API_END(Q3TTS_ERR)
 }
 
-static int pick_engine(q3tts_group* g) { return (int)(g->rr.fetch_add(1) % g->eng.size()); } // request i -> device i % n
+// ---- the forwarders: every function from here to q3tts_group_stop is one of four shapes, each written once ----
+} // extern "C"
+namespace {
+// 1. by request id: fn(the engine the id names, the engine's own id, a...)
+template <class F, class... A> int routed(q3tts_group* g, int64_t id, F fn, A... a) {
+    if (!g || eng_of(id) >= (int)g->eng.size()) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
+    return fn(g->eng[eng_of(id)], rid_of(id), a...);
+}
+// 2. a submission on one engine: engine_index, or the next in turn (kNext; SURVEY 8e: request i -> device i % n).  call(engine) leaves n engine
+// ids in ids, which come back tagged with the engine's index; a refused submission still takes its turn
+constexpr int32_t kNext = -1;
+template <class F> int submit_on(q3tts_group* g, bool have_args, int32_t engine_index, int64_t* ids, int n, F call) {
+    Q3_API_BEGIN
+    Q3_CHECK(have_args, "null argument");
+    Q3_CHECK(engine_index >= kNext && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
+    const int i = engine_index >= 0 ? engine_index : (int)(g->rr.fetch_add(1) % g->eng.size());
+    if (call(g->eng[i]) != Q3TTS_OK) return Q3TTS_ERR;
+    for (int k = 0; k < n; k++) ids[k] = (ids[k] << kEngineBits) | i;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+// 3. on every engine.  ALL_OR_STOP: the first failure ends the walk (the engines are alike: what one refuses the others would); EVERY: each
+// engine is called whatever the others said, and one failure makes the answer (a release, a stop).  null_msg = null: a null group fails silently
+enum Walk { ALL_OR_STOP, EVERY };
+template <class F> int on_every(q3tts_group* g, Walk walk, F call, const char* null_msg = "null argument") {
+    if (!g) { if (null_msg) set_last_error(null_msg); return Q3TTS_ERR; }
+    int rc = Q3TTS_OK;
+    for (auto* e : g->eng) if (call(e) != Q3TTS_OK) { rc = Q3TTS_ERR; if (walk == ALL_OR_STOP) break; }
+    return rc;
+}
+// 4. held objects ([EXT] codec preambles, prompt stems): built on every engine under one id, as voices are.  The engines of a group are alike
+// and hand out ids in order, so what the first engine accepts the others accept under the same id; one created on a single engine behind
+// the group's back breaks that
+struct HeldCalls {
+    const char* noun;
+    int (*poll)(q3tts_engine*, int32_t, int32_t*, int32_t*); int (*wait)(q3tts_engine*, int32_t, double); int (*release)(q3tts_engine*, int32_t);
+    int (*set_voice)(q3tts_engine*, int32_t, int32_t); int (*set_engine)(q3tts_engine*, int32_t);
+};
+const HeldCalls kPreamble = {"preamble", q3tts_preamble_poll, q3tts_preamble_wait, q3tts_preamble_release, q3tts_voice_set_preamble, q3tts_engine_set_preamble};
+const HeldCalls kStem = {"stem", q3tts_stem_poll, q3tts_stem_wait, q3tts_stem_release, q3tts_voice_set_stem, q3tts_engine_set_stem};
+template <class F> int held_create(q3tts_group* g, const HeldCalls& k, int32_t* id_out, F create) {
+    Q3_API_BEGIN
+    Q3_CHECK(g && id_out, "null argument");
+    int32_t first = -1;
+    for (size_t i = 0; i < g->eng.size(); i++) {
+        int32_t id = -1;
+        if (create(g->eng[i], &id) != Q3TTS_OK) {
+            const std::string why = last_error();
+            for (size_t j = 0; j < i; j++) (void)k.release(g->eng[j], first); // all engines or none
+            throw Error(why);
+        }
+        if (i == 0) first = id;
+        Q3_CHECK(id == first, std::string("engines of a group must hand out the same ") + k.noun + " ids (create " + k.noun + "s through the group only)");
+    }
+    *id_out = first;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int held_wait(q3tts_group* g, const HeldCalls& k, int32_t id, double timeout_ms) { // 0 once every engine's copy is READY or FAILED, 1 on timeout
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    int worst = 0;
+    for (auto* e : g->eng) {
+        const int rc = k.wait(e, id, timeout_ms);
+        if (rc < 0) return rc;
+        worst = std::max(worst, rc);
+    }
+    return worst;
+}
+// a setter takes an object that is READY on every engine, checked before any engine is touched: all engines or none
+template <class F> int held_set(q3tts_group* g, const HeldCalls& k, int32_t id, F set) {
+    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
+    const HeldWords words(k.noun); // owns the text set_refusal points into
+    for (size_t i = 0; id >= 0 && i < g->eng.size(); i++) {
+        int32_t st = 0;
+        if (k.poll(g->eng[i], id, &st, nullptr) != Q3TTS_OK) return Q3TTS_ERR;
+        if (const char* why = words.set_refusal(true, st)) { set_last_error(why); return Q3TTS_ERR; }
+    }
+    return on_every(g, ALL_OR_STOP, set);
+}
+} // namespace
+extern "C" {
 
 int q3tts_group_submit(q3tts_group* g, const q3tts_request* r, int32_t want_pcm, int64_t* req_id) { return q3tts_group_submit_ex(g, r, want_pcm, nullptr, req_id); }
 int q3tts_group_submit_ex(q3tts_group* g, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && r && req_id, "null argument");
-    const int i = pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_ex(g->eng[i], r, want_pcm, opts, &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && r && req_id, kNext, req_id, 1, [&](q3tts_engine* e) { return q3tts_submit_ex(e, r, want_pcm, opts, req_id); });
 }
 int q3tts_group_submit_text(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                             int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm, int64_t* req_id) {
@@ -284,285 +356,110 @@ int q3tts_group_submit_text(q3tts_group* g, int32_t voice_id, const int32_t* tex
 int q3tts_group_submit_text_ex(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id, const int32_t* instr_ids,
                                int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps, int32_t mask_eos, int32_t want_pcm,
                                const q3tts_gen_options* opts, int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && req_id, "null argument");
-    const int i = pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_text_ex(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && req_id, kNext, req_id, 1, [&](q3tts_engine* e) {
+        return q3tts_submit_text_ex(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, req_id); });
 }
-#define Q3_GROUP_ENGINE(g, id) ((g) && eng_of(id) < (int)(g)->eng.size() ? (g)->eng[eng_of(id)] : nullptr)
 int q3tts_group_submit_text_streaming(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                                       const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler, int32_t max_steps,
                                       int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts, int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && req_id, "null argument");
-    const int i = pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_text_streaming(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts,
-                                    &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && req_id, kNext, req_id, 1, [&](q3tts_engine* e) {
+        return q3tts_submit_text_streaming(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, req_id); });
 }
 int q3tts_group_submit_text_streaming_open(q3tts_group* g, int32_t voice_id, const int32_t* text_ids, int32_t n_text, int32_t lang_id,
                                            const int32_t* instr_ids, int32_t n_instr, const q3tts_sampler_config* sampler,
                                            int32_t max_steps, int32_t mask_eos, int32_t want_pcm, const q3tts_gen_options* opts,
                                            int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && req_id, "null argument");
-    const int i = pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_text_streaming_open(g->eng[i], voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos,
-                                         want_pcm, opts, &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
-}
-int q3tts_group_text_append(q3tts_group* g, int64_t req_id, const int32_t* text_ids, int32_t n, int32_t is_last) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_text_append(e, rid_of(req_id), text_ids, n, is_last);
-}
-int q3tts_group_trail_append(q3tts_group* g, int64_t req_id, const int32_t* ids, int32_t n, int32_t close) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_trail_append(e, rid_of(req_id), ids, n, close);
-}
-int q3tts_group_trail_progress(q3tts_group* g, int64_t req_id, int32_t* n_appended, int32_t* n_consumed, int32_t* closed) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_trail_progress(e, rid_of(req_id), n_appended, n_consumed, closed);
-}
-int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id) { return (g && eng_of(req_id) < (int)g->slot.size()) ? g->slot[eng_of(req_id)].dev : -1; }
-int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_poll(e, rid_of(req_id), out);
-}
-int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out, int64_t pcm_off,
-                      int64_t pcm_cap, int32_t* got_frames, int64_t* got_pcm) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_fetch(e, rid_of(req_id), codes_out, frame_off, max_frames, pcm_out, pcm_off, pcm_cap, got_frames, got_pcm);
-}
-int q3tts_group_wait(q3tts_group* g, int64_t req_id, double timeout_ms) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_wait(e, rid_of(req_id), timeout_ms);
-}
-int q3tts_group_release(q3tts_group* g, int64_t req_id) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_release(e, rid_of(req_id));
-}
-int q3tts_group_cancel(q3tts_group* g, int64_t req_id) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_cancel(e, rid_of(req_id));
+    return submit_on(g, g && req_id, kNext, req_id, 1, [&](q3tts_engine* e) {
+        return q3tts_submit_text_streaming_open(e, voice_id, text_ids, n_text, lang_id, instr_ids, n_instr, sampler, max_steps, mask_eos, want_pcm, opts, req_id); });
 }
 int q3tts_group_submit_resume(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                               const int32_t* trail_ids, int32_t n_trail, int32_t open, const int32_t* prefix_codes, int32_t n_prefix, int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && r && req_id, "null argument");
-    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
-    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_resume(g->eng[i], r, want_pcm, opts, trail_ids, n_trail, open, prefix_codes, n_prefix, &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && r && req_id, engine_index, req_id, 1, [&](q3tts_engine* e) {
+        return q3tts_submit_resume(e, r, want_pcm, opts, trail_ids, n_trail, open, prefix_codes, n_prefix, req_id); });
 }
 int q3tts_group_submit_score(q3tts_group* g, int32_t engine_index, const float* prompt, int32_t n_prompt, const int32_t* trail_ids, int32_t n_trail,
                              const int32_t* codes, int32_t n, int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && req_id, "null argument");
-    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
-    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_score(g->eng[i], prompt, n_prompt, trail_ids, n_trail, codes, n, &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && req_id, engine_index, req_id, 1, [&](q3tts_engine* e) { return q3tts_submit_score(e, prompt, n_prompt, trail_ids, n_trail, codes, n, req_id); });
 }
 int q3tts_group_submit_decode(q3tts_group* g, int32_t engine_index, const int32_t* codes, int32_t n, int64_t* req_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && codes && req_id, "null argument");
-    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
-    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
-    int64_t id = 0;
-    if (q3tts_submit_decode(g->eng[i], codes, n, &id) != Q3TTS_OK) return Q3TTS_ERR;
-    *req_id = (id << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && codes && req_id, engine_index, req_id, 1, [&](q3tts_engine* e) { return q3tts_submit_decode(e, codes, n, req_id); });
 }
 int q3tts_group_submit_candidates(q3tts_group* g, int32_t engine_index, const q3tts_request* r, int32_t want_pcm, const q3tts_gen_options* opts,
                                   const int32_t* trail_ids, int32_t n_trail, const uint64_t* seeds, int32_t n, int64_t* req_ids) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && r, "null argument");
-    Q3_CHECK(engine_index >= -1 && engine_index < (int)g->eng.size(), "engine_index outside the group (-1 = round robin)");
-    const int i = engine_index >= 0 ? engine_index : pick_engine(g);
-    if (q3tts_submit_candidates(g->eng[i], r, want_pcm, opts, trail_ids, n_trail, seeds, n, req_ids) != Q3TTS_OK) return Q3TTS_ERR;
-    for (int k = 0; k < n; k++) req_ids[k] = (req_ids[k] << kEngineBits) | i;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
+    return submit_on(g, g && r, engine_index, req_ids, n, [&](q3tts_engine* e) { // req_ids: the engine's own check
+        return q3tts_submit_candidates(e, r, want_pcm, opts, trail_ids, n_trail, seeds, n, req_ids); });
 }
-int q3tts_group_set_logprobs(q3tts_group* g, int32_t on) { // [EXT] q3tts_engine_set_logprobs on every engine
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    for (auto* e : g->eng) if (q3tts_engine_set_logprobs(e, on) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
+
+int32_t q3tts_group_device_of(q3tts_group* g, int64_t req_id) { return (g && eng_of(req_id) < (int)g->slot.size()) ? g->slot[eng_of(req_id)].dev : -1; }
+int q3tts_group_text_append(q3tts_group* g, int64_t req_id, const int32_t* text_ids, int32_t n, int32_t is_last) { return routed(g, req_id, q3tts_text_append, text_ids, n, is_last); }
+int q3tts_group_trail_append(q3tts_group* g, int64_t req_id, const int32_t* ids, int32_t n, int32_t close) { return routed(g, req_id, q3tts_trail_append, ids, n, close); }
+int q3tts_group_trail_progress(q3tts_group* g, int64_t req_id, int32_t* n_appended, int32_t* n_consumed, int32_t* closed) {
+    return routed(g, req_id, q3tts_trail_progress, n_appended, n_consumed, closed);
 }
+int q3tts_group_poll(q3tts_group* g, int64_t req_id, q3tts_req_status* out) { return routed(g, req_id, q3tts_poll, out); }
+int q3tts_group_fetch(q3tts_group* g, int64_t req_id, int32_t* codes_out, int32_t frame_off, int32_t max_frames, float* pcm_out, int64_t pcm_off,
+                      int64_t pcm_cap, int32_t* got_frames, int64_t* got_pcm) {
+    return routed(g, req_id, q3tts_fetch, codes_out, frame_off, max_frames, pcm_out, pcm_off, pcm_cap, got_frames, got_pcm);
+}
+int q3tts_group_wait(q3tts_group* g, int64_t req_id, double timeout_ms) { return routed(g, req_id, q3tts_wait, timeout_ms); }
+int q3tts_group_release(q3tts_group* g, int64_t req_id) { return routed(g, req_id, q3tts_release); }
+int q3tts_group_cancel(q3tts_group* g, int64_t req_id) { return routed(g, req_id, q3tts_cancel); }
 int q3tts_group_fetch_logprobs(q3tts_group* g, int64_t req_id, float* out, int32_t frame_off, int32_t max_frames, int32_t* got_frames) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_fetch_logprobs(e, rid_of(req_id), out, frame_off, max_frames, got_frames);
+    return routed(g, req_id, q3tts_fetch_logprobs, out, frame_off, max_frames, got_frames);
 }
-int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f) { // [EXT] q3tts_engine_set_output_format on every engine
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    if (f && q3tts_pcm_format_check(f) != Q3TTS_OK) return Q3TTS_ERR; // all engines or none
-    for (auto* e : g->eng) if (q3tts_engine_set_output_format(e, f) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
+int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got) { return routed(g, req_id, q3tts_fetch_pcm16, out, off, cap, got); }
+int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out) { return routed(g, req_id, q3tts_request_format, out); }
+int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamble_id) { return routed(g, req_id, q3tts_request_preamble, preamble_id); }
+int q3tts_group_request_stem(q3tts_group* g, int64_t req_id, int32_t* stem_id, int32_t* rows_reused) { return routed(g, req_id, q3tts_request_stem, stem_id, rows_reused); }
+int q3tts_group_request_speech_rate(q3tts_group* g, int64_t req_id, int32_t* rate_pct) { return routed(g, req_id, q3tts_request_speech_rate, rate_pct); }
+
+// [EXT] the engine-level settings, on every engine; a value is checked before any engine is touched: all engines or none
+int q3tts_group_set_logprobs(q3tts_group* g, int32_t on) { return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_logprobs(e, on); }); }
+int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f) {
+    if (g && f && q3tts_pcm_format_check(f) != Q3TTS_OK) return Q3TTS_ERR;
+    return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_output_format(e, f); });
 }
-int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_fetch_pcm16(e, rid_of(req_id), out, off, cap, got);
+int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) {
+    if (g && q3tts_tsm_samples(rate_pct, 0, 0) < 0) { set_last_error("speech rate out of range [50, 200]"); return Q3TTS_ERR; }
+    return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_speech_rate(e, rate_pct); });
 }
-int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_request_format(e, rid_of(req_id), out);
-}
-// [EXT] codec preambles: built on every engine under one id, as voices are.  The engines of a group are alike and hand out ids in order, so
-// what the first engine accepts the others accept under the same id; a preamble created on one engine behind the group's back breaks that
-int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && preamble_id, "null argument");
-    int32_t pid = -1;
-    for (size_t i = 0; i < g->eng.size(); i++) {
-        int32_t id = -1;
-        if (q3tts_preamble_create(g->eng[i], codes, n, &id) != Q3TTS_OK) {
-            const std::string why = last_error();
-            for (size_t k = 0; k < i; k++) (void)q3tts_preamble_release(g->eng[k], pid); // all engines or none
-            throw Error(why);
-        }
-        if (i == 0) pid = id;
-        Q3_CHECK(id == pid, "engines of a group must hand out the same preamble ids (create preambles through the group only)");
-    }
-    *preamble_id = pid;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
-}
-int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms) { // 0 once every engine's copy is READY or FAILED, 1 on timeout
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    int worst = 0;
-    for (auto* e : g->eng) {
-        const int rc = q3tts_preamble_wait(e, preamble_id, timeout_ms);
-        if (rc < 0) return rc;
-        worst = std::max(worst, rc);
-    }
-    return worst;
-}
-int q3tts_group_preamble_release(q3tts_group* g, int32_t preamble_id) {
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    int rc = Q3TTS_OK;
-    for (auto* e : g->eng) if (q3tts_preamble_release(e, preamble_id) != Q3TTS_OK) rc = Q3TTS_ERR;
+int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
+    const int rc = on_every(g, ALL_OR_STOP, q3tts_sched_start, nullptr);
+    if (rc == Q3TTS_OK) g->started = true;
     return rc;
 }
-static int group_preamble_ready(q3tts_group* g, int32_t preamble_id) { // a setter takes a preamble that is READY on every engine: all engines or none
-    if (preamble_id < 0) return Q3TTS_OK;
-    for (auto* e : g->eng) {
-        int32_t st = 0;
-        if (q3tts_preamble_poll(e, preamble_id, &st, nullptr) != Q3TTS_OK) return Q3TTS_ERR;
-        if (const char* why = preamble_set_refusal(true, st)) { set_last_error(why); return Q3TTS_ERR; }
-    }
-    return Q3TTS_OK;
+int q3tts_group_stop(q3tts_group* g) {
+    const int rc = on_every(g, EVERY, q3tts_sched_stop, nullptr);
+    if (g) g->started = false;
+    return rc;
 }
+
+// [EXT] codec preambles
+int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id) {
+    return held_create(g, kPreamble, preamble_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_preamble_create(e, codes, n, id); });
+}
+int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms) { return held_wait(g, kPreamble, preamble_id, timeout_ms); }
+int q3tts_group_preamble_release(q3tts_group* g, int32_t preamble_id) { return on_every(g, EVERY, [&](q3tts_engine* e) { return q3tts_preamble_release(e, preamble_id); }); }
 int q3tts_group_voice_set_preamble(q3tts_group* g, int32_t voice_id, int32_t preamble_id) {
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    if (group_preamble_ready(g, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
-    for (auto* e : g->eng) if (q3tts_voice_set_preamble(e, voice_id, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
+    return held_set(g, kPreamble, preamble_id, [&](q3tts_engine* e) { return q3tts_voice_set_preamble(e, voice_id, preamble_id); });
 }
 int q3tts_group_set_preamble(q3tts_group* g, int32_t preamble_id) {
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    if (group_preamble_ready(g, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
-    for (auto* e : g->eng) if (q3tts_engine_set_preamble(e, preamble_id) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
+    return held_set(g, kPreamble, preamble_id, [&](q3tts_engine* e) { return q3tts_engine_set_preamble(e, preamble_id); });
 }
-int q3tts_group_request_preamble(q3tts_group* g, int64_t req_id, int32_t* preamble_id) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_request_preamble(e, rid_of(req_id), preamble_id);
-}
-// [EXT] prompt stems: built on every engine under one id, as preambles are (create stems through the group only)
-static int group_stem_create(q3tts_group* g, int32_t* stem_id, const std::function<int(q3tts_engine*, int32_t*)>& create) {
-    Q3_API_BEGIN
-    Q3_CHECK(g && stem_id, "null argument");
-    int32_t sid = -1;
-    for (size_t i = 0; i < g->eng.size(); i++) {
-        int32_t id = -1;
-        if (create(g->eng[i], &id) != Q3TTS_OK) {
-            const std::string why = last_error();
-            for (size_t k = 0; k < i; k++) (void)q3tts_stem_release(g->eng[k], sid); // all engines or none
-            throw Error(why);
-        }
-        if (i == 0) sid = id;
-        Q3_CHECK(id == sid, "engines of a group must hand out the same stem ids (create stems through the group only)");
-    }
-    *stem_id = sid;
-    return Q3TTS_OK;
-    Q3_API_END(Q3TTS_ERR)
-}
+// [EXT] prompt stems
 int q3tts_group_stem_create(q3tts_group* g, const float* rows, int32_t n_rows, int32_t* stem_id) {
-    return group_stem_create(g, stem_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_stem_create(e, rows, n_rows, id); });
+    return held_create(g, kStem, stem_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_stem_create(e, rows, n_rows, id); });
 }
 int q3tts_group_voice_stem_create(q3tts_group* g, int32_t voice_id, int32_t lang_id, const int32_t* instr_ids, int32_t n_instr, int32_t* stem_id) {
-    return group_stem_create(g, stem_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_voice_stem_create(e, voice_id, lang_id, instr_ids, n_instr, id); });
+    return held_create(g, kStem, stem_id, [&](q3tts_engine* e, int32_t* id) { return q3tts_voice_stem_create(e, voice_id, lang_id, instr_ids, n_instr, id); });
 }
-int q3tts_group_stem_wait(q3tts_group* g, int32_t stem_id, double timeout_ms) { // 0 once every engine's copy is READY or FAILED, 1 on timeout
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    int worst = 0;
-    for (auto* e : g->eng) {
-        const int rc = q3tts_stem_wait(e, stem_id, timeout_ms);
-        if (rc < 0) return rc;
-        worst = std::max(worst, rc);
-    }
-    return worst;
-}
-int q3tts_group_stem_release(q3tts_group* g, int32_t stem_id) {
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    int rc = Q3TTS_OK;
-    for (auto* e : g->eng) if (q3tts_stem_release(e, stem_id) != Q3TTS_OK) rc = Q3TTS_ERR;
-    return rc;
-}
-static int group_stem_ready(q3tts_group* g, int32_t stem_id) { // a setter takes a stem that is READY on every engine: all engines or none
-    if (stem_id < 0) return Q3TTS_OK;
-    for (auto* e : g->eng) {
-        int32_t st = 0;
-        if (q3tts_stem_poll(e, stem_id, &st, nullptr) != Q3TTS_OK) return Q3TTS_ERR;
-        if (const char* why = stem_set_refusal(true, st)) { set_last_error(why); return Q3TTS_ERR; }
-    }
-    return Q3TTS_OK;
-}
+int q3tts_group_stem_wait(q3tts_group* g, int32_t stem_id, double timeout_ms) { return held_wait(g, kStem, stem_id, timeout_ms); }
+int q3tts_group_stem_release(q3tts_group* g, int32_t stem_id) { return on_every(g, EVERY, [&](q3tts_engine* e) { return q3tts_stem_release(e, stem_id); }); }
 int q3tts_group_voice_set_stem(q3tts_group* g, int32_t voice_id, int32_t stem_id) {
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    if (group_stem_ready(g, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
-    for (auto* e : g->eng) if (q3tts_voice_set_stem(e, voice_id, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
+    return held_set(g, kStem, stem_id, [&](q3tts_engine* e) { return q3tts_voice_set_stem(e, voice_id, stem_id); });
 }
 int q3tts_group_set_stem(q3tts_group* g, int32_t stem_id) {
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    if (group_stem_ready(g, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
-    for (auto* e : g->eng) if (q3tts_engine_set_stem(e, stem_id) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
-}
-int q3tts_group_request_stem(q3tts_group* g, int64_t req_id, int32_t* stem_id, int32_t* rows_reused) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_request_stem(e, rid_of(req_id), stem_id, rows_reused);
+    return held_set(g, kStem, stem_id, [&](q3tts_engine* e) { return q3tts_engine_set_stem(e, stem_id); });
 }
 int q3tts_group_stem_stats(q3tts_group* g, q3tts_stem_stats* out) { // the engines' counters added up
     if (!g || !out) { set_last_error("null argument"); return Q3TTS_ERR; }
@@ -575,30 +472,6 @@ int q3tts_group_stem_stats(q3tts_group* g, q3tts_stem_stats* out) { // the engin
     }
     *out = sum;
     return Q3TTS_OK;
-}
-int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) { // [EXT] q3tts_engine_set_speech_rate on every engine
-    if (!g) { set_last_error("null argument"); return Q3TTS_ERR; }
-    if (q3tts_tsm_samples(rate_pct, 0, 0) < 0) { set_last_error("speech rate out of range [50, 200]"); return Q3TTS_ERR; } // all engines or none
-    for (auto* e : g->eng) if (q3tts_engine_set_speech_rate(e, rate_pct) != Q3TTS_OK) return Q3TTS_ERR;
-    return Q3TTS_OK;
-}
-int q3tts_group_request_speech_rate(q3tts_group* g, int64_t req_id, int32_t* rate_pct) {
-    q3tts_engine* e = Q3_GROUP_ENGINE(g, req_id);
-    if (!e) { set_last_error("unknown group request id"); return Q3TTS_ERR; }
-    return q3tts_request_speech_rate(e, rid_of(req_id), rate_pct);
-}
-int q3tts_group_start(q3tts_group* g) { // one scheduler thread per device
-    if (!g) return Q3TTS_ERR;
-    for (auto* e : g->eng) if (q3tts_sched_start(e) != Q3TTS_OK) return Q3TTS_ERR;
-    g->started = true;
-    return Q3TTS_OK;
-}
-int q3tts_group_stop(q3tts_group* g) {
-    if (!g) return Q3TTS_ERR;
-    int rc = Q3TTS_OK;
-    for (auto* e : g->eng) if (q3tts_sched_stop(e) != Q3TTS_OK) rc = Q3TTS_ERR;
-    g->started = false;
-    return rc;
 }
 
 // ---------------- one process per GPU ----------------

@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble (with who holds one) and of a prompt stem (with its take rule), what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -7,6 +7,10 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <map>
+#include <optional>
+#include <stdexcept>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -251,6 +255,85 @@ inline const char* decode_refusal(const int32_t* codes, int n, int max_steps, bo
     if (!codes) return "codes missing";
     return resume_refusal(1, n + 1, codes, n, false, 0, (int64_t)n + 2); // the ranges alone: its own limits are out of the way
 }
+
+// [EXT] held objects: what codec preambles and prompt stems have in common.  Both are numbered things built once, asynchronously, by a hidden
+// request.  Who holds one: its creator until the release call, and `holders` = the voices it is set on, the engine-level setting, and the
+// requests submitted with it that have not ended (a request with PCM ends behind its fence, so every restore it enqueued has completed).
+enum { HELD_BUILDING = 0, HELD_READY = 1, HELD_FAILED = -1 };
+static_assert(Q3TTS_PREAMBLE_BUILDING == HELD_BUILDING && Q3TTS_PREAMBLE_READY == HELD_READY && Q3TTS_PREAMBLE_FAILED == HELD_FAILED &&
+              Q3TTS_STEM_BUILDING == HELD_BUILDING && Q3TTS_STEM_READY == HELD_READY && Q3TTS_STEM_FAILED == HELD_FAILED, "one table serves both kinds");
+struct HeldRefs {
+    bool creator = true; int holders = 0; int state = HELD_BUILDING;
+    // what the object owns on the device goes back only when nobody holds it and its build has ended (a building one is still being written)
+    bool recyclable() const { return !creator && holders == 0 && state != HELD_BUILDING; }
+};
+struct HeldWords { // the messages of one kind, noun = "preamble" / "stem"
+    const std::string unknown, released, building, failed, bad_id;
+    explicit HeldWords(const std::string& noun)
+        : unknown("unknown " + noun + " id"), released("the " + noun + " has already been released"),
+          building("the " + noun + " is still building: wait for it (q3tts_" + noun + "_wait)"), failed("the " + noun + " failed to build"),
+          bad_id(noun + " id must be -1 (none) or a " + noun + "'s id") {}
+    // what a setter (voice or engine level) refuses, or null: it takes a READY object only, so "primed or not" / "taken or not" never depends on timing
+    const char* set_refusal(bool known, int state) const {
+        return !known ? unknown.c_str() : state == HELD_BUILDING ? building.c_str() : state != HELD_READY ? failed.c_str() : nullptr;
+    }
+};
+// the same two answers asked per kind, as the rule drivers of tests/host ask them: both kinds count alike and word their refusals alike
+typedef HeldRefs PreambleRefs;
+inline bool preamble_recyclable(const HeldRefs& p) { return p.recyclable(); }
+inline const char* preamble_set_refusal(bool known, int state) { static const HeldWords w("preamble"); return w.set_refusal(known, state); }
+inline const char* stem_set_refusal(bool known, int state) { static const HeldWords w("stem"); return w.set_refusal(known, state); }
+// The live objects of one kind by id, the next id (never reused) and the engine-level setting (-1: none).  No lock: the engine calls it under
+// its own.  Whatever ends the last hold -- unhold, release_creator, finish, swap_setting -- removes the entry and hands its payload back, and the
+// caller disposes of what the payload owns; nothing else removes an entry.
+template <class Payload> class HeldTable {
+public:
+    struct Entry { HeldRefs refs; int n = 0; Payload payload{}; }; // n: frames of a preamble, rows of a stem
+    using Recycled = std::optional<Payload>;
+    const HeldWords words; int setting = -1;
+    explicit HeldTable(const char* noun) : words(noun) {}
+    const std::map<int, Entry>& entries() const { return map_; }
+    int live() const { return (int)map_.size(); }
+    int add(int n) { const int id = next_++; map_[id].n = n; return id; } // its creator holds it, nobody else, building
+    Entry* find(int id) { auto it = map_.find(id); return it == map_.end() ? nullptr : &it->second; }
+    Entry& at(int id) { if (Entry* e = find(id)) return *e; throw std::runtime_error(words.unknown); }
+    void hold(int id) { at(id).refs.holders++; }
+    Recycled unhold(int id) { // one holder less; an unknown id is nobody's
+        auto it = map_.find(id);
+        if (it == map_.end()) return std::nullopt;
+        it->second.refs.holders--;
+        if (!it->second.refs.recyclable()) return std::nullopt;
+        Recycled out(std::move(it->second.payload));
+        map_.erase(it);
+        return out;
+    }
+    Recycled release_creator(int id) { // the creator's reference becomes a holder's, which is dropped: recycles when nobody else holds it
+        Entry& e = at(id);
+        if (!e.refs.creator) throw std::runtime_error(words.released);
+        e.refs.creator = false; e.refs.holders++;
+        return unhold(id);
+    }
+    Recycled finish(int id, bool ok) { // the build has ended; recycles at once when it was released while it built
+        Entry* e = find(id);
+        if (!e) return std::nullopt;
+        e->refs.state = ok ? HELD_READY : HELD_FAILED; e->refs.holders++;
+        return unhold(id);
+    }
+    void fail_building() { for (auto& kv : map_) if (kv.second.refs.state == HELD_BUILDING) kv.second.refs.state = HELD_FAILED; } // nothing builds them any more
+    const char* set_refusal(int id) const { auto it = map_.find(id); return words.set_refusal(it != map_.end(), it != map_.end() ? it->second.refs.state : 0); }
+    // a setter: `which` (a voice's setting or this table's own) becomes id.  The new object is held before the old one is dropped, so setting the
+    // same id twice never recycles it; a refusal leaves everything as it was
+    Recycled swap_setting(int& which, int id) {
+        if (id >= 0) { if (const char* why = set_refusal(id)) throw std::runtime_error(why); hold(id); }
+        else if (id != -1) throw std::runtime_error(words.bad_id);
+        const int old = which;
+        which = id;
+        return old >= 0 ? unhold(old) : std::nullopt;
+    }
+private:
+    std::map<int, Entry> map_; int next_ = 0;
+};
+
 // [EXT] codec preambles (q3tts_spec.h "codec preambles"): why a preamble of n frames is refused, or null.  Pure, like the four above.  A preamble
 // is built like a decode-only request, so decode_refusal's reasons come first; live = preambles the engine holds now (building ones included).
 // Frame f of a primed request sits at RoPE position n + f, so n + max_steps must stay within the codec's positions.
@@ -260,18 +343,6 @@ inline const char* preamble_refusal(const int32_t* codes, int n, int max_steps, 
     if ((int64_t)n + max_steps > max_positions) return "n + max_steps exceeds the codec's frame positions";
     return nullptr;
 }
-// Who holds a preamble: its creator until q3tts_preamble_release, and `holders` = the voices it is set on, the engine-level setting, and the
-// requests submitted with it that have not ended (a request with PCM ends behind its fence, so every restore it enqueued has completed).
-struct PreambleRefs { bool creator = true; int holders = 0; int state = Q3TTS_PREAMBLE_BUILDING; };
-// the snapshot's slot goes back only when nobody holds the preamble and its build has ended (a building preamble's stream is still decoding)
-inline bool preamble_recyclable(const PreambleRefs& p) { return !p.creator && p.holders == 0 && p.state != Q3TTS_PREAMBLE_BUILDING; }
-// what a setter (voice or engine level) refuses, or null: it takes a READY preamble only, so "primed or not" never depends on timing
-inline const char* preamble_set_refusal(bool known, int state) {
-    if (!known) return "unknown preamble id";
-    if (state == Q3TTS_PREAMBLE_BUILDING) return "the preamble is still building: wait for it (q3tts_preamble_wait)";
-    if (state != Q3TTS_PREAMBLE_READY) return "the preamble failed to build";
-    return nullptr;
-}
 // the preamble a request is primed with: never without PCM; a text form takes its voice's, a raw-prompt form the engine-level setting
 enum { PREAMBLE_NONE = -1, PREAMBLE_ENGINE = -2 };
 inline int preamble_of_request(bool want_pcm, int asked, int engine_level) {
@@ -279,11 +350,8 @@ inline int preamble_of_request(bool want_pcm, int asked, int engine_level) {
     return asked == PREAMBLE_ENGINE ? engine_level : asked;
 }
 
-// [EXT] prompt stems (q3tts_spec.h "prompt stems").  The states and the holder rule are the preamble's (PreambleRefs / preamble_recyclable): the
-// store goes back when nobody holds the stem and its build has ended; a request that took it holds it from submit to its end, so every
-// restore enqueued from it has completed by then.
-static_assert(Q3TTS_STEM_BUILDING == Q3TTS_PREAMBLE_BUILDING && Q3TTS_STEM_READY == Q3TTS_PREAMBLE_READY && Q3TTS_STEM_FAILED == Q3TTS_PREAMBLE_FAILED,
-              "stems share PreambleRefs: the states must agree");
+// [EXT] prompt stems (q3tts_spec.h "prompt stems").  The states and the holder rule are HeldTable's: the store goes back when nobody holds the
+// stem and its build has ended; a request that took it holds it from submit to its end, so every restore enqueued from it has completed by then.
 // why a stem of n rows is refused, or null.  Pure; live = stems the engine holds now (building ones included)
 inline const char* stem_refusal(const float* rows, int n, int max_prompt, int live, bool ggml) {
     if (ggml) return "prompt stems are not available with Q3_SPEC=ggml (the ggml-arithmetic mode serves the reference's decoding only)";
@@ -291,12 +359,6 @@ inline const char* stem_refusal(const float* rows, int n, int max_prompt, int li
     if (n < 1) return "n_rows must be >= 1";
     if (n >= max_prompt) return "n_rows must be below max_prompt: a request that takes a stem has at least one row of its own";
     if (live >= Q3TTS_MAX_STEMS) return "Q3TTS_MAX_STEMS stems are live: release one first";
-    return nullptr;
-}
-inline const char* stem_set_refusal(bool known, int state) {
-    if (!known) return "unknown stem id";
-    if (state == Q3TTS_STEM_BUILDING) return "the stem is still building: wait for it (q3tts_stem_wait)";
-    if (state != Q3TTS_STEM_READY) return "the stem failed to build";
     return nullptr;
 }
 // the stem that applies to a request: a text form passes its voice's, a raw-prompt form takes the engine-level setting
