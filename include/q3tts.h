@@ -552,8 +552,11 @@ int q3tts_decoder_snapshot_free(q3tts_decoder* d, int32_t snapshot);
 int64_t q3tts_decoder_snapshot_bytes(q3tts_decoder* d);
 
 /* ---- mel front end (device) ---- */
+/* q3tts_mel_frames is the number of frames q3tts_mel writes: 0 below 256 samples (no whole frame fits the padded clip), n / 256 from there on.
+ * q3tts_mel_tables (host only, no device needed) fills the f32 periodic Hann window and Slaney filterbank the kernel reads. */
 int q3tts_mel_frames(int32_t n_samples);
 int q3tts_mel(const float* audio, int32_t n_samples, float* mel_out /* [frames][128] */);
+int q3tts_mel_tables(float* hann /* [1024] */, float* fb /* [128][513] */);
 
 /* ---- transformer contexts (shared with the llama shim; also the layer-level parity surface) ---- */
 typedef struct q3tts_tf q3tts_tf;

@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "pcm_out.h"
 #include "tsm.h"
+#include "mel.h"
 
 using namespace q3;
 #define Q3_API_BEGIN try {
@@ -1333,7 +1334,7 @@ int q3tts_op_tsm(const float* in, int32_t G, const int32_t* chunk_samples, int32
     Q3_API_END(Q3TTS_ERR)
 }
 
-int q3tts_mel_frames(int32_t n) { const int plen = n + 768; return (plen > 1024 ? plen - 1024 : 0) / 256 + 1; }
+int q3tts_mel_frames(int32_t n) { return mel_frames(n); }
 
 } // extern "C"
 

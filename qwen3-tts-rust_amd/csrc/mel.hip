@@ -5,11 +5,12 @@
 // for the 513 bins (0.5 MFLOP per frame: launch-bound, not worth an FFT), then the filterbank in ascending-k order.
 #include "../../include/q3tts.h"
 #include "q3_common.h"
+#include "mel.h"
 #include <cmath>
 
 namespace q3 {
 
-constexpr int N_FFT = 1024, HOP = 256, N_MELS = 128, N_BINS = N_FFT / 2 + 1;
+constexpr int N_FFT = MEL_N_FFT, HOP = MEL_HOP, N_MELS = MEL_N_MELS, N_BINS = MEL_N_BINS;
 
 __global__ void __launch_bounds__(256) k_mel(const float* __restrict__ padded, int plen, const float* __restrict__ hann,
                                             const float* __restrict__ fb, float* __restrict__ mel) {
@@ -53,12 +54,8 @@ static float mel_to_hz(float mel) { // onnx.rs:195-207
     return mel >= min_log_mel ? min_log_hz * expf(logstep * (mel - min_log_mel)) : f_sp * mel;
 }
 
-int mel_device(const float* audio, int n, float* mel_out) {
-    const int padding = (N_FFT - HOP) / 2, plen = padding + n + padding;
-    int n_frames = (plen > N_FFT ? plen - N_FFT : 0) / HOP + 1; // :283
-    while (n_frames > 0 && (n_frames - 1) * HOP + N_FFT > plen) n_frames--; // :288-290
-    if (n_frames <= 0) return 0;
-    std::vector<float> fb((size_t)N_MELS * N_BINS, 0.0f), edges(N_MELS + 2), hann(N_FFT), padded((size_t)plen);
+void mel_tables(float* hann, float* fb) {
+    std::vector<float> edges(N_MELS + 2);
     const float mmin = hz_to_mel(0.0f), mmax = hz_to_mel(12000.0f);
     for (int i = 0; i <= N_MELS + 1; i++) edges[i] = mel_to_hz(mmin + (mmax - mmin) * (float)i / (float)(N_MELS + 1));
     for (int m = 0; m < N_MELS; m++) {
@@ -71,11 +68,19 @@ int mel_device(const float* audio, int n, float* mel_out) {
             fb[(size_t)m * N_BINS + k] = w * norm;
         }
     }
+    for (int i = 0; i < N_FFT; i++) hann[i] = 0.5f * (1.0f - cosf(2.0f * 3.14159265358979323846f * (float)i / (float)N_FFT));
+}
+
+int mel_device(const float* audio, int n, float* mel_out) {
+    const int padding = MEL_PAD, plen = padding + n + padding;
+    const int n_frames = mel_frames(n); // :283, :288-290
+    if (n_frames <= 0) return 0;
+    std::vector<float> fb((size_t)N_MELS * N_BINS), hann(N_FFT), padded((size_t)plen);
+    mel_tables(hann.data(), fb.data());
     int pi = 0;
     for (int i = padding; i >= 1; i--) padded[pi++] = (i < n) ? audio[i] : 0.0f;
     for (int i = 0; i < n; i++) padded[pi++] = audio[i];
     for (int i = 1; i <= padding; i++) { int idx = n - (1 + i); if (idx < 0) idx = 0; padded[pi++] = (idx < n) ? audio[idx] : 0.0f; }
-    for (int i = 0; i < N_FFT; i++) hann[i] = 0.5f * (1.0f - cosf(2.0f * 3.14159265358979323846f * (float)i / (float)N_FFT));
     DevBuf<float> d_p(padded.size()), d_h(N_FFT), d_fb(fb.size()), d_mel((size_t)n_frames * N_MELS);
     d_p.upload(padded.data(), padded.size()); d_h.upload(hann.data(), N_FFT); d_fb.upload(fb.data(), fb.size());
     hipLaunchKernelGGL(k_mel, dim3(n_frames), dim3(256), 0, 0, d_p.p, plen, d_h.p, d_fb.p, d_mel.p);
@@ -92,6 +97,14 @@ extern "C" int q3tts_mel(const float* audio, int32_t n, float* mel_out) {
         if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw q3::Error("no HIP device available: the HIP path is the only compute path (no CPU fallback)");
         if (!audio || !mel_out || n < 0) throw q3::Error("bad arguments");
         q3::mel_device(audio, n, mel_out);
+        return Q3TTS_OK;
+    } catch (const std::exception& ex) { q3::set_last_error(ex.what()); return Q3TTS_ERR; }
+}
+
+extern "C" int q3tts_mel_tables(float* hann, float* fb) { // host only
+    try {
+        if (!hann || !fb) throw q3::Error("null argument");
+        q3::mel_tables(hann, fb);
         return Q3TTS_OK;
     } catch (const std::exception& ex) { q3::set_last_error(ex.what()); return Q3TTS_ERR; }
 }

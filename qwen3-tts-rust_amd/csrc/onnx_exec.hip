@@ -640,7 +640,7 @@ struct OnnxSession::Impl {
 
     // general strided copy (transpose / slice / expand / tile) on either side
     XTensor nd_copy(const XTensor& in, const std::vector<int64_t>& oshape, const std::vector<int64_t>& istride, const std::vector<int64_t>& imod, int64_t ioff) {
-        Q3_CHECK(oshape.size() <= (size_t)XR, "rank above 8");
+        Q3_CHECK(oshape.size() <= (size_t)XR, "rank above 8 (rank " + std::to_string(oshape.size()) + ")");
         const int64_t n = prod(oshape);
         if (in.on_host) {
             XTensor o = host_tensor(in.dtype, oshape, std::vector<double>((size_t)n));
@@ -690,6 +690,7 @@ struct OnnxSession::Impl {
             return o;
         }
         Q3_CHECK(!(a0.dtype == 7 && b0.dtype == 7 && !a0.on_host && !b0.on_host && op == B_DIV), "integer division of device tensors");
+        Q3_CHECK(os.size() <= (size_t)XR, "rank above 8 (rank " + std::to_string(os.size()) + ")");
         XTensor a = as_f32(a0), b = as_f32(b0);
         XTensor o = dev_tensor(out_dtype == 7 ? 1 : out_dtype, os);
         if (n) {
@@ -1107,6 +1108,7 @@ void OnnxSession::run() {
                     }
                     out(0, o);
                 } else {
+                    Q3_CHECK(os.size() <= (size_t)XR, "Where: rank above 8 (rank " + std::to_string(os.size()) + ")");
                     XTensor cd = I.as_f32(c), ad = dtype == 7 ? I.as_i64(a) : I.as_f32(a), bd = dtype == 7 ? I.as_i64(b) : I.as_f32(b);
                     XTensor o = I.dev_tensor(dtype, os);
                     if (n) {
@@ -1377,9 +1379,10 @@ void OnnxSession::run() {
                 const std::string mode = as("mode", "constant");
                 PadArgs p{}; p.rank = rank; p.mode = mode == "constant" ? 0 : mode == "reflect" ? 1 : mode == "edge" ? 2 : -1; p.value = value;
                 Q3_CHECK(p.mode >= 0, "Pad mode " + mode);
+                Q3_CHECK(rank <= XR, "Pad: rank above 8 (rank " + std::to_string(rank) + ")");
                 std::vector<int64_t> os = x.shape;
                 for (int d = 0; d < rank; d++) { p.ishape[d] = x.shape[(size_t)d]; p.begin[d] = 0; }
-                for (size_t i = 0; i < axes.size(); i++) { int64_t a = axes[i]; if (a < 0) a += rank; p.begin[a] = pads[i]; os[(size_t)a] += pads[i] + pads[i + axes.size()]; }
+                for (size_t i = 0; i < axes.size(); i++) { int64_t a = axes[i]; if (a < 0) a += rank; Q3_CHECK(a >= 0 && a < rank, "Pad: axis out of range"); p.begin[a] = pads[i]; os[(size_t)a] += pads[i] + pads[i + axes.size()]; }
                 for (int d = 0; d < rank; d++) p.oshape[d] = os[(size_t)d];
                 XTensor o = I.dev_tensor(1, os);
                 const int64_t n = o.numel();
@@ -1434,7 +1437,7 @@ void OnnxSession::run() {
                 const int rank = (int)x.shape.size();
                 ResizeArgs a{}; a.rank = rank;
                 std::vector<int64_t> os = x.shape;
-                Q3_CHECK(rank >= 1 && rank <= 8, "Resize: rank out of range");
+                Q3_CHECK(rank >= 1 && rank <= XR, "Resize: rank out of range (rank " + std::to_string(rank) + ")");
                 const bool old_layout = I.opset < 11; // opset 10: inputs (X, scales); opset >= 11: (X, roi, scales, sizes)
                 if (!old_layout && has(3)) { os = I.ints_of(in(3)); Q3_CHECK((int)os.size() == rank, "Resize sizes rank"); for (int d = 0; d < rank; d++) { Q3_CHECK(x.shape[(size_t)d] > 0 && os[(size_t)d] >= 0, "Resize: empty input extent"); a.scale[d] = (float)os[(size_t)d] / (float)x.shape[(size_t)d]; } }
                 else { const int si = old_layout ? 1 : 2; Q3_CHECK(has(si), "Resize needs scales or sizes"); const XTensor sc = I.to_host(in(si)); Q3_CHECK((int)sc.hv.size() == rank, "Resize scales rank");

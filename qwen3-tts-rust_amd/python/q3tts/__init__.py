@@ -110,7 +110,7 @@ SYMBOLS = [
     "q3tts_group_stem_create", "q3tts_group_voice_stem_create", "q3tts_group_stem_wait", "q3tts_group_stem_release",
     "q3tts_group_voice_set_stem", "q3tts_group_set_stem", "q3tts_group_request_stem", "q3tts_group_stem_stats",
     "q3tts_engine_set_speech_rate", "q3tts_request_speech_rate", "q3tts_engine_tsm_stats", "q3tts_group_set_speech_rate",
-    "q3tts_group_request_speech_rate", "q3tts_tsm_samples", "q3tts_tsm_windows", "q3tts_op_tsm",
+    "q3tts_group_request_speech_rate", "q3tts_tsm_samples", "q3tts_tsm_windows", "q3tts_op_tsm", "q3tts_mel_tables",
 ]
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
@@ -190,6 +190,7 @@ def lib():
         L.q3tts_decoder_decode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
         L.q3tts_mel_frames.argtypes = [C.c_int32]
         L.q3tts_mel.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.q3tts_mel_tables.argtypes = [C.c_void_p, C.c_void_p]
         L.q3tts_tf_open.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.q3tts_tf_close.argtypes = [C.c_void_p]
         L.q3tts_tf_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
@@ -1542,9 +1543,21 @@ def op_codec_kernel(kernel, G, T, C_, H=0, ins=(), outs=(), p0=None, p1=None, me
 def mel(audio):
     audio = np.ascontiguousarray(audio, np.float32)
     n = lib().q3tts_mel_frames(audio.size)
-    out = np.zeros((n, 128), np.float32)
-    _chk(lib().q3tts_mel(_p(audio), audio.size, _p(out)))
-    return out
+    out = np.zeros((max(n, 1), 128), np.float32)   # never an empty buffer: a null pointer is an error of the C entry
+    src = audio if audio.size else np.zeros(1, np.float32)
+    _chk(lib().q3tts_mel(_p(src), audio.size, _p(out)))
+    return out[:n]
+
+
+def mel_frames(n):
+    return int(lib().q3tts_mel_frames(int(n)))
+
+
+def mel_tables():
+    """the f32 tables the mel kernel reads: periodic Hann [1024], Slaney filterbank [128, 513] (host only)"""
+    hann, fb = np.zeros(1024, np.float32), np.zeros((128, 513), np.float32)
+    _chk(lib().q3tts_mel_tables(_p(hann), _p(fb)))
+    return hann, fb
 
 
 class OnnxSession:
