@@ -722,6 +722,9 @@ int q3tts_op_codec_gemm(q3tts_codec_gemm_desc* d);
 /* host only (no device needed): the decoder's dispatch for d's shape -> form_ran / ksplit_ran / reducer_ran.  Pointers are not dereferenced:
  * NULL stands for a 16-byte aligned buffer (out_off still applies) */
 int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d);
+/* host only: 1 if the GEMM d describes (form AUTO: as the decoder dispatches it; a forced form: form / ksplit as given) runs k_conv_gemm_h3's
+ * tap-reusing main loop, 0 if it runs a tap-major loop, < 0 on a bad descriptor.  Pointers are not dereferenced */
+int q3tts_codec_gemm_tap_reuse(const q3tts_codec_gemm_desc* d);
 
 /* One codec-decoder kernel other than the GEMMs (csrc/codec.hip), launched as decode_group_async launches it.  R = G * T logical rows: stream g's
  * rows are g*T .. g*T+T-1.  An "extended" buffer is [G][H + T][C]: per stream H history rows (right-aligned), then the T new rows.

@@ -931,6 +931,12 @@ int q3tts_codec_gemm_plan(q3tts_codec_gemm_desc* d) {
     Q3_API_END(Q3TTS_ERR)
 }
 
+int q3tts_codec_gemm_tap_reuse(const q3tts_codec_gemm_desc* d) {
+    Q3_API_BEGIN
+    return codec_gemm_tap_reuse(d);
+    Q3_API_END(Q3TTS_ERR)
+}
+
 int q3tts_op_codec_kernel(q3tts_codec_kernel_desc* d) {
     Q3_API_BEGIN
     require_gpu();

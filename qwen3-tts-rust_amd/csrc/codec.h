@@ -70,6 +70,7 @@ private:
 // test entry points (include/q3tts.h: q3tts_op_codec_gemm, q3tts_codec_gemm_plan): one codec GEMM, dispatched as the decoder does or forced
 void codec_gemm_run(q3tts_codec_gemm_desc* d);
 void codec_gemm_plan_only(q3tts_codec_gemm_desc* d); // host only
+int codec_gemm_tap_reuse(const q3tts_codec_gemm_desc* d); // host only: 1 = the GEMM d describes runs k_conv_gemm_h3's tap-reusing loop
 void codec_kernel_run(q3tts_codec_kernel_desc* d); // q3tts_op_codec_kernel: one non-GEMM kernel as the decoder launches it
 
 } // namespace q3

@@ -349,21 +349,33 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h(GemmArgs g, const _Float16*
 // 128 x (32 NT) form: the 4 waves stack along M (32 rows each) and every wave owns NT column tiles, so a k-step of 16 reads 2 + 2 NT LDS
 // fragments for 3 NT matrix instructions (NT = 3: 8 for 9, against 4 for 3 in k_conv_gemm_h<1>), a 96-column stage has no padded columns
 // (BN = 64 wastes a quarter of the matrix work at N = 96) and the activation tile is fetched once per 96 output columns instead of once per 64.
-// One K tile in flight and ~110 VGPRs / 36 KB of LDS keep 4 workgroups per CU -- the middle ground between k_conv_gemm_h<1> (8 per CU, the
-// L2 -> LDS traffic 2.3 x larger) and a 256 x 96 register-blocked tile (2 per CU, spills; removed).  Reads pre-split operands as copies.
+// One K tile in flight and ~110 VGPRs; the EPL forms' staged output tile makes the LDS footprint 51 200 B (the operand tiles alone are 35 840 B), so
+// 3 workgroups fit a CU (163 840 B) -- between k_conv_gemm_h<1> (8 per CU, the L2 -> LDS traffic 2.3 x larger) and a 256 x 96 register-blocked
+// tile (2 per CU, spills; removed).  Reads pre-split operands as copies.
 // EPL = 1: the finished tile goes through LDS once so that every lane handles 4 consecutive columns of a row -- bias / residual / SnakeBeta parameter
 // loads and the output stores become 16-byte accesses (a row of the tile = one 384-byte burst) instead of 48 four-byte accesses per lane.
 // PF = K tiles whose loads are in flight in registers; SPLIT = operands arrive pre-split (g.a_split) -- a template parameter, and every load of the K loop is
 // unconditional (rows beyond M re-read row M - 1, spare loader slots re-read a valid weight row; their results are never stored): with exec-mask
 // branches around the loads the compiler's wait-count pass falls back to s_waitcnt vmcnt(0) at every join, which serialises any prefetch.
-template <int MR, int NT, int BK, int EPL, int PF, bool SPLIT>
-__global__ void __launch_bounds__(256) k_conv_gemm_h3(GemmArgs g, const _Float16* __restrict__ Wh, const _Float16* __restrict__ Wl) {
+// TAPS = the tap-reusing main loop for taps > 1 (chosen by h3_tap_reuse on the host).  k = j * cin + ci, so the present loop's K tile is one tap j and 32
+// channels of the 128 rows arow + j * dil: consecutive taps fetch, split and store almost the same rows again, 7 times per row at k = 7.  Here the channel
+// chunk is outermost: the workgroup stages its halo tile once per chunk -- every physical row p0 .. p0 + span - 1 that some (row of the tile, tap) reads,
+// gaps between segments included -- and the taps walk over it, each staging only its 96 x 32 weight tile; the A fragments of tap j are read j * dil rows
+// further down.  H3_HALO_ROWS rows of 160 B (hi + lo) + the weights' 15 360 B = 53 760 B: still 3 workgroups per CU.  The next chunk's halo loads are
+// issued during tap 0 and stored after the last tap; halo rows are clamped to the tile's last row, so nothing beyond the last row a valid output reads is touched.
+// The halo's 8 float4 prefetch slots per thread would make the allocator take 192 registers (2 waves per SIMD); amdgpu_waves_per_eu(3) holds it to 168.
+constexpr int H3_HALO_ROWS = 240;
+template <int MR, int NT, int BK, int EPL, int PF, bool SPLIT, bool TAPS = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAPS ? 3 : 1))) k_conv_gemm_h3(GemmArgs g, const _Float16* __restrict__ Wh, const _Float16* __restrict__ Wl) {
     constexpr int BM = 128 * MR, BN = 32 * NT, LD = BK + 8; // LD: padded row stride (f16); 80 / 144 B keep the b128 fragment reads conflict-free
     constexpr int KQ = BK / 4, KC = BK / 8;                  // float4 pieces of an A row, uint4 pieces of a B row per K tile
     constexpr int NA = BM * KQ / 256;
     constexpr int NB = (BN * KC + 255) / 256;
     constexpr int CLD = BN + 4;                              // row stride (floats) of the staged output tile
-    struct Stage { _Float16 Ah[BM][LD], Al[BM][LD], Bh[BN][LD], Bl[BN][LD]; };
+    constexpr int AR = TAPS ? H3_HALO_ROWS : BM;             // rows of the staged activation tile
+    constexpr int NH = (AR * KQ + 255) / 256;                // TAPS: float4 fetches of the halo tile per thread per channel chunk
+    static_assert(!TAPS || (MR == 1 && PF == 1), "the tap-reusing loop is written for the 128-row tile, one K tile in flight");
+    struct Stage { _Float16 Ah[AR][LD], Al[AR][LD], Bh[BN][LD], Bl[BN][LD]; };
     union Shared { Stage s; float Ct[EPL ? BM : 1][CLD]; };   // the finished tile reuses the operand tiles' space
     __shared__ __attribute__((aligned(16))) Shared sh;
     auto& Ah = sh.s.Ah; auto& Al = sh.s.Al; auto& Bh = sh.s.Bh; auto& Bl = sh.s.Bl;
@@ -390,55 +402,60 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h3(GemmArgs g, const _Float16
     int arow[NA];
 #pragma unroll
     for (int i = 0; i < NA; i++) { int mm = m0 + (tid + i * 256) / KQ; mm = mm < g.M ? mm : g.M - 1; arow[i] = mm + seg_of(mm, g.a_segT) * g.a_skip; }
-    struct Regs { float4 ra[NA]; uint4 rh[NB], rl[NB]; };
-    auto fetch = [&](Regs& s, int k0) {
-        const int j = k0 / g.cin, ci0 = k0 % g.cin;
+    typedef unsigned u4v __attribute__((ext_vector_type(4))); // (a native vector: copies of HIP's uint4 struct through a reference stay memcpys, i.e. scratch)
+    struct Regs { float4 ra[NA]; u4v rh[NB], rl[NB]; };
+    auto load_a = [&](size_t row, int ci) {
+        if constexpr (SPLIT) return load_a4_split_raw(g, row, ci);
+        else return *reinterpret_cast<const float4*>(g.A + row * g.lda + ci);
+    };
+    auto split_store = [&](const float4& v, int r, int c) { // 4 channels of one staged row: f32 -> hi / lo f16 (pre-split operands: a copy)
+        if constexpr (SPLIT) {
+            *reinterpret_cast<float2*>(&Ah[r][c]) = make_float2(v.x, v.y);
+            *reinterpret_cast<float2*>(&Al[r][c]) = make_float2(v.z, v.w);
+        } else {
+            const float x[4] = {v.x, v.y, v.z, v.w};
+            h4v hi, lo;
 #pragma unroll
-        for (int i = 0; i < NA; i++) {
-            const int kq = (tid + i * 256) % KQ;
-            const size_t row = (size_t)(arow[i] + j * g.dil);
-            if constexpr (SPLIT) s.ra[i] = load_a4_split_raw(g, row, ci0 + 4 * kq);
-            else s.ra[i] = *reinterpret_cast<const float4*>(g.A + row * g.lda + ci0 + 4 * kq);
+            for (int c4 = 0; c4 < 4; c4++) { hi[c4] = (_Float16)x[c4]; lo[c4] = (_Float16)(x[c4] - (float)hi[c4]); }
+            *reinterpret_cast<h4v*>(&Ah[r][c]) = hi;
+            *reinterpret_cast<h4v*>(&Al[r][c]) = lo;
         }
+    };
+    auto fetch_b = [&](u4v (&rh)[NB], u4v (&rl)[NB], int k0) {
 #pragma unroll
         for (int i = 0; i < NB; i++) {
             int e = tid + i * 256;
             e = e < BN * KC ? e : e - 256;              // spare slots of the last round re-read a valid piece (never written to LDS)
             const int r = e / KC, wk = 8 * (e % KC);
-            s.rh[i] = *reinterpret_cast<const uint4*>(Wh + (size_t)(n0 + r) * g.K + k0 + wk);
-            s.rl[i] = *reinterpret_cast<const uint4*>(Wl + (size_t)(n0 + r) * g.K + k0 + wk);
+            rh[i] = *reinterpret_cast<const u4v*>(Wh + (size_t)(n0 + r) * g.K + k0 + wk);
+            rl[i] = *reinterpret_cast<const u4v*>(Wl + (size_t)(n0 + r) * g.K + k0 + wk);
+        }
+    };
+    auto fetch = [&](Regs& s, int k0) {
+        const int j = k0 / g.cin, ci0 = k0 % g.cin;
+#pragma unroll
+        for (int i = 0; i < NA; i++) s.ra[i] = load_a((size_t)(arow[i] + j * g.dil), ci0 + 4 * ((tid + i * 256) % KQ));
+        fetch_b(s.rh, s.rl, k0);
+    };
+    auto stash_b = [&](const u4v (&rh)[NB], const u4v (&rl)[NB]) {
+#pragma unroll
+        for (int i = 0; i < NB; i++) {
+            const int e = tid + i * 256, r = e / KC, wk = 8 * (e % KC);
+            if (e < BN * KC) { *reinterpret_cast<u4v*>(&Bh[r][wk]) = rh[i]; *reinterpret_cast<u4v*>(&Bl[r][wk]) = rl[i]; }
         }
     };
     auto stash = [&](const Regs& s) {
 #pragma unroll
-        for (int i = 0; i < NA; i++) {
-            const int e = tid + i * 256, r = e / KQ, kq = e % KQ;
-            if constexpr (SPLIT) {
-                *reinterpret_cast<float2*>(&Ah[r][4 * kq]) = make_float2(s.ra[i].x, s.ra[i].y);
-                *reinterpret_cast<float2*>(&Al[r][4 * kq]) = make_float2(s.ra[i].z, s.ra[i].w);
-            } else {
-                const float x[4] = {s.ra[i].x, s.ra[i].y, s.ra[i].z, s.ra[i].w};
-                h4v hi, lo;
-#pragma unroll
-                for (int c = 0; c < 4; c++) { hi[c] = (_Float16)x[c]; lo[c] = (_Float16)(x[c] - (float)hi[c]); }
-                *reinterpret_cast<h4v*>(&Ah[r][4 * kq]) = hi;
-                *reinterpret_cast<h4v*>(&Al[r][4 * kq]) = lo;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NB; i++) {
-            const int e = tid + i * 256, r = e / KC, wk = 8 * (e % KC);
-            if (e < BN * KC) { *reinterpret_cast<uint4*>(&Bh[r][wk]) = s.rh[i]; *reinterpret_cast<uint4*>(&Bl[r][wk]) = s.rl[i]; }
-        }
+        for (int i = 0; i < NA; i++) { const int e = tid + i * 256; split_store(s.ra[i], e / KQ, 4 * (e % KQ)); }
+        stash_b(s.rh, s.rl);
     };
-    auto multiply = [&]() {
+    auto multiply = [&](int ar0) { // ar0: this lane's row of the staged activation tile (MR == 1)
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 16) {
             const int ko = kk + 8 * (lane >> 5);
             if constexpr (MR == 1) {
-                const int ar = wave * 32 + (lane & 31);
-                const h8v ah = *reinterpret_cast<const h8v*>(&Ah[ar][ko]);
-                const h8v al = *reinterpret_cast<const h8v*>(&Al[ar][ko]);
+                const h8v ah = *reinterpret_cast<const h8v*>(&Ah[ar0][ko]);
+                const h8v al = *reinterpret_cast<const h8v*>(&Al[ar0][ko]);
 #pragma unroll
                 for (int u = 0; u < NT; u++) {
                     const h8v bh = *reinterpret_cast<const h8v*>(&Bh[u * 32 + (lane & 31)][ko]);
@@ -475,32 +492,73 @@ __global__ void __launch_bounds__(256) k_conv_gemm_h3(GemmArgs g, const _Float16
     float wsc[NT]; // the weight prescale of this lane's columns (N % 96 == 0: every column exists), loaded before the K loop
 #pragma unroll
     for (int u = 0; u < NT; u++) wsc[u] = g.wscale[n0 + u * 32 + (lane & 31)];
-    Regs st[PF];
+    if constexpr (TAPS) {
+        // (ksplit == 1, taps > 1 and span <= H3_HALO_ROWS for every tile: h3_tap_reuse)
+        const int taps = g.K / g.cin, nchunk = g.cin / BK;
+        const int mlast = (m0 + BM < g.M ? m0 + BM : g.M) - 1;
+        const int p0 = m0 + seg_of(m0, g.a_segT) * g.a_skip;                                                  // first physical row of the tile
+        const int span = mlast + seg_of(mlast, g.a_segT) * g.a_skip + (taps - 1) * g.dil - p0 + 1;           // ... and how many the tile's taps reach
+        int mm = m0 + wave * 32 + (lane & 31); mm = mm < g.M ? mm : g.M - 1;
+        const int aoff = mm + seg_of(mm, g.a_segT) * g.a_skip - p0;                                           // this lane's row of the halo tile at tap 0
+        const int hr0 = tid / KQ, hc = 4 * (tid % KQ);                                                        // loader slot i: halo row hr0 + i * (256 / KQ), channels hc .. hc + 3
+        float4 ha[NH];
+        u4v wh[NB], wl[NB];
+        auto fetch_halo = [&](int ci0) { // unconditional: slots beyond the span re-read its last row
 #pragma unroll
-    for (int j = 0; j < PF; j++)
-        if (kbeg + j * BK < kend) fetch(st[j], kbeg + j * BK);
-    int k0 = kbeg;
-    // steady state: every refill is unconditional, so the wait before a stash is a counted vmcnt that leaves the other stages' loads in flight
-    // (a conditional refill makes the wait-count pass assume the worst path and drain everything)
-    for (; k0 + 2 * PF * BK <= kend; k0 += PF * BK) {
+            for (int i = 0; i < NH; i++) { const int r = hr0 + i * (256 / KQ); ha[i] = load_a((size_t)(p0 + (r < span ? r : span - 1)), ci0 + hc); }
+        };
+        auto stash_halo = [&] {
 #pragma unroll
-        for (int j = 0; j < PF; j++) {
-            stash(st[j]);
+            for (int i = 0; i < NH; i++) { const int r = hr0 + i * (256 / KQ); if (r < span) split_store(ha[i], r, hc); }
+        };
+        fetch_halo(0);
+        fetch_b(wh, wl, 0);
+        for (int c = 0; c < nchunk; c++) {
+            const int ci0 = c * BK, cnext = (c + 1 < nchunk ? c + 1 : c) * BK; // the chunk after this one (the last chunk re-reads itself)
+            stash_halo();
+            stash_b(wh, wl);
             lds_barrier();
-            fetch(st[j], k0 + (j + PF) * BK);
-            multiply();
+            fetch_halo(cnext);
+            fetch_b(wh, wl, g.cin + ci0);
+            multiply(aoff);
             lds_barrier();
+            for (int j = 1; j < taps; j++) {
+                stash_b(wh, wl);
+                lds_barrier();
+                fetch_b(wh, wl, j + 1 < taps ? (j + 1) * g.cin + ci0 : cnext); // tap 0 of the next chunk after the last tap
+                multiply(aoff + j * g.dil);
+                lds_barrier();
+            }
         }
-    }
-    for (; k0 < kend; k0 += PF * BK) { // the last tiles
+    } else {
+        const int ar0 = wave * 32 + (lane & 31);
+        Regs st[PF];
 #pragma unroll
-        for (int j = 0; j < PF; j++) {
-            if (k0 + j * BK < kend) { // (uniform)
+        for (int j = 0; j < PF; j++)
+            if (kbeg + j * BK < kend) fetch(st[j], kbeg + j * BK);
+        int k0 = kbeg;
+        // steady state: every refill is unconditional, so the wait before a stash is a counted vmcnt that leaves the other stages' loads in flight
+        // (a conditional refill makes the wait-count pass assume the worst path and drain everything)
+        for (; k0 + 2 * PF * BK <= kend; k0 += PF * BK) {
+#pragma unroll
+            for (int j = 0; j < PF; j++) {
                 stash(st[j]);
                 lds_barrier();
-                if (k0 + (j + PF) * BK < kend) fetch(st[j], k0 + (j + PF) * BK);
-                multiply();
+                fetch(st[j], k0 + (j + PF) * BK);
+                multiply(ar0);
                 lds_barrier();
+            }
+        }
+        for (; k0 < kend; k0 += PF * BK) { // the last tiles
+#pragma unroll
+            for (int j = 0; j < PF; j++) {
+                if (k0 + j * BK < kend) { // (uniform)
+                    stash(st[j]);
+                    lds_barrier();
+                    if (k0 + (j + PF) * BK < kend) fetch(st[j], k0 + (j + PF) * BK);
+                    multiply(ar0);
+                    lds_barrier();
+                }
             }
         }
     }
@@ -705,13 +763,38 @@ static const char* gemm_plan_error(const GemmArgs& g, const GemmPlan& p, size_t 
     } else if (p.red != -1) return "a reducer without split-K";
     return nullptr;
 }
+// The largest halo span of one 128-row tile of k_conv_gemm_h3: physical rows from the tile's first row at tap 0 to its last row at the last tap, the
+// a_skip history rows of every segment boundary inside the tile included.  A tile's span depends on m0 % a_segT only, which repeats every
+// a_segT / gcd(a_segT, 128) tiles, so at most that many tiles are walked (a shorter last tile never spans more than a full one at the same offset).
+static int h3_halo_span(const GemmArgs& g) {
+    const int taps = g.K / g.cin, ntiles = (g.M + 127) / 128;
+    int period = 1;
+    if (g.a_segT != SEG_NONE) { int a = g.a_segT, b = 128; while (b) { const int t = a % b; a = b; b = t; } period = g.a_segT / a; }
+    const bool whole = ntiles > period; // the first `period` tiles are full ones
+    int span = 0;
+    for (int t = 0; t < (whole ? period : ntiles); t++) {
+        const int m0 = t * 128, m1 = (whole || m0 + 128 < g.M ? m0 + 128 : g.M) - 1;
+        const int s0 = g.a_segT == SEG_NONE ? 0 : m0 / g.a_segT, s1 = g.a_segT == SEG_NONE ? 0 : m1 / g.a_segT;
+        span = std::max(span, m1 - m0 + (s1 - s0) * g.a_skip + (taps - 1) * g.dil + 1);
+    }
+    return span;
+}
+// Does an H3 / H3_EPL plan take the tap-reusing main loop?  More than one tap, no split-K (K cannot be cut by channel ranges in general) and every
+// tile's halo within the LDS budget.  Q3_CODEC_H3_TAPS=0 keeps the tap-major loop for every launch (A/B switch).
+static bool h3_tap_reuse(const GemmArgs& g, const GemmPlan& p) {
+    static const int on = [] { const char* e = std::getenv("Q3_CODEC_H3_TAPS"); return e ? atoi(e) : 1; }();
+    if (!on || (p.form != Q3TTS_GEMM_H3 && p.form != Q3TTS_GEMM_H3_EPL) || p.ks != 1 || g.cin % 32 != 0 || g.K / g.cin < 2) return false;
+    return h3_halo_span(g) <= H3_HALO_ROWS;
+}
 static void launch_gemm(hipStream_t st, const GemmArgs& g, const GemmPlan& p, const _Float16* wh, const _Float16* wl) {
     const dim3 b256(256);
     const unsigned ks = (unsigned)p.ks;
+    const bool taps = h3_tap_reuse(g, p);
 #define Q3_H(MRV, EPLV, GRID) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h<MRV, EPLV, true>), GRID, b256, 0, st, g, wh, wl); \
                                    else hipLaunchKernelGGL((k_conv_gemm_h<MRV, EPLV, false>), GRID, b256, 0, st, g, wh, wl); } while (0)
-#define Q3_H3(EPLV, PFV) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, true>), grid3, b256, 0, st, g, wh, wl); \
-                              else hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, false>), grid3, b256, 0, st, g, wh, wl); } while (0)
+#define Q3_H3T(EPLV, PFV, TAPSV) do { if (g.a_split) hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, true, TAPSV>), grid3, b256, 0, st, g, wh, wl); \
+                                      else hipLaunchKernelGGL((k_conv_gemm_h3<1, 3, 32, EPLV, PFV, false, TAPSV>), grid3, b256, 0, st, g, wh, wl); } while (0)
+#define Q3_H3(EPLV, PFV) do { if (taps) Q3_H3T(EPLV, PFV, true); else Q3_H3T(EPLV, PFV, false); } while (0)
     const dim3 grid_sk((g.N + 7) / 8), grid_t((g.N + 63) / 64, (g.M + 127) / 128, ks), grid_s((g.N + 63) / 64, (g.M + 63) / 64, ks);
     const dim3 grid3(g.N / 96, (g.M + 127) / 128, ks);
     switch (p.form) {
@@ -730,6 +813,7 @@ static void launch_gemm(hipStream_t st, const GemmArgs& g, const GemmPlan& p, co
     }
 #undef Q3_H
 #undef Q3_H3
+#undef Q3_H3T
     if (p.ks > 1) {
         const size_t n = (size_t)g.M * g.N;
         if (p.red == 1) hipLaunchKernelGGL(k_splitk_reduce4, dim3((unsigned)((n / 4 + 255) / 256)), b256, 0, st, g, p.ks);
@@ -1780,6 +1864,14 @@ void codec_gemm_plan_only(q3tts_codec_gemm_desc* d) {
     g.snake_ea = at(d->snake_ea, 0); g.snake_ib = at(d->snake_ib, 0); g.out = at(d->out, d->out_off); g.ws = at(nullptr, 0);
     const GemmPlan p = plan_gemm(g, (size_t)d->ws_floats, true);
     d->form_ran = p.form; d->ksplit_ran = p.ks; d->reducer_ran = p.red;
+}
+// the plan d asks for (AUTO: the decoder's; aligned stand-in pointers as in codec_gemm_plan_only) -> does its main loop reuse staged rows across taps?
+int codec_gemm_tap_reuse(const q3tts_codec_gemm_desc* d) {
+    Q3_CHECK(d && d->M >= 1 && d->N >= 1 && d->cin >= 1 && d->taps >= 1 && d->dil >= 1 && d->out_off >= 0, "bad codec GEMM descriptor");
+    q3tts_codec_gemm_desc c = *d;
+    if (c.form == Q3TTS_GEMM_AUTO) codec_gemm_plan_only(&c);
+    else { c.form_ran = c.form; c.ksplit_ran = c.ksplit; c.reducer_ran = c.reducer; }
+    return h3_tap_reuse(desc_args(*d), GemmPlan{c.form_ran, c.ksplit_ran, c.reducer_ran}) ? 1 : 0;
 }
 void codec_gemm_run(q3tts_codec_gemm_desc* d) {
     Q3_CHECK(d, "null codec GEMM descriptor");

@@ -86,7 +86,7 @@ SYMBOLS = [
     "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
-    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan",
+    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_codec_gemm_tap_reuse", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan",
     "q3tts_op_linear", "q3tts_linear_plan", "q3tts_argmax_key",
     "q3tts_submit_trailing_open", "q3tts_trail_append", "q3tts_trail_progress", "q3tts_submit_text_streaming_open", "q3tts_text_append",
     "q3tts_group_submit_text_streaming_open", "q3tts_group_text_append", "q3tts_group_trail_append", "q3tts_group_trail_progress",
@@ -1484,6 +1484,18 @@ def codec_gemm_plan(M, N, cin, taps=1, dil=1, lda=None, ldo=None, out_off=0, o_s
     lib().q3tts_codec_gemm_plan.argtypes = [C.POINTER(CodecGemmDesc)]
     _chk(lib().q3tts_codec_gemm_plan(C.byref(d)))
     return GEMM_FORM_NAMES[d.form_ran], d.ksplit_ran, d.reducer_ran
+
+
+def codec_gemm_tap_reuse(M, N, cin, taps=1, dil=1, lda=None, ldo=None, out_off=0, o_segT=0, o_skip=0, a_segT=0, a_skip=0, epi=EPI_NONE, ldr=0,
+                         r_segT=0, r_skip=0, a_split=False, o_split=False, ws_floats=1 << 22, form="AUTO", ksplit=1, reducer=-1):
+    """does this GEMM run k_conv_gemm_h3's tap-reusing main loop?  (host only; form AUTO: as the decoder dispatches it, else the forced form)"""
+    d = _codec_gemm_desc(M, N, cin, taps, dil, cin if lda is None else lda, 0, a_segT, a_skip, epi, ldr, 0, r_segT, r_skip,
+                         N if ldo is None else ldo, 0, out_off, o_segT, o_skip, a_split, o_split, ws_floats, form, ksplit, reducer)
+    lib().q3tts_codec_gemm_tap_reuse.argtypes = [C.POINTER(CodecGemmDesc)]
+    r = lib().q3tts_codec_gemm_tap_reuse(C.byref(d))
+    if r < 0:
+        _chk(r)
+    return bool(r)
 
 
 # codec non-GEMM kernels (include/q3tts.h Q3TTS_CK_*) and the per-stream frame limit

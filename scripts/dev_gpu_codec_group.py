@@ -1,4 +1,5 @@
-"""codec-only throughput of grouped decoding on the full-size synthetic codec: audio seconds per second for G streams x 4 frames per pass"""
+"""codec-only throughput of grouped decoding on the full-size synthetic codec: audio seconds per second for G streams x 4 frames per pass
+usage: dev_gpu_codec_group.py [MODEL_DIR [G,G,...]]   (default stream counts 1,4,16,32)"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,7 @@ if not os.path.exists(path):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
     subprocess.check_call([tool, "--out", out, "--preset", "full", "--quant", "q8_0", "--what", "4"])
 rng = np.random.default_rng(1)
-for G in (1, 4, 16, 32):
+for G in ([int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else (1, 4, 16, 32)):
     gd = Q.Decoder(path, n_streams=G, max_frames=4, max_group=G)
     for s in range(G):
         gd.reset(s)
