@@ -227,6 +227,27 @@ int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64
 int q3tts_engine_set_speech_rate(q3tts_engine* e, int32_t rate_pct);
 int q3tts_request_speech_rate(q3tts_engine* e, int64_t req_id, int32_t* rate_pct);
 int q3tts_engine_tsm_stats(q3tts_engine* e, int64_t* chunks, int64_t* frames_out, int64_t* flushes);
+/* [EXT] pitch (q3tts_spec.h "pitch"): a request's pitch is shifted on the device, behind the codec, with or without a speaking rate: the
+ * stretcher at the tempo rate / pitch and an L / M = 100 / pitch resampler behind it, in one launch.  The duration is that of the rate alone.
+ * Opt-in per request; a request with pitch 100 keeps its launches and its bytes (a rate-only one those of "speaking rate"), and codes and
+ * log-probability rows never depend on the pitch.
+ * q3tts_engine_set_pitch: requests submitted from now on, through any q3tts_submit* form with want_pcm (text, trailing, open, resume,
+ * candidates, decode), have their fundamental multiplied by pitch_pct / 100, an integer in [50, 200]; 100 = off.  Read once per request at
+ * submit and once per candidate set, together with the speaking rate.  Thread-safe; works under Q3_SPEC=ggml.  < 0: out of range, or an engine
+ * without a codec.
+ * The pair is judged at submit: rate / pitch must lie in [1/2, 2].  A request with a pitch delivers 24000 Hz, f32 or s16, and
+ * q3tts_pitch_samples(rate, pitch, max_steps * 1920, 1) samples of its encoding must fit the engine's staging for one request.  Otherwise the
+ * submit fails and nothing is queued.
+ * While it runs, N native samples have delivered q3tts_pitch_samples(rate, pitch, N, 0) samples; at its end both stages are flushed and a
+ * request of n frames delivers q3tts_pitch_samples(rate, pitch, n * 1920, 1).  A cancelled request keeps what it has and is not flushed.
+ * q3tts_poll's n_pcm and every offset, capacity and count of the fetch calls are in delivered samples.
+ * Not shifted: want_pcm = 0, q3tts_generate_batch*, scoring, preamble builds.  A primed request starts both stages from a reset.
+ * q3tts_request_pitch: the pitch a request was submitted with (100 when none was set).
+ * q3tts_engine_pitch_stats: stream chunks the shifter has taken, samples it has delivered, flushes, and the bytes of tap tables on the device
+ * (all 0 while no request had a pitch; the tables of all 151 pitches are built and uploaded once, by the first such request). */
+int q3tts_engine_set_pitch(q3tts_engine* e, int32_t pitch_pct);
+int q3tts_request_pitch(q3tts_engine* e, int64_t req_id, int32_t* pitch_pct);
+int q3tts_engine_pitch_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes);
 /* [EXT] codec preambles (q3tts_spec.h "codec preambles"): a request's codec stream starts from the state behind given frames -- a clone
  * voice's reference codes -- instead of zeros, so its first sample is already "in the voice".  The state is built once per preamble and
  * kept on the device; a primed request restores it with one device-to-device launch where the zeroing launch ran.  Opt-in; codes,
@@ -444,6 +465,8 @@ int q3tts_group_fetch_pcm16(q3tts_group* g, int64_t req_id, int16_t* out, int64_
 int q3tts_group_request_format(q3tts_group* g, int64_t req_id, q3tts_pcm_format* out);
 int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct);   /* [EXT] q3tts_engine_set_speech_rate on every engine */
 int q3tts_group_request_speech_rate(q3tts_group* g, int64_t req_id, int32_t* rate_pct);
+int q3tts_group_set_pitch(q3tts_group* g, int32_t pitch_pct);   /* [EXT] q3tts_engine_set_pitch on every engine */
+int q3tts_group_request_pitch(q3tts_group* g, int64_t req_id, int32_t* pitch_pct);
 /* [EXT] codec preambles on every engine under one id, as voices are (create preambles through the group only); _wait waits for all of them */
 int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id);
 int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms);
@@ -1016,6 +1039,31 @@ int q3tts_tsm_windows(float* w, float* w2);
 int q3tts_op_tsm(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
                  const int32_t* rate_pct, const int32_t* encoding, const int32_t* reset_before, int32_t flush, void* const* out,
                  const int64_t* out_bytes, int64_t* n_out, int32_t* const* delta_trace, const int64_t* trace_len, float* hist_store);
+
+/* [EXT] pitch (q3tts_spec.h "pitch"): the pitch shifter on the device, behind the codec.
+ * Host only, no device needed:
+ *   q3tts_pitch_samples  samples delivered for n_native native samples from a stream's reset at the pair (rate_pct, pitch_pct): ceil(480 f L / M)
+ *                        with f the stage-1 frames, #{k : a_k + 1200 <= n_native} while streaming (final = 0), ceil(pitch n_native / (480 rate))
+ *                        once flushed; < 0 for a value or the pair out of range
+ *   q3tts_pitch_plan     L / M = 100 / pitch_pct in lowest terms, the taps of the prototype and the most terms one sample sums (outputs may
+ *                        be NULL); < 0 for a pitch out of range
+ *   q3tts_pitch_filter   the normative f32 prototype h32 of pitch_pct into h32[cap]; returns its length, < 0 when cap is too small
+ * q3tts_op_pitch is the test surface of the pitch kernel: q3tts_op_tsm plus pitch_pct[G] and a second whole, guarded state store.  G streams
+ * run through n_chunks launches of the engine's launcher, one per chunk, and one more (no input, flush) when `flush` is nonzero, on a fresh
+ * shifter.  A stream with pitch 100 and a rate goes through the stretcher's launcher beside it, as in a decode pass; one with neither is
+ * copied through as native f32.
+ *   in, chunk_samples, streams, rate_pct, encoding, reset_before, out, delta_trace, hist_store   as q3tts_op_tsm's
+ *   pitch_pct     [G]
+ *   n_out[g]      the delivered samples of stream g
+ *   zhist_store   in/out, WHOLE: Q3TTS_GLUE_GUARD floats, [n_streams][64], Q3TTS_GLUE_GUARD floats
+ * Everything is checked before anything is launched; a refused call leaves every buffer unwritten. */
+int64_t q3tts_pitch_samples(int32_t rate_pct, int32_t pitch_pct, int64_t n_native, int32_t final);
+int q3tts_pitch_plan(int32_t pitch_pct, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_output);
+int64_t q3tts_pitch_filter(int32_t pitch_pct, float* h32, int64_t cap);
+int q3tts_op_pitch(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                   const int32_t* rate_pct, const int32_t* pitch_pct, const int32_t* encoding, const int32_t* reset_before, int32_t flush,
+                   void* const* out, const int64_t* out_bytes, int64_t* n_out, int32_t* const* delta_trace, const int64_t* trace_len,
+                   float* hist_store, float* zhist_store);
 
 #ifdef __cplusplus
 }

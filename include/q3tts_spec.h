@@ -493,6 +493,44 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3_TSM_MIN 50
 #define Q3_TSM_MAX 200
 
+/* ---------------- pitch [EXT] (q3tts_engine_set_pitch, q3tts_pitch_samples / _plan / _filter, q3tts_op_pitch) ----------------
+ * A pitch shift of the native 24000 Hz stream, strictly behind the codec: a time-scale change to the tempo rate / pitch ("speaking rate"
+ * with a rational tempo) followed by a resample that consumes pitch / 100 intermediate samples per delivered sample ("output formats" with a
+ * ratio that is no sample rate), inside one launch.  x[n] is the native stream, z[m] the intermediate one, y[n] the delivered one; every
+ * position is a sample index counted from the stream's reset.  The duration is that of the rate alone, the fundamental is multiplied.
+ *   pitch      P = pitch_pct, an integer percent in [Q3_PITCH_MIN, Q3_PITCH_MAX]; the delivered fundamental is P / 100 times the native one.
+ *              100 means off: nothing of this section runs, and a request with rate_pct != 100 and pitch 100 is the stretched request of
+ *              "speaking rate", bit for bit
+ *   pair       with R = rate_pct the tempo R / P must lie in [1/2, 2]: 2 R >= P and R <= 2 P.  Checked at submit, where both settings are
+ *              read together; a submit with a pair out of range fails and queues nothing
+ *   stage 1    z is y of "speaking rate" word for word with a_k = floor(k * 480 * R / P) in 64-bit integers: windows, template, candidates,
+ *              cost chain, selection order and the output rule with its clamp are unchanged, so z with P = 100 is that section's y
+ *   reach      a_k - a_{k-1} lies in [floor(480 R / P), ceil(480 R / P)], inside [240, 960] by the pair rule.  t_k = a_{k-1} + d_{k-1} + 480,
+ *              so t_k - a_k = 480 + d_{k-1} - (a_k - a_{k-1}) lies in [480 - 240 - 960, 480 + 240 - 240] = [-720, 480]: the template reads
+ *              x[a_k - 720 .. a_k + 960).  A candidate reads x[a_k - 240 .. a_k + 720) and p_k + 960 <= a_k + 1200.  Frame k therefore reads
+ *              inside [a_k - 720, a_k + 1200), Q3_TSM_HIST samples, whatever the pair
+ *   available  frame k is computed once N, the native samples seen, satisfies a_k + 1200 <= N, which suffices by the reach.  While streaming, N
+ *              samples have made #{k : a_k + 1200 <= N} frames: 0 for N < 1200, else (P (N - 1199) - 1) div (480 R) + 1.  Once flushed
+ *              (x[n >= N] = 0, every frame with a_k < N): ceil(P N / (480 R)) frames
+ *   history    the next frame k to make has a_k + 1200 > N and reaches back to a_k - 720 > N - 1920 at most: the last Q3_TSM_HIST native
+ *              samples per stream, d of the last frame and the two counters (N, frames made) are stage 1's whole state, as in "speaking rate"
+ *   stage 2    g = gcd(100, P), L = 100 / g, M = P / g, F = max(L, M), Z = Q3_PCM_FILTER_Z, N_taps = 2 Z F + 1, fc = 0.9 / (2F), and h32 the
+ *              prototype of "output formats" for this (L, M): h[i] = L * 2fc * sinc(2fc (i - Z F)) * kaiser_9(i), in double, rounded to f32.
+ *              Output sample n: t = n M, p = t mod L, j = t div L, y[n] = sum over k = 0, 1, ... with p + k L < N_taps of
+ *              h32[p + k L] * z[j - k], z[< 0] = 0; one f32 accumulator from +0, k ascending, one fmaf per term; clamped to [-1, 1].
+ *              s16 is (int16) rintf(y * 32767.0f) of the clamped value
+ *   counts     Nz intermediate samples give exactly ceil(Nz L / M) delivered samples: y[n] needs z[j] and nothing later.  The phase is a pure
+ *              function of n, so the delivered stream does not depend on how the native stream was cut into chunks
+ *   delay      Z F / L intermediate samples, at most 32; as with the formats nothing is flushed for it
+ *   state      stage 1's state, the last Q3_PITCH_HIST samples of z (one output reaches back 2 Z F / L <= 64) and the two data-independent
+ *              counters (Nz, outputs made), which live on the host as the stretcher's do
+ *   flush      at the end of an utterance stage 1 is flushed as in "speaking rate" and stage 2 delivers ceil(Nz_final L / M) in all.  A
+ *              cancelled request is not flushed
+ * A request with a pitch delivers 24000 Hz, f32 or s16; a pitch combined with a resampled format is not defined. */
+#define Q3_PITCH_MIN 50
+#define Q3_PITCH_MAX 200
+#define Q3_PITCH_HIST 64         /* intermediate samples of history per stream */
+
 /* ---------------- prompt stems [EXT] (q3tts_stem_*, q3tts_op_kv_stem) ----------------
  * A stem is n rows [n][2048] f32, 1 <= n < max_prompt, together with the talker K/V of those rows at positions 0 .. n-1: the head a voice's
  * prompts share, prefilled once, kept on the device in a store of its own (ceil(n / 64) whole pages per plane, the pool's page layout) and

@@ -400,6 +400,22 @@ int q3tts_engine_tsm_stats(q3tts_engine* e, int64_t* chunks, int64_t* frames_out
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] pitch */
+int q3tts_engine_set_pitch(q3tts_engine* e, int32_t pitch_pct) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_pitch(pitch_pct); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_pitch(q3tts_engine* e, int64_t id, int32_t* pitch_pct) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && pitch_pct, "null argument");
+    *pitch_pct = e->e->request_pitch(id);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_pitch_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && chunks && samples_out && flushes && table_bytes, "null argument");
+    e->e->pitch_stats(chunks, samples_out, flushes, table_bytes);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

@@ -7,6 +7,8 @@
 #include "kernels.h"
 #include "pcm_out.h"
 #include "tsm.h"
+#include "pitch.h"
+#include <memory>
 #include "mel.h"
 
 using namespace q3;
@@ -1336,6 +1338,127 @@ int q3tts_op_tsm(const float* in, int32_t G, const int32_t* chunk_samples, int32
         n_out[g] = bytes[g] / esz[g];
     }
     d_hist.download(hist_store, hist_n);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] pitch: the host-only half (sched_logic.h, pitch.h) */
+int64_t q3tts_pitch_samples(int32_t rate_pct, int32_t pitch_pct, int64_t n_native, int32_t final) { return pitch_out_samples(rate_pct, pitch_pct, n_native, final != 0); }
+int q3tts_pitch_plan(int32_t pitch_pct, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_output) {
+    PitchPlan p;
+    if (!pitch_plan(pitch_pct, &p)) { set_last_error("pitch out of range [50, 200]"); return Q3TTS_ERR; }
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (n_taps) *n_taps = p.n_taps;
+    if (taps_per_output) *taps_per_output = p.taps_per_output;
+    return Q3TTS_OK;
+}
+int64_t q3tts_pitch_filter(int32_t pitch_pct, float* h32, int64_t cap) {
+    Q3_API_BEGIN
+    const std::vector<float> h = pitch_filter(pitch_pct);
+    Q3_CHECK(!h.empty(), "pitch out of range [50, 200]");
+    Q3_CHECK(h32 && cap >= (int64_t)h.size(), "filter buffer too small or missing");
+    std::copy(h.begin(), h.end(), h32);
+    return (int64_t)h.size();
+    Q3_API_END(-1)
+}
+
+/* [EXT] the pitch kernel over guarded host buffers (include/q3tts.h): per chunk one launch_tsm_pitch and, when a stream has a rate alone, one
+ * launch_tsm_stretch over the same history store, as a decode pass runs them; one more of each for the flush.  Each stream's samples are
+ * appended behind its earlier ones inside its guarded buffer on the device, everything downloaded whole. */
+int q3tts_op_pitch(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                   const int32_t* rate_pct, const int32_t* pitch_pct, const int32_t* encoding, const int32_t* reset_before, int32_t flush,
+                   void* const* out, const int64_t* out_bytes, int64_t* n_out, int32_t* const* delta_trace, const int64_t* trace_len,
+                   float* hist_store, float* zhist_store) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(in && chunk_samples && streams && rate_pct && pitch_pct && encoding && out && out_bytes && n_out && delta_trace && trace_len && hist_store && zhist_store, "null argument");
+    Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
+    // every chunk is checked as its launch will be, and every count is worked out as the launchers will, before anything is allocated
+    int64_t in_floats = 0;
+    for (int c = 0; c < n_chunks; c++) {
+        if (const char* why = pitch_launch_refusal(G, G, chunk_samples[c], false, streams + (size_t)c * G, n_streams, rate_pct, pitch_pct, encoding)) throw Error(std::string("tsm pitch: ") + why);
+        in_floats += (int64_t)G * chunk_samples[c];
+    }
+    std::vector<int32_t> kind(G), tpct(G, 100);   // 0 native, 1 a rate alone (the stretcher's), 2 a pitch (the shifter's)
+    bool any_rate = false;
+    for (int g = 0; g < G; g++) {
+        kind[g] = pitch_pct[g] != 100 ? 2 : (rate_pct[g] != 100 ? 1 : 0);
+        if (kind[g] == 1) { tpct[g] = rate_pct[g]; any_rate = true; }
+    }
+    std::vector<int64_t> seen((size_t)n_streams, 0), done((size_t)n_streams, 0), frames(G, 0), need(G, 0), esz(G), reg(G), treg(G);
+    for (int c = 0; c <= n_chunks; c++) {
+        if (c == n_chunks && !flush) break;
+        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;   // the flush follows the last chunk's slots
+        const int64_t T = c < n_chunks ? chunk_samples[c] : 0;
+        for (int g = 0; g < G; g++) {
+            int64_t& sn = seen[(size_t)sl[g]]; int64_t& dn = done[(size_t)sl[g]];
+            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) sn = dn = 0;
+            if (kind[g] == 0) { need[g] += T; continue; }
+            const int64_t total = std::max<int64_t>(kind[g] == 2 ? pitch_frames(rate_pct[g], pitch_pct[g], sn + T, c == n_chunks) : tsm_frames(rate_pct[g], sn + T, c == n_chunks), dn);
+            if (kind[g] == 2) {
+                PitchPlan p;
+                pitch_plan(pitch_pct[g], &p);
+                need[g] += pitch_samples_of_z(p, total * Q3_TSM_HOP) - pitch_samples_of_z(p, dn * Q3_TSM_HOP);
+            } else need[g] += (total - dn) * Q3_TSM_HOP;
+            frames[g] += total - dn; sn += T; dn = total;
+        }
+    }
+    int64_t total = 0, ttotal = 0;
+    for (int g = 0; g < G; g++) {
+        esz[g] = kind[g] != 0 && encoding[g] == Q3_PCM_S16 ? 2 : 4;   // a native stream is copied through as f32
+        need[g] *= esz[g];
+        Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
+        Q3_CHECK(delta_trace[g] && trace_len[g] >= frames[g] + 2 * Q3TTS_GLUE_GUARD, "guarded trace buffer too small or missing");
+        reg[g] = total; total += (out_bytes[g] + 255) / 256 * 256;
+        treg[g] = ttotal; ttotal += (trace_len[g] + 63) / 64 * 64;
+    }
+    DevBuf<uint8_t> d_out((size_t)total);
+    DevBuf<int32_t> d_trace((size_t)ttotal);
+    for (int g = 0; g < G; g++) {
+        Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
+        Q3_HIP(hipMemcpy(d_trace.p + treg[g], delta_trace[g], (size_t)trace_len[g] * 4, hipMemcpyHostToDevice));
+    }
+    DevBuf<float> d_in((size_t)std::max<int64_t>(in_floats, 1)); d_in.upload(in, (size_t)in_floats);
+    const size_t hist_n = (size_t)n_streams * Q3_TSM_HIST + 2 * Q3TTS_GLUE_GUARD, zhist_n = (size_t)n_streams * Q3_PITCH_HIST + 2 * Q3TTS_GLUE_GUARD;
+    DevBuf<float> d_hist(hist_n), d_zhist(zhist_n); d_hist.upload(hist_store, hist_n); d_zhist.upload(zhist_store, zhist_n);
+    PitchShifter ps(n_streams, G);
+    ps.hist = d_hist.p + Q3TTS_GLUE_GUARD; ps.zhist = d_zhist.p + Q3TTS_GLUE_GUARD;
+    std::unique_ptr<TsmStretcher> ts;
+    if (any_rate) { ts.reset(new TsmStretcher(n_streams, G)); ts->hist = ps.hist; }
+    std::vector<int64_t> off(G), toff(G), bytes(G, 0), fr(G, 0), cnt(G), pcnt(G);
+    const float* x = d_in.p;
+    for (int c = 0; c <= n_chunks; c++) {
+        if (c == n_chunks && !flush) break;
+        const int T = c < n_chunks ? chunk_samples[c] : 0;
+        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;
+        for (int g = 0; g < G; g++) {
+            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) { ps.reset_async(0, sl[g]); if (ts) ts->reset_async(0, sl[g]); }
+            off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + bytes[g];
+            toff[g] = treg[g] + Q3TTS_GLUE_GUARD + fr[g];
+            cnt[g] = pcnt[g] = 0;
+        }
+        std::vector<int64_t> kd0(G), td0(G);
+        for (int g = 0; g < G; g++) { kd0[g] = ps.k_done[(size_t)sl[g]]; td0[g] = ts ? ts->k_done[(size_t)sl[g]] : 0; }
+        launch_tsm_pitch(0, ps, x, G, T, c == n_chunks, sl, rate_pct, pitch_pct, encoding, d_out.p, off.data(), pcnt.data(), d_trace.p, toff.data());
+        if (ts) launch_tsm_stretch(0, *ts, x, G, T, c == n_chunks, sl, tpct.data(), encoding, d_out.p, off.data(), cnt.data(), d_trace.p, toff.data());
+        for (int g = 0; g < G; g++) {
+            if (kind[g] == 0 && T > 0) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
+            if (kind[g] == 0) bytes[g] += (int64_t)T * 4;
+            else if (kind[g] == 1) { bytes[g] += cnt[g] * esz[g]; fr[g] += ts->k_done[(size_t)sl[g]] - td0[g]; }
+            else { bytes[g] += pcnt[g] * esz[g]; fr[g] += ps.k_done[(size_t)sl[g]] - kd0[g]; }
+        }
+        x += (size_t)G * T;
+    }
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    for (int g = 0; g < G; g++) {
+        Q3_CHECK(bytes[g] == need[g], "the launchers' counts differ from the plan");
+        Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
+        Q3_HIP(hipMemcpy(delta_trace[g], d_trace.p + treg[g], (size_t)trace_len[g] * 4, hipMemcpyDeviceToHost));
+        n_out[g] = bytes[g] / esz[g];
+    }
+    d_hist.download(hist_store, hist_n); d_zhist.download(zhist_store, zhist_n);
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

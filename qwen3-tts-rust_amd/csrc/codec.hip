@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "pcm_out.h"
 #include "tsm.h"
+#include "pitch.h"
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -1200,6 +1201,23 @@ struct CodecDecoder::Impl {
     }
     void tsm_reset(hipStream_t st, int s) { if (tsm) { tsm->reset_async(st, s); tsm_pct[(size_t)s] = 0; } }
     void tsm_count(int64_t c0, int64_t f0, int64_t l0) { tsm_chunks += tsm->chunks - c0; tsm_frames += tsm->frames_out - f0; tsm_flushes += tsm->flushes - l0; }
+    // [EXT] pitch: made by the first call that shifts -- the decoder thread, which owns the codec's streams -- under capture_mutex(): all 151 tap
+    // tables are built and uploaded there, once.  pitch_out[lane] = the delivered samples of each stream of a pass, region g of tsm_region()
+    // floats (a chunk delivers at most 2 T + 961 samples, a flush at most 3361).  pitch_R / pitch_P / pitch_enc = what a stream was last shifted
+    // with since its reset (pitch_P 0: it was not), which is what its flush runs with
+    std::unique_ptr<PitchShifter> pitch; std::vector<DevBuf<float>> pitch_out; std::vector<int32_t> pitch_R, pitch_P, pitch_enc;
+    std::atomic<int64_t> pitch_chunks{0}, pitch_samples{0}, pitch_flushes{0}, pitch_table_bytes{0};
+    void ensure_pitch() {
+        if (pitch) return;
+        std::lock_guard<std::mutex> cap(capture_mutex());
+        pitch_out.resize(lanes.size());
+        for (auto& b : pitch_out) b.alloc((size_t)gmax * tsm_region());
+        pitch_R.assign((size_t)n_streams, 0); pitch_P.assign((size_t)n_streams, 0); pitch_enc.assign((size_t)n_streams, 0);
+        pitch.reset(new PitchShifter(n_streams, gmax));
+        pitch_table_bytes = pitch->table_bytes;
+    }
+    void pitch_reset(hipStream_t st, int s) { if (pitch) { pitch->reset_async(st, s); pitch_P[(size_t)s] = 0; } }
+    void pitch_count(int64_t c0, int64_t s0, int64_t l0) { pitch_chunks += pitch->chunks - c0; pitch_samples += pitch->samples_out - s0; pitch_flushes += pitch->flushes - l0; }
     // [EXT] codec preambles: the snapshot store.  A slot holds one stream's histories back to back in all_ext order (the shape of one stream's
     // share of the history stores) and the two host counters as they stood when the snapshot was enqueued.  A slot's buffer is allocated by the
     // first snapshot that takes it, under capture_mutex(), and kept for the next one; snap_mu guards the table (a slot may be freed by
@@ -1492,7 +1510,12 @@ void CodecDecoder::reset(int s) {
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
     if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
     if (m.tsm) { m.tsm_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
+    if (m.pitch) { m.pitch_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
     m.kv_len[s] = 0; m.n_seen[s] = 0;
+}
+void CodecDecoder::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
+    *chunks = impl_->pitch_chunks.load(); *samples_out = impl_->pitch_samples.load(); *flushes = impl_->pitch_flushes.load();
+    *table_bytes = impl_->pitch_table_bytes.load();
 }
 void CodecDecoder::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
     *chunks = impl_->tsm_chunks.load(); *frames_out = impl_->tsm_frames.load(); *flushes = impl_->tsm_flushes.load();
@@ -1580,6 +1603,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     flush();
     if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
     m.tsm_reset(st, s);                     // and so is the stretcher's state
+    m.pitch_reset(st, s);                   // and the pitch shifter's
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1631,6 +1655,7 @@ void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* p
         Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
     }
     m.tsm_reset(st, s); // [EXT] speaking rate: a primed stream's stretcher starts from a reset
+    m.pitch_reset(st, s); // [EXT] pitch: and both stages of its pitch shifter
     m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
 }
 void CodecDecoder::snapshot_free(int snap) {
@@ -1654,7 +1679,7 @@ int CodecDecoder::decode_async(hipStream_t st, int s, const int64_t* codes, int 
 // One pass for G streams that each contribute n_frames new frames: every GEMM runs over G*T rows, so the 733 MB of
 // codec weights are streamed once per group instead of once per stream, and one set of launches serves the group.
 int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane,
-                                     const q3tts_pcm_format* fmt, int64_t* n_out, const int32_t* rate) {
+                                     const q3tts_pcm_format* fmt, int64_t* n_out, const int32_t* rate, const int32_t* pitch) {
     Impl& m = *impl_;
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     Q3_CHECK(G >= 1 && G <= m.gmax, "group size out of range");
@@ -1762,7 +1787,9 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
-    bool converts = false, stretches = false;
+    bool converts = false, stretches = false, shifts = false;
+    for (int g = 0; pitch && g < G; g++) shifts = shifts || pitch[g] != 100;
+    if (shifts) return decode_group_tail_pitch(st, G, streams, T, pcm, lane, fmt, n_out, rate, pitch);   // [EXT] pitch: a pass without one runs what follows, as it did
     for (int g = 0; rate && g < G; g++) stretches = stretches || rate[g] != 100;
     for (int g = 0; fmt && g < G; g++) converts = converts || (!pcm_format_native(fmt[g]) && !(rate && rate[g] != 100));
     if (!converts && !stretches) {
@@ -1811,6 +1838,69 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     return T;
 }
 
+// [EXT] pitch: what follows the output conv in a pass that holds a stream with a pitch.  The streams are of four kinds -- native, converted
+// (the converter's), rate-only (the stretcher's) and pitched (the shifter's) -- and each stage sees the streams of the other stages as ones it
+// leaves alone; a stage nobody needs is not launched.  Then every stream's bytes go out from where its stage left them
+int CodecDecoder::decode_group_tail_pitch(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt,
+                                          int64_t* n_out, const int32_t* rate, const int32_t* pitch) {
+    Impl& m = *impl_;
+    const q3tts_pcm_format native{Q3_PCM_NATIVE_RATE, Q3_PCM_F32};
+    std::vector<q3tts_pcm_format> cf((size_t)G, native);
+    std::vector<int32_t> pct((size_t)G, 100), pr((size_t)G, 100), pp((size_t)G, 100), enc((size_t)G, Q3_PCM_F32);
+    bool converts = false, stretches = false;
+    for (int g = 0; g < G; g++) {
+        const bool pitched = pitch[g] != 100, rated = !pitched && rate && rate[g] != 100;
+        if (pitched || rated) {
+            Q3_CHECK(!fmt || fmt[g].sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate or a pitch needs the 24000 Hz output format");
+            enc[(size_t)g] = fmt ? fmt[g].encoding : Q3_PCM_F32;
+            if (pitched) { pr[(size_t)g] = rate ? rate[g] : 100; pp[(size_t)g] = pitch[g]; }
+            else { pct[(size_t)g] = rate[g]; stretches = true; }
+        } else if (fmt) { cf[(size_t)g] = fmt[g]; converts = converts || !pcm_format_native(fmt[g]); }
+    }
+    std::vector<int64_t> cnt((size_t)G, T), tcnt((size_t)G, T), pcnt((size_t)G, T), toff((size_t)G);
+    Q3_CHECK(2 * (size_t)T + 3 * Q3_TSM_HOP <= m.tsm_region(), "chunk too long for the stretcher's buffers");
+    for (int g = 0; g < G; g++) toff[(size_t)g] = (int64_t)((size_t)g * m.tsm_region() * sizeof(float));
+    if (converts) {
+        m.ensure_conv();
+        const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
+        launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, cf.data(), m.pcm_out[lane].p, nullptr, cnt.data());
+        Q3_LAUNCH_CHECK();
+        m.conv_chunks += m.conv->chunks_converted - c0; m.conv_samples += m.conv->samples_out - s0;
+    }
+    if (stretches) {
+        m.ensure_tsm();
+        const int64_t c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;
+        launch_tsm_stretch(st, *m.tsm, m.S->pcm.p, G, T, false, streams, pct.data(), enc.data(), m.tsm_out[lane].p, toff.data(), tcnt.data());
+        Q3_LAUNCH_CHECK();
+        m.tsm_count(c0, f0, l0);
+    }
+    {
+        m.ensure_pitch();
+        const int64_t c0 = m.pitch->chunks, s0 = m.pitch->samples_out, l0 = m.pitch->flushes;
+        launch_tsm_pitch(st, *m.pitch, m.S->pcm.p, G, T, false, streams, pr.data(), pp.data(), enc.data(), m.pitch_out[lane].p, toff.data(), pcnt.data());
+        Q3_LAUNCH_CHECK();
+        m.pitch_count(c0, s0, l0);
+    }
+    for (int g = 0; g < G; g++) {
+        const size_t sb = enc[(size_t)g] == Q3_PCM_S16 ? 2 : 4;
+        if (pp[(size_t)g] != 100) {
+            m.pitch_R[(size_t)streams[g]] = pr[(size_t)g]; m.pitch_P[(size_t)streams[g]] = pp[(size_t)g]; m.pitch_enc[(size_t)streams[g]] = enc[(size_t)g];
+            cnt[(size_t)g] = pcnt[(size_t)g];
+            Q3_CHECK((size_t)cnt[(size_t)g] <= m.tsm_region(), "a pass delivered more than the shifter's buffer holds");
+            if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], m.pitch_out[lane].p + (size_t)g * m.tsm_region(), (size_t)cnt[(size_t)g] * sb, hipMemcpyDeviceToHost, st));
+        }
+        else if (pct[(size_t)g] != 100) {
+            m.tsm_pct[(size_t)streams[g]] = pct[(size_t)g]; m.tsm_enc[(size_t)streams[g]] = enc[(size_t)g];
+            cnt[(size_t)g] = tcnt[(size_t)g];
+            if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], m.tsm_out[lane].p + (size_t)g * m.tsm_region(), (size_t)cnt[(size_t)g] * sb, hipMemcpyDeviceToHost, st));
+        }
+        else if (pcm_format_native(cf[(size_t)g])) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+        else Q3_HIP(hipMemcpyAsync(pcm[g], m.pcm_out[lane].p + (size_t)g * T, (size_t)cnt[(size_t)g] * (cf[(size_t)g].encoding == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+        if (n_out) n_out[g] = cnt[(size_t)g];
+    }
+    return T;
+}
+
 // [EXT] speaking rate: the end of a stretched utterance.  The stream's input ends in zeros and every frame with a_k < N comes out: one launch
 // without input, then the copy of its hops to dst (pinned).  A stream that was not stretched since its reset gives nothing
 void CodecDecoder::tsm_flush_async(hipStream_t st, int s, void* dst, int64_t* n_out, int lane) {
@@ -1818,6 +1908,17 @@ void CodecDecoder::tsm_flush_async(hipStream_t st, int s, void* dst, int64_t* n_
     Q3_CHECK(s >= 0 && s < m.n_streams && n_out, "stream out of range");
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     *n_out = 0;
+    if (m.pitch && m.pitch_P[(size_t)s] != 0) { // [EXT] pitch: the stream is the shifter's; stage 1 is flushed and stage 2 delivers what that completes
+        const int32_t sl = s, R = m.pitch_R[(size_t)s], P = m.pitch_P[(size_t)s], enc = m.pitch_enc[(size_t)s];
+        const int64_t off = 0, c0 = m.pitch->chunks, s0 = m.pitch->samples_out, l0 = m.pitch->flushes;
+        launch_tsm_pitch(st, *m.pitch, nullptr, 1, 0, true, &sl, &R, &P, &enc, m.pitch_out[lane].p, &off, n_out);
+        Q3_LAUNCH_CHECK();
+        m.pitch_count(c0, s0, l0);
+        Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the shifter's buffer");
+        if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, m.pitch_out[lane].p, (size_t)*n_out * (enc == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+        m.pitch_P[(size_t)s] = 0; // flushed: the stream is reset before it is used again
+        return;
+    }
     if (!m.tsm || m.tsm_pct[(size_t)s] == 0) return;
     const int32_t sl = s, pct = m.tsm_pct[(size_t)s], enc = m.tsm_enc[(size_t)s];
     const int64_t off = 0, c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;

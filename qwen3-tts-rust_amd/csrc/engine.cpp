@@ -217,6 +217,13 @@ struct Engine::Req {
     // [EXT] speaking rate: the percent the request is spoken at, read at submit (100: off).  pcm_enq / pcm_ready / pcm_n count the samples
     // delivered; tsm_native = the native samples its stream has been given (decoder thread)
     int rate_pct = 100; int64_t tsm_native = 0;
+    // [EXT] pitch: the percent the request's pitch is shifted to, read with the rate at submit (100: off).  With a pitch the delivered counts are
+    // pitch_out_samples(rate_pct, pitch_pct, tsm_native, .) and the stream is the pitch shifter's, not the stretcher's
+    int pitch_pct = 100;
+    bool stretched() const { return rate_pct != 100 || pitch_pct != 100; }
+    int64_t prosody_samples(int64_t n_native, bool final) const {
+        return pitch_pct != 100 ? pitch_out_samples(rate_pct, pitch_pct, n_native, final) : tsm_out_samples(rate_pct, n_native, final);
+    }
     bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
     // [EXT] codec preambles: the preamble the request is primed with (-1: none; kept for request_preamble after the end), whether it still
@@ -723,14 +730,15 @@ void Engine::decoder_main() {
                 std::vector<int64_t> codes((size_t)G * nf * 16);
                 std::vector<q3tts_pcm_format> fmt(G); std::vector<int64_t> n_out(G); bool converts = false; // [EXT] output formats
                 std::vector<int32_t> rate(G); bool stretches = false;                                       // [EXT] speaking rate
+                std::vector<int32_t> pitch(G); bool shifts = false;                                         // [EXT] pitch
                 for (int g = 0; g < G; g++) {
                     Req* r = grp[g].r;
                     fmt[g] = r->fmt; converts = converts || !pcm_format_native(r->fmt);
                     size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
-                    rate[g] = r->rate_pct;
-                    if (r->rate_pct != 100) { // the hops that become available with these frames: possibly none, at a slow rate more than native
-                        stretches = converts = true;
-                        add = (size_t)(tsm_out_samples(r->rate_pct, r->tsm_native + (int64_t)nf * spf, false) - tsm_out_samples(r->rate_pct, r->tsm_native, false)) * r->sample_bytes();
+                    rate[g] = r->rate_pct; pitch[g] = r->pitch_pct;
+                    if (r->stretched()) { // the samples that become available with these frames: possibly none, at a slow rate more than native
+                        stretches = converts = true; shifts = shifts || r->pitch_pct != 100;
+                        add = (size_t)(r->prosody_samples(r->tsm_native + (int64_t)nf * spf, false) - r->prosody_samples(r->tsm_native, false)) * r->sample_bytes();
                         r->tsm_native += (int64_t)nf * spf;
                     }
                     streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(pcm_stage(*r, add));
@@ -738,15 +746,15 @@ void Engine::decoder_main() {
                 }
                 // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
                 const int got = codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane,
-                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr, stretches ? rate.data() : nullptr);
+                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr, stretches ? rate.data() : nullptr, shifts ? pitch.data() : nullptr);
                 for (int g = 0; g < G; g++) grp[g].r->pcm_enq += converts ? (size_t)n_out[g] : (size_t)std::max(got, 0);
             }
             // [EXT] speaking rate: the fence of a stretching request that was not cancelled flushes its stretcher -- the hops its last samples
             // still owe -- behind its last chunk (this lane has waited for it above), before the fence's completion is recorded
             for (auto& t : grp) {
                 Req* r = t.r;
-                if (!t.fence || r->rate_pct == 100 || r->cancel || r->cs < 0) continue;
-                const size_t add = (size_t)(tsm_out_samples(r->rate_pct, r->tsm_native, true) - tsm_out_samples(r->rate_pct, r->tsm_native, false)) * r->sample_bytes();
+                if (!t.fence || !r->stretched() || r->cancel || r->cs < 0) continue;
+                const size_t add = (size_t)(r->prosody_samples(r->tsm_native, true) - r->prosody_samples(r->tsm_native, false)) * r->sample_bytes();
                 int64_t n = 0;
                 codec_->tsm_flush_async(st2_[lane], r->cs, pcm_stage(*r, add), &n, lane);
                 r->pcm_enq += (size_t)n;
@@ -970,7 +978,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->shared = sh;
         r->want_pcm = want_pcm && codec_;
         if (r->want_pcm) r->fmt = set_fmt;
-        if (r->want_pcm) take_rate(r.get(), g.max_steps, i == 0 ? -1 : rs[0]->rate_pct); // [EXT] the speech rate, read once per set
+        if (r->want_pcm) take_rate(r.get(), g.max_steps, i == 0 ? -1 : rs[0]->rate_pct, i == 0 ? -1 : rs[0]->pitch_pct); // [EXT] the speech rate and the pitch, read once per set
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
@@ -1653,11 +1661,21 @@ void Engine::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) cons
 void Engine::set_speech_rate(int pct) {
     Q3_CHECK(codec_, "the engine has no codec");
     if (const char* why = tsm_rate_why_not(pct)) throw Error(why);
+    std::lock_guard<std::mutex> lk(prosody_mu_);
     rate_pct_ = pct;
 }
 // the engine's rate (or `given`, the one a candidate set's first member read) becomes the request's, if the request's format and length allow it
-void Engine::take_rate(Req* r, int max_steps, int given) const {
-    const int pct = given >= 0 ? given : rate_pct_.load();
+void Engine::take_rate(Req* r, int max_steps, int given, int given_pitch) const {
+    int pct, pitch;
+    {   // [EXT] pitch: the two settings are read together, so that the pair rule judges a pair somebody set
+        std::lock_guard<std::mutex> lk(prosody_mu_);
+        pct = given >= 0 ? given : rate_pct_.load(); pitch = given_pitch >= 0 ? given_pitch : pitch_pct_.load();
+    }
+    if (pitch != 100) {
+        if (const char* why = pitch_submit_refusal(pct, pitch, r->fmt, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
+        r->rate_pct = pct; r->pitch_pct = pitch;
+        return;
+    }
     if (pct == 100) return;
     if (const char* why = tsm_submit_refusal(pct, r->fmt, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
     r->rate_pct = pct;
@@ -1665,6 +1683,21 @@ void Engine::take_rate(Req* r, int max_steps, int given) const {
 int Engine::request_speech_rate(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
     return req(id).rate_pct;
+}
+// [EXT] pitch (q3tts_spec.h "pitch")
+void Engine::set_pitch(int pct) {
+    Q3_CHECK(codec_, "the engine has no codec");
+    if (const char* why = pitch_why_not(pct)) throw Error(why);
+    std::lock_guard<std::mutex> lk(prosody_mu_);
+    pitch_pct_ = pct;
+}
+int Engine::request_pitch(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return req(id).pitch_pct;
+}
+void Engine::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
+    *chunks = *samples_out = *flushes = *table_bytes = 0;
+    if (codec_) codec_->pitch_stats(chunks, samples_out, flushes, table_bytes);
 }
 void Engine::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
     *chunks = *frames_out = *flushes = 0;

@@ -122,6 +122,13 @@ public:
     void set_speech_rate(int pct);
     int request_speech_rate(int64_t id);
     void tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const; // stream chunks stretched, synthesis frames made, flushes
+    // [EXT] pitch (q3tts_spec.h "pitch"): requests submitted from now on with want_pcm have their pitch shifted to pct percent (100: off), with
+    // or without a rate; read with the rate, once per request at submit and once per candidate set, wherever the rate is read.  Thread-safe, no
+    // HIP calls; throws for a pitch outside [50, 200] or an engine without a codec.  The pair is judged at submit: a submit throws
+    // pitch_submit_refusal's reason before anything is queued
+    void set_pitch(int pct);
+    int request_pitch(int64_t id);
+    void pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const; // stream chunks shifted, samples delivered, flushes, bytes of tap tables on the device
     // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
     // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
     // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The
@@ -253,7 +260,9 @@ private:
     static q3tts_pcm_format unpack_fmt(int64_t v) { return q3tts_pcm_format{(int32_t)(v / 4), (int32_t)(v % 4)}; }
     std::atomic<int64_t> out_fmt_{(int64_t)Q3_PCM_NATIVE_RATE * 4 + Q3_PCM_F32}; // what submit() reads
     std::atomic<int> rate_pct_{100};                                             // [EXT] speaking rate: what submit() reads
-    void take_rate(Req* r, int max_steps, int given = -1) const;
+    std::atomic<int> pitch_pct_{100};                                            // [EXT] pitch: what submit() reads, with rate_pct_ under prosody_mu_
+    mutable std::mutex prosody_mu_;
+    void take_rate(Req* r, int max_steps, int given = -1, int given_pitch = -1) const;
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).

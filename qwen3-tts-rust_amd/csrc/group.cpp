@@ -419,6 +419,11 @@ int q3tts_group_set_output_format(q3tts_group* g, const q3tts_pcm_format* f) {
     if (g && f && q3tts_pcm_format_check(f) != Q3TTS_OK) return Q3TTS_ERR;
     return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_output_format(e, f); });
 }
+int q3tts_group_request_pitch(q3tts_group* g, int64_t req_id, int32_t* pitch_pct) { return routed(g, req_id, q3tts_request_pitch, pitch_pct); }
+int q3tts_group_set_pitch(q3tts_group* g, int32_t pitch_pct) { // [EXT] q3tts_engine_set_pitch on every engine: all of them or none
+    if (g && q3tts_pitch_plan(pitch_pct, nullptr, nullptr, nullptr, nullptr) != Q3TTS_OK) { set_last_error("pitch out of range [50, 200]"); return Q3TTS_ERR; }
+    return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_pitch(e, pitch_pct); });
+}
 int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) {
     if (g && q3tts_tsm_samples(rate_pct, 0, 0) < 0) { set_last_error("speech rate out of range [50, 200]"); return Q3TTS_ERR; }
     return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_speech_rate(e, rate_pct); });

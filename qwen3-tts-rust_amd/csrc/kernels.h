@@ -394,4 +394,44 @@ void launch_tsm_stretch(hipStream_t st, TsmStretcher& s, const float* in, int G,
                         const int32_t* enc, void* out, const int64_t* out_off, int64_t* n_out, int32_t* trace = nullptr,
                         const int64_t* trace_off = nullptr);
 
+// [EXT] pitch (pitch.hip, q3tts_spec.h "pitch"): the stretcher at the rational tempo R / P and the L / M resampler behind it, in one launch.
+// One entry per stream of a launch, written by launch_tsm_pitch into the shifter's upload ring.  As with the stretcher every count is
+// data-independent: the host keeps the counters and hands the kernel what it derived from them.
+struct PitchStreamMeta {
+    int32_t enc;              // Q3_PCM_F32 / Q3_PCM_S16; -1: the stream has no pitch, its workgroup exits at once
+    int32_t slot, R, P;       // state store entry; the rate and the pitch
+    int32_t L, M, n_taps;     // 100 / P in lowest terms and the taps of its prototype
+    int32_t tab_off;          // first float of the pitch's h32 in the shifter's tables
+    int32_t n_frames, pad;    // stage-1 frames this launch makes: k0 .. k0 + n_frames - 1
+    int64_t n_prev, k0;       // native samples seen before this chunk; first frame to make
+    int64_t out_off;          // first output byte, from the launch's `out`
+    int64_t trace_off;        // first entry of the launch's `trace` (unused when that is NULL)
+};
+// The shifter's device state: the stretcher's (window tables, history [n_streams][Q3_TSM_HIST], d of every stream's last frame), the
+// intermediate history [n_streams][Q3_PITCH_HIST] (a stream's last 64 samples of z), all 151 tap tables (pitch.h), and an upload ring as
+// the stretcher's.  n_seen / k_done are the host's counters per stream; Nz = 480 k_done and the outputs made follow from them.  One owner
+// thread, as for the stretcher.
+struct PitchShifter {
+    PitchShifter(int n_streams, int max_group);
+    ~PitchShifter();
+    PitchShifter(const PitchShifter&) = delete; PitchShifter& operator=(const PitchShifter&) = delete;
+    void reset_async(hipStream_t st, int slot);    // zeroes the slot's two histories, offset and counters: its next sample is sample 0 of a stream
+    int n_streams, max_group;
+    float* hist; float* zhist;                     // = the own stores, or a caller's of the same shapes (the test entry point's guarded ones)
+    DevBuf<float> wins, tabs, hist_own, zhist_own; DevBuf<int32_t> d_prev; DevBuf<PitchStreamMeta> d_ring;
+    int tab_off[151]; int64_t table_bytes = 0;
+    PitchStreamMeta* h_ring = nullptr; int ring_idx = 0; std::vector<hipEvent_t> ring_ev; std::vector<char> ring_used;
+    std::vector<int64_t> n_seen, k_done;
+    int64_t chunks = 0, samples_out = 0, flushes = 0;
+};
+// in [G][T] native samples (T a multiple of 1920; 0 with flush alone), stream g of state slot streams[g] at rate[g] percent and pitch[g]
+// percent in encoding enc[g].  The delivered samples that became available (with flush: those of every frame with a_k < N) go to
+// out + out_off[g] bytes, which need the alignment of one sample only; n_out[g] receives their count.  A stream at pitch 100 is not touched:
+// n_out[g] is left alone and its bytes stay where they are.  trace (optional, device) receives d_k of every stage-1 frame made, stream g's
+// from entry trace_off[g] on.  A flushed stream must be reset before it is used again.
+// Refused (pitch_launch_refusal, pitch.h) before anything is uploaded or launched.
+void launch_tsm_pitch(hipStream_t st, PitchShifter& s, const float* in, int G, int T, bool flush, const int32_t* streams, const int32_t* rate,
+                      const int32_t* pitch, const int32_t* enc, void* out, const int64_t* out_off, int64_t* n_out, int32_t* trace = nullptr,
+                      const int64_t* trace_off = nullptr);
+
 } // namespace q3

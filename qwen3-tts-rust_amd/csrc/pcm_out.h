@@ -27,20 +27,23 @@ inline double pcm_bessel_i0(double x) { // power series; every term is positive,
 }
 
 // h[i] = L * 2fc * sinc(2fc * (i - Z*F)) * kaiser_9(i), i = 0 .. N-1, fc = 0.9 / (2F), in double, then rounded to f32
-inline std::vector<float> pcm_filter(int rate) {
-    PcmPlan p;
-    std::vector<float> h;
-    if (!pcm_plan(rate, &p) || p.n_taps == 0) return h;
-    const int F = p.L > p.M ? p.L : p.M, c = Q3_PCM_FILTER_Z * F;
+// the prototype of any ratio L / M in lowest terms (the eight rates here, a pitch's 100 / P in pitch.h): N = 2 Z max(L, M) + 1 taps
+inline std::vector<float> pcm_filter_lm(int L, int M) {
+    const int F = L > M ? L : M, c = Q3_PCM_FILTER_Z * F, n_taps = 2 * c + 1;
     const double pi = 3.14159265358979323846, fc2 = 0.9 / (double)F, i0b = pcm_bessel_i0(Q3_PCM_FILTER_BETA);
-    h.resize((size_t)p.n_taps);
-    for (int i = 0; i < p.n_taps; i++) {
+    std::vector<float> h((size_t)n_taps);
+    for (int i = 0; i < n_taps; i++) {
         const double x = fc2 * (double)(i - c), r = (double)(i - c) / (double)c;
         const double sinc = (i == c) ? 1.0 : std::sin(pi * x) / (pi * x);
         const double w = pcm_bessel_i0(Q3_PCM_FILTER_BETA * std::sqrt(1.0 - r * r)) / i0b;
-        h[(size_t)i] = (float)((double)p.L * fc2 * sinc * w);
+        h[(size_t)i] = (float)((double)L * fc2 * sinc * w);
     }
     return h;
+}
+inline std::vector<float> pcm_filter(int rate) {
+    PcmPlan p;
+    if (!pcm_plan(rate, &p) || p.n_taps == 0) return std::vector<float>();
+    return pcm_filter_lm(p.L, p.M);
 }
 // [L][stride]: row p holds h[p], h[p + L], h[p + 2L], ... and zeros behind the last tap below N
 inline std::vector<float> pcm_filter_phase_major(const PcmPlan& p, const std::vector<float>& h) {

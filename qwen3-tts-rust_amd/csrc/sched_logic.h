@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, and the counts and the submit rule of the speaking rate.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -553,6 +553,60 @@ inline const char* tsm_submit_refusal(int pct, const q3tts_pcm_format& f, int ma
     if (f.encoding != Q3_PCM_F32 && f.encoding != Q3_PCM_S16) return "unknown encoding";
     if (tsm_out_samples(pct, (int64_t)max_steps * Q3_PCM_FRAME, true) * (f.encoding == Q3_PCM_S16 ? 2 : 4) > cap_bytes)
         return "max_steps at this speech rate makes more PCM than a request's staging holds";
+    return nullptr;
+}
+
+// [EXT] pitch (q3tts_spec.h "pitch"): a shift by P percent is the stretcher at the rational tempo R / P followed by an L / M resample,
+// L / M = 100 / P in lowest terms.  Which pitches and (rate, pitch) pairs exist, the plan of a pitch's resampler, how many stage-1 frames and
+// delivered samples n_native samples come to, and what a request with a pitch may ask for.  Every count depends on R, P and n_native alone.
+inline const char* pitch_why_not(int P) { return (P < Q3_PITCH_MIN || P > Q3_PITCH_MAX) ? "pitch out of range [50, 200]" : nullptr; }
+// the pair rule: the tempo R / P lies in [1/2, 2], which keeps a frame's reach inside Q3_TSM_HIST (q3tts_spec.h "pitch", reach)
+inline const char* prosody_pair_why_not(int R, int P) {
+    if (const char* why = tsm_rate_why_not(R)) return why;
+    if (const char* why = pitch_why_not(P)) return why;
+    return (2 * R < P || R > 2 * P) ? "speech rate / pitch outside [1/2, 2]" : nullptr;
+}
+inline int64_t pitch_analysis_pos(int R, int P, int64_t k) { return k * Q3_TSM_HOP * R / P; }
+// stage-1 frames of a stream that has seen n_native samples: #{k : a_k + 1200 <= N} while streaming, #{k : a_k < N} once it is final
+inline int64_t pitch_frames(int R, int P, int64_t n_native, bool final) {
+    if (prosody_pair_why_not(R, P) || n_native < 0) return -1;
+    const int64_t step = (int64_t)Q3_TSM_HOP * R;   // a_k = floor(k * step / P)
+    if (final) return (P * n_native + step - 1) / step;
+    if (n_native < Q3_TSM_LOOK) return 0;
+    return (P * (n_native - Q3_TSM_LOOK + 1) - 1) / step + 1;   // a_k <= N - 1200  <=>  k * step < P (N - 1199)
+}
+// the resampler of a pitch: L / M = 100 / P in lowest terms, n_taps = N of the prototype, taps_per_output = the most terms one sample sums
+struct PitchPlan { int L = 1, M = 1, n_taps = 0, taps_per_output = 0; };
+inline bool pitch_plan(int P, PitchPlan* out) {
+    if (pitch_why_not(P)) return false;
+    int a = 100, b = P;
+    while (b) { const int t = a % b; a = b; b = t; }
+    PitchPlan p;
+    p.L = 100 / a; p.M = P / a;
+    const int F = p.L > p.M ? p.L : p.M;
+    p.n_taps = 2 * Q3_PCM_FILTER_Z * F + 1;
+    p.taps_per_output = (p.n_taps + p.L - 1) / p.L;
+    *out = p;
+    return true;
+}
+// delivered samples of nz stage-1 samples from a stream's reset: ceil(nz * L / M), since y[n] needs z[n M div L] and nothing later
+inline int64_t pitch_samples_of_z(const PitchPlan& p, int64_t nz) { return (nz * p.L + p.M - 1) / p.M; }
+inline int64_t pitch_out_samples(int R, int P, int64_t n_native, bool final) {
+    const int64_t f = pitch_frames(R, P, n_native, final);
+    PitchPlan p;
+    if (f < 0 || !pitch_plan(P, &p)) return -1;
+    return pitch_samples_of_z(p, f * Q3_TSM_HOP);
+}
+// the submit rule of a request with pitch P != 100 at rate R: the pair, 24000 Hz, f32 or s16, and its flushed utterance of max_steps frames
+// must fit the stream's staging region of cap_bytes bytes.  nullptr = it may be queued
+inline const char* pitch_submit_refusal(int R, int P, const q3tts_pcm_format& f, int max_steps, int64_t cap_bytes, bool have_codec) {
+    if (!have_codec) return "the engine has no codec";
+    if (const char* why = prosody_pair_why_not(R, P)) return why;
+    if (P == 100) return tsm_submit_refusal(R, f, max_steps, cap_bytes, have_codec);
+    if (f.sample_rate != Q3_PCM_NATIVE_RATE) return "a pitch needs the 24000 Hz output format";
+    if (f.encoding != Q3_PCM_F32 && f.encoding != Q3_PCM_S16) return "unknown encoding";
+    if (pitch_out_samples(R, P, (int64_t)max_steps * Q3_PCM_FRAME, true) * (f.encoding == Q3_PCM_S16 ? 2 : 4) > cap_bytes)
+        return "max_steps at this speech rate and pitch makes more PCM than a request's staging holds";
     return nullptr;
 }
 

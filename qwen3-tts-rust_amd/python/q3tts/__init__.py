@@ -111,6 +111,8 @@ SYMBOLS = [
     "q3tts_group_voice_set_stem", "q3tts_group_set_stem", "q3tts_group_request_stem", "q3tts_group_stem_stats",
     "q3tts_engine_set_speech_rate", "q3tts_request_speech_rate", "q3tts_engine_tsm_stats", "q3tts_group_set_speech_rate",
     "q3tts_group_request_speech_rate", "q3tts_tsm_samples", "q3tts_tsm_windows", "q3tts_op_tsm", "q3tts_mel_tables",
+    "q3tts_engine_set_pitch", "q3tts_request_pitch", "q3tts_engine_pitch_stats", "q3tts_group_set_pitch", "q3tts_group_request_pitch",
+    "q3tts_pitch_samples", "q3tts_pitch_plan", "q3tts_pitch_filter", "q3tts_op_pitch",
 ]
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
@@ -126,6 +128,7 @@ PCM_F32, PCM_S16 = 0, 1                                                  # q3tts
 PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)      # q3tts_spec.h "output formats"
 PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
 TSM_HOP, TSM_WIN, TSM_SEARCH, TSM_LOOK, TSM_HIST, TSM_MIN, TSM_MAX = 480, 960, 240, 1200, 1920, 50, 200   # q3tts_spec.h "speaking rate"
+PITCH_MIN, PITCH_MAX, PITCH_HIST = 50, 200, 64                           # q3tts_spec.h "pitch"
 MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
 PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
 MAX_STEMS = 64                                                           # Q3TTS_MAX_STEMS (q3tts_spec.h "prompt stems")
@@ -326,6 +329,19 @@ def lib():
         L.q3tts_tsm_windows.argtypes = [C.c_void_p, C.c_void_p]
         L.q3tts_op_tsm.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+        L.q3tts_engine_set_pitch.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_request_pitch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.q3tts_engine_pitch_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
+        L.q3tts_group_set_pitch.argtypes = L.q3tts_engine_set_pitch.argtypes
+        L.q3tts_group_request_pitch.argtypes = L.q3tts_request_pitch.argtypes
+        L.q3tts_pitch_samples.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+        L.q3tts_pitch_samples.restype = C.c_int64
+        L.q3tts_pitch_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
+        L.q3tts_pitch_filter.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
+        L.q3tts_pitch_filter.restype = C.c_int64
+        L.q3tts_op_pitch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -615,6 +631,16 @@ def group_set_speech_rate(group, rate_pct=100):
 def group_request_speech_rate(group, rid):
     """[EXT] q3tts_group_request_speech_rate: the percent a group request id is spoken at"""
     return _request_speech_rate(lib().q3tts_group_request_speech_rate, group, rid)
+
+
+def group_set_pitch(group, pitch_pct=100):
+    """[EXT] q3tts_group_set_pitch on a q3tts_group handle: every engine of the group (100 = off)"""
+    _chk(lib().q3tts_group_set_pitch(group, int(pitch_pct)))
+
+
+def group_request_pitch(group, rid):
+    """[EXT] q3tts_group_request_pitch: the percent a group request id's pitch is shifted to"""
+    return _request_speech_rate(lib().q3tts_group_request_pitch, group, rid)
 
 
 def _preamble_create(fn, h, codes):
@@ -1092,6 +1118,22 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _chk(lib().q3tts_engine_tsm_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(chunks=a.value, frames_out=b.value, flushes=c.value)
+
+    def set_pitch(self, pitch_pct=100):
+        """[EXT] pitch (q3tts_engine_set_pitch): requests submitted from now on with want_pcm have their fundamental multiplied by
+        pitch_pct / 100, PITCH_MIN .. PITCH_MAX, with or without a speech rate; 100 = off.  Such a request delivers 24000 Hz (f32 or s16) and
+        pitch_samples(rate_pct, pitch_pct, n * 1920, True) samples for n frames; rate / pitch must lie in [1/2, 2] when it is submitted"""
+        _chk(lib().q3tts_engine_set_pitch(self.h, int(pitch_pct)))
+
+    def request_pitch(self, rid):
+        """[EXT] the percent the request's pitch is shifted to (100: not shifted)"""
+        return _request_speech_rate(lib().q3tts_request_pitch, self.h, rid)
+
+    def pitch_stats(self):
+        """[EXT] q3tts_engine_pitch_stats: dict(chunks, samples_out, flushes, table_bytes)"""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_pitch_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(chunks=a.value, samples_out=b.value, flushes=c.value, table_bytes=d.value)
 
     def wait(self, rid, timeout_ms=-1.0):
         rc = lib().q3tts_wait(self.h, rid, timeout_ms)
@@ -2301,3 +2343,110 @@ def op_tsm(x, chunk_samples, streams, n_streams, rates, encodings, reset_before=
     outs = [w.view(dt)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, dt, (n, fr) in zip(wholes, dts, want)]
     traces = [t[GLUE_GUARD: GLUE_GUARD + fr].copy() for t, (n, fr) in zip(twholes, want)]
     return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist
+
+
+# ---- pitch: the host-only half and the pitch kernel (q3tts_op_pitch) ----
+def pitch_samples(rate_pct, pitch_pct, n_native, final=False):
+    """samples delivered for n_native native samples at the pair (rate_pct, pitch_pct): while streaming, or (final) once flushed; < 0 for a
+    value or the pair out of range"""
+    return int(lib().q3tts_pitch_samples(int(rate_pct), int(pitch_pct), int(n_native), 1 if final else 0))
+
+
+def pitch_plan(pitch_pct):
+    """dict(L, M, n_taps, taps_per_output) of a pitch's resampler; raises Q3Error for a pitch out of range"""
+    v = [C.c_int32() for _ in range(4)]
+    _chk(lib().q3tts_pitch_plan(int(pitch_pct), *[C.byref(t) for t in v]))
+    return dict(L=v[0].value, M=v[1].value, n_taps=v[2].value, taps_per_output=v[3].value)
+
+
+def pitch_filter(pitch_pct):
+    """the normative f32 prototype h32 of a pitch's resampler"""
+    h = np.zeros(pitch_plan(pitch_pct)["n_taps"], np.float32)
+    if int(lib().q3tts_pitch_filter(int(pitch_pct), _p(h), h.size)) != h.size:
+        raise Q3Error(lib().q3tts_last_error().decode())
+    return h
+
+
+def pitch_frames(rate_pct, pitch_pct, n_native, final=False):
+    """stage-1 frames behind pitch_samples (q3tts_spec.h "pitch", available / flush), for sizing a trace; 0 for anything out of range"""
+    R, P, N = int(rate_pct), int(pitch_pct), int(n_native)
+    if not (TSM_MIN <= R <= TSM_MAX and PITCH_MIN <= P <= PITCH_MAX and 2 * R >= P and R <= 2 * P) or N < 0:
+        return 0
+    if final:
+        return -(-P * N // (TSM_HOP * R))
+    return 0 if N < TSM_LOOK else (P * (N - TSM_LOOK + 1) - 1) // (TSM_HOP * R) + 1
+
+
+def op_pitch(x, chunk_samples, streams, n_streams, rates, pitches, encodings, reset_before=None, flush=False, hist=None, zhist=None, slack=0,
+             fill=0x5A):
+    """the pitch kernel over host buffers, one launch of the engine's launcher per chunk and one more for the flush: op_tsm plus pitches [G]
+    and a second state store.  A position with pitch 100 and a rate goes through the stretcher beside it; one with neither is copied through.
+    hist / zhist: whole guarded stores ([n_streams][1920] and [n_streams][64] between GLUE_GUARD floats) or None for zero stores between
+    guards of -3e38.  Every output and trace buffer is made exactly as large as the result plus `slack` elements, every byte `fill`.
+    Returns (outs, traces, wholes, twholes, n_out, hist, zhist).  A refused call raises Q3Error carrying wholes / twholes / n_out / hist /
+    zhist as they are then."""
+    x = np.ascontiguousarray(x, np.float32)
+    G = x.shape[0] if x.ndim == 2 else 0
+    cs = np.ascontiguousarray(chunk_samples, np.int32)
+    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
+    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    rt = np.ascontiguousarray(rates, np.int32)
+    pt = np.ascontiguousarray(pitches, np.int32)
+    en = np.ascontiguousarray(encodings, np.int32)
+    parts, at = [], 0
+    for t in cs:                       # [n_chunks concatenated][G][T_c]
+        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
+        at += max(int(t), 0)
+    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G and sum(p.size for p in parts) else np.zeros(1, np.float32)
+    wholes, twholes, want, dts = [], [], [], []
+    seen, ns, frs = {}, [0] * len(rt), [0] * len(rt)   # the plan, as the call works it out: native samples per slot, starting over at a reset
+
+    def made(g, n, final):   # (stage-1 frames, delivered samples) of position g after n native samples of an utterance
+        if pt[g] == 100:
+            v = max(tsm_samples(rt[g], n, final), 0)
+            return v // TSM_HOP, v
+        return pitch_frames(rt[g], pt[g], n, final), max(pitch_samples(rt[g], pt[g], n, final), 0)
+
+    for c in range(cs.size + (1 if flush else 0)):
+        T = max(int(cs[c]), 0) if c < cs.size else 0
+        for g in range(len(rt)):
+            s = int(sl[min(c, cs.size - 1), g]) if sl.size else 0
+            if c < cs.size and rb is not None and rb[c, g]:
+                seen[s] = 0
+            if rt[g] == 100 and pt[g] == 100:
+                ns[g] += T
+                continue
+            (f0, v0), (f1, v1) = made(g, seen.get(s, 0), False), made(g, seen.get(s, 0) + T, c == cs.size)
+            seen[s] = seen.get(s, 0) + T
+            ns[g] += max(v1 - v0, 0)
+            frs[g] += max(f1 - f0, 0)
+    for g in range(len(rt)):
+        dt = np.int16 if (en[g] == PCM_S16 and (rt[g] != 100 or pt[g] != 100)) else np.float32
+        want.append((ns[g], frs[g])); dts.append(dt)
+        wholes.append(np.full((ns[g] + slack + 2 * GLUE_GUARD) * np.dtype(dt).itemsize, fill, np.uint8))
+        twholes.append(np.full(frs[g] + slack + 2 * GLUE_GUARD, 0x5A5A5A5A, np.int32))
+
+    def store(h, width):
+        if h is None:
+            h = np.zeros(n_streams * width + 2 * GLUE_GUARD, np.float32)
+            h[:GLUE_GUARD] = h[-GLUE_GUARD:] = -3e38
+        assert h.dtype == np.float32 and h.size == n_streams * width + 2 * GLUE_GUARD and h.flags["C_CONTIGUOUS"]
+        return h
+
+    hist, zhist = store(hist, TSM_HIST), store(zhist, PITCH_HIST)
+    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
+    tptrs = (C.c_void_p * max(len(twholes), 1))(*[w.ctypes.data for w in twholes])
+    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
+    tlen = np.array([w.size for w in twholes] or [0], np.int64)
+    n_out = np.full(max(len(wholes), 1), -1, np.int64)
+    try:
+        pad = np.zeros(1, np.int32)    # an empty list still hands the call a pointer
+        _chk(lib().q3tts_op_pitch(_p(flat), G, _p(cs), cs.size, _p(sl if sl.size else pad), n_streams, _p(rt if rt.size else pad),
+                                  _p(pt if pt.size else pad), _p(en if en.size else pad), _p(rb), 1 if flush else 0, ptrs, _p(nbytes),
+                                  _p(n_out), tptrs, _p(tlen), _p(hist), _p(zhist)))
+    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
+        ex.wholes, ex.twholes, ex.n_out, ex.hist, ex.zhist = wholes, twholes, n_out[: len(wholes)].copy(), hist, zhist
+        raise
+    outs = [w.view(dt)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, dt, (n, fr) in zip(wholes, dts, want)]
+    traces = [t[GLUE_GUARD: GLUE_GUARD + fr].copy() for t, (n, fr) in zip(twholes, want)]
+    return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist, zhist
