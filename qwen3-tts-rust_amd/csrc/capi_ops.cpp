@@ -398,6 +398,103 @@ template <class T> struct GlueBuf {
     void down() { if (host) d.download(host, n); }
 };
 
+// ---- [EXT] what q3tts_op_pcm_convert, q3tts_op_tsm and q3tts_op_pitch share: every stream's guarded output (and trace) buffer goes whole into
+// its region of one device buffer -- regions start on 256 bytes (64 trace entries) -- the chunks are walked with each stream's output
+// appended behind its earlier chunks', and everything comes back whole ----
+struct GuardedStore {   // a whole guarded state store: GLUE_GUARD floats, the store, GLUE_GUARD floats
+    float* host; size_t n; DevBuf<float> dev;
+    GuardedStore(float* h, size_t core_floats) : host(h), n(core_floats + 2 * Q3TTS_GLUE_GUARD), dev(n) { dev.upload(host, n); }
+    float* core() const { return dev.p + Q3TTS_GLUE_GUARD; }
+    void download() { dev.download(host, n); }
+};
+struct GuardedRun {
+    const int G, n_chunks; const bool flush;
+    const int32_t* const chunk_samples; const int32_t* const streams; const int32_t* const reset_before;
+    void* const* const out; const int64_t* const out_bytes; int32_t* const* const trace; const int64_t* const trace_len;
+    const std::vector<int64_t>& esz;                  // bytes of one output sample of stream g
+    std::vector<int64_t> reg, treg, bytes, fr;        // region starts; output bytes and trace entries made so far
+    std::vector<int64_t> off, toff;                   // the current chunk's first output byte and trace entry
+    DevBuf<uint8_t> d_out; DevBuf<int32_t> d_trace; DevBuf<float> d_in;
+    int c = -1, T = 0; const float* x = nullptr; const int32_t* sl = nullptr;   // the current chunk, its samples per stream, its input and slots
+    // need[g] = the output bytes the plan gives stream g, frames[g] its trace entries (trace NULL: the call has no traces)
+    GuardedRun(const float* in, int G_, const int32_t* chunk_samples_, int n_chunks_, bool flush_, const int32_t* streams_, const int32_t* reset_before_,
+               const std::vector<int64_t>& esz_, const std::vector<int64_t>& need, const std::vector<int64_t>* frames, void* const* out_,
+               const int64_t* out_bytes_, int32_t* const* trace_, const int64_t* trace_len_)
+        : G(G_), n_chunks(n_chunks_), flush(flush_), chunk_samples(chunk_samples_), streams(streams_), reset_before(reset_before_), out(out_),
+          out_bytes(out_bytes_), trace(trace_), trace_len(trace_len_), esz(esz_), reg(G_), treg(G_), bytes(G_, 0), fr(G_, 0), off(G_), toff(G_) {
+        int64_t total = 0, ttotal = 0, in_floats = 0;
+        for (int g = 0; g < G; g++) {
+            Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
+            reg[g] = total; total += (out_bytes[g] + 255) / 256 * 256;
+            if (!trace) continue;
+            Q3_CHECK(trace[g] && trace_len[g] >= (*frames)[g] + 2 * Q3TTS_GLUE_GUARD, "guarded trace buffer too small or missing");
+            treg[g] = ttotal; ttotal += (trace_len[g] + 63) / 64 * 64;
+        }
+        d_out.alloc((size_t)total); d_trace.alloc((size_t)ttotal);
+        for (int g = 0; g < G; g++) {
+            Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
+            if (trace) Q3_HIP(hipMemcpy(d_trace.p + treg[g], trace[g], (size_t)trace_len[g] * 4, hipMemcpyHostToDevice));
+        }
+        for (int i = 0; i < n_chunks; i++) in_floats += (int64_t)G * chunk_samples[i];
+        d_in.alloc((size_t)std::max<int64_t>(in_floats, 1)); d_in.upload(in, (size_t)in_floats);
+        x = d_in.p;
+    }
+    bool next() {   // the next chunk, or the flush behind the last one, which follows the last chunk's slots
+        if (c >= 0) x += (size_t)G * T;
+        if (++c > n_chunks || (c == n_chunks && !flush)) return false;
+        T = c < n_chunks ? chunk_samples[c] : 0;
+        sl = streams + (size_t)std::min(c, n_chunks - 1) * G;
+        for (int g = 0; g < G; g++) { off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + bytes[g]; toff[g] = treg[g] + Q3TTS_GLUE_GUARD + fr[g]; }
+        return true;
+    }
+    bool flushing() const { return c == n_chunks; }
+    bool reset(int g) const { return c < n_chunks && reset_before && reset_before[(size_t)c * G + g]; }
+    void copy_native(int g) {   // a stream no stage touches is copied through as f32
+        if (T > 0) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
+        bytes[g] += (int64_t)T * 4;
+    }
+    void finish(int64_t* n_out, const std::vector<int64_t>* need, const char* differ) {   // need: the plan the launchers' counts must have met
+        Q3_LAUNCH_CHECK();
+        Q3_HIP(hipDeviceSynchronize());
+        for (int g = 0; g < G; g++) {
+            if (need) Q3_CHECK(bytes[g] == (*need)[g], differ);
+            Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
+            if (trace) Q3_HIP(hipMemcpy(trace[g], d_trace.p + treg[g], (size_t)trace_len[g] * 4, hipMemcpyDeviceToHost));
+            n_out[g] = bytes[g] / esz[g];
+        }
+    }
+};
+// every count of q3tts_op_tsm / q3tts_op_pitch worked out as the launchers will (pitch_pct NULL: no stream has a pitch): frames[g] = the
+// stage-1 frames stream g makes, need[g] = its output bytes, esz[g] = the bytes of one of its samples.  A position whose slot is reset starts over
+static void prosody_op_plan(int G, const int32_t* chunk_samples, int n_chunks, bool flush, const int32_t* streams, int n_streams, const int32_t* reset_before,
+                            const int32_t* rate_pct, const int32_t* pitch_pct, const int32_t* encoding, std::vector<int64_t>& frames,
+                            std::vector<int64_t>& need, std::vector<int64_t>& esz) {
+    std::vector<int64_t> seen((size_t)n_streams, 0), done((size_t)n_streams, 0);
+    frames.assign(G, 0); need.assign(G, 0); esz.assign(G, 4);
+    for (int c = 0; c <= n_chunks; c++) {
+        if (c == n_chunks && !flush) break;
+        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;   // the flush follows the last chunk's slots
+        const int64_t T = c < n_chunks ? chunk_samples[c] : 0;
+        for (int g = 0; g < G; g++) {
+            int64_t& sn = seen[(size_t)sl[g]]; int64_t& dn = done[(size_t)sl[g]];
+            const int P = pitch_pct ? pitch_pct[g] : 100;
+            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) sn = dn = 0;
+            if (P == 100 && rate_pct[g] == 100) { need[g] += T; continue; }
+            const int64_t total = std::max<int64_t>(P != 100 ? pitch_frames(rate_pct[g], P, sn + T, c == n_chunks) : tsm_frames(rate_pct[g], sn + T, c == n_chunks), dn);
+            if (P != 100) {
+                PitchPlan p;
+                pitch_plan(P, &p);
+                need[g] += pitch_samples_of_z(p, total * Q3_TSM_HOP) - pitch_samples_of_z(p, dn * Q3_TSM_HOP);
+            } else need[g] += (total - dn) * Q3_TSM_HOP;
+            frames[g] += total - dn; sn += T; dn = total;
+        }
+    }
+    for (int g = 0; g < G; g++) {
+        esz[g] = ((pitch_pct && pitch_pct[g] != 100) || rate_pct[g] != 100) && encoding[g] == Q3_PCM_S16 ? 2 : 4;   // a native stream is copied through as f32
+        need[g] *= esz[g];
+    }
+}
+
 extern "C" {
 
 int q3tts_op_attention(q3tts_attention_desc* d) {
@@ -1205,50 +1302,28 @@ int q3tts_op_pcm_convert(const float* in, int32_t G, const int32_t* chunk_sample
     Q3_CHECK(in && chunk_samples && streams && fmt && out && out_bytes && n_out && hist_store, "null argument");
     Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
     // every chunk is checked as its launch will be, before anything is allocated
-    int64_t in_floats = 0;
-    for (int c = 0; c < n_chunks; c++) {
+    for (int c = 0; c < n_chunks; c++)
         if (const char* why = pcm_convert_refusal(G, G, chunk_samples[c], streams + (size_t)c * G, n_streams, fmt)) throw Error(std::string("pcm convert: ") + why);
-        in_floats += (int64_t)G * chunk_samples[c];
-    }
-    std::vector<int64_t> reg(G), esz(G), need(G, 0);   // each stream's region of the one device buffer, its element size, its output bytes
-    int64_t total = 0;
+    std::vector<int64_t> esz(G), need(G, 0);
     for (int g = 0; g < G; g++) {
         esz[g] = fmt[g].encoding == Q3_PCM_S16 ? 2 : 4;
         for (int c = 0; c < n_chunks; c++) need[g] += pcm_samples_of_native(fmt[g].sample_rate, chunk_samples[c]) * esz[g];
-        Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
-        reg[g] = total;
-        total += (out_bytes[g] + 255) / 256 * 256;
     }
-    DevBuf<uint8_t> d_out((size_t)total);
-    for (int g = 0; g < G; g++) Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
-    DevBuf<float> d_in((size_t)in_floats); d_in.upload(in, (size_t)in_floats);
-    const size_t hist_n = (size_t)n_streams * 2 * Q3_PCM_HIST + 2 * Q3TTS_GLUE_GUARD;
-    DevBuf<float> d_hist(hist_n); d_hist.upload(hist_store, hist_n);
+    GuardedRun r(in, G, chunk_samples, n_chunks, false, streams, reset_before, esz, need, nullptr, out, out_bytes, nullptr, nullptr);
+    GuardedStore hist(hist_store, (size_t)n_streams * 2 * Q3_PCM_HIST);
     PcmConverter conv(n_streams, G);
-    conv.hist = d_hist.p + Q3TTS_GLUE_GUARD;
-    std::vector<int64_t> off(G), done(G, 0), cnt(G);
-    const float* x = d_in.p;
-    for (int c = 0; c < n_chunks; c++) {
-        const int T = chunk_samples[c];
-        const int32_t* sl = streams + (size_t)c * G;
+    conv.hist = hist.core();
+    std::vector<int64_t> cnt(G);
+    while (r.next()) {
+        for (int g = 0; g < G; g++) if (r.reset(g)) conv.reset_async(0, r.sl[g]);
+        launch_pcm_convert(0, conv, r.x, G, r.T, r.sl, fmt, r.d_out.p, r.off.data(), cnt.data());
         for (int g = 0; g < G; g++) {
-            if (reset_before && reset_before[(size_t)c * G + g]) conv.reset_async(0, sl[g]);
-            off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + done[g];
+            if (pcm_format_native(fmt[g])) r.copy_native(g);
+            else r.bytes[g] += cnt[g] * esz[g];
         }
-        launch_pcm_convert(0, conv, x, G, T, sl, fmt, d_out.p, off.data(), cnt.data());
-        for (int g = 0; g < G; g++) {
-            if (pcm_format_native(fmt[g])) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
-            done[g] += cnt[g] * esz[g];
-        }
-        x += (size_t)G * T;
     }
-    Q3_LAUNCH_CHECK();
-    Q3_HIP(hipDeviceSynchronize());
-    for (int g = 0; g < G; g++) {
-        Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
-        n_out[g] = done[g] / esz[g];
-    }
-    d_hist.download(hist_store, hist_n);
+    r.finish(n_out, nullptr, nullptr);
+    hist.download();
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -1273,71 +1348,25 @@ int q3tts_op_tsm(const float* in, int32_t G, const int32_t* chunk_samples, int32
     Q3_CHECK(in && chunk_samples && streams && rate_pct && encoding && out && out_bytes && n_out && delta_trace && trace_len && hist_store, "null argument");
     Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
     // every chunk is checked as its launch will be, and every count is worked out as the launcher will, before anything is allocated
-    int64_t in_floats = 0;
-    for (int c = 0; c < n_chunks; c++) {
+    for (int c = 0; c < n_chunks; c++)
         if (const char* why = tsm_launch_refusal(G, G, chunk_samples[c], false, streams + (size_t)c * G, n_streams, rate_pct, encoding)) throw Error(std::string("tsm stretch: ") + why);
-        in_floats += (int64_t)G * chunk_samples[c];
-    }
-    std::vector<int64_t> seen((size_t)n_streams, 0), done((size_t)n_streams, 0), frames(G, 0), need(G, 0), esz(G), reg(G), treg(G);
-    for (int c = 0; c <= n_chunks; c++) {
-        if (c == n_chunks && !flush) break;
-        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;   // the flush follows the last chunk's slots
-        const int64_t T = c < n_chunks ? chunk_samples[c] : 0;
-        for (int g = 0; g < G; g++) {
-            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) seen[(size_t)sl[g]] = done[(size_t)sl[g]] = 0;
-            if (rate_pct[g] == 100) { need[g] += T * 4; continue; }
-            const int64_t total = tsm_frames(rate_pct[g], seen[(size_t)sl[g]] + T, c == n_chunks), nf = std::max<int64_t>(total - done[(size_t)sl[g]], 0);
-            seen[(size_t)sl[g]] += T; done[(size_t)sl[g]] += nf; frames[g] += nf;
-        }
-    }
-    int64_t total = 0, ttotal = 0;
-    for (int g = 0; g < G; g++) {
-        esz[g] = rate_pct[g] != 100 && encoding[g] == Q3_PCM_S16 ? 2 : 4;   // a stream at 100 is copied through as native f32
-        if (rate_pct[g] != 100) need[g] = frames[g] * Q3_TSM_HOP * esz[g];
-        Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
-        Q3_CHECK(delta_trace[g] && trace_len[g] >= frames[g] + 2 * Q3TTS_GLUE_GUARD, "guarded trace buffer too small or missing");
-        reg[g] = total; total += (out_bytes[g] + 255) / 256 * 256;
-        treg[g] = ttotal; ttotal += (trace_len[g] + 63) / 64 * 64;
-    }
-    DevBuf<uint8_t> d_out((size_t)total);
-    DevBuf<int32_t> d_trace((size_t)ttotal);
-    for (int g = 0; g < G; g++) {
-        Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
-        Q3_HIP(hipMemcpy(d_trace.p + treg[g], delta_trace[g], (size_t)trace_len[g] * 4, hipMemcpyHostToDevice));
-    }
-    DevBuf<float> d_in((size_t)std::max<int64_t>(in_floats, 1)); d_in.upload(in, (size_t)in_floats);
-    const size_t hist_n = (size_t)n_streams * Q3_TSM_HIST + 2 * Q3TTS_GLUE_GUARD;
-    DevBuf<float> d_hist(hist_n); d_hist.upload(hist_store, hist_n);
+    std::vector<int64_t> frames, need, esz;
+    prosody_op_plan(G, chunk_samples, n_chunks, flush != 0, streams, n_streams, reset_before, rate_pct, nullptr, encoding, frames, need, esz);
+    GuardedRun r(in, G, chunk_samples, n_chunks, flush != 0, streams, reset_before, esz, need, &frames, out, out_bytes, delta_trace, trace_len);
+    GuardedStore hist(hist_store, (size_t)n_streams * Q3_TSM_HIST);
     TsmStretcher ts(n_streams, G);
-    ts.hist = d_hist.p + Q3TTS_GLUE_GUARD;
-    std::vector<int64_t> off(G), toff(G), bytes(G, 0), fr(G, 0), cnt(G);
-    const float* x = d_in.p;
-    for (int c = 0; c <= n_chunks; c++) {
-        if (c == n_chunks && !flush) break;
-        const int T = c < n_chunks ? chunk_samples[c] : 0;
-        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;
+    ts.hist = hist.core();
+    std::vector<int64_t> cnt(G);
+    while (r.next()) {
+        for (int g = 0; g < G; g++) if (r.reset(g)) ts.reset_async(0, r.sl[g]);
+        launch_tsm_stretch(0, ts, r.x, G, r.T, r.flushing(), r.sl, rate_pct, encoding, r.d_out.p, r.off.data(), cnt.data(), r.d_trace.p, r.toff.data());
         for (int g = 0; g < G; g++) {
-            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) ts.reset_async(0, sl[g]);
-            off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + bytes[g];
-            toff[g] = treg[g] + Q3TTS_GLUE_GUARD + fr[g];
+            if (rate_pct[g] == 100) r.copy_native(g);
+            else { r.bytes[g] += cnt[g] * esz[g]; r.fr[g] += cnt[g] / Q3_TSM_HOP; }
         }
-        launch_tsm_stretch(0, ts, x, G, T, c == n_chunks, sl, rate_pct, encoding, d_out.p, off.data(), cnt.data(), d_trace.p, toff.data());
-        for (int g = 0; g < G; g++) {
-            if (rate_pct[g] == 100 && T > 0) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
-            bytes[g] += cnt[g] * esz[g];
-            if (rate_pct[g] != 100) fr[g] += cnt[g] / Q3_TSM_HOP;
-        }
-        x += (size_t)G * T;
     }
-    Q3_LAUNCH_CHECK();
-    Q3_HIP(hipDeviceSynchronize());
-    for (int g = 0; g < G; g++) {
-        Q3_CHECK(bytes[g] == need[g], "the launcher's counts differ from the plan");
-        Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
-        Q3_HIP(hipMemcpy(delta_trace[g], d_trace.p + treg[g], (size_t)trace_len[g] * 4, hipMemcpyDeviceToHost));
-        n_out[g] = bytes[g] / esz[g];
-    }
-    d_hist.download(hist_store, hist_n);
+    r.finish(n_out, &need, "the launcher's counts differ from the plan");
+    hist.download();
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -1375,90 +1404,39 @@ int q3tts_op_pitch(const float* in, int32_t G, const int32_t* chunk_samples, int
     Q3_CHECK(in && chunk_samples && streams && rate_pct && pitch_pct && encoding && out && out_bytes && n_out && delta_trace && trace_len && hist_store && zhist_store, "null argument");
     Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
     // every chunk is checked as its launch will be, and every count is worked out as the launchers will, before anything is allocated
-    int64_t in_floats = 0;
-    for (int c = 0; c < n_chunks; c++) {
+    for (int c = 0; c < n_chunks; c++)
         if (const char* why = pitch_launch_refusal(G, G, chunk_samples[c], false, streams + (size_t)c * G, n_streams, rate_pct, pitch_pct, encoding)) throw Error(std::string("tsm pitch: ") + why);
-        in_floats += (int64_t)G * chunk_samples[c];
-    }
     std::vector<int32_t> kind(G), tpct(G, 100);   // 0 native, 1 a rate alone (the stretcher's), 2 a pitch (the shifter's)
     bool any_rate = false;
     for (int g = 0; g < G; g++) {
         kind[g] = pitch_pct[g] != 100 ? 2 : (rate_pct[g] != 100 ? 1 : 0);
         if (kind[g] == 1) { tpct[g] = rate_pct[g]; any_rate = true; }
     }
-    std::vector<int64_t> seen((size_t)n_streams, 0), done((size_t)n_streams, 0), frames(G, 0), need(G, 0), esz(G), reg(G), treg(G);
-    for (int c = 0; c <= n_chunks; c++) {
-        if (c == n_chunks && !flush) break;
-        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;   // the flush follows the last chunk's slots
-        const int64_t T = c < n_chunks ? chunk_samples[c] : 0;
-        for (int g = 0; g < G; g++) {
-            int64_t& sn = seen[(size_t)sl[g]]; int64_t& dn = done[(size_t)sl[g]];
-            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) sn = dn = 0;
-            if (kind[g] == 0) { need[g] += T; continue; }
-            const int64_t total = std::max<int64_t>(kind[g] == 2 ? pitch_frames(rate_pct[g], pitch_pct[g], sn + T, c == n_chunks) : tsm_frames(rate_pct[g], sn + T, c == n_chunks), dn);
-            if (kind[g] == 2) {
-                PitchPlan p;
-                pitch_plan(pitch_pct[g], &p);
-                need[g] += pitch_samples_of_z(p, total * Q3_TSM_HOP) - pitch_samples_of_z(p, dn * Q3_TSM_HOP);
-            } else need[g] += (total - dn) * Q3_TSM_HOP;
-            frames[g] += total - dn; sn += T; dn = total;
-        }
-    }
-    int64_t total = 0, ttotal = 0;
-    for (int g = 0; g < G; g++) {
-        esz[g] = kind[g] != 0 && encoding[g] == Q3_PCM_S16 ? 2 : 4;   // a native stream is copied through as f32
-        need[g] *= esz[g];
-        Q3_CHECK(out[g] && out_bytes[g] >= need[g] + 2 * Q3TTS_GLUE_GUARD * esz[g], "guarded output buffer too small or missing");
-        Q3_CHECK(delta_trace[g] && trace_len[g] >= frames[g] + 2 * Q3TTS_GLUE_GUARD, "guarded trace buffer too small or missing");
-        reg[g] = total; total += (out_bytes[g] + 255) / 256 * 256;
-        treg[g] = ttotal; ttotal += (trace_len[g] + 63) / 64 * 64;
-    }
-    DevBuf<uint8_t> d_out((size_t)total);
-    DevBuf<int32_t> d_trace((size_t)ttotal);
-    for (int g = 0; g < G; g++) {
-        Q3_HIP(hipMemcpy(d_out.p + reg[g], out[g], (size_t)out_bytes[g], hipMemcpyHostToDevice));
-        Q3_HIP(hipMemcpy(d_trace.p + treg[g], delta_trace[g], (size_t)trace_len[g] * 4, hipMemcpyHostToDevice));
-    }
-    DevBuf<float> d_in((size_t)std::max<int64_t>(in_floats, 1)); d_in.upload(in, (size_t)in_floats);
-    const size_t hist_n = (size_t)n_streams * Q3_TSM_HIST + 2 * Q3TTS_GLUE_GUARD, zhist_n = (size_t)n_streams * Q3_PITCH_HIST + 2 * Q3TTS_GLUE_GUARD;
-    DevBuf<float> d_hist(hist_n), d_zhist(zhist_n); d_hist.upload(hist_store, hist_n); d_zhist.upload(zhist_store, zhist_n);
+    std::vector<int64_t> frames, need, esz;
+    prosody_op_plan(G, chunk_samples, n_chunks, flush != 0, streams, n_streams, reset_before, rate_pct, pitch_pct, encoding, frames, need, esz);
+    GuardedRun r(in, G, chunk_samples, n_chunks, flush != 0, streams, reset_before, esz, need, &frames, out, out_bytes, delta_trace, trace_len);
+    GuardedStore hist(hist_store, (size_t)n_streams * Q3_TSM_HIST), zhist(zhist_store, (size_t)n_streams * Q3_PITCH_HIST);
     PitchShifter ps(n_streams, G);
-    ps.hist = d_hist.p + Q3TTS_GLUE_GUARD; ps.zhist = d_zhist.p + Q3TTS_GLUE_GUARD;
+    ps.hist = hist.core(); ps.zhist = zhist.core();
     std::unique_ptr<TsmStretcher> ts;
     if (any_rate) { ts.reset(new TsmStretcher(n_streams, G)); ts->hist = ps.hist; }
-    std::vector<int64_t> off(G), toff(G), bytes(G, 0), fr(G, 0), cnt(G), pcnt(G);
-    const float* x = d_in.p;
-    for (int c = 0; c <= n_chunks; c++) {
-        if (c == n_chunks && !flush) break;
-        const int T = c < n_chunks ? chunk_samples[c] : 0;
-        const int32_t* sl = streams + (size_t)std::min(c, n_chunks - 1) * G;
+    std::vector<int64_t> cnt(G), pcnt(G), kd0(G);
+    while (r.next()) {
         for (int g = 0; g < G; g++) {
-            if (c < n_chunks && reset_before && reset_before[(size_t)c * G + g]) { ps.reset_async(0, sl[g]); if (ts) ts->reset_async(0, sl[g]); }
-            off[g] = reg[g] + Q3TTS_GLUE_GUARD * esz[g] + bytes[g];
-            toff[g] = treg[g] + Q3TTS_GLUE_GUARD + fr[g];
+            if (r.reset(g)) { ps.reset_async(0, r.sl[g]); if (ts) ts->reset_async(0, r.sl[g]); }
             cnt[g] = pcnt[g] = 0;
+            kd0[g] = ps.k_done[(size_t)r.sl[g]];
         }
-        std::vector<int64_t> kd0(G), td0(G);
-        for (int g = 0; g < G; g++) { kd0[g] = ps.k_done[(size_t)sl[g]]; td0[g] = ts ? ts->k_done[(size_t)sl[g]] : 0; }
-        launch_tsm_pitch(0, ps, x, G, T, c == n_chunks, sl, rate_pct, pitch_pct, encoding, d_out.p, off.data(), pcnt.data(), d_trace.p, toff.data());
-        if (ts) launch_tsm_stretch(0, *ts, x, G, T, c == n_chunks, sl, tpct.data(), encoding, d_out.p, off.data(), cnt.data(), d_trace.p, toff.data());
+        launch_tsm_pitch(0, ps, r.x, G, r.T, r.flushing(), r.sl, rate_pct, pitch_pct, encoding, r.d_out.p, r.off.data(), pcnt.data(), r.d_trace.p, r.toff.data());
+        if (ts) launch_tsm_stretch(0, *ts, r.x, G, r.T, r.flushing(), r.sl, tpct.data(), encoding, r.d_out.p, r.off.data(), cnt.data(), r.d_trace.p, r.toff.data());
         for (int g = 0; g < G; g++) {
-            if (kind[g] == 0 && T > 0) Q3_HIP(hipMemcpyAsync(d_out.p + off[g], x + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
-            if (kind[g] == 0) bytes[g] += (int64_t)T * 4;
-            else if (kind[g] == 1) { bytes[g] += cnt[g] * esz[g]; fr[g] += ts->k_done[(size_t)sl[g]] - td0[g]; }
-            else { bytes[g] += pcnt[g] * esz[g]; fr[g] += ps.k_done[(size_t)sl[g]] - kd0[g]; }
+            if (kind[g] == 0) r.copy_native(g);
+            else if (kind[g] == 1) { r.bytes[g] += cnt[g] * esz[g]; r.fr[g] += cnt[g] / Q3_TSM_HOP; }
+            else { r.bytes[g] += pcnt[g] * esz[g]; r.fr[g] += ps.k_done[(size_t)r.sl[g]] - kd0[g]; }
         }
-        x += (size_t)G * T;
     }
-    Q3_LAUNCH_CHECK();
-    Q3_HIP(hipDeviceSynchronize());
-    for (int g = 0; g < G; g++) {
-        Q3_CHECK(bytes[g] == need[g], "the launchers' counts differ from the plan");
-        Q3_HIP(hipMemcpy(out[g], d_out.p + reg[g], (size_t)out_bytes[g], hipMemcpyDeviceToHost));
-        Q3_HIP(hipMemcpy(delta_trace[g], d_trace.p + treg[g], (size_t)trace_len[g] * 4, hipMemcpyDeviceToHost));
-        n_out[g] = bytes[g] / esz[g];
-    }
-    d_hist.download(hist_store, hist_n); d_zhist.download(zhist_store, zhist_n);
+    r.finish(n_out, &need, "the launchers' counts differ from the plan");
+    hist.download(); zhist.download();
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

@@ -69,8 +69,6 @@ public:
     void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks the converter took, output samples it made
     double flops_per_frame() const;
 private:
-    int decode_group_tail_pitch(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt,
-                                int64_t* n_out, const int32_t* rate, const int32_t* pitch);
     struct Impl;
     std::unique_ptr<Impl> impl_;
 };

@@ -1179,45 +1179,57 @@ struct CodecDecoder::Impl {
         DevBuf<float> h, xn, qkv, att, gu, act, t1, t2, pcm, splitk_ws; DevBuf<int64_t> d_in; // d_in = codes then meta
         std::vector<DevBuf<float>> work;              // batched extended buffers, indexed by Ext::id
         int64_t* h_in = nullptr; int ring_idx = 0;    // pinned staging ring for the (tiny) code + metadata uploads of async calls
+        std::vector<uint8_t> kind;                    // [gmax]: the kind of each stream of the pass in flight (deliver)
     };
     std::vector<Scratch> lanes; Scratch* S = nullptr; int ring = 256;
     // [EXT] output formats: made by the first call that converts (decode_group_async), under capture_mutex(); pcm_out[lane] = the converted
     // chunk of each stream of a pass, region g at g * T * 4 bytes.  The counters are read by other threads
     std::unique_ptr<PcmConverter> conv; std::vector<DevBuf<float>> pcm_out; size_t pcm_lane_floats = 0;
     std::atomic<int64_t> conv_chunks{0}, conv_samples{0};
-    // [EXT] speaking rate: made by the first call that stretches, under capture_mutex(); tsm_out[lane] = the hops of each stream of a pass,
-    // region g of tsm_region floats (a chunk at rate 50 makes twice its samples plus a hop; a flush at most six hops).  tsm_pct / tsm_enc =
-    // what a stream was last stretched with since its reset (0: it was not), which is what its flush runs with
-    std::unique_ptr<TsmStretcher> tsm; std::vector<DevBuf<float>> tsm_out; std::vector<int32_t> tsm_pct, tsm_enc;
+    // [EXT] speaking rate / pitch: the stretcher is made by the first call that stretches and the shifter by the first call that shifts -- the
+    // decoder thread, which owns the codec's streams -- under capture_mutex(); all 151 tap tables are built and uploaded there, once.
+    // tsm_out[lane] / pitch_out[lane] = what the stage made of each stream of a pass, region g of tsm_region() floats: a chunk of T samples
+    // gives at most 2 T samples plus a hop at rate 50 and 2 T + 961 at the tempo 1/2, a flush at most six hops or 3361 samples.
+    // prosody[s] = what stream s was last stretched or shifted with since its reset, which is what its flush runs with
+    std::unique_ptr<TsmStretcher> tsm; std::unique_ptr<PitchShifter> pitch; std::vector<DevBuf<float>> tsm_out, pitch_out;
+    struct Prosody { int32_t rate = 0, pitch = 100, enc = Q3_PCM_F32; };   // rate 0: neither since the reset; pitch 100: the stretcher's stream
+    std::vector<Prosody> prosody;
     size_t tsm_region() const { return 2 * (pcm_lane_floats / (size_t)gmax) + 8 * Q3_TSM_HOP; }
     std::atomic<int64_t> tsm_chunks{0}, tsm_frames{0}, tsm_flushes{0};
-    void ensure_tsm() {
-        if (tsm) return;
-        std::lock_guard<std::mutex> cap(capture_mutex());
-        tsm_out.resize(lanes.size());
-        for (auto& b : tsm_out) b.alloc((size_t)gmax * tsm_region());
-        tsm_pct.assign((size_t)n_streams, 0); tsm_enc.assign((size_t)n_streams, 0);
-        tsm.reset(new TsmStretcher(n_streams, gmax));
-    }
-    void tsm_reset(hipStream_t st, int s) { if (tsm) { tsm->reset_async(st, s); tsm_pct[(size_t)s] = 0; } }
-    void tsm_count(int64_t c0, int64_t f0, int64_t l0) { tsm_chunks += tsm->chunks - c0; tsm_frames += tsm->frames_out - f0; tsm_flushes += tsm->flushes - l0; }
-    // [EXT] pitch: made by the first call that shifts -- the decoder thread, which owns the codec's streams -- under capture_mutex(): all 151 tap
-    // tables are built and uploaded there, once.  pitch_out[lane] = the delivered samples of each stream of a pass, region g of tsm_region()
-    // floats (a chunk delivers at most 2 T + 961 samples, a flush at most 3361).  pitch_R / pitch_P / pitch_enc = what a stream was last shifted
-    // with since its reset (pitch_P 0: it was not), which is what its flush runs with
-    std::unique_ptr<PitchShifter> pitch; std::vector<DevBuf<float>> pitch_out; std::vector<int32_t> pitch_R, pitch_P, pitch_enc;
     std::atomic<int64_t> pitch_chunks{0}, pitch_samples{0}, pitch_flushes{0}, pitch_table_bytes{0};
-    void ensure_pitch() {
-        if (pitch) return;
+    template <class Stage> bool ensure_stage(std::unique_ptr<Stage>& stage, std::vector<DevBuf<float>>& out) {   // true: made by this call
+        if (stage) return false;
         std::lock_guard<std::mutex> cap(capture_mutex());
-        pitch_out.resize(lanes.size());
-        for (auto& b : pitch_out) b.alloc((size_t)gmax * tsm_region());
-        pitch_R.assign((size_t)n_streams, 0); pitch_P.assign((size_t)n_streams, 0); pitch_enc.assign((size_t)n_streams, 0);
-        pitch.reset(new PitchShifter(n_streams, gmax));
-        pitch_table_bytes = pitch->table_bytes;
+        out.resize(lanes.size());
+        for (auto& b : out) b.alloc((size_t)gmax * tsm_region());
+        prosody.resize((size_t)n_streams);
+        stage.reset(new Stage(n_streams, gmax));
+        return true;
     }
-    void pitch_reset(hipStream_t st, int s) { if (pitch) { pitch->reset_async(st, s); pitch_P[(size_t)s] = 0; } }
-    void pitch_count(int64_t c0, int64_t s0, int64_t l0) { pitch_chunks += pitch->chunks - c0; pitch_samples += pitch->samples_out - s0; pitch_flushes += pitch->flushes - l0; }
+    void prosody_reset(hipStream_t st, int s) {
+        if (tsm) tsm->reset_async(st, s);
+        if (pitch) pitch->reset_async(st, s);
+        if (!prosody.empty()) prosody[(size_t)s] = Prosody{};
+    }
+    // one launch of a stage over the chunk in S->pcm (in = false: a flush alone) and its accounting
+    void run_tsm(hipStream_t st, bool in, int G, int T, const int32_t* streams, const int32_t* pct, const int32_t* enc, int lane,
+                 const int64_t* off, int64_t* n) {
+        ensure_stage(tsm, tsm_out);
+        const int64_t c0 = tsm->chunks, f0 = tsm->frames_out, l0 = tsm->flushes;
+        launch_tsm_stretch(st, *tsm, in ? S->pcm.p : nullptr, G, T, !in, streams, pct, enc, tsm_out[lane].p, off, n);
+        Q3_LAUNCH_CHECK();
+        tsm_chunks += tsm->chunks - c0; tsm_frames += tsm->frames_out - f0; tsm_flushes += tsm->flushes - l0;
+    }
+    void run_pitch(hipStream_t st, bool in, int G, int T, const int32_t* streams, const int32_t* rate, const int32_t* pct, const int32_t* enc,
+                   int lane, const int64_t* off, int64_t* n) {
+        if (ensure_stage(pitch, pitch_out)) pitch_table_bytes = pitch->table_bytes;
+        const int64_t c0 = pitch->chunks, s0 = pitch->samples_out, l0 = pitch->flushes;
+        launch_tsm_pitch(st, *pitch, in ? S->pcm.p : nullptr, G, T, !in, streams, rate, pct, enc, pitch_out[lane].p, off, n);
+        Q3_LAUNCH_CHECK();
+        pitch_chunks += pitch->chunks - c0; pitch_samples += pitch->samples_out - s0; pitch_flushes += pitch->flushes - l0;
+    }
+    void deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt, int64_t* n_out,
+                 const int32_t* rate, const int32_t* pitch_pct);
     // [EXT] codec preambles: the snapshot store.  A slot holds one stream's histories back to back in all_ext order (the shape of one stream's
     // share of the history stores) and the two host counters as they stood when the snapshot was enqueued.  A slot's buffer is allocated by the
     // first snapshot that takes it, under capture_mutex(), and kept for the next one; snap_mu guards the table (a slot may be freed by
@@ -1485,7 +1497,7 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
         m.pcm_lane_floats = (size_t)GM * T;
         L.work.resize(m.all_ext.size());
         for (Ext* e : m.all_ext) L.work[e->id].alloc((size_t)GM * (e->H + e->Tmax) * e->C);
-        L.d_in.alloc(m.in_slot());
+        L.d_in.alloc(m.in_slot()); L.kind.resize((size_t)GM);
         L.splitk_ws.alloc(std::max<size_t>(max_act * 2, (size_t)1 << 20));
         Q3_HIP(hipHostMalloc((void**)&L.h_in, (size_t)m.ring * m.in_slot() * sizeof(int64_t)));
     }
@@ -1509,8 +1521,7 @@ void CodecDecoder::reset(int s) {
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
     if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
-    if (m.tsm) { m.tsm_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
-    if (m.pitch) { m.pitch_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
+    if (m.tsm || m.pitch) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 void CodecDecoder::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
@@ -1602,8 +1613,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     }
     flush();
     if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
-    m.tsm_reset(st, s);                     // and so is the stretcher's state
-    m.pitch_reset(st, s);                   // and the pitch shifter's
+    m.prosody_reset(st, s);                 // and so are the stretcher's state and the pitch shifter's
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1654,8 +1664,7 @@ void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* p
         m.ensure_conv();
         Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
     }
-    m.tsm_reset(st, s); // [EXT] speaking rate: a primed stream's stretcher starts from a reset
-    m.pitch_reset(st, s); // [EXT] pitch: and both stages of its pitch shifter
+    m.prosody_reset(st, s); // [EXT] speaking rate / pitch: a primed stream's stretcher and both stages of its pitch shifter start from a reset
     m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
 }
 void CodecDecoder::snapshot_free(int snap) {
@@ -1787,147 +1796,86 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
-    bool converts = false, stretches = false, shifts = false;
-    for (int g = 0; pitch && g < G; g++) shifts = shifts || pitch[g] != 100;
-    if (shifts) return decode_group_tail_pitch(st, G, streams, T, pcm, lane, fmt, n_out, rate, pitch);   // [EXT] pitch: a pass without one runs what follows, as it did
-    for (int g = 0; rate && g < G; g++) stretches = stretches || rate[g] != 100;
-    for (int g = 0; fmt && g < G; g++) converts = converts || (!pcm_format_native(fmt[g]) && !(rate && rate[g] != 100));
-    if (!converts && !stretches) {
-        for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-        for (int g = 0; n_out && g < G; g++) n_out[g] = T;
-        return T;
-    }
-    // [EXT] output formats / speaking rate: one convert launch and / or one stretch launch behind the output conv, then every stream's bytes
-    // from where its stage left them.  A stretching stream delivers 24000 Hz and is the stretcher's alone: the converter sees it as native
-    const q3tts_pcm_format native{Q3_PCM_NATIVE_RATE, Q3_PCM_F32};
-    std::vector<q3tts_pcm_format> cf((size_t)G, native);
-    std::vector<int32_t> pct((size_t)G, 100), enc((size_t)G, Q3_PCM_F32);
-    for (int g = 0; g < G; g++) {
-        if (rate && rate[g] != 100) {
-            Q3_CHECK(!fmt || fmt[g].sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate needs the 24000 Hz output format");
-            pct[(size_t)g] = rate[g]; enc[(size_t)g] = fmt ? fmt[g].encoding : Q3_PCM_F32;
-        } else if (fmt) cf[(size_t)g] = fmt[g];
-    }
-    std::vector<int64_t> cnt((size_t)G, T), tcnt((size_t)G, T), toff((size_t)G);
-    if (converts) {
-        m.ensure_conv();
-        const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
-        launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, cf.data(), m.pcm_out[lane].p, nullptr, cnt.data());
-        Q3_LAUNCH_CHECK();
-        m.conv_chunks += m.conv->chunks_converted - c0; m.conv_samples += m.conv->samples_out - s0;
-    }
-    if (stretches) {
-        m.ensure_tsm();
-        Q3_CHECK(2 * (size_t)T + Q3_TSM_HOP <= m.tsm_region(), "chunk too long for the stretcher's buffers");
-        for (int g = 0; g < G; g++) toff[(size_t)g] = (int64_t)((size_t)g * m.tsm_region() * sizeof(float));
-        const int64_t c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;
-        launch_tsm_stretch(st, *m.tsm, m.S->pcm.p, G, T, false, streams, pct.data(), enc.data(), m.tsm_out[lane].p, toff.data(), tcnt.data());
-        Q3_LAUNCH_CHECK();
-        m.tsm_count(c0, f0, l0);
-    }
-    for (int g = 0; g < G; g++) {
-        if (pct[(size_t)g] != 100) {
-            m.tsm_pct[(size_t)streams[g]] = pct[(size_t)g]; m.tsm_enc[(size_t)streams[g]] = enc[(size_t)g];
-            cnt[(size_t)g] = tcnt[(size_t)g];
-            if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], m.tsm_out[lane].p + (size_t)g * m.tsm_region(), (size_t)cnt[(size_t)g] * (enc[(size_t)g] == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
-        }
-        else if (pcm_format_native(cf[(size_t)g])) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-        else Q3_HIP(hipMemcpyAsync(pcm[g], m.pcm_out[lane].p + (size_t)g * T, (size_t)cnt[(size_t)g] * (cf[(size_t)g].encoding == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
-        if (n_out) n_out[g] = cnt[(size_t)g];
-    }
+    m.deliver(st, G, streams, T, pcm, lane, fmt, n_out, rate, pitch);
     return T;
 }
 
-// [EXT] pitch: what follows the output conv in a pass that holds a stream with a pitch.  The streams are of four kinds -- native, converted
-// (the converter's), rate-only (the stretcher's) and pitched (the shifter's) -- and each stage sees the streams of the other stages as ones it
-// leaves alone; a stage nobody needs is not launched.  Then every stream's bytes go out from where its stage left them
-int CodecDecoder::decode_group_tail_pitch(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt,
-                                          int64_t* n_out, const int32_t* rate, const int32_t* pitch) {
-    Impl& m = *impl_;
+// [EXT] output formats / speaking rate / pitch: what follows the output conv.  A stream is of one of four kinds -- native, converted (the
+// converter's), rate-only (the stretcher's), pitched (the shifter's) -- and each stage sees the streams of the other stages as ones it leaves
+// alone; a stage nobody needs is not launched, and a pass of native streams is G copies.  A stretched or shifted stream delivers 24000 Hz.
+// Then every stream's bytes go out from where its stage left them
+void CodecDecoder::Impl::deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt,
+                                 int64_t* n_out, const int32_t* rate, const int32_t* pitch_pct) {
+    enum Kind : uint8_t { NATIVE, CONVERTED, RATED, PITCHED };
+    bool any[4] = {false, false, false, false};
+    uint8_t* const kind = S->kind.data();
+    for (int g = 0; g < G; g++) {
+        kind[g] = pitch_pct && pitch_pct[g] != 100 ? PITCHED : rate && rate[g] != 100 ? RATED : fmt && !pcm_format_native(fmt[g]) ? CONVERTED : NATIVE;
+        any[kind[g]] = true;
+    }
+    if (!any[CONVERTED] && !any[RATED] && !any[PITCHED]) {
+        for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+        for (int g = 0; n_out && g < G; g++) n_out[g] = T;
+        return;
+    }
     const q3tts_pcm_format native{Q3_PCM_NATIVE_RATE, Q3_PCM_F32};
     std::vector<q3tts_pcm_format> cf((size_t)G, native);
     std::vector<int32_t> pct((size_t)G, 100), pr((size_t)G, 100), pp((size_t)G, 100), enc((size_t)G, Q3_PCM_F32);
-    bool converts = false, stretches = false;
     for (int g = 0; g < G; g++) {
-        const bool pitched = pitch[g] != 100, rated = !pitched && rate && rate[g] != 100;
-        if (pitched || rated) {
-            Q3_CHECK(!fmt || fmt[g].sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate or a pitch needs the 24000 Hz output format");
-            enc[(size_t)g] = fmt ? fmt[g].encoding : Q3_PCM_F32;
-            if (pitched) { pr[(size_t)g] = rate ? rate[g] : 100; pp[(size_t)g] = pitch[g]; }
-            else { pct[(size_t)g] = rate[g]; stretches = true; }
-        } else if (fmt) { cf[(size_t)g] = fmt[g]; converts = converts || !pcm_format_native(fmt[g]); }
+        if (kind[g] == NATIVE) continue;
+        if (kind[g] == CONVERTED) { cf[(size_t)g] = fmt[g]; continue; }
+        Q3_CHECK(!fmt || fmt[g].sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate or a pitch needs the 24000 Hz output format");
+        enc[(size_t)g] = fmt ? fmt[g].encoding : Q3_PCM_F32;
+        if (kind[g] == PITCHED) { pr[(size_t)g] = rate ? rate[g] : 100; pp[(size_t)g] = pitch_pct[g]; }
+        else pct[(size_t)g] = rate[g];
     }
-    std::vector<int64_t> cnt((size_t)G, T), tcnt((size_t)G, T), pcnt((size_t)G, T), toff((size_t)G);
-    Q3_CHECK(2 * (size_t)T + 3 * Q3_TSM_HOP <= m.tsm_region(), "chunk too long for the stretcher's buffers");
-    for (int g = 0; g < G; g++) toff[(size_t)g] = (int64_t)((size_t)g * m.tsm_region() * sizeof(float));
-    if (converts) {
-        m.ensure_conv();
-        const int64_t c0 = m.conv->chunks_converted, s0 = m.conv->samples_out;
-        launch_pcm_convert(st, *m.conv, m.S->pcm.p, G, T, streams, cf.data(), m.pcm_out[lane].p, nullptr, cnt.data());
+    std::vector<int64_t> cnt((size_t)G, T), scnt((size_t)G, T), toff((size_t)G);   // the converter's counts; the stretcher's and the shifter's
+    if (any[CONVERTED]) {
+        ensure_conv();
+        const int64_t c0 = conv->chunks_converted, s0 = conv->samples_out;
+        launch_pcm_convert(st, *conv, S->pcm.p, G, T, streams, cf.data(), pcm_out[lane].p, nullptr, cnt.data());
         Q3_LAUNCH_CHECK();
-        m.conv_chunks += m.conv->chunks_converted - c0; m.conv_samples += m.conv->samples_out - s0;
+        conv_chunks += conv->chunks_converted - c0; conv_samples += conv->samples_out - s0;
     }
-    if (stretches) {
-        m.ensure_tsm();
-        const int64_t c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;
-        launch_tsm_stretch(st, *m.tsm, m.S->pcm.p, G, T, false, streams, pct.data(), enc.data(), m.tsm_out[lane].p, toff.data(), tcnt.data());
-        Q3_LAUNCH_CHECK();
-        m.tsm_count(c0, f0, l0);
+    if (any[RATED] || any[PITCHED]) {
+        Q3_CHECK(2 * (size_t)T + 3 * Q3_TSM_HOP <= tsm_region(), "chunk too long for the stretcher's buffers");
+        for (int g = 0; g < G; g++) toff[(size_t)g] = (int64_t)((size_t)g * tsm_region() * sizeof(float));
     }
-    {
-        m.ensure_pitch();
-        const int64_t c0 = m.pitch->chunks, s0 = m.pitch->samples_out, l0 = m.pitch->flushes;
-        launch_tsm_pitch(st, *m.pitch, m.S->pcm.p, G, T, false, streams, pr.data(), pp.data(), enc.data(), m.pitch_out[lane].p, toff.data(), pcnt.data());
-        Q3_LAUNCH_CHECK();
-        m.pitch_count(c0, s0, l0);
-    }
+    // the stretcher sets T for every stream it leaves alone and the shifter sets its own streams' counts only: they share scnt in this order
+    if (any[RATED]) run_tsm(st, true, G, T, streams, pct.data(), enc.data(), lane, toff.data(), scnt.data());
+    if (any[PITCHED]) run_pitch(st, true, G, T, streams, pr.data(), pp.data(), enc.data(), lane, toff.data(), scnt.data());
     for (int g = 0; g < G; g++) {
-        const size_t sb = enc[(size_t)g] == Q3_PCM_S16 ? 2 : 4;
-        if (pp[(size_t)g] != 100) {
-            m.pitch_R[(size_t)streams[g]] = pr[(size_t)g]; m.pitch_P[(size_t)streams[g]] = pp[(size_t)g]; m.pitch_enc[(size_t)streams[g]] = enc[(size_t)g];
-            cnt[(size_t)g] = pcnt[(size_t)g];
-            Q3_CHECK((size_t)cnt[(size_t)g] <= m.tsm_region(), "a pass delivered more than the shifter's buffer holds");
-            if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], m.pitch_out[lane].p + (size_t)g * m.tsm_region(), (size_t)cnt[(size_t)g] * sb, hipMemcpyDeviceToHost, st));
+        const float* src = S->pcm.p + (size_t)g * T;
+        size_t sb = 4;
+        if (kind[g] == CONVERTED) { src = pcm_out[lane].p + (size_t)g * T; sb = cf[(size_t)g].encoding == Q3_PCM_S16 ? 2 : 4; }
+        else if (kind[g] != NATIVE) {
+            src = (kind[g] == PITCHED ? pitch_out : tsm_out)[lane].p + (size_t)g * tsm_region(); sb = enc[(size_t)g] == Q3_PCM_S16 ? 2 : 4;
+            prosody[(size_t)streams[g]] = Prosody{kind[g] == PITCHED ? pr[(size_t)g] : pct[(size_t)g], pp[(size_t)g], enc[(size_t)g]};
+            cnt[(size_t)g] = scnt[(size_t)g];
+            Q3_CHECK((size_t)cnt[(size_t)g] <= tsm_region(), "a pass delivered more than the stage's buffer holds");
         }
-        else if (pct[(size_t)g] != 100) {
-            m.tsm_pct[(size_t)streams[g]] = pct[(size_t)g]; m.tsm_enc[(size_t)streams[g]] = enc[(size_t)g];
-            cnt[(size_t)g] = tcnt[(size_t)g];
-            if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], m.tsm_out[lane].p + (size_t)g * m.tsm_region(), (size_t)cnt[(size_t)g] * sb, hipMemcpyDeviceToHost, st));
-        }
-        else if (pcm_format_native(cf[(size_t)g])) Q3_HIP(hipMemcpyAsync(pcm[g], m.S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-        else Q3_HIP(hipMemcpyAsync(pcm[g], m.pcm_out[lane].p + (size_t)g * T, (size_t)cnt[(size_t)g] * (cf[(size_t)g].encoding == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+        if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], src, (size_t)cnt[(size_t)g] * sb, hipMemcpyDeviceToHost, st));
         if (n_out) n_out[g] = cnt[(size_t)g];
     }
-    return T;
 }
 
-// [EXT] speaking rate: the end of a stretched utterance.  The stream's input ends in zeros and every frame with a_k < N comes out: one launch
-// without input, then the copy of its hops to dst (pinned).  A stream that was not stretched since its reset gives nothing
+// [EXT] speaking rate / pitch: the end of a stretched or shifted utterance.  The stream's input ends in zeros and every frame with a_k < N
+// comes out -- of a pitched stream stage 1 is flushed and stage 2 delivers what that completes: one launch without input, then the copy to
+// dst (pinned).  A stream that was neither stretched nor shifted since its reset gives nothing
 void CodecDecoder::tsm_flush_async(hipStream_t st, int s, void* dst, int64_t* n_out, int lane) {
     Impl& m = *impl_;
     Q3_CHECK(s >= 0 && s < m.n_streams && n_out, "stream out of range");
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     *n_out = 0;
-    if (m.pitch && m.pitch_P[(size_t)s] != 0) { // [EXT] pitch: the stream is the shifter's; stage 1 is flushed and stage 2 delivers what that completes
-        const int32_t sl = s, R = m.pitch_R[(size_t)s], P = m.pitch_P[(size_t)s], enc = m.pitch_enc[(size_t)s];
-        const int64_t off = 0, c0 = m.pitch->chunks, s0 = m.pitch->samples_out, l0 = m.pitch->flushes;
-        launch_tsm_pitch(st, *m.pitch, nullptr, 1, 0, true, &sl, &R, &P, &enc, m.pitch_out[lane].p, &off, n_out);
-        Q3_LAUNCH_CHECK();
-        m.pitch_count(c0, s0, l0);
-        Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the shifter's buffer");
-        if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, m.pitch_out[lane].p, (size_t)*n_out * (enc == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
-        m.pitch_P[(size_t)s] = 0; // flushed: the stream is reset before it is used again
-        return;
-    }
-    if (!m.tsm || m.tsm_pct[(size_t)s] == 0) return;
-    const int32_t sl = s, pct = m.tsm_pct[(size_t)s], enc = m.tsm_enc[(size_t)s];
-    const int64_t off = 0, c0 = m.tsm->chunks, f0 = m.tsm->frames_out, l0 = m.tsm->flushes;
-    launch_tsm_stretch(st, *m.tsm, nullptr, 1, 0, true, &sl, &pct, &enc, m.tsm_out[lane].p, &off, n_out);
-    Q3_LAUNCH_CHECK();
-    m.tsm_count(c0, f0, l0);
-    Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the stretcher's buffer");
-    if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, m.tsm_out[lane].p, (size_t)*n_out * (enc == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
-    m.tsm_pct[(size_t)s] = 0; // flushed: the stream is reset before it is used again
+    if (m.prosody.empty() || m.prosody[(size_t)s].rate == 0) return;
+    const Impl::Prosody p = m.prosody[(size_t)s];
+    const int32_t sl = s;
+    const int64_t off = 0;
+    if (p.pitch != 100) m.run_pitch(st, false, 1, 0, &sl, &p.rate, &p.pitch, &p.enc, lane, &off, n_out);
+    else m.run_tsm(st, false, 1, 0, &sl, &p.rate, &p.enc, lane, &off, n_out);
+    Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the stage's buffer");
+    if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, (p.pitch != 100 ? m.pitch_out : m.tsm_out)[lane].p, (size_t)*n_out * (p.enc == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
+    m.prosody[(size_t)s].rate = 0; // flushed: the stream is reset before it is used again
 }
 
 // ---------------- test entry points: one GEMM as the decoder dispatches it, or with a named form forced ----------------

@@ -325,6 +325,37 @@ void launch_kv_fork(hipStream_t st, const KvCache& kv, int src_seq, const int32_
 struct StemJob { uint16_t* k; uint16_t* v; int32_t n_pages, first, n_dst, pad; };
 void launch_kv_stem(hipStream_t st, const KvCache& kv, const StemJob* jobs, int n_jobs, int max_pages, const int32_t* slots, bool save);
 
+// The output stages' upload ring: 64 slots of max_group launch entries each, pinned host + device, every slot with the event of the launch
+// that last read it.  take() waits for that launch, on whichever HIP stream it ran, and hands out the slot's host entries and their device
+// address; commit() uploads the first G of them on the launch's stream; launched() records the launch.  One owner thread.
+template <class Meta> struct UploadRing {
+    static constexpr int SLOTS = 64;
+    UploadRing() = default;
+    UploadRing(const UploadRing&) = delete; UploadRing& operator=(const UploadRing&) = delete;
+    ~UploadRing() {
+        for (auto e : ev) if (e) (void)hipEventDestroy(e);
+        if (host) (void)hipHostFree(host);
+    }
+    void alloc(int max_group_) {
+        max_group = max_group_;
+        dev.alloc((size_t)SLOTS * max_group);
+        Q3_HIP(hipHostMalloc((void**)&host, sizeof(Meta) * SLOTS * max_group));
+        for (auto& e : ev) Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    Meta* take(const Meta** d) {
+        cur = next; next = (next + 1) % SLOTS;
+        if (used[cur]) Q3_HIP(hipEventSynchronize(ev[cur]));   // the slot's previous launch has consumed its upload
+        *d = dev.p + (size_t)cur * max_group;
+        return host + (size_t)cur * max_group;
+    }
+    void commit(hipStream_t st, int G) {
+        Q3_HIP(hipMemcpyAsync(dev.p + (size_t)cur * max_group, host + (size_t)cur * max_group, sizeof(Meta) * G, hipMemcpyHostToDevice, st));
+    }
+    void launched(hipStream_t st) { Q3_HIP(hipEventRecord(ev[cur], st)); used[cur] = 1; }
+    int max_group = 0, cur = 0, next = 0;
+    DevBuf<Meta> dev; Meta* host = nullptr; hipEvent_t ev[SLOTS] = {}; char used[SLOTS] = {};
+};
+
 // [EXT] output formats (pcmout.hip, q3tts_spec.h "output formats"): sample-rate conversion and int16 PCM behind the codec.
 // One entry per stream of a launch, written by launch_pcm_convert into the converter's upload ring.
 struct PcmStreamMeta {
@@ -334,18 +365,16 @@ struct PcmStreamMeta {
     int32_t tab_off, n_out;   // first float of the rate's table in PcmConverter::tabs; output samples of this chunk
     int64_t out_off, pad;     // first output byte, from the launch's `out`
 };
-// The converter's device state: the eight filter tables (phase-major, pcm_out.h), the history store [n_streams][2][Q3_PCM_HIST], and a ring
-// of upload slots (pinned host + device) of max_group entries each, every slot with the event of the launch that last read it.  One owner
-// thread; its launches may go to different HIP streams, and the caller orders a stream slot's chunks across them as it does for the codec.
+// The converter's device state: the eight filter tables (phase-major, pcm_out.h), the history store [n_streams][2][Q3_PCM_HIST], and its
+// upload ring.  One owner thread; its launches may go to different HIP streams, and the caller orders a stream slot's chunks across them
+// as it does for the codec.
 struct PcmConverter {
     PcmConverter(int n_streams, int max_group);
-    ~PcmConverter();
     PcmConverter(const PcmConverter&) = delete; PcmConverter& operator=(const PcmConverter&) = delete;
     void reset_async(hipStream_t st, int slot);   // zeroes the slot's history: its next sample is sample 0 of a stream
     int n_streams, max_group;
     float* hist;                                   // = hist_own.p, or a caller's store of the same shape (the test entry point's guarded one)
-    DevBuf<float> tabs, hist_own; DevBuf<PcmStreamMeta> d_ring;
-    PcmStreamMeta* h_ring = nullptr; int ring_idx = 0; std::vector<hipEvent_t> ring_ev; std::vector<char> ring_used;
+    DevBuf<float> tabs, hist_own; UploadRing<PcmStreamMeta> ring;
     int tab_off[8], tab_stride[8], tab_L[8], tab_M[8];
     std::vector<uint8_t> parity;                   // per slot: the half the next launch reads
     int64_t chunks_converted = 0, samples_out = 0;
@@ -374,13 +403,11 @@ struct TsmStreamMeta {
 // thread; its launches may go to different HIP streams, and the caller orders a stream slot's chunks across them as it does for the codec.
 struct TsmStretcher {
     TsmStretcher(int n_streams, int max_group);
-    ~TsmStretcher();
     TsmStretcher(const TsmStretcher&) = delete; TsmStretcher& operator=(const TsmStretcher&) = delete;
     void reset_async(hipStream_t st, int slot);    // zeroes the slot's history, offset and counters: its next sample is sample 0 of a stream
     int n_streams, max_group;
     float* hist;                                   // = hist_own.p, or a caller's store of the same shape (the test entry point's guarded one)
-    DevBuf<float> tabs, hist_own; DevBuf<int32_t> d_prev; DevBuf<TsmStreamMeta> d_ring;
-    TsmStreamMeta* h_ring = nullptr; int ring_idx = 0; std::vector<hipEvent_t> ring_ev; std::vector<char> ring_used;
+    DevBuf<float> tabs, hist_own; DevBuf<int32_t> d_prev; UploadRing<TsmStreamMeta> ring;
     std::vector<int64_t> n_seen, k_done;
     int64_t chunks = 0, frames_out = 0, flushes = 0;
 };
@@ -413,14 +440,12 @@ struct PitchStreamMeta {
 // thread, as for the stretcher.
 struct PitchShifter {
     PitchShifter(int n_streams, int max_group);
-    ~PitchShifter();
     PitchShifter(const PitchShifter&) = delete; PitchShifter& operator=(const PitchShifter&) = delete;
     void reset_async(hipStream_t st, int slot);    // zeroes the slot's two histories, offset and counters: its next sample is sample 0 of a stream
     int n_streams, max_group;
     float* hist; float* zhist;                     // = the own stores, or a caller's of the same shapes (the test entry point's guarded ones)
-    DevBuf<float> wins, tabs, hist_own, zhist_own; DevBuf<int32_t> d_prev; DevBuf<PitchStreamMeta> d_ring;
+    DevBuf<float> wins, tabs, hist_own, zhist_own; DevBuf<int32_t> d_prev; UploadRing<PitchStreamMeta> ring;
     int tab_off[151]; int64_t table_bytes = 0;
-    PitchStreamMeta* h_ring = nullptr; int ring_idx = 0; std::vector<hipEvent_t> ring_ev; std::vector<char> ring_used;
     std::vector<int64_t> n_seen, k_done;
     int64_t chunks = 0, samples_out = 0, flushes = 0;
 };

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "kdev.h"
 #include "pcm_out.h"
+#include "wsola.h"
 
 namespace q3 {
 
@@ -23,10 +24,6 @@ namespace q3 {
 #define PO_TILE 1024                                   // output samples per block
 #define PO_TAB_MAX (147 * 36)                          // floats of the largest table (22050 and 44100 Hz)
 #define PO_WIN_MAX 3200                                // floats of the largest window: 1023 * 3 + 1 + 100 at 8000 Hz
-#define PO_RING 64
-
-__device__ __forceinline__ float po_clamp(float y) { return y < -1.0f ? -1.0f : (y > 1.0f ? 1.0f : y); }
-__device__ __forceinline__ uint32_t po_s16(float y) { return (uint32_t)(uint16_t)(int16_t)rintf(y * 32767.0f); }
 
 struct PcmConvertArgs { const float* in; int T; const PcmStreamMeta* meta; const float* tabs; float* hist; unsigned char* out; };
 
@@ -40,7 +37,7 @@ __global__ void __launch_bounds__(PO_THREADS) k_pcm_convert(PcmConvertArgs a) {
     const int cnt = min(PO_TILE, mt.n_out - m0), L = mt.L, M = mt.M, stride = mt.stride;
     const float* __restrict__ x = a.in + (size_t)g * a.T;
     if (stride == 0) {   // 24000 Hz: no filter
-        for (int i = tid; i < cnt; i += PO_THREADS) stage[i] = po_clamp(x[m0 + i]);
+        for (int i = tid; i < cnt; i += PO_THREADS) stage[i] = pcm_clamp(x[m0 + i]);
     } else {
         const float* __restrict__ hr = a.hist + ((size_t)mt.slot * 2 + mt.parity) * Q3_PCM_HIST;
         if (blockIdx.x == 0 && tid < Q3_PCM_HIST) a.hist[((size_t)mt.slot * 2 + (mt.parity ^ 1)) * Q3_PCM_HIST + tid] = x[a.T - Q3_PCM_HIST + tid];
@@ -65,7 +62,7 @@ __global__ void __launch_bounds__(PO_THREADS) k_pcm_convert(PcmConvertArgs a) {
                 acc = fmaf(h.z, xw[-4 * k4 - 2], acc);
                 acc = fmaf(h.w, xw[-4 * k4 - 3], acc);
             }
-            stage[ml] = po_clamp(acc);
+            stage[ml] = pcm_clamp(acc);
         }
     }
     wg_barrier_lds();
@@ -75,13 +72,9 @@ __global__ void __launch_bounds__(PO_THREADS) k_pcm_convert(PcmConvertArgs a) {
         uint16_t* o = reinterpret_cast<uint16_t*>(ob);
         const int nv = vec ? cnt >> 3 : 0;
         for (int v = tid; v < nv; v += PO_THREADS) {
-            const float4 lo = reinterpret_cast<const float4*>(stage)[2 * v], hi = reinterpret_cast<const float4*>(stage)[2 * v + 1];
-            uint4 w;
-            w.x = po_s16(lo.x) | (po_s16(lo.y) << 16); w.y = po_s16(lo.z) | (po_s16(lo.w) << 16);
-            w.z = po_s16(hi.x) | (po_s16(hi.y) << 16); w.w = po_s16(hi.z) | (po_s16(hi.w) << 16);
-            reinterpret_cast<uint4*>(o)[v] = w;
+            reinterpret_cast<uint4*>(o)[v] = pcm_pack8(reinterpret_cast<const float4*>(stage)[2 * v], reinterpret_cast<const float4*>(stage)[2 * v + 1]);
         }
-        for (int i = (nv << 3) + tid; i < cnt; i += PO_THREADS) o[i] = (uint16_t)po_s16(stage[i]);
+        for (int i = (nv << 3) + tid; i < cnt; i += PO_THREADS) o[i] = (uint16_t)pcm_s16(stage[i]);
     } else {
         // f32: the launcher saw to it that the destination is 16-byte aligned and the count a multiple of 4 (both hold for whole frames)
         for (int v = tid; v < (cnt >> 2); v += PO_THREADS) reinterpret_cast<float4*>(ob)[v] = reinterpret_cast<const float4*>(stage)[v];
@@ -104,15 +97,8 @@ PcmConverter::PcmConverter(int n_streams_, int max_group_) : n_streams(n_streams
     tabs.alloc(all.size()); tabs.upload(all.data(), all.size());
     hist_own.alloc((size_t)n_streams * 2 * Q3_PCM_HIST); hist_own.zero();
     hist = hist_own.p;
-    d_ring.alloc((size_t)PO_RING * max_group);
-    Q3_HIP(hipHostMalloc((void**)&h_ring, sizeof(PcmStreamMeta) * PO_RING * max_group));
+    ring.alloc(max_group);
     parity.assign((size_t)n_streams, 0);
-    ring_ev.resize(PO_RING); ring_used.assign(PO_RING, 0);
-    for (auto& e : ring_ev) Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-}
-PcmConverter::~PcmConverter() {
-    for (auto e : ring_ev) if (e) (void)hipEventDestroy(e);
-    if (h_ring) (void)hipHostFree(h_ring);
 }
 
 void PcmConverter::reset_async(hipStream_t st, int slot) {
@@ -134,11 +120,8 @@ void launch_pcm_convert(hipStream_t st, PcmConverter& c, const float* in, int G,
     }
     for (int g = 0; g < G; g++) n_out[g] = pcm_samples_of_native(fmt[g].sample_rate, T);
     if (most == 0) return;   // every stream is native: nothing to run
-    const int rs = c.ring_idx;   // the slot's previous launch, on whichever stream it ran, has consumed its upload
-    c.ring_idx = (c.ring_idx + 1) % PO_RING;
-    if (c.ring_used[(size_t)rs]) Q3_HIP(hipEventSynchronize(c.ring_ev[(size_t)rs]));
-    const size_t slot0 = (size_t)rs * c.max_group;
-    PcmStreamMeta* hm = c.h_ring + slot0;
+    const PcmStreamMeta* dm;
+    PcmStreamMeta* hm = c.ring.take(&dm);
     for (int g = 0; g < G; g++) {
         const int r = pcm_rate_index(fmt[g].sample_rate);
         PcmStreamMeta& m = hm[g];
@@ -148,11 +131,10 @@ void launch_pcm_convert(hipStream_t st, PcmConverter& c, const float* in, int G,
         m.out_off = out_off ? out_off[g] : (int64_t)g * T * 4; m.pad = 0;
         if (m.enc >= 0) { c.parity[(size_t)streams[g]] ^= 1; c.chunks_converted++; c.samples_out += n_out[g]; }
     }
-    Q3_HIP(hipMemcpyAsync(c.d_ring.p + slot0, hm, sizeof(PcmStreamMeta) * G, hipMemcpyHostToDevice, st));
-    PcmConvertArgs a{in, T, c.d_ring.p + slot0, c.tabs.p, c.hist, (unsigned char*)out};
+    c.ring.commit(st, G);
+    PcmConvertArgs a{in, T, dm, c.tabs.p, c.hist, (unsigned char*)out};
     hipLaunchKernelGGL(k_pcm_convert, dim3((unsigned)((most + PO_TILE - 1) / PO_TILE), G), dim3(PO_THREADS), 0, st, a);
-    Q3_HIP(hipEventRecord(c.ring_ev[(size_t)rs], st));
-    c.ring_used[(size_t)rs] = 1;
+    c.ring.launched(st);
 }
 
 } // namespace q3

@@ -33,22 +33,12 @@ inline PitchTables pitch_tables() {
     return t;
 }
 
-// what a pitch launch refuses (nullptr = it may run): G streams of T native samples each, streams[] slots of an n_streams state store,
-// stream g at rate[g] percent and pitch[g] percent (pitch 100: the stream is not touched, whatever its rate) in encoding enc[g].
-// T = 0 is a flush alone
+// what a pitch launch refuses (nullptr = it may run): prosody_launch_refusal (tsm.h) with stream g at rate[g] percent and pitch[g] percent
+// (pitch 100: the stream is not touched, whatever its rate)
 inline const char* pitch_launch_refusal(int G, int max_group, int64_t T, bool flush, const int32_t* streams, int n_streams, const int32_t* rate,
                                         const int32_t* pitch, const int32_t* enc) {
-    if (G < 1 || G > max_group) return "group size out of range";
-    if (T < 0 || T % Q3_TSM_HIST != 0 || (T == 0 && !flush)) return "chunk length is no positive multiple of 1920 samples";
-    if (T > (int64_t)1 << 24) return "chunk too long";
-    if (!streams || !rate || !pitch || !enc) return "null streams / rates / pitches / encodings";
-    for (int g = 0; g < G; g++) {
-        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
-        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
-        if (const char* why = prosody_pair_why_not(rate[g], pitch[g])) return why;
-        if (enc[g] != Q3_PCM_F32 && enc[g] != Q3_PCM_S16) return "unknown encoding";
-    }
-    return nullptr;
+    return prosody_launch_refusal(G, max_group, T, flush, streams, n_streams, enc, streams && rate && pitch && enc,
+                                  "null streams / rates / pitches / encodings", [&](int g) { return prosody_pair_why_not(rate[g], pitch[g]); });
 }
 
 } // namespace q3

@@ -1,9 +1,8 @@
 // pitch.hip -- [EXT] pitch (q3tts_spec.h "pitch"): the stretcher at the rational tempo R / P and the L / M = 100 / P resampler behind it, one
 // launch per decode pass that has a stream with a pitch.
 //
-// k_tsm_pitch: grid = G, 512 lanes, one workgroup per stream; a stream without a pitch exits at once.  Stage 1 is k_tsm_stretch's frame walk
-// with a_k = floor(k * 480 * R / P): the 1920-float window x[a_k - 720 .. a_k + 1200) in LDS, lane `tid` < 481 the candidate d = tid - 240, the
-// (SSD bits << 32 | o) keys reduced by xor shuffles and 8 LDS words.  The hop z[480 k .. 480 k + 480) is not delivered: it goes into LDS behind
+// k_tsm_pitch: grid = G, 512 lanes, one workgroup per stream; a stream without a pitch exits at once.  Stage 1 is the stretcher's frame
+// step, wsola_frame (wsola.h), with a_k = floor(k * 480 * R / P).  The hop z[480 k .. 480 k + 480) is not delivered: it goes into LDS behind
 // the stream's last 64 samples of z (zb[0 .. 64) = z[480 k - 64 .. 480 k), zb[64 + i] = z[480 k + i]).  Stage 2 then forms the delivered
 // samples this hop completes, n in [ceil(480 k L / M), ceil(480 (k + 1) L / M)), at most 961: lane i takes n_lo + i, n_lo + i + 512; with
 // t = n M, j = t div L and p = t mod L it sums h32[p + kk L] * z[j - kk], kk ascending, one fmaf per term.  j lies in this hop and kk <= 64, so
@@ -23,30 +22,23 @@
 #include "kernels.h"
 #include "kdev.h"
 #include "pitch.h"
+#include "wsola.h"
 #include <mutex>
 
 namespace q3 {
 
-#define PT_THREADS 512
-#define PT_WAVES (PT_THREADS / 64)
-#define PT_CAND (2 * Q3_TSM_SEARCH + 1)
-#define PT_BACK (Q3_TSM_HIST - Q3_TSM_LOOK)            // 720: how far below a_k a frame reaches
 #define PT_TAB_MAX 6400                                // floats of the longest table: 2 * 16 * 199 + 1 = 6369
 #define PT_OUT_MAX 964                                 // delivered samples one hop completes: at most ceil(480 * 2) + 1
-#define PT_RING 64
-
-__device__ __forceinline__ float pt_clamp(float y) { return y < -1.0f ? -1.0f : (y > 1.0f ? 1.0f : y); }
-__device__ __forceinline__ uint32_t pt_s16(float y) { return (uint32_t)(uint16_t)(int16_t)rintf(y * 32767.0f); }
 
 struct PitchArgs { const float* in; int T; const PitchStreamMeta* meta; const float* wins; const float* tabs; float* hist; float* zhist; int32_t* d_prev; unsigned char* out; int32_t* trace; };
 
-__global__ void __launch_bounds__(PT_THREADS) k_tsm_pitch(PitchArgs a) {
+__global__ void __launch_bounds__(WS_THREADS) k_tsm_pitch(PitchArgs a) {
     __shared__ __attribute__((aligned(16))) float win[Q3_TSM_HIST];
     __shared__ __attribute__((aligned(16))) float wt[2 * Q3_TSM_HOP];
     __shared__ __attribute__((aligned(16))) float zb[Q3_PITCH_HIST + Q3_TSM_HOP];
     __shared__ __attribute__((aligned(16))) float stage[PT_OUT_MAX];
     __shared__ __attribute__((aligned(16))) float tab[PT_TAB_MAX];
-    __shared__ unsigned long long best[PT_WAVES];
+    __shared__ unsigned long long best[WS_WAVES];
     const int g = blockIdx.x, tid = threadIdx.x;
     const PitchStreamMeta mt = a.meta[g];
     if (mt.enc < 0) return;   // uniform: the stream has no pitch
@@ -55,8 +47,8 @@ __global__ void __launch_bounds__(PT_THREADS) k_tsm_pitch(PitchArgs a) {
     float* const zh = a.zhist + (size_t)mt.slot * Q3_PITCH_HIST;
     const long long n_prev = mt.n_prev, n_new = mt.n_prev + a.T, step = (long long)Q3_TSM_HOP * mt.R;
     const int L = mt.L, M = mt.M, n_taps = mt.n_taps < PT_TAB_MAX ? mt.n_taps : PT_TAB_MAX, esz = mt.enc == Q3_PCM_S16 ? 2 : 4;
-    for (int i = tid; i < 2 * Q3_TSM_HOP; i += PT_THREADS) wt[i] = a.wins[i];
-    for (int i = tid; i < n_taps; i += PT_THREADS) tab[i] = a.tabs[mt.tab_off + i];
+    for (int i = tid; i < 2 * Q3_TSM_HOP; i += WS_THREADS) wt[i] = a.wins[i];
+    for (int i = tid; i < n_taps; i += WS_THREADS) tab[i] = a.tabs[mt.tab_off + i];
     if (tid < Q3_PITCH_HIST) zb[tid] = zh[tid];   // lane tid alone reads and writes zb[tid] outside stage 2
     int d_prev = a.d_prev[mt.slot];
     const long long n_first = (mt.k0 * Q3_TSM_HOP * L + M - 1) / M;   // delivered samples before this launch
@@ -64,50 +56,14 @@ __global__ void __launch_bounds__(PT_THREADS) k_tsm_pitch(PitchArgs a) {
     for (int f = 0; f < mt.n_frames; f++) {
         const long long k = mt.k0 + f, ak = k * step / mt.P;
         const long long tk = k == 0 ? 0 : (k - 1) * step / mt.P + d_prev + Q3_TSM_HOP;
-        const long long base = ak - PT_BACK;
-        for (int i = tid; i < Q3_TSM_HIST; i += PT_THREADS) {
-            const long long n = base + i, rel = n - n_prev;
-            float v = 0.0f;
-            if (n >= 0 && n < n_new) {
-                if (rel >= 0) v = x[rel];
-                else if (rel >= -Q3_TSM_HIST) v = h[Q3_TSM_HIST + rel];
-            }
-            win[i] = v;
-        }
-        int tb = (int)(tk - base);   // in [0, 1200] by the spec's reach; clamped so that no read can leave the window
-        tb = tb < 0 ? 0 : (tb > Q3_TSM_HIST - Q3_TSM_HOP ? Q3_TSM_HIST - Q3_TSM_HOP : tb);
-        wg_barrier_lds();
-        unsigned long long key = ~0ull;
-        if (tid < PT_CAND && ak + tid - Q3_TSM_SEARCH >= 0) {
-            const float* __restrict__ c = win + (PT_BACK - Q3_TSM_SEARCH) + tid;
-            const float* __restrict__ t = win + tb;
-            float acc = 0.0f;
-#pragma unroll 16
-            for (int i = 0; i < Q3_TSM_HOP; i++) {
-                const float d = c[i] - t[i];
-                acc = fmaf(d, d, acc);
-            }
-            key = ((unsigned long long)__float_as_uint(acc) << 32) | (unsigned)tsm_visit_order(tid - Q3_TSM_SEARCH);
-        }
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-            const unsigned long long o = __shfl_xor(key, s, 64);
-            key = o < key ? o : key;
-        }
-        if ((tid & 63) == 0) best[tid >> 6] = key;
-        wg_barrier_lds();
-        unsigned long long kmin = best[0];
-#pragma unroll
-        for (int w = 1; w < PT_WAVES; w++) kmin = best[w] < kmin ? best[w] : kmin;
-        const int d = tsm_offset_of_order((int)(unsigned)(kmin & 0xffffffffull));   // uniform, in [-240, 240]
-        if (tid < Q3_TSM_HOP) zb[Q3_PITCH_HIST + tid] = pt_clamp(fmaf(wt[tid], win[PT_BACK + d + tid], __fmul_rn(wt[Q3_TSM_HOP + tid], win[tb + tid])));
+        const int d = wsola_frame(ak, tk, x, h, n_prev, n_new, win, wt, best, zb + Q3_PITCH_HIST);
         wg_barrier_lds();
         // stage 2: the delivered samples this hop completes
         const long long n_lo = (k * Q3_TSM_HOP * L + M - 1) / M, n_hi = ((k + 1) * Q3_TSM_HOP * L + M - 1) / M;
         const int cnt = (int)(n_hi - n_lo) < PT_OUT_MAX ? (int)(n_hi - n_lo) : PT_OUT_MAX;   // at most 961 by L <= 2 M
         const long long t0 = n_lo * M, j0 = t0 / L;
         const int r0 = (int)(t0 - j0 * L), jb = (int)(j0 - k * Q3_TSM_HOP) + Q3_PITCH_HIST;   // j0 >= 480 k: jb >= 64
-        for (int i = tid; i < cnt; i += PT_THREADS) {
+        for (int i = tid; i < cnt; i += WS_THREADS) {
             const int ti = r0 + i * M, q = ti / L, p = ti - q * L;
             int jl = jb + q;   // zb index of z[j]; j < 480 (k + 1) by the choice of n_hi
             jl = jl > Q3_PITCH_HIST + Q3_TSM_HOP - 1 ? Q3_PITCH_HIST + Q3_TSM_HOP - 1 : jl;
@@ -115,7 +71,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_tsm_pitch(PitchArgs a) {
             K = K > jl + 1 ? jl + 1 : K;
             float acc = 0.0f;
             for (int kk = 0; kk < K; kk++) acc = fmaf(tab[p + kk * L], zb[jl - kk], acc);
-            stage[i] = pt_clamp(acc);
+            stage[i] = pcm_clamp(acc);
         }
         wg_barrier_lds();
         // the hop's samples leave: plain stores up to the first 16-byte boundary of the destination, whole vectors, plain stores behind them
@@ -126,31 +82,26 @@ __global__ void __launch_bounds__(PT_THREADS) k_tsm_pitch(PitchArgs a) {
         const int nv = (cnt - head) / per, tail0 = head + nv * per;
         if (mt.enc == Q3_PCM_S16) {
             uint16_t* o16 = reinterpret_cast<uint16_t*>(o);
-            for (int v = tid; v < nv; v += PT_THREADS) {
+            for (int v = tid; v < nv; v += WS_THREADS) {
                 const float* s = stage + head + 8 * v;
-                uint4 w;
-                w.x = pt_s16(s[0]) | (pt_s16(s[1]) << 16); w.y = pt_s16(s[2]) | (pt_s16(s[3]) << 16);
-                w.z = pt_s16(s[4]) | (pt_s16(s[5]) << 16); w.w = pt_s16(s[6]) | (pt_s16(s[7]) << 16);
-                *reinterpret_cast<uint4*>(o16 + head + 8 * v) = w;
+                *reinterpret_cast<uint4*>(o16 + head + 8 * v) = pcm_pack8(make_float4(s[0], s[1], s[2], s[3]), make_float4(s[4], s[5], s[6], s[7]));
             }
-            for (int i = tid; i < head + (cnt - tail0); i += PT_THREADS) { const int e = i < head ? i : tail0 + (i - head); o16[e] = (uint16_t)pt_s16(stage[e]); }
+            for (int i = tid; i < head + (cnt - tail0); i += WS_THREADS) { const int e = i < head ? i : tail0 + (i - head); o16[e] = (uint16_t)pcm_s16(stage[e]); }
         } else {
             float* o32 = reinterpret_cast<float*>(o);
-            for (int v = tid; v < nv; v += PT_THREADS) {
+            for (int v = tid; v < nv; v += WS_THREADS) {
                 const float* s = stage + head + 4 * v;
                 *reinterpret_cast<float4*>(o32 + head + 4 * v) = make_float4(s[0], s[1], s[2], s[3]);
             }
-            for (int i = tid; i < head + (cnt - tail0); i += PT_THREADS) { const int e = i < head ? i : tail0 + (i - head); o32[e] = stage[e]; }
+            for (int i = tid; i < head + (cnt - tail0); i += WS_THREADS) { const int e = i < head ? i : tail0 + (i - head); o32[e] = stage[e]; }
         }
         if (tid < Q3_PITCH_HIST) zb[tid] = zb[Q3_TSM_HOP + tid];   // the last 64 of z move to the front: nobody else touches either range here
         if (tid == 0 && a.trace) a.trace[mt.trace_off + f] = d;
         d_prev = d;
         // the next frame's window, keys, hop and samples are written behind barriers that follow every read of this frame's
     }
-    __syncthreads();   // every read of the histories is done: the stream's only workgroup replaces them
-    if (a.T >= Q3_TSM_HIST) for (int i = tid; i < Q3_TSM_HIST; i += PT_THREADS) h[i] = x[a.T - Q3_TSM_HIST + i];
+    wsola_finish(x, a.T, h, a.d_prev + mt.slot, d_prev);   // behind its barrier every read of the histories is done
     if (tid < Q3_PITCH_HIST) zh[tid] = zb[tid];
-    if (tid == 0) a.d_prev[mt.slot] = d_prev;
 }
 
 // all 151 tables are built once per process (1.47 MB of floats, a few milliseconds) and uploaded once per shifter
@@ -179,15 +130,8 @@ PitchShifter::PitchShifter(int n_streams_, int max_group_) : n_streams(n_streams
     hist = hist_own.p; zhist = zhist_own.p;
     d_prev.alloc((size_t)n_streams); d_prev.zero();
     Q3_HIP(hipStreamSynchronize(nullptr)); // the memsets ran on the null stream, which the caller's non-blocking streams do not wait for
-    d_ring.alloc((size_t)PT_RING * max_group);
-    Q3_HIP(hipHostMalloc((void**)&h_ring, sizeof(PitchStreamMeta) * PT_RING * max_group));
+    ring.alloc(max_group);
     n_seen.assign((size_t)n_streams, 0); k_done.assign((size_t)n_streams, 0);
-    ring_ev.resize(PT_RING); ring_used.assign(PT_RING, 0);
-    for (auto& e : ring_ev) Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-}
-PitchShifter::~PitchShifter() {
-    for (auto e : ring_ev) if (e) (void)hipEventDestroy(e);
-    if (h_ring) (void)hipHostFree(h_ring);
 }
 
 void PitchShifter::reset_async(hipStream_t st, int slot) {
@@ -211,11 +155,8 @@ void launch_tsm_pitch(hipStream_t st, PitchShifter& s, const float* in, int G, i
         Q3_CHECK(out_off[g] >= 0 && (dst & (enc[g] == Q3_PCM_S16 ? 1u : 3u)) == 0, "misaligned output");
     }
     if (!any) return;   // no stream has a pitch: nothing to run
-    const int rs = s.ring_idx;   // the slot's previous launch, on whichever stream it ran, has consumed its upload
-    s.ring_idx = (s.ring_idx + 1) % PT_RING;
-    if (s.ring_used[(size_t)rs]) Q3_HIP(hipEventSynchronize(s.ring_ev[(size_t)rs]));
-    const size_t slot0 = (size_t)rs * s.max_group;
-    PitchStreamMeta* hm = s.h_ring + slot0;
+    const PitchStreamMeta* dm;
+    PitchStreamMeta* hm = s.ring.take(&dm);
     for (int g = 0; g < G; g++) {
         PitchStreamMeta& m = hm[g];
         m = PitchStreamMeta{};
@@ -233,11 +174,10 @@ void launch_tsm_pitch(hipStream_t st, PitchShifter& s, const float* in, int G, i
         seen += T; done = total;
         s.chunks += T > 0; s.samples_out += n_out[g]; s.flushes += flush;
     }
-    Q3_HIP(hipMemcpyAsync(s.d_ring.p + slot0, hm, sizeof(PitchStreamMeta) * G, hipMemcpyHostToDevice, st));
-    PitchArgs a{in, T, s.d_ring.p + slot0, s.wins.p, s.tabs.p, s.hist, s.zhist, s.d_prev.p, (unsigned char*)out, trace};
-    hipLaunchKernelGGL(k_tsm_pitch, dim3((unsigned)G), dim3(PT_THREADS), 0, st, a);
-    Q3_HIP(hipEventRecord(s.ring_ev[(size_t)rs], st));
-    s.ring_used[(size_t)rs] = 1;
+    s.ring.commit(st, G);
+    PitchArgs a{in, T, dm, s.wins.p, s.tabs.p, s.hist, s.zhist, s.d_prev.p, (unsigned char*)out, trace};
+    hipLaunchKernelGGL(k_tsm_pitch, dim3((unsigned)G), dim3(WS_THREADS), 0, st, a);
+    s.ring.launched(st);
 }
 
 } // namespace q3

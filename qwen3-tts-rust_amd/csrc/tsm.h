@@ -22,21 +22,30 @@ inline void tsm_windows(float* w, float* w2) {
 constexpr int tsm_visit_order(int d) { return d == 0 ? 0 : (d < 0 ? -2 * d - 1 : 2 * d); }
 constexpr int tsm_offset_of_order(int o) { return (o & 1) ? -((o + 1) >> 1) : (o >> 1); }
 
-// what a stretch launch refuses (nullptr = it may run): G streams of T native samples each, streams[] slots of an n_streams state store,
-// stream g at pct[g] percent (100: the stream is not touched) in encoding enc[g].  T = 0 is a flush alone
-inline const char* tsm_launch_refusal(int G, int max_group, int64_t T, bool flush, const int32_t* streams, int n_streams, const int32_t* pct,
-                                      const int32_t* enc) {
+// what a stretch launch and a pitch launch refuse alike, in the order both state it: G streams of T native samples each (T = 0 is a flush
+// alone), streams[] slots of an n_streams state store, encodings enc[].  no_nulls / null_text: whether the caller's arrays are all there,
+// and what it says when not; why_not(g): what stream g's rate or pair is refused for, asked between its slot and its encoding
+template <class WhyNot>
+inline const char* prosody_launch_refusal(int G, int max_group, int64_t T, bool flush, const int32_t* streams, int n_streams, const int32_t* enc,
+                                          bool no_nulls, const char* null_text, WhyNot why_not) {
     if (G < 1 || G > max_group) return "group size out of range";
     if (T < 0 || T % Q3_TSM_HIST != 0 || (T == 0 && !flush)) return "chunk length is no positive multiple of 1920 samples";
     if (T > (int64_t)1 << 24) return "chunk too long";
-    if (!streams || !pct || !enc) return "null streams / rates / encodings";
+    if (!no_nulls) return null_text;
     for (int g = 0; g < G; g++) {
         if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
         for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
-        if (const char* why = tsm_rate_why_not(pct[g])) return why;
+        if (const char* why = why_not(g)) return why;
         if (enc[g] != Q3_PCM_F32 && enc[g] != Q3_PCM_S16) return "unknown encoding";
     }
     return nullptr;
+}
+
+// what a stretch launch refuses (nullptr = it may run): stream g at pct[g] percent (100: the stream is not touched) in encoding enc[g]
+inline const char* tsm_launch_refusal(int G, int max_group, int64_t T, bool flush, const int32_t* streams, int n_streams, const int32_t* pct,
+                                      const int32_t* enc) {
+    return prosody_launch_refusal(G, max_group, T, flush, streams, n_streams, enc, streams && pct && enc, "null streams / rates / encodings",
+                                  [&](int g) { return tsm_rate_why_not(pct[g]); });
 }
 
 } // namespace q3
