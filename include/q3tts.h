@@ -248,6 +248,25 @@ int q3tts_engine_tsm_stats(q3tts_engine* e, int64_t* chunks, int64_t* frames_out
 int q3tts_engine_set_pitch(q3tts_engine* e, int32_t pitch_pct);
 int q3tts_request_pitch(q3tts_engine* e, int64_t req_id, int32_t* pitch_pct);
 int q3tts_engine_pitch_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes);
+/* [EXT] volume (q3tts_spec.h "volume"): a request's loudness is changed on the device, behind the output conv and in front of every other
+ * output stage: a gain in dB with a look-ahead peak limiter, so that a boost never clips and an s16 request is quantised after the gain, not
+ * before it.  Opt-in per request; a request with volume 0 keeps its launches and its bytes, and codes and log-probability rows never depend
+ * on the volume.
+ * q3tts_engine_set_volume: requests submitted from now on, through any q3tts_submit* form with want_pcm (text, trailing, open, resume,
+ * candidates, decode), get a gain of db10 tenths of a dB, an integer in [-400, 200]; 0 = off.  Read once per request at submit and once per
+ * candidate set, together with the speaking rate and the pitch.  Thread-safe; works under Q3_SPEC=ggml.  < 0: out of range, or an engine
+ * without a codec.
+ * It composes with every output format, rate and pitch, whose counts, offsets and staging rules are unchanged: n native samples in give n
+ * out.  The stream is delayed by Q3_VOL_DELAY = 127 native samples (5.3 ms), which are not flushed: the first 127 native samples of a
+ * request with a volume are zeros and its last 127 do not come out.  A cancelled request keeps what it has.
+ * Not volumed: want_pcm = 0, q3tts_generate_batch*, scoring, preamble builds.  A primed request starts the stage from a reset; one with a
+ * converted format keeps the converter's restored history, the preamble's last native samples as they were decoded, without the gain.
+ * q3tts_request_volume: the volume a request was submitted with (0 when none was set).
+ * q3tts_engine_volume_stats: stream chunks the stage has taken and native samples it has rewritten (both 0 while no request had a volume;
+ * the state store is allocated by the first such request). */
+int q3tts_engine_set_volume(q3tts_engine* e, int32_t db10);
+int q3tts_request_volume(q3tts_engine* e, int64_t req_id, int32_t* db10);
+int q3tts_engine_volume_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples);
 /* [EXT] codec preambles (q3tts_spec.h "codec preambles"): a request's codec stream starts from the state behind given frames -- a clone
  * voice's reference codes -- instead of zeros, so its first sample is already "in the voice".  The state is built once per preamble and
  * kept on the device; a primed request restores it with one device-to-device launch where the zeroing launch ran.  Opt-in; codes,
@@ -467,6 +486,8 @@ int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct);   /* [EXT] q3
 int q3tts_group_request_speech_rate(q3tts_group* g, int64_t req_id, int32_t* rate_pct);
 int q3tts_group_set_pitch(q3tts_group* g, int32_t pitch_pct);   /* [EXT] q3tts_engine_set_pitch on every engine */
 int q3tts_group_request_pitch(q3tts_group* g, int64_t req_id, int32_t* pitch_pct);
+int q3tts_group_set_volume(q3tts_group* g, int32_t db10);   /* [EXT] q3tts_engine_set_volume on every engine */
+int q3tts_group_request_volume(q3tts_group* g, int64_t req_id, int32_t* db10);
 /* [EXT] codec preambles on every engine under one id, as voices are (create preambles through the group only); _wait waits for all of them */
 int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id);
 int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms);
@@ -1064,6 +1085,27 @@ int q3tts_op_pitch(const float* in, int32_t G, const int32_t* chunk_samples, int
                    const int32_t* rate_pct, const int32_t* pitch_pct, const int32_t* encoding, const int32_t* reset_before, int32_t flush,
                    void* const* out, const int64_t* out_bytes, int64_t* n_out, int32_t* const* delta_trace, const int64_t* trace_len,
                    float* hist_store, float* zhist_store);
+
+/* [EXT] volume (q3tts_spec.h "volume"): the gain and limiter stage on the device, behind the output conv.
+ * Host only, no device needed:
+ *   q3tts_volume_gain    G = (float) pow(10.0, db10 / 200.0) of a volume in tenths of a dB; NaN for one outside [Q3_VOL_MIN, Q3_VOL_MAX]
+ * q3tts_op_volume is the test surface of the volume kernel.  G streams run through n_chunks launches of the engine's launcher, one per chunk,
+ * on a fresh stage; each launch rewrites a copy of the chunk in place, as a decode pass rewrites the output conv's buffer, and every
+ * stream's T samples are then appended to its output.  A stream with volume 0 is not touched and comes out as it went in.
+ *   in            [n_chunks] chunks one after the other, each [G][chunk_samples[c]] native f32 samples
+ *   chunk_samples [n_chunks], each a positive multiple of 1920
+ *   streams       [n_chunks][G] state slots in [0, n_streams); reset_before [n_chunks][G] (optional): nonzero = the slot is reset first
+ *   vol_db10      [G]
+ *   out[g]        in/out, WHOLE: Q3TTS_GLUE_GUARD floats, the stream's samples, Q3TTS_GLUE_GUARD floats; out_bytes[g] = its size in bytes
+ *   n_out[g]      the samples of stream g (the sum of the chunks)
+ *   gain_trace    optional (NULL: none).  gain_trace[g]: in/out, WHOLE, guarded like out[g]: g[n] of every sample, trace_len[g] floats in all;
+ *                 a stream with volume 0 leaves its core unwritten
+ *   hist_store    in/out, WHOLE: Q3TTS_GLUE_GUARD floats, [n_streams][Q3_VOL_HIST], Q3TTS_GLUE_GUARD floats
+ * Everything is checked before anything is launched; a refused call leaves every buffer unwritten. */
+float q3tts_volume_gain(int32_t db10);
+int q3tts_op_volume(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                    const int32_t* vol_db10, const int32_t* reset_before, float* const* out, const int64_t* out_bytes, int64_t* n_out,
+                    float* const* gain_trace, const int64_t* trace_len, float* hist_store);
 
 #ifdef __cplusplus
 }

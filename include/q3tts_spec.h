@@ -531,6 +531,37 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3_PITCH_MAX 200
 #define Q3_PITCH_HIST 64         /* intermediate samples of history per stream */
 
+/* ---------------- volume [EXT] (q3tts_engine_set_volume, q3tts_volume_gain, q3tts_op_volume) ----------------
+ * A gain with a look-ahead peak limiter on the native 24000 Hz stream, behind the output conv and in front of every other output stage
+ * ("output formats", "speaking rate", "pitch"): it rewrites the native samples those stages read, so it composes with all of them and a
+ * boost never clips.  x[n] is the stream's native f32 samples since its reset (the output conv's clamped values), y[n] what replaces them;
+ * every position is a sample index counted from the stream's reset.
+ *   volume     db10, an integer in tenths of a dB in [Q3_VOL_MIN, Q3_VOL_MAX].  0 means off: nothing of this section runs.
+ *              G = (float) pow(10.0, db10 / 200.0), computed on the host in double and rounded once (q3tts_volume_gain; NaN out of range)
+ *   input      v[n] = G * x[n], one f32 multiply; v[n < 0] = 0
+ *   required   r[j] = 1 for j < 0 or |v[j]| <= 1, else r[j] = 1.0f / |v[j]|, the correctly rounded f32 quotient
+ *   hold       m[k] = min r[k - (Q3_VOL_HOLD - 1) .. k]; exact, whatever the order
+ *   smoothing  s_0 = m, s_{i+1}[k] = s_i[k - 2^i] + s_i[k] for i = 0 .. 6 in f32: s_7[k] is the sum of m[k - 127 .. k] in that fixed tree
+ *              (Q3_VOL_LOOK = 128 terms); g[n] = 0x1p-7f * s_7[n]
+ *   output     y[n] = clamp(g[n] * v[n - Q3_VOL_DELAY], -1, 1), one f32 multiply.  In exact arithmetic |g[n] v[n - 127]| <= 1, since every
+ *              hold window [k - 511, k] with k in [n - 127, n] contains n - 127: the clamp only removes rounding residue.  Where every |v| of
+ *              the window is <= 1, g = 1 exactly (128 ones sum exactly) and y[n] = v[n - 127] bit for bit: any attenuation, and a boost of a
+ *              quiet signal
+ *   delay      Q3_VOL_DELAY = 127 native samples (5.3 ms).  Nothing is flushed, as with the converter's delay: the last 127 native samples of
+ *              an utterance do not come out.  n native samples in give n samples out per chunk, so every count, offset and staging rule of
+ *              the later stages is unchanged (q3tts_pcm_out_samples, q3tts_tsm_samples, q3tts_pitch_samples)
+ *   state      per stream the last Q3_VOL_HIST = Q3_VOL_HOLD - 1 + Q3_VOL_DELAY values of v; zeroed by the stream's reset and by a preamble
+ *              restore (a primed request starts from a reset).  No data-dependent counters: y depends on n and the stream alone, never on
+ *              how the stream was cut into chunks
+ *   error      given the same f32 v, y lies within 10 u |y64| + 2^-149 of the float64 evaluation and g within 8 u |g64|, u = 2^-24: one
+ *              rounding in r, none in the minimum, seven in the tree of non-negative adds, one in the product */
+#define Q3_VOL_MIN -400
+#define Q3_VOL_MAX 200
+#define Q3_VOL_LOOK 128          /* terms of the smoothing sum */
+#define Q3_VOL_HOLD 512          /* samples of the hold minimum */
+#define Q3_VOL_DELAY 127         /* native samples the stream is delayed by */
+#define Q3_VOL_HIST 638          /* = Q3_VOL_HOLD - 1 + Q3_VOL_DELAY: values of v kept per stream */
+
 /* ---------------- prompt stems [EXT] (q3tts_stem_*, q3tts_op_kv_stem) ----------------
  * A stem is n rows [n][2048] f32, 1 <= n < max_prompt, together with the talker K/V of those rows at positions 0 .. n-1: the head a voice's
  * prompts share, prefilled once, kept on the device in a store of its own (ceil(n / 64) whole pages per plane, the pool's page layout) and

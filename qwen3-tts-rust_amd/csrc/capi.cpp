@@ -416,6 +416,22 @@ int q3tts_engine_pitch_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples_
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] volume */
+int q3tts_engine_set_volume(q3tts_engine* e, int32_t db10) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_volume(db10); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_volume(q3tts_engine* e, int64_t id, int32_t* db10) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && db10, "null argument");
+    *db10 = e->e->request_volume(id);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_volume_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && chunks && samples, "null argument");
+    e->e->volume_stats(chunks, samples);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

@@ -8,6 +8,7 @@
 #include "pcm_out.h"
 #include "tsm.h"
 #include "pitch.h"
+#include "volume.h"
 #include <memory>
 #include "mel.h"
 
@@ -1437,6 +1438,41 @@ int q3tts_op_pitch(const float* in, int32_t G, const int32_t* chunk_samples, int
     }
     r.finish(n_out, &need, "the launchers' counts differ from the plan");
     hist.download(); zhist.download();
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] volume: the host-only half (sched_logic.h) */
+float q3tts_volume_gain(int32_t db10) { return volume_gain(db10); }
+
+/* [EXT] the volume kernel over guarded host buffers (include/q3tts.h): one launch_volume per chunk, in place on the run's copy of the chunk
+ * as a decode pass runs it on the output conv's buffer; each stream's samples are then appended behind its earlier ones inside its guarded
+ * buffer on the device, everything downloaded whole. */
+int q3tts_op_volume(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                    const int32_t* vol_db10, const int32_t* reset_before, float* const* out, const int64_t* out_bytes, int64_t* n_out,
+                    float* const* gain_trace, const int64_t* trace_len, float* hist_store) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(in && chunk_samples && streams && vol_db10 && out && out_bytes && n_out && (!gain_trace || trace_len) && hist_store, "null argument");
+    Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
+    // every chunk is checked as its launch will be before anything is allocated
+    for (int c = 0; c < n_chunks; c++)
+        if (const char* why = volume_launch_refusal(G, G, chunk_samples[c], streams + (size_t)c * G, n_streams, vol_db10)) throw Error(std::string("volume: ") + why);
+    int64_t total = 0;
+    for (int c = 0; c < n_chunks; c++) total += chunk_samples[c];
+    const std::vector<int64_t> esz((size_t)G, 4), need((size_t)G, total * 4), entries((size_t)G, total);
+    GuardedRun r(in, G, chunk_samples, n_chunks, false, streams, reset_before, esz, need, &entries, reinterpret_cast<void* const*>(out), out_bytes,
+                 reinterpret_cast<int32_t* const*>(gain_trace), trace_len);   // a trace entry is four bytes, whatever it holds
+    GuardedStore hist(hist_store, (size_t)n_streams * Q3_VOL_HIST);
+    VolumeStage vs(n_streams, G);
+    vs.hist = hist.core();
+    while (r.next()) {
+        for (int g = 0; g < G; g++) if (r.reset(g)) vs.reset_async(0, r.sl[g]);
+        launch_volume(0, vs, const_cast<float*>(r.x), G, r.T, r.sl, vol_db10, gain_trace ? reinterpret_cast<float*>(r.d_trace.p) : nullptr, r.toff.data());
+        for (int g = 0; g < G; g++) { r.copy_native(g); r.fr[g] += r.T; }
+    }
+    r.finish(n_out, &need, "the chunks differ from the plan");
+    hist.download();
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

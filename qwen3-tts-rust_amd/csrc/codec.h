@@ -51,7 +51,8 @@ public:
     // stream's copy takes its T*L/M samples of 4 or 2 bytes from the converted buffer; pcm_pinned[g] then receives those bytes.  n_out[g]
     // (optional) = the samples stream g was given.  The converter's tables, history store and per-lane buffers are allocated on first use
     int decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm_pinned, int lane = 0,
-                           const q3tts_pcm_format* fmt = nullptr, int64_t* n_out = nullptr, const int32_t* rate = nullptr, const int32_t* pitch = nullptr);
+                           const q3tts_pcm_format* fmt = nullptr, int64_t* n_out = nullptr, const int32_t* rate = nullptr, const int32_t* pitch = nullptr,
+                           const int32_t* volume = nullptr);
     // [EXT] speaking rate (q3tts_spec.h): rate[g] = the percent stream g is spoken at.  NULL, or every entry 100, is the call without it, launch
     // for launch.  Otherwise one stretch launch (tsm.hip) follows the output conv on `st`; a stretching stream delivers 24000 Hz in fmt[g]'s
     // encoding (f32 when fmt is NULL), the converter leaves it alone, and its copy takes the n_out[g] samples that became available -- 480 a
@@ -63,7 +64,12 @@ public:
     // holds a stream with a rate alone; a stream with a pitch runs at the tempo rate[g] / pitch[g], delivers 24000 Hz in fmt[g]'s encoding, and
     // its copy takes the n_out[g] samples that became available.  tsm_flush_async ends its utterance too.  All 151 tap tables, the state stores
     // and the per-lane buffers are made by the first call that shifts
+    // [EXT] volume (q3tts_spec.h "volume"): volume[g] = stream g's volume in tenths of a dB.  NULL, or every entry 0, is the call without it,
+    // launch for launch.  Otherwise one volume launch (volume.hip) follows the output conv on `st` and rewrites the chunks of the streams with a
+    // volume in place, in front of whatever stage or copy takes them next: no count changes.  The state store is made by the first call with a
+    // volume; a reset and a snapshot restore zero a stream's entry
     void tsm_flush_async(hipStream_t st, int stream, void* dst, int64_t* n_out, int lane = 0);
+    void volume_stats(int64_t* chunks, int64_t* samples) const; // stream chunks the volume stage took, samples it rewrote
     void pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const; // stream chunks shifted, samples delivered, flushes, bytes of tap tables
     void tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const; // stream chunks the stretcher took, synthesis frames made, flushes
     void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks the converter took, output samples it made

@@ -13,6 +13,7 @@
 #include "pcm_out.h"
 #include "tsm.h"
 #include "pitch.h"
+#include "volume.h"
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -1206,9 +1207,26 @@ struct CodecDecoder::Impl {
         stage.reset(new Stage(n_streams, gmax));
         return true;
     }
+    // [EXT] volume: the stage is made by the first pass that holds a stream with a volume, under capture_mutex(); it has no buffers of its own
+    std::unique_ptr<VolumeStage> volume;
+    std::atomic<int64_t> vol_chunks{0}, vol_samples{0};
+    void run_volume(hipStream_t st, int G, int T, const int32_t* streams, const int32_t* db10) {   // one launch over the chunk in S->pcm
+        bool any = false;
+        for (int g = 0; g < G; g++) any = any || db10[g] != 0;
+        if (!any) return;
+        if (!volume) {
+            std::lock_guard<std::mutex> cap(capture_mutex());
+            volume.reset(new VolumeStage(n_streams, gmax));
+        }
+        const int64_t c0 = volume->chunks, s0 = volume->samples;
+        launch_volume(st, *volume, S->pcm.p, G, T, streams, db10);
+        Q3_LAUNCH_CHECK();
+        vol_chunks += volume->chunks - c0; vol_samples += volume->samples - s0;
+    }
     void prosody_reset(hipStream_t st, int s) {
         if (tsm) tsm->reset_async(st, s);
         if (pitch) pitch->reset_async(st, s);
+        if (volume) volume->reset_async(st, s);
         if (!prosody.empty()) prosody[(size_t)s] = Prosody{};
     }
     // one launch of a stage over the chunk in S->pcm (in = false: a flush alone) and its accounting
@@ -1521,13 +1539,14 @@ void CodecDecoder::reset(int s) {
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
     if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
-    if (m.tsm || m.pitch) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
+    if (m.tsm || m.pitch || m.volume) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 void CodecDecoder::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
     *chunks = impl_->pitch_chunks.load(); *samples_out = impl_->pitch_samples.load(); *flushes = impl_->pitch_flushes.load();
     *table_bytes = impl_->pitch_table_bytes.load();
 }
+void CodecDecoder::volume_stats(int64_t* chunks, int64_t* samples) const { *chunks = impl_->vol_chunks.load(); *samples = impl_->vol_samples.load(); }
 void CodecDecoder::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
     *chunks = impl_->tsm_chunks.load(); *frames_out = impl_->tsm_frames.load(); *flushes = impl_->tsm_flushes.load();
 }
@@ -1613,7 +1632,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     }
     flush();
     if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
-    m.prosody_reset(st, s);                 // and so are the stretcher's state and the pitch shifter's
+    m.prosody_reset(st, s);                 // and so are the stretcher's state, the pitch shifter's and the volume stage's
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1664,7 +1683,7 @@ void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* p
         m.ensure_conv();
         Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
     }
-    m.prosody_reset(st, s); // [EXT] speaking rate / pitch: a primed stream's stretcher and both stages of its pitch shifter start from a reset
+    m.prosody_reset(st, s); // [EXT] speaking rate / pitch / volume: a primed stream's stretcher, both stages of its pitch shifter and its volume stage start from a reset
     m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
 }
 void CodecDecoder::snapshot_free(int snap) {
@@ -1688,7 +1707,7 @@ int CodecDecoder::decode_async(hipStream_t st, int s, const int64_t* codes, int 
 // One pass for G streams that each contribute n_frames new frames: every GEMM runs over G*T rows, so the 733 MB of
 // codec weights are streamed once per group instead of once per stream, and one set of launches serves the group.
 int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane,
-                                     const q3tts_pcm_format* fmt, int64_t* n_out, const int32_t* rate, const int32_t* pitch) {
+                                     const q3tts_pcm_format* fmt, int64_t* n_out, const int32_t* rate, const int32_t* pitch, const int32_t* volume) {
     Impl& m = *impl_;
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     Q3_CHECK(G >= 1 && G <= m.gmax, "group size out of range");
@@ -1796,6 +1815,7 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
+    if (volume) m.run_volume(st, G, T, streams, volume);   // [EXT] volume: in place, in front of every stage deliver runs
     m.deliver(st, G, streams, T, pcm, lane, fmt, n_out, rate, pitch);
     return T;
 }

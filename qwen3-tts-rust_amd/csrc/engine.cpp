@@ -220,6 +220,8 @@ struct Engine::Req {
     // [EXT] pitch: the percent the request's pitch is shifted to, read with the rate at submit (100: off).  With a pitch the delivered counts are
     // pitch_out_samples(rate_pct, pitch_pct, tsm_native, .) and the stream is the pitch shifter's, not the stretcher's
     int pitch_pct = 100;
+    // [EXT] volume: the request's volume in tenths of a dB, read with the rate and the pitch at submit (0: off).  It changes no count
+    int vol_db10 = 0;
     bool stretched() const { return rate_pct != 100 || pitch_pct != 100; }
     int64_t prosody_samples(int64_t n_native, bool final) const {
         return pitch_pct != 100 ? pitch_out_samples(rate_pct, pitch_pct, n_native, final) : tsm_out_samples(rate_pct, n_native, final);
@@ -731,11 +733,13 @@ void Engine::decoder_main() {
                 std::vector<q3tts_pcm_format> fmt(G); std::vector<int64_t> n_out(G); bool converts = false; // [EXT] output formats
                 std::vector<int32_t> rate(G); bool stretches = false;                                       // [EXT] speaking rate
                 std::vector<int32_t> pitch(G); bool shifts = false;                                         // [EXT] pitch
+                std::vector<int32_t> vol(G); bool volumes = false;                                          // [EXT] volume
                 for (int g = 0; g < G; g++) {
                     Req* r = grp[g].r;
                     fmt[g] = r->fmt; converts = converts || !pcm_format_native(r->fmt);
                     size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
                     rate[g] = r->rate_pct; pitch[g] = r->pitch_pct;
+                    vol[g] = r->vol_db10; volumes = volumes || r->vol_db10 != 0;
                     if (r->stretched()) { // the samples that become available with these frames: possibly none, at a slow rate more than native
                         stretches = converts = true; shifts = shifts || r->pitch_pct != 100;
                         add = (size_t)(r->prosody_samples(r->tsm_native + (int64_t)nf * spf, false) - r->prosody_samples(r->tsm_native, false)) * r->sample_bytes();
@@ -746,7 +750,8 @@ void Engine::decoder_main() {
                 }
                 // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
                 const int got = codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane,
-                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr, stretches ? rate.data() : nullptr, shifts ? pitch.data() : nullptr);
+                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr, stretches ? rate.data() : nullptr, shifts ? pitch.data() : nullptr,
+                                                           volumes ? vol.data() : nullptr);
                 for (int g = 0; g < G; g++) grp[g].r->pcm_enq += converts ? (size_t)n_out[g] : (size_t)std::max(got, 0);
             }
             // [EXT] speaking rate: the fence of a stretching request that was not cancelled flushes its stretcher -- the hops its last samples
@@ -978,7 +983,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->shared = sh;
         r->want_pcm = want_pcm && codec_;
         if (r->want_pcm) r->fmt = set_fmt;
-        if (r->want_pcm) take_rate(r.get(), g.max_steps, i == 0 ? -1 : rs[0]->rate_pct, i == 0 ? -1 : rs[0]->pitch_pct); // [EXT] the speech rate and the pitch, read once per set
+        if (r->want_pcm) take_rate(r.get(), g.max_steps, i == 0 ? -1 : rs[0]->rate_pct, i == 0 ? -1 : rs[0]->pitch_pct, i == 0 ? nullptr : &rs[0]->vol_db10); // [EXT] the speech rate, the pitch and the volume, read once per set
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
@@ -1665,11 +1670,16 @@ void Engine::set_speech_rate(int pct) {
     rate_pct_ = pct;
 }
 // the engine's rate (or `given`, the one a candidate set's first member read) becomes the request's, if the request's format and length allow it
-void Engine::take_rate(Req* r, int max_steps, int given, int given_pitch) const {
-    int pct, pitch;
-    {   // [EXT] pitch: the two settings are read together, so that the pair rule judges a pair somebody set
+void Engine::take_rate(Req* r, int max_steps, int given, int given_pitch, const int* given_vol) const {
+    int pct, pitch, vol;
+    {   // [EXT] pitch: the two settings are read together, so that the pair rule judges a pair somebody set; [EXT] volume: read with them
         std::lock_guard<std::mutex> lk(prosody_mu_);
         pct = given >= 0 ? given : rate_pct_.load(); pitch = given_pitch >= 0 ? given_pitch : pitch_pct_.load();
+        vol = given_vol ? *given_vol : vol_db10_.load();
+    }
+    if (vol != 0) {   // a refusal below throws as well, and the request is dropped with what it was given here
+        if (const char* why = volume_submit_refusal(vol, codec_ != nullptr)) throw Error(why);
+        r->vol_db10 = vol;
     }
     if (pitch != 100) {
         if (const char* why = pitch_submit_refusal(pct, pitch, r->fmt, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
@@ -1698,6 +1708,20 @@ int Engine::request_pitch(int64_t id) {
 void Engine::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
     *chunks = *samples_out = *flushes = *table_bytes = 0;
     if (codec_) codec_->pitch_stats(chunks, samples_out, flushes, table_bytes);
+}
+// [EXT] volume (q3tts_spec.h "volume")
+void Engine::set_volume(int db10) {
+    if (const char* why = volume_submit_refusal(db10, codec_ != nullptr)) throw Error(why);
+    std::lock_guard<std::mutex> lk(prosody_mu_);
+    vol_db10_ = db10;
+}
+int Engine::request_volume(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return req(id).vol_db10;
+}
+void Engine::volume_stats(int64_t* chunks, int64_t* samples) const {
+    *chunks = *samples = 0;
+    if (codec_) codec_->volume_stats(chunks, samples);
 }
 void Engine::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
     *chunks = *frames_out = *flushes = 0;

@@ -129,6 +129,12 @@ public:
     void set_pitch(int pct);
     int request_pitch(int64_t id);
     void pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const; // stream chunks shifted, samples delivered, flushes, bytes of tap tables on the device
+    // [EXT] volume (q3tts_spec.h "volume"): requests submitted from now on with want_pcm have a gain of db10 tenths of a dB behind a look-ahead
+    // limiter (0: off), in front of whatever format, rate or pitch they have; read with the rate and the pitch, wherever those are read.
+    // Thread-safe, no HIP calls; throws volume_submit_refusal's reason for a volume outside [-400, 200] or an engine without a codec
+    void set_volume(int db10);
+    int request_volume(int64_t id);
+    void volume_stats(int64_t* chunks, int64_t* samples) const; // stream chunks the stage took, samples it rewrote
     // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
     // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
     // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The
@@ -261,8 +267,9 @@ private:
     std::atomic<int64_t> out_fmt_{(int64_t)Q3_PCM_NATIVE_RATE * 4 + Q3_PCM_F32}; // what submit() reads
     std::atomic<int> rate_pct_{100};                                             // [EXT] speaking rate: what submit() reads
     std::atomic<int> pitch_pct_{100};                                            // [EXT] pitch: what submit() reads, with rate_pct_ under prosody_mu_
+    std::atomic<int> vol_db10_{0};                                               // [EXT] volume: what submit() reads, with the two above under prosody_mu_
     mutable std::mutex prosody_mu_;
-    void take_rate(Req* r, int max_steps, int given = -1, int given_pitch = -1) const;
+    void take_rate(Req* r, int max_steps, int given = -1, int given_pitch = -1, const int* given_vol = nullptr) const;
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).

@@ -15,6 +15,7 @@
 #include "engine.h"
 #include <dlfcn.h>
 #include <atomic>
+#include <cmath>
 
 using namespace q3;
 
@@ -423,6 +424,11 @@ int q3tts_group_request_pitch(q3tts_group* g, int64_t req_id, int32_t* pitch_pct
 int q3tts_group_set_pitch(q3tts_group* g, int32_t pitch_pct) { // [EXT] q3tts_engine_set_pitch on every engine: all of them or none
     if (g && q3tts_pitch_plan(pitch_pct, nullptr, nullptr, nullptr, nullptr) != Q3TTS_OK) { set_last_error("pitch out of range [50, 200]"); return Q3TTS_ERR; }
     return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_pitch(e, pitch_pct); });
+}
+int q3tts_group_request_volume(q3tts_group* g, int64_t req_id, int32_t* db10) { return routed(g, req_id, q3tts_request_volume, db10); }
+int q3tts_group_set_volume(q3tts_group* g, int32_t db10) { // [EXT] q3tts_engine_set_volume on every engine: all of them or none
+    if (g && std::isnan(q3tts_volume_gain(db10))) { set_last_error("volume out of range [-400, 200]"); return Q3TTS_ERR; }
+    return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_volume(e, db10); });
 }
 int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) {
     if (g && q3tts_tsm_samples(rate_pct, 0, 0) < 0) { set_last_error("speech rate out of range [50, 200]"); return Q3TTS_ERR; }

@@ -459,4 +459,29 @@ void launch_tsm_pitch(hipStream_t st, PitchShifter& s, const float* in, int G, i
                       const int32_t* pitch, const int32_t* enc, void* out, const int64_t* out_off, int64_t* n_out, int32_t* trace = nullptr,
                       const int64_t* trace_off = nullptr);
 
+// [EXT] volume (volume.hip, q3tts_spec.h "volume"): a gain with a look-ahead peak limiter, in place on the native chunk, in front of the other
+// output stages.  One entry per stream of a launch, written by launch_volume into the stage's upload ring.
+struct VolStreamMeta {
+    float gain;               // G of the stream's volume
+    int32_t slot;             // state store entry; -1: the stream has no volume, its workgroup exits at once
+    int64_t trace_off;        // first entry of the launch's `trace` (unused when that is NULL)
+};
+// The stage's device state: the store [n_streams][Q3_VOL_HIST] (a stream's last 638 values of v) and an upload ring as the other stages'.
+// There are no counters: the stage maps sample n to sample n.  One owner thread, as for the stretcher.
+struct VolumeStage {
+    VolumeStage(int n_streams, int max_group);
+    VolumeStage(const VolumeStage&) = delete; VolumeStage& operator=(const VolumeStage&) = delete;
+    void reset_async(hipStream_t st, int slot);    // zeroes the slot's store: its next sample is sample 0 of a stream
+    int n_streams, max_group;
+    float* hist;                                   // = hist_own.p, or a caller's store of the same shape (the test entry point's guarded one)
+    DevBuf<float> hist_own; UploadRing<VolStreamMeta> ring;
+    int64_t chunks = 0, samples = 0;
+};
+// pcm [G][T] native samples (T a multiple of 1920, pcm 16-byte aligned), rewritten in place: stream g of state slot streams[g] at db10[g]
+// tenths of a dB becomes y of "volume".  A stream at 0 is not touched.  trace (optional, device) receives g[n] of every sample made, stream
+// g's from entry trace_off[g] on.  Nothing runs when no stream has a volume.
+// Refused (volume_launch_refusal, volume.h) before anything is uploaded or launched.
+void launch_volume(hipStream_t st, VolumeStage& s, float* pcm, int G, int T, const int32_t* streams, const int32_t* db10, float* trace = nullptr,
+                   const int64_t* trace_off = nullptr);
+
 } // namespace q3

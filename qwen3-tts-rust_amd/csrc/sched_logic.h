@@ -1,9 +1,10 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -608,6 +609,17 @@ inline const char* pitch_submit_refusal(int R, int P, const q3tts_pcm_format& f,
     if (pitch_out_samples(R, P, (int64_t)max_steps * Q3_PCM_FRAME, true) * (f.encoding == Q3_PCM_S16 ? 2 : 4) > cap_bytes)
         return "max_steps at this speech rate and pitch makes more PCM than a request's staging holds";
     return nullptr;
+}
+
+// [EXT] volume (q3tts_spec.h "volume"): which volumes exist, the f32 gain of one, and what a request with a volume may ask for.  The stage
+// changes no count: n native samples in, n out.
+inline const char* volume_why_not(int db10) { return (db10 < Q3_VOL_MIN || db10 > Q3_VOL_MAX) ? "volume out of range [-400, 200]" : nullptr; }
+// G = (float) pow(10.0, db10 / 200.0); NaN for a volume out of range
+inline float volume_gain(int db10) { return volume_why_not(db10) ? std::nanf("") : (float)std::pow(10.0, (double)db10 / 200.0); }
+// the submit rule of a request with volume db10 (0: off, always allowed where there is a codec).  nullptr = it may be queued
+inline const char* volume_submit_refusal(int db10, bool have_codec) {
+    if (!have_codec) return "the engine has no codec";
+    return volume_why_not(db10);
 }
 
 } // namespace q3

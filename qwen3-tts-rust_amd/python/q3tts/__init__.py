@@ -113,6 +113,8 @@ SYMBOLS = [
     "q3tts_group_request_speech_rate", "q3tts_tsm_samples", "q3tts_tsm_windows", "q3tts_op_tsm", "q3tts_mel_tables",
     "q3tts_engine_set_pitch", "q3tts_request_pitch", "q3tts_engine_pitch_stats", "q3tts_group_set_pitch", "q3tts_group_request_pitch",
     "q3tts_pitch_samples", "q3tts_pitch_plan", "q3tts_pitch_filter", "q3tts_op_pitch",
+    "q3tts_engine_set_volume", "q3tts_request_volume", "q3tts_engine_volume_stats", "q3tts_group_set_volume", "q3tts_group_request_volume",
+    "q3tts_volume_gain", "q3tts_op_volume",
 ]
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
@@ -129,6 +131,7 @@ PCM_RATES = (8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000)      # q3tts
 PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
 TSM_HOP, TSM_WIN, TSM_SEARCH, TSM_LOOK, TSM_HIST, TSM_MIN, TSM_MAX = 480, 960, 240, 1200, 1920, 50, 200   # q3tts_spec.h "speaking rate"
 PITCH_MIN, PITCH_MAX, PITCH_HIST = 50, 200, 64                           # q3tts_spec.h "pitch"
+VOL_MIN, VOL_MAX, VOL_LOOK, VOL_HOLD, VOL_DELAY, VOL_HIST = -400, 200, 128, 512, 127, 638   # q3tts_spec.h "volume"
 MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
 PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
 MAX_STEMS = 64                                                           # Q3TTS_MAX_STEMS (q3tts_spec.h "prompt stems")
@@ -334,6 +337,15 @@ def lib():
         L.q3tts_engine_pitch_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
         L.q3tts_group_set_pitch.argtypes = L.q3tts_engine_set_pitch.argtypes
         L.q3tts_group_request_pitch.argtypes = L.q3tts_request_pitch.argtypes
+        L.q3tts_engine_set_volume.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_request_volume.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.q3tts_engine_volume_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 2
+        L.q3tts_group_set_volume.argtypes = L.q3tts_engine_set_volume.argtypes
+        L.q3tts_group_request_volume.argtypes = L.q3tts_request_volume.argtypes
+        L.q3tts_volume_gain.argtypes = [C.c_int32]
+        L.q3tts_volume_gain.restype = C.c_float
+        L.q3tts_op_volume.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.q3tts_pitch_samples.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
         L.q3tts_pitch_samples.restype = C.c_int64
         L.q3tts_pitch_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
@@ -641,6 +653,16 @@ def group_set_pitch(group, pitch_pct=100):
 def group_request_pitch(group, rid):
     """[EXT] q3tts_group_request_pitch: the percent a group request id's pitch is shifted to"""
     return _request_speech_rate(lib().q3tts_group_request_pitch, group, rid)
+
+
+def group_set_volume(group, db10=0):
+    """[EXT] q3tts_group_set_volume on a q3tts_group handle: every engine of the group (tenths of a dB, 0 = off)"""
+    _chk(lib().q3tts_group_set_volume(group, int(db10)))
+
+
+def group_request_volume(group, rid):
+    """[EXT] q3tts_group_request_volume: the volume of a group request id in tenths of a dB"""
+    return _request_speech_rate(lib().q3tts_group_request_volume, group, rid)
 
 
 def _preamble_create(fn, h, codes):
@@ -1134,6 +1156,22 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         _chk(lib().q3tts_engine_pitch_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(chunks=a.value, samples_out=b.value, flushes=c.value, table_bytes=d.value)
+
+    def set_volume(self, db10=0):
+        """[EXT] volume (q3tts_engine_set_volume): requests submitted from now on with want_pcm get a gain of db10 tenths of a dB, VOL_MIN ..
+        VOL_MAX, behind a look-ahead peak limiter, in front of whatever format, rate or pitch they have; 0 = off.  No count changes; the
+        stream is delayed by VOL_DELAY native samples, which are not flushed"""
+        _chk(lib().q3tts_engine_set_volume(self.h, int(db10)))
+
+    def request_volume(self, rid):
+        """[EXT] the request's volume in tenths of a dB (0: none)"""
+        return _request_speech_rate(lib().q3tts_request_volume, self.h, rid)
+
+    def volume_stats(self):
+        """[EXT] q3tts_engine_volume_stats: dict(chunks, samples)"""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_volume_stats(self.h, C.byref(a), C.byref(b)))
+        return dict(chunks=a.value, samples=b.value)
 
     def wait(self, rid, timeout_ms=-1.0):
         rc = lib().q3tts_wait(self.h, rid, timeout_ms)
@@ -2342,6 +2380,53 @@ def op_tsm(x, chunk_samples, streams, n_streams, rates, encodings, reset_before=
         raise
     outs = [w.view(dt)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, dt, (n, fr) in zip(wholes, dts, want)]
     traces = [t[GLUE_GUARD: GLUE_GUARD + fr].copy() for t, (n, fr) in zip(twholes, want)]
+    return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist
+
+
+# ---- volume: the host-only half and the volume kernel (q3tts_op_volume) ----
+def volume_gain(db10):
+    """G = (float) pow(10.0, db10 / 200.0) as np.float32; NaN for a volume outside [VOL_MIN, VOL_MAX]"""
+    return np.float32(lib().q3tts_volume_gain(int(db10)))
+
+
+def op_volume(x, chunk_samples, streams, n_streams, volumes, reset_before=None, hist=None, trace=True, slack=0, fill=0x5A):
+    """the volume kernel over host buffers, one launch of the engine's launcher per chunk.  x [G][sum(chunk_samples)] f32: the native signal of
+    each position; streams [n_chunks][G] state slots; volumes [G] tenths of a dB.  hist: a whole guarded store (GLUE_GUARD floats,
+    [n_streams][VOL_HIST], GLUE_GUARD floats) or None for a zero store between guards of -3e38.  Every output and trace buffer is made exactly
+    as large as the result plus `slack` elements, every byte `fill`; trace=False passes no traces.  Returns (outs, traces, wholes, twholes,
+    n_out, hist).  A refused call raises Q3Error carrying wholes / twholes / n_out / hist as they are then."""
+    x = np.ascontiguousarray(x, np.float32)
+    G = x.shape[0] if x.ndim == 2 else 0
+    cs = np.ascontiguousarray(chunk_samples, np.int32)
+    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
+    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    vo = np.ascontiguousarray(volumes, np.int32)
+    parts, at = [], 0
+    for t in cs:                       # [n_chunks concatenated][G][T_c]
+        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
+        at += max(int(t), 0)
+    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G and sum(p.size for p in parts) else np.zeros(1, np.float32)
+    n = int(sum(max(int(t), 0) for t in cs))
+    wholes = [np.full((n + slack + 2 * GLUE_GUARD) * 4, fill, np.uint8) for _ in range(len(vo))]
+    twholes = [np.full((n + slack + 2 * GLUE_GUARD) * 4, fill, np.uint8) for _ in range(len(vo))] if trace else []
+    if hist is None:
+        hist = np.zeros(n_streams * VOL_HIST + 2 * GLUE_GUARD, np.float32)
+        hist[:GLUE_GUARD] = hist[-GLUE_GUARD:] = -3e38
+    assert hist.dtype == np.float32 and hist.size == n_streams * VOL_HIST + 2 * GLUE_GUARD and hist.flags["C_CONTIGUOUS"]
+    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
+    tptrs = (C.c_void_p * max(len(twholes), 1))(*[w.ctypes.data for w in twholes]) if trace else None
+    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
+    tlen = np.array([w.size // 4 for w in twholes] or [0], np.int64)
+    n_out = np.full(max(len(wholes), 1), -1, np.int64)
+    try:
+        pad = np.zeros(1, np.int32)    # an empty list still hands the call a pointer
+        _chk(lib().q3tts_op_volume(_p(flat), G, _p(cs), cs.size, _p(sl if sl.size else pad), n_streams, _p(vo if vo.size else pad), _p(rb),
+                                   ptrs, _p(nbytes), _p(n_out), tptrs, _p(tlen), _p(hist)))
+    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
+        ex.wholes, ex.twholes, ex.n_out, ex.hist = wholes, twholes, n_out[: len(wholes)].copy(), hist
+        raise
+    outs = [w.view(np.float32)[GLUE_GUARD: GLUE_GUARD + n].copy() for w in wholes]
+    traces = [t.view(np.float32)[GLUE_GUARD: GLUE_GUARD + n].copy() for t in twholes]
     return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist
 
 
