@@ -273,7 +273,8 @@ int q3tts_fetch_pcm16(q3tts_engine* e, int64_t id, int16_t* out, int64_t off, in
 int q3tts_engine_pcm_out_stats(q3tts_engine* e, int64_t* chunks_converted, int64_t* samples_out) {
     Q3_API_BEGIN
     Q3_CHECK(e && chunks_converted && samples_out, "null argument");
-    e->e->pcm_out_stats(chunks_converted, samples_out);
+    const OutputStageStats s = e->e->output_stats();
+    *chunks_converted = s.conv_chunks; *samples_out = s.conv_samples;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -396,7 +397,8 @@ int q3tts_request_speech_rate(q3tts_engine* e, int64_t id, int32_t* rate_pct) {
 int q3tts_engine_tsm_stats(q3tts_engine* e, int64_t* chunks, int64_t* frames_out, int64_t* flushes) {
     Q3_API_BEGIN
     Q3_CHECK(e && chunks && frames_out && flushes, "null argument");
-    e->e->tsm_stats(chunks, frames_out, flushes);
+    const OutputStageStats s = e->e->output_stats();
+    *chunks = s.tsm_chunks; *frames_out = s.tsm_frames; *flushes = s.tsm_flushes;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -412,7 +414,8 @@ int q3tts_request_pitch(q3tts_engine* e, int64_t id, int32_t* pitch_pct) {
 int q3tts_engine_pitch_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) {
     Q3_API_BEGIN
     Q3_CHECK(e && chunks && samples_out && flushes && table_bytes, "null argument");
-    e->e->pitch_stats(chunks, samples_out, flushes, table_bytes);
+    const OutputStageStats s = e->e->output_stats();
+    *chunks = s.pitch_chunks; *samples_out = s.pitch_samples; *flushes = s.pitch_flushes; *table_bytes = s.pitch_table_bytes;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -428,7 +431,8 @@ int q3tts_request_volume(q3tts_engine* e, int64_t id, int32_t* db10) {
 int q3tts_engine_volume_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples) {
     Q3_API_BEGIN
     Q3_CHECK(e && chunks && samples, "null argument");
-    e->e->volume_stats(chunks, samples);
+    const OutputStageStats s = e->e->output_stats();
+    *chunks = s.vol_chunks; *samples = s.vol_samples;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

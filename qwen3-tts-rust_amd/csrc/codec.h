@@ -2,6 +2,7 @@
 // (/root/reference/src/models/onnx.rs:324-496).  Architecture "Q3TTS-codec-synth" (see DESIGN.md).
 #pragma once
 #include "q3_common.h"
+#include "sched_logic.h"
 #include <memory>
 #include <string>
 #include <vector>
@@ -46,33 +47,18 @@ public:
     // same, but returns right after enqueueing: pcm_pinned must be hipHostMalloc'd and stay valid until `st` is synchronised
     int decode_async(hipStream_t st, int stream, const int64_t* codes, int n_frames, bool is_last, float* pcm_pinned, int lane = 0);
     // G distinct streams, each with n_frames new frames: codes [G][n_frames][16], pcm[g] pinned destinations
-    // [EXT] output formats (q3tts_spec.h): fmt[g] = the format stream g is delivered in.  NULL, or every entry {24000, f32}, is the plain call:
-    // the same launches, the same copies.  Otherwise one convert launch (pcmout.hip) follows the output conv on `st` and a converting
-    // stream's copy takes its T*L/M samples of 4 or 2 bytes from the converted buffer; pcm_pinned[g] then receives those bytes.  n_out[g]
-    // (optional) = the samples stream g was given.  The converter's tables, history store and per-lane buffers are allocated on first use
+    // [EXT] out[g] = what stream g is delivered as (OutSpec, sched_logic.h); NULL, or every entry the default, is the plain call: the same
+    // launches, the same copies.  Otherwise, behind the output conv on `st`: one volume launch (volume.hip) rewrites the chunks of the streams
+    // with a volume in place; then one launch of each stage that a stream of the pass belongs to (out_kind: convert, pcmout.hip; stretch,
+    // tsm.hip; pitch, pitch.hip), and every stream's copy takes the n_out[g] (optional) samples its stage made -- of a stretched or shifted
+    // stream those that became available, possibly none -- in 4 or 2 bytes each.  A stage's tables, state store and per-lane buffers are
+    // made by the first call that needs it; a reset and a snapshot restore zero a stream's state in all of them
     int decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm_pinned, int lane = 0,
-                           const q3tts_pcm_format* fmt = nullptr, int64_t* n_out = nullptr, const int32_t* rate = nullptr, const int32_t* pitch = nullptr,
-                           const int32_t* volume = nullptr);
-    // [EXT] speaking rate (q3tts_spec.h): rate[g] = the percent stream g is spoken at.  NULL, or every entry 100, is the call without it, launch
-    // for launch.  Otherwise one stretch launch (tsm.hip) follows the output conv on `st`; a stretching stream delivers 24000 Hz in fmt[g]'s
-    // encoding (f32 when fmt is NULL), the converter leaves it alone, and its copy takes the n_out[g] samples that became available -- 480 a
-    // hop, possibly none -- from the stretched buffer.  tsm_flush_async ends a stretched utterance: the hops its last samples still owe go to
-    // dst (pinned) and *n_out is their sample count (0 for a stream that was not stretched since its reset).  The stretcher's tables, state
-    // store and per-lane buffers are allocated on first use; a reset and a snapshot restore zero a stream's stretcher state
-    // [EXT] pitch (q3tts_spec.h "pitch"): pitch[g] = the percent stream g's pitch is shifted to.  NULL, or every entry 100, is the call without
-    // it, launch for launch.  Otherwise one pitch launch (pitch.hip) follows the output conv on `st`, beside the stretch launch when the pass also
-    // holds a stream with a rate alone; a stream with a pitch runs at the tempo rate[g] / pitch[g], delivers 24000 Hz in fmt[g]'s encoding, and
-    // its copy takes the n_out[g] samples that became available.  tsm_flush_async ends its utterance too.  All 151 tap tables, the state stores
-    // and the per-lane buffers are made by the first call that shifts
-    // [EXT] volume (q3tts_spec.h "volume"): volume[g] = stream g's volume in tenths of a dB.  NULL, or every entry 0, is the call without it,
-    // launch for launch.  Otherwise one volume launch (volume.hip) follows the output conv on `st` and rewrites the chunks of the streams with a
-    // volume in place, in front of whatever stage or copy takes them next: no count changes.  The state store is made by the first call with a
-    // volume; a reset and a snapshot restore zero a stream's entry
+                           const OutSpec* out = nullptr, int64_t* n_out = nullptr);
+    // ends a stretched or shifted utterance: the hops its last samples still owe go to dst (pinned) and *n_out is their sample count (0 for a
+    // stream that was neither since its reset)
     void tsm_flush_async(hipStream_t st, int stream, void* dst, int64_t* n_out, int lane = 0);
-    void volume_stats(int64_t* chunks, int64_t* samples) const; // stream chunks the volume stage took, samples it rewrote
-    void pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const; // stream chunks shifted, samples delivered, flushes, bytes of tap tables
-    void tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const; // stream chunks the stretcher took, synthesis frames made, flushes
-    void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks the converter took, output samples it made
+    OutputStageStats output_stats() const; // the counters of the four stages (read by other threads)
     double flops_per_frame() const;
 private:
     struct Impl;

@@ -1180,7 +1180,9 @@ struct CodecDecoder::Impl {
         DevBuf<float> h, xn, qkv, att, gu, act, t1, t2, pcm, splitk_ws; DevBuf<int64_t> d_in; // d_in = codes then meta
         std::vector<DevBuf<float>> work;              // batched extended buffers, indexed by Ext::id
         int64_t* h_in = nullptr; int ring_idx = 0;    // pinned staging ring for the (tiny) code + metadata uploads of async calls
-        std::vector<uint8_t> kind;                    // [gmax]: the kind of each stream of the pass in flight (deliver)
+        // [gmax] each, sized once: what deliver hands the stage launchers for the pass in flight -- the converter's formats, the stretcher's
+        // percents, the shifter's rates and pitches, the encodings, the converter's counts, the stretcher's and shifter's, their byte offsets
+        std::vector<q3tts_pcm_format> cf; std::vector<int32_t> pct, pr, pp, enc, vol; std::vector<int64_t> cnt, scnt, toff;
     };
     std::vector<Scratch> lanes; Scratch* S = nullptr; int ring = 256;
     // [EXT] output formats: made by the first call that converts (decode_group_async), under capture_mutex(); pcm_out[lane] = the converted
@@ -1191,9 +1193,10 @@ struct CodecDecoder::Impl {
     // decoder thread, which owns the codec's streams -- under capture_mutex(); all 151 tap tables are built and uploaded there, once.
     // tsm_out[lane] / pitch_out[lane] = what the stage made of each stream of a pass, region g of tsm_region() floats: a chunk of T samples
     // gives at most 2 T samples plus a hop at rate 50 and 2 T + 961 at the tempo 1/2, a flush at most six hops or 3361 samples.
-    // prosody[s] = what stream s was last stretched or shifted with since its reset, which is what its flush runs with
+    // prosody[s] = what stream s was last stretched or shifted with since its reset, which is what its flush runs with; live = false:
+    // neither since the reset, or flushed
     std::unique_ptr<TsmStretcher> tsm; std::unique_ptr<PitchShifter> pitch; std::vector<DevBuf<float>> tsm_out, pitch_out;
-    struct Prosody { int32_t rate = 0, pitch = 100, enc = Q3_PCM_F32; };   // rate 0: neither since the reset; pitch 100: the stretcher's stream
+    struct Prosody { OutSpec out; bool live = false; };
     std::vector<Prosody> prosody;
     size_t tsm_region() const { return 2 * (pcm_lane_floats / (size_t)gmax) + 8 * Q3_TSM_HOP; }
     std::atomic<int64_t> tsm_chunks{0}, tsm_frames{0}, tsm_flushes{0};
@@ -1210,9 +1213,10 @@ struct CodecDecoder::Impl {
     // [EXT] volume: the stage is made by the first pass that holds a stream with a volume, under capture_mutex(); it has no buffers of its own
     std::unique_ptr<VolumeStage> volume;
     std::atomic<int64_t> vol_chunks{0}, vol_samples{0};
-    void run_volume(hipStream_t st, int G, int T, const int32_t* streams, const int32_t* db10) {   // one launch over the chunk in S->pcm
+    void run_volume(hipStream_t st, int G, int T, const int32_t* streams, const OutSpec* out) {   // one launch over the chunk in S->pcm
         bool any = false;
-        for (int g = 0; g < G; g++) any = any || db10[g] != 0;
+        int32_t* const db10 = S->vol.data();
+        for (int g = 0; g < G; g++) { db10[g] = out[g].vol_db10; any = any || db10[g] != 0; }
         if (!any) return;
         if (!volume) {
             std::lock_guard<std::mutex> cap(capture_mutex());
@@ -1246,8 +1250,7 @@ struct CodecDecoder::Impl {
         Q3_LAUNCH_CHECK();
         pitch_chunks += pitch->chunks - c0; pitch_samples += pitch->samples_out - s0; pitch_flushes += pitch->flushes - l0;
     }
-    void deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt, int64_t* n_out,
-                 const int32_t* rate, const int32_t* pitch_pct);
+    void deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const OutSpec* out, int64_t* n_out);
     // [EXT] codec preambles: the snapshot store.  A slot holds one stream's histories back to back in all_ext order (the shape of one stream's
     // share of the history stores) and the two host counters as they stood when the snapshot was enqueued.  A slot's buffer is allocated by the
     // first snapshot that takes it, under capture_mutex(), and kept for the next one; snap_mu guards the table (a slot may be freed by
@@ -1515,7 +1518,8 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
         m.pcm_lane_floats = (size_t)GM * T;
         L.work.resize(m.all_ext.size());
         for (Ext* e : m.all_ext) L.work[e->id].alloc((size_t)GM * (e->H + e->Tmax) * e->C);
-        L.d_in.alloc(m.in_slot()); L.kind.resize((size_t)GM);
+        L.d_in.alloc(m.in_slot()); L.cf.resize((size_t)GM); L.cnt.resize((size_t)GM); L.scnt.resize((size_t)GM); L.toff.resize((size_t)GM);
+        for (auto* v : {&L.pct, &L.pr, &L.pp, &L.enc, &L.vol}) v->resize((size_t)GM);
         L.splitk_ws.alloc(std::max<size_t>(max_act * 2, (size_t)1 << 20));
         Q3_HIP(hipHostMalloc((void**)&L.h_in, (size_t)m.ring * m.in_slot() * sizeof(int64_t)));
     }
@@ -1542,16 +1546,15 @@ void CodecDecoder::reset(int s) {
     if (m.tsm || m.pitch || m.volume) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
-void CodecDecoder::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
-    *chunks = impl_->pitch_chunks.load(); *samples_out = impl_->pitch_samples.load(); *flushes = impl_->pitch_flushes.load();
-    *table_bytes = impl_->pitch_table_bytes.load();
-}
-void CodecDecoder::volume_stats(int64_t* chunks, int64_t* samples) const { *chunks = impl_->vol_chunks.load(); *samples = impl_->vol_samples.load(); }
-void CodecDecoder::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
-    *chunks = impl_->tsm_chunks.load(); *frames_out = impl_->tsm_frames.load(); *flushes = impl_->tsm_flushes.load();
-}
-void CodecDecoder::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const {
-    *chunks_converted = impl_->conv_chunks.load(); *samples_out = impl_->conv_samples.load();
+OutputStageStats CodecDecoder::output_stats() const {
+    const Impl& m = *impl_;
+    OutputStageStats s;
+    s.conv_chunks = m.conv_chunks.load(); s.conv_samples = m.conv_samples.load();
+    s.tsm_chunks = m.tsm_chunks.load(); s.tsm_frames = m.tsm_frames.load(); s.tsm_flushes = m.tsm_flushes.load();
+    s.pitch_chunks = m.pitch_chunks.load(); s.pitch_samples = m.pitch_samples.load(); s.pitch_flushes = m.pitch_flushes.load();
+    s.pitch_table_bytes = m.pitch_table_bytes.load();
+    s.vol_chunks = m.vol_chunks.load(); s.vol_samples = m.vol_samples.load();
+    return s;
 }
 
 // ---- DecoderState export / import (onnx.rs:461-496: the reference carries the streaming state as named tensors between decode calls;
@@ -1707,7 +1710,7 @@ int CodecDecoder::decode_async(hipStream_t st, int s, const int64_t* codes, int 
 // One pass for G streams that each contribute n_frames new frames: every GEMM runs over G*T rows, so the 733 MB of
 // codec weights are streamed once per group instead of once per stream, and one set of launches serves the group.
 int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane,
-                                     const q3tts_pcm_format* fmt, int64_t* n_out, const int32_t* rate, const int32_t* pitch, const int32_t* volume) {
+                                     const OutSpec* out, int64_t* n_out) {
     Impl& m = *impl_;
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     Q3_CHECK(G >= 1 && G <= m.gmax, "group size out of range");
@@ -1815,8 +1818,8 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
-    if (volume) m.run_volume(st, G, T, streams, volume);   // [EXT] volume: in place, in front of every stage deliver runs
-    m.deliver(st, G, streams, T, pcm, lane, fmt, n_out, rate, pitch);
+    if (out) m.run_volume(st, G, T, streams, out);   // [EXT] volume: in place, in front of every stage deliver runs
+    m.deliver(st, G, streams, T, pcm, lane, out, n_out);
     return T;
 }
 
@@ -1824,58 +1827,54 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
 // converter's), rate-only (the stretcher's), pitched (the shifter's) -- and each stage sees the streams of the other stages as ones it leaves
 // alone; a stage nobody needs is not launched, and a pass of native streams is G copies.  A stretched or shifted stream delivers 24000 Hz.
 // Then every stream's bytes go out from where its stage left them
-void CodecDecoder::Impl::deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const q3tts_pcm_format* fmt,
-                                 int64_t* n_out, const int32_t* rate, const int32_t* pitch_pct) {
-    enum Kind : uint8_t { NATIVE, CONVERTED, RATED, PITCHED };
+void CodecDecoder::Impl::deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const OutSpec* out, int64_t* n_out) {
     bool any[4] = {false, false, false, false};
-    uint8_t* const kind = S->kind.data();
-    for (int g = 0; g < G; g++) {
-        kind[g] = pitch_pct && pitch_pct[g] != 100 ? PITCHED : rate && rate[g] != 100 ? RATED : fmt && !pcm_format_native(fmt[g]) ? CONVERTED : NATIVE;
-        any[kind[g]] = true;
-    }
-    if (!any[CONVERTED] && !any[RATED] && !any[PITCHED]) {
+    for (int g = 0; out && g < G; g++) any[out_kind(out[g])] = true;
+    if (!any[OUT_CONVERTED] && !any[OUT_RATED] && !any[OUT_PITCHED]) {
         for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
         for (int g = 0; n_out && g < G; g++) n_out[g] = T;
         return;
     }
-    const q3tts_pcm_format native{Q3_PCM_NATIVE_RATE, Q3_PCM_F32};
-    std::vector<q3tts_pcm_format> cf((size_t)G, native);
-    std::vector<int32_t> pct((size_t)G, 100), pr((size_t)G, 100), pp((size_t)G, 100), enc((size_t)G, Q3_PCM_F32);
+    // every stage sees the streams of the other stages as ones it leaves alone: the native format, 100 percent
+    q3tts_pcm_format* const cf = S->cf.data();
+    int32_t *const pct = S->pct.data(), *const pr = S->pr.data(), *const pp = S->pp.data(), *const enc = S->enc.data();
+    int64_t *const cnt = S->cnt.data(), *const scnt = S->scnt.data(), *const toff = S->toff.data();   // the converter's counts; the stretcher's and the shifter's
     for (int g = 0; g < G; g++) {
-        if (kind[g] == NATIVE) continue;
-        if (kind[g] == CONVERTED) { cf[(size_t)g] = fmt[g]; continue; }
-        Q3_CHECK(!fmt || fmt[g].sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate or a pitch needs the 24000 Hz output format");
-        enc[(size_t)g] = fmt ? fmt[g].encoding : Q3_PCM_F32;
-        if (kind[g] == PITCHED) { pr[(size_t)g] = rate ? rate[g] : 100; pp[(size_t)g] = pitch_pct[g]; }
-        else pct[(size_t)g] = rate[g];
+        const OutKind k = out_kind(out[g]);
+        cf[g] = OutSpec().fmt; pct[g] = pr[g] = pp[g] = 100; enc[g] = Q3_PCM_F32; cnt[g] = scnt[g] = T; toff[g] = 0;
+        if (k == OUT_CONVERTED) cf[g] = out[g].fmt;
+        if (k < OUT_RATED) continue;
+        Q3_CHECK(out[g].fmt.sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate or a pitch needs the 24000 Hz output format");
+        enc[g] = out[g].fmt.encoding;
+        if (k == OUT_PITCHED) { pr[g] = out[g].rate_pct; pp[g] = out[g].pitch_pct; }
+        else pct[g] = out[g].rate_pct;
     }
-    std::vector<int64_t> cnt((size_t)G, T), scnt((size_t)G, T), toff((size_t)G);   // the converter's counts; the stretcher's and the shifter's
-    if (any[CONVERTED]) {
+    if (any[OUT_CONVERTED]) {
         ensure_conv();
         const int64_t c0 = conv->chunks_converted, s0 = conv->samples_out;
-        launch_pcm_convert(st, *conv, S->pcm.p, G, T, streams, cf.data(), pcm_out[lane].p, nullptr, cnt.data());
+        launch_pcm_convert(st, *conv, S->pcm.p, G, T, streams, cf, pcm_out[lane].p, nullptr, cnt);
         Q3_LAUNCH_CHECK();
         conv_chunks += conv->chunks_converted - c0; conv_samples += conv->samples_out - s0;
     }
-    if (any[RATED] || any[PITCHED]) {
+    if (any[OUT_RATED] || any[OUT_PITCHED]) {
         Q3_CHECK(2 * (size_t)T + 3 * Q3_TSM_HOP <= tsm_region(), "chunk too long for the stretcher's buffers");
-        for (int g = 0; g < G; g++) toff[(size_t)g] = (int64_t)((size_t)g * tsm_region() * sizeof(float));
+        for (int g = 0; g < G; g++) toff[g] = (int64_t)((size_t)g * tsm_region() * sizeof(float));
     }
     // the stretcher sets T for every stream it leaves alone and the shifter sets its own streams' counts only: they share scnt in this order
-    if (any[RATED]) run_tsm(st, true, G, T, streams, pct.data(), enc.data(), lane, toff.data(), scnt.data());
-    if (any[PITCHED]) run_pitch(st, true, G, T, streams, pr.data(), pp.data(), enc.data(), lane, toff.data(), scnt.data());
+    if (any[OUT_RATED]) run_tsm(st, true, G, T, streams, pct, enc, lane, toff, scnt);
+    if (any[OUT_PITCHED]) run_pitch(st, true, G, T, streams, pr, pp, enc, lane, toff, scnt);
     for (int g = 0; g < G; g++) {
+        const OutKind k = out_kind(out[g]);
         const float* src = S->pcm.p + (size_t)g * T;
-        size_t sb = 4;
-        if (kind[g] == CONVERTED) { src = pcm_out[lane].p + (size_t)g * T; sb = cf[(size_t)g].encoding == Q3_PCM_S16 ? 2 : 4; }
-        else if (kind[g] != NATIVE) {
-            src = (kind[g] == PITCHED ? pitch_out : tsm_out)[lane].p + (size_t)g * tsm_region(); sb = enc[(size_t)g] == Q3_PCM_S16 ? 2 : 4;
-            prosody[(size_t)streams[g]] = Prosody{kind[g] == PITCHED ? pr[(size_t)g] : pct[(size_t)g], pp[(size_t)g], enc[(size_t)g]};
-            cnt[(size_t)g] = scnt[(size_t)g];
-            Q3_CHECK((size_t)cnt[(size_t)g] <= tsm_region(), "a pass delivered more than the stage's buffer holds");
+        if (k == OUT_CONVERTED) src = pcm_out[lane].p + (size_t)g * T;
+        else if (k != OUT_NATIVE) {
+            src = (k == OUT_PITCHED ? pitch_out : tsm_out)[lane].p + (size_t)g * tsm_region();
+            prosody[(size_t)streams[g]] = Prosody{out[g], true};
+            cnt[g] = scnt[g];
+            Q3_CHECK((size_t)cnt[g] <= tsm_region(), "a pass delivered more than the stage's buffer holds");
         }
-        if (cnt[(size_t)g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], src, (size_t)cnt[(size_t)g] * sb, hipMemcpyDeviceToHost, st));
-        if (n_out) n_out[g] = cnt[(size_t)g];
+        if (cnt[g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], src, (size_t)cnt[g] * out_sample_bytes(out[g]), hipMemcpyDeviceToHost, st));
+        if (n_out) n_out[g] = cnt[g];
     }
 }
 
@@ -1887,15 +1886,16 @@ void CodecDecoder::tsm_flush_async(hipStream_t st, int s, void* dst, int64_t* n_
     Q3_CHECK(s >= 0 && s < m.n_streams && n_out, "stream out of range");
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     *n_out = 0;
-    if (m.prosody.empty() || m.prosody[(size_t)s].rate == 0) return;
-    const Impl::Prosody p = m.prosody[(size_t)s];
+    if (m.prosody.empty() || !m.prosody[(size_t)s].live) return;
+    const OutSpec o = m.prosody[(size_t)s].out;
+    const bool pitched = out_kind(o) == OUT_PITCHED;
     const int32_t sl = s;
     const int64_t off = 0;
-    if (p.pitch != 100) m.run_pitch(st, false, 1, 0, &sl, &p.rate, &p.pitch, &p.enc, lane, &off, n_out);
-    else m.run_tsm(st, false, 1, 0, &sl, &p.rate, &p.enc, lane, &off, n_out);
+    if (pitched) m.run_pitch(st, false, 1, 0, &sl, &o.rate_pct, &o.pitch_pct, &o.fmt.encoding, lane, &off, n_out);
+    else m.run_tsm(st, false, 1, 0, &sl, &o.rate_pct, &o.fmt.encoding, lane, &off, n_out);
     Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the stage's buffer");
-    if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, (p.pitch != 100 ? m.pitch_out : m.tsm_out)[lane].p, (size_t)*n_out * (p.enc == Q3_PCM_S16 ? 2 : 4), hipMemcpyDeviceToHost, st));
-    m.prosody[(size_t)s].rate = 0; // flushed: the stream is reset before it is used again
+    if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, (pitched ? m.pitch_out : m.tsm_out)[lane].p, (size_t)*n_out * out_sample_bytes(o), hipMemcpyDeviceToHost, st));
+    m.prosody[(size_t)s].live = false; // flushed: the stream is reset before it is used again
 }
 
 // ---------------- test entry points: one GEMM as the decoder dispatches it, or with a named form forced ----------------

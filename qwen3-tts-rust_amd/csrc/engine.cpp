@@ -210,21 +210,15 @@ struct Engine::Req {
     bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
     int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
-    // [EXT] output formats: what the request's PCM is delivered in, read at submit.  pcm_enq / pcm_ready count samples of that format; pcm
-    // holds their bytes as the converter left them (pcm_n samples of 4 or 2 bytes, rounded up to whole floats)
-    q3tts_pcm_format fmt{Q3_PCM_NATIVE_RATE, Q3_PCM_F32}; int64_t pcm_n = 0;
-    size_t sample_bytes() const { return fmt.encoding == Q3_PCM_S16 ? 2 : 4; }
-    // [EXT] speaking rate: the percent the request is spoken at, read at submit (100: off).  pcm_enq / pcm_ready / pcm_n count the samples
-    // delivered; tsm_native = the native samples its stream has been given (decoder thread)
-    int rate_pct = 100; int64_t tsm_native = 0;
-    // [EXT] pitch: the percent the request's pitch is shifted to, read with the rate at submit (100: off).  With a pitch the delivered counts are
-    // pitch_out_samples(rate_pct, pitch_pct, tsm_native, .) and the stream is the pitch shifter's, not the stretcher's
-    int pitch_pct = 100;
-    // [EXT] volume: the request's volume in tenths of a dB, read with the rate and the pitch at submit (0: off).  It changes no count
-    int vol_db10 = 0;
-    bool stretched() const { return rate_pct != 100 || pitch_pct != 100; }
-    int64_t prosody_samples(int64_t n_native, bool final) const {
-        return pitch_pct != 100 ? pitch_out_samples(rate_pct, pitch_pct, n_native, final) : tsm_out_samples(rate_pct, n_native, final);
+    // [EXT] output formats, speaking rate, pitch, volume: what the request's PCM is delivered as, read once at submit (take_out).  pcm_enq /
+    // pcm_ready / pcm_n count delivered samples -- out_delivered(out, tsm_native, .), tsm_native = the native samples its stream has been
+    // given (decoder thread) --; pcm holds their bytes as the stage left them (pcm_n samples of 4 or 2 bytes, rounded up to whole floats)
+    OutSpec out; int64_t pcm_n = 0, tsm_native = 0;
+    size_t sample_bytes() const { return out_sample_bytes(out); }
+    bool stretched() const { return out_kind(out) >= OUT_RATED; }
+    // bytes of the samples that become available with n_more native samples more, or (final) with the flush
+    size_t bytes_due(int64_t n_more, bool final) const {
+        return (size_t)(out_delivered(out, tsm_native + n_more, final) - out_delivered(out, tsm_native, false)) * sample_bytes();
     }
     bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
@@ -721,7 +715,7 @@ void Engine::decoder_main() {
             }
             if (grp[0].reset && grp[0].r->pre_snap >= 0) { // [EXT] codec preambles: the stream starts from the snapshot; a converting one also from the preamble's tail
                 Req* r = grp[0].r;
-                codec_->restore_async(st2_[lane], r->pre_snap, r->cs, pcm_format_native(r->fmt) ? nullptr : r->pre_tail);
+                codec_->restore_async(st2_[lane], r->pre_snap, r->cs, pcm_format_native(r->out.fmt) ? nullptr : r->pre_tail);
                 pre_restores_++;
             }
             else if (grp[0].reset) codec_->reset_async(st2_[lane], grp[0].r->cs); // AudioDecoder::create_state for a new request
@@ -730,36 +724,26 @@ void Engine::decoder_main() {
                 std::vector<int> streams(G);
                 std::vector<float*> dst(G);
                 std::vector<int64_t> codes((size_t)G * nf * 16);
-                std::vector<q3tts_pcm_format> fmt(G); std::vector<int64_t> n_out(G); bool converts = false; // [EXT] output formats
-                std::vector<int32_t> rate(G); bool stretches = false;                                       // [EXT] speaking rate
-                std::vector<int32_t> pitch(G); bool shifts = false;                                         // [EXT] pitch
-                std::vector<int32_t> vol(G); bool volumes = false;                                          // [EXT] volume
+                std::vector<OutSpec> out(G); std::vector<int64_t> n_out(G); // [EXT] what each stream is delivered as, what it was given
                 for (int g = 0; g < G; g++) {
                     Req* r = grp[g].r;
-                    fmt[g] = r->fmt; converts = converts || !pcm_format_native(r->fmt);
-                    size_t add = pcm_format_native(r->fmt) ? (size_t)nf * spf * 4 : (size_t)pcm_out_bytes(r->fmt, nf);
-                    rate[g] = r->rate_pct; pitch[g] = r->pitch_pct;
-                    vol[g] = r->vol_db10; volumes = volumes || r->vol_db10 != 0;
-                    if (r->stretched()) { // the samples that become available with these frames: possibly none, at a slow rate more than native
-                        stretches = converts = true; shifts = shifts || r->pitch_pct != 100;
-                        add = (size_t)(r->prosody_samples(r->tsm_native + (int64_t)nf * spf, false) - r->prosody_samples(r->tsm_native, false)) * r->sample_bytes();
-                        r->tsm_native += (int64_t)nf * spf;
-                    }
+                    out[g] = r->out;
+                    // the samples that become available with these frames: of a stretched stream possibly none, at a slow rate more than native
+                    const size_t add = r->bytes_due((int64_t)nf * spf, false);
+                    r->tsm_native += (int64_t)nf * spf;
                     streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(pcm_stage(*r, add));
                     std::copy(grp[g].codes.begin(), grp[g].codes.end(), codes.begin() + (size_t)g * nf * 16);
                 }
                 // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
-                const int got = codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane,
-                                                           converts ? fmt.data() : nullptr, converts ? n_out.data() : nullptr, stretches ? rate.data() : nullptr, shifts ? pitch.data() : nullptr,
-                                                           volumes ? vol.data() : nullptr);
-                for (int g = 0; g < G; g++) grp[g].r->pcm_enq += converts ? (size_t)n_out[g] : (size_t)std::max(got, 0);
+                codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane, out.data(), n_out.data());
+                for (int g = 0; g < G; g++) grp[g].r->pcm_enq += (size_t)n_out[g];
             }
             // [EXT] speaking rate: the fence of a stretching request that was not cancelled flushes its stretcher -- the hops its last samples
             // still owe -- behind its last chunk (this lane has waited for it above), before the fence's completion is recorded
             for (auto& t : grp) {
                 Req* r = t.r;
                 if (!t.fence || !r->stretched() || r->cancel || r->cs < 0) continue;
-                const size_t add = (size_t)(r->prosody_samples(r->tsm_native, true) - r->prosody_samples(r->tsm_native, false)) * r->sample_bytes();
+                const size_t add = r->bytes_due(0, true);
                 int64_t n = 0;
                 codec_->tsm_flush_async(st2_[lane], r->cs, pcm_stage(*r, add), &n, lane);
                 r->pcm_enq += (size_t)n;
@@ -946,8 +930,7 @@ int64_t Engine::submit(const GenRequest& g, bool want_pcm, bool copy_prompt, boo
     }
     r->r.prefix = r->prefix_own.data();
     r->want_pcm = want_pcm && codec_;
-    if (r->want_pcm && may_record) r->fmt = unpack_fmt(out_fmt_.load()); // [EXT] the engine's output format, read once per request; a blocking batch is native
-    if (r->want_pcm && may_record) take_rate(r.get(), g.max_steps);       // [EXT] and its speech rate; throws before anything is queued
+    if (r->want_pcm && may_record) take_out(r.get(), g.max_steps); // [EXT] the engine's output settings, read once per request; throws before anything is queued; a blocking batch is native
     r->t_submit = now_ms();
     r->seed = g.sampler.has_seed ? g.sampler.seed
                                  : (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count(); // :473-478
@@ -973,7 +956,6 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
     sh->trail.assign(g.trail, g.trail + g.n_trail);
     g.prompt = sh->prompt.data(); g.trail = sh->trail.data();
     g.logprobs = g.logprobs || lp_on_.load(); // the engine's flag, read once per set
-    const q3tts_pcm_format set_fmt = unpack_fmt(out_fmt_.load()); // and its output format
     std::vector<std::unique_ptr<Req>> rs;
     const double t = now_ms();
     for (int i = 0; i < n; i++) {
@@ -982,8 +964,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->r.prefix = r->prefix_own.data();
         r->shared = sh;
         r->want_pcm = want_pcm && codec_;
-        if (r->want_pcm) r->fmt = set_fmt;
-        if (r->want_pcm) take_rate(r.get(), g.max_steps, i == 0 ? -1 : rs[0]->rate_pct, i == 0 ? -1 : rs[0]->pitch_pct, i == 0 ? nullptr : &rs[0]->vol_db10); // [EXT] the speech rate, the pitch and the volume, read once per set
+        if (r->want_pcm) take_out(r.get(), g.max_steps, i == 0 ? nullptr : &rs[0]->out); // [EXT] the output settings, read once per set
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
@@ -1185,8 +1166,7 @@ int64_t Engine::submit_decode(const int32_t* codes, int n) {
     if (const char* why = decode_refusal(codes, n, p_.max_steps, codec_ != nullptr)) throw Error(why);
     std::unique_ptr<Req> r(new Req());
     r->decode = true; r->want_pcm = true;
-    r->fmt = unpack_fmt(out_fmt_.load());
-    take_rate(r.get(), n); // [EXT] speaking rate
+    take_out(r.get(), n); // [EXT] the engine's output settings
     r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
     r->t_submit = now_ms();
@@ -1616,7 +1596,7 @@ ReqStatus Engine::poll(int64_t id) {
 void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, float* pcm, int64_t pcm_off, int64_t pcm_cap, int* got_frames, int64_t* got_pcm) {
     std::lock_guard<std::mutex> lk(mu_);
     const Req& r = req(id);
-    if (pcm) Q3_CHECK(r.fmt.encoding == Q3_PCM_F32, "the request delivers int16 PCM: fetch it with fetch_pcm16"); // [EXT] output formats; nothing is copied
+    if (pcm) Q3_CHECK(r.out.fmt.encoding == Q3_PCM_F32, "the request delivers int16 PCM: fetch it with fetch_pcm16"); // [EXT] output formats; nothing is copied
     int nf = 0; int64_t np = 0;
     if (codes && frame_off >= 0 && frame_off < r.fed) {
         nf = std::min(max_frames, r.fed - frame_off);
@@ -1643,89 +1623,62 @@ int64_t Engine::copy_pcm(const Req& r, void* out, int64_t off, int64_t cap) cons
 // [EXT] output formats (q3tts_spec.h "output formats")
 void Engine::set_output_format(const q3tts_pcm_format* f) {
     if (const char* why = pcm_format_refusal(f, codec_ != nullptr)) throw Error(why);
-    out_fmt_ = f ? pack_fmt(*f) : pack_fmt(q3tts_pcm_format{Q3_PCM_NATIVE_RATE, Q3_PCM_F32});
+    std::lock_guard<std::mutex> lk(out_mu_);
+    out_.fmt = f ? *f : OutSpec().fmt;
 }
 q3tts_pcm_format Engine::request_format(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).fmt;
+    return req(id).out.fmt;
 }
 void Engine::fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
     std::lock_guard<std::mutex> lk(mu_);
     const Req& r = req(id);
-    Q3_CHECK(r.fmt.encoding == Q3_PCM_S16, "the request delivers f32 PCM: fetch it with fetch");
+    Q3_CHECK(r.out.fmt.encoding == Q3_PCM_S16, "the request delivers f32 PCM: fetch it with fetch");
     Q3_CHECK(out && off >= 0, "null buffer or negative offset");
     const int64_t n = copy_pcm(r, out, off, cap);
     if (got) *got = n;
 }
-void Engine::pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const {
-    *chunks_converted = *samples_out = 0;
-    if (codec_) codec_->pcm_out_stats(chunks_converted, samples_out);
-}
+OutputStageStats Engine::output_stats() const { return codec_ ? codec_->output_stats() : OutputStageStats(); }
 
 // [EXT] speaking rate (q3tts_spec.h "speaking rate")
 void Engine::set_speech_rate(int pct) {
     Q3_CHECK(codec_, "the engine has no codec");
     if (const char* why = tsm_rate_why_not(pct)) throw Error(why);
-    std::lock_guard<std::mutex> lk(prosody_mu_);
-    rate_pct_ = pct;
+    std::lock_guard<std::mutex> lk(out_mu_);
+    out_.rate_pct = pct;
 }
-// the engine's rate (or `given`, the one a candidate set's first member read) becomes the request's, if the request's format and length allow it
-void Engine::take_rate(Req* r, int max_steps, int given, int given_pitch, const int* given_vol) const {
-    int pct, pitch, vol;
-    {   // [EXT] pitch: the two settings are read together, so that the pair rule judges a pair somebody set; [EXT] volume: read with them
-        std::lock_guard<std::mutex> lk(prosody_mu_);
-        pct = given >= 0 ? given : rate_pct_.load(); pitch = given_pitch >= 0 ? given_pitch : pitch_pct_.load();
-        vol = given_vol ? *given_vol : vol_db10_.load();
-    }
-    if (vol != 0) {   // a refusal below throws as well, and the request is dropped with what it was given here
-        if (const char* why = volume_submit_refusal(vol, codec_ != nullptr)) throw Error(why);
-        r->vol_db10 = vol;
-    }
-    if (pitch != 100) {
-        if (const char* why = pitch_submit_refusal(pct, pitch, r->fmt, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
-        r->rate_pct = pct; r->pitch_pct = pitch;
-        return;
-    }
-    if (pct == 100) return;
-    if (const char* why = tsm_submit_refusal(pct, r->fmt, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
-    r->rate_pct = pct;
+// the whole record is read at once, so that the rules judge settings that stood together at some instant
+void Engine::take_out(Req* r, int max_steps, const OutSpec* given) const {
+    OutSpec o;
+    if (given) o = *given;
+    else { std::lock_guard<std::mutex> lk(out_mu_); o = out_; }
+    if (const char* why = out_submit_refusal(o, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
+    r->out = o;
 }
 int Engine::request_speech_rate(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).rate_pct;
+    return req(id).out.rate_pct;
 }
 // [EXT] pitch (q3tts_spec.h "pitch")
 void Engine::set_pitch(int pct) {
     Q3_CHECK(codec_, "the engine has no codec");
     if (const char* why = pitch_why_not(pct)) throw Error(why);
-    std::lock_guard<std::mutex> lk(prosody_mu_);
-    pitch_pct_ = pct;
+    std::lock_guard<std::mutex> lk(out_mu_);
+    out_.pitch_pct = pct;
 }
 int Engine::request_pitch(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).pitch_pct;
-}
-void Engine::pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const {
-    *chunks = *samples_out = *flushes = *table_bytes = 0;
-    if (codec_) codec_->pitch_stats(chunks, samples_out, flushes, table_bytes);
+    return req(id).out.pitch_pct;
 }
 // [EXT] volume (q3tts_spec.h "volume")
 void Engine::set_volume(int db10) {
     if (const char* why = volume_submit_refusal(db10, codec_ != nullptr)) throw Error(why);
-    std::lock_guard<std::mutex> lk(prosody_mu_);
-    vol_db10_ = db10;
+    std::lock_guard<std::mutex> lk(out_mu_);
+    out_.vol_db10 = db10;
 }
 int Engine::request_volume(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).vol_db10;
-}
-void Engine::volume_stats(int64_t* chunks, int64_t* samples) const {
-    *chunks = *samples = 0;
-    if (codec_) codec_->volume_stats(chunks, samples);
-}
-void Engine::tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const {
-    *chunks = *frames_out = *flushes = 0;
-    if (codec_) codec_->tsm_stats(chunks, frames_out, flushes);
+    return req(id).out.vol_db10;
 }
 
 // [EXT] codec preambles and prompt stems (q3tts_spec.h "codec preambles" / "prompt stems"): the held objects.  Who holds what is counted by

@@ -114,27 +114,24 @@ public:
     void set_output_format(const q3tts_pcm_format* f);
     q3tts_pcm_format request_format(int64_t id);
     void fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got);
-    void pcm_out_stats(int64_t* chunks_converted, int64_t* samples_out) const; // stream chunks converted, output samples made
+    OutputStageStats output_stats() const; // the counters of the four output stages; all zeros without a codec
     // [EXT] speaking rate (q3tts_spec.h "speaking rate"): requests submitted from now on with want_pcm are spoken at pct percent of the native
     // tempo (100: off); read once per request at submit and once per candidate set; generate_batch, scoring and preamble builds are never
     // stretched.  Thread-safe, no HIP calls; throws for a rate outside [50, 200] or an engine without a codec.  A submit with a rate throws
     // tsm_submit_refusal's reason.  poll()'s n_pcm and the fetch offsets count delivered samples
     void set_speech_rate(int pct);
     int request_speech_rate(int64_t id);
-    void tsm_stats(int64_t* chunks, int64_t* frames_out, int64_t* flushes) const; // stream chunks stretched, synthesis frames made, flushes
     // [EXT] pitch (q3tts_spec.h "pitch"): requests submitted from now on with want_pcm have their pitch shifted to pct percent (100: off), with
     // or without a rate; read with the rate, once per request at submit and once per candidate set, wherever the rate is read.  Thread-safe, no
     // HIP calls; throws for a pitch outside [50, 200] or an engine without a codec.  The pair is judged at submit: a submit throws
     // pitch_submit_refusal's reason before anything is queued
     void set_pitch(int pct);
     int request_pitch(int64_t id);
-    void pitch_stats(int64_t* chunks, int64_t* samples_out, int64_t* flushes, int64_t* table_bytes) const; // stream chunks shifted, samples delivered, flushes, bytes of tap tables on the device
     // [EXT] volume (q3tts_spec.h "volume"): requests submitted from now on with want_pcm have a gain of db10 tenths of a dB behind a look-ahead
     // limiter (0: off), in front of whatever format, rate or pitch they have; read with the rate and the pitch, wherever those are read.
     // Thread-safe, no HIP calls; throws volume_submit_refusal's reason for a volume outside [-400, 200] or an engine without a codec
     void set_volume(int db10);
     int request_volume(int64_t id);
-    void volume_stats(int64_t* chunks, int64_t* samples) const; // stream chunks the stage took, samples it rewrote
     // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
     // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
     // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The
@@ -262,14 +259,12 @@ private:
     void retire(Req* r, bool flush_tail); // the slot leaves the batch: EOS / max_steps (tail flushed) or a cancel (tail and unstarted chunks dropped)
     void decoder_main();
     int64_t copy_pcm(const Req& r, void* out, int64_t off, int64_t cap) const;
-    static int64_t pack_fmt(const q3tts_pcm_format& f) { return (int64_t)f.sample_rate * 4 + f.encoding; }
-    static q3tts_pcm_format unpack_fmt(int64_t v) { return q3tts_pcm_format{(int32_t)(v / 4), (int32_t)(v % 4)}; }
-    std::atomic<int64_t> out_fmt_{(int64_t)Q3_PCM_NATIVE_RATE * 4 + Q3_PCM_F32}; // what submit() reads
-    std::atomic<int> rate_pct_{100};                                             // [EXT] speaking rate: what submit() reads
-    std::atomic<int> pitch_pct_{100};                                            // [EXT] pitch: what submit() reads, with rate_pct_ under prosody_mu_
-    std::atomic<int> vol_db10_{0};                                               // [EXT] volume: what submit() reads, with the two above under prosody_mu_
-    mutable std::mutex prosody_mu_;
-    void take_rate(Req* r, int max_steps, int given = -1, int given_pitch = -1, const int* given_vol = nullptr) const;
+    // [EXT] output formats, speaking rate, pitch, volume: the engine-level settings as one record (OutSpec, sched_logic.h).  A setter writes its
+    // field and take_out reads the whole record, both under out_mu_, so a request's settings are a record that stood at some instant.  A
+    // request with PCM takes the engine's record, or `given` -- what the first member of its candidate set took -- if its length allows it
+    // (out_submit_refusal: throws before anything is queued)
+    OutSpec out_; mutable std::mutex out_mu_;
+    void take_out(Req* r, int max_steps, const OutSpec* given = nullptr) const;
     void upload_slot_state(); // the whole slot table, routing rows derived first, in one copy
     // All scheduler transfers go through a pinned arena on the AR stream: the engine's streams are non-blocking, so nothing the
     // scheduler does waits for the codec lanes (a synchronous hipMemcpy on the null stream would).

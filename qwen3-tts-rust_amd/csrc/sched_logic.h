@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume, and the one record of a stream's output settings with what follows from it.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -621,5 +621,42 @@ inline const char* volume_submit_refusal(int db10, bool have_codec) {
     if (!have_codec) return "the engine has no codec";
     return volume_why_not(db10);
 }
+
+// [EXT] the output settings of one stream (q3tts_spec.h "output formats" / "speaking rate" / "pitch" / "volume") as one record: what the
+// engine's setters write, what a request reads once at submit and what the codec's pass tail is given per stream.  The default is the plain
+// stream: native format, no rate, no pitch, no volume.  A setting more is a field here and a branch where the pass tail delivers.
+struct OutSpec { q3tts_pcm_format fmt{Q3_PCM_NATIVE_RATE, Q3_PCM_F32}; int32_t rate_pct = 100, pitch_pct = 100, vol_db10 = 0; };
+// whose stream it is behind the output conv: nobody's, the converter's, the stretcher's, the shifter's (a pitch wins over a rate, a rate over a
+// format).  The volume is no kind: it rewrites the native chunk in front of any of them
+enum OutKind : uint8_t { OUT_NATIVE, OUT_CONVERTED, OUT_RATED, OUT_PITCHED };
+inline OutKind out_kind(const OutSpec& o) {
+    return o.pitch_pct != 100 ? OUT_PITCHED : o.rate_pct != 100 ? OUT_RATED : !pcm_format_native(o.fmt) ? OUT_CONVERTED : OUT_NATIVE;
+}
+inline size_t out_sample_bytes(const OutSpec& o) { return o.fmt.encoding == Q3_PCM_S16 ? 2 : 4; }
+// samples delivered once the stream has been given n_native native samples since its reset (final: and has been flushed).  Additive over
+// whole-frame chunks for every kind -- of the converter because a frame of 1920 native samples is a whole number of samples at all eight rates
+inline int64_t out_delivered(const OutSpec& o, int64_t n_native, bool final) {
+    switch (out_kind(o)) {
+    case OUT_PITCHED: return pitch_out_samples(o.rate_pct, o.pitch_pct, n_native, final);
+    case OUT_RATED: return tsm_out_samples(o.rate_pct, n_native, final);
+    case OUT_CONVERTED: return pcm_samples_of_native(o.fmt.sample_rate, n_native);
+    default: return n_native;
+    }
+}
+// the submit rule of a request with these settings: the volume's, then the pitch's (which judges the pair and the format), else the rate's.
+// nullptr = it may be queued
+inline const char* out_submit_refusal(const OutSpec& o, int max_steps, int64_t cap_bytes, bool have_codec) {
+    if (o.vol_db10 != 0) if (const char* why = volume_submit_refusal(o.vol_db10, have_codec)) return why;
+    if (o.pitch_pct != 100) return pitch_submit_refusal(o.rate_pct, o.pitch_pct, o.fmt, max_steps, cap_bytes, have_codec);
+    if (o.rate_pct != 100) return tsm_submit_refusal(o.rate_pct, o.fmt, max_steps, cap_bytes, have_codec);
+    return nullptr;
+}
+// [EXT] the counters of the codec's output stages, as one snapshot: stream chunks the converter took and samples it made; stream chunks the
+// stretcher took, synthesis frames it made, its flushes; stream chunks shifted, samples delivered, flushes, bytes of tap tables on the device;
+// stream chunks the volume stage took and samples it rewrote
+struct OutputStageStats {
+    int64_t conv_chunks = 0, conv_samples = 0, tsm_chunks = 0, tsm_frames = 0, tsm_flushes = 0;
+    int64_t pitch_chunks = 0, pitch_samples = 0, pitch_flushes = 0, pitch_table_bytes = 0, vol_chunks = 0, vol_samples = 0;
+};
 
 } // namespace q3

@@ -2265,46 +2265,73 @@ def pcm_dtype(encoding):
     return np.int16 if encoding == PCM_S16 else np.float32
 
 
-def op_pcm_convert(x, chunk_samples, streams, n_streams, fmts, reset_before=None, hist=None, slack=0, fill=0x5A):
-    """the convert kernel over host buffers, one launch of the engine's launcher per chunk.  x [G][sum(chunk_samples)] f32: the native signal of
-    each position; streams [n_chunks][G] history slots; fmts [G] (rate, encoding).  hist: a whole guarded store (GLUE_GUARD floats,
-    [n_streams][2][96], GLUE_GUARD floats) or None for a zero store between guards of -3e38.  Every output buffer is made exactly as large as
-    the result plus `slack` elements, every byte `fill`.  Returns (outs, wholes, n_out, hist): the converted samples per position, the whole
-    buffers as they came back, the counts the call reported, the whole store.  A refused call raises Q3Error carrying wholes / n_out / hist as they are then."""
+# ---- what the four output-stage entry points (op_pcm_convert, op_tsm, op_volume, op_pitch) share in front of their call and behind it ----
+def _stage_inputs(x, chunk_samples, streams, reset_before, pad_empty=True):
+    """(G, chunk lengths, slots [n_chunks][G], resets or None, the chunks flattened [n_chunks concatenated][G][T_c]); pad_empty: chunks that hold
+    nothing still hand the call one float"""
     x = np.ascontiguousarray(x, np.float32)
     G = x.shape[0] if x.ndim == 2 else 0
     cs = np.ascontiguousarray(chunk_samples, np.int32)
     sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
     rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
     parts, at = [], 0
-    for t in cs:                       # [n_chunks concatenated][G][T_c]
+    for t in cs:
         parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
         at += max(int(t), 0)
-    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G else np.zeros(1, np.float32)
+    some = parts and G and (not pad_empty or sum(p.size for p in parts))
+    return G, cs, sl, rb, np.ascontiguousarray(np.concatenate(parts)) if some else np.zeros(1, np.float32)
+
+
+def _stage_store(h, n_streams, width):
+    """a whole guarded state store: the caller's, or a zero store between guards of -3e38"""
+    if h is None:
+        h = np.zeros(n_streams * width + 2 * GLUE_GUARD, np.float32)
+        h[:GLUE_GUARD] = h[-GLUE_GUARD:] = -3e38
+    assert h.dtype == np.float32 and h.size == n_streams * width + 2 * GLUE_GUARD and h.flags["C_CONTIGUOUS"]
+    return h
+
+
+def _stage_bufs(bufs, per=1):
+    """(pointer array, lengths in units of `per` elements) of a list of whole buffers; an empty list still hands the call one entry of each"""
+    return (C.c_void_p * max(len(bufs), 1))(*[w.ctypes.data for w in bufs]), np.array([w.size // per for w in bufs] or [0], np.int64)
+
+
+def _pz(a):
+    return _p(a if a.size else np.zeros(1, np.int32))   # an empty list still hands the call a pointer
+
+
+def _stage_call(fn, *args, n_out, **carried):
+    """the call; returns a copy of n_out, the counts it reported.  A refused call raises Q3Error carrying n_out and `carried` as they are
+    then: the caller can see that nothing was written"""
+    try:
+        _chk(fn(*args))
+    except Q3Error as ex:
+        ex.n_out = n_out.copy()
+        for k, v in carried.items():
+            setattr(ex, k, v)
+        raise
+    return n_out.copy()
+
+
+def op_pcm_convert(x, chunk_samples, streams, n_streams, fmts, reset_before=None, hist=None, slack=0, fill=0x5A):
+    """the convert kernel over host buffers, one launch of the engine's launcher per chunk.  x [G][sum(chunk_samples)] f32: the native signal of
+    each position; streams [n_chunks][G] history slots; fmts [G] (rate, encoding).  hist: a whole guarded store (GLUE_GUARD floats,
+    [n_streams][2][96], GLUE_GUARD floats) or None for a zero store between guards of -3e38.  Every output buffer is made exactly as large as
+    the result plus `slack` elements, every byte `fill`.  Returns (outs, wholes, n_out, hist): the converted samples per position, the whole
+    buffers as they came back, the counts the call reported, the whole store.  A refused call raises Q3Error carrying wholes / n_out / hist as they are then."""
+    G, cs, sl, rb, flat = _stage_inputs(x, chunk_samples, streams, reset_before, pad_empty=False)
     fm = (PcmFormat * max(len(fmts), 1))(*[PcmFormat(int(r), int(e)) for r, e in fmts])
     wholes, want = [], []
     for r, e in fmts:
         n = sum(max(pcm_out_samples(r, int(t)), 0) for t in cs)
         want.append(n)
         wholes.append(np.full((n + slack + 2 * GLUE_GUARD) * np.dtype(pcm_dtype(e)).itemsize, fill, np.uint8))
-    if hist is None:
-        hist = np.zeros(n_streams * 2 * PCM_HIST + 2 * GLUE_GUARD, np.float32)
-        hist[:GLUE_GUARD] = hist[-GLUE_GUARD:] = -3e38
-    assert hist.dtype == np.float32 and hist.size == n_streams * 2 * PCM_HIST + 2 * GLUE_GUARD and hist.flags["C_CONTIGUOUS"]
-    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
-    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
-    n_out = np.full(max(len(wholes), 1), -1, np.int64)
-    try:
-        _chk(lib().q3tts_op_pcm_convert(_p(flat), G, _p(cs), cs.size, _p(sl), n_streams, C.cast(fm, C.c_void_p), _p(rb), ptrs, _p(nbytes),
-                                        _p(n_out), _p(hist)))
-    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
-        ex.wholes, ex.n_out, ex.hist = wholes, n_out[: len(wholes)].copy(), hist
-        raise
-    outs = []
-    for w, (r, e), n in zip(wholes, fmts, want):
-        v = w.view(pcm_dtype(e))
-        outs.append(v[GLUE_GUARD: GLUE_GUARD + n].copy())
-    return outs, wholes, n_out[: len(wholes)].copy(), hist
+    hist = _stage_store(hist, n_streams, 2 * PCM_HIST)
+    (ptrs, nbytes), n_out = _stage_bufs(wholes), np.full(max(len(wholes), 1), -1, np.int64)
+    n_out = _stage_call(lib().q3tts_op_pcm_convert, _p(flat), G, _p(cs), cs.size, _p(sl), n_streams, C.cast(fm, C.c_void_p), _p(rb), ptrs, _p(nbytes),
+                        _p(n_out), _p(hist), n_out=n_out[: len(wholes)], wholes=wholes, hist=hist)
+    outs = [w.view(pcm_dtype(e))[GLUE_GUARD: GLUE_GUARD + n].copy() for w, (r, e), n in zip(wholes, fmts, want)]
+    return outs, wholes, n_out, hist
 
 
 # ---- speaking rate: the host-only half and the stretch kernel (q3tts_op_tsm) ----
@@ -2327,18 +2354,9 @@ def op_tsm(x, chunk_samples, streams, n_streams, rates, encodings, reset_before=
     is made exactly as large as the result plus `slack` elements, every byte `fill`.  A position whose slot is reset starts a new utterance: its
     counts start over.  Returns (outs, traces, wholes, twholes, n_out, hist).  A refused call raises Q3Error carrying wholes / twholes / n_out /
     hist as they are then."""
-    x = np.ascontiguousarray(x, np.float32)
-    G = x.shape[0] if x.ndim == 2 else 0
-    cs = np.ascontiguousarray(chunk_samples, np.int32)
-    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
-    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    G, cs, sl, rb, flat = _stage_inputs(x, chunk_samples, streams, reset_before)
     rt = np.ascontiguousarray(rates, np.int32)
     en = np.ascontiguousarray(encodings, np.int32)
-    parts, at = [], 0
-    for t in cs:                       # [n_chunks concatenated][G][T_c]
-        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
-        at += max(int(t), 0)
-    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G and sum(p.size for p in parts) else np.zeros(1, np.float32)
     wholes, twholes, want, dts = [], [], [], []
     seen, done, ns, frs = {}, {}, [0] * len(rt), [0] * len(rt)   # the plan, as the call works it out: counters per slot, starting over at a reset
     for c in range(cs.size + (1 if flush else 0)):
@@ -2361,26 +2379,13 @@ def op_tsm(x, chunk_samples, streams, n_streams, rates, encodings, reset_before=
         want.append((ns[g], frs[g])); dts.append(dt)
         wholes.append(np.full((ns[g] + slack + 2 * GLUE_GUARD) * np.dtype(dt).itemsize, fill, np.uint8))
         twholes.append(np.full(frs[g] + slack + 2 * GLUE_GUARD, 0x5A5A5A5A, np.int32))
-    if hist is None:
-        hist = np.zeros(n_streams * TSM_HIST + 2 * GLUE_GUARD, np.float32)
-        hist[:GLUE_GUARD] = hist[-GLUE_GUARD:] = -3e38
-    assert hist.dtype == np.float32 and hist.size == n_streams * TSM_HIST + 2 * GLUE_GUARD and hist.flags["C_CONTIGUOUS"]
-    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
-    tptrs = (C.c_void_p * max(len(twholes), 1))(*[w.ctypes.data for w in twholes])
-    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
-    tlen = np.array([w.size for w in twholes] or [0], np.int64)
-    n_out = np.full(max(len(wholes), 1), -1, np.int64)
-    try:
-        pad = np.zeros(1, np.int32)    # an empty list still hands the call a pointer
-        _chk(lib().q3tts_op_tsm(_p(flat), G, _p(cs), cs.size, _p(sl if sl.size else pad), n_streams, _p(rt if rt.size else pad),
-                                _p(en if en.size else pad), _p(rb), 1 if flush else 0, ptrs, _p(nbytes),
-                                _p(n_out), tptrs, _p(tlen), _p(hist)))
-    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
-        ex.wholes, ex.twholes, ex.n_out, ex.hist = wholes, twholes, n_out[: len(wholes)].copy(), hist
-        raise
+    hist = _stage_store(hist, n_streams, TSM_HIST)
+    (ptrs, nbytes), (tptrs, tlen), n_out = _stage_bufs(wholes), _stage_bufs(twholes), np.full(max(len(wholes), 1), -1, np.int64)
+    n_out = _stage_call(lib().q3tts_op_tsm, _p(flat), G, _p(cs), cs.size, _pz(sl), n_streams, _pz(rt), _pz(en), _p(rb), 1 if flush else 0, ptrs,
+                        _p(nbytes), _p(n_out), tptrs, _p(tlen), _p(hist), n_out=n_out[: len(wholes)], wholes=wholes, twholes=twholes, hist=hist)
     outs = [w.view(dt)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, dt, (n, fr) in zip(wholes, dts, want)]
     traces = [t[GLUE_GUARD: GLUE_GUARD + fr].copy() for t, (n, fr) in zip(twholes, want)]
-    return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist
+    return outs, traces, wholes, twholes, n_out, hist
 
 
 # ---- volume: the host-only half and the volume kernel (q3tts_op_volume) ----
@@ -2395,39 +2400,18 @@ def op_volume(x, chunk_samples, streams, n_streams, volumes, reset_before=None, 
     [n_streams][VOL_HIST], GLUE_GUARD floats) or None for a zero store between guards of -3e38.  Every output and trace buffer is made exactly
     as large as the result plus `slack` elements, every byte `fill`; trace=False passes no traces.  Returns (outs, traces, wholes, twholes,
     n_out, hist).  A refused call raises Q3Error carrying wholes / twholes / n_out / hist as they are then."""
-    x = np.ascontiguousarray(x, np.float32)
-    G = x.shape[0] if x.ndim == 2 else 0
-    cs = np.ascontiguousarray(chunk_samples, np.int32)
-    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
-    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    G, cs, sl, rb, flat = _stage_inputs(x, chunk_samples, streams, reset_before)
     vo = np.ascontiguousarray(volumes, np.int32)
-    parts, at = [], 0
-    for t in cs:                       # [n_chunks concatenated][G][T_c]
-        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
-        at += max(int(t), 0)
-    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G and sum(p.size for p in parts) else np.zeros(1, np.float32)
     n = int(sum(max(int(t), 0) for t in cs))
     wholes = [np.full((n + slack + 2 * GLUE_GUARD) * 4, fill, np.uint8) for _ in range(len(vo))]
     twholes = [np.full((n + slack + 2 * GLUE_GUARD) * 4, fill, np.uint8) for _ in range(len(vo))] if trace else []
-    if hist is None:
-        hist = np.zeros(n_streams * VOL_HIST + 2 * GLUE_GUARD, np.float32)
-        hist[:GLUE_GUARD] = hist[-GLUE_GUARD:] = -3e38
-    assert hist.dtype == np.float32 and hist.size == n_streams * VOL_HIST + 2 * GLUE_GUARD and hist.flags["C_CONTIGUOUS"]
-    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
-    tptrs = (C.c_void_p * max(len(twholes), 1))(*[w.ctypes.data for w in twholes]) if trace else None
-    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
-    tlen = np.array([w.size // 4 for w in twholes] or [0], np.int64)
-    n_out = np.full(max(len(wholes), 1), -1, np.int64)
-    try:
-        pad = np.zeros(1, np.int32)    # an empty list still hands the call a pointer
-        _chk(lib().q3tts_op_volume(_p(flat), G, _p(cs), cs.size, _p(sl if sl.size else pad), n_streams, _p(vo if vo.size else pad), _p(rb),
-                                   ptrs, _p(nbytes), _p(n_out), tptrs, _p(tlen), _p(hist)))
-    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
-        ex.wholes, ex.twholes, ex.n_out, ex.hist = wholes, twholes, n_out[: len(wholes)].copy(), hist
-        raise
+    hist = _stage_store(hist, n_streams, VOL_HIST)
+    (ptrs, nbytes), (tptrs, tlen), n_out = _stage_bufs(wholes), _stage_bufs(twholes, 4), np.full(max(len(wholes), 1), -1, np.int64)
+    n_out = _stage_call(lib().q3tts_op_volume, _p(flat), G, _p(cs), cs.size, _pz(sl), n_streams, _pz(vo), _p(rb), ptrs, _p(nbytes), _p(n_out),
+                        tptrs if trace else None, _p(tlen), _p(hist), n_out=n_out[: len(wholes)], wholes=wholes, twholes=twholes, hist=hist)
     outs = [w.view(np.float32)[GLUE_GUARD: GLUE_GUARD + n].copy() for w in wholes]
     traces = [t.view(np.float32)[GLUE_GUARD: GLUE_GUARD + n].copy() for t in twholes]
-    return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist
+    return outs, traces, wholes, twholes, n_out, hist
 
 
 # ---- pitch: the host-only half and the pitch kernel (q3tts_op_pitch) ----
@@ -2470,19 +2454,10 @@ def op_pitch(x, chunk_samples, streams, n_streams, rates, pitches, encodings, re
     guards of -3e38.  Every output and trace buffer is made exactly as large as the result plus `slack` elements, every byte `fill`.
     Returns (outs, traces, wholes, twholes, n_out, hist, zhist).  A refused call raises Q3Error carrying wholes / twholes / n_out / hist /
     zhist as they are then."""
-    x = np.ascontiguousarray(x, np.float32)
-    G = x.shape[0] if x.ndim == 2 else 0
-    cs = np.ascontiguousarray(chunk_samples, np.int32)
-    sl = np.ascontiguousarray(streams, np.int32).reshape(cs.size, -1)
-    rb = None if reset_before is None else np.ascontiguousarray(reset_before, np.int32).reshape(cs.size, -1)
+    G, cs, sl, rb, flat = _stage_inputs(x, chunk_samples, streams, reset_before)
     rt = np.ascontiguousarray(rates, np.int32)
     pt = np.ascontiguousarray(pitches, np.int32)
     en = np.ascontiguousarray(encodings, np.int32)
-    parts, at = [], 0
-    for t in cs:                       # [n_chunks concatenated][G][T_c]
-        parts.append(x[:, at: at + max(int(t), 0)].reshape(-1))
-        at += max(int(t), 0)
-    flat = np.ascontiguousarray(np.concatenate(parts)) if parts and G and sum(p.size for p in parts) else np.zeros(1, np.float32)
     wholes, twholes, want, dts = [], [], [], []
     seen, ns, frs = {}, [0] * len(rt), [0] * len(rt)   # the plan, as the call works it out: native samples per slot, starting over at a reset
 
@@ -2510,28 +2485,11 @@ def op_pitch(x, chunk_samples, streams, n_streams, rates, pitches, encodings, re
         want.append((ns[g], frs[g])); dts.append(dt)
         wholes.append(np.full((ns[g] + slack + 2 * GLUE_GUARD) * np.dtype(dt).itemsize, fill, np.uint8))
         twholes.append(np.full(frs[g] + slack + 2 * GLUE_GUARD, 0x5A5A5A5A, np.int32))
-
-    def store(h, width):
-        if h is None:
-            h = np.zeros(n_streams * width + 2 * GLUE_GUARD, np.float32)
-            h[:GLUE_GUARD] = h[-GLUE_GUARD:] = -3e38
-        assert h.dtype == np.float32 and h.size == n_streams * width + 2 * GLUE_GUARD and h.flags["C_CONTIGUOUS"]
-        return h
-
-    hist, zhist = store(hist, TSM_HIST), store(zhist, PITCH_HIST)
-    ptrs = (C.c_void_p * max(len(wholes), 1))(*[w.ctypes.data for w in wholes])
-    tptrs = (C.c_void_p * max(len(twholes), 1))(*[w.ctypes.data for w in twholes])
-    nbytes = np.array([w.size for w in wholes] or [0], np.int64)
-    tlen = np.array([w.size for w in twholes] or [0], np.int64)
-    n_out = np.full(max(len(wholes), 1), -1, np.int64)
-    try:
-        pad = np.zeros(1, np.int32)    # an empty list still hands the call a pointer
-        _chk(lib().q3tts_op_pitch(_p(flat), G, _p(cs), cs.size, _p(sl if sl.size else pad), n_streams, _p(rt if rt.size else pad),
-                                  _p(pt if pt.size else pad), _p(en if en.size else pad), _p(rb), 1 if flush else 0, ptrs, _p(nbytes),
-                                  _p(n_out), tptrs, _p(tlen), _p(hist), _p(zhist)))
-    except Q3Error as ex:   # a refused call: the caller can see that nothing was written
-        ex.wholes, ex.twholes, ex.n_out, ex.hist, ex.zhist = wholes, twholes, n_out[: len(wholes)].copy(), hist, zhist
-        raise
+    hist, zhist = _stage_store(hist, n_streams, TSM_HIST), _stage_store(zhist, n_streams, PITCH_HIST)
+    (ptrs, nbytes), (tptrs, tlen), n_out = _stage_bufs(wholes), _stage_bufs(twholes), np.full(max(len(wholes), 1), -1, np.int64)
+    n_out = _stage_call(lib().q3tts_op_pitch, _p(flat), G, _p(cs), cs.size, _pz(sl), n_streams, _pz(rt), _pz(pt), _pz(en), _p(rb), 1 if flush else 0,
+                        ptrs, _p(nbytes), _p(n_out), tptrs, _p(tlen), _p(hist), _p(zhist), n_out=n_out[: len(wholes)], wholes=wholes, twholes=twholes,
+                        hist=hist, zhist=zhist)
     outs = [w.view(dt)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, dt, (n, fr) in zip(wholes, dts, want)]
     traces = [t[GLUE_GUARD: GLUE_GUARD + fr].copy() for t, (n, fr) in zip(twholes, want)]
-    return outs, traces, wholes, twholes, n_out[: len(wholes)].copy(), hist, zhist
+    return outs, traces, wholes, twholes, n_out, hist, zhist

@@ -4,9 +4,10 @@ the counts and the history stores.  The cases go through op_pcm_convert, op_tsm 
 script runs unchanged against any build that has those entry points: a refactor of the stages is judged by running it against the build
 before and the build after.  At most 9 frames a case, one process, a few seconds.
 
-  python scripts/output_stage_digest.py [--lib PATH/libq3tts.so] [--out FILE.json]
+  python scripts/output_stage_digest.py [--lib PATH/libq3tts.so] [--out FILE.json] [--volume-out FILE.json]
 
-tests/golden/output_stage_digests.json holds what one build printed; tests/test_gpu_output_stage_bits.py asserts it of the current one."""
+tests/golden/output_stage_digests.json holds what one build printed; tests/test_gpu_output_stage_bits.py asserts it of the current one.
+volume_cases() does the same for op_volume, recorded apart (tests/golden/output_stage_volume_digests.json) by a later build."""
 import argparse
 import hashlib
 import json
@@ -97,22 +98,41 @@ def cases(q):
                   hist=store(q, 5, 2 * q.PCM_HIST, 34))
 
 
+def volume_cases(q):
+    """the same for op_volume, traces on: tests/golden/output_stage_volume_digests.json"""
+    x = signals()
+
+    def volume(name, sched, vols, **kw):
+        slots = kw.pop("slots", np.tile(np.arange(3, dtype=np.int32), (len(sched), 1)))
+        outs, traces, wholes, twholes, n_out, hist = q.op_volume(x, [f * FRAME for f in sched], slots, kw.pop("n_streams", 3), vols, trace=True,
+                                                                 slack=8, **kw)
+        return name, sha(*wholes, *twholes, n_out, hist)
+
+    for sched in ((9,), STREAMED):
+        yield volume("volume/%s" % "-".join(map(str, sched)), sched, [120, -60, 200])
+    yield volume("volume/with-unity", STREAMED, [0, 200, 0])
+    slots, reset = permuted(STREAMED)
+    yield volume("volume/permuted-reset", STREAMED, [120, -60, 200], slots=slots, n_streams=5, reset_before=reset, hist=store(q, 5, q.VOL_HIST, 35))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", help="another build's libq3tts.so to run the cases against")
     ap.add_argument("--out", help="also write the digests to this JSON file")
+    ap.add_argument("--volume-out", help="also write the op_volume digests to this JSON file")
     a = ap.parse_args()
     import q3tts as q
     if a.lib:
         q.LIB_PATH = os.path.abspath(a.lib)
-    got = {}
-    for name, d in cases(q):
-        print("%s  %s" % (d, name), flush=True)
-        got[name] = d
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(got, f, indent=1, sort_keys=True)
-            f.write("\n")
+    for gen, path in ((cases, a.out), (volume_cases, a.volume_out)):
+        got = {}
+        for name, d in gen(q):
+            print("%s  %s" % (d, name), flush=True)
+            got[name] = d
+        if path:
+            with open(path, "w") as f:
+                json.dump(got, f, indent=1, sort_keys=True)
+                f.write("\n")
 
 
 if __name__ == "__main__":

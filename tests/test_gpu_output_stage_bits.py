@@ -5,7 +5,11 @@ tests/golden/output_stage_digests.json was recorded by scripts/output_stage_dige
 k_pcm_convert each carried their own copy of the frame step, the upload ring and the int16 packing.  One SHA-1 per case over every byte
 q3tts_op_pcm_convert, q3tts_op_tsm and q3tts_op_pitch return: the outputs and traces with their guards, the counts, the history stores.  The
 other GPU tests of these kernels judge them against float64 with bounds; this one holds a change that is meant to compute nothing new to
-the same bits.  A digest that differs means the kernels or their launchers changed what they compute: the fixture is not re-recorded for that."""
+the same bits.  A digest that differs means the kernels or their launchers changed what they compute: the fixture is not re-recorded for that.
+
+tests/golden/output_stage_volume_digests.json is the same for q3tts_op_volume (volume_cases of the script), recorded against the build of commit
+87dfdfc ("Volume: gain with a look-ahead limiter on the device, any output stage"), the last one in which the four entry points' Python
+wrappers each carried their own prelude and postlude."""
 import importlib.util
 import json
 import os
@@ -17,14 +21,21 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 with open(os.path.join(ROOT, "tests", "golden", "output_stage_digests.json")) as f:
     GOLDEN = json.load(f)
+with open(os.path.join(ROOT, "tests", "golden", "output_stage_volume_digests.json")) as f:
+    GOLDEN_VOLUME = json.load(f)
 
 
 @pytest.fixture(scope="module")
-def digests(gpu):
+def script():
     spec = importlib.util.spec_from_file_location("output_stage_digest", os.path.join(ROOT, "scripts", "output_stage_digest.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    return dict(mod.cases(gpu))
+    return mod
+
+
+@pytest.fixture(scope="module")
+def digests(gpu, script):
+    return dict(script.cases(gpu))
 
 
 def test_the_cases_are_the_recorded_ones(digests):
@@ -34,3 +45,7 @@ def test_the_cases_are_the_recorded_ones(digests):
 @pytest.mark.parametrize("name", sorted(GOLDEN))
 def test_bytes_are_those_of_the_recorded_build(digests, name):
     assert digests[name] == GOLDEN[name]
+
+
+def test_the_volume_stage_gives_the_bytes_of_the_recorded_build(gpu, script):
+    assert dict(script.volume_cases(gpu)) == GOLDEN_VOLUME

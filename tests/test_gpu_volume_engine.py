@@ -371,6 +371,109 @@ def test_three_volumes_side_by_side_with_a_native_request(gpu, eng4, takes):
         _check(gpu, o["pcm"], ref["pcm"], db10, "side by side")
 
 
+def test_all_four_kinds_of_stream_in_the_same_passes(gpu, eng4, takes):
+    """native, converted, stretched and shifted side by side: every stage of the pass tail runs in every pass, each on its own stream"""
+    n, S16, F32 = 8, gpu.PCM_S16, gpu.PCM_F32
+    refs = takes.together([(90 + i, n, {}) for i in range(4)])             # the same four side by side, without any setting
+    #          format          rate pitch volume
+    specs = [(None,            100, 100, 0),
+             ((16000, S16),    100, 100, 60),
+             ((24000, F32),    125, 100, -60),
+             ((24000, S16),    100, 80,  200)]
+    stats = lambda: (eng4.pcm_out_stats(), eng4.tsm_stats(), eng4.pitch_stats(), eng4.volume_stats())
+    c0, t0, p0, v0 = stats()
+    rids = []
+    for i, (fmt, rate, pitch, db10) in enumerate(specs):
+        eng4.set_output_format(*(fmt or (None,)))
+        eng4.set_speech_rate(rate)
+        eng4.set_pitch(pitch)
+        eng4.set_volume(db10)
+        rids.append(eng4.submit(takes.prompt(90 + i), max_steps=n, seed=90 + i, mask_eos=True, want_pcm=True))
+    eng4.set_volume(0)
+    eng4.set_pitch(100)
+    eng4.set_speech_rate(100)
+    eng4.set_output_format(None)
+    for r, (fmt, rate, pitch, db10) in zip(rids, specs):
+        assert eng4.request_format(r) == (fmt or (24000, F32))
+        assert (eng4.request_speech_rate(r), eng4.request_pitch(r), eng4.request_volume(r)) == (rate, pitch, db10)
+    _until(eng4, lambda: all(eng4.poll(r)["state"] == gpu.REQ_DONE for r in rids))
+    out = [eng4.result(r, want_pcm=True) for r in rids]
+    c1, t1, p1, v1 = stats()
+    for o, ref in zip(out, refs):
+        assert np.array_equal(o["codes"], ref["codes"])
+    v = [volumed(gpu, ref["pcm"], s[3]) for ref, s in zip(refs, specs)]
+    want = [refs[0]["pcm"],                                                # the native request: the bytes of the run without any setting
+            gpu.op_pcm_convert(v[1][None, :], [v[1].size], [[0]], 1, [(16000, S16)])[0][0],
+            gpu.op_tsm(v[2][None, :], [v[2].size], [[0]], 1, [125], [F32], flush=True)[0][0],
+            gpu.op_pitch(v[3][None, :], [v[3].size], [[0]], 1, [100], [80], [S16], flush=True)[0][0]]
+    counts = [n * SPF, gpu.pcm_out_samples(16000, n * SPF), gpu.tsm_samples(125, n * SPF, True), gpu.pitch_samples(100, 80, n * SPF, True)]
+    assert counts[1] == n * 1280 and counts[2] % gpu.TSM_HOP == 0 and min(counts) > 0
+    for o, w, cnt, what in zip(out, want, counts, ("native", "converted", "stretched", "shifted")):
+        assert o["n_pcm"] == cnt == w.size and o["pcm"].dtype == w.dtype and o["pcm"].size == cnt, what
+        assert np.array_equal(o["pcm"].view(np.uint8), w.view(np.uint8)), what
+    chunks = -(-n // 4)
+    assert (c1["chunks_converted"] - c0["chunks_converted"], c1["samples_out"] - c0["samples_out"]) == (chunks, counts[1])
+    assert (t1["chunks"] - t0["chunks"], t1["frames_out"] - t0["frames_out"], t1["flushes"] - t0["flushes"]) == (chunks, counts[2] // gpu.TSM_HOP, 1)
+    assert (p1["chunks"] - p0["chunks"], p1["samples_out"] - p0["samples_out"], p1["flushes"] - p0["flushes"]) == (chunks, counts[3], 1)
+    assert p1["table_bytes"] == 366999 * 4                                 # all 151 tables, uploaded once
+    assert (v1["chunks"] - v0["chunks"], v1["samples"] - v0["samples"]) == (3 * chunks, 3 * n * SPF)
+    _drain(eng4)
+
+
+KNOWN_REFUSALS = ("a speech rate needs the 24000 Hz output format", "max_steps at this speech rate makes more PCM than a request's staging holds")
+
+
+def test_a_request_takes_settings_that_stood_together(gpu, eng4, takes):
+    """One lock over the whole record.  With the scheduler stopped, a thread flips (format, rate) between (16000 s16, 100) and (24000 f32, 125)
+    through the two setters, in an order such that every state on the way -- (24000 f32, 100) -- is itself acceptable, while this thread
+    submits.  Every accepted request carries a pair that stood at some instant; a refusal carries a known text.  (16000 s16, 125), the old
+    format with the new rate or the reverse, never stood: a submit that read it would have been refused with the first of the texts, and a
+    request that carries it is a torn record."""
+    import threading
+    S16, F32 = gpu.PCM_S16, gpu.PCM_F32
+    stood = {((16000, S16), 100), ((24000, F32), 100), ((24000, F32), 125)}
+    prompt, stop, failed = takes.prompt(95), threading.Event(), []
+
+    def flip():
+        try:
+            for _ in range(3000):
+                if stop.is_set():
+                    break
+                eng4.set_output_format(24000, F32)                         # (16000 s16, 100) -> (24000 f32, 100) -> (24000 f32, 125)
+                eng4.set_speech_rate(125)
+                eng4.set_speech_rate(100)                                  # and back: the rate first, then the format
+                eng4.set_output_format(16000, S16)
+        except Exception as ex:                                            # noqa: BLE001 -- reported by the main thread
+            failed.append(ex)
+
+    eng4.set_output_format(16000, S16)
+    th = threading.Thread(target=flip)
+    th.start()
+    rids, seen = [], set()
+    try:
+        for i in range(64):
+            try:
+                rid = eng4.submit(prompt, max_steps=1, seed=95, mask_eos=True, want_pcm=True)
+            except gpu.Q3Error as ex:
+                assert any(t in str(ex) for t in KNOWN_REFUSALS), str(ex)
+                continue
+            rids.append(rid)
+            pair = (eng4.request_format(rid), eng4.request_speech_rate(rid))
+            assert pair in stood, pair
+            seen.add(pair)
+    finally:
+        stop.set()
+        th.join(WAIT_MS / 1e3)
+        eng4.set_speech_rate(100)
+        eng4.set_output_format(None)
+    assert not th.is_alive() and not failed, failed
+    print("%d of 64 accepted, pairs seen: %s" % (len(rids), sorted(seen)))
+    _until(eng4, lambda: all(eng4.poll(r)["state"] == gpu.REQ_DONE for r in rids), limit=20000)
+    for r in rids:
+        eng4.release(r)
+    _drain(eng4)
+
+
 def test_under_the_ggml_arithmetic(gpu, tiny_model, vivian):
     old = os.environ.get("Q3_SPEC")
     os.environ["Q3_SPEC"] = "ggml"
