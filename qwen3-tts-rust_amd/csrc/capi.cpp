@@ -516,7 +516,7 @@ static int submit_text(q3tts_engine* e, int32_t voice_id, const int32_t* text_id
 
 int q3tts_engine_stats(q3tts_engine* e, q3tts_stats* o) {
     Q3_API_BEGIN
-    const EngineStats& s = e->e->stats;
+    const EngineStats& s = e->e->read_stats();
     o->frame_loop_ms = s.frame_loop_ms; o->frames = s.frames; o->prefill_ms = s.prefill_ms; o->gemv_ms = s.gemv_ms;
     o->gemv_launches = s.gemv_launches; o->gemv_bytes = s.gemv_bytes; o->codec_ms = s.codec_ms; o->codec_calls = s.codec_calls;
     o->gu_ms = s.gu_ms; o->gu_launches = s.gu_launches; o->gu_bytes = s.gu_bytes;

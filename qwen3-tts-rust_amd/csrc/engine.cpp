@@ -152,10 +152,7 @@ Engine::Engine(const EngineParams& p) : p_(p) {
         static const int lanes_env = [] { const char* e = std::getenv("Q3_CODEC_LANES"); return e ? atoi(e) : 0; }();
         const int n_lanes = B > 1 ? (lanes_env > 0 ? std::min(lanes_env, 8) : 2) : 1;
         codec_.reset(new CodecDecoder(p.model_dir + "/onnx/q3tts_codec.gguf", n_cs, 4, n_lanes, gmax));
-        st2_.resize(n_lanes);
-        for (auto& s2 : st2_) Q3_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-        slot_cap_ = (size_t)p.max_steps * codec_->samples_per_frame();
-        Q3_HIP(hipHostMalloc((void**)&pcm_pinned_, (size_t)n_cs * slot_cap_ * sizeof(float)));
+        worker_.reset(new CodecWorker(codec_.get(), dev_, n_lanes, n_cs, (size_t)p.max_steps * codec_->samples_per_frame()));
         Q3_HIP(hipHostMalloc((void**)&pre_tails_, (size_t)Q3TTS_MAX_PREAMBLES * Q3_PCM_HIST * sizeof(float))); // [EXT] codec preambles: 24 KB
         for (int i = Q3TTS_MAX_PREAMBLES - 1; i >= 0; i--) pre_tail_free_.push_back(i);
         for (int c = n_cs - 1; c >= 0; c--) cs_free_.push_back(c);
@@ -201,31 +198,22 @@ void* Engine::d2h_begin(const void* src, size_t bytes) {
 // ---------------------------------------------------------------------------------------------------------------
 struct CandSet { std::vector<float> prompt; std::vector<int32_t> trail; }; // [EXT] candidate sets: what the members of a set share
 struct Engine::Req {
-    int64_t id = 0;
+    // What the decoder thread sees of the request (codec_worker.h); everything else here is the scheduler's, and the thread cannot name it.
+    // A decode-only one (job.decode): codes / fed hold the caller's frames from submission on; never has a slot, job.cs from admit_decodes to its fence
+    CodecJob job;
     int64_t set = 0; std::shared_ptr<const CandSet> shared; // [EXT] candidate sets: the set's id (0 = a plain request) and its one prompt / trail copy
     const std::vector<int32_t>& trail_ids() const { return shared ? shared->trail : trail_own; }
     GenRequest r; std::vector<float> prompt_own; std::vector<int32_t> trail_own; bool want_pcm = false;
     std::vector<int32_t> prefix_own; // [EXT] resume: the caller's frames [n_prefix][16]; codes starts as a copy of it and fed at n_prefix
     bool closed = false;  // [EXT] open trail (r.open): closed by append_trail; trail_own and closed change under mu_ only
-    bool cancel = false;  // [EXT] set by cancel() under mu_, never cleared: the request ends as REQ_CANCELLED
-    int state = REQ_QUEUED; int slot = -1, cs = -1; int fed = 0;
+    int state = REQ_QUEUED; int slot = -1; int fed = 0;
     std::vector<int32_t> codes; std::vector<float> pcm;
-    // [EXT] output formats, speaking rate, pitch, volume: what the request's PCM is delivered as, read once at submit (take_out).  pcm_enq /
-    // pcm_ready / pcm_n count delivered samples -- out_delivered(out, tsm_native, .), tsm_native = the native samples its stream has been
-    // given (decoder thread) --; pcm holds their bytes as the stage left them (pcm_n samples of 4 or 2 bytes, rounded up to whole floats)
-    OutSpec out; int64_t pcm_n = 0, tsm_native = 0;
-    size_t sample_bytes() const { return out_sample_bytes(out); }
-    bool stretched() const { return out_kind(out) >= OUT_RATED; }
-    // bytes of the samples that become available with n_more native samples more, or (final) with the flush
-    size_t bytes_due(int64_t n_more, bool final) const {
-        return (size_t)(out_delivered(out, tsm_native + n_more, final) - out_delivered(out, tsm_native, false)) * sample_bytes();
-    }
-    bool decode = false;  // [EXT] decoding given frames: codes / fed hold the caller's frames from submission on; never has a slot, cs from admit_decodes to its fence
+    int64_t pcm_n = 0; // pcm_ready / pcm_n count samples of job.out's format; pcm: their bytes as the stage left them, rounded up to whole floats
     bool score = false;   // [EXT] scoring: prefix_own holds all n frames, r.n_prefix = n - 1 feedback rows; never live; codes / lp / fed appear when it is done
     // [EXT] codec preambles: the preamble the request is primed with (-1: none; kept for request_preamble after the end), whether it still
-    // holds it, the snapshot and pinned tail its `reset` task restores (fixed at submit: the preamble was READY); build_pre: this is the hidden
-    // decode-only request that builds that preamble, and build_snap the snapshot the decoder thread enqueued at its fence
-    int pre = -1; bool pre_held = false; int pre_snap = -1; const float* pre_tail = nullptr; int build_pre = -1, build_snap = -1;
+    // holds it (what its `reset` task restores is job.pre_snap / pre_tail, fixed at submit: the preamble was READY); build_pre: this is the
+    // hidden decode-only request that builds that preamble (job.snapshot), and job.snap the snapshot the decoder thread enqueued at its fence
+    int pre = -1; bool pre_held = false; int build_pre = -1;
     // [EXT] prompt stems: the stem the request took (-1: none; kept for request_stem after the end), whether it still holds it, the rows its
     // prefill skips and the store its wave restores them from (fixed at submit: the stem was READY); build_stem: this is the hidden wave
     // member that builds that stem -- stem_rows keeps its rows alive, build_store is what the scheduler allocated for it
@@ -233,7 +221,6 @@ struct Engine::Req {
     int build_stem = -1; std::shared_ptr<const std::vector<float>> stem_rows; uint16_t* build_store = nullptr;
     bool offline() const { return score || build_stem >= 0; } // takes a slot for one wave and never goes live
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
-    size_t pcm_enq = 0;   // samples enqueued by the decoder thread (its private cursor)
     size_t pcm_ready = 0; // samples whose decode has completed (harvested events)
     std::unique_ptr<Chunker> chunker;
     uint64_t seed = 0;
@@ -249,22 +236,10 @@ static void push_frames(Chunker& c, const int32_t* codes, int n) { // n frames [
         c.push(fc, 16, false);
     }
 }
-// in bytes: a stream's region holds slot_cap_ native floats, and no format needs more bytes per frame than the native one
-unsigned char* Engine::pcm_stage(const Req& r, size_t add) const {
-    const size_t at = r.pcm_enq * r.sample_bytes();
-    Q3_CHECK(at + add <= slot_cap_ * sizeof(float), "pcm staging overflow");
-    return reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)r.cs * slot_cap_) + at;
-}
-
 Engine::~Engine() {
     (void)hipSetDevice(dev_);
     try { stop_driver(); } catch (...) {}
-    if (dec_started_) {
-        { std::lock_guard<std::mutex> lk(dmu_); dec_stop_ = true; }
-        dcv_.notify_all();
-        dec_thread_.join();
-    }
-    for (auto& c : comp_) (void)hipEventDestroy(c.ev);
+    worker_.reset(); // joins the decoder thread
     for (auto& kv : reqs_) if (kv.second->ev_admit) (void)hipEventDestroy(kv.second->ev_admit);
     for (auto& g : graphs_) {
         if (g.second->exec) (void)hipGraphExecDestroy(g.second->exec);
@@ -272,14 +247,12 @@ Engine::~Engine() {
     }
     for (auto& s : stems_.entries()) if (s.second.payload.store) (void)hipFree(s.second.payload.store); // [EXT] prompt stems
     for (auto& d : stem_garbage_) (void)hipFree(d.first);
-    if (pcm_pinned_) (void)hipHostFree(pcm_pinned_);
     if (pre_tails_) (void)hipHostFree(pre_tails_);
     if (ar_.arena) (void)hipHostFree(ar_.arena);
     if (pf_.arena) (void)hipHostFree(pf_.arena);
     if (pf_done_) (void)hipEventDestroy(pf_done_);
     if (pf_e0_) (void)hipEventDestroy(pf_e0_);
     if (st_pf_) (void)hipStreamDestroy(st_pf_);
-    for (auto s2 : st2_) (void)hipStreamDestroy(s2);
     if (st_) (void)hipStreamDestroy(st_);
 }
 
@@ -667,137 +640,13 @@ void Engine::first_head_logprobs(hipStream_t st, const float* logits_row, int b,
     launch_logprob_rows(st, la, 1);
 }
 
-// ---------------- decoder thread (the reference decodes on a second thread too, engine.rs:495-543): it owns every codec
-// launch, so the ~200 kernel launches of a chunk never delay the AR stream's launches ----------------
-void Engine::decoder_main() {
-    try {
-        Q3_HIP(hipSetDevice(dev_)); // HIP's current device is per thread
-        const int spf = codec_->samples_per_frame(), gmax = codec_->max_group(), n_lanes = (int)st2_.size();
-        std::map<Req*, std::pair<int, hipEvent_t>> last;            // request -> (lane, event after its latest chunk)
-        int next_lane = 0, dry = 0;                                 // dry: seat_chunks' count of passes that left a decode-only chunk waiting
-        for (;;) {
-            // take the oldest task; if it is a chunk, add the first pending chunk of other requests with the same frame count:
-            // one decode pass then serves the whole group (weights streamed once, one set of launches).  [EXT] The chunks of decode-only
-            // requests wait in a queue of their own and take the seats that are left; the rule is seat_chunks (sched_logic.h)
-            std::vector<DecTask> grp;
-            {
-                std::unique_lock<std::mutex> lk(dmu_);
-                dcv_.wait(lk, [&] { return dec_stop_ || (!dec_hold_ && (!dq_.empty() || !dq_lo_.empty())); });
-                if (dq_.empty() && dq_lo_.empty()) return;
-                auto heads = [](const std::deque<DecTask>& q) {
-                    std::vector<TaskHead> h;
-                    for (const DecTask& t : q) h.push_back({t.r->id, (int)t.codes.size() / 16, t.reset ? TASK_RESET : t.fence ? TASK_FENCE : TASK_CHUNK, t.epoch});
-                    return h;
-                };
-                const Seating s = seat_chunks(heads(dq_), heads(dq_lo_), gmax, dry);
-                dry = s.dry;
-                for (const Seat& c : s.seats) grp.push_back(std::move((c.low ? dq_lo_ : dq_)[c.index]));
-                for (int low = 0; low < 2; low++) { // the seated tasks leave their queue, last first
-                    std::deque<DecTask>& q = low ? dq_lo_ : dq_;
-                    std::vector<int> idx;
-                    for (const Seat& c : s.seats) if ((int)c.low == low) idx.push_back(c.index);
-                    std::sort(idx.rbegin(), idx.rend());
-                    for (int i : idx) q.erase(q.begin() + i);
-                }
-            }
-            const int G = (int)grp.size();
-            if (!grp[0].fence && !grp[0].reset) {
-                int n_low = 0;
-                for (const DecTask& t : grp) n_low += t.r->decode;
-                dec_chunks_ += n_low;
-                if (n_low < G) dec_shared_ += n_low;
-            }
-            int lane = next_lane;
-            { auto it = last.find(grp[0].r); if (G == 1 && it != last.end()) lane = it->second.first; else next_lane = (next_lane + 1) % n_lanes; }
-            for (auto& t : grp) { // a request's chunks must run in order even when consecutive groups use different lanes
-                auto it = last.find(t.r);
-                if (it != last.end() && it->second.first != lane) Q3_HIP(hipStreamWaitEvent(st2_[lane], it->second.second, 0));
-            }
-            if (grp[0].reset && grp[0].r->pre_snap >= 0) { // [EXT] codec preambles: the stream starts from the snapshot; a converting one also from the preamble's tail
-                Req* r = grp[0].r;
-                codec_->restore_async(st2_[lane], r->pre_snap, r->cs, pcm_format_native(r->out.fmt) ? nullptr : r->pre_tail);
-                pre_restores_++;
-            }
-            else if (grp[0].reset) codec_->reset_async(st2_[lane], grp[0].r->cs); // AudioDecoder::create_state for a new request
-            else if (!grp[0].fence) {
-                const int nf = (int)grp[0].codes.size() / 16;
-                std::vector<int> streams(G);
-                std::vector<float*> dst(G);
-                std::vector<int64_t> codes((size_t)G * nf * 16);
-                std::vector<OutSpec> out(G); std::vector<int64_t> n_out(G); // [EXT] what each stream is delivered as, what it was given
-                for (int g = 0; g < G; g++) {
-                    Req* r = grp[g].r;
-                    out[g] = r->out;
-                    // the samples that become available with these frames: of a stretched stream possibly none, at a slow rate more than native
-                    const size_t add = r->bytes_due((int64_t)nf * spf, false);
-                    r->tsm_native += (int64_t)nf * spf;
-                    streams[g] = r->cs; dst[g] = reinterpret_cast<float*>(pcm_stage(*r, add));
-                    std::copy(grp[g].codes.begin(), grp[g].codes.end(), codes.begin() + (size_t)g * nf * 16);
-                }
-                // engine.rs:520: decode the chunk(s) -- enqueued on a codec stream, overlapping the next AR frames
-                codec_->decode_group_async(st2_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane, out.data(), n_out.data());
-                for (int g = 0; g < G; g++) grp[g].r->pcm_enq += (size_t)n_out[g];
-            }
-            // [EXT] speaking rate: the fence of a stretching request that was not cancelled flushes its stretcher -- the hops its last samples
-            // still owe -- behind its last chunk (this lane has waited for it above), before the fence's completion is recorded
-            for (auto& t : grp) {
-                Req* r = t.r;
-                if (!t.fence || !r->stretched() || r->cancel || r->cs < 0) continue;
-                const size_t add = r->bytes_due(0, true);
-                int64_t n = 0;
-                codec_->tsm_flush_async(st2_[lane], r->cs, pcm_stage(*r, add), &n, lane);
-                r->pcm_enq += (size_t)n;
-            }
-            // [EXT] codec preambles: a build's fence enqueues the snapshot behind its last chunk (this lane has waited for it above)
-            if (grp[0].fence && grp[0].r->build_pre >= 0 && !grp[0].r->cancel) grp[0].r->build_snap = codec_->snapshot_async(st2_[lane], grp[0].r->cs);
-            for (auto& t : grp) {
-                hipEvent_t ev = nullptr;
-                if (!t.reset) {
-                    Q3_HIP(hipEventCreate(&ev));
-                    Q3_HIP(hipEventRecord(ev, st2_[lane])); // first one = the reference's first stream_tx.send (:522-523)
-                }
-                if (t.fence) { auto it = last.find(t.r); if (it != last.end()) { (void)hipEventDestroy(it->second.second); last.erase(it); } }
-                else {
-                    hipEvent_t ord;
-                    auto it = last.find(t.r);
-                    if (it == last.end()) { Q3_HIP(hipEventCreateWithFlags(&ord, hipEventDisableTiming)); last[t.r] = {lane, ord}; }
-                    else { ord = it->second.second; it->second.first = lane; }
-                    Q3_HIP(hipEventRecord(ord, st2_[lane]));
-                }
-                if (t.reset) continue;
-                std::lock_guard<std::mutex> lk(dmu_);
-                comp_.push_back(Completion{t.r, ev, t.r->pcm_enq, t.fence});
-                if (!t.fence) stats.codec_calls++;
-            }
-            dcv_.notify_all();
-        }
-    } catch (const std::exception& ex) {
-        std::lock_guard<std::mutex> lk(dmu_);
-        derr_ = ex.what();
-        dcv_.notify_all();
-    }
-}
-
 // collects finished codec work: PCM watermark per request, first-chunk latency, request completion
 void Engine::harvest(bool block) {
     for (;;) {
-        Completion c;
-        {
-            std::unique_lock<std::mutex> lk(dmu_);
-            if (!derr_.empty()) throw Error("decoder thread: " + derr_);
-            if (comp_.empty()) {
-                if (!block) return;
-                dcv_.wait_for(lk, std::chrono::milliseconds(2));
-                if (comp_.empty()) return;
-            }
-            c = comp_.front();
-            if (!block && hipEventQuery(c.ev) != hipSuccess) return; // completions of a lane finish in order; keep it simple: FIFO
-            comp_.pop_front();
-            dec_pending_--;
-        }
-        Q3_HIP(hipEventSynchronize(c.ev));
-        Req* r = c.r;
+        CodecWorker::Completion c;
+        if (!worker_ || !worker_->poll_completion(block, &c)) return;
         std::lock_guard<std::mutex> lk(mu_);
+        Req* r = &req(c.job->id);
         r->pcm_ready = c.pcm_after;
         if (!r->first_seen && c.pcm_after > 0) {
             float ms = 0;
@@ -808,18 +657,18 @@ void Engine::harvest(bool block) {
         (void)hipEventDestroy(c.ev);
         if (c.fence) {
             r->pcm_n = (int64_t)c.pcm_after; // the bytes as they are: whole floats for f32, (n + 1) / 2 of them for s16
-            r->pcm.assign(pcm_pinned_ + (size_t)r->cs * slot_cap_, pcm_pinned_ + (size_t)r->cs * slot_cap_ + (c.pcm_after * r->sample_bytes() + 3) / 4);
-            cs_free_.push_back(r->cs);
-            r->cs = -1;
-            r->state = fenced_state(r->cancel); r->t_done = now_ms();
+            r->pcm.assign(worker_->staging(r->job.cs), worker_->staging(r->job.cs) + (c.pcm_after * r->job.sample_bytes() + 3) / 4);
+            cs_free_.push_back(r->job.cs);
+            r->job.cs = -1;
+            r->state = fenced_state(r->job.cancel); r->t_done = now_ms();
             n_draining_--;
-            if (r->decode) n_decoding_--;
+            if (r->job.decode) n_decoding_--;
             drop_held(r); // [EXT] codec preambles, prompt stems: the restores this request and its wave enqueued have completed
             if (r->build_pre >= 0) { // the preamble is built: its snapshot is on the device, its last native samples become its tail
                 bool ok = false;
                 if (auto* e = pres_.find(r->build_pre)) {
                     PreHeld& p = e->payload;
-                    p.snap = r->build_snap;
+                    p.snap = r->job.snap;
                     ok = p.snap >= 0 && r->pcm.size() >= (size_t)Q3_PCM_HIST;
                     if (ok) { std::copy(r->pcm.end() - Q3_PCM_HIST, r->pcm.end(), pre_tails_ + (size_t)p.tail * Q3_PCM_HIST); pre_built_++; }
                 }
@@ -905,7 +754,7 @@ Engine::Req& Engine::req(int64_t id) {
     return *it->second;
 }
 int64_t Engine::enqueue(std::unique_ptr<Req> r, std::deque<Req*>& queue) {
-    const int64_t id = r->id = next_id_++;
+    const int64_t id = r->job.id = next_id_++;
     queue.push_back(r.get());
     reqs_[id] = std::move(r);
     wake_++;
@@ -964,7 +813,7 @@ void Engine::submit_candidates(const GenRequest& g0, bool want_pcm, const uint64
         r->r.prefix = r->prefix_own.data();
         r->shared = sh;
         r->want_pcm = want_pcm && codec_;
-        if (r->want_pcm) take_out(r.get(), g.max_steps, i == 0 ? nullptr : &rs[0]->out); // [EXT] the output settings, read once per set
+        if (r->want_pcm) take_out(r.get(), g.max_steps, i == 0 ? nullptr : &rs[0]->job.out); // [EXT] the output settings, read once per set
         r->t_submit = t;
         rs.push_back(std::move(r));
     }
@@ -993,7 +842,7 @@ int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
     Req& r = req(id);
     Q3_CHECK(r.r.open, "the request was not submitted with an open trail");
     Q3_CHECK(!r.closed, "the request's trail is already closed");
-    if (r.cancel || (r.state != REQ_QUEUED && r.state != REQ_RUNNING)) return 1; // cancelled, finished (EOS / max_steps), done or failed: nothing appended
+    if (r.job.cancel || (r.state != REQ_QUEUED && r.state != REQ_RUNNING)) return 1; // cancelled, finished (EOS / max_steps), done or failed: nothing appended
     Q3_CHECK(r.trail_own.size() + (size_t)n <= (size_t)p_.max_prompt, "the trail would exceed max_prompt ids");
     r.trail_own.insert(r.trail_own.end(), ids, ids + n);
     if (close) r.closed = true;
@@ -1006,7 +855,7 @@ int Engine::append_trail(int64_t id, const int32_t* ids, int n, bool close) {
 void Engine::trail_progress(int64_t id, int* n_appended, int* n_consumed, bool* closed) {
     std::lock_guard<std::mutex> lk(mu_);
     const Req& r = req(id);
-    Q3_CHECK(!r.decode, "a decode-only request has no trail");
+    Q3_CHECK(!r.job.decode, "a decode-only request has no trail");
     const int n = (int)r.trail_ids().size();
     *n_appended = n; *n_consumed = std::min(r.fed, n); *closed = !r.r.open || r.closed;
 }
@@ -1039,10 +888,10 @@ int Engine::cancel(int64_t id) {
     Req& r = req(id);
     Q3_CHECK(r.build_stem < 0, "unknown request id"); // [EXT] prompt stems: a build is internal; q3tts_stem_release is how a stem goes
     if (req_ended(r.state)) return 1;
-    if (r.cancel) return 0; // the first cancel is still pending
-    r.cancel = true;
+    if (r.job.cancel) return 0; // the first cancel is still pending
+    r.job.cancel = true;
     if (cancel_action(r.state, false, false, r.want_pcm) == CANCEL_AT_ONCE) {
-        std::deque<Req*>& q = r.decode ? decode_q_ : pending_;
+        std::deque<Req*>& q = r.job.decode ? decode_q_ : pending_;
         q.erase(std::find(q.begin(), q.end(), &r));
         r.state = REQ_CANCELLED; r.t_done = now_ms();
         drop_held(&r); // [EXT] codec preambles, prompt stems: it never enqueued a restore
@@ -1050,15 +899,6 @@ int Engine::cancel(int64_t id) {
     wake_++;
     cv_.notify_all();
     return 0;
-}
-
-// drops the chunk tasks of r the decoder thread has not taken yet (dmu_ held); what it has taken runs to its end
-void Engine::purge_chunks(Req* r) {
-    std::deque<DecTask>& q = r->decode ? dq_lo_ : dq_;
-    for (auto it = q.begin(); it != q.end();) {
-        if (it->r == r && !it->fence && !it->reset) { it = q.erase(it); dec_pending_--; }
-        else ++it;
-    }
 }
 
 // scheduler thread, between two frame groups: live slots of cancelled requests are retired, draining ones lose their unstarted chunks;
@@ -1078,7 +918,7 @@ void Engine::collect_cancels() {
             switch (cancel_action(r->state, r->slot >= 0 && !is_live, is_live, r->want_pcm)) {
             case CANCEL_AT_ACTIVATE: cancel_ids_.push_back(id); break;
             case CANCEL_RETIRE: case CANCEL_RETIRE_FENCE: live.push_back(r); break;
-            case CANCEL_PURGE: { std::lock_guard<std::mutex> dlk(dmu_); purge_chunks(r); } break;
+            case CANCEL_PURGE: worker_->purge(&r->job); break;
             default: break;
             }
         }
@@ -1112,7 +952,7 @@ void Engine::admit(bool stalled) {
             for (int b = 0; b < B_; b++) if (!slot_req_[b]) { slot = b; break; }
             pending_.pop_front();
             r->slot = slot;
-            if (r->want_pcm) { r->cs = cs_free_.back(); cs_free_.pop_back(); }
+            if (r->want_pcm) { r->job.cs = cs_free_.back(); cs_free_.pop_back(); }
             r->state = REQ_RUNNING; r->t_admit = now_ms();
             slot_req_[slot] = r;
             batch.push_back(r);
@@ -1121,15 +961,8 @@ void Engine::admit(bool stalled) {
     if (batch.empty()) return;
     alloc_stem_stores(batch); // [EXT] prompt stems: the stores of the wave's builds
     for (Req* r : batch) {
-        if (r->want_pcm) { // the decoder thread clears the codec stream's state right before the request's first chunk
-            { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, {}, false, false, true}); }
-            dcv_.notify_all();
-        }
-        r->chunker.reset(new Chunker([this, r](const int64_t* codes, int n_codes, bool is_final) {
-            if (!r->want_pcm) return;
-            { std::lock_guard<std::mutex> lk(dmu_); dq_.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false, dec_epoch_}); dec_pending_++; }
-            dcv_.notify_all();
-        }));
+        if (r->want_pcm) worker_->push_reset(&r->job); // the decoder thread clears the codec stream's state right before the request's first chunk
+        r->chunker.reset(new Chunker([this, r](const int64_t* codes, int n_codes, bool is_final) { if (r->want_pcm) worker_->push_chunk(&r->job, codes, n_codes, is_final); }));
         Q3_HIP(hipEventCreate(&r->ev_admit));
     }
     if (async_pf_ && n_active_ > 0) { prefill_async(batch); return; } // sequences are running: do not stall them
@@ -1165,7 +998,7 @@ void Engine::admit(bool stalled) {
 int64_t Engine::submit_decode(const int32_t* codes, int n) {
     if (const char* why = decode_refusal(codes, n, p_.max_steps, codec_ != nullptr)) throw Error(why);
     std::unique_ptr<Req> r(new Req());
-    r->decode = true; r->want_pcm = true;
+    r->job.decode = true; r->want_pcm = true;
     take_out(r.get(), n); // [EXT] the engine's output settings
     r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
@@ -1183,32 +1016,26 @@ void Engine::admit_decodes() {
     for (int take = decode_admit((int)decode_q_.size(), (int)cs_free_.size(), n_decoding_, decode_w_); take > 0; take--) {
         Req* r = decode_q_.front();
         decode_q_.pop_front();
-        r->cs = cs_free_.back(); cs_free_.pop_back();
+        r->job.cs = cs_free_.back(); cs_free_.pop_back();
         r->state = REQ_DRAINING; r->t_admit = now_ms();
         n_draining_++; n_decoding_++;
         dec_admitted_.push_back(r);
     }
 }
 
-// A request's whole task list -- reset, the chunks a Chunker cuts from its frames, fence -- goes to the low queue in one piece.
+// A request's whole task list -- reset, the chunks a Chunker cuts from its frames, fence -- goes to the low queue in one piece (part of run_group's hand-over, or one of its own).
 void Engine::enqueue_decodes() {
     std::vector<Req*> batch;
     batch.swap(dec_admitted_);
     for (Req* r : batch) {
         Q3_HIP(hipEventCreate(&r->ev_admit));
         Q3_HIP(hipEventRecord(r->ev_admit, st_)); // the AR stream is idle here: marks "admitted"
-        std::vector<DecTask> tasks;
-        tasks.push_back(DecTask{r, {}, false, false, true});
-        Chunker cut([&](const int64_t* codes, int n_codes, bool is_final) { tasks.push_back(DecTask{r, std::vector<int64_t>(codes, codes + n_codes), is_final, false, false}); });
+        CodecWorker::Handover piece(worker_.get(), true);
+        worker_->push_reset(&r->job);
+        Chunker cut([&](const int64_t* codes, int n_codes, bool is_final) { worker_->push_chunk(&r->job, codes, n_codes, is_final); });
         push_frames(cut, r->codes.data(), r->fed);
         cut.push(nullptr, 0, true);
-        tasks.push_back(DecTask{r, {}, false, true, false});
-        {
-            std::lock_guard<std::mutex> lk(dmu_);
-            dec_pending_ += (int)tasks.size() - 1; // the chunks and the fence
-            for (DecTask& t : tasks) dq_lo_.push_back(std::move(t));
-        }
-        dcv_.notify_all();
+        worker_->push_fence(&r->job);
     }
 }
 
@@ -1236,7 +1063,7 @@ void Engine::go_live(const std::vector<Req*>& batch) {
     bool prefix_pcm = false; // [EXT] resume: the chunks the wave's prefixes make up are one hand-over to the decoder thread
     for (Req* r : batch) prefix_pcm = prefix_pcm || (r->want_pcm && r->r.n_prefix >= 4);
     {
-        DecHold hold(this, codec_ != nullptr && prefix_pcm);
+        CodecWorker::Handover hold(worker_.get(), worker_ && prefix_pcm);
         for (Req* r : batch) {
             const int b = r->slot;
             slots_.load(b, r->r);
@@ -1286,8 +1113,8 @@ void Engine::activate() {
     {   // [EXT] requests cancelled while the wave ran do not go live; their wave-mates are not disturbed
         std::lock_guard<std::mutex> lk(mu_);
         const double t = now_ms();
-        for (Req* r : batch) if (r->cancel) { r->prefill_ms = t - r->t_submit; dropped.push_back(r); }
-        batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->cancel; }), batch.end());
+        for (Req* r : batch) if (r->job.cancel) { r->prefill_ms = t - r->t_submit; dropped.push_back(r); }
+        batch.erase(std::remove_if(batch.begin(), batch.end(), [](Req* r) { return r->job.cancel.load(); }), batch.end());
     }
     for (Req* r : dropped) retire(r, false); // slot, KV pages and -- through the fence, behind the reset task already queued -- codec stream
     for (Req* r : batch) if (r->score) scores.push_back(r); // [EXT] scoring: a score request never goes live
@@ -1408,7 +1235,7 @@ void Engine::finish_scores(const std::vector<Req*>& scores) {
     for (Req* r : scores) {
         const int b = r->slot, n = r->r.max_steps;
         bool cancelled;
-        { std::lock_guard<std::mutex> lk(mu_); cancelled = r->cancel; }
+        { std::lock_guard<std::mutex> lk(mu_); cancelled = r->job.cancel; }
         const float* rows = nullptr;
         if (!cancelled) {
             ar_.cur.reset();
@@ -1417,7 +1244,7 @@ void Engine::finish_scores(const std::vector<Req*>& scores) {
         }
         {
             std::lock_guard<std::mutex> lk(mu_);
-            if (r->cancel) r->state = REQ_CANCELLED;
+            if (r->job.cancel) r->state = REQ_CANCELLED;
             else {
                 r->codes = r->prefix_own;
                 r->lp.assign(rows, rows + (size_t)n * Q3_LOGPROB_COLS);
@@ -1443,17 +1270,13 @@ void Engine::retire(Req* r, bool flush_tail) {
         slot_req_[b] = nullptr;
         if (slots_.live[b]) { slots_.live[b] = 0; n_active_--; }
         r->slot = -1;
-        r->state = retired_state(r->want_pcm, r->cancel);
+        r->state = retired_state(r->want_pcm, r->job.cancel);
         if (r->want_pcm) n_draining_++;
         else { r->t_done = now_ms(); drop_held(r); cv_.notify_all(); } // [EXT] prompt stems: its wave completed before it went live or was dropped (without PCM it holds no preamble)
     }
     if (r->want_pcm) {
-        {
-            std::lock_guard<std::mutex> lk(dmu_);
-            if (!flush_tail) purge_chunks(r);
-            dq_.push_back(DecTask{r, {}, false, true, false}); dec_pending_++;
-        }
-        dcv_.notify_all();
+        if (!flush_tail) worker_->purge(&r->job);
+        worker_->push_fence(&r->job);
     }
     slots_.reset(b); h_pend_[b].clear();
     kv_t_->release(b); // from the next group on the slot steps on the scratch sequence (upload_slot_state)
@@ -1517,10 +1340,8 @@ void Engine::run_group() {
     }
     std::memcpy(h_nfr, p_nfr, (size_t)width * 4); std::memcpy(h_fin, p_fin, (size_t)width * 4);
     // The group's chunks, the tails and fences of the slots it retires and the tasks of the decode-only requests admitted in this step reach
-    // the decoder thread as one hand-over: it forms no pass meanwhile (microseconds), and seat_chunks keeps the chunks of one hand-over
-    // together.  Handed over one by one, the thread would start a pass with the chunks that happened to have arrived: which streams share a
-    // pass, and with it the GEMM forms a request's samples go through, would depend on the two threads' timing
-    DecHold hold(this, codec_ != nullptr);
+    // the decoder thread as one hand-over (CodecWorker::Handover): it forms no pass meanwhile (microseconds)
+    CodecWorker::Handover hold(worker_.get(), worker_ != nullptr);
     for (int b = 0; b < width; b++) {
         if (!slots_.live[b]) continue;
         Req* r = slot_req_[b];
@@ -1546,7 +1367,7 @@ static const bool g_trace = std::getenv("Q3_SCHED_TRACE") != nullptr;
 bool Engine::step() {
     std::lock_guard<std::mutex> step_lock(step_mu_);
     Q3_HIP(hipSetDevice(dev_)); // HIP's current device is per thread: any thread may drive any engine of a multi-device group
-    if (codec_ && !dec_started_) { dec_started_ = true; dec_thread_ = std::thread([this] { decoder_main(); }); }
+    if (worker_) worker_->start();
     const double t0 = now_ms();
     harvest(false);
     const double t1 = now_ms();
@@ -1564,8 +1385,7 @@ bool Engine::step() {
     // [EXT] live text append: when every live slot waits for text, no frame group runs (graph_frames stays put); prefill and codec
     // work still proceed, and with none left the driver sleeps until a submit or an append
     const bool stalled = n_active_ > 0 && slots_.all_live_stalled();
-    int dec_pending = 0;
-    if (stalled) { std::lock_guard<std::mutex> lk(dmu_); dec_pending = dec_pending_; }
+    const int dec_pending = stalled && worker_ ? worker_->pending() : 0;
     if (n_active_ > 0 && !stalled) run_group();
     else if (n_prefilling_ > 0) { Q3_HIP(hipEventSynchronize(pf_done_)); activate(); }
     else if (n_draining_ > 0 || dec_pending > 0) harvest(true);
@@ -1596,7 +1416,7 @@ ReqStatus Engine::poll(int64_t id) {
 void Engine::fetch(int64_t id, int32_t* codes, int frame_off, int max_frames, float* pcm, int64_t pcm_off, int64_t pcm_cap, int* got_frames, int64_t* got_pcm) {
     std::lock_guard<std::mutex> lk(mu_);
     const Req& r = req(id);
-    if (pcm) Q3_CHECK(r.out.fmt.encoding == Q3_PCM_F32, "the request delivers int16 PCM: fetch it with fetch_pcm16"); // [EXT] output formats; nothing is copied
+    if (pcm) Q3_CHECK(r.job.out.fmt.encoding == Q3_PCM_F32, "the request delivers int16 PCM: fetch it with fetch_pcm16"); // [EXT] output formats; nothing is copied
     int nf = 0; int64_t np = 0;
     if (codes && frame_off >= 0 && frame_off < r.fed) {
         nf = std::min(max_frames, r.fed - frame_off);
@@ -1612,10 +1432,10 @@ int64_t Engine::copy_pcm(const Req& r, void* out, int64_t off, int64_t cap) cons
     const bool done = r.state == REQ_DONE || r.state == REQ_CANCELLED;
     const int64_t avail = done ? r.pcm_n : (int64_t)r.pcm_ready;
     const unsigned char* src = done ? reinterpret_cast<const unsigned char*>(r.pcm.data())
-                                    : (r.cs >= 0 ? reinterpret_cast<const unsigned char*>(pcm_pinned_ + (size_t)r.cs * slot_cap_) : nullptr);
+                                    : (r.job.cs >= 0 ? reinterpret_cast<const unsigned char*>(worker_->staging(r.job.cs)) : nullptr);
     if (!src || off >= avail || cap <= 0) return 0;
     const int64_t n = std::min(cap, avail - off);
-    const size_t b = r.sample_bytes();
+    const size_t b = r.job.sample_bytes();
     std::memcpy(out, src + (size_t)off * b, (size_t)n * b);
     return n;
 }
@@ -1628,12 +1448,12 @@ void Engine::set_output_format(const q3tts_pcm_format* f) {
 }
 q3tts_pcm_format Engine::request_format(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).out.fmt;
+    return req(id).job.out.fmt;
 }
 void Engine::fetch_pcm16(int64_t id, int16_t* out, int64_t off, int64_t cap, int64_t* got) {
     std::lock_guard<std::mutex> lk(mu_);
     const Req& r = req(id);
-    Q3_CHECK(r.out.fmt.encoding == Q3_PCM_S16, "the request delivers f32 PCM: fetch it with fetch");
+    Q3_CHECK(r.job.out.fmt.encoding == Q3_PCM_S16, "the request delivers f32 PCM: fetch it with fetch");
     Q3_CHECK(out && off >= 0, "null buffer or negative offset");
     const int64_t n = copy_pcm(r, out, off, cap);
     if (got) *got = n;
@@ -1652,12 +1472,12 @@ void Engine::take_out(Req* r, int max_steps, const OutSpec* given) const {
     OutSpec o;
     if (given) o = *given;
     else { std::lock_guard<std::mutex> lk(out_mu_); o = out_; }
-    if (const char* why = out_submit_refusal(o, max_steps, (int64_t)(slot_cap_ * sizeof(float)), codec_ != nullptr)) throw Error(why);
-    r->out = o;
+    if (const char* why = out_submit_refusal(o, max_steps, worker_ ? (int64_t)worker_->slot_bytes() : 0, codec_ != nullptr)) throw Error(why);
+    r->job.out = o;
 }
 int Engine::request_speech_rate(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).out.rate_pct;
+    return req(id).job.out.rate_pct;
 }
 // [EXT] pitch (q3tts_spec.h "pitch")
 void Engine::set_pitch(int pct) {
@@ -1668,7 +1488,7 @@ void Engine::set_pitch(int pct) {
 }
 int Engine::request_pitch(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).out.pitch_pct;
+    return req(id).job.out.pitch_pct;
 }
 // [EXT] volume (q3tts_spec.h "volume")
 void Engine::set_volume(int db10) {
@@ -1678,7 +1498,7 @@ void Engine::set_volume(int db10) {
 }
 int Engine::request_volume(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
-    return req(id).out.vol_db10;
+    return req(id).job.out.vol_db10;
 }
 
 // [EXT] codec preambles and prompt stems (q3tts_spec.h "codec preambles" / "prompt stems"): the held objects.  Who holds what is counted by
@@ -1699,7 +1519,7 @@ void Engine::drop_held(Req* r) {
 }
 void Engine::end_build(Req* r) {
     if (r->ev_admit) (void)hipEventDestroy(r->ev_admit);
-    reqs_.erase(r->id);
+    reqs_.erase(r->job.id);
     cv_.notify_all();
 }
 template <class T> void Engine::held_poll(T& tab, int id, int* state, int* n) {
@@ -1750,14 +1570,14 @@ void Engine::pre_attach(Req* r, int pid) {
     auto* p = pres_.find(pid);
     Q3_CHECK(p && p->refs.state == Q3TTS_PREAMBLE_READY, "the request's preamble is not ready");
     pres_.hold(pid);
-    r->pre = pid; r->pre_held = true; r->pre_snap = p->payload.snap; r->pre_tail = pre_tails_ + (size_t)p->payload.tail * Q3_PCM_HIST;
+    r->pre = pid; r->pre_held = true; r->job.pre_snap = p->payload.snap; r->job.pre_tail = pre_tails_ + (size_t)p->payload.tail * Q3_PCM_HIST;
 }
 int Engine::preamble_create(const int32_t* codes, int n) {
     std::unique_ptr<Req> r(new Req());
     int live = 0;
     { std::lock_guard<std::mutex> lk(mu_); live = pres_.live(); }
     if (const char* why = preamble_refusal(codes, n, p_.max_steps, codec_ != nullptr, live, Q3TTS_CODEC_MAX_FRAMES)) throw Error(why);
-    r->decode = true; r->want_pcm = true; // native format: the tail is taken from the staging region's floats
+    r->job.decode = true; r->want_pcm = true; // native format: the tail is taken from the staging region's floats
     r->r.max_steps = n; r->r.n_prompt = 0; r->r.sampler.temperature = 0.0f;
     r->codes.assign(codes, codes + (size_t)n * 16); r->fed = n;
     r->t_submit = now_ms();
@@ -1765,7 +1585,7 @@ int Engine::preamble_create(const int32_t* codes, int n) {
     Q3_CHECK(pres_.live() < Q3TTS_MAX_PREAMBLES && !pre_tail_free_.empty(), "Q3TTS_MAX_PREAMBLES preambles are live: release one first");
     const int pid = pres_.add(n);
     pres_.at(pid).payload.tail = pre_tail_free_.back(); pre_tail_free_.pop_back();
-    r->build_pre = pid;
+    r->build_pre = pid; r->job.snapshot = true;
     enqueue(std::move(r), decode_q_);
     return pid;
 }
@@ -1774,7 +1594,7 @@ int Engine::request_preamble(int64_t id) {
     return req(id).pre;
 }
 void Engine::preamble_stats(int64_t* built, int64_t* restores, int64_t* bytes_per_snapshot) const {
-    *built = pre_built_.load(); *restores = pre_restores_.load();
+    *built = pre_built_.load(); *restores = worker_ ? worker_->pre_restores.load() : 0;
     *bytes_per_snapshot = codec_ ? (int64_t)codec_->snapshot_bytes() : 0;
 }
 

@@ -5,13 +5,14 @@
 // hipGraph (everything a frame needs -- codes, positions, sampler state, finished flags -- lives on the device).
 // A scheduler admits queued requests into free slots (batched multi-sequence prefill), replays the frame graph in
 // groups of 4 frames (one streaming step, engine.rs:505-512), retires sequences on EOS / max_steps and hands
-// finished 4-frame chunks to a decoder thread (engine.rs:495-543) that runs the codec on its own HIP streams.
+// finished 4-frame chunks to a decoder thread (engine.rs:495-543; CodecWorker, codec_worker.h) that runs the codec on its own HIP streams.
 // Sampling (greedy and temperature/top-k/top-p, llama/mod.rs:666-776) is on device.
 #pragma once
 #include "transformer.h"
 #include "host_logic.h"
 #include "sched_logic.h"
 #include "codec.h"
+#include "codec_worker.h"
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -105,7 +106,7 @@ public:
     int decode_width() const { return decode_w_; }
     // decode-only requests accepted, their chunks decoded, and of those the chunks that shared a pass with a generating request's chunk
     void decode_stats(int64_t* requests, int64_t* chunks, int64_t* chunks_shared) const {
-        *requests = dec_reqs_.load(); *chunks = dec_chunks_.load(); *chunks_shared = dec_shared_.load();
+        *requests = dec_reqs_.load(); *chunks = worker_ ? worker_->dec_chunks.load() : 0; *chunks_shared = worker_ ? worker_->dec_shared.load() : 0;
     }
     // [EXT] output formats (q3tts_spec.h "output formats"): requests submitted from now on with want_pcm deliver this format (NULL: native);
     // read once per request at submit and once per candidate set; generate_batch always delivers native.  Thread-safe, no HIP calls; throws
@@ -178,7 +179,8 @@ public:
     Transformer& talker() { return *talker_; }
     Transformer& predictor() { return *predictor_; }
     CodecDecoder* codec() { return codec_.get(); }
-    EngineStats stats; void reset_stats() { stats = EngineStats(); }
+    EngineStats stats; void reset_stats() { read_stats(); stats = EngineStats(); }
+    const EngineStats& read_stats() { if (worker_) stats.codec_calls += worker_->take_codec_calls(); return stats; } // the decoder thread counts its own
     void set_instrument(bool on) { instrument_ = on; }
     size_t bytes_per_frame_step(int batch, double mean_ctx) const; // algorithmic HBM bytes of one batched frame step
     size_t pred_table_bytes() const { return pred_table_bytes_; }  // the predictor's layer-0 q/k/v table (0 = off: Q3_PRED_L0_TABLE=0 or Q3_SPEC=ggml)
@@ -255,9 +257,7 @@ private:
     void collect_appends();   // scheduler: new ids / close flags of live open slots into the slot table (upload in run_group)
     void collect_cancels();   // scheduler: retires the slots of cancelled requests, drops the unstarted chunks of draining ones
     void harvest(bool block);
-    void purge_chunks(Req* r);
     void retire(Req* r, bool flush_tail); // the slot leaves the batch: EOS / max_steps (tail flushed) or a cancel (tail and unstarted chunks dropped)
-    void decoder_main();
     int64_t copy_pcm(const Req& r, void* out, int64_t off, int64_t cap) const;
     // [EXT] output formats, speaking rate, pitch, volume: the engine-level settings as one record (OutSpec, sched_logic.h).  A setter writes its
     // field and take_out reads the whole record, both under out_mu_, so a request's settings are a record that stood at some instant.  A
@@ -274,9 +274,6 @@ private:
 
     EngineParams p_;
     hipStream_t st_ = nullptr; int dev_ = 0;
-    std::vector<hipStream_t> st2_; // codec decoder lanes: overlapped with the next AR frames and with each other
-    float* pcm_pinned_ = nullptr; size_t slot_cap_ = 0;
-    unsigned char* pcm_stage(const Req& r, size_t add) const; // where the decoder thread's next `add` bytes of r land in its stream's region
     std::unique_ptr<HostAssets> assets_;
     std::unique_ptr<Transformer> talker_, predictor_, talker_pf_;
     hipStream_t st_pf_ = nullptr; PrefillLane ar_, pf_;
@@ -285,6 +282,7 @@ private:
     int pf_chunk_ = 256; // rows of one prompt chunk of the asynchronous lane, and the least the in-line lane takes (512: Q8_0 talker, wide GEMM forms)
     std::unique_ptr<KvPool> kv_t_, kv_p_;
     std::unique_ptr<CodecDecoder> codec_;
+    std::unique_ptr<CodecWorker> worker_; // the decoder thread with its lanes, queues and PCM staging; with a codec only
     // device assets
     DevBuf<float> d_codec_tab_[16]; DevBuf<float> d_proj_tab_[16];
     DevBuf<float> d_qkv0_tab_[16]; bool pred_l0_table_ = false; size_t pred_table_bytes_ = 0; // Q_q[c]: the predictor's layer-0 q/k/v of P_q[c], q = 1..14
@@ -339,7 +337,7 @@ private:
     // too), the limit, and the counters
     std::deque<Req*> decode_q_; int n_decoding_ = 0, decode_w_ = 0;
     std::vector<Req*> dec_admitted_;    // admitted in this step, tasks not yet enqueued (scheduler thread only)
-    std::atomic<int64_t> dec_reqs_{0}, dec_chunks_{0}, dec_shared_{0};
+    std::atomic<int64_t> dec_reqs_{0};
     // [EXT] codec preambles and prompt stems (all under mu_) live in one HeldTable each (sched_logic.h): the live objects by id, the next id,
     // the engine-level setting and every count of who holds what are the table's.  The engine keeps what the two kinds differ in: what an
     // object owns (its payload) and how a recycled payload is disposed of (recycled()).
@@ -352,7 +350,7 @@ private:
     HeldTable<PreHeld> pres_{"preamble"}; HeldTable<StemHeld> stems_{"stem"};
     float* pre_tails_ = nullptr; std::vector<int> pre_tail_free_;
     std::vector<std::pair<uint16_t*, int64_t>> stem_garbage_;
-    std::atomic<int64_t> pre_built_{0}, pre_restores_{0};
+    std::atomic<int64_t> pre_built_{0};
     std::atomic<int64_t> stem_built_{0}, stem_restores_{0}, stem_rows_{0}, stem_pages_{0}, stem_miss_{0}, stem_bytes_{0};
     void recycled(const std::optional<PreHeld>& p);  // nothing when the table handed nothing back (mu_ held, as everything below)
     void recycled(const std::optional<StemHeld>& s);
@@ -372,21 +370,6 @@ private:
     bool stalled_idle_ = false;         // the last step() ran nothing: every live slot waits for text and nothing else is in flight
     std::vector<Voice> voices_;
     std::thread driver_; bool driver_on_ = false, driver_stop_ = false;
-    // decoder thread
-    struct DecTask { Req* r; std::vector<int64_t> codes; bool is_final; bool fence; bool reset; int64_t epoch = 0; }; // epoch: the hand-over it came with (seat_chunks)
-    struct Completion { Req* r; hipEvent_t ev; size_t pcm_after; bool fence; };
-    std::thread dec_thread_; bool dec_started_ = false, dec_stop_ = false;
-    std::mutex dmu_; std::condition_variable dcv_;
-    std::deque<DecTask> dq_, dq_lo_; std::deque<Completion> comp_; // dq_lo_: [EXT] the tasks of decode-only requests (seat_chunks)
-    bool dec_hold_ = false;             // the scheduler is handing over a frame group's chunks and decode-only tasks: no pass is formed meanwhile (dmu_)
-    int64_t dec_epoch_ = 0;             // hand-overs so far (scheduler thread): the tasks of one carry its number and arrive in one piece
-    struct DecHold {                    // one hand-over: a new epoch, and the decoder thread forms no pass until every task of it is queued
-        Engine* e; bool on;
-        DecHold(Engine* e_, bool on_) : e(e_), on(on_) { if (on) { e->dec_epoch_++; std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = true; } }
-        ~DecHold() { if (on) { { std::lock_guard<std::mutex> lk(e->dmu_); e->dec_hold_ = false; } e->dcv_.notify_all(); } }
-    };
-    int dec_pending_ = 0;               // chunk / fence tasks whose completion has not been harvested yet (dmu_)
-    std::string derr_;
     LaunchTimer timer_, timer_gu_;
 };
 

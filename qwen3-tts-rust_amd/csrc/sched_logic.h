@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume, and the one record of a stream's output settings with what follows from it.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass and the queues they wait in, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume, and the one record of a stream's output settings with what follows from it.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <optional>
 #include <stdexcept>
@@ -433,6 +434,51 @@ inline Seating seat_chunks(const std::vector<TaskHead>& live, const std::vector<
     out.dry = seated_low ? 0 : heads.empty() ? 0 : dry + 1;
     return out;
 }
+
+// The decoder thread's two queues and every count that goes with them; the thread's owner locks around it.  Job is what the thread sees of a
+// request: `id` (TaskHead::req) and `decode` (which queue).
+//   pending  chunk and fence tasks queued, or taken and their completion not yet popped (a reset completes nothing).  Assigned here only
+//   hold     hand-overs open: the scheduler queues a frame group's chunks, fences and decode-only tasks and no step is taken meanwhile
+//   epoch    hand-overs so far; a generating request's chunk carries the number of the one it came with, every other task none (seat_chunks)
+template <class Job> struct CodecQueue {
+    struct Task { Job* job; TaskKind kind; std::vector<int64_t> codes; bool is_final; int64_t epoch; };
+    std::deque<Task> live, low;
+    int pending = 0, hold = 0, dry = 0; int64_t epoch = 0; // dry: seat_chunks' count, carried from step to step
+    void open() { if (hold++ == 0) epoch++; } // a hand-over inside another belongs to it
+    void close() { hold--; }
+    void push(Job* j, TaskKind kind, const int64_t* codes = nullptr, int n_codes = 0, bool is_final = false) {
+        (j->decode ? low : live).push_back(Task{j, kind, std::vector<int64_t>(codes, codes + n_codes), is_final, kind == TASK_CHUNK && !j->decode ? epoch : 0});
+        if (kind != TASK_RESET) pending++;
+    }
+    void purge(Job* j) { // the chunks of j nobody has taken yet; what has been taken runs to its end
+        std::deque<Task>& q = j->decode ? low : live;
+        for (auto it = q.begin(); it != q.end();) {
+            if (it->job == j && it->kind == TASK_CHUNK) { it = q.erase(it); pending--; }
+            else ++it;
+        }
+    }
+    bool ready() const { return hold == 0 && !(live.empty() && low.empty()); }
+    std::vector<Task> take(int gmax) { // the next step: what seat_chunks seats, in its order; nothing while a hand-over is open
+        std::vector<Task> step;
+        if (!ready()) return step;
+        auto heads = [](const std::deque<Task>& q) {
+            std::vector<TaskHead> h;
+            for (const Task& t : q) h.push_back({t.job->id, (int)t.codes.size() / 16, t.kind, t.epoch});
+            return h;
+        };
+        const Seating s = seat_chunks(heads(live), heads(low), gmax, dry);
+        dry = s.dry;
+        for (const Seat& c : s.seats) step.push_back(std::move((c.low ? low : live)[c.index]));
+        for (int lo = 0; lo < 2; lo++) { // the seated tasks leave their queue, last first
+            std::vector<int> idx;
+            for (const Seat& c : s.seats) if ((int)c.low == lo) idx.push_back(c.index);
+            std::sort(idx.rbegin(), idx.rend());
+            for (int i : idx) (lo ? low : live).erase((lo ? low : live).begin() + i);
+        }
+        return step;
+    }
+    void popped() { pending--; } // a chunk's or a fence's completion has left the completion FIFO
+};
 
 // How many entries from the head of the queue the next admission wave takes.  A plain request (set = 0) needs a slot, a codec stream when it
 // wants PCM, and -- limit_rows: an asynchronous wave, whose prompts sit in one staging arena -- room for its rows below max_rows unless it
