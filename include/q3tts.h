@@ -267,6 +267,31 @@ int q3tts_engine_pitch_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples_
 int q3tts_engine_set_volume(q3tts_engine* e, int32_t db10);
 int q3tts_request_volume(q3tts_engine* e, int64_t req_id, int32_t* db10);
 int q3tts_engine_volume_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples);
+/* [EXT] loudness (q3tts_spec.h "loudness"): a request's loudness is measured on the device, as ITU-R BS.1770-4 defines it: K-weighting and
+ * the energy and sample peak of every 100 ms block of the native 24000 Hz stream, read behind the output conv and in front of the volume
+ * and every other output stage, so the meter sees what the model made whatever the request is delivered as (s16, 8000 Hz, a rate, a pitch,
+ * a volume).  The gate runs on the host.  Opt-in per request; an unmetered request keeps its launches, and codes, log-probability rows and
+ * PCM never depend on the meter.
+ * q3tts_engine_set_loudness: requests submitted from now on, through any q3tts_submit* form with want_pcm (text, trailing, open, resume,
+ * candidates, decode), are metered (on != 0) or not.  Read once per request at submit and once per candidate set, together with the other
+ * output settings.  Thread-safe; works under Q3_SPEC=ggml.  < 0: an engine without a codec.
+ * Not metered: want_pcm = 0, q3tts_generate_batch*, scoring, preamble builds.  A primed request starts the meter from a reset.
+ * q3tts_fetch_loudness: rows [block_off, block_off + max_blocks) that are available now into out [got][2] = {energy, peak}: the sum of the
+ * squared K-weighted samples of the block and the largest |x| in it.  The rows grow with q3tts_poll's n_pcm; n frames give floor(0.8 n) at
+ * the end, the unfinished last block does not come out, and a cancelled request keeps the rows of the chunks it keeps.  < 0: an unknown
+ * id, or a request that is not metered.
+ * q3tts_request_loudness: q3tts_loudness_gate over the rows so far.
+ * q3tts_request_metered: whether a request was submitted metered.
+ * q3tts_engine_loudness_stats: stream chunks the meter has taken and blocks it has completed (both 0, and nothing allocated, while no
+ * request was metered).
+ * To bring a request to a target loudness: meter it, take q3tts_loudness_gain_db10(integrated_lufs, target), set that volume and
+ * q3tts_submit_decode the request's frames. */
+typedef struct { double integrated_lufs, momentary_max_lufs, peak_dbfs; int32_t n_blocks, n_gated; } q3tts_loudness;
+int q3tts_engine_set_loudness(q3tts_engine* e, int32_t on);
+int q3tts_fetch_loudness(q3tts_engine* e, int64_t req_id, double* out /* [got][2] */, int64_t block_off, int64_t max_blocks, int64_t* got);
+int q3tts_request_loudness(q3tts_engine* e, int64_t req_id, q3tts_loudness* out);
+int q3tts_request_metered(q3tts_engine* e, int64_t req_id, int32_t* on);
+int q3tts_engine_loudness_stats(q3tts_engine* e, int64_t* chunks, int64_t* blocks);
 /* [EXT] codec preambles (q3tts_spec.h "codec preambles"): a request's codec stream starts from the state behind given frames -- a clone
  * voice's reference codes -- instead of zeros, so its first sample is already "in the voice".  The state is built once per preamble and
  * kept on the device; a primed request restores it with one device-to-device launch where the zeroing launch ran.  Opt-in; codes,
@@ -488,6 +513,10 @@ int q3tts_group_set_pitch(q3tts_group* g, int32_t pitch_pct);   /* [EXT] q3tts_e
 int q3tts_group_request_pitch(q3tts_group* g, int64_t req_id, int32_t* pitch_pct);
 int q3tts_group_set_volume(q3tts_group* g, int32_t db10);   /* [EXT] q3tts_engine_set_volume on every engine */
 int q3tts_group_request_volume(q3tts_group* g, int64_t req_id, int32_t* db10);
+int q3tts_group_set_loudness(q3tts_group* g, int32_t on);   /* [EXT] q3tts_engine_set_loudness on every engine */
+int q3tts_group_fetch_loudness(q3tts_group* g, int64_t req_id, double* out, int64_t block_off, int64_t max_blocks, int64_t* got);
+int q3tts_group_request_loudness(q3tts_group* g, int64_t req_id, q3tts_loudness* out);
+int q3tts_group_request_metered(q3tts_group* g, int64_t req_id, int32_t* on);
 /* [EXT] codec preambles on every engine under one id, as voices are (create preambles through the group only); _wait waits for all of them */
 int q3tts_group_preamble_create(q3tts_group* g, const int32_t* codes, int32_t n, int32_t* preamble_id);
 int q3tts_group_preamble_wait(q3tts_group* g, int32_t preamble_id, double timeout_ms);
@@ -1106,6 +1135,34 @@ float q3tts_volume_gain(int32_t db10);
 int q3tts_op_volume(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
                     const int32_t* vol_db10, const int32_t* reset_before, float* const* out, const int64_t* out_bytes, int64_t* n_out,
                     float* const* gain_trace, const int64_t* trace_len, float* hist_store);
+
+/* [EXT] loudness (q3tts_spec.h "loudness"): the BS.1770 meter, its host half and its kernel.
+ * Host only, no device needed:
+ *   q3tts_loudness_tables     coef[10] = the shelf stage's b0 b1 b2 a1 a2, then the high-pass stage's (b = 1, -2, 1), at 24000 Hz; m[16] = A^96,
+ *                             row-major: column i is the filter state after 96 zero-input steps from the unit state e_i
+ *   q3tts_loudness_gate       the gate over rows [n][2] = {energy, peak} of n 100 ms blocks: gated integrated loudness, the largest momentary
+ *                             (400 ms) loudness and the sample peak in dBFS, -INFINITY where no block qualifies; n_blocks = n, n_gated = the
+ *                             400 ms blocks past both gates.  < 0: a null argument or n < 0
+ *   q3tts_loudness_gain_db10  the volume, in tenths of a dB, that takes measured_lufs to target_lufs: rounded to nearest, clamped to
+ *                             [Q3_VOL_MIN, Q3_VOL_MAX]; 0 for a non-finite input
+ * q3tts_op_loudness is the test surface of the loudness kernel.  G streams run through n_chunks launches of the engine's launcher, one per
+ * chunk, on a fresh stage; the call keeps each slot's position as the engine keeps a request's: it grows by the chunk and a reset sets it
+ * to 0.  A stream that is not metered is neither read nor written.
+ *   in            [n_chunks] chunks one after the other, each [G][chunk_samples[c]] native f32 samples
+ *   chunk_samples [n_chunks], each a positive multiple of 1920
+ *   streams       [n_chunks][G] state slots in [0, n_streams); reset_before [n_chunks][G] (optional): nonzero = the slot is reset first
+ *   metered       [G], nonzero = the stream is metered
+ *   rows[g]       in/out, WHOLE: Q3TTS_GLUE_GUARD rows, the stream's rows [n_rows[g]][2] doubles, Q3TTS_GLUE_GUARD rows; rows_bytes[g] = its
+ *                 size in bytes (16 per row); an unmetered stream leaves its core unwritten
+ *   n_rows[g]     the blocks stream g completed
+ *   state_store   in/out, WHOLE: Q3TTS_GLUE_GUARD doubles, [n_streams][Q3_LOUD_STATE], Q3TTS_GLUE_GUARD doubles
+ * Everything is checked before anything is launched; a refused call leaves every buffer unwritten. */
+int q3tts_loudness_tables(double* coef /* [10] */, double* m /* [16] */);
+int q3tts_loudness_gate(const double* rows, int32_t n, q3tts_loudness* out);
+int32_t q3tts_loudness_gain_db10(double measured_lufs, double target_lufs);
+int q3tts_op_loudness(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                      const int32_t* metered, const int32_t* reset_before, double* const* rows, const int64_t* rows_bytes, int64_t* n_rows,
+                      double* state_store);
 
 #ifdef __cplusplus
 }

@@ -562,6 +562,44 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3_VOL_DELAY 127         /* native samples the stream is delayed by */
 #define Q3_VOL_HIST 638          /* = Q3_VOL_HOLD - 1 + Q3_VOL_DELAY: values of v kept per stream */
 
+/* ---------------- loudness [EXT] (q3tts_engine_set_loudness, q3tts_fetch_loudness, q3tts_loudness_*, q3tts_op_loudness) ----------------
+ * An ITU-R BS.1770-4 meter on the native 24000 Hz stream: K-weighting and 100 ms block energies on the device, the gate on the host.  It
+ * reads the output conv's chunk in front of "volume" and of every other output stage and writes no sample: what it measures is what the
+ * model made, never the caller's gain, format, rate or pitch.  x[n] is the stream's native f32 samples since its reset; every position is
+ * a sample index counted from the stream's reset (a preamble-primed request starts from a reset).  All of it is float64 without fused
+ * multiply-adds.
+ *   weighting  mono, channel weight 1, two biquads at fs = 24000.  The coefficients come from BS.1770's analog prototypes through the
+ *              bilinear transform, on the host in double (q3tts_loudness_tables).  With K = tan(pi f0 / fs), a0 = 1 + K/Q + K^2:
+ *                shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G/20),
+ *                           Vb = Vh^0.4996667741545416; b = [(Vh + Vb K/Q + K^2)/a0, 2(K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],
+ *                           a1 = 2(K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0
+ *                high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1], a1' and a2' as above with this K and Q
+ *              At fs = 48000 the formulas give the table printed in BS.1770
+ *   filter     transposed direct form II, v = (double) x[n], state (s1, s2, t1, t2) zero at the reset:
+ *                y = b0 v + s1;  s1 = (b1 v - a1 y) + s2;  s2 = b2 v - a2 y
+ *                z = y + t1;     t1 = (-2 y - a1' z) + t2; t2 = y - a2' z
+ *              Double is needed: the high-pass poles sit at radius 0.99 next to z = 1
+ *   segments   the evaluation order is the definition.  The stream is cut into segments of Q3_LOUD_SEG = 96 samples (96 divides a frame
+ *              of 1920 and a block of 2400).  M = A^96 is the 4x4 double matrix whose column i is the state after 96 zero-input steps from
+ *              the unit state e_i.  Per chunk: (1) every segment k runs from the zero state to its end state z_k; (2) one ascending walk,
+ *              start_0 = the stream's stored state, start_{k+1}[r] = (((M[r][0] s[0] + M[r][1] s[1]) + M[r][2] s[2]) + M[r][3] s[3]) + z_k[r]
+ *              with s = start_k; (3) every segment runs again from start_k and gives q_k = the sum of z^2, a double sum ascending from +0,
+ *              and p_k = max |x|
+ *   blocks     block j covers samples [2400 j, 2400 j + 2400): e[j] = (..((q_25j + q_25j+1) + ..) + q_25j+24), peak[j] = max p.  A block a
+ *              chunk leaves incomplete keeps its running sum and peak in the stream's state, so the sum is the same however the stream was
+ *              cut.  A chunk of T samples at position pos completes floor((pos + T) / 2400) - floor(pos / 2400) blocks, each one row
+ *              {energy, peak} of two doubles; n frames give floor(0.8 n) rows, and the unfinished last block does not come out
+ *   state      per stream Q3_LOUD_STATE = 6 doubles: s1, s2, t1, t2, the running energy, the running peak; zeroed by the stream's reset and
+ *              by a preamble restore.  No device counters: the host passes pos.  A row depends on the stream alone, never on the chunking
+ *   gate       on the host (q3tts_loudness_gate), rows e[0 .. n): 400 ms blocks at 100 ms hop, z_j = (((e_j + e_j+1) + e_j+2) + e_j+3) / 9600,
+ *              l_j = -0.691 + 10 log10 z_j.  Absolute gate l_j > -70; relative gate l_j > -0.691 + 10 log10(mean z of the absolutely gated
+ *              blocks) - 10.  integrated = -0.691 + 10 log10(mean z of the blocks past both gates); momentary maximum = max l_j;
+ *              peak = 20 log10 max peak[j] (the sample peak).  Where no block qualifies the value is -INFINITY and n_gated says so
+ *   not here   true peak (4x oversampled), short-term 3 s loudness, loudness range, an automatic gain */
+#define Q3_LOUD_SEG 96           /* samples per segment */
+#define Q3_LOUD_BLOCK 2400       /* samples per 100 ms block */
+#define Q3_LOUD_STATE 6          /* doubles of state per stream */
+
 /* ---------------- prompt stems [EXT] (q3tts_stem_*, q3tts_op_kv_stem) ----------------
  * A stem is n rows [n][2048] f32, 1 <= n < max_prompt, together with the talker K/V of those rows at positions 0 .. n-1: the head a voice's
  * prompts share, prefilled once, kept on the device in a store of its own (ceil(n / 64) whole pages per plane, the pool's page layout) and

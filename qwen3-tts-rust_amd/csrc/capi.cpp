@@ -436,6 +436,51 @@ int q3tts_engine_volume_stats(q3tts_engine* e, int64_t* chunks, int64_t* samples
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
+/* [EXT] loudness */
+int q3tts_engine_set_loudness(q3tts_engine* e, int32_t on) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->set_loudness(on != 0); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
+int q3tts_request_metered(q3tts_engine* e, int64_t id, int32_t* on) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && on, "null argument");
+    *on = e->e->request_metered(id) ? 1 : 0;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_fetch_loudness(q3tts_engine* e, int64_t id, double* out, int64_t block_off, int64_t max_blocks, int64_t* got) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && out && got, "null argument");
+    int64_t n = 0;
+    e->e->fetch_loudness(id, out, block_off, max_blocks, &n);
+    *got = n;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_request_loudness(q3tts_engine* e, int64_t id, q3tts_loudness* out) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && out, "null argument");
+    std::vector<double> rows;
+    int64_t n = 0;
+    for (;;) {   // the rows so far: fetched in pieces, since they may grow between two calls
+        const size_t at = rows.size();
+        rows.resize(at + 2 * 256);
+        e->e->fetch_loudness(id, rows.data() + at, (int64_t)(at / 2), 256, &n);
+        rows.resize(at + 2 * (size_t)n);
+        if (n < 256) break;
+    }
+    LoudResult r;
+    loud_gate(rows.data(), (int32_t)(rows.size() / 2), &r);
+    out->integrated_lufs = r.integrated_lufs; out->momentary_max_lufs = r.momentary_max_lufs; out->peak_dbfs = r.peak_dbfs;
+    out->n_blocks = r.n_blocks; out->n_gated = r.n_gated;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_engine_loudness_stats(q3tts_engine* e, int64_t* chunks, int64_t* blocks) {
+    Q3_API_BEGIN
+    Q3_CHECK(e && chunks && blocks, "null argument");
+    const OutputStageStats s = e->e->output_stats();
+    *chunks = s.loud_chunks; *blocks = s.loud_blocks;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 int q3tts_sched_start(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->start_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_stop(q3tts_engine* e) { Q3_API_BEGIN Q3_CHECK(e, "null argument"); e->e->stop_driver(); return Q3TTS_OK; Q3_API_END(Q3TTS_ERR) }
 int q3tts_sched_step(q3tts_engine* e, int32_t* busy) {

@@ -9,6 +9,7 @@
 #include "tsm.h"
 #include "pitch.h"
 #include "volume.h"
+#include "loudness.h"
 #include <memory>
 #include "mel.h"
 
@@ -402,12 +403,13 @@ template <class T> struct GlueBuf {
 // ---- [EXT] what q3tts_op_pcm_convert, q3tts_op_tsm and q3tts_op_pitch share: every stream's guarded output (and trace) buffer goes whole into
 // its region of one device buffer -- regions start on 256 bytes (64 trace entries) -- the chunks are walked with each stream's output
 // appended behind its earlier chunks', and everything comes back whole ----
-struct GuardedStore {   // a whole guarded state store: GLUE_GUARD floats, the store, GLUE_GUARD floats
-    float* host; size_t n; DevBuf<float> dev;
-    GuardedStore(float* h, size_t core_floats) : host(h), n(core_floats + 2 * Q3TTS_GLUE_GUARD), dev(n) { dev.upload(host, n); }
-    float* core() const { return dev.p + Q3TTS_GLUE_GUARD; }
+template <class T> struct GuardedStoreOf {   // a whole guarded state store: GLUE_GUARD elements, the store, GLUE_GUARD elements
+    T* host; size_t n; DevBuf<T> dev;
+    GuardedStoreOf(T* h, size_t core_elems) : host(h), n(core_elems + 2 * Q3TTS_GLUE_GUARD), dev(n) { dev.upload(host, n); }
+    T* core() const { return dev.p + Q3TTS_GLUE_GUARD; }
     void download() { dev.download(host, n); }
 };
+typedef GuardedStoreOf<float> GuardedStore;
 struct GuardedRun {
     const int G, n_chunks; const bool flush;
     const int32_t* const chunk_samples; const int32_t* const streams; const int32_t* const reset_before;
@@ -1473,6 +1475,71 @@ int q3tts_op_volume(const float* in, int32_t G, const int32_t* chunk_samples, in
     }
     r.finish(n_out, &need, "the chunks differ from the plan");
     hist.download();
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] loudness: the host-only half (loudness.h) */
+int q3tts_loudness_tables(double* coef, double* m) {
+    Q3_API_BEGIN
+    Q3_CHECK(coef && m, "null argument");
+    LoudTables t;
+    loud_tables(&t);
+    std::copy(t.coef, t.coef + 10, coef); std::copy(t.m, t.m + 16, m);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_loudness_gate(const double* rows, int32_t n, q3tts_loudness* out) {
+    Q3_API_BEGIN
+    Q3_CHECK(out && n >= 0 && (rows || n == 0), "null argument or negative count");
+    LoudResult r;
+    loud_gate(rows, n, &r);
+    out->integrated_lufs = r.integrated_lufs; out->momentary_max_lufs = r.momentary_max_lufs; out->peak_dbfs = r.peak_dbfs;
+    out->n_blocks = r.n_blocks; out->n_gated = r.n_gated;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int32_t q3tts_loudness_gain_db10(double measured_lufs, double target_lufs) { return loud_gain_db10(measured_lufs, target_lufs); }
+
+/* [EXT] the loudness kernel over guarded host buffers (include/q3tts.h): one launch_loudness per chunk on the run's copy of the chunk, as a
+ * decode pass runs it on the output conv's buffer; each stream's rows are appended behind its earlier ones inside its guarded buffer on the
+ * device, everything downloaded whole.  The call keeps every slot's position as the decoder thread keeps a job's. */
+int q3tts_op_loudness(const float* in, int32_t G, const int32_t* chunk_samples, int32_t n_chunks, const int32_t* streams, int32_t n_streams,
+                      const int32_t* metered, const int32_t* reset_before, double* const* rows, const int64_t* rows_bytes, int64_t* n_rows,
+                      double* state_store) {
+    Q3_API_BEGIN
+    require_gpu();
+    Q3_CHECK(in && chunk_samples && streams && metered && rows && rows_bytes && n_rows && state_store, "null argument");
+    Q3_CHECK(n_chunks >= 1 && n_streams >= 1 && n_streams <= 65536, "bad chunk / stream count");
+    Q3_CHECK(G >= 1 && G <= 65536, "loudness: group size out of range");
+    // every chunk is checked as its launch will be, and every row count is worked out as the launcher will, before anything is allocated
+    const std::vector<int64_t> esz((size_t)G, 16);
+    std::vector<int64_t> need((size_t)G, 0), pos((size_t)n_streams, 0), at((size_t)G, 0), cnt((size_t)G, 0);
+    for (int c = 0; c < n_chunks; c++) {
+        const int32_t* sl = streams + (size_t)c * G;
+        if (const char* why = loudness_launch_refusal(G, G, chunk_samples[c], sl, n_streams, metered, std::vector<int64_t>((size_t)G, 0).data())) throw Error(std::string("loudness: ") + why);
+        for (int g = 0; g < G; g++) {
+            int64_t& p = pos[(size_t)sl[g]];
+            if (reset_before && reset_before[(size_t)c * G + g]) p = 0;
+            if (metered[g]) need[(size_t)g] += loud_blocks(p, chunk_samples[c]) * 16;
+            p += chunk_samples[c];
+        }
+    }
+    GuardedRun r(in, G, chunk_samples, n_chunks, false, streams, reset_before, esz, need, nullptr, reinterpret_cast<void* const*>(rows), rows_bytes, nullptr, nullptr);
+    GuardedStoreOf<double> state(state_store, (size_t)n_streams * Q3_LOUD_STATE);
+    LoudnessStage ls(n_streams, G);
+    ls.state = state.core();
+    std::fill(pos.begin(), pos.end(), 0);
+    while (r.next()) {
+        for (int g = 0; g < G; g++) {
+            if (r.reset(g)) { ls.reset_async(0, r.sl[g]); pos[(size_t)r.sl[g]] = 0; }
+            at[(size_t)g] = pos[(size_t)r.sl[g]];
+        }
+        launch_loudness(0, ls, r.x, G, r.T, r.sl, metered, at.data(), r.d_out.p, r.off.data(), cnt.data());
+        for (int g = 0; g < G; g++) { r.bytes[g] += cnt[(size_t)g] * 16; pos[(size_t)r.sl[g]] += r.T; }
+    }
+    r.finish(n_rows, &need, "the launcher's counts differ from the plan");
+    state.download();
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

@@ -12,6 +12,9 @@ struct q3tts_codec_kernel_desc;
 
 namespace q3 {
 
+// [EXT] loudness: where a metered stream of a pass stands and where its rows go.  pos = native samples the stream was given before this
+// chunk, since its reset; rows = pinned host memory for the rows {energy, peak} the chunk completes (loud_blocks(pos, T), loudness.h)
+struct LoudDst { int64_t pos = 0; double* rows = nullptr; };
 struct CodecStateEntry { std::string name; int64_t offset; int rows, cols; }; // one named tensor of a stream's state blob ([rows][cols] f32 at `offset` floats)
 
 class CodecDecoder {
@@ -52,13 +55,16 @@ public:
     // with a volume in place; then one launch of each stage that a stream of the pass belongs to (out_kind: convert, pcmout.hip; stretch,
     // tsm.hip; pitch, pitch.hip), and every stream's copy takes the n_out[g] (optional) samples its stage made -- of a stretched or shifted
     // stream those that became available, possibly none -- in 4 or 2 bytes each.  A stage's tables, state store and per-lane buffers are
-    // made by the first call that needs it; a reset and a snapshot restore zero a stream's state in all of them
+    // made by the first call that needs it; a reset and a snapshot restore zero a stream's state in all of them.
+    // [EXT] loudness: a stream with out[g].loud is metered -- in front of the volume launch one loudness launch (loudness.hip) reads the chunks
+    // of the metered streams, and the rows stream g completes are copied to loud[g].rows, which it then needs (an unmetered stream's entry is
+    // not looked at)
     int decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm_pinned, int lane = 0,
-                           const OutSpec* out = nullptr, int64_t* n_out = nullptr);
+                           const OutSpec* out = nullptr, int64_t* n_out = nullptr, const LoudDst* loud = nullptr);
     // ends a stretched or shifted utterance: the hops its last samples still owe go to dst (pinned) and *n_out is their sample count (0 for a
     // stream that was neither since its reset)
     void tsm_flush_async(hipStream_t st, int stream, void* dst, int64_t* n_out, int lane = 0);
-    OutputStageStats output_stats() const; // the counters of the four stages (read by other threads)
+    OutputStageStats output_stats() const; // the counters of the output stages and the meter (read by other threads)
     double flops_per_frame() const;
 private:
     struct Impl;

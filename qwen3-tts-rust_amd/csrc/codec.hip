@@ -14,6 +14,7 @@
 #include "tsm.h"
 #include "pitch.h"
 #include "volume.h"
+#include "loudness.h"
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -1183,6 +1184,7 @@ struct CodecDecoder::Impl {
         // [gmax] each, sized once: what deliver hands the stage launchers for the pass in flight -- the converter's formats, the stretcher's
         // percents, the shifter's rates and pitches, the encodings, the converter's counts, the stretcher's and shifter's, their byte offsets
         std::vector<q3tts_pcm_format> cf; std::vector<int32_t> pct, pr, pp, enc, vol; std::vector<int64_t> cnt, scnt, toff;
+        std::vector<int32_t> lmet; std::vector<int64_t> lpos, loff, lcnt;   // [EXT] loudness: metered, position, row offset, rows per stream
     };
     std::vector<Scratch> lanes; Scratch* S = nullptr; int ring = 256;
     // [EXT] output formats: made by the first call that converts (decode_group_async), under capture_mutex(); pcm_out[lane] = the converted
@@ -1227,7 +1229,40 @@ struct CodecDecoder::Impl {
         Q3_LAUNCH_CHECK();
         vol_chunks += volume->chunks - c0; vol_samples += volume->samples - s0;
     }
+    // [EXT] loudness: the stage and its row buffers -- loud_rows[lane] = [gmax][loud_row_cap()][2] doubles, the rows each stream of a pass
+    // completes -- are made by the first pass that holds a metered stream, under capture_mutex()
+    std::unique_ptr<LoudnessStage> loudness; std::vector<DevBuf<double>> loud_rows;
+    std::atomic<int64_t> loud_chunks{0}, loud_blocks_n{0};
+    size_t loud_row_cap() const { return pcm_lane_floats / (size_t)gmax / Q3_LOUD_BLOCK + 1; }
+    void run_loudness(hipStream_t st, int G, int T, const int32_t* streams, const OutSpec* out, const LoudDst* loud, int lane) {   // one launch over the chunk in S->pcm
+        bool any = false;
+        int32_t* const met = S->lmet.data();
+        int64_t *const pos = S->lpos.data(), *const off = S->loff.data(), *const cnt = S->lcnt.data();
+        for (int g = 0; g < G; g++) {
+            met[g] = out[g].loud != 0; any = any || met[g];
+            Q3_CHECK(!met[g] || (loud && loud[g].rows), "a metered stream needs a place for its rows");
+            pos[g] = met[g] ? loud[g].pos : 0;
+            off[g] = (int64_t)((size_t)g * loud_row_cap() * 2 * sizeof(double));
+        }
+        if (!any) return;
+        if (!loudness) {
+            std::lock_guard<std::mutex> cap(capture_mutex());
+            loud_rows.resize(lanes.size());
+            for (auto& b : loud_rows) b.alloc((size_t)gmax * loud_row_cap() * 2);
+            loudness.reset(new LoudnessStage(n_streams, gmax));
+        }
+        const int64_t c0 = loudness->chunks, b0 = loudness->blocks;
+        launch_loudness(st, *loudness, S->pcm.p, G, T, streams, met, pos, loud_rows[lane].p, off, cnt);
+        Q3_LAUNCH_CHECK();
+        loud_chunks += loudness->chunks - c0; loud_blocks_n += loudness->blocks - b0;
+        for (int g = 0; g < G; g++) {
+            if (!met[g] || cnt[g] <= 0) continue;
+            Q3_CHECK((size_t)cnt[g] <= loud_row_cap(), "a pass completed more blocks than the meter's buffer holds");
+            Q3_HIP(hipMemcpyAsync(loud[g].rows, reinterpret_cast<const unsigned char*>(loud_rows[lane].p) + off[g], (size_t)cnt[g] * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+    }
     void prosody_reset(hipStream_t st, int s) {
+        if (loudness) loudness->reset_async(st, s);
         if (tsm) tsm->reset_async(st, s);
         if (pitch) pitch->reset_async(st, s);
         if (volume) volume->reset_async(st, s);
@@ -1519,7 +1554,8 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
         L.work.resize(m.all_ext.size());
         for (Ext* e : m.all_ext) L.work[e->id].alloc((size_t)GM * (e->H + e->Tmax) * e->C);
         L.d_in.alloc(m.in_slot()); L.cf.resize((size_t)GM); L.cnt.resize((size_t)GM); L.scnt.resize((size_t)GM); L.toff.resize((size_t)GM);
-        for (auto* v : {&L.pct, &L.pr, &L.pp, &L.enc, &L.vol}) v->resize((size_t)GM);
+        for (auto* v : {&L.pct, &L.pr, &L.pp, &L.enc, &L.vol, &L.lmet}) v->resize((size_t)GM);
+        for (auto* v : {&L.lpos, &L.loff, &L.lcnt}) v->resize((size_t)GM);
         L.splitk_ws.alloc(std::max<size_t>(max_act * 2, (size_t)1 << 20));
         Q3_HIP(hipHostMalloc((void**)&L.h_in, (size_t)m.ring * m.in_slot() * sizeof(int64_t)));
     }
@@ -1543,7 +1579,7 @@ void CodecDecoder::reset(int s) {
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
     if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
-    if (m.tsm || m.pitch || m.volume) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
+    if (m.tsm || m.pitch || m.volume || m.loudness) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 OutputStageStats CodecDecoder::output_stats() const {
@@ -1554,6 +1590,7 @@ OutputStageStats CodecDecoder::output_stats() const {
     s.pitch_chunks = m.pitch_chunks.load(); s.pitch_samples = m.pitch_samples.load(); s.pitch_flushes = m.pitch_flushes.load();
     s.pitch_table_bytes = m.pitch_table_bytes.load();
     s.vol_chunks = m.vol_chunks.load(); s.vol_samples = m.vol_samples.load();
+    s.loud_chunks = m.loud_chunks.load(); s.loud_blocks = m.loud_blocks_n.load();
     return s;
 }
 
@@ -1635,7 +1672,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
     }
     flush();
     if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
-    m.prosody_reset(st, s);                 // and so are the stretcher's state, the pitch shifter's and the volume stage's
+    m.prosody_reset(st, s);                 // and so are the stretcher's state, the pitch shifter's, the volume stage's and the meter's
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1686,7 +1723,7 @@ void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* p
         m.ensure_conv();
         Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
     }
-    m.prosody_reset(st, s); // [EXT] speaking rate / pitch / volume: a primed stream's stretcher, both stages of its pitch shifter and its volume stage start from a reset
+    m.prosody_reset(st, s); // [EXT] speaking rate / pitch / volume: a primed stream's stretcher, both stages of its pitch shifter, its volume stage and its meter start from a reset
     m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
 }
 void CodecDecoder::snapshot_free(int snap) {
@@ -1710,7 +1747,7 @@ int CodecDecoder::decode_async(hipStream_t st, int s, const int64_t* codes, int 
 // One pass for G streams that each contribute n_frames new frames: every GEMM runs over G*T rows, so the 733 MB of
 // codec weights are streamed once per group instead of once per stream, and one set of launches serves the group.
 int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm, int lane,
-                                     const OutSpec* out, int64_t* n_out) {
+                                     const OutSpec* out, int64_t* n_out, const LoudDst* loud) {
     Impl& m = *impl_;
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
     Q3_CHECK(G >= 1 && G <= m.gmax, "group size out of range");
@@ -1818,6 +1855,7 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
+    if (out) m.run_loudness(st, G, T, streams, out, loud, lane);   // [EXT] loudness: reads the chunk as the output conv wrote it
     if (out) m.run_volume(st, G, T, streams, out);   // [EXT] volume: in place, in front of every stage deliver runs
     m.deliver(st, G, streams, T, pcm, lane, out, n_out);
     return T;

@@ -4,7 +4,7 @@
 
 namespace q3 {
 
-CodecWorker::CodecWorker(CodecDecoder* codec, int dev, int n_lanes, int n_cs, size_t slot_cap) : codec_(codec), dev_(dev), st_(n_lanes), slot_cap_(slot_cap) {
+CodecWorker::CodecWorker(CodecDecoder* codec, int dev, int n_lanes, int n_cs, size_t slot_cap) : codec_(codec), dev_(dev), st_(n_lanes), slot_cap_(slot_cap), n_cs_(n_cs) {
     for (auto& s : st_) Q3_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     Q3_HIP(hipHostMalloc((void**)&pcm_pinned_, (size_t)n_cs * slot_cap_ * sizeof(float)));
 }
@@ -18,6 +18,7 @@ CodecWorker::~CodecWorker() {
     for (auto& c : comp_) (void)hipEventDestroy(c.ev);
     for (auto& kv : last_) (void)hipEventDestroy(kv.second.second);
     if (pcm_pinned_) (void)hipHostFree(pcm_pinned_);
+    if (loud_pinned_.load()) (void)hipHostFree(loud_pinned_.load());
     for (auto s : st_) (void)hipStreamDestroy(s);
 }
 
@@ -51,6 +52,18 @@ unsigned char* CodecWorker::stage(const CodecJob& j, size_t add) const {
     return reinterpret_cast<unsigned char*>(pcm_pinned_ + (size_t)j.cs * slot_cap_) + at;
 }
 
+// [EXT] loudness: the thread's own; the allocation must not land inside another thread's stream capture
+double* CodecWorker::loud_stage(const CodecJob& j, size_t add) {
+    if (!loud_pinned_.load()) {
+        std::lock_guard<std::mutex> cap(capture_mutex());
+        double* p = nullptr;
+        Q3_HIP(hipHostMalloc((void**)&p, (size_t)n_cs_ * loud_cap() * 2 * sizeof(double)));
+        loud_pinned_.store(p);
+    }
+    Q3_CHECK(j.loud_enq + add <= loud_cap(), "loudness staging overflow");
+    return loud_pinned_.load() + ((size_t)j.cs * loud_cap() + j.loud_enq) * 2;
+}
+
 // A job's tasks must run in order even when consecutive steps use different lanes.  A job's task alone stays on the job's lane.
 int CodecWorker::pick_lane(const Step& s) {
     int lane = next_lane_;
@@ -81,17 +94,22 @@ void CodecWorker::decode_pass(int lane, const Step& s) {
     if (n_low < G) dec_shared += n_low;
     std::vector<int> streams(G); std::vector<float*> dst(G); std::vector<int64_t> codes((size_t)G * nf * 16);
     std::vector<OutSpec> out(G); std::vector<int64_t> n_out(G); // [EXT] what each stream is delivered as, what it was given
+    std::vector<LoudDst> loud(G); std::vector<size_t> rows(G, 0); // [EXT] loudness: where each metered stream stands, the rows this chunk completes
     for (int g = 0; g < G; g++) {
         CodecJob* j = s[g].job;
         out[g] = j->out;
         // the samples that become available with these frames: of a stretched stream possibly none, at a slow rate more than native
         const size_t add = j->bytes_due((int64_t)nf * spf, false);
+        if (j->out.loud) {
+            rows[g] = (size_t)loud_blocks(j->tsm_native, (int64_t)nf * spf);
+            loud[g].pos = j->tsm_native; loud[g].rows = loud_stage(*j, rows[g]);
+        }
         j->tsm_native += (int64_t)nf * spf;
         streams[g] = j->cs; dst[g] = reinterpret_cast<float*>(stage(*j, add));
         std::copy(s[g].codes.begin(), s[g].codes.end(), codes.begin() + (size_t)g * nf * 16);
     }
-    codec_->decode_group_async(st_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane, out.data(), n_out.data());
-    for (int g = 0; g < G; g++) s[g].job->pcm_enq += (size_t)n_out[g];
+    codec_->decode_group_async(st_[lane], G, streams.data(), codes.data(), nf, dst.data(), lane, out.data(), n_out.data(), loud.data());
+    for (int g = 0; g < G; g++) { s[g].job->pcm_enq += (size_t)n_out[g]; s[g].job->loud_enq += rows[g]; }
 }
 
 // [EXT] speaking rate: the fence of a stretching request that was not cancelled flushes its stretcher -- the hops its last samples still owe --
@@ -127,7 +145,7 @@ void CodecWorker::record(int lane, const Step& s) {
         }
         if (t.kind == TASK_RESET) continue;
         std::lock_guard<std::mutex> lk(mu_);
-        comp_.push_back(Completion{t.job, ev, t.job->pcm_enq, t.kind == TASK_FENCE});
+        comp_.push_back(Completion{t.job, ev, t.job->pcm_enq, t.kind == TASK_FENCE, t.job->loud_enq});
         if (t.kind == TASK_CHUNK) codec_calls_++;
     }
     cv_.notify_all();

@@ -2,6 +2,7 @@
 // kernel launches of a chunk never delay the AR stream's.  The scheduler gives it typed tasks and takes completions back (CodecQueue, sched_logic.h).
 #pragma once
 #include "codec.h"
+#include "loudness.h"
 #include "sched_logic.h"
 #include <atomic>
 #include <condition_variable>
@@ -12,7 +13,7 @@ namespace q3 {
 
 // A request as the decoder thread sees it.  The scheduler fills the first block before the request's first task is pushed and changes it only
 // behind the fence's completion; the second block is the thread's own from the first task to the fence, and the scheduler reads it behind a
-// completion (pcm_enq travels in the completion itself).  `cancel` alone changes while tasks are in flight.
+// completion (pcm_enq and loud_enq travel in the completion itself).  `cancel` alone changes while tasks are in flight.
 struct CodecJob {
     int64_t id = 0;          // TaskHead::req
     bool decode = false;     // [EXT] decoding given frames: its tasks wait in the low queue
@@ -23,6 +24,7 @@ struct CodecJob {
     std::atomic<bool> cancel{false}; // [EXT] set once by Engine::cancel, never cleared; looked at when the fence runs
     int64_t tsm_native = 0;  // native samples its stream has been given
     size_t pcm_enq = 0;      // delivered samples enqueued: out_delivered(out, tsm_native, .)
+    size_t loud_enq = 0;     // [EXT] loudness: rows enqueued, loud_blocks(0, tsm_native) of a metered job
     int snap = -1;           // the snapshot its fence enqueued
     size_t sample_bytes() const { return out_sample_bytes(out); }
     bool stretched() const { return out_kind(out) >= OUT_RATED; }
@@ -34,7 +36,7 @@ struct CodecJob {
 
 class CodecWorker {
 public:
-    struct Completion { CodecJob* job; hipEvent_t ev; size_t pcm_after; bool fence; };
+    struct Completion { CodecJob* job; hipEvent_t ev; size_t pcm_after; bool fence; size_t loud_after; }; // loud_after: [EXT] loudness rows reached
     // n_lanes HIP streams (consecutive passes overlap with the next AR frames and with each other) and pinned staging of slot_cap native
     // floats for each of n_cs codec streams
     CodecWorker(CodecDecoder* codec, int dev, int n_lanes, int n_cs, size_t slot_cap);
@@ -65,6 +67,10 @@ public:
     size_t slot_bytes() const { return slot_cap_ * sizeof(float); }
     const float* staging(int cs) const { return pcm_pinned_ + (size_t)cs * slot_cap_; }
     unsigned char* stage(const CodecJob& j, size_t add) const; // where the next `add` bytes of j land; throws "pcm staging overflow"
+    // [EXT] loudness: a stream's rows {energy, peak}, loud_cap() of them, beside the PCM staging; pinned by the first pass that holds a
+    // metered job, nullptr until then.  Read by the scheduler behind a completion with loud_after > 0
+    size_t loud_cap() const { return slot_cap_ / Q3_LOUD_BLOCK + 1; }
+    const double* loud_staging(int cs) const { return loud_pinned_.load() + (size_t)cs * loud_cap() * 2; }
 
     // decode-only chunks decoded, and of those the ones that shared a pass with a generating request's chunk; preamble restores
     std::atomic<int64_t> dec_chunks{0}, dec_shared{0}, pre_restores{0};
@@ -86,6 +92,8 @@ private:
     CodecDecoder* codec_; int dev_;
     std::vector<hipStream_t> st_;
     float* pcm_pinned_ = nullptr; size_t slot_cap_ = 0;
+    std::atomic<double*> loud_pinned_{nullptr}; int n_cs_ = 0;
+    double* loud_stage(const CodecJob& j, size_t add); // where the next `add` rows of j land; throws "loudness staging overflow"
     std::thread thread_; bool started_ = false, stop_ = false;
     std::mutex mu_; std::condition_variable cv_; // mu_: q_, comp_, err_, stop_
     CodecQueue<CodecJob> q_; std::deque<Completion> comp_; std::string err_;

@@ -222,6 +222,7 @@ struct Engine::Req {
     bool offline() const { return score || build_stem >= 0; } // takes a slot for one wave and never goes live
     std::vector<float> lp; // [EXT] log-probabilities [fed][17] of a recording request (r.logprobs); grows with codes under mu_
     size_t pcm_ready = 0; // samples whose decode has completed (harvested events)
+    size_t loud_ready = 0; std::vector<double> loud; // [EXT] loudness: rows whose chunk has completed; the rows [loud_ready][2] once the request has ended
     std::unique_ptr<Chunker> chunker;
     uint64_t seed = 0;
     hipEvent_t ev_admit = nullptr; bool first_seen = false;
@@ -647,7 +648,7 @@ void Engine::harvest(bool block) {
         if (!worker_ || !worker_->poll_completion(block, &c)) return;
         std::lock_guard<std::mutex> lk(mu_);
         Req* r = &req(c.job->id);
-        r->pcm_ready = c.pcm_after;
+        r->pcm_ready = c.pcm_after; r->loud_ready = c.loud_after;
         if (!r->first_seen && c.pcm_after > 0) {
             float ms = 0;
             Q3_HIP(hipEventElapsedTime(&ms, r->ev_admit, c.ev));
@@ -658,6 +659,7 @@ void Engine::harvest(bool block) {
         if (c.fence) {
             r->pcm_n = (int64_t)c.pcm_after; // the bytes as they are: whole floats for f32, (n + 1) / 2 of them for s16
             r->pcm.assign(worker_->staging(r->job.cs), worker_->staging(r->job.cs) + (c.pcm_after * r->job.sample_bytes() + 3) / 4);
+            if (c.loud_after > 0) r->loud.assign(worker_->loud_staging(r->job.cs), worker_->loud_staging(r->job.cs) + c.loud_after * 2); // [EXT] loudness
             cs_free_.push_back(r->job.cs);
             r->job.cs = -1;
             r->state = fenced_state(r->job.cancel); r->t_done = now_ms();
@@ -1499,6 +1501,32 @@ void Engine::set_volume(int db10) {
 int Engine::request_volume(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
     return req(id).job.out.vol_db10;
+}
+
+// [EXT] loudness (q3tts_spec.h "loudness")
+void Engine::set_loudness(bool on) {
+    if (const char* why = loudness_submit_refusal(codec_ != nullptr)) throw Error(why);
+    std::lock_guard<std::mutex> lk(out_mu_);
+    out_.loud = on ? 1 : 0;
+}
+bool Engine::request_metered(int64_t id) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return req(id).job.out.loud != 0;
+}
+void Engine::fetch_loudness(int64_t id, double* out, int64_t block_off, int64_t max_blocks, int64_t* got) {
+    std::lock_guard<std::mutex> lk(mu_);
+    const Req& r = req(id);
+    Q3_CHECK(r.job.out.loud != 0, "the request is not metered");
+    Q3_CHECK(out && block_off >= 0, "null buffer or negative offset");
+    const bool done = r.state == REQ_DONE || r.state == REQ_CANCELLED;
+    const double* src = done ? r.loud.data() : (r.job.cs >= 0 && r.loud_ready > 0 ? worker_->loud_staging(r.job.cs) : nullptr);
+    const int64_t avail = done ? (int64_t)(r.loud.size() / 2) : (int64_t)r.loud_ready;
+    int64_t n = 0;
+    if (src && block_off < avail && max_blocks > 0) {
+        n = std::min(max_blocks, avail - block_off);
+        std::memcpy(out, src + (size_t)block_off * 2, (size_t)n * 2 * sizeof(double));
+    }
+    if (got) *got = n;
 }
 
 // [EXT] codec preambles and prompt stems (q3tts_spec.h "codec preambles" / "prompt stems"): the held objects.  Who holds what is counted by

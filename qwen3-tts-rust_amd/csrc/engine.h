@@ -133,6 +133,13 @@ public:
     // Thread-safe, no HIP calls; throws volume_submit_refusal's reason for a volume outside [-400, 200] or an engine without a codec
     void set_volume(int db10);
     int request_volume(int64_t id);
+    // [EXT] loudness (q3tts_spec.h "loudness"): requests submitted from now on with want_pcm are metered -- the K-weighted energy and the
+    // sample peak of every 100 ms block of their native stream, whatever they are delivered as; read with the other output settings, wherever
+    // those are read.  Thread-safe, no HIP calls; throws on an engine without a codec.  fetch_loudness: rows [block_off, block_off + max_blocks)
+    // that are available now ({energy, peak}, two doubles each; they grow with poll()'s n_pcm); throws for a request that is not metered
+    void set_loudness(bool on);
+    bool request_metered(int64_t id);
+    void fetch_loudness(int64_t id, double* out, int64_t block_off, int64_t max_blocks, int64_t* got);
     // [EXT] codec preambles (q3tts_spec.h "codec preambles"): a codec stream state to start requests from, built once from codes [n][16] like a
     // decode-only request (decode_q_, a codec stream, reset / chunks / fence through the decoder thread, which enqueues the snapshot at the
     // fence) and kept on the device.  create: thread-safe, no HIP calls; throws preamble_refusal's reason before anything is queued.  The

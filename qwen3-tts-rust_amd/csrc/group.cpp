@@ -430,6 +430,13 @@ int q3tts_group_set_volume(q3tts_group* g, int32_t db10) { // [EXT] q3tts_engine
     if (g && std::isnan(q3tts_volume_gain(db10))) { set_last_error("volume out of range [-400, 200]"); return Q3TTS_ERR; }
     return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_volume(e, db10); });
 }
+// [EXT] loudness: the meter on every engine, and a request's rows and summary from the engine that runs it
+int q3tts_group_set_loudness(q3tts_group* g, int32_t on) { return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_loudness(e, on); }); }
+int q3tts_group_fetch_loudness(q3tts_group* g, int64_t req_id, double* out, int64_t block_off, int64_t max_blocks, int64_t* got) {
+    return routed(g, req_id, q3tts_fetch_loudness, out, block_off, max_blocks, got);
+}
+int q3tts_group_request_loudness(q3tts_group* g, int64_t req_id, q3tts_loudness* out) { return routed(g, req_id, q3tts_request_loudness, out); }
+int q3tts_group_request_metered(q3tts_group* g, int64_t req_id, int32_t* on) { return routed(g, req_id, q3tts_request_metered, on); }
 int q3tts_group_set_speech_rate(q3tts_group* g, int32_t rate_pct) {
     if (g && q3tts_tsm_samples(rate_pct, 0, 0) < 0) { set_last_error("speech rate out of range [50, 200]"); return Q3TTS_ERR; }
     return on_every(g, ALL_OR_STOP, [&](q3tts_engine* e) { return q3tts_engine_set_speech_rate(e, rate_pct); });

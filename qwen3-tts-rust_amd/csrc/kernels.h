@@ -484,4 +484,32 @@ struct VolumeStage {
 void launch_volume(hipStream_t st, VolumeStage& s, float* pcm, int G, int T, const int32_t* streams, const int32_t* db10, float* trace = nullptr,
                    const int64_t* trace_off = nullptr);
 
+// [EXT] loudness (loudness.hip, q3tts_spec.h "loudness"): the K-weighted 100 ms block energies and peaks of the native chunk, in front of the
+// volume stage; it reads the chunk and never writes it.  One entry per stream of a launch, written by launch_loudness into the upload ring.
+struct LoudStreamMeta {
+    int32_t slot;             // state store entry; -1: the stream is not metered, its workgroup exits at once
+    int32_t pad;
+    int64_t pos;              // native samples the stream was given before this chunk, since its reset
+    int64_t out_off;          // first output byte, from the launch's `out`
+};
+// The stage's device state: the store [n_streams][Q3_LOUD_STATE] doubles (filter state, running energy and peak), the tables (loudness.h,
+// built once on the host) and an upload ring as the other stages'.  No counters: the host passes every stream's position.  One owner thread.
+struct LoudnessStage {
+    LoudnessStage(int n_streams, int max_group);
+    LoudnessStage(const LoudnessStage&) = delete; LoudnessStage& operator=(const LoudnessStage&) = delete;
+    void reset_async(hipStream_t st, int slot);    // zeroes the slot's state: its next sample is sample 0 of a stream
+    int n_streams, max_group;
+    double* state;                                 // = state_own.p, or a caller's store of the same shape (the test entry point's guarded one)
+    DevBuf<double> state_own; UploadRing<LoudStreamMeta> ring;
+    double coef[10], m[16];
+    int64_t chunks = 0, blocks = 0;
+};
+// pcm [G][T] native samples (T a multiple of 1920), read only.  Stream g of state slot streams[g], metered where metered[g] != 0 and then at
+// stream position pos[g] (a multiple of 1920): the rows {energy, peak} of the blocks the chunk completes go to out + out_off[g] bytes
+// (8-byte aligned), 16 bytes each, and n_out[g] receives their count, floor((pos + T) / 2400) - floor(pos / 2400); an unmetered stream has
+// n_out[g] = 0 and nothing of it is read or written.  Nothing runs when no stream is metered.
+// Refused (loudness_launch_refusal, loudness.h) before anything is uploaded or launched.
+void launch_loudness(hipStream_t st, LoudnessStage& s, const float* pcm, int G, int T, const int32_t* streams, const int32_t* metered,
+                     const int64_t* pos, void* out, const int64_t* out_off, int64_t* n_out);
+
 } // namespace q3

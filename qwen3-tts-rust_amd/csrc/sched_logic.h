@@ -671,9 +671,10 @@ inline const char* volume_submit_refusal(int db10, bool have_codec) {
 // [EXT] the output settings of one stream (q3tts_spec.h "output formats" / "speaking rate" / "pitch" / "volume") as one record: what the
 // engine's setters write, what a request reads once at submit and what the codec's pass tail is given per stream.  The default is the plain
 // stream: native format, no rate, no pitch, no volume.  A setting more is a field here and a branch where the pass tail delivers.
-struct OutSpec { q3tts_pcm_format fmt{Q3_PCM_NATIVE_RATE, Q3_PCM_F32}; int32_t rate_pct = 100, pitch_pct = 100, vol_db10 = 0; };
+// loud: [EXT] loudness (q3tts_spec.h "loudness"): nonzero = the stream is metered; it changes no sample and no count
+struct OutSpec { q3tts_pcm_format fmt{Q3_PCM_NATIVE_RATE, Q3_PCM_F32}; int32_t rate_pct = 100, pitch_pct = 100, vol_db10 = 0; int32_t loud = 0; };
 // whose stream it is behind the output conv: nobody's, the converter's, the stretcher's, the shifter's (a pitch wins over a rate, a rate over a
-// format).  The volume is no kind: it rewrites the native chunk in front of any of them
+// format).  The volume is no kind: it rewrites the native chunk in front of any of them; nor is the meter, which reads it in front of the volume
 enum OutKind : uint8_t { OUT_NATIVE, OUT_CONVERTED, OUT_RATED, OUT_PITCHED };
 inline OutKind out_kind(const OutSpec& o) {
     return o.pitch_pct != 100 ? OUT_PITCHED : o.rate_pct != 100 ? OUT_RATED : !pcm_format_native(o.fmt) ? OUT_CONVERTED : OUT_NATIVE;
@@ -692,6 +693,7 @@ inline int64_t out_delivered(const OutSpec& o, int64_t n_native, bool final) {
 // the submit rule of a request with these settings: the volume's, then the pitch's (which judges the pair and the format), else the rate's.
 // nullptr = it may be queued
 inline const char* out_submit_refusal(const OutSpec& o, int max_steps, int64_t cap_bytes, bool have_codec) {
+    if (o.loud != 0 && !have_codec) return "the engine has no codec";   // loudness_submit_refusal (loudness.h)
     if (o.vol_db10 != 0) if (const char* why = volume_submit_refusal(o.vol_db10, have_codec)) return why;
     if (o.pitch_pct != 100) return pitch_submit_refusal(o.rate_pct, o.pitch_pct, o.fmt, max_steps, cap_bytes, have_codec);
     if (o.rate_pct != 100) return tsm_submit_refusal(o.rate_pct, o.fmt, max_steps, cap_bytes, have_codec);
@@ -699,10 +701,11 @@ inline const char* out_submit_refusal(const OutSpec& o, int max_steps, int64_t c
 }
 // [EXT] the counters of the codec's output stages, as one snapshot: stream chunks the converter took and samples it made; stream chunks the
 // stretcher took, synthesis frames it made, its flushes; stream chunks shifted, samples delivered, flushes, bytes of tap tables on the device;
-// stream chunks the volume stage took and samples it rewrote
+// stream chunks the volume stage took and samples it rewrote; stream chunks the loudness meter took and blocks it completed
 struct OutputStageStats {
     int64_t conv_chunks = 0, conv_samples = 0, tsm_chunks = 0, tsm_frames = 0, tsm_flushes = 0;
     int64_t pitch_chunks = 0, pitch_samples = 0, pitch_flushes = 0, pitch_table_bytes = 0, vol_chunks = 0, vol_samples = 0;
+    int64_t loud_chunks = 0, loud_blocks = 0;
 };
 
 } // namespace q3

@@ -115,10 +115,18 @@ SYMBOLS = [
     "q3tts_pitch_samples", "q3tts_pitch_plan", "q3tts_pitch_filter", "q3tts_op_pitch",
     "q3tts_engine_set_volume", "q3tts_request_volume", "q3tts_engine_volume_stats", "q3tts_group_set_volume", "q3tts_group_request_volume",
     "q3tts_volume_gain", "q3tts_op_volume",
+    "q3tts_engine_set_loudness", "q3tts_fetch_loudness", "q3tts_request_loudness", "q3tts_request_metered", "q3tts_engine_loudness_stats",
+    "q3tts_group_set_loudness", "q3tts_group_fetch_loudness", "q3tts_group_request_loudness", "q3tts_group_request_metered",
+    "q3tts_loudness_tables", "q3tts_loudness_gate", "q3tts_loudness_gain_db10", "q3tts_op_loudness",
 ]
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
     _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32)]
+
+
+class Loudness(C.Structure):  # q3tts_loudness
+    _fields_ = [("integrated_lufs", C.c_double), ("momentary_max_lufs", C.c_double), ("peak_dbfs", C.c_double), ("n_blocks", C.c_int32),
+                ("n_gated", C.c_int32)]
 
 
 class StemStats(C.Structure):  # q3tts_stem_stats
@@ -132,6 +140,7 @@ PCM_NATIVE_RATE, PCM_FRAME, PCM_HIST = 24000, 1920, 96
 TSM_HOP, TSM_WIN, TSM_SEARCH, TSM_LOOK, TSM_HIST, TSM_MIN, TSM_MAX = 480, 960, 240, 1200, 1920, 50, 200   # q3tts_spec.h "speaking rate"
 PITCH_MIN, PITCH_MAX, PITCH_HIST = 50, 200, 64                           # q3tts_spec.h "pitch"
 VOL_MIN, VOL_MAX, VOL_LOOK, VOL_HOLD, VOL_DELAY, VOL_HIST = -400, 200, 128, 512, 127, 638   # q3tts_spec.h "volume"
+LOUD_SEG, LOUD_BLOCK, LOUD_STATE = 96, 2400, 6                           # q3tts_spec.h "loudness"
 MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
 PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
 MAX_STEMS = 64                                                           # Q3TTS_MAX_STEMS (q3tts_spec.h "prompt stems")
@@ -346,6 +355,21 @@ def lib():
         L.q3tts_volume_gain.restype = C.c_float
         L.q3tts_op_volume.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.q3tts_engine_set_loudness.argtypes = [C.c_void_p, C.c_int32]
+        L.q3tts_fetch_loudness.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.q3tts_request_loudness.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Loudness)]
+        L.q3tts_request_metered.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.q3tts_engine_loudness_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 2
+        L.q3tts_group_set_loudness.argtypes = L.q3tts_engine_set_loudness.argtypes
+        L.q3tts_group_fetch_loudness.argtypes = L.q3tts_fetch_loudness.argtypes
+        L.q3tts_group_request_loudness.argtypes = L.q3tts_request_loudness.argtypes
+        L.q3tts_group_request_metered.argtypes = L.q3tts_request_metered.argtypes
+        L.q3tts_loudness_tables.argtypes = [C.c_void_p, C.c_void_p]
+        L.q3tts_loudness_gate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Loudness)]
+        L.q3tts_loudness_gain_db10.argtypes = [C.c_double, C.c_double]
+        L.q3tts_loudness_gain_db10.restype = C.c_int32
+        L.q3tts_op_loudness.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
         L.q3tts_pitch_samples.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
         L.q3tts_pitch_samples.restype = C.c_int64
         L.q3tts_pitch_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
@@ -663,6 +687,45 @@ def group_set_volume(group, db10=0):
 def group_request_volume(group, rid):
     """[EXT] q3tts_group_request_volume: the volume of a group request id in tenths of a dB"""
     return _request_speech_rate(lib().q3tts_group_request_volume, group, rid)
+
+
+def _loudness_dict(o):
+    return dict(integrated_lufs=o.integrated_lufs, momentary_max_lufs=o.momentary_max_lufs, peak_dbfs=o.peak_dbfs, n_blocks=o.n_blocks,
+                n_gated=o.n_gated)
+
+
+def _fetch_loudness(fn, h, rid, off=0, cap=None):
+    """rows [got][2] float64 = {energy, peak} of the 100 ms blocks [off, off + cap) of a metered request that are available now"""
+    cap = 1 << 14 if cap is None else int(cap)
+    out, got = np.zeros((max(cap, 1), 2), np.float64), C.c_int64(-1)
+    _chk(fn(h, rid, _p(out), int(off), cap, C.byref(got)))
+    return out[: got.value].copy()
+
+
+def _request_loudness(fn, h, rid):
+    o = Loudness()
+    _chk(fn(h, rid, C.byref(o)))
+    return _loudness_dict(o)
+
+
+def group_set_loudness(group, on=True):
+    """[EXT] q3tts_group_set_loudness on a q3tts_group handle: every engine of the group"""
+    _chk(lib().q3tts_group_set_loudness(group, 1 if on else 0))
+
+
+def group_fetch_loudness(group, rid, off=0, cap=None):
+    """[EXT] q3tts_group_fetch_loudness: the rows of a group request id"""
+    return _fetch_loudness(lib().q3tts_group_fetch_loudness, group, rid, off, cap)
+
+
+def group_request_loudness(group, rid):
+    """[EXT] q3tts_group_request_loudness: the gate over the rows of a group request id so far"""
+    return _request_loudness(lib().q3tts_group_request_loudness, group, rid)
+
+
+def group_request_metered(group, rid):
+    """[EXT] q3tts_group_request_metered: whether a group request id is metered"""
+    return bool(_request_speech_rate(lib().q3tts_group_request_metered, group, rid))
 
 
 def _preamble_create(fn, h, codes):
@@ -1172,6 +1235,30 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         a, b = C.c_int64(), C.c_int64()
         _chk(lib().q3tts_engine_volume_stats(self.h, C.byref(a), C.byref(b)))
         return dict(chunks=a.value, samples=b.value)
+
+    def set_loudness(self, on=True):
+        """[EXT] loudness (q3tts_engine_set_loudness): requests submitted from now on with want_pcm are metered: the K-weighted energy and
+        the sample peak of every 100 ms block of their native stream, whatever format, rate, pitch or volume they are delivered with"""
+        _chk(lib().q3tts_engine_set_loudness(self.h, 1 if on else 0))
+
+    def request_metered(self, rid):
+        """[EXT] whether the request was submitted metered"""
+        return bool(_request_speech_rate(lib().q3tts_request_metered, self.h, rid))
+
+    def fetch_loudness(self, rid, off=0, cap=None):
+        """[EXT] q3tts_fetch_loudness: rows [got][2] float64 = {energy, peak} of the blocks [off, off + cap) available now; they grow with
+        poll()'s n_pcm, and n frames give (4 * n) // 5 at the end.  Raises Q3Error for a request that is not metered"""
+        return _fetch_loudness(lib().q3tts_fetch_loudness, self.h, rid, off, cap)
+
+    def request_loudness(self, rid):
+        """[EXT] q3tts_request_loudness: loudness_gate over the request's rows so far"""
+        return _request_loudness(lib().q3tts_request_loudness, self.h, rid)
+
+    def loudness_stats(self):
+        """[EXT] q3tts_engine_loudness_stats: dict(chunks, blocks)"""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(lib().q3tts_engine_loudness_stats(self.h, C.byref(a), C.byref(b)))
+        return dict(chunks=a.value, blocks=b.value)
 
     def wait(self, rid, timeout_ms=-1.0):
         rc = lib().q3tts_wait(self.h, rid, timeout_ms)
@@ -2412,6 +2499,57 @@ def op_volume(x, chunk_samples, streams, n_streams, volumes, reset_before=None, 
     outs = [w.view(np.float32)[GLUE_GUARD: GLUE_GUARD + n].copy() for w in wholes]
     traces = [t.view(np.float32)[GLUE_GUARD: GLUE_GUARD + n].copy() for t in twholes]
     return outs, traces, wholes, twholes, n_out, hist
+
+
+# ---- loudness: the host-only half and the loudness kernel (q3tts_op_loudness) ----
+def loudness_tables():
+    """(coef [10], m [4][4]) float64: the two K-weighting stages at 24000 Hz (b0 b1 b2 a1 a2 each) and A^LOUD_SEG"""
+    coef, m = np.zeros(10, np.float64), np.zeros((4, 4), np.float64)
+    _chk(lib().q3tts_loudness_tables(_p(coef), _p(m)))
+    return coef, m
+
+
+def loudness_gate(rows):
+    """the BS.1770 gate over rows [n][2] = {energy, peak}: dict(integrated_lufs, momentary_max_lufs, peak_dbfs, n_blocks, n_gated)"""
+    r = np.ascontiguousarray(rows, np.float64).reshape(-1, 2)
+    o = Loudness()
+    _chk(lib().q3tts_loudness_gate(_p(r if r.size else np.zeros((1, 2), np.float64)), r.shape[0], C.byref(o)))
+    return _loudness_dict(o)
+
+
+def loudness_gain_db10(measured_lufs, target_lufs):
+    """the volume in tenths of a dB that takes measured_lufs to target_lufs, rounded and clamped to [VOL_MIN, VOL_MAX]; 0 for a non-finite input"""
+    return int(lib().q3tts_loudness_gain_db10(float(measured_lufs), float(target_lufs)))
+
+
+def op_loudness(x, chunk_samples, streams, n_streams, metered, reset_before=None, state=None, slack=0, fill=0x5A):
+    """the loudness kernel over host buffers, one launch of the engine's launcher per chunk.  x [G][sum(chunk_samples)] f32: the native signal
+    of each position; streams [n_chunks][G] state slots; metered [G].  state: a whole guarded store (GLUE_GUARD doubles, [n_streams][LOUD_STATE],
+    GLUE_GUARD doubles) or None for a zero store between guards of -3e300.  Every row buffer is made exactly as large as the result plus `slack`
+    rows, every byte `fill`.  Returns (rows, wholes, n_rows, state): the rows [n][2] per position, the whole buffers as they came back, the
+    counts the call reported, the whole store.  A refused call raises Q3Error carrying wholes / n_out / state as they are then."""
+    G, cs, sl, rb, flat = _stage_inputs(x, chunk_samples, streams, reset_before)
+    me = np.ascontiguousarray(metered, np.int32)
+    pos, want = {}, [0] * len(me)   # the plan, as the call works it out: a position per slot, starting over at a reset
+    for c in range(cs.size):
+        T = max(int(cs[c]), 0)
+        for g in range(len(me)):
+            s = int(sl[c, g]) if sl.size else 0
+            if rb is not None and rb[c, g]:
+                pos[s] = 0
+            if me[g]:
+                want[g] += (pos.get(s, 0) + T) // LOUD_BLOCK - pos.get(s, 0) // LOUD_BLOCK
+            pos[s] = pos.get(s, 0) + T
+    wholes = [np.full((n + slack + 2 * GLUE_GUARD) * 16, fill, np.uint8) for n in want]
+    if state is None:
+        state = np.zeros(n_streams * LOUD_STATE + 2 * GLUE_GUARD, np.float64)
+        state[:GLUE_GUARD] = state[-GLUE_GUARD:] = -3e300
+    assert state.dtype == np.float64 and state.size == n_streams * LOUD_STATE + 2 * GLUE_GUARD and state.flags["C_CONTIGUOUS"]
+    (ptrs, nbytes), n_out = _stage_bufs(wholes), np.full(max(len(wholes), 1), -1, np.int64)
+    n_out = _stage_call(lib().q3tts_op_loudness, _p(flat), G, _p(cs), cs.size, _pz(sl), n_streams, _pz(me), _p(rb), ptrs, _p(nbytes), _p(n_out),
+                        _p(state), n_out=n_out[: len(wholes)], wholes=wholes, state=state)
+    rows = [w.view(np.float64).reshape(-1, 2)[GLUE_GUARD: GLUE_GUARD + n].copy() for w, n in zip(wholes, want)]
+    return rows, wholes, n_out, state
 
 
 # ---- pitch: the host-only half and the pitch kernel (q3tts_op_pitch) ----
