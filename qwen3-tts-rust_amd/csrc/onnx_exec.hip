@@ -2,14 +2,16 @@
 // convolutions), then the interpreter.  Operator semantics follow the public ONNX operator specification [EXT]; every operator is
 // checked against numpy in tests/test_gpu_onnx_exec.py.
 #include "onnx_exec.h"
+#include "onnx_shape.h"
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
-#include <functional>
 #include <limits>
 #include <set>
 
 namespace q3 {
+using namespace xs; // the operator codes (UOp / BOp / ROp), apply_binary_d and every host-only rule: onnx_shape.h
 
 // =============================================================== kernels ===============================================================
 constexpr int XR = 8; // maximum rank
@@ -25,8 +27,6 @@ template <typename T> __global__ void k_nd_copy(T* __restrict__ out, const T* __
     if (i < n) out[i] = in[nd_off(m, i)];
 }
 
-enum UOp { U_RELU, U_SIGMOID, U_TANH, U_EXP, U_LOG, U_SQRT, U_RECIP, U_NEG, U_ABS, U_SIN, U_COS, U_ERF, U_FLOOR, U_CEIL, U_ROUND, U_SIGN, U_ELU,
-           U_LEAKY, U_HSIG, U_GELU, U_GELU_TANH, U_SOFTPLUS, U_SELU, U_NOT, U_CLIP, U_IDENT, U_SOFTSIGN, U_HSWISH, U_ISNAN, U_CELU, U_THRELU, U_MISH, U_TAN, U_ATAN, U_SINH, U_COSH, U_LOG1P_EXP_NEG };
 __device__ __forceinline__ float apply_unary(int op, float x, float a, float b) {
     switch (op) {
         case U_RELU: return x > 0.f ? x : 0.f;
@@ -72,31 +72,6 @@ __global__ void k_unary(float* __restrict__ out, const float* __restrict__ in, i
     if (i < n) out[i] = apply_unary(op, in[i], a, b);
 }
 
-enum BOp { B_ADD, B_SUB, B_MUL, B_DIV, B_POW, B_MIN, B_MAX, B_EQ, B_LT, B_GT, B_LE, B_GE, B_AND, B_OR, B_XOR, B_MOD, B_FMOD, B_PRELU, B_IDIV };
-__host__ __device__ __forceinline__ double apply_binary_d(int op, double x, double y) {
-    switch (op) {
-        case B_ADD: return x + y;
-        case B_SUB: return x - y;
-        case B_MUL: return x * y;
-        case B_DIV: return x / y;
-        case B_IDIV: return y != 0 ? (double)(long long)(x / y) : 0.0; // integer division truncates towards zero
-        case B_POW: return pow(x, y);
-        case B_MIN: return x < y ? x : y;
-        case B_MAX: return x > y ? x : y;
-        case B_EQ: return x == y ? 1.0 : 0.0;
-        case B_LT: return x < y ? 1.0 : 0.0;
-        case B_GT: return x > y ? 1.0 : 0.0;
-        case B_LE: return x <= y ? 1.0 : 0.0;
-        case B_GE: return x >= y ? 1.0 : 0.0;
-        case B_AND: return (x != 0 && y != 0) ? 1.0 : 0.0;
-        case B_OR: return (x != 0 || y != 0) ? 1.0 : 0.0;
-        case B_XOR: return ((x != 0) != (y != 0)) ? 1.0 : 0.0;
-        case B_MOD: { if (y == 0) return 0.0; double r = fmod(x, y); if (r != 0 && ((r < 0) != (y < 0))) r += y; return r; } // sign of the divisor (fmod = 0)
-        case B_FMOD: return fmod(x, y);
-        case B_PRELU: return x > 0 ? x : x * y;
-        default: return x;
-    }
-}
 __device__ __forceinline__ float apply_binary(int op, float x, float y) {
     switch (op) {
         case B_ADD: return x + y;
@@ -159,7 +134,6 @@ template <typename T> __global__ void k_gather(T* __restrict__ out, const T* __r
     out[i] = data[(o * axis_dim + k) * inner + in_];
 }
 
-enum ROp { R_SUM, R_MEAN, R_MAX, R_MIN, R_PROD, R_L2, R_SUMSQ, R_L1, R_LOGSUMEXP, R_ARGMAX, R_ARGMIN };
 // one workgroup per row; fixed-shape tree, so results do not depend on scheduling
 __global__ void __launch_bounds__(256) k_reduce_rows(float* __restrict__ out, int64_t* __restrict__ out_idx, const float* __restrict__ in, int op, int64_t cols, int select_last) {
     __shared__ float sv[256];
@@ -516,61 +490,30 @@ __global__ void k_pad(float* __restrict__ out, const float* __restrict__ in, Pad
 }
 
 // ============================================================= interpreter =============================================================
+// One handler per operator (op_* below), one table of them (op_table: the supported set), and a run() that walks the nodes.  The host-only rules
+// the handlers share -- checked axes, shape rules, Slice / convolution geometry, the evaluators of host tensors -- are in onnx_shape.h.
 static dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-static std::vector<int64_t> strides_of(const std::vector<int64_t>& s) { std::vector<int64_t> st(s.size(), 1); for (int d = (int)s.size() - 2; d >= 0; d--) st[d] = st[d + 1] * s[d + 1]; return st; }
-static int64_t prod(const std::vector<int64_t>& s, size_t a = 0, size_t b = (size_t)-1) { int64_t n = 1; for (size_t i = a; i < std::min(b, s.size()); i++) n *= s[i]; return n; }
-static std::vector<int64_t> bshape(const std::vector<int64_t>& a, const std::vector<int64_t>& b) {
-    const size_t r = std::max(a.size(), b.size());
-    std::vector<int64_t> o(r);
-    for (size_t i = 0; i < r; i++) {
-        const int64_t x = i + a.size() >= r ? a[i + a.size() - r] : 1, y = i + b.size() >= r ? b[i + b.size() - r] : 1;
-        if (x != y && x != 1 && y != 1) throw Error("shapes do not broadcast");
-        o[i] = x == 1 ? y : x;
-    }
-    return o;
-}
-static std::vector<int64_t> bstrides(const std::vector<int64_t>& in, const std::vector<int64_t>& out) { // strides of `in` seen through `out` (0 on broadcast dims)
-    std::vector<int64_t> st = strides_of(in), o(out.size(), 0);
-    for (size_t i = 0; i < in.size(); i++) { const size_t d = out.size() - in.size() + i; o[d] = in[i] == 1 ? 0 : st[i]; }
-    return o;
-}
+static dim3 grid_rows(int64_t rows, int64_t cols = 1) { return dim3((unsigned)(rows && cols ? rows : 0)); } // one workgroup per row; empty when there is nothing to do
+template <typename T> struct arg_of { using type = T; }; // keeps a kernel's parameter types out of deduction: arguments convert as in a direct call
 
-static const std::map<std::string, int>& unary_table() {
-    static const std::map<std::string, int> t = {{"Relu", U_RELU}, {"Sigmoid", U_SIGMOID}, {"Tanh", U_TANH}, {"Exp", U_EXP}, {"Log", U_LOG}, {"Sqrt", U_SQRT},
-        {"Reciprocal", U_RECIP}, {"Neg", U_NEG}, {"Abs", U_ABS}, {"Sin", U_SIN}, {"Cos", U_COS}, {"Erf", U_ERF}, {"Floor", U_FLOOR}, {"Ceil", U_CEIL},
-        {"Round", U_ROUND}, {"Sign", U_SIGN}, {"Elu", U_ELU}, {"LeakyRelu", U_LEAKY}, {"HardSigmoid", U_HSIG}, {"Gelu", U_GELU}, {"Softplus", U_SOFTPLUS},
-        {"Selu", U_SELU}, {"Not", U_NOT}, {"Softsign", U_SOFTSIGN}, {"HardSwish", U_HSWISH}, {"IsNaN", U_ISNAN}, {"Celu", U_CELU}, {"ThresholdedRelu", U_THRELU},
-        {"Mish", U_MISH}, {"Tan", U_TAN}, {"Atan", U_ATAN}, {"Sinh", U_SINH}, {"Cosh", U_COSH}};
-    return t;
-}
-static const std::map<std::string, int>& binary_table() {
-    static const std::map<std::string, int> t = {{"Add", B_ADD}, {"Sub", B_SUB}, {"Mul", B_MUL}, {"Div", B_DIV}, {"Pow", B_POW}, {"Min", B_MIN}, {"Max", B_MAX},
-        {"Equal", B_EQ}, {"Less", B_LT}, {"Greater", B_GT}, {"LessOrEqual", B_LE}, {"GreaterOrEqual", B_GE}, {"And", B_AND}, {"Or", B_OR}, {"Xor", B_XOR},
-        {"Mod", B_MOD}, {"PRelu", B_PRELU}, {"Sum", B_ADD}, {"Mean", B_ADD}};
-    return t;
-}
-static const std::map<std::string, int>& reduce_table() {
-    static const std::map<std::string, int> t = {{"ReduceSum", R_SUM}, {"ReduceMean", R_MEAN}, {"ReduceMax", R_MAX}, {"ReduceMin", R_MIN}, {"ReduceProd", R_PROD},
-        {"ReduceL2", R_L2}, {"ReduceSumSquare", R_SUMSQ}, {"ReduceL1", R_L1}, {"ReduceLogSumExp", R_LOGSUMEXP}, {"ArgMax", R_ARGMAX}, {"ArgMin", R_ARGMIN}};
-    return t;
-}
-static const std::set<std::string>& other_ops() {
-    static const std::set<std::string> t = {"Identity", "Dropout", "Reshape", "Flatten", "Squeeze", "Unsqueeze", "Transpose", "Concat", "Slice", "Split", "Gather",
-        "Shape", "Size", "Constant", "ConstantOfShape", "Range", "Cast", "Expand", "Tile", "Where", "Clip", "Softmax", "LogSoftmax", "LayerNormalization",
-        "InstanceNormalization", "BatchNormalization", "MatMul", "Gemm", "Conv", "ConvTranspose", "Pad", "CumSum", "GlobalAveragePool", "GlobalMaxPool",
-        "Trilu", "GatherElements", "ScatterND", "Resize", "GroupNormalization", "LpNormalization"};
-    return t;
-}
-bool onnx_exec_supports(const std::string& op) { return unary_table().count(op) || binary_table().count(op) || reduce_table().count(op) || other_ops().count(op); }
+struct NodeCtx;
+struct OpEntry { const char* name; void (*fn)(NodeCtx&); int arg; }; // arg: the U_* / B_* / R_* code, or the variant of a shared body
 
-struct OnnxSession::Impl {
-    std::map<std::string, XTensor> vals;     // every live edge
+struct Exec { // the executor's state and the helpers every handler is written with (OnnxSession::Impl is exactly this)
+    std::map<std::string, XTensor> vals;     // every live edge of the current run
     std::map<std::string, XTensor> consts;   // initialisers (uploaded once)
     std::map<std::string, XTensor> inputs;
     std::map<size_t, std::vector<std::shared_ptr<DevBuf<uint8_t>>>> pool; // buffers by byte size, reused between nodes / runs
+    std::vector<const OpEntry*> entry;       // per node, resolved once when the session opens (nullptr: no handler)
     int64_t opset = 17;
     long* launches = nullptr;
 
+    const XTensor* find(const std::string& name) const { // an edge of this run, or an initialiser
+        auto it = vals.find(name);
+        if (it != vals.end()) return &it->second;
+        it = consts.find(name);
+        return it != consts.end() ? &it->second : nullptr;
+    }
     std::shared_ptr<DevBuf<uint8_t>> alloc(size_t bytes) {
         bytes = std::max<size_t>((bytes + 255) & ~(size_t)255, 256);
         auto& v = pool[bytes];
@@ -578,16 +521,7 @@ struct OnnxSession::Impl {
         v.push_back(std::make_shared<DevBuf<uint8_t>>(bytes));
         return v.back();
     }
-    // every tensor is made here: a shape computed from graph data (Reshape / Expand / ConstantOfShape / Tile ... operands) with a negative
-    // dimension or an element count that overflows becomes an Error before any buffer is sized from it
-    static int64_t checked_numel(const std::vector<int64_t>& shape) {
-        int64_t n = 1;
-        for (auto d : shape) {
-            Q3_CHECK(d >= 0, "tensor shape has a negative dimension");
-            Q3_CHECK(!__builtin_mul_overflow(n, d, &n) && n <= ((int64_t)1 << 33), "tensor element count overflows / exceeds 2^33");
-        }
-        return n;
-    }
+    // every tensor is made here, so a shape computed from graph data (Reshape / Expand / ConstantOfShape / Tile ... operands) is checked before any buffer is sized from it
     XTensor dev_tensor(int dtype, const std::vector<int64_t>& shape) {
         XTensor t; t.dtype = dtype; t.shape = shape; t.dev = alloc((size_t)std::max<int64_t>(checked_numel(shape), 1) * t.esize()); return t;
     }
@@ -595,17 +529,35 @@ struct OnnxSession::Impl {
         Q3_CHECK((size_t)checked_numel(shape) == v.size(), "host tensor: " + std::to_string(v.size()) + " values for a shape of " + std::to_string(checked_numel(shape)) + " elements");
         XTensor t; t.dtype = dtype; t.shape = shape; t.on_host = true; t.hv = std::move(v); return t;
     }
-    float* f(const XTensor& t) const { return reinterpret_cast<float*>(t.dev->p); }
-    int64_t* i64(const XTensor& t) const { return reinterpret_cast<int64_t*>(t.dev->p); }
+    template <typename T> T* ptr(const XTensor& t) const { return reinterpret_cast<T*>(t.dev->p); }
+    float* f(const XTensor& t) const { return ptr<float>(t); }
+    int64_t* i64(const XTensor& t) const { return ptr<int64_t>(t); }
     void count() { if (launches) (*launches)++; }
+    // every plain launch of the interpreter: 256 threads on the null stream, nothing for an empty grid, one count per launch
+    template <typename... P> void launch(dim3 grid, void (*k)(P...), typename arg_of<P>::type... args) {
+        if (grid.x == 0) return;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, 0, args...);
+        count();
+    }
+    template <typename... P> void launch(int64_t n, void (*k)(P...), typename arg_of<P>::type... args) { launch(grid1(n), k, args...); } // one thread per element
+    void launch_mm_fast(float* out, const float* A, const float* B, const MmFast& g, int64_t batch) {
+        launch(dim3((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64), (unsigned)batch), k_mm_mfma, out, A, B, g);
+    }
+    // fn(T*) with T = int64_t for i64 payloads and float for everything else (bool is f32 on the device): the kernel choice of the data-movement operators
+    template <typename F> static void by_dtype(int dtype, F&& fn) { if (dtype == 7) fn((int64_t*)nullptr); else fn((float*)nullptr); }
 
+    // host values <-> device payload through a staging vector of the payload's element type
+    // (`up` set: upload it; otherwise download into `down`)
+    template <typename T> static void stage(void* dev, size_t n, const double* up, double* down) {
+        std::vector<T> b(n);
+        if (up) { for (size_t i = 0; i < n; i++) b[i] = (T)up[i]; Q3_HIP(hipMemcpy(dev, b.data(), n * sizeof(T), hipMemcpyHostToDevice)); }
+        else { Q3_HIP(hipMemcpy(b.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; i++) down[i] = (double)b[i]; }
+    }
     XTensor to_device(const XTensor& t) {
         if (!t.on_host) return t;
         XTensor d = dev_tensor(t.dtype, t.shape);
-        const int64_t n = t.numel();
-        if (n == 0) return d;
-        if (t.dtype == 7) { std::vector<int64_t> h((size_t)n); for (int64_t i = 0; i < n; i++) h[(size_t)i] = (int64_t)t.hv[(size_t)i]; Q3_HIP(hipMemcpy(d.dev->p, h.data(), (size_t)n * 8, hipMemcpyHostToDevice)); }
-        else { std::vector<float> h((size_t)n); for (int64_t i = 0; i < n; i++) h[(size_t)i] = (float)t.hv[(size_t)i]; Q3_HIP(hipMemcpy(d.dev->p, h.data(), (size_t)n * 4, hipMemcpyHostToDevice)); }
+        if (t.numel() == 0) return d;
+        by_dtype(t.dtype, [&](auto* tag) { stage<std::remove_pointer_t<decltype(tag)>>(d.dev->p, t.hv.size(), t.hv.data(), nullptr); });
         return d;
     }
     XTensor to_host(const XTensor& t) {
@@ -615,8 +567,7 @@ struct OnnxSession::Impl {
         XTensor h = host_tensor(t.dtype, t.shape, std::vector<double>((size_t)n));
         if (n == 0) return h;
         Q3_HIP(hipDeviceSynchronize());
-        if (t.dtype == 7) { std::vector<int64_t> b((size_t)n); Q3_HIP(hipMemcpy(b.data(), t.dev->p, (size_t)n * 8, hipMemcpyDeviceToHost)); for (int64_t i = 0; i < n; i++) h.hv[(size_t)i] = (double)b[(size_t)i]; }
-        else { std::vector<float> b((size_t)n); Q3_HIP(hipMemcpy(b.data(), t.dev->p, (size_t)n * 4, hipMemcpyDeviceToHost)); for (int64_t i = 0; i < n; i++) h.hv[(size_t)i] = (double)b[(size_t)i]; }
+        by_dtype(t.dtype, [&](auto* tag) { stage<std::remove_pointer_t<decltype(tag)>>(t.dev->p, (size_t)n, nullptr, h.hv.data()); });
         return h;
     }
     // device tensor with f32 payload (i64 device tensors are converted; bool is f32 already)
@@ -624,43 +575,30 @@ struct OnnxSession::Impl {
         XTensor t = to_device(t0);
         if (t.dtype != 7) return t;
         XTensor o = dev_tensor(1, t.shape);
-        const int64_t n = t.numel();
-        if (n) { hipLaunchKernelGGL(k_i64_to_f32, grid1(n), dim3(256), 0, 0, f(o), i64(t), n); count(); }
+        launch(t.numel(), k_i64_to_f32, f(o), i64(t), t.numel());
         return o;
     }
     XTensor as_i64(const XTensor& t0) {
         XTensor t = to_device(t0);
         if (t.dtype == 7) return t;
         XTensor o = dev_tensor(7, t.shape);
-        const int64_t n = t.numel();
-        if (n) { hipLaunchKernelGGL(k_f32_to_i64, grid1(n), dim3(256), 0, 0, i64(o), f(t), n); count(); }
+        launch(t.numel(), k_f32_to_i64, i64(o), f(t), t.numel());
         return o;
     }
+    XTensor as_payload(const XTensor& t, int dtype) { return dtype == 7 ? as_i64(t) : as_f32(t); }
     std::vector<int64_t> ints_of(const XTensor& t) { XTensor h = to_host(t); std::vector<int64_t> v(h.hv.size()); for (size_t i = 0; i < v.size(); i++) v[i] = (int64_t)h.hv[i]; return v; }
 
     // general strided copy (transpose / slice / expand / tile) on either side
     XTensor nd_copy(const XTensor& in, const std::vector<int64_t>& oshape, const std::vector<int64_t>& istride, const std::vector<int64_t>& imod, int64_t ioff) {
         Q3_CHECK(oshape.size() <= (size_t)XR, "rank above 8 (rank " + std::to_string(oshape.size()) + ")");
         const int64_t n = prod(oshape);
-        if (in.on_host) {
-            XTensor o = host_tensor(in.dtype, oshape, std::vector<double>((size_t)n));
-            for (int64_t i = 0; i < n; i++) {
-                int64_t r = i, off = ioff;
-                for (int d = (int)oshape.size() - 1; d >= 0; d--) { const int64_t q = r / oshape[d], x = r - q * oshape[d]; off += (x % imod[d]) * istride[d]; r = q; }
-                o.hv[(size_t)i] = in.hv[(size_t)off];
-            }
-            return o;
-        }
+        if (in.on_host) return host_tensor(in.dtype, oshape, host_copy(in.hv, oshape, istride, imod, ioff));
         XTensor o = dev_tensor(in.dtype, oshape);
-        if (n == 0) return o;
         NdMap m{}; m.rank = (int)oshape.size(); m.ioff = ioff;
         for (size_t d = 0; d < oshape.size(); d++) { m.oshape[d] = oshape[d]; m.istride[d] = istride[d]; m.imod[d] = imod[d]; }
-        if (in.dtype == 7) hipLaunchKernelGGL(k_nd_copy<int64_t>, grid1(n), dim3(256), 0, 0, i64(o), i64(in), m, n);
-        else hipLaunchKernelGGL(k_nd_copy<float>, grid1(n), dim3(256), 0, 0, f(o), f(in), m, n);
-        count();
+        by_dtype(in.dtype, [&](auto* tag) { using T = std::remove_pointer_t<decltype(tag)>; launch(n, k_nd_copy<T>, ptr<T>(o), ptr<T>(in), m, n); });
         return o;
     }
-    static std::vector<int64_t> nomod(size_t r) { return std::vector<int64_t>(r, std::numeric_limits<int64_t>::max()); }
     XTensor transpose(const XTensor& in, const std::vector<int64_t>& perm) {
         Q3_CHECK(perm.size() == in.shape.size(), "Transpose: perm has " + std::to_string(perm.size()) + " entries for a rank-" + std::to_string(in.shape.size()) + " tensor");
         { std::vector<char> seen(perm.size(), 0); for (auto p : perm) { Q3_CHECK(p >= 0 && p < (int64_t)perm.size() && !seen[(size_t)p], "Transpose: perm is not a permutation"); seen[(size_t)p] = 1; } }
@@ -675,50 +613,29 @@ struct OnnxSession::Impl {
     }
     XTensor reshaped(const XTensor& in, const std::vector<int64_t>& shape) { XTensor o = in; o.shape = shape; Q3_CHECK(o.numel() == in.numel(), "reshape changes the element count"); return o; }
 
+    // the broadcast map of up to three device operands seen through the output shape
+    static NdMap2 map2(const std::vector<int64_t>& os, const XTensor& a, const XTensor& b, const XTensor* c = nullptr) {
+        NdMap2 m{}; m.rank = (int)os.size();
+        const auto as = bstrides(a.shape, os), bs = bstrides(b.shape, os), cs = c ? bstrides(c->shape, os) : std::vector<int64_t>(os.size(), 0);
+        for (size_t d = 0; d < os.size(); d++) { m.oshape[d] = os[d]; m.as[d] = as[d]; m.bs[d] = bs[d]; m.cs[d] = cs[d]; }
+        return m;
+    }
     XTensor binary(int op, const XTensor& a0, const XTensor& b0, int out_dtype) {
         const auto os = bshape(a0.shape, b0.shape);
-        const int64_t n = prod(os);
-        if (a0.on_host && b0.on_host) {
-            XTensor o = host_tensor(out_dtype, os, std::vector<double>((size_t)n));
-            const auto as = bstrides(a0.shape, os), bs = bstrides(b0.shape, os);
-            const int hop = (op == B_DIV && a0.dtype == 7 && b0.dtype == 7) ? B_IDIV : op;
-            for (int64_t i = 0; i < n; i++) {
-                int64_t r = i, ao = 0, bo = 0;
-                for (int d = (int)os.size() - 1; d >= 0; d--) { const int64_t q = r / os[d], x = r - q * os[d]; ao += x * as[d]; bo += x * bs[d]; r = q; }
-                o.hv[(size_t)i] = apply_binary_d(hop, a0.hv[(size_t)ao], b0.hv[(size_t)bo]);
-            }
-            return o;
-        }
+        if (a0.on_host && b0.on_host) return host_tensor(out_dtype, os, host_binary(op, a0.hv, a0.shape, b0.hv, b0.shape, os, a0.dtype == 7 && b0.dtype == 7));
         Q3_CHECK(!(a0.dtype == 7 && b0.dtype == 7 && !a0.on_host && !b0.on_host && op == B_DIV), "integer division of device tensors");
         Q3_CHECK(os.size() <= (size_t)XR, "rank above 8 (rank " + std::to_string(os.size()) + ")");
         XTensor a = as_f32(a0), b = as_f32(b0);
         XTensor o = dev_tensor(out_dtype == 7 ? 1 : out_dtype, os);
-        if (n) {
-            NdMap2 m{}; m.rank = (int)os.size();
-            const auto as = bstrides(a.shape, os), bs = bstrides(b.shape, os);
-            for (size_t d = 0; d < os.size(); d++) { m.oshape[d] = os[d]; m.as[d] = as[d]; m.bs[d] = bs[d]; }
-            hipLaunchKernelGGL(k_binary, grid1(n), dim3(256), 0, 0, f(o), f(a), f(b), op, m, n);
-            count();
-        }
-        if (out_dtype == 7) { XTensor r = as_i64(o); return r; } // integer arithmetic on large device tensors goes through f32 (exact below 2^24)
-        return o;
+        const int64_t n = prod(os);
+        if (n) launch(n, k_binary, f(o), f(a), f(b), op, map2(os, a, b), n);
+        return out_dtype == 7 ? as_i64(o) : o; // integer arithmetic on large device tensors goes through f32 (exact below 2^24)
     }
     XTensor unary(int op, const XTensor& x0, float a, float b) {
-        if (x0.on_host && x0.dtype == 7 && (op == U_NEG || op == U_ABS || op == U_SIGN || op == U_IDENT || op == U_NOT)) {
-            XTensor o = x0;
-            for (auto& v : o.hv) v = op == U_NEG ? -v : op == U_ABS ? std::fabs(v) : op == U_SIGN ? (v > 0) - (v < 0) : op == U_NOT ? (v != 0 ? 0 : 1) : v;
-            return o;
-        }
-        if (x0.on_host && (op == U_FLOOR || op == U_CEIL || op == U_SQRT || op == U_NEG || op == U_ABS || op == U_ROUND || op == U_NOT)) {
-            XTensor o = x0;
-            for (auto& v : o.hv) v = op == U_FLOOR ? std::floor(v) : op == U_CEIL ? std::ceil(v) : op == U_SQRT ? std::sqrt(v) : op == U_NEG ? -v : op == U_ABS ? std::fabs(v)
-                                   : op == U_ROUND ? std::nearbyint(v) : (v != 0 ? 0 : 1);
-            return o;
-        }
+        if (x0.on_host) { XTensor o = x0; if (host_unary(op, x0.dtype == 7, o.hv)) return o; }
         XTensor x = as_f32(x0);
         XTensor o = dev_tensor(op == U_NOT || op == U_ISNAN ? 9 : 1, x.shape);
-        const int64_t n = x.numel();
-        if (n) { hipLaunchKernelGGL(k_unary, grid1(n), dim3(256), 0, 0, f(o), f(x), op, a, b, n); count(); }
+        launch(x.numel(), k_unary, f(o), f(x), op, a, b, x.numel());
         return o;
     }
     // rows x cols view with the given axes moved last (in order); returns the permuted tensor and fills rows / cols
@@ -736,8 +653,18 @@ struct OnnxSession::Impl {
         for (int d = 0; d < r; d++) if (perm[(size_t)d] != d) ident = false;
         return ident ? x : transpose(x, perm);
     }
-    std::vector<int64_t> norm_axes(std::vector<int64_t> axes, int rank) { for (auto& a : axes) { if (a < 0) a += rank; Q3_CHECK(a >= 0 && a < rank, "axis out of range"); } std::sort(axes.begin(), axes.end()); axes.erase(std::unique(axes.begin(), axes.end()), axes.end()); return axes; }
+    // axis `a` moved last, fn(q, p, rows, cols) fills q from p row by row, and the result is permuted back to the input's layout
+    template <typename F> XTensor rows_over_axis(const XTensor& x, int64_t a, F&& fn) {
+        int64_t rows, cols; std::vector<int64_t> perm;
+        XTensor p = axes_last(x, {a}, rows, cols, &perm);
+        XTensor q = dev_tensor(1, p.shape);
+        fn(q, p, rows, cols);
+        std::vector<int64_t> inv(perm.size());
+        for (size_t d = 0; d < perm.size(); d++) inv[(size_t)perm[d]] = (int64_t)d;
+        return transpose(q, inv);
+    }
 };
+struct OnnxSession::Impl : Exec {};
 
 // Decodes a TensorProto payload into doubles after checking it against the declared dims: the element count is computed with overflow
 // checks and capped, raw_data / the typed repeated field must hold at least that many elements (a truncated or crafted file must become
@@ -766,6 +693,607 @@ static std::vector<double> tensor_values(const OnnxTensor& t, const std::string&
     return v;
 }
 
+// =============================================================== handlers ==============================================================
+// What a handler sees of its node: inputs (an edge of this run or an initialiser), attributes with their defaults, and out(), the only writer of vals.
+struct NodeCtx {
+    Exec& I;
+    const OnnxNode& nd;
+    int arg;
+    const std::string& op() const { return nd.op_type; }
+    bool has(size_t i) const { return i < nd.inputs.size() && !nd.inputs[i].empty(); }
+    const XTensor& in(size_t i) const {
+        Q3_CHECK(has(i), "missing input " + std::to_string(i));
+        const XTensor* t = I.find(nd.inputs[i]);
+        if (!t) throw Error("input " + nd.inputs[i] + " has no producer");
+        return *t;
+    }
+    std::vector<int64_t> ints(size_t i) const { return I.ints_of(in(i)); }
+    int64_t ai(const char* n, int64_t d) const { auto* a = nd.attr(n); return a ? a->i : d; }
+    float af(const char* n, float d) const { auto* a = nd.attr(n); return a ? a->f : d; }
+    std::string as(const char* n, const char* d) const { auto* a = nd.attr(n); return a ? a->s : std::string(d); }
+    std::vector<int64_t> aints(const char* n) const { auto* a = nd.attr(n); return a ? a->ints : std::vector<int64_t>(); }
+    int64_t axis(const char* n, int64_t d, size_t rank) const { return axis_of(ai(n, d), (int64_t)rank, op()); } // a checked axis attribute
+    void out(size_t i, XTensor t) const { if (i < nd.outputs.size() && !nd.outputs[i].empty()) I.vals[nd.outputs[i]] = std::move(t); }
+};
+
+static void op_unary(NodeCtx& c) {
+    int u = c.arg;
+    float a = 0.f, b = 0.f;
+    switch (u) {
+        case U_ELU: a = c.af("alpha", 1.0f); break;
+        case U_LEAKY: a = c.af("alpha", 0.01f); break;
+        case U_HSIG: a = c.af("alpha", 0.2f); b = c.af("beta", 0.5f); break;
+        case U_SELU: a = c.af("alpha", 1.67326319217681884765625f); b = c.af("gamma", 1.05070102214813232421875f); break;
+        case U_GELU: if (c.as("approximate", "none") == "tanh") u = U_GELU_TANH; break;
+        case U_CELU: a = c.af("alpha", 1.0f); break;
+        case U_THRELU: a = c.af("alpha", 1.0f); break;
+    }
+    c.out(0, c.I.unary(u, c.in(0), a, b));
+}
+static void op_binary(NodeCtx& c) { // variadic for Sum / Mean / Min / Max: folded left to right
+    int b = c.arg;
+    if (b == B_MOD && c.ai("fmod", 0)) b = B_FMOD;
+    const bool cmp = b == B_EQ || b == B_LT || b == B_GT || b == B_LE || b == B_GE || b == B_AND || b == B_OR || b == B_XOR;
+    XTensor acc = c.in(0);
+    for (size_t i = 1; i < c.nd.inputs.size(); i++) {
+        const XTensor& y = c.in(i);
+        const int od = cmp ? 9 : (acc.dtype == 7 && y.dtype == 7) ? 7 : 1;
+        acc = c.I.binary(b, acc, y, od);
+    }
+    if (c.op() == "Mean" && c.nd.inputs.size() > 1) acc = c.I.binary(B_DIV, acc, Exec::host_tensor(1, {}, {(double)c.nd.inputs.size()}), 1);
+    c.out(0, acc);
+}
+static void op_identity(NodeCtx& c) { c.out(0, c.in(0)); } // Identity, Dropout (inference)
+static void op_shape(NodeCtx& c) {
+    const auto& s = c.in(0).shape;
+    int64_t b = c.ai("start", 0), e = c.ai("end", (int64_t)s.size());
+    if (b < 0) b += (int64_t)s.size();
+    if (e < 0) e += (int64_t)s.size();
+    b = std::max<int64_t>(0, std::min<int64_t>(b, (int64_t)s.size())); e = std::max<int64_t>(b, std::min<int64_t>(e, (int64_t)s.size()));
+    std::vector<double> v; for (int64_t i = b; i < e; i++) v.push_back((double)s[(size_t)i]);
+    c.out(0, Exec::host_tensor(7, {(int64_t)v.size()}, v));
+}
+static void op_size(NodeCtx& c) { c.out(0, Exec::host_tensor(7, {}, {(double)c.in(0).numel()})); }
+static void op_constant(NodeCtx& c) {
+    const OnnxNode& nd = c.nd;
+    if (auto* a = nd.attr("value")) {
+        const OnnxTensor& t = a->t;
+        int dtype = 1;
+        std::vector<double> v = tensor_values(t, "Constant " + nd.name, &dtype);
+        const int64_t n = (int64_t)v.size();
+        XTensor h = Exec::host_tensor(dtype, t.dims, std::move(v));
+        c.out(0, (dtype == 7 || n <= 4096) ? h : c.I.to_device(h));
+    } else if (auto* a2 = nd.attr("value_float")) c.out(0, Exec::host_tensor(1, {}, {(double)a2->f}));
+    else if (auto* a3 = nd.attr("value_int")) c.out(0, Exec::host_tensor(7, {}, {(double)a3->i}));
+    else if (auto* a4 = nd.attr("value_ints")) { std::vector<double> v(a4->ints.begin(), a4->ints.end()); c.out(0, Exec::host_tensor(7, {(int64_t)v.size()}, v)); }
+    else if (auto* a5 = nd.attr("value_floats")) { std::vector<double> v(a5->floats.begin(), a5->floats.end()); c.out(0, Exec::host_tensor(1, {(int64_t)v.size()}, v)); }
+    else throw Error("Constant without a supported value attribute");
+}
+static void op_constant_of_shape(NodeCtx& c) {
+    Exec& I = c.I;
+    const auto shape = c.ints(0);
+    double v = 0; int dtype = 1;
+    if (auto* a = c.nd.attr("value")) {
+        const std::vector<double> tv = tensor_values(a->t, "ConstantOfShape " + c.nd.name + " value", &dtype);
+        Q3_CHECK(tv.size() >= 1, "ConstantOfShape " + c.nd.name + ": empty value tensor");
+        v = tv[0];
+    }
+    const int64_t n = prod(shape);
+    if (n <= 65536) { c.out(0, Exec::host_tensor(dtype, shape, std::vector<double>((size_t)n, v))); return; }
+    XTensor o = I.dev_tensor(dtype == 7 ? 1 : dtype, shape);
+    I.launch(n, k_fill, I.f(o), (float)v, n);
+    c.out(0, dtype == 7 ? I.as_i64(o) : o);
+}
+static void op_range(NodeCtx& c) {
+    const XTensor s = c.I.to_host(c.in(0)), l = c.I.to_host(c.in(1)), d = c.I.to_host(c.in(2));
+    const double st = s.hv.at(0), li = l.hv.at(0), de = d.hv.at(0);
+    const int64_t n = std::max<int64_t>(0, (int64_t)std::ceil((li - st) / de));
+    std::vector<double> v((size_t)n);
+    for (int64_t i = 0; i < n; i++) v[(size_t)i] = st + (double)i * de;
+    c.out(0, Exec::host_tensor(s.dtype, {n}, v));
+}
+static void op_cast(NodeCtx& c) {
+    Exec& I = c.I;
+    const int64_t to = c.ai("to", 1);
+    const XTensor& x = c.in(0);
+    // f64 (11) is carried as f32 (documented precision loss); f16 / bf16 / string targets would need a rounding pass this executor does not have
+    Q3_CHECK(to == 1 || to == 11 || to == 7 || to == 6 || to == 2 || to == 3 || to == 5 || to == 12 || to == 13 || to == 9,
+             "Cast to element type " + std::to_string(to) + " is not supported (tensors are f32 / i64 / bool on this executor)");
+    const int dt = (to == 7 || to == 6 || to == 2 || to == 3 || to == 5 || to == 12 || to == 13) ? 7 : to == 9 ? 9 : 1;
+    if (x.on_host) {
+        XTensor o = x; o.dtype = dt;
+        if (dt == 7) for (auto& v : o.hv) v = std::trunc(v);
+        else if (dt == 9) for (auto& v : o.hv) v = v != 0 ? 1 : 0;
+        else for (auto& v : o.hv) v = (double)(float)v;
+        c.out(0, o);
+    } else if (dt == 7) c.out(0, I.as_i64(x));
+    else if (dt == 9) { XTensor z = Exec::host_tensor(1, {}, {0.0}); XTensor e = I.binary(B_EQ, x, z, 9); c.out(0, I.unary(U_NOT, e, 0, 0)); }
+    else { XTensor o = I.as_f32(x); o.dtype = 1; c.out(0, o); }
+}
+static void op_reshape(NodeCtx& c) {
+    const XTensor& x = c.in(0);
+    c.out(0, c.I.reshaped(x, reshape_shape(x.shape, c.ints(1), c.ai("allowzero", 0) != 0)));
+}
+static void op_flatten(NodeCtx& c) { const XTensor& x = c.in(0); c.out(0, c.I.reshaped(x, flatten_shape(x.shape, c.ai("axis", 1)))); }
+static void op_squeeze(NodeCtx& c) { // arg 1: Unsqueeze
+    const XTensor& x = c.in(0);
+    const std::vector<int64_t> axes = c.has(1) ? c.ints(1) : c.aints("axes");
+    c.out(0, c.I.reshaped(x, c.arg ? unsqueeze_shape(x.shape, axes) : squeeze_shape(x.shape, axes)));
+}
+static void op_transpose(NodeCtx& c) {
+    const XTensor& x = c.in(0);
+    std::vector<int64_t> perm = c.aints("perm");
+    if (perm.empty()) for (int d = (int)x.shape.size() - 1; d >= 0; d--) perm.push_back(d);
+    c.out(0, c.I.transpose(x, perm));
+}
+static void op_expand(NodeCtx& c) { const XTensor& x = c.in(0); c.out(0, c.I.expand(x, bshape(x.shape, c.ints(1)))); }
+static void op_tile(NodeCtx& c) {
+    const XTensor& x = c.in(0);
+    const auto os = tile_shape(x.shape, c.ints(1));
+    std::vector<int64_t> mod = x.shape; for (auto& m : mod) m = std::max<int64_t>(m, 1);
+    c.out(0, c.I.nd_copy(x, os, strides_of(x.shape), mod, 0));
+}
+static void op_slice(NodeCtx& c) {
+    const XTensor& x = c.in(0);
+    std::vector<int64_t> starts, ends, axes, steps;
+    if (c.has(1)) { starts = c.ints(1); ends = c.ints(2); if (c.has(3)) axes = c.ints(3); if (c.has(4)) steps = c.ints(4); }
+    else { starts = c.aints("starts"); ends = c.aints("ends"); axes = c.aints("axes"); }
+    if (axes.empty()) for (size_t i = 0; i < starts.size(); i++) axes.push_back((int64_t)i);
+    if (steps.empty()) steps.assign(starts.size(), 1);
+    Q3_CHECK(ends.size() == starts.size() && axes.size() == starts.size() && steps.size() == starts.size(), "Slice: starts / ends / axes / steps differ in length");
+    std::vector<int64_t> os = x.shape, st = strides_of(x.shape), is = st;
+    int64_t off = 0;
+    for (size_t i = 0; i < starts.size(); i++) {
+        const size_t a = (size_t)axis_of(axes[i], (int64_t)x.shape.size(), "Slice");
+        const SliceAxis g = slice_axis(x.shape[a], starts[i], ends[i], steps[i]);
+        os[a] = g.count; is[a] = st[a] * g.step; off += g.start * st[a];
+    }
+    c.out(0, c.I.nd_copy(x, os, is, nomod(os.size()), off));
+}
+static void op_split(NodeCtx& c) {
+    const XTensor& x = c.in(0);
+    const size_t a = (size_t)c.axis("axis", 0, x.shape.size());
+    const auto sizes = split_sizes(x.shape[a], c.has(1) ? c.ints(1) : c.aints("split"), c.nd.outputs.size());
+    const auto st = strides_of(x.shape);
+    int64_t at = 0;
+    for (size_t i = 0; i < sizes.size(); i++) {
+        std::vector<int64_t> os = x.shape; os[a] = sizes[i];
+        c.out(i, c.I.nd_copy(x, os, st, nomod(os.size()), at * st[a]));
+        at += sizes[i];
+    }
+}
+static void op_concat(NodeCtx& c) {
+    Exec& I = c.I;
+    const OnnxNode& nd = c.nd;
+    const int r = (int)c.in(0).shape.size();
+    const int64_t a = c.axis("axis", 0, (size_t)r);
+    for (size_t i = 1; i < nd.inputs.size(); i++) {
+        Q3_CHECK((int)c.in(i).shape.size() == r, "Concat: input " + std::to_string(i) + " (" + nd.inputs[i] + ") has rank " + std::to_string(c.in(i).shape.size()) + ", input 0 (" + nd.inputs[0] + ") rank " + std::to_string(r));
+        for (int d = 0; d < r; d++) Q3_CHECK(d == a || c.in(i).shape[(size_t)d] == c.in(0).shape[(size_t)d], "Concat: inputs differ off the concatenation axis");
+    }
+    bool all_host = true; int dtype = c.in(0).dtype; int64_t total = 0;
+    for (size_t i = 0; i < nd.inputs.size(); i++) { all_host = all_host && c.in(i).on_host; total += c.in(i).shape.at((size_t)a); if (c.in(i).dtype != 7) dtype = c.in(i).dtype == 9 && dtype == 9 ? 9 : 1; }
+    std::vector<int64_t> os = c.in(0).shape; os[(size_t)a] = total;
+    const int64_t inner = prod(os, (size_t)a + 1), outer = prod(os, 0, (size_t)a);
+    XTensor o = all_host ? Exec::host_tensor(dtype, os, std::vector<double>((size_t)prod(os))) : I.dev_tensor(dtype, os);
+    int64_t at = 0;
+    for (size_t i = 0; i < nd.inputs.size(); i++) {
+        const int64_t part = c.in(i).shape[(size_t)a];
+        if (all_host) host_concat_part(o.hv, c.in(i).hv, outer, part, inner, total, at);
+        else {
+            XTensor t = I.as_payload(c.in(i), dtype);
+            Exec::by_dtype(dtype, [&](auto* tag) { using T = std::remove_pointer_t<decltype(tag)>; I.launch(t.numel(), k_concat<T>, I.ptr<T>(o), I.ptr<T>(t), part, inner, total, at, t.numel()); });
+        }
+        at += part;
+    }
+    c.out(0, o);
+}
+static void op_gather(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor& x = c.in(0); const XTensor& idx = c.in(1);
+    const int64_t a = c.axis("axis", 0, x.shape.size());
+    const int64_t dim = x.shape.at((size_t)a), inner = prod(x.shape, (size_t)a + 1), outer = prod(x.shape, 0, (size_t)a), nidx = idx.numel();
+    const auto os = gather_shape(x.shape, idx.shape, a);
+    if (x.on_host && idx.on_host) { c.out(0, Exec::host_tensor(x.dtype, os, host_gather(x.hv, idx.hv, outer, dim, inner))); return; }
+    XTensor xd = I.to_device(x), id = I.as_i64(idx);
+    XTensor o = I.dev_tensor(xd.dtype, os);
+    const int64_t n = o.numel();
+    Exec::by_dtype(xd.dtype, [&](auto* tag) { using T = std::remove_pointer_t<decltype(tag)>; I.launch(n, k_gather<T>, I.ptr<T>(o), I.ptr<T>(xd), I.i64(id), nidx, dim, inner, n); });
+    c.out(0, o);
+}
+static void op_where(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor& cd0 = c.in(0); const XTensor& a = c.in(1); const XTensor& b = c.in(2);
+    const auto os = bshape(bshape(cd0.shape, a.shape), b.shape);
+    const int dtype = (a.dtype == 7 && b.dtype == 7) ? 7 : (a.dtype == 9 && b.dtype == 9) ? 9 : 1;
+    if (cd0.on_host && a.on_host && b.on_host) { c.out(0, Exec::host_tensor(dtype, os, host_where(cd0.hv, cd0.shape, a.hv, a.shape, b.hv, b.shape, os))); return; }
+    Q3_CHECK(os.size() <= (size_t)XR, "Where: rank above 8 (rank " + std::to_string(os.size()) + ")");
+    XTensor cd = I.as_f32(cd0), ad = I.as_payload(a, dtype), bd = I.as_payload(b, dtype);
+    XTensor o = I.dev_tensor(dtype, os);
+    const int64_t n = prod(os);
+    if (n) Exec::by_dtype(dtype, [&](auto* tag) { using T = std::remove_pointer_t<decltype(tag)>; I.launch(n, k_where<T>, I.ptr<T>(o), I.f(cd), I.ptr<T>(ad), I.ptr<T>(bd), Exec::map2(os, ad, bd, &cd), n); });
+    c.out(0, o);
+}
+static void op_clip(NodeCtx& c) {
+    float lo = -std::numeric_limits<float>::infinity(), hi = std::numeric_limits<float>::infinity();
+    if (c.nd.attr("min")) lo = c.af("min", lo);
+    if (c.nd.attr("max")) hi = c.af("max", hi);
+    if (c.has(1)) lo = (float)c.I.to_host(c.in(1)).hv.at(0);
+    if (c.has(2)) hi = (float)c.I.to_host(c.in(2)).hv.at(0);
+    c.out(0, c.I.unary(U_CLIP, c.in(0), lo, hi));
+}
+static void op_reduce(NodeCtx& c) { // the Reduce* family, ArgMax and ArgMin
+    Exec& I = c.I;
+    const int r = c.arg;
+    const XTensor& x0 = c.in(0);
+    const int rank = (int)x0.shape.size();
+    const bool arg = r == R_ARGMAX || r == R_ARGMIN;
+    std::vector<int64_t> axes;
+    if (arg) axes = {c.ai("axis", 0)};
+    else if (c.has(1)) axes = c.ints(1);
+    else axes = c.aints("axes");
+    const bool keep = c.ai("keepdims", 1) != 0;
+    if (axes.empty() && !arg) {
+        if (c.ai("noop_with_empty_axes", 0)) { c.out(0, x0); return; }
+        for (int d = 0; d < rank; d++) axes.push_back(d);
+    }
+    axes = norm_axes(axes, rank);
+    const auto os = reduce_shape(x0.shape, axes, keep);
+    int64_t rows, cols;
+    if (x0.on_host && host_reduce_ok(r)) { // shape arithmetic (ReduceProd of a shape, ...)
+        XTensor p = I.axes_last(x0, axes, rows, cols);
+        c.out(0, Exec::host_tensor(x0.dtype, os, host_reduce(r, p.hv, rows, cols)));
+        return;
+    }
+    XTensor p = I.axes_last(I.as_f32(x0), axes, rows, cols);
+    XTensor o = I.dev_tensor(arg ? 7 : 1, os);
+    if (rows) {
+        Q3_CHECK(cols > 0, "reduction over an empty axis");
+        I.launch(grid_rows(rows), k_reduce_rows, arg ? nullptr : I.f(o), arg ? I.i64(o) : nullptr, I.f(p), r, cols, (int)c.ai("select_last_index", 0));
+    }
+    c.out(0, o);
+}
+static void op_softmax(NodeCtx& c) { // arg 1: LogSoftmax
+    Exec& I = c.I;
+    const int rank = (int)c.in(0).shape.size();
+    const int64_t a = c.axis("axis", I.opset >= 13 ? -1 : 1, (size_t)rank);
+    const XTensor x = I.as_f32(c.in(0));
+    if (I.opset < 13 || a == rank - 1) { // rows = everything before the axis, cols = the rest (opset < 13 flattens; for the last axis both readings agree)
+        const int64_t cols = prod(x.shape, (size_t)a), rows = prod(x.shape, 0, (size_t)a);
+        XTensor o = I.dev_tensor(1, x.shape);
+        I.launch(grid_rows(rows, cols), k_softmax_rows, I.f(o), I.f(x), cols, c.arg);
+        c.out(0, o);
+    } else c.out(0, I.rows_over_axis(x, a, [&](XTensor& q, const XTensor& p, int64_t rows, int64_t cols) { I.launch(grid_rows(rows, cols), k_softmax_rows, I.f(q), I.f(p), cols, c.arg); }));
+}
+static void op_layer_norm(NodeCtx& c) {
+    Exec& I = c.I;
+    const int64_t a = c.axis("axis", -1, c.in(0).shape.size());
+    const XTensor x = I.as_f32(c.in(0));
+    const int64_t cols = prod(x.shape, (size_t)a), rows = prod(x.shape, 0, (size_t)a);
+    XTensor g = c.has(1) ? I.as_f32(c.in(1)) : XTensor(), b = c.has(2) ? I.as_f32(c.in(2)) : XTensor();
+    Q3_CHECK((!c.has(1) || g.numel() == cols) && (!c.has(2) || b.numel() == cols), "LayerNormalization: scale / bias length does not match the normalised extent");
+    XTensor o = I.dev_tensor(1, x.shape);
+    I.launch(grid_rows(rows, cols), k_norm_rows, I.f(o), I.f(x), c.has(1) ? I.f(g) : nullptr, c.has(2) ? I.f(b) : nullptr, cols, c.af("epsilon", 1e-5f), 0, 1);
+    c.out(0, o);
+}
+static void op_instance_norm(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0)), g = I.as_f32(c.in(1)), b = I.as_f32(c.in(2));
+    const int64_t C = x.shape.at(1), rows = x.shape.at(0) * C, cols = prod(x.shape, 2);
+    Q3_CHECK(g.numel() == C && b.numel() == C, "InstanceNormalization: scale / bias length does not match the channels");
+    XTensor o = I.dev_tensor(1, x.shape);
+    I.launch(grid_rows(rows, cols), k_norm_rows, I.f(o), I.f(x), I.f(g), I.f(b), cols, c.af("epsilon", 1e-5f), 1, C);
+    c.out(0, o);
+}
+static void op_batch_norm(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0)), sc = I.as_f32(c.in(1)), bi = I.as_f32(c.in(2)), mean = I.as_f32(c.in(3)), var = I.as_f32(c.in(4));
+    const int64_t C = x.shape.at(1), inner = prod(x.shape, 2), n = x.numel();
+    Q3_CHECK(sc.numel() == C && bi.numel() == C && mean.numel() == C && var.numel() == C, "BatchNormalization: parameter lengths do not match the channels");
+    XTensor o = I.dev_tensor(1, x.shape);
+    I.launch(n, k_batchnorm, I.f(o), I.f(x), I.f(sc), I.f(bi), I.f(mean), I.f(var), c.af("epsilon", 1e-5f), C, inner, n);
+    c.out(0, o);
+}
+static void op_global_pool(NodeCtx& c) { // arg: R_MEAN (GlobalAveragePool) or R_MAX (GlobalMaxPool)
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0));
+    const int64_t rows = x.shape.at(0) * x.shape.at(1), cols = prod(x.shape, 2);
+    std::vector<int64_t> os = x.shape; for (size_t d = 2; d < os.size(); d++) os[d] = 1;
+    XTensor o = I.dev_tensor(1, os);
+    I.launch(grid_rows(rows), k_reduce_rows, I.f(o), nullptr, I.f(x), c.arg, cols, 0);
+    c.out(0, o);
+}
+static void op_cumsum(NodeCtx& c) {
+    Exec& I = c.I;
+    const int64_t a = axis_of(c.ints(1).at(0), (int64_t)c.in(0).shape.size(), c.op());
+    const int ex = (int)c.ai("exclusive", 0), rev = (int)c.ai("reverse", 0);
+    c.out(0, I.rows_over_axis(I.as_f32(c.in(0)), a, [&](XTensor& q, const XTensor& p, int64_t rows, int64_t cols) {
+        if (rows && cols) I.launch(rows, k_cumsum_rows, I.f(q), I.f(p), rows, cols, ex, rev);
+    }));
+}
+static MmFast mm_fast_of(const MmArgs& g) { // the same product for k_mm_mfma (extents checked by mm_fast_ok)
+    MmFast f{};
+    f.M = (int)g.M; f.N = (int)g.N; f.K = (int)g.K; f.a_b = g.a_b; f.a_m = g.a_m; f.a_k = g.a_k; f.b_b = g.b_b; f.b_k = g.b_k; f.b_n = g.b_n;
+    f.bias = g.bias; f.bias_m = g.bias_m; f.bias_n = g.bias_n; f.alpha = g.alpha; f.beta = g.beta;
+    return f;
+}
+static void op_matmul(NodeCtx& c) { // arg 1: Gemm
+    Exec& I = c.I;
+    XTensor A = I.as_f32(c.in(0)), B = I.as_f32(c.in(1));
+    MmArgs g{};
+    g.alpha = 1.f; g.beta = 1.f;
+    std::vector<int64_t> os;
+    int64_t batch = 1;
+    XTensor bias;
+    if (c.arg) {
+        Q3_CHECK(A.shape.size() == 2 && B.shape.size() == 2, "Gemm takes matrices");
+        const bool ta = c.ai("transA", 0) != 0, tb = c.ai("transB", 0) != 0;
+        g.M = ta ? A.shape[1] : A.shape[0]; g.K = ta ? A.shape[0] : A.shape[1]; g.N = tb ? B.shape[0] : B.shape[1];
+        Q3_CHECK((tb ? B.shape[1] : B.shape[0]) == g.K, "Gemm inner dimensions differ");
+        g.a_m = ta ? 1 : A.shape[1]; g.a_k = ta ? A.shape[1] : 1; g.b_k = tb ? 1 : B.shape[1]; g.b_n = tb ? B.shape[1] : 1;
+        g.alpha = c.af("alpha", 1.f); g.beta = c.af("beta", 1.f);
+        if (c.has(2)) {
+            bias = I.as_f32(c.in(2));
+            const auto bs = bstrides(bias.shape, {g.M, g.N});
+            g.bias = I.f(bias); g.bias_m = bs[0]; g.bias_n = bs[1];
+        }
+        os = {g.M, g.N};
+    } else {
+        std::vector<int64_t> as_ = A.shape, bs_ = B.shape;
+        const bool va = as_.size() == 1, vb = bs_.size() == 1;
+        if (va) as_.insert(as_.begin(), 1);
+        if (vb) bs_.push_back(1);
+        g.M = as_[as_.size() - 2]; g.K = as_.back(); g.N = bs_.back();
+        Q3_CHECK(bs_[bs_.size() - 2] == g.K, "MatMul inner dimensions differ");
+        std::vector<int64_t> ab(as_.begin(), as_.end() - 2), bb(bs_.begin(), bs_.end() - 2);
+        const auto bd = bshape(ab, bb);
+        batch = prod(bd);
+        // operands whose batch dims are smaller than the broadcast batch are expanded first (rare: attention uses equal batches)
+        auto full = [&](XTensor& T, std::vector<int64_t>& s, const std::vector<int64_t>& own) {
+            if (own == bd) return;
+            if (prod(own) == 1) return; // pure broadcast: batch stride 0
+            std::vector<int64_t> tgt = bd; tgt.push_back(s[s.size() - 2]); tgt.push_back(s.back());
+            T = I.expand(I.reshaped(T, s), tgt); s = tgt;
+        };
+        full(A, as_, ab); full(B, bs_, bb);
+        g.a_b = (as_.size() > 2 && prod(as_, 0, as_.size() - 2) > 1) ? g.M * g.K : 0;
+        g.b_b = (bs_.size() > 2 && prod(bs_, 0, bs_.size() - 2) > 1) ? g.K * g.N : 0;
+        g.a_m = g.K; g.a_k = 1; g.b_k = g.N; g.b_n = 1;
+        os = bd;
+        if (!va) os.push_back(g.M);
+        if (!vb) os.push_back(g.N);
+    }
+    XTensor o = I.dev_tensor(1, os);
+    if (o.numel()) {
+        if (mm_fast_ok(g.M, g.N, g.K, batch)) I.launch_mm_fast(I.f(o), I.f(A), I.f(B), mm_fast_of(g), batch);
+        else I.launch(dim3((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)batch), k_matmul, I.f(o), I.f(A), I.f(B), g);
+    }
+    c.out(0, o);
+}
+static void op_conv(NodeCtx& c) { // arg 1: ConvTranspose
+    Exec& I = c.I;
+    const bool tr = c.arg != 0;
+    const std::string& op = c.op();
+    XTensor x = I.as_f32(c.in(0)), w = I.as_f32(c.in(1)), b = c.has(2) ? I.as_f32(c.in(2)) : XTensor();
+    const int sp = (int)x.shape.size() - 2;
+    Q3_CHECK(sp == 1 || sp == 2, "convolutions over 1 or 2 spatial dimensions");
+    Q3_CHECK(w.shape.size() == x.shape.size(), op + ": weight rank does not match the input rank");
+    // every per-dimension list as (H, W); one spatial dimension is H of 1
+    auto two = [&](std::vector<int64_t> v, int64_t fill, int64_t lead) { if (v.empty()) v.assign((size_t)sp, fill); if (sp == 1) v.insert(v.begin(), lead); return v; };
+    const std::vector<int64_t> strides = two(c.aints("strides"), 1, 1), dil = two(c.aints("dilations"), 1, 1), pads = c.aints("pads"), ks = two(std::vector<int64_t>(w.shape.begin() + 2, w.shape.end()), 1, 1);
+    Q3_CHECK(strides.size() == 2 && dil.size() == 2 && (pads.empty() || pads.size() == (size_t)(2 * sp)), op + ": strides / dilations / pads do not match the spatial rank");
+    ConvArgs g{};
+    g.N = x.shape[0]; g.C = x.shape[1]; g.H = sp == 1 ? 1 : x.shape[2]; g.W = x.shape.back();
+    g.kh = ks[0]; g.kw = ks[1]; g.sh = strides[0]; g.sw = strides[1]; g.dh = dil[0]; g.dw = dil[1]; g.groups = c.ai("group", 1);
+    // operand shapes against what k_conv2d / k_convtr2d index (they divide by groups and strides and trust the weight / bias extents)
+    Q3_CHECK(g.sh > 0 && g.sw > 0 && g.dh > 0 && g.dw > 0 && g.kh > 0 && g.kw > 0, op + ": strides, dilations and kernel extents must be positive");
+    Q3_CHECK(g.groups > 0 && g.C % g.groups == 0, op + ": group does not divide the input channels");
+    if (!tr) Q3_CHECK(w.shape[1] * g.groups == g.C && w.shape[0] % g.groups == 0, "Conv: weight shape [M, C/group, ...] does not match the input channels");
+    else Q3_CHECK(w.shape[0] == g.C, "ConvTranspose: weight shape [C, M/group, ...] does not match the input channels");
+    g.M = tr ? w.shape[1] * g.groups : w.shape[0];
+    Q3_CHECK(!c.has(2) || b.numel() == g.M, op + ": bias length does not match the output channels");
+    for (auto pv : pads) Q3_CHECK(pv >= 0, op + ": negative padding");
+    std::vector<int64_t> pb(2, 0), pe(2, 0);
+    if (!pads.empty()) { if (sp == 1) { pb[1] = pads[0]; pe[1] = pads[1]; } else { pb[0] = pads[0]; pb[1] = pads[1]; pe[0] = pads[2]; pe[1] = pads[3]; } }
+    const std::string ap = c.as("auto_pad", "NOTSET");
+    const std::vector<int64_t> opad = two(tr ? c.aints("output_padding") : std::vector<int64_t>(), 0, 0);
+    std::vector<int64_t> oshape = tr ? c.aints("output_shape") : std::vector<int64_t>();
+    if (!oshape.empty()) oshape = two(oshape, 1, 1);
+    Q3_CHECK(opad.size() == 2 && (oshape.empty() || oshape.size() == 2), op + ": output_padding / output_shape do not match the spatial rank");
+    const int64_t in_sp[2] = {g.H, g.W};
+    ConvDim O[2];
+    for (size_t d = 0; d < 2; d++)
+        O[d] = tr ? convtr_dim(in_sp[d], ks[d], strides[d], dil[d], pb[d], pe[d], opad[d], !oshape.empty(), oshape.empty() ? 0 : oshape[d], ap) : conv_dim(in_sp[d], ks[d], strides[d], dil[d], pb[d], pe[d], ap);
+    g.ph = O[0].pb; g.pw = O[1].pb; g.OH = O[0].out; g.OW = O[1].out;
+    Q3_CHECK(g.OH >= 0 && g.OW >= 0, "negative convolution output size");
+    std::vector<int64_t> os = {g.N, g.M};
+    if (sp == 2) os.push_back(g.OH);
+    os.push_back(g.OW);
+    XTensor o = I.dev_tensor(1, os);
+    const int64_t n = o.numel();
+    if (n) {
+        const float* bias = c.has(2) ? I.f(b) : nullptr;
+        const bool one_d = sp == 1 && g.groups == 1 && g.W < (1 << 30) && g.OW < (1 << 30) && g.sw < (1 << 20) && g.pw < (1 << 30) && g.dw < (1 << 20) && g.kw < (1 << 20);
+        if (!tr && one_d && mm_fast_ok(g.M, g.OW, g.C * g.kw, g.N)) {
+            // implicit GEMM: W[M][C * kw] x im2col(x)[C * kw][OW] per batch element; the NCW output is the product's row-major layout
+            MmFast f{};
+            f.M = (int)g.M; f.N = (int)g.OW; f.K = (int)(g.C * g.kw); f.a_b = 0; f.a_m = g.C * g.kw; f.a_k = 1; f.b_b = g.C * g.W;
+            f.conv = 1; f.kw = (int)g.kw; f.cs = (int)g.sw; f.cp = (int)g.pw; f.cd = (int)g.dw; f.W = (int)g.W;
+            f.bias = bias; f.bias_m = 1; f.bias_n = 0; f.alpha = 1.f; f.beta = 1.f;
+            I.launch_mm_fast(I.f(o), I.f(w), I.f(x), f, g.N);
+        } else if (tr && one_d && mm_fast_ok(g.M * g.kw, g.W, g.C, g.N)) {
+            // Y[b][m * kw + k][i] = sum_c w[c][m][k] x[b][c][i] (the weight tensor read as its own transpose), then the taps are overlap-added
+            XTensor y = I.dev_tensor(1, {g.N, g.M * g.kw, g.W});
+            MmFast f{};
+            f.M = (int)(g.M * g.kw); f.N = (int)g.W; f.K = (int)g.C; f.a_b = 0; f.a_m = 1; f.a_k = g.M * g.kw; f.b_b = g.C * g.W; f.b_k = g.W; f.b_n = 1;
+            f.alpha = 1.f; f.beta = 0.f;
+            I.launch_mm_fast(I.f(y), I.f(w), I.f(x), f, g.N);
+            I.launch(n, k_col2im1d, I.f(o), I.f(y), bias, g.M, g.OW, g.W, (int)g.kw, (int)g.sw, (int)g.pw, (int)g.dw, n);
+        } else I.launch(n, tr ? k_convtr2d : k_conv2d, I.f(o), I.f(x), I.f(w), bias, g, n);
+    }
+    c.out(0, o);
+}
+static void op_pad(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0));
+    const int rank = (int)x.shape.size();
+    std::vector<int64_t> pads = c.has(1) ? c.ints(1) : c.aints("pads");
+    float value = c.af("value", 0.f);
+    if (c.has(2)) value = (float)I.to_host(c.in(2)).hv.at(0);
+    std::vector<int64_t> axes;
+    if (c.has(3)) axes = c.ints(3); else for (int d = 0; d < rank; d++) axes.push_back(d);
+    Q3_CHECK(pads.size() == 2 * axes.size(), "Pad: pads do not match the axes");
+    const std::string mode = c.as("mode", "constant");
+    PadArgs p{}; p.rank = rank; p.mode = mode == "constant" ? 0 : mode == "reflect" ? 1 : mode == "edge" ? 2 : -1; p.value = value;
+    Q3_CHECK(p.mode >= 0, "Pad mode " + mode);
+    Q3_CHECK(rank <= XR, "Pad: rank above 8 (rank " + std::to_string(rank) + ")");
+    std::vector<int64_t> os = x.shape;
+    for (int d = 0; d < rank; d++) { p.ishape[d] = x.shape[(size_t)d]; p.begin[d] = 0; }
+    for (size_t i = 0; i < axes.size(); i++) { const int64_t a = axis_of(axes[i], rank, "Pad"); p.begin[a] = pads[i]; os[(size_t)a] += pads[i] + pads[i + axes.size()]; }
+    for (int d = 0; d < rank; d++) p.oshape[d] = os[(size_t)d];
+    XTensor o = I.dev_tensor(1, os);
+    I.launch(o.numel(), k_pad, I.f(o), I.f(x), p, o.numel());
+    c.out(0, o);
+}
+static void op_trilu(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0));
+    Q3_CHECK(x.shape.size() >= 2, "Trilu needs a matrix");
+    const int64_t k2 = c.has(1) ? c.ints(1).at(0) : 0, rows = x.shape[x.shape.size() - 2], cols = x.shape.back(), n = x.numel();
+    XTensor o = I.dev_tensor(c.in(0).dtype == 9 ? 9 : 1, x.shape);
+    I.launch(n, k_trilu, I.f(o), I.f(x), rows, cols, k2, (int)c.ai("upper", 1), n);
+    c.out(0, c.in(0).dtype == 7 ? I.as_i64(o) : o);
+}
+static void op_gather_elements(NodeCtx& c) {
+    Exec& I = c.I;
+    const int64_t a = c.axis("axis", 0, c.in(0).shape.size());
+    const XTensor x = I.to_device(c.in(0)), idx = I.as_i64(c.in(1));
+    Q3_CHECK(idx.shape.size() == x.shape.size(), "GatherElements: rank mismatch");
+    for (size_t d = 0; d < x.shape.size(); d++) Q3_CHECK((int64_t)d == a || idx.shape[d] == x.shape[d], "GatherElements: indices must match the data outside the axis");
+    const int64_t inner = prod(x.shape, (size_t)a + 1), nj = idx.shape[(size_t)a], n = idx.numel();
+    XTensor o = I.dev_tensor(x.dtype, idx.shape);
+    Exec::by_dtype(x.dtype, [&](auto* tag) { using T = std::remove_pointer_t<decltype(tag)>; I.launch(n, k_gather_elems<T>, I.ptr<T>(o), I.ptr<T>(x), I.i64(idx), nj, x.shape[(size_t)a], inner, n); });
+    c.out(0, o);
+}
+static void op_scatter_nd(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0)), upd = I.as_f32(c.in(2));
+    const XTensor ih = I.to_host(c.in(1)); // index tuples are small (cache positions): evaluated on the host into slice offsets
+    Q3_CHECK(c.as("reduction", "none") == "none", "ScatterND with a reduction");
+    const int64_t kdim = ih.shape.back(), nup = kdim ? ih.numel() / kdim : 0;
+    Q3_CHECK(kdim >= 1 && kdim <= (int64_t)x.shape.size(), "ScatterND index depth");
+    const int64_t slice = prod(x.shape, (size_t)kdim);
+    const auto st = strides_of(x.shape);
+    std::vector<double> offs((size_t)nup);
+    for (int64_t u = 0; u < nup; u++) {
+        int64_t off = 0;
+        for (int64_t d = 0; d < kdim; d++) { int64_t v = (int64_t)ih.hv[(size_t)(u * kdim + d)]; if (v < 0) v += x.shape[(size_t)d]; Q3_CHECK(v >= 0 && v < x.shape[(size_t)d], "ScatterND index out of range"); off += v * st[(size_t)d]; }
+        offs[(size_t)u] = (double)(off / std::max<int64_t>(slice, 1));
+    }
+    XTensor o = I.dev_tensor(1, x.shape);
+    if (x.numel()) Q3_HIP(hipMemcpyAsync(o.dev->p, x.dev->p, (size_t)x.numel() * 4, hipMemcpyDeviceToDevice, 0)); // a copy, not a launch: not counted
+    const int64_t n = nup * slice;
+    if (n) {
+        XTensor od = I.to_device(Exec::host_tensor(7, {nup}, offs));
+        I.launch(n, k_scatter_rows, I.f(o), I.f(upd), I.i64(od), slice, n);
+    }
+    c.out(0, o);
+}
+static void op_resize(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0));
+    Q3_CHECK(c.as("mode", "nearest") == "nearest", "Resize: only nearest is implemented");
+    const int rank = (int)x.shape.size();
+    ResizeArgs a{}; a.rank = rank;
+    std::vector<int64_t> os = x.shape;
+    Q3_CHECK(rank >= 1 && rank <= XR, "Resize: rank out of range (rank " + std::to_string(rank) + ")");
+    const bool old_layout = I.opset < 11; // opset 10: inputs (X, scales); opset >= 11: (X, roi, scales, sizes)
+    if (!old_layout && c.has(3)) {
+        os = c.ints(3);
+        Q3_CHECK((int)os.size() == rank, "Resize sizes rank");
+        for (int d = 0; d < rank; d++) { Q3_CHECK(x.shape[(size_t)d] > 0 && os[(size_t)d] >= 0, "Resize: empty input extent"); a.scale[d] = (float)os[(size_t)d] / (float)x.shape[(size_t)d]; }
+    } else {
+        const int si = old_layout ? 1 : 2;
+        Q3_CHECK(c.has(si), "Resize needs scales or sizes");
+        const XTensor sc = I.to_host(c.in(si));
+        Q3_CHECK((int)sc.hv.size() == rank, "Resize scales rank");
+        for (int d = 0; d < rank; d++) { Q3_CHECK(sc.hv[(size_t)d] > 0, "Resize: scales must be positive"); a.scale[d] = (float)sc.hv[(size_t)d]; os[(size_t)d] = (int64_t)std::floor((double)x.shape[(size_t)d] * sc.hv[(size_t)d]); }
+    }
+    const std::string ctm = c.as("coordinate_transformation_mode", old_layout ? "asymmetric" : "half_pixel"), nm = c.as("nearest_mode", old_layout ? "floor" : "round_prefer_floor");
+    bool whole = true;
+    for (int d = 0; d < rank; d++) whole = whole && a.scale[d] >= 1.0f && a.scale[d] == std::floor(a.scale[d]);
+    Q3_CHECK(resize_mode_ok(ctm, nm, whole), "Resize: coordinate_transformation_mode=" + ctm + " nearest_mode=" + nm + " is only implemented for whole-number up-scaling");
+    for (int d = 0; d < rank; d++) { a.oshape[d] = os[(size_t)d]; a.ishape[d] = x.shape[(size_t)d]; }
+    XTensor o = I.dev_tensor(1, os);
+    I.launch(o.numel(), k_resize_nearest, I.f(o), I.f(x), a, o.numel());
+    c.out(0, o);
+}
+static void op_group_norm(NodeCtx& c) {
+    Exec& I = c.I;
+    const XTensor x = I.as_f32(c.in(0)), g = I.as_f32(c.in(1)), b = I.as_f32(c.in(2));
+    const int64_t G = c.ai("num_groups", 1), C = x.shape.at(1), sp = prod(x.shape, 2);
+    Q3_CHECK(G > 0 && C % G == 0, "GroupNormalization groups");
+    const int64_t rows = x.shape.at(0) * G, cols = (C / G) * sp;
+    Q3_CHECK((g.numel() == C || g.numel() == G) && b.numel() == g.numel(), "GroupNormalization: scale / bias length is neither the channels nor the groups");
+    XTensor nrm = I.dev_tensor(1, x.shape);
+    I.launch(grid_rows(rows, cols), k_norm_rows, I.f(nrm), I.f(x), nullptr, nullptr, cols, c.af("epsilon", 1e-5f), 0, 1);
+    // per-channel affine (opset 21 form; opset 18 files carry per-group scale / bias of length G)
+    std::vector<int64_t> bs(x.shape.size(), 1); bs[1] = g.numel() == C ? C : G;
+    XTensor y = nrm;
+    if (g.numel() == C) { y = I.binary(B_MUL, nrm, I.reshaped(g, bs), 1); y = I.binary(B_ADD, y, I.reshaped(b, bs), 1); }
+    else { std::vector<int64_t> gs = {x.shape[0], G, C / G}; gs.insert(gs.end(), x.shape.begin() + 2, x.shape.end()); std::vector<int64_t> gb(gs.size(), 1); gb[1] = G;
+           y = I.binary(B_ADD, I.binary(B_MUL, I.reshaped(nrm, gs), I.reshaped(g, gb), 1), I.reshaped(b, gb), 1); y = I.reshaped(y, x.shape); }
+    c.out(0, y);
+}
+static void op_lp_norm(NodeCtx& c) {
+    Exec& I = c.I;
+    const int64_t a = c.axis("axis", -1, c.in(0).shape.size());
+    const XTensor x = I.as_f32(c.in(0));
+    const int64_t p2 = c.ai("p", 2);
+    Q3_CHECK(p2 == 1 || p2 == 2, "LpNormalization p");
+    int64_t rows, cols;
+    XTensor perm = I.axes_last(x, {a}, rows, cols);
+    std::vector<int64_t> ks = x.shape; ks[(size_t)a] = 1;
+    XTensor nm = I.dev_tensor(1, ks);
+    I.launch(grid_rows(rows), k_reduce_rows, I.f(nm), nullptr, I.f(perm), p2 == 2 ? R_L2 : R_L1, cols, 0);
+    c.out(0, I.binary(B_DIV, x, nm, 1));
+}
+
+// The supported set: an operator is executable exactly when it has a row here.  To add one, write its handler above and give it a row.
+static const OpEntry op_table[] = {
+    {"Relu", op_unary, U_RELU}, {"Sigmoid", op_unary, U_SIGMOID}, {"Tanh", op_unary, U_TANH}, {"Exp", op_unary, U_EXP}, {"Log", op_unary, U_LOG}, {"Sqrt", op_unary, U_SQRT},
+    {"Reciprocal", op_unary, U_RECIP}, {"Neg", op_unary, U_NEG}, {"Abs", op_unary, U_ABS}, {"Sin", op_unary, U_SIN}, {"Cos", op_unary, U_COS}, {"Erf", op_unary, U_ERF},
+    {"Floor", op_unary, U_FLOOR}, {"Ceil", op_unary, U_CEIL}, {"Round", op_unary, U_ROUND}, {"Sign", op_unary, U_SIGN}, {"Elu", op_unary, U_ELU}, {"LeakyRelu", op_unary, U_LEAKY},
+    {"HardSigmoid", op_unary, U_HSIG}, {"Gelu", op_unary, U_GELU}, {"Softplus", op_unary, U_SOFTPLUS}, {"Selu", op_unary, U_SELU}, {"Not", op_unary, U_NOT}, {"Softsign", op_unary, U_SOFTSIGN},
+    {"HardSwish", op_unary, U_HSWISH}, {"IsNaN", op_unary, U_ISNAN}, {"Celu", op_unary, U_CELU}, {"ThresholdedRelu", op_unary, U_THRELU}, {"Mish", op_unary, U_MISH}, {"Tan", op_unary, U_TAN},
+    {"Atan", op_unary, U_ATAN}, {"Sinh", op_unary, U_SINH}, {"Cosh", op_unary, U_COSH},
+    {"Add", op_binary, B_ADD}, {"Sub", op_binary, B_SUB}, {"Mul", op_binary, B_MUL}, {"Div", op_binary, B_DIV}, {"Pow", op_binary, B_POW}, {"Min", op_binary, B_MIN}, {"Max", op_binary, B_MAX},
+    {"Equal", op_binary, B_EQ}, {"Less", op_binary, B_LT}, {"Greater", op_binary, B_GT}, {"LessOrEqual", op_binary, B_LE}, {"GreaterOrEqual", op_binary, B_GE}, {"And", op_binary, B_AND},
+    {"Or", op_binary, B_OR}, {"Xor", op_binary, B_XOR}, {"Mod", op_binary, B_MOD}, {"PRelu", op_binary, B_PRELU}, {"Sum", op_binary, B_ADD}, {"Mean", op_binary, B_ADD},
+    {"ReduceSum", op_reduce, R_SUM}, {"ReduceMean", op_reduce, R_MEAN}, {"ReduceMax", op_reduce, R_MAX}, {"ReduceMin", op_reduce, R_MIN}, {"ReduceProd", op_reduce, R_PROD},
+    {"ReduceL2", op_reduce, R_L2}, {"ReduceSumSquare", op_reduce, R_SUMSQ}, {"ReduceL1", op_reduce, R_L1}, {"ReduceLogSumExp", op_reduce, R_LOGSUMEXP}, {"ArgMax", op_reduce, R_ARGMAX},
+    {"ArgMin", op_reduce, R_ARGMIN},
+    {"Identity", op_identity, 0}, {"Dropout", op_identity, 0}, {"Reshape", op_reshape, 0}, {"Flatten", op_flatten, 0}, {"Squeeze", op_squeeze, 0}, {"Unsqueeze", op_squeeze, 1},
+    {"Transpose", op_transpose, 0}, {"Concat", op_concat, 0}, {"Slice", op_slice, 0}, {"Split", op_split, 0}, {"Gather", op_gather, 0}, {"Shape", op_shape, 0}, {"Size", op_size, 0},
+    {"Constant", op_constant, 0}, {"ConstantOfShape", op_constant_of_shape, 0}, {"Range", op_range, 0}, {"Cast", op_cast, 0}, {"Expand", op_expand, 0}, {"Tile", op_tile, 0},
+    {"Where", op_where, 0}, {"Clip", op_clip, 0}, {"Softmax", op_softmax, 0}, {"LogSoftmax", op_softmax, 1}, {"LayerNormalization", op_layer_norm, 0},
+    {"InstanceNormalization", op_instance_norm, 0}, {"BatchNormalization", op_batch_norm, 0}, {"MatMul", op_matmul, 0}, {"Gemm", op_matmul, 1}, {"Conv", op_conv, 0},
+    {"ConvTranspose", op_conv, 1}, {"Pad", op_pad, 0}, {"CumSum", op_cumsum, 0}, {"GlobalAveragePool", op_global_pool, R_MEAN}, {"GlobalMaxPool", op_global_pool, R_MAX},
+    {"Trilu", op_trilu, 0}, {"GatherElements", op_gather_elements, 0}, {"ScatterND", op_scatter_nd, 0}, {"Resize", op_resize, 0}, {"GroupNormalization", op_group_norm, 0},
+    {"LpNormalization", op_lp_norm, 0},
+};
+static const OpEntry* find_op(const std::string& name) {
+    static const std::map<std::string, const OpEntry*> by_name = [] {
+        std::map<std::string, const OpEntry*> m;
+        for (const OpEntry& e : op_table) { const bool fresh = m.emplace(e.name, &e).second; assert(fresh && "an operator appears twice in op_table"); (void)fresh; }
+        return m;
+    }();
+    auto it = by_name.find(name);
+    return it == by_name.end() ? nullptr : it->second;
+}
+bool onnx_exec_supports(const std::string& op) { return find_op(op) != nullptr; }
+
+// ================================================================ session ==============================================================
 OnnxSession::OnnxSession(const std::string& path, int device) : model_(new OnnxModel(path)), impl_(new Impl()), device_(device) {
     Q3_HIP(hipSetDevice(device_));
     impl_->launches = &launches_;
@@ -781,12 +1309,13 @@ OnnxSession::OnnxSession(const std::string& path, int device) : model_(new OnnxM
         // integer tensors and tiny float tensors (scalars, epsilons) stay on the host; weights go to HBM once
         impl_->consts[t.name] = (dtype == 7 || n <= 8) ? h : impl_->to_device(h);
     }
+    for (const auto& n : model_->nodes) impl_->entry.push_back(find_op(n.op_type)); // a node without a handler still opens: unsupported_ops() reports it, run() refuses it
 }
 OnnxSession::~OnnxSession() = default;
 
 std::vector<std::string> OnnxSession::unsupported_ops() const {
     std::set<std::string> s;
-    for (const auto& n : model_->nodes) if (!onnx_exec_supports(n.op_type)) s.insert(n.op_type);
+    for (size_t k = 0; k < model_->nodes.size(); k++) if (!impl_->entry[k]) s.insert(model_->nodes[k].op_type);
     return std::vector<std::string>(s.begin(), s.end());
 }
 
@@ -809,9 +1338,9 @@ XTensor OnnxSession::zeros(int dtype, const std::vector<int64_t>& shape) {
     return t;
 }
 const XTensor& OnnxSession::value(const std::string& name) const {
-    auto it = impl_->vals.find(name);
-    if (it == impl_->vals.end()) throw Error("no value named " + name + " (run() first; only graph outputs and live edges are kept)");
-    return it->second;
+    const XTensor* t = impl_->find(name);
+    if (!t) throw Error("no value named " + name + " (run() first; only graph outputs and live edges are kept)");
+    return *t;
 }
 void OnnxSession::fetch(const XTensor& t, void* dst, size_t cap) const {
     const size_t n = (size_t)t.numel();
@@ -831,7 +1360,6 @@ void OnnxSession::run() {
     Q3_HIP(hipSetDevice(device_));
     Impl& I = *impl_;
     I.vals.clear();
-    for (auto& kv : I.consts) I.vals[kv.first] = kv.second;
     for (const auto& vi : model_->inputs) {
         if (I.consts.count(vi.name)) continue; // initialisers listed as inputs (older exporters)
         auto it = I.inputs.find(vi.name);
@@ -846,655 +1374,21 @@ void OnnxSession::run() {
     for (size_t k = 0; k < model_->nodes.size(); k++) {
         const OnnxNode& nd = model_->nodes[k];
         try {
-            auto has = [&](size_t i) { return i < nd.inputs.size() && !nd.inputs[i].empty(); };
-            auto in = [&](size_t i) -> const XTensor& {
-                Q3_CHECK(has(i), "missing input " + std::to_string(i));
-                auto it = I.vals.find(nd.inputs[i]);
-                if (it == I.vals.end()) throw Error("input " + nd.inputs[i] + " has no producer");
-                return it->second;
-            };
-            auto ai = [&](const char* n, int64_t d) { auto* a = nd.attr(n); return a ? a->i : d; };
-            auto af = [&](const char* n, float d) { auto* a = nd.attr(n); return a ? a->f : d; };
-            auto as = [&](const char* n, const char* d) { auto* a = nd.attr(n); return a ? a->s : std::string(d); };
-            auto aints = [&](const char* n) { auto* a = nd.attr(n); return a ? a->ints : std::vector<int64_t>(); };
-            auto out = [&](size_t i, XTensor t) { if (i < nd.outputs.size() && !nd.outputs[i].empty()) I.vals[nd.outputs[i]] = std::move(t); };
-            const std::string& op = nd.op_type;
-
-            if (unary_table().count(op)) {
-                int u = unary_table().at(op);
-                float a = 0.f, b = 0.f;
-                if (op == "Elu") a = af("alpha", 1.0f);
-                else if (op == "LeakyRelu") a = af("alpha", 0.01f);
-                else if (op == "HardSigmoid") { a = af("alpha", 0.2f); b = af("beta", 0.5f); }
-                else if (op == "Selu") { a = af("alpha", 1.67326319217681884765625f); b = af("gamma", 1.05070102214813232421875f); }
-                else if (op == "Gelu" && as("approximate", "none") == "tanh") u = U_GELU_TANH;
-                else if (op == "Celu") a = af("alpha", 1.0f);
-                else if (op == "ThresholdedRelu") a = af("alpha", 1.0f);
-                out(0, I.unary(u, in(0), a, b));
-            } else if (binary_table().count(op)) {
-                int b = binary_table().at(op);
-                if (op == "Mod" && ai("fmod", 0)) b = B_FMOD;
-                const bool cmp = b == B_EQ || b == B_LT || b == B_GT || b == B_LE || b == B_GE || b == B_AND || b == B_OR || b == B_XOR;
-                XTensor acc = in(0);
-                for (size_t i = 1; i < nd.inputs.size(); i++) {
-                    const XTensor& y = in(i);
-                    const int od = cmp ? 9 : (acc.dtype == 7 && y.dtype == 7) ? 7 : 1;
-                    acc = I.binary(b, acc, y, od);
-                }
-                if (op == "Mean" && nd.inputs.size() > 1) acc = I.binary(B_DIV, acc, Impl::host_tensor(1, {}, {(double)nd.inputs.size()}), 1);
-                out(0, acc);
-            } else if (op == "Identity" || op == "Dropout") {
-                out(0, in(0));
-            } else if (op == "Shape") {
-                const auto& s = in(0).shape;
-                int64_t b = ai("start", 0), e = ai("end", (int64_t)s.size());
-                if (b < 0) b += (int64_t)s.size();
-                if (e < 0) e += (int64_t)s.size();
-                b = std::max<int64_t>(0, std::min<int64_t>(b, (int64_t)s.size())); e = std::max<int64_t>(b, std::min<int64_t>(e, (int64_t)s.size()));
-                std::vector<double> v; for (int64_t i = b; i < e; i++) v.push_back((double)s[(size_t)i]);
-                out(0, Impl::host_tensor(7, {(int64_t)v.size()}, v));
-            } else if (op == "Size") {
-                out(0, Impl::host_tensor(7, {}, {(double)in(0).numel()}));
-            } else if (op == "Constant") {
-                if (auto* a = nd.attr("value")) {
-                    const OnnxTensor& t = a->t;
-                    int dtype = 1;
-                    std::vector<double> v = tensor_values(t, "Constant " + nd.name, &dtype);
-                    const int64_t n = (int64_t)v.size();
-                    XTensor h = Impl::host_tensor(dtype, t.dims, std::move(v));
-                    out(0, (dtype == 7 || n <= 4096) ? h : I.to_device(h));
-                } else if (auto* a2 = nd.attr("value_float")) out(0, Impl::host_tensor(1, {}, {(double)a2->f}));
-                else if (auto* a3 = nd.attr("value_int")) out(0, Impl::host_tensor(7, {}, {(double)a3->i}));
-                else if (auto* a4 = nd.attr("value_ints")) { std::vector<double> v(a4->ints.begin(), a4->ints.end()); out(0, Impl::host_tensor(7, {(int64_t)v.size()}, v)); }
-                else if (auto* a5 = nd.attr("value_floats")) { std::vector<double> v(a5->floats.begin(), a5->floats.end()); out(0, Impl::host_tensor(1, {(int64_t)v.size()}, v)); }
-                else throw Error("Constant without a supported value attribute");
-            } else if (op == "ConstantOfShape") {
-                const auto shape = I.ints_of(in(0));
-                double v = 0; int dtype = 1;
-                if (auto* a = nd.attr("value")) {
-                    const OnnxTensor& t = a->t;
-                    const std::vector<double> tv = tensor_values(t, "ConstantOfShape " + nd.name + " value", &dtype);
-                    Q3_CHECK(tv.size() >= 1, "ConstantOfShape " + nd.name + ": empty value tensor");
-                    v = tv[0];
-                }
-                const int64_t n = prod(shape);
-                if (n <= 65536) out(0, Impl::host_tensor(dtype, shape, std::vector<double>((size_t)n, v)));
-                else { XTensor o = I.dev_tensor(dtype == 7 ? 1 : dtype, shape); hipLaunchKernelGGL(k_fill, grid1(n), dim3(256), 0, 0, I.f(o), (float)v, n); I.count(); out(0, dtype == 7 ? I.as_i64(o) : o); }
-            } else if (op == "Range") {
-                const XTensor s = I.to_host(in(0)), l = I.to_host(in(1)), d = I.to_host(in(2));
-                const double st = s.hv.at(0), li = l.hv.at(0), de = d.hv.at(0);
-                const int64_t n = std::max<int64_t>(0, (int64_t)std::ceil((li - st) / de));
-                std::vector<double> v((size_t)n);
-                for (int64_t i = 0; i < n; i++) v[(size_t)i] = st + (double)i * de;
-                out(0, Impl::host_tensor(s.dtype, {n}, v));
-            } else if (op == "Cast") {
-                const int64_t to = ai("to", 1);
-                const XTensor& x = in(0);
-                // f64 (11) is carried as f32 (documented precision loss); f16 / bf16 / string targets would need a rounding pass this executor does not have
-                Q3_CHECK(to == 1 || to == 11 || to == 7 || to == 6 || to == 2 || to == 3 || to == 5 || to == 12 || to == 13 || to == 9,
-                         "Cast to element type " + std::to_string(to) + " is not supported (tensors are f32 / i64 / bool on this executor)");
-                const int dt = (to == 7 || to == 6 || to == 2 || to == 3 || to == 5 || to == 12 || to == 13) ? 7 : to == 9 ? 9 : 1;
-                if (x.on_host) {
-                    XTensor o = x; o.dtype = dt;
-                    if (dt == 7) for (auto& v : o.hv) v = std::trunc(v);
-                    else if (dt == 9) for (auto& v : o.hv) v = v != 0 ? 1 : 0;
-                    else for (auto& v : o.hv) v = (double)(float)v;
-                    out(0, o);
-                } else if (dt == 7) out(0, I.as_i64(x));
-                else if (dt == 9) { XTensor z = Impl::host_tensor(1, {}, {0.0}); XTensor e = I.binary(B_EQ, x, z, 9); out(0, I.unary(U_NOT, e, 0, 0)); }
-                else { XTensor o = I.as_f32(x); o.dtype = 1; out(0, o); }
-            } else if (op == "Reshape") {
-                const XTensor& x = in(0);
-                auto shape = I.ints_of(in(1));
-                const bool allowzero = ai("allowzero", 0) != 0;
-                int64_t known = 1; int neg = -1;
-                for (size_t d = 0; d < shape.size(); d++) {
-                    if (shape[d] == 0 && !allowzero) { Q3_CHECK(d < x.shape.size(), "Reshape: 0 beyond the input rank"); shape[d] = x.shape[d]; }
-                    if (shape[d] == -1) neg = (int)d; else known *= shape[d];
-                }
-                if (neg >= 0) shape[(size_t)neg] = known ? x.numel() / known : 0;
-                out(0, I.reshaped(x, shape));
-            } else if (op == "Flatten") {
-                const XTensor& x = in(0);
-                int64_t a = ai("axis", 1); if (a < 0) a += (int64_t)x.shape.size();
-                out(0, I.reshaped(x, {prod(x.shape, 0, (size_t)a), prod(x.shape, (size_t)a)}));
-            } else if (op == "Squeeze" || op == "Unsqueeze") {
-                const XTensor& x = in(0);
-                std::vector<int64_t> axes = has(1) ? I.ints_of(in(1)) : aints("axes");
-                std::vector<int64_t> s;
-                if (op == "Squeeze") {
-                    if (axes.empty()) { for (auto d : x.shape) if (d != 1) s.push_back(d); }
-                    else { axes = I.norm_axes(axes, (int)x.shape.size()); for (size_t d = 0; d < x.shape.size(); d++) if (!std::binary_search(axes.begin(), axes.end(), (int64_t)d)) s.push_back(x.shape[d]); }
-                } else {
-                    const int r = (int)(x.shape.size() + axes.size());
-                    axes = I.norm_axes(axes, r);
-                    size_t src = 0;
-                    for (int d = 0; d < r; d++) s.push_back(std::binary_search(axes.begin(), axes.end(), (int64_t)d) ? 1 : x.shape[src++]);
-                }
-                out(0, I.reshaped(x, s));
-            } else if (op == "Transpose") {
-                const XTensor& x = in(0);
-                std::vector<int64_t> perm = aints("perm");
-                if (perm.empty()) for (int d = (int)x.shape.size() - 1; d >= 0; d--) perm.push_back(d);
-                out(0, I.transpose(x, perm));
-            } else if (op == "Expand") {
-                const XTensor& x = in(0);
-                out(0, I.expand(x, bshape(x.shape, I.ints_of(in(1)))));
-            } else if (op == "Tile") {
-                const XTensor& x = in(0);
-                const auto rep = I.ints_of(in(1));
-                Q3_CHECK(rep.size() == x.shape.size(), "Tile: repeats has " + std::to_string(rep.size()) + " entries for a rank-" + std::to_string(x.shape.size()) + " tensor");
-                std::vector<int64_t> os(x.shape.size());
-                for (size_t d = 0; d < os.size(); d++) { Q3_CHECK(rep[d] >= 0 && rep[d] <= (1 << 24), "Tile: repeat count out of range"); os[d] = x.shape[d] * rep[d]; }
-                std::vector<int64_t> mod = x.shape; for (auto& m : mod) m = std::max<int64_t>(m, 1);
-                out(0, I.nd_copy(x, os, strides_of(x.shape), mod, 0));
-            } else if (op == "Slice") {
-                const XTensor& x = in(0);
-                const int r = (int)x.shape.size();
-                std::vector<int64_t> starts, ends, axes, steps;
-                if (has(1)) { starts = I.ints_of(in(1)); ends = I.ints_of(in(2)); if (has(3)) axes = I.ints_of(in(3)); if (has(4)) steps = I.ints_of(in(4)); }
-                else { starts = aints("starts"); ends = aints("ends"); axes = aints("axes"); }
-                if (axes.empty()) for (size_t i = 0; i < starts.size(); i++) axes.push_back((int64_t)i);
-                if (steps.empty()) steps.assign(starts.size(), 1);
-                std::vector<int64_t> os = x.shape, st = strides_of(x.shape), is = st;
-                int64_t off = 0;
-                for (size_t i = 0; i < starts.size(); i++) {
-                    int64_t a = axes[i]; if (a < 0) a += r;
-                    const int64_t dim = x.shape[(size_t)a], step = steps[i];
-                    Q3_CHECK(step != 0, "Slice step 0");
-                    int64_t s = starts[i], e = ends[i];
-                    if (s < 0) s += dim;
-                    if (e < 0) e += dim;
-                    if (step > 0) { s = std::max<int64_t>(0, std::min(s, dim)); e = std::max<int64_t>(0, std::min(e, dim)); }
-                    else { s = std::max<int64_t>(0, std::min(s, dim - 1)); e = std::max<int64_t>(-1, std::min(e, dim - 1)); if (ends[i] < -dim) e = -1; }
-                    const int64_t cnt = step > 0 ? std::max<int64_t>(0, (e - s + step - 1) / step) : std::max<int64_t>(0, (s - e + (-step) - 1) / (-step));
-                    os[(size_t)a] = cnt; is[(size_t)a] = st[(size_t)a] * step; off += s * st[(size_t)a];
-                }
-                out(0, I.nd_copy(x, os, is, Impl::nomod(os.size()), off));
-            } else if (op == "Split") {
-                const XTensor& x = in(0);
-                int64_t a = ai("axis", 0); if (a < 0) a += (int64_t)x.shape.size();
-                Q3_CHECK(a >= 0 && a < (int64_t)x.shape.size(), "Split: axis out of range");
-                std::vector<int64_t> sizes = has(1) ? I.ints_of(in(1)) : aints("split");
-                { int64_t tot = 0; for (auto z : sizes) { Q3_CHECK(z >= 0, "Split: negative size"); tot += z; } Q3_CHECK(sizes.empty() || tot == x.shape[(size_t)a], "Split: sizes do not add up to the axis length"); }
-                Q3_CHECK(sizes.empty() || sizes.size() <= nd.outputs.size(), "Split: more sizes than outputs");
-                if (sizes.empty()) {
-                    const int64_t parts = (int64_t)nd.outputs.size(), dim = x.shape[(size_t)a], each = (dim + parts - 1) / parts;
-                    for (int64_t i = 0; i < parts; i++) sizes.push_back(std::min(each, dim - i * each));
-                }
-                const auto st = strides_of(x.shape);
-                int64_t at = 0;
-                for (size_t i = 0; i < sizes.size(); i++) {
-                    std::vector<int64_t> os = x.shape; os[(size_t)a] = sizes[i];
-                    out(i, I.nd_copy(x, os, st, Impl::nomod(os.size()), at * st[(size_t)a]));
-                    at += sizes[i];
-                }
-            } else if (op == "Concat") {
-                const int r = (int)in(0).shape.size();
-                int64_t a = ai("axis", 0); if (a < 0) a += r;
-                Q3_CHECK(a >= 0 && a < r, "Concat: axis out of range");
-                for (size_t i = 1; i < nd.inputs.size(); i++) {
-                    Q3_CHECK((int)in(i).shape.size() == r, "Concat: input " + std::to_string(i) + " (" + nd.inputs[i] + ") has rank " + std::to_string(in(i).shape.size()) + ", input 0 (" + nd.inputs[0] + ") rank " + std::to_string(r));
-                    for (int d = 0; d < r; d++) Q3_CHECK(d == a || in(i).shape[(size_t)d] == in(0).shape[(size_t)d], "Concat: inputs differ off the concatenation axis");
-                }
-                bool all_host = true; int dtype = in(0).dtype; int64_t total = 0;
-                for (size_t i = 0; i < nd.inputs.size(); i++) { all_host = all_host && in(i).on_host; total += in(i).shape.at((size_t)a); if (in(i).dtype != 7) dtype = in(i).dtype == 9 && dtype == 9 ? 9 : 1; }
-                std::vector<int64_t> os = in(0).shape; os[(size_t)a] = total;
-                const int64_t inner = prod(os, (size_t)a + 1), outer = prod(os, 0, (size_t)a);
-                if (all_host) {
-                    XTensor o = Impl::host_tensor(dtype, os, std::vector<double>((size_t)prod(os)));
-                    int64_t at = 0;
-                    for (size_t i = 0; i < nd.inputs.size(); i++) {
-                        const XTensor& t = in(i); const int64_t part = t.shape[(size_t)a];
-                        for (int64_t o_ = 0; o_ < outer; o_++) for (int64_t p = 0; p < part; p++) for (int64_t q = 0; q < inner; q++)
-                            o.hv[(size_t)((o_ * total + at + p) * inner + q)] = t.hv[(size_t)((o_ * part + p) * inner + q)];
-                        at += part;
-                    }
-                    out(0, o);
-                } else {
-                    XTensor o = I.dev_tensor(dtype, os);
-                    int64_t at = 0;
-                    for (size_t i = 0; i < nd.inputs.size(); i++) {
-                        XTensor t = dtype == 7 ? I.as_i64(in(i)) : I.as_f32(in(i));
-                        const int64_t part = t.shape[(size_t)a], n = t.numel();
-                        if (n) {
-                            if (dtype == 7) hipLaunchKernelGGL(k_concat<int64_t>, grid1(n), dim3(256), 0, 0, I.i64(o), I.i64(t), part, inner, total, at, n);
-                            else hipLaunchKernelGGL(k_concat<float>, grid1(n), dim3(256), 0, 0, I.f(o), I.f(t), part, inner, total, at, n);
-                            I.count();
-                        }
-                        at += part;
-                    }
-                    out(0, o);
-                }
-            } else if (op == "Gather") {
-                const XTensor& x = in(0); const XTensor& idx = in(1);
-                int64_t a = ai("axis", 0); if (a < 0) a += (int64_t)x.shape.size();
-                Q3_CHECK(a >= 0 && a < (int64_t)x.shape.size(), "Gather: axis out of range");
-                const int64_t dim = x.shape.at((size_t)a), inner = prod(x.shape, (size_t)a + 1), outer = prod(x.shape, 0, (size_t)a), nidx = idx.numel();
-                std::vector<int64_t> os(x.shape.begin(), x.shape.begin() + a);
-                os.insert(os.end(), idx.shape.begin(), idx.shape.end());
-                os.insert(os.end(), x.shape.begin() + a + 1, x.shape.end());
-                if (x.on_host && idx.on_host) {
-                    XTensor o = Impl::host_tensor(x.dtype, os, std::vector<double>((size_t)prod(os)));
-                    for (int64_t o_ = 0; o_ < outer; o_++) for (int64_t j = 0; j < nidx; j++) {
-                        int64_t k2 = (int64_t)idx.hv[(size_t)j]; if (k2 < 0) k2 += dim;
-                        Q3_CHECK(k2 >= 0 && k2 < dim, "Gather index out of range");
-                        for (int64_t q = 0; q < inner; q++) o.hv[(size_t)((o_ * nidx + j) * inner + q)] = x.hv[(size_t)((o_ * dim + k2) * inner + q)];
-                    }
-                    out(0, o);
-                } else {
-                    XTensor xd = I.to_device(x), id = I.as_i64(idx);
-                    XTensor o = I.dev_tensor(xd.dtype, os);
-                    const int64_t n = o.numel();
-                    if (n) {
-                        if (xd.dtype == 7) hipLaunchKernelGGL(k_gather<int64_t>, grid1(n), dim3(256), 0, 0, I.i64(o), I.i64(xd), I.i64(id), nidx, dim, inner, n);
-                        else hipLaunchKernelGGL(k_gather<float>, grid1(n), dim3(256), 0, 0, I.f(o), I.f(xd), I.i64(id), nidx, dim, inner, n);
-                        I.count();
-                    }
-                    out(0, o);
-                }
-            } else if (op == "Where") {
-                const XTensor& c = in(0); const XTensor& a = in(1); const XTensor& b = in(2);
-                const auto os = bshape(bshape(c.shape, a.shape), b.shape);
-                const int64_t n = prod(os);
-                const int dtype = (a.dtype == 7 && b.dtype == 7) ? 7 : (a.dtype == 9 && b.dtype == 9) ? 9 : 1;
-                if (c.on_host && a.on_host && b.on_host) {
-                    XTensor o = Impl::host_tensor(dtype, os, std::vector<double>((size_t)n));
-                    const auto cs = bstrides(c.shape, os), as_ = bstrides(a.shape, os), bs = bstrides(b.shape, os);
-                    for (int64_t i = 0; i < n; i++) {
-                        int64_t r = i, co = 0, ao = 0, bo = 0;
-                        for (int d = (int)os.size() - 1; d >= 0; d--) { const int64_t q = r / os[d], x = r - q * os[d]; co += x * cs[d]; ao += x * as_[d]; bo += x * bs[d]; r = q; }
-                        o.hv[(size_t)i] = c.hv[(size_t)co] != 0 ? a.hv[(size_t)ao] : b.hv[(size_t)bo];
-                    }
-                    out(0, o);
-                } else {
-                    Q3_CHECK(os.size() <= (size_t)XR, "Where: rank above 8 (rank " + std::to_string(os.size()) + ")");
-                    XTensor cd = I.as_f32(c), ad = dtype == 7 ? I.as_i64(a) : I.as_f32(a), bd = dtype == 7 ? I.as_i64(b) : I.as_f32(b);
-                    XTensor o = I.dev_tensor(dtype, os);
-                    if (n) {
-                        NdMap2 m{}; m.rank = (int)os.size();
-                        const auto cs = bstrides(cd.shape, os), as_ = bstrides(ad.shape, os), bs = bstrides(bd.shape, os);
-                        for (size_t d = 0; d < os.size(); d++) { m.oshape[d] = os[d]; m.as[d] = as_[d]; m.bs[d] = bs[d]; m.cs[d] = cs[d]; }
-                        if (dtype == 7) hipLaunchKernelGGL(k_where<int64_t>, grid1(n), dim3(256), 0, 0, I.i64(o), I.f(cd), I.i64(ad), I.i64(bd), m, n);
-                        else hipLaunchKernelGGL(k_where<float>, grid1(n), dim3(256), 0, 0, I.f(o), I.f(cd), I.f(ad), I.f(bd), m, n);
-                        I.count();
-                    }
-                    out(0, o);
-                }
-            } else if (op == "Clip") {
-                float lo = -std::numeric_limits<float>::infinity(), hi = std::numeric_limits<float>::infinity();
-                if (nd.attr("min")) lo = af("min", lo);
-                if (nd.attr("max")) hi = af("max", hi);
-                if (has(1)) lo = (float)I.to_host(in(1)).hv.at(0);
-                if (has(2)) hi = (float)I.to_host(in(2)).hv.at(0);
-                out(0, I.unary(U_CLIP, in(0), lo, hi));
-            } else if (reduce_table().count(op)) {
-                const int r = reduce_table().at(op);
-                const XTensor& x0 = in(0);
-                const int rank = (int)x0.shape.size();
-                const bool arg = r == R_ARGMAX || r == R_ARGMIN;
-                std::vector<int64_t> axes;
-                if (arg) axes = {ai("axis", 0)};
-                else if (has(1)) axes = I.ints_of(in(1));
-                else axes = aints("axes");
-                const bool keep = ai("keepdims", 1) != 0;
-                if (axes.empty() && !arg) {
-                    if (ai("noop_with_empty_axes", 0)) { out(0, x0); continue; }
-                    for (int d = 0; d < rank; d++) axes.push_back(d);
-                }
-                axes = I.norm_axes(axes, rank);
-                std::vector<int64_t> os;
-                for (int d = 0; d < rank; d++) { const bool red = std::binary_search(axes.begin(), axes.end(), (int64_t)d); if (!red) os.push_back(x0.shape[(size_t)d]); else if (keep) os.push_back(1); }
-                if (x0.on_host && (r == R_SUM || r == R_PROD || r == R_MAX || r == R_MIN || r == R_MEAN)) { // shape arithmetic (ReduceProd of a shape, ...)
-                    int64_t rows, cols;
-                    XTensor p = I.axes_last(x0, axes, rows, cols);
-                    XTensor o = Impl::host_tensor(x0.dtype, os, std::vector<double>((size_t)rows));
-                    for (int64_t i = 0; i < rows; i++) {
-                        double acc = r == R_PROD ? 1 : r == R_MAX ? -INFINITY : r == R_MIN ? INFINITY : 0;
-                        for (int64_t c = 0; c < cols; c++) { const double v = p.hv[(size_t)(i * cols + c)]; acc = r == R_PROD ? acc * v : r == R_MAX ? std::max(acc, v) : r == R_MIN ? std::min(acc, v) : acc + v; }
-                        o.hv[(size_t)i] = r == R_MEAN ? acc / (double)cols : acc;
-                    }
-                    out(0, o);
-                } else {
-                    int64_t rows, cols;
-                    XTensor p = I.axes_last(I.as_f32(x0), axes, rows, cols);
-                    XTensor o = I.dev_tensor(arg ? 7 : 1, os);
-                    if (rows) {
-                        Q3_CHECK(cols > 0, "reduction over an empty axis");
-                        hipLaunchKernelGGL(k_reduce_rows, dim3((unsigned)rows), dim3(256), 0, 0, arg ? nullptr : I.f(o), arg ? I.i64(o) : nullptr, I.f(p), r, cols, (int)ai("select_last_index", 0));
-                        I.count();
-                    }
-                    out(0, o);
-                }
-            } else if (op == "Softmax" || op == "LogSoftmax") {
-                const XTensor x = I.as_f32(in(0));
-                const int rank = (int)x.shape.size();
-                int64_t a = ai("axis", I.opset >= 13 ? -1 : 1); if (a < 0) a += rank;
-                XTensor o = I.dev_tensor(1, x.shape);
-                if (I.opset < 13 || a == rank - 1) { // rows = everything before the axis, cols = the rest (opset < 13 flattens; for the last axis both readings agree)
-                    const int64_t cols = prod(x.shape, (size_t)a), rows = prod(x.shape, 0, (size_t)a);
-                    if (rows && cols) { hipLaunchKernelGGL(k_softmax_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(o), I.f(x), cols, op == "LogSoftmax" ? 1 : 0); I.count(); }
-                    out(0, o);
-                } else {
-                    int64_t rows, cols; std::vector<int64_t> perm;
-                    XTensor p = I.axes_last(x, {a}, rows, cols, &perm);
-                    XTensor q = I.dev_tensor(1, p.shape);
-                    if (rows && cols) { hipLaunchKernelGGL(k_softmax_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(q), I.f(p), cols, op == "LogSoftmax" ? 1 : 0); I.count(); }
-                    std::vector<int64_t> inv(perm.size());
-                    for (size_t d = 0; d < perm.size(); d++) inv[(size_t)perm[d]] = (int64_t)d;
-                    out(0, I.transpose(q, inv));
-                }
-            } else if (op == "LayerNormalization") {
-                const XTensor x = I.as_f32(in(0));
-                int64_t a = ai("axis", -1); if (a < 0) a += (int64_t)x.shape.size();
-                Q3_CHECK(a >= 0 && a < (int64_t)x.shape.size(), "LayerNormalization: axis out of range");
-                const int64_t cols = prod(x.shape, (size_t)a), rows = prod(x.shape, 0, (size_t)a);
-                XTensor g = has(1) ? I.as_f32(in(1)) : XTensor(), b = has(2) ? I.as_f32(in(2)) : XTensor();
-                Q3_CHECK((!has(1) || g.numel() == cols) && (!has(2) || b.numel() == cols), "LayerNormalization: scale / bias length does not match the normalised extent");
-                XTensor o = I.dev_tensor(1, x.shape);
-                if (rows && cols) { hipLaunchKernelGGL(k_norm_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(o), I.f(x), has(1) ? I.f(g) : nullptr, has(2) ? I.f(b) : nullptr, cols, af("epsilon", 1e-5f), 0, (int64_t)1); I.count(); }
-                out(0, o);
-            } else if (op == "InstanceNormalization") {
-                const XTensor x = I.as_f32(in(0)), g = I.as_f32(in(1)), b = I.as_f32(in(2));
-                const int64_t C = x.shape.at(1), rows = x.shape.at(0) * C, cols = prod(x.shape, 2);
-                Q3_CHECK(g.numel() == C && b.numel() == C, "InstanceNormalization: scale / bias length does not match the channels");
-                XTensor o = I.dev_tensor(1, x.shape);
-                if (rows && cols) { hipLaunchKernelGGL(k_norm_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(o), I.f(x), I.f(g), I.f(b), cols, af("epsilon", 1e-5f), 1, C); I.count(); }
-                out(0, o);
-            } else if (op == "BatchNormalization") {
-                const XTensor x = I.as_f32(in(0)), sc = I.as_f32(in(1)), bi = I.as_f32(in(2)), mean = I.as_f32(in(3)), var = I.as_f32(in(4));
-                const int64_t C = x.shape.at(1), inner = prod(x.shape, 2), n = x.numel();
-                Q3_CHECK(sc.numel() == C && bi.numel() == C && mean.numel() == C && var.numel() == C, "BatchNormalization: parameter lengths do not match the channels");
-                XTensor o = I.dev_tensor(1, x.shape);
-                if (n) { hipLaunchKernelGGL(k_batchnorm, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), I.f(sc), I.f(bi), I.f(mean), I.f(var), af("epsilon", 1e-5f), C, inner, n); I.count(); }
-                out(0, o);
-            } else if (op == "GlobalAveragePool" || op == "GlobalMaxPool") {
-                const XTensor x = I.as_f32(in(0));
-                const int64_t rows = x.shape.at(0) * x.shape.at(1), cols = prod(x.shape, 2);
-                std::vector<int64_t> os = x.shape; for (size_t d = 2; d < os.size(); d++) os[d] = 1;
-                XTensor o = I.dev_tensor(1, os);
-                if (rows) { hipLaunchKernelGGL(k_reduce_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(o), (int64_t*)nullptr, I.f(x), op == "GlobalMaxPool" ? R_MAX : R_MEAN, cols, 0); I.count(); }
-                out(0, o);
-            } else if (op == "CumSum") {
-                const XTensor x = I.as_f32(in(0));
-                int64_t a = I.ints_of(in(1)).at(0); if (a < 0) a += (int64_t)x.shape.size();
-                int64_t rows, cols; std::vector<int64_t> perm;
-                XTensor p = I.axes_last(x, {a}, rows, cols, &perm);
-                XTensor q = I.dev_tensor(1, p.shape);
-                if (rows && cols) { hipLaunchKernelGGL(k_cumsum_rows, grid1(rows), dim3(256), 0, 0, I.f(q), I.f(p), rows, cols, (int)ai("exclusive", 0), (int)ai("reverse", 0)); I.count(); }
-                std::vector<int64_t> inv(perm.size());
-                for (size_t d = 0; d < perm.size(); d++) inv[(size_t)perm[d]] = (int64_t)d;
-                out(0, I.transpose(q, inv));
-            } else if (op == "MatMul" || op == "Gemm") {
-                XTensor A = I.as_f32(in(0)), B = I.as_f32(in(1));
-                MmArgs g{};
-                g.alpha = 1.f; g.beta = 1.f;
-                std::vector<int64_t> os;
-                int64_t batch = 1;
-                XTensor bias;
-                if (op == "Gemm") {
-                    Q3_CHECK(A.shape.size() == 2 && B.shape.size() == 2, "Gemm takes matrices");
-                    const bool ta = ai("transA", 0) != 0, tb = ai("transB", 0) != 0;
-                    g.M = ta ? A.shape[1] : A.shape[0]; g.K = ta ? A.shape[0] : A.shape[1]; g.N = tb ? B.shape[0] : B.shape[1];
-                    Q3_CHECK((tb ? B.shape[1] : B.shape[0]) == g.K, "Gemm inner dimensions differ");
-                    g.a_m = ta ? 1 : A.shape[1]; g.a_k = ta ? A.shape[1] : 1; g.b_k = tb ? 1 : B.shape[1]; g.b_n = tb ? B.shape[1] : 1;
-                    g.alpha = af("alpha", 1.f); g.beta = af("beta", 1.f);
-                    if (has(2)) {
-                        bias = I.as_f32(in(2));
-                        const auto bs = bstrides(bias.shape, {g.M, g.N});
-                        g.bias = I.f(bias); g.bias_m = bs[0]; g.bias_n = bs[1];
-                    }
-                    os = {g.M, g.N};
-                } else {
-                    std::vector<int64_t> as_ = A.shape, bs_ = B.shape;
-                    const bool va = as_.size() == 1, vb = bs_.size() == 1;
-                    if (va) as_.insert(as_.begin(), 1);
-                    if (vb) bs_.push_back(1);
-                    g.M = as_[as_.size() - 2]; g.K = as_.back(); g.N = bs_.back();
-                    Q3_CHECK(bs_[bs_.size() - 2] == g.K, "MatMul inner dimensions differ");
-                    std::vector<int64_t> ab(as_.begin(), as_.end() - 2), bb(bs_.begin(), bs_.end() - 2);
-                    const auto bd = bshape(ab, bb);
-                    batch = prod(bd);
-                    // operands whose batch dims are smaller than the broadcast batch are expanded first (rare: attention uses equal batches)
-                    auto full = [&](XTensor& T, std::vector<int64_t>& s, const std::vector<int64_t>& own) {
-                        if (own == bd) return;
-                        if (prod(own) == 1) return; // pure broadcast: batch stride 0
-                        std::vector<int64_t> tgt = bd; tgt.push_back(s[s.size() - 2]); tgt.push_back(s.back());
-                        T = I.expand(I.reshaped(T, s), tgt); s = tgt;
-                    };
-                    full(A, as_, ab); full(B, bs_, bb);
-                    g.a_b = (as_.size() > 2 && prod(as_, 0, as_.size() - 2) > 1) ? g.M * g.K : 0;
-                    g.b_b = (bs_.size() > 2 && prod(bs_, 0, bs_.size() - 2) > 1) ? g.K * g.N : 0;
-                    g.a_m = g.K; g.a_k = 1; g.b_k = g.N; g.b_n = 1;
-                    os = bd;
-                    if (!va) os.push_back(g.M);
-                    if (!vb) os.push_back(g.N);
-                }
-                XTensor o = I.dev_tensor(1, os);
-                if (o.numel()) {
-                    if (mm_fast_ok(g.M, g.N, g.K, batch)) {
-                        MmFast f{};
-                        f.M = (int)g.M; f.N = (int)g.N; f.K = (int)g.K; f.a_b = g.a_b; f.a_m = g.a_m; f.a_k = g.a_k; f.b_b = g.b_b; f.b_k = g.b_k; f.b_n = g.b_n;
-                        f.bias = g.bias; f.bias_m = g.bias_m; f.bias_n = g.bias_n; f.alpha = g.alpha; f.beta = g.beta;
-                        launch_mm_fast(I.f(o), I.f(A), I.f(B), f, batch);
-                    } else
-                    hipLaunchKernelGGL(k_matmul, dim3((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)batch), dim3(256), 0, 0, I.f(o), I.f(A), I.f(B), g);
-                    I.count();
-                }
-                out(0, o);
-            } else if (op == "Conv" || op == "ConvTranspose") {
-                XTensor x = I.as_f32(in(0)), w = I.as_f32(in(1)), b = has(2) ? I.as_f32(in(2)) : XTensor();
-                const int sp = (int)x.shape.size() - 2;
-                Q3_CHECK(sp == 1 || sp == 2, "convolutions over 1 or 2 spatial dimensions");
-                Q3_CHECK(w.shape.size() == x.shape.size(), op + ": weight rank does not match the input rank");
-                auto two = [&](std::vector<int64_t> v, int64_t fill) { if (v.empty()) v.assign((size_t)sp, fill); if (sp == 1) v.insert(v.begin(), fill == 0 ? 0 : 1); return v; };
-                std::vector<int64_t> strides = two(aints("strides"), 1), dil = two(aints("dilations"), 1), pads = aints("pads"), ks(w.shape.begin() + 2, w.shape.end());
-                if (sp == 1) ks.insert(ks.begin(), 1);
-                ConvArgs g{};
-                g.N = x.shape[0]; g.C = x.shape[1]; g.H = sp == 1 ? 1 : x.shape[2]; g.W = x.shape.back();
-                g.kh = ks[0]; g.kw = ks[1]; g.sh = strides[0]; g.sw = strides[1]; g.dh = dil[0]; g.dw = dil[1]; g.groups = ai("group", 1);
-                // operand shapes against what k_conv2d / k_convtr2d index (they divide by groups and strides and trust the weight / bias extents)
-                Q3_CHECK(strides.size() == 2 && dil.size() == 2 && (pads.empty() || pads.size() == (size_t)(2 * sp)), op + ": strides / dilations / pads do not match the spatial rank");
-                Q3_CHECK(g.sh > 0 && g.sw > 0 && g.dh > 0 && g.dw > 0 && g.kh > 0 && g.kw > 0, op + ": strides, dilations and kernel extents must be positive");
-                Q3_CHECK(g.groups > 0 && g.C % g.groups == 0, op + ": group does not divide the input channels");
-                if (op == "Conv") Q3_CHECK(w.shape[1] * g.groups == g.C && w.shape[0] % g.groups == 0, "Conv: weight shape [M, C/group, ...] does not match the input channels");
-                else Q3_CHECK(w.shape[0] == g.C, "ConvTranspose: weight shape [C, M/group, ...] does not match the input channels");
-                Q3_CHECK(!has(2) || b.numel() == (op == "Conv" ? w.shape[0] : w.shape[1] * g.groups), op + ": bias length does not match the output channels");
-                for (auto pv : pads) Q3_CHECK(pv >= 0, op + ": negative padding");
-                std::vector<int64_t> pb(2, 0), pe(2, 0);
-                if (!pads.empty()) { if (sp == 1) { pb[1] = pads[0]; pe[1] = pads[1]; } else { pb[0] = pads[0]; pb[1] = pads[1]; pe[0] = pads[2]; pe[1] = pads[3]; } }
-                const std::string ap = as("auto_pad", "NOTSET");
-                const int64_t inH[2] = {g.H, g.W};
-                int64_t O[2];
-                if (op == "Conv") {
-                    g.M = w.shape[0];
-                    for (int d = 0; d < 2; d++) {
-                        const int64_t eff = (ks[(size_t)d] - 1) * dil[(size_t)d] + 1;
-                        if (ap == "SAME_UPPER" || ap == "SAME_LOWER") {
-                            O[d] = (inH[d] + strides[(size_t)d] - 1) / strides[(size_t)d];
-                            const int64_t tot = std::max<int64_t>(0, (O[d] - 1) * strides[(size_t)d] + eff - inH[d]);
-                            pb[(size_t)d] = ap == "SAME_UPPER" ? tot / 2 : tot - tot / 2; pe[(size_t)d] = tot - pb[(size_t)d];
-                        } else {
-                            if (ap == "VALID") { pb[(size_t)d] = pe[(size_t)d] = 0; }
-                            O[d] = (inH[d] + pb[(size_t)d] + pe[(size_t)d] - eff) / strides[(size_t)d] + 1;
-                        }
-                    }
-                } else {
-                    g.M = w.shape[1] * g.groups;
-                    std::vector<int64_t> opad = aints("output_padding"), oshape = aints("output_shape");
-                    if (opad.empty()) opad.assign((size_t)sp, 0);
-                    if (sp == 1) { opad.insert(opad.begin(), 0); if (!oshape.empty()) oshape.insert(oshape.begin(), 1); }
-                    for (int d = 0; d < 2; d++) {
-                        const int64_t eff = (ks[(size_t)d] - 1) * dil[(size_t)d] + 1;
-                        if (!oshape.empty()) {
-                            O[d] = oshape[(size_t)d];
-                            const int64_t tot = std::max<int64_t>(0, (inH[d] - 1) * strides[(size_t)d] + opad[(size_t)d] + eff - O[d]);
-                            pb[(size_t)d] = ap == "SAME_UPPER" ? tot / 2 : tot - tot / 2; pe[(size_t)d] = tot - pb[(size_t)d];
-                        } else if (ap == "SAME_UPPER" || ap == "SAME_LOWER") {
-                            O[d] = inH[d] * strides[(size_t)d];
-                            const int64_t tot = std::max<int64_t>(0, (inH[d] - 1) * strides[(size_t)d] + opad[(size_t)d] + eff - O[d]);
-                            pb[(size_t)d] = ap == "SAME_UPPER" ? tot / 2 : tot - tot / 2; pe[(size_t)d] = tot - pb[(size_t)d];
-                        } else O[d] = (inH[d] - 1) * strides[(size_t)d] - pb[(size_t)d] - pe[(size_t)d] + eff + opad[(size_t)d];
-                    }
-                }
-                g.ph = pb[0]; g.pw = pb[1]; g.OH = O[0]; g.OW = O[1];
-                Q3_CHECK(g.OH >= 0 && g.OW >= 0, "negative convolution output size");
-                std::vector<int64_t> os = {g.N, g.M};
-                if (sp == 2) os.push_back(g.OH);
-                os.push_back(g.OW);
-                XTensor o = I.dev_tensor(1, os);
-                const int64_t n = o.numel();
-                if (n) {
-                    const bool one_d = sp == 1 && g.groups == 1 && g.W < (1 << 30) && g.OW < (1 << 30) && g.sw < (1 << 20) && g.pw < (1 << 30) && g.dw < (1 << 20) && g.kw < (1 << 20);
-                    if (op == "Conv" && one_d && mm_fast_ok(g.M, g.OW, g.C * g.kw, g.N)) {
-                        // implicit GEMM: W[M][C * kw] x im2col(x)[C * kw][OW] per batch element; the NCW output is the product's row-major layout
-                        MmFast f{};
-                        f.M = (int)g.M; f.N = (int)g.OW; f.K = (int)(g.C * g.kw); f.a_b = 0; f.a_m = g.C * g.kw; f.a_k = 1; f.b_b = g.C * g.W;
-                        f.conv = 1; f.kw = (int)g.kw; f.cs = (int)g.sw; f.cp = (int)g.pw; f.cd = (int)g.dw; f.W = (int)g.W;
-                        f.bias = has(2) ? I.f(b) : nullptr; f.bias_m = 1; f.bias_n = 0; f.alpha = 1.f; f.beta = 1.f;
-                        launch_mm_fast(I.f(o), I.f(w), I.f(x), f, g.N);
-                    } else if (op == "ConvTranspose" && one_d && mm_fast_ok(g.M * g.kw, g.W, g.C, g.N)) {
-                        // Y[b][m * kw + k][i] = sum_c w[c][m][k] x[b][c][i] (the weight tensor read as its own transpose), then the taps are overlap-added
-                        XTensor y = I.dev_tensor(1, {g.N, g.M * g.kw, g.W});
-                        MmFast f{};
-                        f.M = (int)(g.M * g.kw); f.N = (int)g.W; f.K = (int)g.C; f.a_b = 0; f.a_m = 1; f.a_k = g.M * g.kw; f.b_b = g.C * g.W; f.b_k = g.W; f.b_n = 1;
-                        f.alpha = 1.f; f.beta = 0.f;
-                        launch_mm_fast(I.f(y), I.f(w), I.f(x), f, g.N);
-                        I.count();
-                        hipLaunchKernelGGL(k_col2im1d, grid1(n), dim3(256), 0, 0, I.f(o), I.f(y), has(2) ? I.f(b) : nullptr, g.M, g.OW, g.W, (int)g.kw, (int)g.sw, (int)g.pw, (int)g.dw, n);
-                    } else if (op == "Conv") hipLaunchKernelGGL(k_conv2d, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), I.f(w), has(2) ? I.f(b) : nullptr, g, n);
-                    else hipLaunchKernelGGL(k_convtr2d, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), I.f(w), has(2) ? I.f(b) : nullptr, g, n);
-                    I.count();
-                }
-                out(0, o);
-            } else if (op == "Pad") {
-                const XTensor x = I.as_f32(in(0));
-                const int rank = (int)x.shape.size();
-                std::vector<int64_t> pads = has(1) ? I.ints_of(in(1)) : aints("pads");
-                float value = af("value", 0.f);
-                if (has(2)) value = (float)I.to_host(in(2)).hv.at(0);
-                std::vector<int64_t> axes;
-                if (has(3)) axes = I.ints_of(in(3)); else for (int d = 0; d < rank; d++) axes.push_back(d);
-                Q3_CHECK(pads.size() == 2 * axes.size(), "Pad: pads do not match the axes");
-                const std::string mode = as("mode", "constant");
-                PadArgs p{}; p.rank = rank; p.mode = mode == "constant" ? 0 : mode == "reflect" ? 1 : mode == "edge" ? 2 : -1; p.value = value;
-                Q3_CHECK(p.mode >= 0, "Pad mode " + mode);
-                Q3_CHECK(rank <= XR, "Pad: rank above 8 (rank " + std::to_string(rank) + ")");
-                std::vector<int64_t> os = x.shape;
-                for (int d = 0; d < rank; d++) { p.ishape[d] = x.shape[(size_t)d]; p.begin[d] = 0; }
-                for (size_t i = 0; i < axes.size(); i++) { int64_t a = axes[i]; if (a < 0) a += rank; Q3_CHECK(a >= 0 && a < rank, "Pad: axis out of range"); p.begin[a] = pads[i]; os[(size_t)a] += pads[i] + pads[i + axes.size()]; }
-                for (int d = 0; d < rank; d++) p.oshape[d] = os[(size_t)d];
-                XTensor o = I.dev_tensor(1, os);
-                const int64_t n = o.numel();
-                if (n) { hipLaunchKernelGGL(k_pad, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), p, n); I.count(); }
-                out(0, o);
-            } else if (op == "Trilu") {
-                const XTensor x = I.as_f32(in(0));
-                Q3_CHECK(x.shape.size() >= 2, "Trilu needs a matrix");
-                const int64_t k2 = has(1) ? I.ints_of(in(1)).at(0) : 0, rows = x.shape[x.shape.size() - 2], cols = x.shape.back(), n = x.numel();
-                XTensor o = I.dev_tensor(in(0).dtype == 9 ? 9 : 1, x.shape);
-                if (n) { hipLaunchKernelGGL(k_trilu, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), rows, cols, k2, (int)ai("upper", 1), n); I.count(); }
-                out(0, in(0).dtype == 7 ? I.as_i64(o) : o);
-            } else if (op == "GatherElements") {
-                const XTensor x = I.to_device(in(0)), idx = I.as_i64(in(1));
-                int64_t a = ai("axis", 0); if (a < 0) a += (int64_t)x.shape.size();
-                Q3_CHECK(idx.shape.size() == x.shape.size(), "GatherElements: rank mismatch");
-                for (size_t d = 0; d < x.shape.size(); d++) Q3_CHECK((int64_t)d == a || idx.shape[d] == x.shape[d], "GatherElements: indices must match the data outside the axis");
-                const int64_t inner = prod(x.shape, (size_t)a + 1), nj = idx.shape[(size_t)a], n = idx.numel();
-                XTensor o = I.dev_tensor(x.dtype, idx.shape);
-                if (n) {
-                    if (x.dtype == 7) hipLaunchKernelGGL(k_gather_elems<int64_t>, grid1(n), dim3(256), 0, 0, I.i64(o), I.i64(x), I.i64(idx), nj, x.shape[(size_t)a], inner, n);
-                    else hipLaunchKernelGGL(k_gather_elems<float>, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), I.i64(idx), nj, x.shape[(size_t)a], inner, n);
-                    I.count();
-                }
-                out(0, o);
-            } else if (op == "ScatterND") {
-                const XTensor x = I.as_f32(in(0)), upd = I.as_f32(in(2));
-                const XTensor ih = I.to_host(in(1)); // index tuples are small (cache positions): evaluated on the host into slice offsets
-                Q3_CHECK(as("reduction", "none") == "none", "ScatterND with a reduction");
-                const int64_t kdim = ih.shape.back(), nup = kdim ? ih.numel() / kdim : 0;
-                Q3_CHECK(kdim >= 1 && kdim <= (int64_t)x.shape.size(), "ScatterND index depth");
-                const int64_t slice = prod(x.shape, (size_t)kdim);
-                const auto st = strides_of(x.shape);
-                std::vector<double> offs((size_t)nup);
-                for (int64_t u = 0; u < nup; u++) {
-                    int64_t off = 0;
-                    for (int64_t d = 0; d < kdim; d++) { int64_t v = (int64_t)ih.hv[(size_t)(u * kdim + d)]; if (v < 0) v += x.shape[(size_t)d]; Q3_CHECK(v >= 0 && v < x.shape[(size_t)d], "ScatterND index out of range"); off += v * st[(size_t)d]; }
-                    offs[(size_t)u] = (double)(off / std::max<int64_t>(slice, 1));
-                }
-                XTensor o = I.dev_tensor(1, x.shape);
-                if (x.numel()) Q3_HIP(hipMemcpyAsync(o.dev->p, x.dev->p, (size_t)x.numel() * 4, hipMemcpyDeviceToDevice, 0));
-                const int64_t n = nup * slice;
-                if (n) {
-                    XTensor od = I.to_device(Impl::host_tensor(7, {nup}, offs));
-                    hipLaunchKernelGGL(k_scatter_rows, grid1(n), dim3(256), 0, 0, I.f(o), I.f(upd), I.i64(od), slice, n);
-                    I.count();
-                }
-                out(0, o);
-            } else if (op == "Resize") {
-                const XTensor x = I.as_f32(in(0));
-                Q3_CHECK(as("mode", "nearest") == "nearest", "Resize: only nearest is implemented");
-                const int rank = (int)x.shape.size();
-                ResizeArgs a{}; a.rank = rank;
-                std::vector<int64_t> os = x.shape;
-                Q3_CHECK(rank >= 1 && rank <= XR, "Resize: rank out of range (rank " + std::to_string(rank) + ")");
-                const bool old_layout = I.opset < 11; // opset 10: inputs (X, scales); opset >= 11: (X, roi, scales, sizes)
-                if (!old_layout && has(3)) { os = I.ints_of(in(3)); Q3_CHECK((int)os.size() == rank, "Resize sizes rank"); for (int d = 0; d < rank; d++) { Q3_CHECK(x.shape[(size_t)d] > 0 && os[(size_t)d] >= 0, "Resize: empty input extent"); a.scale[d] = (float)os[(size_t)d] / (float)x.shape[(size_t)d]; } }
-                else { const int si = old_layout ? 1 : 2; Q3_CHECK(has(si), "Resize needs scales or sizes"); const XTensor sc = I.to_host(in(si)); Q3_CHECK((int)sc.hv.size() == rank, "Resize scales rank");
-                       for (int d = 0; d < rank; d++) { Q3_CHECK(sc.hv[(size_t)d] > 0, "Resize: scales must be positive"); a.scale[d] = (float)sc.hv[(size_t)d]; os[(size_t)d] = (int64_t)std::floor((double)x.shape[(size_t)d] * sc.hv[(size_t)d]); } }
-                { // the kernel samples x_in = floor(x_out / scale) (asymmetric + floor).  ONNX defaults to half_pixel + round_prefer_floor, which picks the same
-                  // sample exactly when every scale is a whole number >= 1; any other combination is refused instead of silently resampling differently
-                    const std::string ctm = as("coordinate_transformation_mode", old_layout ? "asymmetric" : "half_pixel"), nm = as("nearest_mode", old_layout ? "floor" : "round_prefer_floor");
-                    bool whole = true;
-                    for (int d = 0; d < rank; d++) whole = whole && a.scale[d] >= 1.0f && a.scale[d] == std::floor(a.scale[d]);
-                    const bool native = ctm == "asymmetric" && nm == "floor";
-                    const bool equivalent = whole && (ctm == "half_pixel" || ctm == "pytorch_half_pixel" || ctm == "asymmetric") && (nm == "round_prefer_floor" || nm == "floor");
-                    Q3_CHECK(native || equivalent, "Resize: coordinate_transformation_mode=" + ctm + " nearest_mode=" + nm + " is only implemented for whole-number up-scaling");
-                }
-                for (int d = 0; d < rank; d++) { a.oshape[d] = os[(size_t)d]; a.ishape[d] = x.shape[(size_t)d]; }
-                XTensor o = I.dev_tensor(1, os);
-                const int64_t n = o.numel();
-                if (n) { hipLaunchKernelGGL(k_resize_nearest, grid1(n), dim3(256), 0, 0, I.f(o), I.f(x), a, n); I.count(); }
-                out(0, o);
-            } else if (op == "GroupNormalization") {
-                const XTensor x = I.as_f32(in(0)), g = I.as_f32(in(1)), b = I.as_f32(in(2));
-                const int64_t G = ai("num_groups", 1), C = x.shape.at(1), sp = prod(x.shape, 2);
-                Q3_CHECK(G > 0 && C % G == 0, "GroupNormalization groups");
-                const int64_t rows = x.shape.at(0) * G, cols = (C / G) * sp;
-                Q3_CHECK((g.numel() == C || g.numel() == G) && b.numel() == g.numel(), "GroupNormalization: scale / bias length is neither the channels nor the groups");
-                XTensor nrm = I.dev_tensor(1, x.shape);
-                if (rows && cols) { hipLaunchKernelGGL(k_norm_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(nrm), I.f(x), (const float*)nullptr, (const float*)nullptr, cols, af("epsilon", 1e-5f), 0, (int64_t)1); I.count(); }
-                // per-channel affine (opset 21 form; opset 18 files carry per-group scale / bias of length G)
-                std::vector<int64_t> bs(x.shape.size(), 1); bs[1] = g.numel() == C ? C : G;
-                XTensor y = nrm;
-                if (g.numel() == C) { y = I.binary(B_MUL, nrm, I.reshaped(g, bs), 1); y = I.binary(B_ADD, y, I.reshaped(b, bs), 1); }
-                else { std::vector<int64_t> gs = {x.shape[0], G, C / G}; gs.insert(gs.end(), x.shape.begin() + 2, x.shape.end()); std::vector<int64_t> gb(gs.size(), 1); gb[1] = G;
-                       y = I.binary(B_ADD, I.binary(B_MUL, I.reshaped(nrm, gs), I.reshaped(g, gb), 1), I.reshaped(b, gb), 1); y = I.reshaped(y, x.shape); }
-                out(0, y);
-            } else if (op == "LpNormalization") {
-                const XTensor x = I.as_f32(in(0));
-                int64_t a = ai("axis", -1); if (a < 0) a += (int64_t)x.shape.size();
-                const int64_t p2 = ai("p", 2);
-                Q3_CHECK(p2 == 1 || p2 == 2, "LpNormalization p");
-                int64_t rows, cols;
-                XTensor perm = I.axes_last(x, {a}, rows, cols);
-                std::vector<int64_t> ks = x.shape; ks[(size_t)a] = 1;
-                XTensor nm = I.dev_tensor(1, ks);
-                if (rows) { hipLaunchKernelGGL(k_reduce_rows, dim3((unsigned)rows), dim3(256), 0, 0, I.f(nm), (int64_t*)nullptr, I.f(perm), p2 == 2 ? R_L2 : R_L1, cols, 0); I.count(); }
-                out(0, I.binary(B_DIV, x, nm, 1));
-            } else {
-                throw Error("operator is not supported by this executor");
-            }
+            const OpEntry* e = I.entry[k];
+            if (!e) throw Error("operator is not supported by this executor");
+            NodeCtx c{I, nd, e->arg};
+            e->fn(c);
             Q3_LAUNCH_CHECK();
         } catch (const std::exception& e) {
             throw Error("node " + std::to_string(k) + " (" + nd.op_type + (nd.name.empty() ? "" : " '" + nd.name + "'") + "): " + e.what());
         }
-        // release edges that nobody reads again
+        // release edges that nobody reads again (an initialiser is not an edge of the run)
         for (auto& s : nd.inputs) { auto it = last.find(s); if (it != last.end() && it->second == k && !I.consts.count(s)) I.vals.erase(s); }
     }
     Q3_HIP(hipDeviceSynchronize());
-    for (auto& o : model_->outputs) if (!I.vals.count(o.name)) throw Error("graph output " + o.name + " was not produced");
+    for (auto& o : model_->outputs) if (!I.find(o.name)) throw Error("graph output " + o.name + " was not produced");
 }
+
 
 OnnxStreamDecoder::OnnxStreamDecoder(const std::string& path, int device) : s_(path, device) {
     const std::string miss = s_.model().check_decoder_contract();

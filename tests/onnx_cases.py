@@ -546,7 +546,287 @@ def row_cases():
     return reduce_cases() + arg_cases() + softmax_cases() + norm_cases() + cumsum_cases()
 
 
+# ------------------------------------------------------------------------------------------------------------------ the operator zoo
+# One tiny graph per operator name that the product and row tables do not reach (plus a few forms they leave out), for
+# scripts/onnx_exec_digest.py: no reference, the outputs are pinned bit for bit in tests/golden/onnx_exec_digests.json.  Tensors hold at
+# most 256 elements and have rank at most 4.  Feeds are device tensors; integer initialisers and float initialisers of at most 8 elements
+# stay on the host, so `h*` operands below take the executor's host evaluators and the rest its kernels.
+UNARY_OPS = ("Relu", "Sigmoid", "Tanh", "Exp", "Log", "Sqrt", "Reciprocal", "Neg", "Abs", "Sin", "Cos", "Erf", "Floor", "Ceil", "Round", "Sign", "Elu",
+             "LeakyRelu", "HardSigmoid", "Gelu", "Softplus", "Selu", "Not", "Softsign", "HardSwish", "IsNaN", "Celu", "ThresholdedRelu", "Mish", "Tan",
+             "Atan", "Sinh", "Cosh")
+BINARY_OPS = ("Add", "Sub", "Mul", "Div", "Pow", "Min", "Max", "Equal", "Less", "Greater", "LessOrEqual", "GreaterOrEqual", "And", "Or", "Xor", "Mod",
+              "PRelu", "Sum", "Mean")
+OTHER_OPS = ("Identity", "Dropout", "Reshape", "Flatten", "Squeeze", "Unsqueeze", "Transpose", "Concat", "Slice", "Split", "Gather", "Shape", "Size",
+             "Constant", "ConstantOfShape", "Range", "Cast", "Expand", "Tile", "Where", "Clip", "Softmax", "LogSoftmax", "LayerNormalization",
+             "InstanceNormalization", "BatchNormalization", "MatMul", "Gemm", "Conv", "ConvTranspose", "Pad", "CumSum", "GlobalAveragePool",
+             "GlobalMaxPool", "Trilu", "GatherElements", "ScatterND", "Resize", "GroupNormalization", "LpNormalization")
+EXECUTABLE_OPS = UNARY_OPS + BINARY_OPS + REDUCE_OPS + ("ArgMax", "ArgMin") + OTHER_OPS     # 33 + 19 + 11 + 40 = 103 names
+NOT_EXECUTABLE_OPS = ("LSTM", "GRU", "AveragePool", "SimplifiedLayerNormalization", "RMSNormalization", "NoSuchOp")
+
+
+def _zoo(name, nodes, inits, feeds, outs, opset=17):
+    assert all(np.asarray(v).size <= 256 and np.asarray(v).ndim <= 4 for v in feeds.values()), name
+    return Case(name, nodes, inits, feeds, None, None, "zoo", opset=opset, out=list(outs))
+
+
+def _i(name, v):
+    return W.tensor(name, np.asarray(v, np.int64))
+
+
+def _q(rng, *shape):
+    """normals rounded to halves: exact zeros, ties for Round and equal pairs for the comparisons all occur"""
+    return (np.round(2 * rng.standard_normal(shape)) / 2).astype(np.float32)
+
+
+def _zoo_unary():
+    attrs = {"Elu": [W.attr_float("alpha", 0.7)], "LeakyRelu": [W.attr_float("alpha", 0.1)], "HardSigmoid": [W.attr_float("alpha", 0.25), W.attr_float("beta", 0.4)],
+             "Selu": [W.attr_float("alpha", 1.5), W.attr_float("gamma", 1.1)], "Gelu": [W.attr_str("approximate", "tanh")], "Celu": [W.attr_float("alpha", 1.5)],
+             "ThresholdedRelu": [W.attr_float("alpha", 0.3)]}
+    out = []
+    for op in UNARY_OPS:
+        name = "zoo_" + op
+        rng = _rng(name)
+        x = _q(rng, 2, 3, 4) + np.float32(0.25) * _f(rng, 2, 3, 4)
+        x[0, 0] = [0.0, 0.5, -1.5, 2.5]
+        if op in ("Log", "Sqrt"):
+            x = np.abs(x) + np.float32(0.125)
+        if op == "IsNaN":
+            x[1, 2, 3] = np.nan
+        nodes, outs = [W.node(op, ["x"], ["y"])], ["y"]
+        if op in attrs:
+            nodes.append(W.node(op, ["x"], ["y_attr"], attrs=attrs[op])); outs.append("y_attr")
+        if op in ("Floor", "Ceil", "Sqrt", "Neg", "Abs", "Round", "Not", "Sign"):          # a host float operand
+            nodes.append(W.node(op, ["hf"], ["y_hf"])); outs.append("y_hf")
+        if op in ("Neg", "Abs", "Sign", "Not", "Floor"):                                   # a host integer operand
+            nodes.append(W.node(op, ["hi"], ["y_hi"])); outs.append("y_hi")
+        inits = [W.tensor("hf", np.asarray([[0.0, 0.5, 1.5], [2.25, 6.5, 0.75]], np.float32)), _i("hi", [[-3, 0], [2, 7]])]
+        out.append(_zoo(name, nodes, inits, {"x": x}, outs))
+    return out
+
+
+def _zoo_binary():
+    out = []
+    for op in BINARY_OPS:
+        name = "zoo_" + op
+        rng = _rng(name)
+        a, b, c = _q(rng, 2, 1, 4), _q(rng, 3, 1), _q(rng, 4)
+        if op == "Pow":
+            a = np.abs(a) + np.float32(0.5)
+        ia, ib = np.asarray([[7], [-7]], np.int64), np.asarray([2, -3, 5], np.int64)
+        inits = [W.tensor("s", np.float32(1.5).reshape(())), _i("hi", [[7], [-7]]), _i("hj", [2, -3, 5])]
+        nodes = [W.node(op, ["a", "b"], ["y"]),                   # device, rank 3 against rank 2
+                 W.node(op, ["a", "s"], ["y_s"]),                 # a host scalar against a device tensor
+                 W.node(op, ["hi", "hj"], ["y_h"])]               # both on the host, integers
+        outs = ["y", "y_s", "y_h"]
+        if op != "Div":                                           # integer division of device tensors is refused
+            nodes.append(W.node(op, ["ia", "ib"], ["y_i"])); outs.append("y_i")
+        if op == "Mod":
+            nodes += [W.node(op, ["a", "b"], ["y_f"], attrs=[W.attr_int("fmod", 1)]), W.node(op, ["hi", "hj"], ["y_hf"], attrs=[W.attr_int("fmod", 1)])]
+            outs += ["y_f", "y_hf"]
+        if op in ("Sum", "Mean"):
+            nodes += [W.node(op, ["a", "b", "c"], ["y3"]), W.node(op, ["a"], ["y1"])]
+            outs += ["y3", "y1"]
+        out.append(_zoo(name, nodes, inits, {"a": a, "b": b, "c": c, "ia": ia, "ib": ib}, outs))
+    return out
+
+
+def _zoo_other():
+    n, out = W.node, []
+
+    def add(op, nodes, inits, feeds, outs, opset=17, name=None):
+        out.append(_zoo(name or "zoo_" + op, nodes, inits, feeds, outs, opset))
+
+    def x_of(name, *shape):
+        return _f(_rng(name), *shape)
+
+    hi = _i("hi", [[-3, 0], [2, 7]])
+    x = x_of("zoo_x234", 2, 3, 4)
+    add("Identity", [n("Identity", ["x"], ["y"]), n("Identity", ["hi"], ["y_h"])], [hi], {"x": x}, ["y", "y_h"])
+    add("Dropout", [n("Dropout", ["x"], ["y"])], [], {"x": x}, ["y"])
+    add("Reshape", [n("Reshape", ["x", "s0"], ["y0"]), n("Reshape", ["x", "s1"], ["y1"]), n("Reshape", ["x", "s2"], ["y2"], attrs=[W.attr_int("allowzero", 1)]),
+                    n("Reshape", ["hi", "s3"], ["y_h"])],
+        [hi, _i("s0", [0, -1]), _i("s1", [4, 0, -1]), _i("s2", [6, 4]), _i("s3", [4])], {"x": x}, ["y0", "y1", "y2", "y_h"])
+    add("Flatten", [n("Flatten", ["x"], ["y1"]), n("Flatten", ["x"], ["ym1"], attrs=[W.attr_int("axis", -1)]), n("Flatten", ["x"], ["y0"], attrs=[W.attr_int("axis", 0)]),
+                    n("Flatten", ["x"], ["y3"], attrs=[W.attr_int("axis", 3)]), n("Flatten", ["hi"], ["y_h"])], [hi], {"x": x}, ["y1", "ym1", "y0", "y3", "y_h"])
+    xs = x_of("zoo_Squeeze", 2, 1, 4, 1)
+    add("Squeeze", [n("Squeeze", ["x", "a1"], ["y1"]), n("Squeeze", ["x", "am"], ["ym"]), n("Squeeze", ["x"], ["yall"]),
+                    n("Squeeze", ["x"], ["yattr"], attrs=[W.attr_ints("axes", [-1])]), n("Squeeze", ["h1"], ["y_h"])],
+        [_i("a1", [1]), _i("am", [-1, 1]), _i("h1", [[5], [6]])], {"x": xs}, ["y1", "ym", "yall", "yattr", "y_h"])
+    xu = x_of("zoo_Unsqueeze", 2, 3)
+    add("Unsqueeze", [n("Unsqueeze", ["x", "a0"], ["y0"]), n("Unsqueeze", ["x", "am"], ["ym"]), n("Unsqueeze", ["x", "a03"], ["y03"]),
+                      n("Unsqueeze", ["x"], ["yattr"], attrs=[W.attr_ints("axes", [1])]), n("Unsqueeze", ["hi", "a0"], ["y_h"])],
+        [hi, _i("a0", [0]), _i("am", [-1]), _i("a03", [3, 0])], {"x": xu}, ["y0", "ym", "y03", "yattr", "y_h"])
+    add("Transpose", [n("Transpose", ["x"], ["yrev"]), n("Transpose", ["x"], ["y120"], attrs=[W.attr_ints("perm", [1, 2, 0])]),
+                      n("Transpose", ["x"], ["yid"], attrs=[W.attr_ints("perm", [0, 1, 2])]), n("Transpose", ["hi"], ["y_h"]), n("Transpose", ["xi"], ["y_i"], attrs=[W.attr_ints("perm", [1, 0])])],
+        [hi], {"x": x, "xi": np.arange(6, dtype=np.int64).reshape(2, 3) - 2}, ["yrev", "y120", "yid", "y_h", "y_i"])
+    x2 = x_of("zoo_Concat", 2, 2, 4)
+    add("Concat", [n("Concat", ["x", "x2"], ["y1"], attrs=[W.attr_int("axis", 1)]), n("Concat", ["x", "x"], ["ym1"], attrs=[W.attr_int("axis", -1)]),
+                   n("Concat", ["hi", "hj"], ["y_h"], attrs=[W.attr_int("axis", 0)]), n("Concat", ["hi", "hk"], ["y_h1"], attrs=[W.attr_int("axis", -1)]),
+                   n("Concat", ["xf", "hi"], ["y_mixed"], attrs=[W.attr_int("axis", 0)]), n("Concat", ["xi", "hi"], ["y_i"], attrs=[W.attr_int("axis", 0)]), n("Concat", ["x"], ["y_one"], attrs=[W.attr_int("axis", 2)])],
+        [hi, _i("hj", [[9, 9]]), _i("hk", [[1], [2]])], {"x": x, "x2": x2, "xf": x_of("zoo_Concat_f", 1, 2), "xi": np.asarray([[1 << 40, -5]], np.int64)}, ["y1", "ym1", "y_h", "y_h1", "y_mixed", "y_i", "y_one"])
+    x456 = x_of("zoo_Slice", 4, 5, 6)
+    add("Slice", [n("Slice", ["x", "st0", "en0", "ax0", "sp0"], ["y0"]),          # axis 1 1:5:2, axis -1 4:begin:-1
+                  n("Slice", ["x", "st1", "en1"], ["y1"]),                         # default axes and steps, bounds past both ends
+                  n("Slice", ["x", "st2", "en2", "ax2", "sp2"], ["y2"]),           # negative step past the start: everything reversed, step -2
+                  n("Slice", ["x"], ["yattr"], attrs=[W.attr_ints("starts", [1, 0]), W.attr_ints("ends", [3, 100]), W.attr_ints("axes", [0, 2])]),
+                  n("Slice", ["x", "st3", "en3", "ax3"], ["yempty"]),              # start == end
+                  n("Shape", ["x"], ["shp"]), n("Slice", ["shp", "st4", "en4"], ["y_h"])],
+        [_i("st0", [1, 4]), _i("en0", [5, -(1 << 62)]), _i("ax0", [1, -1]), _i("sp0", [2, -1]), _i("st1", [-100, 2]), _i("en1", [100, -1]),
+         _i("st2", [100]), _i("en2", [-100]), _i("ax2", [-2]), _i("sp2", [-2]), _i("st3", [2]), _i("en3", [2]), _i("ax3", [0]), _i("st4", [1]), _i("en4", [3])],
+        {"x": x456}, ["y0", "y1", "y2", "yattr", "yempty", "y_h"])
+    x264 = x_of("zoo_Split", 2, 6, 4)
+    add("Split", [n("Split", ["x", "sz"], ["a0", "a1", "a2"], attrs=[W.attr_int("axis", 1)]), n("Split", ["x"], ["b0", "b1"], attrs=[W.attr_int("axis", -1)]),
+                  n("Split", ["x"], ["c0", "c1"], attrs=[W.attr_int("axis", 0), W.attr_ints("split", [1, 1])]), n("Split", ["hi"], ["d0", "d1"], attrs=[W.attr_int("axis", 1)])],
+        [hi, _i("sz", [1, 2, 3])], {"x": x264}, ["a0", "a1", "a2", "b0", "b1", "c0", "c1", "d0", "d1"])
+    x345 = x_of("zoo_Gather", 3, 4, 5)
+    add("Gather", [n("Gather", ["x", "idx"], ["y1"], attrs=[W.attr_int("axis", 1)]), n("Gather", ["x", "idx"], ["ym1"], attrs=[W.attr_int("axis", -1)]),
+                   n("Gather", ["x", "i0"], ["y0"]), n("Shape", ["x"], ["shp"]), n("Gather", ["shp", "i0"], ["y_h"]), n("Gather", ["shp", "idm"], ["y_hm"]),
+                   n("Gather", ["xi", "idx"], ["y_i"]), n("Gather", ["x", "di"], ["y_dev_idx"], attrs=[W.attr_int("axis", 2)])],
+        [_i("idx", [[0, 2], [1, -1]]), _i("i0", 2), _i("idm", [-1, 0])],
+        {"x": x345, "xi": (np.arange(12, dtype=np.int64).reshape(4, 3) - 6) * ((1 << 40) + 1), "di": np.asarray([4, -5, 0], np.int64)}, ["y1", "ym1", "y0", "y_h", "y_hm", "y_i", "y_dev_idx"])
+    add("Shape", [n("Shape", ["x"], ["y"]), n("Shape", ["x"], ["y1"], attrs=[W.attr_int("start", 1)]), n("Shape", ["x"], ["ye"], attrs=[W.attr_int("end", -1)]),
+                  n("Shape", ["x"], ["ys"], attrs=[W.attr_int("start", -2), W.attr_int("end", 100)]), n("Shape", ["hi"], ["y_h"])], [hi], {"x": x}, ["y", "y1", "ye", "ys", "y_h"])
+    add("Size", [n("Size", ["x"], ["y"]), n("Size", ["hi"], ["y_h"])], [hi], {"x": x}, ["y", "y_h"])
+    add("Constant", [n("Constant", [], ["yt"], attrs=[W.attr_tensor("value", np.arange(6, dtype=np.float32).reshape(2, 3) / 4)]),
+                     n("Constant", [], ["yti"], attrs=[W.attr_tensor("value", np.asarray([3, -4], np.int64))]), n("Constant", [], ["yf"], attrs=[W.attr_float("value_float", 0.75)]),
+                     n("Constant", [], ["yi"], attrs=[W.attr_int("value_int", -9)]), n("Constant", [], ["yis"], attrs=[W.attr_ints("value_ints", [4, 5, 6])]),
+                     n("Constant", [], ["yfs"], attrs=[W.attr_floats("value_floats", [0.5, -2.25])]), n("Add", ["x", "yt"], ["y"])],
+        [], {"x": x_of("zoo_Constant", 2, 3)}, ["yt", "yti", "yf", "yi", "yis", "yfs", "y"])
+    add("ConstantOfShape", [n("ConstantOfShape", ["s"], ["yf"], attrs=[W.attr_tensor("value", np.asarray([1.5], np.float32))]), n("ConstantOfShape", ["s"], ["y0"]),
+                            n("ConstantOfShape", ["s"], ["yi"], attrs=[W.attr_tensor("value", np.asarray([7], np.int64))]), n("Shape", ["x"], ["shp"]),
+                            n("ConstantOfShape", ["shp"], ["yx"]), n("Add", ["x", "yf"], ["y"])],
+        [_i("s", [2, 3])], {"x": x_of("zoo_ConstantOfShape", 2, 3)}, ["yf", "y0", "yi", "yx", "y"])
+    add("Range", [n("Range", ["c0", "c20", "c3"], ["yi"]), n("Range", ["f0", "f1", "fd"], ["yf"]), n("Range", ["c20", "c0", "cm7"], ["yneg"]), n("Range", ["c0", "lim", "c3"], ["ydev"]),
+                  n("Range", ["c20", "c0", "c3"], ["yempty"])],
+        [_i("c0", 0), _i("c20", 20), _i("c3", 3), _i("cm7", -7), W.tensor("f0", np.float32(0.5).reshape(())), W.tensor("f1", np.float32(3.0).reshape(())),
+         W.tensor("fd", np.float32(0.75).reshape(()))], {"lim": np.asarray(10, np.int64)}, ["yi", "yf", "yneg", "ydev", "yempty"])
+    xc = _q(_rng("zoo_Cast"), 2, 3, 4) * np.float32(1.25)
+    add("Cast", [n("Cast", ["x"], ["y7"], attrs=[W.attr_int("to", 7)]), n("Cast", ["x"], ["y9"], attrs=[W.attr_int("to", 9)]), n("Cast", ["x"], ["y11"], attrs=[W.attr_int("to", 11)]),
+                 n("Cast", ["x"], ["y6"], attrs=[W.attr_int("to", 6)]), n("Cast", ["xi"], ["yi1"], attrs=[W.attr_int("to", 1)]), n("Cast", ["xi"], ["yi9"], attrs=[W.attr_int("to", 9)]),
+                 n("Cast", ["hi"], ["yh1"], attrs=[W.attr_int("to", 1)]), n("Cast", ["hf"], ["yh7"], attrs=[W.attr_int("to", 7)]), n("Cast", ["hf"], ["yh9"], attrs=[W.attr_int("to", 9)]),
+                 n("Cast", ["hf"], ["yhf1"], attrs=[W.attr_int("to", 1)])],
+        [hi, W.tensor("hf", np.asarray([-1.75, 0.0, 2.5], np.float32))], {"x": xc, "xi": np.asarray([[3, 0], [-2, 1 << 20]], np.int64)},
+        ["y7", "y9", "y11", "y6", "yi1", "yi9", "yh1", "yh7", "yh9", "yhf1"])
+    add("Expand", [n("Expand", ["x", "s"], ["y"]), n("Expand", ["x", "s1"], ["ysame"]), n("Expand", ["h", "sh"], ["y_h"]), n("Expand", ["xi", "s"], ["y_i"])],
+        [_i("s", [2, 3, 4]), _i("s1", [3, 1]), _i("h", [[5], [6]]), _i("sh", [2, 3])], {"x": x_of("zoo_Expand", 3, 1), "xi": np.asarray([[1], [2], [3]], np.int64)}, ["y", "ysame", "y_h", "y_i"])
+    add("Tile", [n("Tile", ["x", "r0"], ["y0"]), n("Tile", ["x", "r1"], ["y1"]), n("Tile", ["hi", "r0"], ["y_h"]), n("Tile", ["x", "rz"], ["yzero"])],
+        [hi, _i("r0", [2, 1]), _i("r1", [1, 3]), _i("rz", [0, 2])], {"x": x_of("zoo_Tile", 2, 3)}, ["y0", "y1", "y_h", "yzero"])
+    rw = _rng("zoo_Where")
+    add("Where", [n("Where", ["c", "a", "b"], ["y"]), n("Where", ["c", "ia", "ib"], ["y_i"]), n("Where", ["hc", "hi", "hj"], ["y_h"]), n("Less", ["a", "b"], ["lt"]),
+                  n("Greater", ["a", "b"], ["gt"]), n("Where", ["c", "lt", "gt"], ["y_b"]), n("Where", ["hc", "a", "hk"], ["y_mixed"])],
+        [hi, _i("hc", [[1], [0]]), _i("hj", [[10, 20]]), _i("hk", [[1], [2]])],
+        {"c": (rw.random((3, 1)) < 0.5).astype(np.float32), "a": _q(rw, 2, 1, 4), "b": _q(rw, 4), "ia": np.asarray([[(1 << 40) + 1], [-3]], np.int64).reshape(2, 1, 1), "ib": np.arange(4, dtype=np.int64)},
+        ["y", "y_i", "y_h", "y_b", "y_mixed"])
+    add("Clip", [n("Clip", ["x", "lo", "hi"], ["y"]), n("Clip", ["x", "lo"], ["ylo"]), n("Clip", ["x", "", "hi"], ["yhi"]), n("Clip", ["x"], ["ynone"]),
+                 n("Clip", ["x"], ["yattr"], attrs=[W.attr_float("min", -0.25), W.attr_float("max", 0.5)])],
+        [W.tensor("lo", np.float32(-0.5).reshape(())), W.tensor("hi", np.float32(0.8).reshape(()))], {"x": x}, ["y", "ylo", "yhi", "ynone", "yattr"])
+    rb = _rng("zoo_BatchNormalization")
+    add("BatchNormalization", [n("BatchNormalization", ["x", "g", "b", "m", "v"], ["y"]), n("BatchNormalization", ["x4", "g", "b", "m", "v"], ["y4"], attrs=[W.attr_float("epsilon", 1e-3)])],
+        [W.tensor("g", _f(rb, 3)), W.tensor("b", _f(rb, 3)), W.tensor("m", _f(rb, 3)), W.tensor("v", (rb.random(3) + 0.5).astype(np.float32))],
+        {"x": x, "x4": _f(rb, 2, 3, 2, 5)}, ["y", "y4"])
+    add("Pad", [n("Pad", ["x", "p6", "pv"], ["yc"]), n("Pad", ["x", "p2", "", "axm1"], ["yr"], attrs=[W.attr_str("mode", "reflect")]),
+                n("Pad", ["x", "p4", "", "ax02"], ["ye"], attrs=[W.attr_str("mode", "edge")]),
+                n("Pad", ["x"], ["yattr"], attrs=[W.attr_ints("pads", [0, 1, 0, 0, 0, 2]), W.attr_float("value", -1.0)]), n("Pad", ["x", "pneg"], ["ycrop"])],
+        [_i("p6", [1, 0, 2, 0, 1, 0]), W.tensor("pv", np.float32(0.25).reshape(())), _i("p2", [2, 3]), _i("axm1", [-1]), _i("p4", [1, 2, 0, 1]), _i("ax02", [0, -1]),
+         _i("pneg", [0, 0, -1, 0, 0, 0])], {"x": x}, ["yc", "yr", "ye", "yattr", "ycrop"])
+    x2345 = x_of("zoo_pool", 2, 3, 4, 5)
+    add("GlobalAveragePool", [n("GlobalAveragePool", ["x"], ["y"]), n("GlobalAveragePool", ["x3"], ["y3"])], [], {"x": x2345, "x3": x}, ["y", "y3"])
+    add("GlobalMaxPool", [n("GlobalMaxPool", ["x"], ["y"]), n("GlobalMaxPool", ["x3"], ["y3"])], [], {"x": x2345, "x3": x}, ["y", "y3"])
+    add("Trilu", [n("Trilu", ["x"], ["yu"]), n("Trilu", ["x", "km1"], ["yl"], attrs=[W.attr_int("upper", 0)]), n("Trilu", ["x", "k1"], ["yu1"]), n("Trilu", ["xi"], ["y_i"], attrs=[W.attr_int("upper", 0)])],
+        [_i("km1", -1), _i("k1", 1)], {"x": x_of("zoo_Trilu", 2, 4, 5), "xi": np.arange(12, dtype=np.int64).reshape(3, 4) + 1}, ["yu", "yl", "yu1", "y_i"])
+    rg = _rng("zoo_GatherElements")
+    add("GatherElements", [n("GatherElements", ["x", "i1"], ["y1"], attrs=[W.attr_int("axis", 1)]), n("GatherElements", ["x", "im1"], ["ym1"], attrs=[W.attr_int("axis", -1)]),
+                           n("GatherElements", ["x", "i0"], ["y0"]), n("GatherElements", ["xi", "ii"], ["y_i"], attrs=[W.attr_int("axis", 1)])],
+        [_i("i1", rg.integers(-4, 4, (3, 2, 5))), _i("im1", rg.integers(-5, 5, (3, 4, 7))), _i("i0", rg.integers(0, 3, (1, 4, 5))), _i("ii", [[1, 0, 0], [-1, -2, 1]])],
+        {"x": x345, "xi": np.asarray([[(1 << 40) + 1, 2], [3, -(1 << 41)]], np.int64)}, ["y1", "ym1", "y0", "y_i"])
+    add("ScatterND", [n("ScatterND", ["kv", "i3", "u3"], ["y3"]), n("ScatterND", ["kv", "i2", "u2"], ["y2"]), n("ScatterND", ["kv", "i4", "u4"], ["y4"])],
+        [_i("i3", [[0, 1, 2], [0, 0, 8], [0, -1, 0]]), _i("i2", [[0, 1], [0, 0]]), _i("i4", [[0, 1, 8, 3], [0, 0, 0, 0]])],
+        {"kv": x_of("zoo_ScatterND", 1, 2, 9, 4), "u3": x_of("zoo_ScatterND_u3", 3, 4), "u2": x_of("zoo_ScatterND_u2", 2, 9, 4), "u4": x_of("zoo_ScatterND_u4", 2)}, ["y3", "y2", "y4"])
+    x1234 = x_of("zoo_Resize", 1, 2, 3, 4)
+    native = [W.attr_str("mode", "nearest"), W.attr_str("coordinate_transformation_mode", "asymmetric"), W.attr_str("nearest_mode", "floor")]
+    add("Resize", [n("Resize", ["x", "roi", "sc"], ["ys"], attrs=native), n("Resize", ["x", "roi", "", "sz"], ["yz"], attrs=native), n("Resize", ["x", "", "sc"], ["ydef"]),
+                   n("Resize", ["x", "", "sc15"], ["y15"], attrs=native)],
+        [W.tensor("sc", np.asarray([1, 1, 2, 3], np.float32)), W.tensor("sc15", np.asarray([1, 1, 1.5, 0.5], np.float32)), W.tensor("roi", np.zeros(0, np.float32)), _i("sz", [1, 2, 6, 4])],
+        {"x": x1234}, ["ys", "yz", "ydef", "y15"], opset=13)
+    add("Resize", [n("Resize", ["x", "sc"], ["y"]), n("Resize", ["x", "sc"], ["ymode"], attrs=[W.attr_str("mode", "nearest")])],
+        [W.tensor("sc", np.asarray([1, 1, 2, 3], np.float32))], {"x": x1234}, ["y", "ymode"], opset=10, name="zoo_resize_opset10")
+    add("Softmax", [n("Softmax", ["x"], ["ydef"]), n("Softmax", ["x"], ["y0"], attrs=[W.attr_int("axis", 0)]), n("Softmax", ["x"], ["ym1"], attrs=[W.attr_int("axis", -1)]),
+                    n("LogSoftmax", ["x"], ["ylog2"], attrs=[W.attr_int("axis", 2)]), n("LogSoftmax", ["x"], ["ylogdef"])],
+        [], {"x": x}, ["ydef", "y0", "ym1", "ylog2", "ylogdef"], opset=12, name="zoo_softmax_opset12")
+    add("Softmax", [n("Softmax", ["x"], ["ydef"]), n("Softmax", ["x"], ["y0"], attrs=[W.attr_int("axis", 0)]), n("Softmax", ["x"], ["ym2"], attrs=[W.attr_int("axis", -2)]),
+                    n("LogSoftmax", ["x"], ["ylog0"], attrs=[W.attr_int("axis", -3)]), n("Softmax", ["hi"], ["y_h"])],
+        [hi], {"x": x}, ["ydef", "y0", "ym2", "ylog0", "y_h"], opset=13, name="zoo_softmax_axes")
+    # the reduce family: pass-through with noop_with_empty_axes (the node after it still finds its input), the host evaluator, negative and non-last axes
+    add("ReduceSum", [n("ReduceSum", ["x", "none"], ["ynoop"], attrs=[W.attr_int("noop_with_empty_axes", 1)]), n("Neg", ["ynoop"], ["yafter"]),
+                      n("ReduceMean", ["x", "none"], ["ymnoop"], attrs=[W.attr_int("noop_with_empty_axes", 1), W.attr_int("keepdims", 0)]),
+                      n("ReduceMax", ["x", "none"], ["yall"], attrs=[W.attr_int("keepdims", 0)]),
+                      n("ReduceSum", ["hi", "none"], ["y_hnoop"], attrs=[W.attr_int("noop_with_empty_axes", 1)])],
+        [hi, _i("none", np.zeros((0,), np.int64))], {"x": x}, ["ynoop", "yafter", "ymnoop", "yall", "y_hnoop"], opset=18, name="zoo_reduce_noop_empty_axes")
+    hnodes, houts = [n("Shape", ["x"], ["shp"])], []
+    for op in ("ReduceSum", "ReduceProd", "ReduceMax", "ReduceMin", "ReduceMean"):
+        hnodes += [n(op, ["shp"], ["s_" + op], attrs=[W.attr_int("keepdims", 0)]), n(op, ["hi", "am1"], ["h_" + op]), n(op, ["hi", "a0"], ["h0_" + op], attrs=[W.attr_int("keepdims", 0)])]
+        houts += ["s_" + op, "h_" + op, "h0_" + op]
+    hnodes += [n("ReduceL1", ["hi", "am1"], ["h_l1"]), n("ArgMax", ["hi"], ["h_argmax"], attrs=[W.attr_int("axis", -1)]),
+               n("ArgMin", ["x"], ["argmin_m2"], attrs=[W.attr_int("axis", -2), W.attr_int("keepdims", 0)]), n("ArgMax", ["x"], ["argmax_0"])]
+    add("ReduceProd", hnodes, [hi, _i("am1", [-1]), _i("a0", [0])], {"x": x}, houts + ["h_l1", "h_argmax", "argmin_m2", "argmax_0"], opset=18, name="zoo_reduce_host_and_arg_axes")
+    # forms of the row operators that the row table leaves out: a non-last normalised extent, no bias, per-group affine, a middle LpNormalization axis
+    rn = _rng("zoo_norm_forms")
+    add("LayerNormalization", [n("LayerNormalization", ["x", "g34"], ["y1"], attrs=[W.attr_int("axis", 1)]), n("LayerNormalization", ["x", "g4", "b4"], ["ym1"]),
+                               n("LayerNormalization", ["x", "g34", "b34"], ["ym2"], attrs=[W.attr_int("axis", -2), W.attr_float("epsilon", 1e-3)]),
+                               n("GroupNormalization", ["x4", "gg", "gb"], ["ygn"], attrs=[W.attr_int("num_groups", 2)]),
+                               n("LpNormalization", ["x"], ["ylp1"], attrs=[W.attr_int("axis", 1), W.attr_int("p", 1)]), n("LpNormalization", ["x"], ["ylp0"], attrs=[W.attr_int("axis", -3)]),
+                               n("InstanceNormalization", ["x4", "ig", "ib"], ["yin"]), n("CumSum", ["x", "c0"], ["ycs0"], attrs=[W.attr_int("reverse", 1)]), n("CumSum", ["x", "cm2"], ["ycsm2"])],
+        [W.tensor("g34", _f(rn, 3, 4)), W.tensor("b34", _f(rn, 3, 4)), W.tensor("g4", _f(rn, 4)), W.tensor("b4", _f(rn, 4)), W.tensor("gg", _f(rn, 2)), W.tensor("gb", _f(rn, 2)),
+         W.tensor("ig", _f(rn, 4)), W.tensor("ib", _f(rn, 4)), _i("c0", 0), _i("cm2", -2)],
+        {"x": x, "x4": _f(rn, 2, 4, 3, 2)}, ["y1", "ym1", "ym2", "ygn", "ylp1", "ylp0", "yin", "ycs0", "ycsm2"], opset=18, name="zoo_row_forms")
+    return out
+
+
+def zoo_cases():
+    cases = _zoo_unary() + _zoo_binary() + _zoo_other()
+    names = [c.name for c in cases]
+    assert len(set(names)) == len(names)
+    return cases
+
+
 # ------------------------------------------------------------------------------------------------------------------ running a case
+def run_outputs(q3, tmp_dir, case):
+    """-> ({output name: array}, launches of the run) of any case, with or without a reference (the declared output shapes are not read by the executor)"""
+    path = os.path.join(str(tmp_dir), case.name + ".onnx")
+    ins = [W.value_info(k, I64 if np.issubdtype(np.asarray(v).dtype, np.integer) else F32, list(np.asarray(v).shape)) for k, v in case.feeds.items()]
+    outs = case.out if isinstance(case.out, (list, tuple)) else [case.out]
+    with open(path, "wb") as f:
+        f.write(W.model(case.nodes, case.inits, ins, [W.value_info(o, F32, []) for o in outs], opset=case.opset))
+    s = q3.OnnxSession(path)
+    try:
+        assert s.unsupported() == [], s.unsupported()
+        r = s.run(case.feeds, list(outs))
+        n = s.launches()
+    finally:
+        s.close()
+    return r, n
+
+
+def digest_cases(q3, tmp_dir):
+    """{case name: {"ops": operator names of the graph, "sha256": over dtype, shape and bytes of every output in order, "launches": of the run}}
+    for every product, row and zoo case, on whichever kernel family the loaded library runs (scripts/onnx_exec_digest.py)"""
+    import hashlib
+    res = {}
+    for case in product_cases() + row_cases() + zoo_cases():
+        got, launches = run_outputs(q3, tmp_dir, case)
+        h = hashlib.sha256()
+        for o in (case.out if isinstance(case.out, (list, tuple)) else [case.out]):
+            a = np.ascontiguousarray(got[o])
+            h.update(("%s %s %s;" % (o, a.dtype.str, list(a.shape))).encode())
+            h.update(a.tobytes())
+        m = q3.OnnxModel(os.path.join(str(tmp_dir), case.name + ".onnx"))
+        ops = sorted({m.node(i)["op_type"] for i in range(m.n_nodes)})
+        m.close()
+        assert case.name not in res
+        res[case.name] = {"ops": ops, "sha256": h.hexdigest(), "launches": int(launches)}
+    return res
+
+
 def run_case(q3, tmp_dir, case):
     """-> (output array, launches of the run)"""
     path = os.path.join(str(tmp_dir), case.name + ".onnx")

@@ -727,6 +727,36 @@ def test_malformed_graphs_are_errors_not_faults(gpu, tmp_path):
     assert np.array_equal(r["y"], np.repeat(x, 2, axis=2))
 
 
+def test_axis_out_of_range_is_an_error(gpu, tmp_path):
+    """Flatten, Softmax, LogSoftmax, CumSum, LpNormalization, GatherElements and Slice used to add the rank to a negative axis and index the
+    shape with whatever came out.  Every handler now takes its axis through the one checked normalisation (axis_of, csrc/onnx_shape.h): an
+    axis outside [-rank, rank) is an error of that node before anything is allocated or launched, and the library carries on."""
+    x = np.arange(6, dtype=np.float32).reshape(2, 3)
+    idx = np.zeros((2, 3), np.int64)
+    i = lambda name, v: W.tensor(name, np.asarray(v, np.int64))
+    graphs = {
+        "Flatten": lambda a: ([W.node("Flatten", ["x"], ["y"], "n0", [W.attr_int("axis", a)])], []),
+        "Softmax": lambda a: ([W.node("Softmax", ["x"], ["y"], "n0", [W.attr_int("axis", a)])], []),
+        "LogSoftmax": lambda a: ([W.node("LogSoftmax", ["x"], ["y"], "n0", [W.attr_int("axis", a)])], []),
+        "CumSum": lambda a: ([W.node("CumSum", ["x", "ax"], ["y"], "n0")], [i("ax", a)]),
+        "LpNormalization": lambda a: ([W.node("LpNormalization", ["x"], ["y"], "n0", [W.attr_int("axis", a)])], []),
+        "GatherElements": lambda a: ([W.node("GatherElements", ["x", "idx"], ["y"], "n0", [W.attr_int("axis", a)])], []),
+        "Slice": lambda a: ([W.node("Slice", ["x", "st", "en", "ax"], ["y"], "n0")], [i("st", [0]), i("en", [1]), i("ax", [a])]),
+    }
+    for op, make in graphs.items():
+        for axis in (5, -5):
+            nodes, inits = make(axis)
+            with pytest.raises(gpu.Q3Error) as e:
+                run_graph(gpu, tmp_path, nodes, inits, {"x": x, "idx": idx}, [("y", F32, [2, 3])])
+            msg = str(e.value)
+            assert "node 0 (" + op + " 'n0')" in msg and "axis out of range" in msg, msg
+        nodes, inits = make(-1)                                           # the same graph with an axis inside the range runs, in the same process
+        r = run_graph(gpu, tmp_path, nodes, inits, {"x": x, "idx": idx}, [("y", F32, [2, 3])])
+        assert np.all(np.isfinite(r["y"])), op
+    good = run_graph(gpu, tmp_path, [W.node("Add", ["x", "x"], ["y"])], [], {"x": x, "idx": idx}, [("y", F32, [2, 3])])
+    assert np.array_equal(good["y"], x + x)
+
+
 def test_decoder_state_import_rejects_bad_blobs(gpu, tiny_model):
     """q3tts_decoder_state_import validates the caller's length and the blob's trailer before committing: a blob of another size, a cached-position
     count outside the attention window, NaN or negative counters are errors -- not out-of-range device indexing on the next decode."""
