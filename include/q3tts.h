@@ -1164,6 +1164,32 @@ int q3tts_op_loudness(const float* in, int32_t G, const int32_t* chunk_samples, 
                       const int32_t* metered, const int32_t* reset_before, double* const* rows, const int64_t* rows_bytes, int64_t* n_rows,
                       double* state_store);
 
+/* [EXT] reference audio intake (q3tts_spec.h "reference audio intake"): reference audio in the caller's rate, sample format and channel
+ * count, decoded, downmixed and resampled to the encoders' mono f32 at 24000 Hz on the device.  Host only (no device needed):
+ *   q3tts_intake_plan      24000 / rate = L / M, the prototype's tap count N and the most taps one output sample sums (24000: 1, 1, 0, 0);
+ *                          < 0 for a rate the intake does not take.  Any output pointer may be NULL
+ *   q3tts_intake_filter    the f32 prototype h32[0..N) into h32[cap]; returns N, < 0 for such a rate or cap < N
+ *   q3tts_intake_samples   ceil(n_frames L / M); < 0 for such a rate or n_frames < 0
+ *   q3tts_intake_tile      output samples one block of the kernel computes at this rate (a multiple of 4 in [64, 1024]); < 0 for such a rate
+ *   q3tts_intake_check     0 if the clip may run, else < 0 and q3tts_last_error says why: the rate, channels outside [1, 8], the sample
+ *                          format, the downmix, n_frames < 1, more than 120 s of output, NULL data
+ *   q3tts_wav_probe        reads a RIFF/WAVE header from bytes[0..n): PCM (tag 1) at 8, 16, 24, 32 bits, IEEE float (tag 3) at 32 bits, and
+ *                          WAVE_FORMAT_EXTENSIBLE of either; chunks in any order with fmt before data, odd chunks padded; a data chunk
+ *                          longer than the file is cut to the file.  Anything else is < 0 with a reason; no byte at or past n is read
+ * q3tts_intake: n_clips in [1, 64] clips in one launch.  out[i] receives exactly n_out[i] = q3tts_intake_samples(rate_i, n_frames_i) floats
+ * and must hold out_cap[i] >= that many.  Everything is checked before anything is launched, and a refused or failed call writes neither
+ * out nor n_out; a clip with a non-finite sample fails the call, and the error names the clip.  Safe beside running engines.
+ * q3tts_wav_intake: a WAV file through q3tts_wav_probe and q3tts_intake; info (optional) receives the header.  cap < the sample count is
+ * refused; with out == NULL and cap == 0 only *n_out and *info are written (a size query, no device needed). */
+int q3tts_intake_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_output);
+int64_t q3tts_intake_filter(int32_t rate, float* h32, int64_t cap);
+int64_t q3tts_intake_samples(int32_t rate, int64_t n_frames);
+int32_t q3tts_intake_tile(int32_t rate);
+int q3tts_intake_check(const q3tts_intake_clip* c);
+int q3tts_wav_probe(const void* bytes, int64_t n, q3tts_wav_info* out);
+int q3tts_intake(int32_t device, const q3tts_intake_clip* clips, int32_t n_clips, float* const* out, const int64_t* out_cap, int64_t* n_out);
+int q3tts_wav_intake(const char* path, int32_t downmix, int32_t device, float* out, int64_t cap, int64_t* n_out, q3tts_wav_info* info);
+
 #ifdef __cplusplus
 }
 #endif

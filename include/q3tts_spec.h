@@ -624,6 +624,42 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 #define Q3TTS_STEM_READY 1
 #define Q3TTS_STEM_FAILED -1
 
+/* ---------------- reference audio intake [EXT] (q3tts_intake*, q3tts_wav_probe, q3tts_wav_intake) ----------------
+ * The encoders read mono f32 at 24000 Hz.  The intake makes that of a clip in the caller's form: n frames of C interleaved channels at R Hz
+ * in one of five sample formats.  It stands in front of the encoders as "output formats" stands behind the codec, with the same prototype.
+ *   decode     u8 (v - 128) / 128; s16 v / 32768; s24 (3 bytes, little endian, sign-extended) v / 8388608; s32 (float)v / 2147483648;
+ *              f32 as it is.  All in f32; s16, s32 and f32 are the reference's own arithmetic (engine.rs:348-359)
+ *   downmix    Q3_INTAKE_FIRST: channel 0 (the reference).  Q3_INTAKE_MEAN: ((x0 + x1) + ... + x[C-1]) / (float)C, f32 adds in channel
+ *              order and one f32 division (upstream's mono)
+ *   ratio      L / M = 24000 / R in lowest terms, F = max(L, M), c = Z F, h32 = the prototype of "output formats" for this (L, M):
+ *              N = 2 Z F + 1 taps, h[i] = L * 2fc * sinc(2fc (i - c)) * kaiser_9(i), fc = 0.9 / (2F), in double, rounded to f32
+ *   sample     the clip is zero outside [0, n).  y[m] = sum over i of h32[c + m M - i L] * x[i], m in [0, n_out), n_out = ceil(n L / M):
+ *              zero phase, nothing delayed and nothing dropped.  With t = m M + c, p = t mod L, j = t div L:
+ *              y[m] = sum over k = 0, 1, ... with p + k L < N of h32[p + k L] * x[j - k].  One f32 accumulator starting at +0, k ascending,
+ *              one fmaf per term (the converter's order).  No clamp: the encoders take what the reference would hand them
+ *   24000      no filter: y is the decoded, downmixed clip bit for bit
+ *   accepted   R in [8000, 192000] with max(L, M) <= Q3_INTAKE_MAX_F (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 64000,
+ *              88200, 96000, 176400, 192000 among them); C in [1, 8]; n >= 1; n_out <= Q3_INTAKE_MAX_OUT (120 s), which keeps m M + c and
+ *              i L below 2^31; at most Q3_INTAKE_MAX_CLIPS clips per call
+ *   non-finite a downmixed sample that is not finite (an f32 clip's NaN or infinity, or a mean that overflows) fails the call, which names
+ *              the clip; no output of that call is delivered
+ * One output sample sums at most ceil(N / L) terms: 33 when upsampling, up to 257 at 192000 Hz. */
+#define Q3_INTAKE_U8 0
+#define Q3_INTAKE_S16 1
+#define Q3_INTAKE_S24 2
+#define Q3_INTAKE_S32 3
+#define Q3_INTAKE_F32 4
+#define Q3_INTAKE_FIRST 0
+#define Q3_INTAKE_MEAN 1
+#define Q3_INTAKE_MIN_RATE 8000
+#define Q3_INTAKE_MAX_RATE 192000
+#define Q3_INTAKE_MAX_F 320
+#define Q3_INTAKE_MAX_CH 8
+#define Q3_INTAKE_MAX_OUT 2880000
+#define Q3_INTAKE_MAX_CLIPS 64
+typedef struct { const void* data; int64_t n_frames; int32_t sample_rate, channels, sample_format, downmix; } q3tts_intake_clip;
+typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t data_offset, n_frames; } q3tts_wav_info;
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

@@ -10,6 +10,7 @@
 #include "pitch.h"
 #include "volume.h"
 #include "loudness.h"
+#include "intake.h"
 #include <memory>
 #include "mel.h"
 
@@ -1545,6 +1546,102 @@ int q3tts_op_loudness(const float* in, int32_t G, const int32_t* chunk_samples, 
 }
 
 int q3tts_mel_frames(int32_t n) { return mel_frames(n); }
+
+/* [EXT] reference audio intake: the host-only half (intake.h) */
+int q3tts_intake_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* n_taps, int32_t* taps_per_output) {
+    Q3_API_BEGIN
+    IntakePlan p;
+    if (const char* why = intake_rate_why_not(rate)) throw Error(why);
+    Q3_CHECK(intake_plan(rate, &p), "no tile fits this ratio");
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (n_taps) *n_taps = p.n_taps;
+    if (taps_per_output) *taps_per_output = p.taps;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int64_t q3tts_intake_filter(int32_t rate, float* h32, int64_t cap) {
+    Q3_API_BEGIN
+    if (const char* why = intake_rate_why_not(rate)) throw Error(why);
+    const std::vector<float> h = intake_filter(rate);
+    Q3_CHECK((h32 || h.empty()) && cap >= (int64_t)h.size(), "h32 is too small for the rate's taps");
+    std::copy(h.begin(), h.end(), h32);
+    return (int64_t)h.size();
+    Q3_API_END(Q3TTS_ERR)
+}
+int64_t q3tts_intake_samples(int32_t rate, int64_t n_frames) {
+    Q3_API_BEGIN
+    if (const char* why = intake_rate_why_not(rate)) throw Error(why);
+    Q3_CHECK(n_frames >= 0, "negative frame count");
+    return intake_samples(rate, n_frames);
+    Q3_API_END(Q3TTS_ERR)
+}
+int32_t q3tts_intake_tile(int32_t rate) {
+    Q3_API_BEGIN
+    IntakePlan p;
+    if (const char* why = intake_rate_why_not(rate)) throw Error(why);
+    Q3_CHECK(intake_plan(rate, &p), "no tile fits this ratio");
+    return p.tile;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_intake_check(const q3tts_intake_clip* c) {
+    Q3_API_BEGIN
+    if (const char* why = intake_refusal(c)) throw Error(std::string("intake: ") + why);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_wav_probe(const void* bytes, int64_t n, q3tts_wav_info* out) {
+    Q3_API_BEGIN
+    q3tts_wav_info w{};
+    if (const char* why = wav_probe(bytes, n, &w)) throw Error(std::string("WAV error: ") + why);
+    *out = w;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+/* [EXT] the intake itself: host clips in, host samples out, one launch of k_intake (intake.hip) */
+int q3tts_intake(int32_t device, const q3tts_intake_clip* clips, int32_t n_clips, float* const* out, const int64_t* out_cap, int64_t* n_out) {
+    Q3_API_BEGIN
+    require_gpu();
+    int nd = 0;
+    Q3_HIP(hipGetDeviceCount(&nd));
+    Q3_CHECK(device >= 0 && device < nd, "device out of range");
+    intake_run(intake_stage(device), clips, n_clips, out, out_cap, n_out);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+int q3tts_wav_intake(const char* path, int32_t downmix, int32_t device, float* out, int64_t cap, int64_t* n_out, q3tts_wav_info* info) {
+    Q3_API_BEGIN
+    Q3_CHECK(path && n_out, "null argument");
+    FILE* f = fopen(path, "rb");
+    if (!f) throw Error(std::string("WAV error: cannot open ") + path);
+    std::vector<unsigned char> d;
+    unsigned char buf[65536];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof(buf), f)) > 0) d.insert(d.end(), buf, buf + got);
+    fclose(f);
+    q3tts_wav_info w{};
+    if (const char* why = wav_probe(d.data(), (int64_t)d.size(), &w)) throw Error(std::string("WAV error: ") + why);
+    const q3tts_intake_clip c{d.data() + w.data_offset, w.n_frames, w.sample_rate, w.channels, w.sample_format, downmix};
+    if (const char* why = intake_refusal(&c)) throw Error(std::string("intake: ") + why);
+    const int64_t n = intake_samples(c.sample_rate, c.n_frames);
+    if (!out && cap == 0) {   // the size query
+        *n_out = n;
+        if (info) *info = w;
+        return Q3TTS_OK;
+    }
+    require_gpu();
+    int nd = 0;
+    Q3_HIP(hipGetDeviceCount(&nd));
+    Q3_CHECK(device >= 0 && device < nd, "device out of range");
+    int64_t cnt = 0;
+    float* const outs[1] = {out};
+    intake_run(intake_stage(device), &c, 1, outs, &cap, &cnt);
+    *n_out = cnt;
+    if (info) *info = w;
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
 
 } // extern "C"
 

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <map>
+#include <mutex>
 #include <vector>
 #include "wlayout.h"
 #include "q3_common.h"
@@ -386,6 +388,39 @@ struct PcmConverter {
 // format, a stream out of range or listed twice.
 void launch_pcm_convert(hipStream_t st, PcmConverter& c, const float* in, int G, int T, const int32_t* streams, const q3tts_pcm_format* fmt,
                         void* out, const int64_t* out_off, int64_t* n_out);
+
+// [EXT] reference audio intake (intake.hip, q3tts_spec.h "reference audio intake"): decode, downmix and resampling to 24000 Hz in front
+// of the encoders.  One entry per clip of a launch.
+struct IntakeClipMeta {
+    const unsigned char* src; // the clip's raw interleaved samples, on the device, aligned to its sample size (3-byte samples to nothing)
+    float* dst;               // its n_out output samples, 16-byte aligned
+    const float* tab;         // the ratio's table, phase-major [L][stride]; unused at 24000 Hz
+    int32_t n, n_out;         // input frames; output samples
+    int32_t L, M, stride, c;  // the ratio, floats per phase row (0: 24000 Hz, no filter), the prototype's centre
+    int32_t tile, win;        // outputs per block; floats of LDS set aside for a tile's input window
+    int32_t C, fmt, mix;      // channels, Q3_INTAKE_U8 .. F32, Q3_INTAKE_FIRST / MEAN
+    int32_t flag_off;         // the clip's first entry of the launch's flag array, one per tile
+};
+struct IntakePlan;
+// A device's intake state: the tables of the ratios it has met, each built and uploaded once.  intake_stage(device) is the process's one
+// stage of that device; intake_run serialises its callers.
+struct IntakeStage {
+    explicit IntakeStage(int device);
+    IntakeStage(const IntakeStage&) = delete; IntakeStage& operator=(const IntakeStage&) = delete;
+    const float* table(int rate, IntakePlan* plan);   // under mu and capture_mutex(), on the stage's device
+    int device;
+    std::mutex mu;
+    std::map<int, DevBuf<float>> tabs;
+    // a call's raw clips, samples, per-tile flags and meta entries on the device: grown as calls need, kept for the next one
+    DevBuf<unsigned char> in; DevBuf<float> out; DevBuf<int32_t> flags; DevBuf<IntakeClipMeta> meta;
+};
+IntakeStage& intake_stage(int device);
+// the kernel alone: grid (tiles, n_clips); d_flags holds one int per tile of every clip, and every tile within a clip's n_out writes its own
+void launch_intake(hipStream_t st, const IntakeClipMeta* d_meta, int n_clips, int tiles, int32_t* d_flags);
+// host buffers in, host buffers out, synchronous: clip i's ceil(n L / M) samples go to out[i] (capacity out_cap[i] floats), their count to
+// n_out[i].  Refused (intake_refusal, intake.h; a short capacity; more than 64 clips) before anything is allocated; a clip with a
+// non-finite sample fails the call after the launch and before any output is copied.  A failed call writes nothing.
+void intake_run(IntakeStage& s, const q3tts_intake_clip* clips, int n_clips, float* const* out, const int64_t* out_cap, int64_t* n_out);
 
 // [EXT] speaking rate (tsm.hip, q3tts_spec.h "speaking rate"): WSOLA time-scale change behind the codec.
 // One entry per stream of a launch, written by launch_tsm_stretch into the stretcher's upload ring.  The counts are data-independent, so the

@@ -253,7 +253,7 @@ TtsEngine& TtsEngine::operator=(TtsEngine&& o) noexcept {
         if (enc_) q3tts_onnx_session_close(enc_);
         if (spk_) q3tts_onnx_session_close(spk_);
         enc_ = o.enc_; spk_ = o.spk_; o.enc_ = o.spk_ = nullptr;
-        if (e_) q3tts_engine_destroy(e_); e_ = o.e_; o.e_ = nullptr; tok_ = std::move(o.tok_); speakers_ = std::move(o.speakers_); max_steps_ = o.max_steps_; sampler_ = o.sampler_;
+        if (e_) q3tts_engine_destroy(e_); e_ = o.e_; o.e_ = nullptr; tok_ = std::move(o.tok_); speakers_ = std::move(o.speakers_); max_steps_ = o.max_steps_; sampler_ = o.sampler_; intake_ = o.intake_;
     }
     return *this;
 }
@@ -339,7 +339,7 @@ AudioSample TtsEngine::generate_ids(const std::vector<int32_t>& text_ids, const 
     std::string cache_path = ref_audio_path;
     const size_t slash = cache_path.find_last_of('/'), dot = cache_path.find_last_of('.');
     if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) cache_path.resize(dot);
-    cache_path += ".cache"; // Path::with_extension("cache")
+    cache_path += intake_ >= 0 ? ".intake.cache" : ".cache"; // Path::with_extension("cache"); [EXT] the intake keeps a cache of its own
     VoiceFile v;
     bool hit = false;
     if (FILE* f = fopen(cache_path.c_str(), "rb")) {
@@ -348,7 +348,7 @@ AudioSample TtsEngine::generate_ids(const std::vector<int32_t>& text_ids, const 
     }
     if (!hit) {
         AudioSample a;
-        try { a = AudioSample::load_wav(ref_audio_path); } catch (const std::exception& e) { throw std::runtime_error(std::string("Failed to load audio: ") + e.what()); }
+        try { if (intake_ >= 0) a.samples = read_reference(ref_audio_path); else a = AudioSample::load_wav(ref_audio_path); } catch (const std::exception& e) { throw std::runtime_error(std::string("Failed to load audio: ") + e.what()); }
         if (!enc_) throw std::runtime_error("AudioEncoder not loaded (required for processing raw audio)");     // :288-290
         try { v.audio_codes = encode_audio(a.samples); } catch (const std::exception& e) { throw std::runtime_error(std::string("Audio encode failed: ") + e.what()); }
         if (!spk_) throw std::runtime_error("SpeakerEncoder not loaded (required for processing raw audio)"); // :294-296
@@ -511,10 +511,24 @@ static std::vector<float> read_wav_for_voice(const std::string& path) {
     throw std::runtime_error("WAV error: no data chunk found");
 }
 
+void TtsEngine::set_reference_intake(int mode) {
+    if (mode != -1 && mode != Q3_INTAKE_FIRST && mode != Q3_INTAKE_MEAN) throw std::runtime_error("reference intake mode must be -1, Q3_INTAKE_FIRST or Q3_INTAKE_MEAN");
+    intake_ = mode;
+}
+std::vector<float> TtsEngine::read_reference(const std::string& path) const {
+    const int32_t dev = q3tts_engine_device(e_);
+    int64_t n = 0;
+    if (q3tts_wav_intake(path.c_str(), intake_, dev, nullptr, 0, &n, nullptr) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error()); // the size
+    std::vector<float> audio((size_t)n);
+    if (q3tts_wav_intake(path.c_str(), intake_, dev, audio.data(), n, &n, nullptr) != Q3TTS_OK) throw std::runtime_error(q3tts_last_error());
+    audio.resize((size_t)n);
+    return audio;
+}
+
 VoiceFile TtsEngine::create_voice_file(const std::string& audio_path, const std::string& ref_text) { // engine.rs:324-387
     if (!enc_) throw std::runtime_error("AudioEncoder not loaded. Please ensure models/onnx/qwen3_tts_codec_encoder.onnx exists.");
     if (!spk_) throw std::runtime_error("SpeakerEncoder not loaded. Please ensure models/onnx/qwen3_tts_speaker_encoder.onnx exists.");
-    const std::vector<float> audio = read_wav_for_voice(audio_path);
+    const std::vector<float> audio = intake_ >= 0 ? read_reference(audio_path) : read_wav_for_voice(audio_path);
     VoiceFile v;
     v.ref_text = ref_text;
     v.audio_codes = encode_audio(audio);

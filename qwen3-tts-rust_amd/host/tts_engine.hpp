@@ -90,6 +90,12 @@ public:
     // f-2): <model_dir>/onnx/qwen3_tts_codec_encoder.onnx ("input_values" [1, T] -> "audio_codes") and qwen3_tts_speaker_encoder.onnx ("mels"
     // [1, n, 128] from q3tts_mel -> "spk_emb"), loaded when the files exist (engine.rs:106-127); without them the reference's errors are returned.
     VoiceFile create_voice_file(const std::string& audio_path, const std::string& ref_text);
+    // [EXT] reference audio intake (q3tts_wav_intake): -1 = off, the default and the reference's behaviour -- create_voice_file refuses anything
+    // but 24000 Hz and generate reads every file as 24000 Hz mono s16.  Q3_INTAKE_FIRST or Q3_INTAKE_MEAN: both read the WAV at any accepted
+    // rate, sample format and channel count, resampled to 24000 Hz on the device, and generate keeps its cache in "<stem>.intake.cache", so a
+    // ".cache" written from a misread clip is never picked up.  Throws for any other mode
+    void set_reference_intake(int mode);
+    int reference_intake() const { return intake_; }
     bool has_encoders() const { return enc_ && spk_; }
     std::vector<int64_t> encode_audio(const std::vector<float>& audio) const;       // AudioEncoder::encode, onnx.rs:97-121
     std::vector<float> encode_speaker(const std::vector<float>& audio) const;       // SpeakerEncoder::encode, onnx.rs:140-163
@@ -104,6 +110,8 @@ private:
     std::map<std::string, VoiceFile> speakers_;
     size_t max_steps_ = 512;
     SamplerConfig sampler_;
+    int intake_ = -1;
+    std::vector<float> read_reference(const std::string& path) const;   // the intake's mono 24000 Hz samples of a WAV file (intake_ >= 0)
 };
 
 } // namespace q3tts

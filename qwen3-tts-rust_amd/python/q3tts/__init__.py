@@ -118,7 +118,20 @@ SYMBOLS = [
     "q3tts_engine_set_loudness", "q3tts_fetch_loudness", "q3tts_request_loudness", "q3tts_request_metered", "q3tts_engine_loudness_stats",
     "q3tts_group_set_loudness", "q3tts_group_fetch_loudness", "q3tts_group_request_loudness", "q3tts_group_request_metered",
     "q3tts_loudness_tables", "q3tts_loudness_gate", "q3tts_loudness_gain_db10", "q3tts_op_loudness",
+    "q3tts_intake_plan", "q3tts_intake_filter", "q3tts_intake_samples", "q3tts_intake_tile", "q3tts_intake_check", "q3tts_wav_probe",
+    "q3tts_intake", "q3tts_wav_intake",
 ]
+
+
+class IntakeClip(C.Structure):  # q3tts_intake_clip
+    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_int64), ("sample_rate", C.c_int32), ("channels", C.c_int32),
+                ("sample_format", C.c_int32), ("downmix", C.c_int32)]
+
+
+class WavInfo(C.Structure):  # q3tts_wav_info
+    _fields_ = [("sample_format", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("bits", C.c_int32),
+                ("data_offset", C.c_int64), ("n_frames", C.c_int64)]
+
 
 class PcmFormat(C.Structure):  # q3tts_pcm_format
     _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32)]
@@ -141,6 +154,10 @@ TSM_HOP, TSM_WIN, TSM_SEARCH, TSM_LOOK, TSM_HIST, TSM_MIN, TSM_MAX = 480, 960, 2
 PITCH_MIN, PITCH_MAX, PITCH_HIST = 50, 200, 64                           # q3tts_spec.h "pitch"
 VOL_MIN, VOL_MAX, VOL_LOOK, VOL_HOLD, VOL_DELAY, VOL_HIST = -400, 200, 128, 512, 127, 638   # q3tts_spec.h "volume"
 LOUD_SEG, LOUD_BLOCK, LOUD_STATE = 96, 2400, 6                           # q3tts_spec.h "loudness"
+INTAKE_U8, INTAKE_S16, INTAKE_S24, INTAKE_S32, INTAKE_F32 = 0, 1, 2, 3, 4   # q3tts_spec.h "reference audio intake"
+INTAKE_FIRST, INTAKE_MEAN = 0, 1
+INTAKE_SAMPLE_BYTES = (1, 2, 3, 4, 4)
+INTAKE_MAX_CLIPS, INTAKE_MAX_OUT = 64, 2880000
 MAX_PREAMBLES = 64                                                       # Q3TTS_MAX_PREAMBLES (q3tts_spec.h "codec preambles")
 PREAMBLE_BUILDING, PREAMBLE_READY, PREAMBLE_FAILED = 0, 1, -1            # Q3TTS_PREAMBLE_*
 MAX_STEMS = 64                                                           # Q3TTS_MAX_STEMS (q3tts_spec.h "prompt stems")
@@ -370,6 +387,17 @@ def lib():
         L.q3tts_loudness_gain_db10.restype = C.c_int32
         L.q3tts_op_loudness.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.q3tts_intake_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
+        L.q3tts_intake_filter.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
+        L.q3tts_intake_filter.restype = C.c_int64
+        L.q3tts_intake_samples.argtypes = [C.c_int32, C.c_int64]
+        L.q3tts_intake_samples.restype = C.c_int64
+        L.q3tts_intake_tile.argtypes = [C.c_int32]
+        L.q3tts_intake_tile.restype = C.c_int32
+        L.q3tts_intake_check.argtypes = [C.POINTER(IntakeClip)]
+        L.q3tts_wav_probe.argtypes = [C.c_void_p, C.c_int64, C.POINTER(WavInfo)]
+        L.q3tts_intake.argtypes = [C.c_int32, C.POINTER(IntakeClip), C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+        L.q3tts_wav_intake.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(WavInfo)]
         L.q3tts_pitch_samples.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
         L.q3tts_pitch_samples.restype = C.c_int64
         L.q3tts_pitch_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 4
@@ -2350,6 +2378,92 @@ def pcm_format_ok(rate, encoding):
 
 def pcm_dtype(encoding):
     return np.int16 if encoding == PCM_S16 else np.float32
+
+
+# ---- reference audio intake: the host-only half, the WAV header reader and the intake itself (q3tts_intake, q3tts_wav_intake) ----
+def intake_plan(rate):
+    """(L, M, n_taps, taps_per_output): 24000 / rate = L / M"""
+    v = [C.c_int32() for _ in range(4)]
+    _chk(lib().q3tts_intake_plan(rate, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def intake_filter(rate):
+    """the f32 prototype filter of this rate (empty at 24000)"""
+    h = np.zeros(intake_plan(rate)[2], np.float32)
+    n = lib().q3tts_intake_filter(rate, _p(h), h.size)
+    if n != h.size:
+        raise Q3Error(lib().q3tts_last_error().decode())
+    return h
+
+
+def intake_samples(rate, n_frames):
+    """ceil(n_frames L / M); < 0 for a rate the intake does not take"""
+    return int(lib().q3tts_intake_samples(rate, n_frames))
+
+
+def intake_tile(rate):
+    """output samples one block of the kernel computes at this rate"""
+    t = int(lib().q3tts_intake_tile(rate))
+    if t < 0:
+        raise Q3Error(lib().q3tts_last_error().decode())
+    return t
+
+
+def _intake_clip(clip):
+    """(the C struct, the array that keeps its bytes alive) of (data, sample_rate, channels, sample_format, downmix[, n_frames]); data is
+    the clip's raw interleaved samples as an array of any dtype or as bytes"""
+    data, rate, ch, fmt, mix = clip[:5]
+    raw = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    row = ch * INTAKE_SAMPLE_BYTES[fmt] if 0 <= fmt < 5 and ch > 0 else 0
+    n = int(clip[5]) if len(clip) > 5 else (raw.size // row if row else 0)
+    if row and n * row > raw.size:
+        raise ValueError("clip holds fewer than n_frames frames")
+    return IntakeClip(raw.ctypes.data if raw.size else None, n, rate, ch, fmt, mix), raw
+
+
+def intake_why_not(clip):
+    """None if q3tts_intake_check lets the clip run, else its reason"""
+    c, _keep = _intake_clip(clip)
+    return None if lib().q3tts_intake_check(C.byref(c)) == 0 else lib().q3tts_last_error().decode()
+
+
+def wav_probe(data):
+    """q3tts_wav_probe over the bytes of a WAV file: dict(sample_format, channels, sample_rate, bits, data_offset, n_frames)"""
+    raw = np.frombuffer(bytes(data), np.uint8)
+    w = WavInfo()
+    _chk(lib().q3tts_wav_probe(raw.ctypes.data if raw.size else None, raw.size, C.byref(w)))
+    return {k: int(getattr(w, k)) for k, _ in WavInfo._fields_}
+
+
+def intake(clips, device=0, slack=0, fill=0x5A, caps=None):
+    """q3tts_intake: a list of clips (see _intake_clip) -> a list of f32 arrays, mono at 24000 Hz.  slack > 0 over-allocates every output by
+    that many floats of `fill` bytes and returns (outs, wholes, n_out) for a test to look behind the samples; a refused call raises Q3Error
+    with .wholes and .n_out as the call left them.  caps: the capacities to declare instead of the buffers' own (never more than those)"""
+    cs = [_intake_clip(c) for c in clips]
+    arr = (IntakeClip * max(len(cs), 1))(*[c for c, _ in cs])
+    want = [max(intake_samples(c.sample_rate, c.n_frames), 0) for c, _ in cs]
+    wholes = [np.full((n + slack) * 4, fill, np.uint8).view(np.float32) for n in want]
+    ptrs = (C.c_void_p * max(len(cs), 1))(*[w.ctypes.data for w in wholes])
+    if caps is not None and any(c > w.size for c, w in zip(caps, wholes)):
+        raise ValueError("a declared capacity exceeds its buffer")
+    caps = np.array([w.size for w in wholes] + [0] if caps is None else list(caps) + [0], np.int64)
+    n_out = np.full(len(cs) + 1, -1, np.int64)
+    if lib().q3tts_intake(device, arr, len(cs), ptrs, _p(caps), _p(n_out)) != 0:
+        ex = Q3Error(lib().q3tts_last_error().decode())
+        ex.wholes, ex.n_out = wholes, n_out[: len(cs)]
+        raise ex
+    outs = [w[:n].copy() for w, n in zip(wholes, n_out[: len(cs)])]
+    return (outs, wholes, n_out[: len(cs)]) if slack else outs
+
+
+def wav_intake(path, downmix=INTAKE_FIRST, device=0):
+    """q3tts_wav_intake: (samples, info) of a WAV file at any accepted rate, sample format and channel count"""
+    n, w = C.c_int64(), WavInfo()
+    _chk(lib().q3tts_wav_intake(path.encode(), downmix, device, None, 0, C.byref(n), C.byref(w)))   # the size query
+    out = np.zeros(n.value, np.float32)
+    _chk(lib().q3tts_wav_intake(path.encode(), downmix, device, _p(out), out.size, C.byref(n), C.byref(w)))
+    return out[: n.value], {k: int(getattr(w, k)) for k, _ in WavInfo._fields_}
 
 
 # ---- what the four output-stage entry points (op_pcm_convert, op_tsm, op_volume, op_pitch) share in front of their call and behind it ----
