@@ -5,6 +5,7 @@
 #include "kdev.h"
 #include "codec.h"
 #include "kernels.h"
+#include "out_stages.h"
 #include "pcm_out.h"
 #include "tsm.h"
 #include "pitch.h"

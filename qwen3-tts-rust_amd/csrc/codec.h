@@ -12,9 +12,6 @@ struct q3tts_codec_kernel_desc;
 
 namespace q3 {
 
-// [EXT] loudness: where a metered stream of a pass stands and where its rows go.  pos = native samples the stream was given before this
-// chunk, since its reset; rows = pinned host memory for the rows {energy, peak} the chunk completes (loud_blocks(pos, T), loudness.h)
-struct LoudDst { int64_t pos = 0; double* rows = nullptr; };
 struct CodecStateEntry { std::string name; int64_t offset; int rows, cols; }; // one named tensor of a stream's state blob ([rows][cols] f32 at `offset` floats)
 
 class CodecDecoder {
@@ -57,8 +54,8 @@ public:
     // stream those that became available, possibly none -- in 4 or 2 bytes each.  A stage's tables, state store and per-lane buffers are
     // made by the first call that needs it; a reset and a snapshot restore zero a stream's state in all of them.
     // [EXT] loudness: a stream with out[g].loud is metered -- in front of the volume launch one loudness launch (loudness.hip) reads the chunks
-    // of the metered streams, and the rows stream g completes are copied to loud[g].rows, which it then needs (an unmetered stream's entry is
-    // not looked at)
+    // of the metered streams, and the rows stream g completes are copied to loud[g].rows (LoudDst, sched_logic.h), which it then needs (an
+    // unmetered stream's entry is not looked at).  All of it is OutChain::run (out_chain.h) over the routing out_route works out (sched_logic.h)
     int decode_group_async(hipStream_t st, int G, const int* streams, const int64_t* codes, int n_frames, float* const* pcm_pinned, int lane = 0,
                            const OutSpec* out = nullptr, int64_t* n_out = nullptr, const LoudDst* loud = nullptr);
     // ends a stretched or shifted utterance: the hops its last samples still owe go to dst (pinned) and *n_out is their sample count (0 for a

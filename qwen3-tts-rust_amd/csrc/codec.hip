@@ -10,12 +10,7 @@
 #include "../../include/q3tts.h"
 #include "gguf.h"
 #include "kernels.h"
-#include "pcm_out.h"
-#include "tsm.h"
-#include "pitch.h"
-#include "volume.h"
-#include "loudness.h"
-#include <atomic>
+#include "out_chain.h"
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -1181,111 +1176,10 @@ struct CodecDecoder::Impl {
         DevBuf<float> h, xn, qkv, att, gu, act, t1, t2, pcm, splitk_ws; DevBuf<int64_t> d_in; // d_in = codes then meta
         std::vector<DevBuf<float>> work;              // batched extended buffers, indexed by Ext::id
         int64_t* h_in = nullptr; int ring_idx = 0;    // pinned staging ring for the (tiny) code + metadata uploads of async calls
-        // [gmax] each, sized once: what deliver hands the stage launchers for the pass in flight -- the converter's formats, the stretcher's
-        // percents, the shifter's rates and pitches, the encodings, the converter's counts, the stretcher's and shifter's, their byte offsets
-        std::vector<q3tts_pcm_format> cf; std::vector<int32_t> pct, pr, pp, enc, vol; std::vector<int64_t> cnt, scnt, toff;
-        std::vector<int32_t> lmet; std::vector<int64_t> lpos, loff, lcnt;   // [EXT] loudness: metered, position, row offset, rows per stream
     };
     std::vector<Scratch> lanes; Scratch* S = nullptr; int ring = 256;
-    // [EXT] output formats: made by the first call that converts (decode_group_async), under capture_mutex(); pcm_out[lane] = the converted
-    // chunk of each stream of a pass, region g at g * T * 4 bytes.  The counters are read by other threads
-    std::unique_ptr<PcmConverter> conv; std::vector<DevBuf<float>> pcm_out; size_t pcm_lane_floats = 0;
-    std::atomic<int64_t> conv_chunks{0}, conv_samples{0};
-    // [EXT] speaking rate / pitch: the stretcher is made by the first call that stretches and the shifter by the first call that shifts -- the
-    // decoder thread, which owns the codec's streams -- under capture_mutex(); all 151 tap tables are built and uploaded there, once.
-    // tsm_out[lane] / pitch_out[lane] = what the stage made of each stream of a pass, region g of tsm_region() floats: a chunk of T samples
-    // gives at most 2 T samples plus a hop at rate 50 and 2 T + 961 at the tempo 1/2, a flush at most six hops or 3361 samples.
-    // prosody[s] = what stream s was last stretched or shifted with since its reset, which is what its flush runs with; live = false:
-    // neither since the reset, or flushed
-    std::unique_ptr<TsmStretcher> tsm; std::unique_ptr<PitchShifter> pitch; std::vector<DevBuf<float>> tsm_out, pitch_out;
-    struct Prosody { OutSpec out; bool live = false; };
-    std::vector<Prosody> prosody;
-    size_t tsm_region() const { return 2 * (pcm_lane_floats / (size_t)gmax) + 8 * Q3_TSM_HOP; }
-    std::atomic<int64_t> tsm_chunks{0}, tsm_frames{0}, tsm_flushes{0};
-    std::atomic<int64_t> pitch_chunks{0}, pitch_samples{0}, pitch_flushes{0}, pitch_table_bytes{0};
-    template <class Stage> bool ensure_stage(std::unique_ptr<Stage>& stage, std::vector<DevBuf<float>>& out) {   // true: made by this call
-        if (stage) return false;
-        std::lock_guard<std::mutex> cap(capture_mutex());
-        out.resize(lanes.size());
-        for (auto& b : out) b.alloc((size_t)gmax * tsm_region());
-        prosody.resize((size_t)n_streams);
-        stage.reset(new Stage(n_streams, gmax));
-        return true;
-    }
-    // [EXT] volume: the stage is made by the first pass that holds a stream with a volume, under capture_mutex(); it has no buffers of its own
-    std::unique_ptr<VolumeStage> volume;
-    std::atomic<int64_t> vol_chunks{0}, vol_samples{0};
-    void run_volume(hipStream_t st, int G, int T, const int32_t* streams, const OutSpec* out) {   // one launch over the chunk in S->pcm
-        bool any = false;
-        int32_t* const db10 = S->vol.data();
-        for (int g = 0; g < G; g++) { db10[g] = out[g].vol_db10; any = any || db10[g] != 0; }
-        if (!any) return;
-        if (!volume) {
-            std::lock_guard<std::mutex> cap(capture_mutex());
-            volume.reset(new VolumeStage(n_streams, gmax));
-        }
-        const int64_t c0 = volume->chunks, s0 = volume->samples;
-        launch_volume(st, *volume, S->pcm.p, G, T, streams, db10);
-        Q3_LAUNCH_CHECK();
-        vol_chunks += volume->chunks - c0; vol_samples += volume->samples - s0;
-    }
-    // [EXT] loudness: the stage and its row buffers -- loud_rows[lane] = [gmax][loud_row_cap()][2] doubles, the rows each stream of a pass
-    // completes -- are made by the first pass that holds a metered stream, under capture_mutex()
-    std::unique_ptr<LoudnessStage> loudness; std::vector<DevBuf<double>> loud_rows;
-    std::atomic<int64_t> loud_chunks{0}, loud_blocks_n{0};
-    size_t loud_row_cap() const { return pcm_lane_floats / (size_t)gmax / Q3_LOUD_BLOCK + 1; }
-    void run_loudness(hipStream_t st, int G, int T, const int32_t* streams, const OutSpec* out, const LoudDst* loud, int lane) {   // one launch over the chunk in S->pcm
-        bool any = false;
-        int32_t* const met = S->lmet.data();
-        int64_t *const pos = S->lpos.data(), *const off = S->loff.data(), *const cnt = S->lcnt.data();
-        for (int g = 0; g < G; g++) {
-            met[g] = out[g].loud != 0; any = any || met[g];
-            Q3_CHECK(!met[g] || (loud && loud[g].rows), "a metered stream needs a place for its rows");
-            pos[g] = met[g] ? loud[g].pos : 0;
-            off[g] = (int64_t)((size_t)g * loud_row_cap() * 2 * sizeof(double));
-        }
-        if (!any) return;
-        if (!loudness) {
-            std::lock_guard<std::mutex> cap(capture_mutex());
-            loud_rows.resize(lanes.size());
-            for (auto& b : loud_rows) b.alloc((size_t)gmax * loud_row_cap() * 2);
-            loudness.reset(new LoudnessStage(n_streams, gmax));
-        }
-        const int64_t c0 = loudness->chunks, b0 = loudness->blocks;
-        launch_loudness(st, *loudness, S->pcm.p, G, T, streams, met, pos, loud_rows[lane].p, off, cnt);
-        Q3_LAUNCH_CHECK();
-        loud_chunks += loudness->chunks - c0; loud_blocks_n += loudness->blocks - b0;
-        for (int g = 0; g < G; g++) {
-            if (!met[g] || cnt[g] <= 0) continue;
-            Q3_CHECK((size_t)cnt[g] <= loud_row_cap(), "a pass completed more blocks than the meter's buffer holds");
-            Q3_HIP(hipMemcpyAsync(loud[g].rows, reinterpret_cast<const unsigned char*>(loud_rows[lane].p) + off[g], (size_t)cnt[g] * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-    }
-    void prosody_reset(hipStream_t st, int s) {
-        if (loudness) loudness->reset_async(st, s);
-        if (tsm) tsm->reset_async(st, s);
-        if (pitch) pitch->reset_async(st, s);
-        if (volume) volume->reset_async(st, s);
-        if (!prosody.empty()) prosody[(size_t)s] = Prosody{};
-    }
-    // one launch of a stage over the chunk in S->pcm (in = false: a flush alone) and its accounting
-    void run_tsm(hipStream_t st, bool in, int G, int T, const int32_t* streams, const int32_t* pct, const int32_t* enc, int lane,
-                 const int64_t* off, int64_t* n) {
-        ensure_stage(tsm, tsm_out);
-        const int64_t c0 = tsm->chunks, f0 = tsm->frames_out, l0 = tsm->flushes;
-        launch_tsm_stretch(st, *tsm, in ? S->pcm.p : nullptr, G, T, !in, streams, pct, enc, tsm_out[lane].p, off, n);
-        Q3_LAUNCH_CHECK();
-        tsm_chunks += tsm->chunks - c0; tsm_frames += tsm->frames_out - f0; tsm_flushes += tsm->flushes - l0;
-    }
-    void run_pitch(hipStream_t st, bool in, int G, int T, const int32_t* streams, const int32_t* rate, const int32_t* pct, const int32_t* enc,
-                   int lane, const int64_t* off, int64_t* n) {
-        if (ensure_stage(pitch, pitch_out)) pitch_table_bytes = pitch->table_bytes;
-        const int64_t c0 = pitch->chunks, s0 = pitch->samples_out, l0 = pitch->flushes;
-        launch_tsm_pitch(st, *pitch, in ? S->pcm.p : nullptr, G, T, !in, streams, rate, pct, enc, pitch_out[lane].p, off, n);
-        Q3_LAUNCH_CHECK();
-        pitch_chunks += pitch->chunks - c0; pitch_samples += pitch->samples_out - s0; pitch_flushes += pitch->flushes - l0;
-    }
-    void deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const OutSpec* out, int64_t* n_out);
+    // [EXT] everything behind the output conv -- format, rate, pitch, volume, meter -- and its state per stream (out_chain.h)
+    std::unique_ptr<OutChain> chain;
     // [EXT] codec preambles: the snapshot store.  A slot holds one stream's histories back to back in all_ext order (the shape of one stream's
     // share of the history stores) and the two host counters as they stood when the snapshot was enqueued.  A slot's buffer is allocated by the
     // first snapshot that takes it, under capture_mutex(), and kept for the next one; snap_mu guards the table (a slot may be freed by
@@ -1308,13 +1202,6 @@ struct CodecDecoder::Impl {
             if (tab.n == 48) flush();
         }
         flush();
-    }
-    void ensure_conv() { // the converter's one-time allocation, by the first call that needs it
-        if (conv) return;
-        std::lock_guard<std::mutex> cap(capture_mutex());
-        pcm_out.resize(lanes.size());
-        for (auto& b : pcm_out) b.alloc(pcm_lane_floats);
-        conv.reset(new PcmConverter(n_streams, gmax));
     }
     size_t in_slot() const { return (size_t)gmax * max_frames * n_q + 3 * (size_t)gmax; }
     double flops_frame = 0;
@@ -1550,16 +1437,14 @@ CodecDecoder::CodecDecoder(const std::string& path, int n_streams, int max_frame
         L.h.alloc(R0 * H); L.xn.alloc(R0 * H); L.qkv.alloc(R0 * 3 * H); L.att.alloc(R0 * H);
         L.gu.alloc(R0 * 2 * m.ffn); L.act.alloc(R0 * m.ffn);
         L.t1.alloc(max_act); L.t2.alloc(max_act); L.pcm.alloc((size_t)GM * T);
-        m.pcm_lane_floats = (size_t)GM * T;
         L.work.resize(m.all_ext.size());
         for (Ext* e : m.all_ext) L.work[e->id].alloc((size_t)GM * (e->H + e->Tmax) * e->C);
-        L.d_in.alloc(m.in_slot()); L.cf.resize((size_t)GM); L.cnt.resize((size_t)GM); L.scnt.resize((size_t)GM); L.toff.resize((size_t)GM);
-        for (auto* v : {&L.pct, &L.pr, &L.pp, &L.enc, &L.vol, &L.lmet}) v->resize((size_t)GM);
-        for (auto* v : {&L.lpos, &L.loff, &L.lcnt}) v->resize((size_t)GM);
+        L.d_in.alloc(m.in_slot());
         L.splitk_ws.alloc(std::max<size_t>(max_act * 2, (size_t)1 << 20));
         Q3_HIP(hipHostMalloc((void**)&L.h_in, (size_t)m.ring * m.in_slot() * sizeof(int64_t)));
     }
     m.S = &m.lanes[0];
+    m.chain.reset(new OutChain(n_streams, GM, (int)m.lanes.size(), (size_t)GM * T));
     Q3_HIP(hipDeviceSynchronize());
 }
 CodecDecoder::~CodecDecoder() { if (impl_) for (auto& L : impl_->lanes) if (L.h_in) (void)hipHostFree(L.h_in); }
@@ -1578,21 +1463,11 @@ void CodecDecoder::reset(int s) {
     Q3_CHECK(s >= 0 && s < m.n_streams, "stream out of range");
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Ext* e : m.all_ext) if (e->H) Q3_HIP(hipMemset(e->hist.p + (size_t)s * e->H * e->C, 0, (size_t)e->H * e->C * 4));
-    if (m.conv) Q3_HIP(hipMemset(m.conv->hist + (size_t)s * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST));
-    if (m.tsm || m.pitch || m.volume || m.loudness) { m.prosody_reset(nullptr, s); Q3_HIP(hipStreamSynchronize(nullptr)); }
+    m.chain->reset(nullptr, s);
+    Q3_HIP(hipStreamSynchronize(nullptr));
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
-OutputStageStats CodecDecoder::output_stats() const {
-    const Impl& m = *impl_;
-    OutputStageStats s;
-    s.conv_chunks = m.conv_chunks.load(); s.conv_samples = m.conv_samples.load();
-    s.tsm_chunks = m.tsm_chunks.load(); s.tsm_frames = m.tsm_frames.load(); s.tsm_flushes = m.tsm_flushes.load();
-    s.pitch_chunks = m.pitch_chunks.load(); s.pitch_samples = m.pitch_samples.load(); s.pitch_flushes = m.pitch_flushes.load();
-    s.pitch_table_bytes = m.pitch_table_bytes.load();
-    s.vol_chunks = m.vol_chunks.load(); s.vol_samples = m.vol_samples.load();
-    s.loud_chunks = m.loud_chunks.load(); s.loud_blocks = m.loud_blocks_n.load();
-    return s;
-}
+OutputStageStats CodecDecoder::output_stats() const { return impl_->chain->stats(); }
 
 // ---- DecoderState export / import (onnx.rs:461-496: the reference carries the streaming state as named tensors between decode calls;
 // here it lives on the device, and these calls move one stream's state out / in as a flat f32 blob with a published layout) ----
@@ -1671,8 +1546,7 @@ void CodecDecoder::reset_async(hipStream_t st, int s) {
         if (tab.n == 48) flush();
     }
     flush();
-    if (m.conv) m.conv->reset_async(st, s); // the converter's history is part of the stream (one made later starts from zeros)
-    m.prosody_reset(st, s);                 // and so are the stretcher's state, the pitch shifter's, the volume stage's and the meter's
+    m.chain->reset(st, s); // the output stages' state is part of the stream
     m.kv_len[s] = 0; m.n_seen[s] = 0;
 }
 
@@ -1719,11 +1593,7 @@ void CodecDecoder::restore_async(hipStream_t st, int snap, int s, const float* p
         Q3_CHECK(sn->live, "the snapshot has been freed");
     }
     m.copy_hist(st, sn->buf.p, s, false);
-    if (pcm_tail) { // the stream is delivered converted: its converter history is the preamble's last Q3_PCM_HIST native samples, not zeros
-        m.ensure_conv();
-        Q3_HIP(hipMemcpyAsync(m.conv->hist + ((size_t)s * 2 + m.conv->parity[(size_t)s]) * Q3_PCM_HIST, pcm_tail, sizeof(float) * Q3_PCM_HIST, hipMemcpyHostToDevice, st));
-    }
-    m.prosody_reset(st, s); // [EXT] speaking rate / pitch / volume: a primed stream's stretcher, both stages of its pitch shifter, its volume stage and its meter start from a reset
+    m.chain->restore(st, s, pcm_tail); // the output stages start from a reset, the converter of a stream delivered converted from the preamble's tail
     m.kv_len[s] = sn->kv_len; m.n_seen[s] = sn->n_seen;
 }
 void CodecDecoder::snapshot_free(int snap) {
@@ -1855,85 +1725,16 @@ int CodecDecoder::decode_group_async(hipStream_t st, int G, const int* streams, 
     launch_conv_out(st, m.work(m.out_ext), m.out_ext.C, m.conv_out_w.p, m.conv_out_b, m.S->pcm.p, G, T, m.base_map(m.out_ext, T), conv_out_win_ok(m.out_ext.C, T));
     m.move_hist(st, G, meta, true);
     Q3_LAUNCH_CHECK();
-    if (out) m.run_loudness(st, G, T, streams, out, loud, lane);   // [EXT] loudness: reads the chunk as the output conv wrote it
-    if (out) m.run_volume(st, G, T, streams, out);   // [EXT] volume: in place, in front of every stage deliver runs
-    m.deliver(st, G, streams, T, pcm, lane, out, n_out);
+    m.chain->run(st, lane, G, T, streams, m.S->pcm.p, out, loud, pcm, n_out);   // [EXT] meter, volume, format / rate / pitch, and every stream's copy
     return T;
 }
 
-// [EXT] output formats / speaking rate / pitch: what follows the output conv.  A stream is of one of four kinds -- native, converted (the
-// converter's), rate-only (the stretcher's), pitched (the shifter's) -- and each stage sees the streams of the other stages as ones it leaves
-// alone; a stage nobody needs is not launched, and a pass of native streams is G copies.  A stretched or shifted stream delivers 24000 Hz.
-// Then every stream's bytes go out from where its stage left them
-void CodecDecoder::Impl::deliver(hipStream_t st, int G, const int* streams, int T, float* const* pcm, int lane, const OutSpec* out, int64_t* n_out) {
-    bool any[4] = {false, false, false, false};
-    for (int g = 0; out && g < G; g++) any[out_kind(out[g])] = true;
-    if (!any[OUT_CONVERTED] && !any[OUT_RATED] && !any[OUT_PITCHED]) {
-        for (int g = 0; g < G; g++) Q3_HIP(hipMemcpyAsync(pcm[g], S->pcm.p + (size_t)g * T, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-        for (int g = 0; n_out && g < G; g++) n_out[g] = T;
-        return;
-    }
-    // every stage sees the streams of the other stages as ones it leaves alone: the native format, 100 percent
-    q3tts_pcm_format* const cf = S->cf.data();
-    int32_t *const pct = S->pct.data(), *const pr = S->pr.data(), *const pp = S->pp.data(), *const enc = S->enc.data();
-    int64_t *const cnt = S->cnt.data(), *const scnt = S->scnt.data(), *const toff = S->toff.data();   // the converter's counts; the stretcher's and the shifter's
-    for (int g = 0; g < G; g++) {
-        const OutKind k = out_kind(out[g]);
-        cf[g] = OutSpec().fmt; pct[g] = pr[g] = pp[g] = 100; enc[g] = Q3_PCM_F32; cnt[g] = scnt[g] = T; toff[g] = 0;
-        if (k == OUT_CONVERTED) cf[g] = out[g].fmt;
-        if (k < OUT_RATED) continue;
-        Q3_CHECK(out[g].fmt.sample_rate == Q3_PCM_NATIVE_RATE, "a speech rate or a pitch needs the 24000 Hz output format");
-        enc[g] = out[g].fmt.encoding;
-        if (k == OUT_PITCHED) { pr[g] = out[g].rate_pct; pp[g] = out[g].pitch_pct; }
-        else pct[g] = out[g].rate_pct;
-    }
-    if (any[OUT_CONVERTED]) {
-        ensure_conv();
-        const int64_t c0 = conv->chunks_converted, s0 = conv->samples_out;
-        launch_pcm_convert(st, *conv, S->pcm.p, G, T, streams, cf, pcm_out[lane].p, nullptr, cnt);
-        Q3_LAUNCH_CHECK();
-        conv_chunks += conv->chunks_converted - c0; conv_samples += conv->samples_out - s0;
-    }
-    if (any[OUT_RATED] || any[OUT_PITCHED]) {
-        Q3_CHECK(2 * (size_t)T + 3 * Q3_TSM_HOP <= tsm_region(), "chunk too long for the stretcher's buffers");
-        for (int g = 0; g < G; g++) toff[g] = (int64_t)((size_t)g * tsm_region() * sizeof(float));
-    }
-    // the stretcher sets T for every stream it leaves alone and the shifter sets its own streams' counts only: they share scnt in this order
-    if (any[OUT_RATED]) run_tsm(st, true, G, T, streams, pct, enc, lane, toff, scnt);
-    if (any[OUT_PITCHED]) run_pitch(st, true, G, T, streams, pr, pp, enc, lane, toff, scnt);
-    for (int g = 0; g < G; g++) {
-        const OutKind k = out_kind(out[g]);
-        const float* src = S->pcm.p + (size_t)g * T;
-        if (k == OUT_CONVERTED) src = pcm_out[lane].p + (size_t)g * T;
-        else if (k != OUT_NATIVE) {
-            src = (k == OUT_PITCHED ? pitch_out : tsm_out)[lane].p + (size_t)g * tsm_region();
-            prosody[(size_t)streams[g]] = Prosody{out[g], true};
-            cnt[g] = scnt[g];
-            Q3_CHECK((size_t)cnt[g] <= tsm_region(), "a pass delivered more than the stage's buffer holds");
-        }
-        if (cnt[g] > 0) Q3_HIP(hipMemcpyAsync(pcm[g], src, (size_t)cnt[g] * out_sample_bytes(out[g]), hipMemcpyDeviceToHost, st));
-        if (n_out) n_out[g] = cnt[g];
-    }
-}
-
-// [EXT] speaking rate / pitch: the end of a stretched or shifted utterance.  The stream's input ends in zeros and every frame with a_k < N
-// comes out -- of a pitched stream stage 1 is flushed and stage 2 delivers what that completes: one launch without input, then the copy to
-// dst (pinned).  A stream that was neither stretched nor shifted since its reset gives nothing
+// [EXT] speaking rate / pitch: the end of a stretched or shifted utterance (OutChain::flush)
 void CodecDecoder::tsm_flush_async(hipStream_t st, int s, void* dst, int64_t* n_out, int lane) {
     Impl& m = *impl_;
     Q3_CHECK(s >= 0 && s < m.n_streams && n_out, "stream out of range");
     Q3_CHECK(lane >= 0 && lane < (int)m.lanes.size(), "codec lane out of range");
-    *n_out = 0;
-    if (m.prosody.empty() || !m.prosody[(size_t)s].live) return;
-    const OutSpec o = m.prosody[(size_t)s].out;
-    const bool pitched = out_kind(o) == OUT_PITCHED;
-    const int32_t sl = s;
-    const int64_t off = 0;
-    if (pitched) m.run_pitch(st, false, 1, 0, &sl, &o.rate_pct, &o.pitch_pct, &o.fmt.encoding, lane, &off, n_out);
-    else m.run_tsm(st, false, 1, 0, &sl, &o.rate_pct, &o.fmt.encoding, lane, &off, n_out);
-    Q3_CHECK((size_t)*n_out <= m.tsm_region(), "flush larger than the stage's buffer");
-    if (*n_out > 0) Q3_HIP(hipMemcpyAsync(dst, (pitched ? m.pitch_out : m.tsm_out)[lane].p, (size_t)*n_out * out_sample_bytes(o), hipMemcpyDeviceToHost, st));
-    m.prosody[(size_t)s].live = false; // flushed: the stream is reset before it is used again
+    m.chain->flush(st, lane, s, dst, n_out);
 }
 
 // ---------------- test entry points: one GEMM as the decoder dispatches it, or with a named form forced ----------------

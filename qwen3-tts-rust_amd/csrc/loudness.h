@@ -5,6 +5,7 @@
 // in loud_step changes the bits.
 #pragma once
 #include "../../include/q3tts_spec.h"
+#include "sched_logic.h"
 #include <cmath>
 #include <cstdint>
 
@@ -144,16 +145,11 @@ inline int32_t loud_gain_db10(double measured_lufs, double target_lufs) {
 // what a loudness launch refuses (nullptr = it may run): G streams of T native samples each, streams[] slots of an n_streams state store,
 // stream g metered where metered[g] != 0, then at stream position pos[g]
 inline const char* loudness_launch_refusal(int G, int max_group, int64_t T, const int32_t* streams, int n_streams, const int32_t* metered, const int64_t* pos) {
-    if (G < 1 || G > max_group) return "group size out of range";
-    if (T <= 0 || T % Q3_PCM_FRAME != 0) return "chunk length is no positive multiple of 1920 samples";
-    if (T > (int64_t)1 << 24) return "chunk too long";
-    if (!streams || !metered || !pos) return "null streams / metered / positions";
-    for (int g = 0; g < G; g++) {
-        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
-        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
-        if (metered[g] && (pos[g] < 0 || pos[g] % Q3_PCM_FRAME != 0)) return "stream position is no multiple of 1920 samples";
-    }
-    return nullptr;
+    const char* const chunk_why = (T <= 0 || T % Q3_PCM_FRAME != 0) ? "chunk length is no positive multiple of 1920 samples"
+                                  : T > (int64_t)1 << 24 ? "chunk too long" : (!streams || !metered || !pos) ? "null streams / metered / positions" : nullptr;
+    return stage_launch_refusal(G, max_group, chunk_why, streams, n_streams, [&](int g) -> const char* {
+        return (metered[g] && (pos[g] < 0 || pos[g] % Q3_PCM_FRAME != 0)) ? "stream position is no multiple of 1920 samples" : nullptr;
+    });
 }
 // the submit rule of a metered request.  nullptr = it may be queued
 inline const char* loudness_submit_refusal(bool have_codec) { return have_codec ? nullptr : "the engine has no codec"; }

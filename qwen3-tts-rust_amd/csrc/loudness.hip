@@ -9,7 +9,7 @@
 //
 // All arithmetic is float64 through loud_step / loud_carry (loudness.h), the one definition the host shares; the file is compiled without
 // contraction.  LDS arrays are [component][lane], so a phase's stores are contiguous across lanes.  No counters, no atomics, no scratch.
-#include "kernels.h"
+#include "out_stages.h"
 #include "kdev.h"
 #include "loudness.h"
 
@@ -94,8 +94,7 @@ __global__ void __launch_bounds__(LOUD_THREADS) k_loudness(LoudArgs a) {
     if (tid < Q3_LOUD_STATE) st[tid] = carry[tid];
 }
 
-LoudnessStage::LoudnessStage(int n_streams_, int max_group_) : n_streams(n_streams_), max_group(max_group_) {
-    Q3_CHECK(n_streams >= 1 && max_group >= 1, "bad loudness stage shape");
+LoudnessStage::LoudnessStage(int n_streams_, int max_group_, StageCounters* count_) : StageBase(n_streams_, max_group_, count_, "loudness stage") {
     LoudTables t;
     loud_tables(&t);
     std::copy(t.coef, t.coef + 10, coef); std::copy(t.m, t.m + 16, m);
@@ -106,7 +105,7 @@ LoudnessStage::LoudnessStage(int n_streams_, int max_group_) : n_streams(n_strea
 }
 
 void LoudnessStage::reset_async(hipStream_t st, int slot) {
-    Q3_CHECK(slot >= 0 && slot < n_streams, "stream out of range");
+    check_slot(slot);
     Q3_HIP(hipMemsetAsync(state + (size_t)slot * Q3_LOUD_STATE, 0, sizeof(double) * Q3_LOUD_STATE, st));
 }
 
@@ -130,7 +129,7 @@ void launch_loudness(hipStream_t st, LoudnessStage& s, const float* pcm, int G, 
         m.pos = metered[g] ? pos[g] : 0; m.out_off = metered[g] ? out_off[g] : 0;
         if (m.slot < 0) continue;
         n_out[g] = loud_blocks(pos[g], T);
-        s.chunks += 1; s.blocks += n_out[g];
+        s.count->loud_chunks += 1; s.count->loud_blocks += n_out[g];
     }
     s.ring.commit(st, G);
     LoudArgs a;

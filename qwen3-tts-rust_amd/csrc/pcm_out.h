@@ -56,16 +56,10 @@ inline std::vector<float> pcm_filter_phase_major(const PcmPlan& p, const std::ve
 
 // what a convert launch refuses (nullptr = it may run): G streams of T native samples each, streams[] slots of an n_streams history store
 inline const char* pcm_convert_refusal(int G, int max_group, int64_t T, const int32_t* streams, int n_streams, const q3tts_pcm_format* fmt) {
-    if (G < 1 || G > max_group) return "group size out of range";
-    if (T < Q3_PCM_FRAME || T % Q3_PCM_FRAME != 0) return "chunk length is no whole number of frames";
-    if (T > (int64_t)0x7fffffff / 147) return "chunk too long";   // n * M and T * L stay below 2^31 for every rate
-    if (!streams || !fmt) return "null streams / formats";
-    for (int g = 0; g < G; g++) {
-        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
-        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
-        if (const char* why = pcm_format_why_not(fmt[g].sample_rate, fmt[g].encoding)) return why;
-    }
-    return nullptr;
+    const char* const chunk_why = (T < Q3_PCM_FRAME || T % Q3_PCM_FRAME != 0) ? "chunk length is no whole number of frames"
+                                  : T > (int64_t)0x7fffffff / 147 ? "chunk too long"   // n * M and T * L stay below 2^31 for every rate
+                                  : (!streams || !fmt) ? "null streams / formats" : nullptr;
+    return stage_launch_refusal(G, max_group, chunk_why, streams, n_streams, [&](int g) { return pcm_format_why_not(fmt[g].sample_rate, fmt[g].encoding); });
 }
 
 } // namespace q3

@@ -13,7 +13,7 @@
 // History: [n_streams][2][96].  A launch reads the half meta.parity names and tile 0 of the stream leaves the chunk's last 96 samples in
 // the other half, so no block of the launch can read what another one wrote; the host flips the parity per launch.  Every chunk is at
 // least one frame long, so the tail always comes from one chunk.  No atomics, no scratch, no global workspace; the barriers wait for LDS only.
-#include "kernels.h"
+#include "out_stages.h"
 #include "kdev.h"
 #include "pcm_out.h"
 #include "wsola.h"
@@ -81,8 +81,7 @@ __global__ void __launch_bounds__(PO_THREADS) k_pcm_convert(PcmConvertArgs a) {
     }
 }
 
-PcmConverter::PcmConverter(int n_streams_, int max_group_) : n_streams(n_streams_), max_group(max_group_) {
-    Q3_CHECK(n_streams >= 1 && max_group >= 1, "bad converter shape");
+PcmConverter::PcmConverter(int n_streams_, int max_group_, StageCounters* count_) : StageBase(n_streams_, max_group_, count_, "converter") {
     std::vector<float> all;
     for (int r = 0; r < PCM_N_RATES; r++) {
         PcmPlan p;
@@ -102,7 +101,7 @@ PcmConverter::PcmConverter(int n_streams_, int max_group_) : n_streams(n_streams
 }
 
 void PcmConverter::reset_async(hipStream_t st, int slot) {
-    Q3_CHECK(slot >= 0 && slot < n_streams, "stream out of range");
+    check_slot(slot);
     Q3_HIP(hipMemsetAsync(hist + (size_t)slot * 2 * Q3_PCM_HIST, 0, sizeof(float) * 2 * Q3_PCM_HIST, st));
 }
 
@@ -129,7 +128,7 @@ void launch_pcm_convert(hipStream_t st, PcmConverter& c, const float* in, int G,
         m.slot = streams[g]; m.parity = c.parity[(size_t)streams[g]];
         m.L = c.tab_L[r]; m.M = c.tab_M[r]; m.stride = c.tab_stride[r]; m.tab_off = c.tab_off[r]; m.n_out = (int32_t)n_out[g];
         m.out_off = out_off ? out_off[g] : (int64_t)g * T * 4; m.pad = 0;
-        if (m.enc >= 0) { c.parity[(size_t)streams[g]] ^= 1; c.chunks_converted++; c.samples_out += n_out[g]; }
+        if (m.enc >= 0) { c.parity[(size_t)streams[g]] ^= 1; c.count->conv_chunks++; c.count->conv_samples += n_out[g]; }
     }
     c.ring.commit(st, G);
     PcmConvertArgs a{in, T, dm, c.tabs.p, c.hist, (unsigned char*)out};

@@ -19,7 +19,7 @@
 // State: hist [n_streams][1920] and d_prev [n_streams] as the stretcher's, zhist [n_streams][64]; all updated in place by the stream's only
 // workgroup after its last read.  The counters are data-independent and live on the host.  No atomics, no scratch, no global workspace; the
 // barriers inside the frame loop wait for LDS only.
-#include "kernels.h"
+#include "out_stages.h"
 #include "kdev.h"
 #include "pitch.h"
 #include "wsola.h"
@@ -111,8 +111,7 @@ static const PitchTables& pt_host_tables() {
     return t;
 }
 
-PitchShifter::PitchShifter(int n_streams_, int max_group_) : n_streams(n_streams_), max_group(max_group_) {
-    Q3_CHECK(n_streams >= 1 && max_group >= 1, "bad shifter shape");
+PitchShifter::PitchShifter(int n_streams_, int max_group_, StageCounters* count_) : StageBase(n_streams_, max_group_, count_, "shifter") {
     std::vector<float> w(2 * Q3_TSM_HOP);
     tsm_windows(w.data(), w.data() + Q3_TSM_HOP);
     wins.alloc(w.size()); wins.upload(w.data(), w.size());
@@ -124,7 +123,7 @@ PitchShifter::PitchShifter(int n_streams_, int max_group_) : n_streams(n_streams
         tab_off[P - Q3_PITCH_MIN] = t.off[P - Q3_PITCH_MIN];
     }
     tabs.alloc(t.all.size()); tabs.upload(t.all.data(), t.all.size());
-    table_bytes = t.taps * (int64_t)sizeof(float);
+    count->pitch_table_bytes = t.taps * (int64_t)sizeof(float);
     hist_own.alloc((size_t)n_streams * Q3_TSM_HIST); hist_own.zero();
     zhist_own.alloc((size_t)n_streams * Q3_PITCH_HIST); zhist_own.zero();
     hist = hist_own.p; zhist = zhist_own.p;
@@ -135,7 +134,7 @@ PitchShifter::PitchShifter(int n_streams_, int max_group_) : n_streams(n_streams
 }
 
 void PitchShifter::reset_async(hipStream_t st, int slot) {
-    Q3_CHECK(slot >= 0 && slot < n_streams, "stream out of range");
+    check_slot(slot);
     Q3_HIP(hipMemsetAsync(hist + (size_t)slot * Q3_TSM_HIST, 0, sizeof(float) * Q3_TSM_HIST, st));
     Q3_HIP(hipMemsetAsync(zhist + (size_t)slot * Q3_PITCH_HIST, 0, sizeof(float) * Q3_PITCH_HIST, st));
     Q3_HIP(hipMemsetAsync(d_prev.p + slot, 0, sizeof(int32_t), st));
@@ -172,7 +171,7 @@ void launch_tsm_pitch(hipStream_t st, PitchShifter& s, const float* in, int G, i
         m.n_prev = seen; m.k0 = done; m.n_frames = (int32_t)(total - done);
         n_out[g] = pitch_samples_of_z(p, total * Q3_TSM_HOP) - pitch_samples_of_z(p, done * Q3_TSM_HOP);
         seen += T; done = total;
-        s.chunks += T > 0; s.samples_out += n_out[g]; s.flushes += flush;
+        s.count->pitch_chunks += T > 0; s.count->pitch_samples += n_out[g]; s.count->pitch_flushes += flush;
     }
     s.ring.commit(st, G);
     PitchArgs a{in, T, dm, s.wins.p, s.tabs.p, s.hist, s.zhist, s.d_prev.p, (unsigned char*)out, trace};

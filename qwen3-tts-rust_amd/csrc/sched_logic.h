@@ -1,5 +1,5 @@
 // sched_logic.h -- the scheduler's pure bookkeeping (no HIP, no threads; engine.cpp keeps what touches either): the request structs,
-// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass and the queues they wait in, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume, and the one record of a stream's output settings with what follows from it.
+// the frame variant, the per-slot state table, the request states with what a cancel does in each, the staging cursor, the prefill chunk packer, the checks of a resumed prefix, of a score request, of a candidate set, of a decode-only request, of a codec preamble and of a prompt stem (with its take rule), the table of held objects both live in, what an admission wave takes from the queue, the chunk rows a score request needs the head for, how the decoder thread seats chunks in a codec pass and the queues they wait in, the rules of the output formats, the counts and the submit rule of the speaking rate, and the pair rule, the plan, the counts and the submit rule of the pitch, and the range, the gain and the submit rule of the volume, and the one record of a stream's output settings with what follows from it: the counts, the submit rule, the checks every output stage's launch shares and the routing of a pass's streams behind the output conv.
 // tests/test_sched_logic_cpu.py builds it with plain g++.
 #pragma once
 #include "../../include/q3tts_spec.h"
@@ -699,6 +699,72 @@ inline const char* out_submit_refusal(const OutSpec& o, int max_steps, int64_t c
     if (o.rate_pct != 100) return tsm_submit_refusal(o.rate_pct, o.fmt, max_steps, cap_bytes, have_codec);
     return nullptr;
 }
+// [EXT] loudness: where a metered stream of a pass stands and where its rows go.  pos = native samples the stream was given before this
+// chunk, since its reset; rows = pinned host memory for the rows {energy, peak} the chunk completes (loud_blocks(pos, T), loudness.h)
+struct LoudDst { int64_t pos = 0; double* rows = nullptr; };
+
+// what every output stage's launch refuses, in the order all of them state it (pcm_out.h, tsm.h, volume.h, loudness.h): the group size;
+// chunk_why = what the stage has against the chunk length or a missing array (nullptr: nothing), worked out by the caller from values alone;
+// then stream by stream its slot, that it appears once, and why_not(g) = what the stage has against stream g's own arguments
+template <class WhyNot>
+inline const char* stage_launch_refusal(int G, int max_group, const char* chunk_why, const int32_t* streams, int n_streams, WhyNot why_not) {
+    if (G < 1 || G > max_group) return "group size out of range";
+    if (chunk_why) return chunk_why;
+    for (int g = 0; g < G; g++) {
+        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
+        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
+        if (const char* why = why_not(g)) return why;
+    }
+    return nullptr;
+}
+
+// [EXT] what follows the output conv for the G streams of a pass, as arithmetic on their records: which stages run, what each is handed
+// per stream, and where each stream's copy comes from.  A stream is of one of four kinds (out_kind) and each stage sees the streams of the
+// other stages as ones it leaves alone -- the native format, 100 percent, volume 0, unmetered; a stage nobody needs is not launched, and a
+// pass of native streams is G copies of the native chunk.  A stretched or shifted stream delivers 24000 Hz.  The arrays hold max_group
+// entries each and are sized once: out_route writes the first G.
+struct OutRoute {
+    explicit OutRoute(int max_group)
+        : cf((size_t)max_group), pct((size_t)max_group), pr((size_t)max_group), pp((size_t)max_group), enc((size_t)max_group),
+          vol((size_t)max_group), metered((size_t)max_group), toff((size_t)max_group), loff((size_t)max_group), src((size_t)max_group),
+          src_off((size_t)max_group), bytes((size_t)max_group) {}
+    bool run[4] = {false, false, false, false};   // by OutKind: run[OUT_CONVERTED], run[OUT_RATED], run[OUT_PITCHED]; run[OUT_NATIVE] = some stream is native
+    bool any_volume = false, any_metered = false;
+    bool all_native() const { return !run[OUT_CONVERTED] && !run[OUT_RATED] && !run[OUT_PITCHED]; }
+    std::vector<q3tts_pcm_format> cf;             // the converter's formats
+    std::vector<int32_t> pct, pr, pp, enc;        // the stretcher's percents; the shifter's rates and pitches; the encodings both write
+    std::vector<int32_t> vol, metered;            // the volume stage's tenths of a dB; the meter's flags
+    std::vector<int64_t> toff, loff;              // first byte of the stream's region in the stretcher's / shifter's lane buffer; in the meter's
+    std::vector<OutKind> src;                     // whose lane buffer the stream's copy reads (OUT_NATIVE: the native chunk)
+    std::vector<size_t> src_off, bytes;           // its first float there; bytes per delivered sample
+};
+// out == NULL is a pass of plain streams.  T = native samples per stream; region = floats per stream of the stretcher's and the shifter's
+// lane buffers, loud_rows = rows per stream of the meter's.  Returns what the pass is refused for (nullptr: it may run; r is then whole)
+inline const char* out_route(const OutSpec* out, int G, int64_t T, size_t region, size_t loud_rows, OutRoute* r) {
+    for (bool& b : r->run) b = false;
+    r->any_volume = r->any_metered = false;
+    for (int g = 0; out && g < G; g++) r->run[out_kind(out[g])] = true;
+    const bool prosody = r->run[OUT_RATED] || r->run[OUT_PITCHED];
+    for (int g = 0; g < G; g++) {
+        const OutSpec o = out ? out[g] : OutSpec();
+        const OutKind k = out_kind(o);
+        r->cf[g] = OutSpec().fmt; r->pct[g] = r->pr[g] = r->pp[g] = 100; r->enc[g] = Q3_PCM_F32;
+        r->vol[g] = o.vol_db10; r->metered[g] = o.loud != 0;
+        r->any_volume = r->any_volume || r->vol[g] != 0; r->any_metered = r->any_metered || r->metered[g];
+        r->toff[g] = prosody ? (int64_t)((size_t)g * region * sizeof(float)) : 0;
+        r->loff[g] = (int64_t)((size_t)g * loud_rows * 2 * sizeof(double));
+        r->src[g] = k; r->src_off[g] = (size_t)g * (k >= OUT_RATED ? region : (size_t)T); r->bytes[g] = out_sample_bytes(o);
+        if (k == OUT_CONVERTED) r->cf[g] = o.fmt;
+        if (k < OUT_RATED) continue;
+        if (o.fmt.sample_rate != Q3_PCM_NATIVE_RATE) return "a speech rate or a pitch needs the 24000 Hz output format";
+        r->enc[g] = o.fmt.encoding;
+        if (k == OUT_PITCHED) { r->pr[g] = o.rate_pct; r->pp[g] = o.pitch_pct; }
+        else r->pct[g] = o.rate_pct;
+    }
+    if (prosody && 2 * (size_t)T + 3 * Q3_TSM_HOP > region) return "chunk too long for the stretcher's buffers";
+    return nullptr;
+}
+
 // [EXT] the counters of the codec's output stages, as one snapshot: stream chunks the converter took and samples it made; stream chunks the
 // stretcher took, synthesis frames it made, its flushes; stream chunks shifted, samples delivered, flushes, bytes of tap tables on the device;
 // stream chunks the volume stage took and samples it rewrote; stream chunks the loudness meter took and blocks it completed

@@ -28,17 +28,12 @@ constexpr int tsm_offset_of_order(int o) { return (o & 1) ? -((o + 1) >> 1) : (o
 template <class WhyNot>
 inline const char* prosody_launch_refusal(int G, int max_group, int64_t T, bool flush, const int32_t* streams, int n_streams, const int32_t* enc,
                                           bool no_nulls, const char* null_text, WhyNot why_not) {
-    if (G < 1 || G > max_group) return "group size out of range";
-    if (T < 0 || T % Q3_TSM_HIST != 0 || (T == 0 && !flush)) return "chunk length is no positive multiple of 1920 samples";
-    if (T > (int64_t)1 << 24) return "chunk too long";
-    if (!no_nulls) return null_text;
-    for (int g = 0; g < G; g++) {
-        if (streams[g] < 0 || streams[g] >= n_streams) return "stream out of range";
-        for (int h = 0; h < g; h++) if (streams[h] == streams[g]) return "a stream may appear once per launch";
+    const char* const chunk_why = (T < 0 || T % Q3_TSM_HIST != 0 || (T == 0 && !flush)) ? "chunk length is no positive multiple of 1920 samples"
+                                  : T > (int64_t)1 << 24 ? "chunk too long" : !no_nulls ? null_text : nullptr;
+    return stage_launch_refusal(G, max_group, chunk_why, streams, n_streams, [&](int g) -> const char* {
         if (const char* why = why_not(g)) return why;
-        if (enc[g] != Q3_PCM_F32 && enc[g] != Q3_PCM_S16) return "unknown encoding";
-    }
-    return nullptr;
+        return (enc[g] != Q3_PCM_F32 && enc[g] != Q3_PCM_S16) ? "unknown encoding" : nullptr;
+    });
 }
 
 // what a stretch launch refuses (nullptr = it may run): stream g at pct[g] percent (100: the stream is not touched) in encoding enc[g]

@@ -9,7 +9,7 @@
 // State: hist [n_streams][1920] and d_prev [n_streams], updated in place by the stream's only workgroup behind a barrier, after its last
 // read.  The counters (samples seen, frames made) are data-independent and live on the host; the launch's meta entry carries them.
 // No atomics, no scratch, no global workspace; the barriers inside the frame loop wait for LDS only.
-#include "kernels.h"
+#include "out_stages.h"
 #include "kdev.h"
 #include "tsm.h"
 #include "wsola.h"
@@ -50,8 +50,7 @@ __global__ void __launch_bounds__(WS_THREADS) k_tsm_stretch(TsmArgs a) {
     wsola_finish(x, a.T, h, a.d_prev + mt.slot, d_prev);
 }
 
-TsmStretcher::TsmStretcher(int n_streams_, int max_group_) : n_streams(n_streams_), max_group(max_group_) {
-    Q3_CHECK(n_streams >= 1 && max_group >= 1, "bad stretcher shape");
+TsmStretcher::TsmStretcher(int n_streams_, int max_group_, StageCounters* count_) : StageBase(n_streams_, max_group_, count_, "stretcher") {
     std::vector<float> t(2 * Q3_TSM_HOP);
     tsm_windows(t.data(), t.data() + Q3_TSM_HOP);
     tabs.alloc(t.size()); tabs.upload(t.data(), t.size());
@@ -64,7 +63,7 @@ TsmStretcher::TsmStretcher(int n_streams_, int max_group_) : n_streams(n_streams
 }
 
 void TsmStretcher::reset_async(hipStream_t st, int slot) {
-    Q3_CHECK(slot >= 0 && slot < n_streams, "stream out of range");
+    check_slot(slot);
     Q3_HIP(hipMemsetAsync(hist + (size_t)slot * Q3_TSM_HIST, 0, sizeof(float) * Q3_TSM_HIST, st));
     Q3_HIP(hipMemsetAsync(d_prev.p + slot, 0, sizeof(int32_t), st));
     n_seen[(size_t)slot] = 0; k_done[(size_t)slot] = 0;
@@ -96,7 +95,7 @@ void launch_tsm_stretch(hipStream_t st, TsmStretcher& s, const float* in, int G,
         m.n_prev = seen; m.k0 = done; m.n_frames = (int32_t)std::max<int64_t>(total - done, 0);
         seen += T; done += m.n_frames;
         n_out[g] = (int64_t)m.n_frames * Q3_TSM_HOP;
-        s.chunks += T > 0; s.frames_out += m.n_frames; s.flushes += flush;
+        s.count->tsm_chunks += T > 0; s.count->tsm_frames += m.n_frames; s.count->tsm_flushes += flush;
     }
     s.ring.commit(st, G);
     TsmArgs a{in, T, dm, s.tabs.p, s.hist, s.d_prev.p, (unsigned char*)out, trace};

@@ -11,7 +11,7 @@
 //
 // State: hist [n_streams][638], a stream's last 638 values of v.  The topmost tile, walked first, keeps the chunk's last 638 values in LDS;
 // they are stored behind the barriers that follow the lowest tile's read of the store.  No counters, no atomics, no scratch.
-#include "kernels.h"
+#include "out_stages.h"
 #include "kdev.h"
 #include "volume.h"
 #include "wsola.h"
@@ -89,8 +89,7 @@ __global__ void __launch_bounds__(VOL_THREADS) k_volume(VolArgs a) {
     for (int j = tid; j < Q3_VOL_HIST; j += VOL_THREADS) h[j] = keep[j];
 }
 
-VolumeStage::VolumeStage(int n_streams_, int max_group_) : n_streams(n_streams_), max_group(max_group_) {
-    Q3_CHECK(n_streams >= 1 && max_group >= 1, "bad volume stage shape");
+VolumeStage::VolumeStage(int n_streams_, int max_group_, StageCounters* count_) : StageBase(n_streams_, max_group_, count_, "volume stage") {
     hist_own.alloc((size_t)n_streams * Q3_VOL_HIST); hist_own.zero();
     hist = hist_own.p;
     Q3_HIP(hipStreamSynchronize(nullptr)); // the memset ran on the null stream, which the caller's non-blocking streams do not wait for
@@ -98,7 +97,7 @@ VolumeStage::VolumeStage(int n_streams_, int max_group_) : n_streams(n_streams_)
 }
 
 void VolumeStage::reset_async(hipStream_t st, int slot) {
-    Q3_CHECK(slot >= 0 && slot < n_streams, "stream out of range");
+    check_slot(slot);
     Q3_HIP(hipMemsetAsync(hist + (size_t)slot * Q3_VOL_HIST, 0, sizeof(float) * Q3_VOL_HIST, st));
 }
 
@@ -121,7 +120,7 @@ void launch_volume(hipStream_t st, VolumeStage& s, float* pcm, int G, int T, con
         m.slot = db10[g] == 0 ? -1 : streams[g];
         m.trace_off = trace ? trace_off[g] : 0;
         if (m.slot < 0) continue;
-        s.chunks += 1; s.samples += T;
+        s.count->vol_chunks += 1; s.count->vol_samples += T;
     }
     s.ring.commit(st, G);
     VolArgs a{pcm, T, dm, s.hist, trace};

@@ -2,6 +2,7 @@
 // gate, the gain helper, the launch check and the submit rule -- alone, plain g++ under the host sanitizers.  Reads commands on stdin, prints
 // one result line per answer.  Doubles and floats travel as hex bit patterns, so that nothing is rounded on the way.
 #include "../../qwen3-tts-rust_amd/csrc/loudness.h"
+#include "stage_preamble.h"
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -82,6 +83,12 @@ int main() {
             std::cin >> have_codec;
             const char* why = loudness_submit_refusal(have_codec != 0);
             printf("%s\n", why ? why : "ok");
+        } else if (cmd == "preamble") { // preamble -> "preamble <cases>": the shared checks in their order (stage_preamble.h)
+            if (!check_stage_preamble([](int G, int gmax, bool chunk_ok, const int32_t* s, int n, int bad) {
+                    int32_t met[4] = {1, 1, 1, 1}; int64_t pos[4];
+                    for (int g = 0; g < 4; g++) pos[g] = g == bad ? 7 : 1920;
+                    return loudness_launch_refusal(G, gmax, chunk_ok ? 1920 : 1000, s, n, met, pos);
+                }, "chunk length is no positive multiple of 1920 samples", "stream position is no multiple of 1920 samples")) return 1;
         } else {
             fprintf(stderr, "unknown command %s\n", cmd.c_str());
             return 2;

@@ -2,6 +2,7 @@
 // builder and launch check in csrc/pcm_out.h -- alone, plain g++ under the host sanitizers.  Reads commands on stdin, prints one result line
 // per answer.
 #include "../../qwen3-tts-rust_amd/csrc/pcm_out.h"
+#include "stage_preamble.h"
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -54,6 +55,12 @@ int main() {
             slots.push_back(0); fmt.push_back({0, 0});   // never read: keeps data() valid at G <= 0
             const char* why = pcm_convert_refusal(G, gmax, T, slots.data(), n_streams, fmt.data());
             printf("%s\n", why ? why : "ok");
+        } else if (cmd == "preamble") { // preamble -> "preamble <cases>": the shared checks in their order (stage_preamble.h)
+            if (!check_stage_preamble([](int G, int gmax, bool chunk_ok, const int32_t* s, int n, int bad) {
+                    q3tts_pcm_format fmt[4];
+                    for (int g = 0; g < 4; g++) fmt[g] = q3tts_pcm_format{g == bad ? 12345 : 16000, Q3_PCM_S16};
+                    return pcm_convert_refusal(G, gmax, chunk_ok ? 1920 : 1000, s, n, fmt);
+                }, "chunk length is no whole number of frames", "unknown sample rate")) return 1;
         } else {
             fprintf(stderr, "unknown command %s\n", cmd.c_str());
             return 2;

@@ -2,6 +2,7 @@
 // window tables, the visit order and the launch check in csrc/tsm.h -- alone, plain g++ under the host sanitizers.  Reads commands on stdin,
 // prints one result line per answer.
 #include "../../qwen3-tts-rust_amd/csrc/tsm.h"
+#include "stage_preamble.h"
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -53,6 +54,12 @@ int main() {
             const q3tts_pcm_format f{rate, enc};
             const char* why = tsm_submit_refusal(pct, f, max_steps, cap, have_codec != 0);
             printf("%s\n", why ? why : "ok");
+        } else if (cmd == "preamble") { // preamble -> "preamble <cases>": the shared checks in their order (stage_preamble.h)
+            if (!check_stage_preamble([](int G, int gmax, bool chunk_ok, const int32_t* s, int n, int bad) {
+                    int32_t pct[4], enc[4] = {Q3_PCM_F32, Q3_PCM_S16, Q3_PCM_F32, Q3_PCM_S16};
+                    for (int g = 0; g < 4; g++) pct[g] = g == bad ? 49 : 125;
+                    return tsm_launch_refusal(G, gmax, chunk_ok ? 1920 : 1000, false, s, n, pct, enc);
+                }, "chunk length is no positive multiple of 1920 samples", "speech rate out of range [50, 200]")) return 1;
         } else {
             fprintf(stderr, "unknown command %s\n", cmd.c_str());
             return 2;

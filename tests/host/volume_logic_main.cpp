@@ -1,6 +1,7 @@
 // Driver of tests/test_volume_ref_cpu.py: the host half of [EXT] volume -- the range, the gain and the submit rule in csrc/sched_logic.h and
 // the launch check in csrc/volume.h -- alone, plain g++ under the host sanitizers.  Reads commands on stdin, prints one result line per answer.
 #include "../../qwen3-tts-rust_amd/csrc/volume.h"
+#include "stage_preamble.h"
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -38,6 +39,12 @@ int main() {
             std::cin >> v >> have_codec;
             const char* why = volume_submit_refusal(v, have_codec != 0);
             printf("%s\n", why ? why : "ok");
+        } else if (cmd == "preamble") { // preamble -> "preamble <cases>": the shared checks in their order (stage_preamble.h)
+            if (!check_stage_preamble([](int G, int gmax, bool chunk_ok, const int32_t* s, int n, int bad) {
+                    int32_t db10[4];
+                    for (int g = 0; g < 4; g++) db10[g] = g == bad ? 201 : 60;
+                    return volume_launch_refusal(G, gmax, chunk_ok ? 1920 : 1000, s, n, db10);
+                }, "chunk length is no positive multiple of 1920 samples", "volume out of range [-400, 200]")) return 1;
         } else {
             fprintf(stderr, "unknown command %s\n", cmd.c_str());
             return 2;

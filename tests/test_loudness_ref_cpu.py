@@ -321,5 +321,10 @@ def test_launch_check(driver):
     assert driver(ok.replace(" 0 0 0 ", " 0 0 77 "))[0] == "ok"               # an unmetered stream's position is not looked at
 
 
+def test_the_shared_launch_checks_come_in_the_order_each_stage_stated_them(driver):
+    """group size, chunk, then stream by stream slot, once, own argument -- 5000 inputs with any number of them failing at once (tests/host/stage_preamble.h)"""
+    assert driver("preamble\n") == ["preamble 5000"]
+
+
 def test_submit_rule(driver):
     assert driver("submit 1\n") == ["ok"] and "codec" in driver("submit 0\n")[0]

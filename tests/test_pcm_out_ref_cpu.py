@@ -167,3 +167,8 @@ def test_launch_check(driver):
     assert "24000 Hz only" in driver(ok.replace("48000 1", "48000 0"))[0]
     assert "rate" in driver(ok.replace("8000 1", "11025 1"))[0] and "encoding" in driver(ok.replace("8000 1", "8000 2"))[0]
     assert "long" in driver(ok.replace("7680", str(1920 * 7700)))[0]
+
+
+def test_the_shared_launch_checks_come_in_the_order_each_stage_stated_them(driver):
+    """group size, chunk, then stream by stream slot, once, own argument -- 5000 inputs with any number of them failing at once (tests/host/stage_preamble.h)"""
+    assert driver("preamble\n") == ["preamble 5000"]

@@ -173,6 +173,11 @@ def test_launch_check(driver):
     assert "encoding" in driver(ok.replace(" 5 100 50 1", " 5 100 50 2"))[0] and "encoding" in driver(ok.replace(" 2 150 75 0", " 2 150 75 -1"))[0]
 
 
+def test_the_shared_launch_checks_come_in_the_order_each_stage_stated_them(driver):
+    """group size, chunk, then stream by stream slot, once, own argument -- 5000 inputs with any number of them failing at once (tests/host/stage_preamble.h)"""
+    assert driver("preamble\n") == ["preamble 5000"]
+
+
 def test_submit_rule(driver):
     cap = 24 * 1920 * 4                                                  # an engine of max_steps 24
     assert driver("submit 100 100 16000 1 24 %d 1\n" % cap)[0] == "ok"   # both off: any format, any length

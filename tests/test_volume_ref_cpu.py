@@ -174,6 +174,11 @@ def test_launch_check(driver):
     assert driver(ok.replace(" 5 120", " 5 200").replace(" 2 -60", " 2 -400"))[0] == "ok"
 
 
+def test_the_shared_launch_checks_come_in_the_order_each_stage_stated_them(driver):
+    """group size, chunk, then stream by stream slot, once, own argument -- 5000 inputs with any number of them failing at once (tests/host/stage_preamble.h)"""
+    assert driver("preamble\n") == ["preamble 5000"]
+
+
 def test_submit_rule(driver):
     assert driver("submit 0 1\nsubmit 120 1\nsubmit -400 1\nsubmit 200 1\n") == ["ok"] * 4
     assert all("volume out of range" in s for s in driver("submit 201 1\nsubmit -401 1\n"))
