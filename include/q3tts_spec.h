@@ -660,9 +660,16 @@ typedef struct q3tts_pcm_format { int32_t sample_rate; int32_t encoding; } q3tts
 typedef struct { const void* data; int64_t n_frames; int32_t sample_rate, channels, sample_format, downmix; } q3tts_intake_clip;
 typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t data_offset, n_frames; } q3tts_wav_info;
 
+/* ---------------- S3, K-quant rows: Q4_K ----------------
+ * Q4_K super-block (144 bytes, 256 weights): {f16 d, f16 dmin, u8 scales[12], u8 qs[128]} -- the Q5_K super-block without its qh[32].
+ * A Q4_K row IS the Q5_K row with the same d, dmin, scales and nibbles and bit 4 of every weight clear: weight = d * sc_b * q - dmin * m_b,
+ * q in [0, 15], (sc_b, m_b) the 6-bit pair of block b unpacked from scales[12] as for Q5_K.  Its chain is the Q5_K chain verbatim,
+ *   acc = fma(d * f(sc_b * isum_b) - dmin * f(m_b * xsum_b), dx_b, acc)     isum_b = sum q x (exact int32), xsum_b = sum x of the block,
+ * with the same block order inside a segment, the same segment order and the same super-segment slabs.  Nothing else of S3 changes. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
-    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30
+    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30
 };
 
 #endif /* Q3TTS_SPEC_H */

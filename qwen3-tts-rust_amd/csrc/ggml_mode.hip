@@ -263,7 +263,7 @@ void gg_quant(hipStream_t st, const float* x, int k, const GgAct& a, int ntok) {
     hipLaunchKernelGGL(k_gg_quant, dim3((k / 32 + 63) / 64, ntok), dim3(64), 0, st, x, k, a.q8, a.d8, a.qk, a.dk, a.bs);
 }
 void gg_matvec(hipStream_t st, const GgMat& w, int row0, int nrows, const GgAct& a, float* out, int out_stride, int ntok) {
-    Q3_CHECK(w.type == Q3_T_Q8_0 || w.type == Q3_T_Q5_K || w.type == Q3_T_Q6_K, "ggml mode serves Q8_0 / Q5_K / Q6_K matrices");
+    Q3_CHECK(gg_type_ok(w.type), gg_type_msg(w.type));
     Q3_CHECK(row0 >= 0 && nrows >= 0 && row0 + nrows <= w.n, "ggml-mode matvec row range");
     if (nrows == 0 || ntok == 0) return;
     hipLaunchKernelGGL(k_gg_matvec, dim3((nrows + 63) / 64, ntok), dim3(64), 0, st, w, row0, nrows, a, out, out_stride, ntok);

@@ -141,10 +141,11 @@ static int mfma_ztiles(int rowgroups, int nsseg, int ntok) {
 bool prefill_wide() { const char* e = std::getenv("Q3_PREFILL_WIDE"); return !(e && e[0] == '0'); }
 
 // =====================================================================================================
-// Mixed-type form (Q5_K_M files: Q5_K + Q6_K + Q8_0 rows in one fused matrix).  Same wave mapping and the same
+// Mixed-type form (Q5_K_M / Q4_K_M files: Q5_K or Q4_K + Q6_K + Q8_0 rows in one fused matrix).  Same wave mapping and the same
 // int8 tile layout as k_gemv_q8; the per-block arithmetic follows the weight type of the row group (spec S3):
 //   Q8_0: acc = fma(f(isum), dw*dx, acc)
 //   Q5_K: acc = fma(d*f(sc*isum1) - dmin*f(m*isum2), dx, acc)      isum2 = sum of the activation block
+//   Q4_K: the Q5_K line; the weights are the nibbles alone
 //   Q6_K: acc = fma(d*f(sc0*isum_lo + sc1*isum_hi), dx, acc)        (the two 16-element halves are the sub-blocks)
 // =====================================================================================================
 template <int LPR, int MT, int TS>
@@ -255,7 +256,7 @@ LinearPlan plan_linear(const LinearPlanIn& in) {
             // layers of the same shape take 4.7 us) with the same instruction and fetch counts but 4 x the SQ busy cycles
             // (gpurun_out/pmc_kq.txt, round 2); 4 lanes per row does not show it, so Q6_K matrices stop at 4.  Q3_KQ_Q6_LPR8=1 restores 8 for A/B.
             static const bool q6_lpr8 = [] { const char* e = std::getenv("Q3_KQ_Q6_LPR8"); return e && e[0] == '1'; }();
-            if (lpr == 8 && !in.lpr_hint && !q6_lpr8 && in.wts != Q3_T_Q5_K && in.wts != Q3_T_Q8_0) lpr = 4;
+            if (lpr == 8 && !in.lpr_hint && !q6_lpr8 && in.wts != Q3_T_Q5_K && in.wts != Q3_T_Q4_K && in.wts != Q3_T_Q8_0) lpr = 4;
             p.form = LIN_GEMV_KQ; p.lpr = lpr; p.mt = mt_of(in.ntok);
             return p;
         }
@@ -984,11 +985,12 @@ __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_tile1(Q8Mat w, int row0, int nrows, 
 }
 
 // -----------------------------------------------------------------------------------------------------
-// K-quant form of the matrix-core GEMM (Q5_K_M files, >= 16 tokens): the packed Q5_K / Q6_K planes are unpacked into the same int8 B operand
+// K-quant form of the matrix-core GEMM (Q5_K_M / Q4_K_M files, >= 16 tokens): the packed Q4_K / Q5_K / Q6_K planes are unpacked into the same int8 B operand
 // the Q8_0 kernel loads ready-made (WSlice<2, WT>: lane = half * 32 + row, 16 weights of the block), and v_mfma_i32_32x32x32_i8 again delivers the
 // exact integer block dots of 32 tokens x 32 rows.  What differs is the chain that follows (spec S3, K-quant rows):
 //   Q5_K  acc = fma(d * f(sc_b * idot) - dmin * f(m_b * xsum), dx, acc)     xsum[token] = sum of the activation block -- a second MFMA against an
 //                                                                          all-ones B tile puts it in every column of the C layout
+//   Q4_K  the Q5_K line: the B operand is the masked nibble words, nothing else differs
 //   Q6_K  acc = fma(d * f(s_lo * idot_lo + s_hi * idot_hi), dx, acc)         the two 16-element halves are separate sub-blocks: two MFMAs with the
 //         other half's lanes of B zeroed; stored values are q + 32, so idot_x = (stored dot) - 32 * xsum_x (two more MFMAs against half-ones tiles)
 // d, dmin, sc_b, m_b belong to the lane's weight row (C column); dx[token, block] comes, as in the Q8_0 kernel, from the f32 matrix pipe: an outer
@@ -1013,7 +1015,7 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
     const int row_first = row0 + blockIdx.x * 32; // (a workgroup's rows sit in one 32-row group: one weight type)
     wslice_dispatch<TS>(w, (row_first > w.Npad - 1 ? w.Npad - 1 : row_first) >> 5, [&](auto tag) {
         constexpr int WT = decltype(tag)::value;
-        constexpr bool Q5 = WT == Q3_T_Q5_K, Q6 = WT == Q3_T_Q6_K;
+        constexpr bool Q5 = WT == Q3_T_Q5_K || WT == Q3_T_Q4_K, Q6 = WT == Q3_T_Q6_K; // (Q4_K runs the Q5_K chain on its 4-bit operand)
 #pragma unroll 1
         for (int q = 0; q < NM; q++) {
             WSlice<2, WT> ws;
@@ -1056,11 +1058,9 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
                                 const int scb = ws.mbyte(i), mb = ws.mbyte(8 + i);
 #pragma unroll
                                 for (int g = 0; g < 16; g++) {
-                                    const int i1 = __mul24(scb, c[g]), i2v = __mul24(mb, cx[g]); // |idot| <= 32 * 31 * 127 and the 6-bit scales fit v_mul_i32_i24 (full rate; v_mul_lo_u32 is quarter rate)
-                                    const float a = d0 * (float)i1;
-                                    const float a2 = d1 * (float)i2v;
-                                    const float diff = a - a2;
-                                    acc[g] = q3_fmaf(diff, D[16 * i2 + g], acc[g]);
+                                    const int i1 = __mul24(scb, c[g]), i2v = __mul24(mb, cx[g]); // |idot| <= 32 * 31 * 127 (Q4_K: 32 * 15 * 127) and the 6-bit scales fit v_mul_i32_i24 (full rate; v_mul_lo_u32 is quarter rate)
+                                    const float diff = kq_block_term<WT == Q3_T_Q4_K>(d0, i1, d1, i2v);
+                                    acc[g] = kq_block_fma<WT == Q3_T_Q4_K>(diff, D[16 * i2 + g], acc[g]);
                                 }
                             } else if (Q6) {
                                 const i32x4v wlo = half ? zero4 : wv, whi = half ? wv : zero4, olo = half ? zero4 : ones, ohi = half ? ones : zero4;

@@ -56,6 +56,41 @@ __global__ void k_repack_q5k(const uint8_t* __restrict__ raw, int n, int K, int 
         memcpy(base + 4096 + r32 * 32 + j * 4, &H, 4);
     }
 }
+// Q4_K super-block {f16 d, dmin; u8 scales[12]; u8 qs[128]} -> the nibble plane alone (4096 B per row group and segment, kernels.h) + {d,dmin} +
+// {sc[8], m[8]}.  One thread per (row, segment, block): the nibble plane of a block is 16 B per row, written as four dwords.
+__global__ void k_repack_q4k(const uint8_t* __restrict__ raw, int n, int K, int row_off, uint8_t* __restrict__ qs, const uint32_t* __restrict__ rg_off,
+                             uint16_t* __restrict__ sc, uint8_t* __restrict__ meta) {
+    const int nseg = K >> 8;
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (size_t)n * nseg * 8) return;
+    const int j = (int)(id & 7);
+    const size_t rs = id >> 3;
+    const int r = (int)(rs / nseg), s = (int)(rs % nseg);
+    const uint8_t* blk = raw + rs * 144;
+    const int row = row_off + r, rg = row >> 5, r32 = row & 31;
+    const size_t vidx = ((size_t)rg * nseg + s) * 32 + r32;
+    const uint8_t *scales = blk + 4, *ql = blk + 16 + 32 * (j >> 1);
+    if (j == 0) {
+        uint16_t d, dm;
+        memcpy(&d, blk, 2); memcpy(&dm, blk + 2, 2);
+        for (int i = 0; i < 8; i++) sc[vidx * 8 + i] = i == 0 ? d : i == 1 ? dm : 0;
+    }
+    int scv, mv;
+    if (j < 4) { scv = scales[j] & 63; mv = scales[j + 4] & 63; }
+    else { scv = (scales[j + 4] & 0xF) | ((scales[j - 4] >> 6) << 4); mv = (scales[j + 4] >> 4) | ((scales[j] >> 6) << 4); }
+    meta[vidx * 16 + j] = (uint8_t)scv; meta[vidx * 16 + 8 + j] = (uint8_t)mv;
+    const int sh = 4 * (j & 1); // even blocks are the low nibbles of their 32 bytes, odd blocks the high ones
+    uint8_t* base = qs + (size_t)rg_off[rg] * 16 + (size_t)s * 4096 + j * 512 + r32 * 8;
+    for (int h = 0; h < 2; h++)
+        for (int w = 0; w < 2; w++) {
+            uint32_t word = 0; // byte bb = weights 16h + 8w + bb (low nibble) and 16h + 8w + 4 + bb (high nibble) of the block
+            for (int bb = 0; bb < 4; bb++) {
+                const uint32_t lo = (ql[16 * h + 8 * w + bb] >> sh) & 0xFu, hi = (ql[16 * h + 8 * w + 4 + bb] >> sh) & 0xFu;
+                word |= (lo | (hi << 4)) << (8 * bb);
+            }
+            memcpy(base + h * 256 + w * 4, &word, 4);
+        }
+}
 // Q6_K super-block {u8 ql[128]; u8 qh[64]; i8 scales[16]; f16 d} -> packed planes (values kept +32, unsigned 6 bit) + d + 16 sub-block scales
 __global__ void k_repack_q6k(const uint8_t* __restrict__ raw, int n, int K, int row_off, uint8_t* __restrict__ qs, const uint32_t* __restrict__ rg_off,
                              uint16_t* __restrict__ sc, uint8_t* __restrict__ meta) {
@@ -120,10 +155,11 @@ Q8Mat build_q8mat(const WLayout& L, const void* const* raw, DevBuf<uint8_t>& blo
         const size_t raw_bytes = (size_t)t.rows * q3_gguf_row_bytes(t.type, L.K);
         DevBuf<uint8_t> d(raw_bytes);
         d.upload((const uint8_t*)raw[i], raw_bytes);
-        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 ? 32 : 256));
+        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 || t.type == Q3_T_Q4_K ? 32 : 256)); // threads: one per block (Q8_0, Q4_K) or super-block
         const dim3 grid((unsigned)((nblk + 255) / 256));
         // Q8_0 tiles are laid out the same in both layouts: the kernel is based on the tensor's first row group and counts rows from there
         if (t.type == Q3_T_Q8_0) hipLaunchKernelGGL(k_repack_q8, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0 & 31, base + (size_t)L.rg_off[(size_t)(t.row0 / 32)] * 16, sc, t.row0 & ~31);
+        else if (t.type == Q3_T_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else if (t.type == Q3_T_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         Q3_HIP(hipDeviceSynchronize());
@@ -135,19 +171,20 @@ Q8Mat kqmat_from_host(const void* const* raw, const int32_t* types, const int32_
     std::vector<WTensor> t;
     int n = 0;
     for (int i = 0; i < nw; i++) { t.push_back({types[i], n, rows[i]}); n += rows[i]; }
-    return build_q8mat(plan_wlayout(t, n, k, true), raw, storage);
+    return build_q8mat(plan_wlayout(t, n, k, true, WL_TYPES_KQ4), raw, storage);
 }
 
 Q8Mat Transformer::make_mat(const Gguf& g, const std::vector<std::pair<std::string, int>>& rows, int N, int K) {
     std::vector<WTensor> tensors; std::vector<const void*> raw;
     for (auto& r : rows) {
         const GgufTensor& t = g.need(r.first);
-        if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K)
-            throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q5_K, Q6_K)");
+        if (ggml_mode_) Q3_CHECK(gg_type_ok(t.type), "ggml mode: type of " + r.first + ": " + gg_type_msg(t.type)); // before anything is repacked
+        if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q4_K && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K)
+            throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q4_K, Q5_K, Q6_K)");
         Q3_CHECK(t.ne[0] == K, "unexpected K for " + r.first);
         tensors.push_back({t.type, r.second, (int)t.ne[1]}); raw.push_back(t.data);
     }
-    const WLayout L = plan_wlayout(tensors, N, K, false);
+    const WLayout L = plan_wlayout(tensors, N, K, false, WL_TYPES_KQ4);
     blobs_.emplace_back();
     return build_q8mat(L, raw.data(), blobs_.back());
 }
@@ -206,6 +243,7 @@ Transformer::Transformer(const std::string& path, int n_ctx, int max_tok) : n_ct
     Q3_CHECK(hp_.n_head * 128 <= 2048, "n_head*128 must be <= 2048 (single super-segment o-proj)");
     const int d = hp_.n_embd, dq = hp_.n_head * 128, dkv = hp_.n_kv * 128, ff = hp_.n_ff;
     layers_.resize(hp_.n_layer);
+    if (const char* e = std::getenv("Q3_SPEC")) ggml_mode_ = std::string(e) == "ggml"; // (read before the matrices are built: make_mat refuses a type the mode lacks)
     {
         const int t0 = g.need("blk.0.attn_q.weight").type;
         float_mode_ = (t0 == Q3_T_F32 || t0 == Q3_T_F16 || t0 == Q3_T_BF16);
@@ -239,7 +277,6 @@ Transformer::Transformer(const std::string& path, int n_ctx, int max_tok) : n_ct
         if (l == 0) layer_weight_bytes_ = L.wqkv.bytes() + L.wo.bytes() + L.wgu.bytes() + L.wdown.bytes();
         weight_bytes_ += L.wqkv.bytes() + L.wo.bytes() + L.wgu.bytes() + L.wdown.bytes();
     }
-    if (const char* e = std::getenv("Q3_SPEC")) ggml_mode_ = std::string(e) == "ggml";
     if (ggml_mode_) {
         Q3_CHECK(!float_mode_, "Q3_SPEC=ggml serves Q8_0 / Q5_K_M files (float-weight files have no ggml-mode kernels)");
         gg_layers_.resize(hp_.n_layer);
@@ -324,7 +361,7 @@ void Transformer::alloc_workspace() {
 GgMat Transformer::gg_load(const Gguf& g, const std::string& name, int n_expect, int k_expect) {
     const GgufTensor& t = g.need(name);
     Q3_CHECK((int)t.ne[0] == k_expect && (int)t.ne[1] == n_expect, "ggml mode: shape of " + name);
-    Q3_CHECK(t.type == Q3_T_Q8_0 || t.type == Q3_T_Q5_K || t.type == Q3_T_Q6_K, "ggml mode: type of " + name);
+    Q3_CHECK(gg_type_ok(t.type), "ggml mode: type of " + name + ": " + gg_type_msg(t.type));
     GgMat m; m.type = t.type; m.n = n_expect; m.k = k_expect;
     m.row_bytes = q3_gguf_row_bytes(t.type, k_expect);
     blobs_.emplace_back(m.row_bytes * (size_t)n_expect);

@@ -4,7 +4,7 @@
  * No real Qwen3-TTS weights exist offline (the reference downloads them at run time,
  * /root/reference/src/download.rs:66-87), so benchmarks and parity tests run on seeded random weights of
  * the same architecture, written in the same container format the reference loads:
- *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
+ *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
  *   <out>/onnx/q3tts_codec.gguf        (stand-in for qwen3_tts_decoder.onnx)
  * (directory names: /root/reference/src/tts/engine.rs:91-95,123-124).
  *
@@ -48,16 +48,18 @@ static void enc_q8_0(const float* x, int64_t k, uint8_t* out) {
         for (int i = 0; i < 32; i++) out[34 * b + 2 + i] = (uint8_t)(int8_t)lrintf(x[32 * b + i] * id);
     }
 }
-static void enc_q5_k(const float* x, int64_t k, uint8_t* out) {
+/* Q5_K and Q4_K share one encoder: `levels` = 31 or 15 quantisation steps, `bsz` = 176 (Q5_K: qh[32] in front of qs) or 144 (Q4_K: no qh).
+ * 15 levels in 176-byte blocks is the Q5_K twin of a Q4_K row (--q4k-as-q5k): the same d, dmin, scales and nibbles under an all-zero qh. */
+static void enc_q45_k(const float* x, int64_t k, uint8_t* out, int levels, int bsz) {
     for (int64_t s = 0; s < k / 256; s++) {
         const float* xs = x + 256 * s;
-        uint8_t* blk = out + 176 * s;
-        memset(blk, 0, 176);
+        uint8_t* blk = out + bsz * s;
+        memset(blk, 0, (size_t)bsz);
         float scale[8], mn[8], maxscale = 0, maxmin = 0;
         for (int j = 0; j < 8; j++) {
             float lo = 0, hi = 0;
             for (int l = 0; l < 32; l++) { float v = xs[32 * j + l]; if (v < lo) lo = v; if (v > hi) hi = v; }
-            scale[j] = (hi - lo) / 31.0f; mn[j] = -lo;
+            scale[j] = (hi - lo) / (float)levels; mn[j] = -lo;
             if (scale[j] > maxscale) maxscale = scale[j];
             if (mn[j] > maxmin) maxmin = mn[j];
         }
@@ -69,7 +71,7 @@ static void enc_q5_k(const float* x, int64_t k, uint8_t* out) {
             mq[j] = dmin > 0 ? (int)lrintf(mn[j] / dmin) : 0; if (mq[j] > 63) mq[j] = 63;
         }
         memcpy(blk, &dh, 2); memcpy(blk + 2, &dmh, 2);
-        uint8_t* scales = blk + 4; uint8_t* qh = blk + 16; uint8_t* qs = blk + 48;
+        uint8_t* scales = blk + 4; uint8_t* qh = blk + 16; uint8_t* qs = blk + bsz - 128;
         for (int j = 0; j < 4; j++) {
             scales[j] = (uint8_t)(sc[j] | ((sc[j + 4] >> 4) << 6));
             scales[j + 4] = (uint8_t)(mq[j] | ((mq[j + 4] >> 4) << 6));
@@ -80,17 +82,20 @@ static void enc_q5_k(const float* x, int64_t k, uint8_t* out) {
             float de = d * (float)sc[j], me = dmin * (float)mq[j];
             for (int l = 0; l < 32; l++) {
                 int v = de > 0 ? (int)lrintf((xs[32 * j + l] + me) / de) : 0;
-                q[32 * j + l] = v < 0 ? 0 : (v > 31 ? 31 : v);
+                q[32 * j + l] = v < 0 ? 0 : (v > levels ? levels : v);
             }
         }
         for (int jj = 0; jj < 4; jj++)
             for (int l = 0; l < 32; l++) {
                 int a = q[64 * jj + l], b = q[64 * jj + 32 + l];
                 qs[32 * jj + l] = (uint8_t)((a & 0xF) | ((b & 0xF) << 4));
-                qh[l] |= (uint8_t)(((a >> 4) << (2 * jj)) | ((b >> 4) << (2 * jj + 1)));
+                if (bsz == 176) qh[l] |= (uint8_t)(((a >> 4) << (2 * jj)) | ((b >> 4) << (2 * jj + 1)));
             }
     }
 }
+static int g_q4k_as_q5k = 0; /* --q4k-as-q5k: Q5_K tensors carry 15-level values */
+static void enc_q5_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, g_q4k_as_q5k ? 15 : 31, 176); }
+static void enc_q4_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, 15, 144); }
 static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
     for (int64_t s = 0; s < k / 256; s++) {
         const float* xs = x + 256 * s;
@@ -133,6 +138,7 @@ static size_t row_bytes(int type, int64_t k) {
         case Q3_T_F32: return (size_t)k * 4;
         case Q3_T_F16: case Q3_T_BF16: return (size_t)k * 2;
         case Q3_T_Q8_0: return (size_t)(k / 32) * 34;
+        case Q3_T_Q4_K: return (size_t)(k / 256) * 144;
         case Q3_T_Q5_K: return (size_t)(k / 256) * 176;
         case Q3_T_Q6_K: return (size_t)(k / 256) * 210;
     }
@@ -144,6 +150,7 @@ static void enc_row(int type, const float* x, int64_t k, uint8_t* out) {
         case Q3_T_F16: for (int64_t i = 0; i < k; i++) { uint16_t h = q3_f32_to_f16(x[i]); memcpy(out + 2 * i, &h, 2); } break;
         case Q3_T_BF16: for (int64_t i = 0; i < k; i++) { uint16_t h = q3_f32_to_bf16(x[i]); memcpy(out + 2 * i, &h, 2); } break;
         case Q3_T_Q8_0: enc_q8_0(x, k, out); break;
+        case Q3_T_Q4_K: enc_q4_k(x, k, out); break;
         case Q3_T_Q5_K: enc_q5_k(x, k, out); break;
         case Q3_T_Q6_K: enc_q6_k(x, k, out); break;
     }
@@ -260,10 +267,10 @@ static int wtype(const char* quant, const char* kind, int layer, int n_layer) {
     if (!strcmp(quant, "bf16")) return Q3_T_BF16;
     if (!strcmp(quant, "f16")) return Q3_T_F16;
     if (!strcmp(quant, "f32")) return Q3_T_F32;
-    if (!strcmp(quant, "q5_k_m")) {
+    if (!strcmp(quant, "q5_k_m") || !strcmp(quant, "q4_k_m")) { /* llama.cpp's Q4_K_M is the same mix with Q4_K where Q5_K stands [EXT] */
         if (!strcmp(kind, "output")) return Q3_T_Q6_K;
         if ((!strcmp(kind, "attn_v") || !strcmp(kind, "ffn_down")) && use_more_bits(layer, n_layer)) return Q3_T_Q6_K;
-        return Q3_T_Q5_K;
+        return (quant[1] == '4' && !g_q4k_as_q5k) ? Q3_T_Q4_K : Q3_T_Q5_K;
     }
     fprintf(stderr, "unknown quant %s\n", quant);
     exit(2);
@@ -413,9 +420,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = strtoull(argv[++i], NULL, 10);
         else if (!strcmp(argv[i], "--text-rows") && i + 1 < argc) text_rows = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--what") && i + 1 < argc) what = atoi(argv[++i]);
-        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|bf16|f16|f32] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
+        else if (!strcmp(argv[i], "--q4k-as-q5k")) g_q4k_as_q5k = 1;
+        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|bf16|f16|f32] [--q4k-as-q5k] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
     }
     if (!out) { fprintf(stderr, "--out required\n"); return 2; }
+    if (g_q4k_as_q5k && strcmp(quant, "q4_k_m")) { fprintf(stderr, "--q4k-as-q5k goes with --quant q4_k_m\n"); return 2; }
 #ifdef _OPENMP
     if (!getenv("OMP_NUM_THREADS")) { int n = omp_get_num_procs(); omp_set_num_threads(n > 8 ? 8 : n); } /* cgroup CPU shares are smaller than the core count */
 #endif
@@ -429,7 +438,7 @@ int main(int argc, char** argv) {
         pred = (tfcfg){ 256, 2, 2, 1, 512, 30720, 0 };
         codec = (ccfg){ 64, 32, 2, 2, 32, 128, 8, 256, 2, 4, { 2, 2 }, { 8, 5, 4, 3 } };
     } else { fprintf(stderr, "unknown preset\n"); return 2; }
-    const char* qdir = !strcmp(quant, "q8_0") ? "gguf_q8_0" : !strcmp(quant, "q5_k_m") ? "gguf_q5_k_m" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
+    const char* qdir = !strcmp(quant, "q8_0") ? "gguf_q8_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") ? "gguf_q4_k_m" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
     char p[1024];
     mkdir(out, 0755);
     snprintf(p, sizeof(p), "%s/%s", out, qdir); mkdir(p, 0755);
