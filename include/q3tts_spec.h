@@ -667,9 +667,22 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
  *   acc = fma(d * f(sc_b * isum_b) - dmin * f(m_b * xsum_b), dx_b, acc)     isum_b = sum q x (exact int32), xsum_b = sum x of the block,
  * with the same block order inside a segment, the same segment order and the same super-segment slabs.  Nothing else of S3 changes. */
 
+/* ---------------- S3, K-quant rows: Q3_K [EXT] ----------------
+ * Q3_K super-block (110 bytes, 256 weights) [EXT: restated from the public ggml format, no ggml source was at hand; no real Q3_K_M file has been
+ * through the engine]: {u8 hmask[32], u8 qs[64], u8 scales[12], f16 d}.  Weight e = 128 h + 32 g + l (h in 0..1, g in 0..3, l in 0..31):
+ *   low2 = (qs[32 h + l] >> 2 g) & 3,   q = low2 - ((hmask[l] >> (4 h + g)) & 1 ? 0 : 4)   in [-4, 3];
+ * sub-block is = e / 16 has the 6-bit scale s6[is], j = is & 3:
+ *   is 0..3: (scales[j] & 15) | ((scales[8+j] & 3) << 4)          is 4..7:   (scales[4+j] & 15) | (((scales[8+j] >> 2) & 3) << 4)
+ *   is 8..11: (scales[j] >> 4) | (((scales[8+j] >> 4) & 3) << 4)  is 12..15: (scales[4+j] >> 4) | (((scales[8+j] >> 6) & 3) << 4)
+ * and w[e] = d * (s6[is] - 32) * q.  A Q3_K row IS the Q6_K row with the same d, i8 sub-block scales s6 - 32 and quants q: its segment value is
+ * seg_q6_k of that twin -- per 32-block j, i = sc[2j] * s1 + sc[2j+1] * s2 in int32 (s1, s2 the exact int dots of the two 16-element sub-blocks),
+ * a = d * (float)i, acc = fma(a, xd[j], acc) -- with the same block order, segment order and super-segment slabs.  Nothing else of S3 changes.
+ * The Q3_K_M mix q3synth writes (attn_q, attn_k, ffn_gate, ffn_up Q3_K; attn_v Q5_K in layers 0 and 1, else Q4_K; attn_output Q4_K; ffn_down
+ * Q5_K below n_layer / 16, else Q4_K; output / head tensors Q6_K) is llama.cpp's as remembered [EXT, unpinned]. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
-    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30
+    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q3_K = 11, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30
 };
 
 #endif /* Q3TTS_SPEC_H */

@@ -12,6 +12,7 @@ namespace q3 {
 static std::string quant_dir(const std::string& q) { // engine.rs:91-95 (+ this engine's extra dirs)
     if (q == "q5_k_m") return "gguf_q5_k_m";
     if (q == "q4_k_m") return "gguf_q4_k_m";
+    if (q == "q3_k_m") return "gguf_q3_k_m";
     if (q == "q8_0") return "gguf_q8_0";
     if (q == "bf16") return "gguf_bf16";
     if (q == "f16") return "gguf_f16";

@@ -20,14 +20,18 @@ struct Q8Mat {
     int N = 0;      // logical rows
     int Npad = 0;   // rows padded to 32
     int K = 0;
-    // K-quant rows (Q4_K / Q5_K / Q6_K) stay PACKED in HBM and are unpacked in registers in front of the int8 dot products.  A matrix with K-quant
+    // K-quant rows (Q3_K / Q4_K / Q5_K / Q6_K) stay PACKED in HBM and are unpacked in registers in front of the int8 dot products.  A matrix with K-quant
     // row groups carries the ggml type and the byte offset (in 16-B units) of every 32-row group; per (row group, 256-segment):
     //   nibble plane   [8 blocks][2 halves][32 rows][8 B]   low 4 bits; byte b of word w holds weights 8w+b (low nibble) and 8w+4+b (high nibble) of the half
     //   high plane     Q4_K: none -- the nibble plane is the whole (row group, segment), 4096 B
     //                  Q5_K: [32 rows][8 blocks][4 B]        bit 8b+J of the word = bit 4 of weight 4J+b of the block
     //                  Q6_K: [32 rows][8 blocks][2][4 B]     the same for bit 4 (word 0) and bit 5 (word 1); values are stored +32 (unsigned 6 bit)
-    // = 0.5 / 0.625 / 0.75 B per weight (+ 0.125 of scales and metadata), against 1.125 for the int8 planes round 1 expanded them to.
-    // Metadata: one 16-B vector per (row, segment): Q4_K, Q5_K = {sc[8], m[8]} u8 with d,dmin in sc[0..1]; Q6_K = 16 i8 sub-block scales with d in sc[0].
+    // Q3_K has planes of its own, 3072 B per (row group, segment):
+    //   2-bit plane    [8 blocks][32 rows][2 halves][4 B]   bits 8b+2s, 8b+2s+1 of a half's word = low 2 bits of weight 4s+b of the half: (word >> 2s) & 0x03030303
+    //   bit plane      [32 rows][8 blocks][4 B]             bit 8b+J of the word = third bit of weight 4J+b of the block (the Q5_K arrangement); values are stored +4
+    // = 0.375 / 0.5 / 0.625 / 0.75 B per weight (+ 0.125 of scales and metadata), against 1.125 for the int8 planes round 1 expanded them to.
+    // Metadata: one 16-B vector per (row, segment): Q4_K, Q5_K = {sc[8], m[8]} u8 with d,dmin in sc[0..1]; Q6_K, Q3_K = 16 i8 sub-block scales with d in sc[0]
+    // (Q3_K: the 6-bit codes of the file minus 32, unpacked at load).
     const uint8_t* rg_type = nullptr;   // [Npad/32], null => all Q8_0 (uniform 1-KiB tiles)
     const uint32_t* rg_off = nullptr;   // [Npad/32] offset of the row group's quants from qs in 16-B units (K-quant matrices only)
     const uint8_t* meta = nullptr;      // [N/32][K/256][32 rows][16 B]
@@ -206,7 +210,7 @@ bool prefill_wide(); // Q3_PREFILL_WIDE != 0 (the default): prompt chunks of 512
 struct LinearPlanIn {
     int op = LOP_GEMV;
     int K = 0, row0 = 0, nrows = 0, ntok = 0, ff = 0;
-    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 8 / 12 / 13 / 14 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
+    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 8 / 11 / 12 / 13 / 14 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
     bool kq = false;      // quantised matrix built from K-quant-file tensors (Q8Mat::rg_type != null)
     int kq_parts = 0;     // Q8Mat::nparts
     bool has_wt = false;  // float: the tiled copy exists

@@ -147,6 +147,7 @@ bool prefill_wide() { const char* e = std::getenv("Q3_PREFILL_WIDE"); return !(e
 //   Q5_K: acc = fma(d*f(sc*isum1) - dmin*f(m*isum2), dx, acc)      isum2 = sum of the activation block
 //   Q4_K: the Q5_K line; the weights are the nibbles alone
 //   Q6_K: acc = fma(d*f(sc0*isum_lo + sc1*isum_hi), dx, acc)        (the two 16-element halves are the sub-blocks)
+//   Q3_K: the Q6_K line; the weights are 3-bit values unpacked to int8 q (Q3_K_M files: q, k, gate, up)
 // =====================================================================================================
 template <int LPR, int MT, int TS>
 __global__ void __launch_bounds__(512) k_gemv_kq(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq,
@@ -993,6 +994,8 @@ __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_tile1(Q8Mat w, int row0, int nrows, 
 //   Q4_K  the Q5_K line: the B operand is the masked nibble words, nothing else differs
 //   Q6_K  acc = fma(d * f(s_lo * idot_lo + s_hi * idot_hi), dx, acc)         the two 16-element halves are separate sub-blocks: two MFMAs with the
 //         other half's lanes of B zeroed; stored values are q + 32, so idot_x = (stored dot) - 32 * xsum_x (two more MFMAs against half-ones tiles)
+//   Q3_K  the Q6_K line, two MFMAs per block: the B operand is the 2-bit word merged with its plane bits and sign-extended to int8 q (wslice.h),
+//         so the stored dot IS idot_x and no half-ones tile is multiplied
 // d, dmin, sc_b, m_b belong to the lane's weight row (C column); dx[token, block] comes, as in the Q8_0 kernel, from the f32 matrix pipe: an outer
 // product with 1.0 lays the activation scales of two blocks out in the C layout.  Built for 2 waves per SIMD (the extra accumulators do not fit 128 VGPRs).
 // Before this kernel the batched path of a Q5_K_M file swept the weights once per 8 tokens (k_gemv_kq z tiles): C3 247 audio-s/s against 620 on Q8_0.
@@ -1015,7 +1018,8 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
     const int row_first = row0 + blockIdx.x * 32; // (a workgroup's rows sit in one 32-row group: one weight type)
     wslice_dispatch<TS>(w, (row_first > w.Npad - 1 ? w.Npad - 1 : row_first) >> 5, [&](auto tag) {
         constexpr int WT = decltype(tag)::value;
-        constexpr bool Q5 = WT == Q3_T_Q5_K || WT == Q3_T_Q4_K, Q6 = WT == Q3_T_Q6_K; // (Q4_K runs the Q5_K chain on its 4-bit operand)
+        constexpr bool Q5 = WT == Q3_T_Q5_K || WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, Q6 = WT == Q3_T_Q6_K || Q3; // (Q4_K runs the Q5_K chain on its 4-bit operand, Q3_K the Q6_K chain on its 3-bit one)
+        constexpr int SUBOFF = WSlice<2, WT>::SUBOFF;
 #pragma unroll 1
         for (int q = 0; q < NM; q++) {
             WSlice<2, WT> ws;
@@ -1066,14 +1070,14 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
                                 const i32x4v wlo = half ? zero4 : wv, whi = half ? wv : zero4, olo = half ? zero4 : ones, ohi = half ? ones : zero4;
                                 const i32x16 clo = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, wlo, z16, 0, 0, 0);
                                 const i32x16 chi = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, whi, z16, 0, 0, 0);
-                                const i32x16 xlo = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, olo, z16, 0, 0, 0);
-                                const i32x16 xhi = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, ohi, z16, 0, 0, 0);
+                                const i32x16 xlo = SUBOFF ? __builtin_amdgcn_mfma_i32_32x32x32_i8(av, olo, z16, 0, 0, 0) : z16;
+                                const i32x16 xhi = SUBOFF ? __builtin_amdgcn_mfma_i32_32x32x32_i8(av, ohi, z16, 0, 0, 0) : z16;
                                 const int s0 = (int)(int8_t)ws.mbyte(2 * i), s1 = (int)(int8_t)ws.mbyte(2 * i + 1);
 #pragma unroll
                                 for (int g = 0; g < 16; g++) {
-                                    const int isum = __mul24(clo[g] - 32 * xlo[g], s0) + __mul24(chi[g] - 32 * xhi[g], s1); // 17-bit x 8-bit factors: exact in the 24-bit multiplier
-                                    const float a = d0 * (float)isum;
-                                    acc[g] = q3_fmaf(a, D[16 * i2 + g], acc[g]);
+                                    const int isum = __mul24(clo[g] - SUBOFF * xlo[g], s0) + __mul24(chi[g] - SUBOFF * xhi[g], s1); // 17-bit x 8-bit factors: exact in the 24-bit multiplier
+                                    const float a = kq_block_scale<Q3>(d0, isum);
+                                    acc[g] = kq_block_fma<Q3>(a, D[16 * i2 + g], acc[g]);
                                 }
                             } else { // Q8_0 row group of a K-quant matrix: f(idot) * (dw * dx)
                                 const i32x16 c = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, wv, z16, 0, 0, 0);

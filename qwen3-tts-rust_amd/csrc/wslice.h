@@ -1,6 +1,6 @@
 // wslice.h -- one lane's slice of a weight matrix for the GEMV family: the quants of (row, 256-segment) this lane multiplies, fetched from
 // the Q8_0 tiles or from the packed K-quant planes (kernels.h), and the block chain of spec S3 that turns them into a partial sum.
-// Shared by k_gemv_kq, k_gemv_q8_norm, and k_gateup_swiglu, so the fused decode path serves Q5_K_M and Q4_K_M files with the same
+// Shared by k_gemv_kq, k_gemv_q8_norm, and k_gateup_swiglu, so the fused decode path serves Q5_K_M, Q4_K_M and Q3_K_M files with the same
 // launches as Q8_0 files.  The weight type is a TEMPLATE parameter: a kernel reads the type of its row group from the kernel arguments (a
 // scalar) and enters the body compiled for it -- with the type as a run-time value inside one body the compiler merges the three load
 // sequences with selects on loaded data, which parks the wave on the weight stream before the norm prologue (measured: 16 -> 20 us).
@@ -9,6 +9,8 @@
 //   WT = Q5_K     acc = fma(d*f(sc*isum) - dmin*f(m*xsum), dx, acc)        xsum = sum of the activation block
 //   WT = Q4_K     the Q5_K chain on 4-bit values: the nibble plane is the whole segment, no plane word is fetched and none is merged
 //   WT = Q6_K     acc = fma(d*f(sc0*isum_lo + sc1*isum_hi), dx, acc)        the two 16-element halves are the sub-blocks; stored values are q + 32
+//   WT = Q3_K     the Q6_K chain on 3-bit values: one 2-bit word and one bit-plane word per 16 weights, i8 scales unpacked at load.  HBM holds
+//                 q + 4 (unsigned); finish() sign-extends to the int8 q itself, so the chain needs no offset term: sum q x comes out of v_dot4 whole
 #pragma once
 #include <type_traits>
 #include "kdev.h"
@@ -45,6 +47,16 @@ __device__ __forceinline__ float kq_block_fma(float diff, float dx, float acc) {
     return r;
 }
 
+// a = d * f(isum) of the Q6_K / Q3_K chain: plain C++ for Q6_K as ever, one VALU instruction for the Q3_K body (see above)
+template <bool SCALAR>
+__device__ __forceinline__ float kq_block_scale(float d0, int isum) {
+    if (!SCALAR) return d0 * (float)isum;
+    const float f = (float)isum;
+    float a;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(a) : "v"(d0), "v"(f));
+    return a;
+}
+
 // 16 packed K-quant weights of (block, half) -> 16 unsigned bytes in k order: nibble words + one bit-plane word per extra bit
 // (kernels.h: bit 8b+J of a plane word belongs to weight 4J+b of the block; J = 4*half + word index)
 template <bool SIX>
@@ -63,12 +75,21 @@ __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
     return rgs >= w.p2_rg0 ? w.p2_type : rgs >= w.p1_rg0 ? w.p1_type : w.p0_type;
 }
 // run body(wt_tag<type>) for the type of row group rg.  TS = what the host knows about the launch: 0 = all-Q8_0 matrix (uniform tiles),
-// Q8_0 / Q4_K / Q5_K / Q6_K = K-quant matrix whose rows all have that type (one body in the kernel: o-proj, down, gate/up), -1 = mixed (fused
-// QKV of a Q5_K_M or Q4_K_M file: q, k Q5_K or Q4_K and v Q6_K) -- the type is read from the kernel arguments and all four bodies are in the kernel.
+// Q8_0 / Q3_K / Q4_K / Q5_K / Q6_K = K-quant matrix whose rows all have that type (one body in the kernel: o-proj, down, gate/up), -1 = mixed (fused
+// QKV of a Q5_K_M or Q4_K_M file: q, k Q5_K or Q4_K and v Q6_K) -- the type is read from the kernel arguments and the four bodies those files
+// need are in the kernel; -2 = mixed with a Q3_K part (fused QKV of a Q3_K_M file: q, k Q3_K and v Q4_K or Q5_K): the Q3_K, Q4_K and Q5_K
+// bodies, which is every mixture build_q8mat lets Q3_K into.  The fifth body has kernels of its own because adding it to the -1 kernels changed
+// their registers (k_gemv_kq<8, *, -1> gained scratch): a Q5_K_M or Q4_K_M file keeps launching exactly the code it launched before Q3_K existed.
 template <int TS, typename F>
 __device__ __forceinline__ void wslice_dispatch(const Q8Mat& w, int rg, F&& body) {
     if (TS >= 0) { body(wt_tag<(TS >= 0 ? TS : 0)>{}); return; }
     const int wt = wslice_type(w, rg);
+    if constexpr (TS == -2) {
+        if (wt == Q3_T_Q3_K) body(wt_tag<Q3_T_Q3_K>{});
+        else if (wt == Q3_T_Q5_K) body(wt_tag<Q3_T_Q5_K>{});
+        else body(wt_tag<Q3_T_Q4_K>{});
+        return;
+    }
     if (wt == Q3_T_Q5_K) body(wt_tag<Q3_T_Q5_K>{});
     else if (wt == Q3_T_Q4_K) body(wt_tag<Q3_T_Q4_K>{});
     else if (wt == Q3_T_Q6_K) body(wt_tag<Q3_T_Q6_K>{});
@@ -76,18 +97,23 @@ __device__ __forceinline__ void wslice_dispatch(const Q8Mat& w, int rg, F&& body
 }
 // host side: the TS of a matrix, and a switch that instantiates its statement once per value (the statement sees `constexpr int TS`)
 inline int wslice_ts(const Q8Mat& w) { return !w.rg_type ? 0 : w.nparts == 1 ? w.p0_type : -1; }
-#define Q3_TS_SWITCH(w, ...) do { switch (wslice_ts(w)) { \
+inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matrices split by whether a part is Q3_K
+    const int ts = wslice_ts(w);
+    return ts == -1 && (w.p0_type == Q3_T_Q3_K || w.p1_type == Q3_T_Q3_K || w.p2_type == Q3_T_Q3_K) ? -2 : ts;
+}
+#define Q3_TS_SWITCH(w, ...) do { switch (wslice_launch_ts(w)) { \
     case 0: { constexpr int TS = 0; __VA_ARGS__; break; } case Q3_T_Q8_0: { constexpr int TS = Q3_T_Q8_0; __VA_ARGS__; break; } \
-    case Q3_T_Q4_K: { constexpr int TS = Q3_T_Q4_K; __VA_ARGS__; break; } \
+    case Q3_T_Q3_K: { constexpr int TS = Q3_T_Q3_K; __VA_ARGS__; break; } case Q3_T_Q4_K: { constexpr int TS = Q3_T_Q4_K; __VA_ARGS__; break; } \
     case Q3_T_Q5_K: { constexpr int TS = Q3_T_Q5_K; __VA_ARGS__; break; } case Q3_T_Q6_K: { constexpr int TS = Q3_T_Q6_K; __VA_ARGS__; break; } \
-    default: { constexpr int TS = -1; __VA_ARGS__; break; } } } while (0)
+    case -2: { constexpr int TS = -2; __VA_ARGS__; break; } default: { constexpr int TS = -1; __VA_ARGS__; break; } } } while (0)
 
 // LPR lanes share a row: lane = (r, half, bil) with r = lane % R the row inside the workgroup's R = 64 / LPR rows, half = which 16 of a
 // block's 32 weights, bil = which of the BPL = LPR / 2 blocks of a load step.  A lane holds NLD = 8 / BPL loads of 16 weights.
 template <int LPR, int WT>
 struct WSlice {
     static constexpr int R = 64 / LPR, BPL = LPR / 2, NLD = 8 / BPL;
-    static constexpr bool Q4 = WT == Q3_T_Q4_K, KQ = Q4 || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
+    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, KQ = Q4 || Q3 || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
+    static constexpr int SUBOFF = Q3 ? 0 : 32; // Q6_K / Q3_K chain: what the unpacked operand is above q (Q3_K unpacks to q itself)
     uint4 wv[NLD];
     uint4 dwv;          // Q8_0: the 8 block scales; K-quants: d, dmin in halfs 0, 1
     uint4 mv;           // K-quants: 16 metadata bytes of (row, segment)
@@ -107,7 +133,7 @@ struct WSlice {
         const bool in1 = rgs >= w.p1_rg0, in2 = rgs >= w.p2_rg0;
         const uint32_t poff = in2 ? w.p2_off : in1 ? w.p1_off : w.p0_off;
         const int prg0 = in2 ? w.p2_rg0 : in1 ? w.p1_rg0 : 0;
-        constexpr int seg_bytes = Q4 ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
+        constexpr int seg_bytes = Q3 ? 3072 : Q4 ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
         const uint8_t* sbase = w.qs + (size_t)poff * 16 + ((size_t)(rgs - prg0) * nseg + seg) * seg_bytes;
         if (!KQ) {
             const uint8_t* base = sbase + half * 512 + r32 * 16;
@@ -126,6 +152,15 @@ struct WSlice {
             }
             return;
         }
+        if (Q3) { // [8 blocks][32 rows][8 B] of 2-bit values, a dword per half, then [32 rows][8 blocks][4 B] of third bits; x = 2-bit word, y = plane word
+#pragma unroll
+            for (int i = 0; i < NLD; i++) {
+                const int b = i * BPL + bil;
+                wv[i].x = *reinterpret_cast<const uint32_t*>(sbase + b * 256 + r32 * 8 + half * 4);
+                wv[i].y = *reinterpret_cast<const uint32_t*>(sbase + 2048 + r32 * 32 + b * 4);
+            }
+            return;
+        }
         const uint8_t* hrow = sbase + 4096 + r32 * (WT == Q3_T_Q6_K ? 64 : 32);
 #pragma unroll
         for (int i = 0; i < NLD; i++) {
@@ -136,13 +171,26 @@ struct WSlice {
         }
     }
 
-    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32); call once, after the prologue
+    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3); call once, after the prologue
     __device__ __forceinline__ void finish(int half) {
         if (!KQ) return;
         if (Q4) { // two masks and a shift per word
             const uint32_t m = 0x0F0F0F0Fu;
 #pragma unroll
             for (int i = 0; i < NLD; i++) wv[i] = make_uint4(wv[i].x & m, (wv[i].x >> 4) & m, wv[i].y & m, (wv[i].y >> 4) & m);
+            return;
+        }
+        if (Q3) { // four shifts of the 2-bit word give the dwords in k order; plane bit 8b + J belongs to byte b of dword J - 4 half.  The stored
+            // value is u = q + 4 = low2 | bit << 2, so q as int8 is low2 with bits 2..7 set where the plane bit is CLEAR: s * 0xFC per byte, s = the
+            // inverted bit, written (s << 8) - s (= s * 255: no byte carries into the next) under the mask
+            const uint32_t m = 0x03030303u, one = 0x01010101u, ext = 0xFCFCFCFCu;
+#pragma unroll
+            for (int i = 0; i < NLD; i++) {
+                const uint32_t q2 = wv[i].x, N = ~wv[i].y >> (4 * half);
+                const uint32_t s0 = N & one, s1 = (N >> 1) & one, s2 = (N >> 2) & one, s3 = (N >> 3) & one;
+                wv[i] = make_uint4((q2 & m) | (((s0 << 8) - s0) & ext), ((q2 >> 2) & m) | (((s1 << 8) - s1) & ext), ((q2 >> 4) & m) | (((s2 << 8) - s2) & ext),
+                                   ((q2 >> 6) & m) | (((s3 << 8) - s3) & ext));
+            }
             return;
         }
 #pragma unroll
@@ -194,17 +242,17 @@ struct WSlice {
             return acc;
         }
 #pragma unroll
-        for (int i = 0; i < NLD; i++) { // Q6_K
+        for (int i = 0; i < NLD; i++) { // Q6_K, and Q3_K without the offset term
             const uint4 xv = *reinterpret_cast<const uint4*>(xseg + (i * BPL + bil) * 32 + half * 16);
             const int bsel = i * BPL + bil; // block of THIS lane's data
-            // sum (q - 32) x = sum (stored) x - 32 sum x, exact in int32; the lane's 16 weights are one sub-block
-            int isum = __mul24(dot16(wv[i], xv) - 32 * dot16(ones, xv), (int)(int8_t)mbyte(2 * bsel + half));
+            // sum (q - 32) x = sum (stored) x - 32 sum x, exact in int32 (Q3_K: the operand is q, SUBOFF = 0 and the second dot is not compiled); the lane's 16 weights are one sub-block
+            int isum = __mul24(dot16(wv[i], xv) - SUBOFF * dot16(ones, xv), (int)(int8_t)mbyte(2 * bsel + half));
             isum += xor_lane<R>(isum);
-            const float a = d0 * (float)isum;
+            const float a = kq_block_scale<Q3>(d0, isum);
 #pragma unroll
             for (int j = 0; j < BPL; j++) {
                 const float aj = (BPL == 1) ? a : __shfl(a, r + 2 * j * R);
-                acc = q3_fmaf(aj, h2f(half_of(dxv, i * BPL + j)), acc);
+                acc = kq_block_fma<Q3>(aj, h2f(half_of(dxv, i * BPL + j)), acc);
             }
         }
         return acc;

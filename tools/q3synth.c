@@ -4,7 +4,7 @@
  * No real Qwen3-TTS weights exist offline (the reference downloads them at run time,
  * /root/reference/src/download.rs:66-87), so benchmarks and parity tests run on seeded random weights of
  * the same architecture, written in the same container format the reference loads:
- *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
+ *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_q3_k_m|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
  *   <out>/onnx/q3tts_codec.gguf        (stand-in for qwen3_tts_decoder.onnx)
  * (directory names: /root/reference/src/tts/engine.rs:91-95,123-124).
  *
@@ -93,14 +93,74 @@ static void enc_q45_k(const float* x, int64_t k, uint8_t* out, int levels, int b
             }
     }
 }
-static int g_q4k_as_q5k = 0; /* --q4k-as-q5k: Q5_K tensors carry 15-level values */
-static void enc_q5_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, g_q4k_as_q5k ? 15 : 31, 176); }
-static void enc_q4_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, 15, 144); }
+/* Twin files: a tensor is quantised as its own type and stored as the wider type that holds the same values (stored_type, enc_row) */
+static int g_q4k_as_q5k = 0; /* --q4k-as-q5k: Q4_K tensors are stored as Q5_K blocks with an all-zero qh */
+static int g_q3k_as_q6k = 0; /* --q3k-as-q6k: Q3_K tensors are stored as Q6_K blocks with the same d, scales - 32 and quants */
+static void enc_q5_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, 31, 176); }
+static void enc_q4_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, 15, g_q4k_as_q5k ? 176 : 144); }
+/* one Q6_K super-block from its fields: q[256] unsigned 6-bit values (q + 32) */
+static void pack_q6_k(uint8_t* blk, uint16_t dh, const int8_t* sc, const int* q) {
+    memset(blk, 0, 210);
+    memcpy(blk + 192, sc, 16); memcpy(blk + 208, &dh, 2);
+    uint8_t* ql = blk; uint8_t* qh = blk + 128;
+    for (int n = 0; n < 2; n++)
+        for (int l = 0; l < 32; l++) {
+            int q1 = q[128 * n + l], q2 = q[128 * n + l + 32], q3 = q[128 * n + l + 64], q4 = q[128 * n + l + 96];
+            ql[64 * n + l] = (uint8_t)((q1 & 0xF) | ((q3 & 0xF) << 4));
+            ql[64 * n + l + 32] = (uint8_t)((q2 & 0xF) | ((q4 & 0xF) << 4));
+            qh[32 * n + l] = (uint8_t)((q1 >> 4) | ((q2 >> 4) << 2) | ((q3 >> 4) << 4) | ((q4 >> 4) << 6));
+        }
+}
+/* Q3_K {u8 hmask[32], u8 qs[64], u8 scales[12], f16 d} (110 bytes, spec S3 [EXT]): per 16 weights the scale max|x| / 4 as a 6-bit multiple of
+ * d = largest scale / 31 (codes 32..63: this encoder writes no negative scale), q = round(x / (d * s)) in [-4, 3].  With --q3k-as-q6k the same
+ * d, s and q go into a Q6_K block instead: the twin the oracle reads. */
+static void enc_q3_k(const float* x, int64_t k, uint8_t* out) {
+    for (int64_t s = 0; s < k / 256; s++) {
+        const float* xs = x + 256 * s;
+        float scale[16], maxscale = 0;
+        for (int j = 0; j < 16; j++) {
+            float amax = 0;
+            for (int l = 0; l < 16; l++) { float a = fabsf(xs[16 * j + l]); if (a > amax) amax = a; }
+            scale[j] = amax / 4.0f;
+            if (scale[j] > maxscale) maxscale = scale[j];
+        }
+        uint16_t dh = q3_f32_to_f16(maxscale / 31.0f);
+        float d = q3_f16_to_f32(dh);
+        int8_t sc[16]; int q[256];
+        for (int j = 0; j < 16; j++) {
+            int si = d > 0 ? (int)lrintf(scale[j] / d) : 0; if (si > 31) si = 31;
+            sc[j] = (int8_t)si;
+            float de = d * (float)si;
+            for (int l = 0; l < 16; l++) {
+                int v = de > 0 ? (int)lrintf(xs[16 * j + l] / de) : 0;
+                q[16 * j + l] = v < -4 ? -4 : (v > 3 ? 3 : v);
+            }
+        }
+        if (g_q3k_as_q6k) {
+            for (int e = 0; e < 256; e++) q[e] += 32;
+            pack_q6_k(out + 210 * s, dh, sc, q);
+            continue;
+        }
+        uint8_t* blk = out + 110 * s;
+        memset(blk, 0, 110);
+        uint8_t* hmask = blk; uint8_t* qs = blk + 32; uint8_t* scales = blk + 96;
+        memcpy(blk + 108, &dh, 2);
+        for (int is = 0; is < 16; is++) {
+            int s6 = sc[is] + 32, j = is & 3, quad = is >> 2;
+            scales[4 * (quad & 1) + j] |= (uint8_t)((s6 & 15) << (4 * (quad >> 1)));
+            scales[8 + j] |= (uint8_t)((s6 >> 4) << (2 * quad));
+        }
+        for (int e = 0; e < 256; e++) {
+            int h = e >> 7, g = (e >> 5) & 3, l = e & 31, u = q[e] + 4;
+            qs[32 * h + l] |= (uint8_t)((u & 3) << (2 * g));
+            hmask[l] |= (uint8_t)((u >> 2) << (4 * h + g));
+        }
+    }
+}
 static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
     for (int64_t s = 0; s < k / 256; s++) {
         const float* xs = x + 256 * s;
         uint8_t* blk = out + 210 * s;
-        memset(blk, 0, 210);
         float scale[16], maxabs = 0;
         for (int j = 0; j < 16; j++) {
             float amax = 0;
@@ -110,8 +170,7 @@ static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
         }
         uint16_t dh = q3_f32_to_f16(maxabs / 127.0f);
         float d = q3_f16_to_f32(dh);
-        int8_t* sc = (int8_t*)(blk + 192);
-        memcpy(blk + 208, &dh, 2);
+        int8_t sc[16];
         int q[256];
         for (int j = 0; j < 16; j++) {
             int si = d > 0 ? (int)lrintf(scale[j] / d) : 0; if (si > 127) si = 127;
@@ -123,21 +182,16 @@ static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
                 q[16 * j + l] = v + 32;
             }
         }
-        uint8_t* ql = blk; uint8_t* qh = blk + 128;
-        for (int n = 0; n < 2; n++)
-            for (int l = 0; l < 32; l++) {
-                int q1 = q[128 * n + l], q2 = q[128 * n + l + 32], q3 = q[128 * n + l + 64], q4 = q[128 * n + l + 96];
-                ql[64 * n + l] = (uint8_t)((q1 & 0xF) | ((q3 & 0xF) << 4));
-                ql[64 * n + l + 32] = (uint8_t)((q2 & 0xF) | ((q4 & 0xF) << 4));
-                qh[32 * n + l] = (uint8_t)((q1 >> 4) | ((q2 >> 4) << 2) | ((q3 >> 4) << 4) | ((q4 >> 4) << 6));
-            }
+        pack_q6_k(blk, dh, sc, q);
     }
 }
+static int stored_type(int type) { return type == Q3_T_Q3_K && g_q3k_as_q6k ? Q3_T_Q6_K : type == Q3_T_Q4_K && g_q4k_as_q5k ? Q3_T_Q5_K : type; }
 static size_t row_bytes(int type, int64_t k) {
     switch (type) {
         case Q3_T_F32: return (size_t)k * 4;
         case Q3_T_F16: case Q3_T_BF16: return (size_t)k * 2;
         case Q3_T_Q8_0: return (size_t)(k / 32) * 34;
+        case Q3_T_Q3_K: return (size_t)(k / 256) * 110;
         case Q3_T_Q4_K: return (size_t)(k / 256) * 144;
         case Q3_T_Q5_K: return (size_t)(k / 256) * 176;
         case Q3_T_Q6_K: return (size_t)(k / 256) * 210;
@@ -150,6 +204,7 @@ static void enc_row(int type, const float* x, int64_t k, uint8_t* out) {
         case Q3_T_F16: for (int64_t i = 0; i < k; i++) { uint16_t h = q3_f32_to_f16(x[i]); memcpy(out + 2 * i, &h, 2); } break;
         case Q3_T_BF16: for (int64_t i = 0; i < k; i++) { uint16_t h = q3_f32_to_bf16(x[i]); memcpy(out + 2 * i, &h, 2); } break;
         case Q3_T_Q8_0: enc_q8_0(x, k, out); break;
+        case Q3_T_Q3_K: enc_q3_k(x, k, out); break;
         case Q3_T_Q4_K: enc_q4_k(x, k, out); break;
         case Q3_T_Q5_K: enc_q5_k(x, k, out); break;
         case Q3_T_Q6_K: enc_q6_k(x, k, out); break;
@@ -157,7 +212,7 @@ static void enc_row(int type, const float* x, int64_t k, uint8_t* out) {
 }
 
 /* ---------- GGUF writer ---------- */
-typedef struct { char name[128]; int n_dims; int64_t ne[4]; int type; float std, mean; uint64_t seed; uint64_t offset; size_t nbytes; } tdesc;
+typedef struct { char name[128]; int n_dims; int64_t ne[4]; int type, enc; float std, mean; uint64_t seed; uint64_t offset; size_t nbytes; } tdesc;
 typedef struct { char key[128]; int type; uint64_t u; double f; char str[64]; int32_t arr[8]; int arr_n; } kvdesc;
 typedef struct { tdesc* t; int nt, ct; kvdesc* kv; int nkv, ckv; uint64_t seed_base; } gw;
 
@@ -181,7 +236,7 @@ static void gw_tensor(gw* g, const char* name, int type, int64_t ne0, int64_t ne
     snprintf(t->name, sizeof(t->name), "%s", name);
     t->n_dims = ne2 > 1 ? 3 : (ne1 > 1 ? 2 : 1);
     t->ne[0] = ne0; t->ne[1] = ne1; t->ne[2] = ne2; t->ne[3] = 1;
-    t->type = type; t->std = std; t->mean = mean;
+    t->enc = type; t->type = type = stored_type(type); t->std = std; t->mean = mean; /* enc: the type that quantises; type: the blocks in the file */
     t->seed = g->seed_base + (uint64_t)g->nt; /* seed = base + tensor index */
     t->nbytes = row_bytes(type, ne0) * (size_t)(ne1 * ne2);
     g->nt++;
@@ -241,7 +296,7 @@ static int gw_write(gw* g, const char* path) {
                 for (int64_t r = 0; r < rn; r++) {
                     uint64_t base = (uint64_t)(r0 + r) * (uint64_t)k;
                     for (int64_t i = 0; i < k; i++) x[i] = t->mean + t->std * gauss(t->seed, base + (uint64_t)i);
-                    enc_row(t->type, x, k, buf + rb * (size_t)r);
+                    enc_row(t->enc, x, k, buf + rb * (size_t)r);
                 }
                 free(x);
             }
@@ -270,7 +325,14 @@ static int wtype(const char* quant, const char* kind, int layer, int n_layer) {
     if (!strcmp(quant, "q5_k_m") || !strcmp(quant, "q4_k_m")) { /* llama.cpp's Q4_K_M is the same mix with Q4_K where Q5_K stands [EXT] */
         if (!strcmp(kind, "output")) return Q3_T_Q6_K;
         if ((!strcmp(kind, "attn_v") || !strcmp(kind, "ffn_down")) && use_more_bits(layer, n_layer)) return Q3_T_Q6_K;
-        return (quant[1] == '4' && !g_q4k_as_q5k) ? Q3_T_Q4_K : Q3_T_Q5_K;
+        return quant[1] == '4' ? Q3_T_Q4_K : Q3_T_Q5_K;
+    }
+    if (!strcmp(quant, "q3_k_m")) { /* llama.cpp's Q3_K_M mix as remembered [EXT, unpinned] (spec S3) */
+        if (!strcmp(kind, "output")) return Q3_T_Q6_K;
+        if (!strcmp(kind, "attn_v")) return layer < 2 ? Q3_T_Q5_K : Q3_T_Q4_K;
+        if (!strcmp(kind, "attn_output")) return Q3_T_Q4_K;
+        if (!strcmp(kind, "ffn_down")) return layer < n_layer / 16 ? Q3_T_Q5_K : Q3_T_Q4_K;
+        return Q3_T_Q3_K;
     }
     fprintf(stderr, "unknown quant %s\n", quant);
     exit(2);
@@ -421,10 +483,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--text-rows") && i + 1 < argc) text_rows = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--what") && i + 1 < argc) what = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--q4k-as-q5k")) g_q4k_as_q5k = 1;
-        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|bf16|f16|f32] [--q4k-as-q5k] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
+        else if (!strcmp(argv[i], "--q3k-as-q6k")) g_q3k_as_q6k = 1;
+        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|q3_k_m|bf16|f16|f32] [--q4k-as-q5k] [--q3k-as-q6k] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
     }
     if (!out) { fprintf(stderr, "--out required\n"); return 2; }
-    if (g_q4k_as_q5k && strcmp(quant, "q4_k_m")) { fprintf(stderr, "--q4k-as-q5k goes with --quant q4_k_m\n"); return 2; }
+    if (g_q4k_as_q5k && strcmp(quant, "q4_k_m") && strcmp(quant, "q3_k_m")) { fprintf(stderr, "--q4k-as-q5k goes with --quant q4_k_m or q3_k_m\n"); return 2; }
+    if (g_q3k_as_q6k && strcmp(quant, "q3_k_m")) { fprintf(stderr, "--q3k-as-q6k goes with --quant q3_k_m\n"); return 2; }
 #ifdef _OPENMP
     if (!getenv("OMP_NUM_THREADS")) { int n = omp_get_num_procs(); omp_set_num_threads(n > 8 ? 8 : n); } /* cgroup CPU shares are smaller than the core count */
 #endif
@@ -438,7 +502,7 @@ int main(int argc, char** argv) {
         pred = (tfcfg){ 256, 2, 2, 1, 512, 30720, 0 };
         codec = (ccfg){ 64, 32, 2, 2, 32, 128, 8, 256, 2, 4, { 2, 2 }, { 8, 5, 4, 3 } };
     } else { fprintf(stderr, "unknown preset\n"); return 2; }
-    const char* qdir = !strcmp(quant, "q8_0") ? "gguf_q8_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") ? "gguf_q4_k_m" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
+    const char* qdir = !strcmp(quant, "q8_0") ? "gguf_q8_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") || g_q3k_as_q6k ? "gguf_q4_k_m" : !strcmp(quant, "q3_k_m") ? "gguf_q3_k_m" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
     char p[1024];
     mkdir(out, 0755);
     snprintf(p, sizeof(p), "%s/%s", out, qdir); mkdir(p, 0755);
