@@ -868,6 +868,40 @@ int q3tts_op_attention_keyed(q3tts_attention_desc* d, const uint64_t* keys, int3
 /* host only (no device needed): the form AUTO picks for d's ntok / n_head / n_kv / flags -> form_ran; no buffer is read */
 int q3tts_attention_plan(q3tts_attention_desc* d);
 
+/* [EXT] KV cache type Q8_0 (q3tts_spec.h "KV cache type Q8_0"): the talker's K and V rows as int8 blocks of 32 with f16 scales, 53 % of the
+ * F16 cache's bytes per token.  The type ids are ggml's (what llama.cpp's type_k / type_v hold). */
+enum { Q3TTS_KV_F16 = 1, Q3TTS_KV_Q8_0 = 8 };
+enum { Q3TTS_ATTN_Q8KV = 6 /* k_qk_rope_append_q8 + k_attention_q8kv */ };
+/* host only (no device needed): bytes one cached token takes in both planes, every layer and kv head, and bytes of one plane page (K or V
+ * of 64 positions, padded to a multiple of 16 KiB, the tile the page-copy kernels move).  An unknown type is refused. */
+int q3tts_kv_layout(int32_t n_layer, int32_t n_kv, int32_t kv_type, int64_t* bytes_per_token, int64_t* plane_page_bytes);
+/* q3tts_engine_create / q3tts_tf_open with the talker's (the context's) KV cache type given.  Q3TTS_KV_F16 is exactly the plain call; with
+ * Q3TTS_KV_Q8_0 every step, decode and prefill, runs k_qk_rope_append_q8 + k_attention_q8kv, and candidate sets, prompt stems, resume and
+ * scoring work on the int8 pages (stem stores are sized in the pool's page layout).  The code predictor keeps its f16 cache.  A
+ * Q3_SPEC=ggml model refuses Q3TTS_KV_Q8_0 by name; an unknown type is refused.  The llama.cpp-ABI shim maps type_k == type_v == 8 here. */
+int q3tts_engine_create_kv(const q3tts_engine_params* params, int32_t kv_type, q3tts_engine** out);
+int q3tts_tf_open_kv(const char* gguf_path, int32_t n_ctx, int32_t max_tok, int32_t kv_type, q3tts_tf** out);
+/* One attention step over a Q8_0 cache for one layer (S4', S5, the Q8_0 append, quantised-query attention, S2 of the output), on host
+ * buffers.  qkv, norms, RoPE, tokens (seq / slot / pos, all required) and paging as q3tts_attention_desc.  The four cache arrays,
+ * uploaded and written back whole:
+ *   kq [n_pages][n_layer][n_kv][4 blocks][64 pos][32] int8     ks [n_pages][n_layer][n_kv][4][64] f16
+ *   vq [n_pages][n_layer][n_kv][64 pos][128] int8              vs [n_pages][n_layer][n_kv][64][4] f16
+ * Outputs: att [ntok][n_head*128] f32 and qrot (the rotated f32 query rows, same shape), either may be NULL; aq / ad as q3tts_op_attention.
+ * Refused before anything is uploaded or launched: n_head / n_kv not in {1, 2, 4, 8}, a slot beyond the paging or n_ctx, a page id
+ * outside the arrays, two tokens writing one (sequence, slot). */
+typedef struct q3tts_attention_q8kv_desc {
+    int32_t n_head, n_kv, n_layer, layer, ntok;
+    const float* qkv; int32_t qkv_stride;
+    const float* q_norm; const float* k_norm;                          /* [128] each */
+    float eps, rope_base; int32_t n_ctx; int32_t mrope_sec[4];
+    const int32_t* seq; const int32_t* slot; const int32_t* pos;
+    const int32_t* page_table; int32_t n_seq, max_pages;
+    int8_t* kq; uint16_t* ks; int8_t* vq; uint16_t* vs; int32_t n_pages;
+    float* att; float* qrot; int8_t* aq; uint16_t* ad;
+    int32_t form_ran;                                                  /* Q3TTS_ATTN_Q8KV */
+} q3tts_attention_q8kv_desc;
+int q3tts_op_attention_q8kv(q3tts_attention_q8kv_desc* d);
+
 /* One talker / predictor linear-layer operation (csrc/kernels.hip, kernels_fused.hip) with a form forced, or as the engine dispatches it (AUTO).
  * Ops: GEMV int8 x -> f32 super-segment slabs out[out_off + (s*ntok + t)*out_stride + r], s < ceil(K/2048), NOT summed;
  *      GATEUP int8 x -> SwiGLU -> aq [ntok][ff] / ad [ntok][ff/32] (weights: gate rows [0, ff) then up rows);

@@ -680,6 +680,26 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
  * The Q3_K_M mix q3synth writes (attn_q, attn_k, ffn_gate, ffn_up Q3_K; attn_v Q5_K in layers 0 and 1, else Q4_K; attn_output Q4_K; ffn_down
  * Q5_K below n_layer / 16, else Q4_K; output / head tensors Q6_K) is llama.cpp's as remembered [EXT, unpinned]. */
 
+/* ---------------- KV cache type Q8_0 [EXT] (q3tts_kv_layout, q3tts_op_attention_q8kv) ----------------
+ * The talker's K and V rows kept as int8 blocks of 32 with f16 scales (ggml's -ctk q8_0 -ctv q8_0) instead of f16.  Not a bit-exact item
+ * against the oracle: it is pinned to float64 (tests/test_gpu_kv_q8.py).  F16 stays the default and every S6 / S7 kernel is unchanged.
+ *   append (S6')  the K row is the f32 result of S4' and S5, the V row the raw f32 v, 128 values each.  Each row is four blocks of 32,
+ *                 each quantised by q3_quant_block32 (S2): d = amax / 127, id = 1 / d or 0, q = rint(x * id), the scale stored as f16
+ *   query         the rotated f32 query row is quantised the same way: scales e_b, quants r_b, b = 0..3
+ *   score         I_b = sum_i r_b[i] * k_jb[i] in int32, exact (at most 32 * 127^2 < 2^24, so (float)I_b is exact too).  acc = +0; for b
+ *                 ascending acc = fmaf((float)I_b, f32(e_b) * f32(dk_jb), acc); s_j = acc * scale.  (ggml's vec_dot_q8_0_q8_0 shape)
+ *   softmax       S7 unchanged: chunks of 256 positions, the chunk maximum, p_j = q3_expf(s_j - m), the M / L merges
+ *   PV            S7's 16 chains and combine tree unchanged; the term fmaf(p_j, v_jd, S) becomes w = p_j * f32(dv_jb), S = fmaf(w, (float)qv_jd, S),
+ *                 b the block of dimension d
+ *   output        the f32 row and its S2 quantisation unchanged
+ * Tolerance against float64 (tests/test_gpu_kv_q8.py): |y - y64| <= tol * sum_j p_j |v_j| per element, except where the quantised V is exactly
+ * 0 at every position whose p_j q3_expf does not flush to 0 (below -87): there the device's element is 0, float64's is the sum of the flushed
+ * terms, and the bound is e^-86 * sum_j |v_jd| instead.
+ * A token's result depends on its q row, its context length and the cache bytes only: not on the launch geometry, the batch width or
+ * how a prefill was cut into chunks.
+ * Bytes: a (64-position page, layer, kv head) unit is 8192 + 512 bytes per plane against 16384; a plane page (every layer and kv head) is
+ * padded to a multiple of 16 KiB.  28 layers x 8 kv heads: 60 928 bytes per token against 114 688. */
+
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
     Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q3_K = 11, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30

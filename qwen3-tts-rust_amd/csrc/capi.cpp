@@ -34,14 +34,16 @@ void q3tts_engine_params_default(q3tts_engine_params* p) {
     p->max_steps = Q3_DEFAULT_MAX_STEPS; p->load_codec = 1; p->use_graph = 1;
 }
 
-int q3tts_engine_create(const q3tts_engine_params* p, q3tts_engine** out) {
+int q3tts_engine_create(const q3tts_engine_params* p, q3tts_engine** out) { return q3tts_engine_create_kv(p, Q3TTS_KV_F16, out); }
+int q3tts_engine_create_kv(const q3tts_engine_params* p, int32_t kv_type, q3tts_engine** out) {
     Q3_API_BEGIN
     Q3_CHECK(p && out && p->model_dir, "null argument");
+    Q3_CHECK(kv_type == Q3TTS_KV_F16 || kv_type == Q3TTS_KV_Q8_0, "unknown KV cache type (1 = F16, 8 = Q8_0)");
     require_gpu();
     Q3_HIP(hipSetDevice(p->device));
     EngineParams ep;
     ep.model_dir = p->model_dir; ep.quant = p->quant ? p->quant : "q8_0"; ep.max_batch = p->max_batch; ep.max_prompt = p->max_prompt;
-    ep.max_steps = p->max_steps; ep.load_codec = p->load_codec != 0; ep.use_graph = p->use_graph != 0;
+    ep.max_steps = p->max_steps; ep.load_codec = p->load_codec != 0; ep.use_graph = p->use_graph != 0; ep.kv_type = kv_type;
     auto* h = new q3tts_engine();
     try { h->e.reset(new Engine(ep)); } catch (...) { delete h; throw; }
     h->assets_view.a = &h->e->assets();
@@ -568,7 +570,9 @@ int q3tts_engine_stats(q3tts_engine* e, q3tts_stats* o) {
     o->sched_steps = s.steps; o->slot_frames = s.slot_frames; o->graph_frames = s.graph_frames;
     o->talker_weight_bytes = (double)e->e->talker().weight_bytes(); o->predictor_weight_bytes = (double)e->e->predictor().weight_bytes();
     const auto& hp = e->e->talker().hp();
-    o->kv_bytes_per_token = (double)hp.n_layer * 2 * hp.n_kv * 128 * 2;
+    size_t kv_bpt = 0;
+    kv_layout(hp.n_layer, hp.n_kv, e->e->kv_type(), &kv_bpt, nullptr);   // F16: n_layer * 2 * n_kv * 128 * 2, as before
+    o->kv_bytes_per_token = (double)kv_bpt;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }
@@ -789,12 +793,14 @@ int32_t q3tts_decoder_state_entry(q3tts_decoder* d, int32_t i, const char** name
 }
 
 // ---------------- transformer contexts ----------------
-int q3tts_tf_open(const char* path, int32_t n_ctx, int32_t max_tok, q3tts_tf** out) {
+int q3tts_tf_open(const char* path, int32_t n_ctx, int32_t max_tok, q3tts_tf** out) { return q3tts_tf_open_kv(path, n_ctx, max_tok, Q3TTS_KV_F16, out); }
+int q3tts_tf_open_kv(const char* path, int32_t n_ctx, int32_t max_tok, int32_t kv_type, q3tts_tf** out) {
     Q3_API_BEGIN
+    Q3_CHECK(kv_type == Q3TTS_KV_F16 || kv_type == Q3TTS_KV_Q8_0, "unknown KV cache type (1 = F16, 8 = Q8_0)");
     require_gpu();
     auto model = std::make_shared<Transformer>(path, n_ctx, max_tok);
     auto* h = new q3tts_tf();
-    h->c.reset(new TfContext(model, n_ctx));
+    h->c.reset(new TfContext(model, n_ctx, kv_type));
     *out = h;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)

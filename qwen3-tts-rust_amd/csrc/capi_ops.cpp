@@ -131,6 +131,66 @@ static void attention_op_run(q3tts_attention_desc* dp, const uint64_t* keys = nu
     d.form_ran = form;
 }
 
+// ---- q3tts_op_attention_q8kv: the same step over a Q8_0 cache (kvq8.hip); four tight cache arrays ----
+static void attention_q8kv_check(const q3tts_attention_q8kv_desc& d) {
+    Q3_CHECK(d.ntok >= 1 && d.ntok <= 65535 && d.n_head >= 1 && d.n_kv >= 1 && d.n_kv <= 65535 && d.n_head % d.n_kv == 0, "bad attention shape");
+    const int grp = d.n_head / d.n_kv;
+    Q3_CHECK(grp == 1 || grp == 2 || grp == 4 || grp == 8, "the Q8_0 KV attention serves 1, 2, 4 or 8 query heads per kv head");
+    Q3_CHECK(d.n_layer >= 1 && d.layer >= 0 && d.layer < d.n_layer, "bad layer");
+    Q3_CHECK(d.qkv && d.q_norm && d.k_norm && d.qkv_stride >= (d.n_head + 2 * d.n_kv) * 128, "bad qkv / norm buffers");
+    Q3_CHECK(d.kq && d.ks && d.vq && d.vs && d.n_pages >= 1 && d.n_ctx >= 1, "bad cache arrays / n_ctx");
+    Q3_CHECK((uint64_t)d.n_pages * d.n_layer * d.n_kv * 8192 < (1ull << 32), "cache arrays too large for the op");
+    Q3_CHECK(d.aq && d.ad && d.seq && d.slot && d.pos, "aq / ad and per-token seq / slot / pos are required");
+    if (d.page_table) {
+        Q3_CHECK(d.n_seq >= 1 && d.max_pages >= 1, "bad page table shape");
+        for (int64_t i = 0; i < (int64_t)d.n_seq * d.max_pages; i++)
+            Q3_CHECK(d.page_table[i] >= 0 && d.page_table[i] < d.n_pages, "page table entry out of range");
+    }
+    std::map<std::pair<int, int>, int> seen;
+    for (int t = 0; t < d.ntok; t++) {
+        const int seq = d.seq[t], slot = d.slot[t];
+        Q3_CHECK(slot >= 0 && slot < d.n_ctx, "slot out of [0, n_ctx)");
+        if (d.page_table) Q3_CHECK(seq >= 0 && seq < d.n_seq && slot < d.max_pages * 64, "sequence or slot beyond the page table");
+        else Q3_CHECK(seq >= 0 && seq < d.n_pages && slot < 64, "identity paging: sequence beyond the cache or slot beyond its one page");
+        Q3_CHECK(seen[std::make_pair(seq, slot)]++ == 0, "two tokens write the same (sequence, slot)");
+    }
+}
+static void attention_q8kv_run(q3tts_attention_q8kv_desc* dp) {
+    Q3_CHECK(dp, "null attention descriptor");
+    q3tts_attention_q8kv_desc& d = *dp;
+    attention_q8kv_check(d);
+    require_gpu();
+    const int nt = d.ntok, dq = d.n_head * 128, qs = d.qkv_stride;
+    DevBuf<float> qkv((size_t)nt * qs); qkv.upload(d.qkv, qkv.n);
+    DevBuf<float> qn(128), kn(128); qn.upload(d.q_norm, 128); kn.upload(d.k_norm, 128);
+    std::vector<float> hc, hs;
+    build_rope_tables(d.rope_base, d.n_ctx, hc, hs);
+    DevBuf<float> rc(hc.size()), rs(hs.size()); rc.upload(hc.data(), hc.size()); rs.upload(hs.data(), hs.size());
+    DevBuf<int32_t> sec(4), dseq(nt), dslot(nt), dpos((size_t)nt * 4), dtab;
+    sec.upload(d.mrope_sec, 4); dseq.upload(d.seq, nt); dslot.upload(d.slot, nt); dpos.upload(d.pos, (size_t)nt * 4);
+    const TokMeta tm{dseq.p, dslot.p, dpos.p};
+    const size_t units = (size_t)d.n_pages * d.n_layer * d.n_kv;
+    DevBuf<int8_t> kq(units * 8192), vq(units * 8192); DevBuf<uint16_t> ks(units * 256), vs(units * 256);
+    kq.upload(d.kq, kq.n); vq.upload(d.vq, vq.n); ks.upload(d.ks, ks.n); vs.upload(d.vs, vs.n);
+    KvCacheQ8 kv;
+    kv.kq = kq.p; kv.ks = ks.p; kv.vq = vq.p; kv.vs = vs.p; kv.page_table = nullptr; kv.max_pages = d.page_table ? d.max_pages : 1;
+    kv.n_layer = d.n_layer; kv.n_kv = d.n_kv; kv.head_q = 8192; kv.head_s = 256;
+    kv.page_q = (uint32_t)((size_t)d.n_layer * d.n_kv * 8192); kv.page_s = (uint32_t)((size_t)d.n_layer * d.n_kv * 256);
+    if (d.page_table) { dtab.alloc((size_t)d.n_seq * d.max_pages); dtab.upload(d.page_table, dtab.n); kv.page_table = dtab.p; }
+    DevBuf<float> att((size_t)nt * dq), qrot((size_t)nt * dq);
+    DevBuf<int8_t> aq((size_t)nt * dq); DevBuf<uint16_t> ad((size_t)nt * (dq / 32));
+    const QkvRows rows(qkv.p, qs);
+    launch_qk_rope_append_q8(0, rows, d.n_head, d.n_kv, qn.p, kn.p, d.eps, rc.p, rs.p, d.n_ctx, sec.p, tm, kv, d.layer, qrot.p, nt);
+    launch_attention_q8kv(0, qrot.p, d.n_head, d.n_kv, tm, kv, d.layer, att.p, aq.p, ad.p, nt);
+    Q3_LAUNCH_CHECK();
+    Q3_HIP(hipDeviceSynchronize());
+    kq.download(d.kq, kq.n); vq.download(d.vq, vq.n); ks.download(d.ks, ks.n); vs.download(d.vs, vs.n);
+    if (d.att) att.download(d.att, att.n);
+    if (d.qrot) qrot.download(d.qrot, qrot.n);
+    aq.download(d.aq, aq.n); ad.download(d.ad, ad.n);
+    d.form_ran = ATTN_Q8KV;
+}
+
 // ---- q3tts_op_linear: one linear-layer operation through the same run_* launches as the engine ----
 static bool lin_quant(const q3tts_linear_desc& d) { return d.op <= LOP_NORM_GATEUP && d.op != LOP_NORM; }
 static bool lin_kq(const q3tts_linear_desc& d) {
@@ -515,6 +575,23 @@ int q3tts_op_attention_keyed(q3tts_attention_desc* d, const uint64_t* keys, int3
     require_gpu();
     Q3_CHECK(keys, "null keys");
     attention_op_run(d, keys, key_stride, qkv_rows);
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_op_attention_q8kv(q3tts_attention_q8kv_desc* d) {
+    Q3_API_BEGIN
+    attention_q8kv_run(d);   // (the descriptor is checked first, the device second: a refusal reads the same with and without one)
+    return Q3TTS_OK;
+    Q3_API_END(Q3TTS_ERR)
+}
+
+int q3tts_kv_layout(int32_t n_layer, int32_t n_kv, int32_t kv_type, int64_t* bytes_per_token, int64_t* plane_page_bytes) {
+    Q3_API_BEGIN
+    size_t bpt = 0, page = 0;
+    kv_layout(n_layer, n_kv, kv_type, &bpt, &page);
+    if (bytes_per_token) *bytes_per_token = (int64_t)bpt;
+    if (plane_page_bytes) *plane_page_bytes = (int64_t)page;
     return Q3TTS_OK;
     Q3_API_END(Q3TTS_ERR)
 }

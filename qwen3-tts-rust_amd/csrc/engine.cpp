@@ -92,7 +92,8 @@ Engine::Engine(const EngineParams& p) : p_(p) {
     kv_rows_ = (int64_t)pages_per_seq * 64;
     // talker page-table row B is the scratch sequence: idle slots of the frame graph read and write its single page, so the pages of a
     // slot that is being prefilled (or was just recycled) are never touched by the graph
-    kv_t_.reset(new KvPool(talker_->hp().n_layer, talker_->hp().n_kv, B * pages_per_seq + 1, B + 1, pages_per_seq));
+    kv_t_.reset(new KvPool(talker_->hp().n_layer, talker_->hp().n_kv, B * pages_per_seq + 1, B + 1, pages_per_seq, p.kv_type));
+    if (p.kv_type == KV_Q8_0) { const KvCacheQ8 c = kv_t_->view_q8(); talker_->set_kv_q8(&c); } // talker_pf_ (below) copies the setting
     kv_p_.reset(new KvPool(predictor_->hp().n_layer, predictor_->hp().n_kv, B, B, 1));
     for (int b = 0; b < B; b++) kv_p_->ensure(b, 16);
     pred_identity_pages_ = true; // sequence b owns physical page b: the predictor's attention can skip the page-table lookup
@@ -264,7 +265,8 @@ size_t Engine::bytes_per_frame_step(int batch, double mean_ctx) const {
     const auto& t = talker_->hp();
     const size_t head_t = (size_t)tl_stride_ * talker_->head_bytes_per_row();
     const size_t head_p = (size_t)15 * Q3_CODEBOOK_SIZE * predictor_->head_bytes_per_row();
-    const size_t kv_per_tok = (size_t)t.n_layer * 2 * t.n_kv * 128 * 2;
+    size_t kv_per_tok = 0;
+    kv_layout(t.n_layer, t.n_kv, p_.kv_type, &kv_per_tok, nullptr);
     // the predictor's weights count once per frame (they stay in cache across its 15 passes, and pass A still reads layer 0's q/k/v rows), so
     // the layer-0 table takes nothing off them; it adds one f32 q/k/v row per slot in each of passes 1..14
     const size_t tab_rows = pred_l0_table_ ? (size_t)batch * 14 * (size_t)(predictor_->hp().n_head + 2 * predictor_->hp().n_kv) * 128 * 4 : 0;
@@ -573,7 +575,8 @@ void Engine::alloc_stem_stores(const std::vector<Req*>& wave) {
     std::lock_guard<std::mutex> cap(capture_mutex());
     for (Req* r : wave) {
         if (r->build_stem < 0) continue;
-        const int64_t bytes = stem_store_bytes(r->r.n_prompt, talker_->hp().n_layer, talker_->hp().n_kv);
+        // K plane pages then V plane pages in the pool's page layout (F16: stem_store_bytes; Q8_0: the padded int8 plane page)
+        const int64_t bytes = (int64_t)2 * stem_pages(r->r.n_prompt) * (int64_t)kv_t_->view().page_stride() * 2;
         Q3_HIP(hipMalloc((void**)&r->build_store, (size_t)bytes));
         stem_bytes_ += bytes;
         std::lock_guard<std::mutex> lk(mu_);

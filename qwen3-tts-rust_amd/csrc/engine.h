@@ -31,6 +31,7 @@ struct EngineParams {
     int max_steps = Q3_DEFAULT_MAX_STEPS;
     bool load_codec = true;
     bool use_graph = true;
+    int kv_type = KV_F16;       // [EXT] the talker's KV cache type (KV_Q8_0: int8 pages); the code predictor's 17 positions stay f16
 };
 
 struct GenResult {
@@ -190,6 +191,7 @@ public:
     const EngineStats& read_stats() { if (worker_) stats.codec_calls += worker_->take_codec_calls(); return stats; } // the decoder thread counts its own
     void set_instrument(bool on) { instrument_ = on; }
     size_t bytes_per_frame_step(int batch, double mean_ctx) const; // algorithmic HBM bytes of one batched frame step
+    int kv_type() const { return p_.kv_type; }                     // [EXT] the talker's KV cache type (KV_F16 / KV_Q8_0)
     size_t pred_table_bytes() const { return pred_table_bytes_; }  // the predictor's layer-0 q/k/v table (0 = off: Q3_PRED_L0_TABLE=0 or Q3_SPEC=ggml)
     hipStream_t stream() const { return st_; }
     int max_batch() const { return B_; }

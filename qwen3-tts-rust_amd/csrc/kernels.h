@@ -69,6 +69,25 @@ struct KvCache {           // paged f16 KV cache (pages of 64 positions)
     __device__ __forceinline__ int page_of(int seq, int logical) const { return page_table ? page_table[(size_t)seq * max_pages + logical] : seq; }
 };
 
+// [EXT] KV cache type Q8_0 (kvq8.hip, q3tts_spec.h "KV cache type Q8_0"): paged int8 KV cache, pages of 64 positions.  A struct of its own:
+// KvCache is a by-value argument of every f16 attention kernel and stays as it is.  Unit of one (page, layer, kv head):
+//   kq [4 blocks][64 pos][32] int8, ks [4][64] f16, vq [64 pos][128] int8, vs [64][4] f16
+// The unit of (page, layer, kvh) starts page * page_q + (layer * n_kv + kvh) * head_q bytes into kq / vq and page * page_s + (..) * head_s
+// halfs into ks / vs, so one struct describes four tight arrays (head_q = 8192, head_s = 256) and two padded planes whose units hold
+// the quants and then the scales (head_q = KVQ8_UNIT, head_s = KVQ8_UNIT / 2, ks = kq + 8192 bytes).
+enum KvType { KV_F16 = 1, KV_Q8_0 = 8 };   // ggml's type ids (q3tts.h Q3TTS_KV_*)
+constexpr int KVQ8_UNIT = 8192 + 512;      // bytes of one plane's unit: 64 positions x (128 quants + 4 f16 scales)
+struct KvCacheQ8 {
+    int8_t* kq; uint16_t* ks; int8_t* vq; uint16_t* vs;
+    const int32_t* page_table; // [n_seq][max_pages]; null = identity
+    int max_pages;
+    int n_layer, n_kv;
+    uint32_t page_q, page_s, head_q, head_s;
+    __host__ __device__ size_t q_off(int page, int layer, int kvh) const { return (size_t)page * page_q + ((size_t)layer * n_kv + kvh) * head_q; }
+    __host__ __device__ size_t s_off(int page, int layer, int kvh) const { return (size_t)page * page_s + ((size_t)layer * n_kv + kvh) * head_s; }
+    __device__ __forceinline__ int page_of(int seq, int logical) const { return page_table ? page_table[(size_t)seq * max_pages + logical] : seq; }
+};
+
 // out[(sseg*ntok + tok)*out_stride + r] = super-segment partial of row (row0+r) . x[tok]      (spec S3)
 // batched steps: gate/up GEMM on the matrix cores with the SwiGLU + quantisation epilogue; false = shape not supported (caller falls back)
 bool launch_gateup_mfma(hipStream_t st, const Q8Mat& wgu, int ff, const int8_t* xq, const uint16_t* xd, int8_t* aq, uint16_t* ad, int ntok);
@@ -111,6 +130,17 @@ void launch_qk_rope_append(hipStream_t st, const QkvRows& qkv, const float* part
 // causal GQA attention over the paged cache (spec S7) + int8 quantisation of the output
 void launch_attention(hipStream_t st, const float* qrot, int n_head, int n_kv, const TokMeta& tm, const KvCache& kv,
                       int layer, float* att /*optional [ntok][n_head*128]*/, int8_t* aq, uint16_t* ad, int ntok);
+
+// [EXT] KV cache type Q8_0 (kvq8.hip)
+// per-head q/k RMSNorm + M-RoPE as launch_qk_rope_append; q -> qrot f32; the K and V rows -> int8 blocks of 32 with f16 scales (spec S2)
+void launch_qk_rope_append_q8(hipStream_t st, const QkvRows& qkv, int n_head, int n_kv, const float* q_norm_w, const float* k_norm_w, float eps,
+                              const float* rope_cos, const float* rope_sin, int n_ctx, const int32_t* mrope_sec /*device [4]*/, const TokMeta& tm,
+                              const KvCacheQ8& kv, int layer, float* qrot, int ntok);
+// causal GQA attention over the int8 pages + int8 quantisation of the output; n_head / n_kv in {1, 2, 4, 8}, anything else throws
+void launch_attention_q8kv(hipStream_t st, const float* qrot, int n_head, int n_kv, const TokMeta& tm, const KvCacheQ8& kv, int layer,
+                           float* att /*optional [ntok][n_head*128]*/, int8_t* aq, uint16_t* ad, int ntok);
+// host only: bytes of one plane page (K or V: 64 positions of every layer and kv head, padded to a multiple of 16 KiB) and of one token
+void kv_layout(int n_layer, int n_kv, int kv_type, size_t* bytes_per_token, size_t* plane_page_bytes);
 
 // a = silu(g)*u over gate/up slabs, quantise (spec S8,S2). gu layout: [ntok][2*ff] with gate first.
 void launch_swiglu_quant(hipStream_t st, const float* gu, int ff, int8_t* aq, uint16_t* ad, int ntok);

@@ -72,7 +72,8 @@ struct llama_context* llama_init_from_model(struct llama_model* m, llama_context
     if (n_ctx > m->tf->n_ctx()) throw Error("n_ctx exceeds the model's RoPE table");
     auto* c = new llama_context();
     c->model = m; c->params = p; c->mem.ctx = c;
-    c->c.reset(new TfContext(m->tf, n_ctx));
+    // type_k == type_v == 8 (GGML_TYPE_Q8_0): the Q8_0 KV cache; every other pair keeps the f16 cache
+    c->c.reset(new TfContext(m->tf, n_ctx, p.type_k == 8 && p.type_v == 8 ? KV_Q8_0 : KV_F16));
     return c;
     SHIM_CATCH(nullptr)
 }

@@ -7,10 +7,12 @@ namespace q3 {
 
 class TfContext {
 public:
-    TfContext(std::shared_ptr<Transformer> model, int n_ctx) : model_(std::move(model)), n_ctx_(n_ctx) {
+    TfContext(std::shared_ptr<Transformer> model, int n_ctx, int kv_type = KV_F16) : model_(std::move(model)), n_ctx_(n_ctx) {
         const auto& hp = model_->hp();
         const int pages = (n_ctx + 63) / 64;
-        kv_.reset(new KvPool(hp.n_layer, hp.n_kv, pages, 1, pages));
+        kv_.reset(new KvPool(hp.n_layer, hp.n_kv, pages, 1, pages, kv_type));
+        Q3_CHECK(!(kv_type == KV_Q8_0 && model_->ggml_mode()), "Q3_SPEC=ggml has no KV cache type Q8_0 (an [EXT] mode): use the F16 cache");
+        if (kv_type == KV_Q8_0) kvq8_ = kv_->view_q8();
         const int mt = model_->max_tok();
         d_x_.alloc((size_t)mt * hp.n_embd); d_hid_.alloc((size_t)mt * hp.n_embd);
         d_seq_.alloc(mt); d_slot_.alloc(mt); d_pos_.alloc((size_t)4 * mt);
@@ -36,6 +38,7 @@ public:
             TokMeta tm{d_seq_.p, d_slot_.p, d_pos_.p};
             Transformer::Input in; in.x = d_x_.p; in.x_stride = hp.n_embd;
             model_->set_same_seq_tokens(true);
+            model_->set_kv_q8(kv_->kv_type() == KV_Q8_0 ? &kvq8_ : nullptr);   // (contexts of both types may share the model)
             model_->forward(st_, in, n, tm, kv_->view(), nullptr);
             const bool want_logits = logits_out && row1 > row0;
             const int r0 = row0 & ~31, nr = want_logits ? row1 - r0 : 0;
@@ -63,7 +66,7 @@ public:
 private:
     std::shared_ptr<Transformer> model_;
     int n_ctx_, n_past_ = 0;
-    std::unique_ptr<KvPool> kv_;
+    std::unique_ptr<KvPool> kv_; KvCacheQ8 kvq8_{};
     DevBuf<float> d_x_, d_hid_, d_logits_;
     DevBuf<int32_t> d_seq_, d_slot_, d_pos_;
     hipStream_t st_ = nullptr;

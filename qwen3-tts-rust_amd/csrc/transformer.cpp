@@ -357,6 +357,8 @@ void build_rope_tables(float rope_base, int n_ctx, std::vector<float>& c, std::v
 }
 
 int plan_attention(const AttnPlanIn& a) {
+    Q3_CHECK(!(a.kv_q8 && a.ggml_mode), "Q3_SPEC=ggml has no KV cache type Q8_0 (an [EXT] mode): use the F16 cache");
+    if (a.kv_q8) return ATTN_Q8KV;
     if (a.ggml_mode) return ATTN_GGML;
     // the single-wave form: wide steps of one token per sequence, two q heads per kv head
     if (a.short_attn_min > 0 && a.ntok >= a.short_attn_min && !a.same_seq && a.n_head == 2 * a.n_kv)
@@ -366,10 +368,17 @@ int plan_attention(const AttnPlanIn& a) {
     return ATTN_UNFUSED;
 }
 
+void Transformer::set_kv_q8(const KvCacheQ8* c) {
+    Q3_CHECK(!c || !ggml_mode_, "Q3_SPEC=ggml has no KV cache type Q8_0 (an [EXT] mode): use the F16 cache");
+    kv_q8_ = c != nullptr;
+    if (c) kvq8_ = *c;
+}
+
 int Transformer::attention_form(int ntok) const {
     AttnPlanIn a;
     a.ntok = ntok; a.fused = fused; a.fused_max_tok = fused_max_tok_; a.same_seq = same_seq_; a.short_attn_min = short_attn_min_;
     a.n_head = hp_.n_head; a.n_kv = hp_.n_kv; a.hpw1_max = short_attn_hpw1_max(); a.float_mode = float_mode_; a.ggml_mode = ggml_mode_;
+    a.kv_q8 = kv_q8_;
     return plan_attention(a);
 }
 
@@ -378,6 +387,7 @@ Transformer::Transformer(const Transformer& o, int max_tok)
     : fused(o.fused), float_mode_(o.float_mode_), foutput_(o.foutput_), hp_(o.hp_), n_ctx_(o.n_ctx_), max_tok_(max_tok), layers_(o.layers_), output_(o.output_),
       output_norm_(o.output_norm_), ws_(o.ws_), weight_bytes_(o.weight_bytes_), layer_weight_bytes_(o.layer_weight_bytes_),
       ggml_mode_(o.ggml_mode_), gg_layers_(o.gg_layers_), gg_output_(o.gg_output_) {
+    kvq8_ = o.kvq8_; kv_q8_ = o.kv_q8_;
     alloc_workspace();
 }
 
@@ -475,7 +485,12 @@ void Transformer::qkv(const Pass& s, const Layer& L, const NormPro& a) {
 
 void Transformer::attention(const Pass& s, const Layer& L, int l, const QkvRows& rows) {
     float* att = float_mode_ ? attf_.p : nullptr; // f32 rows for the float o-projection; the int8 copy (aq_, ad_) is always written
-    if (s.af == ATTN_SHORT1 || s.af == ATTN_SHORT2)
+    if (s.af == ATTN_Q8KV) {
+        KvCacheQ8 c = kvq8_; c.page_table = s.kv.page_table; c.max_pages = s.kv.max_pages;
+        launch_qk_rope_append_q8(s.st, rows, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p, n_ctx_, d_mrope_.p, s.tm, c, l,
+                                 qrot_.p, s.ntok);
+        launch_attention_q8kv(s.st, qrot_.p, hp_.n_head, hp_.n_kv, s.tm, c, l, att, aq_.p, ad_.p, s.ntok);
+    } else if (s.af == ATTN_SHORT1 || s.af == ATTN_SHORT2)
         launch_attention_short(s.st, s.af == ATTN_SHORT1 ? 1 : 2, rows, hp_.n_head, hp_.n_kv, L.q_norm, L.k_norm, hp_.eps, rope_cos_.p, rope_sin_.p,
                                n_ctx_, d_mrope_.p, s.tm, s.kv, l, aq_.p, ad_.p, s.ntok, att);
     else if (s.af == ATTN_FUSED)
@@ -620,9 +635,10 @@ void Transformer::head_impl(hipStream_t st, int tok0, int tok_count, int row0, i
 }
 
 // ------------------------------------------------------------------------------------------------
-KvPool::KvPool(int n_layer, int n_kv, int n_pages, int n_seq, int max_pages_per_seq)
-    : n_layer_(n_layer), n_kv_(n_kv), n_pages_(n_pages), n_seq_(n_seq), max_pages_(max_pages_per_seq) {
-    const size_t per_page = (size_t)n_layer * n_kv * 8192;
+KvPool::KvPool(int n_layer, int n_kv, int n_pages, int n_seq, int max_pages_per_seq, int kv_type)
+    : n_layer_(n_layer), n_kv_(n_kv), n_pages_(n_pages), n_seq_(n_seq), max_pages_(max_pages_per_seq), kv_type_(kv_type) {
+    kv_layout(n_layer, n_kv, kv_type, nullptr, &plane_page_);   // (refuses an unknown type)
+    const size_t per_page = plane_page_ / 2;                     // halfs; F16: n_layer * n_kv * 8192
     k_.alloc(per_page * n_pages); v_.alloc(per_page * n_pages);
     k_.zero(); v_.zero();
     const size_t nt = (size_t)n_seq * max_pages_per_seq;
@@ -636,6 +652,15 @@ KvPool::KvPool(int n_layer, int n_kv, int n_pages, int n_seq, int max_pages_per_
 KvCache KvPool::view() const {
     KvCache c;
     c.k = k_.p; c.v = v_.p; c.page_table = d_table_.p; c.max_pages = max_pages_; c.n_layer = n_layer_; c.n_kv = n_kv_;
+    if (kv_type_ == KV_Q8_0) { c.n_layer = (int)(plane_page_ / 16384); c.n_kv = 1; }
+    return c;
+}
+KvCacheQ8 KvPool::view_q8() const {
+    Q3_CHECK(kv_type_ == KV_Q8_0, "not a Q8_0 KV pool");
+    KvCacheQ8 c;
+    c.kq = (int8_t*)k_.p; c.ks = k_.p + 4096; c.vq = (int8_t*)v_.p; c.vs = v_.p + 4096;   // a unit: 8192 bytes of quants, then 256 scales
+    c.page_table = d_table_.p; c.max_pages = max_pages_; c.n_layer = n_layer_; c.n_kv = n_kv_;
+    c.page_q = (uint32_t)plane_page_; c.page_s = (uint32_t)(plane_page_ / 2); c.head_q = KVQ8_UNIT; c.head_s = KVQ8_UNIT / 2;
     return c;
 }
 int KvPool::alloc_page() { Q3_CHECK(!free_.empty(), "KV pool exhausted"); int p = free_.back(); free_.pop_back(); return p; }

@@ -18,8 +18,9 @@ struct TfHparams {
 
 // The attention forms of spec S7 (S4' per-head RMSNorm, S5 M-RoPE, S6 f16 KV append, causal GQA softmax.V), numbered as q3tts.h's
 // Q3TTS_ATTN_*: UNFUSED = k_qk_rope_append + k_attention, FUSED = k_attention_fused, SHORT1 / SHORT2 = k_attention_short<1|2>,
-// GGML = k_gg_qk_rope_append + k_gg_attention (the Q3_SPEC=ggml arithmetic).
-enum AttnForm { ATTN_UNFUSED = 1, ATTN_FUSED = 2, ATTN_SHORT1 = 3, ATTN_SHORT2 = 4, ATTN_GGML = 5 };
+// GGML = k_gg_qk_rope_append + k_gg_attention (the Q3_SPEC=ggml arithmetic), Q8KV = k_qk_rope_append_q8 + k_attention_q8kv ([EXT] KV cache
+// type Q8_0: every step over an int8 cache, decode and prefill, takes that pair).
+enum AttnForm { ATTN_UNFUSED = 1, ATTN_FUSED = 2, ATTN_SHORT1 = 3, ATTN_SHORT2 = 4, ATTN_GGML = 5, ATTN_Q8KV = 6 };
 struct AttnPlanIn {
     int ntok = 1;
     bool fused = true; int fused_max_tok = 8;   // Transformer::fused and the 5-launch layer path's token limit
@@ -28,6 +29,7 @@ struct AttnPlanIn {
     int n_head = 1, n_kv = 1;
     int hpw1_max = 128;                         // short_attn_hpw1_max()
     bool float_mode = false, ggml_mode = false;
+    bool kv_q8 = false;                         // the step's cache is a KvCacheQ8 (refused in ggml mode)
 };
 // host only: the form Transformer::forward runs for one step (its launches depend on nothing else)
 int plan_attention(const AttnPlanIn& in);
@@ -75,6 +77,9 @@ public:
     // input: the rows Input::qkv0 takes.  Runs in chunks of max_tok rows on this context's workspace.
     void build_layer0_qkv(hipStream_t st, const float* x, int x_stride, int64_t rows, float* out);
     void set_same_seq_tokens(bool v) { same_seq_ = v; }
+    // [EXT] KV cache type Q8_0: with a descriptor set, every step appends to and attends over these int8 pages (ATTN_Q8KV) and reads only
+    // the page table of forward()'s KvCache; null = the f16 cache.  Refused by name in ggml mode.  A copy (second context) inherits it.
+    void set_kv_q8(const KvCacheQ8* c);
     // steps of at least `min_tok` tokens (0 = never) use the single-wave attention kernel, which reads page 0 of a sequence only: the
     // caller states that no sequence ever holds more than `max_positions` positions, and that must fit one KV page (64)
     void set_short_attention(int min_tok, int max_positions) {
@@ -134,6 +139,7 @@ private:
     void alloc_workspace();
     // activations
     DevBuf<float> h_, h2_, parts_o_, parts_d_, qkv_, qrot_, gu_;
+    KvCacheQ8 kvq8_{}; bool kv_q8_ = false;
     bool same_seq_ = false; int short_attn_min_ = 0; int fused_max_tok_ = 8; bool last_fused_ = false; int last_ntok_ = 0;
     DevBuf<int8_t> xq_, aq_, fq_;
     DevBuf<uint16_t> xd_, ad_, fd_;
@@ -160,10 +166,14 @@ Q8Mat kqmat_from_host(const void* const* raw, const int32_t* types, const int32_
 // simple paged KV pool (pages of 64 positions) -- "paged KV cache sized for 288 GB HBM3E"
 class KvPool {
 public:
-    KvPool(int n_layer, int n_kv, int n_pages, int n_seq, int max_pages_per_seq);
+    KvPool(int n_layer, int n_kv, int n_pages, int n_seq, int max_pages_per_seq, int kv_type = KV_F16);
     ~KvPool();
     KvPool(const KvPool&) = delete; KvPool& operator=(const KvPool&) = delete;
+    // F16: the cache.  Q8_0: the same two planes as the page-copy kernels and the stem stores see them -- n_layer = the 16-KiB tiles of a
+    // plane page, n_kv = 1, so page_stride() is the plane page and k_kv_fork / k_kv_stem move it tile by tile as they always did.
     KvCache view() const;
+    KvCacheQ8 view_q8() const;   // Q8_0 pools only: units of quants then scales inside the padded plane pages
+    int kv_type() const { return kv_type_; }
     // host-side page accounting
     int alloc_page();
     void free_page(int p);
@@ -176,7 +186,7 @@ public:
     size_t bytes() const { return (k_.n + v_.n) * 2; }
 private:
     int grow(int seq, int n_positions); // host table only: takes the missing pages, returns the first new logical page
-    int n_layer_, n_kv_, n_pages_, n_seq_, max_pages_;
+    int n_layer_, n_kv_, n_pages_, n_seq_, max_pages_, kv_type_; size_t plane_page_ = 0; // bytes
     DevBuf<uint16_t> k_, v_;
     DevBuf<int32_t> d_table_;
     int32_t* table_ = nullptr; // pinned host mirror of the page table

@@ -86,7 +86,7 @@ SYMBOLS = [
     "q3tts_gen_options_default", "q3tts_submit_ex", "q3tts_submit_text_ex", "q3tts_generate_batch_ex", "q3tts_group_submit_ex",
     "q3tts_group_submit_text_ex", "q3tts_op_sample_rows",
     "q3tts_prompt_build_streaming", "q3tts_submit_trailing", "q3tts_submit_text_streaming", "q3tts_generate_batch_trailing",
-    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_codec_gemm_tap_reuse", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan",
+    "q3tts_group_submit_text_streaming", "q3tts_op_codec_gemm", "q3tts_codec_gemm_plan", "q3tts_codec_gemm_tap_reuse", "q3tts_op_codec_kernel", "q3tts_op_attention", "q3tts_attention_plan", "q3tts_op_attention_q8kv", "q3tts_kv_layout", "q3tts_engine_create_kv", "q3tts_tf_open_kv",
     "q3tts_op_linear", "q3tts_linear_plan", "q3tts_argmax_key",
     "q3tts_submit_trailing_open", "q3tts_trail_append", "q3tts_trail_progress", "q3tts_submit_text_streaming_open", "q3tts_text_append",
     "q3tts_group_submit_text_streaming_open", "q3tts_group_text_append", "q3tts_group_trail_append", "q3tts_group_trail_progress",
@@ -905,7 +905,9 @@ class Chunker:  # engine.rs:495-543
 
 
 class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
-    def __init__(self, model_dir, quant="q8_0", max_batch=1, max_prompt=1024, max_steps=512, load_codec=True, use_graph=True, device=0):
+    def __init__(self, model_dir, quant="q8_0", max_batch=1, max_prompt=1024, max_steps=512, load_codec=True, use_graph=True, device=0,
+                 kv_type=None):
+        """kv_type: None = q3tts_engine_create; "f16" / "q8_0" (or a type id) = q3tts_engine_create_kv with that talker KV cache type"""
         p = EngineParams()
         lib().q3tts_engine_params_default(C.byref(p))
         self._md = model_dir.encode()
@@ -919,7 +921,11 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
         p.load_codec = 1 if load_codec else 0
         p.use_graph = 1 if use_graph else 0
         h = C.c_void_p()
-        _chk(lib().q3tts_engine_create(C.byref(p), C.byref(h)))
+        if kv_type is None:
+            _chk(lib().q3tts_engine_create(C.byref(p), C.byref(h)))
+        else:
+            lib().q3tts_engine_create_kv.argtypes = [C.POINTER(EngineParams), C.c_int32, C.POINTER(C.c_void_p)]
+            _chk(lib().q3tts_engine_create_kv(C.byref(p), KV_TYPES.get(kv_type, kv_type), C.byref(h)))
         self.h = h.value
         self.max_steps = max_steps
         self._voice_ref = {}   # voice id -> its reference codes [n][16] (prime_voice)
@@ -1412,9 +1418,14 @@ class Engine:  # TtsEngine (engine.rs:53-169) at the embedding level
 
 
 class TfContext:  # LlamaModel + LlamaContext at the embedding level (llama/mod.rs:326-513)
-    def __init__(self, path, n_ctx=4096, max_tok=64):
+    def __init__(self, path, n_ctx=4096, max_tok=64, kv_type=None):
+        """kv_type: None = q3tts_tf_open; "f16" / "q8_0" (or a type id) = q3tts_tf_open_kv with that KV cache type"""
         h = C.c_void_p()
-        _chk(lib().q3tts_tf_open(path.encode(), n_ctx, max_tok, C.byref(h)))
+        if kv_type is None:
+            _chk(lib().q3tts_tf_open(path.encode(), n_ctx, max_tok, C.byref(h)))
+        else:
+            lib().q3tts_tf_open_kv.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+            _chk(lib().q3tts_tf_open_kv(path.encode(), n_ctx, max_tok, KV_TYPES.get(kv_type, kv_type), C.byref(h)))
         self.h = h.value
         d = [C.c_int32() for _ in range(4)]
         lib().q3tts_tf_dims(self.h, *[C.byref(x) for x in d])
@@ -1944,6 +1955,66 @@ def op_attention(qkv, q_norm, k_norm, k_cache, v_cache, n_head, n_kv, n_layer, l
     if keys is not None:
         r["qkv"] = qkv
     return r
+
+
+KV_TYPES = {"f16": 1, "q8_0": 8}  # Q3TTS_KV_*: ggml's type ids
+
+
+def kv_layout(n_layer, n_kv, kv_type="f16"):
+    """(bytes per cached token, bytes per plane page) of a KV cache type (q3tts_kv_layout; host only).  kv_type: a KV_TYPES name or a type id"""
+    bpt, page = C.c_int64(0), C.c_int64(0)
+    lib().q3tts_kv_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    _chk(lib().q3tts_kv_layout(n_layer, n_kv, KV_TYPES.get(kv_type, kv_type), C.byref(bpt), C.byref(page)))
+    return bpt.value, page.value
+
+
+class AttentionQ8kvDesc(C.Structure):  # q3tts_attention_q8kv_desc
+    _fields_ = [("n_head", C.c_int32), ("n_kv", C.c_int32), ("n_layer", C.c_int32), ("layer", C.c_int32), ("ntok", C.c_int32),
+                ("qkv", C.c_void_p), ("qkv_stride", C.c_int32), ("q_norm", C.c_void_p), ("k_norm", C.c_void_p),
+                ("eps", C.c_float), ("rope_base", C.c_float), ("n_ctx", C.c_int32), ("mrope_sec", C.c_int32 * 4),
+                ("seq", C.c_void_p), ("slot", C.c_void_p), ("pos", C.c_void_p),
+                ("page_table", C.c_void_p), ("n_seq", C.c_int32), ("max_pages", C.c_int32),
+                ("kq", C.c_void_p), ("ks", C.c_void_p), ("vq", C.c_void_p), ("vs", C.c_void_p), ("n_pages", C.c_int32),
+                ("att", C.c_void_p), ("qrot", C.c_void_p), ("aq", C.c_void_p), ("ad", C.c_void_p), ("form_ran", C.c_int32)]
+
+
+def op_attention_q8kv(qkv, q_norm, k_norm, kq, ks, vq, vs, n_head, n_kv, n_layer, layer, seq, slot, pos, eps=1e-6, rope_base=1e6,
+                      n_ctx=4096, mrope_sec=(0, 0, 0, 0), page_table=None, copy=True):
+    """one layer's attention step over a Q8_0 KV cache (q3tts_op_attention_q8kv).  kq / vq int8 [n_pages][n_layer][n_kv][8192] and
+    ks / vs uint16 [n_pages][n_layer][n_kv][256] in the device layouts (copied, or -- copy=False, C-contiguous arrays of those types -- written in place; the written-back arrays are
+    returned).  Returns dict(att, qrot [ntok][n_head*128] f32, aq, ad, kq, ks, vq, vs)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    ntok = qkv.shape[0]
+    q_norm = np.ascontiguousarray(q_norm, np.float32)
+    k_norm = np.ascontiguousarray(k_norm, np.float32)
+    if copy:
+        kq, ks, vq, vs = (np.array(a, t, copy=True, order="C") for a, t in ((kq, np.int8), (ks, np.uint16), (vq, np.int8), (vs, np.uint16)))
+    assert all(a.flags.c_contiguous and a.dtype == t for a, t in ((kq, np.int8), (ks, np.uint16), (vq, np.int8), (vs, np.uint16)))
+    unit = n_layer * n_kv
+    n_pages = kq.size // (unit * 8192)
+    assert kq.size == vq.size == n_pages * unit * 8192 and ks.size == vs.size == n_pages * unit * 256
+    seq = np.ascontiguousarray(seq, np.int32)
+    slot = np.ascontiguousarray(slot, np.int32)
+    pos = np.ascontiguousarray(pos, np.int32).reshape(ntok, 4)
+    d = AttentionQ8kvDesc()
+    d.n_head, d.n_kv, d.n_layer, d.layer, d.ntok = n_head, n_kv, n_layer, layer, ntok
+    d.qkv, d.qkv_stride, d.q_norm, d.k_norm = _p(qkv), qkv.shape[1], _p(q_norm), _p(k_norm)
+    d.eps, d.rope_base, d.n_ctx = eps, rope_base, n_ctx
+    for i in range(4):
+        d.mrope_sec[i] = int(mrope_sec[i])
+    d.seq, d.slot, d.pos = _p(seq), _p(slot), _p(pos)
+    if page_table is not None:
+        page_table = np.ascontiguousarray(page_table, np.int32)
+        d.page_table, d.n_seq, d.max_pages = _p(page_table), page_table.shape[0], page_table.shape[1]
+    d.kq, d.ks, d.vq, d.vs, d.n_pages = _p(kq), _p(ks), _p(vq), _p(vs), n_pages
+    att = np.full((ntok, n_head * 128), np.nan, np.float32)
+    qrot = np.full((ntok, n_head * 128), np.nan, np.float32)
+    aq = np.zeros((ntok, n_head * 128), np.int8)
+    ad = np.zeros((ntok, n_head * 4), np.uint16)
+    d.att, d.qrot, d.aq, d.ad = _p(att), _p(qrot), _p(aq), _p(ad)
+    lib().q3tts_op_attention_q8kv.argtypes = [C.POINTER(AttentionQ8kvDesc)]
+    _chk(lib().q3tts_op_attention_q8kv(C.byref(d)))
+    return dict(att=att, qrot=qrot, aq=aq, ad=ad, kq=kq, ks=ks, vq=vq, vs=vs)
 
 
 def op_gemv_kq(parts, k, xq, xd, lpr=0):
