@@ -9,29 +9,13 @@ import numpy as np
 import pytest
 
 import linear_ref as R
-import q3k_ref as K3
 import q3tts as Q
-import q4k_ref as K4
 import synth_models
+from kq_ref import decode as _decode, weights as _weights
 from test_gpu_linear import POISON, _acts, _bits, _norm_inputs, _poison
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RAND = {11: K3.rand_rows_q3k, 12: K4.rand_rows_q4k}
-TWIN = {11: lambda raw: (K3.widen_to_q6k(raw), 14), 12: lambda raw: (K4.widen(raw), 13)}
-DEC = {11: K3.dec_q3_k, 12: K4.dec_q4_k}
-
-
-def _weights(rng, types, rows, k):
-    """-> (device tensors, oracle tensors): Q3_K rows go to the oracle as their Q6_K twin, Q4_K rows as their Q5_K twin"""
-    dev = [(RAND[t](rng, n, k) if t in RAND else R.rand_rows(rng, t, n, k), t, n) for t, n in zip(types, rows)]
-    return dev, [TWIN[t](raw) + (n,) if t in TWIN else (raw, t, n) for raw, t, n in dev]
-
-
-def _decode(dev, k):
-    A, B = zip(*[DEC[t](r, n, k) if t in DEC else R.decode(r, t, n, k) for r, t, n in dev])
-    return np.concatenate(A), np.concatenate(B)
-
 
 MIXED = [([11, 11, t], [32, 32, 32], 512, nt, 0, 96) for t in (13, 12) for nt in (1, 33)]
 GEMV_CASES = [([11], [32], 256, 1, 0, 32), ([11], [64], 2048, 3, 32, 32), ([11], [64], 2304, 9, 0, 64), ([11], [64], 1024, 17, 0, 64)] + MIXED

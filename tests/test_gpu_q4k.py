@@ -10,24 +10,12 @@ import pytest
 
 import linear_ref as R
 import q3tts as Q
-import q4k_ref as K4
 import synth_models
+from kq_ref import decode as _decode, weights as _weights
 from test_gpu_linear import POISON, _acts, _bits, _norm_inputs, _poison
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _weights(rng, types, rows, k):
-    """-> (device tensors, oracle tensors): Q4_K rows go to the oracle as their Q5_K twin"""
-    dev = [(K4.rand_rows_q4k(rng, n, k) if t == 12 else R.rand_rows(rng, t, n, k), t, n) for t, n in zip(types, rows)]
-    return dev, [(K4.widen(raw), 13, n) if t == 12 else (raw, t, n) for raw, t, n in dev]
-
-
-def _decode(dev, k):
-    A, B = zip(*[K4.dec_q4_k(r, n, k) if t == 12 else R.decode(r, t, n, k) for r, t, n in dev])
-    return np.concatenate(A), np.concatenate(B)
-
 
 GEMV_CASES = [([12], [32], 256, 1, 0, 32), ([12], [64], 2048, 3, 32, 32), ([12], [64], 2304, 9, 0, 64), ([12], [64], 1024, 17, 0, 64),
               ([12], [32], 512, 33, 0, 32), ([12, 14], [32, 32], 1024, 40, 0, 64), ([12, 14, 8], [32, 32, 32], 256, 2, 0, 96),
