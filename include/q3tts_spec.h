@@ -681,8 +681,11 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
  * Q5_K below n_layer / 16, else Q4_K; output / head tensors Q6_K) is llama.cpp's as remembered [EXT, unpinned]. */
 
 /* ---------------- KV cache type Q8_0 [EXT] (q3tts_kv_layout, q3tts_op_attention_q8kv) ----------------
- * The talker's K and V rows kept as int8 blocks of 32 with f16 scales (ggml's -ctk q8_0 -ctv q8_0) instead of f16.  Not a bit-exact item
- * against the oracle: it is pinned to float64 (tests/test_gpu_kv_q8.py).  F16 stays the default and every S6 / S7 kernel is unchanged.
+ * The talker's K and V rows kept as int8 blocks of 32 with f16 scales (ggml's -ctk q8_0 -ctv q8_0) instead of f16.  A bit-exact item
+ * against the oracle: the text below is a complete, ordered restatement, q3o_attn_head_q8 and the oracle model's Q8_0 cache type are written
+ * from it, and the kernels, TfContext, the engine and the llama shim equal them bit for bit (tests/test_gpu_kv_q8.py,
+ * tests/test_gpu_kv_q8_parity.py).  The oracle's head is itself held to float64 by the derived bound below
+ * (tests/test_kv_q8_oracle_cpu.py), and so are the kernels.  F16 stays the default and every S6 / S7 kernel is unchanged.
  *   append (S6')  the K row is the f32 result of S4' and S5, the V row the raw f32 v, 128 values each.  Each row is four blocks of 32,
  *                 each quantised by q3_quant_block32 (S2): d = amax / 127, id = 1 / d or 0, q = rint(x * id), the scale stored as f16
  *   query         the rotated f32 query row is quantised the same way: scales e_b, quants r_b, b = 0..3
@@ -690,8 +693,11 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
  *                 ascending acc = fmaf((float)I_b, f32(e_b) * f32(dk_jb), acc); s_j = acc * scale.  (ggml's vec_dot_q8_0_q8_0 shape)
  *   softmax       S7 unchanged: chunks of 256 positions, the chunk maximum, p_j = q3_expf(s_j - m), the M / L merges
  *   PV            S7's 16 chains and combine tree unchanged; the term fmaf(p_j, v_jd, S) becomes w = p_j * f32(dv_jb), S = fmaf(w, (float)qv_jd, S),
- *                 b the block of dimension d
- *   output        the f32 row and its S2 quantisation unchanged
+ *                 b the block of dimension d.  A chain takes one term per position of the chunk and none past the chunk's last one; filling
+ *                 the last 16-row step with terms fmaf(+0, +0, S), as the kernel does, gives the same bits, because a chain is never -0:
+ *                 it starts at +0, w * qv is an exact zero or at least one subnormal in magnitude (|qv| >= 1), and +0 plus a zero of
+ *                 either sign, like an exact cancellation, is +0 in round-to-nearest
+ *   output       the f32 row and its S2 quantisation unchanged
  * Tolerance against float64 (tests/test_gpu_kv_q8.py): |y - y64| <= tol * sum_j p_j |v_j| per element, except where the quantised V is exactly
  * 0 at every position whose p_j q3_expf does not flush to 0 (below -87): there the device's element is 0, float64's is the sum of the flushed
  * terms, and the bound is e^-86 * sum_j |v_jd| instead.

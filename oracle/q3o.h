@@ -91,6 +91,10 @@ void q3o_head_rope(const float* x, const float* g, float eps, const int32_t pos[
                    const float* rope_sin, int n_ctx, int ggml, float* out);
 /* spec S7: one query head against n cached f16 positions, element (pos, d) of K / V at base[pos * stride + d] */
 void q3o_attn_head(const float* q, const uint16_t* K, const uint16_t* V, size_t stride, int n, float* out);
+/* spec "KV cache type Q8_0": one query head against n cached positions of int8 blocks of 32 with f16 scales; position j's 128 quants at
+ * Kq / Vq + j * qstride, its four scales at Ks / Vs + j * sstride */
+void q3o_attn_head_q8(const float* q, const int8_t* Kq, const uint16_t* Ks, const int8_t* Vq, const uint16_t* Vs, size_t qstride,
+                      size_t sstride, int n, float* out);
 
 /* ---------------- transformer (talker / predictor) ---------------- */
 typedef struct q3o_layer {
@@ -112,10 +116,15 @@ typedef struct q3o_model {
     float* rope_cos; /* [n_ctx][64] */
     float* rope_sin;
     int n_threads;
+    int kv_type;      /* Q3_T_F16 (default) or Q3_T_Q8_0: spec "KV cache type Q8_0" */
+    int8_t *kq8, *vq8;     /* Q8_0 type: [layer][pos][kvh][128] quants, allocated when the type is first set */
+    uint16_t *ks8, *vs8;   /*            [layer][pos][kvh][4] f16 scales */
 } q3o_model;
 
 q3o_model* q3o_model_load(const char* path, int n_ctx, char* err, size_t errlen);
 void q3o_model_free(q3o_model* m);
+/* KV cache type of the following evaluations (clears the cache): 0 = set, -1 = unknown type, -2 = Q8_0 under Q3_SPEC=ggml, which has none */
+int q3o_model_set_kv_type(q3o_model* m, int kv_type);
 void q3o_model_clear_kv(q3o_model* m);
 /* one token: x[n_embd] embedding, pos[4] M-RoPE streams (predictor: pos[0] only, others ignored when
  * sections are zero).  hidden_out[n_embd] = final-norm hidden (may be NULL); logits for rows
@@ -201,6 +210,8 @@ typedef struct q3o_engine {
 
 q3o_engine* q3o_engine_create(const char* model_dir_quant, const char* codec_path, int n_threads, char* err, size_t errlen);
 void q3o_engine_free(q3o_engine* e);
+/* KV cache type of the talker (q3o_model_set_kv_type's values and results); the predictor keeps F16, as the product's engine does */
+int q3o_engine_set_kv_type(q3o_engine* e, int kv_type);
 /* prompt [n_prompt][2048]; codes_out capacity max_steps*16; pcm_out may be NULL.
  * returns number of frames generated, <0 on error. n_pcm_out receives sample count. */
 int q3o_engine_generate(q3o_engine* e, const float* prompt, int n_prompt, int32_t* codes_out,

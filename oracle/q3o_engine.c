@@ -293,6 +293,7 @@ void q3o_engine_free(q3o_engine* e) {
     if (e->codec) q3o_codec_free(e->codec);
     free(e);
 }
+int q3o_engine_set_kv_type(q3o_engine* e, int kv_type) { return q3o_model_set_kv_type(e->talker, kv_type); }
 
 typedef struct { q3o_codec* codec; float* pcm; int max_pcm; int n_pcm; } dec_ctx;
 static void dec_cb(void* user, const int64_t* codes, int n_codes, int is_final) {

@@ -5,7 +5,7 @@
  * src/tts/engine.rs:460-462,580-582,607-609,637-639).
  *
  * Block structure [EXT, llama.cpp qwen3 graph == transformers Qwen3DecoderLayer]: RMSNorm -> q/k/v ->
- * per-head q/k RMSNorm -> NeoX (M-)RoPE -> causal GQA attention over an f16 KV cache -> o-proj ->
+ * per-head q/k RMSNorm -> NeoX (M-)RoPE -> causal GQA attention over an f16 (or, [EXT], Q8_0) KV cache -> o-proj ->
  * residual; RMSNorm -> SwiGLU FFN -> residual; final RMSNorm ("embeddings") -> output matrix (logits).
  * Arithmetic: include/q3tts_spec.h (S2-S9).
  */
@@ -67,6 +67,7 @@ q3o_model* q3o_model_load(const char* path, int n_ctx, char* err, size_t errlen)
             for (uint64_t i = 0; i < s->arr_n && i < 4; i++) m->mrope_sec[i] = ((int32_t*)s->arr)[i];
     }
     m->n_ctx = n_ctx;
+    m->kv_type = Q3_T_F16;
     if (m->n_embd <= 0 || m->n_layer <= 0 || m->n_head <= 0 || m->head_dim != Q3_HEAD_DIM ||
         m->n_embd % Q3_SEG || m->n_ff % Q3_SEG || m->n_head % m->n_head_kv) {
         snprintf(err, errlen, "unsupported hparams embd=%d layer=%d head=%d/%d hd=%d ff=%d", m->n_embd,
@@ -100,7 +101,7 @@ q3o_model* q3o_model_load(const char* path, int n_ctx, char* err, size_t errlen)
 
 void q3o_model_free(q3o_model* m) {
     if (!m) return;
-    free(m->layers); free(m->kcache); free(m->vcache); free(m->rope_cos); free(m->rope_sin);
+    free(m->layers); free(m->kcache); free(m->vcache); free(m->kq8); free(m->ks8); free(m->vq8); free(m->vs8); free(m->rope_cos); free(m->rope_sin);
     q3o_gguf_close(m->g);
     free(m);
 }
@@ -192,9 +193,94 @@ void q3o_attn_head(const float* q, const uint16_t* K, const uint16_t* V, size_t 
     for (int d = 0; d < 128; d++) out[d] = O[d] / L;
 }
 
+/* spec "KV cache type Q8_0": one query head against n cached positions held as int8 blocks of 32 with f16 scales.  Position j's 128 quants
+ * are at Kq / Vq + j * qstride, its four scales at Ks / Vs + j * sstride.  Written from the spec paragraph: the query goes through S2, a
+ * score is four exact int32 block dots folded by one fma each, and the chunk loop, lc, the M / L merge and the final divide are
+ * q3o_attn_head's lines.  PV: a chain takes one term per position of the chunk and none for a position past the chunk's last one (cn);
+ * a kernel that fills its last 16-row step with terms fmaf(+0, +0, S) computes the same bits, since a chain starts at +0 and is never
+ * -0 (see the spec paragraph). */
+void q3o_attn_head_q8(const float* q, const int8_t* Kq, const uint16_t* Ks, const int8_t* Vq, const uint16_t* Vs, size_t qstride,
+                      size_t sstride, int n, float* out) {
+    const float scale = 0.08838834764831845f; /* 1/sqrt(128) */
+    int8_t r[128];
+    uint16_t e16[4];
+    float e[4];
+    q3o_quant_act(q, 128, r, e16);
+    for (int b = 0; b < 4; b++) e[b] = q3_f16_to_f32(e16[b]);
+    float M = 0, L = 0, O[128];
+    float s[Q3_ATT_CHUNK], p[Q3_ATT_CHUNK];
+    for (int c0 = 0; c0 < n; c0 += Q3_ATT_CHUNK) {
+        int cn = n - c0 < Q3_ATT_CHUNK ? n - c0 : Q3_ATT_CHUNK;
+        float mc = 0;
+        for (int j = 0; j < cn; j++) {
+            const int8_t* kr = Kq + (size_t)(c0 + j) * qstride;
+            const uint16_t* kd = Ks + (size_t)(c0 + j) * sstride;
+            float acc = 0.0f;
+            for (int b = 0; b < 4; b++) {
+                int32_t I = 0;
+                for (int i = 0; i < 32; i++) I += (int32_t)r[32 * b + i] * (int32_t)kr[32 * b + i];
+                float ed = e[b] * q3_f16_to_f32(kd[b]);
+                acc = q3_fmaf((float)I, ed, acc);
+            }
+            s[j] = acc * scale;
+            if (j == 0 || s[j] > mc) mc = s[j];
+        }
+        for (int j = 0; j < cn; j++) p[j] = q3_expf(s[j] - mc);
+        float part[64], tmp[64];
+        for (int l = 0; l < 64; l++) {
+            float a = 0.0f;
+            for (int t = 0; t < 4; t++) { int j = l + 64 * t; if (j < cn) a = a + p[j]; }
+            part[l] = a;
+        }
+        for (int sft = 32; sft >= 1; sft >>= 1) {
+            for (int l = 0; l < 64; l++) tmp[l] = part[l] + part[l ^ sft];
+            memcpy(part, tmp, sizeof(part));
+        }
+        float lc = part[0];
+        float oc[128];
+        for (int d = 0; d < 128; d++) { /* 16 interleaved chains r = j mod 16, fixed combine tree */
+            float S[16] = { 0 };
+            for (int j = 0; j < cn; j++) {
+                float w = p[j] * q3_f16_to_f32(Vs[(size_t)(c0 + j) * sstride + d / 32]);
+                S[j & 15] = q3_fmaf(w, (float)Vq[(size_t)(c0 + j) * qstride + d], S[j & 15]);
+            }
+            float T4[4];
+            for (int w = 0; w < 4; w++) T4[w] = (S[4 * w] + S[4 * w + 1]) + (S[4 * w + 2] + S[4 * w + 3]);
+            oc[d] = (T4[0] + T4[1]) + (T4[2] + T4[3]);
+        }
+        if (c0 == 0) {
+            M = mc; L = lc; memcpy(O, oc, sizeof(O));
+        } else {
+            float mn = M > mc ? M : mc;
+            float a = q3_expf(M - mn), b = q3_expf(mc - mn);
+            float t = lc * b;
+            L = q3_fmaf(L, a, t);
+            for (int d = 0; d < 128; d++) { float u = oc[d] * b; O[d] = q3_fmaf(O[d], a, u); }
+            M = mn;
+        }
+    }
+    for (int d = 0; d < 128; d++) out[d] = O[d] / L;
+}
+
+/* the KV cache type: Q3_T_F16 (the default) or Q3_T_Q8_0 (spec "KV cache type Q8_0"), which Q3_SPEC=ggml does not have.  0 = set */
+int q3o_model_set_kv_type(q3o_model* m, int kv_type) {
+    if (kv_type != Q3_T_F16 && kv_type != Q3_T_Q8_0) return -1;
+    if (kv_type == Q3_T_Q8_0 && q3o_arith_mode()) return -2;
+    if (kv_type == Q3_T_Q8_0 && !m->kq8) {
+        size_t kvn = (size_t)m->n_layer * (size_t)m->n_ctx * (size_t)m->n_head_kv;
+        m->kq8 = (int8_t*)calloc(kvn, Q3_HEAD_DIM); m->vq8 = (int8_t*)calloc(kvn, Q3_HEAD_DIM);
+        m->ks8 = (uint16_t*)calloc(kvn * 4, 2); m->vs8 = (uint16_t*)calloc(kvn * 4, 2);
+    }
+    m->kv_type = kv_type;
+    m->n_past = 0;
+    return 0;
+}
+
 int q3o_model_eval(q3o_model* m, const float* x, const int32_t pos[4], float* hidden_out,
                    float* logits_out, int row0, int row1) {
     if (m->n_past >= m->n_ctx) return -1;
+    const int q8kv = m->kv_type == Q3_T_Q8_0;
+    if (q8kv && q3o_arith_mode()) return -2;
 #ifdef _OPENMP
     if (m->n_threads > 0) omp_set_num_threads(m->n_threads);
 #endif
@@ -228,15 +314,27 @@ int q3o_model_eval(q3o_model* m, const float* x, const int32_t pos[4], float* hi
             q3o_head_rope(vec, (const float*)(hh < nh ? L->q_norm->data : L->k_norm->data), m->eps, pos, m->mrope_sec, m->rope_cos, m->rope_sin,
                           m->n_ctx, q3o_arith_mode(), vec);
         }
-        for (int i = 0; i < dkv; i++) {
-            Kl[(size_t)slot * stride + i] = q3_f32_to_f16(k[i]);
-            Vl[(size_t)slot * stride + i] = q3_f32_to_f16(v[i]);
+        /* Q8_0 cache: planes [layer][pos][kvh][128] int8 and [layer][pos][kvh][4] f16; the rotated K row and the raw V row through S2 */
+        const size_t sstride = (size_t)nkv * 4;
+        int8_t *Kq = NULL, *Vq = NULL;
+        uint16_t *Ks = NULL, *Vs = NULL;
+        if (q8kv) {
+            Kq = m->kq8 + (size_t)l * m->n_ctx * stride; Vq = m->vq8 + (size_t)l * m->n_ctx * stride;
+            Ks = m->ks8 + (size_t)l * m->n_ctx * sstride; Vs = m->vs8 + (size_t)l * m->n_ctx * sstride;
+            q3o_quant_act(k, dkv, Kq + (size_t)slot * stride, Ks + (size_t)slot * sstride);
+            q3o_quant_act(v, dkv, Vq + (size_t)slot * stride, Vs + (size_t)slot * sstride);
+        } else {
+            for (int i = 0; i < dkv; i++) {
+                Kl[(size_t)slot * stride + i] = q3_f32_to_f16(k[i]);
+                Vl[(size_t)slot * stride + i] = q3_f32_to_f16(v[i]);
+            }
         }
         const int grp = nh / nkv;
 #pragma omp parallel for schedule(static)
         for (int hh = 0; hh < nh; hh++) {
             int kvh = hh / grp;
-            if (q3o_arith_mode()) q3o_attn_head_ggml(q + 128 * hh, Kl + 128 * kvh, Vl + 128 * kvh, stride, slot + 1, att + 128 * hh);
+            if (q8kv) q3o_attn_head_q8(q + 128 * hh, Kq + 128 * kvh, Ks + 4 * kvh, Vq + 128 * kvh, Vs + 4 * kvh, stride, sstride, slot + 1, att + 128 * hh);
+            else if (q3o_arith_mode()) q3o_attn_head_ggml(q + 128 * hh, Kl + 128 * kvh, Vl + 128 * kvh, stride, slot + 1, att + 128 * hh);
             else q3o_attn_head(q + 128 * hh, Kl + 128 * kvh, Vl + 128 * kvh, stride, slot + 1, att + 128 * hh);
         }
         q3o_quant_act(att, dq, xq, xd);

@@ -3,7 +3,9 @@
 // symbols, and drives them with the reference's own host-side glue (f32 project on the CPU in the reference's order,
 // assets_manager.rs:383-399; greedy sampler llama/mod.rs:690-701).  Used by tests to show that the unmodified Rust
 // crate, pointed at this library, would emit the oracle's codec tokens.
-//   usage: ref_replay <model_quant_dir> <prompt.f32> <n_prompt> <max_steps> <codes_out.i32> [mask_eos]
+//   usage: ref_replay <model_quant_dir> <prompt.f32> <n_prompt> <max_steps> <codes_out.i32> [mask_eos [type_k type_v]]
+// type_k / type_v: the talker context's llama_context_params.type_k / type_v (ggml type ids, llama.cpp's -ctk / -ctv); the reference leaves
+// the defaults (f16), and the predictor's context keeps them here.
 #include "../../include/q3tts.h"
 #include "../../include/q3tts_llama.h"
 #include <dlfcn.h>
@@ -63,14 +65,17 @@ int main(int argc, char** argv) {
     if (!talker || !pred) { fprintf(stderr, "Failed to load model\n"); return 4; }
     const int talker_embd = p_llama_model_n_embd(talker), pred_embd = p_llama_model_n_embd(pred);
     const int t_vocab = p_llama_vocab_n_tokens(p_llama_model_get_vocab(talker)), p_vocab = p_llama_vocab_n_tokens(p_llama_model_get_vocab(pred));
-    auto mkctx = [&](llama_model* m, uint32_t n_ctx, uint32_t n_batch, bool emb, int thr) { // llama/mod.rs:409-432
+    const bool kv_types = argc > 8;
+    const int type_k = kv_types ? atoi(argv[7]) : 0, type_v = kv_types ? atoi(argv[8]) : 0;
+    auto mkctx = [&](llama_model* m, uint32_t n_ctx, uint32_t n_batch, bool emb, int thr, bool set_kv) { // llama/mod.rs:409-432
         llama_context_params cp = p_llama_context_default_params();
         cp.n_ctx = n_ctx; cp.n_batch = n_batch; cp.n_ubatch = 512; cp.n_seq_max = 1; cp.embeddings = emb; cp.flash_attn_type = 1;
         cp.offload_kqv = true; cp.no_perf = true; cp.n_threads = thr > 0 ? thr : 4;
+        if (set_kv) { cp.type_k = (decltype(cp.type_k))type_k; cp.type_v = (decltype(cp.type_v))type_v; }
         return p_llama_init_from_model(m, cp);
     };
-    llama_context* tctx = mkctx(talker, 4096, 2048, true, -1);  // engine.rs:133
-    llama_context* pctx = mkctx(pred, 512, 32, false, 4);        // engine.rs:136
+    llama_context* tctx = mkctx(talker, 4096, 2048, true, -1, kv_types);  // engine.rs:133
+    llama_context* pctx = mkctx(pred, 512, 32, false, 4, false);          // engine.rs:136
     if (!tctx || !pctx) { fprintf(stderr, "Failed to create context\n"); return 4; }
     auto set_embd = [&](llama_batch& b, const float* e, size_t n_floats, int n_embd, const std::vector<int32_t>& pos, size_t cap) { // mod.rs:556-615
         const int n = (int)(n_floats / n_embd);

@@ -1,6 +1,8 @@
 """Float64 restatement of one transformer attention step, written from the spec's words and independent of the C code: per-head RMSNorm
 (S4'), NeoX M-RoPE (S5), f16 KV append (S6), causal GQA attention (S7), int8 block quantisation (S2), and the paged device layout of the
-KV caches.  Also the error bound the GPU attention tests hold every kernel form to (tests/test_gpu_attention.py)."""
+KV caches.  Also the error bound the GPU attention tests hold every kernel form to (tests/test_gpu_attention.py), and the
+quantised arithmetic of the KV cache type Q8_0 with the bound its kernels and the oracle's head are held to (tests/test_gpu_kv_q8.py,
+tests/test_kv_q8_oracle_cpu.py)."""
 import math
 
 import numpy as np
@@ -117,6 +119,43 @@ def quant_blocks(x):
     inv = np.where(d != 0, np.float32(1) / np.where(d != 0, d, np.float32(1)), np.float32(0)).astype(np.float32)
     q = np.rint(x * inv[:, None]).astype(np.int8)
     return q.reshape(-1), f16_bits(d)
+
+
+# ---------------- KV cache type Q8_0 ----------------
+FLUSH = math.exp(-86.0)
+
+
+def tol_q8(n, s, S):
+    """tol of |y - y64| <= tol * sum_j p_j |v_j|, as attention_tol's UNFUSED branch with two changes.  The inputs are the
+    quantised q and the stored cache themselves, so no norm / rotation term; the score is four fma terms of exact integers, the scale
+    product and the scale: E_j = (4 + 3) u S_j, S_j = scale * sum_b |I_b e_b dk_b|.  The PV order is S7's with one more rounding per term
+    (w = p_j * dv, rounded once, not accumulated): gamma = (chain + 1 + 8 + chunks * (8 + R)) u.
+    The issue's bound, tol * w, holds every element but one kind: q3_expf returns 0 below -87 where float64 keeps e^x, so where quantised
+    V is exactly 0 at every position the device does not flush, the device's element is 0 and w itself is a sum of flushed terms only
+    (1e-45 in the spread case).  There, and only there, the caller allows FLUSH * sum_j |v_j| instead: p_j below e^-86 (one unit of
+    margin for the score errors, far below 1 here) against L >= 1."""
+    E = 7 * U * S
+    spread = float(s.max() - s.min() + 2 * E.max())
+    delta = 2 * float(E.max()) + U * spread + 3 * U
+    chunks, chain = -(-n // CHUNK), -(-min(n, CHUNK) // 16)
+    gamma = (chain + 1 + 8 + chunks * (8 + spread)) * U
+    return 2 * delta + 2 * gamma + U
+
+
+def attention_q8(qq, qe, Kq, dk, V):
+    """the spec's quantised arithmetic in float64 for one query head over n stored positions: qq [128] int8 and qe [4] f16 bits = S2 of the
+    rotated query, Kq [n][4][32] int64 and dk [n][4] float64 the stored K quants and scales, V [n][128] float64 the stored V dequantised.
+    Returns (y64 [128], bound [128], tol): the kernel and the oracle are held to |y - y64| <= bound per element"""
+    n = Kq.shape[0]
+    terms = np.einsum("nbi,bi->nb", Kq, qq.reshape(4, 32).astype(np.int64)) * (h2f(qe)[None, :] * dk) / math.sqrt(HD)
+    s = terms.sum(1)
+    e = np.exp(s - s.max())
+    p = e / e.sum()
+    y64, w = p @ V, p @ np.abs(V)
+    tol = tol_q8(n, s, np.abs(terms).sum(1))
+    kept = (s - s.max() >= -86.0).astype(np.float64) @ np.abs(V)          # > 0 where a position the device keeps has v != 0
+    bound = np.where(kept > 0, tol * w, FLUSH * np.abs(V).sum(0))
+    return y64, bound, tol
 
 
 # ---------------- paged layout ----------------

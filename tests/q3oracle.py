@@ -76,6 +76,11 @@ def lib():
                                     C.c_void_p]
         L.q3o_attn_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.q3o_attn_head_ggml.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.q3o_attn_head_q8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]
+        L.q3o_model_set_kv_type.restype = C.c_int
+        L.q3o_model_set_kv_type.argtypes = [C.c_void_p, C.c_int]
+        L.q3o_engine_set_kv_type.restype = C.c_int
+        L.q3o_engine_set_kv_type.argtypes = [C.c_void_p, C.c_int]
         L.q3o_sumsq_vec.restype = C.c_float
         L.q3o_sumsq_vec.argtypes = [C.c_void_p, C.c_int64]
         L.q3o_gguf_open.restype = C.c_void_p
@@ -161,12 +166,26 @@ class Assets:
         return out[:n].copy()
 
 
+KV_TYPES = {"f16": 1, "q8_0": 8}   # ggml's type ids, as the product's
+
+
+def _kv_type_result(rc, kv_type):
+    if rc:
+        raise RuntimeError("Q3_SPEC=ggml has no KV cache type Q8_0" if rc == -2 else "unknown KV cache type %r" % (kv_type,))
+
+
 class Model:
-    def __init__(self, path, n_ctx=4096):
+    def __init__(self, path, n_ctx=4096, kv_type=None):
+        """kv_type: None = the F16 cache; "f16" / "q8_0" (or a type id) = that KV cache type (spec "KV cache type Q8_0")"""
         err = C.create_string_buffer(256)
         self.h = lib().q3o_model_load(path.encode(), n_ctx, err, 256)
         if not self.h:
             raise RuntimeError(err.value.decode())
+        if kv_type is not None:
+            rc = lib().q3o_model_set_kv_type(self.h, KV_TYPES.get(kv_type, kv_type))
+            if rc:
+                self.close()
+            _kv_type_result(rc, kv_type)
 
     def close(self):
         if self.h:
@@ -188,11 +207,17 @@ class Model:
 
 
 class Engine:
-    def __init__(self, quant_dir, codec_path=None, n_threads=0):
+    def __init__(self, quant_dir, codec_path=None, n_threads=0, kv_type=None):
+        """kv_type: the talker's KV cache type as Model's; the predictor keeps F16"""
         err = C.create_string_buffer(256)
         self.h = lib().q3o_engine_create(quant_dir.encode(), (codec_path or "").encode(), n_threads, err, 256)
         if not self.h:
             raise RuntimeError(err.value.decode())
+        if kv_type is not None:
+            rc = lib().q3o_engine_set_kv_type(self.h, KV_TYPES.get(kv_type, kv_type))
+            if rc:
+                self.close()
+            _kv_type_result(rc, kv_type)
         self.s = EngineStruct.from_address(self.h)
         self.assets = Assets.borrow(self.s.assets)
 
@@ -319,6 +344,19 @@ def attn_head(q, K, V, ggml=False):
     out = np.zeros(128, np.float32)
     fn = lib().q3o_attn_head_ggml if ggml else lib().q3o_attn_head
     fn(_p(q), _p(K), _p(V), 128, K.shape[0], _p(out))
+    return out
+
+
+def attn_head_q8(q, Kq, Ks, Vq, Vs):
+    """spec "KV cache type Q8_0": one query head q[128] f32 against n cached positions, Kq, Vq [n][128] int8 and Ks, Vs [n][4] f16 bit
+    patterns (uint16), in logical order"""
+    q = np.ascontiguousarray(q, np.float32)
+    Kq, Vq = (np.ascontiguousarray(a, np.int8) for a in (Kq, Vq))
+    Ks, Vs = (np.ascontiguousarray(a, np.uint16) for a in (Ks, Vs))
+    n = Kq.shape[0]
+    assert Kq.shape == Vq.shape == (n, 128) and Ks.shape == Vs.shape == (n, 4)
+    out = np.zeros(128, np.float32)
+    lib().q3o_attn_head_q8(_p(q), _p(Kq), _p(Ks), _p(Vq), _p(Vs), 128, 4, n, _p(out))
     return out
 
 

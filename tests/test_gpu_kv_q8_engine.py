@@ -1,7 +1,8 @@
 """[EXT] KV cache type Q8_0 through the engine (q3tts_engine_create_kv, Engine(kv_type="q8_0")) on the tiny synthetic model: a request's
 codes depend on its prompt, seed and options alone -- not on what runs beside it, on how its prefill wave was shared, or on whether its
 pages came from a fork (k_kv_fork), a stem store (k_kv_stem) or its own prefill -- and resume continues the straight run.  The F16 type is
-the plain engine.  No threshold on Q8_0-against-F16 agreement: it is a quantisation effect and is only printed.  (-m gpu)"""
+the plain engine.  These are invariances; the values themselves are pinned to the oracle bit for bit in tests/test_gpu_kv_q8_parity.py and,
+here, in test_both_types_side_by_side.  No threshold on Q8_0-against-F16 agreement: it is a quantisation effect and is only printed.  (-m gpu)"""
 import os
 
 import numpy as np
@@ -83,13 +84,19 @@ def test_resume_at_5(q8, vivian):
     assert np.array_equal(run(q8, p, 900, prefix_codes=want[:5]), want)
 
 
-def test_both_types_side_by_side(gpu, q8, tiny_model, vivian):
-    """an F16 engine beside the Q8_0 one: both run; F16 through create_kv is the plain engine, bit for bit"""
+def test_both_types_side_by_side(gpu, oracle, q8, tiny_model, vivian):
+    """an F16 engine beside the Q8_0 one: each equals the oracle with its cache type (the decode crosses slot 64); F16 through create_kv
+    is the plain engine, bit for bit"""
     f16 = gpu.Engine(tiny_model, "q8_0", max_batch=4, max_steps=40, load_codec=False, kv_type="f16")
     plain = gpu.Engine(tiny_model, "q8_0", max_batch=4, max_steps=40, load_codec=False)
     p = prompt(q8, vivian, 60, 40)
     a, b, c = (codes(e, [e.submit(p, max_steps=32, seed=1, mask_eos=True)])[0] for e in (q8, f16, plain))
     assert a.shape == b.shape == (32, 16) and np.array_equal(b, c)
+    for got, kv_type in ((a, "q8_0"), (b, "f16")):
+        oe = oracle.Engine(os.path.join(tiny_model, "gguf_q8_0"), None, 4, kv_type=kv_type)
+        want, _ = oe.generate(p, max_steps=32, mask_eos=True)
+        oe.close()
+        assert np.array_equal(got, want), kv_type
     print("greedy code_0 equal in %d of 32 frames between the Q8_0 and the F16 cache" % int((a[:, 0] == b[:, 0]).sum()))
     f16.close()
     plain.close()

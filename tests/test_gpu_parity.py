@@ -809,6 +809,16 @@ def test_llama_abi_replay_matches_oracle(gpu, oracle, tiny_model, vivian, tmp_pa
     got = np.fromfile(cf, np.int32).reshape(-1, 16)
     assert np.array_equal(got, oc)
     assert "timing prefill_ms" in r.stdout   # the zero-Rust-change path reports its own plumbing cost (scripts/replay_fullsize.sh for the full model)
+    # the talker context's type_k / type_v: 8, 8 is the Q8_0 KV cache and equals the Q8_0 oracle; every other pair keeps the f16 cache
+    oq = oracle.Engine(os.path.join(tiny_model, "gguf_q8_0"), None, 4, kv_type="q8_0")
+    oc_q8, _ = oq.generate(prompt, max_steps=6, mask_eos=True)
+    oq.close()
+    assert not np.array_equal(oc_q8, oc)      # (the two oracles disagree on this prompt, so each run below tells the types apart)
+    for tk, tv, want in (("8", "8", oc_q8), ("8", "1", oc)):
+        rk = subprocess.run([os.path.join(pkg, "ref_replay"), os.path.join(tiny_model, "gguf_q8_0"), pf, str(prompt.shape[0]), "6", cf, "1", tk, tv],
+                            cwd=pkg, capture_output=True, text=True)    # a fresh child process per run
+        assert rk.returncode == 0, rk.stderr[-1500:]
+        assert np.array_equal(np.fromfile(cf, np.int32).reshape(-1, 16), want), (tk, tv)
     # prompt longer than the batch's pos allocation / 4 (reference quirk 3): the shim must not read past the n_tokens ints the caller owns
     long_prompt = np.repeat(prompt, 100, axis=0)[:1100]
     long_prompt.tofile(pf)
