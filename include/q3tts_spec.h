@@ -680,6 +680,21 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
  * The Q3_K_M mix q3synth writes (attn_q, attn_k, ffn_gate, ffn_up Q3_K; attn_v Q5_K in layers 0 and 1, else Q4_K; attn_output Q4_K; ffn_down
  * Q5_K below n_layer / 16, else Q4_K; output / head tensors Q6_K) is llama.cpp's as remembered [EXT, unpinned]. */
 
+/* ---------------- S3, K-quant rows: IQ4_XS [EXT] ----------------
+ * IQ4_XS super-block (136 bytes, 256 weights) [EXT, restated, unpinned: from the public ggml format, neither ggml source nor the gguf Python
+ * package was at hand; no real IQ4_XS file has been through the engine]: {f16 d, u16 scales_h, u8 scales_l[4], u8 qs[128]}.
+ * Block b of 32 (b = 0..7) has one 6-bit scale, ls_b = ((scales_l[b/2] >> 4*(b%2)) & 15) | (((scales_h >> 2*b) & 3) << 4), s_b = ls_b - 32 in
+ * [-32, 31], and its nibbles index a table of 16 int8 levels, kv = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}:
+ *   w[32b + j] = d * s_b * kv[qs[16b + j] & 15],   w[32b + 16 + j] = d * s_b * kv[qs[16b + j] >> 4],   j = 0..15.
+ * There is no min term.  An IQ4_XS row IS the Q6_K row with the same d, the i8 sub-block scales s_b, s_b (one scale for both halves of a
+ * block) and the quants kv[.]: per (row, activation block b with int8 xq and f16 scale dx_b)
+ *   I_b = sum_j kv[q_j] * xq_j (exact int32),   a = d * (float)(s_b * I_b),   acc = fma(a, dx_b, acc),
+ * the blocks in ascending k exactly as the Q6_K chain takes them, with the same segment order, super-segment slabs, nparts split and lane and
+ * wave reductions.  |s_b * I_b| <= 32 * 32 * 127 * 127 = 16 516 096 < 2^24, so the int-to-float conversion is exact at every input.
+ * Nothing else of S3 changes.  The oracle has no twin of this type; the kernels are held to a float64 decode of this paragraph
+ * (tests/test_gpu_iq4xs.py).  The mix q3synth writes for --quant iq4_xs (attn_q, attn_k, attn_output, ffn_gate, ffn_up, ffn_down IQ4_XS;
+ * attn_v Q5_K; output / head tensors Q6_K) is llama.cpp's as remembered [EXT, unpinned]. */
+
 /* ---------------- KV cache type Q8_0 [EXT] (q3tts_kv_layout, q3tts_op_attention_q8kv) ----------------
  * The talker's K and V rows kept as int8 blocks of 32 with f16 scales (ggml's -ctk q8_0 -ctv q8_0) instead of f16.  A bit-exact item
  * against the oracle: the text below is a complete, ordered restatement, q3o_attn_head_q8 and the oracle model's Q8_0 cache type are written
@@ -708,7 +723,7 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
 
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
-    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q3_K = 11, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_BF16 = 30
+    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q8_0 = 8, Q3_T_Q3_K = 11, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_IQ4_XS = 23, Q3_T_BF16 = 30
 };
 
 #endif /* Q3TTS_SPEC_H */

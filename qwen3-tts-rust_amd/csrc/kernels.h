@@ -32,6 +32,9 @@ struct Q8Mat {
     // = 0.375 / 0.5 / 0.625 / 0.75 B per weight (+ 0.125 of scales and metadata), against 1.125 for the int8 planes round 1 expanded them to.
     // Metadata: one 16-B vector per (row, segment): Q4_K, Q5_K = {sc[8], m[8]} u8 with d,dmin in sc[0..1]; Q6_K, Q3_K = 16 i8 sub-block scales with d in sc[0]
     // (Q3_K: the 6-bit codes of the file minus 32, unpacked at load).
+    // IQ4_XS (ggml type 23) is the nibble plane alone like Q4_K, 4096 B, but its nibbles are indices into the 16 int8 levels of spec S3; the
+    // kernels turn them into int8 operands with byte permutes (wslice.h).  Metadata: the 8 block scales ls - 32 as i8 in bytes 0..7 (unpacked
+    // at load), bytes 8..15 zero, d in sc[0].
     const uint8_t* rg_type = nullptr;   // [Npad/32], null => all Q8_0 (uniform 1-KiB tiles)
     const uint32_t* rg_off = nullptr;   // [Npad/32] offset of the row group's quants from qs in 16-B units (K-quant matrices only)
     const uint8_t* meta = nullptr;      // [N/32][K/256][32 rows][16 B]
@@ -240,7 +243,7 @@ bool prefill_wide(); // Q3_PREFILL_WIDE != 0 (the default): prompt chunks of 512
 struct LinearPlanIn {
     int op = LOP_GEMV;
     int K = 0, row0 = 0, nrows = 0, ntok = 0, ff = 0;
-    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 8 / 11 / 12 / 13 / 14 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
+    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 8 / 11 / 12 / 13 / 14 / 23 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
     bool kq = false;      // quantised matrix built from K-quant-file tensors (Q8Mat::rg_type != null)
     int kq_parts = 0;     // Q8Mat::nparts
     bool has_wt = false;  // float: the tiled copy exists

@@ -148,6 +148,7 @@ bool prefill_wide() { const char* e = std::getenv("Q3_PREFILL_WIDE"); return !(e
 //   Q4_K: the Q5_K line; the weights are the nibbles alone
 //   Q6_K: acc = fma(d*f(sc0*isum_lo + sc1*isum_hi), dx, acc)        (the two 16-element halves are the sub-blocks)
 //   Q3_K: the Q6_K line; the weights are 3-bit values unpacked to int8 q (Q3_K_M files: q, k, gate, up)
+//   IQ4_XS: acc = fma(d*f(s*isum), dx, acc)   one scale per block; the weights are the int8 levels the nibbles index (IQ4_XS files: all but v and the heads)
 // =====================================================================================================
 template <int LPR, int MT, int TS>
 __global__ void __launch_bounds__(512) k_gemv_kq(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq,
@@ -996,6 +997,8 @@ __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_tile1(Q8Mat w, int row0, int nrows, 
 //         other half's lanes of B zeroed; stored values are q + 32, so idot_x = (stored dot) - 32 * xsum_x (two more MFMAs against half-ones tiles)
 //   Q3_K  the Q6_K line, two MFMAs per block: the B operand is the 2-bit word merged with its plane bits and sign-extended to int8 q (wslice.h),
 //         so the stored dot IS idot_x and no half-ones tile is multiplied
+//   IQ4_XS  acc = fma(d * f(s_b * idot), dx, acc)   one MFMA per block: the B operand is the nibbles looked up in the level table (wslice.h, iq4_lut4),
+//         a block has one scale for both halves and no offset, so neither a half-zeroed tile nor an ones tile is multiplied
 // d, dmin, sc_b, m_b belong to the lane's weight row (C column); dx[token, block] comes, as in the Q8_0 kernel, from the f32 matrix pipe: an outer
 // product with 1.0 lays the activation scales of two blocks out in the C layout.  Built for 2 waves per SIMD (the extra accumulators do not fit 128 VGPRs).
 // Before this kernel the batched path of a Q5_K_M file swept the weights once per 8 tokens (k_gemv_kq z tiles): C3 247 audio-s/s against 620 on Q8_0.
@@ -1020,6 +1023,7 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
         constexpr int WT = decltype(tag)::value;
         constexpr bool Q5 = WT == Q3_T_Q5_K || WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, Q6 = WT == Q3_T_Q6_K || Q3; // (Q4_K runs the Q5_K chain on its 4-bit operand, Q3_K the Q6_K chain on its 3-bit one)
         constexpr int SUBOFF = WSlice<2, WT>::SUBOFF;
+        constexpr bool IQ = WT == Q3_T_IQ4_XS;
 #pragma unroll 1
         for (int q = 0; q < NM; q++) {
             WSlice<2, WT> ws;
@@ -1065,6 +1069,15 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
                                     const int i1 = __mul24(scb, c[g]), i2v = __mul24(mb, cx[g]); // |idot| <= 32 * 31 * 127 (Q4_K: 32 * 15 * 127) and the 6-bit scales fit v_mul_i32_i24 (full rate; v_mul_lo_u32 is quarter rate)
                                     const float diff = kq_block_term<WT == Q3_T_Q4_K>(d0, i1, d1, i2v);
                                     acc[g] = kq_block_fma<WT == Q3_T_Q4_K>(diff, D[16 * i2 + g], acc[g]);
+                                }
+                            } else if (IQ) {
+                                const i32x16 c = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, wv, z16, 0, 0, 0);
+                                const int sb = (int)(int8_t)ws.mbyte(i);
+#pragma unroll
+                                for (int g = 0; g < 16; g++) {
+                                    const int isum = __mul24(c[g], sb); // |idot| <= 32 * 127 * 127 < 2^23 and |s_b| <= 32: exact in the 24-bit multiplier, |isum| < 2^24
+                                    const float a = kq_block_scale<true>(d0, isum);
+                                    acc[g] = kq_block_fma<true>(a, D[16 * i2 + g], acc[g]);
                                 }
                             } else if (Q6) {
                                 const i32x4v wlo = half ? zero4 : wv, whi = half ? wv : zero4, olo = half ? zero4 : ones, ohi = half ? ones : zero4;

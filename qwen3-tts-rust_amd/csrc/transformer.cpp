@@ -91,6 +91,39 @@ __global__ void k_repack_q4k(const uint8_t* __restrict__ raw, int n, int K, int 
             memcpy(base + h * 256 + w * 4, &word, 4);
         }
 }
+// IQ4_XS super-block {f16 d; u16 scales_h; u8 scales_l[4]; u8 qs[128]} -> the nibble plane alone in Q4_K's word order (4096 B per row group and
+// segment, kernels.h) + d + the 8 block scales as i8, already ls - 32 (no kernel sees the 4 + 2 bit packing).  One thread per (row, segment, block j):
+// weight t of half h of the block is nibble h of qs[16 j + t] -- a table index, carried as it is.
+__global__ void k_repack_iq4xs(const uint8_t* __restrict__ raw, int n, int K, int row_off, uint8_t* __restrict__ qs, const uint32_t* __restrict__ rg_off,
+                               uint16_t* __restrict__ sc, uint8_t* __restrict__ meta) {
+    const int nseg = K >> 8;
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (size_t)n * nseg * 8) return;
+    const int j = (int)(id & 7);
+    const size_t rs = id >> 3;
+    const int r = (int)(rs / nseg), s = (int)(rs % nseg);
+    const uint8_t* blk = raw + rs * 136;
+    const int row = row_off + r, rg = row >> 5, r32 = row & 31;
+    const size_t vidx = ((size_t)rg * nseg + s) * 32 + r32;
+    uint16_t d, sh;
+    memcpy(&d, blk, 2); memcpy(&sh, blk + 2, 2);
+    if (j == 0)
+        for (int i = 0; i < 8; i++) sc[vidx * 8 + i] = i == 0 ? d : 0;
+    const int ls = ((blk[4 + (j >> 1)] >> (4 * (j & 1))) & 15) | (((sh >> (2 * j)) & 3) << 4);
+    meta[vidx * 16 + j] = (uint8_t)(int8_t)(ls - 32);
+    meta[vidx * 16 + 8 + j] = 0;
+    const uint8_t* ql = blk + 8 + 16 * j;
+    uint8_t* base = qs + (size_t)rg_off[rg] * 16 + (size_t)s * 4096 + j * 512 + r32 * 8;
+    for (int h = 0; h < 2; h++)
+        for (int w = 0; w < 2; w++) {
+            uint32_t word = 0; // byte bb = weights 8w + bb (low nibble) and 8w + 4 + bb (high nibble) of half h
+            for (int bb = 0; bb < 4; bb++) {
+                const uint32_t lo = (ql[8 * w + bb] >> (4 * h)) & 0xFu, hi = (ql[8 * w + 4 + bb] >> (4 * h)) & 0xFu;
+                word |= (lo | (hi << 4)) << (8 * bb);
+            }
+            memcpy(base + h * 256 + w * 4, &word, 4);
+        }
+}
 // Q3_K super-block {u8 hmask[32]; u8 qs[64]; u8 scales[12]; f16 d} -> 2-bit plane + bit plane (3072 B per row group and segment, kernels.h; values
 // kept +4, unsigned 3 bit) + d + the 16 sub-block scales as i8, already minus 32 (the Q6_K metadata: no kernel sees the 6-bit packing).
 // One thread per (row, segment, block j): block j = 4h + g is weights 128h + 32g + l, its low bits (qs[32h + l] >> 2g) & 3, its third bit
@@ -190,17 +223,20 @@ Q8Mat build_q8mat(const WLayout& L, const void* const* raw, DevBuf<uint8_t>& blo
         m.p0_off = L.p0_off; m.p1_off = L.p1_off; m.p2_off = L.p2_off;
         if (L.nparts > 1 && std::count(L.rg_type.begin(), L.rg_type.end(), (uint8_t)Q3_T_Q3_K)) // the mixed kernels with the Q3_K body carry the Q4_K and Q5_K ones beside it and no other (wslice_dispatch, TS = -2)
             for (uint8_t ty : L.rg_type) Q3_CHECK(ty == Q3_T_Q3_K || ty == Q3_T_Q4_K || ty == Q3_T_Q5_K, "a fused matrix with Q3_K rows holds Q3_K, Q4_K and Q5_K tensors only");
+        if (L.nparts > 1 && std::count(L.rg_type.begin(), L.rg_type.end(), (uint8_t)Q3_T_IQ4_XS)) // the mixed kernels with the IQ4_XS body carry the Q5_K one beside it and no other (wslice_dispatch, TS = -3)
+            for (uint8_t ty : L.rg_type) Q3_CHECK(ty == Q3_T_IQ4_XS || ty == Q3_T_Q5_K, "a fused matrix with IQ4_XS rows holds IQ4_XS and Q5_K tensors only");
     }
     for (size_t i = 0; i < L.tensors.size(); i++) {
         const WTensor& t = L.tensors[i];
         const size_t raw_bytes = (size_t)t.rows * q3_gguf_row_bytes(t.type, L.K);
         DevBuf<uint8_t> d(raw_bytes);
         d.upload((const uint8_t*)raw[i], raw_bytes);
-        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 || t.type == Q3_T_Q4_K || t.type == Q3_T_Q3_K ? 32 : 256)); // threads: one per block (Q8_0, Q4_K, Q3_K) or super-block
+        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 || t.type == Q3_T_Q4_K || t.type == Q3_T_Q3_K || t.type == Q3_T_IQ4_XS ? 32 : 256)); // threads: one per block (Q8_0, Q4_K, Q3_K, IQ4_XS) or super-block
         const dim3 grid((unsigned)((nblk + 255) / 256));
         // Q8_0 tiles are laid out the same in both layouts: the kernel is based on the tensor's first row group and counts rows from there
         if (t.type == Q3_T_Q8_0) hipLaunchKernelGGL(k_repack_q8, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0 & 31, base + (size_t)L.rg_off[(size_t)(t.row0 / 32)] * 16, sc, t.row0 & ~31);
         else if (t.type == Q3_T_Q3_K) hipLaunchKernelGGL(k_repack_q3k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
+        else if (t.type == Q3_T_IQ4_XS) hipLaunchKernelGGL(k_repack_iq4xs, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else if (t.type == Q3_T_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else if (t.type == Q3_T_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
@@ -213,7 +249,7 @@ Q8Mat kqmat_from_host(const void* const* raw, const int32_t* types, const int32_
     std::vector<WTensor> t;
     int n = 0;
     for (int i = 0; i < nw; i++) { t.push_back({types[i], n, rows[i]}); n += rows[i]; }
-    return build_q8mat(plan_wlayout(t, n, k, true, WL_TYPES_KQ3), raw, storage);
+    return build_q8mat(plan_wlayout(t, n, k, true, WL_TYPES_IQ4), raw, storage);
 }
 
 Q8Mat Transformer::make_mat(const Gguf& g, const std::vector<std::pair<std::string, int>>& rows, int N, int K) {
@@ -221,12 +257,12 @@ Q8Mat Transformer::make_mat(const Gguf& g, const std::vector<std::pair<std::stri
     for (auto& r : rows) {
         const GgufTensor& t = g.need(r.first);
         if (ggml_mode_) Q3_CHECK(gg_type_ok(t.type), "ggml mode: type of " + r.first + ": " + gg_type_msg(t.type)); // before anything is repacked
-        if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q3_K && t.type != Q3_T_Q4_K && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K)
-            throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q3_K, Q4_K, Q5_K, Q6_K)");
+        if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q3_K && t.type != Q3_T_Q4_K && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K && t.type != Q3_T_IQ4_XS)
+            throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS)");
         Q3_CHECK(t.ne[0] == K, "unexpected K for " + r.first);
         tensors.push_back({t.type, r.second, (int)t.ne[1]}); raw.push_back(t.data);
     }
-    const WLayout L = plan_wlayout(tensors, N, K, false, WL_TYPES_KQ3);
+    const WLayout L = plan_wlayout(tensors, N, K, false, WL_TYPES_IQ4);
     blobs_.emplace_back();
     return build_q8mat(L, raw.data(), blobs_.back());
 }

@@ -1,6 +1,6 @@
 // wslice.h -- one lane's slice of a weight matrix for the GEMV family: the quants of (row, 256-segment) this lane multiplies, fetched from
 // the Q8_0 tiles or from the packed K-quant planes (kernels.h), and the block chain of spec S3 that turns them into a partial sum.
-// Shared by k_gemv_kq, k_gemv_q8_norm, and k_gateup_swiglu, so the fused decode path serves Q5_K_M, Q4_K_M and Q3_K_M files with the same
+// Shared by k_gemv_kq, k_gemv_q8_norm, and k_gateup_swiglu, so the fused decode path serves Q5_K_M, Q4_K_M, Q3_K_M and IQ4_XS files with the same
 // launches as Q8_0 files.  The weight type is a TEMPLATE parameter: a kernel reads the type of its row group from the kernel arguments (a
 // scalar) and enters the body compiled for it -- with the type as a run-time value inside one body the compiler merges the three load
 // sequences with selects on loaded data, which parks the wave on the weight stream before the norm prologue (measured: 16 -> 20 us).
@@ -11,6 +11,8 @@
 //   WT = Q6_K     acc = fma(d*f(sc0*isum_lo + sc1*isum_hi), dx, acc)        the two 16-element halves are the sub-blocks; stored values are q + 32
 //   WT = Q3_K     the Q6_K chain on 3-bit values: one 2-bit word and one bit-plane word per 16 weights, i8 scales unpacked at load.  HBM holds
 //                 q + 4 (unsigned); finish() sign-extends to the int8 q itself, so the chain needs no offset term: sum q x comes out of v_dot4 whole
+//   WT = IQ4_XS   the Q6_K chain with one scale for both halves of a block, acc = fma(d*f(s_b*I_b), dx, acc): the nibble plane of Q4_K, but a
+//                 nibble is an index into 16 int8 levels; finish() looks the levels up with byte permutes (iq4_lut4), so v_dot4 gives I_b whole
 #pragma once
 #include <type_traits>
 #include "kdev.h"
@@ -47,7 +49,7 @@ __device__ __forceinline__ float kq_block_fma(float diff, float dx, float acc) {
     return r;
 }
 
-// a = d * f(isum) of the Q6_K / Q3_K chain: plain C++ for Q6_K as ever, one VALU instruction for the Q3_K body (see above)
+// a = d * f(isum) of the Q6_K / Q3_K / IQ4_XS chain: plain C++ for Q6_K as ever, one VALU instruction for the Q3_K and IQ4_XS bodies (see above)
 template <bool SCALAR>
 __device__ __forceinline__ float kq_block_scale(float d0, int isum) {
     if (!SCALAR) return d0 * (float)isum;
@@ -69,6 +71,19 @@ __device__ __forceinline__ uint4 kq_unpack16(uint2 nib, uint32_t h4, uint32_t h5
     return v;
 }
 
+// IQ4_XS: the four 4-bit indices in bits SH..SH+3 of each byte of x -> their four int8 levels, byte for byte.  The table of spec S3 is four dwords,
+// kv[0..3], kv[4..7], kv[8..11], kv[12..15].  v_perm_b32 picks each result byte from the 8 bytes of its two sources by a 3-bit selector, so one
+// permute with idx & 7 reads the lower half of the table and one the upper half, and a third permute takes byte j from the one or the other by
+// bit 3 of index j (selector j, or 4 + j for the upper half).  Three permutes and four bit operations per dword; a select through a byte mask
+// ((b << 8) - b and v_bfi_b32) costs one operation more, a 16-entry LDS table a round trip per dword (DESIGN.md, IQ4_XS weights).
+template <int SH>
+__device__ __forceinline__ uint32_t iq4_lut4(uint32_t x) {
+    const uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u; // -127 -104 -83 -65 | -49 -35 -22 -10 | 1 13 25 38 | 53 69 89 113
+    const uint32_t idx = x >> SH, sel = idx & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(T1, T0, sel), hi = __builtin_amdgcn_perm(T3, T2, sel);
+    return __builtin_amdgcn_perm(hi, lo, 0x03020100u | ((idx & 0x08080808u) >> 1));
+}
+
 // type of row group rg (wave-uniform) from the tensor map in the kernel arguments
 __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
     const int rgs = __builtin_amdgcn_readfirstlane(rg);
@@ -80,10 +95,17 @@ __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
 // need are in the kernel; -2 = mixed with a Q3_K part (fused QKV of a Q3_K_M file: q, k Q3_K and v Q4_K or Q5_K): the Q3_K, Q4_K and Q5_K
 // bodies, which is every mixture build_q8mat lets Q3_K into.  The fifth body has kernels of its own because adding it to the -1 kernels changed
 // their registers (k_gemv_kq<8, *, -1> gained scratch): a Q5_K_M or Q4_K_M file keeps launching exactly the code it launched before Q3_K existed.
+// For the same reason IQ4_XS = a matrix that is all IQ4_XS has its one body, and -3 = mixed with an IQ4_XS part (fused QKV of an IQ4_XS file: q, k
+// IQ4_XS and v Q5_K) has the IQ4_XS and Q5_K bodies and no other: build_q8mat lets IQ4_XS into no other mixture.
 template <int TS, typename F>
 __device__ __forceinline__ void wslice_dispatch(const Q8Mat& w, int rg, F&& body) {
     if (TS >= 0) { body(wt_tag<(TS >= 0 ? TS : 0)>{}); return; }
     const int wt = wslice_type(w, rg);
+    if constexpr (TS == -3) {
+        if (wt == Q3_T_IQ4_XS) body(wt_tag<Q3_T_IQ4_XS>{});
+        else body(wt_tag<Q3_T_Q5_K>{});
+        return;
+    }
     if constexpr (TS == -2) {
         if (wt == Q3_T_Q3_K) body(wt_tag<Q3_T_Q3_K>{});
         else if (wt == Q3_T_Q5_K) body(wt_tag<Q3_T_Q5_K>{});
@@ -97,14 +119,16 @@ __device__ __forceinline__ void wslice_dispatch(const Q8Mat& w, int rg, F&& body
 }
 // host side: the TS of a matrix, and a switch that instantiates its statement once per value (the statement sees `constexpr int TS`)
 inline int wslice_ts(const Q8Mat& w) { return !w.rg_type ? 0 : w.nparts == 1 ? w.p0_type : -1; }
-inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matrices split by whether a part is Q3_K
+inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matrices split by whether a part is Q3_K (-2) or IQ4_XS (-3)
     const int ts = wslice_ts(w);
+    if (ts == -1 && (w.p0_type == Q3_T_IQ4_XS || w.p1_type == Q3_T_IQ4_XS || w.p2_type == Q3_T_IQ4_XS)) return -3;
     return ts == -1 && (w.p0_type == Q3_T_Q3_K || w.p1_type == Q3_T_Q3_K || w.p2_type == Q3_T_Q3_K) ? -2 : ts;
 }
 #define Q3_TS_SWITCH(w, ...) do { switch (wslice_launch_ts(w)) { \
     case 0: { constexpr int TS = 0; __VA_ARGS__; break; } case Q3_T_Q8_0: { constexpr int TS = Q3_T_Q8_0; __VA_ARGS__; break; } \
     case Q3_T_Q3_K: { constexpr int TS = Q3_T_Q3_K; __VA_ARGS__; break; } case Q3_T_Q4_K: { constexpr int TS = Q3_T_Q4_K; __VA_ARGS__; break; } \
     case Q3_T_Q5_K: { constexpr int TS = Q3_T_Q5_K; __VA_ARGS__; break; } case Q3_T_Q6_K: { constexpr int TS = Q3_T_Q6_K; __VA_ARGS__; break; } \
+    case Q3_T_IQ4_XS: { constexpr int TS = Q3_T_IQ4_XS; __VA_ARGS__; break; } case -3: { constexpr int TS = -3; __VA_ARGS__; break; } \
     case -2: { constexpr int TS = -2; __VA_ARGS__; break; } default: { constexpr int TS = -1; __VA_ARGS__; break; } } } while (0)
 
 // LPR lanes share a row: lane = (r, half, bil) with r = lane % R the row inside the workgroup's R = 64 / LPR rows, half = which 16 of a
@@ -112,8 +136,8 @@ inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matric
 template <int LPR, int WT>
 struct WSlice {
     static constexpr int R = 64 / LPR, BPL = LPR / 2, NLD = 8 / BPL;
-    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, KQ = Q4 || Q3 || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
-    static constexpr int SUBOFF = Q3 ? 0 : 32; // Q6_K / Q3_K chain: what the unpacked operand is above q (Q3_K unpacks to q itself)
+    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, IQ = WT == Q3_T_IQ4_XS, KQ = Q4 || Q3 || IQ || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
+    static constexpr int SUBOFF = Q3 || IQ ? 0 : 32; // Q6_K / Q3_K / IQ4_XS chain: what the unpacked operand is above q (Q3_K unpacks to q itself, IQ4_XS to its level)
     uint4 wv[NLD];
     uint4 dwv;          // Q8_0: the 8 block scales; K-quants: d, dmin in halfs 0, 1
     uint4 mv;           // K-quants: 16 metadata bytes of (row, segment)
@@ -133,7 +157,7 @@ struct WSlice {
         const bool in1 = rgs >= w.p1_rg0, in2 = rgs >= w.p2_rg0;
         const uint32_t poff = in2 ? w.p2_off : in1 ? w.p1_off : w.p0_off;
         const int prg0 = in2 ? w.p2_rg0 : in1 ? w.p1_rg0 : 0;
-        constexpr int seg_bytes = Q3 ? 3072 : Q4 ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
+        constexpr int seg_bytes = Q3 ? 3072 : Q4 || IQ ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
         const uint8_t* sbase = w.qs + (size_t)poff * 16 + ((size_t)(rgs - prg0) * nseg + seg) * seg_bytes;
         if (!KQ) {
             const uint8_t* base = sbase + half * 512 + r32 * 16;
@@ -144,7 +168,7 @@ struct WSlice {
         mv = *reinterpret_cast<const uint4*>(w.meta + vidx * 16);
         // packed planes: the raw words park in wv (x, y = nibbles; z, w = bit planes) until finish() -- unpacking here would make the wave
         // wait for the weights before the norm prologue instead of behind it
-        if (Q4) { // nibble words only: no plane row address, no plane word; z, w of wv stay unused
+        if (Q4 || IQ) { // nibble words only: no plane row address, no plane word; z, w of wv stay unused
 #pragma unroll
             for (int i = 0; i < NLD; i++) {
                 const uint2 nib = *reinterpret_cast<const uint2*>(sbase + (i * BPL + bil) * 512 + half * 256 + r32 * 8);
@@ -171,13 +195,18 @@ struct WSlice {
         }
     }
 
-    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3); call once, after the prologue
+    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3; IQ4_XS: signed, the level of the index); call once, after the prologue
     __device__ __forceinline__ void finish(int half) {
         if (!KQ) return;
         if (Q4) { // two masks and a shift per word
             const uint32_t m = 0x0F0F0F0Fu;
 #pragma unroll
             for (int i = 0; i < NLD; i++) wv[i] = make_uint4(wv[i].x & m, (wv[i].x >> 4) & m, wv[i].y & m, (wv[i].y >> 4) & m);
+            return;
+        }
+        if (IQ) { // Q4_K's four dwords in k order, each nibble replaced by its level
+#pragma unroll
+            for (int i = 0; i < NLD; i++) wv[i] = make_uint4(iq4_lut4<0>(wv[i].x), iq4_lut4<4>(wv[i].x), iq4_lut4<0>(wv[i].y), iq4_lut4<4>(wv[i].y));
             return;
         }
         if (Q3) { // four shifts of the 2-bit word give the dwords in k order; plane bit 8b + J belongs to byte b of dword J - 4 half.  The stored
@@ -242,17 +271,18 @@ struct WSlice {
             return acc;
         }
 #pragma unroll
-        for (int i = 0; i < NLD; i++) { // Q6_K, and Q3_K without the offset term
+        for (int i = 0; i < NLD; i++) { // Q6_K, and Q3_K and IQ4_XS without the offset term
             const uint4 xv = *reinterpret_cast<const uint4*>(xseg + (i * BPL + bil) * 32 + half * 16);
             const int bsel = i * BPL + bil; // block of THIS lane's data
             // sum (q - 32) x = sum (stored) x - 32 sum x, exact in int32 (Q3_K: the operand is q, SUBOFF = 0 and the second dot is not compiled); the lane's 16 weights are one sub-block
-            int isum = __mul24(dot16(wv[i], xv) - SUBOFF * dot16(ones, xv), (int)(int8_t)mbyte(2 * bsel + half));
+            // (IQ4_XS: both halves carry the block's one scale s_b, metadata byte bsel, so the lane pair's sum below is s_b * I_b; |dot16| <= 16 * 127 * 127 fits the 24-bit multiplier)
+            int isum = __mul24(dot16(wv[i], xv) - SUBOFF * dot16(ones, xv), (int)(int8_t)mbyte(IQ ? bsel : 2 * bsel + half));
             isum += xor_lane<R>(isum);
-            const float a = kq_block_scale<Q3>(d0, isum);
+            const float a = kq_block_scale<Q3 || IQ>(d0, isum);
 #pragma unroll
             for (int j = 0; j < BPL; j++) {
                 const float aj = (BPL == 1) ? a : __shfl(a, r + 2 * j * R);
-                acc = kq_block_fma<Q3>(aj, h2f(half_of(dxv, i * BPL + j)), acc);
+                acc = kq_block_fma<Q3 || IQ>(aj, h2f(half_of(dxv, i * BPL + j)), acc);
             }
         }
         return acc;

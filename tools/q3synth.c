@@ -4,7 +4,7 @@
  * No real Qwen3-TTS weights exist offline (the reference downloads them at run time,
  * /root/reference/src/download.rs:66-87), so benchmarks and parity tests run on seeded random weights of
  * the same architecture, written in the same container format the reference loads:
- *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_q3_k_m|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
+ *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_q3_k_m|gguf_iq4_xs|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
  *   <out>/onnx/q3tts_codec.gguf        (stand-in for qwen3_tts_decoder.onnx)
  * (directory names: /root/reference/src/tts/engine.rs:91-95,123-124).
  *
@@ -157,6 +157,41 @@ static void enc_q3_k(const float* x, int64_t k, uint8_t* out) {
         }
     }
 }
+/* IQ4_XS {f16 d, u16 scales_h, u8 scales_l[4], u8 qs[128]} (136 bytes, spec S3 [EXT]): per block of 32 the scale max|x| / 113 (the largest level
+ * both signs have) as a 6-bit multiple of d = largest scale / 31, rounded up so that no value is clipped (codes 32..63: this encoder writes no
+ * negative scale), then the nearest of the 16 levels. */
+static const int8_t kv_iq4[16] = { -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 };
+static void enc_iq4_xs(const float* x, int64_t k, uint8_t* out) {
+    for (int64_t s = 0; s < k / 256; s++) {
+        const float* xs = x + 256 * s;
+        uint8_t* blk = out + 136 * s;
+        memset(blk, 0, 136);
+        float scale[8], maxscale = 0;
+        for (int j = 0; j < 8; j++) {
+            float amax = 0;
+            for (int l = 0; l < 32; l++) { float a = fabsf(xs[32 * j + l]); if (a > amax) amax = a; }
+            scale[j] = amax / 113.0f;
+            if (scale[j] > maxscale) maxscale = scale[j];
+        }
+        uint16_t dh = q3_f32_to_f16(maxscale / 31.0f), sh = 0;
+        float d = q3_f16_to_f32(dh);
+        memcpy(blk, &dh, 2);
+        for (int j = 0; j < 8; j++) {
+            int si = d > 0 ? (int)ceilf(scale[j] / d) : 0; if (si > 31) si = 31;
+            int ls = si + 32;
+            blk[4 + j / 2] |= (uint8_t)((ls & 15) << (4 * (j & 1)));
+            sh |= (uint16_t)((ls >> 4) << (2 * j));
+            float de = d * (float)si;
+            for (int l = 0; l < 32; l++) {
+                float v = de > 0 ? xs[32 * j + l] / de : 0;
+                int best = 0;
+                for (int c = 1; c < 16; c++) if (fabsf(v - (float)kv_iq4[c]) < fabsf(v - (float)kv_iq4[best])) best = c;
+                blk[8 + 16 * j + (l & 15)] |= (uint8_t)(best << (4 * (l >> 4)));
+            }
+        }
+        memcpy(blk + 2, &sh, 2);
+    }
+}
 static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
     for (int64_t s = 0; s < k / 256; s++) {
         const float* xs = x + 256 * s;
@@ -195,6 +230,7 @@ static size_t row_bytes(int type, int64_t k) {
         case Q3_T_Q4_K: return (size_t)(k / 256) * 144;
         case Q3_T_Q5_K: return (size_t)(k / 256) * 176;
         case Q3_T_Q6_K: return (size_t)(k / 256) * 210;
+        case Q3_T_IQ4_XS: return (size_t)(k / 256) * 136;
     }
     return 0;
 }
@@ -208,6 +244,7 @@ static void enc_row(int type, const float* x, int64_t k, uint8_t* out) {
         case Q3_T_Q4_K: enc_q4_k(x, k, out); break;
         case Q3_T_Q5_K: enc_q5_k(x, k, out); break;
         case Q3_T_Q6_K: enc_q6_k(x, k, out); break;
+        case Q3_T_IQ4_XS: enc_iq4_xs(x, k, out); break;
     }
 }
 
@@ -333,6 +370,11 @@ static int wtype(const char* quant, const char* kind, int layer, int n_layer) {
         if (!strcmp(kind, "attn_output")) return Q3_T_Q4_K;
         if (!strcmp(kind, "ffn_down")) return layer < n_layer / 16 ? Q3_T_Q5_K : Q3_T_Q4_K;
         return Q3_T_Q3_K;
+    }
+    if (!strcmp(quant, "iq4_xs")) { /* llama.cpp's IQ4_XS mix as remembered [EXT, unpinned] (spec S3) */
+        if (!strcmp(kind, "output")) return Q3_T_Q6_K;
+        if (!strcmp(kind, "attn_v")) return Q3_T_Q5_K;
+        return Q3_T_IQ4_XS;
     }
     fprintf(stderr, "unknown quant %s\n", quant);
     exit(2);
@@ -484,7 +526,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--what") && i + 1 < argc) what = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--q4k-as-q5k")) g_q4k_as_q5k = 1;
         else if (!strcmp(argv[i], "--q3k-as-q6k")) g_q3k_as_q6k = 1;
-        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|q3_k_m|bf16|f16|f32] [--q4k-as-q5k] [--q3k-as-q6k] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
+        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|q3_k_m|iq4_xs|bf16|f16|f32] [--q4k-as-q5k] [--q3k-as-q6k] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
     }
     if (!out) { fprintf(stderr, "--out required\n"); return 2; }
     if (g_q4k_as_q5k && strcmp(quant, "q4_k_m") && strcmp(quant, "q3_k_m")) { fprintf(stderr, "--q4k-as-q5k goes with --quant q4_k_m or q3_k_m\n"); return 2; }
@@ -502,7 +544,7 @@ int main(int argc, char** argv) {
         pred = (tfcfg){ 256, 2, 2, 1, 512, 30720, 0 };
         codec = (ccfg){ 64, 32, 2, 2, 32, 128, 8, 256, 2, 4, { 2, 2 }, { 8, 5, 4, 3 } };
     } else { fprintf(stderr, "unknown preset\n"); return 2; }
-    const char* qdir = !strcmp(quant, "q8_0") ? "gguf_q8_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") || g_q3k_as_q6k ? "gguf_q4_k_m" : !strcmp(quant, "q3_k_m") ? "gguf_q3_k_m" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
+    const char* qdir = !strcmp(quant, "q8_0") ? "gguf_q8_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") || g_q3k_as_q6k ? "gguf_q4_k_m" : !strcmp(quant, "q3_k_m") ? "gguf_q3_k_m" : !strcmp(quant, "iq4_xs") ? "gguf_iq4_xs" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
     char p[1024];
     mkdir(out, 0755);
     snprintf(p, sizeof(p), "%s/%s", out, qdir); mkdir(p, 0755);
