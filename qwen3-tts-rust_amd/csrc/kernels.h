@@ -35,6 +35,8 @@ struct Q8Mat {
     // IQ4_XS (ggml type 23) is the nibble plane alone like Q4_K, 4096 B, but its nibbles are indices into the 16 int8 levels of spec S3; the
     // kernels turn them into int8 operands with byte permutes (wslice.h).  Metadata: the 8 block scales ls - 32 as i8 in bytes 0..7 (unpacked
     // at load), bytes 8..15 zero, d in sc[0].
+    // Q4_0 (ggml type 2) is the same nibble plane, 4096 B, nibble = q + 8; the kernels subtract the 8 inside each byte (wslice.h).  Its 8 f16 block
+    // scales of (row, segment) are sc[0..7], where a Q8_0 row group keeps them; it has no metadata.
     const uint8_t* rg_type = nullptr;   // [Npad/32], null => all Q8_0 (uniform 1-KiB tiles)
     const uint32_t* rg_off = nullptr;   // [Npad/32] offset of the row group's quants from qs in 16-B units (K-quant matrices only)
     const uint8_t* meta = nullptr;      // [N/32][K/256][32 rows][16 B]
@@ -243,7 +245,7 @@ bool prefill_wide(); // Q3_PREFILL_WIDE != 0 (the default): prompt chunks of 512
 struct LinearPlanIn {
     int op = LOP_GEMV;
     int K = 0, row0 = 0, nrows = 0, ntok = 0, ff = 0;
-    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 8 / 11 / 12 / 13 / 14 / 23 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
+    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 2 / 8 / 11 / 12 / 13 / 14 / 23 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
     bool kq = false;      // quantised matrix built from K-quant-file tensors (Q8Mat::rg_type != null)
     int kq_parts = 0;     // Q8Mat::nparts
     bool has_wt = false;  // float: the tiled copy exists

@@ -13,6 +13,9 @@
 //                 q + 4 (unsigned); finish() sign-extends to the int8 q itself, so the chain needs no offset term: sum q x comes out of v_dot4 whole
 //   WT = IQ4_XS   the Q6_K chain with one scale for both halves of a block, acc = fma(d*f(s_b*I_b), dx, acc): the nibble plane of Q4_K, but a
 //                 nibble is an index into 16 int8 levels; finish() looks the levels up with byte permutes (iq4_lut4), so v_dot4 gives I_b whole
+//   WT = Q4_0     the Q8_0 chain on 4-bit values, acc = fma(f(I_b), dw*dx, acc): the nibble plane of Q4_K with nibble = q + 8 and the f16 block
+//                 scales where a Q8_0 row group keeps them; finish() subtracts the 8 inside each byte (q40_sign4), so v_dot4 gives I_b whole and
+//                 the bits are those of the Q8_0 body on the twin rows {d, int8 q}
 #pragma once
 #include <type_traits>
 #include "kdev.h"
@@ -84,6 +87,22 @@ __device__ __forceinline__ uint32_t iq4_lut4(uint32_t x) {
     return __builtin_amdgcn_perm(hi, lo, 0x03020100u | ((idx & 0x08080808u) >> 1));
 }
 
+// Q4_0: the four nibbles u = q + 8 in bits SH..SH+3 of each byte of x -> the four int8 q = u - 8, byte for byte.  With bit 7 of every byte set the
+// subtraction of 8 cannot borrow from the next byte (0x80 + u - 8 >= 0x78), and flipping bit 7 back leaves u - 8 mod 256.  The compiler folds the or and the subtraction into one add of 0x78 per byte:
+// v_and_b32, v_add_u32, v_xor_b32, after one shift for the high nibbles -- 3.5 instructions per four weights (read in k_gemv_kq<4, 1, 2>), paid once per launch whatever the token count.  Keeping the
+// nibbles unsigned and subtracting 8 * sum x (the Q6_K route) costs 1.5 here but a second dot16, a lane exchange and a multiply-subtract per block
+// and TOKEN, and a ones tile on the matrix cores; iq4_lut4 with a linear table costs 7 (DESIGN.md, Q4_0 weights).
+template <int SH>
+__device__ __forceinline__ uint32_t q40_sign4(uint32_t x) {
+    return ((((x >> SH) & 0x0F0F0F0Fu) | 0x80808080u) - 0x08080808u) ^ 0x80808080u;
+}
+// the two f32 steps of the Q8_0 chain as one VALU instruction each (kq_block_term's precaution, for the Q4_0 body): sc = dw * dx
+__device__ __forceinline__ float q40_scale(float dw, float dx) {
+    float s;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(s) : "v"(dw), "v"(dx));
+    return s;
+}
+
 // type of row group rg (wave-uniform) from the tensor map in the kernel arguments
 __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
     const int rgs = __builtin_amdgcn_readfirstlane(rg);
@@ -96,7 +115,8 @@ __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
 // bodies, which is every mixture build_q8mat lets Q3_K into.  The fifth body has kernels of its own because adding it to the -1 kernels changed
 // their registers (k_gemv_kq<8, *, -1> gained scratch): a Q5_K_M or Q4_K_M file keeps launching exactly the code it launched before Q3_K existed.
 // For the same reason IQ4_XS = a matrix that is all IQ4_XS has its one body, and -3 = mixed with an IQ4_XS part (fused QKV of an IQ4_XS file: q, k
-// IQ4_XS and v Q5_K) has the IQ4_XS and Q5_K bodies and no other: build_q8mat lets IQ4_XS into no other mixture.
+// IQ4_XS and v Q5_K) has the IQ4_XS and Q5_K bodies and no other: build_q8mat lets IQ4_XS into no other mixture.  Q4_0 = a matrix that is all Q4_0
+// has its one body; a Q4_0 file's q, k, v are all Q4_0, so there is no mixed value with a Q4_0 part and plan_wlayout refuses such a matrix.
 template <int TS, typename F>
 __device__ __forceinline__ void wslice_dispatch(const Q8Mat& w, int rg, F&& body) {
     if (TS >= 0) { body(wt_tag<(TS >= 0 ? TS : 0)>{}); return; }
@@ -128,6 +148,7 @@ inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matric
     case 0: { constexpr int TS = 0; __VA_ARGS__; break; } case Q3_T_Q8_0: { constexpr int TS = Q3_T_Q8_0; __VA_ARGS__; break; } \
     case Q3_T_Q3_K: { constexpr int TS = Q3_T_Q3_K; __VA_ARGS__; break; } case Q3_T_Q4_K: { constexpr int TS = Q3_T_Q4_K; __VA_ARGS__; break; } \
     case Q3_T_Q5_K: { constexpr int TS = Q3_T_Q5_K; __VA_ARGS__; break; } case Q3_T_Q6_K: { constexpr int TS = Q3_T_Q6_K; __VA_ARGS__; break; } \
+    case Q3_T_Q4_0: { constexpr int TS = Q3_T_Q4_0; __VA_ARGS__; break; } \
     case Q3_T_IQ4_XS: { constexpr int TS = Q3_T_IQ4_XS; __VA_ARGS__; break; } case -3: { constexpr int TS = -3; __VA_ARGS__; break; } \
     case -2: { constexpr int TS = -2; __VA_ARGS__; break; } default: { constexpr int TS = -1; __VA_ARGS__; break; } } } while (0)
 
@@ -136,10 +157,10 @@ inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matric
 template <int LPR, int WT>
 struct WSlice {
     static constexpr int R = 64 / LPR, BPL = LPR / 2, NLD = 8 / BPL;
-    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, IQ = WT == Q3_T_IQ4_XS, KQ = Q4 || Q3 || IQ || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
+    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, IQ = WT == Q3_T_IQ4_XS, Q40 = WT == Q3_T_Q4_0, KQ = Q4 || Q3 || IQ || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
     static constexpr int SUBOFF = Q3 || IQ ? 0 : 32; // Q6_K / Q3_K / IQ4_XS chain: what the unpacked operand is above q (Q3_K unpacks to q itself, IQ4_XS to its level)
     uint4 wv[NLD];
-    uint4 dwv;          // Q8_0: the 8 block scales; K-quants: d, dmin in halfs 0, 1
+    uint4 dwv;          // Q8_0, Q4_0: the 8 block scales; K-quants: d, dmin in halfs 0, 1
     uint4 mv;           // K-quants: 16 metadata bytes of (row, segment)
 
     // issue the loads; the R <= 32 rows of a wave sit in one 32-row group, so the group's base address is a scalar
@@ -157,8 +178,16 @@ struct WSlice {
         const bool in1 = rgs >= w.p1_rg0, in2 = rgs >= w.p2_rg0;
         const uint32_t poff = in2 ? w.p2_off : in1 ? w.p1_off : w.p0_off;
         const int prg0 = in2 ? w.p2_rg0 : in1 ? w.p1_rg0 : 0;
-        constexpr int seg_bytes = Q3 ? 3072 : Q4 || IQ ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
+        constexpr int seg_bytes = Q3 ? 3072 : Q4 || IQ || Q40 ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
         const uint8_t* sbase = w.qs + (size_t)poff * 16 + ((size_t)(rgs - prg0) * nseg + seg) * seg_bytes;
+        if (Q40) { // Q4_K's nibble words; the block scales are in dwv already and no metadata is fetched
+#pragma unroll
+            for (int i = 0; i < NLD; i++) {
+                const uint2 nib = *reinterpret_cast<const uint2*>(sbase + (i * BPL + bil) * 512 + half * 256 + r32 * 8);
+                wv[i].x = nib.x; wv[i].y = nib.y;
+            }
+            return;
+        }
         if (!KQ) {
             const uint8_t* base = sbase + half * 512 + r32 * 16;
 #pragma unroll
@@ -195,8 +224,13 @@ struct WSlice {
         }
     }
 
-    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3; IQ4_XS: signed, the level of the index); call once, after the prologue
+    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3; IQ4_XS: signed, the level of the index; Q4_0: signed, q in -8..7); call once, after the prologue
     __device__ __forceinline__ void finish(int half) {
+        if (Q40) { // Q4_K's four dwords in k order, each nibble minus 8
+#pragma unroll
+            for (int i = 0; i < NLD; i++) wv[i] = make_uint4(q40_sign4<0>(wv[i].x), q40_sign4<4>(wv[i].x), q40_sign4<0>(wv[i].y), q40_sign4<4>(wv[i].y));
+            return;
+        }
         if (!KQ) return;
         if (Q4) { // two masks and a shift per word
             const uint32_t m = 0x0F0F0F0Fu;
@@ -244,6 +278,7 @@ struct WSlice {
                 for (int j = 0; j < BPL; j++) {
                     const int isj = (BPL == 1) ? isum : __shfl(isum, r + 2 * j * R);
                     const int b = i * BPL + j;
+                    if (Q40) { acc = kq_block_fma<true>((float)isj, q40_scale(h2f(half_of(dwv, b)), h2f(half_of(dxv, b))), acc); continue; } // the two statements below, one instruction each
                     const float sc = h2f(half_of(dwv, b)) * h2f(half_of(dxv, b));
                     acc = q3_fmaf((float)isj, sc, acc);
                 }
