@@ -706,6 +706,17 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
  * no dmin.  Every result is held bit for bit to the oracle's Q8_0 arithmetic on the twin (tests/test_gpu_q40.py).  A Q4_0 file as q3synth
  * writes it (--quant q4_0) has every layer matrix Q4_0 and the output / head tensors Q6_K. */
 
+/* ---------------- S3, Q5_0 rows [EXT] ----------------
+ * Q5_0 block (22 bytes, 32 weights, ggml type 6) [EXT, the public ggml format]: {f16 d, u8 qh[4], u8 qs[16]}, qh a little-endian u32.  Weight j
+ * (j = 0..15) is u = (qs[j] & 15) | ((qh >> j) & 1) << 4, weight j + 16 is u = (qs[j] >> 4) | ((qh >> (j + 16)) & 1) << 4, and w = d * (u - 16).
+ * The signed value q = u - 16 lies in -16..15, an int8, so the block {d, int8 q[32]} is a Q8_0 block with the same decoded weights (its twin),
+ * and a Q5_0 row IS its twin Q8_0 row: the Q8_0 chain of S3 unchanged,
+ *   I_b = sum_j q_j * xq_j (exact int32),   acc = fma(f(I_b), dw_b * dx_b, acc),
+ * with the same order of blocks, segments and super-segment slabs and the same lane and wave reductions.  |I_b| <= 32 * 16 * 127 = 65 024 < 2^24,
+ * so the conversion is exact.  There is no offset term, no sub-block scale and no dmin.  Every result is held bit for bit to the oracle's Q8_0
+ * arithmetic on the twin (tests/test_gpu_q50.py).  A Q5_0 file as q3synth writes it (--quant q5_0) has every layer matrix Q5_0 and the output /
+ * head tensors Q6_K. */
+
 /* ---------------- KV cache type Q8_0 [EXT] (q3tts_kv_layout, q3tts_op_attention_q8kv) ----------------
  * The talker's K and V rows kept as int8 blocks of 32 with f16 scales (ggml's -ctk q8_0 -ctv q8_0) instead of f16.  A bit-exact item
  * against the oracle: the text below is a complete, ordered restatement, q3o_attn_head_q8 and the oracle model's Q8_0 cache type are written
@@ -734,7 +745,7 @@ typedef struct { int32_t sample_format, channels, sample_rate, bits; int64_t dat
 
 /* ggml tensor types used by this engine (public GGUF spec [EXT]) */
 enum q3_ggml_type {
-    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q4_0 = 2, Q3_T_Q8_0 = 8, Q3_T_Q3_K = 11, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_IQ4_XS = 23, Q3_T_BF16 = 30
+    Q3_T_F32 = 0, Q3_T_F16 = 1, Q3_T_Q4_0 = 2, Q3_T_Q5_0 = 6, Q3_T_Q8_0 = 8, Q3_T_Q3_K = 11, Q3_T_Q4_K = 12, Q3_T_Q5_K = 13, Q3_T_Q6_K = 14, Q3_T_IQ4_XS = 23, Q3_T_BF16 = 30
 };
 
 #endif /* Q3TTS_SPEC_H */

@@ -242,7 +242,7 @@ static void lin_check(const q3tts_linear_desc& d, const LinearPlan& p) {
         Q3_CHECK(d.nw >= 1 && d.nw <= 3, "1 to 3 weight tensors");
         for (int i = 0; i < d.nw; i++) Q3_CHECK(d.raw[i] && d.rows[i] >= 1, "missing weight tensor");
         if (d.op >= LOP_F_GEMV) Q3_CHECK(d.nw == 1 && (d.type[0] == Q3_T_F32 || d.type[0] == Q3_T_F16 || d.type[0] == Q3_T_BF16), "float ops take one f32 / f16 / bf16 tensor");
-        else if (kq) for (int i = 0; i < d.nw; i++) Q3_CHECK(in_set(d.type[i], {Q3_T_Q8_0, Q3_T_Q3_K, Q3_T_Q4_K, Q3_T_Q5_K, Q3_T_Q6_K, Q3_T_IQ4_XS, Q3_T_Q4_0}) && d.rows[i] % 32 == 0, "K-quant layout: Q8_0 / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_XS / Q4_0 tensors of 32-row multiples");
+        else if (kq) for (int i = 0; i < d.nw; i++) Q3_CHECK(in_set(d.type[i], {Q3_T_Q8_0, Q3_T_Q3_K, Q3_T_Q4_K, Q3_T_Q5_K, Q3_T_Q6_K, Q3_T_IQ4_XS, Q3_T_Q4_0, Q3_T_Q5_0}) && d.rows[i] % 32 == 0, "K-quant layout: Q8_0 / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_XS / Q4_0 / Q5_0 tensors of 32-row multiples");
         Q3_CHECK(d.row0 + d.nrows <= lin_rows(d), "rows past the matrix");
     }
     if (d.op == LOP_GATEUP) Q3_CHECK(K <= 2048, "int8 gate/up: K <= 2048 (k_swiglu_quant reads one super-segment slab)");

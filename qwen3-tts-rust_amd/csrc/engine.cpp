@@ -15,6 +15,7 @@ static std::string quant_dir(const std::string& q) { // engine.rs:91-95 (+ this 
     if (q == "q3_k_m") return "gguf_q3_k_m";
     if (q == "iq4_xs") return "gguf_iq4_xs";
     if (q == "q4_0") return "gguf_q4_0";
+    if (q == "q5_0") return "gguf_q5_0";
     if (q == "q8_0") return "gguf_q8_0";
     if (q == "bf16") return "gguf_bf16";
     if (q == "f16") return "gguf_f16";

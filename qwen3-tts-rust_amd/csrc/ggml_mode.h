@@ -5,9 +5,9 @@
 
 namespace q3 {
 
-// the one type rule of the mode and its message (Q4_K, Q3_K, IQ4_XS and Q4_0 are named: Q4_K_M, Q3_K_M, IQ4_XS and Q4_0 files load in the spec arithmetic only)
+// the one type rule of the mode and its message (Q4_K, Q3_K, IQ4_XS, Q4_0 and Q5_0 are named: Q4_K_M, Q3_K_M, IQ4_XS, Q4_0 and Q5_0 files load in the spec arithmetic only)
 inline bool gg_type_ok(int type) { return type == Q3_T_Q8_0 || type == Q3_T_Q5_K || type == Q3_T_Q6_K; }
-inline std::string gg_type_msg(int type) { return "ggml mode serves Q8_0 / Q5_K / Q6_K matrices, not ggml type " + std::to_string(type) + (type == Q3_T_Q4_K ? " (Q4_K)" : type == Q3_T_Q3_K ? " (Q3_K)" : type == Q3_T_IQ4_XS ? " (IQ4_XS)" : type == Q3_T_Q4_0 ? " (Q4_0)" : ""); }
+inline std::string gg_type_msg(int type) { return "ggml mode serves Q8_0 / Q5_K / Q6_K matrices, not ggml type " + std::to_string(type) + (type == Q3_T_Q4_K ? " (Q4_K)" : type == Q3_T_Q3_K ? " (Q3_K)" : type == Q3_T_IQ4_XS ? " (IQ4_XS)" : type == Q3_T_Q4_0 ? " (Q4_0)" : type == Q3_T_Q5_0 ? " (Q5_0)" : ""); }
 struct GgMat { const uint8_t* p = nullptr; int type = 0, n = 0, k = 0; size_t row_bytes = 0; }; // a GGUF matrix exactly as stored (raw blocks, row-major)
 struct GgAct { int8_t* q8; uint16_t* d8; int8_t* qk; float* dk; int16_t* bs; };                 // activations as Q8_0 (per 32) and Q8_K (per 256) blocks
 

@@ -50,12 +50,13 @@ int64_t GgufValue::as_int(int64_t def) const { return (type >= 0 && type != 8 &&
 double GgufValue::as_float(double def) const { return (type >= 0 && type != 8 && type != 9) ? f : def; }
 
 size_t Gguf::row_bytes(int type, int64_t k) {
-    const int64_t blk = (type == Q3_T_Q8_0 || type == Q3_T_Q4_0) ? 32 : (type == Q3_T_Q3_K || type == Q3_T_Q4_K || type == Q3_T_Q5_K || type == Q3_T_Q6_K || type == Q3_T_IQ4_XS) ? 256 : 1;
+    const int64_t blk = (type == Q3_T_Q8_0 || type == Q3_T_Q4_0 || type == Q3_T_Q5_0) ? 32 : (type == Q3_T_Q3_K || type == Q3_T_Q4_K || type == Q3_T_Q5_K || type == Q3_T_Q6_K || type == Q3_T_IQ4_XS) ? 256 : 1;
     if (k <= 0 || k % blk != 0) return 0; // a partial block would silently truncate the row
     switch (type) {
         case Q3_T_F32: return (size_t)k * 4;
         case Q3_T_F16: case Q3_T_BF16: return (size_t)k * 2;
         case Q3_T_Q4_0: return (size_t)(k / 32) * 18;
+        case Q3_T_Q5_0: return (size_t)(k / 32) * 22;
         case Q3_T_Q8_0: return (size_t)(k / 32) * 34;
         case Q3_T_Q3_K: return (size_t)(k / 256) * 110;
         case Q3_T_Q4_K: return (size_t)(k / 256) * 144;

@@ -37,6 +37,9 @@ struct Q8Mat {
     // at load), bytes 8..15 zero, d in sc[0].
     // Q4_0 (ggml type 2) is the same nibble plane, 4096 B, nibble = q + 8; the kernels subtract the 8 inside each byte (wslice.h).  Its 8 f16 block
     // scales of (row, segment) are sc[0..7], where a Q8_0 row group keeps them; it has no metadata.
+    // Q5_0 (ggml type 6) is Q5_K's two planes, 5120 B: the nibble plane holds the low four bits of u = q + 16 in Q4_K's word order, the high plane
+    // [32 rows][8 blocks][4 B] its bit 4 as the file has it (set = u >= 16), bit 8b + J of a block's word for weight 4J + b.  The kernels pick each
+    // byte's high nibble from that bit (wslice.h, q50_sign16).  Its 8 f16 block scales are sc[0..7] as for Q4_0; its metadata exists and is not read.
     const uint8_t* rg_type = nullptr;   // [Npad/32], null => all Q8_0 (uniform 1-KiB tiles)
     const uint32_t* rg_off = nullptr;   // [Npad/32] offset of the row group's quants from qs in 16-B units (K-quant matrices only)
     const uint8_t* meta = nullptr;      // [N/32][K/256][32 rows][16 B]
@@ -245,7 +248,7 @@ bool prefill_wide(); // Q3_PREFILL_WIDE != 0 (the default): prompt chunks of 512
 struct LinearPlanIn {
     int op = LOP_GEMV;
     int K = 0, row0 = 0, nrows = 0, ntok = 0, ff = 0;
-    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 2 / 8 / 11 / 12 / 13 / 14 / 23 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
+    int wts = 0;          // quantised: wslice_ts of the matrix (0 = all Q8_0, 2 / 6 / 8 / 11 / 12 / 13 / 14 / 23 = one K-quant-file type, -1 = mixed); float: 0 / 1 / 30
     bool kq = false;      // quantised matrix built from K-quant-file tensors (Q8Mat::rg_type != null)
     int kq_parts = 0;     // Q8Mat::nparts
     bool has_wt = false;  // float: the tiled copy exists

@@ -150,6 +150,7 @@ bool prefill_wide() { const char* e = std::getenv("Q3_PREFILL_WIDE"); return !(e
 //   Q3_K: the Q6_K line; the weights are 3-bit values unpacked to int8 q (Q3_K_M files: q, k, gate, up)
 //   IQ4_XS: acc = fma(d*f(s*isum), dx, acc)   one scale per block; the weights are the int8 levels the nibbles index (IQ4_XS files: all but v and the heads)
 //   Q4_0: the Q8_0 line; the weights are the nibbles minus 8 (Q4_0 files: all but the heads)
+//   Q5_0: the Q8_0 line; the weights are the 5-bit values minus 16 (Q5_0 files: all but the heads)
 // =====================================================================================================
 template <int LPR, int MT, int TS>
 __global__ void __launch_bounds__(512) k_gemv_kq(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq,
@@ -259,8 +260,8 @@ LinearPlan plan_linear(const LinearPlanIn& in) {
             // layers of the same shape take 4.7 us) with the same instruction and fetch counts but 4 x the SQ busy cycles
             // (gpurun_out/pmc_kq.txt, round 2); 4 lanes per row does not show it, so Q6_K matrices stop at 4.  Q3_KQ_Q6_LPR8=1 restores 8 for A/B.
             static const bool q6_lpr8 = [] { const char* e = std::getenv("Q3_KQ_Q6_LPR8"); return e && e[0] == '1'; }();
-            // (Q4_0 takes what Q4_K takes: no cap.  Whether 4 would serve it better has not been measured.)
-            if (lpr == 8 && !in.lpr_hint && !q6_lpr8 && in.wts != Q3_T_Q5_K && in.wts != Q3_T_Q4_K && in.wts != Q3_T_Q4_0 && in.wts != Q3_T_Q8_0) lpr = 4;
+            // (Q4_0 takes what Q4_K takes: no cap.  Whether 4 would serve it better has not been measured.  Q5_0 takes what Q4_0 takes, unmeasured as well.)
+            if (lpr == 8 && !in.lpr_hint && !q6_lpr8 && in.wts != Q3_T_Q5_K && in.wts != Q3_T_Q4_K && in.wts != Q3_T_Q4_0 && in.wts != Q3_T_Q5_0 && in.wts != Q3_T_Q8_0) lpr = 4;
             p.form = LIN_GEMV_KQ; p.lpr = lpr; p.mt = mt_of(in.ntok);
             return p;
         }
@@ -1003,6 +1004,7 @@ __global__ void Q3_GEMM_Q8_BUDGET k_gemm_q8_tile1(Q8Mat w, int row0, int nrows, 
 //         a block has one scale for both halves and no offset, so neither a half-zeroed tile nor an ones tile is multiplied
 //   Q4_0  acc = fma(f(idot), dw_b * dx, acc)   the Q8_0 line of a K-quant matrix, one MFMA per block: the B operand is the nibbles minus 8 (wslice.h,
 //         q40_sign4), dw_b the block's own f16 scale from the scale section
+//   Q5_0  the Q4_0 line, one MFMA per block: the B operand is the int8 u - 16 that q50_sign16 builds from the nibble words and the plane word
 // d, dmin, sc_b, m_b belong to the lane's weight row (C column); dx[token, block] comes, as in the Q8_0 kernel, from the f32 matrix pipe: an outer
 // product with 1.0 lays the activation scales of two blocks out in the C layout.  Built for 2 waves per SIMD (the extra accumulators do not fit 128 VGPRs).
 // Before this kernel the batched path of a Q5_K_M file swept the weights once per 8 tokens (k_gemv_kq z tiles): C3 247 audio-s/s against 620 on Q8_0.
@@ -1096,7 +1098,7 @@ k_gemm_kq_mfma(Q8Mat w, int row0, int nrows, const int8_t* __restrict__ xq, cons
                                     const float a = kq_block_scale<Q3>(d0, isum);
                                     acc[g] = kq_block_fma<Q3>(a, D[16 * i2 + g], acc[g]);
                                 }
-                            } else if (WT == Q3_T_Q4_0) { // the Q8_0 line below on the signed nibbles, each f32 step one VALU instruction
+                            } else if (WT == Q3_T_Q4_0 || WT == Q3_T_Q5_0) { // the Q8_0 line below on the signed nibbles (Q5_0: 5-bit values), each f32 step one VALU instruction
                                 const i32x16 c = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, wv, z16, 0, 0, 0);
                                 const float dwf = h2f(half_of(ws.dwv, i));
 #pragma unroll

@@ -151,6 +151,39 @@ __global__ void k_repack_q40(const uint8_t* __restrict__ raw, int n, int K, int 
             memcpy(base + h * 256 + w * 4, &word, 4);
         }
 }
+// Q5_0 block {f16 d; u8 qh[4]; u8 qs[16]} (22 bytes, 32 weights) -> Q5_K's planes (5120 B per row group and segment, kernels.h) + d in the scale
+// section where Q4_0 keeps it.  One thread per (row, block b): the nibble words exactly as k_repack_q40 writes them (weight t of half h is nibble
+// h of qs[t]), and the block's plane word, bit 8 (l & 3) + (l >> 2) = bit l of qh: the fifth bit of weight l in the file's own polarity, since
+// q50_sign16 reads it through a table and either polarity costs the same.  The meta section stays zero and is not read.
+__global__ void k_repack_q50(const uint8_t* __restrict__ raw, int n, int K, int row_off, uint8_t* __restrict__ qs, const uint32_t* __restrict__ rg_off,
+                             uint16_t* __restrict__ sc) {
+    const int nb = K >> 5, nseg = K >> 8;
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (size_t)n * nb) return;
+    const int r = (int)(id / nb), b = (int)(id % nb), s = b >> 3, j = b & 7;
+    const uint8_t* blk = raw + id * 22;
+    const int row = row_off + r, rg = row >> 5, r32 = row & 31;
+    const size_t vidx = ((size_t)rg * nseg + s) * 32 + r32;
+    uint16_t d;
+    memcpy(&d, blk, 2);
+    sc[vidx * 8 + j] = d;
+    const uint32_t qh = (uint32_t)blk[2] | ((uint32_t)blk[3] << 8) | ((uint32_t)blk[4] << 16) | ((uint32_t)blk[5] << 24);
+    const uint8_t* ql = blk + 6;
+    uint8_t* seg = qs + (size_t)rg_off[rg] * 16 + (size_t)s * 5120;
+    uint8_t* base = seg + j * 512 + r32 * 8;
+    for (int h = 0; h < 2; h++)
+        for (int w = 0; w < 2; w++) {
+            uint32_t word = 0; // byte bb = weights 8w + bb (low nibble) and 8w + 4 + bb (high nibble) of half h
+            for (int bb = 0; bb < 4; bb++) {
+                const uint32_t lo = (ql[8 * w + bb] >> (4 * h)) & 0xFu, hi = (ql[8 * w + 4 + bb] >> (4 * h)) & 0xFu;
+                word |= (lo | (hi << 4)) << (8 * bb);
+            }
+            memcpy(base + h * 256 + w * 4, &word, 4);
+        }
+    uint32_t H = 0;
+    for (int l = 0; l < 32; l++) H |= ((qh >> l) & 1u) << (8 * (l & 3) + (l >> 2));
+    memcpy(seg + 4096 + r32 * 32 + j * 4, &H, 4);
+}
 // Q3_K super-block {u8 hmask[32]; u8 qs[64]; u8 scales[12]; f16 d} -> 2-bit plane + bit plane (3072 B per row group and segment, kernels.h; values
 // kept +4, unsigned 3 bit) + d + the 16 sub-block scales as i8, already minus 32 (the Q6_K metadata: no kernel sees the 6-bit packing).
 // One thread per (row, segment, block j): block j = 4h + g is weights 128h + 32g + l, its low bits (qs[32h + l] >> 2g) & 3, its third bit
@@ -258,13 +291,14 @@ Q8Mat build_q8mat(const WLayout& L, const void* const* raw, DevBuf<uint8_t>& blo
         const size_t raw_bytes = (size_t)t.rows * q3_gguf_row_bytes(t.type, L.K);
         DevBuf<uint8_t> d(raw_bytes);
         d.upload((const uint8_t*)raw[i], raw_bytes);
-        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 || t.type == Q3_T_Q4_K || t.type == Q3_T_Q3_K || t.type == Q3_T_IQ4_XS || t.type == Q3_T_Q4_0 ? 32 : 256)); // threads: one per block (Q8_0, Q4_K, Q3_K, IQ4_XS, Q4_0) or super-block
+        const size_t nblk = (size_t)t.rows * (L.K / (t.type == Q3_T_Q8_0 || t.type == Q3_T_Q4_K || t.type == Q3_T_Q3_K || t.type == Q3_T_IQ4_XS || t.type == Q3_T_Q4_0 || t.type == Q3_T_Q5_0 ? 32 : 256)); // threads: one per block (Q8_0, Q4_K, Q3_K, IQ4_XS, Q4_0, Q5_0) or super-block
         const dim3 grid((unsigned)((nblk + 255) / 256));
         // Q8_0 tiles are laid out the same in both layouts: the kernel is based on the tensor's first row group and counts rows from there
         if (t.type == Q3_T_Q8_0) hipLaunchKernelGGL(k_repack_q8, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0 & 31, base + (size_t)L.rg_off[(size_t)(t.row0 / 32)] * 16, sc, t.row0 & ~31);
         else if (t.type == Q3_T_Q3_K) hipLaunchKernelGGL(k_repack_q3k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else if (t.type == Q3_T_IQ4_XS) hipLaunchKernelGGL(k_repack_iq4xs, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else if (t.type == Q3_T_Q4_0) hipLaunchKernelGGL(k_repack_q40, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc);
+        else if (t.type == Q3_T_Q5_0) hipLaunchKernelGGL(k_repack_q50, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc);
         else if (t.type == Q3_T_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else if (t.type == Q3_T_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
         else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(256), 0, 0, d.p, t.rows, L.K, t.row0, base, off, sc, meta);
@@ -277,7 +311,7 @@ Q8Mat kqmat_from_host(const void* const* raw, const int32_t* types, const int32_
     std::vector<WTensor> t;
     int n = 0;
     for (int i = 0; i < nw; i++) { t.push_back({types[i], n, rows[i]}); n += rows[i]; }
-    return build_q8mat(plan_wlayout(t, n, k, true, WL_TYPES_Q40), raw, storage);
+    return build_q8mat(plan_wlayout(t, n, k, true, WL_TYPES_Q50), raw, storage);
 }
 
 Q8Mat Transformer::make_mat(const Gguf& g, const std::vector<std::pair<std::string, int>>& rows, int N, int K) {
@@ -285,12 +319,12 @@ Q8Mat Transformer::make_mat(const Gguf& g, const std::vector<std::pair<std::stri
     for (auto& r : rows) {
         const GgufTensor& t = g.need(r.first);
         if (ggml_mode_) Q3_CHECK(gg_type_ok(t.type), "ggml mode: type of " + r.first + ": " + gg_type_msg(t.type)); // before anything is repacked
-        if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q3_K && t.type != Q3_T_Q4_K && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K && t.type != Q3_T_IQ4_XS && t.type != Q3_T_Q4_0)
-            throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q4_0)");
+        if (t.type != Q3_T_Q8_0 && t.type != Q3_T_Q3_K && t.type != Q3_T_Q4_K && t.type != Q3_T_Q5_K && t.type != Q3_T_Q6_K && t.type != Q3_T_IQ4_XS && t.type != Q3_T_Q4_0 && t.type != Q3_T_Q5_0)
+            throw Error("tensor " + r.first + ": ggml type " + std::to_string(t.type) + " is not supported by the HIP path (Q8_0, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q4_0, Q5_0)");
         Q3_CHECK(t.ne[0] == K, "unexpected K for " + r.first);
         tensors.push_back({t.type, r.second, (int)t.ne[1]}); raw.push_back(t.data);
     }
-    const WLayout L = plan_wlayout(tensors, N, K, false, WL_TYPES_Q40);
+    const WLayout L = plan_wlayout(tensors, N, K, false, WL_TYPES_Q50);
     blobs_.emplace_back();
     return build_q8mat(L, raw.data(), blobs_.back());
 }

@@ -8,13 +8,14 @@
 
 namespace q3 {
 
-// bytes of one 32-row group of K columns in HBM, by ggml type (2 = Q4_0, 8 = Q8_0, 11 = Q3_K, 12 = Q4_K, 13 = Q5_K, 14 = Q6_K, 23 = IQ4_XS).  Q3_K: the 2-bit plane
+// bytes of one 32-row group of K columns in HBM, by ggml type (2 = Q4_0, 6 = Q5_0, 8 = Q8_0, 11 = Q3_K, 12 = Q4_K, 13 = Q5_K, 14 = Q6_K, 23 = IQ4_XS).  Q3_K: the 2-bit plane
 // (2048 B) and the bit plane (1024 B); with the 512 B of sub-block scales in the meta section and its f16 d a (row group, segment) is 3648 B.
 // IQ4_XS: the nibble plane alone, Q4_K's footprint (the nibbles are table indices; its 8 block scales sit in the meta section as i8).
-// Q4_0: the same nibble plane (nibble = q + 8); its f16 block scales sit in the scale section where a Q8_0 row group keeps them, its meta is unused
-inline size_t q3_rowgroup_bytes(int type, int K) { return type == 2 || type == 23 ? (size_t)(K / 256) * 4096 : type == 11 ? (size_t)(K / 256) * 3072 : type == 12 ? (size_t)(K / 256) * 4096 : type == 13 ? (size_t)(K / 256) * 5120 : type == 14 ? (size_t)(K / 256) * 6144 : (size_t)(K / 32) * 1024; }
-// bytes of one GGUF row of K columns: Q4_0 blocks of 18, Q8_0 blocks of 34, Q3_K / Q4_K / Q5_K / Q6_K / IQ4_XS super-blocks of 110 / 144 / 176 / 210 / 136
-inline size_t q3_gguf_row_bytes(int type, int K) { return type == 2 ? (size_t)(K / 32) * 18 : type == 23 ? (size_t)(K / 256) * 136 : type == 11 ? (size_t)(K / 256) * 110 : type == 12 ? (size_t)(K / 256) * 144 : type == 13 ? (size_t)(K / 256) * 176 : type == 14 ? (size_t)(K / 256) * 210 : (size_t)(K / 32) * 34; }
+// Q4_0: the same nibble plane (nibble = q + 8); its f16 block scales sit in the scale section where a Q8_0 row group keeps them, its meta is unused.
+// Q5_0: Q5_K's footprint, the nibble plane (low four bits of q + 16) and the bit plane; scales and meta as for Q4_0
+inline size_t q3_rowgroup_bytes(int type, int K) { return type == 2 || type == 23 ? (size_t)(K / 256) * 4096 : type == 11 ? (size_t)(K / 256) * 3072 : type == 12 ? (size_t)(K / 256) * 4096 : type == 13 || type == 6 ? (size_t)(K / 256) * 5120 : type == 14 ? (size_t)(K / 256) * 6144 : (size_t)(K / 32) * 1024; }
+// bytes of one GGUF row of K columns: Q4_0 blocks of 18, Q5_0 blocks of 22, Q8_0 blocks of 34, Q3_K / Q4_K / Q5_K / Q6_K / IQ4_XS super-blocks of 110 / 144 / 176 / 210 / 136
+inline size_t q3_gguf_row_bytes(int type, int K) { return type == 2 ? (size_t)(K / 32) * 18 : type == 6 ? (size_t)(K / 32) * 22 : type == 23 ? (size_t)(K / 256) * 136 : type == 11 ? (size_t)(K / 256) * 110 : type == 12 ? (size_t)(K / 256) * 144 : type == 13 ? (size_t)(K / 256) * 176 : type == 14 ? (size_t)(K / 256) * 210 : (size_t)(K / 32) * 34; }
 
 struct WTensor { int type, row0, rows; }; // ggml type, first row in the fused matrix, row count
 
@@ -39,10 +40,11 @@ struct WLayout {
 
 // `types`: the ggml types the caller's kernels have a body for, bit t = type t.  The layout rule knows the size of every type listed above; which of
 // them a matrix may hold is the caller's word, so a caller written before a type existed keeps refusing it.  WL_TYPES_KQ4 adds Q4_K,
-// WL_TYPES_KQ3 adds Q3_K to that, WL_TYPES_IQ4 adds IQ4_XS to that, WL_TYPES_Q40 adds Q4_0 to that.  Q4_0 goes into no mixture: the kernels
+// WL_TYPES_KQ3 adds Q3_K to that, WL_TYPES_IQ4 adds IQ4_XS to that, WL_TYPES_Q40 adds Q4_0 to that, WL_TYPES_Q50 adds Q5_0 to that.  Q4_0 goes into no mixture: the kernels
 // have its body in the all-Q4_0 instantiations only (wslice.h), so a fused matrix with Q4_0 rows and rows of another type is refused here.
+// The same holds for Q5_0.
 constexpr uint32_t WL_TYPES = (1u << 8) | (1u << 13) | (1u << 14), WL_TYPES_KQ4 = WL_TYPES | (1u << 12), WL_TYPES_KQ3 = WL_TYPES_KQ4 | (1u << 11),
-                   WL_TYPES_IQ4 = WL_TYPES_KQ3 | (1u << 23), WL_TYPES_Q40 = WL_TYPES_IQ4 | (1u << 2);
+                   WL_TYPES_IQ4 = WL_TYPES_KQ3 | (1u << 23), WL_TYPES_Q40 = WL_TYPES_IQ4 | (1u << 2), WL_TYPES_Q50 = WL_TYPES_Q40 | (1u << 6);
 inline WLayout plan_wlayout(const std::vector<WTensor>& tensors, int N, int K, bool force_map, uint32_t types = WL_TYPES) {
     auto need = [](bool ok, const char* msg) { if (!ok) throw std::runtime_error(msg); };
     need(K > 0 && K % 256 == 0, "K must be a multiple of 256");
@@ -50,7 +52,7 @@ inline WLayout plan_wlayout(const std::vector<WTensor>& tensors, int N, int K, b
     WLayout L;
     L.N = N; L.Npad = (N + 31) & ~31; L.K = K; L.tensors = tensors; L.mapped = force_map;
     for (const WTensor& t : tensors) {
-        need(t.type >= 0 && t.type < 32 && (types >> t.type & 1u) && (WL_TYPES_Q40 >> t.type & 1u), "unsupported weight type (Q8_0, Q5_K, Q6_K; Q4_K, Q3_K, IQ4_XS, Q4_0 where the caller serves them)");
+        need(t.type >= 0 && t.type < 32 && (types >> t.type & 1u) && (WL_TYPES_Q50 >> t.type & 1u), "unsupported weight type (Q8_0, Q5_K, Q6_K; Q4_K, Q3_K, IQ4_XS, Q4_0, Q5_0 where the caller serves them)");
         L.mapped = L.mapped || t.type != 8;
     }
     const int nrg = L.Npad / 32;
@@ -78,6 +80,7 @@ inline WLayout plan_wlayout(const std::vector<WTensor>& tensors, int N, int K, b
         else { L.p2_rg0 = i; L.p2_type = last; L.p2_off = L.rg_off[(size_t)i]; }
         L.nparts++;
     }
+    for (uint8_t ty : L.rg_type) need(ty != 6 || L.nparts == 1, "a fused matrix with Q5_0 rows holds Q5_0 tensors only");
     for (uint8_t ty : L.rg_type) need(ty != 2 || L.nparts == 1, "a fused matrix with Q4_0 rows holds Q4_0 tensors only");
     return L;
 }

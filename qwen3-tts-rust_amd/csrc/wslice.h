@@ -16,6 +16,9 @@
 //   WT = Q4_0     the Q8_0 chain on 4-bit values, acc = fma(f(I_b), dw*dx, acc): the nibble plane of Q4_K with nibble = q + 8 and the f16 block
 //                 scales where a Q8_0 row group keeps them; finish() subtracts the 8 inside each byte (q40_sign4), so v_dot4 gives I_b whole and
 //                 the bits are those of the Q8_0 body on the twin rows {d, int8 q}
+//   WT = Q5_0     the Q8_0 chain on 5-bit values: Q5_K's planes (nibble words + one bit-plane word per block) and Q4_0's block scales; finish()
+//                 merges the fifth bit and sign-extends in one step (q50_sign16: the plane bits pick each byte's high nibble from a table), so
+//                 v_dot4 gives I_b = sum (u - 16) x whole and the bits are those of the Q8_0 body on the twin rows {d, int8 (u - 16)}
 #pragma once
 #include <type_traits>
 #include "kdev.h"
@@ -103,6 +106,23 @@ __device__ __forceinline__ float q40_scale(float dw, float dx) {
     return s;
 }
 
+// Q5_0: 16 weights of (block, half) -> their 16 int8 q = u - 16 in k order.  nib: the nibble words (Q4_K's order), h: the block's plane word, bit
+// 8b + J = bit 4 of weight 4J + b as the file has it (kernels.h).  q as int8 is the nibble with 0xF0 above it where bit 4 is CLEAR (u < 16: q =
+// nibble - 16) and 0x00 where it is set (q = nibble), so the high nibble of every result byte is a function of one plane bit and nothing is added
+// or subtracted.  A byte of hp = h >> 4 half holds the bits of J = 0..3 for byte position b; two of them are a 2-bit index, and v_perm_b32 looks
+// four such indices up in a 4-entry table at once: TA answers for the index's bit 0, TB for its bit 1 (an index byte must be masked: selectors
+// above 7 mean constants and sign fills).  Per 16 weights: 1 shift by 4 half, 2 and + 1 shift for the two index words, 4 v_perm_b32, 2 shifts for
+// the high nibbles and 4 v_and_or_b32 that mask the nibble and merge the high one: 14 instructions, 3.5 per four weights (read in
+// k_gemv_kq<4, 1, 6>), what q40_sign4 costs for 4 bits, paid once per launch whatever the token count.  The arithmetic routes, kq_unpack16<false>
+// + q40_sign4's trick with 16 and an inverted bit spread as (s << 8) - (s << 4), cost 6.6 and 4.6, and the compiler turns the second into a
+// quarter-rate v_mul_lo_u32 by 240 per dword (DESIGN.md, Q5_0 weights).
+__device__ __forceinline__ uint4 q50_sign16(uint2 nib, uint32_t h, int half) {
+    const uint32_t m = 0x0F0F0F0Fu, two = 0x03030303u, TA = 0x00F000F0u, TB = 0x0000F0F0u; // index 0..3 -> F0 00 F0 00 (bit 0 clear) | F0 F0 00 00 (bit 1 clear)
+    const uint32_t hp = h >> (4 * half), i01 = hp & two, i23 = (hp >> 2) & two;
+    return make_uint4((nib.x & m) | __builtin_amdgcn_perm(0u, TA, i01), ((nib.x >> 4) & m) | __builtin_amdgcn_perm(0u, TB, i01),
+                      (nib.y & m) | __builtin_amdgcn_perm(0u, TA, i23), ((nib.y >> 4) & m) | __builtin_amdgcn_perm(0u, TB, i23));
+}
+
 // type of row group rg (wave-uniform) from the tensor map in the kernel arguments
 __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
     const int rgs = __builtin_amdgcn_readfirstlane(rg);
@@ -117,6 +137,7 @@ __device__ __forceinline__ int wslice_type(const Q8Mat& w, int rg) {
 // For the same reason IQ4_XS = a matrix that is all IQ4_XS has its one body, and -3 = mixed with an IQ4_XS part (fused QKV of an IQ4_XS file: q, k
 // IQ4_XS and v Q5_K) has the IQ4_XS and Q5_K bodies and no other: build_q8mat lets IQ4_XS into no other mixture.  Q4_0 = a matrix that is all Q4_0
 // has its one body; a Q4_0 file's q, k, v are all Q4_0, so there is no mixed value with a Q4_0 part and plan_wlayout refuses such a matrix.
+// Q5_0 likewise: one body in the all-Q5_0 instantiations, no mixed value.
 template <int TS, typename F>
 __device__ __forceinline__ void wslice_dispatch(const Q8Mat& w, int rg, F&& body) {
     if (TS >= 0) { body(wt_tag<(TS >= 0 ? TS : 0)>{}); return; }
@@ -148,7 +169,7 @@ inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matric
     case 0: { constexpr int TS = 0; __VA_ARGS__; break; } case Q3_T_Q8_0: { constexpr int TS = Q3_T_Q8_0; __VA_ARGS__; break; } \
     case Q3_T_Q3_K: { constexpr int TS = Q3_T_Q3_K; __VA_ARGS__; break; } case Q3_T_Q4_K: { constexpr int TS = Q3_T_Q4_K; __VA_ARGS__; break; } \
     case Q3_T_Q5_K: { constexpr int TS = Q3_T_Q5_K; __VA_ARGS__; break; } case Q3_T_Q6_K: { constexpr int TS = Q3_T_Q6_K; __VA_ARGS__; break; } \
-    case Q3_T_Q4_0: { constexpr int TS = Q3_T_Q4_0; __VA_ARGS__; break; } \
+    case Q3_T_Q4_0: { constexpr int TS = Q3_T_Q4_0; __VA_ARGS__; break; } case Q3_T_Q5_0: { constexpr int TS = Q3_T_Q5_0; __VA_ARGS__; break; } \
     case Q3_T_IQ4_XS: { constexpr int TS = Q3_T_IQ4_XS; __VA_ARGS__; break; } case -3: { constexpr int TS = -3; __VA_ARGS__; break; } \
     case -2: { constexpr int TS = -2; __VA_ARGS__; break; } default: { constexpr int TS = -1; __VA_ARGS__; break; } } } while (0)
 
@@ -157,10 +178,10 @@ inline int wslice_launch_ts(const Q8Mat& w) { // wslice_ts with the mixed matric
 template <int LPR, int WT>
 struct WSlice {
     static constexpr int R = 64 / LPR, BPL = LPR / 2, NLD = 8 / BPL;
-    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, IQ = WT == Q3_T_IQ4_XS, Q40 = WT == Q3_T_Q4_0, KQ = Q4 || Q3 || IQ || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
+    static constexpr bool Q4 = WT == Q3_T_Q4_K, Q3 = WT == Q3_T_Q3_K, IQ = WT == Q3_T_IQ4_XS, Q40 = WT == Q3_T_Q4_0, Q50 = WT == Q3_T_Q5_0, KQ = Q4 || Q3 || IQ || WT == Q3_T_Q5_K || WT == Q3_T_Q6_K;
     static constexpr int SUBOFF = Q3 || IQ ? 0 : 32; // Q6_K / Q3_K / IQ4_XS chain: what the unpacked operand is above q (Q3_K unpacks to q itself, IQ4_XS to its level)
     uint4 wv[NLD];
-    uint4 dwv;          // Q8_0, Q4_0: the 8 block scales; K-quants: d, dmin in halfs 0, 1
+    uint4 dwv;          // Q8_0, Q4_0, Q5_0: the 8 block scales; K-quants: d, dmin in halfs 0, 1
     uint4 mv;           // K-quants: 16 metadata bytes of (row, segment)
 
     // issue the loads; the R <= 32 rows of a wave sit in one 32-row group, so the group's base address is a scalar
@@ -178,13 +199,23 @@ struct WSlice {
         const bool in1 = rgs >= w.p1_rg0, in2 = rgs >= w.p2_rg0;
         const uint32_t poff = in2 ? w.p2_off : in1 ? w.p1_off : w.p0_off;
         const int prg0 = in2 ? w.p2_rg0 : in1 ? w.p1_rg0 : 0;
-        constexpr int seg_bytes = Q3 ? 3072 : Q4 || IQ || Q40 ? 4096 : WT == Q3_T_Q5_K ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
+        constexpr int seg_bytes = Q3 ? 3072 : Q4 || IQ || Q40 ? 4096 : WT == Q3_T_Q5_K || Q50 ? 5120 : WT == Q3_T_Q6_K ? 6144 : 8192;
         const uint8_t* sbase = w.qs + (size_t)poff * 16 + ((size_t)(rgs - prg0) * nseg + seg) * seg_bytes;
         if (Q40) { // Q4_K's nibble words; the block scales are in dwv already and no metadata is fetched
 #pragma unroll
             for (int i = 0; i < NLD; i++) {
                 const uint2 nib = *reinterpret_cast<const uint2*>(sbase + (i * BPL + bil) * 512 + half * 256 + r32 * 8);
                 wv[i].x = nib.x; wv[i].y = nib.y;
+            }
+            return;
+        }
+        if (Q50) { // Q5_K's words: x, y = nibbles, z = the block's plane word; the block scales are in dwv already and no metadata is fetched
+            const uint8_t* hrow = sbase + 4096 + r32 * 32;
+#pragma unroll
+            for (int i = 0; i < NLD; i++) {
+                const int b = i * BPL + bil;
+                const uint2 nib = *reinterpret_cast<const uint2*>(sbase + b * 512 + half * 256 + r32 * 8);
+                wv[i].x = nib.x; wv[i].y = nib.y; wv[i].z = *reinterpret_cast<const uint32_t*>(hrow + b * 4);
             }
             return;
         }
@@ -224,11 +255,16 @@ struct WSlice {
         }
     }
 
-    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3; IQ4_XS: signed, the level of the index; Q4_0: signed, q in -8..7); call once, after the prologue
+    // unpack the K-quant words parked by load() (unsigned values: Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 = q + 32; Q3_K: signed, q in -4..3; IQ4_XS: signed, the level of the index; Q4_0: signed, q in -8..7; Q5_0: signed, q in -16..15); call once, after the prologue
     __device__ __forceinline__ void finish(int half) {
         if (Q40) { // Q4_K's four dwords in k order, each nibble minus 8
 #pragma unroll
             for (int i = 0; i < NLD; i++) wv[i] = make_uint4(q40_sign4<0>(wv[i].x), q40_sign4<4>(wv[i].x), q40_sign4<0>(wv[i].y), q40_sign4<4>(wv[i].y));
+            return;
+        }
+        if (Q50) { // nibble and plane bit to int8 u - 16 in one step
+#pragma unroll
+            for (int i = 0; i < NLD; i++) wv[i] = q50_sign16(make_uint2(wv[i].x, wv[i].y), wv[i].z, half);
             return;
         }
         if (!KQ) return;
@@ -278,7 +314,7 @@ struct WSlice {
                 for (int j = 0; j < BPL; j++) {
                     const int isj = (BPL == 1) ? isum : __shfl(isum, r + 2 * j * R);
                     const int b = i * BPL + j;
-                    if (Q40) { acc = kq_block_fma<true>((float)isj, q40_scale(h2f(half_of(dwv, b)), h2f(half_of(dxv, b))), acc); continue; } // the two statements below, one instruction each
+                    if (Q40 || Q50) { acc = kq_block_fma<true>((float)isj, q40_scale(h2f(half_of(dwv, b)), h2f(half_of(dxv, b))), acc); continue; } // the two statements below, one instruction each
                     const float sc = h2f(half_of(dwv, b)) * h2f(half_of(dxv, b));
                     acc = q3_fmaf((float)isj, sc, acc);
                 }

@@ -4,7 +4,7 @@
  * No real Qwen3-TTS weights exist offline (the reference downloads them at run time,
  * /root/reference/src/download.rs:66-87), so benchmarks and parity tests run on seeded random weights of
  * the same architecture, written in the same container format the reference loads:
- *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_q3_k_m|gguf_iq4_xs|gguf_q4_0|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
+ *   <out>/<gguf|gguf_q8_0|gguf_q5_k_m|gguf_q4_k_m|gguf_q3_k_m|gguf_iq4_xs|gguf_q4_0|gguf_q5_0|gguf_bf16>/{qwen3_assets,qwen3_tts_talker,qwen3_tts_predictor}.gguf
  *   <out>/onnx/q3tts_codec.gguf        (stand-in for qwen3_tts_decoder.onnx)
  * (directory names: /root/reference/src/tts/engine.rs:91-95,123-124).
  *
@@ -97,6 +97,7 @@ static void enc_q45_k(const float* x, int64_t k, uint8_t* out, int levels, int b
 static int g_q4k_as_q5k = 0; /* --q4k-as-q5k: Q4_K tensors are stored as Q5_K blocks with an all-zero qh */
 static int g_q3k_as_q6k = 0; /* --q3k-as-q6k: Q3_K tensors are stored as Q6_K blocks with the same d, scales - 32 and quants */
 static int g_q40_as_q80 = 0; /* --q4_0-as-q8_0: Q4_0 tensors are stored as Q8_0 blocks {d, int8 (nibble - 8)[32]}, the same weights */
+static int g_q50_as_q80 = 0; /* --q5_0-as-q8_0: Q5_0 tensors are stored as Q8_0 blocks {d, int8 (u - 16)[32]}, the same weights */
 static void enc_q5_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, 31, 176); }
 static void enc_q4_k(const float* x, int64_t k, uint8_t* out) { enc_q45_k(x, k, out, 15, g_q4k_as_q5k ? 176 : 144); }
 /* one Q6_K super-block from its fields: q[256] unsigned 6-bit values (q + 32) */
@@ -210,6 +211,27 @@ static void enc_q4_0(const float* x, int64_t k, uint8_t* out) {
         else for (int j = 0; j < 16; j++) blk[2 + j] = (uint8_t)(q[j] | (q[j + 16] << 4));
     }
 }
+/* Q5_0 {f16 d, u8 qh[4], u8 qs[16]} (22 bytes, spec S3 [EXT]) with ggml's reference rounding: max = the value of largest magnitude, sign kept,
+ * d = max / -16, u = min(31, (int)(x / d + 16.5)); byte j holds the low four bits of weight j in its low and of weight j + 16 in its high nibble,
+ * bit l of the little-endian qh is bit 4 of weight l.  The twin is the Q8_0 block of u - 16. */
+static void enc_q5_0(const float* x, int64_t k, uint8_t* out) {
+    for (int64_t b = 0; b < k / 32; b++) {
+        const float* xb = x + 32 * b;
+        float amax = 0, max = 0;
+        for (int i = 0; i < 32; i++) { float a = fabsf(xb[i]); if (a > amax) { amax = a; max = xb[i]; } }
+        const float d = max / -16.0f, id = d ? 1.0f / d : 0.0f;
+        uint16_t dh = q3_f32_to_f16(d);
+        int q[32];
+        for (int i = 0; i < 32; i++) { int v = (int)(xb[i] * id + 16.5f); q[i] = v > 31 ? 31 : v; }
+        uint8_t* blk = out + (g_q50_as_q80 ? 34 : 22) * b;
+        memcpy(blk, &dh, 2);
+        if (g_q50_as_q80) { for (int i = 0; i < 32; i++) blk[2 + i] = (uint8_t)(int8_t)(q[i] - 16); continue; }
+        uint32_t qh = 0;
+        for (int i = 0; i < 32; i++) qh |= (uint32_t)(q[i] >> 4) << i;
+        for (int i = 0; i < 4; i++) blk[2 + i] = (uint8_t)(qh >> (8 * i));
+        for (int j = 0; j < 16; j++) blk[6 + j] = (uint8_t)((q[j] & 15) | ((q[j + 16] & 15) << 4));
+    }
+}
 static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
     for (int64_t s = 0; s < k / 256; s++) {
         const float* xs = x + 256 * s;
@@ -238,12 +260,13 @@ static void enc_q6_k(const float* x, int64_t k, uint8_t* out) {
         pack_q6_k(blk, dh, sc, q);
     }
 }
-static int stored_type(int type) { return type == Q3_T_Q4_0 && g_q40_as_q80 ? Q3_T_Q8_0 : type == Q3_T_Q3_K && g_q3k_as_q6k ? Q3_T_Q6_K : type == Q3_T_Q4_K && g_q4k_as_q5k ? Q3_T_Q5_K : type; }
+static int stored_type(int type) { return (type == Q3_T_Q4_0 && g_q40_as_q80) || (type == Q3_T_Q5_0 && g_q50_as_q80) ? Q3_T_Q8_0 : type == Q3_T_Q3_K && g_q3k_as_q6k ? Q3_T_Q6_K : type == Q3_T_Q4_K && g_q4k_as_q5k ? Q3_T_Q5_K : type; }
 static size_t row_bytes(int type, int64_t k) {
     switch (type) {
         case Q3_T_F32: return (size_t)k * 4;
         case Q3_T_F16: case Q3_T_BF16: return (size_t)k * 2;
         case Q3_T_Q4_0: return (size_t)(k / 32) * 18;
+        case Q3_T_Q5_0: return (size_t)(k / 32) * 22;
         case Q3_T_Q8_0: return (size_t)(k / 32) * 34;
         case Q3_T_Q3_K: return (size_t)(k / 256) * 110;
         case Q3_T_Q4_K: return (size_t)(k / 256) * 144;
@@ -265,6 +288,7 @@ static void enc_row(int type, const float* x, int64_t k, uint8_t* out) {
         case Q3_T_Q6_K: enc_q6_k(x, k, out); break;
         case Q3_T_IQ4_XS: enc_iq4_xs(x, k, out); break;
         case Q3_T_Q4_0: enc_q4_0(x, k, out); break;
+        case Q3_T_Q5_0: enc_q5_0(x, k, out); break;
     }
 }
 
@@ -397,6 +421,7 @@ static int wtype(const char* quant, const char* kind, int layer, int n_layer) {
         return Q3_T_IQ4_XS;
     }
     if (!strcmp(quant, "q4_0")) return !strcmp(kind, "output") ? Q3_T_Q6_K : Q3_T_Q4_0; /* every layer matrix Q4_0, the heads Q6_K as in the K-quant mixes */
+    if (!strcmp(quant, "q5_0")) return !strcmp(kind, "output") ? Q3_T_Q6_K : Q3_T_Q5_0; /* as q4_0 */
     fprintf(stderr, "unknown quant %s\n", quant);
     exit(2);
 }
@@ -548,12 +573,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--q4k-as-q5k")) g_q4k_as_q5k = 1;
         else if (!strcmp(argv[i], "--q3k-as-q6k")) g_q3k_as_q6k = 1;
         else if (!strcmp(argv[i], "--q4_0-as-q8_0")) g_q40_as_q80 = 1;
-        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|q3_k_m|iq4_xs|q4_0|bf16|f16|f32] [--q4k-as-q5k] [--q3k-as-q6k] [--q4_0-as-q8_0] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
+        else if (!strcmp(argv[i], "--q5_0-as-q8_0")) g_q50_as_q80 = 1;
+        else { fprintf(stderr, "usage: q3synth --out DIR [--preset full|tiny] [--quant q8_0|q5_k_m|q4_k_m|q3_k_m|iq4_xs|q4_0|q5_0|bf16|f16|f32] [--q4k-as-q5k] [--q3k-as-q6k] [--q4_0-as-q8_0] [--q5_0-as-q8_0] [--seed N] [--text-rows N] [--what mask]\n"); return 2; }
     }
     if (!out) { fprintf(stderr, "--out required\n"); return 2; }
     if (g_q4k_as_q5k && strcmp(quant, "q4_k_m") && strcmp(quant, "q3_k_m")) { fprintf(stderr, "--q4k-as-q5k goes with --quant q4_k_m or q3_k_m\n"); return 2; }
     if (g_q3k_as_q6k && strcmp(quant, "q3_k_m")) { fprintf(stderr, "--q3k-as-q6k goes with --quant q3_k_m\n"); return 2; }
     if (g_q40_as_q80 && strcmp(quant, "q4_0")) { fprintf(stderr, "--q4_0-as-q8_0 goes with --quant q4_0\n"); return 2; }
+    if (g_q50_as_q80 && strcmp(quant, "q5_0")) { fprintf(stderr, "--q5_0-as-q8_0 goes with --quant q5_0\n"); return 2; }
 #ifdef _OPENMP
     if (!getenv("OMP_NUM_THREADS")) { int n = omp_get_num_procs(); omp_set_num_threads(n > 8 ? 8 : n); } /* cgroup CPU shares are smaller than the core count */
 #endif
@@ -567,7 +594,7 @@ int main(int argc, char** argv) {
         pred = (tfcfg){ 256, 2, 2, 1, 512, 30720, 0 };
         codec = (ccfg){ 64, 32, 2, 2, 32, 128, 8, 256, 2, 4, { 2, 2 }, { 8, 5, 4, 3 } };
     } else { fprintf(stderr, "unknown preset\n"); return 2; }
-    const char* qdir = !strcmp(quant, "q8_0") || g_q40_as_q80 ? "gguf_q8_0" : !strcmp(quant, "q4_0") ? "gguf_q4_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") || g_q3k_as_q6k ? "gguf_q4_k_m" : !strcmp(quant, "q3_k_m") ? "gguf_q3_k_m" : !strcmp(quant, "iq4_xs") ? "gguf_iq4_xs" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
+    const char* qdir = !strcmp(quant, "q8_0") || g_q40_as_q80 || g_q50_as_q80 ? "gguf_q8_0" : !strcmp(quant, "q4_0") ? "gguf_q4_0" : !strcmp(quant, "q5_0") ? "gguf_q5_0" : !strcmp(quant, "q5_k_m") || g_q4k_as_q5k ? "gguf_q5_k_m" : !strcmp(quant, "q4_k_m") || g_q3k_as_q6k ? "gguf_q4_k_m" : !strcmp(quant, "q3_k_m") ? "gguf_q3_k_m" : !strcmp(quant, "iq4_xs") ? "gguf_iq4_xs" : !strcmp(quant, "f32") ? "gguf" : !strcmp(quant, "bf16") ? "gguf_bf16" : "gguf_f16";
     char p[1024];
     mkdir(out, 0755);
     snprintf(p, sizeof(p), "%s/%s", out, qdir); mkdir(p, 0755);
